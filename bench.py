@@ -37,6 +37,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -47,6 +49,38 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X fp64 matrix peak (spec); the measured sustained rate is in profiles/
 USER_LIB = os.path.join(ROOT, "examples", "librandom_convex_user.so")
 WEIGHTING_LIB = os.path.join(ROOT, "examples", "libweighting_user.so")  # config 4 as a user's ParOptSparseProblem
+# --dump-outputs: design-sized vectors are written as a fixed, seeded sample of their global entries (the same indices
+# in every run with the same arguments), sparse-constraint-sized ones likewise; 4 x 8 MB + 6 x 4 MB <= 64 MB in all
+DUMP_SEED = 20240917
+DUMP_SAMPLE_DESIGN = 1 << 20
+DUMP_SAMPLE_SPARSE = 1 << 19
+
+
+def sample_vectors(vecs, seed, cap, dist=None):
+    """{name: rank-local shard (PVec)} -> {name: float64 array} of the GLOBAL vectors at `cap` seeded indices (all of
+    them when the vector is shorter), plus "index" with those global indices; the shards of the ranks are
+    concatenated in rank order.  Every rank calls it; the arrays are complete on rank 0."""
+    names = sorted(vecs)
+    nloc = len(vecs[names[0]])
+    sizes = [nloc]
+    if dist is not None:
+        sizes = [None] * dist.get_world_size()
+        dist.all_gather_object(sizes, nloc)
+    rank = dist.get_rank() if dist is not None else 0
+    start, total = sum(sizes[:rank]), sum(sizes)
+    if total <= cap:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(total, cap, replace=False))
+    mine = idx[(idx >= start) & (idx < start + nloc)]
+    # the host mirror of each shard, synchronised from HBM (one download per vector, the timed runs are over)
+    part = {nm: np.array(vecs[nm]._peek()[mine - start], dtype=np.float64) for nm in names}
+    if dist is not None:
+        parts = [None] * len(sizes)
+        dist.all_gather_object(parts, part)
+        part = {nm: np.concatenate([p[nm] for p in parts]) for nm in names}
+    part["index"] = idx.astype(np.float64)  # exact: indices < 2^53
+    return part
 
 
 # ------------------------------------------------------------------------------------------------
@@ -333,6 +367,10 @@ def parse_args(argv=None):
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N>1: continue on a torch.distributed callback if the native RCCL communicator fails "
                          "(default: exit non-zero)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline variant's optimize() returned in its last "
+                         "repeat as DIR/<name>.npy (float64): x, zl, zu (and the sparse multipliers and slacks) at a "
+                         "fixed seeded sample of their entries, the dense multipliers and slacks, fobj and the counters")
     return ap.parse_args(argv)
 
 
@@ -500,9 +538,11 @@ def main():
     opts = {"qn_type": a.qn, "qn_subspace_size": a.qn_size, "abs_res_tol": 1e-30,
             "start_affine_multiplier_min": 0.01, "max_major_iters": W + K, "write_output_frequency": 0}
 
-    def measure(prob, own_bytes=None):
+    outputs = {}  # --dump-outputs: what the headline variant's last optimize() returned
+
+    def measure(prob, own_bytes=None, keep_outputs=False):
         """R optimize() runs on `prob`; returns (median seconds of the K timed iterations, sorted times, details of
-        the median run, all runs)."""
+        the median run, all runs).  keep_outputs: the result of the last run goes to `outputs`."""
         ip = pa.InteriorPoint(prob, opts)
         ip.setCallbackTiming(True)  # user_eval_ms_per_iter below (event records around the problem's callbacks)
         stamp = {}
@@ -550,10 +590,31 @@ def main():
         times = sorted(r[0] for r in runs)
         med = statistics.median(times)
         det = min(runs, key=lambda r: abs(r[0] - med))[1]
+        if keep_outputs:
+            outputs.update(solver_outputs(ip))
         ip.setIterationCallback(lambda k: None)  # break the cycle ip -> callback -> ip: the solver's vectors
         del ip                                   # (tens of GB at the full size) are freed before the next variant
         gc.collect()
         return med, times, det, runs
+
+    def solver_outputs(ip):
+        """The arrays a caller of optimize() receives: getOptimizedPoint / Slacks / Sparse, getObjective and the
+        counters (design- and sparse-sized vectors as a seeded sample, DUMP_* above)."""
+        x, z, zl, zu = ip.getOptimizedPoint()
+        design = {nm: v for nm, v in (("x", x), ("zl", zl), ("zu", zu)) if v is not None}
+        out = {"x_" + k if k == "index" else k: v
+               for k, v in sample_vectors(design, DUMP_SEED, DUMP_SAMPLE_DESIGN, dist).items()}
+        out["z"] = np.asarray(z, dtype=np.float64)
+        for nm, v in zip(("s", "t", "zs", "zt"), ip.getOptimizedSlacks()):
+            out[nm] = np.asarray(v, dtype=np.float64)
+        wv = ip.getOptimizedSparse()
+        if wv is not None:
+            sparse = dict(zip(("zw", "sw", "tw", "zsw", "ztw"), wv))
+            out.update({"w_" + k if k == "index" else k: v
+                        for k, v in sample_vectors(sparse, DUMP_SEED + 1, DUMP_SAMPLE_SPARSE, dist).items()})
+        out["fobj"] = np.array(ip.getObjective(), dtype=np.float64)  # (fobj, penalty rho)
+        out["counters"] = np.array(ip.getIterationCounters(), dtype=np.float64)  # (niter, neval, ngeval)
+        return out
 
     def summary(v):
         """Per-variant numbers of the line: rate, host syncs, launches and the iteration-level roofline."""
@@ -571,6 +632,7 @@ def main():
                     (lib_bytes / (lib_ms * 1e-3) * 1e-9 / HBM_PEAK_GBPS) if lib_ms > 0 else None}
 
     # ---- the built-in problem: reference contract first (headline), the API extension beside it ----
+    dump = a.dump_outputs is not None
     variants = {}
     prob = pa.SeparableProblem(ctx, a.problem, a.n, a.ncon, 0)
     nl, offset = prob.nvars, prob.offset
@@ -578,7 +640,7 @@ def main():
         prob.setWeighting(a.nwcon, a.nw, 0, 0)
     if a.boundary != "facade":
         prob.setLinearConstraints(False)
-        variants["jacobian_rewritten_every_gradient_call"] = measure(prob)
+        variants["jacobian_rewritten_every_gradient_call"] = measure(prob, keep_outputs=dump)
         if not a.skip_extension_variant:
             prob.setLinearConstraints(True)
             variants["linear_constraints_declared__API_EXTENSION"] = measure(prob)
@@ -602,7 +664,7 @@ def main():
             # interface (setSparseJacobianData pattern + the entries the gradient callback writes); the library
             # recognises the grouped pattern and runs its fused group kernels
             up = pa.UserLibraryProblem(ctx, user_lib, a.n, a.ncon, prefix="wt", nwcon=a.nwcon, nw=a.nw)
-            fac = {"reference_semantics": measure(up, lambda: up.ownKernelBytes(True))}
+            fac = {"reference_semantics": measure(up, lambda: up.ownKernelBytes(True), dump and a.boundary == "facade")}
             up.close()
             boundary = {"what": "config 4 as a USER ParOptSparseProblem subclass on include/ParOptAMD.hpp, compiled "
                                 "outside libparopt_amd.so with its own HIP kernels (examples/weighting_amd.cpp): the "
@@ -616,7 +678,7 @@ def main():
                 variants = {"facade_reference_semantics": fac["reference_semantics"]}
         else:
             up = pa.UserLibraryProblem(ctx, USER_LIB, a.n, a.ncon)
-            fac = {"reference_semantics": measure(up, lambda: up.ownKernelBytes(True))}
+            fac = {"reference_semantics": measure(up, lambda: up.ownKernelBytes(True), dump and a.boundary == "facade")}
             up.setDeferredReductions(True)
             fac["deferred_reductions__API_EXTENSION"] = measure(up, lambda: up.ownKernelBytes(True))
             up.close()
@@ -631,6 +693,13 @@ def main():
                             "facade_deferred_reductions__API_EXTENSION": fac["deferred_reductions__API_EXTENSION"]}
     head = next(iter(variants))
     elapsed, times, det, runs = variants[head]
+    if dump and rank == 0:
+        assert outputs, "no outputs kept for the headline variant %s" % head
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for nm, arr in sorted(outputs.items()):
+            np.save(os.path.join(a.dump_outputs, nm + ".npy"), arr)
+        log("outputs of %s: %d arrays, %.1f MB -> %s" % (
+            head, len(outputs), sum(v.nbytes for v in outputs.values()) / 1e6, a.dump_outputs))
     all_runs = [r for v in variants.values() for r in v[3]]
 
     # ---- roofline of the headline kernel, measured live with HIP events on the context stream ----

@@ -167,3 +167,63 @@ def test_host_cpu_budget_respects_affinity_cpu():
         assert info["usable"] <= max(1, int(info["cgroup_quota_cpus"]))
     # traffic model of the reference's own sequence: 5200 doubles per variable at c = 32, k = 10
     assert abs(bench.reference_traffic_bytes(1, 32, 10) / 8 - (332 + 48 * 32 + 32 * 32 + 450 + 1600 + 200)) < 1e-9
+
+
+def test_dump_outputs_sample_is_fixed_cpu():
+    """--dump-outputs samples design-sized vectors at the same seeded, sorted global indices in every run, within the
+    cap; a shorter vector is written whole."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    class Shard:  # the two members of PVec the sampler uses
+        def __init__(self, a):
+            self.a = a
+
+        def __len__(self):
+            return len(self.a)
+
+        def _peek(self):
+            return self.a
+
+    n = 3 * bench.DUMP_SAMPLE_DESIGN + 7
+    x = np.arange(n, dtype=np.float64) * 0.5
+    one = bench.sample_vectors({"x": Shard(x), "y": Shard(-x)}, bench.DUMP_SEED, bench.DUMP_SAMPLE_DESIGN)
+    two = bench.sample_vectors({"x": Shard(x.copy()), "y": Shard(-x)}, bench.DUMP_SEED, bench.DUMP_SAMPLE_DESIGN)
+    idx = one["index"]
+    assert len(idx) == bench.DUMP_SAMPLE_DESIGN and np.all(np.diff(idx) > 0) and idx[-1] < n
+    np.testing.assert_array_equal(idx, two["index"])
+    np.testing.assert_array_equal(one["x"], 0.5 * idx)
+    np.testing.assert_array_equal(one["y"], -0.5 * idx)
+    small = bench.sample_vectors({"x": Shard(x[:100])}, bench.DUMP_SEED, bench.DUMP_SAMPLE_DESIGN)
+    np.testing.assert_array_equal(small["x"], x[:100])
+    # the largest dump (x, zl, zu + sparse multipliers and slacks, their index arrays) stays within 64 MB
+    assert 8 * (4 * bench.DUMP_SAMPLE_DESIGN + 6 * bench.DUMP_SAMPLE_SPARSE) <= 64 * 2 ** 20
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the headline variant's result after the timed steps as DIR/<name>.npy, float64, at most
+    64 MB, the same arrays from two runs with the same arguments; the solver ran exactly warmup + steps iterations."""
+    import numpy as np
+
+    args = ["--nglobal", "3000000", "--steps", "3", "--warmup", "3", "--repeats", "1", "--no-cpu-baseline",
+            "--qn-size", "3", "--boundary", "builtin", "--skip-extension-variant"]
+    dumps = []
+    for tag in ("a", "b"):
+        out, lines = _run(args + ["--dump-outputs", str(tmp_path / tag)], {}, 900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        files = sorted(os.listdir(str(tmp_path / tag)))
+        assert {"x.npy", "x_index.npy", "zl.npy", "zu.npy", "z.npy", "fobj.npy", "counters.npy"} <= set(files), files
+        d = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+        assert sum(os.path.getsize(str(tmp_path / tag / f)) for f in files) <= 64 * 2 ** 20
+        assert int(d["counters"][0]) == r["warmup"] + r["steps"]
+        assert len(d["x"]) == len(d["x_index"]) < 3000000 and len(d["z"]) == 32
+        assert np.all(np.isfinite(d["x"]))
+        dumps.append(d)
+    for k, v in dumps[0].items():
+        np.testing.assert_array_equal(v, dumps[1][k], err_msg=k)
