@@ -1046,6 +1046,7 @@ int po_ip_get_debug_ints(po_ip ip, const int **gpiv, int *ngpiv, int *check_flag
 }
 int po_ip_get_bounds(po_ip ip, po_vec *lb, po_vec *ub) {
   PO_CHECK_PTR(ip);
+  ip->ip->clearUniformBounds();
   if (lb) *lb = static_cast<po_vec>(ip->ip->lowerBounds());
   if (ub) *ub = static_cast<po_vec>(ip->ip->upperBounds());
   return PO_OK;

@@ -26,7 +26,7 @@ void set_error(const char *fmt, ...) {
 }
 const char *last_error() { return g_err; }
 
-static int g_dbg_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static int g_dbg_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 double host_now() {
   struct timespec t;
   clock_gettime(CLOCK_MONOTONIC, &t);
@@ -693,7 +693,7 @@ int batch_flush(Ctx *c, const double *keep_partials, size_t keep_len) {
   return PO_OK;
 }
 
-int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *host_out, bool now) {
+int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *host_out, bool now, double *local_out) {
   const int nslots = nsum + nmin + nmax;
   if (nslots > kMaxRed) {
     set_error("reduction of %d slots exceeds kMaxRed=%d", nslots, kMaxRed);
@@ -715,6 +715,9 @@ int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *hos
     }
   }
   if (c->batch_depth > 0 || !c->batch_pend.empty()) {
+    if (local_out) {
+      for (int s = 0; s < nslots; s++) local_out[s] = NAN;
+    }
     c->batch_pend.push_back(Ctx::PendingRed{c->batch_cursor, nsum, nmin, nmax, host_out, part, nblocks});
     c->batch_cursor += nslots;
     if (now || c->batch_depth == 0) return batch_flush(c);
@@ -725,6 +728,13 @@ int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *hos
   int nparts = 1;
   PO_TRY(exchange_reduced(c, nslots, nmin == 0 && nmax == 0, &parts, &nparts));
   combine_segment(parts, nparts, nslots, 0, nsum, nmin, nmax, host_out);
+  if (local_out) {
+    // A mixed payload is gathered in rank order, and a single part is this rank's own.  A pure sum over several
+    // ranks may have been all-reduced in place, which leaves no per-rank values.
+    const double *mine = parts + (nparts > 1 ? (size_t)c->rank * nslots : 0);
+    const bool have = nparts > 1 || c->size == 1 || nmin + nmax > 0;
+    for (int s = 0; s < nslots; s++) local_out[s] = have ? mine[s] : NAN;
+  }
   return PO_OK;
 }
 

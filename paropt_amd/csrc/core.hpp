@@ -157,7 +157,10 @@ struct VirtCols {
 // Reduction finish: combine first-stage partials ([slot][nblocks] in ctx->d_partials) into
 // host_out[nsum+nmin+nmax]; slots are ordered sums, then mins, then maxs.  Collective.
 // Inside a BatchScope the call returns before host_out is valid unless `now` is set (which flushes the batch).
-int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *host_out, bool now = false);
+// local_out != nullptr: also this rank's own values of the nsum + nmin + nmax slots (NaN when the reduction was queued
+// behind a batch)
+int reduce_finish(Ctx *c, int nblocks, int nsum, int nmin, int nmax, double *host_out, bool now = false,
+                  double *local_out = nullptr);
 bool red_direct(const Ctx *c);  // the final stages write straight into the pinned host buffer (no RCCL collective)
 // collective + host sync for everything queued; runs the after_reduce() work in order (keep_partials: an overflow
 // region that is still waiting for its final stage and must survive the flush)
@@ -232,7 +235,8 @@ struct BatchScope {
 // po_debug_set_switch wins, else the environment variable, else the default.  Not part of the interface.
 enum DbgSwitch { SW_WGRAM_RS = 0, SW_LINCOMB_2D = 1, SW_REDO_DT = 2, SW_LEAN_STEP = 3, SW_WGRAM_PRIO = 4,
                  SW_WGRAM_ABLATE = 5, SW_FUSED_MERIT = 6, SW_REDO_DT1 = 7, SW_BPC3 = 8, SW_BPC4 = 9, SW_LINCOMB_BPC = 10,
-                 SW_PERTURB_W = 11, SW_GS_PRODUCER = 12, SW_S2D_TWO = 13, SW_MPC_FUSE = 14, SW_MPC_POLY = 15, SW_SPEC_DT = 16, SW_COUNT = 17 };  // one entry per use: an A/B run changes one thing
+                 SW_PERTURB_W = 11, SW_GS_PRODUCER = 12, SW_S2D_TWO = 13, SW_MPC_FUSE = 14, SW_MPC_POLY = 15, SW_SPEC_DT = 16,
+                 SW_UNIFORM_BOUNDS = 17, SW_COUNT = 18 };  // one entry per use: an A/B run changes one thing
 int dbg_switch(int id, const char *env, int dflt);
 double host_now();  // seconds, monotonic
 // around a kernel launch when Ctx::host_trace is on (see Ctx): begin closes the gap behind the last synchronisation
@@ -364,7 +368,13 @@ struct Bounds {  // the per-element data every bound-aware kernel needs
   const double *x, *lb, *ub, *zl, *zu;
   double max_bound;  // max_bound_value (1e20)
   int use_lower, use_upper;
+  // uniform bounds: every element of this rank's lb (ub) has the bits of lb_c (ub_c) -- the kernels take the scalar
+  // and do not read the vector (found by k_check_bounds; the vectors stay allocated and current)
+  int lb_uni = 0, ub_uni = 0;
+  double lb_c = 0.0, ub_c = 0.0;
 };
+// n-sized streams of lb / ub a bound-aware kernel does not read (count_bytes)
+inline int uniform_bound_streams(const Bounds &b) { return (b.lb_uni ? 1 : 0) + (b.ub_uni ? 1 : 0); }
 // rx = [L]zl - [U]zu - g + sum z_j A_j ; out = {comp product, active-bound count, l1 rx, l1 rzl,
 // l1 rzu, l2^2 rx, l2^2 rzl, l2^2 rzu, max|rx|, max|rzl|, max|rzu|} with
 // rzl = -((x-lb) zl - beta*mu), rzu = -((ub-x) zu - beta*mu).
@@ -509,8 +519,10 @@ int k_update_mult(Ctx *c, double *zl, const double *pzl, double *zu, const doubl
 int k_affine_mult(Ctx *c, const Bounds &b, double *zl, const double *pzl, double *zu,
                   const double *pzu, double amin, int64_t n);
 // initAndCheckDesignAndBounds :4290-4360; out flag bits 1/2/4; zl/zu zeroed on inactive bounds
+// uni != nullptr: uni[0] / uni[1] = every element of this rank's stored lb / ub has the bits of val[0] / val[1]
 int k_check_bounds(Ctx *c, double *x, double *lb, double *ub, double *zl, double *zu,
-                   double max_bound, double rel_bound, int both, int64_t n, int *flag);
+                   double max_bound, double rel_bound, int both, int64_t n, int *flag, int uni[2] = nullptr,
+                   double val[2] = nullptr);
 int k_bounds_mode(Ctx *c, double *x, double *lb, double *ub, int mode, int64_t offset, int64_t n);
 // entries at their clamp values: out = {#x == lb + eps, #x == ub - eps, #zl == eps, #zu == eps} (global sums)
 int k_clamp_count(Ctx *c, const double *x, const double *lb, const double *ub, const double *zl, const double *zu,

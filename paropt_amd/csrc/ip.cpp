@@ -193,6 +193,12 @@ Bounds InteriorPoint::bounds() const {
   b.max_bound = options.real("max_bound_value");
   b.use_lower = use_lower;
   b.use_upper = use_upper;
+  if (dbg_switch(SW_UNIFORM_BOUNDS, nullptr, 1) != 0) {
+    b.lb_uni = bounds_uni[0];
+    b.ub_uni = bounds_uni[1];
+    b.lb_c = bounds_val[0];
+    b.ub_c = bounds_val[1];
+  }
   return b;
 }
 
@@ -259,6 +265,7 @@ void InteriorPoint::userHarvest() {
 // bounds / starting point
 // ================================================================================================
 int InteriorPoint::initAndCheckDesignAndBounds() {  // :4277-4361
+  bounds_uni[0] = bounds_uni[1] = 0;
   int rc = prob->getVarsAndBounds(x, lb, ub);
   if (rc != 0) {
     set_error("getVarsAndBounds failed with code %d", rc);
@@ -267,7 +274,7 @@ int InteriorPoint::initAndCheckDesignAndBounds() {  // :4277-4361
   const double rel_bound = 0.001 * barrier_param;
   int flag = 0;
   PO_TRY(k_check_bounds(ctx, x->d, lb->d, ub->d, zl->d, zu->d, options.real("max_bound_value"),
-                        rel_bound, use_lower && use_upper, n, &flag));
+                        rel_bound, use_lower && use_upper, n, &flag, bounds_uni, bounds_val));
   check_flag |= flag;
   if (ctx->rank == 0) {
     if (flag & 1) history += "ParOpt Warning: Variable bounds are inconsistent\n";
@@ -304,6 +311,7 @@ static int refreshLiveMirror(Vec *v) {
 
 int InteriorPoint::resetDesignAndBounds() {  // :1249-1251
   cwx_valid = false;
+  bounds_uni[0] = bounds_uni[1] = 0;  // (found again by the next optimize())
   int rc = prob->getVarsAndBounds(x, lb, ub);
   if (rc != 0) return PO_ERR_USER;
   PO_TRY(refreshLiveMirror(x));
@@ -1161,6 +1169,7 @@ int InteriorPoint::checkKKTStep(int iteration, double mu) {
 }
 
 int InteriorPoint::checkGradients(double dh, std::string *report) {  // :6196-6199
+  spec_dt_valid = false;  // (tvec is its scratch)
   return prob->checkGradients(dh, x, options.integer("use_hvec_product"), xt, tvec, report);
 }
 
@@ -2181,6 +2190,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
     if (gradient_verification_frequency > 0 && (k % gradient_verification_frequency) == 0) {
       std::string rep;
       PO_TRY(prob->checkGradients(options.real("gradient_check_step_length"), x, use_hvec_product, xt, tvec, &rep));
+      spec_dt_valid = false;  // (tvec was its scratch: the t the residual pass left behind is gone)
       if (ctx->rank == 0) history += rep;
     }
 

@@ -67,6 +67,8 @@ class InteriorPoint {
   const std::vector<int> &gPivots() const { return gpiv; }
   Vec *lowerBounds() { return lb; }
   Vec *upperBounds() { return ub; }
+  // the caller may write lb / ub through a handle: the kernels read the vectors until the next optimize()
+  void clearUniformBounds() { bounds_uni[0] = bounds_uni[1] = 0; }
   int checkFlag() const { return check_flag; }
   int clampCounts(double out[8]);
   // checkKKTStep (:6212-6360), step_verification_frequency: appends the block maxima of the linearised KKT
@@ -319,6 +321,10 @@ class InteriorPoint {
   void userEnd();
   void userHarvest();
   int check_flag = 0;  // OR of the bound-repair bits of every initAndCheckDesignAndBounds call (:4290-4344)
+  // uniform lb / ub of this rank as the last initAndCheckDesignAndBounds found them (bounds() hands them to the
+  // kernels); every other writer of lb / ub clears them
+  int bounds_uni[2] = {0, 0};
+  double bounds_val[2] = {0.0, 0.0};
   bool ac_valid = false;
   // A^T z of a problem with linear dense constraints, kept by recurrence (computeResidual / computeStepAndUpdate)
   static const int kAczRefresh = 16;

@@ -14,6 +14,7 @@
 
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace po {
 
@@ -977,8 +978,16 @@ __device__ __forceinline__ BE bound_elem(double x, double lb, double ub, double 
     e1.xl = 1.0;                                                                         \
     e1.xu = 1.0;                                                                         \
   }
+// A uniform bound (Bounds::lb_uni / ub_uni) is the scalar: the flag is a kernel argument, so the branch is scalar and
+// the vector load is skipped.  Every element has the scalar's bits, so nothing changes but the traffic (the pad
+// element of an odd-length shard is masked by _has2 at every use).
+__device__ __forceinline__ double2 ld2_bound(const double *__restrict__ p, int uni, double v, int64_t q, int64_t n) {
+  return uni ? make_double2(v, v) : ld2(p, q, n);
+}
+#define PO_LD2_LB(b, q, n) ld2_bound((b).lb, (b).lb_uni, (b).lb_c, q, n)
+#define PO_LD2_UB(b, q, n) ld2_bound((b).ub, (b).ub_uni, (b).ub_c, q, n)
 #define PO_LOAD_BOUNDS(b, q, n)                                                         \
-  const double2 _x = ld2((b).x, q, n), _lb = ld2((b).lb, q, n), _ub = ld2((b).ub, q, n), \
+  const double2 _x = ld2((b).x, q, n), _lb = PO_LD2_LB(b, q, n), _ub = PO_LD2_UB(b, q, n), \
                 _zl = ld2((b).zl, q, n), _zu = ld2((b).zu, q, n);                        \
   PO_MAKE_BOUNDS(b, q, n)
 
@@ -1081,7 +1090,7 @@ int k_kkt_res(Ctx *c, const Bounds &b, const double *g, const double *const *A, 
     PO_TRY(collapse_range(c, 0, z, A, 0, nc, n, &w));
     return k_kkt_res(c, b, g, &w, &one, 1, beta_mu, n, rx, out, yqn, beta_mu2, gcol, gcoef);
   }
-  count_bytes(c, 7 + nc + (yqn ? 2 : 0), n);
+  count_bytes(c, 7 + nc + (yqn ? 2 : 0) - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 13));
   PtrTable pt;
@@ -1110,7 +1119,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 int k_res_norms(Ctx *c, const Bounds &b, double beta_mu, int64_t n, double out[11]) {
-  count_bytes(c, 5, n);
+  count_bytes(c, 5 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);
   PO_TRY(ensure_partials(c, (size_t)grid * 11));
   PO_LAUNCH(res_norms_kernel, grid, b, beta_mu, n, c->d_partials);
@@ -1135,7 +1144,7 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 int k_dinv(Ctx *c, const Bounds &b, double diag, int64_t n, double *dinv, const double *hdiag) {
-  count_bytes(c, 6 + (hdiag ? 1 : 0), n);
+  count_bytes(c, 6 + (hdiag ? 1 : 0) - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PO_LAUNCH(dinv_kernel, grid_for(c, n), b, diag, hdiag, n, dinv);
   return PO_OK;
@@ -1170,7 +1179,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_d1(Ctx *c, const Bounds &b, const double *rx, const double *dinv, double beta_mu, int64_t n,
          double *t, const double *cl, const double *cu) {
-  count_bytes(c, 7 + (dinv ? 1 : 0) + (cl ? 2 : 0), n);
+  count_bytes(c, 7 + (dinv ? 1 : 0) + (cl ? 2 : 0) - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PO_LAUNCH(d1_kernel, grid_for(c, n), b, rx, dinv, beta_mu, cl, cu, n, t);
   return PO_OK;
@@ -1197,7 +1206,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_dinv_d1(Ctx *c, const Bounds &b, double diag, const double *hdiag, const double *rx, double beta_mu,
               int64_t n, double *dinv, double *t, int raw) {
-  count_bytes(c, 8 + (hdiag ? 1 : 0), n);
+  count_bytes(c, 8 + (hdiag ? 1 : 0) - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PO_LAUNCH(dinv_d1_kernel, grid_for(c, n), b, diag, hdiag, rx, beta_mu, n, dinv, t, raw);
   return PO_OK;
@@ -1217,7 +1226,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_corrector(Ctx *c, const Bounds &b, const double *px, const double *pzl, const double *pzu,
                 int64_t n, double *cl, double *cu) {
-  count_bytes(c, 8, n);  // x, lb, ub (the bound predicates), px, pzl, pzu in; cl, cu out (zl / zu are not used)
+  count_bytes(c, 8 - uniform_bound_streams(b), n);  // x, lb, ub (the bound predicates), px, pzl, pzu in; cl, cu out (zl / zu are not used)
   if (n <= 0) return PO_OK;
   PO_LAUNCH(corrector_kernel, grid_for(c, n), b, px, pzl, pzu, n, cl, cu);
   return PO_OK;
@@ -1274,7 +1283,7 @@ int k_corr_d1_dots(Ctx *c, const Bounds &b, const double *px, const double *pzl,
     set_error("k_corr_d1_dots: %d panel columns (1..%d)", nv, kCorrDotsMax);
     return PO_ERR_ARG;
   }
-  count_bytes(c, nv + 11, n);
+  count_bytes(c, nv + 11 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n, 5);  // mdot's grid: the products come out with mdot's bits
   PO_TRY(ensure_partials(c, (size_t)grid * nv));
   PtrTable pt;
@@ -1556,7 +1565,7 @@ int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const
               double *pzl, double *pzu, double *va, int nca, double out[2], const double *ar, const double *rx,
               double diag, int ca0, const double *const *vs, int nvirt, double b0v, const double *g,
               double *merit_out, double dinv_diag, const GroupCol *gcol, double gc1, double gc2) {
-  count_bytes(c, nv + nvirt + 7 + (t1 ? 2 : 0) + (pzl ? 2 : 0) + (va ? 1 : 0) + (g ? 1 : 0), n);
+  count_bytes(c, nv + nvirt + 7 + (t1 ? 2 : 0) + (pzl ? 2 : 0) + (va ? 1 : 0) + (g ? 1 : 0) - uniform_bound_streams(b), n);
   PO_TRY(gcol_check(gcol, n, "k_solve2r"));
   if (gcol && t2 == nullptr) {
     set_error("k_solve2r: a grouped column is only taken in the stored right-hand side form");
@@ -1627,7 +1636,7 @@ int k_solve2(Ctx *c, const Bounds &b, const double *t, const double *dinv, const
              double *px, double *pzl, double *pzu, double out[2], const double *coef2,
              const double *rx, double diag, double *tout, double *va, int nca, const double *cl,
              const double *cu) {
-  count_bytes(c, nv + 10 + (refine ? 3 : 0) + (va ? (refine ? 2 : 1) : 0) + (coef2 ? 2 : 0) + (cl ? 2 : 0), n);
+  count_bytes(c, nv + 10 + (refine ? 3 : 0) + (va ? (refine ? 2 : 1) : 0) + (coef2 ? 2 : 0) + (cl ? 2 : 0) - uniform_bound_streams(b), n);
   if (nv > kMaxPanel) {
     if (coef2) {
       set_error("k_solve2: the fused refinement residual is not available for a panel of %d (> %d) columns", nv,
@@ -1735,8 +1744,8 @@ __global__ void __launch_bounds__(kBlock, OCC)
     ein = _ir < n;                                                                           \
     ie = ein ? _ir : n - 1;                                                                  \
     eb[0] = b.x[ie];                                                                         \
-    eb[1] = b.lb[ie];                                                                        \
-    eb[2] = b.ub[ie];                                                                        \
+    eb[1] = b.lb_uni ? b.lb_c : b.lb[ie];                                                    \
+    eb[2] = b.ub_uni ? b.ub_c : b.ub[ie];                                                    \
     eb[3] = b.zl[ie];                                                                        \
     eb[4] = b.zu[ie];                                                                        \
     if (t) { /* (nullptr: t and Dinv re-formed from the bound data and rx, as dinv_d1_kernel formed them) */ \
@@ -1942,8 +1951,8 @@ __global__ void __launch_bounds__(kBlock, OCC)
     ein = _mine < ntiles && _ir < n;                                                         \
     const int64_t _ie = ein ? _ir : n - 1;                                                   \
     eb[0] = b.x[_ie];                                                                        \
-    eb[1] = b.lb[_ie];                                                                       \
-    eb[2] = b.ub[_ie];                                                                       \
+    eb[1] = b.lb_uni ? b.lb_c : b.lb[_ie];                                                   \
+    eb[2] = b.ub_uni ? b.ub_c : b.ub[_ie];                                                   \
     eb[3] = b.zl[_ie];                                                                       \
     eb[4] = b.zu[_ie];                                                                       \
     if (t) {                                                                                 \
@@ -2156,7 +2165,7 @@ int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, 
                   const double *rx, double diag, int64_t n, double *px, double *pzl, double *pzu,
                   double *tout, double *va, int nca, double *out, double *traw, int store_step, int ca0,
                   const double *const *vs, int nvirt, double b0v, double dinv_diag, const GroupCols2 *gcols) {
-  count_bytes(c, nv + nvirt + 6 + (t ? 2 : 0) + (store_step == 1 ? 3 + (va ? 1 : 0) : (store_step == 2 ? 1 : 0)) + ((traw || tout) ? 1 : 0), n);
+  count_bytes(c, nv + nvirt + 6 + (t ? 2 : 0) + (store_step == 1 ? 3 + (va ? 1 : 0) : (store_step == 2 ? 1 : 0)) + ((traw || tout) ? 1 : 0) - uniform_bound_streams(b), n);
   const GroupCols2 gcs = gcols ? *gcols : GroupCols2();
   for (int e = 0; e < gcs.count; e++) PO_TRY(gcol_check(&gcs.g[e], n, "k_solve2_dots"));
   for (int e = 0; e < gcs.count; e++) count_bytes(c, 1.0, gcs.g[e].nwcon);
@@ -2257,7 +2266,7 @@ int k_step_check(Ctx *c, const Bounds &b, const double *rx, const double *px, co
     PO_TRY(collapse_range(c, 0, coef, P, 0, nv, n, &w));
     return k_step_check(c, b, rx, px, pzl, pzu, &one, &w, 1, diag, beta_mu, n, out);
   }
-  count_bytes(c, nv + 9, n);
+  count_bytes(c, nv + 9 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 3));
   PtrTable pt;
@@ -2275,7 +2284,7 @@ int k_res_step(Ctx *c, const Bounds &b, const double *rx, const double *px, cons
     PO_TRY(collapse_range(c, 0, coef, P, 0, nv, n, &w));
     return k_res_step(c, b, rx, px, pzl, pzu, dinv, &one, &w, 1, diag, beta_mu, n, tprime);
   }
-  count_bytes(c, nv + 10 + (dinv ? 1 : 0), n);
+  count_bytes(c, nv + 10 + (dinv ? 1 : 0) - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PtrTable pt;
   CoefTable ct;
@@ -2317,7 +2326,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_comp_step(Ctx *c, const Bounds &b, const double *px, const double *pzl, const double *pzu,
                 double ax, double az, int64_t n, double out[2]) {
-  count_bytes(c, 8, n);
+  count_bytes(c, 8 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);
   PO_TRY(ensure_partials(c, (size_t)grid * 2));
   PO_LAUNCH(comp_step_kernel, grid, b, px, pzl, pzu, ax, az, n, c->d_partials);
@@ -2360,7 +2369,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_merit0(Ctx *c, const Bounds &b, const double *px, double sx, const double *g, int64_t n,
              double out[6]) {
-  count_bytes(c, 7, n);
+  count_bytes(c, 7 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);
   PO_TRY(ensure_partials(c, (size_t)grid * 6));
   PO_LAUNCH(merit0_kernel, grid, b, px, sx, g, n, c->d_partials);
@@ -2414,7 +2423,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_comp_merit(Ctx *c, const Bounds &b, const double *px, const double *pzl, const double *pzu, double ax,
                  double az, const double *g, int64_t n, double out[9]) {
-  count_bytes(c, 9, n);
+  count_bytes(c, 9 - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);
   PO_TRY(ensure_partials(c, (size_t)grid * 9));
   PO_LAUNCH(comp_merit_kernel, grid, b, px, pzl, pzu, ax, az, g, n, c->d_partials);
@@ -2501,7 +2510,7 @@ int k_solve2c(Ctx *c, const Bounds &b, const double *t, const double *dinv, cons
     set_error("k_solve2c: panel of %d vectors exceeds kMaxPanel=%d", nv, kMaxPanel);
     return PO_ERR_ARG;
   }
-  count_bytes(c, nv + 14 + (va ? 1 : 0), n);
+  count_bytes(c, nv + 14 + (va ? 1 : 0) - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);  // comp_merit_kernel's grid
   PO_TRY(ensure_partials(c, (size_t)grid * 12));
   PtrTable pt;
@@ -2524,7 +2533,7 @@ __global__ void __launch_bounds__(kBlock)
   __shared__ double sm[4 * 2];
   double s[2] = {0.0, 0.0};
   PO_PAIR_LOOP(q, n) {
-    const double2 x = ld2(b.x, q, n), lb = ld2(b.lb, q, n), ub = ld2(b.ub, q, n), p = ld2(px, q, n);
+    const double2 x = ld2(b.x, q, n), lb = PO_LD2_LB(b, q, n), ub = PO_LD2_UB(b, q, n), p = ld2(px, q, n);
     const bool has2 = (2 * q + 1 < n);
     // computeStep :3146-3191: the clamps use the bound vectors themselves (no predicate)
     double2 v;
@@ -2544,7 +2553,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_trial(Ctx *c, const Bounds &b, const double *px, double a, double eps, int64_t n, double *xt,
             double out[2], double *sout) {
-  count_bytes(c, 5 + (sout ? 1 : 0), n);
+  count_bytes(c, 5 + (sout ? 1 : 0) - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n);
   PO_TRY(ensure_partials(c, (size_t)grid * 2));
   PO_LAUNCH(trial_kernel, grid, b, px, a, eps, n, xt, sout, c->d_partials);
@@ -2641,7 +2650,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_form_pz(Ctx *c, const Bounds &b, const double *px, double beta_mu, int64_t n, double *pzl, double *pzu) {
   if (n <= 0) return PO_OK;
-  count_bytes(c, 8, n);
+  count_bytes(c, 8 - uniform_bound_streams(b), n);
   PO_LAUNCH(form_pz_kernel, grid_for(c, n), b, px, beta_mu, n, pzl, pzu);
   return PO_OK;
 }
@@ -2668,7 +2677,7 @@ __global__ void __launch_bounds__(kBlock)
   PO_PAIR_LOOP(q, n) {
     GRaw graw;  // the grouped column's entries: requested first, used by the panel sum below
     if (gcol.w) graw = gcol_request(gcol, q, n);
-    const double2 _x = ld2(b.x, q, n), _lb = ld2(b.lb, q, n), _ub = ld2(b.ub, q, n);
+    const double2 _x = ld2(b.x, q, n), _lb = PO_LD2_LB(b, q, n), _ub = PO_LD2_UB(b, q, n);
     // pxs != nullptr ("lean step"): the refinement pass did not store the bound-multiplier steps; they are formed
     // here from the design step px, the OLD point (xold) and the old multipliers by the first-solve formula
     // pzl = [L] (rzl - zl px) / (x - lb), pzu = [U] (rzu + zu px) / (ub - x) -- which the refined values equal up to the
@@ -2800,7 +2809,7 @@ int k_kkt_res_update(Ctx *c, const Bounds &b, const double *g, const double *con
     return k_kkt_res_update(c, b, g, &w, &one, 1, beta_mu, n, rx, out, yqn, zl, pzl, zu, pzu, a, eps, va, az, acz, az_acz,
                             pxs, xold, beta_mu_step, beta_mu2, gcol, gcoef, dinv_out, t_out, spec_diag, spec_beta_mu);
   }
-  count_bytes(c, (yqn ? 14 : 11) + (acz ? (az_acz != 0.0 ? 2 : 1) : nc) + (dinv_out ? 2 : 0), n);
+  count_bytes(c, (yqn ? 14 : 11) + (acz ? (az_acz != 0.0 ? 2 : 1) : nc) + (dinv_out ? 2 : 0) - uniform_bound_streams(b), n);
   const int grid = grid_for(c, n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 13));
   PtrTable pt;
@@ -2831,18 +2840,31 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_affine_mult(Ctx *c, const Bounds &b, double *zl, const double *pzl, double *zu,
                   const double *pzu, double amin, int64_t n) {
-  count_bytes(c, 9, n);
+  count_bytes(c, 9 - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PO_LAUNCH(affine_mult_kernel, grid_for(c, n), b, zl, pzl, zu, pzu, amin, n);
   return PO_OK;
 }
 
+// The same pass finds uniform bounds: the minimum and maximum over the shard of each 32-bit half of the bit pattern
+// of the STORED lb / ub (after the repair above) -- bits, not values, so -0.0 and 0.0 differ.  Halves are exact as
+// doubles, so the reduction of the flags carries them.
+__device__ __forceinline__ void bits_minmax(double v, double *mn, double *mx) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const double hi = (double)(unsigned)(u >> 32), lo = (double)(unsigned)(u & 0xffffffffull);
+  mn[0] = fmin(mn[0], hi);
+  mn[1] = fmin(mn[1], lo);
+  mx[0] = fmax(mx[0], hi);
+  mx[1] = fmax(mx[1], lo);
+}
 __global__ void __launch_bounds__(kBlock)
     check_bounds_kernel(double *__restrict__ x, double *__restrict__ lb, double *__restrict__ ub,
                         double *__restrict__ zl, double *__restrict__ zu, double maxb,
                         double rel_bound, int both, int64_t n, double *__restrict__ partials) {
-  __shared__ double sm[4 * 3];
-  double flags[3] = {0.0, 0.0, 0.0};
+  __shared__ double sm[4 * 7];
+  // bmin: min of the lb hi / lo halves, ub hi / lo; flags[3..6]: max of the same
+  double bmin[4] = {8589934592.0, 8589934592.0, 8589934592.0, 8589934592.0};
+  double flags[7] = {0.0, 0.0, 0.0, -1.0, -1.0, -1.0, -1.0};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     double xv = x[i], l = lb[i], u = ub[i];
@@ -2870,19 +2892,36 @@ __global__ void __launch_bounds__(kBlock)
     }
     if (l <= -maxb) zl[i] = 0.0;
     if (u >= maxb) zu[i] = 0.0;
+    bits_minmax(l, &bmin[0], &flags[3]);
+    bits_minmax(u, &bmin[2], &flags[5]);
   }
-  block_reduce_store<3, OP_MAX>(flags, partials, 0, sm);
+  block_reduce_store<4, OP_MIN>(bmin, partials, 0, sm);
+  block_reduce_store<7, OP_MAX>(flags, partials, 4, sm);
 }
 int k_check_bounds(Ctx *c, double *x, double *lb, double *ub, double *zl, double *zu,
-                   double max_bound, double rel_bound, int both, int64_t n, int *flag) {
+                   double max_bound, double rel_bound, int both, int64_t n, int *flag, int uni[2],
+                   double val[2]) {
   count_bytes(c, 5, n);
   const int grid = grid_for(c, n);
-  PO_TRY(ensure_partials(c, (size_t)grid * 3));
+  PO_TRY(ensure_partials(c, (size_t)grid * 11));
   PO_LAUNCH(check_bounds_kernel, grid, x, lb, ub, zl, zu, max_bound, rel_bound, both, n,
             c->d_partials);
-  double out[3];
-  PO_TRY(reduce_finish(c, grid, 0, 0, 3, out, true));
-  *flag = (out[0] > 0.0 ? 1 : 0) | (out[1] > 0.0 ? 2 : 0) | (out[2] > 0.0 ? 4 : 0);
+  // out: the flags over all ranks; mine: this rank's halves (its kernels read its own shard only)
+  double out[11], mine[11];
+  PO_TRY(reduce_finish(c, grid, 0, 4, 7, out, true, mine));
+  *flag = (out[4] > 0.0 ? 1 : 0) | (out[5] > 0.0 ? 2 : 0) | (out[6] > 0.0 ? 4 : 0);
+  if (uni) {
+    for (int k = 0; k < 2; k++) {
+      const double *mn = mine + 2 * k, *mx = mine + 7 + 2 * k;
+      // (an empty shard leaves min > max: not uniform, and nothing to read either)
+      uni[k] = mn[0] == mx[0] && mn[1] == mx[1];
+      val[k] = 0.0;
+      if (uni[k]) {
+        const unsigned long long u = ((unsigned long long)(unsigned)mn[0] << 32) | (unsigned long long)(unsigned)mn[1];
+        memcpy(&val[k], &u, sizeof(double));
+      }
+    }
+  }
   return PO_OK;
 }
 
@@ -3104,7 +3143,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_d1s(Ctx *c, const Bounds &b, const double *bx, const double *dinv, double alpha, double beta_mu,
           int64_t n, double *t) {
-  count_bytes(c, 8, n);
+  count_bytes(c, 8 - uniform_bound_streams(b), n);
   if (n <= 0) return PO_OK;
   PO_LAUNCH(d1s_kernel, grid_for(c, n), b, bx, dinv, alpha, beta_mu, n, t);
   return PO_OK;
@@ -3152,7 +3191,7 @@ int k_solve2s(Ctx *c, const Bounds &b, const double *t, const double *dinv, cons
     PO_TRY(collapse_range(c, 0, coef, P, 0, nv, n, &w));
     return k_solve2s(c, b, t, dinv, &one, &w, 1, alpha, beta_mu, full, tau, n, px, pzl, pzu, out);
   }
-  count_bytes(c, nv + 10, n);
+  count_bytes(c, nv + 10 - uniform_bound_streams(b), n);
   if (nv > kMaxPanel) {
     set_error("panel of %d vectors exceeds kMaxPanel=%d", nv, kMaxPanel);
     return PO_ERR_ARG;
