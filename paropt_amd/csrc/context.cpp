@@ -26,19 +26,63 @@ void set_error(const char *fmt, ...) {
 }
 const char *last_error() { return g_err; }
 
-static int g_dbg_switch[SW_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 double host_now() {
   struct timespec t;
   clock_gettime(CLOCK_MONOTONIC, &t);
   return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
 }
-int dbg_switch(int id, const char *env, int dflt) {
-  if (id >= 0 && id < SW_COUNT && g_dbg_switch[id] >= 0) return g_dbg_switch[id];
-  const char *e = env ? getenv(env) : nullptr;
-  return e ? atoi(e) : dflt;
+
+// The switch table (core.hpp DbgSwitch).  `presence`: the variable switches on by being set, whatever its value;
+// otherwise its value is read as an integer.  Each switch is read where its code reads it: at context creation, solver
+// construction, symbolic analysis, ... (INTEGRATION.md "Diagnostics").
+struct SwitchDef {
+  DbgSwitch id;
+  const char *env;  // nullptr: po_debug_set_switch only
+  int dflt;
+  bool presence;
+};
+static const SwitchDef kSwitches[] = {
+    {SW_PERTURB_W, nullptr, 0, false},
+    {SW_MPC_FUSE, "PAROPT_AMD_MPC_FUSE", 1, false},
+    {SW_MPC_POLY, "PAROPT_AMD_MPC_POLY", 1, false},
+    {SW_SPEC_DT, "PAROPT_AMD_SPEC_DT", 1, false},
+    {SW_UNIFORM_BOUNDS, nullptr, 1, false},
+    {SW_WGRAM_PRIO, "PAROPT_AMD_WGRAM_PRIO", 2, false},
+    {SW_WGRAM_ABLATE, "PAROPT_AMD_WGRAM_ABLATE", 0, false},
+    {SW_EXPLICIT_DOTS, "PAROPT_AMD_EXPLICIT_DOTS", 0, true},
+    {SW_NO_RECOMPUTE, "PAROPT_AMD_NO_RECOMPUTE", 0, true},
+    {SW_NO_RECOMPUTE_RHS, "PAROPT_AMD_NO_RECOMPUTE_RHS", 0, true},
+    {SW_NO_FUSED_MERIT, "PAROPT_AMD_NO_FUSED_MERIT", 0, true},
+    {SW_NO_LEAN_STEP, "PAROPT_AMD_NO_LEAN_STEP", 0, true},
+    {SW_NO_RECOMPUTE_DT, "PAROPT_AMD_NO_RECOMPUTE_DT", 0, true},
+    {SW_NO_FUSED_UPDATE, "PAROPT_AMD_NO_FUSED_UPDATE", 0, true},
+    {SW_NO_CSR_GROUPS, "PAROPT_AMD_NO_CSR_GROUPS", 0, true},
+    {SW_NO_FRONTS, "PAROPT_AMD_NO_FRONTS", 0, false},
+    {SW_FORCE_RCCL, "PAROPT_AMD_FORCE_RCCL", 0, true},
+    {SW_RCCL_ALLGATHER, "PAROPT_AMD_RCCL_ALLGATHER", 0, true},
+    {SW_NO_DIRECT_RED, "PAROPT_AMD_NO_DIRECT_RED", 0, true},
+    {SW_NO_FLAG_POLL, "PAROPT_AMD_NO_FLAG_POLL", 0, true},
+    {SW_NO_BATCH, "PAROPT_AMD_NO_BATCH", 0, true},
+    {SW_HOST_TRACE, "PAROPT_AMD_HOST_TRACE", 0, true},
+    {SW_SYNC_TRACE, "PAROPT_AMD_SYNC_TRACE", 0, true},
+    {SW_USER_TIMING, "PAROPT_AMD_USER_TIMING", 0, true},
+    {SW_DUMP_LONG_SOLVES, "PAROPT_AMD_DUMP_LONG_SOLVES", -1, false},
+};
+static struct {
+  int value = -1;  // >= 0: set through po_debug_set_switch
+} g_dbg_switch[SW_COUNT];
+
+int dbg_switch(DbgSwitch id) {
+  if (g_dbg_switch[id].value >= 0) return g_dbg_switch[id].value;
+  for (const SwitchDef &s : kSwitches) {
+    if (s.id != id) continue;
+    const char *e = s.env ? getenv(s.env) : nullptr;
+    return e ? (s.presence ? 1 : atoi(e)) : s.dflt;
+  }
+  return 0;  // (a retired id)
 }
 void dbg_switch_set(int id, int value) {
-  if (id >= 0 && id < SW_COUNT) g_dbg_switch[id] = value;
+  if (id >= 0 && id < SW_COUNT) g_dbg_switch[id].value = value;
 }
 
 int launch_reduce_final(Ctx *c, int nblocks, int nslots, int nsum, int nmin, int dst_off);
@@ -60,7 +104,7 @@ static int alloc_h_red(Ctx *c, size_t doubles) {
   } else {
     c->h_red_coherent = 1;
   }
-  if (getenv("PAROPT_AMD_NO_DIRECT_RED") ||
+  if (dbg_switch(SW_NO_DIRECT_RED) ||
       hipHostGetDevicePointer((void **)&c->h_red_dev, c->h_red, 0) != hipSuccess) {
     (void)hipGetLastError();
     c->h_red_dev = nullptr;
@@ -77,7 +121,7 @@ static int alloc_h_red(Ctx *c, size_t doubles) {
   // the completion flag of the final reduction stages (see Ctx::h_flag): allocated once
   // (without the explicit coherence guarantee the flag is not used at all: results behind a flag the host has seen
   // could themselves be stale)
-  if (c->h_red_dev && !c->h_flag && c->h_red_coherent && !getenv("PAROPT_AMD_NO_FLAG_POLL")) {
+  if (c->h_red_dev && !c->h_flag && c->h_red_coherent && !dbg_switch(SW_NO_FLAG_POLL)) {
     if (hipHostMalloc((void **)&c->h_flag, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
         hipHostGetDevicePointer((void **)&c->h_flag_dev, c->h_flag, 0) == hipSuccess &&
         hipMalloc((void **)&c->d_ticket, sizeof(unsigned)) == hipSuccess &&
@@ -192,7 +236,7 @@ int comm_init_rccl(Ctx *c, int rank, int size, const void *id128) {
   c->size = size;
   // PAROPT_AMD_FORCE_RCCL=1 routes even a single rank through ncclCommInitRank / ncclAllGather, so
   // the RCCL plumbing (dlopen, by-value unique id, stream use) can be exercised on a 1-GPU box
-  if (size == 1 && !getenv("PAROPT_AMD_FORCE_RCCL")) {
+  if (size == 1 && !dbg_switch(SW_FORCE_RCCL)) {
     c->comm_kind = COMM_SELF;
     return PO_OK;
   }
@@ -210,7 +254,7 @@ int comm_init_rccl(Ctx *c, int rank, int size, const void *id128) {
   c->comm_kind = COMM_RCCL;
   // PAROPT_AMD_RCCL_ALLGATHER=1: every reduction through the rank-ordered all-gather (bit-identical across
   // rank-to-GPU placements); default: pure-sum payloads use ncclAllReduce, mixed SUM/MIN/MAX the all-gather
-  c->rccl_allreduce = getenv("PAROPT_AMD_RCCL_ALLGATHER") ? 0 : 1;
+  c->rccl_allreduce = dbg_switch(SW_RCCL_ALLGATHER) ? 0 : 1;
   // gather buffers sized for the communicator
   if (c->d_gather) (void)hipFree(c->d_gather);
   PO_HIP(hipMalloc((void **)&c->d_gather, sizeof(double) * (size_t)size * kMaxRed));
@@ -279,7 +323,7 @@ int ctx_create(int device, Ctx **out) {
   PO_HIP(hipGetDeviceProperties(&prop, device));
   po_ctx_s *c = new po_ctx_s();
   c->device = device;
-  c->host_trace = getenv("PAROPT_AMD_HOST_TRACE") != nullptr;
+  c->host_trace = dbg_switch(SW_HOST_TRACE) != 0;
   if (c->host_trace) {
     if (g_traced.empty()) atexit(host_trace_atexit);
     g_traced.push_back(c);
@@ -294,7 +338,7 @@ int ctx_create(int device, Ctx **out) {
   PO_HIP(hipEventCreate(&c->ev_mdot0));
   PO_HIP(hipEventCreate(&c->ev_mdot1));
   c->partials_cap = 0;
-  if (getenv("PAROPT_AMD_NO_BATCH")) c->batch_enabled = 0;
+  if (dbg_switch(SW_NO_BATCH)) c->batch_enabled = 0;
   *out = c;
   return ensure_partials(c, (size_t)c->max_blocks * 64);
 }
@@ -424,7 +468,7 @@ static int exchange_reduced(Ctx *c, int total, bool pure_sum, const double **par
   const double *parts = c->h_red;
   c->n_reductions++;
   const double ht0 = c->host_trace ? host_now() : 0.0;
-  static const bool trace = getenv("PAROPT_AMD_SYNC_TRACE") != nullptr;  // development aid: who synchronises?
+  static const bool trace = dbg_switch(SW_SYNC_TRACE) != 0;  // development aid: who synchronises?
   if (trace) {
     void *frames[12];
     const int nf = backtrace(frames, 12);

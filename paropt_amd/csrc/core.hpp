@@ -145,15 +145,6 @@ struct PtrTable {
 struct CoefTable {
   double a[kMaxPanel];
 };
-// Unformed L-SR1 columns at the head of a panel: column j < count has the value P.p[j] - b0 * s[j] (P.p[j] = Y_j,
-// s[j] = S_j), formed in registers by the consumer -- never written to HBM (a write costs about four reads).
-constexpr int kMaxVirt = 12;
-struct VirtCols {
-  const double *s[kMaxVirt];
-  int count;
-  double b0;
-};
-
 // Reduction finish: combine first-stage partials ([slot][nblocks] in ctx->d_partials) into
 // host_out[nsum+nmin+nmax]; slots are ordered sums, then mins, then maxs.  Collective.
 // Inside a BatchScope the call returns before host_out is valid unless `now` is set (which flushes the batch).
@@ -231,18 +222,25 @@ struct BatchScope {
   BatchScope(const BatchScope &) = delete;
   BatchScope &operator=(const BatchScope &) = delete;
 };
-// Kernel-variant switches for A/B measurements inside ONE process (tools/ab_switch.py): the value set through
-// po_debug_set_switch wins, else the environment variable, else the default.  Not part of the interface.
-enum DbgSwitch { SW_WGRAM_RS = 0, SW_LINCOMB_2D = 1, SW_REDO_DT = 2, SW_LEAN_STEP = 3, SW_WGRAM_PRIO = 4,
-                 SW_WGRAM_ABLATE = 5, SW_FUSED_MERIT = 6, SW_REDO_DT1 = 7, SW_BPC3 = 8, SW_BPC4 = 9, SW_LINCOMB_BPC = 10,
-                 SW_PERTURB_W = 11, SW_GS_PRODUCER = 12, SW_S2D_TWO = 13, SW_MPC_FUSE = 14, SW_MPC_POLY = 15, SW_SPEC_DT = 16,
-                 SW_UNIFORM_BOUNDS = 17, SW_COUNT = 18 };  // one entry per use: an A/B run changes one thing
-int dbg_switch(int id, const char *env, int dflt);
+// Switches: A/B measurements inside ONE process (tools/ab_switch.py), the plain forms the tests compare the fused ones
+// against, and operational / diagnostic settings.  One entry per switch; its environment name and default are in the
+// table in context.cpp (INTEGRATION.md "Diagnostics" lists them).  The ids are stable: a retired id is never reused.
+// Not part of the interface.
+enum DbgSwitch {
+  SW_PERTURB_W = 11, SW_MPC_FUSE = 14, SW_MPC_POLY = 15, SW_SPEC_DT = 16, SW_UNIFORM_BOUNDS = 17,
+  SW_WGRAM_PRIO = 18, SW_WGRAM_ABLATE = 19, SW_EXPLICIT_DOTS = 20, SW_NO_RECOMPUTE = 21, SW_NO_RECOMPUTE_RHS = 22,
+  SW_NO_FUSED_MERIT = 23, SW_NO_LEAN_STEP = 24, SW_NO_RECOMPUTE_DT = 25, SW_NO_FUSED_UPDATE = 26,
+  SW_NO_CSR_GROUPS = 27, SW_NO_FRONTS = 28, SW_FORCE_RCCL = 29, SW_RCCL_ALLGATHER = 30, SW_NO_DIRECT_RED = 31,
+  SW_NO_FLAG_POLL = 32, SW_NO_BATCH = 33, SW_HOST_TRACE = 34, SW_SYNC_TRACE = 35, SW_USER_TIMING = 36,
+  SW_DUMP_LONG_SOLVES = 37, SW_COUNT = 38
+};
+// the value set through po_debug_set_switch, else the environment variable, else the default
+int dbg_switch(DbgSwitch id);
+void dbg_switch_set(int id, int value);  // value < 0: back to environment / default
 double host_now();  // seconds, monotonic
 // around a kernel launch when Ctx::host_trace is on (see Ctx): begin closes the gap behind the last synchronisation
 inline double host_trace_begin(Ctx *c);
 inline void host_trace_end(Ctx *c, double t0);
-void dbg_switch_set(int id, int value);  // value < 0: back to environment / default
 int ensure_partials(Ctx *c, size_t doubles);
 inline double host_trace_begin(Ctx *c) {
   if (!c->host_trace) return 0.0;
@@ -459,7 +457,6 @@ int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, 
                   double *tout, double *va, int nca, double *out, double *traw = nullptr,
                   int store_step = 1,  // 0: nothing of the step, 1: px, pzl, pzu (and va), 2: px only
                   int ca0 = 0,  // the nca constraint columns are P[ca0 .. ca0 + nca)
-                  const double *const *vs = nullptr, int nvirt = 0, double b0v = 0.0,  // P[j] - b0v vs[j], j < nvirt
                   double dinv_diag = 0.0,  // t == nullptr: Dinv (this diagonal) and t re-formed from the bound data and rx
                   // grouped columns behind P (panel positions nv, nv + 1): they enter the two row sums with (ca, cb);
                   // no panel dots are taken for them (out keeps its layout {dots[nv], max_x, max_z})
@@ -471,7 +468,6 @@ int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const
               double *pzl, double *pzu, double *va, int nca, double out[2], const double *ar = nullptr,
               const double *rx = nullptr, double diag = 0.0,  // t2 == nullptr: t2 recomputed from (ar, rx, diag)
               int ca0 = 0,  // the nca constraint columns are P[ca0 .. ca0 + nca)
-              const double *const *vs = nullptr, int nvirt = 0, double b0v = 0.0,  // P[j] - b0v vs[j], j < nvirt
               // g != nullptr (recomputed right-hand side form only): merit_out[10] = {S10, S01, S11, ppos, pneg, g.px,
               // px.px | max_x, max_z | max|px|} of the final step (see solve2r_kernel) instead of `out`
               const double *g = nullptr, double *merit_out = nullptr,

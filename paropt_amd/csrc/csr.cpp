@@ -20,15 +20,7 @@ int internal_error(const char *what) {
   return PO_ERR_ARG;
 }
 
-// subsets this small are numbered as they come (PAROPT_AMD_ND_LEAF overrides, for experiments)
-int leaf_size() {
-  static int v = 0;
-  if (v == 0) {
-    const char *e = getenv("PAROPT_AMD_ND_LEAF");
-    v = e && atoi(e) > 0 ? atoi(e) : 8;
-  }
-  return v;
-}
+constexpr int kNdLeaf = 8;  // subsets this small are numbered as they come
 
 // Nested dissection from BFS level structures (George's automatic nested dissection): the middle
 // level of a rooted level structure from a pseudo-peripheral vertex separates the graph; the two
@@ -74,7 +66,7 @@ struct Dissector {
 
   // number the vertices of `verts` (all carrying region id `reg`) into positions [lo, lo + |verts|)
   void order(std::vector<int> &verts, int reg, int lo, int depth) {
-    if ((int)verts.size() <= leaf_size() || depth > 96) {
+    if ((int)verts.size() <= kNdLeaf || depth > 96) {
       number(verts, lo);
       return;
     }
@@ -87,7 +79,7 @@ struct Dissector {
       if (region[verts[s]] != reg) continue;
       const int r = next_region++;
       bfs(verts[s], reg, comp, r);
-      if ((int)comp.size() <= leaf_size()) {
+      if ((int)comp.size() <= kNdLeaf) {
         small.insert(small.end(), comp.begin(), comp.end());
       } else {
         big.push_back(comp);
@@ -157,8 +149,7 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
                             bool allow_fronts);
 
 int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out) {
-  const char *e = getenv("PAROPT_AMD_NO_FRONTS");
-  int rc = csr_analyse_impl(n, w, rowp, cols, out, !(e && atoi(e) > 0));
+  int rc = csr_analyse_impl(n, w, rowp, cols, out, dbg_switch(SW_NO_FRONTS) <= 0);
   if (rc == PO_ERR_NUMERIC) {  // a chain that is not a dense front after all: schedule row by row
     *out = CsrSymbolic();
     rc = csr_analyse_impl(n, w, rowp, cols, out, false);

@@ -37,15 +37,15 @@ InteriorPoint::InteriorPoint(Problem *p)
       tvec(nullptr), xt(nullptr), y_qn(nullptr), s_qn(nullptr), vA(nullptr), qn_created(false), qn_owned(true), wk(0),
       comp_prod(0), comp_count(0), max_rx(0), max_rzl(0), max_rzu(0), sx(1.0), sz(1.0),
       ptpx_valid(false), residual_fused(false), residual_cached(false), corrector_active(false),
-      norm_type(0), tdots_valid(false), fused_dots(true), phase_t0(0) {
+      norm_type(0), tdots_valid(false), phase_t0(0) {
   qn_handle.qn = nullptr;
   hdiag = nullptr;
   vA_valid = false;
   inexact_newton_step = false;
   merit_cache_valid = false;
-  fuse_merit = !getenv("PAROPT_AMD_NO_FUSED_MERIT");
-  lean_step = !getenv("PAROPT_AMD_NO_LEAN_STEP");
-  recompute_dt = !getenv("PAROPT_AMD_NO_RECOMPUTE_DT");
+  fuse_merit = !dbg_switch(SW_NO_FUSED_MERIT);
+  lean_step = !dbg_switch(SW_NO_LEAN_STEP);
+  recompute_dt = !dbg_switch(SW_NO_RECOMPUTE_DT);
   nhvec = 0;
   nw = p->nwcon;
   has_w = false;
@@ -56,20 +56,10 @@ InteriorPoint::InteriorPoint(Problem *p)
   for (int i = 0; i < 7; i++) w_sums[i] = 0.0;
   for (int i = 0; i < 5; i++) w_maxs[i] = 0.0;
   // debugging / test switch: re-measure P^T px with explicit mdot passes instead of W-based algebra
-  if (getenv("PAROPT_AMD_EXPLICIT_DOTS")) analytic_panel_dots = false;
-  if (getenv("PAROPT_AMD_NO_FUSED_DOTS")) fused_dots = false;
-  fused_tdots = !getenv("PAROPT_AMD_NO_FUSED_TDOTS");
-  recompute_first_step = !getenv("PAROPT_AMD_NO_RECOMPUTE");
-  fuse_mult_update = !getenv("PAROPT_AMD_NO_FUSED_UPDATE");
-  fast_yqn_w = !getenv("PAROPT_AMD_NO_FAST_YQN_W");
-  w_lean = !getenv("PAROPT_AMD_NO_W_LEAN");
-  spec_mu_on = !getenv("PAROPT_AMD_NO_SPEC_MU");
-  recompute_rhs = recompute_first_step && !getenv("PAROPT_AMD_NO_RECOMPUTE_RHS");
-  // Off by default: leaving the L-SR1 columns unformed saves the Gram pass 0.6 ms (its ten output streams) but costs
-  // the two solve passes ten more input streams each, +1.2 ms at n = 50 M; kept as a switch.
-  virtual_z = recompute_rhs && getenv("PAROPT_AMD_VIRTUAL_Z") != nullptr;
-  use_acz = !getenv("PAROPT_AMD_NO_ACZ");
-  use_ztpx_hint = !getenv("PAROPT_AMD_NO_ZTS_HINT");
+  if (dbg_switch(SW_EXPLICIT_DOTS)) analytic_panel_dots = false;
+  recompute_first_step = !dbg_switch(SW_NO_RECOMPUTE);
+  fuse_mult_update = !dbg_switch(SW_NO_FUSED_UPDATE);
+  recompute_rhs = recompute_first_step && !dbg_switch(SW_NO_RECOMPUTE_RHS);
   use_lower = prob->useLowerBounds();
   use_upper = prob->useUpperBounds();
   vars.resize(c);
@@ -193,7 +183,7 @@ Bounds InteriorPoint::bounds() const {
   b.max_bound = options.real("max_bound_value");
   b.use_lower = use_lower;
   b.use_upper = use_upper;
-  if (dbg_switch(SW_UNIFORM_BOUNDS, nullptr, 1) != 0) {
+  if (dbg_switch(SW_UNIFORM_BOUNDS) != 0) {
     b.lb_uni = bounds_uni[0];
     b.ub_uni = bounds_uni[1];
     b.lb_c = bounds_val[0];
@@ -415,7 +405,7 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   double *out = res_out;  // a member: inside a BatchScope the values arrive at the flush (after_reduce below)
   // speculative maxima for the next barrier parameter (see ip.hpp): only beside the norms of the CURRENT one
-  const bool spec = vectors && spec_enabled && spec_mu_on && !has_w && mu == barrier_param;
+  const bool spec = vectors && spec_enabled && !has_w && mu == barrier_param;
   const double mu2 = spec ? nextMonotoneMu() : 0.0;
   const double beta_mu2 = spec ? options.real("rel_bound_barrier") * mu2 : -1.0;
   spec_valid = false;
@@ -431,7 +421,7 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
     // A problem that declared its dense constraints linear (constant Jacobian): A^T z is kept in `acz` and
     // follows the multiplier steps (computeStepAndUpdate), so the residual does not stream the c constraint
     // gradients; it is rebuilt from the gradients every kAczRefresh uses to bound the round-off drift.
-    if (prob->linear_constraints && ac_valid && c > 0 && use_acz) {
+    if (prob->linear_constraints && ac_valid && c > 0) {
       if (!acz) acz = vec_new(ctx, n);
       if (!acz) return PO_ERR_HIP;
       if (!acz_valid || acz_age >= kAczRefresh) {
@@ -465,8 +455,8 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
       // No quasi-Newton update follows (a fixed approximation, the sequential linear method): the diagonal of the next
       // KKT system is known already, so this pass also leaves Dinv and t = Dinv o d1 of the next first solve behind
       // (spec_dt_*: setUpKKTSystem skips its pass over the bound data when diagonal and barrier parameter still match)
-      const bool spec_dt = spec_dt_want && !has_w && fused_tdots && !options.integer("use_diag_hessian") &&
-                           dbg_switch(SW_SPEC_DT, "PAROPT_AMD_SPEC_DT", 1) != 0;
+      const bool spec_dt = spec_dt_want && !has_w && !options.integer("use_diag_hessian") &&
+                           dbg_switch(SW_SPEC_DT) != 0;
       const double sdiag = spec_dt ? options.real("qn_sigma") + ((qn && !options.integer("sequential_linear_method"))
                                                                     ? qn->diag() : 0.0) : 0.0;
       const double sbmu = spec_dt ? options.real("rel_bound_barrier") * spec_dt_mu : 0.0;
@@ -609,11 +599,11 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // built now (in the same pass over the bound data as Dinv) and rides through the Gram pass as one more,
   // pre-weighted, column, so that P^T t -- the mdot pass at the head of solveKKT -- comes out of the pass over P
   // that the Schur complements need anyway.
-  const bool fuse_t = rhs_mu && fused_tdots && !has_w && c + (qn && use_qn && !diag_only ? qn->size() : 0) > 0;
+  const bool fuse_t = rhs_mu && !has_w && c + (qn && use_qn && !diag_only ? qn->size() : 0) > 0;
   t_is_plain_dinv_d1 = false;
   // sparse constraints: the RAW right-hand side d1 of the first solve (the block solve applies to it) comes out of
   // the same pass over the bound data as Dinv (round 4; it is used below when the fused first solve is taken)
-  const bool raw_d1_w = has_w && rhs_mu && fused_tdots && !corrector_active;
+  const bool raw_d1_w = has_w && rhs_mu && !corrector_active;
   const bool have_spec_dt = spec_dt_valid;
   spec_dt_valid = false;  // consumed here, or overwritten below
   if (fuse_t && have_spec_dt && !use_hdiag && spec_dt_diag == b0 + sigma &&
@@ -648,14 +638,8 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
     for (Vec *a : Ac) P2.push_back(a->d);
     if (fuse_t) P2.push_back(tvec->d);
     std::vector<double> W2((size_t)mt * mt, 0.0);
-    // Leave the columns unformed when the solves that follow take them unformed too (solveKKT): the ten output
-    // streams of the formation cost as much as forty input streams.  Any other consumer forms them on demand
-    // (CompactQuasiNewton::zPointers).
-    const bool leave_unformed = virtual_z && allow_virtual_z && fuse_t && k <= kMaxVirt;
-    std::vector<double *> Znull(Zo.size(), nullptr);
-    PO_TRY(k_wgram(ctx, Dinv->d, P2.data(), mt, n, W2.data(), Sp.data(), leave_unformed ? Znull.data() : Zo.data(), k,
-                   b0z, fuse_t ? 1 : 0));
-    if (!leave_unformed) qn->pendingZDone();
+    PO_TRY(k_wgram(ctx, Dinv->d, P2.data(), mt, n, W2.data(), Sp.data(), Zo.data(), k, b0z, fuse_t ? 1 : 0));
+    qn->pendingZDone();
     W.assign((size_t)m2 * m2, 0.0);
     auto perm = [&](int i) { return i < c ? k + i : i - c; };  // index in [Ac | Z] -> index in [Z | Ac]
     for (int j = 0; j < m2; j++)
@@ -684,7 +668,7 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   bool t0_ready = fuse_z && fuse_t;
   if (has_w) {  // Cw = 1/(sw/zsw + tw/ztw + Aw Dinv Aw^T) (:1912-1930)
     PO_TRY(prob->sparseFactorFromSlacks(x, Dinv, wv(), Cw));  // Cdiag (:1912-1927) + mat->factor (:1930)
-    fuse_tw = rhs_mu && fused_tdots && m > 0 && m + 1 <= kWgramMaxVecs && !corrector_active;
+    fuse_tw = rhs_mu && m > 0 && m + 1 <= kWgramMaxVecs && !corrector_active;
     if (fuse_tw) {
       PO_TRY(computeResidualW(*rhs_mu, true, true));  // ... with d2 of the block solve below (wd2)
       if (!raw_d1_w)
@@ -737,7 +721,7 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // test aid: a relative perturbation of 1e-9 in one Gram entry, which the known-answer tests must detect
   // (tests/test_gpu_kat.py::test_kat_detects_a_perturbed_gram)
   // -- reachable only through po_debug_set_switch and only inside po_ip_debug_kkt (no environment variable)
-  if (m > 1 && debug_keep_schur && dbg_switch(SW_PERTURB_W, nullptr, 0) != 0) {
+  if (m > 1 && debug_keep_schur && dbg_switch(SW_PERTURB_W) != 0) {
     W[1] *= 1.0 + 1e-9;
     W[m] = W[1];
   }
@@ -791,7 +775,7 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
   }
   const int m = c + k;
   // The panel [Ac | Z] is only asked for when a pass needs it: zPointers() FORMS unformed L-SR1 columns (one pass
-  // over 3k vectors, k of them written), and the fused passes below take them unformed (Y_j - b0 S_j in registers).
+  // over 3k vectors, k of them written).
   std::vector<const double *> P;
   bool have_panel = false;
   auto need_panel = [&]() {
@@ -893,28 +877,8 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
       }
     }
   }
-  // Unformed L-SR1 columns (setUpKKTSystem left them unformed on purpose): the two fused passes take the panel as
-  // [Y_0..Y_{k-1} | Ac] with the S partners beside it; coefficients and products are permuted on the host.
-  std::vector<const double *> Yp, Sp;
-  std::vector<double *> Zo;
-  double b0z = 0.0;
-  const bool first_fused = fuse && fused_dots && m > 0 && !corr;
-  const bool virt = virtual_z && recompute_first_step && recompute_rhs && !have_panel && k > 0 && k <= kMaxVirt &&
-                    (first_fused || (refine_pass && step_deferred && virt_first)) && qn &&
-                    qn->pendingZ(&Yp, &Sp, &Zo, &b0z) && (int)Yp.size() == k;
-  std::vector<const double *> Pv;
-  auto to_virt = [&](const std::vector<double> &a) {  // [Ac | Z] order -> [Z | Ac] order
-    std::vector<double> r(m > 0 ? m : 1, 0.0);
-    for (int j = 0; j < k; j++) r[j] = a[c + j];
-    for (int i = 0; i < c; i++) r[k + i] = a[i];
-    return r;
-  };
-  if (virt) {
-    Pv = Yp;
-    for (Vec *a : Ac) Pv.push_back(a->d);
-  } else {
-    need_panel();
-  }
+  const bool first_fused = fuse && m > 0 && !corr;
+  need_panel();
   if (first_fused) {
     // one pass: t' = refinement rhs and P^T t' for the refinement solve.  The step itself (px, pzl, pzu, A^T pz) is
     // NOT stored: the refinement pass recomputes it from (t, alpha) in registers (k_solve2r) -- four output streams
@@ -925,24 +889,12 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
     // again from the residual coefficients (an output stream costs about four input streams)
     double *tp_out = !defer ? tvec->d : (recompute_rhs ? nullptr : xt->d);
     // Dinv and t re-formed in the element epilogue from the bound data and rx it loads anyway (same bits)
-    const bool redo_dt1 = recompute_dt && defer && recompute_rhs && first_t_recomputable &&
-                          dbg_switch(SW_REDO_DT1, nullptr, 1) != 0;
+    const bool redo_dt1 = recompute_dt && defer && recompute_rhs && first_t_recomputable;
     const double *t_in = redo_dt1 ? nullptr : tvec->d;
-    if (virt) {
-      const std::vector<double> av = to_virt(alpha), cv = to_virt(coef);
-      PO_TRY(k_solve2_dots(ctx, bounds(), t_in, Dinv->d, av.data(), cv.data(), Pv.data(), m, beta_mu, tau, rx->d,
-                           diag, n, px->d, pzl->d, pzu->d, tp_out, vA->d, c, out.data(), nullptr, 0, k, Sp.data(), k,
-                           b0z, t0_diag));
-      tdots.assign(m, 0.0);
-      for (int j = 0; j < k; j++) tdots[c + j] = out[j];
-      for (int i = 0; i < c; i++) tdots[i] = out[k + i];
-    } else {
-      PO_TRY(k_solve2_dots(ctx, bounds(), t_in, Dinv->d, alpha.data(), coef.data(), P.data(), m,
-                           beta_mu, tau, rx->d, diag, n, px->d, pzl->d, pzu->d, tp_out, vA->d, c,
-                           out.data(), nullptr, defer ? 0 : 1, 0, nullptr, 0, 0.0, t0_diag));
-      tdots.assign(out.begin(), out.begin() + m);
-    }
-    virt_first = virt;
+    PO_TRY(k_solve2_dots(ctx, bounds(), t_in, Dinv->d, alpha.data(), coef.data(), P.data(), m, beta_mu, tau, rx->d,
+                         diag, n, px->d, pzl->d, pzu->d, tp_out, vA->d, c, out.data(), nullptr, defer ? 0 : 1, 0,
+                         t0_diag));
+    tdots.assign(out.begin(), out.begin() + m);
     tdots_valid = true;
     step_mins[0] = out[m];
     step_mins[1] = out[m + 1];
@@ -956,31 +908,22 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
     step_deferred = false;
     // the same sweep takes the sums the complementarity check of scaleKKTStep and the merit derivative need of the
     // final step (see solve2r_kernel): no separate pass over the step afterwards
-    const bool take_merit = fuse_merit && recompute_rhs && !corr && dbg_switch(SW_FUSED_MERIT, nullptr, 1) != 0;
+    const bool take_merit = fuse_merit && recompute_rhs && !corr;
     const double *gm = take_merit ? g->d : nullptr;
     double *mo = take_merit ? fused_merit : nullptr;
     // lean step: (pzl, pzu) stay in registers; their only consumer left, the multiplier update, re-forms them
-    const bool lean = lean_step && lean_step_allowed && take_merit && iterate_logs_valid &&
-                      dbg_switch(SW_LEAN_STEP, nullptr, 1) != 0;
+    const bool lean = lean_step && lean_step_allowed && take_merit && iterate_logs_valid;
     double *pzl_out = lean ? nullptr : pzl->d, *pzu_out = lean ? nullptr : pzu->d;
     // Dinv and the first right-hand side t re-formed in registers from data the pass loads anyway (same bits)
-    const bool redo_dt = recompute_dt && recompute_rhs && first_t_recomputable &&
-                         dbg_switch(SW_REDO_DT, nullptr, 1) != 0;
+    const bool redo_dt = recompute_dt && recompute_rhs && first_t_recomputable;
     const double *t1p = redo_dt ? nullptr : tvec->d;
     if (lean) {
       pz_stored = false;
       step_beta_mu = beta_mu;
     }
-    if (virt) {
-      const std::vector<double> a1v = to_virt(alpha_first), a2v = to_virt(alpha), crv = to_virt(coef_first);
-      PO_TRY(k_solve2r(ctx, bounds(), t1p, nullptr, Dinv->d, a1v.data(), a2v.data(), Pv.data(), m, beta_mu, tau, n,
-                       px->d, pzl_out, pzu_out, vA->d, c, step_mins, crv.data(), rx->d, diag_first, k, Sp.data(), k,
-                       b0z, gm, mo, t0_diag));
-    } else {
-      PO_TRY(k_solve2r(ctx, bounds(), t1p, recompute_rhs ? nullptr : xt->d, Dinv->d, alpha_first.data(),
-                       alpha.data(), P.data(), m, beta_mu, tau, n, px->d, pzl_out, pzu_out, vA->d, c, step_mins,
-                       coef_first.data(), rx->d, diag_first, 0, nullptr, 0, 0.0, gm, mo, t0_diag));
-    }
+    PO_TRY(k_solve2r(ctx, bounds(), t1p, recompute_rhs ? nullptr : xt->d, Dinv->d, alpha_first.data(), alpha.data(),
+                     P.data(), m, beta_mu, tau, n, px->d, pzl_out, pzu_out, vA->d, c, step_mins, coef_first.data(),
+                     rx->d, diag_first, 0, gm, mo, t0_diag));
     if (take_merit) {
       after_reduce(ctx, [this] {
         step_mins[0] = fused_merit[7];
@@ -1334,11 +1277,7 @@ int InteriorPoint::debugKKT(double mu, int mode, double tau) {
   } else {
     PO_TRY(createQuasiNewton());
     PO_TRY(computeResidual(mu, true));
-    allow_virtual_z = analytic_panel_dots && fused_dots && options.integer("iterative_refinement_steps") == 1 &&
-                      !options.integer("use_diag_hessian") && !options.integer("sequential_linear_method");
-    const int setup_rc = setUpKKTSystem(true, false, &mu);
-    allow_virtual_z = false;
-    PO_TRY(setup_rc);
+    PO_TRY(setUpKKTSystem(true, false, &mu));
     lean_step_allowed = false;  // (pzl, pzu) are stored: the test reads them
     PO_TRY(computeKKTStepWithRefinement(mu, true, tau));
     PO_TRY(batch_flush(ctx));
@@ -1365,7 +1304,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
     if (step.zt[i] < 0.0) max_z = std::min(max_z, -vars.zt[i] / step.zt[i]);
   }
   double cs[2];
-  if (fused_merit_valid && !has_w && dbg_switch(SW_MPC_POLY, "PAROPT_AMD_MPC_POLY", 1) != 0) {
+  if (fused_merit_valid && !has_w && dbg_switch(SW_MPC_POLY) != 0) {
     // the refinement pass of the affine solve took the complementarity polynomial of its step (solve2r_kernel):
     // S00 + ax S10 + az S01 + ax az S11 at the probe lengths, S00 / the bound count from the residual pass of this
     // iterate -- no pass over the step and no host round trip (round 6; scaleKKTStep uses the same form)
@@ -1400,7 +1339,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
     // affine step (:1729-1789); no refinement with the corrector (:5040-5041)
     // (one-pass corrector right-hand side + corrector solve with the merit sums: see solveKKT)
     corrector_fused = !has_w && c + wk >= 1 && c + wk <= kCorrDotsMax &&
-                      dbg_switch(SW_MPC_FUSE, "PAROPT_AMD_MPC_FUSE", 1) != 0;
+                      dbg_switch(SW_MPC_FUSE) != 0;
     if (!corrector_fused) PO_TRY(k_corrector(ctx, bounds(), px->d, pzl->d, pzu->d, n, s_qn->d, y_qn->d));
     denseResidual(barrier_param, res);
     for (int i = 0; i < c; i++) {
@@ -1863,7 +1802,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   // formed here, from the final step, in one pass over the c constraint gradients: two panel passes, two sparse
   // transposes and the separate multiplier update disappear.  (Not with the linear-constraint recurrence, whose
   // `acz` follows the dense part of this vector alone.)
-  const bool fast_w = has_w && do_qn && analytic_panel_dots && fast_yqn_w && !prob->linear_constraints;
+  const bool fast_w = has_w && do_qn && analytic_panel_dots && !prob->linear_constraints;
   const bool fast_yqn = do_qn && analytic_panel_dots && ((!has_w && vA_valid) || fast_w);
   if (fast_w) {
     // vA <- sz Aw^T pzw + sum_j step.z[j] A_j   (step.z already carries sz: scaleKKTStep)
@@ -2005,7 +1944,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     if (rcc != 0) return PO_ERR_USER;
     // Z^T s = alpha sx Z^T px is known from the solves (ptpx) when the step came from this very panel
     const int kz = qn->size();
-    if (analytic_panel_dots && ptpx_valid && use_ztpx_hint && kz == wk && kz > 0 && (int)ptpx.size() == c + kz &&
+    if (analytic_panel_dots && ptpx_valid && kz == wk && kz > 0 && (int)ptpx.size() == c + kz &&
         !inexact_newton_step && !prob->quasiNewtonCorrectionMayChangeStep()) {
       std::vector<double> zts(kz);
       for (int j = 0; j < kz; j++) zts[j] = alpha * sx * ptpx[c + j];
@@ -2355,14 +2294,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
       // nothing to do: computeKKTGMRESStep left the step in (px, pzl, pzu, step)
     } else {
     const double rhs_mu = mehrotra ? 0.0 : barrier_param;  // of the solve that follows
-    // unformed L-SR1 columns may stay unformed when every pass of this iteration that reads the panel is one of the
-    // fused ones: a single quasi-Newton solve with one refinement step, no corrector solve
-    allow_virtual_z = !mehrotra && use_qn && !diagonal_quasi_newton_step && analytic_panel_dots && fused_dots &&
-                      options.integer("iterative_refinement_steps") == 1 && !options.integer("use_diag_hessian") &&
-                      !options.integer("sequential_linear_method");
-    const int setup_rc = setUpKKTSystem(use_qn, diagonal_quasi_newton_step != 0, &rhs_mu);
-    allow_virtual_z = false;
-    PO_TRY(setup_rc);
+    PO_TRY(setUpKKTSystem(use_qn, diagonal_quasi_newton_step != 0, &rhs_mu));
     phaseEnd("setup_kkt");
     if (!mehrotra) {
       // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
@@ -2514,8 +2446,8 @@ void InteriorPoint::flushHistory() {
   // debugging aid: PAROPT_AMD_DUMP_LONG_SOLVES=<N> prints the head and tail of the iteration table of
   // every solve that took at least N major iterations (e.g. a stalled trust-region subproblem)
   if (ctx->rank == 0) {
-    const char *dbg = getenv("PAROPT_AMD_DUMP_LONG_SOLVES");
-    if (dbg && niter >= atoi(dbg)) {
+    const int dump_from = dbg_switch(SW_DUMP_LONG_SOLVES);
+    if (dump_from >= 0 && niter >= dump_from) {
       const size_t len = history.size();
       fprintf(stderr, "---- paropt_amd: solve with %d iterations ----\n%s\n   [...]\n%s\n", niter,
               history.substr(0, std::min<size_t>(len, 6000)).c_str(),

@@ -145,7 +145,7 @@ class InteriorPoint {
   // is a packet between two kernels and costs the stream dispatch latency -- 850 / 853 against 863 / 866 inner it/s
   // at config 5 in one call (5-6 callbacks per 1.2 ms inner iteration), nothing measurable at n >= 10 M.
   // po_ip_set_callback_timing switches it on (bench.py does, for the figure it reports).
-  bool user_timing = getenv("PAROPT_AMD_USER_TIMING") != nullptr;
+  bool user_timing = dbg_switch(SW_USER_TIMING) != 0;
 
   // step storage (exposed for the single-step known-answer tests)
   Vec *px, *pzl, *pzu;
@@ -195,7 +195,6 @@ class InteriorPoint {
   int norm_type;          // 0 infinity, 1 l1, 2 l2 (ParOptNormType)
   std::vector<double> tdots;  // P^T t' produced by the fused first solve pass
   bool tdots_valid;
-  bool fused_dots;        // use k_solve2_dots (switch PAROPT_AMD_NO_FUSED_DOTS=1 to compare)
 
   // ---- second-order information (ip_gmres.cpp) ----
   Vec *hdiag;                  // use_diag_hessian: diagonal of the Lagrangian Hessian (zero until evaluated)
@@ -256,8 +255,8 @@ class InteriorPoint {
   double res_out[13] = {0}, wres_out[12] = {0};  // landing area of the residual reductions (see after_reduce)
   // Monotone barrier strategy with the infinity norm (round 4): the residual pass also takes max|rzl|, max|rzu| for the
   // barrier parameter the strategy would switch to (a function of the current one alone), so that the switch needs
-  // neither the mu-only pass over the bound data nor its host synchronisation (PAROPT_AMD_NO_SPEC_MU=1 restores it)
-  bool spec_mu_on = true, spec_enabled = false, spec_valid = false;
+  // neither the mu-only pass over the bound data nor its host synchronisation
+  bool spec_enabled = false, spec_valid = false;
   double spec_mu = 0.0, spec_max[2] = {0.0, 0.0};
   double nextMonotoneMu() const;
   WVars wv() const;
@@ -329,17 +328,16 @@ class InteriorPoint {
   // A^T z of a problem with linear dense constraints, kept by recurrence (computeResidual / computeStepAndUpdate)
   static const int kAczRefresh = 16;
   Vec *acz = nullptr;
-  bool acz_valid = false, use_acz = true, use_ztpx_hint = true;
+  bool acz_valid = false;
   int acz_age = 0;
   // P^T t of the first solve, produced by the Gram pass of setUpKKTSystem (see there)
   bool fuse_mult_update = true;
-  bool fast_yqn_w = true;  // sparse constraints: y_qn from the residuals (PAROPT_AMD_NO_FAST_YQN_W=1 restores the passes)
-  // sparse constraints, round 4 ("lean" solve passes, PAROPT_AMD_NO_W_LEAN=1 restores the stored forms): the fused
+  // sparse constraints, round 4: y_qn from the residuals, and "lean" solve passes: the fused
   // first pass stores px only (px_first_only), the refinement pass re-forms the first bound-multiplier steps from it,
   // takes the complementarity / merit sums of the final step (fused_merit, as on the dense path) and, in the plain
   // quasi-Newton iteration, stores px only again; the sparse blocks' share of the complementarity polynomial comes
   // out of the step kernel (w_comp_poly) and the sparse merit sums ride in the same batch (w_merit_cache, sx = 1)
-  bool w_lean = true, px_first_only = false;
+  bool px_first_only = false;
   double w_step_out[5] = {0, 0, 0, 0, 0}, w_comp_poly[3] = {0, 0, 0}, w_merit_cache[10] = {0};
   bool w_comp_valid = false, w_merit_cache_valid = false;
   bool s_qn_from_trial = false;  // s_qn holds s_qn_a * px, written by the last trial pass of the line search
@@ -348,9 +346,7 @@ class InteriorPoint {
   std::vector<double> alpha_first, coef_first;  // coefficients of that first pass (solve, refinement residual)
   double diag_first = 0.0;
   bool recompute_rhs = true;  // ... and the refinement right-hand side is recomputed as well
-  // unformed L-SR1 columns are consumed unformed by the Gram pass and both solve passes (never written)
-  bool virtual_z = true, virt_first = false, allow_virtual_z = false;
-  bool fused_tdots = true, t0_valid = false;
+  bool t0_valid = false;
   double t0_mu = 0.0;
   std::vector<double> t0dots;  // Ac holds the Jacobian of a problem with linear_constraints
 };

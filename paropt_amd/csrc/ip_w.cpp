@@ -222,7 +222,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   // before the axpy pass starts, and so is the sparse multiplier step pzw (it depends on wyw only), so ONE pass
   // over P writes the step, the RAW right-hand side d1' of the refinement solve (its design rows, :1451-1483, with
   // the extra column Aw^T pzw) and the panel products of Dinv o d1'.
-  const bool fuse = fuse_residual && !refine_pass && fused_dots && analytic_panel_dots && kq == k && m > 0 &&
+  const bool fuse = fuse_residual && !refine_pass && analytic_panel_dots && kq == k && m > 0 &&
                     (int)Uw.size() >= m && panel_valid && panel_plain && !cl &&
                     !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
   if (fuse) {
@@ -232,8 +232,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
     // the two extra columns Aw^T wtmp2 (coefficient 1 in the step's row sum) and Aw^T pzw (1 in the residual's): n-sized
     // vectors from Problem::setSparseJacobianTranspose, or -- structured problems -- described and formed by the pass
     GroupCols2 gcs;
-    static const bool s2d_grouped = getenv("PAROPT_AMD_GROUP_COLS_S2D") ? atoi(getenv("PAROPT_AMD_GROUP_COLS_S2D")) != 0 : true;
-    const bool grouped = s2d_grouped && prob->sparseTransposeColumn(1.0, x, wtmp2, &gcs.g[0]);
+    const bool grouped = prob->sparseTransposeColumn(1.0, x, wtmp2, &gcs.g[0]);
     if (!grouped && prob->setSparseJacobianTranspose(1.0, x, wtmp2, d1v) != 0) return PO_ERR_USER;
     // sparse blocks of the step first: pzw = wstepv[0] feeds the residual column Aw^T pzw (its minima wait for
     // those of the design blocks unless user code runs in between)
@@ -273,13 +272,12 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
     std::vector<double> so(m + 4, 0.0);
     // the raw right-hand side lands in y_qn (free while no corrector is active: y_qn is rebuilt from scratch by
     // computeStepAndUpdate) -- d1v is one of the columns being read -- and the two exchange buffers afterwards.
-    // Of the step only px is stored (w_lean): the refinement's sparse rows need Aw px as a vector, the bound-
+    // Of the step only px is stored (store_step 2): the refinement's sparse rows need Aw px as a vector, the bound-
     // multiplier steps are re-formed from px by the refinement pass (two output streams less)
-    const int sstep = w_lean ? 2 : 1;
     PO_TRY(k_solve2_dots(ctx, bounds(), tvec->d, Dinv->d, a1.data(), c2.data(), P1.data(), np1, beta_mu, tau,
-                         rx->d, diag, n, px->d, pzl->d, pzu->d, nullptr, nullptr, 0, so.data(), y_qn->d, sstep, 0,
-                         nullptr, 0, 0.0, 0.0, grouped ? &gcs : nullptr));
-    px_first_only = sstep == 2;
+                         rx->d, diag, n, px->d, pzl->d, pzu->d, nullptr, nullptr, 0, so.data(), y_qn->d, 2, 0,
+                         0.0, grouped ? &gcs : nullptr));
+    px_first_only = true;
     std::swap(d1v->d, y_qn->d);
     PO_TRY(minbatch.end());
     tdots.assign(so.begin(), so.begin() + m);
@@ -311,12 +309,12 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
       // solves) and the two buffers are exchanged.  Lean step: (pzl, pzu) are not stored either -- their only
       // consumer left is the multiplier update of computeStepAndUpdate, which re-forms them (kkt_res_update_kernel)
       const bool take_merit = fuse_merit && !cl;
-      const bool lean = take_merit && lean_step && lean_step_allowed && iterate_logs_valid && fast_yqn_w &&
+      const bool lean = take_merit && lean_step && lean_step_allowed && iterate_logs_valid &&
                         !prob->linear_constraints && options.integer("iterative_refinement_steps") == 1;
       std::vector<double> azero(m + 1, 0.0);
       PO_TRY(k_solve2r(ctx, bounds(), px->d, tvec->d, Dinv->d, azero.data(), a1.data(), P1.data(), (int)P1.size(), beta_mu,
                        tau, n, xt->d, lean ? nullptr : pzl->d, lean ? nullptr : pzu->d, nullptr, 0, mins_x, nullptr,
-                       nullptr, 0.0, 0, nullptr, 0, 0.0, take_merit ? g->d : nullptr,
+                       nullptr, 0.0, 0, take_merit ? g->d : nullptr,
                        take_merit ? fused_merit : nullptr, 0.0, grouped ? &gcol : nullptr, 0.0, 1.0));
       std::swap(px->d, xt->d);
       if (lean) {

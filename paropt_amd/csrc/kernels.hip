@@ -244,8 +244,6 @@ int launch_reduce_final_multi(Ctx *c, const Ctx::PendingRed *pend, int count) {
 // swept in-process at config 3 (profiles/r03_ab_bpc.txt): the panel-streaming kernels (c+k+~10 concurrent
 // streams per thread) are fastest at 2 per CU, the few-stream kernels at 4.
 int grid_for(Ctx *c, int64_t n, int bpc) {
-  if (bpc == kBpcPanel) bpc = dbg_switch(SW_BPC3, "PAROPT_AMD_BPC_PANEL", bpc);
-  else if (bpc == kBpcStream) bpc = dbg_switch(SW_BPC4, "PAROPT_AMD_BPC_STREAM", bpc);
   const int64_t npairs = (n + 1) >> 1;
   int64_t blocks = (npairs + kBlock - 1) / kBlock;
   const int64_t cap = (int64_t)c->num_cu * bpc;
@@ -460,22 +458,10 @@ __device__ __forceinline__ void panel_sum2(const PtrTable &P, const CoefTable &a
 template <int B>
 __device__ __forceinline__ void panel_batch3(const PtrTable &P, const CoefTable &a, const CoefTable &b2,
                                              const CoefTable &c3, int j, int64_t q, f64x2 &acc, f64x2 &acc2,
-                                             f64x2 &acc3, const VirtCols &vc) {
+                                             f64x2 &acc3) {
   f64x2 v[B];
 #pragma unroll
   for (int u = 0; u < B; u++) v[u] = ld_stream(P.p[j + u] + 2 * q);
-  if (j < vc.count) {  // unformed L-SR1 columns: Z = Y - b0 S in registers
-    f64x2 w[B];
-#pragma unroll
-    for (int u = 0; u < B; u++) w[u] = ld_stream(vc.s[(j + u) < vc.count ? (j + u) : 0] + 2 * q);
-#pragma unroll
-    for (int u = 0; u < B; u++) {
-      if (j + u < vc.count) {
-        v[u].x -= vc.b0 * w[u].x;
-        v[u].y -= vc.b0 * w[u].y;
-      }
-    }
-  }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int u = 0; u < B; u++) {
@@ -491,18 +477,18 @@ __device__ __forceinline__ void panel_batch3(const PtrTable &P, const CoefTable 
 // columns [j, nv) added onto (s1, s2, s3)
 __device__ __forceinline__ void panel_sum3(const PtrTable &P, const CoefTable &a, const CoefTable &b2,
                                            const CoefTable &c3, int nv, int64_t q, double2 &s1, double2 &s2,
-                                           double2 &s3, int j, const VirtCols &vc) {
+                                           double2 &s3, int j) {
   f64x2 acc = (f64x2){s1.x, s1.y}, acc2 = (f64x2){s2.x, s2.y}, acc3 = (f64x2){s3.x, s3.y};
-  for (; j + 8 <= nv; j += 8) panel_batch3<8>(P, a, b2, c3, j, q, acc, acc2, acc3, vc);
+  for (; j + 8 <= nv; j += 8) panel_batch3<8>(P, a, b2, c3, j, q, acc, acc2, acc3);
   if (j + 4 <= nv) {
-    panel_batch3<4>(P, a, b2, c3, j, q, acc, acc2, acc3, vc);
+    panel_batch3<4>(P, a, b2, c3, j, q, acc, acc2, acc3);
     j += 4;
   }
   if (j + 2 <= nv) {
-    panel_batch3<2>(P, a, b2, c3, j, q, acc, acc2, acc3, vc);
+    panel_batch3<2>(P, a, b2, c3, j, q, acc, acc2, acc3);
     j += 2;
   }
-  if (j < nv) panel_batch3<1>(P, a, b2, c3, j, q, acc, acc2, acc3, vc);
+  if (j < nv) panel_batch3<1>(P, a, b2, c3, j, q, acc, acc2, acc3);
   s1 = make_double2(acc.x, acc.y);
   s2 = make_double2(acc2.x, acc2.y);
   s3 = make_double2(acc3.x, acc3.y);
@@ -641,25 +627,6 @@ __global__ void __launch_bounds__(kBlock)
     }
   }
 }
-// the same with the columns spread over blockIdx.y: every workgroup streams ONE column (a contiguous read and a
-// contiguous write stream per workgroup, like the plain copy kernel) instead of touching all nv columns per row pair
-__global__ void __launch_bounds__(kBlock)
-    panel_lincomb2d_kernel(PtrTableW dst, double a, PtrTable X, double b, PtrTable Y, int has_y, int64_t n) {
-  const int j = blockIdx.y;
-  const double *__restrict__ xp = X.p[j];
-  const double *__restrict__ yp = Y.p[j];
-  double *__restrict__ dp = dst.p[j];
-  PO_PAIR_LOOP(q, n) {
-    const f64x2 xv = ld_stream(xp + 2 * q);
-    double2 r = make_double2(a * xv.x, a * xv.y);
-    if (has_y) {
-      const f64x2 yv = ld_stream(yp + 2 * q);
-      r.x += b * yv.x;
-      r.y += b * yv.y;
-    }
-    st2(dp, q, n, r);
-  }
-}
 
 int k_panel_lincomb(Ctx *c, double *const *dst, double a, const double *const *X, double b,
                     const double *const *Y, int nv, int64_t n) {
@@ -673,35 +640,9 @@ int k_panel_lincomb(Ctx *c, double *const *dst, double a, const double *const *X
     for (int j = 0; j < kMaxPanel; j++) d.p[j] = j < w ? dst[j0 + j] : nullptr;
     fill_tables(nullptr, X + j0, w, &ct, &x);
     fill_tables(nullptr, Y ? Y + j0 : nullptr, Y ? w : 0, &ct, &y);
-    // A/B (profiles/r03_ab_lincomb.txt): all columns per row pair (0, default), one column per blockIdx.y (1) and one
-    // launch per column (2) all copy at 5.1-6.2 TB/s with the same run-to-run spread; the best samples of each sit on
-    // the copy ceiling measured in the same process (6.15 TB/s)
-    const int form2d = dbg_switch(SW_LINCOMB_2D, "PAROPT_AMD_LINCOMB_2D", 0);
-    if (form2d == 2) {  // one launch per column (A/B: the plain 1-D copy shape)
-      for (int j = 0; j < w; j++) {
-        PtrTableW d1;
-        PtrTable x1, y1;
-        for (int q = 0; q < kMaxPanel; q++) {
-          d1.p[q] = d.p[j];
-          x1.p[q] = x.p[j];
-          y1.p[q] = y.p[j];
-        }
-        hipLaunchKernelGGL(panel_lincomb2d_kernel, dim3(grid_for(c, n), 1), dim3(kBlock), 0, c->stream, d1, a, x1, b, y1,
-                           Y ? 1 : 0, n);
-        c->n_launches++;
-      }
-      PO_HIP(hipGetLastError());
-    } else if (form2d && w >= 4) {
-      int gx = (c->num_cu * dbg_switch(SW_LINCOMB_BPC, "PAROPT_AMD_LINCOMB_BPC", 8) + w - 1) / w;  // ~8 workgroups per CU in all
-      const int need = grid_for(c, n);
-      if (gx > need) gx = need;
-      if (gx < 1) gx = 1;
-      hipLaunchKernelGGL(panel_lincomb2d_kernel, dim3(gx, w), dim3(kBlock), 0, c->stream, d, a, x, b, y, Y ? 1 : 0, n);
-      c->n_launches++;
-      PO_HIP(hipGetLastError());
-    } else {
-      PO_LAUNCH(panel_lincomb_kernel, grid_for(c, n), d, a, x, b, y, w, Y ? 1 : 0, n);
-    }
+    // (profiles/r03_ab_lincomb.txt: all columns per row pair, one column per blockIdx.y and one launch per column all
+    // copy at 5.1-6.2 TB/s with the same run-to-run spread; the best samples of each sit on the copy ceiling)
+    PO_LAUNCH(panel_lincomb_kernel, grid_for(c, n), d, a, x, b, y, w, Y ? 1 : 0, n);
   }
   return PO_OK;
 }
@@ -1447,7 +1388,7 @@ __global__ void __launch_bounds__(kBlock)
                    const double *__restrict__ dinv, CoefTable a1, CoefTable a2, CoefTable ar, PtrTable P, int nv,
                    double beta_mu, double tau, const double *__restrict__ rx, double diag, int64_t n,
                    double *__restrict__ px, double *__restrict__ pzl, double *__restrict__ pzu,
-                   double *__restrict__ va, int nca, int ca0, VirtCols vc, const double *__restrict__ g,
+                   double *__restrict__ va, int nca, int ca0, const double *__restrict__ g,
                    double dinv_diag, GroupCol gcol, double gc1, double gc2, double *__restrict__ partials) {
   __shared__ double sm[4 * 8];
   double mins[2] = {1.0, 1.0};
@@ -1460,10 +1401,10 @@ __global__ void __launch_bounds__(kBlock)
     double2 a1A = zero2, a2A = zero2, acc1 = zero2, acc2 = zero2, arA = zero2, accr = zero2;
     if (RECT) {
       // the constraint columns [ca0, ca0 + nca) are summed apart (A^T pz is kept), the rest in panel order:
-      // [0, ca0) (the quasi-Newton columns when they lead the panel, unformed ones included), then the tail
-      panel_sum3(P, a1, a2, ar, ca0 + nca, q, a1A, a2A, arA, ca0, vc);
-      if (ca0 > 0) panel_sum3(P, a1, a2, ar, ca0, q, acc1, acc2, accr, 0, vc);
-      panel_sum3(P, a1, a2, ar, nv, q, acc1, acc2, accr, ca0 + nca, vc);
+      // [0, ca0) (the quasi-Newton columns when they lead the panel), then the tail
+      panel_sum3(P, a1, a2, ar, ca0 + nca, q, a1A, a2A, arA, ca0);
+      if (ca0 > 0) panel_sum3(P, a1, a2, ar, ca0, q, acc1, acc2, accr, 0);
+      panel_sum3(P, a1, a2, ar, nv, q, acc1, acc2, accr, ca0 + nca);
       accr.x += arA.x;
       accr.y += arA.y;
     } else {
@@ -1563,9 +1504,9 @@ __global__ void __launch_bounds__(kBlock)
 int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const double *dinv, const double *a1,
               const double *a2, const double *const *P, int nv, double beta_mu, double tau, int64_t n, double *px,
               double *pzl, double *pzu, double *va, int nca, double out[2], const double *ar, const double *rx,
-              double diag, int ca0, const double *const *vs, int nvirt, double b0v, const double *g,
-              double *merit_out, double dinv_diag, const GroupCol *gcol, double gc1, double gc2) {
-  count_bytes(c, nv + nvirt + 7 + (t1 ? 2 : 0) + (pzl ? 2 : 0) + (va ? 1 : 0) + (g ? 1 : 0) - uniform_bound_streams(b), n);
+              double diag, int ca0, const double *g, double *merit_out, double dinv_diag, const GroupCol *gcol,
+              double gc1, double gc2) {
+  count_bytes(c, nv + 7 + (t1 ? 2 : 0) + (pzl ? 2 : 0) + (va ? 1 : 0) + (g ? 1 : 0) - uniform_bound_streams(b), n);
   PO_TRY(gcol_check(gcol, n, "k_solve2r"));
   if (gcol && t2 == nullptr) {
     set_error("k_solve2r: a grouped column is only taken in the stored right-hand side form");
@@ -1588,19 +1529,6 @@ int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const
   fill_tables(a1, P, nv, &ct1, &pt);
   fill_tables(a2, P, nv, &ct2, &pt);
   fill_tables(ar, P, nv, &ctr, &pt);
-  VirtCols vc;
-  vc.count = 0;
-  vc.b0 = b0v;
-  for (int j = 0; j < kMaxVirt; j++) vc.s[j] = nullptr;
-  if (nvirt > 0) {
-    if (nvirt > kMaxVirt || t2 != nullptr || ca0 < nvirt) {
-      set_error("k_solve2r: %d unformed columns (at most %d, leading the panel, recomputed right-hand side only)", nvirt,
-                kMaxVirt);
-      return PO_ERR_ARG;
-    }
-    vc.count = nvirt;
-    for (int j = 0; j < nvirt; j++) vc.s[j] = vs[j];
-  }
   if (t2 != nullptr && ca0 != 0) {
     set_error("k_solve2r: the stored right-hand side form expects the constraint columns first");
     return PO_ERR_ARG;
@@ -1612,21 +1540,21 @@ int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const
     }
     if (g && merit_out) {
       PO_LAUNCH((solve2r_kernel<1, 1>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px,
-                pzl, pzu, va, nca, ca0, vc, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+                pzl, pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
       // {7 sums, 2 minima, 1 maximum} land in merit_out[0..10); the minima are copied to `out` by the caller's hook
       (void)out;
       return reduce_finish(c, grid, 7, 2, 1, merit_out);
     }
     PO_LAUNCH((solve2r_kernel<1, 0>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, vc, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
   } else if (g && merit_out) {
     PO_LAUNCH((solve2r_kernel<0, 1>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, vc, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
     (void)out;
     return reduce_finish(c, grid, 7, 2, 1, merit_out);
   } else {
     PO_LAUNCH((solve2r_kernel<0, 0>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, vc, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
   }
   return reduce_finish(c, grid, 0, 2, 0, out);
 }
@@ -1683,14 +1611,14 @@ int k_solve2(Ctx *c, const Bounds &b, const double *t, const double *dinv, const
 // Each wave reads back only the LDS columns it wrote itself, so two barriers per tile suffice.
 // -------------------------------------------------------------------------------------------------
 constexpr int kS2Tile = 128;
-template <int NPASS, int OCC, int VIRT>
+template <int NPASS, int OCC>
 __global__ void __launch_bounds__(kBlock, OCC)
     solve2_dots_kernel(Bounds b, const double *t, const double *__restrict__ dinv, CoefTable alpha,
                        CoefTable coef2, PtrTable P, int nv, double beta_mu, double tau,
                        const double *__restrict__ rx, double diag, int64_t n, int64_t ntiles,
                        double *__restrict__ px, double *__restrict__ pzl, double *__restrict__ pzu,
                        double *tout, double *__restrict__ va, int nca, double *__restrict__ traw,
-                       int store_step, int ca0, VirtCols vc, double dinv_diag, GroupCols2 gcs,
+                       int store_step, int ca0, double dinv_diag, GroupCols2 gcs,
                        double *__restrict__ partials) {
   extern __shared__ double s2lds[];  // [4][NPASS][128] column slices, [4*64*6] partial sums, [128] t', [8]
   double *pt = s2lds;
@@ -1707,7 +1635,6 @@ __global__ void __launch_bounds__(kBlock, OCC)
   double mins[2] = {1.0, 1.0};
   const int64_t qlast = (n - 1) >> 1;
   f64x2 buf[NPASS];
-  f64x2 sbuf[VIRT ? 3 : 1];  // S partners of this wave's unformed L-SR1 columns (they lead the panel: j < 12)
   // the grouped column this wave adds behind its own columns (if any), prefetched with them
   const int gmine = (gcs.count > 0 && wave == (nv & 3)) ? 0 : ((gcs.count > 1 && wave == ((nv + 1) & 3)) ? 1 : -1);
   GRaw gbuf;
@@ -1729,12 +1656,6 @@ __global__ void __launch_bounds__(kBlock, OCC)
     _Pragma("unroll") for (int it = 0; it < NPASS; it++) {                                   \
       const int j = wave + 4 * it;                                                           \
       buf[it] = ld_stream(P.p[j < nv ? j : 0] + 2 * q);                                      \
-    }                                                                                        \
-    if (VIRT) {                                                                              \
-      _Pragma("unroll") for (int it = 0; it < (VIRT ? 3 : 0); it++) {                        \
-        const int j = wave + 4 * it;                                                         \
-        sbuf[it] = ld_stream(vc.s[j < vc.count ? j : 0] + 2 * q);                            \
-      }                                                                                      \
     }                                                                                        \
     if (gmine >= 0) gbuf = gcol_request(gcs.g[gmine], q, n);                                 \
   }
@@ -1766,10 +1687,6 @@ __global__ void __launch_bounds__(kBlock, OCC)
     for (int it = 0; it < NPASS; it++) {
       const int j = wave + 4 * it;  // coefficient tables are zero beyond nv
       f64x2 v = buf[it];
-      if (VIRT && it < 3 && j < vc.count) {  // Z_j = Y_j - b0 S_j in registers
-        v.x -= vc.b0 * sbuf[VIRT ? it : 0].x;
-        v.y -= vc.b0 * sbuf[VIRT ? it : 0].y;
-      }
       if (!inc) v = (f64x2){0.0, 0.0};
       const double ca = alpha.a[j], cb = coef2.a[j], cA = (j >= ca0 && j < ca0 + nca) ? ca : 0.0;
       a1 += ca * v;
@@ -1890,229 +1807,17 @@ __global__ void __launch_bounds__(kBlock, OCC)
   block_reduce_store<2, OP_MIN>(mins, partials, nv, sm);
 }
 
-// -------------------------------------------------------------------------------------------------
-// TWO TILES PER STEP (round 5; narrow panels, NPASS <= 6, no unformed columns).  What bounds the form above on a narrow
-// panel is the instruction stream of the element epilogue -- 13 IEEE divisions per element -- which two of the four
-// wavefronts run while the other two wait (HISTORY R5.11).  Here a workgroup takes its next TWO tiles (the same tiles
-// in the same order as above: blockIdx.x + k gridDim.x, k = 2 m and 2 m + 1) at once: waves 0-1 finish the elements of
-// the first, waves 2-3 those of the second, at the same time.  The columns stay in registers (no LDS slices: the request
-// for the next pair goes out behind the dots, and the other workgroups of the CU cover its latency -- R5.11 measured that
-// they do), every wave takes the dots of its own columns with the first tile's t' and THEN with the second's: the order
-// in which the form above adds them, so every sum keeps its bits.
-// -------------------------------------------------------------------------------------------------
-template <int NPASS, int OCC>
-__global__ void __launch_bounds__(kBlock, OCC)
-    solve2_dots2_kernel(Bounds b, const double *t, const double *__restrict__ dinv, CoefTable alpha,
-                        CoefTable coef2, PtrTable P, int nv, double beta_mu, double tau,
-                        const double *__restrict__ rx, double diag, int64_t n, int64_t ntiles,
-                        double *__restrict__ px, double *__restrict__ pzl, double *__restrict__ pzu,
-                        double *tout, double *__restrict__ va, int nca, double *__restrict__ traw,
-                        int store_step, int ca0, double dinv_diag, GroupCols2 gcs,
-                        double *__restrict__ partials) {
-  extern __shared__ double s2lds[];  // [2][4*64*6] partial sums, [2][128] t', [8]
-  double *sacc = s2lds;
-  double *stp = s2lds + 2 * (4 * 64 * 6);
-  double *sm = stp + 2 * kS2Tile;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ex = wave >> 1, eh = wave & 1;  // epilogue: rows 64 eh + lane of tile `ex` of the pair
-  double dotacc[NPASS];
-#pragma unroll
-  for (int it = 0; it < NPASS; it++) dotacc[it] = 0.0;
-  double mins[2] = {1.0, 1.0};
-  const int64_t qlast = (n - 1) >> 1;
-  f64x2 buf[2][NPASS];
-  const int gmine = (gcs.count > 0 && wave == (nv & 3)) ? 0 : ((gcs.count > 1 && wave == ((nv + 1) & 3)) ? 1 : -1);
-  GRaw gbuf[2];
-  bool in[2] = {false, false};
-  double eb[8];
-  bool ein = false;
-#pragma unroll
-  for (int x = 0; x < 2; x++) {
-    gbuf[x].raw = (f64x2){0.0, 0.0};
-    gbuf[x].valid = 0;
-  }
-  // columns of both tiles of the pair that starts at FIRST, and this wave's element operands of its own tile
-#define PO_S22_REQUEST(FIRST)                                                                \
-  {                                                                                          \
-    _Pragma("unroll") for (int x = 0; x < 2; x++) {                                          \
-      const int64_t _tile = (FIRST) + x * (int64_t)gridDim.x;                                \
-      int64_t _q = _tile * 64 + lane;                                                        \
-      in[x] = _tile < ntiles && 2 * _q < n;                                                  \
-      if (!in[x]) _q = qlast;                                                                \
-      _Pragma("unroll") for (int it = 0; it < NPASS; it++) {                                 \
-        const int j = wave + 4 * it;                                                         \
-        buf[x][it] = ld_stream(P.p[j < nv ? j : 0] + 2 * _q);                                \
-      }                                                                                      \
-      if (gmine >= 0) gbuf[x] = gcol_request(gcs.g[gmine], _q, n);                           \
-    }                                                                                        \
-    const int64_t _mine = (FIRST) + ex * (int64_t)gridDim.x;                                 \
-    const int64_t _ir = _mine * kS2Tile + 64 * eh + lane;                                    \
-    ein = _mine < ntiles && _ir < n;                                                         \
-    const int64_t _ie = ein ? _ir : n - 1;                                                   \
-    eb[0] = b.x[_ie];                                                                        \
-    eb[1] = b.lb_uni ? b.lb_c : b.lb[_ie];                                                   \
-    eb[2] = b.ub_uni ? b.ub_c : b.ub[_ie];                                                   \
-    eb[3] = b.zl[_ie];                                                                       \
-    eb[4] = b.zu[_ie];                                                                       \
-    if (t) {                                                                                 \
-      eb[5] = t[_ie];                                                                        \
-      eb[6] = dinv[_ie];                                                                     \
-    }                                                                                        \
-    eb[7] = rx[_ie];                                                                         \
-  }
-  if ((int64_t)blockIdx.x < ntiles) PO_S22_REQUEST((int64_t)blockIdx.x);
-  for (int64_t first = blockIdx.x; first < ntiles; first += 2 * (int64_t)gridDim.x) {
-    const bool has2 = first + gridDim.x < ntiles;  // (workgroup-uniform)
-#pragma unroll
-    for (int x = 0; x < 2; x++) {
-      f64x2 a1 = (f64x2){0.0, 0.0}, a2 = a1, aA = a1;
-#pragma unroll
-      for (int it = 0; it < NPASS; it++) {
-        const int j = wave + 4 * it;  // coefficient tables are zero beyond nv
-        f64x2 v = buf[x][it];
-        if (!in[x]) v = (f64x2){0.0, 0.0};
-        buf[x][it] = v;  // (what the form above parks in LDS)
-        const double ca = alpha.a[j], cb = coef2.a[j], cA = (j >= ca0 && j < ca0 + nca) ? ca : 0.0;
-        a1 += ca * v;
-        a2 += cb * v;
-        aA += cA * v;
-      }
-      if (gmine >= 0) {
-        f64x2 v = gcol_value(gcs.g[gmine], gbuf[x]);
-        if (!in[x]) v = (f64x2){0.0, 0.0};
-        a1 += gcs.ca[gmine] * v;
-        a2 += gcs.cb[gmine] * v;
-      }
-      double *sa = sacc + x * (4 * 64 * 6) + wave * 64 + lane;
-      sa[0 * 256] = a1.x;
-      sa[1 * 256] = a1.y;
-      sa[2 * 256] = a2.x;
-      sa[3 * 256] = a2.y;
-      sa[4 * 256] = aA.x;
-      sa[5 * 256] = aA.y;
-    }
-    __syncthreads();
-    if (ex == 0 || has2) {
-      const int64_t tile = first + ex * (int64_t)gridDim.x;
-      const int er = 64 * eh + lane, el = er >> 1, ec = er & 1;
-      double acc = 0.0, acc2 = 0.0, accA = 0.0;
-#pragma unroll
-      for (int w = 0; w < 4; w++) {
-        const double *sp = sacc + ex * (4 * 64 * 6) + w * 64 + el;
-        acc += sp[(0 + ec) * 256];
-        acc2 += sp[(2 + ec) * 256];
-        accA += sp[(4 + ec) * 256];
-      }
-      double tp = 0.0;
-      const int64_t i = tile * kS2Tile + er;
-      if (ein) {
-        const double _x = eb[0], _lb = eb[1], _ub = eb[2], _zl = eb[3], _zu = eb[4];
-        const BE e = bound_elem(_x, _lb, _ub, _zl, _zu, b.max_bound, b.use_lower, b.use_upper);
-        const double r = eb[7];
-        double tv, dv;
-        if (t) {
-          tv = eb[5];
-          dv = eb[6];
-        } else {
-          dv = dinv_elem(e, dinv_diag);
-          tv = dv * d1_elem(e, r, beta_mu);
-        }
-        if (va && store_step == 1) va[i] = accA;
-        const Step3 s0 = solve2_elem<0>(e, tv + dv * acc, beta_mu, 0.0, 0.0, 0.0);
-        if (store_step) {
-          px[i] = s0.px;
-          if (store_step == 1) {
-            pzl[i] = s0.pzl;
-            pzu[i] = s0.pzu;
-          }
-        }
-        const double raw = res_step_elem(e, r, acc2, diag, s0.px, s0.pzl, s0.pzu, 1.0, beta_mu, b.use_lower,
-                                         b.use_upper);
-        tp = dv * raw;
-        if (traw) {
-          traw[i] = raw;
-        } else if (tout) {
-          tout[i] = tp;
-        }
-        max_step_elem(b, _x, _lb, _ub, _zl, _zu, s0, tau, mins[0], mins[1]);
-      } else if (i == n && (n & 1)) {
-        if (va && store_step == 1) va[i] = 0.0;
-        if (store_step) {
-          px[i] = 0.0;
-          if (store_step == 1) {
-            pzl[i] = 0.0;
-            pzu[i] = 0.0;
-          }
-        }
-        if (traw) {
-          traw[i] = 0.0;
-        } else if (tout) {
-          tout[i] = 0.0;
-        }
-      }
-      stp[ex * kS2Tile + er] = tp;
-    }
-    __syncthreads();
-    {
-      const f64x2 tt = *reinterpret_cast<const f64x2 *>(stp + 2 * lane);
-#pragma unroll
-      for (int it = 0; it < NPASS; it++) dotacc[it] = fma(buf[0][it].x, tt.x, fma(buf[0][it].y, tt.y, dotacc[it]));
-    }
-    if (has2) {
-      const f64x2 tt = *reinterpret_cast<const f64x2 *>(stp + kS2Tile + 2 * lane);
-#pragma unroll
-      for (int it = 0; it < NPASS; it++) dotacc[it] = fma(buf[1][it].x, tt.x, fma(buf[1][it].y, tt.y, dotacc[it]));
-    }
-    if (first + 2 * (int64_t)gridDim.x < ntiles) PO_S22_REQUEST(first + 2 * (int64_t)gridDim.x);
-  }
-#undef PO_S22_REQUEST
-#pragma unroll
-  for (int it = 0; it < NPASS; it++) {
-    const double v = wave_reduce<OP_SUM>(dotacc[it]);
-    const int j = wave + 4 * it;
-    if (lane == 0 && j < nv) partials[(size_t)j * gridDim.x + blockIdx.x] = v;
-  }
-  __syncthreads();
-  block_reduce_store<2, OP_MIN>(mins, partials, nv, sm);
-}
-
 template <int NP, int OCC>
-static int solve2_dots2_launch(Ctx *c, const Bounds &b, const double *t, const double *dinv, const CoefTable &ct,
-                               const CoefTable &ct2, const PtrTable &pt, int nv, double beta_mu, double tau,
-                               const double *rx, double diag, int64_t n, int64_t ntiles, double *px, double *pzl,
-                               double *pzu, double *tout, double *va, int nca, double *traw, int store_step, int ca0,
-                               double dinv_diag, int *grid_out, const GroupCols2 &gcs) {
-  const size_t lds = sizeof(double) * (size_t)(2 * (4 * 64 * 6) + 2 * kS2Tile + 8);
-  // the grid of the one-tile form (same tiles per workgroup, same partial sums)
-  const size_t lds1 = sizeof(double) * (size_t)(4 * NP * kS2Tile + 4 * 64 * 6 + kS2Tile + 8);
-  int per_cu = (int)((160 * 1024) / lds1);
-  if (per_cu > OCC) per_cu = OCC;
-  if (per_cu < 1) per_cu = 1;
-  int64_t g = (int64_t)c->num_cu * per_cu;
-  if (g > ntiles) g = ntiles;
-  if (g < 1) g = 1;
-  PO_TRY(ensure_partials(c, (size_t)g * (nv + 2)));
-  hipLaunchKernelGGL((solve2_dots2_kernel<NP, OCC>), dim3((int)g), dim3(kBlock), lds, c->stream, b, t, dinv, ct, ct2, pt,
-                     nv, beta_mu, tau, rx, diag, n, ntiles, px, pzl, pzu, tout, va, nca, traw, store_step, ca0,
-                     dinv_diag, gcs, c->d_partials);
-  c->n_launches++;
-  PO_HIP(hipGetLastError());
-  *grid_out = (int)g;
-  return PO_OK;
-}
-
-template <int NP, int OCC, int VIRT>
 static int solve2_dots_launch(Ctx *c, int grid_cap, const Bounds &b, const double *t, const double *dinv,
                               const CoefTable &ct, const CoefTable &ct2, const PtrTable &pt, int nv, double beta_mu,
                               double tau, const double *rx, double diag, int64_t n, int64_t ntiles, double *px,
                               double *pzl, double *pzu, double *tout, double *va, int nca, double *traw,
-                              int store_step, int ca0, const VirtCols &vc, double dinv_diag, int *grid_out,
+                              int store_step, int ca0, double dinv_diag, int *grid_out,
                               const GroupCols2 &gcs) {
   const size_t lds = sizeof(double) * (size_t)(4 * NP * kS2Tile + 4 * 64 * 6 + kS2Tile + 8);
   static bool attr_set = false;
   if (!attr_set) {
-    PO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(solve2_dots_kernel<NP, OCC, VIRT>),
+    PO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(solve2_dots_kernel<NP, OCC>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
@@ -2123,40 +1828,25 @@ static int solve2_dots_launch(Ctx *c, int grid_cap, const Bounds &b, const doubl
   if (g > ntiles) g = ntiles;
   if (g < 1) g = 1;
   PO_TRY(ensure_partials(c, (size_t)g * (nv + 2)));
-  hipLaunchKernelGGL((solve2_dots_kernel<NP, OCC, VIRT>), dim3((int)g), dim3(kBlock), lds, c->stream, b, t, dinv, ct, ct2, pt, nv,
-                     beta_mu, tau, rx, diag, n, ntiles, px, pzl, pzu, tout, va, nca, traw, store_step, ca0, vc,
-                     dinv_diag, gcs, c->d_partials);
+  hipLaunchKernelGGL((solve2_dots_kernel<NP, OCC>), dim3((int)g), dim3(kBlock), lds, c->stream, b, t, dinv, ct, ct2, pt, nv,
+                     beta_mu, tau, rx, diag, n, ntiles, px, pzl, pzu, tout, va, nca, traw, store_step, ca0, dinv_diag,
+                     gcs, c->d_partials);
   c->n_launches++;
   PO_HIP(hipGetLastError());
   *grid_out = (int)g;
   return PO_OK;
 }
 
-// (OD / OA: workgroups per CU, default and alternative (PAROPT_AMD_S2D_OCC).  Until the element epilogue moved to two
-// waves with one element per lane the stored-step form of narrow panels -- the sparse-constraint path -- took 2 by
-// default (its epilogue kept the step and the raw right-hand side live beside the prefetched operands and spilled at
-// 3); with 129-143 registers it takes 3 like the others: 177.8 -> 181.3 it/s at config 4 in one call.  Wider panels
-// stay at 2: 3 spills there and costs 1 % at config 3, 7 % at config 2.)
+// (OD: workgroups per CU.  Until the element epilogue moved to two waves with one element per lane the stored-step
+// form of narrow panels -- the sparse-constraint path -- took 2 (its epilogue kept the step and the raw right-hand side
+// live beside the prefetched operands and spilled at 3); with 129-143 registers it takes 3 like the others: 177.8 ->
+// 181.3 it/s at config 4 in one call.  Wider panels stay at 2: 3 spills there and costs 1 % at config 3, 7 % at
+// config 2.  Every instantiation is scratch-free, tests/test_kernel_resources.py.)
 #define PO_S2D_CASE(NP)                                                                                    \
   case NP: {                                                                                               \
-    /* (round 5: the alternatives of the wide panels -- 3 workgroups per CU at 11 / 12 slots, 2 at 20 / 24 --       \
-       spilled to scratch and are gone: every instantiation left is scratch-free, tests/test_kernel_resources.py) */ \
-    constexpr int OD = NP <= 8 ? 3 : (NP <= 16 ? 2 : 1), OA = NP <= 8 ? 2 : OD;                            \
-    constexpr int OV = NP <= 16 ? 2 : 1; /* with unformed columns: three more prefetch registers */        \
-    /* (two tiles per step up to 6 slots per wave: 8 slots would need 168 + 13 registers at three workgroups per CU) */ \
-    if (NP <= 6 && vc.count == 0 && two_tiles && occ_env != OA) {                                          \
-      constexpr int NP2 = NP <= 6 ? NP : 6;                                                                \
-      PO_TRY((solve2_dots2_launch<NP2, 3>(c, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, px, pzl, \
-                                          pzu, tout, va, nca, traw, store_step, ca0, dinv_diag, &grid, gcs))); \
-    } else if (vc.count > 0)                                                                               \
-      PO_TRY((solve2_dots_launch<NP, OV, 1>(c, 0, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, \
-                                            px, pzl, pzu, tout, va, nca, traw, store_step, ca0, vc, dinv_diag, &grid, gcs))); \
-    else if (occ_env == OA)                                                                                \
-      PO_TRY((solve2_dots_launch<NP, OA, 0>(c, 0, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, \
-                                            px, pzl, pzu, tout, va, nca, traw, store_step, ca0, vc, dinv_diag, &grid, gcs))); \
-    else                                                                                                   \
-      PO_TRY((solve2_dots_launch<NP, OD, 0>(c, 0, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, \
-                                            px, pzl, pzu, tout, va, nca, traw, store_step, ca0, vc, dinv_diag, &grid, gcs))); \
+    constexpr int OD = NP <= 8 ? 3 : (NP <= 16 ? 2 : 1);                                                   \
+    PO_TRY((solve2_dots_launch<NP, OD>(c, 0, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, px, pzl, \
+                                       pzu, tout, va, nca, traw, store_step, ca0, dinv_diag, &grid, gcs)));  \
   } break;
 
 // out = {dots[nv] = P^T t', max_x, max_z}
@@ -2164,8 +1854,8 @@ int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, 
                   const double *coef2, const double *const *P, int nv, double beta_mu, double tau,
                   const double *rx, double diag, int64_t n, double *px, double *pzl, double *pzu,
                   double *tout, double *va, int nca, double *out, double *traw, int store_step, int ca0,
-                  const double *const *vs, int nvirt, double b0v, double dinv_diag, const GroupCols2 *gcols) {
-  count_bytes(c, nv + nvirt + 6 + (t ? 2 : 0) + (store_step == 1 ? 3 + (va ? 1 : 0) : (store_step == 2 ? 1 : 0)) + ((traw || tout) ? 1 : 0) - uniform_bound_streams(b), n);
+                  double dinv_diag, const GroupCols2 *gcols) {
+  count_bytes(c, nv + 6 + (t ? 2 : 0) + (store_step == 1 ? 3 + (va ? 1 : 0) : (store_step == 2 ? 1 : 0)) + ((traw || tout) ? 1 : 0) - uniform_bound_streams(b), n);
   const GroupCols2 gcs = gcols ? *gcols : GroupCols2();
   for (int e = 0; e < gcs.count; e++) PO_TRY(gcol_check(&gcs.g[e], n, "k_solve2_dots"));
   for (int e = 0; e < gcs.count; e++) count_bytes(c, 1.0, gcs.g[e].nwcon);
@@ -2173,26 +1863,8 @@ int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, 
     set_error("panel of %d vectors outside 1..%d", nv, kMaxPanel);
     return PO_ERR_ARG;
   }
-  VirtCols vc;
-  vc.count = 0;
-  vc.b0 = b0v;
-  for (int j = 0; j < kMaxVirt; j++) vc.s[j] = nullptr;
-  if (nvirt > 0) {
-    if (nvirt > kMaxVirt || ca0 < nvirt) {
-      set_error("k_solve2_dots: %d unformed columns (at most %d, leading the panel)", nvirt, kMaxVirt);
-      return PO_ERR_ARG;
-    }
-    vc.count = nvirt;
-    for (int j = 0; j < nvirt; j++) vc.s[j] = vs[j];
-  }
   const int64_t ntiles = (((n + 1) >> 1) + 63) / 64;
   int grid = 0;
-  static const int occ_env = getenv("PAROPT_AMD_S2D_OCC") ? atoi(getenv("PAROPT_AMD_S2D_OCC")) : 0;
-  // PAROPT_AMD_S2D_TWO=1: narrow panels two tiles per step (solve2_dots2_kernel; same bits either way).  OFF by
-  // default: measured in one call (profiles/r05_ab_solve2_dots_two_tiles.jsonl) the kernels are 9-15 % faster at
-  // n = 5 M (config 5: 93.5 / 137.9 / 174.5 us against 109 / 150.9 / 194.9) and 5-7 % SLOWER at n = 20 M (config 4:
-  // 1053 against 1006 us), and neither line moves (782 / 794 against 791 / 783 inner it/s, 178.0 against 178.0 it/s).
-  const bool two_tiles = dbg_switch(SW_S2D_TWO, "PAROPT_AMD_S2D_TWO", 0) != 0;
   PtrTable pt;
   CoefTable ct, ct2;
   fill_tables(alpha, P, nv, &ct, &pt);

@@ -48,7 +48,7 @@ int Problem::setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *r
     set_error("setSparseJacobianData: bad arguments");
     return PO_ERR_ARG;
   }
-  static const bool no_groups = getenv("PAROPT_AMD_NO_CSR_GROUPS") != nullptr;
+  static const bool no_groups = dbg_switch(SW_NO_CSR_GROUPS) != 0;
   GroupMap gm;
   bool rec = !no_groups && nwblock == 1 && ((nwcon_ == 0 && ctx->size > 1) || recognise_groups(nlocal, nwcon_, rowp, cols, &gm));
   if (ctx->size > 1) {  // all ranks or none (the two paths issue different reductions): collective
@@ -334,8 +334,7 @@ int Problem::checkGradients(double dh, Vec *x, bool check_hvec, Vec *xt, Vec *px
 }
 
 bool Problem::sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *col) {
-  static const bool off = getenv("PAROPT_AMD_NO_GROUP_COLS") != nullptr;
-  if (off || !grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
+  if (!grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
   col->w = pzw->d;
   col->scale = alpha * group_alpha;  // the value k_group_scatter_set(..., alpha * group_alpha, ...) stores
   col->period = (unsigned)(gmap.nw + gmap.skip);

@@ -133,6 +133,10 @@ __device__ __forceinline__ void gram_tile(const double *__restrict__ pt, const d
 constexpr int kGramRowSplitMaxNG = 14;  // NG (NG + 1) / 2 accumulators of 2 VGPRs each must fit beside the operands
 constexpr int kGramRowSplitMinNG = 5;   // narrow panels (<= 16 columns) are nowhere near the LDS / matrix limits: they
                                         // keep the output split (and with it round 2's summation order)
+// Panels of fewer groups take the single-role form (k_wgram_launch): all producer/consumer panels up to
+// kGramRowSplitMaxNG groups split rows
+constexpr int kGramPcMinNG = 6;
+static_assert(kGramPcMinNG >= kGramRowSplitMinNG, "a producer/consumer panel narrower than the row split");
 
 template <int NG>
 __device__ __forceinline__ void gram_step_all(const double (&a)[NG], double w, bool tsel,
@@ -558,36 +562,6 @@ __global__ void __launch_bounds__(512, 1)
     const bool stamp = want_stamps && blockIdx.x == 0 && wave == 4;
     const unsigned long long st_c0 = stamp ? __builtin_amdgcn_s_memtime() : 0;
     const unsigned long long st_r0 = stamp ? __builtin_amdgcn_s_memrealtime() : 0;
-    // GS == 2 (round 5): the group sums of the panel image are taken by the PRODUCER waves, off the consumers' critical
-    // path (matrix work only): behind the barrier that publishes tile t the 256 producer lanes request the operands of
-    // their (column, group) pair from tile t's buffer, stage tile t + 1 and issue the loads of tile t + 4 while the
-    // requests are in flight, then add (same rounded products, same order: the bits of group_panel_tiled_kernel) and
-    // store.  Branch-free like the rest of the producers' loop (a lane without a pair reads clamped addresses and
-    // stores 0.0 to the pad element behind the first output column), so that hipcc keeps exact counts of the
-    // outstanding prefetch loads; the first step "finishes" a tile that does not exist the same way.
-    [[maybe_unused]] GramGroupOps gops;
-    [[maybe_unused]] int g2_u = 0, g2_gi = 0, g2_uc = 0;
-    [[maybe_unused]] bool g2_lane = false;
-    if constexpr (GS == 2) {
-      const int ptid = tid - 256;
-      g2_u = ptid / gg.G;
-      g2_gi = ptid - g2_u * gg.G;
-      g2_lane = g2_u < gg.ncols;
-      g2_uc = g2_lane ? g2_u : 0;
-    }
-    typedef __attribute__((address_space(1))) double g2double;
-    [[maybe_unused]] g2double *g2_up = nullptr;
-    if constexpr (GS == 2) g2_up = (g2double *)utab[g2_uc];  // (published by the barrier above)
-#define PO_GS2_REQUEST(BUF) gram_groups_request((BUF), (BUF) + M * kGramLd, gg, g2_uc, g2_gi, gops)
-#define PO_GS2_FINISH(TIDX)                                                                                   \
-  {                                                                                                           \
-    const int64_t _tile = first + (TIDX) * stride;                                                            \
-    const int64_t _g0 = _tile * gg.G;                                                                         \
-    const bool _mine = g2_lane && (TIDX) >= 0 && _tile < gg.ngt && _g0 + g2_gi < gg.nwcon;                    \
-    const double _sum = gram_groups_sum(gg, gops);                                                            \
-    const int64_t _idx = _mine ? _g0 + g2_gi : gg.nwcon;                                                      \
-    g2_up[_idx] = _mine ? _sum : 0.0;                                                                         \
-  }
     // (Round 5, measured and NOT kept: with the loads under `if (tile < ntiles)` and the steps under `if (it + R < nt)`
     // hipcc's wait-count bookkeeping merges "issued" and "not issued" at the joins and from then on takes every load in
     // flight for kGramDepth-1 tiles younger than it is: tile t is staged behind vmcnt(NG) instead of
@@ -599,7 +573,6 @@ __global__ void __launch_bounds__(512, 1)
 #define PO_PC_STEP(R)                                                                                         \
   if (it + (R) < nt) {                                                                                        \
     double *bt = lds + (size_t)((it + (R)) & 1) * kBufDoubles;                                                \
-    if constexpr (GS == 2) PO_GS2_REQUEST(lds + (size_t)((it + (R) + 1) & 1) * kBufDoubles);                  \
     const unsigned long long _t0 = stamp ? __builtin_amdgcn_s_memtime() : 0;                                  \
     if (ablate == 2) {                                                                                        \
       if (P.buf[R][0].x == 1.2345e301) bt[0] = P.buf[R][NG - 1].y;                                            \
@@ -612,7 +585,6 @@ __global__ void __launch_bounds__(512, 1)
     const unsigned long long _t1 = stamp ? __builtin_amdgcn_s_memtime() : 0;                                  \
     if (ablate != 3) gram_pc_load<NG, ZP, (R)>(P, colp, scol, d, first + (it + (R) + kGramDepth) * stride, ntiles, n, ilast, lane, gg); \
     const unsigned long long _t2 = stamp ? __builtin_amdgcn_s_memtime() : 0;                                  \
-    if constexpr (GS == 2) PO_GS2_FINISH(it + (R) - 1);                                                       \
     __syncthreads();                                                                                          \
     if (stamp) {                                                                                              \
       const unsigned long long _t3 = __builtin_amdgcn_s_memtime();                                            \
@@ -627,17 +599,6 @@ __global__ void __launch_bounds__(512, 1)
       PO_PC_STEP(2)
     }
 #undef PO_PC_STEP
-    if constexpr (GS == 2) {
-      // the sums of the last tile (staged and published by the last step's barrier; the consumers overwrite the tile
-      // buffers only behind the trailing barrier below)
-      if (nt > 0) {
-        const double *bl = lds + (size_t)((nt - 1) & 1) * kBufDoubles;
-        PO_GS2_REQUEST(bl);
-        PO_GS2_FINISH(nt - 1);
-      }
-    }
-#undef PO_GS2_REQUEST
-#undef PO_GS2_FINISH
     if (stamp && lane == 0) {
       g_wgram_stamp[2] = st_stage;
       g_wgram_stamp[3] = st_load;
@@ -918,7 +879,8 @@ __global__ void __launch_bounds__(512, 1)
 }
 
 template <int NG>
-static int wgram_pc64_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv, int64_t n, int tcol, int *grid_out) {
+static int wgram_pc64_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv, int64_t n, int tcol, int ablate,
+                               int prio, int *grid_out) {
   const size_t lds = (size_t)2 * (4 * NG * kG64Ld + kG64Tile) * sizeof(double);
   static bool attr_set = false;
   if (!attr_set) {
@@ -931,8 +893,7 @@ static int wgram_pc64_launch_t(Ctx *c, const double *d, const PtrTable &pt, int 
   if (g > ntiles) g = ntiles;
   if (g < 1) g = 1;
   PO_TRY(ensure_partials(c, (size_t)g * (NG * (NG + 1) / 2) * 16));
-  const int prio = dbg_switch(SW_WGRAM_PRIO, "PAROPT_AMD_WGRAM_PRIO", 2);
-  const int stamps = (dbg_switch(SW_WGRAM_ABLATE, "PAROPT_AMD_WGRAM_ABLATE", 0) & 16) != 0;
+  const int stamps = (ablate & 16) != 0;
   hipLaunchKernelGGL((wgram_pc64_kernel<NG>), dim3((int)g), dim3(512), lds, c->stream, d, pt, nv, n, ntiles,
                      c->d_partials, tcol, prio, stamps);
   c->n_launches++;
@@ -943,8 +904,8 @@ static int wgram_pc64_launch_t(Ctx *c, const double *d, const PtrTable &pt, int 
 
 template <int NG, int ZP, int RS, int GS = 0>
 static int wgram_pc_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv, int64_t n, int64_t ntiles,
-                             const PtrTable &st, const PtrTableW &zt, int kpend, double b0, int tcol, int *grid_out,
-                             const GramGeom *gg = nullptr, const PtrTableW *ut = nullptr) {
+                             const PtrTable &st, const PtrTableW &zt, int kpend, double b0, int tcol, int ablate,
+                             int prio, int *grid_out, const GramGeom *gg = nullptr, const PtrTableW *ut = nullptr) {
   const size_t lds = (size_t)2 * (4 * NG * kGramLd + kGramTile) * sizeof(double) + (GS ? kMaxPanel * sizeof(double *) : 0);
   static bool attr_set = false;
   if (!attr_set) {
@@ -952,14 +913,10 @@ static int wgram_pc_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  const int ablate = dbg_switch(SW_WGRAM_ABLATE, "PAROPT_AMD_WGRAM_ABLATE", 0);
   int64_t g = (int64_t)c->num_cu;  // one workgroup per CU
   if (g > ntiles) g = ntiles;
   if (g < 1) g = 1;
   PO_TRY(ensure_partials(c, (size_t)g * (NG * (NG + 1) / 2) * 16));
-  // producers at raised priority: their address arithmetic no longer queues behind the consumers' matrix
-  // instructions on the shared SIMD (-4 % on the plain form, -1.7 % with the L-SR1 columns formed; 0 switches it off)
-  const int prio = dbg_switch(SW_WGRAM_PRIO, "PAROPT_AMD_WGRAM_PRIO", 2);
   static const PtrTableW no_u = PtrTableW();
   hipLaunchKernelGGL((wgram_pc_kernel<NG, ZP, RS, GS>), dim3((int)g), dim3(512), lds, c->stream, d, pt, nv, n, ntiles,
                      c->d_partials, st, zt, kpend, b0, tcol, ablate, prio, gg ? *gg : GramGeom(), ut ? *ut : no_u);
@@ -971,7 +928,8 @@ static int wgram_pc_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv
 
 template <int NG, int ZP, int OCC>
 static int wgram_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv, int64_t n, int64_t ntiles,
-                          const PtrTable &st, const PtrTableW &zt, int kpend, double b0, int tcol, int *grid_out) {
+                          const PtrTable &st, const PtrTableW &zt, int kpend, double b0, int tcol, int ablate,
+                          int *grid_out) {
   const size_t lds = (size_t)(4 * NG * kGramLd + kGramTile) * sizeof(double);
   static bool attr_set = false;
   if (!attr_set) {
@@ -979,7 +937,6 @@ static int wgram_launch_t(Ctx *c, const double *d, const PtrTable &pt, int nv, i
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  static const int ablate = getenv("PAROPT_AMD_WGRAM_ABLATE") ? atoi(getenv("PAROPT_AMD_WGRAM_ABLATE")) : 0;
   int per_cu = (int)((160 * 1024) / lds);
   if (per_cu > OCC) per_cu = OCC;  // one wavefront of every resident workgroup per SIMD
   if (per_cu < 1) per_cu = 1;
@@ -1001,8 +958,6 @@ static int wgram_groups(int nv) { return (nv + 3) / 4; }
 // caller then runs group_panel_tiled_kernel as before)
 static bool wgram_groups_geom(const GramGroups *g, int nv, int64_t n, int kpend, GramGeom *gg) {
   if (!g || g->nwcon <= 0 || g->ncols <= 0 || g->ncols > nv || !g->U || kpend > 0) return false;
-  static const bool off = getenv("PAROPT_AMD_NO_GRAM_GROUPS") != nullptr;
-  if (off) return false;
   const int64_t period = (int64_t)g->nw + g->skip;
   if (g->start != 0 || g->nw <= 0 || g->nw > kGramGroupNw || period > kGramTile) return false;
   if ((g->nwcon - 1) * period + g->nw > n) return false;
@@ -1052,46 +1007,33 @@ int k_wgram_launch(Ctx *c, const double *d, const double *const *V, int nv, int6
   }
   int grid = 0;
   GramGeom gg;
-  // resident wavefronts per SIMD the kernel is compiled for (register budget 512 / OCC per lane)
-  static const int occ_env = getenv("PAROPT_AMD_WGRAM_OCC") ? atoi(getenv("PAROPT_AMD_WGRAM_OCC")) : 0;
-  // PAROPT_AMD_WGRAM_PC=0: the single-role form (every wavefront loads, stages and multiplies) for all widths
-  static const bool use_pc = !(getenv("PAROPT_AMD_WGRAM_PC") && atoi(getenv("PAROPT_AMD_WGRAM_PC")) == 0);
-  // PAROPT_AMD_WGRAM_RS=0: consumers split the OUTPUT (block pairs) instead of the tile's rows (A/B switch)
-  // measured in one process (tools/ab_switch.py, profiles/r03_ab_wgram.txt, n = 50 M, 43 columns): the row split is
-  // 8 % faster than the output split on the plain form (2.93 vs 3.18 ms = 0.75 of the HBM peak) and 2 % with the L-SR1
-  // columns formed in the pass -- once its operand fetches stay ds_read_b64 (see gram_tile_rows)
-  const bool row_split = dbg_switch(SW_WGRAM_RS, "PAROPT_AMD_WGRAM_RS", 1) != 0;
-  // Narrow panels (<= 20 columns) take the single-role form: one workgroup per CU with three 128-row tiles of a few
-  // columns in flight does not cover the HBM latency (5 columns: 0.31 of the peak at any n, 9: 0.45, 17: 0.65), four
+  // PAROPT_AMD_WGRAM_ABLATE (tuning: 16 = cycle stamps, low bits = what is cut) and PAROPT_AMD_WGRAM_PRIO: producers
+  // at raised priority, their address arithmetic no longer queues behind the consumers' matrix instructions on the
+  // shared SIMD (-4 % on the plain form, -1.7 % with the L-SR1 columns formed; 0 switches it off)
+  const int ablate = dbg_switch(SW_WGRAM_ABLATE), prio = dbg_switch(SW_WGRAM_PRIO);
+  // The producer/consumer form's consumers split the tile's ROWS (kGramRowSplitMinNG..MaxNG groups) -- measured in one
+  // process against splitting the output (tools/ab_switch.py, profiles/r03_ab_wgram.txt, n = 50 M, 43 columns): 8 %
+  // faster on the plain form (2.93 vs 3.18 ms = 0.75 of the HBM peak) and 2 % with the L-SR1 columns formed in the pass.
+  // Narrow panels (< kGramPcMinNG groups) take the single-role form: one workgroup per CU with three 128-row tiles of a
+  // few columns in flight does not cover the HBM latency (5 columns: 0.31 of the peak at any n, 9: 0.45, 17: 0.65), four
   // single-role workgroups per CU do (0.70 / 0.79 / 0.66-0.77); from 25 columns on the two forms are level and the
-  // producer/consumer form wins beyond (round 4, tools/dbg/wgram_pc_grid.py; PAROPT_AMD_WGRAM_PC_MIN_NG to move it).
-  // (The same threshold for a panel image riding in the pass: on a narrow panel the single-role Gram plus the
-  // stand-alone panel image are faster than the fused producer/consumer form -- 0.18 + 0.14 against 0.9 ms at 5 columns.)
-  // PAROPT_AMD_WGRAM_PC64=0: panels of 65-80 columns on the single-role kernel, as before round 5 (A/B)
-  static const bool use_pc64 = !(getenv("PAROPT_AMD_WGRAM_PC64") && atoi(getenv("PAROPT_AMD_WGRAM_PC64")) == 0);
-  static const int pc_min_ng = getenv("PAROPT_AMD_WGRAM_PC_MIN_NG") ? atoi(getenv("PAROPT_AMD_WGRAM_PC_MIN_NG")) : 6;
-  if (use_pc && NG >= pc_min_ng && wgram_groups_geom(groups, nv, n, kpend, &gg)) {
-    // the pass also takes the structured panel image (see GramGeom): group tiles first, ordinary tiles behind them
+  // producer/consumer form wins beyond (round 4, tools/dbg/wgram_pc_grid.py).  (The same threshold for a panel image
+  // riding in the pass: on a narrow panel the single-role Gram plus the stand-alone panel image are faster than the fused
+  // producer/consumer form -- 0.18 + 0.14 against 0.9 ms at 5 columns.)
+  if (NG >= kGramPcMinNG && wgram_groups_geom(groups, nv, n, kpend, &gg)) {
+    // the pass also takes the structured panel image (see GramGeom): group tiles first, ordinary tiles behind them;
+    // the consumers take the group sums (on the producer waves, measured in round 5, the Gram phase was 1.76 against
+    // 1.46 ms at config 4: profiles/r05_ab_gs_producer.jsonl)
     ntiles = gg.ngt + (n - gg.rg + kGramTile - 1) / kGramTile;
     for (int j = 0; j < gg.ncols; j++) ut.p[j] = groups->U[j];
     count_bytes(c, (double)gg.ncols, gg.nwcon);
-    // round 5 experiment, OFF by default: the sums on the PRODUCER waves (GS = 2: same bits; all 621 GPU tests pass with
-    // it).  Measured in one process at config 4 (tools/ab_switch.py, profiles/r05_ab_gs_producer.jsonl): 5.93 against
-    // 5.52 ms per iteration, the Gram phase 1.76 against 1.46 ms -- the producers' staging + load issue + 40 operand
-    // requests is the longer path of a tile, not the consumers' matrix work + sums.  PAROPT_AMD_GS_PRODUCER=1 selects it.
-    const bool gs_prod = gg.G * gg.ncols <= 256 && dbg_switch(SW_GS_PRODUCER, "PAROPT_AMD_GS_PRODUCER", 0) != 0;
-#define PO_WGG(NGv)                                                                                                  \
-  case NGv:                                                                                                          \
-    if (NGv >= kGramRowSplitMinNG && row_split && gs_prod)                                                           \
-      PO_TRY((wgram_pc_launch_t<(NGv >= kGramRowSplitMinNG ? NGv : kGramRowSplitMinNG), 0, 1, 2>(                    \
-          c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid, &gg, &ut)));                                         \
-    else if (NGv >= kGramRowSplitMinNG && row_split)                                                                 \
-      PO_TRY((wgram_pc_launch_t<NGv, 0, 1, 1>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid, &gg, &ut)));     \
-    else                                                                                                             \
-      PO_TRY((wgram_pc_launch_t<NGv, 0, 0, 1>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid, &gg, &ut)));     \
+#define PO_WGG(NGv)                                                                                              \
+  case NGv:                                                                                                      \
+    PO_TRY((wgram_pc_launch_t<NGv, 0, 1, 1>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, ablate, prio, &grid, &gg, \
+                                            &ut)));                                                              \
     break;
     switch (NG) {
-      PO_WGG(1) PO_WGG(2) PO_WGG(3) PO_WGG(4) PO_WGG(5) PO_WGG(6) PO_WGG(7) PO_WGG(8) PO_WGG(9)
+      PO_WGG(6) PO_WGG(7) PO_WGG(8) PO_WGG(9)
     }
 #undef PO_WGG
     if (groups_done) *groups_done = true;
@@ -1106,28 +1048,26 @@ int k_wgram_launch(Ctx *c, const double *d, const double *const *V, int nv, int6
     /* (round 5: 11 groups at 3 wavefronts per SIMD and the column-forming form of 10 / 11 groups at 3 spilled   \
        to scratch: 2 there; every instantiation left is scratch-free, tests/test_kernel_resources.py) */        \
     constexpr int OCC0 = NGv <= 8 ? 4 : (NGv <= 10 ? 3 : (NGv <= 14 ? 2 : 1));                         \
-    constexpr int OCC0A = OCC0 > 1 ? OCC0 - 1 : 1;                                                     \
     constexpr int OCCZ = NGv <= 7 ? 3 : (NGv <= 13 ? 2 : 1);                                           \
-    constexpr int OCCZA = NGv <= 7 ? 4 : (NGv <= 9 ? 3 : OCCZ);                                        \
-    if (NGv >= 17 && use_pc && use_pc64 && kpend == 0 && n >= 4 * kGramTile) {                         \
+    /* (the template arguments below are clamped into the range where each branch is taken) */        \
+    constexpr int NGc = NGv < kGramPcMinNG ? kGramPcMinNG : (NGv <= 16 ? NGv : 16);                    \
+    constexpr int NGr = NGc <= kGramRowSplitMaxNG ? NGc : kGramRowSplitMaxNG;                          \
+    constexpr int NGo = NGc > kGramRowSplitMaxNG ? NGc : kGramRowSplitMaxNG + 1;                       \
+    if (NGv >= 17 && kpend == 0 && n >= 4 * kGramTile) {                                               \
       constexpr int NGw = NGv >= 17 ? NGv : 17;                                                        \
-      PO_TRY((wgram_pc64_launch_t<NGw>(c, d, pt, nv, n, tcol, &grid)));                                \
-    } else if (NGv <= 16 && use_pc && n >= 4 * kGramTile && NGv >= pc_min_ng) {                        \
-      constexpr int NGc = NGv <= 16 ? NGv : 16;                                                        \
-      if (NGv >= kGramRowSplitMinNG && NGv <= kGramRowSplitMaxNG && row_split) {                       \
-        constexpr int NGr = NGv <= kGramRowSplitMaxNG ? NGv : kGramRowSplitMaxNG;                      \
-        if (kpend > 0) PO_TRY((wgram_pc_launch_t<NGr, 3, 1>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, &grid))); \
-        else PO_TRY((wgram_pc_launch_t<NGr, 0, 1>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid)));              \
+      PO_TRY((wgram_pc64_launch_t<NGw>(c, d, pt, nv, n, tcol, ablate, prio, &grid)));                  \
+    } else if (NGv <= 16 && NGv >= kGramPcMinNG && n >= 4 * kGramTile) {                               \
+      if (NGv <= kGramRowSplitMaxNG) {                                                                 \
+        if (kpend > 0) PO_TRY((wgram_pc_launch_t<NGr, 3, 1>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, ablate, prio, &grid))); \
+        else PO_TRY((wgram_pc_launch_t<NGr, 0, 1>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, ablate, prio, &grid)));              \
       } else if (kpend > 0 && NGv == 16) /* (the producer/consumer form with column formation spills at 16 groups) */ \
-        PO_TRY((wgram_launch_t<NGv, 3, 1>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, &grid)));                   \
-      else if (kpend > 0) PO_TRY((wgram_pc_launch_t<(NGc < 16 ? NGc : 15), 3, 0>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, &grid))); \
-      else PO_TRY((wgram_pc_launch_t<NGc, 0, 0>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid)));                \
+        PO_TRY((wgram_launch_t<NGv, 3, 1>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, ablate, &grid)));                   \
+      else if (kpend > 0) PO_TRY((wgram_pc_launch_t<(NGo < 16 ? NGo : 15), 3, 0>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, ablate, prio, &grid))); \
+      else PO_TRY((wgram_pc_launch_t<NGo, 0, 0>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, ablate, prio, &grid)));                \
     } else if (kpend > 0) {                                                                            \
-      if (occ_env == OCCZA) PO_TRY((wgram_launch_t<NGv, 3, OCCZA>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, &grid))); \
-      else PO_TRY((wgram_launch_t<NGv, 3, OCCZ>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, &grid)));     \
+      PO_TRY((wgram_launch_t<NGv, 3, OCCZ>(c, d, pt, nv, n, ntiles, st, zt, kpend, b0, tcol, ablate, &grid))); \
     } else {                                                                                           \
-      if (occ_env == OCC0A) PO_TRY((wgram_launch_t<NGv, 0, OCC0A>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid)));    \
-      else PO_TRY((wgram_launch_t<NGv, 0, OCC0>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, &grid)));        \
+      PO_TRY((wgram_launch_t<NGv, 0, OCC0>(c, d, pt, nv, n, ntiles, st, zt, 0, 0.0, tcol, ablate, &grid)));    \
     }                                                                                                  \
   } break;
   switch (NG) {

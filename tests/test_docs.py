@@ -37,3 +37,21 @@ def test_cited_profile_files_exist():
     assert cited, "the documents cite their evidence"
     missing = sorted(f for f in cited if not os.path.exists(os.path.join(ROOT, "profiles", f)))
     assert not missing, missing
+
+
+def test_switch_table_is_the_only_registry():
+    """Every environment switch of the library is one entry of the table in context.cpp, each entry is a row of the
+    INTEGRATION.md switch table and the other way round, and no other code reads a PAROPT_AMD_ variable (besides the
+    table's reader only PAROPT_AMD_RCCL_LIB, a path, is read directly)."""
+    csrc = os.path.join(ROOT, "paropt_amd", "csrc")
+    table = set(re.findall(r'\{SW_\w+, "(PAROPT_AMD_\w+)"', _read("paropt_amd/csrc/context.cpp")))
+    documented = set(re.findall(r"^\| \d+ \| `(PAROPT_AMD_\w+)`", _read("INTEGRATION.md"), re.M))
+    assert table and table == documented, (sorted(table - documented), sorted(documented - table))
+    direct = []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".cpp", ".hpp", ".hip")):
+            direct += [(f, v) for v in re.findall(r'getenv\("(PAROPT_AMD_\w+)"', _read(os.path.join("paropt_amd", "csrc", f)))]
+    assert direct == [("context.cpp", "PAROPT_AMD_RCCL_LIB")], direct
+    # tools/ab_switch.py resets every id between its variants
+    count = re.search(r"SW_COUNT = (\d+)", _read("paropt_amd/csrc/core.hpp")).group(1)
+    assert re.search(r"^SW_COUNT = %s\b" % count, _read("tools/ab_switch.py"), re.M), count

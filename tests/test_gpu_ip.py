@@ -994,8 +994,7 @@ def test_write_saving_fusions_against_their_plain_forms(monkeypatch, problem, qn
 
     def run(env):
         for k in ("PAROPT_AMD_NO_FUSED_UPDATE", "PAROPT_AMD_NO_RECOMPUTE", "PAROPT_AMD_NO_RECOMPUTE_RHS",
-                  "PAROPT_AMD_VIRTUAL_Z", "PAROPT_AMD_NO_FUSED_MERIT", "PAROPT_AMD_NO_LEAN_STEP",
-                  "PAROPT_AMD_NO_RECOMPUTE_DT"):
+                  "PAROPT_AMD_NO_FUSED_MERIT", "PAROPT_AMD_NO_LEAN_STEP", "PAROPT_AMD_NO_RECOMPUTE_DT"):
             monkeypatch.delenv(k, raising=False)
         for k in env:
             monkeypatch.setenv(k, "1")
@@ -1033,16 +1032,14 @@ def test_write_saving_fusions_against_their_plain_forms(monkeypatch, problem, qn
     np.testing.assert_array_equal(xb_lean, xr)
     window = 12 if qn == "sr1" else len(base)
     # ... PAROPT_AMD_NO_RECOMPUTE_RHS: only the step is recomputed, the refinement right-hand side is stored;
-    # PAROPT_AMD_VIRTUAL_Z (off by default: slower): the L-SR1 columns Z_j = Y_j - b0 S_j are never formed in HBM,
-    # the Gram pass and both solve passes form them in registers
     # PAROPT_AMD_NO_FUSED_MERIT (round 3): the complementarity / merit sums of the final step in their own pass
     # (comp_merit_kernel) instead of inside the refinement pass (solve2r_kernel<.,1>, polynomial form of the
     # complementarity at the scaled step): sums in another order, same counters, state to 1e-9
     # PAROPT_AMD_NO_LEAN_STEP (round 3): the refinement pass stores the bound-multiplier steps (pzl, pzu) instead of
     # leaving them to be re-formed from px inside the multiplier update (they differ by the round-off the refinement
     # corrects)
-    for switch in ("PAROPT_AMD_NO_RECOMPUTE", "PAROPT_AMD_NO_RECOMPUTE_RHS", "PAROPT_AMD_VIRTUAL_Z",
-                   "PAROPT_AMD_NO_FUSED_MERIT", "PAROPT_AMD_NO_LEAN_STEP"):
+    for switch in ("PAROPT_AMD_NO_RECOMPUTE", "PAROPT_AMD_NO_RECOMPUTE_RHS", "PAROPT_AMD_NO_FUSED_MERIT",
+                   "PAROPT_AMD_NO_LEAN_STEP"):
         other, xs = run([switch])
         assert len(other) == len(base), switch
         for sa, sb in list(zip(base, other))[:window]:
@@ -1147,57 +1144,6 @@ def test_reset_design_and_bounds_wins_over_a_live_mirror(ctx, tmp_path):
     view[:] = 0.123
     ip.readSolutionFile(ckpt)
     np.testing.assert_array_equal(view, xopt)
-
-
-
-
-@pytest.mark.parametrize("case", ["c2_bfgs5", "c8_bfgs6", "c4_weighting", "c3_mehrotra", "c1_small"])
-def test_first_solve_pass_two_tiles_per_step_keeps_every_bit(ctx, case):
-    """Narrow panels (up to 24 columns, no unformed L-SR1 columns) take the first solve pass two tiles per step
-    (solve2_dots2_kernel: all four wavefronts in the element epilogue; the dots of a workgroup's tiles are still added
-    in tile order).  Against the one-tile form (debug switch 13 = 0) in the same process: every iterate, multiplier,
-    norm and counter the same bits -- sizes with several tiles per workgroup, an odd number of tiles per workgroup, an
-    odd n, fewer tiles than workgroups, and the grouped columns of the weighting constraints."""
-    import paropt_amd as pa
-    from paropt_amd import lib as L
-
-    SW_S2D_TWO = 13
-    cfg = {
-        "c2_bfgs5": dict(kind="convex", n=400003, c=2, opts={"qn_type": "bfgs", "qn_subspace_size": 5}),
-        "c8_bfgs6": dict(kind="quadratic", n=300001, c=8, opts={"qn_type": "bfgs", "qn_subspace_size": 6}),
-        "c4_weighting": dict(kind="convex", n=400000, c=4, nwcon=20000, nw=20, opts={"qn_type": "bfgs", "qn_subspace_size": 4}),
-        "c3_mehrotra": dict(kind="convex", n=700001, c=3,
-                            opts={"qn_type": "bfgs", "qn_subspace_size": 3, "barrier_strategy": "mehrotra"}),
-        "c1_small": dict(kind="quadratic", n=20011, c=1, opts={"qn_type": "bfgs", "qn_subspace_size": 2}),
-    }[case]
-
-    def run(two):
-        L.lib.po_debug_set_switch(SW_S2D_TWO, 1 if two else 0)
-        try:
-            prob = pa.SeparableProblem(ctx, cfg["kind"], cfg["n"], cfg["c"], 3)
-            if "nwcon" in cfg:
-                prob.setWeighting(cfg["nwcon"], cfg["nw"])
-            ip = pa.InteriorPoint(prob, dict({"abs_res_tol": 1e-9, "start_affine_multiplier_min": 0.01, "max_major_iters": 16,
-                                              "write_output_frequency": 0}, **cfg["opts"]))
-            sn = []
-            ip.setIterationCallback(lambda k: sn.append(ip.snapshot()))
-            ip.optimize()
-            x, z, zl, zu = ip.getOptimizedPoint()[:4]
-            return sn, x.to_numpy(), np.array(z), zl.to_numpy(), zu.to_numpy(), ip.getHistory()
-        finally:
-            L.lib.po_debug_set_switch(SW_S2D_TWO, -1)
-
-    a, b = run(False), run(True)
-    assert len(a[0]) == len(b[0]) >= 8
-    for sa, sb in zip(a[0], b[0]):
-        np.testing.assert_array_equal(sa["counters"], sb["counters"])
-        assert sa["fobj"] == sb["fobj"] and sa["mu"] == sb["mu"]
-        np.testing.assert_array_equal(sa["norms"], sb["norms"])
-    for va, vb in zip(a[1:5], b[1:5]):
-        np.testing.assert_array_equal(va, vb)
-    table = lambda h: [ln for ln in h.splitlines() if ln[:5].strip().isdigit()]  # noqa: E731
-    assert len(table(a[5])) >= 8 and table(a[5]) == table(b[5])
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["seq_lin_c3", "bfgs_c3", "quadratic_c2_large", "quadratic_odd_small", "no_line_search"])

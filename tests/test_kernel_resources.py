@@ -20,8 +20,7 @@ CSRC = os.path.join(ROOT, "paropt_amd", "csrc")
 
 # vector-register copies into the accumulator half of the unified register file (no memory traffic)
 AGPR_PARKED = {
-    r"solve2_dots_kernelILi24ELi1ELi[01]E": 16,
-    r"solve2_dots_kernelILi20ELi1ELi1E": 16,
+    r"solve2_dots_kernelILi24ELi1EE": 16,
 }
 
 
@@ -54,7 +53,7 @@ def test_no_kernel_uses_scratch_memory(meta):
     assert not bad, "kernels with scratch memory: %s" % bad
 
 
-def test_no_vector_register_spills(meta):
+def test_no_vector_register_spills_beyond_the_parked_copies(meta):
     for name, v in meta.items():
         allowed = 0
         for pat, bound in AGPR_PARKED.items():
@@ -66,12 +65,12 @@ def test_no_vector_register_spills(meta):
         assert any(re.search(pat, n) for n in meta), pat
 
 
-def test_hot_kernels_of_the_metric_fit_their_occupancy(meta):
+def test_hot_kernels_of_config_3_fit_their_occupancy(meta):
     """The instantiations config 3 runs: register counts within the budget of the occupancy they
     are compiled for (512 / OCC per lane, unified file)."""
     # (round 5: the tiled group kernels are launched eight workgroups per CU -- 64 registers per lane; left to itself
     # the compiler took 88-106 and five or four of the eight were resident, HISTORY R5.15)
-    want = {r"mdot_kernelILi32E": 128, r"wgram_pc_kernelILi11ELi3ELi1ELi0E": 256, r"solve2_dots_kernelILi11ELi2ELi1E": 256,
+    want = {r"mdot_kernelILi32E": 128, r"wgram_pc_kernelILi11ELi3ELi1ELi0E": 256, r"solve2_dots_kernelILi11ELi2EE": 256,
             r"solve2r_kernelILi1ELi1E": 128, r"group_sum_tiled_kernelILi[01]E": 64, r"group_k0_tiled_kernel": 64,
             r"wgram_pc64_kernelILi(17|18|19|20)E": 256}
     for pat, budget in want.items():

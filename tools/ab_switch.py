@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """A/B of kernel variants inside ONE process (cdna guide rule 24: interleaved rounds, one process, report the
-distribution): the variants are settings of the library's debug switches (core.hpp DbgSwitch, po_debug_set_switch).
+distribution): the variants are settings of the library's debug switches (core.hpp DbgSwitch, po_debug_set_switch;
+the ids are in INTEGRATION.md "Diagnostics").
 
-    python tools/ab_switch.py --variants "0=0;0=1" --rounds 4 --what micro --filter wgram
-    python tools/ab_switch.py --variants "0=0,1=0;0=1,1=1" --rounds 3 --what iter
+    python tools/ab_switch.py --variants "18=0;18=2" --rounds 4 --what micro --filter wgram
+    python tools/ab_switch.py --variants "14=0,15=0;14=1,15=1" --rounds 3 --what iter
 
 micro: po_bench_kernels (every hot kernel in isolation, n = 50 M, c = 32, k = 10); iter: the metric's interior-point
 iteration (config 3, Jacobian rewritten at every gradient call), ms per iteration over 20 iterations after 12."""
@@ -16,10 +17,12 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+SW_COUNT = 38  # core.hpp DbgSwitch: ids 0 .. SW_COUNT - 1 (tests/test_docs.py keeps the two equal)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", required=True, help='e.g. "0=0;0=1": switch id = value, comma separated, per variant')
+    ap.add_argument("--variants", required=True, help='e.g. "18=0;18=2": switch id = value, comma separated, per variant')
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--what", default="micro", choices=["micro", "iter"])
     ap.add_argument("--filter", default="")
@@ -40,7 +43,7 @@ def main():
         variants.append([(int(p.split("=")[0]), int(p.split("=")[1])) for p in v.split(",") if p])
 
     def apply(v):
-        for i in range(17):
+        for i in range(SW_COUNT):
             lib.po_debug_set_switch(i, -1)
         for i, val in v:
             lib.po_debug_set_switch(i, val)
