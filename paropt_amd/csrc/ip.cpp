@@ -31,21 +31,15 @@ static const int LS_SUCCESS = 1, LS_FAILURE = 2, LS_MIN_STEP = 4, LS_MAX_ITERS =
 InteriorPoint::InteriorPoint(Problem *p)
     : prob(p), ctx(p->ctx), n(p->nlocal), c(p->ncon), qn(nullptr), x(nullptr), zl(nullptr),
       zu(nullptr), lb(nullptr), ub(nullptr), g(nullptr), fobj(0.0), barrier_param(0.1),
-      rho_penalty_search(0.0), niter(0), neval(0), ngeval(0), analytic_panel_dots(true),
+      rho_penalty_search(0.0), niter(0), neval(0), ngeval(0),
       iter_cb(nullptr),
       iter_cb_user(nullptr), px(nullptr), pzl(nullptr), pzu(nullptr), Dinv(nullptr), rx(nullptr),
-      tvec(nullptr), xt(nullptr), y_qn(nullptr), s_qn(nullptr), vA(nullptr), qn_created(false), qn_owned(true), wk(0),
+      tvec(nullptr), xt(nullptr), y_qn(nullptr), s_qn(nullptr), vA(nullptr), qn_created(false), qn_owned(true),
       comp_prod(0), comp_count(0), max_rx(0), max_rzl(0), max_rzu(0), sx(1.0), sz(1.0),
-      ptpx_valid(false), residual_fused(false), residual_cached(false), corrector_active(false),
-      norm_type(0), tdots_valid(false), phase_t0(0) {
+      corrector_active(false), norm_type(0), phase_t0(0) {
   qn_handle.qn = nullptr;
   hdiag = nullptr;
-  vA_valid = false;
   inexact_newton_step = false;
-  merit_cache_valid = false;
-  fuse_merit = !dbg_switch(SW_NO_FUSED_MERIT);
-  lean_step = !dbg_switch(SW_NO_LEAN_STEP);
-  recompute_dt = !dbg_switch(SW_NO_RECOMPUTE_DT);
   nhvec = 0;
   nw = p->nwcon;
   has_w = false;
@@ -55,13 +49,9 @@ InteriorPoint::InteriorPoint(Problem *p)
   for (int i = 0; i < 10; i++) w_merit_last[i] = 0.0;
   for (int i = 0; i < 7; i++) w_sums[i] = 0.0;
   for (int i = 0; i < 5; i++) w_maxs[i] = 0.0;
-  // debugging / test switch: re-measure P^T px with explicit mdot passes instead of W-based algebra
-  if (dbg_switch(SW_EXPLICIT_DOTS)) analytic_panel_dots = false;
-  recompute_first_step = !dbg_switch(SW_NO_RECOMPUTE);
-  fuse_mult_update = !dbg_switch(SW_NO_FUSED_UPDATE);
-  recompute_rhs = recompute_first_step && !dbg_switch(SW_NO_RECOMPUTE_RHS);
   use_lower = prob->useLowerBounds();
   use_upper = prob->useUpperBounds();
+  kkt.c = c;
   vars.resize(c);
   res.resize(c);
   step.resize(c);
@@ -69,6 +59,18 @@ InteriorPoint::InteriorPoint(Problem *p)
   cvals.assign(c, 0.0);
   step_mins[0] = step_mins[1] = 1.0;
   setPenaltyGamma(options.real("penalty_gamma"));
+}
+
+InteriorPoint::Forms InteriorPoint::readForms() {
+  Forms f;
+  f.analytic_panel_dots = !dbg_switch(SW_EXPLICIT_DOTS);
+  f.fuse_merit = !dbg_switch(SW_NO_FUSED_MERIT);
+  f.lean_step = !dbg_switch(SW_NO_LEAN_STEP);
+  f.recompute_dt = !dbg_switch(SW_NO_RECOMPUTE_DT);
+  f.recompute_first_step = !dbg_switch(SW_NO_RECOMPUTE);
+  f.recompute_rhs = f.recompute_first_step && !dbg_switch(SW_NO_RECOMPUTE_RHS);
+  f.fuse_mult_update = !dbg_switch(SW_NO_FUSED_UPDATE);
+  return f;
 }
 
 int InteriorPoint::allocate() {
@@ -136,9 +138,7 @@ int InteriorPoint::resetProblemInstance(Problem *p) {  // :745-764
     return PO_ERR_ARG;
   }
   prob = p;
-  ac_valid = false;
-  acz_valid = false;
-  cwx_valid = false;
+  stateReplaced();
   return PO_OK;
 }
 
@@ -300,7 +300,7 @@ static int refreshLiveMirror(Vec *v) {
 }
 
 int InteriorPoint::resetDesignAndBounds() {  // :1249-1251
-  cwx_valid = false;
+  stateReplaced();
   bounds_uni[0] = bounds_uni[1] = 0;  // (found again by the next optimize())
   int rc = prob->getVarsAndBounds(x, lb, ub);
   if (rc != 0) return PO_ERR_USER;
@@ -314,7 +314,7 @@ void InteriorPoint::resetQuasiNewtonHessian() {
 }
 
 int InteriorPoint::initLeastSquaresMultipliers() {  // :5366-5534 (w = 0)
-  acz_valid = false;
+  iterate_flags.acz_valid = false;
   const double mu0 = options.real("init_barrier_param");
   PO_TRY(k_fill(ctx, zl->d, n, mu0));
   PO_TRY(k_fill(ctx, zu->d, n, mu0));
@@ -362,7 +362,7 @@ int InteriorPoint::initAffineStepMultipliers() {  // :5536-5656
   } else {
     PO_TRY(solveKKT(res, 0.0, use_qn, false, 1.0, step));
   }
-  acz_valid = false;
+  iterate_flags.acz_valid = false;
   for (int i = 0; i < c; i++) {
     vars.z[i] = vars.z[i] + step.z[i];
     vars.s[i] = std::max(amin, fabs(vars.s[i] + step.s[i]));
@@ -408,8 +408,8 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
   const bool spec = vectors && spec_enabled && !has_w && mu == barrier_param;
   const double mu2 = spec ? nextMonotoneMu() : 0.0;
   const double beta_mu2 = spec ? options.real("rel_bound_barrier") * mu2 : -1.0;
-  spec_valid = false;
-  spec_dt_valid = false;  // (rx is about to change: a Dinv / t pair left by an earlier pass is stale)
+  iterate_flags.spec_valid = false;
+  scratch_flags.spec_dt_valid = false;  // (rx is about to change: a Dinv / t pair left by an earlier pass is stale)
   // sparse and design blocks of the residual share one collective + sync (the problem's sparse callbacks run in
   // between: built-in problems only)
   BatchScope wbatch(ctx, has_w && prob->reductionsBatchable());
@@ -421,14 +421,14 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
     // A problem that declared its dense constraints linear (constant Jacobian): A^T z is kept in `acz` and
     // follows the multiplier steps (computeStepAndUpdate), so the residual does not stream the c constraint
     // gradients; it is rebuilt from the gradients every kAczRefresh uses to bound the round-off drift.
-    if (prob->linear_constraints && ac_valid && c > 0) {
+    if (prob->linear_constraints && iterate_flags.ac_valid && c > 0) {
       if (!acz) acz = vec_new(ctx, n);
       if (!acz) return PO_ERR_HIP;
-      if (!acz_valid || acz_age >= kAczRefresh) {
+      if (!iterate_flags.acz_valid || acz_age >= kAczRefresh) {
         std::vector<const double *> Ap;
         for (Vec *a : Ac) Ap.push_back(a->d);
         PO_TRY(k_panel_axpy(ctx, acz->d, 0.0, nullptr, 0.0, vars.z.data(), Ap.data(), c, n));
-        acz_valid = true;
+        iterate_flags.acz_valid = true;
         acz_age = 0;
         acz_rebuilt = true;
       }
@@ -463,11 +463,12 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
       PO_TRY(k_kkt_res_update(ctx, bounds(), g->d, A.data(), zc.data(), acz_mode ? 0 : (int)A.size(), beta_mu, n,
                               rx->d, out, yqn_complete ? yqn_complete->d : nullptr, zl->d, pzl->d, zu->d, pzu->d,
                               upd->a, upd->eps, (yqn_complete || az_acz != 0.0) ? vA->d : nullptr,
-                              upd->az, acz_mode ? acz->d : nullptr, az_acz, pz_stored ? nullptr : px->d,
-                              pz_stored ? nullptr : xt->d, step_beta_mu, beta_mu2, have_gcol ? &gcol : nullptr, 1.0,
+                              upd->az, acz_mode ? acz->d : nullptr, az_acz, step_flags.pz_stored ? nullptr : px->d,
+                              step_flags.pz_stored ? nullptr : xt->d, step_beta_mu, beta_mu2,
+                              have_gcol ? &gcol : nullptr, 1.0,
                               spec_dt ? Dinv->d : nullptr, spec_dt ? tvec->d : nullptr, sdiag, sbmu));
       if (spec_dt) {
-        spec_dt_valid = true;
+        scratch_flags.spec_dt_valid = true;
         spec_dt_diag = sdiag;
         spec_dt_bmu = sbmu;
       }
@@ -489,7 +490,7 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
       spec_mu = mu2;
       spec_max[0] = o[11];
       spec_max[1] = o[12];
-      spec_valid = true;
+      iterate_flags.spec_valid = true;
     }
     comp_prod = o[0];
     comp_count = o[1];
@@ -590,8 +591,8 @@ int InteriorPoint::getComplementarity(double *comp) {
 // the KKT system
 // ================================================================================================
 int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs_mu) {  // setUpKKTDiagSystem + setUpKKTSystem
-  ptpx_valid = false;
-  t0_valid = false;
+  step_flags.ptpx_valid = false;
+  scratch_flags.t0_valid = false;
   const double sigma = options.real("qn_sigma");
   const bool use_hdiag = options.integer("use_diag_hessian") && hdiag;  // h_i replaces b0 (:1840-1842)
   const double b0 = (!use_hdiag && qn && (use_qn || diag_only)) ? qn->diag() : 0.0;
@@ -600,21 +601,21 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // pre-weighted, column, so that P^T t -- the mdot pass at the head of solveKKT -- comes out of the pass over P
   // that the Schur complements need anyway.
   const bool fuse_t = rhs_mu && !has_w && c + (qn && use_qn && !diag_only ? qn->size() : 0) > 0;
-  t_is_plain_dinv_d1 = false;
+  scratch_flags.t_is_plain_dinv_d1 = false;
   // sparse constraints: the RAW right-hand side d1 of the first solve (the block solve applies to it) comes out of
   // the same pass over the bound data as Dinv (round 4; it is used below when the fused first solve is taken)
   const bool raw_d1_w = has_w && rhs_mu && !corrector_active;
-  const bool have_spec_dt = spec_dt_valid;
-  spec_dt_valid = false;  // consumed here, or overwritten below
+  const bool have_spec_dt = scratch_flags.spec_dt_valid;
+  scratch_flags.spec_dt_valid = false;  // consumed here, or overwritten below
   if (fuse_t && have_spec_dt && !use_hdiag && spec_dt_diag == b0 + sigma &&
       spec_dt_bmu == options.real("rel_bound_barrier") * (*rhs_mu)) {
     // the residual pass of this iterate left exactly this Dinv and t behind (kkt_res_update_kernel)
-    t_is_plain_dinv_d1 = true;
+    scratch_flags.t_is_plain_dinv_d1 = true;
     t0_diag = b0 + sigma;
   } else if (fuse_t) {
     PO_TRY(k_dinv_d1(ctx, bounds(), b0 + sigma, use_hdiag ? hdiag->d : nullptr, rx->d,
                      options.real("rel_bound_barrier") * (*rhs_mu), n, Dinv->d, tvec->d));
-    t_is_plain_dinv_d1 = !use_hdiag;
+    scratch_flags.t_is_plain_dinv_d1 = !use_hdiag;
     t0_diag = b0 + sigma;
   } else if (raw_d1_w) {
     PO_TRY(k_dinv_d1(ctx, bounds(), b0 + sigma, use_hdiag ? hdiag->d : nullptr, rx->d,
@@ -640,10 +641,10 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
     std::vector<double> W2((size_t)mt * mt, 0.0);
     PO_TRY(k_wgram(ctx, Dinv->d, P2.data(), mt, n, W2.data(), Sp.data(), Zo.data(), k, b0z, fuse_t ? 1 : 0));
     qn->pendingZDone();
-    W.assign((size_t)m2 * m2, 0.0);
+    kkt.W.assign((size_t)m2 * m2, 0.0);
     auto perm = [&](int i) { return i < c ? k + i : i - c; };  // index in [Ac | Z] -> index in [Z | Ac]
     for (int j = 0; j < m2; j++)
-      for (int i = 0; i < m2; i++) W[i + (size_t)m2 * j] = W2[perm(i) + (size_t)mt * perm(j)];
+      for (int i = 0; i < m2; i++) kkt.W[i + (size_t)m2 * j] = W2[perm(i) + (size_t)mt * perm(j)];
     if (fuse_t) {
       t0dots.assign(m2, 0.0);
       for (int i = 0; i < m2; i++) t0dots[i] = W2[perm(i) + (size_t)mt * m2];
@@ -657,7 +658,7 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
     P = panel(use_qn && !diag_only, &k2);
   }
   const int m = c + k;
-  wk = k;
+  kkt.k = k;
   // Sparse constraints: the right-hand side of the first solve goes through the quasi-definite block solve,
   // t = [K0^-1 (d1, d2)]_x, which needs Cw -- so the factor comes first, then t (and the sparse multiplier part
   // wyw), then the Gram pass with t as its pre-weighted last column, as on the dense path.
@@ -689,7 +690,7 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
     ggp = &gram_groups;
   }
   if (!fuse_z) {
-    W.assign((size_t)m * m, 0.0);
+    kkt.W.assign((size_t)m * m, 0.0);
     if (m > 0 && (fuse_t || fuse_tw) && m + 1 <= kWgramMaxVecs) {
       std::vector<const double *> Pt(P);
       Pt.push_back(tvec->d);
@@ -700,19 +701,19 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
       t0dots.assign(m, 0.0);
       after_reduce(ctx, [this, m, mt] {
         for (int j = 0; j < m; j++)
-          for (int i = 0; i < m; i++) W[i + (size_t)m * j] = Wt_buf[i + (size_t)mt * j];
+          for (int i = 0; i < m; i++) kkt.W[i + (size_t)m * j] = Wt_buf[i + (size_t)mt * j];
         for (int i = 0; i < m; i++) t0dots[i] = Wt_buf[i + (size_t)mt * m];
       });
       t0_ready = true;
     } else {
       if (m > 0)
-        PO_TRY(k_wgram(ctx, Dinv->d, P.data(), m, n, W.data(), nullptr, nullptr, 0, 0.0, 0, wbatch.open, ggp,
+        PO_TRY(k_wgram(ctx, Dinv->d, P.data(), m, n, kkt.W.data(), nullptr, nullptr, 0, 0.0, 0, wbatch.open, ggp,
                        &panel_done));
       t0dots.clear();
     }
   }
   if ((fuse_t || fuse_tw) && m > 0 && t0_ready && (int)t0dots.size() == m) {
-    t0_valid = true;
+    scratch_flags.t0_valid = true;
     t0_mu = *rhs_mu;
   }
   // W -= U^T Cw U (d1v is free again: scratch of the panel image; tvec holds t)
@@ -722,42 +723,16 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // (tests/test_gpu_kat.py::test_kat_detects_a_perturbed_gram)
   // -- reachable only through po_debug_set_switch and only inside po_ip_debug_kkt (no environment variable)
   if (m > 1 && debug_keep_schur && dbg_switch(SW_PERTURB_W) != 0) {
-    W[1] *= 1.0 + 1e-9;
-    W[m] = W[1];
+    kkt.W[1] *= 1.0 + 1e-9;
+    kkt.W[m] = kkt.W[1];
   }
-  // G = W_AA + diag(s/zs + t/zt)   (:1952-1970)
-  Gf.assign((size_t)c * c, 0.0);
-  gpiv.assign(c, 0);
-  for (int j = 0; j < c; j++)
-    for (int i = 0; i < c; i++) Gf[i + (size_t)c * j] = W[i + (size_t)m * j];
-  for (int i = 0; i < c; i++) Gf[(size_t)i * (c + 1)] += vars.s[i] / vars.zs[i] + vars.t[i] / vars.zt[i];
-  if (debug_keep_schur) Gmat0 = Gf;  // as assembled, for po_ip_debug_kkt only
-  if (c > 0) lu_factor(c, Gf.data(), c, gpiv.data());
-  // Ce = W_ZZ - W_ZA G^-1 W_AZ - M / (d0 d0^T)   (:2634-2667 via SURVEY.md 3.4)
-  Cef.clear();
-  cpiv.clear();
+  const double *d0 = nullptr, *M = nullptr;
   if (k > 0) {
-    const double *d0, *M;
     double b0_;
     qn->getCompactMat(&b0_, &d0, &M, nullptr);
-    Cef.assign((size_t)k * k, 0.0);
-    cpiv.assign(k, 0);
-    std::vector<double> col(c > 0 ? c : 1);
-    for (int j = 0; j < k; j++) {
-      for (int i = 0; i < c; i++) col[i] = W[i + (size_t)m * (c + j)];  // W_AZ[:, j]
-      if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), col.data());
-      for (int i = 0; i < k; i++) {
-        double v = W[(c + i) + (size_t)m * (c + j)];
-        for (int l = 0; l < c; l++) v -= W[(c + i) + (size_t)m * l] * col[l];
-        v -= M[i + (size_t)k * j] / (d0[i] * d0[j]);
-        Cef[i + (size_t)k * j] = v;
-      }
-    }
-    if (debug_keep_schur) Ce0 = Cef;
-    lu_factor(k, Cef.data(), k, cpiv.data());
-  } else {
-    Ce0.clear();
   }
+  kkt.factor(vars, d0, M, debug_keep_schur ? &Gmat0 : nullptr, debug_keep_schur ? &Ce0 : nullptr);
+  if (k == 0) Ce0.clear();
   return PO_OK;
 }
 
@@ -769,10 +744,7 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
                             Dense &out, bool fuse_residual) {
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   const int k = (qn && use_qn) ? qn->size() : 0;
-  if (k != wk) {
-    set_error("internal: panel width changed between setUpKKTSystem and solve (%d vs %d)", k, wk);
-    return PO_ERR_ARG;
-  }
+  PO_TRY(kkt.checkWidth(k));
   const int m = c + k;
   // The panel [Ac | Z] is only asked for when a pass needs it: zPointers() FORMS unformed L-SR1 columns (one pass
   // over 3k vectors, k of them written).
@@ -796,7 +768,7 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
     return PO_ERR_ARG;
   }
   // t = Dinv o d1 and P^T t were produced by setUpKKTSystem's Gram pass when the right-hand side was known then
-  const bool have_t0 = !refine_pass && t0_valid && t0_mu == mu && !corr && (int)t0dots.size() == m;
+  const bool have_t0 = !refine_pass && scratch_flags.t0_valid && t0_mu == mu && !corr && (int)t0dots.size() == m;
   std::vector<double> dots(m > 0 ? m : 1, 0.0);
   if (corr_fused) {
     // corrector products, t = Dinv o d1 and P^T t in ONE pass (the bits of k_corrector + k_d1 + k_mdot)
@@ -807,63 +779,32 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
     if (!refine_pass && !have_t0) PO_TRY(k_d1(ctx, bounds(), rx->d, Dinv->d, beta_mu, n, tvec->d, cl, cu));
     if (have_t0) {
       for (int i = 0; i < m; i++) dots[i] = t0dots[i];
-    } else if (refine_pass && tdots_valid && (int)tdots.size() == m) {
+    } else if (refine_pass && step_flags.tdots_valid && (int)tdots.size() == m) {
       dots = tdots;  // P^T t' came out of the fused first pass (k_solve2_dots)
     } else if (m > 0) {
       need_panel();
       PO_TRY(k_mdot(ctx, tvec->d, P.data(), m, n, dots.data()));
     }
   }
-  if (!refine_pass) first_t_recomputable = have_t0 && t_is_plain_dinv_d1;  // tvec / Dinv are dinv_d1's for this mu
-  if (!refine_pass) t0_valid = false;  // tvec is overwritten by the passes below
-  tdots_valid = false;
-  // yz = G^-1 (d3 - A yx0)   (:2150-2159)
-  std::vector<double> yz(c > 0 ? c : 1, 0.0), yz2(c > 0 ? c : 1, 0.0), zeta(k > 0 ? k : 1, 0.0);
-  for (int i = 0; i < c; i++) {
-    yz[i] = (b.z[i] + (b.zs[i] + vars.s[i] * b.s[i]) / vars.zs[i] -
-             (b.zt[i] + vars.t[i] * b.t[i]) / vars.zt[i] - dots[i]);
-  }
-  if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz.data());
-  if (k > 0) {
-    // Z^T px0 = Z^T Dinv d1 + W_ZA yz ; zeta = Ce^-1 (Z^T px0) ; yz2 = G^-1 (-W_AZ zeta)
-    for (int i = 0; i < k; i++) {
-      double v = dots[c + i];
-      for (int l = 0; l < c; l++) v += W[(c + i) + (size_t)m * l] * yz[l];
-      zeta[i] = v;
-    }
-    lu_solve(k, Cef.data(), k, cpiv.data(), zeta.data());
-    for (int i = 0; i < c; i++) {
-      double v = 0.0;
-      for (int j = 0; j < k; j++) v += W[i + (size_t)m * (c + j)] * zeta[j];
-      yz2[i] = -v;
-    }
-    if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz2.data());
-  }
-  std::vector<double> alpha(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < c; i++) alpha[i] = yz[i] - yz2[i];
-  for (int j = 0; j < k; j++) alpha[c + j] = -zeta[j];
-  // P^T (t + Dinv P alpha) = dots + W alpha
-  if (!refine_pass) ptpx.assign(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < m; i++) {
-    double v = dots[i];
-    for (int j = 0; j < m; j++) v += W[i + (size_t)m * j] * alpha[j];
-    ptpx[i] = refine_pass ? ptpx[i] + v : v;
-  }
-  ptpx_valid = true;
-  merit_cache_valid = false;  // the step is about to change
-  px_amax_valid = false;
-  fused_merit_valid = false;
-  w_comp_valid = w_merit_cache_valid = false;
-  pz_stored = true;
+  // tvec / Dinv are dinv_d1's for this mu
+  if (!refine_pass) scratch_flags.first_t_recomputable = have_t0 && scratch_flags.t_is_plain_dinv_d1;
+  if (!refine_pass) scratch_flags.t0_valid = false;  // tvec is overwritten by the passes below
+  const bool deferred = refine_pass && step_flags.step_deferred;  // the first pass stored no step
+  stepWillChange();
+  Bordered::Sol sol;
+  kkt.solve(1.0, b, vars, dots.data(), &sol);
+  const std::vector<double> &alpha = sol.coef;
+  kkt.panelDots(dots.data(), sol, refine_pass, &ptpx);  // P^T (t + Dinv P alpha) = dots + W alpha
+  step_flags.ptpx_valid = true;
   // Fused refinement residual: the coefficients of addKKTResStep (:1475-1483) are known before
   // the axpy pass starts (A-part = p.z = alpha_A; Z-part = d0 M^-1 d0 Z^T px with Z^T px = ptpx),
   // so the same pass over P also emits the right-hand side t' of the refinement solve.
   const bool seq_lin = options.integer("sequential_linear_method");
   const int kq = (qn && !seq_lin) ? qn->size() : 0;
   // (a panel wider than one kernel's argument tables takes the plain sequence: the launchers collapse it, kernels.hip)
-  const bool fuse = fuse_residual && !refine_pass && analytic_panel_dots && kq == k &&
+  const bool fuse = fuse_residual && !refine_pass && forms.analytic_panel_dots && kq == k &&
                     !options.integer("use_diag_hessian") && !inexact_newton_step && m <= kMaxPanel;
-  vA_valid = true;
+  step_flags.vA_valid = true;
   std::vector<double> coef(m > 0 ? m : 1, 0.0);
   double diag = options.real("qn_sigma");
   if (fuse) {
@@ -884,58 +825,56 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
     // NOT stored: the refinement pass recomputes it from (t, alpha) in registers (k_solve2r) -- four output streams
     // less, and an HBM write costs about four reads here.  t' goes to xt (free during the solves), t stays in tvec.
     std::vector<double> out(m + 2, 0.0);
-    const bool defer = recompute_first_step;
+    const bool defer = forms.recompute_first_step;
     // ... and with recompute_rhs not even t': the pass only takes the products P^T t', the refinement pass forms t'
     // again from the residual coefficients (an output stream costs about four input streams)
-    double *tp_out = !defer ? tvec->d : (recompute_rhs ? nullptr : xt->d);
+    double *tp_out = !defer ? tvec->d : (forms.recompute_rhs ? nullptr : xt->d);
     // Dinv and t re-formed in the element epilogue from the bound data and rx it loads anyway (same bits)
-    const bool redo_dt1 = recompute_dt && defer && recompute_rhs && first_t_recomputable;
+    const bool redo_dt1 = forms.recompute_dt && defer && forms.recompute_rhs && scratch_flags.first_t_recomputable;
     const double *t_in = redo_dt1 ? nullptr : tvec->d;
     PO_TRY(k_solve2_dots(ctx, bounds(), t_in, Dinv->d, alpha.data(), coef.data(), P.data(), m, beta_mu, tau, rx->d,
                          diag, n, px->d, pzl->d, pzu->d, tp_out, vA->d, c, out.data(), nullptr, defer ? 0 : 1, 0,
                          t0_diag));
     tdots.assign(out.begin(), out.begin() + m);
-    tdots_valid = true;
+    step_flags.tdots_valid = true;
     step_mins[0] = out[m];
     step_mins[1] = out[m + 1];
-    step_deferred = defer;
+    step_flags.step_deferred = defer;
     if (defer) {
       alpha_first = alpha;
       coef_first = coef;
       diag_first = diag;
     }
-  } else if (refine_pass && step_deferred) {
-    step_deferred = false;
+  } else if (deferred) {
     // the same sweep takes the sums the complementarity check of scaleKKTStep and the merit derivative need of the
     // final step (see solve2r_kernel): no separate pass over the step afterwards
-    const bool take_merit = fuse_merit && recompute_rhs && !corr;
+    const bool take_merit = forms.fuse_merit && forms.recompute_rhs && !corr;
     const double *gm = take_merit ? g->d : nullptr;
     double *mo = take_merit ? fused_merit : nullptr;
     // lean step: (pzl, pzu) stay in registers; their only consumer left, the multiplier update, re-forms them
-    const bool lean = lean_step && lean_step_allowed && take_merit && iterate_logs_valid;
+    const bool lean = forms.lean_step && lean_step_allowed && take_merit && iterate_flags.iterate_logs_valid;
     double *pzl_out = lean ? nullptr : pzl->d, *pzu_out = lean ? nullptr : pzu->d;
     // Dinv and the first right-hand side t re-formed in registers from data the pass loads anyway (same bits)
-    const bool redo_dt = recompute_dt && recompute_rhs && first_t_recomputable;
+    const bool redo_dt = forms.recompute_dt && forms.recompute_rhs && scratch_flags.first_t_recomputable;
     const double *t1p = redo_dt ? nullptr : tvec->d;
     if (lean) {
-      pz_stored = false;
+      step_flags.pz_stored = false;
       step_beta_mu = beta_mu;
     }
-    PO_TRY(k_solve2r(ctx, bounds(), t1p, recompute_rhs ? nullptr : xt->d, Dinv->d, alpha_first.data(), alpha.data(),
-                     P.data(), m, beta_mu, tau, n, px->d, pzl_out, pzu_out, vA->d, c, step_mins, coef_first.data(),
-                     rx->d, diag_first, 0, gm, mo, t0_diag));
+    PO_TRY(k_solve2r(ctx, bounds(), t1p, forms.recompute_rhs ? nullptr : xt->d, Dinv->d, alpha_first.data(),
+                     alpha.data(), P.data(), m, beta_mu, tau, n, px->d, pzl_out, pzu_out, vA->d, c, step_mins,
+                     coef_first.data(), rx->d, diag_first, 0, gm, mo, t0_diag));
     if (take_merit) {
       after_reduce(ctx, [this] {
         step_mins[0] = fused_merit[7];
         step_mins[1] = fused_merit[8];
-        fused_merit_valid = true;
+        step_flags.fused_merit_valid = true;
       });
     }
   } else if (corr_fused) {
-    step_deferred = false;
     // corrector solve: the corrector terms re-formed from the affine step this pass overwrites, and the sums of
     // scaleKKTStep / evalMeritInitDeriv of the step it has in registers (k_comp_merit and its round trip disappear)
-    const bool want_logs = !iterate_logs_valid;
+    const bool want_logs = !iterate_flags.iterate_logs_valid;
     PO_TRY(k_solve2c(ctx, bounds(), tvec->d, Dinv->d, alpha.data(), P.data(), m, beta_mu, tau, n, px->d, pzl->d,
                      pzu->d, vA->d, c, g->d, want_logs ? 1 : 0, corr_out));
     after_reduce(ctx, [this, want_logs] {
@@ -946,27 +885,17 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
       if (want_logs) {  // the barrier sums of the iterate, as k_comp_merit takes them
         iterate_logs[0] = corr_out[7];
         iterate_logs[1] = corr_out[8];
-        iterate_logs_valid = true;
+        iterate_flags.iterate_logs_valid = true;
       }
-      fused_merit_valid = true;
+      step_flags.fused_merit_valid = true;
     });
   } else {
-    if (!refine_pass) step_deferred = false;
     PO_TRY(k_solve2(ctx, bounds(), tvec->d, Dinv->d, alpha.data(), P.data(), m, beta_mu,
                     refine_pass ? 1 : 0, tau, n, px->d, pzl->d, pzu->d, step_mins,
                     fuse ? coef.data() : nullptr, rx->d, diag, tvec->d, vA->d, c, cl, cu));
   }
-  residual_fused = fuse;
-  // dense blocks: full solve (:2165-2170) minus the bx-only solve (:2300-2305)
-  for (int i = 0; i < c; i++) {
-    const double zs1 = yz[i] - b.s[i];
-    const double zt1 = -b.t[i] - yz[i];
-    out.z[i] = yz[i] - yz2[i];
-    out.zs[i] = zs1 - yz2[i];
-    out.zt[i] = zt1 + yz2[i];
-    out.s[i] = (b.zs[i] - vars.s[i] * zs1) / vars.zs[i] + (vars.s[i] * yz2[i]) / vars.zs[i];
-    out.t[i] = (b.zt[i] - vars.t[i] * zt1) / vars.zt[i] - (vars.t[i] * yz2[i]) / vars.zt[i];
-  }
+  step_flags.residual_fused = fuse;
+  kkt.backSubstitute(1.0, b, vars, sol, true, out);
   return PO_OK;
 }
 
@@ -992,7 +921,7 @@ int InteriorPoint::computeKKTStepWithRefinement(double mu, bool use_qn, double t
     };
     const int mq = c + kq;
     std::vector<double> dots(mq > 0 ? mq : 1, 0.0);
-    if (analytic_panel_dots && ptpx_valid && mq == c + wk) {
+    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
       for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
     } else if (mq > 0) {
       need_pq();
@@ -1023,7 +952,7 @@ int InteriorPoint::computeKKTStepWithRefinement(double mu, bool use_qn, double t
         for (int j = 0; j < kq; j++) coef[c + j] = rz[j];
       }
     }
-    if (!(it == 0 && residual_fused)) {
+    if (!(it == 0 && step_flags.residual_fused)) {
       need_pq();
       PO_TRY(k_res_step(ctx, bounds(), rx->d, px->d, pzl->d, pzu->d, Dinv->d, coef.data(), Pq.data(),
                         mres, diag, beta_mu, n, tvec->d));
@@ -1053,9 +982,10 @@ int InteriorPoint::computeKKTStepWithRefinement(double mu, bool use_qn, double t
 
 int InteriorPoint::checkKKTStep(int iteration, double mu) {
   const double beta_mu = options.real("rel_bound_barrier") * mu;
-  if (!pz_stored) {  // lean step: materialise the bound-multiplier steps exactly as the update will form them
+  // lean step: materialise the bound-multiplier steps exactly as the update will form them
+  if (!step_flags.pz_stored) {
     PO_TRY(k_form_pz(ctx, bounds(), px->d, step_beta_mu, n, pzl->d, pzu->d));
-    pz_stored = true;
+    step_flags.pz_stored = true;
   }
   const bool seq_lin = options.integer("sequential_linear_method");
   int kq = 0;
@@ -1112,13 +1042,13 @@ int InteriorPoint::checkKKTStep(int iteration, double mu) {
 }
 
 int InteriorPoint::checkGradients(double dh, std::string *report) {  // :6196-6199
-  spec_dt_valid = false;  // (tvec is its scratch)
+  scratchLent();  // (tvec and xt are its scratch)
   return prob->checkGradients(dh, x, options.integer("use_hvec_product"), xt, tvec, report);
 }
 
 int InteriorPoint::checkMeritFuncGradient(Vec *xpt, double dh, double out[2]) {  // :3280-3432
   if (xpt) PO_TRY(k_copy(ctx, x->d, xpt->d, n));
-  cwx_valid = false;
+  iterateReplaced();
   if (prob->evalObjCon(x, &fobj, cvals.data()) != 0) {
     fprintf(stderr, "ParOpt: Function and constraint evaluation failed\n");
     return PO_ERR_USER;
@@ -1129,11 +1059,7 @@ int InteriorPoint::checkMeritFuncGradient(Vec *xpt, double dh, double out[2]) { 
     return PO_ERR_USER;
   }
   ngeval++;
-  ac_valid = true;
-  acz_valid = false;
-  if (!pz_stored) {  // a lean step keeps px only; nothing below reads pzl / pzu
-    pz_stored = true;
-  }
+  iterate_flags.ac_valid = true;
   if (xpt) {  // a direction of our own: px = -g / |g|, fixed slack steps, zero elsewhere (:3327-3352)
     double g2 = 0.0;
     PO_TRY(k_reduce1(ctx, RED_SUMSQ, g->d, nullptr, n, &g2));
@@ -1154,11 +1080,7 @@ int InteriorPoint::checkMeritFuncGradient(Vec *xpt, double dh, double out[2]) { 
     }
   }
   sx = sz = 1.0;
-  ptpx_valid = false;
-  merit_cache_valid = false;
-  fused_merit_valid = false;
-  w_comp_valid = w_merit_cache_valid = false;
-  px_amax_valid = false;
+  stepWillChange();  // (a lean step keeps px only; nothing below reads pzl / pzu)
   double m0 = 0.0, dm0 = 0.0;
   PO_TRY(evalMeritInitDeriv(1.0, &m0, &dm0));
   // the merit function at (x + dh px, s + dh ps, t + dh pt, sw + dh psw, tw + dh ptw) (:3386-3409)
@@ -1172,8 +1094,6 @@ int InteriorPoint::checkMeritFuncGradient(Vec *xpt, double dh, double out[2]) { 
   {
     // k_trial clamps into [lb + eps, ub - eps]; with eps = 0 an interior point is left alone
     PO_TRY(k_trial(ctx, bounds(), px->d, dh, eps, n, xt->d, sums));
-    trial_logs_valid = false;
-    s_qn_from_trial = false;
   }
   double ftemp = 0.0;
   if (prob->evalObjCon(xt, &ftemp, cs.data()) != 0) {
@@ -1230,23 +1150,13 @@ int InteriorPoint::debugSetState(const double *z, const double *s, const double 
     norm_type = nt == "infinity" ? 0 : (nt == "l1" ? 1 : 2);
   }
   // nothing carried between the passes of an iteration survives a state written from outside
-  cwx_valid = trial_cw_valid = false;
-  residual_cached = false;
-  iterate_logs_valid = trial_logs_valid = fused_merit_valid = false;
-  w_comp_valid = w_merit_cache_valid = merit_cache_valid = false;
-  px_first_only = false;
-  spec_enabled = spec_valid = false;
-  acz_valid = false;
-  ptpx_valid = tdots_valid = t0_valid = false;
-  step_deferred = false;
-  s_qn_from_trial = false;
+  stateReplaced();
+  spec_enabled = false;
   corrector_active = false;
   inexact_newton_step = false;
-  pz_stored = true;
-  panel_valid = false;
   if (prob->evalObjCon(x, &fobj, cvals.data()) != 0) return PO_ERR_USER;
   if (prob->evalObjConGradient(x, g, Ac.data()) != 0) return PO_ERR_USER;
-  ac_valid = true;
+  iterate_flags.ac_valid = true;
   return PO_OK;
 }
 
@@ -1304,7 +1214,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
     if (step.zt[i] < 0.0) max_z = std::min(max_z, -vars.zt[i] / step.zt[i]);
   }
   double cs[2];
-  if (fused_merit_valid && !has_w && dbg_switch(SW_MPC_POLY) != 0) {
+  if (step_flags.fused_merit_valid && !has_w && dbg_switch(SW_MPC_POLY) != 0) {
     // the refinement pass of the affine solve took the complementarity polynomial of its step (solve2r_kernel):
     // S00 + ax S10 + az S01 + ax az S11 at the probe lengths, S00 / the bound count from the residual pass of this
     // iterate -- no pass over the step and no host round trip (round 6; scaleKKTStep uses the same form)
@@ -1338,7 +1248,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
     // corrector: res.zl -= px*pzl, res.zu += px*pzu, res.zs -= ps*pzs, res.zt -= pt*pzt of the
     // affine step (:1729-1789); no refinement with the corrector (:5040-5041)
     // (one-pass corrector right-hand side + corrector solve with the merit sums: see solveKKT)
-    corrector_fused = !has_w && c + wk >= 1 && c + wk <= kCorrDotsMax &&
+    corrector_fused = !has_w && c + kkt.k >= 1 && c + kkt.k <= kCorrDotsMax &&
                       dbg_switch(SW_MPC_FUSE) != 0;
     if (!corrector_fused) PO_TRY(k_corrector(ctx, bounds(), px->d, pzl->d, pzu->d, n, s_qn->d, y_qn->d));
     denseResidual(barrier_param, res);
@@ -1410,7 +1320,7 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     }
   }
   double out[9], wprod = 0.0;
-  if (fused_merit_valid && iterate_logs_valid && (!has_w || w_comp_valid)) {
+  if (step_flags.fused_merit_valid && iterate_flags.iterate_logs_valid && (!has_w || step_flags.w_comp_valid)) {
     // (sparse constraints: the slacks' share of the polynomial came out of the step kernel, S00 = the complementarity
     // sum of the iterate's sparse slacks from its residual pass)
     if (has_w) wprod = w_sums[0] + ax * w_comp_poly[0] + az * w_comp_poly[1] + ax * az * w_comp_poly[2];
@@ -1433,12 +1343,12 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     merit_cache[4] = fused_merit[5];
     merit_cache[5] = fused_merit[6];
     merit_cache[6] = fused_merit[9];
-    merit_cache_valid = true;
+    step_flags.merit_cache_valid = true;
   } else if (!has_w) {
     // one pass also yields the merit pieces and the step norm the line search is about to ask for
     PO_TRY(k_comp_merit(ctx, bounds(), px->d, pzl->d, pzu->d, ax, az, g->d, n, out));
     for (int i = 0; i < 7; i++) merit_cache[i] = out[2 + i];
-    merit_cache_valid = true;
+    step_flags.merit_cache_valid = true;
   } else {
     BatchScope batch(ctx);  // design and sparse parts of the complementarity: one collective + sync
     // (the design pass also yields the merit pieces and max|px| the line search is about to ask for, as on the
@@ -1447,7 +1357,7 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     PO_TRY(wCompStep(ax, az, &wprod));  // :2866-2889
     PO_TRY(batch.end());
     for (int i = 0; i < 7; i++) merit_cache[i] = out[2 + i];
-    merit_cache_valid = true;
+    step_flags.merit_cache_valid = true;
   }
   double prod = out[0] / options.real("rel_bound_barrier"), count = out[1];
   if (has_w) {
@@ -1533,7 +1443,7 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
     // design part, panel products (when not known analytically) and sparse part: one collective + sync (the
     // problem's sparse callbacks run in between: built-in problems only)
     BatchScope batch(ctx, has_w && prob->reductionsBatchable());
-    if (merit_cache_valid) {
+    if (step_flags.merit_cache_valid) {
       out[0] = merit_cache[0];
       out[1] = merit_cache[1];
       out[2] = sx * merit_cache[2];
@@ -1544,17 +1454,17 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
       PO_TRY(k_merit0(ctx, bounds(), px->d, sx, g->d, n, out));
       if (batch.open) {  // max|px| for the line search's minimum step rides in this batch (its own sync otherwise)
         PO_TRY(k_reduce1(ctx, RED_AMAX, px->d, nullptr, n, &px_amax_w));
-        px_amax_valid = true;
+        step_flags.px_amax_valid = true;
       }
     }
-    if (analytic_panel_dots && ptpx_valid && mq == c + wk) {
+    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
       for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
     } else if (mq > 0) {
       int k2 = 0;
       Pq = panel(qn && !seq_lin, &k2);
       PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));
     }
-    if (has_w && w_merit_cache_valid) {
+    if (has_w && step_flags.w_merit_cache_valid) {
       // taken at sx = 1 in the refinement batch (solveKKTW); every sum that depends on the step is linear in sx > 0
       for (int i = 0; i < 10; i++) wm[i] = w_merit_cache[i];
       wm[2] *= sx;
@@ -1688,22 +1598,22 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
     BatchScope batch(ctx, batchable);
     PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums, sq));
     s_qn_a = alpha * sx;
-    s_qn_from_trial = sq != nullptr;
+    iterate_flags.s_qn_from_trial = sq != nullptr;
     clampStepDense(rs, vars.s, alpha, step.s, eps, true);
     clampStepDense(rt, vars.t, alpha, step.t, eps, true);
     userBegin();
     int fail_obj = prob->evalObjCon(xt, &fobj, cvals.data());
     userEnd();
-    trial_cw_valid = false;
+    iterate_flags.trial_cw_valid = false;
     if (has_w && batchable && !fail_obj) {  // the sparse slack sums ride in the same collective
       if (prob->evalSparseCon(xt, wtmp) != 0) return PO_ERR_USER;
-      trial_cw_valid = true;  // wtmp = cw(xt): handed to the iterate when this trial is accepted
+      iterate_flags.trial_cw_valid = true;  // wtmp = cw(xt): handed to the iterate when this trial is accepted
       PO_TRY(k_w_trial(ctx, wv(), wp(), alpha * sx, eps, gsw->d, gtw->d, wtmp->d, nw, wsums));
     }
     PO_TRY(batch.end());
     trial_logs[0] = sums[0];  // barrier sums at the point xt holds now
     trial_logs[1] = sums[1];
-    trial_logs_valid = true;
+    iterate_flags.trial_logs_valid = true;
     neval++;
     if (fail_obj) {
       fprintf(stderr, "ParOpt: Evaluation failed during line search, trying new point\n");
@@ -1712,7 +1622,7 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
     }
     if (has_w && !batchable) {
       if (prob->evalSparseCon(xt, wtmp) != 0) return PO_ERR_USER;
-      trial_cw_valid = true;
+      iterate_flags.trial_cw_valid = true;
       PO_TRY(k_w_trial(ctx, wv(), wp(), alpha * sx, eps, gsw->d, gtw->d, wtmp->d, nw, wsums));
     }
     merit = evalMeritFromSums(fobj, cvals.data(), rs.data(), rt.data(), sums[0], sums[1],
@@ -1758,19 +1668,19 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
     }
     if (alpha != best_alpha) {
       alpha = best_alpha;
-      trial_cw_valid = false;  // xt is rebuilt below without its sparse constraint values
+      iterate_flags.trial_cw_valid = false;  // xt is rebuilt below without its sparse constraint values
       double sums[2];
       BatchScope batch(ctx, batchable);
       PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums, sq));
       s_qn_a = alpha * sx;
-      s_qn_from_trial = sq != nullptr;
+      iterate_flags.s_qn_from_trial = sq != nullptr;
       userBegin();
       int fail_obj = prob->evalObjCon(xt, &fobj, cvals.data());
       userEnd();
       PO_TRY(batch.end());
       trial_logs[0] = sums[0];
       trial_logs[1] = sums[1];
-      trial_logs_valid = true;
+      iterate_flags.trial_logs_valid = true;
       neval++;
       if (fail_obj) {
         fprintf(stderr, "ParOpt: Evaluation failed during line search\n");
@@ -1802,8 +1712,8 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   // formed here, from the final step, in one pass over the c constraint gradients: two panel passes, two sparse
   // transposes and the separate multiplier update disappear.  (Not with the linear-constraint recurrence, whose
   // `acz` follows the dense part of this vector alone.)
-  const bool fast_w = has_w && do_qn && analytic_panel_dots && !prob->linear_constraints;
-  const bool fast_yqn = do_qn && analytic_panel_dots && ((!has_w && vA_valid) || fast_w);
+  const bool fast_w = has_w && do_qn && forms.analytic_panel_dots && !prob->linear_constraints;
+  const bool fast_yqn = do_qn && forms.analytic_panel_dots && ((!has_w && step_flags.vA_valid) || fast_w);
   if (fast_w) {
     // vA <- sz Aw^T pzw + sum_j step.z[j] A_j   (step.z already carries sz: scaleKKTStep)
     std::vector<const double *> Aold;
@@ -1818,15 +1728,15 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   }
   if (has_w) PO_TRY(k_w_update(ctx, wv(), wp(), alpha * sx, alpha * sz, eps, nw));  // :4177-4183
   // acz = A^T z follows z += alpha*sz*pz through va = A^T pz when the solves kept va; otherwise it is rebuilt
-  const bool acz_follow = acz && acz_valid && vA_valid;
+  const bool acz_follow = acz && iterate_flags.acz_valid && step_flags.vA_valid;
   // The bound-multiplier step and the first bracket of y_qn ride in the residual pass of the new point when that
   // pass follows anyway (kkt_res_update_kernel): nothing in between reads zl / zu.
-  const bool fuse_upd = fast_yqn && fuse_mult_update;
+  const bool fuse_upd = fast_yqn && forms.fuse_mult_update;
   // No quasi-Newton update (a fixed approximation: the trust-region subproblem solves): the multiplier step still
   // rides in the residual pass of the new point, which is then taken here, right after the gradient, instead of at
   // the top of the next iteration (round 4: one pass over the bound data and one launch less per inner iteration)
-  const bool fuse_upd_noqn = !do_qn && fuse_mult_update && !has_w && pz_stored;
-  if (!pz_stored && !fuse_upd) {
+  const bool fuse_upd_noqn = !do_qn && forms.fuse_mult_update && !has_w && step_flags.pz_stored;
+  if (!step_flags.pz_stored && !fuse_upd) {
     set_error("internal: lean step without the fused multiplier update");
     return PO_ERR_ARG;
   }
@@ -1844,7 +1754,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     PO_TRY(k_update_mult(ctx, zl->d, pzl->d, zu->d, pzu->d, alpha * sz, eps, use_lower, use_upper, n));
     if (acz_follow) PO_TRY(k_axpy(ctx, acz->d, alpha * sz, vA->d, n));
   }
-  if (!acz_follow) acz_valid = false;
+  if (!acz_follow) iterate_flags.acz_valid = false;
   for (int i = 0; i < c; i++) {
     double v = vars.s[i] + alpha * step.s[i];
     vars.s[i] = (v <= eps) ? eps : v;
@@ -1866,25 +1776,25 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     // the line search was skipped: form the new point now
     double sums[2];
     PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums));  // (not in a batch: sums is local)
-    s_qn_from_trial = false;
+    iterate_flags.s_qn_from_trial = false;
     trial_logs[0] = sums[0];
     trial_logs[1] = sums[1];
-    trial_logs_valid = true;
+    iterate_flags.trial_logs_valid = true;
   }
   // the accepted trial point IS the new design point (same clamp, same arithmetic)
   std::swap(x->d, xt->d);
   // ... and so are its sparse constraint values when the line search's last trial left them in wtmp
-  cwx_valid = false;
-  if (has_w && trial_cw_valid && !eval_obj_con) {
+  iterate_flags.cwx_valid = false;
+  if (has_w && iterate_flags.trial_cw_valid && !eval_obj_con) {
     std::swap(cwx->d, wtmp->d);
-    cwx_valid = true;
+    iterate_flags.cwx_valid = true;
   }
-  trial_cw_valid = false;
+  iterate_flags.trial_cw_valid = false;
   // ... and its barrier sums are those of the new iterate (trial_kernel and the merit pass take them alike)
   iterate_logs[0] = trial_logs[0];
   iterate_logs[1] = trial_logs[1];
-  iterate_logs_valid = trial_logs_valid;
-  trial_logs_valid = false;
+  iterate_flags.iterate_logs_valid = iterate_flags.trial_logs_valid;
+  iterate_flags.trial_logs_valid = false;
   if (eval_obj_con) {
     userBegin();
     int fail = prob->evalObjCon(x, &fobj, cvals.data());
@@ -1899,18 +1809,19 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   userBegin();
   // (constantJacobianMask: the library's own model problems may declare single columns constant; those are kept)
   std::vector<Vec *> Acp(Ac);
-  const std::vector<char> *cmask = ac_valid ? prob->constantJacobianMask() : nullptr;
+  const std::vector<char> *cmask = iterate_flags.ac_valid ? prob->constantJacobianMask() : nullptr;
   for (int i = 0; cmask && i < c && i < (int)cmask->size(); i++)
     if ((*cmask)[i]) Acp[i] = nullptr;
-  int fail_g = prob->evalObjConGradient(x, g, (prob->linear_constraints && ac_valid) ? nullptr : Acp.data());
+  int fail_g =
+      prob->evalObjConGradient(x, g, (prob->linear_constraints && iterate_flags.ac_valid) ? nullptr : Acp.data());
   userEnd();
   ngeval++;
   if (fail_g) fprintf(stderr, "ParOpt: Gradient evaluation failed at final line search\n");
   if (do_qn) {
-    if (!(s_qn_from_trial && s_qn_a == alpha * sx)) {
+    if (!(iterate_flags.s_qn_from_trial && s_qn_a == alpha * sx)) {
       PO_TRY(k_panel_axpy(ctx, s_qn->d, alpha * sx, px->d, 0.0, nullptr, nullptr, 0, n));
     }
-    s_qn_from_trial = false;
+    iterate_flags.s_qn_from_trial = false;
     // the next residual's norms and the quasi-Newton products of the update are reduced together: nothing on the
     // host needs the norms before the update has its dots.  Only when no user code runs in between.
     // (user code between the two: only computeQuasiNewtonUpdateCorrection, and only when the problem has one)
@@ -1929,7 +1840,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
       const int rcr = computeResidual(barrier_param, true, y_qn, fuse_upd ? &upd : nullptr);
       spec_dt_want = false;
       PO_TRY(rcr);
-      residual_cached = true;
+      iterate_flags.residual_cached = true;
     } else {
       std::vector<double> mz(c > 0 ? c : 1);
       for (int i = 0; i < c; i++) mz[i] = -vars.z[i];
@@ -1937,14 +1848,14 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
       if (has_w && prob->addSparseJacobianTranspose(-1.0, x, wvar[0], y_qn) != 0) return PO_ERR_USER;
       if (early_w) {
         PO_TRY(computeResidual(barrier_param, true));
-        residual_cached = true;
+        iterate_flags.residual_cached = true;
       }
     }
     int rcc = prob->computeQuasiNewtonUpdateCorrection(x, vars.z.data(), s_qn, y_qn);
     if (rcc != 0) return PO_ERR_USER;
     // Z^T s = alpha sx Z^T px is known from the solves (ptpx) when the step came from this very panel
     const int kz = qn->size();
-    if (analytic_panel_dots && ptpx_valid && kz == wk && kz > 0 && (int)ptpx.size() == c + kz &&
+    if (forms.analytic_panel_dots && step_flags.ptpx_valid && kz == kkt.k && kz > 0 && (int)ptpx.size() == c + kz &&
         !inexact_newton_step && !prob->quasiNewtonCorrectionMayChangeStep()) {
       std::vector<double> zts(kz);
       for (int j = 0; j < kz; j++) zts[j] = alpha * sx * ptpx[c + j];
@@ -1968,7 +1879,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     const int rc = computeResidual(barrier_param, true, nullptr, &upd);
     spec_dt_want = false;
     PO_TRY(rc);
-    residual_cached = true;
+    iterate_flags.residual_cached = true;
   }
   return PO_OK;
 }
@@ -2053,20 +1964,14 @@ int InteriorPoint::optimize(const char *checkpoint) {
   const int gradient_verification_frequency = options.integer("gradient_verification_frequency");
   const std::string start = options.str("starting_point_strategy");
   niter = neval = ngeval = nhvec = 0;
-  cwx_valid = trial_cw_valid = false;
-  residual_cached = false;
-  iterate_logs_valid = trial_logs_valid = fused_merit_valid = false;
-  spec_dt_valid = spec_dt_want = false;
-  w_comp_valid = w_merit_cache_valid = false;
-  px_first_only = false;
-  spec_enabled = spec_valid = false;
+  stateReplaced();
+  spec_dt_want = false;
+  spec_enabled = false;
   history.clear();
   phase_names.clear();
   phase_seconds.clear();
   user_seconds = 0.0;
   user_pending = 0;
-  ac_valid = false;
-  acz_valid = false;
   if (!seq_lin && !qn && !use_diag_hessian) {
     if (ctx->rank == 0)
       fprintf(stderr,
@@ -2092,7 +1997,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
     fprintf(stderr, "ParOpt: Initial gradient evaluation failed\n");
     return fail_g;
   }
-  ac_valid = true;
+  iterate_flags.ac_valid = true;
   if (start == "affine_step") {
     PO_TRY(initAffineStepMultipliers());
   } else if (start == "least_squares_multipliers") {
@@ -2128,8 +2033,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
     // gradient_verification_frequency (:4522-4525, 4635-4639): finite-difference check of the user's gradients
     if (gradient_verification_frequency > 0 && (k % gradient_verification_frequency) == 0) {
       std::string rep;
-      PO_TRY(prob->checkGradients(options.real("gradient_check_step_length"), x, use_hvec_product, xt, tvec, &rep));
-      spec_dt_valid = false;  // (tvec was its scratch: the t the residual pass left behind is gone)
+      PO_TRY(checkGradients(options.real("gradient_check_step_length"), &rep));
       if (ctx->rank == 0) history += rep;
     }
 
@@ -2147,8 +2051,8 @@ int InteriorPoint::optimize(const char *checkpoint) {
     // (the inexact Newton step reads the 2-norms of the bound residuals, computeKKTGMRESStep: no shortcut there)
     spec_enabled = barrier_strategy == B_MONOTONE && norm_type == 0 && !has_w && !use_hvec_product;
     if (barrier_strategy == B_MONOTONE) {
-      if (!residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      residual_cached = false;
+      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
+      iterate_flags.residual_cached = false;
       comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       denseResidual(barrier_param, res);
       resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
@@ -2162,12 +2066,12 @@ int InteriorPoint::optimize(const char *checkpoint) {
         double new_mu = mu_frac;
         if (mu_pow < mu_frac) new_mu = mu_pow;
         if (new_mu < 0.1 * abs_res_tol) new_mu = 0.09999 * abs_res_tol;
-        if (spec_valid && spec_mu == new_mu && norm_type == 0) {
+        if (iterate_flags.spec_valid && spec_mu == new_mu && norm_type == 0) {
           // the residual pass of this iterate took the two maxima for new_mu as well (the complementarity product
           // and the bound count do not depend on mu): what computeResidual(new_mu, false) would produce
           max_rzl = spec_max[0];
           max_rzu = spec_max[1];
-          spec_valid = false;
+          iterate_flags.spec_valid = false;
         } else {
           PO_TRY(computeResidual(new_mu, false));  // rx does not depend on mu
         }
@@ -2177,14 +2081,14 @@ int InteriorPoint::optimize(const char *checkpoint) {
         barrier_param = new_mu;
       }
     } else if (barrier_strategy == B_MEHROTRA || barrier_strategy == B_MPC) {  // :4737-4746
-      if (!residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      residual_cached = false;
+      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
+      iterate_flags.residual_cached = false;
       comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       denseResidual(barrier_param, res);
       resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
     } else {  // complementarity fraction (:4747-4762)
-      if (!residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      residual_cached = false;
+      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
+      iterate_flags.residual_cached = false;
       comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       barrier_param = options.real("monotone_barrier_fraction") * comp;
       if (barrier_param < 0.1 * abs_res_tol) barrier_param = 0.1 * abs_res_tol;
@@ -2298,8 +2202,8 @@ int InteriorPoint::optimize(const char *checkpoint) {
     phaseEnd("setup_kkt");
     if (!mehrotra) {
       // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
-      lean_step_allowed = qn && use_qnu && use_qn && !diagonal_quasi_newton_step && analytic_panel_dots &&
-                          fuse_mult_update && !use_hvec_product && !use_diag_hessian && !seq_lin;
+      lean_step_allowed = qn && use_qnu && use_qn && !diagonal_quasi_newton_step && forms.analytic_panel_dots &&
+                          forms.fuse_mult_update && !use_hvec_product && !use_diag_hessian && !seq_lin;
       const int step_rc = computeKKTStepWithRefinement(barrier_param, use_qn, tau);
       lean_step_allowed = false;
       PO_TRY(step_rc);
@@ -2357,9 +2261,9 @@ int InteriorPoint::optimize(const char *checkpoint) {
           line_fail = LS_FAILURE;
         } else {
           double px_norm = 0.0;
-          if (merit_cache_valid) {
+          if (step_flags.merit_cache_valid) {
             px_norm = merit_cache[6];
-          } else if (px_amax_valid) {
+          } else if (step_flags.px_amax_valid) {
             px_norm = px_amax_w;
           } else {
             PO_TRY(k_reduce1(ctx, RED_AMAX, px->d, nullptr, n, &px_norm));
@@ -2573,8 +2477,7 @@ int InteriorPoint::writeSolutionFile(const char *filename) {
 
 // readSolutionFile (:983-1104): restart state written by writeSolutionFile (same layout, any rank count)
 int InteriorPoint::readSolutionFile(const char *filename) {
-  acz_valid = false;
-  cwx_valid = false;
+  stateReplaced();
   int64_t N = 0, off = 0, Wt = 0, woff = 0;
   PO_TRY(solutionFileOffsets(&N, &off, &Wt, &woff));  // collective
   FILE *fp = fopen(filename, "rb");

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "bordered.hpp"
 #include "problem.hpp"
 #include "qn.hpp"
 
@@ -47,24 +48,13 @@ class Options {
   std::map<std::string, Entry> e;
 };
 
-struct Dense {  // the c-sized blocks of ParOptVars (src/ParOptInteriorPoint.h:373-389)
-  std::vector<double> z, s, t, zs, zt;
-  void resize(int c) {
-    z.assign(c, 0.0);
-    s.assign(c, 0.0);
-    t.assign(c, 0.0);
-    zs.assign(c, 0.0);
-    zt.assign(c, 0.0);
-  }
-};
-
 class InteriorPoint {
  public:
   InteriorPoint(Problem *prob);
   ~InteriorPoint();
   int allocate();  // device storage (fails with PO_ERR_HIP when HBM is exhausted)
   // SURVEY 8a' bookkeeping (po_ip_get_debug_ints)
-  const std::vector<int> &gPivots() const { return gpiv; }
+  const std::vector<int> &gPivots() const { return kkt.gpiv; }
   Vec *lowerBounds() { return lb; }
   Vec *upperBounds() { return ub; }
   // the caller may write lb / ub through a handle: the kernels read the vectors until the next optimize()
@@ -105,8 +95,8 @@ class InteriorPoint {
   std::vector<double> Gmat0, Ce0;   // G and Ce before their LU factorizations (filled inside debugKKT only)
   bool debug_keep_schur = false;
   double debug_norms[4] = {0, 0, 0, 0};  // max_prime, max_dual, max_infeas, res_norm of the last debugKKT
-  const std::vector<double> &gramMatrix() const { return W; }
-  const std::vector<int> &cPivots() const { return cpiv; }
+  const std::vector<double> &gramMatrix() const { return kkt.W; }
+  const std::vector<int> &cPivots() const { return kkt.cpiv; }
   const double *stepMins() const { return step_mins; }
   Vec *dinvVec() { return Dinv; }
   Vec *rxVec() { return rx; }
@@ -134,7 +124,6 @@ class InteriorPoint {
   int niter, neval, ngeval, nhvec;
 
   // observer + history
-  bool analytic_panel_dots;  // debugging switch: false re-measures P^T px with an mdot pass
   po_ip_iteration_fn iter_cb;
   void *iter_cb_user;
   std::string history;
@@ -165,11 +154,57 @@ class InteriorPoint {
   bool qn_created;
   bool qn_owned;
 
-  // small dense systems
-  std::vector<double> W;            // (c+k)^2 weighted Gram, column-major
-  int wk;                           // k used when W was assembled
-  std::vector<double> Gf, Cef;      // LU factors
-  std::vector<int> gpiv, cpiv;
+  // small dense systems: the weighted Gram W of the panel and the factors of the bordered solve
+  Bordered kkt;
+
+  // What the carried buffers and caches hold, grouped by the event that makes them stale.  Each group is dropped as a
+  // whole by its event method (group = {}: a member added later cannot be missed); a flag consumed by the one pass
+  // that reads it is cleared there.  The values recorded with a flag sit beside it below.
+  struct StepFlags {  // the current step in px / pzl / pzu and what was taken of it; stale when a solve writes a step
+    bool ptpx_valid = false;           // ptpx = P^T px
+    bool tdots_valid = false;          // tdots = P^T t' of the fused first pass (consumed by the refinement pass)
+    bool merit_cache_valid = false;    // merit_cache
+    bool fused_merit_valid = false;    // fused_merit
+    bool px_amax_valid = false;        // px_amax_w
+    bool w_comp_valid = false;         // w_comp_poly
+    bool w_merit_cache_valid = false;  // w_merit_cache
+    bool vA_valid = false;             // vA = A^T pz, maintained by the solves
+    bool residual_fused = false;       // the first pass already wrote the refinement right-hand side t'
+    bool pz_stored = true;             // pzl / pzu hold the step (false after a lean step: px only)
+    bool step_deferred = false;        // the first pass stored no step (alpha_first, coef_first, diag_first)
+    bool px_first_only = false;        // sparse path: the first pass stored px only
+  } step_flags;
+  // what the scratch vectors tvec, Dinv, d1v, wd2 and Uw hold; stale when they are lent out (checkGradients) or the
+  // state is written from outside
+  struct ScratchFlags {
+    bool spec_dt_valid = false;         // Dinv / t of the next first solve (spec_dt_diag, spec_dt_bmu, spec_dt_mu)
+    bool t0_valid = false;              // tvec = t of the next first solve, t0dots = P^T t (t0_mu)
+    bool t_is_plain_dinv_d1 = false;    // tvec / Dinv are exactly what dinv_d1_kernel forms (t0_diag)
+    bool first_t_recomputable = false;  // ... and the first solve's t can be re-formed in registers
+    bool wd2_ready = false;             // wd2 = d2 of the next block solve
+    bool panel_valid = false;           // Uw is the panel image of the current setUpKKTSystem (panel_plain)
+  } scratch_flags;
+  // what was evaluated at the current iterate x; stale when x, the bounds or the problem instance change other than
+  // by the step update
+  struct IterateFlags {
+    bool ac_valid = false;            // Ac holds the Jacobian at x
+    bool acz_valid = false;           // acz = A^T z (acz_age)
+    bool cwx_valid = false;           // cwx = cw(x)
+    bool trial_cw_valid = false;      // wtmp = cw(xt) of the last trial point
+    bool iterate_logs_valid = false;  // iterate_logs
+    bool trial_logs_valid = false;    // trial_logs
+    bool residual_cached = false;     // rx / norms of the current state were already evaluated (step update)
+    bool spec_valid = false;          // spec_max for spec_mu
+    bool s_qn_from_trial = false;     // s_qn holds s_qn_a * px, written by the last trial pass of the line search
+  } iterate_flags;
+  void stepWillChange() { step_flags = {}; }
+  void scratchLent() { scratch_flags = {}; }
+  void iterateReplaced() { iterate_flags = {}; }
+  void stateReplaced() {  // x, the multipliers or the problem written from outside: nothing carried survives
+    stepWillChange();
+    scratchLent();
+    iterateReplaced();
+  }
   // residual bookkeeping of the last computeResidual call
   double comp_prod, comp_count, max_rx, max_rzl, max_rzu;
   double l1_rx = 0, l1_rzl = 0, l1_rzu = 0, l2_rx = 0, l2_rzl = 0, l2_rzu = 0;
@@ -180,51 +215,41 @@ class InteriorPoint {
   // (px = t + Dinv*(P alpha)  =>  P^T px = P^T t + W alpha), so that neither iterative refinement
   // nor the merit derivative needs another pass over the panel
   std::vector<double> ptpx;
-  bool ptpx_valid;
-  bool residual_fused;  // the last first-pass solve already wrote the refinement rhs t'
-  bool residual_cached; // rx / norms of the CURRENT state were already evaluated (step update)
   bool corrector_active;  // Mehrotra predictor-corrector: s_qn / y_qn hold the corrector products
   // ... unless the corrector solve forms them itself (round 6: k_corr_d1_dots + k_solve2c, two launches and two host
   // round trips instead of five and three); corr_out: what k_solve2c reduced
   bool corrector_fused = false;
   // Dinv / t of the next first solve left behind by the residual pass of the new point (no quasi-Newton update in
-  // between: round 6); valid for the diagonal and the barrier parameter recorded with them
-  bool spec_dt_valid = false, spec_dt_want = false;
+  // between: round 6; scratch_flags.spec_dt_valid); valid for the diagonal and the barrier parameter recorded with them
+  bool spec_dt_want = false;
   double spec_dt_diag = 0.0, spec_dt_bmu = 0.0, spec_dt_mu = 0.0;
   double corr_out[12] = {0};
   int norm_type;          // 0 infinity, 1 l1, 2 l2 (ParOptNormType)
   std::vector<double> tdots;  // P^T t' produced by the fused first solve pass
-  bool tdots_valid;
 
   // ---- second-order information (ip_gmres.cpp) ----
   Vec *hdiag;                  // use_diag_hessian: diagonal of the Lagrangian Hessian (zero until evaluated)
   std::vector<Vec *> gmresW;   // Krylov basis of computeKKTGMRESStep
-  bool vA_valid;               // vA = A^T pz of the current step was maintained by the solves
   bool inexact_newton_step;    // the current step came from computeKKTGMRESStep
   // merit pieces of the current (unscaled) step, produced together with the complementarity check of
   // scaleKKTStep: {pos log, neg log, ppos, pneg, g.px, px.px, max|px|}
   double merit_cache[7];
   double px_amax_w = 0.0;       // max|px| taken inside evalMeritInitDeriv's batch (sparse-constraint path)
-  bool px_amax_valid = false;
   std::vector<double> Wt_buf, W2_buf;  // landing areas of Gram launches deferred to a batch flush (setUpKKTSystem)
-  bool merit_cache_valid;
   // the same pieces taken by the refinement pass itself (k_solve2r with g): {S10, S01, S11, ppos, pneg, g.px, px.px,
   // max_x, max_z, max|px|}; the log-barrier sums of the iterate are those of the accepted trial point of the last
   // line search (same kernel arithmetic, same element order as the separate pass took them)
   double fused_merit[10] = {0};
-  bool fused_merit_valid = false, fuse_merit = true;
   // "lean step" (round 3): in the plain quasi-Newton iteration the refinement pass stores px only; the bound-
   // multiplier steps are re-formed from it inside the multiplier update (kkt_res_update_kernel) -- two output streams
   // of the refinement pass less.  lean_step_allowed is set by optimize() around the step computation of an iteration
   // whose every later consumer of (pzl, pzu) is that update; pz_stored says whether the vectors hold the current step.
   // tvec / Dinv hold exactly what dinv_d1_kernel formed for (t0_diag, t0_mu) from the bound data and rx: a pass that
   // loads those anyway may re-form them in registers instead of reading them (k_solve2r with t1 == nullptr)
-  bool t_is_plain_dinv_d1 = false, first_t_recomputable = false, recompute_dt = true;
   double t0_diag = 0.0;
-  bool lean_step = true, lean_step_allowed = false, pz_stored = true;
+  bool lean_step_allowed = false;
   double step_beta_mu = 0.0;
   double trial_logs[2] = {0, 0}, iterate_logs[2] = {0, 0};
-  bool trial_logs_valid = false, iterate_logs_valid = false;
   int gatherCounts(int64_t mine, std::vector<int64_t> *all);
   int solutionFileOffsets(int64_t *nvars_total, int64_t *var_off, int64_t *nw_total, int64_t *w_off);
   int ensureHdiag();
@@ -245,18 +270,16 @@ class InteriorPoint {
   // reference calls evalSparseCon each time (:1358, 3740), here the callback runs once per point and the accepted
   // trial point of the line search hands its values over.  Dropped whenever x or the problem instance changes.
   Vec *cwx = nullptr;
-  bool cwx_valid = false, trial_cw_valid = false;
   int sparseConAtIterate(const double **cw);
   Vec *d1v;                 // n-sized: raw d1, then v = d1 + P alpha
   std::vector<Vec *> Uw;    // U_j = Aw (Dinv o P_j)
   bool panel_plain = false;  // Uw is the unscaled panel image (scalar block form)
-  bool panel_valid = false;  // Uw matches the current setUpKKTSystem (consumed by solveKKTW)
   double w_sums[7], w_maxs[5];  // reductions of the last w residual (k_w_res layout)
   double res_out[13] = {0}, wres_out[12] = {0};  // landing area of the residual reductions (see after_reduce)
   // Monotone barrier strategy with the infinity norm (round 4): the residual pass also takes max|rzl|, max|rzu| for the
   // barrier parameter the strategy would switch to (a function of the current one alone), so that the switch needs
   // neither the mu-only pass over the bound data nor its host synchronisation
-  bool spec_enabled = false, spec_valid = false;
+  bool spec_enabled = false;
   double spec_mu = 0.0, spec_max[2] = {0.0, 0.0};
   double nextMonotoneMu() const;
   WVars wv() const;
@@ -266,7 +289,6 @@ class InteriorPoint {
   int applyK0(const double *bx, const double *bw, Vec *yx, Vec *yw);
   // d2out: also wd2 = d2 of the block solve that follows (one launch less); wd2_ready tells solveKKTW
   int computeResidualW(double mu, bool norms = true, bool with_d2 = false);
-  bool wd2_ready = false;
   int sparseGramCorrection(const std::vector<const double *> &P, int m, Vec *work = nullptr, bool may_defer = false,
                            bool panel_done = false);
   int panelImageVectors(int m, std::vector<double *> &U);  // Uw[0..m) as raw pointers (allocated on demand)
@@ -319,34 +341,37 @@ class InteriorPoint {
   void userBegin();
   void userEnd();
   void userHarvest();
+  // Kernel forms, fixed at construction by the test switches (SW_* in core.hpp, INTEGRATION.md "Diagnostics"); each
+  // member is true on the default path and false only under its switch
+  struct Forms {
+    bool analytic_panel_dots;   // P^T px from the W-based algebra (false: re-measured with an mdot pass)
+    bool fuse_merit;            // the refinement pass takes the merit / complementarity sums of the final step
+    bool lean_step;             // ... and, in the plain quasi-Newton iteration, stores px only
+    bool recompute_dt;          // the solve passes re-form Dinv / t in registers where the bound data allow
+    bool recompute_first_step;  // the fused first pass stores no step: the refinement pass re-forms it
+    bool recompute_rhs;         // ... and the refinement right-hand side is re-formed as well
+    bool fuse_mult_update;      // the bound-multiplier update rides in the residual pass of the new point
+  };
+  static Forms readForms();
+  const Forms forms = readForms();
   int check_flag = 0;  // OR of the bound-repair bits of every initAndCheckDesignAndBounds call (:4290-4344)
   // uniform lb / ub of this rank as the last initAndCheckDesignAndBounds found them (bounds() hands them to the
   // kernels); every other writer of lb / ub clears them
   int bounds_uni[2] = {0, 0};
   double bounds_val[2] = {0.0, 0.0};
-  bool ac_valid = false;
   // A^T z of a problem with linear dense constraints, kept by recurrence (computeResidual / computeStepAndUpdate)
   static const int kAczRefresh = 16;
   Vec *acz = nullptr;
-  bool acz_valid = false;
   int acz_age = 0;
-  // P^T t of the first solve, produced by the Gram pass of setUpKKTSystem (see there)
-  bool fuse_mult_update = true;
   // sparse constraints, round 4: y_qn from the residuals, and "lean" solve passes: the fused
   // first pass stores px only (px_first_only), the refinement pass re-forms the first bound-multiplier steps from it,
   // takes the complementarity / merit sums of the final step (fused_merit, as on the dense path) and, in the plain
   // quasi-Newton iteration, stores px only again; the sparse blocks' share of the complementarity polynomial comes
   // out of the step kernel (w_comp_poly) and the sparse merit sums ride in the same batch (w_merit_cache, sx = 1)
-  bool px_first_only = false;
   double w_step_out[5] = {0, 0, 0, 0, 0}, w_comp_poly[3] = {0, 0, 0}, w_merit_cache[10] = {0};
-  bool w_comp_valid = false, w_merit_cache_valid = false;
-  bool s_qn_from_trial = false;  // s_qn holds s_qn_a * px, written by the last trial pass of the line search
   double s_qn_a = 0.0;
-  bool recompute_first_step = true, step_deferred = false;  // see solveKKT: the first pass stores no step
   std::vector<double> alpha_first, coef_first;  // coefficients of that first pass (solve, refinement residual)
   double diag_first = 0.0;
-  bool recompute_rhs = true;  // ... and the refinement right-hand side is recomputed as well
-  bool t0_valid = false;
   double t0_mu = 0.0;
   std::vector<double> t0dots;  // Ac holds the Jacobian of a problem with linear_constraints
 };

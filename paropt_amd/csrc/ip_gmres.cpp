@@ -29,64 +29,20 @@ int InteriorPoint::solveKKTAlpha(const double *bx, double alpha, const Dense &b,
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   int k = 0;
   std::vector<const double *> P = panel(use_qn, &k);
-  if (k != wk) {
-    set_error("internal: panel width changed between setUpKKTSystem and solve (%d vs %d)", k, wk);
-    return PO_ERR_ARG;
-  }
+  PO_TRY(kkt.checkWidth(k));
   const int m = c + k;
   PO_TRY(k_d1s(ctx, bounds(), bx, Dinv->d, alpha, beta_mu, n, tvec->d));
   std::vector<double> dots(m > 0 ? m : 1, 0.0);
   if (m > 0) PO_TRY(k_mdot(ctx, tvec->d, P.data(), m, n, dots.data()));
-  std::vector<double> yz(c > 0 ? c : 1, 0.0), yz2(c > 0 ? c : 1, 0.0), zeta(k > 0 ? k : 1, 0.0);
-  for (int i = 0; i < c; i++) {
-    yz[i] = alpha * (b.z[i] + (b.zs[i] + vars.s[i] * b.s[i]) / vars.zs[i] -
-                     (b.zt[i] + vars.t[i] * b.t[i]) / vars.zt[i]) -
-            dots[i];
-  }
-  if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz.data());
-  if (k > 0) {
-    for (int i = 0; i < k; i++) {
-      double v = dots[c + i];
-      for (int l = 0; l < c; l++) v += W[(c + i) + (size_t)m * l] * yz[l];
-      zeta[i] = v;
-    }
-    lu_solve(k, Cef.data(), k, cpiv.data(), zeta.data());
-    for (int i = 0; i < c; i++) {
-      double v = 0.0;
-      for (int j = 0; j < k; j++) v += W[i + (size_t)m * (c + j)] * zeta[j];
-      yz2[i] = -v;
-    }
-    if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz2.data());
-  }
-  std::vector<double> coef(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < c; i++) coef[i] = yz[i] - yz2[i];
-  for (int j = 0; j < k; j++) coef[c + j] = -zeta[j];
-  ptpx.assign(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < m; i++) {
-    double v = dots[i];
-    for (int j = 0; j < m; j++) v += W[i + (size_t)m * j] * coef[j];
-    ptpx[i] = v;
-  }
-  ptpx_valid = true;
-  merit_cache_valid = false;  // the step is about to change
-  px_amax_valid = false;
-  fused_merit_valid = false;
-  w_comp_valid = w_merit_cache_valid = false;
-  tdots_valid = false;
-  residual_fused = false;
-  vA_valid = false;
+  Bordered::Sol sol;
+  kkt.solve(alpha, b, vars, dots.data(), &sol);
+  const std::vector<double> &coef = sol.coef;
+  stepWillChange();
+  kkt.panelDots(dots.data(), sol, false, &ptpx);
+  step_flags.ptpx_valid = true;
   PO_TRY(k_solve2s(ctx, bounds(), tvec->d, Dinv->d, coef.data(), P.data(), m, alpha, beta_mu, full ? 1 : 0, tau,
                    n, px->d, pzl->d, pzu->d, step_mins));
-  for (int i = 0; i < c; i++) {
-    const double zs1 = yz[i] - alpha * b.s[i];
-    const double zt1 = -alpha * b.t[i] - yz[i];
-    const double y2 = full ? yz2[i] : 0.0;
-    out.z[i] = yz[i] - y2;
-    out.zs[i] = zs1 - y2;
-    out.zt[i] = zt1 + y2;
-    out.s[i] = (alpha * b.zs[i] - vars.s[i] * zs1) / vars.zs[i] + (vars.s[i] * y2) / vars.zs[i];
-    out.t[i] = (alpha * b.zt[i] - vars.t[i] * zt1) / vars.zt[i] - (vars.t[i] * y2) / vars.zt[i];
-  }
+  kkt.backSubstitute(alpha, b, vars, sol, full, out);
   return PO_OK;
 }
 
@@ -99,10 +55,7 @@ int InteriorPoint::solveKKTAlphaW(const double *bx, double alpha, const Dense &b
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   int k = 0;
   std::vector<const double *> P = panel(use_qn, &k);
-  if (k != wk) {
-    set_error("internal: panel width changed between setUpKKTSystem and solve (%d vs %d)", k, wk);
-    return PO_ERR_ARG;
-  }
+  PO_TRY(kkt.checkWidth(k));
   const int m = c + k;
   WVars ws{wscalev[0]->d, wscalev[1]->d, wscalev[2]->d, wscalev[3]->d, wscalev[4]->d};
   PO_TRY(k_d1s(ctx, bounds(), bx, nullptr, alpha, beta_mu, n, d1v->d));
@@ -111,49 +64,17 @@ int InteriorPoint::solveKKTAlphaW(const double *bx, double alpha, const Dense &b
   PO_TRY(applyK0(d1v->d, wd2->d, tvec, wyw));
   std::vector<double> dots(m > 0 ? m : 1, 0.0);
   if (m > 0) PO_TRY(k_mdot(ctx, tvec->d, P.data(), m, n, dots.data()));
-  std::vector<double> yz(c > 0 ? c : 1, 0.0), yz2(c > 0 ? c : 1, 0.0), zeta(k > 0 ? k : 1, 0.0);
-  for (int i = 0; i < c; i++) {
-    yz[i] = alpha * (b.z[i] + (b.zs[i] + vars.s[i] * b.s[i]) / vars.zs[i] -
-                     (b.zt[i] + vars.t[i] * b.t[i]) / vars.zt[i]) -
-            dots[i];
-  }
-  if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz.data());
-  if (k > 0) {
-    for (int i = 0; i < k; i++) {
-      double v = dots[c + i];
-      for (int l = 0; l < c; l++) v += W[(c + i) + (size_t)m * l] * yz[l];
-      zeta[i] = v;
-    }
-    lu_solve(k, Cef.data(), k, cpiv.data(), zeta.data());
-    for (int i = 0; i < c; i++) {
-      double v = 0.0;
-      for (int j = 0; j < k; j++) v += W[i + (size_t)m * (c + j)] * zeta[j];
-      yz2[i] = -v;
-    }
-    if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz2.data());
-  }
-  std::vector<double> coef(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < c; i++) coef[i] = yz[i] - yz2[i];
-  for (int j = 0; j < k; j++) coef[c + j] = -zeta[j];
-  ptpx.assign(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < m; i++) {
-    double v = dots[i];
-    for (int j = 0; j < m; j++) v += W[i + (size_t)m * j] * coef[j];
-    ptpx[i] = v;
-  }
-  ptpx_valid = true;
-  merit_cache_valid = false;
-  px_amax_valid = false;
-  fused_merit_valid = false;
-  w_comp_valid = w_merit_cache_valid = false;
-  tdots_valid = false;
-  residual_fused = false;
-  vA_valid = false;
+  Bordered::Sol sol;
+  kkt.solve(alpha, b, vars, dots.data(), &sol);
+  const std::vector<double> &coef = sol.coef;
+  stepWillChange();
+  kkt.panelDots(dots.data(), sol, false, &ptpx);
+  step_flags.ptpx_valid = true;
   double mins_w[2] = {1.0, 1.0};
   if (!full && k > 0) {
     // w blocks without the quasi-Newton correction: K0^-1 (d1 + Ac yz, d2)
     if (c > 0) {
-      PO_TRY(k_panel_axpy(ctx, xt->d, 1.0, d1v->d, 0.0, yz.data(), P.data(), c, n));
+      PO_TRY(k_panel_axpy(ctx, xt->d, 1.0, d1v->d, 0.0, sol.yz.data(), P.data(), c, n));
       PO_TRY(applyK0(xt->d, wd2->d, tvec, wyw));
     }
     PO_TRY(k_w_step(ctx, wv(), ws, wyw->d, 0, tau, wp(), nw, mins_w));
@@ -169,16 +90,7 @@ int InteriorPoint::solveKKTAlphaW(const double *bx, double alpha, const Dense &b
                    n, px->d, pzl->d, pzu->d, mins_x));
   step_mins[0] = std::min(mins_x[0], mins_w[0]);
   step_mins[1] = std::min(mins_x[1], mins_w[1]);
-  for (int i = 0; i < c; i++) {
-    const double zs1 = yz[i] - alpha * b.s[i];
-    const double zt1 = -alpha * b.t[i] - yz[i];
-    const double y2 = full ? yz2[i] : 0.0;
-    out.z[i] = yz[i] - y2;
-    out.zs[i] = zs1 - y2;
-    out.zt[i] = zt1 + y2;
-    out.s[i] = (alpha * b.zs[i] - vars.s[i] * zs1) / vars.zs[i] + (vars.s[i] * y2) / vars.zs[i];
-    out.t[i] = (alpha * b.zt[i] - vars.t[i] * zt1) / vars.zt[i] - (vars.t[i] * y2) / vars.zt[i];
-  }
+  kkt.backSubstitute(alpha, b, vars, sol, full, out);
   return PO_OK;
 }
 

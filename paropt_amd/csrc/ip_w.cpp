@@ -66,9 +66,9 @@ int InteriorPoint::applyK0(const double *bx, const double *bw, Vec *yx, Vec *yw)
 // the w blocks of computeKKTRes (:1358-1398) and their norms
 // (norms = false: the blocks only -- the caller knows that the sums of this mu and iterate are already in place)
 int InteriorPoint::sparseConAtIterate(const double **cw) {
-  if (!cwx_valid) {
+  if (!iterate_flags.cwx_valid) {
     if (prob->evalSparseCon(x, cwx) != 0) return PO_ERR_USER;
-    cwx_valid = true;
+    iterate_flags.cwx_valid = true;
   }
   *cw = cwx->d;
   return PO_OK;
@@ -77,7 +77,7 @@ int InteriorPoint::sparseConAtIterate(const double **cw) {
 int InteriorPoint::computeResidualW(double mu, bool norms, bool with_d2) {
   const double *cw = nullptr;
   PO_TRY(sparseConAtIterate(&cw));
-  wd2_ready = false;
+  scratch_flags.wd2_ready = false;
   PO_TRY(k_w_res(ctx, wv(), wr(), gsw->d, gtw->d, mu, nw, norms ? wres_out : nullptr, cw, with_d2 ? wd2->d : nullptr));
   if (!norms) return PO_OK;
   after_reduce(ctx, [this] {
@@ -119,9 +119,9 @@ int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, in
   W2_buf.assign((size_t)m * m, 0.0);
   PO_TRY(k_wgram(ctx, weights, Uc.data(), m, nw, W2_buf.data(), nullptr, nullptr, 0, 0.0, 0, may_defer));
   after_reduce(ctx, [this] {
-    for (size_t i = 0; i < W2_buf.size() && i < W.size(); i++) W[i] -= W2_buf[i];
+    for (size_t i = 0; i < W2_buf.size() && i < kkt.W.size(); i++) kkt.W[i] -= W2_buf[i];
   });
-  panel_valid = true;  // Uw holds the (half-solved) panel of the CURRENT Dinv, factor and panel columns
+  scratch_flags.panel_valid = true;  // Uw holds the (half-solved) panel of the CURRENT Dinv, factor and panel columns
   return PO_OK;
 }
 
@@ -132,25 +132,23 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   int k = 0;
   std::vector<const double *> P = panel(use_qn, &k);
-  if (k != wk) {
-    set_error("internal: panel width changed between setUpKKTSystem and solve (%d vs %d)", k, wk);
-    return PO_ERR_ARG;
-  }
+  PO_TRY(kkt.checkWidth(k));
   const int m = c + k;
   const double *cl = (corrector_active && !refine_pass) ? s_qn->d : nullptr;
   const double *cu = (corrector_active && !refine_pass) ? y_qn->d : nullptr;
   // t = [K0^-1 (d1, d2)]_x, wyw and P^T t were produced by setUpKKTSystem when the right-hand side was known then
-  const bool have_t0 = !refine_pass && t0_valid && t0_mu == mu && !cl && (int)t0dots.size() == m && m > 0;
+  const bool have_t0 = !refine_pass && scratch_flags.t0_valid && t0_mu == mu && !cl && (int)t0dots.size() == m && m > 0;
   std::vector<double> dots(m > 0 ? m : 1, 0.0);
   if (have_t0) {
     for (int i = 0; i < m; i++) dots[i] = t0dots[i];
   } else {
     if (!refine_pass) PO_TRY(k_d1(ctx, bounds(), rx->d, nullptr, beta_mu, n, d1v->d, cl, cu));
-    if (!wd2_ready) PO_TRY(k_w_d2(ctx, wv(), wr(), nw, wd2->d));  // (else: formed by the pass that wrote the blocks)
-    wd2_ready = false;
+    // (wd2_ready: formed by the pass that wrote the blocks)
+    if (!scratch_flags.wd2_ready) PO_TRY(k_w_d2(ctx, wv(), wr(), nw, wd2->d));
+    scratch_flags.wd2_ready = false;
     PO_TRY(applyK0(d1v->d, wd2->d, tvec, wyw));
-    if (refine_pass && tdots_valid && (int)tdots.size() == m && m > 0 && panel_valid && panel_plain &&
-        (int)Uw.size() >= m) {
+    if (refine_pass && step_flags.tdots_valid && (int)tdots.size() == m && m > 0 && scratch_flags.panel_valid &&
+        panel_plain && (int)Uw.size() >= m) {
       // tvec = Dinv o (d1' + Aw^T yw): P^T tvec = P^T (Dinv o d1') + U^T yw with U = Aw (Dinv o P) -- the first
       // term came out of the fused first pass, the second is a w-sized product with the panel image
       std::vector<const double *> Uc(m);
@@ -161,53 +159,20 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
       PO_TRY(k_mdot(ctx, tvec->d, P.data(), m, n, dots.data()));
     }
   }
-  if (!refine_pass) t0_valid = false;  // tvec is overwritten below
-  std::vector<double> yz(c > 0 ? c : 1, 0.0), yz2(c > 0 ? c : 1, 0.0), zeta(k > 0 ? k : 1, 0.0);
-  for (int i = 0; i < c; i++) {
-    yz[i] = (b.z[i] + (b.zs[i] + vars.s[i] * b.s[i]) / vars.zs[i] -
-             (b.zt[i] + vars.t[i] * b.t[i]) / vars.zt[i] - dots[i]);
-  }
-  if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz.data());
-  if (k > 0) {
-    for (int i = 0; i < k; i++) {
-      double v = dots[c + i];
-      for (int l = 0; l < c; l++) v += W[(c + i) + (size_t)m * l] * yz[l];
-      zeta[i] = v;
-    }
-    lu_solve(k, Cef.data(), k, cpiv.data(), zeta.data());
-    for (int i = 0; i < c; i++) {
-      double v = 0.0;
-      for (int j = 0; j < k; j++) v += W[i + (size_t)m * (c + j)] * zeta[j];
-      yz2[i] = -v;
-    }
-    if (c > 0) lu_solve(c, Gf.data(), c, gpiv.data(), yz2.data());
-  }
-  std::vector<double> alpha(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < c; i++) alpha[i] = yz[i] - yz2[i];
-  for (int j = 0; j < k; j++) alpha[c + j] = -zeta[j];
-  if (!refine_pass) ptpx.assign(m > 0 ? m : 1, 0.0);
-  for (int i = 0; i < m; i++) {
-    double v = dots[i];
-    for (int j = 0; j < m; j++) v += W[i + (size_t)m * j] * alpha[j];
-    ptpx[i] = refine_pass ? ptpx[i] + v : v;
-  }
-  ptpx_valid = true;
-  merit_cache_valid = false;  // the step is about to change
-  px_amax_valid = false;
-  fused_merit_valid = false;
-  w_comp_valid = false;
-  w_merit_cache_valid = false;
-  pz_stored = true;
-  bool first_px_only = refine_pass && px_first_only;  // px holds the first step, pzl / pzu were not stored
-  px_first_only = false;
-  if (first_px_only && !(m > 0 && (int)Uw.size() >= m && panel_valid)) {
+  if (!refine_pass) scratch_flags.t0_valid = false;  // tvec is overwritten below
+  bool first_px_only = refine_pass && step_flags.px_first_only;  // px holds the first step, pzl / pzu were not stored
+  stepWillChange();
+  Bordered::Sol sol;
+  kkt.solve(1.0, b, vars, dots.data(), &sol);
+  const std::vector<double> &alpha = sol.coef;
+  kkt.panelDots(dots.data(), sol, refine_pass, &ptpx);
+  step_flags.ptpx_valid = true;
+  if (first_px_only && !(m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid)) {
     // (not reached with the flags as they are set: the fused first pass implies a valid panel) the stored-step forms
     // below need the first bound-multiplier steps as vectors
     PO_TRY(k_form_pz(ctx, bounds(), px->d, beta_mu, n, pzl->d, pzu->d));
     first_px_only = false;
   }
-  tdots_valid = false;        // (consumed above by a refinement pass; set again below by a fused first pass)
-  if (!refine_pass) residual_fused = false;
   // (dx, dzw) = K0^-1 (d1 + P alpha, d2) = K0^-1 (d1, d2) + K0^-1 (P alpha, 0), and the second term comes from
   // the panel the Gram correction already holds: dzw += -S^-1 (U alpha), dx += Dinv (P alpha + Aw^T of that) -
   // no second quasi-definite apply, and P alpha rides in the same pass that forms the bound multipliers
@@ -222,8 +187,8 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   // before the axpy pass starts, and so is the sparse multiplier step pzw (it depends on wyw only), so ONE pass
   // over P writes the step, the RAW right-hand side d1' of the refinement solve (its design rows, :1451-1483, with
   // the extra column Aw^T pzw) and the panel products of Dinv o d1'.
-  const bool fuse = fuse_residual && !refine_pass && analytic_panel_dots && kq == k && m > 0 &&
-                    (int)Uw.size() >= m && panel_valid && panel_plain && !cl &&
+  const bool fuse = fuse_residual && !refine_pass && forms.analytic_panel_dots && kq == k && m > 0 &&
+                    (int)Uw.size() >= m && scratch_flags.panel_valid && panel_plain && !cl &&
                     !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
   if (fuse) {
     std::vector<const double *> Uc(m);
@@ -277,15 +242,15 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
     PO_TRY(k_solve2_dots(ctx, bounds(), tvec->d, Dinv->d, a1.data(), c2.data(), P1.data(), np1, beta_mu, tau,
                          rx->d, diag, n, px->d, pzl->d, pzu->d, nullptr, nullptr, 0, so.data(), y_qn->d, 2, 0,
                          0.0, grouped ? &gcs : nullptr));
-    px_first_only = true;
+    step_flags.px_first_only = true;
     std::swap(d1v->d, y_qn->d);
     PO_TRY(minbatch.end());
     tdots.assign(so.begin(), so.begin() + m);
-    tdots_valid = true;
-    residual_fused = true;
+    step_flags.tdots_valid = true;
+    step_flags.residual_fused = true;
     mins_x[0] = so[np1];  // out = {dots[np1], max_x, max_z}
     mins_x[1] = so[np1 + 1];
-  } else if (m > 0 && (int)Uw.size() >= m && panel_valid) {
+  } else if (m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid) {
     std::vector<const double *> Uc(m);
     for (int j = 0; j < m; j++) Uc[j] = Uw[j]->d;
     PO_TRY(prob->sparseCorrection(Uc.data(), m, alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
@@ -308,8 +273,8 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
       // the complementarity / merit sums of the FINAL step (fused_merit); the final px goes to xt (free during the
       // solves) and the two buffers are exchanged.  Lean step: (pzl, pzu) are not stored either -- their only
       // consumer left is the multiplier update of computeStepAndUpdate, which re-forms them (kkt_res_update_kernel)
-      const bool take_merit = fuse_merit && !cl;
-      const bool lean = take_merit && lean_step && lean_step_allowed && iterate_logs_valid &&
+      const bool take_merit = forms.fuse_merit && !cl;
+      const bool lean = take_merit && forms.lean_step && lean_step_allowed && iterate_flags.iterate_logs_valid &&
                         !prob->linear_constraints && options.integer("iterative_refinement_steps") == 1;
       std::vector<double> azero(m + 1, 0.0);
       PO_TRY(k_solve2r(ctx, bounds(), px->d, tvec->d, Dinv->d, azero.data(), a1.data(), P1.data(), (int)P1.size(), beta_mu,
@@ -318,7 +283,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
                        take_merit ? fused_merit : nullptr, 0.0, grouped ? &gcol : nullptr, 0.0, 1.0));
       std::swap(px->d, xt->d);
       if (lean) {
-        pz_stored = false;
+        step_flags.pz_stored = false;
         step_beta_mu = beta_mu;
       }
       if (take_merit) {
@@ -335,9 +300,9 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
         mins_w[0] = w_step_out[3];
         mins_w[1] = w_step_out[4];
         for (int i = 0; i < 3; i++) w_comp_poly[i] = w_step_out[i];
-        fused_merit_valid = true;
-        w_comp_valid = true;
-        w_merit_cache_valid = true;
+        step_flags.fused_merit_valid = true;
+        step_flags.w_comp_valid = true;
+        step_flags.w_merit_cache_valid = true;
         w_done = true;
       }
     } else {
@@ -358,15 +323,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   }
   step_mins[0] = std::min(mins_x[0], mins_w[0]);
   step_mins[1] = std::min(mins_x[1], mins_w[1]);
-  for (int i = 0; i < c; i++) {
-    const double zs1 = yz[i] - b.s[i];
-    const double zt1 = -b.t[i] - yz[i];
-    out.z[i] = yz[i] - yz2[i];
-    out.zs[i] = zs1 - yz2[i];
-    out.zt[i] = zt1 + yz2[i];
-    out.s[i] = (b.zs[i] - vars.s[i] * zs1) / vars.zs[i] + (vars.s[i] * yz2[i]) / vars.zs[i];
-    out.t[i] = (b.zt[i] - vars.t[i] * zt1) / vars.zt[i] - (vars.t[i] * yz2[i]) / vars.zt[i];
-  }
+  kkt.backSubstitute(1.0, b, vars, sol, true, out);
   return PO_OK;
 }
 
@@ -374,7 +331,8 @@ int InteriorPoint::computeKKTStepWithRefinementW(double mu, bool use_qn, double 
   const int nref = options.integer("iterative_refinement_steps");
   const double beta_mu = options.real("rel_bound_barrier") * mu;
   const bool seq_lin = options.integer("sequential_linear_method");
-  if (!(t0_valid && t0_mu == mu)) PO_TRY(computeResidualW(mu));  // (setUpKKTSystem did it for the fused first solve)
+  // (setUpKKTSystem did it for the fused first solve)
+  if (!(scratch_flags.t0_valid && t0_mu == mu)) PO_TRY(computeResidualW(mu));
   denseResidual(mu, res);
   PO_TRY(solveKKTW(res, mu, use_qn, false, tau, step, nref > 0));
   for (int it = 0; it < nref; it++) {  // :4985-4991
@@ -382,7 +340,7 @@ int InteriorPoint::computeKKTStepWithRefinementW(double mu, bool use_qn, double 
     std::vector<const double *> Pq = panel(qn && !seq_lin, &kq);
     const int mq = c + kq;
     std::vector<double> dots(mq > 0 ? mq : 1, 0.0);
-    if (analytic_panel_dots && ptpx_valid && mq == c + wk) {
+    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
       for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
     } else if (mq > 0) {
       PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));
@@ -407,7 +365,7 @@ int InteriorPoint::computeKKTStepWithRefinementW(double mu, bool use_qn, double 
     }
     // addKKTResStep (:1451-1583): design rows with the extra column Aw^T pzw, raw d1' into d1v (already there
     // when the first solve ran in its fused form)
-    if (!(it == 0 && residual_fused)) {
+    if (!(it == 0 && step_flags.residual_fused)) {
       if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], tvec) != 0) return PO_ERR_USER;
       Pq.push_back(tvec->d);
       coef[mres++] = 1.0;
@@ -420,7 +378,7 @@ int InteriorPoint::computeKKTStepWithRefinementW(double mu, bool use_qn, double 
     PO_TRY(computeResidualW(mu, false));
     if (prob->addSparseJacobian(-1.0, x, px, wresv[0]) != 0) return PO_ERR_USER;
     PO_TRY(k_w_res_step(ctx, wv(), wp(), wr(), nw, wd2->d));  // ... and d2 of the refinement's block solve
-    wd2_ready = true;
+    scratch_flags.wd2_ready = true;
     Dense r2;
     r2.resize(c);
     denseResidual(mu, r2);
@@ -454,13 +412,13 @@ int InteriorPoint::initLeastSquaresMultipliersW() {
   PO_TRY(prob->sparseFactor(x, Dinv, Cw));  // mat->factor (:5429)
   int k = 0;
   std::vector<const double *> A = panel(false, &k);
-  W.assign((size_t)c * c, 0.0);
+  kkt.W.assign((size_t)c * c, 0.0);
   std::vector<int> piv(c > 0 ? c : 1);
   if (c > 0) {
-    PO_TRY(k_wgram(ctx, Dinv->d, A.data(), c, n, W.data()));
+    PO_TRY(k_wgram(ctx, Dinv->d, A.data(), c, n, kkt.W.data()));
     PO_TRY(sparseGramCorrection(A, c, nullptr));
-    for (int i = 0; i < c; i++) W[(size_t)i * (c + 1)] += small;
-    lu_factor(c, W.data(), c, piv.data());
+    for (int i = 0; i < c; i++) kkt.W[(size_t)i * (c + 1)] += small;
+    lu_factor(c, kkt.W.data(), c, piv.data());
   }
   // rx = -(g - zl + zu)
   const double al[2] = {1.0, -1.0};
@@ -471,7 +429,7 @@ int InteriorPoint::initLeastSquaresMultipliersW() {
   if (c > 0) {
     PO_TRY(k_mdot(ctx, tvec->d, A.data(), c, n, z.data()));
     for (int i = 0; i < c; i++) z[i] = -z[i];
-    lu_solve(c, W.data(), c, piv.data(), z.data());
+    lu_solve(c, kkt.W.data(), c, piv.data(), z.data());
     PO_TRY(k_panel_axpy(ctx, d1v->d, 0.0, nullptr, 1.0, z.data(), A.data(), c, n));
   }
   PO_TRY(applyK0(d1v->d, nullptr, tvec, wyw));
@@ -480,7 +438,7 @@ int InteriorPoint::initLeastSquaresMultipliersW() {
     vars.z[i] = (z[i] < -gam || z[i] > gam) ? 0.0 : z[i];
   }
   PO_TRY(k_w_clip(ctx, wvar[0]->d, wyw->d, gsw->d, gtw->d, nw));
-  panel_valid = false;  // Uw was built with Dinv = 1 and the constraint columns only
+  scratch_flags.panel_valid = false;  // Uw was built with Dinv = 1 and the constraint columns only
   return PO_OK;
 }
 
