@@ -4,16 +4,22 @@ bench.py -- IP iterations/sec of the MI355X-native interior point on BASELINE.js
 configuration (config 3: separable random_convex, n = 50 M design variables, m = 32 dense
 constraints + bounds, L-SR1(10) Hessian), the HBM roofline of the headline kernel
 (ParOptVec::mdot over the 32-column dense-constraint panel) and of the whole iteration, a second
-roofline entry for the weighted-Gram kernel, same-run stream ceilings and a CPU baseline.
+roofline entry for the weighted-Gram kernel; with --full also same-run stream ceilings and a CPU
+baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--boundary builtin|facade|both]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--boundary builtin|facade|both] [--full]
 
 `value` is measured under the REFERENCE's problem contract (src/ParOptProblem.h:146-189): the gradient callback
-rewrites the whole constraint Jacobian at every call.  The variant with the library's opt-in declaration that the
-dense constraints are linear (po_problem_set_linear_constraints, an EXTENSION of the reference API) is reported
-beside it under `variants`, never as `value`.  --boundary facade makes `value` the same workload implemented as a
-USER's ParOptProblem subclass outside the library (examples/random_convex_amd.cpp on include/ParOptAMD.hpp); the
-default run reports that measurement under `boundary`.
+rewrites the whole constraint Jacobian at every call.  --boundary facade makes `value` the same workload implemented
+as a USER's ParOptProblem subclass outside the library (examples/random_convex_amd.cpp on include/ParOptAMD.hpp).
+
+A plain run measures the headline variant and nothing else: set-up, the R repeats, --dump-outputs, the line (with
+the figures the timed runs themselves record: counters, bytes, phases, the HIP-event times of the mdot and Gram
+launches).  --full adds everything beside it: the variant with the library's opt-in declaration that the dense
+constraints are linear (po_problem_set_linear_constraints, an EXTENSION of the reference API) under `variants`, never
+as `value`; the facade workload under `boundary` (--boundary defaults to both); an isolated mdot loop and same-run
+stream ceilings under `roofline`; the collective exchange (N > 1) under `collective_us`; the CPU baseline under
+`cpu_baseline`.  What a plain run leaves out is null in its line (or, for variants, absent).
 
 N = 1 runs in this process.  N > 1 without WORLD_SIZE in the environment: this script starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py` as a CHILD process
@@ -350,20 +356,23 @@ def parse_args(argv=None):
     ap.add_argument("--nwcon", type=int, default=0,
                     help="config 4: number of sparse weighting constraints (one per group of --nw variables)")
     ap.add_argument("--nw", type=int, default=20)
-    ap.add_argument("--boundary", type=str, default="both", choices=["builtin", "facade", "both"],
+    ap.add_argument("--boundary", type=str, default=None, choices=["builtin", "facade", "both"],
                     help="builtin: the library's own SeparableProblem; facade: the same workload as a user's "
                          "ParOptProblem subclass outside the library (examples/random_convex_amd.cpp), which then "
-                         "is `value`; both (default): `value` from the built-in, the facade measurement under "
-                         "`boundary`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds the CPU baseline leg may take")
+                         "is `value`; both: `value` from the built-in, the facade measurement under `boundary` "
+                         "(default: both with --full, else builtin)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: API-extension variants, the facade under "
+                         "`boundary`, isolated mdot loop and stream ceilings, collective exchange, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds the CPU baseline leg may take (--full)")
     ap.add_argument("--cpu-full-size", action="store_true",
-                    help="also run the reference ONCE at the workload's own n (minutes; builder runs only)")
+                    help="--full: also run the reference ONCE at the workload's own n (minutes; builder runs only)")
     ap.add_argument("--cpu-iters", type=int, default=0,
                     help="major iterations of a CPU baseline run (default and minimum: qn_size + 8, so that at least "
                          "six run with full quasi-Newton memory)")
     ap.add_argument("--skip-extension-variant", action="store_true",
-                    help="do not also measure the linear-constraint declaration (API extension) beside the headline")
+                    help="--full without the linear-constraint declaration (API extension) beside the headline")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N>1: continue on a torch.distributed callback if the native RCCL communicator fails "
                          "(default: exit non-zero)")
@@ -371,7 +380,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the headline variant's optimize() returned in its last "
                          "repeat as DIR/<name>.npy (float64): x, zl, zu (and the sparse multipliers and slacks) at a "
                          "fixed seeded sample of their entries, the dense multipliers and slacks, fobj and the counters")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.boundary is None:
+        a.boundary = "both" if a.full else "builtin"
+    return a
 
 
 def launch_children(a, argv):
@@ -641,7 +653,7 @@ def main():
     if a.boundary != "facade":
         prob.setLinearConstraints(False)
         variants["jacobian_rewritten_every_gradient_call"] = measure(prob, keep_outputs=dump)
-        if not a.skip_extension_variant:
+        if a.full and not a.skip_extension_variant:
             prob.setLinearConstraints(True)
             variants["linear_constraints_declared__API_EXTENSION"] = measure(prob)
             prob.setLinearConstraints(False)
@@ -679,8 +691,9 @@ def main():
         else:
             up = pa.UserLibraryProblem(ctx, USER_LIB, a.n, a.ncon)
             fac = {"reference_semantics": measure(up, lambda: up.ownKernelBytes(True), dump and a.boundary == "facade")}
-            up.setDeferredReductions(True)
-            fac["deferred_reductions__API_EXTENSION"] = measure(up, lambda: up.ownKernelBytes(True))
+            if a.full:
+                up.setDeferredReductions(True)
+                fac["deferred_reductions__API_EXTENSION"] = measure(up, lambda: up.ownKernelBytes(True))
             up.close()
             boundary = {"what": "the workload as a USER ParOptProblem subclass on include/ParOptAMD.hpp, compiled outside "
                                 "libparopt_amd.so with its own HIP kernels (examples/random_convex_amd.cpp); "
@@ -689,8 +702,7 @@ def main():
                                 "opt-in of po_problem_set_deferred_reductions",
                         **{k: summary(v) for k, v in fac.items()}}
             if a.boundary == "facade":
-                variants = {"facade_reference_semantics": fac["reference_semantics"],
-                            "facade_deferred_reductions__API_EXTENSION": fac["deferred_reductions__API_EXTENSION"]}
+                variants = {"facade_" + k: v for k, v in fac.items()}
     head = next(iter(variants))
     elapsed, times, det, runs = variants[head]
     if dump and rank == 0:
@@ -703,23 +715,25 @@ def main():
     all_runs = [r for v in variants.values() for r in v[3]]
 
     # ---- roofline of the headline kernel, measured live with HIP events on the context stream ----
-    x = pa.PVec(ctx, nl).fill_hash(1, 10, offset, 2.0, -1.0)
-    # the dense-constraint panel the solver itself streams: fresh hash vectors of the same shape
-    V = [pa.PVec(ctx, nl).fill_hash(1, 20 + j, offset, 2.0, -1.0) for j in range(a.ncon)]
-    ms_isolated, _ = pa.bench_mdot(x, V, 20)
-    # same-run stream ceilings: what a read-only stream and a copy reach on this box right now
-    ms_ro = pa.bench_stream(x, V[0], 0, 20)
-    ms_cp = pa.bench_stream(x, V[0], 1, 20)
-    stream = {"read_only_GBps": 16.0 * nl / (ms_ro * 1e-3) * 1e-9, "copy_GBps": 16.0 * nl / (ms_cp * 1e-3) * 1e-9,
-              "what": "x.y over two %d-element vectors (read-only) and y <- x (copy), 20 launches each, "
-                      "HIP events on the solver's stream, same process as the timed run" % nl}
+    ms_isolated, stream = None, None
+    if a.full:
+        x = pa.PVec(ctx, nl).fill_hash(1, 10, offset, 2.0, -1.0)
+        # the dense-constraint panel the solver itself streams: fresh hash vectors of the same shape
+        V = [pa.PVec(ctx, nl).fill_hash(1, 20 + j, offset, 2.0, -1.0) for j in range(a.ncon)]
+        ms_isolated, _ = pa.bench_mdot(x, V, 20)
+        # same-run stream ceilings: what a read-only stream and a copy reach on this box right now
+        ms_ro = pa.bench_stream(x, V[0], 0, 20)
+        ms_cp = pa.bench_stream(x, V[0], 1, 20)
+        stream = {"read_only_GBps": 16.0 * nl / (ms_ro * 1e-3) * 1e-9, "copy_GBps": 16.0 * nl / (ms_cp * 1e-3) * 1e-9,
+                  "what": "x.y over two %d-element vectors (read-only) and y <- x (copy), 20 launches each, "
+                          "HIP events on the solver's stream, same process as the timed run" % nl}
     # the figure of record: the mdot<ncon> launches issued in the timed regions (the constraint evaluations of the
     # line search: the problem's own ParOptVec::mdot calls), HIP events on the launch stream
     mdot_ms_run = sum(r[1]["mdot_ms"] for r in all_runs)
     mdot_launches_run = sum(r[1]["mdot_n"] for r in all_runs)
     ms = mdot_ms_run / mdot_launches_run if mdot_launches_run > 0 else ms_isolated
     alg_bytes = 8.0 * (a.ncon + 1) * nl
-    achieved = alg_bytes / (ms * 1e-3) * 1e-9
+    achieved = alg_bytes / (ms * 1e-3) * 1e-9 if ms else None
     traffic, traffic_src = None, None
     # PMC bytes per launch from committed rocprofv3 passes (NOT measured in this run) of this exact shape: round 4's
     # collection of the configuration (per-kernel FETCH_SIZE / WRITE_SIZE), else the older files
@@ -746,7 +760,8 @@ def main():
         except Exception:
             pass
     roofline = {"bound": "hbm", "kernel": "mdot_kernel<32> (ParOptVec::mdot, nvecs=%d, n_local=%d)" % (a.ncon, nl),
-                "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBPS if achieved else None,
                 "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": ms,
                 "launches_timed_in_run": mdot_launches_run,
                 "avg_launch_ms_isolated_loop": ms_isolated, "algorithmic_bytes": alg_bytes,
@@ -775,7 +790,7 @@ def main():
     # ---- N > 1: what one reduction exchange costs on this communicator (the iteration pays host_syncs_per_iter
     # of them), in the two forms the solver uses ----
     collective = None
-    if world > 1 or forced_rccl:
+    if a.full and (world > 1 or forced_rccl):
         collective = {"allreduce_2628_doubles": ctx.bench_collective(2628, True, 50),
                       "allgather_16_doubles": ctx.bench_collective(16, False, 50),
                       "what": "final-stage payload -> collective -> device-to-host copy -> host sync, median of 50 "
@@ -783,7 +798,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(a.n, a.ncon, a.cpu_iters, log, a.nwcon, a.nw, a.qn, a.qn_size, a.problem, a.cpu_budget,
                                a.cpu_full_size)
         niter = det["niter"]

@@ -50,8 +50,8 @@ def test_bench_gpus2_shared_gpu():
     """`python bench.py --gpus 2` (the shape of the driver's command) on a 1-GPU box: both ranks share GPU 0 and
     reduce through the host-callback communicator; the line must say n_gpus == 2 and carry the contract fields."""
     out, lines = _run(["--gpus", "2", "--nglobal", "2000000", "--steps", "3", "--warmup", "3", "--repeats", "2",
-                       "--no-cpu-baseline", "--qn-size", "3", "--boundary", "builtin"], {"PAROPT_BENCH_SHARE_GPU": "1"},
-                      900)
+                       "--full", "--no-cpu-baseline", "--qn-size", "3", "--boundary", "builtin"],
+                      {"PAROPT_BENCH_SHARE_GPU": "1"}, 900)
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(lines) == 1, out.stdout
     r = json.loads(lines[0])
@@ -71,7 +71,7 @@ def test_bench_gpus2_shared_gpu():
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
     out, lines = _run(["--nglobal", "1000000", "--steps", "3", "--warmup", "3", "--repeats", "1",
-                       "--no-cpu-baseline", "--qn-size", "3"], {}, 900)
+                       "--full", "--no-cpu-baseline", "--qn-size", "3"], {}, 900)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads(lines[0])
     assert r["n_gpus"] == 1 and r["metric"].startswith("IP iterations/sec") and "n=1M vars m=32" in r["metric"]
@@ -97,6 +97,26 @@ def test_bench_single_gpu_line():
     assert fd["host_syncs_per_iter"] < fr["host_syncs_per_iter"]
     assert fd["host_syncs_per_iter"] <= head["host_syncs_per_iter"] + 0.5
     assert abs(fr["iteration_bytes"] - head["iteration_bytes"]) < 0.05 * head["iteration_bytes"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full the run measures the headline variant alone: no extension variant, no facade, no isolated
+    loops, no CPU baseline; the figures the timed runs record themselves are still in the line."""
+    out, lines = _run(["--nglobal", "1000000", "--steps", "3", "--warmup", "3", "--repeats", "1", "--qn-size", "3"],
+                      {}, 900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert list(r["variants"]) == ["jacobian_rewritten_every_gradient_call"]
+    assert r["config"]["headline_variant"] == "jacobian_rewritten_every_gradient_call"
+    assert abs(r["value"] - r["variants"]["jacobian_rewritten_every_gradient_call"]["value"]) < 1e-9 * r["value"]
+    assert r["boundary"] is None and r["cpu_baseline"] is None and r["collective_us"] is None
+    roof = r["roofline"]
+    assert roof["stream_ceiling"] is None and roof["avg_launch_ms_isolated_loop"] is None
+    assert roof["launches_timed_in_run"] > 0 and roof["achieved"] > 0
+    assert roof["second"] is not None and roof["second"]["hbm"]["frac"] > 0
+    assert r["iteration_bytes"] > r["iteration_bytes_user_callbacks"] > 0 and r["user_eval_ms_per_iter"] > 0
 
 
 @pytest.mark.gpu
@@ -154,6 +174,17 @@ def test_torchrun_child_at_n1_equals_the_in_process_path():
     assert "n_local" in child["iteration_frac_basis"]
     frac = child["iteration_bytes"] / (child["ms_per_step"] * 1e-3) * 1e-9 / 8000.0
     assert abs(frac - child["iteration_frac"]) <= 1e-9
+
+
+def test_full_selects_the_extra_measurements_cpu():
+    """--boundary follows --full unless given: a plain run measures the built-in problem alone."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert not bench.parse_args([]).full and bench.parse_args([]).boundary == "builtin"
+    assert bench.parse_args(["--full"]).full and bench.parse_args(["--full"]).boundary == "both"
+    assert bench.parse_args(["--boundary", "facade"]).boundary == "facade"
+    assert bench.parse_args(["--full", "--boundary", "builtin"]).boundary == "builtin"
 
 
 def test_host_cpu_budget_respects_affinity_cpu():

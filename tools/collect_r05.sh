@@ -11,10 +11,10 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 case $cfg in
-  c3) prog=bench.py; args="--steps 20 --warmup 5" ;;
-  c3l) prog=bench.py; args="--qn bfgs --qn-size 20 --steps 20 --warmup 22 --boundary builtin" ;;
-  c2) prog=bench.py; args="--nglobal 10000000 --ncon 8 --qn bfgs --qn-size 20 --problem quadratic --steps 20 --warmup 22 --boundary builtin" ;;
-  c4) prog=bench.py; args="--nglobal 20000000 --ncon 4 --nwcon 1000000 --nw 20 --qn bfgs --steps 20 --warmup 12 --boundary both" ;;
+  c3) prog=bench.py; args="--full --steps 20 --warmup 5" ;;
+  c3l) prog=bench.py; args="--full --qn bfgs --qn-size 20 --steps 20 --warmup 22 --boundary builtin" ;;
+  c2) prog=bench.py; args="--full --nglobal 10000000 --ncon 8 --qn bfgs --qn-size 20 --problem quadratic --steps 20 --warmup 22 --boundary builtin" ;;
+  c4) prog=bench.py; args="--full --nglobal 20000000 --ncon 4 --nwcon 1000000 --nw 20 --qn bfgs --steps 20 --warmup 12 --boundary both" ;;
   c5) prog=tools/bench_tr.py; args="" ;;
   *) echo "unknown configuration $cfg"; exit 2 ;;
 esac
