@@ -183,6 +183,44 @@ int po_vec_maxpy(po_vec y, double beta, const double *alpha, const po_vec *vecs,
 int po_vec_fill_hash(po_vec v, uint64_t seed, uint64_t array_id, int64_t offset, double scale,
                      double shift);
 
+/* ---- zero-copy export of a vector (not in the reference): DLPack ------------------------------
+ * The structs below have the layout of DLPack's DLDevice, DLDataType, DLTensor and DLManagedTensor (dlpack.h, the
+ * unversioned ABI that every DLPack consumer accepts), under names of this library so that the header can be
+ * included next to dlpack.h; a pointer to one is a pointer to the other. */
+enum { PO_DL_CPU = 1, PO_DL_ROCM = 10 }; /* DLDeviceType: kDLCPU, kDLROCM */
+enum { PO_DL_FLOAT = 2 };                /* DLDataTypeCode: kDLFloat */
+typedef struct {
+  int32_t device_type;
+  int32_t device_id;
+} po_dl_device;
+typedef struct {
+  uint8_t code;
+  uint8_t bits;
+  uint16_t lanes;
+} po_dl_data_type;
+typedef struct {
+  void *data;
+  po_dl_device device;
+  int32_t ndim;
+  po_dl_data_type dtype;
+  int64_t *shape;
+  int64_t *strides; /* NULL: compact row-major */
+  uint64_t byte_offset;
+} po_dl_tensor;
+typedef struct po_dl_managed_tensor_s {
+  po_dl_tensor dl_tensor;
+  void *manager_ctx;
+  void (*deleter)(struct po_dl_managed_tensor_s *self);
+} po_dl_managed_tensor;
+/* The device ordinal of the context (the device_id of its DLPack tensors). */
+int po_ctx_device(po_ctx ctx, int *device);
+/* The vector's HBM as a DLPack tensor: 1-D, float64, PO_DL_ROCM on the context's device, data = the pointer of
+ * po_vec_get_device_array.  The tensor holds a reference on the vector (HBM outlives every other owner); its deleter
+ * drops that reference, and is a no-op once the context has been destroyed.  A live host mirror (po_vec_get_array) is
+ * uploaded and ended first: afterwards the device copy is authoritative.  The tensor is ordered with the context's
+ * stream like every other use of the vector; a consumer on another stream synchronises with it itself. */
+int po_vec_to_dlpack(po_vec v, po_dl_managed_tensor **out);
+
 /* ---- ParOptCompactQuasiNewton: src/ParOptQuasiNewton.h:32-220 ----------------------------- */
 enum { PO_QN_BFGS = 0, PO_QN_SR1 = 1 };
 enum { PO_BFGS_SKIP_NEGATIVE_CURVATURE = 0, PO_BFGS_DAMPED_UPDATE = 1 }; /* :10-13 */

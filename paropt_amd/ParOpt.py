@@ -221,6 +221,19 @@ class Problem(_api.Problem):
         return self._user["grad"](_Host(x), _Host(g), [_Host(a) for a in A])
 
 
+class TorchProblem(_api.TorchProblem):
+    """``TorchProblem(comm, nvars=, ncon=, ...)``: the keyword arguments of Problem, callbacks on device tensors
+    (paropt_amd.TorchProblem)."""
+
+    def __init__(self, comm=None, **kwargs):
+        nvars, ncon, nwcon, nineq, nwineq = _sizes(kwargs)
+        self.comm = comm
+        super().__init__(getContext(), nvars, ncon, nineq, nwcon=nwcon, nwinequality=nwineq,
+                         use_lower=kwargs.get("use_lower", True), use_upper=kwargs.get("use_upper", True),
+                         rowp=kwargs.get("rowp"), cols=kwargs.get("cols"),
+                         nwblock=max(1, int(kwargs.get("nwblock", 1) or 1)))
+
+
 class _Host:
     """A numpy array dressed as a PVec for the callbacks (same item access / reductions)."""
 

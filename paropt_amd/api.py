@@ -4,6 +4,7 @@ reference's Python layer (paropt/ParOpt.pyx:761-1521: PVec, LBFGS, LSR1, Problem
 InteriorPoint) so tests read like the reference's own; all arithmetic happens in
 libparopt_amd.so on the GPU.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -171,6 +172,23 @@ class Context:
         self._keep.append(cb)
         check(lib.po_ctx_comm_init_callback(self._h, rank, size, cb, None))
 
+    def device(self):
+        """The device ordinal of the context (po_ctx_device)."""
+        d = C.c_int()
+        check(lib.po_ctx_device(self._h, C.byref(d)))
+        return d.value
+
+    def torch_stream(self):
+        """The context's HIP stream as a torch.cuda.ExternalStream (one per context): torch work issued under
+        `with torch.cuda.stream(ctx.torch_stream())` is ordered with the library's kernels without any
+        synchronisation."""
+        if getattr(self, "_torch_stream", None) is None:
+            import torch
+
+            self._torch_stream = torch.cuda.ExternalStream(lib.po_ctx_stream(self._h),
+                                                           device=torch.device("cuda", self.device()))
+        return self._torch_stream
+
     def close(self):
         """Destroy the context.  Objects created from it must not be used afterwards (their
         destructors become no-ops: the device memory went with the context's process)."""
@@ -305,6 +323,60 @@ class PVec:
         check(lib.po_vec_get_device_array(self._h, C.byref(p)))
         return C.cast(p, C.c_void_p).value
 
+    def as_tensor(self):
+        """The vector's HBM as a torch tensor (1-D float64 on the context's device, no copy: data_ptr() ==
+        device_ptr()).  The tensor holds a reference on the vector, so it stays valid after this wrapper and the
+        solver that owns the vector are gone; releasing it after Context.close() is harmless.  A live host mirror
+        (getArray) is uploaded and ended first.  Kernels on the tensor are ordered with the library's only under
+        `torch.cuda.stream(ctx.torch_stream())` (po_vec_to_dlpack)."""
+        mt = C.POINTER(L.DLManagedTensor)()
+        check(lib.po_vec_to_dlpack(self._h, C.byref(mt)))
+        return _tensor_from_dlpack(mt)
+
+
+# DLPack capsules ("dltensor", consumed by torch.from_dlpack) made from a managed tensor pointer
+_DLTENSOR = b"dltensor"
+_PyCapsule_New = C.pythonapi.PyCapsule_New
+_PyCapsule_New.restype = C.py_object
+_PyCapsule_New.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+
+
+def _tensor_from_dlpack(mt):
+    import torch
+
+    try:
+        return torch.from_dlpack(_PyCapsule_New(C.cast(mt, C.c_void_p), _DLTENSOR, None))
+    except BaseException:
+        mt.contents.deleter(mt)  # not consumed: its owner is dropped here
+        raise
+
+
+_BORROWED = {}  # address of a borrowed managed tensor -> the ctypes objects behind it
+
+
+@L.DL_DELETER_FN
+def _borrowed_deleter(mt):
+    try:
+        _BORROWED.pop(C.addressof(mt.contents), None)
+    except Exception:  # pragma: no cover - interpreter shutdown
+        pass
+
+
+def _borrowed_tensor(ptr, n, device):
+    """A torch view of `n` doubles of device memory the library owns (no reference is held: valid while the owner
+    is, e.g. a problem's sparse Jacobian values)."""
+    mt = L.DLManagedTensor()
+    shape = (C.c_int64 * 1)(int(n))
+    t = mt.dl_tensor
+    t.data = ptr
+    t.device.device_type, t.device.device_id = L.DL_ROCM, int(device)
+    t.ndim = 1
+    t.dtype.code, t.dtype.bits, t.dtype.lanes = L.DL_FLOAT, 64, 1
+    t.shape = C.cast(shape, L.c_i64_p)
+    mt.deleter = _borrowed_deleter
+    _BORROWED[C.addressof(mt)] = (mt, shape)
+    return _tensor_from_dlpack(C.pointer(mt))
+
 
 class _QuasiNewton:
     def __init__(self, ctx, kind, n, subspace, handle=None):
@@ -411,42 +483,38 @@ class Problem:
                 if self._pending_exc is not None:
                     return 1  # fail fast until optimize() has re-raised the first exception
                 try:
-                    return fn(*args)
+                    with self._callback_scope():
+                        return fn(*args)
                 except BaseException as e:  # noqa: BLE001 - re-raised by _raise_pending()
                     if self._pending_exc is None:
                         self._pending_exc = e
                     return 1
             return _g
 
+        # argument translation (_arg_in / _arg_out / _finish / _results, below): numpy copies and live host mirrors
+        # here, device views in TorchProblem
         @_guard
         def _gvb(user, x, lb, ub):
-            vx, vl, vu = (PVec(ctx, handle=L.po_vec(h), owned=False) for h in (x, lb, ub))
-            ax, al, au = vx.getArray(), vl.getArray(), vu.getArray()
+            out = []
+            ax, al, au = (self._arg_out(h, out) for h in (x, lb, ub))
             fail = self.getVarsAndBounds(ax, al, au)
-            vx.releaseArray(True), vl.releaseArray(True), vu.releaseArray(True)
+            self._finish(out)
             return int(fail or 0)
 
         @_guard
         def _eval(user, x, fobj, cons):
-            vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-            fail, f, con = self.evalObjCon(vx.to_numpy())
-            fobj[0] = float(f)
-            for j in range(self.ncon):
-                cons[j] = float(con[j])
+            fail, f, con = self.evalObjCon(self._arg_in(x))
+            self._results(fobj, cons, f, con)
             return int(fail)
 
         @_guard
         def _grad(user, x, g, Ac):
-            vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-            vg = PVec(ctx, handle=L.po_vec(g), owned=False)
+            out = []
+            ag = self._arg_out(g, out)
             # Ac is NULL when the problem declared linear constraints and only the objective gradient is wanted
-            va = [PVec(ctx, handle=L.po_vec(Ac[j]), owned=False) for j in range(self.ncon)] if Ac else []
-            ag = vg.getArray()
-            aa = [v.getArray() for v in va] if Ac else None
-            fail = self.evalObjConGradient(vx.to_numpy(), ag, aa)
-            vg.releaseArray(True)
-            for v in va:
-                v.releaseArray(True)
+            aa = [self._arg_out(Ac[j], out) for j in range(self.ncon)] if Ac else None
+            fail = self.evalObjConGradient(self._arg_in(x), ag, aa)
+            self._finish(out)
             return int(fail or 0)
 
         self._cbs = (L.GET_VARS_FN(_gvb), L.EVAL_FN(_eval), L.GRAD_FN(_grad))
@@ -465,28 +533,27 @@ class Problem:
         has_hvec, has_hdiag = hasattr(self, "evalHvecProduct"), hasattr(self, "evalHessianDiag")
         if has_hvec or has_hdiag:
             def _views(x, z, zw):
-                vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-                za = np.array([z[j] for j in range(self.ncon)])
-                zwa = PVec(ctx, handle=L.po_vec(zw), owned=False).to_numpy() if zw else None
-                return vx.to_numpy(), za, zwa
+                xa = self._arg_in(x)
+                za = np.array([z[j] for j in range(self.ncon)])  # z stays on the host, as in the reference
+                zwa = self._arg_in(zw) if zw else None
+                return xa, za, zwa
 
             @_guard
             def _hvec(user, x, z, zw, px, hvec):
                 xa, za, zwa = _views(x, z, zw)
-                vp = PVec(ctx, handle=L.po_vec(px), owned=False)
-                vh = PVec(ctx, handle=L.po_vec(hvec), owned=False)
-                ah = vh.getArray()
-                fail = self.evalHvecProduct(xa, za, zwa, vp.to_numpy(), ah)
-                vh.releaseArray(True)
+                out = []
+                ah = self._arg_out(hvec, out)
+                fail = self.evalHvecProduct(xa, za, zwa, self._arg_in(px), ah)
+                self._finish(out)
                 return int(fail or 0)
 
             @_guard
             def _hdiag(user, x, z, zw, hdiag):
                 xa, za, zwa = _views(x, z, zw)
-                vh = PVec(ctx, handle=L.po_vec(hdiag), owned=False)
-                ah = vh.getArray()
+                out = []
+                ah = self._arg_out(hdiag, out)
                 fail = self.evalHessianDiag(xa, za, zwa, ah)
-                vh.releaseArray(True)
+                self._finish(out)
                 return int(fail or 0)
 
             self._hcbs = (L.HVEC_FN(_hvec) if has_hvec else L.HVEC_FN(), L.HDIAG_FN(_hdiag) if has_hdiag else L.HDIAG_FN())
@@ -497,32 +564,25 @@ class Problem:
             nnz = int(self._rowp[-1])
             if len(self._cols) != nnz:
                 raise ValueError("cols is incorrect length")
-            self._data_host = np.zeros(max(nnz, 1))
+            self._data_host = None
 
             @_guard
             def _sobjcon(user, x, fobj, cons, sparse):
-                vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-                vs = PVec(ctx, handle=L.po_vec(sparse), owned=False)
-                asp = vs.getArray()
-                fail, f, con = self.evalSparseObjCon(vx.to_numpy(), asp)
-                vs.releaseArray(True)
-                fobj[0] = float(f)
-                for j in range(self.ncon):
-                    cons[j] = float(con[j])
+                out = []
+                asp = self._arg_out(sparse, out)
+                fail, f, con = self.evalSparseObjCon(self._arg_in(x), asp)
+                self._finish(out)
+                self._results(fobj, cons, f, con)
                 return int(fail or 0)
 
             @_guard
             def _sgrad(user, x, g, Ac, data, nnz_):
-                vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-                vg = PVec(ctx, handle=L.po_vec(g), owned=False)
-                va = [PVec(ctx, handle=L.po_vec(Ac[j]), owned=False) for j in range(self.ncon)]
-                ag = vg.getArray()
-                aa = [v.getArray() for v in va]
-                fail = self.evalSparseObjConGradient(vx.to_numpy(), ag, aa, self._data_host[:nnz])
-                vg.releaseArray(True)
-                for v in va:
-                    v.releaseArray(True)
-                check(lib.po_ctx_memcpy(ctx.handle, data, self._data_host.ctypes.data, 8 * nnz, 1))
+                out = []
+                ag = self._arg_out(g, out)
+                aa = [self._arg_out(Ac[j], out) for j in range(self.ncon)]
+                fail = self.evalSparseObjConGradient(self._arg_in(x), ag, aa, self._csr_values(data, nnz))
+                self._finish(out)
+                self._csr_values_done(data, nnz)
                 return int(fail or 0)
 
             self._csr_cbs = (L.SPARSE_OBJCON_FN(_sobjcon), L.SPARSE_GRAD_FN(_sgrad))
@@ -533,22 +593,19 @@ class Problem:
             def _wrap(method):
                 @_guard
                 def _f(user, alpha, x, v, out):
-                    vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-                    vv = PVec(ctx, handle=L.po_vec(v), owned=False)
-                    vo = PVec(ctx, handle=L.po_vec(out), owned=False)
-                    ao = vo.getArray()
-                    fail = method(float(alpha), vx.to_numpy(), vv.to_numpy(), ao)
-                    vo.releaseArray(True)
+                    done = []
+                    ao = self._arg_out(out, done)
+                    fail = method(float(alpha), self._arg_in(x), self._arg_in(v), ao)
+                    self._finish(done)
                     return int(fail or 0)
                 return _f
 
             @_guard
             def _wcon(user, x, out):
-                vx = PVec(ctx, handle=L.po_vec(x), owned=False)
-                vo = PVec(ctx, handle=L.po_vec(out), owned=False)
-                ao = vo.getArray()
-                fail = self.evalSparseCon(vx.to_numpy(), ao)
-                vo.releaseArray(True)
+                done = []
+                ao = self._arg_out(out, done)
+                fail = self.evalSparseCon(self._arg_in(x), ao)
+                self._finish(done)
                 return int(fail or 0)
 
             scb = L.ProblemSparseCallbacks()
@@ -570,6 +627,39 @@ class Problem:
         except Exception:
             pass
 
+    # -- argument translation of the callbacks: numpy copies in, live host mirrors out ------------------------------
+    def _callback_scope(self):
+        return contextlib.nullcontext()
+
+    def _arg_in(self, h):
+        """A vector the callback reads (x, px, zw, ...)."""
+        return PVec(self.ctx, handle=L.po_vec(h), owned=False).to_numpy()
+
+    def _arg_out(self, h, out):
+        """A vector the callback writes: its live host mirror, ended by _finish(out) after the callback."""
+        v = PVec(self.ctx, handle=L.po_vec(h), owned=False)
+        out.append(v)
+        return v.getArray()
+
+    def _finish(self, out):
+        for v in out:
+            v.releaseArray(True)
+
+    def _results(self, fobj, cons, f, con):
+        """(fobj, con) of evalObjCon / evalSparseObjCon into the solver's result pointers."""
+        fobj[0] = float(f)
+        for j in range(self.ncon):
+            cons[j] = float(con[j])
+
+    def _csr_values(self, data, nnz):
+        """The `data` argument of evalSparseObjConGradient: a host buffer, copied to the device afterwards."""
+        if self._data_host is None:
+            self._data_host = np.zeros(max(nnz, 1))
+        return self._data_host[:nnz]
+
+    def _csr_values_done(self, data, nnz):
+        check(lib.po_ctx_memcpy(self.ctx.handle, data, self._data_host.ctypes.data, 8 * nnz, 1))
+
     def _raise_pending(self):
         """Re-raise the first exception a callback threw during the last solver call."""
         e, self._pending_exc = self._pending_exc, None
@@ -585,6 +675,96 @@ class Problem:
     @property
     def handle(self):
         return self._h
+
+
+class TorchProblem(Problem):
+    """A user problem in Python whose callbacks work on device tensors (torch): the constructor and the method names
+    of Problem, but every n- or w-sized argument is a zero-copy view of the library's vector (PVec.as_tensor), to be
+    written in place (x[:] = ..., g.copy_(...)).  No host mirror is ever made and nothing is copied between the
+    library's kernels and the user's.
+
+    - Callbacks run under torch.cuda.stream(ctx.torch_stream()); the library stream first waits (an event, not a host
+      synchronisation) for the torch stream that was current, so data prepared there beforehand is complete.
+    - evalObjCon / evalSparseObjCon return (fail, fobj, con) either as host numbers (the final global values, as in
+      Problem) or as float64 tensors on the device (fobj 0-d, con of length ncon): this rank's part, summed over the
+      ranks by the library (po_ctx_reduce_device) into the solver's results.  The tensors are kept until the
+      reduction has consumed them.
+    - A of evalObjConGradient is a list of ncon views (None after setLinearConstraints); z of evalHvecProduct /
+      evalHessianDiag stays a host numpy array, zw is a view; data of evalSparseObjConGradient is a view of the
+      library's device array of Jacobian values (valid during the callback).
+    - setDeferredReductions(True): the results are device tensors and the callbacks never read a library reduction
+      on the host, so the solver may reduce them together with its own (po_problem_set_deferred_reductions).
+    """
+
+    def __init__(self, ctx, nvars, ncon, ninequality=-1, nwcon=0, nwinequality=0, use_lower=True,
+                 use_upper=True, rowp=None, cols=None, nwblock=1):
+        import collections
+
+        import torch
+
+        self._torch = torch
+        self._stream = ctx.torch_stream()
+        self._device = self._stream.device
+        self._held = collections.deque()  # device results until their reduction has consumed them
+        self._drop_cb = L.AFTER_REDUCE_FN(self._drop_held)
+        self._data_view = None
+        super().__init__(ctx, nvars, ncon, ninequality, nwcon=nwcon, nwinequality=nwinequality, use_lower=use_lower,
+                         use_upper=use_upper, rowp=rowp, cols=cols, nwblock=nwblock)
+
+    def setDeferredReductions(self, flag=True):
+        check(lib.po_problem_set_deferred_reductions(self._h, int(bool(flag))))
+        return self
+
+    # -- argument translation: device views ------------------------------------------------------------------------
+    def _callback_scope(self):
+        s = self._stream
+        cur = self._torch.cuda.current_stream(self._device)
+        if cur.cuda_stream != s.cuda_stream:
+            s.wait_stream(cur)
+        return self._torch.cuda.stream(s)
+
+    def _arg_in(self, h):
+        return PVec(self.ctx, handle=L.po_vec(h), owned=False).as_tensor()
+
+    def _arg_out(self, h, out):
+        return PVec(self.ctx, handle=L.po_vec(h), owned=False).as_tensor()
+
+    def _finish(self, out):
+        pass
+
+    def _results(self, fobj, cons, f, con):
+        torch = self._torch
+        if not (isinstance(f, torch.Tensor) or isinstance(con, torch.Tensor)):
+            return super()._results(fobj, cons, f, con)
+        ft = self._device_result(f, 1, "fobj")
+        ct = self._device_result(con, self.ncon, "con") if self.ncon > 0 else None
+        self._held.append((ft, ct))
+        check(lib.po_ctx_reduce_device(self.ctx.handle, ft.data_ptr(), 1, 0, fobj))
+        if ct is not None:
+            check(lib.po_ctx_reduce_device(self.ctx.handle, ct.data_ptr(), self.ncon, 0, cons))
+        check(lib.po_ctx_after_reduce(self.ctx.handle, C.cast(self._drop_cb, C.c_void_p), None))
+
+    def _device_result(self, t, n, what):
+        torch = self._torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self._device
+                and t.numel() == n and t.dim() == (0 if what == "fobj" else 1) and t.is_contiguous()):
+            raise TypeError("TorchProblem: %s must be a contiguous float64 tensor on %s with %s when the results are "
+                            "tensors (got %r)" % (what, self._device, "0 dimensions" if what == "fobj" else
+                                                  "%d entries" % n, t if not isinstance(t, torch.Tensor) else
+                                                  (t.dtype, t.device, tuple(t.shape))))
+        return t
+
+    def _drop_held(self, user):
+        if self._held:
+            self._held.popleft()
+
+    def _csr_values(self, data, nnz):
+        if self._data_view is None or self._data_view[0] != data:
+            self._data_view = (data, _borrowed_tensor(data, nnz, self._device.index))
+        return self._data_view[1]
+
+    def _csr_values_done(self, data, nnz):
+        pass
 
 
 class SeparableProblem:

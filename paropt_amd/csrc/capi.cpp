@@ -394,6 +394,55 @@ int po_vec_get_device_array(po_vec v, double **device) {
   *device = v->d;
   return PO_OK;
 }
+int po_ctx_device(po_ctx ctx, int *device) {
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(device);
+  *device = ctx->device;
+  return PO_OK;
+}
+namespace {
+// what a DLPack tensor of a vector owns: one reference on the vector, and its shape
+struct DlpackOwner {
+  po_dl_managed_tensor managed;
+  Vec *v;
+  Ctx *ctx;
+  unsigned long long ctx_serial;
+  int64_t shape[1];
+};
+void dlpack_deleter(po_dl_managed_tensor *self) {
+  if (!self) return;
+  DlpackOwner *o = static_cast<DlpackOwner *>(self->manager_ctx);
+  // after po_ctx_destroy the vector's stream is gone: nothing may be touched (Context.close's rule)
+  if (ctx_alive(o->ctx, o->ctx_serial)) vec_decref(o->v);
+  delete o;
+}
+}  // namespace
+int po_vec_to_dlpack(po_vec v, po_dl_managed_tensor **out) {
+  PO_CHECK_PTR(v);
+  PO_CHECK_PTR(out);
+  PO_TRY(po_vec_release_array(v, 1));
+  DlpackOwner *o = new DlpackOwner();
+  o->v = v;
+  o->ctx = v->ctx;
+  o->ctx_serial = v->ctx->serial;
+  o->shape[0] = v->n;
+  po_dl_tensor &t = o->managed.dl_tensor;
+  t.data = v->d;
+  t.device.device_type = PO_DL_ROCM;
+  t.device.device_id = v->ctx->device;
+  t.ndim = 1;
+  t.dtype.code = PO_DL_FLOAT;
+  t.dtype.bits = 64;
+  t.dtype.lanes = 1;
+  t.shape = o->shape;
+  t.strides = nullptr;
+  t.byte_offset = 0;
+  o->managed.manager_ctx = o;
+  o->managed.deleter = dlpack_deleter;
+  v->ref++;
+  *out = &o->managed;
+  return PO_OK;
+}
 int po_vec_maxpy(po_vec y, double beta, const double *alpha, const po_vec *vecs, int nvecs) {
   PO_CHECK_PTR(y);
   std::vector<const double *> p(nvecs > 0 ? nvecs : 1);

@@ -9,6 +9,8 @@
 #include <time.h>
 
 #include <algorithm>
+#include <mutex>
+#include <unordered_map>
 
 #include "core.hpp"
 
@@ -306,6 +308,19 @@ static void host_trace_atexit() {
   for (Ctx *c : g_traced)
     if (c) host_trace_report(c);
 }
+// Contexts alive in this process, each with the serial number it was created with: an object that can outlive its
+// context's Python wrapper (a DLPack view, po_vec_to_dlpack) asks here before it touches the context's vectors.  The
+// serial number tells a destroyed context from a new one that the allocator put at the same address.
+static std::mutex g_live_ctx_mutex;
+static std::unordered_map<const Ctx *, unsigned long long> g_live_ctx;
+static unsigned long long g_ctx_serial = 0;
+
+bool ctx_alive(const Ctx *c, unsigned long long serial) {
+  std::lock_guard<std::mutex> lock(g_live_ctx_mutex);
+  auto it = g_live_ctx.find(c);
+  return it != g_live_ctx.end() && it->second == serial;
+}
+
 int ctx_create(int device, Ctx **out) {
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -339,12 +354,21 @@ int ctx_create(int device, Ctx **out) {
   PO_HIP(hipEventCreate(&c->ev_mdot1));
   c->partials_cap = 0;
   if (dbg_switch(SW_NO_BATCH)) c->batch_enabled = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_live_ctx_mutex);
+    c->serial = ++g_ctx_serial;
+    g_live_ctx[c] = c->serial;
+  }
   *out = c;
   return ensure_partials(c, (size_t)c->max_blocks * 64);
 }
 
 int ctx_destroy(Ctx *c) {
   if (!c) return PO_OK;
+  {
+    std::lock_guard<std::mutex> lock(g_live_ctx_mutex);
+    g_live_ctx.erase(c);
+  }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   if (c->host_trace) {

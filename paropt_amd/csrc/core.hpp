@@ -43,6 +43,7 @@ enum CommKind { COMM_SELF = 0, COMM_RCCL = 1, COMM_CALLBACK = 2 };
 
 struct Ctx {
   int device = 0;
+  unsigned long long serial = 0;  // ctx_alive(): tells this context from a later one at the same address
   hipStream_t stream = nullptr;
   int num_cu = 256;
   int max_blocks = 2048;  // persistent-grid cap for streaming kernels
@@ -242,6 +243,8 @@ double host_now();  // seconds, monotonic
 inline double host_trace_begin(Ctx *c);
 inline void host_trace_end(Ctx *c, double t0);
 int ensure_partials(Ctx *c, size_t doubles);
+// the context has been created and not yet destroyed (the serial number it was created with, Ctx::serial)
+bool ctx_alive(const Ctx *c, unsigned long long serial);
 inline double host_trace_begin(Ctx *c) {
   if (!c->host_trace) return 0.0;
   const double t = host_now();

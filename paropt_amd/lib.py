@@ -52,6 +52,30 @@ po_csr_symbolic = C.c_void_p
 c_int_pp = C.POINTER(c_int_p)
 
 
+# DLPack (po_dl_* in include/paropt_amd.h: the layout of dlpack.h's DLManagedTensor)
+class DLDevice(C.Structure):
+    _fields_ = [("device_type", C.c_int32), ("device_id", C.c_int32)]
+
+
+class DLDataType(C.Structure):
+    _fields_ = [("code", C.c_uint8), ("bits", C.c_uint8), ("lanes", C.c_uint16)]
+
+
+class DLTensor(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("device", DLDevice), ("ndim", C.c_int32), ("dtype", DLDataType),
+                ("shape", c_i64_p), ("strides", c_i64_p), ("byte_offset", C.c_uint64)]
+
+
+class DLManagedTensor(C.Structure):
+    pass
+
+
+DL_DELETER_FN = C.CFUNCTYPE(None, C.POINTER(DLManagedTensor))
+DLManagedTensor._fields_ = [("dl_tensor", DLTensor), ("manager_ctx", C.c_void_p), ("deleter", DL_DELETER_FN)]
+DL_ROCM, DL_FLOAT = 10, 2
+AFTER_REDUCE_FN = C.CFUNCTYPE(None, C.c_void_p)
+
+
 class ProblemCallbacks(C.Structure):
     _fields_ = [
         ("user", C.c_void_p),
@@ -159,6 +183,8 @@ SIGNATURES = {
     "po_vec_sync_to_device": (C.c_int, [po_vec]),
     "po_vec_sync_to_host": (C.c_int, [po_vec]),
     "po_vec_get_device_array": (C.c_int, [po_vec, C.POINTER(c_double_p)]),
+    "po_ctx_device": (C.c_int, [po_ctx, c_int_p]),
+    "po_vec_to_dlpack": (C.c_int, [po_vec, C.POINTER(C.POINTER(DLManagedTensor))]),
     "po_vec_maxpy": (C.c_int, [po_vec, C.c_double, c_double_p, vec_p, C.c_int]),
     "po_vec_fill_hash": (C.c_int, [po_vec, C.c_uint64, C.c_uint64, C.c_int64, C.c_double, C.c_double]),
     "po_qn_create": (C.c_int, [po_ctx, C.c_int, C.c_int64, C.c_int, C.POINTER(po_qn)]),
