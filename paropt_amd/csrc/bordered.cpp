@@ -100,4 +100,14 @@ void Bordered::backSubstitute(double alpha, const Dense &b, const Dense &vars, c
   }
 }
 
+void denseResStep(const Dense &vars, const Dense &p, const double *apx, Dense &r) {
+  for (int i = 0; i < (int)r.z.size(); i++) {
+    r.z[i] -= (apx[i] - p.s[i] + p.t[i]);
+    r.s[i] += (p.zs[i] - p.z[i]);
+    r.t[i] += (p.zt[i] + p.z[i]);
+    r.zs[i] -= (p.s[i] * vars.zs[i] + vars.s[i] * p.zs[i]);
+    r.zt[i] -= (p.t[i] * vars.zt[i] + vars.t[i] * p.zt[i]);
+  }
+}
+
 }  // namespace po

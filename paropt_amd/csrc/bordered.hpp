@@ -5,6 +5,7 @@
 //   G  = W_AA + diag(s/zs + t/zt)                       (src/ParOptInteriorPoint.cpp:1952-1970)
 //   Ce = W_ZZ - W_ZA G^-1 W_AZ - M / (d0 d0^T)          (:2634-2667 via SURVEY.md 3.4)
 //   yz = G^-1 (alpha d3 - A t), zeta = Ce^-1 (Z^T t + W_ZA yz), yz2 = G^-1 (-W_AZ zeta)   (:2150-2159)
+// and the dense rows of the linearised KKT residual at a step (addKKTResStep :1529-1535).
 // No device calls: tools/host_sanitize.cpp checks it on the CPU.
 #pragma once
 #include <vector>
@@ -46,5 +47,8 @@ struct Bordered {
   // the dense blocks of the step; full: with the quasi-Newton correction yz2 (the GMRES loop leaves it out)
   void backSubstitute(double alpha, const Dense &b, const Dense &vars, const Sol &s, bool full, Dense &out) const;
 };
+
+// r -= the dense rows of the KKT matrix applied to the step p (addKKTResStep :1529-1535); apx = A px
+void denseResStep(const Dense &vars, const Dense &p, const double *apx, Dense &r);
 
 }  // namespace po

@@ -204,6 +204,52 @@ std::vector<const double *> InteriorPoint::panel(bool use_qn, int *k) const {
   return p;
 }
 
+std::vector<const double *> &InteriorPoint::LazyPanel::get() {
+  if (!asked) {
+    int k = 0;
+    P = ip->panel(use_qn, &k);
+    asked = true;
+  }
+  return P;
+}
+
+int InteriorPoint::stepPanelDots(LazyPanel &P, std::vector<double> &dots) {
+  const int mq = c + ((qn && P.use_qn) ? qn->size() : 0);
+  dots.assign(mq > 0 ? mq : 1, 0.0);
+  if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
+    for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
+  } else if (mq > 0) {
+    PO_TRY(k_mdot(ctx, px->d, P.get().data(), mq, n, dots.data()));
+  }
+  return PO_OK;
+}
+
+std::vector<double> InteriorPoint::compactInverse(const double *ztp, int kq) const {
+  std::vector<double> rz(ztp, ztp + kq);
+  qn->applyCompactInverse(rz.data());
+  return rz;
+}
+
+int InteriorPoint::residualCoefs(ResTerm term, const double *z, const double *ztpx, int kq, std::vector<double> &coef,
+                                 double *diag) {
+  for (int i = 0; i < c; i++) coef[i] = z[i];
+  *diag = options.real("qn_sigma");
+  if (term == RES_QN) {
+    *diag += qn->diag();
+    std::vector<double> rz = compactInverse(ztpx, kq);
+    for (int j = 0; j < kq; j++) coef[c + j] = rz[j];
+  } else if (term != RES_SIGMA) {
+    *diag = 0.0;
+    if (term == RES_HVEC) {
+      if (prob->evalHvecProduct(x, vars.z.data(), nullptr, px, xt) != 0) return PO_ERR_USER;
+    } else {
+      PO_TRY(k_mul(ctx, xt->d, 1.0, hdiag->d, px->d, n));
+    }
+    coef[c + kq] = -1.0;
+  }
+  return PO_OK;
+}
+
 void InteriorPoint::phaseBegin() {
   phase_t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -807,17 +853,7 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
   step_flags.vA_valid = true;
   std::vector<double> coef(m > 0 ? m : 1, 0.0);
   double diag = options.real("qn_sigma");
-  if (fuse) {
-    for (int i = 0; i < c; i++) coef[i] = alpha[i];
-    if (qn && !seq_lin) {
-      diag += qn->diag();
-      if (k > 0) {
-        std::vector<double> rz(ptpx.begin() + c, ptpx.begin() + c + k);
-        qn->applyCompactInverse(rz.data());
-        for (int j = 0; j < k; j++) coef[c + j] = rz[j];
-      }
-    }
-  }
+  if (fuse) PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, alpha.data(), ptpx.data() + c, k, coef, &diag));
   const bool first_fused = fuse && m > 0 && !corr;
   need_panel();
   if (first_fused) {
@@ -900,74 +936,60 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
 }
 
 int InteriorPoint::computeKKTStepWithRefinement(double mu, bool use_qn, double tau) {
-  if (has_w) return computeKKTStepWithRefinementW(mu, use_qn, tau);
   const int nref = options.integer("iterative_refinement_steps");
   const double beta_mu = options.real("rel_bound_barrier") * mu;
+  const bool with_qn = qn && !options.integer("sequential_linear_method");
+  const int mq = c + (with_qn ? qn->size() : 0);
+  // -H px (inexact Newton step) or -h o px in place of the quasi-Newton term.  The sparse path leaves the inexact
+  // Newton step out, which the reference does not (:1461), and tests hdiag besides the option
+  const bool diag_hess = options.integer("use_diag_hessian") && (!has_w || hdiag);
+  const ResTerm term = (!has_w && inexact_newton_step) ? RES_HVEC
+                       : diag_hess                     ? RES_HDIAG
+                       : with_qn                       ? RES_QN
+                                                       : RES_SIGMA;
+  // (setUpKKTSystem did it for the fused first solve)
+  if (has_w && !(scratch_flags.t0_valid && t0_mu == mu)) PO_TRY(computeResidualW(mu));
   denseResidual(mu, res);
-  PO_TRY(solveKKT(res, mu, use_qn, false, tau, step, nref > 0));
+  PO_TRY(has_w ? solveKKTW(res, mu, use_qn, false, tau, step, nref > 0)
+               : solveKKT(res, mu, use_qn, false, tau, step, nref > 0));
   for (int it = 0; it < nref; it++) {  // :4985-4991
-    // dots of the current step with [Ac | Z_qn]: A px for r'.z, Z^T px for B px
-    const bool with_qn = qn && !options.integer("sequential_linear_method");
-    int kq = with_qn ? qn->size() : 0;
-    // (the panel is only asked for when a pass below streams it: zPointers() forms unformed L-SR1 columns)
-    std::vector<const double *> Pq;
-    bool have_pq = false;
-    auto need_pq = [&]() {
-      if (!have_pq) {
-        int k2 = 0;
-        Pq = panel(with_qn, &k2);
-        have_pq = true;
-      }
-    };
-    const int mq = c + kq;
-    std::vector<double> dots(mq > 0 ? mq : 1, 0.0);
-    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
-      for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
-    } else if (mq > 0) {
-      need_pq();
-      PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));
-    }
-    double diag = options.real("qn_sigma");
-    std::vector<double> coef(mq + 1, 0.0);
-    for (int i = 0; i < c; i++) coef[i] = step.z[i];
+    LazyPanel Pq{this, with_qn};
+    if (has_w) Pq.get();  // (the sparse path takes it up front, streamed or not)
+    std::vector<double> dots;  // A px for r'.z, Z^T px for B px
+    PO_TRY(stepPanelDots(Pq, dots));
+    std::vector<double> coef(mq + 2, 0.0);
+    double diag = 0.0;
+    PO_TRY(residualCoefs(term, step.z.data(), dots.data() + c, mq - c, coef, &diag));
     int mres = mq;
-    if (inexact_newton_step || options.integer("use_diag_hessian")) {
-      // addKKTResStep :1461-1473: -H px (Hessian-vector product) or -h o px replaces the whole
-      // quasi-Newton term, sigma included; it rides as one more panel column with coefficient -1
-      diag = 0.0;
-      if (inexact_newton_step) {
-        if (prob->evalHvecProduct(x, vars.z.data(), nullptr, px, xt) != 0) return PO_ERR_USER;
-      } else {
-        PO_TRY(k_mul(ctx, xt->d, 1.0, hdiag->d, px->d, n));
-      }
-      need_pq();
-      Pq.push_back(xt->d);
-      coef[mq] = -1.0;
-      mres = mq + 1;
-    } else if (qn && !options.integer("sequential_linear_method")) {
-      diag += qn->diag();
-      if (kq > 0) {
-        std::vector<double> rz(dots.begin() + c, dots.begin() + c + kq);
-        qn->applyCompactInverse(rz.data());
-        for (int j = 0; j < kq; j++) coef[c + j] = rz[j];
-      }
+    if (term == RES_HVEC || term == RES_HDIAG) {
+      Pq.get().push_back(xt->d);
+      mres++;
     }
+    // addKKTResStep (:1451-1583): the design rows, Dinv o d1' into tvec or -- sparse path -- the raw d1' into d1v with
+    // the extra column Aw^T pzw; already there when the first solve ran in its fused form
     if (!(it == 0 && step_flags.residual_fused)) {
-      need_pq();
-      PO_TRY(k_res_step(ctx, bounds(), rx->d, px->d, pzl->d, pzu->d, Dinv->d, coef.data(), Pq.data(),
-                        mres, diag, beta_mu, n, tvec->d));
+      if (has_w) {
+        if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], tvec) != 0) return PO_ERR_USER;
+        Pq.get().push_back(tvec->d);
+        coef[mres++] = 1.0;
+      }
+      PO_TRY(k_res_step(ctx, bounds(), rx->d, px->d, pzl->d, pzu->d, has_w ? nullptr : Dinv->d, coef.data(),
+                        Pq.get().data(), mres, diag, beta_mu, n, has_w ? d1v->d : tvec->d));
+    }
+    if (has_w) {
+      // sparse rows (:1492-1527); only the blocks are rebuilt here.  w_sums / w_maxs are deliberately LEFT at the
+      // norms of the iterate's own barrier parameter (the affine solve of the Mehrotra strategies runs this with
+      // mu = 0, and nothing reads the norms before the next computeResidual evaluates them again)
+      PO_TRY(computeResidualW(mu, false));
+      if (prob->addSparseJacobian(-1.0, x, px, wresv[0]) != 0) return PO_ERR_USER;
+      PO_TRY(k_w_res_step(ctx, wv(), wp(), wr(), nw, wd2->d));  // ... and d2 of the refinement's block solve
+      scratch_flags.wd2_ready = true;
     }
     Dense r2;
     r2.resize(c);
     denseResidual(mu, r2);
-    for (int i = 0; i < c; i++) {  // addKKTResStep dense rows :1529-1535
-      r2.z[i] -= (dots[i] - step.s[i] + step.t[i]);
-      r2.s[i] += (step.zs[i] - step.z[i]);
-      r2.t[i] += (step.zt[i] + step.z[i]);
-      r2.zs[i] -= (step.s[i] * vars.zs[i] + vars.s[i] * step.zs[i]);
-      r2.zt[i] -= (step.t[i] * vars.zt[i] + vars.t[i] * step.zt[i]);
-    }
-    PO_TRY(solveKKT(r2, mu, use_qn, true, tau, refine));
+    denseResStep(vars, step, dots.data(), r2);
+    PO_TRY(has_w ? solveKKTW(r2, mu, use_qn, true, tau, refine) : solveKKT(r2, mu, use_qn, true, tau, refine));
     for (int i = 0; i < c; i++) {
       step.z[i] += refine.z[i];
       step.s[i] += refine.s[i];
@@ -993,16 +1015,9 @@ int InteriorPoint::checkKKTStep(int iteration, double mu) {
   const int mq = c + kq;
   std::vector<double> dots(mq > 0 ? mq : 1, 0.0), coef(mq > 0 ? mq : 1, 0.0);
   if (mq > 0) PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));  // explicit: this is a check
-  for (int i = 0; i < c; i++) coef[i] = step.z[i];
-  double diag = options.real("qn_sigma");
-  if (qn && !seq_lin && !options.integer("use_diag_hessian")) {
-    diag += qn->diag();
-    if (kq > 0) {
-      std::vector<double> rz(dots.begin() + c, dots.begin() + c + kq);
-      qn->applyCompactInverse(rz.data());
-      for (int j = 0; j < kq; j++) coef[c + j] = rz[j];
-    }
-  }
+  double diag = 0.0;
+  const bool with_qn = qn && !seq_lin && !options.integer("use_diag_hessian");
+  PO_TRY(residualCoefs(with_qn ? RES_QN : RES_SIGMA, step.z.data(), dots.data() + c, kq, coef, &diag));
   if (has_w) {  // the sparse multiplier step enters r'x through Aw^T pzw: one more column
     if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], xt) != 0) return PO_ERR_USER;
     Pq.push_back(xt->d);
@@ -1015,13 +1030,14 @@ int InteriorPoint::checkKKTStep(int iteration, double mu) {
   Dense r;
   r.resize(c);
   denseResidual(mu, r);
+  denseResStep(vars, step, dots.data(), r);
   double mz = 0.0, ms = 0.0, mt = 0.0, mzs = 0.0, mzt = 0.0;
-  for (int i = 0; i < c; i++) {  // addKKTResStep dense rows :1529-1535
-    mz = std::max(mz, fabs(r.z[i] - (dots[i] - step.s[i] + step.t[i])));
-    ms = std::max(ms, fabs(r.s[i] + (step.zs[i] - step.z[i])));
-    mt = std::max(mt, fabs(r.t[i] + (step.zt[i] + step.z[i])));
-    mzs = std::max(mzs, fabs(r.zs[i] - (step.s[i] * vars.zs[i] + vars.s[i] * step.zs[i])));
-    mzt = std::max(mzt, fabs(r.zt[i] - (step.t[i] * vars.zt[i] + vars.t[i] * step.zt[i])));
+  for (int i = 0; i < c; i++) {
+    mz = std::max(mz, fabs(r.z[i]));
+    ms = std::max(ms, fabs(r.s[i]));
+    mt = std::max(mt, fabs(r.t[i]));
+    mzs = std::max(mzs, fabs(r.zs[i]));
+    mzt = std::max(mzt, fabs(r.zt[i]));
   }
   if (ctx->rank == 0) {
     char line[640];
@@ -1436,9 +1452,8 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
   double out[6];
   double wm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const int kq = (qn && !seq_lin) ? qn->size() : 0;
-  std::vector<const double *> Pq;  // (asked for only if streamed: zPointers() forms unformed L-SR1 columns)
   const int mq = c + kq;
-  std::vector<double> dots(mq > 0 ? mq : 1, 0.0);
+  std::vector<double> dots;
   {
     // design part, panel products (when not known analytically) and sparse part: one collective + sync (the
     // problem's sparse callbacks run in between: built-in problems only)
@@ -1457,13 +1472,8 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
         step_flags.px_amax_valid = true;
       }
     }
-    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
-      for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
-    } else if (mq > 0) {
-      int k2 = 0;
-      Pq = panel(qn && !seq_lin, &k2);
-      PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));
-    }
+    LazyPanel Pq{this, qn && !seq_lin};
+    PO_TRY(stepPanelDots(Pq, dots));
     if (has_w && step_flags.w_merit_cache_valid) {
       // taken at sx = 1 in the refinement batch (solveKKTW); every sum that depends on the step is linear in sx > 0
       for (int i = 0; i < 10; i++) wm[i] = w_merit_cache[i];
@@ -1516,10 +1526,8 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
   } else if (qn && !seq_lin) {
     double v = qn->diag() * pxpx;
     if (kq > 0) {
-      std::vector<double> rz(dots.begin() + c, dots.begin() + c + kq);
-      std::vector<double> cf = rz;
-      qn->applyCompactInverse(cf.data());
-      for (int j = 0; j < kq; j++) v -= rz[j] * cf[j];
+      std::vector<double> cf = compactInverse(dots.data() + c, kq);
+      for (int j = 0; j < kq; j++) v -= dots[c + j] * cf[j];
     }
     pTBp = 0.5 * v;
   }

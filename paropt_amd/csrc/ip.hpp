@@ -294,12 +294,33 @@ class InteriorPoint {
   int panelImageVectors(int m, std::vector<double *> &U);  // Uw[0..m) as raw pointers (allocated on demand)
   int solveKKTW(const Dense &b, double mu, bool use_qn, bool refine_pass, double tau, Dense &out,
                 bool fuse_residual = false);
-  int computeKKTStepWithRefinementW(double mu, bool use_qn, double tau);
   int initLeastSquaresMultipliersW();
   int wCompStep(double ax, double az, double *prod);
 
   Bounds bounds() const;
   std::vector<const double *> panel(bool use_qn, int *k) const;
+  // the panel of a caller that may not stream it, asked for on first use: zPointers() forms unformed L-SR1 columns
+  struct LazyPanel {
+    const InteriorPoint *ip;
+    bool use_qn;
+    bool asked = false;
+    std::vector<const double *> P;
+    std::vector<const double *> &get();
+  };
+  // P^T px of the current (unscaled) step, c + kq values: ptpx when the solves kept it, else one k_mdot pass over P
+  int stepPanelDots(LazyPanel &P, std::vector<double> &dots);
+  // d0 M^-1 d0 Z^T p from ztp = Z^T p (kq = qn->size() values)
+  std::vector<double> compactInverse(const double *ztp, int kq) const;
+  // The design rows of the linearised KKT residual at the step (addKKTResStep :1461-1483) as coefficients of the
+  // panel [Ac | Z] with kq quasi-Newton columns: coef[0..c) = z, the step of the dense multipliers, and
+  //   RES_SIGMA:  diag = qn_sigma (no quasi-Newton term)
+  //   RES_QN:     diag = qn_sigma + b0, coef[c..c+kq) = d0 M^-1 d0 Z^T px, ztpx = Z^T px
+  //   RES_HVEC, RES_HDIAG: -H px (Hessian-vector product) or -h o px, formed into xt, replaces the quasi-Newton term,
+  //               sigma included: diag = 0, coef[c+kq] = -1 for xt as one more column of the caller's panel
+  // The caller sizes coef and zeroes it; entries of no term are left alone.
+  enum ResTerm { RES_SIGMA, RES_QN, RES_HVEC, RES_HDIAG };
+  int residualCoefs(ResTerm term, const double *z, const double *ztpx, int kq, std::vector<double> &coef,
+                    double *diag);
 
   int createQuasiNewton();
   int initAndCheckDesignAndBounds();

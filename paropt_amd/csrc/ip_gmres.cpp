@@ -234,8 +234,7 @@ int InteriorPoint::computeKKTGMRESStep(double rtol, double atol, bool use_qn, do
       if (qn && use_qn) {
         cf[0] = -qn->diag();
         if (kq > 0) {
-          std::vector<double> rz(ptpx.begin() + c, ptpx.begin() + c + kq);
-          qn->applyCompactInverse(rz.data());
+          std::vector<double> rz = compactInverse(ptpx.data() + c, kq);
           for (int j = 0; j < kq; j++) cf[1 + j] = rz[j];
           V.insert(V.end(), Z.begin(), Z.end());
         }

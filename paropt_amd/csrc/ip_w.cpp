@@ -223,16 +223,8 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
       a1.push_back(0.0);
     }
     const int np1 = (int)P1.size();
-    for (int i = 0; i < c; i++) c2[i] = alpha[i];  // = step.z
-    double diag = options.real("qn_sigma");
-    if (qn && !seq_lin) {
-      diag += qn->diag();
-      if (k > 0) {
-        std::vector<double> rz(ptpx.begin() + c, ptpx.begin() + c + k);
-        qn->applyCompactInverse(rz.data());
-        for (int j = 0; j < k; j++) c2[c + j] = rz[j];
-      }
-    }
+    double diag = 0.0;  // (alpha[0..c) = step.z)
+    PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, alpha.data(), ptpx.data() + c, k, c2, &diag));
     c2[m + 1] = 1.0;
     std::vector<double> so(m + 4, 0.0);
     // the raw right-hand side lands in y_qn (free while no corrector is active: y_qn is rebuilt from scratch by
@@ -324,81 +316,6 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   step_mins[0] = std::min(mins_x[0], mins_w[0]);
   step_mins[1] = std::min(mins_x[1], mins_w[1]);
   kkt.backSubstitute(1.0, b, vars, sol, true, out);
-  return PO_OK;
-}
-
-int InteriorPoint::computeKKTStepWithRefinementW(double mu, bool use_qn, double tau) {
-  const int nref = options.integer("iterative_refinement_steps");
-  const double beta_mu = options.real("rel_bound_barrier") * mu;
-  const bool seq_lin = options.integer("sequential_linear_method");
-  // (setUpKKTSystem did it for the fused first solve)
-  if (!(scratch_flags.t0_valid && t0_mu == mu)) PO_TRY(computeResidualW(mu));
-  denseResidual(mu, res);
-  PO_TRY(solveKKTW(res, mu, use_qn, false, tau, step, nref > 0));
-  for (int it = 0; it < nref; it++) {  // :4985-4991
-    int kq = 0;
-    std::vector<const double *> Pq = panel(qn && !seq_lin, &kq);
-    const int mq = c + kq;
-    std::vector<double> dots(mq > 0 ? mq : 1, 0.0);
-    if (forms.analytic_panel_dots && step_flags.ptpx_valid && mq == c + kkt.k) {
-      for (int i = 0; i < mq; i++) dots[i] = ptpx[i];
-    } else if (mq > 0) {
-      PO_TRY(k_mdot(ctx, px->d, Pq.data(), mq, n, dots.data()));
-    }
-    double diag = options.real("qn_sigma");
-    std::vector<double> coef(mq + 2, 0.0);
-    for (int i = 0; i < c; i++) coef[i] = step.z[i];
-    int mres = mq;
-    if (options.integer("use_diag_hessian") && hdiag) {
-      // -h o px replaces the whole quasi-Newton term, sigma included (:1464-1473)
-      diag = 0.0;
-      PO_TRY(k_mul(ctx, xt->d, 1.0, hdiag->d, px->d, n));
-      Pq.push_back(xt->d);
-      coef[mres++] = -1.0;
-    } else if (qn && !seq_lin) {
-      diag += qn->diag();
-      if (kq > 0) {
-        std::vector<double> rz(dots.begin() + c, dots.begin() + c + kq);
-        qn->applyCompactInverse(rz.data());
-        for (int j = 0; j < kq; j++) coef[c + j] = rz[j];
-      }
-    }
-    // addKKTResStep (:1451-1583): design rows with the extra column Aw^T pzw, raw d1' into d1v (already there
-    // when the first solve ran in its fused form)
-    if (!(it == 0 && step_flags.residual_fused)) {
-      if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], tvec) != 0) return PO_ERR_USER;
-      Pq.push_back(tvec->d);
-      coef[mres++] = 1.0;
-      PO_TRY(k_res_step(ctx, bounds(), rx->d, px->d, pzl->d, pzu->d, nullptr, coef.data(), Pq.data(),
-                        mres, diag, beta_mu, n, d1v->d));
-    }
-    // sparse rows (:1492-1527); only the blocks are rebuilt here.  w_sums / w_maxs are deliberately LEFT at the norms
-    // of the iterate's own barrier parameter (the affine solve of the Mehrotra strategies runs this with mu = 0, and
-    // nothing reads the norms before the next computeResidual evaluates them again)
-    PO_TRY(computeResidualW(mu, false));
-    if (prob->addSparseJacobian(-1.0, x, px, wresv[0]) != 0) return PO_ERR_USER;
-    PO_TRY(k_w_res_step(ctx, wv(), wp(), wr(), nw, wd2->d));  // ... and d2 of the refinement's block solve
-    scratch_flags.wd2_ready = true;
-    Dense r2;
-    r2.resize(c);
-    denseResidual(mu, r2);
-    for (int i = 0; i < c; i++) {  // dense rows :1529-1535
-      r2.z[i] -= (dots[i] - step.s[i] + step.t[i]);
-      r2.s[i] += (step.zs[i] - step.z[i]);
-      r2.t[i] += (step.zt[i] + step.z[i]);
-      r2.zs[i] -= (step.s[i] * vars.zs[i] + vars.s[i] * step.zs[i]);
-      r2.zt[i] -= (step.t[i] * vars.zt[i] + vars.t[i] * step.zt[i]);
-    }
-    PO_TRY(solveKKTW(r2, mu, use_qn, true, tau, refine));
-    for (int i = 0; i < c; i++) {
-      step.z[i] += refine.z[i];
-      step.s[i] += refine.s[i];
-      step.t[i] += refine.t[i];
-      step.zs[i] += refine.zs[i];
-      step.zt[i] += refine.zt[i];
-    }
-  }
-  sx = sz = 1.0;
   return PO_OK;
 }
 

@@ -251,6 +251,13 @@ SWEEP = [
     ("convex", 640, 98, "bfgs", 3, {"use_hvec_product": True, "gmres_subspace_size": 6, "nk_switch_tol": 1e3,
                                     "max_gmres_rtol": 1.0}, None),
     ("quadratic", 600, 60, "bfgs", 15, {}, None),                   # 60 + 30 = 90 columns: blocked Gram, fused passes
+    # iterative refinement off and twice, on the dense and on the weighting path (the default is one step)
+    ("convex", 257, 3, "bfgs", 5, {"iterative_refinement_steps": 0}, None),
+    ("convex", 257, 3, "bfgs", 5, {"iterative_refinement_steps": 2}, None),
+    ("quadratic", 300, 4, "sr1", 4, {"iterative_refinement_steps": 0}, None),
+    ("quadratic", 300, 4, "sr1", 4, {"iterative_refinement_steps": 2}, None),
+    ("convex", 513, 2, "bfgs", 5, {"iterative_refinement_steps": 0}, (51, 7, 3, 3, 51)),
+    ("convex", 513, 2, "bfgs", 5, {"iterative_refinement_steps": 2}, (51, 7, 3, 3, 51)),
 ]
 
 

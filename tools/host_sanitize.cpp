@@ -1,7 +1,7 @@
 // Host-side C++ of the product under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only, no GPU, no HIP
 // runtime): the in-repo LU (lu.cpp, the reference's dgetrf/dgetrs sites), the dense algebra of the bordered KKT solve
-// (bordered.cpp), the one-time symbolic analysis of the sparse Cholesky (csr.cpp::csr_analyse) and the option registry
-// (options.cpp).  Built by
+// and of the linearised KKT residual (bordered.cpp), the one-time symbolic analysis of the sparse Cholesky
+// (csr.cpp::csr_analyse) and the option registry (options.cpp).  Built by
 // `make -C paropt_amd/csrc sanitize`, run by tests/test_host_sanitize.py.  Exit code 0 = every check passed and no
 // sanitizer report.
 #include <math.h>
@@ -207,6 +207,33 @@ static void test_bordered() {
     }
 }
 
+// The dense rows of the linearised KKT residual (denseResStep): the bits of the expressions the refinement loop and
+// checkKKTStep wrote out, on data spread over six decades (a reassociated sum would round differently)
+static void test_dense_res_step() {
+  auto val = [] { return (rnd() - 0.5) * pow(10.0, 6.0 * rnd() - 3.0); };
+  for (int c : {0, 1, 7, 64}) {
+    Dense vars, p, r;
+    for (Dense *d : {&vars, &p, &r}) {
+      d->resize(c);
+      for (std::vector<double> *v : {&d->z, &d->s, &d->t, &d->zs, &d->zt})
+        for (double &e : *v) e = val();
+    }
+    std::vector<double> apx(c > 0 ? c : 1);
+    for (double &v : apx) v = val();
+    Dense want = r;
+    for (int i = 0; i < c; i++) {
+      want.z[i] = r.z[i] - (apx[i] - p.s[i] + p.t[i]);
+      want.s[i] = r.s[i] + (p.zs[i] - p.z[i]);
+      want.t[i] = r.t[i] + (p.zt[i] + p.z[i]);
+      want.zs[i] = r.zs[i] - (p.s[i] * vars.zs[i] + vars.s[i] * p.zs[i]);
+      want.zt[i] = r.zt[i] - (p.t[i] * vars.zt[i] + vars.t[i] * p.zt[i]);
+    }
+    denseResStep(vars, p, apx.data(), r);
+    CHECK(same_bits(r.z, want.z) && same_bits(r.s, want.s) && same_bits(r.t, want.t) &&
+          same_bits(r.zs, want.zs) && same_bits(r.zt, want.zt));
+  }
+}
+
 static void analyse(int64_t n, const std::vector<int> &rowp, const std::vector<int> &cols, bool expect_ok) {
   CsrSymbolic sym;
   const int64_t w = (int64_t)rowp.size() - 1;
@@ -312,6 +339,7 @@ static void test_options() {
 int main() {
   test_lu();
   test_bordered();
+  test_dense_res_step();
   test_csr();
   test_options();
   if (fails) {
