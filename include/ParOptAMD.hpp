@@ -441,28 +441,54 @@ class ParOptOptions : public ParOptBase {
 };
 
 // ---- ParOptQuasiDefMat: what createQuasiDefMat() returns (src/ParOptSparseMat.h:18-120) ------------------
-// In the reference these objects factor and apply the quasi-definite matrix on the host.  Here the library does
-// that on the device; the objects only say WHICH form the problem asks for: block diagonal with nwblock x nwblock
-// blocks (ParOptQuasiDefBlockMat) or a general sparse matrix from the CSR pattern (ParOptQuasiDefSparseMat).
+// The solver of the quasi-definite block [D Aw^T; Aw -C], with the reference's virtuals.  The two classes the
+// reference ships are library-backed here: they say WHICH of the library's device solvers the problem asks for -- block
+// diagonal with nwblock x nwblock blocks (ParOptQuasiDefBlockMat) or the sparse Cholesky on the CSR pattern
+// (ParOptQuasiDefSparseMat) -- and their factor / apply / getFactorInfo route to po_quasidef_* of the problem they were
+// built for.  ANY OTHER subclass returned by createQuasiDefMat() is the user's own solver: its methods are bound
+// through po_problem_set_quasidef_callbacks and the interior point calls them (cost model there).
 class ParOptProblem;
 class ParOptSparseProblem;
 class ParOptQuasiDefMat : public ParOptBase {
  public:
   virtual ~ParOptQuasiDefMat() {}
+  // :25  Dinv and Cdiag are borrowed until the next factor call; neither may be written
+  virtual int factor(ParOptVec *x, ParOptVec *Dinv, ParOptVec *Cdiag) = 0;
+  // :39 / :55  [D Aw^T; Aw -C] [yx; -yw] = [bx; bw] (bw = 0 in the three-argument form); bx and bw stay unmodified
+  virtual void apply(ParOptVec *bx, ParOptVec *yx, ParOptVec *yw) = 0;
+  virtual void apply(ParOptVec *bx, ParOptVec *bw, ParOptVec *yx, ParOptVec *yw) = 0;
+  virtual const char *getFactorInfo() { return NULL; }
+  // facade: non-zero for the library-backed classes, which then say which form they stand for
+  virtual int isLibraryBacked() { return 0; }
   virtual int getBlockSize() { return 1; }
   virtual int isSparse() { return 0; }
 };
-class ParOptQuasiDefBlockMat : public ParOptQuasiDefMat {
+// the library's own solver of `prob`, held as an object (methods defined behind ParOptProblem)
+class ParOptQuasiDefLibraryMat : public ParOptQuasiDefMat {
  public:
-  ParOptQuasiDefBlockMat(ParOptProblem *, int _nwblock) : nwblock(_nwblock < 1 ? 1 : _nwblock) {}
+  explicit ParOptQuasiDefLibraryMat(ParOptProblem *_prob) : prob(_prob), fx(NULL), fd(NULL), fc(NULL) {}
+  inline int factor(ParOptVec *x, ParOptVec *Dinv, ParOptVec *Cdiag);
+  inline void apply(ParOptVec *bx, ParOptVec *yx, ParOptVec *yw);
+  inline void apply(ParOptVec *bx, ParOptVec *bw, ParOptVec *yx, ParOptVec *yw);
+  inline const char *getFactorInfo();
+  int isLibraryBacked() { return 1; }
+
+ private:
+  ParOptProblem *prob;
+  ParOptVec *fx, *fd, *fc;  // the arguments of the last factor (borrowed, as in the reference)
+};
+class ParOptQuasiDefBlockMat : public ParOptQuasiDefLibraryMat {
+ public:
+  ParOptQuasiDefBlockMat(ParOptProblem *_prob, int _nwblock)
+      : ParOptQuasiDefLibraryMat(_prob), nwblock(_nwblock < 1 ? 1 : _nwblock) {}
   int getBlockSize() { return nwblock; }
 
  private:
   int nwblock;
 };
-class ParOptQuasiDefSparseMat : public ParOptQuasiDefMat {
+class ParOptQuasiDefSparseMat : public ParOptQuasiDefLibraryMat {
  public:
-  explicit ParOptQuasiDefSparseMat(ParOptSparseProblem *) {}
+  inline explicit ParOptQuasiDefSparseMat(ParOptSparseProblem *_prob);
   int isSparse() { return 1; }
 };
 
@@ -471,10 +497,10 @@ class ParOptProblem : public ParOptBase {
  public:
   explicit ParOptProblem(ParOptComm _comm)
       : comm(_comm), ctx(paropt_amd_context(_comm)), nvars(0), ncon(0), ninequality(-1), nwcon(0), nwinequality(-1),
-        nwblock(1), linear_constraints(0), hprob(NULL) {}
+        nwblock(1), linear_constraints(0), hprob(NULL), user_qd(NULL) {}
   ParOptProblem(ParOptComm _comm, int _nvars, int _ncon, int _ninequality, int _nwcon, int _nwinequality)
       : comm(_comm), ctx(paropt_amd_context(_comm)), nvars(_nvars), ncon(_ncon), ninequality(_ninequality),
-        nwcon(_nwcon), nwinequality(_nwinequality), nwblock(1), linear_constraints(0), hprob(NULL) {}
+        nwcon(_nwcon), nwinequality(_nwinequality), nwblock(1), linear_constraints(0), hprob(NULL), user_qd(NULL) {}
   // the nwblock of `new ParOptQuasiDefBlockMat(this, nwblock)` when createQuasiDefMat() is not overridden
   void setSparseBlockSize(int _nwblock) { nwblock = _nwblock; }
   // facade extension (po_problem_set_linear_constraints): the dense constraints are linear, evalObjConGradient is
@@ -492,6 +518,7 @@ class ParOptProblem : public ParOptBase {
   }
   virtual ~ParOptProblem() {
     if (hprob) po_problem_destroy(hprob);
+    if (user_qd) user_qd->decref();
   }
   ParOptComm getMPIComm() { return comm; }
   po_ctx getContext() { return ctx; }
@@ -552,10 +579,14 @@ class ParOptProblem : public ParOptBase {
   virtual po_problem handle() {
     if (!hprob) {
       ParOptQuasiDefMat *qd = createQuasiDefMat();
-      if (qd) {
+      if (qd) {  // asked for once; the solver increfs it, as in the reference
         qd->incref();
-        if (!qd->isSparse()) nwblock = qd->getBlockSize();
-        qd->decref();
+        if (qd->isLibraryBacked()) {
+          if (!qd->isSparse()) nwblock = qd->getBlockSize();
+          qd->decref();
+        } else {
+          user_qd = qd;  // the problem's own solver: bound below, released with the problem
+        }
       }
       po_problem_callbacks cb;
       cb.user = this;
@@ -574,6 +605,14 @@ class ParOptProblem : public ParOptBase {
           po_problem_set_var_bound_options(hprob, useLowerBounds(), useUpperBounds());
         if (linear_constraints) po_problem_set_linear_constraints(hprob, 1);
         if (deferred_reductions) po_problem_set_deferred_reductions(hprob, 1);
+        if (user_qd) {
+          po_quasidef_callbacks qcb;
+          qcb.user = user_qd;
+          qcb.factor = &ParOptProblem::tramp_qfactor;
+          qcb.apply = &ParOptProblem::tramp_qapply;
+          qcb.factor_info = &ParOptProblem::tramp_qinfo;
+          if (po_problem_set_quasidef_callbacks(hprob, &qcb) != 0) fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+        }
       }
     }
     return hprob;
@@ -586,6 +625,7 @@ class ParOptProblem : public ParOptBase {
   int nwblock, linear_constraints;
   int deferred_reductions = 0;
   po_problem hprob;
+  ParOptQuasiDefMat *user_qd;  // createQuasiDefMat()'s result when it is not one of the library-backed classes
   // registers the sparse-constraint callbacks with the library; ParOptSparseProblem registers its CSR form
   virtual void attachSparse() {
     if (nwcon <= 0) return;
@@ -679,7 +719,38 @@ class ParOptProblem : public ParOptBase {
     static_cast<ParOptProblem *>(self)->writeOutput(iter, vx.p());
     return 0;
   }
+  // the user's ParOptQuasiDefMat (po_quasidef_callbacks)
+  static int tramp_qfactor(void *qd, po_vec x, po_vec dinv, po_vec cdiag) {
+    Arg vx(x, 0), vd(dinv, 0), vc(cdiag, 0);
+    return static_cast<ParOptQuasiDefMat *>(qd)->factor(vx.p(), vd.p(), vc.p());
+  }
+  static int tramp_qapply(void *qd, po_vec bx, po_vec bw, po_vec yx, po_vec yw) {
+    Arg vbx(bx, 0), vyx(yx, 1), vyw(yw, 1);
+    if (bw) {
+      Arg vbw(bw, 0);
+      static_cast<ParOptQuasiDefMat *>(qd)->apply(vbx.p(), vbw.p(), vyx.p(), vyw.p());
+    } else {
+      static_cast<ParOptQuasiDefMat *>(qd)->apply(vbx.p(), vyx.p(), vyw.p());
+    }
+    return 0;
+  }
+  static const char *tramp_qinfo(void *qd) { return static_cast<ParOptQuasiDefMat *>(qd)->getFactorInfo(); }
 };
+inline int ParOptQuasiDefLibraryMat::factor(ParOptVec *x, ParOptVec *Dinv, ParOptVec *Cdiag) {
+  fx = x;
+  fd = Dinv;
+  fc = Cdiag;
+  return po_quasidef_factor(prob->handle(), x->handle(), Dinv->handle(), Cdiag->handle());
+}
+inline void ParOptQuasiDefLibraryMat::apply(ParOptVec *bx, ParOptVec *yx, ParOptVec *yw) {
+  apply(bx, NULL, yx, yw);
+}
+inline void ParOptQuasiDefLibraryMat::apply(ParOptVec *bx, ParOptVec *bw, ParOptVec *yx, ParOptVec *yw) {
+  if (!fx || po_quasidef_apply(prob->handle(), fx->handle(), fd->handle(), fc->handle(), bx->handle(),
+                               bw ? bw->handle() : NULL, yx->handle(), yw->handle()) != 0)
+    fprintf(stderr, "ParOptAMD: %s\n", fx ? po_last_error() : "ParOptQuasiDefMat::apply before factor");
+}
+inline const char *ParOptQuasiDefLibraryMat::getFactorInfo() { return po_quasidef_factor_info(prob->handle()); }
 
 // ---- ParOptSparseProblem (src/ParOptProblem.h:301-395): fixed CSR pattern for the sparse Jacobian -------------
 // Overlapping rows are allowed; the quasi-definite system is solved with the device sparse Cholesky
@@ -695,11 +766,24 @@ class ParOptSparseProblem : public ParOptProblem {
     cols.assign(_cols, _cols + rowp[nwcon]);
     data.assign(cols.size() > 0 ? cols.size() : 1, 0.0);
   }
+  // (src/ParOptProblem.cpp:689-703) the HOST copy of the entries: what the last evalSparseObjConGradient wrote
   int getSparseJacobianData(const int **_rowp, const int **_cols, const ParOptScalar **_data) {
     if (_rowp) *_rowp = rowp.data();
     if (_cols) *_cols = cols.data();
     if (_data) *_data = data.data();
     return (int)cols.size();
+  }
+  // Facade extension: the same with the entries where the library keeps them, a DEVICE array of nnz doubles in the
+  // order of cols (po_problem_get_sparse_jacobian_data) -- what a quasi-definite solver with kernels of its own reads
+  int getSparseJacobianDataDevice(const int **_rowp, const int **_cols, const ParOptScalar **_device_data) {
+    double *d = NULL;
+    int64_t nnz = 0;
+    if (po_problem_get_sparse_jacobian_data(handle(), _rowp, _cols, &d, &nnz) != 0) {
+      fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+      return 0;
+    }
+    if (_device_data) *_device_data = d;
+    return (int)nnz;
   }
   virtual int evalSparseObjCon(ParOptVec *x, ParOptScalar *fobj, ParOptScalar *cons, ParOptVec *sparse_con) = 0;
   virtual int evalSparseObjConGradient(ParOptVec *x, ParOptVec *g, ParOptVec **Ac, ParOptScalar *data) = 0;
@@ -753,6 +837,8 @@ class ParOptSparseProblem : public ParOptProblem {
     return fail;
   }
 };
+
+inline ParOptQuasiDefSparseMat::ParOptQuasiDefSparseMat(ParOptSparseProblem *_prob) : ParOptQuasiDefLibraryMat(_prob) {}
 
 // ---- compact quasi-Newton -----------------------------------------------------------------------
 enum ParOptBFGSUpdateType { PAROPT_SKIP_NEGATIVE_CURVATURE, PAROPT_DAMPED_UPDATE };

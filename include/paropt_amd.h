@@ -319,6 +319,30 @@ int po_quasidef_factor(po_problem p, po_vec x, po_vec dinv, po_vec c);
 int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, po_vec bw, po_vec yx, po_vec yw);
 /* getFactorInfo (src/ParOptSparseMat.cpp:433-450): one line about the sparse factor, NULL for the block form */
 const char *po_quasidef_factor_info(po_problem p);
+/* createQuasiDefMat (src/ParOptProblem.h:72): a problem brings its own solver for the quasi-definite block
+ * [D Aw^T; Aw -C] (ParOptQuasiDefMat, src/ParOptSparseMat.h:18-62).  Attach the table to ANY problem (callback, CSR,
+ * built-in) before po_ip_create; trust-region, infeasibility and MMA subproblems carry the table of the problem they
+ * wrap.  cb == NULL: the library's own solver again.  The table is copied.  With a table attached every
+ * sparse-constraint solve of the interior point, po_quasidef_factor / _apply / _factor_info and the MatInfo line of
+ * the output file go through it; per KKT system the solver is asked for one factor, one three-argument apply per
+ * panel column (dense constraints + quasi-Newton columns) and one four-argument apply per bordered solve.  Sparse
+ * constraints are rank-local and so is every call; whether a table is attached must agree on all ranks.  The
+ * callbacks may use any reduction of the library and get its value at once: a problem with a table attached is never
+ * batched, whatever po_problem_set_deferred_reductions said. */
+typedef struct {
+  void *user;
+  /* factor :25.  dinv (n) and cdiag (w) are borrowed until the next factor call; neither may be written.  A non-zero
+   * return is counted (po_quasidef_factor then returns PO_ERR_NUMERIC), warned about once and survived: the
+   * reference ignores the value (src/ParOptInteriorPoint.cpp:1930, 5429). */
+  int (*factor)(void *user, po_vec x, po_vec dinv, po_vec cdiag);
+  /* apply :39 / :55:  [D Aw^T; Aw -C] [yx; -yw] = [bx; bw], i.e. with S = C + Aw D^-1 Aw^T
+   *   yw = S^-1 (bw - Aw D^-1 bx),  yx = D^-1 (bx + Aw^T yw).
+   * bw == NULL is the three-argument form (zero block).  bx and bw are read-only; yx never aliases bx.  A non-zero
+   * return ends optimize() with PO_ERR_USER. */
+  int (*apply)(void *user, po_vec bx, po_vec bw, po_vec yx, po_vec yw);
+  const char *(*factor_info)(void *user); /* getFactorInfo :61; may be NULL */
+} po_quasidef_callbacks;
+int po_problem_set_quasidef_callbacks(po_problem p, const po_quasidef_callbacks *cb);
 /* The one-time host analysis behind po_problem_set_sparse_jacobian_data, exposed so it can be inspected (and
  * tested) without a device: column-sorted pattern, pattern of S = Aw Aw^T, nested-dissection ordering,
  * elimination tree, pattern of L (CSR, diagonal last in each row) and the dependency level sets the device
@@ -524,6 +548,9 @@ int po_ip_debug_kkt_step_sparse(po_ip ip, po_vec *pzw, po_vec *psw, po_vec *ptw,
 /* ---- standalone hot kernels for the roofline bench ----------------------------------------- */
 /* W = P^T diag(d) P, P = [vecs], column-major nvecs x nvecs on the host (MFMA fp64). */
 int po_wgram(po_vec d, const po_vec *vecs, int nvecs, double *W);
+/* X = U^T Z for two panels of nv vectors of equal length: out[r + nv * s] = U_r . Z_s, one pass over both panels
+ * on the matrix cores (the Gram correction of a user-supplied quasi-definite solver).  Any nv >= 1. */
+int po_xgram(const po_vec *U, const po_vec *Z, int nv, double *out);
 /* The same pass with the LAST vector t pre-weighted: W[i][nvecs-1] = W[nvecs-1][i] = vecs[i] . t for i < nvecs-1
  * (the panel dots P^T t of the bordered solve that follows setUpKKTSystem ride in the Gram pass,
  * src/ParOptInteriorPoint.cpp:2139-2147); W[nvecs-1][nvecs-1] = t . t. */

@@ -450,7 +450,129 @@ class LSR1(_QuasiNewton):
         super().__init__(ctx, 1, n, subspace)
 
 
-class Problem:
+class _QuasiDefBinding:
+    """Binds a Python quasi-definite solver -- an object with factor(x, Dinv, Cdiag), apply(bx, bw, yx, yw) (bw may
+    be None) and optionally getFactorInfo() -- to a problem handle (po_problem_set_quasidef_callbacks).  Host mode:
+    numpy copies in, live host mirrors of yx / yw out.  Device mode: zero-copy tensors under the context's stream.
+    device="pvec": the library's vectors themselves as PVec wrappers (valid during the call), for a solver that is
+    written on the library's own vector operations.  A Python exception is kept in owner._pending_exc (re-raised by optimize()) and reported as a failed call."""
+
+    def __init__(self, owner, obj, device):
+        self.owner, self.obj = owner, obj
+        self.pvec = device == "pvec"
+        self.device = bool(device) and not self.pvec
+        ctx = owner.ctx
+        self._info = None
+        if self.device:
+            import torch
+
+            self._torch = torch
+            self._stream = ctx.torch_stream()
+
+        def scope():
+            if not self.device:
+                return contextlib.nullcontext()
+            s, torch = self._stream, self._torch
+            cur = torch.cuda.current_stream(s.device)
+            if cur.cuda_stream != s.cuda_stream:
+                s.wait_stream(cur)
+            return torch.cuda.stream(s)
+
+        def vec(h):
+            return PVec(ctx, handle=L.po_vec(h), owned=False)
+
+        def arg_in(h):
+            if self.pvec:
+                return vec(h)
+            return vec(h).as_tensor() if self.device else vec(h).to_numpy()
+
+        def guard(fn, failed):
+            def _g(*args):
+                if getattr(owner, "_pending_exc", None) is not None:
+                    return failed
+                try:
+                    with scope():
+                        return fn(*args)
+                except BaseException as e:  # noqa: BLE001 - re-raised by the owner's _raise_pending()
+                    if getattr(owner, "_pending_exc", None) is None:
+                        owner._pending_exc = e
+                    return failed
+            return _g
+
+        def _factor(user, x, dinv, cdiag):
+            return int(obj.factor(arg_in(x), arg_in(dinv), arg_in(cdiag)) or 0)
+
+        def _apply(user, bx, bw, yx, yw):
+            abx, abw = arg_in(bx), (arg_in(bw) if bw else None)
+            if self.pvec:
+                return int(obj.apply(abx, abw, vec(yx), vec(yw)) or 0)
+            if self.device:
+                return int(obj.apply(abx, abw, vec(yx).as_tensor(), vec(yw).as_tensor()) or 0)
+            vx, vw = vec(yx), vec(yw)
+            try:
+                return int(obj.apply(abx, abw, vx.getArray(), vw.getArray()) or 0)
+            finally:
+                vx.releaseArray(True)
+                vw.releaseArray(True)
+
+        def _info(user):
+            text = obj.getFactorInfo()
+            if text is None:
+                return None
+            self._info = C.create_string_buffer(str(text).encode())
+            return C.addressof(self._info)
+
+        cb = L.QuasiDefCallbacks()
+        self._fns = (L.QD_FACTOR_FN(guard(_factor, 1)), L.QD_APPLY_FN(guard(_apply, 1)),
+                     L.QD_INFO_FN(guard(_info, None)) if hasattr(obj, "getFactorInfo") else L.QD_INFO_FN())
+        cb.user = None
+        cb.factor, cb.apply, cb.factor_info = self._fns
+        self._cb = cb
+        check(lib.po_problem_set_quasidef_callbacks(owner.handle, C.byref(cb)))
+
+
+class _QuasiDefMixin:
+    """createQuasiDefMat (reference src/ParOptProblem.h:72) for the Python problem classes."""
+
+    _quasidef_device = False
+    _quasidef = None
+
+    def setQuasiDefMat(self, obj, device=None):
+        """Attach the problem's own quasi-definite solver (None: the library's own again): an object with
+        factor(x, Dinv, Cdiag) -> fail, apply(bx, bw, yx, yw) -> fail writing yx / yw in place (bw is None for the
+        three-argument form) and optionally getFactorInfo() -> str.  device=True hands it zero-copy torch tensors
+        under the context's stream instead of numpy arrays, device="pvec" the library's vectors as PVec wrappers.
+        Before the solver is created."""
+        if obj is None:
+            check(lib.po_problem_set_quasidef_callbacks(self.handle, None))
+            self._quasidef = None
+            return self
+        self._quasidef = _QuasiDefBinding(self, obj, self._quasidef_device if device is None else device)
+        return self
+
+    def getSparseJacobianData(self, device=False):
+        """(rowp, cols, data) of the CSR sparse Jacobian (ParOptSparseProblem::getSparseJacobianData): the host
+        pattern and the current entries in the order of cols -- a numpy copy, or with device=True a zero-copy
+        tensor of the library's device array."""
+        rowp, cols = L.c_int_p(), L.c_int_p()
+        data, nnz = C.c_void_p(), C.c_int64()
+        check(lib.po_problem_get_sparse_jacobian_data(self.handle, C.byref(rowp), C.byref(cols), C.byref(data),
+                                                      C.byref(nnz)))
+        w, nz = int(self.nwcon), int(nnz.value)
+        rp = np.array(np.ctypeslib.as_array(rowp, shape=(w + 1,)), copy=True)
+        cl = np.array(np.ctypeslib.as_array(cols, shape=(nz,)), copy=True) if nz else np.zeros(0, dtype=np.intc)
+        if device:
+            dev = C.c_int()
+            check(lib.po_ctx_device(self.ctx.handle, C.byref(dev)))
+            return rp, cl, _borrowed_tensor(data.value, nz, dev.value)
+        vals = np.zeros(max(nz, 1))
+        if nz:
+            check(lib.po_ctx_memcpy(self.ctx.handle, vals.ctypes.data, data.value, 8 * nz, 0))
+        return rp, cl, vals[:nz]
+
+
+class Problem(_QuasiDefMixin):
+    _quasidef_asked = False
     """Base class for user problems implemented in Python (host arrays through getArray).
 
     Mirrors paropt.ParOpt.Problem: override getVarsAndBounds(x, lb, ub), evalObjCon(x) ->
@@ -618,6 +740,13 @@ class Problem:
             check(lib.po_problem_set_sparse_callbacks(self._h, self.nwcon, int(nwinequality), C.byref(scb)))
             if int(nwblock) > 1:  # addSparseInnerProduct then fills packed upper nwblock x nwblock blocks
                 check(lib.po_problem_set_sparse_block_size(self._h, int(nwblock)))
+        self._quasidef_asked = False
+
+    def createQuasiDefMat(self):
+        """Override to bring the problem's own quasi-definite solver (see setQuasiDefMat); None: the library's.
+        Asked for once, when a solver first takes the problem's handle (as the reference asks when the optimizer is
+        created), so the subclass's own __init__ has run by then."""
+        return None
 
     def __del__(self):
         try:
@@ -674,6 +803,11 @@ class Problem:
 
     @property
     def handle(self):
+        if not self._quasidef_asked:
+            self._quasidef_asked = True
+            qd = self.createQuasiDefMat()
+            if qd is not None and self._quasidef is None:  # (an explicit setQuasiDefMat() made earlier stands)
+                self.setQuasiDefMat(qd)
         return self._h
 
 
@@ -710,6 +844,8 @@ class TorchProblem(Problem):
         self._data_view = None
         super().__init__(ctx, nvars, ncon, ninequality, nwcon=nwcon, nwinequality=nwinequality, use_lower=use_lower,
                          use_upper=use_upper, rowp=rowp, cols=cols, nwblock=nwblock)
+
+    _quasidef_device = True  # createQuasiDefMat's solver works on device tensors too
 
     def setDeferredReductions(self, flag=True):
         check(lib.po_problem_set_deferred_reductions(self._h, int(bool(flag))))
@@ -767,10 +903,17 @@ class TorchProblem(Problem):
         pass
 
 
-class SeparableProblem:
+class SeparableProblem(_QuasiDefMixin):
     """Built-in device-resident workloads: 'quadratic', 'convex', 'rosenbrock'."""
 
     KINDS = {"quadratic": 0, "convex": 1, "rosenbrock": 2}
+    _pending_exc = None
+
+    def _raise_pending(self):
+        """Re-raise the first exception an attached quasi-definite solver threw during the last solver call."""
+        e, self._pending_exc = self._pending_exc, None
+        if e is not None:
+            raise e
 
     def __init__(self, ctx, kind, n, c=2, seed=0, eig_min=1.0, eig_max=100.0):
         self.ctx = ctx
@@ -1845,6 +1988,19 @@ def wgram(d, vecs, rhs_last=False):
     fn = lib.po_wgram_with_rhs if rhs_last else lib.po_wgram
     check(fn(d.handle, arr, nv, W.ctypes.data_as(L.c_double_p)))
     return W.T  # column-major symmetric
+
+
+def xgram(U, Z):
+    """X = U^T Z for two panels of equally many vectors of equal length: X[r, s] = U[r] . Z[s], one pass over both
+    panels (po_xgram)."""
+    nv = len(U)
+    if len(Z) != nv:
+        raise ValueError("xgram: the two panels must have the same number of vectors")
+    X = np.zeros((nv, nv))
+    ua = (L.po_vec * max(nv, 1))(*[v.handle for v in U])
+    za = (L.po_vec * max(nv, 1))(*[v.handle for v in Z])
+    check(lib.po_xgram(ua, za, nv, X.ctypes.data_as(L.c_double_p)))
+    return X.T  # out[r + nv * s] is column-major
 
 
 def group_panel(d, vecs, nwcon, nw, skip, alpha, U):

@@ -683,7 +683,10 @@ int po_quasidef_factor(po_problem p, po_vec x, po_vec dinv, po_vec c) {
   }
   const long before = p->p->sparseFactorBreakdowns();
   PO_TRY(p->p->sparseFactor(x, dinv, c));
-  return p->p->sparseFactorBreakdowns() != before ? PO_ERR_NUMERIC : PO_OK;  // the text is already set
+  if (p->p->sparseFactorBreakdowns() == before) return PO_OK;
+  // (the library's own factorizations have set the text; a user solver's failure is announced once only)
+  if (p->p->qd_set) po::set_error("the problem's quasi-definite solver reported a failed factorization (%d)", p->p->qd_last_fail);
+  return PO_ERR_NUMERIC;
 }
 int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, po_vec bw, po_vec yx,
                       po_vec yw) {
@@ -751,6 +754,22 @@ int po_csr_symbolic_arrays(po_csr_symbolic h, const int **perm, const int **pare
 }
 int po_csr_symbolic_destroy(po_csr_symbolic h) {
   delete h;
+  return PO_OK;
+}
+int po_problem_set_quasidef_callbacks(po_problem p, const po_quasidef_callbacks *cb) {
+  PO_CHECK_PTR(p);
+  PO_CHECK_PTR(p->p);
+  if (!cb) {
+    p->p->qd = po_quasidef_callbacks();
+    p->p->qd_set = false;
+    return PO_OK;
+  }
+  if (!cb->factor || !cb->apply) {
+    po::set_error("po_problem_set_quasidef_callbacks: factor and apply are mandatory");
+    return PO_ERR_ARG;
+  }
+  p->p->qd = *cb;
+  p->p->qd_set = true;
   return PO_OK;
 }
 const char *po_quasidef_factor_info(po_problem p) { return p && p->p ? p->p->sparseFactorInfo() : nullptr; }
@@ -1191,6 +1210,20 @@ int po_wgram(po_vec d, const po_vec *vecs, int nvecs, double *W) {
   std::vector<const double *> p;
   PO_TRY(gather_ptrs(d, vecs, nvecs, p));
   return k_wgram(d->ctx, d->d, p.data(), nvecs, d->n, W);
+}
+int po_xgram(const po_vec *U, const po_vec *Z, int nv, double *out) {
+  PO_CHECK_PTR(U);
+  PO_CHECK_PTR(Z);
+  PO_CHECK_PTR(out);
+  if (nv < 1) {
+    po::set_error("po_xgram: needs at least one vector per panel");
+    return PO_ERR_ARG;
+  }
+  PO_CHECK_PTR(U[0]);
+  std::vector<const double *> pu, pz;
+  PO_TRY(gather_ptrs(U[0], U, nv, pu));
+  PO_TRY(gather_ptrs(U[0], Z, nv, pz));
+  return k_xgram(U[0]->ctx, pu.data(), pz.data(), nv, U[0]->n, out);
 }
 int po_wgram_with_rhs(po_vec d, const po_vec *vecs, int nvecs, double *W) {
   PO_CHECK_PTR(d);

@@ -359,6 +359,11 @@ int k_wgram(Ctx *c, const double *d, const double *const *V, int nv, int64_t n, 
             double b0 = 0.0, int preweighted_last = 0, bool may_defer = false,
             const GramGroups *groups = nullptr, bool *groups_done = nullptr);
 int wgram_debug_stamps(double out[8]);  // tuning aid: PAROPT_AMD_WGRAM_ABLATE=16
+// X = U^T Z for two panels of m columns of w rows: out[r + m s] = U_r . Z_s (not symmetric in its inputs), one pass
+// over both panels on the matrix cores (wgram.hip).  Any m >= 1, w >= 0; panels wider than one launch (48 columns
+// per side) go by column blocks.  may_defer: as for k_wgram.
+int k_xgram(Ctx *c, const double *const *U, const double *const *Z, int m, int64_t w, double *out,
+            bool may_defer = false);
 int k_wgram_launch(Ctx *c, const double *d, const double *const *V, int nv, int64_t n,
                    int *nblocks, int *nslots, const double *const *S = nullptr,
                    double *const *Zout = nullptr, int kpend = 0, double b0 = 0.0,

@@ -107,6 +107,7 @@ InteriorPoint::~InteriorPoint() {
     vec_decref(wscalev[i]);
   }
   for (Vec *v : Uw) vec_decref(v);
+  for (Vec *v : Yw) vec_decref(v);
   for (Vec *v : gmresW) vec_decref(v);
   vec_decref(hdiag);
   if (qn_owned) delete qn;

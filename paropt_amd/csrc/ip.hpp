@@ -273,7 +273,12 @@ class InteriorPoint {
   int sparseConAtIterate(const double **cw);
   Vec *d1v;                 // n-sized: raw d1, then v = d1 + P alpha
   std::vector<Vec *> Uw;    // U_j = Aw (Dinv o P_j)
-  bool panel_plain = false;  // Uw is the unscaled panel image (scalar block form)
+  bool panel_plain = false;  // Uw is the unscaled panel image (scalar block form, user solver)
+  // the problem brings its own quasi-definite solver (Problem::sparseUserSolver): Yw_j = -S^-1 U_j beside Uw, the
+  // panel sparseCorrection combines
+  std::vector<Vec *> Yw;
+  bool panel_solved = false;
+  std::vector<const double *> correctionPanel(int m) const;  // Yw (panel_solved) or Uw, m columns
   double w_sums[7], w_maxs[5];  // reductions of the last w residual (k_w_res layout)
   double res_out[13] = {0}, wres_out[12] = {0};  // landing area of the residual reductions (see after_reduce)
   // Monotone barrier strategy with the infinity norm (round 4): the residual pass also takes max|rzl|, max|rzu| for the

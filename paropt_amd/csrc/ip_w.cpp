@@ -16,6 +16,8 @@
 
 namespace po {
 
+int comm_allreduce_host(Ctx *c, double *values, int count, int op);  // context.cpp
+
 WVars InteriorPoint::wv() const { return WVars{wvar[0]->d, wvar[1]->d, wvar[2]->d, wvar[3]->d, wvar[4]->d}; }
 WVars InteriorPoint::wr() const {
   return WVars{wresv[0]->d, wresv[1]->d, wresv[2]->d, wresv[3]->d, wresv[4]->d};
@@ -39,6 +41,16 @@ int InteriorPoint::allocateW() {
   nw_global = total;
   has_w = total > 0.0;
   if (!has_w) return PO_OK;
+  // ... and so must be whether the problem brings its own quasi-definite solver (the two Gram corrections issue
+  // different reductions): checked once, collectively
+  if (ctx->size > 1) {
+    double mm[2] = {prob->sparseUserSolver() ? 1.0 : 0.0, prob->sparseUserSolver() ? -1.0 : 0.0};
+    PO_TRY(comm_allreduce_host(ctx, mm, 2, 1));  // {min of the flag, -max of the flag}
+    if (mm[0] != -mm[1]) {
+      set_error("a quasi-definite solver (po_problem_set_quasidef_callbacks) is attached on some ranks only");
+      return PO_ERR_ARG;
+    }
+  }
   Vec **all[] = {&gsw, &gtw, &Cw, &wd2, &wyw, &wtmp, &wtmp2, &cwx};
   for (Vec **v : all) {
     *v = vec_new(ctx, nw);
@@ -102,6 +114,11 @@ int InteriorPoint::panelImageVectors(int m, std::vector<double *> &U) {
   for (int j = 0; j < m; j++) U[j] = Uw[j]->d;
   return PO_OK;
 }
+std::vector<const double *> InteriorPoint::correctionPanel(int m) const {
+  std::vector<const double *> C(m);
+  for (int j = 0; j < m; j++) C[j] = (panel_solved ? Yw[j] : Uw[j])->d;
+  return C;
+}
 // panel_done: the Gram pass over P has already written U (Problem::sparseGramGroups)
 int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, int m, Vec *work, bool may_defer,
                                         bool panel_done) {
@@ -110,6 +127,36 @@ int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, in
   PO_TRY(panelImageVectors(m, U));
   std::vector<const double *> Uc(U.begin(), U.end());
   if (!panel_done) PO_TRY(prob->sparseJacobianPanel(x, Dinv, P.data(), m, U.data(), work ? work : tvec));
+  panel_solved = prob->sparseUserSolver();
+  if (panel_solved) {
+    // The user exposes no factor, so there is no half solve: Yw_j = -S^-1 U_j from one three-argument apply per panel
+    // column (the reference makes c for G, :1937, and two inside each of the k diagonal solves, :2398, 2427), and the
+    // correction is the cross product W += U^T Yw of two different w-sized panels, symmetric up to rounding: both
+    // halves are averaged.  Uw keeps U itself (panel_plain), Yw is what sparseCorrection combines.
+    while ((int)Yw.size() < m) {
+      Vec *y = vec_new(ctx, nw);
+      if (!y) return PO_ERR_HIP;
+      Yw.push_back(y);
+    }
+    std::vector<double *> Y(m);
+    for (int j = 0; j < m; j++) Y[j] = Yw[j]->d;
+    PO_TRY(prob->sparseSolvedPanel(P.data(), m, Y.data(), work ? work : tvec));
+    std::vector<const double *> Yc(Y.begin(), Y.end());
+    panel_plain = true;
+    if (kkt.W.size() != (size_t)m * m) {  // (the caller sized W for this panel: a Schur-complement term is never dropped)
+      set_error("internal: the Gram matrix holds %zu entries for a panel of %d columns", kkt.W.size(), m);
+      return PO_ERR_ARG;
+    }
+    W2_buf.assign((size_t)m * m, 0.0);
+    PO_TRY(k_xgram(ctx, Uc.data(), Yc.data(), m, nw, W2_buf.data(), may_defer));
+    after_reduce(ctx, [this, m] {
+      for (int j = 0; j < m; j++)
+        for (int i = 0; i < m; i++)
+          kkt.W[i + (size_t)m * j] += 0.5 * (W2_buf[i + (size_t)m * j] + W2_buf[j + (size_t)m * i]);
+    });
+    scratch_flags.panel_valid = true;
+    return PO_OK;
+  }
   // block form: U^T Cw U.  CSR form: U <- L^-1 U with S = L L^T, then U^T U
   const double *weights = Cw->d;
   PO_TRY(prob->sparseHalfSolve(U.data(), m, Cw, &weights));
@@ -191,8 +238,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
                     (int)Uw.size() >= m && scratch_flags.panel_valid && panel_plain && !cl &&
                     !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
   if (fuse) {
-    std::vector<const double *> Uc(m);
-    for (int j = 0; j < m; j++) Uc[j] = Uw[j]->d;
+    std::vector<const double *> Uc = correctionPanel(m);
     PO_TRY(prob->sparseCorrection(Uc.data(), m, alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
     // the two extra columns Aw^T wtmp2 (coefficient 1 in the step's row sum) and Aw^T pzw (1 in the residual's): n-sized
     // vectors from Problem::setSparseJacobianTranspose, or -- structured problems -- described and formed by the pass
@@ -243,8 +289,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
     mins_x[0] = so[np1];  // out = {dots[np1], max_x, max_z}
     mins_x[1] = so[np1 + 1];
   } else if (m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid) {
-    std::vector<const double *> Uc(m);
-    for (int j = 0; j < m; j++) Uc[j] = Uw[j]->d;
+    std::vector<const double *> Uc = correctionPanel(m);
     PO_TRY(prob->sparseCorrection(Uc.data(), m, alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
     // the extra column Aw^T wtmp2 (coefficient 1): stored, or (structured problems, refinement of a px-only first
     // step) described and formed by the pass itself

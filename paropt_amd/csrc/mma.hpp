@@ -61,6 +61,10 @@ class MMA : public Problem {
   int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
     return prob->sparseHalfSolve(U, nv, cw, weights);
   }
+  bool sparseUserSolver() override { return prob->sparseUserSolver(); }
+  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
+    return prob->sparseSolvedPanel(P, nv, Yw, work);
+  }
   const char *sparseFactorInfo() override { return prob->sparseFactorInfo(); }
   long sparseFactorBreakdowns() override { return prob->sparseFactorBreakdowns(); }
   int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) override {

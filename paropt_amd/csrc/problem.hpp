@@ -98,8 +98,25 @@ class Problem {
                                Vec *acc = nullptr);
   // one line for the output file, null when there is nothing to say (getFactorInfo, :61)
   virtual const char *sparseFactorInfo();
-  // number of factorizations so far that met a non-positive pivot (CSR form; 0 otherwise)
-  virtual long sparseFactorBreakdowns() { return csr ? csr->breakdowns : blk_breakdowns; }
+  // number of factorizations so far that met a non-positive pivot (CSR form; 0 otherwise), or that the user's
+  // factor reported as failed
+  virtual long sparseFactorBreakdowns() { return qd_set ? qd_breakdowns : (csr ? csr->breakdowns : blk_breakdowns); }
+  // createQuasiDefMat (src/ParOptProblem.h:72): the problem brings its own quasi-definite solver
+  // (po_problem_set_quasidef_callbacks).  sparseFactor then forms nothing and calls the user's factor(x, d, Cdiag)
+  // with cw = Cdiag left alone, sparseApplyK0 is the user's apply and nothing else, the fused group path is off
+  // (sparseGramGroups / sparseTransposeColumn return false), and the Gram correction cannot be a half solve -- the
+  // user exposes no factor -- so it takes the SOLVED panel below.  Subproblems forward both hooks to the problem they
+  // wrap, which is how they carry its table.
+  virtual bool sparseUserSolver() { return qd_set; }
+  // Yw_j = -S^-1 Aw (d o P_j), j < nv: one three-argument apply(P_j -> work, Yw_j) of the user's solver per column
+  // (P_j n-sized, Yw_j w-sized, `work` n-sized scratch that no P_j aliases).  With U from sparseJacobianPanel the Gram
+  // correction is then the CROSS product W += U^T Yw (k_xgram), and sparseCorrection on the panel Yw is the linear
+  // combination Yw alpha = -S^-1 (U alpha): no further user call.
+  virtual int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work);
+  po_quasidef_callbacks qd = {};
+  bool qd_set = false;
+  long qd_breakdowns = 0;  // factor calls that returned non-zero (qd_last_fail: the last such value)
+  int qd_last_fail = 0;
   long blk_breakdowns = 0;   // block form with nwblock > 1: factorizations that replaced a non-positive pivot
   int64_t blk_nwcon = 0;     // nwcon the packed-block buffers were sized for
   // fixed CSR pattern of the sparse Jacobian (ParOptSparseProblem::setSparseJacobianData, .cpp:632-677);
@@ -166,7 +183,9 @@ class CallbackProblem : public Problem {
   // reductions (po_vec_dot/mdot/..., po_ctx_reduce_device) and post-process them in po_ctx_after_reduce hooks, so
   // the solver may let them share a collective + host sync with its own (reductionsBatchable, above)
   int deferred_reductions = 0;
-  bool reductionsBatchable() override { return deferred_reductions != 0; }
+  // (... and not with a quasi-definite solver of the problem's own attached: its factor / apply are user code that the
+  // promise does not cover, and they run where the solver would otherwise have a batch open)
+  bool reductionsBatchable() override { return deferred_reductions != 0 && !qd_set; }
   po_problem_callbacks cb;
   SparseCallbacks sparse;
   // CSR form (CyParOptSparseProblem, src/CyParOptProblem.h:177-262): the two evaluation callbacks also fill
@@ -187,7 +206,8 @@ class SeparableProblem : public Problem {
   int getVarsAndBounds(Vec *x, Vec *lb, Vec *ub) override;
   int evalObjCon(Vec *x, double *fobj, double *cons) override;
   int evalObjConGradient(Vec *x, Vec *g, Vec **Ac) override;
-  bool reductionsBatchable() override { return true; }
+  // (a user-supplied quasi-definite solver is user code: its reductions must return their values at once)
+  bool reductionsBatchable() override { return !qd_set; }
   double rosen_out[3] = {0, 0, 0};  // landing area of the Rosenbrock reductions (BatchScope::end_then)
   // weighting constraints cw_i = 1 - sum_{k<nw} x[nwstart + i (nw + nwskip) + k] on GLOBAL indices;
   // groups must not straddle rank boundaries (checked)

@@ -103,7 +103,27 @@ Problem::~Problem() {
   vec_decref(wones);
   if (blk_flag) (void)hipFree(blk_flag);
 }
+// A real po_vec handle that borrows raw device storage for the length of a user callback: host-side callbacks may ask
+// it for a pinned mirror (po_vec_get_array), which is released here -- the handle never reaches vec_decref
+struct BorrowedVec : po_vec_s {
+  BorrowedVec(Ctx *c, int64_t n_, const double *d_) {
+    ctx = c;
+    n = n_;
+    d = const_cast<double *>(d_);
+    ref = 1;
+    h = nullptr;
+  }
+  ~BorrowedVec() {
+    if (h) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)hipHostFree(h);
+      mirror_freed();
+    }
+  }
+};
+
 const char *Problem::sparseFactorInfo() {
+  if (qd_set) return qd.factor_info ? qd.factor_info(qd.user) : nullptr;
   if (csr && !grouped) return csr->factorInfo();
   factor_info = "nblock: " + std::to_string(nwblock);  // ParOptQuasiDefBlockMat::getFactorInfo (:218-221)
   return factor_info.c_str();
@@ -163,7 +183,7 @@ int Problem::setSparseJacobian(double alpha, Vec *x, Vec *px, Vec *out) {
 }
 int Problem::sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw) {
   // grouped with entries +-1: Cdiag from the slack blocks, the group sums of d and the reciprocal in ONE launch
-  if (grouped && nwblock == 1 && group_alpha * group_alpha == 1.0) return k_group_factor(ctx, gmap, v, d->d, cw->d);
+  if (!qd_set && grouped && nwblock == 1 && group_alpha * group_alpha == 1.0) return k_group_factor(ctx, gmap, v, d->d, cw->d);
   PO_TRY(k_w_cdiag(ctx, v, nwcon, cw->d));
   return sparseFactor(x, d, cw);
 }
@@ -173,6 +193,15 @@ int Problem::addSparseInnerProduct(double alpha, Vec *, Vec *cvec, Vec *A) {
   return csr->innerProduct(alpha, cvec->d, A->d) != PO_OK;
 }
 int Problem::sparseFactor(Vec *x, Vec *d, Vec *cw) {
+  if (qd_set) {  // the user's factor(x, Dinv, Cdiag); cw stays Cdiag
+    const int fail = qd.factor(qd.user, static_cast<po_vec>(x), static_cast<po_vec>(d), static_cast<po_vec>(cw));
+    if (fail != 0) {  // the reference ignores the value (src/ParOptInteriorPoint.cpp:1930, 5429): warn once, count
+      if (qd_breakdowns == 0) set_error("the problem's quasi-definite solver reported a failed factorization (%d)", fail);
+      qd_breakdowns++;
+      qd_last_fail = fail;
+    }
+    return PO_OK;
+  }
   // grouped: Cw = 1 / (Cdiag + alpha^2 (sum of d over the group)): the group sum and the reciprocal in one launch
   if (grouped && nwblock == 1) return k_group_sum(ctx, gmap, cw->d, 1, 0.0, group_alpha * group_alpha, d->d, 1);
   if (csr) return csr->factor(d->d, cw->d);
@@ -199,7 +228,26 @@ int Problem::sparseFactor(Vec *x, Vec *d, Vec *cw) {
   if (addSparseInnerProduct(1.0, x, d, cw) != 0) return PO_ERR_USER;
   return k_recip(ctx, cw->d, nwcon);
 }
+int Problem::sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) {
+  if (!qd_set) {
+    set_error("internal: the solved panel belongs to a problem with its own quasi-definite solver");
+    return PO_ERR_ARG;
+  }
+  for (int j = 0; j < nv; j++) {
+    BorrowedVec bx(ctx, nlocal, P[j]), yw(ctx, nwcon, Yw[j]);
+    const int fail = qd.apply(qd.user, &bx, nullptr, static_cast<po_vec>(work), &yw);
+    if (fail != 0) {
+      set_error("the problem's quasi-definite solver failed in apply (%d)", fail);
+      return PO_ERR_USER;
+    }
+  }
+  return PO_OK;
+}
 int Problem::sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) {
+  if (qd_set) {
+    set_error("internal: a problem with its own quasi-definite solver has no half solve");
+    return PO_ERR_ARG;
+  }
   if (csr && !grouped) {
     *weights = csr->unitWeights();
     return csr->halfSolve(U, nv);
@@ -213,6 +261,11 @@ int Problem::sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **w
 }
 
 int Problem::sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) {
+  if (qd_set) {  // U is the solved panel Yw = -S^-1 U: out = Yw alpha
+    PO_TRY(k_panel_axpy(ctx, out->d, 0.0, nullptr, 0.0, alpha, U, nv, nwcon));
+    if (acc) PO_TRY(k_axpy(ctx, acc->d, 1.0, out->d, nwcon));
+    return PO_OK;
+  }
   if ((!csr || grouped) && nwblock == 1 && nv <= kMaxPanel) {
     // scalar block form: sum, scale by -cw and the caller's accumulation in ONE w-sized launch (round 4; the same
     // operations in the same order as the three launches below)
@@ -237,7 +290,7 @@ int Problem::sparseCorrection(const double *const *U, int nv, const double *alph
 int Problem::sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
                                  Vec *work) {
   if (grouped) return k_group_panel(ctx, gmap, P, nv, d->d, group_alpha, U);
-  if (csr) return csr->panelPermuted(d->d, P, nv, U);
+  if (csr && !qd_set) return csr->panelPermuted(d->d, P, nv, U);
   for (int j = 0; j < nv; j++) {
     PO_TRY(k_mul(ctx, work->d, 1.0, d->d, P[j], nlocal));
     PO_TRY(k_fill(ctx, U[j], nwcon, 0.0));
@@ -334,7 +387,7 @@ int Problem::checkGradients(double dh, Vec *x, bool check_hvec, Vec *xt, Vec *px
 }
 
 bool Problem::sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *col) {
-  if (!grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
+  if (qd_set || !grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
   col->w = pzw->d;
   col->scale = alpha * group_alpha;  // the value k_group_scatter_set(..., alpha * group_alpha, ...) stores
   col->period = (unsigned)(gmap.nw + gmap.skip);
@@ -343,7 +396,7 @@ bool Problem::sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *co
   return true;
 }
 bool Problem::sparseGramGroups(Vec *x, GramGroups *g) {
-  if (!grouped || nwblock > 1 || nwcon <= 0) return false;
+  if (qd_set || !grouped || nwblock > 1 || nwcon <= 0) return false;
   g->nwcon = gmap.nwcon;
   g->start = gmap.start;
   g->nw = gmap.nw;
@@ -354,6 +407,16 @@ bool Problem::sparseGramGroups(Vec *x, GramGroups *g) {
 
 int Problem::sparseApplyK0(Vec *x, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
                            Vec *wwork) {
+  if (qd_set) {  // the user's apply and nothing else
+    BorrowedVec vbx(ctx, nlocal, bx), vbw(ctx, nwcon, bw);
+    const int fail = qd.apply(qd.user, &vbx, bw ? static_cast<po_vec>(&vbw) : nullptr, static_cast<po_vec>(yx),
+                              static_cast<po_vec>(yw));
+    if (fail != 0) {
+      set_error("the problem's quasi-definite solver failed in apply (%d)", fail);
+      return PO_ERR_USER;
+    }
+    return PO_OK;
+  }
   if (grouped && nwblock == 1) {
     // u = Aw (d o bx) in one tiled pass, yw = cw (bw - u), yx = d (bx + alpha yw[group]); one launch where the map tiles
     bool done = false;

@@ -106,6 +106,10 @@ class TrustRegionSubproblem : public Problem {
   int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
     return prob->sparseHalfSolve(U, nv, cw, weights);
   }
+  bool sparseUserSolver() override { return prob->sparseUserSolver(); }
+  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
+    return prob->sparseSolvedPanel(P, nv, Yw, work);
+  }
   const char *sparseFactorInfo() override { return prob->sparseFactorInfo(); }
   long sparseFactorBreakdowns() override { return prob->sparseFactorBreakdowns(); }
   int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) override {
@@ -274,6 +278,10 @@ class InfeasSubproblem : public Problem {  // :468-650
   int setSparseJacobian(double a, Vec *x, Vec *px, Vec *out) override { return sub->setSparseJacobian(a, x, px, out); }
   int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
     return sub->sparseHalfSolve(U, nv, cw, weights);
+  }
+  bool sparseUserSolver() override { return sub->sparseUserSolver(); }
+  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
+    return sub->sparseSolvedPanel(P, nv, Yw, work);
   }
   const char *sparseFactorInfo() override { return sub->sparseFactorInfo(); }
   long sparseFactorBreakdowns() override { return sub->sparseFactorBreakdowns(); }

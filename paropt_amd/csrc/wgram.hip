@@ -1183,4 +1183,250 @@ static int wgram_one_launch(Ctx *c, const double *d, const double *const *V, int
   return PO_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Two-panel Gram  X = U^T Z  (X[r][s] = U_r . Z_s, NOT symmetric in its inputs): the Gram correction of a problem
+// that brings its own quasi-definite solver, W += U^T Yw with U = Aw (Dinv o P) and Yw = -S^-1 U column by column
+// from the user's apply (ip_w.cpp sparseGramCorrection).  One pass over both panels: 2 m streams of w doubles, where
+// m mdot calls read m (m + 1) and the symmetric kernel on the stacked panel [U | Z] issues about four times the matrix
+// instructions and leaves the single launch at 2 m > 80.
+//
+// Single role, 64-row tiles (row stride 72 doubles == 8 mod 32): the staged set is two panels wide, 8 NG columns =
+// 4.5 KB per column group, 55 KB at 48 + 48 columns, so two workgroups (more for narrower panels) share a CU and one
+// multiplies while the other waits for its loads; the loads of a workgroup's next tile are in registers before it
+// multiplies the current one.  A wavefront loads TWO columns per instruction (lanes 0-31 the 32 row pairs of column
+// cc, lanes 32-63 those of column cc + 4; cc counts over [U | Z] padded to whole groups).  v_mfma_f64_4x4x4_4b with A
+// from the U tile and B from the Z tile (operand layout: head of this file); all NG x NG block pairs, dealt to the
+// four wavefronts by Z column group J (J = wave, wave + 4, ...): no cross-wave reduction, the four row-chunk partials
+// of a block are summed with two lane shuffles at the end.  One partial per workgroup and slot, slot = (I NG + J) 16 +
+// 4 i + j for X[4 I + i][4 J + j]; the final stage is reduce_finish, so the result is bit-reproducible for a fixed grid.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int kXgramMaxVecs = 48;  // columns per side of one launch
+
+template <int NG, int W>
+struct XgramOwn {
+  static constexpr int NJ = W < NG ? (NG - W + 3) / 4 : 0;  // Z column groups of wavefront W (most for W = 0)
+  static constexpr int NQ = NJ * NG > 0 ? NJ * NG : 1;
+};
+
+template <int NG, int NJ>
+__device__ __forceinline__ void xgram_fetch(const double *__restrict__ ub, const double *__restrict__ zb, int off,
+                                            double (&a)[NG], double (&b)[NJ]) {
+#pragma unroll
+  for (int g = 0; g < NG; g++) a[g] = ub[(4 * g) * kG64Ld + off];
+#pragma unroll
+  for (int jj = 0; jj < NJ; jj++) b[jj] = zb[(16 * jj) * kG64Ld + off];
+}
+template <int NG, int NJ>
+__device__ __forceinline__ void xgram_step(const double (&a)[NG], const double (&b)[NJ],
+                                           double (&acc)[XgramOwn<NG, 0>::NQ]) {
+  int q = 0;
+#pragma unroll
+  for (int jj = 0; jj < NJ; jj++) {
+#pragma unroll
+    for (int I = 0; I < NG; I++) {
+      acc[q] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[I], b[jj], acc[q], 0, 0, 0);
+      q++;
+    }
+  }
+}
+
+template <int NG, int W>
+__device__ __forceinline__ void xgram_tile(const double *__restrict__ ut, const double *__restrict__ zt, int lane,
+                                           double (&acc)[XgramOwn<NG, 0>::NQ]) {
+  constexpr int NJ = XgramOwn<NG, W>::NJ;
+  if constexpr (NJ > 0) {
+    const int ci = lane & 3;
+    const int rowoff = ((lane >> 2) & 3) + 4 * (lane >> 4);  // row within the 16-row step: b + 4 k
+    const double *ub = ut + ci * kG64Ld + rowoff;
+    const double *zb = zt + (4 * W + ci) * kG64Ld + rowoff;
+    // (odd steps through an opaque offset: merged into ds_read2_b64 with the even step's fetch, operands 16 doubles
+    // apart are a two-way bank conflict -- see gram_tile_rows)
+    int off1 = 16;
+    asm volatile("" : "+v"(off1));
+    // (one operand set: with the next step's operands requested ahead, as gram_tile does, the wide instantiations
+    // spill -- the other workgroups of the CU cover the LDS latency here)
+    double a[NG], b[NJ];
+#pragma unroll 1
+    for (int s = 0; s < kG64Tile / 16; s += 2) {
+      xgram_fetch<NG, NJ>(ub, zb, 16 * s, a, b);
+      xgram_step<NG, NJ>(a, b, acc);
+      xgram_fetch<NG, NJ>(ub, zb, 16 * s + off1, a, b);
+      xgram_step<NG, NJ>(a, b, acc);
+    }
+  }
+}
+
+template <int NG, int W>
+__device__ __forceinline__ void xgram_store(const double (&acc)[XgramOwn<NG, 0>::NQ], int lane,
+                                            double *__restrict__ partials) {
+  constexpr int NJ = XgramOwn<NG, W>::NJ;
+  int q = 0;
+#pragma unroll
+  for (int jj = 0; jj < NJ; jj++) {
+#pragma unroll
+    for (int I = 0; I < NG; I++) {
+      const int p = I * NG + (W + 4 * jj);
+      double v = acc[q];
+      v += __shfl_xor(v, 4, 64);  // the four row chunks b of the block
+      v += __shfl_xor(v, 8, 64);
+      if (((lane >> 2) & 3) == 0) {
+        const int slot = p * 16 + (lane >> 4) * 4 + (lane & 3);  // element (i, j) of block pair (I, J)
+        partials[(size_t)slot * gridDim.x + blockIdx.x] = v;
+      }
+      q++;
+    }
+  }
+}
+
+template <int NG, int OCC>
+__global__ void __launch_bounds__(kBlock, OCC)
+    xgram_kernel(PtrTable U, PtrTable Z, int nvu, int nvz, int64_t n, int64_t ntiles,
+                 double *__restrict__ partials) {
+  constexpr int M = 4 * NG;
+  extern __shared__ double lds[];  // [2 M][kG64Ld]: the U tile, then the Z tile
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, rp = lane & 31;
+  // zero the padded columns once (never written by the staging)
+  for (int idx = tid; idx < (M - nvu) * kG64Ld; idx += kBlock) lds[nvu * kG64Ld + idx] = 0.0;
+  for (int idx = tid; idx < (M - nvz) * kG64Ld; idx += kBlock) lds[(M + nvz) * kG64Ld + idx] = 0.0;
+  // load `it` of this lane: column cc = wave + 4 half + 8 it of [U | Z]; padded columns re-read the panel's last
+  // column and are not staged, so the loads carry no branch
+  const double *colp[NG];
+#pragma unroll
+  for (int it = 0; it < NG; it++) {
+    const int cc = wave + 4 * half + 8 * it;
+    const int ju = cc < nvu ? cc : nvu - 1, jz = cc < M ? 0 : (cc - M < nvz ? cc - M : nvz - 1);
+    colp[it] = cc < M ? U.p[ju] : Z.p[jz];
+  }
+  const int64_t ilast = ((n - 1) >> 1) << 1;
+  f64x2 buf[NG];
+  bool pre_in = false;
+  // (unconditional: a tile past the end re-requests the last lines and is never staged)
+#define PO_XGRAM_PREFETCH(TILE)                                                       \
+  {                                                                                   \
+    int64_t _i = (TILE) * kG64Tile + 2 * rp;                                          \
+    pre_in = (_i < n);                                                                \
+    if (!pre_in) _i = ilast;                                                          \
+    _Pragma("unroll") for (int it = 0; it < NG; it++) buf[it] = ld_nt(colp[it] + _i); \
+  }
+  // (one accumulator array for the four roles, sized for wavefront 0's share, the largest: see gram64_consume)
+  double acc[XgramOwn<NG, 0>::NQ];
+#pragma unroll
+  for (int q = 0; q < XgramOwn<NG, 0>::NQ; q++) acc[q] = 0.0;
+  PO_XGRAM_PREFETCH((int64_t)blockIdx.x);
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();  // previous tile fully consumed
+#pragma unroll
+    for (int it = 0; it < NG; it++) {
+      const int cc = wave + 4 * half + 8 * it;
+      const bool real = cc < M ? cc < nvu : cc - M < nvz;
+      f64x2 v = buf[it];
+      if (!pre_in) v = (f64x2){0.0, 0.0};
+      if (real) *reinterpret_cast<f64x2 *>(lds + cc * kG64Ld + 2 * rp) = v;
+    }
+    __syncthreads();
+    PO_XGRAM_PREFETCH(tile + gridDim.x);
+    switch (wave) {
+      case 0: xgram_tile<NG, 0>(lds, lds + M * kG64Ld, lane, acc); break;
+      case 1: xgram_tile<NG, 1>(lds, lds + M * kG64Ld, lane, acc); break;
+      case 2: xgram_tile<NG, 2>(lds, lds + M * kG64Ld, lane, acc); break;
+      default: xgram_tile<NG, 3>(lds, lds + M * kG64Ld, lane, acc); break;
+    }
+  }
+#undef PO_XGRAM_PREFETCH
+  switch (wave) {
+    case 0: xgram_store<NG, 0>(acc, lane, partials); break;
+    case 1: xgram_store<NG, 1>(acc, lane, partials); break;
+    case 2: xgram_store<NG, 2>(acc, lane, partials); break;
+    default: xgram_store<NG, 3>(acc, lane, partials); break;
+  }
+}
+
+template <int NG>
+static int xgram_launch_t(Ctx *c, const PtrTable &ut, const PtrTable &zt, int nvu, int nvz, int64_t n, int *grid_out) {
+  // workgroups per CU the registers are budgeted for (the accumulators: 2 NG ceil(NG / 4) registers per lane; every
+  // instantiation is scratch-free at this choice, tests/test_kernel_resources.py)
+  constexpr int OCC = NG <= 7 ? 4 : (NG <= 8 ? 3 : 2);
+  const size_t lds = (size_t)8 * NG * kG64Ld * sizeof(double);
+  static bool attr_set = false;
+  if (!attr_set) {
+    PO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xgram_kernel<NG, OCC>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_set = true;
+  }
+  int per_cu = (int)((160 * 1024) / lds);
+  if (per_cu > OCC) per_cu = OCC;
+  const int64_t ntiles = (n + kG64Tile - 1) / kG64Tile;
+  int64_t g = (int64_t)c->num_cu * per_cu;
+  if (g > ntiles) g = ntiles;
+  if (g < 1) g = 1;
+  PO_TRY(ensure_partials(c, (size_t)g * NG * NG * 16));
+  hipLaunchKernelGGL((xgram_kernel<NG, OCC>), dim3((int)g), dim3(kBlock), lds, c->stream, ut, zt, nvu, nvz, n, ntiles,
+                     c->d_partials);
+  c->n_launches++;
+  PO_HIP(hipGetLastError());
+  *grid_out = (int)g;
+  return PO_OK;
+}
+
+// out[r + ld * s] = U_r . Z_s for r < nvu, s < nvz (nvu, nvz <= kXgramMaxVecs, n >= 1)
+static int xgram_one_launch(Ctx *c, const double *const *U, const double *const *Z, int nvu, int nvz, int64_t n,
+                            double *out, int ld, bool may_defer) {
+  const int NG = wgram_groups(nvu > nvz ? nvu : nvz);
+  PtrTable ut, zt;
+  for (int j = 0; j < kMaxPanel; j++) {
+    ut.p[j] = j < nvu ? U[j] : nullptr;
+    zt.p[j] = j < nvz ? Z[j] : nullptr;
+  }
+  count_bytes(c, nvu + nvz, n);
+  int grid = 0;
+#define PO_XG(NGv) \
+  case NGv: PO_TRY((xgram_launch_t<NGv>(c, ut, zt, nvu, nvz, n, &grid))); break;
+  switch (NG) {
+    PO_XG(1) PO_XG(2) PO_XG(3) PO_XG(4) PO_XG(5) PO_XG(6) PO_XG(7) PO_XG(8) PO_XG(9) PO_XG(10) PO_XG(11) PO_XG(12)
+    default: set_error("xgram: %d column groups in one launch", NG); return PO_ERR_ARG;
+  }
+#undef PO_XG
+  const int nslots = NG * NG * 16;
+  const bool defer = may_defer && c->batch_depth > 0;
+  auto blocks = std::make_shared<std::vector<double>>(nslots);
+  PO_TRY(reduce_finish(c, grid, nslots, 0, 0, blocks->data(), !defer));
+  auto unpack = [blocks, NG, nvu, nvz, out, ld] {
+    for (int I = 0; I < NG; I++)
+      for (int J = 0; J < NG; J++)
+        for (int i = 0; i < 4; i++)
+          for (int j = 0; j < 4; j++) {
+            const int r = 4 * I + i, s = 4 * J + j;
+            if (r < nvu && s < nvz) out[r + (size_t)ld * s] = (*blocks)[(size_t)(I * NG + J) * 16 + i * 4 + j];
+          }
+  };
+  after_reduce(c, unpack);  // (runs at once unless the reduction was queued)
+  return PO_OK;
+}
+
+// Panels wider than one launch go by column blocks of BOTH panels (every pair of blocks is one launch, each block
+// streamed once per block of the other panel), as k_wgram does; the result is then complete on return.
+int k_xgram(Ctx *c, const double *const *U, const double *const *Z, int m, int64_t w, double *out, bool may_defer) {
+  if (m <= 0) return PO_OK;
+  if (w <= 0) {
+    for (size_t i = 0; i < (size_t)m * m; i++) out[i] = 0.0;
+    return PO_OK;
+  }
+  if (m <= kXgramMaxVecs) return xgram_one_launch(c, U, Z, m, m, w, out, m, may_defer);
+  const int nb = (m + kXgramMaxVecs - 1) / kXgramMaxVecs;
+  int bw = (m + nb - 1) / nb;
+  bw = ((bw + 3) / 4) * 4;  // whole column groups
+  for (int I = 0; I < nb; I++) {
+    const int i0 = I * bw, ni = (m - i0 < bw) ? m - i0 : bw;
+    if (ni <= 0) continue;
+    for (int J = 0; J < nb; J++) {
+      const int j0 = J * bw, nj = (m - j0 < bw) ? m - j0 : bw;
+      if (nj <= 0) continue;
+      PO_TRY(xgram_one_launch(c, U + i0, Z + j0, ni, nj, w, out + i0 + (size_t)m * j0, m, false));
+    }
+  }
+  return PO_OK;
+}
+
 }  // namespace po

@@ -87,6 +87,21 @@ class ProblemCallbacks(C.Structure):
     ]
 
 
+# po_quasidef_callbacks (include/paropt_amd.h): a problem's own quasi-definite solver (createQuasiDefMat)
+QD_FACTOR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, po_vec, po_vec)
+QD_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, po_vec, po_vec, po_vec)
+QD_INFO_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p)  # returns const char * (kept alive by the caller)
+
+
+class QuasiDefCallbacks(C.Structure):
+    _fields_ = [
+        ("user", C.c_void_p),
+        ("factor", QD_FACTOR_FN),
+        ("apply", QD_APPLY_FN),
+        ("factor_info", QD_INFO_FN),
+    ]
+
+
 class ProblemSparseCallbacks(C.Structure):
     _fields_ = [
         ("eval_sparse_con", SPARSE_CON_FN),
@@ -219,6 +234,7 @@ SIGNATURES = {
         C.c_int, [po_problem, c_int_pp, c_int_pp, C.POINTER(C.c_void_p), c_i64_p]),
     "po_problem_set_chain": (C.c_int, [po_problem, C.c_int, C.c_int, C.c_int]),
     "po_problem_set_sparse_block_size": (C.c_int, [po_problem, C.c_int]),
+    "po_problem_set_quasidef_callbacks": (C.c_int, [po_problem, C.POINTER(QuasiDefCallbacks)]),
     "po_quasidef_factor": (C.c_int, [po_problem, po_vec, po_vec, po_vec]),
     "po_quasidef_apply": (C.c_int, [po_problem, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec]),
     "po_quasidef_factor_info": (C.c_char_p, [po_problem]),
@@ -353,6 +369,7 @@ SIGNATURES = {
     "po_mma_get_history": (C.c_int, [po_mma, C.POINTER(C.c_char_p)]),
     "po_mma_set_iteration_callback": (C.c_int, [po_mma, TR_ITER_FN, C.c_void_p]),
     "po_wgram": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
+    "po_xgram": (C.c_int, [vec_p, vec_p, C.c_int, c_double_p]),
     "po_wgram_with_rhs": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
     "po_group_panel": (C.c_int, [po_vec, vec_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, vec_p]),
     "po_wgram_with_groups": (C.c_int, [po_vec, vec_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double,
