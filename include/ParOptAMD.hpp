@@ -849,23 +849,139 @@ enum ParOptQuasiNewtonDiagonalType {
   PAROPT_INNER_PRODUCT_YTS_OVER_STS
 };
 
+// The reference's abstract class (src/ParOptQuasiNewton.h:32-67): B = b0 I - Z diag(d) M^-1 diag(d) Z^T.  A subclass
+// written by the USER is bound to the library on first use (handle(problem)): po_qn_create_callbacks with trampolines
+// that wrap the po_vec arguments as borrowed ParOptBasicVec.  The library evaluates B through getCompactMat() alone;
+// mult / multAdd serve po_qn_mult / po_qn_mult_add (checkCompactForm compares the two).  The columns of Z must be
+// library vectors (ParOptBasicVec): a user-written vector class is refused.  The caller keeps the object alive while
+// it is attached.
 class ParOptCompactQuasiNewton : public ParOptBase {
  public:
+  ParOptCompactQuasiNewton() : h(NULL) {}
   virtual ~ParOptCompactQuasiNewton() {
-    for (ParOptVec *v : zwrap) v->decref();
     if (h) po_qn_destroy(h);
+  }
+  virtual void setInitDiagonalType(ParOptQuasiNewtonDiagonalType) {}                                           // :38
+  virtual void reset() = 0;                                                                                    // :42
+  virtual int update(ParOptVec *x, const ParOptScalar *z, ParOptVec *zw, ParOptVec *s, ParOptVec *y) = 0;      // :45
+  virtual int update(ParOptVec *, const ParOptScalar *, ParOptVec *) { return 0; }                             // :51
+  virtual void mult(ParOptVec *x, ParOptVec *y) = 0;                                                           // :56
+  virtual void multAdd(ParOptScalar alpha, ParOptVec *x, ParOptVec *y) = 0;                                    // :59
+  virtual int getCompactMat(ParOptScalar *b0, const ParOptScalar **d, const ParOptScalar **M, ParOptVec ***Z) = 0;  // :62
+  virtual int getMaxLimitedMemorySize() = 0;                                                                   // :66
+
+  // facade additions: the library-side handle.  A library class has one from its constructor; a user-written class
+  // gets one where it is handed over (setQuasiNewton, ParOptQuadraticSubproblem, ParOptEigenQuasiNewton, a user
+  // subproblem's getQuasiNewton), from that place's context and local size.
+  po_qn handle() { return h; }
+  po_qn handle(po_ctx ctx, int nlocal) {
+    if (!h && ctx) {
+      po_qn_callbacks cb;
+      cb.user = this;
+      cb.reset = &t_reset;
+      cb.update = &t_update;
+      cb.update_multipliers = &t_update_mult;
+      cb.mult = &t_mult;
+      cb.mult_add = &t_mult_add;
+      cb.get_compact_mat = &t_compact;
+      cb.get_max_size = &t_max_size;
+      cb.set_init_diagonal_type = &t_diag;
+      if (po_qn_create_callbacks(ctx, nlocal, &cb, &h) != 0) {
+        fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+        h = NULL;
+      }
+    }
+    return h;
+  }
+  inline po_qn handle(ParOptProblem *prob);
+  // max|mult(x) - (b0 x - Z d M^-1 d Z^T x)| / max|mult(x)| for a hashed probe x (po_qn_check_compact); < 0: error
+  inline double checkCompactForm(ParOptProblem *prob, unsigned long long seed = 0);
+
+ protected:
+  po_qn h;
+
+ private:
+  typedef ParOptCompactQuasiNewton Self;
+  static Self *me(void *u) { return static_cast<Self *>(u); }
+  // whatever the user's code took with getArray is released before the library goes on (outputs are uploaded)
+  static void done(po_vec v, int upload) {
+    if (v) po_vec_release_array(v, upload);
+  }
+  static int t_reset(void *u) {
+    me(u)->reset();
+    return 0;
+  }
+  static int t_update(void *u, po_vec x, const double *z, po_vec zw, po_vec s, po_vec y, int *rc) {
+    ParOptBasicVec vx(x), vzw(zw), vs(s), vy(y);
+    *rc = me(u)->update(x ? &vx : NULL, z, zw ? &vzw : NULL, &vs, &vy);
+    done(x, 0), done(zw, 0), done(s, 0), done(y, 0);
+    return 0;
+  }
+  static int t_update_mult(void *u, po_vec x, const double *z, po_vec zw) {
+    ParOptBasicVec vx(x), vzw(zw);
+    me(u)->update(x ? &vx : NULL, z, zw ? &vzw : NULL);
+    done(x, 0), done(zw, 0);
+    return 0;
+  }
+  static int t_mult(void *u, po_vec x, po_vec y) {
+    ParOptBasicVec vx(x), vy(y);
+    me(u)->mult(&vx, &vy);
+    done(x, 0), done(y, 1);
+    return 0;
+  }
+  static int t_mult_add(void *u, double alpha, po_vec x, po_vec y) {
+    ParOptBasicVec vx(x), vy(y);
+    me(u)->multAdd(alpha, &vx, &vy);
+    done(x, 0), done(y, 1);
+    return 0;
+  }
+  static int t_compact(void *u, int *size, double *b0, const double **d, const double **M, const po_vec **Z) {
+    Self *q = me(u);
+    ParOptVec **Zu = NULL;
+    const int k = q->getCompactMat(b0, d, M, &Zu);
+    q->zh.resize(k > 0 ? k : 1);
+    for (int i = 0; i < k; i++) {
+      po_vec hz = (Zu && Zu[i]) ? Zu[i]->handle() : NULL;
+      if (!hz) {
+        fprintf(stderr, "ParOptAMD: column %d of Z is not a library vector (ParOptBasicVec); user-written vector "
+                        "classes are not supported as columns of a quasi-Newton approximation\n", i);
+        return 1;
+      }
+      q->zh[i] = hz;
+    }
+    *size = k;
+    *Z = q->zh.data();
+    return 0;
+  }
+  static int t_max_size(void *u, int *size) {
+    *size = me(u)->getMaxLimitedMemorySize();
+    return 0;
+  }
+  static int t_diag(void *u, int t) {
+    me(u)->setInitDiagonalType(t == PO_QN_YTS_OVER_STS ? PAROPT_YTS_OVER_STS : PAROPT_YTY_OVER_YTS);
+    return 0;
+  }
+  std::vector<po_vec> zh;
+};
+
+// The approximations the library implements (L-BFGS, L-SR1, the eigenvalue combination): every method forwards to the
+// po_qn handle the constructor of the subclass made.
+class ParOptLibraryQuasiNewton : public ParOptCompactQuasiNewton {
+ public:
+  ~ParOptLibraryQuasiNewton() {
+    for (ParOptVec *v : zwrap) v->decref();
   }
   void setInitDiagonalType(ParOptQuasiNewtonDiagonalType t) {
     po_qn_set_diag_type(h, t == PAROPT_YTS_OVER_STS ? PO_QN_YTS_OVER_STS : PO_QN_YTY_OVER_YTS);
   }
   void reset() { po_qn_reset(h); }
-  virtual int update(ParOptVec *, const ParOptScalar *, ParOptVec *, ParOptVec *s, ParOptVec *y) {
+  int update(ParOptVec *, const ParOptScalar *, ParOptVec *, ParOptVec *s, ParOptVec *y) {
     int rc = 0;
     po_qn_update(h, s->handle(), y->handle(), &rc);
     return rc;
   }
   // multiplier-only update (src/ParOptQuasiNewton.h:60-63): a no-op for the limited-memory classes
-  virtual int update(ParOptVec *, const ParOptScalar *, ParOptVec *) { return 0; }
+  int update(ParOptVec *, const ParOptScalar *, ParOptVec *) { return 0; }
   void mult(ParOptVec *x, ParOptVec *y) { po_qn_mult(h, x->handle(), y->handle()); }
   void multAdd(ParOptScalar alpha, ParOptVec *x, ParOptVec *y) { po_qn_mult_add(h, alpha, x->handle(), y->handle()); }
   int getCompactMat(ParOptScalar *b0, const ParOptScalar **d, const ParOptScalar **M, ParOptVec ***Z) {
@@ -884,15 +1000,13 @@ class ParOptCompactQuasiNewton : public ParOptBase {
     return k;
   }
   int getMaxLimitedMemorySize() { int k = 0; po_qn_max_size(h, &k); return k; }
-  po_qn handle() { return h; }
 
  protected:
-  ParOptCompactQuasiNewton() : h(NULL) {}
-  po_qn h;
+  ParOptLibraryQuasiNewton() {}
   std::vector<ParOptVec *> zwrap;
 };
 
-class ParOptLBFGS : public ParOptCompactQuasiNewton {
+class ParOptLBFGS : public ParOptLibraryQuasiNewton {
  public:
   ParOptLBFGS(ParOptProblem *prob, int subspace) {
     int n;
@@ -904,13 +1018,94 @@ class ParOptLBFGS : public ParOptCompactQuasiNewton {
   }
 };
 
-class ParOptLSR1 : public ParOptCompactQuasiNewton {
+class ParOptLSR1 : public ParOptLibraryQuasiNewton {
  public:
   ParOptLSR1(ParOptProblem *prob, int subspace) {
     int n;
     prob->getProblemSizes(&n, NULL, NULL);
     po_qn_create(prob->getContext(), PO_QN_SR1, n, subspace, &h);
   }
+};
+
+inline po_qn ParOptCompactQuasiNewton::handle(ParOptProblem *prob) {
+  if (!h && prob) {
+    int n = 0;
+    prob->getProblemSizes(&n, NULL, NULL);
+    handle(prob->getContext(), n);
+  }
+  return h;
+}
+inline double ParOptCompactQuasiNewton::checkCompactForm(ParOptProblem *prob, unsigned long long seed) {
+  double err = -1.0;
+  if (!handle(prob) || po_qn_check_compact(h, seed, &err) != 0) {
+    fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+    return -1.0;
+  }
+  return err;
+}
+
+// ParOptScaledQuasiNewton: B = z0 B0 with B0 the wrapped approximation and z0 = z[0], the multiplier of the problem's
+// single constraint, taken at every update.  Written on the public virtuals alone (no library support): update scales
+// y by 1 / z0 into a vector of its own and forwards, mult / multAdd scale by z0, the compact form is
+// (z0 b0, sqrt(z0) d, M, Z).  A multiplier z0 <= 0 (which the reference divides by) leaves the previous scaling in
+// place; it starts at 1.
+class ParOptScaledQuasiNewton : public ParOptCompactQuasiNewton {
+ public:
+  ParOptScaledQuasiNewton(ParOptProblem *prob, ParOptCompactQuasiNewton *_qn) : qn(_qn), z0(1.0), ncon(0) {
+    qn->incref();
+    prob->getProblemSizes(NULL, &ncon, NULL);
+    y0 = prob->createDesignVec();
+    y0->incref();
+  }
+  ~ParOptScaledQuasiNewton() {
+    if (h) po_qn_destroy(h);  // before the objects it borrows
+    h = NULL;
+    y0->decref();
+    qn->decref();
+  }
+  void setInitDiagonalType(ParOptQuasiNewtonDiagonalType t) { qn->setInitDiagonalType(t); }
+  void reset() {
+    qn->reset();
+    z0 = 1.0;
+  }
+  int update(ParOptVec *x, const ParOptScalar *z, ParOptVec *zw, ParOptVec *s, ParOptVec *y) {
+    take(z);
+    y0->copyValues(y);
+    y0->scale(1.0 / z0);
+    return qn->update(x, z, zw, s, y0);
+  }
+  int update(ParOptVec *x, const ParOptScalar *z, ParOptVec *zw) {
+    take(z);
+    return qn->update(x, z, zw);
+  }
+  void mult(ParOptVec *x, ParOptVec *y) {
+    qn->mult(x, y);
+    y->scale(z0);
+  }
+  void multAdd(ParOptScalar alpha, ParOptVec *x, ParOptVec *y) { qn->multAdd(z0 * alpha, x, y); }
+  int getCompactMat(ParOptScalar *b0, const ParOptScalar **d, const ParOptScalar **M, ParOptVec ***Z) {
+    ParOptScalar b = 0.0;
+    const ParOptScalar *dq = NULL;
+    const int k = qn->getCompactMat(&b, &dq, M, Z);
+    const ParOptScalar rt = sqrt(z0);
+    dz.resize(k > 0 ? k : 1);
+    for (int i = 0; i < k; i++) dz[i] = rt * dq[i];
+    if (b0) *b0 = z0 * b;
+    if (d) *d = dz.data();
+    return k;
+  }
+  int getMaxLimitedMemorySize() { return qn->getMaxLimitedMemorySize(); }
+  ParOptScalar getScaling() { return z0; }
+
+ private:
+  void take(const ParOptScalar *z) {
+    if (z && ncon > 0 && z[0] > 0.0) z0 = z[0];
+  }
+  ParOptCompactQuasiNewton *qn;
+  ParOptVec *y0;
+  ParOptScalar z0;
+  int ncon;
+  std::vector<ParOptScalar> dz;
 };
 
 // ---- ParOptInteriorPoint ------------------------------------------------------------------------
@@ -995,7 +1190,9 @@ class ParOptInteriorPoint : public ParOptBase {
   void setPenaltyGamma(double gamma) { po_ip_set_penalty_gamma(ip, gamma); }
   void setPenaltyGamma(const double *gamma) { po_ip_set_penalty_gamma_array(ip, gamma); }
   // the caller keeps ownership of (and must keep alive) the approximation; NULL detaches it
-  void setQuasiNewton(ParOptCompactQuasiNewton *qn) { po_ip_set_quasi_newton(ip, qn ? qn->handle() : NULL); }
+  void setQuasiNewton(ParOptCompactQuasiNewton *qn) {
+    if (po_ip_set_quasi_newton(ip, qn ? qn->handle(prob) : NULL) != 0) fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+  }
   void resetProblemInstance(ParOptProblem *problem) {
     if (po_ip_reset_problem_instance(ip, problem->handle()) == 0) {
       problem->incref();
@@ -1068,7 +1265,8 @@ class ParOptInteriorPoint : public ParOptBase {
 // c(s) = c0 + g0^T s + 1/2 s^T H M H^T s with N curvature directions H = [h_0 .. h_{N-1}]
 class ParOptCompactEigenApprox : public ParOptBase {
  public:
-  ParOptCompactEigenApprox(ParOptProblem *problem, int _N) : h(NULL), g0w(NULL) {
+  ParOptCompactEigenApprox(ParOptProblem *problem, int _N) : h(NULL), ctx(problem->getContext()), nlocal(0), g0w(NULL) {
+    problem->getProblemSizes(&nlocal, NULL, NULL);
     if (po_eig_create(problem->handle(), _N, &h) != 0) fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
   }
   ~ParOptCompactEigenApprox() {
@@ -1105,6 +1303,8 @@ class ParOptCompactEigenApprox : public ParOptBase {
     po_eig_eval_approximation_gradient(h, s->handle(), grad->handle());
   }
   po_eig handle() { return h; }
+  po_ctx getContext() { return ctx; }
+  int getLocalSize() { return nlocal; }
 
  private:
   void dropWrappers() {
@@ -1114,18 +1314,20 @@ class ParOptCompactEigenApprox : public ParOptBase {
     hw.clear();
   }
   po_eig h;
+  po_ctx ctx;
+  int nlocal;
   ParOptVec *g0w;
   std::vector<ParOptVec *> hw;
 };
 
 // B = B_qn - z0 * H M H^T as one compact matrix over [Z_qn | H]; z0 follows the multiplier of constraint `index`
-class ParOptEigenQuasiNewton : public ParOptCompactQuasiNewton {
+class ParOptEigenQuasiNewton : public ParOptLibraryQuasiNewton {
  public:
   ParOptEigenQuasiNewton(ParOptCompactQuasiNewton *_qn, ParOptCompactEigenApprox *_eigh, int _index = 0)
       : qn(_qn), eigh(_eigh), index(_index) {
     if (qn) qn->incref();
     eigh->incref();
-    if (po_eigqn_create(qn ? qn->handle() : NULL, eigh->handle(), index, &h) != 0)
+    if (po_eigqn_create(qn ? qn->handle(eigh->getContext(), eigh->getLocalSize()) : NULL, eigh->handle(), index, &h) != 0)
       fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
   }
   ~ParOptEigenQuasiNewton() {
@@ -1219,7 +1421,7 @@ class ParOptTrustRegionSubproblem : public ParOptProblem {
   static Self *me(void *u) { return static_cast<Self *>(u); }
   static int ts_qn(void *u, po_qn *qn) {
     ParOptCompactQuasiNewton *q = me(u)->getQuasiNewton();
-    *qn = q ? q->handle() : NULL;
+    *qn = q ? q->handle(me(u)) : NULL;
     return 0;
   }
   static int ts_init(void *u, double tr) {
@@ -1389,7 +1591,7 @@ class ParOptQuadraticSubproblem : public ParOptLibrarySubproblem {
   ParOptQuadraticSubproblem(ParOptProblem *_problem, ParOptCompactQuasiNewton *_qn)
       : ParOptLibrarySubproblem(_problem), qn(_qn) {
     if (qn) qn->incref();
-    check(po_trsub_create_quadratic(_problem->handle(), qn ? qn->handle() : NULL, &sub));
+    check(po_trsub_create_quadratic(_problem->handle(), qn ? qn->handle(_problem) : NULL, &sub));
   }
   ~ParOptQuadraticSubproblem() {
     if (sub) po_trsub_destroy(sub);  // before the quasi-Newton object it borrows

@@ -250,6 +250,36 @@ int po_qn_get_pivots(po_qn qn, const int **mfpiv, int *n);
 int po_qn_debug_load(po_qn qn, int msub, double b0, const double *B, const double *L, const double *D, int ld,
                      const po_vec *S, const po_vec *Y);
 
+/* A compact quasi-Newton approximation of the USER's own (ParOptCompactQuasiNewton, src/ParOptQuasiNewton.h:32-67).
+ * Every callback returns 0 on success; a non-zero return ends optimize() with PO_ERR_USER.  Vectors handed to a
+ * callback are coherent on the device when it is called.  The callbacks run outside any batched reduction: the user's
+ * code may call any reduction of this ABI and gets its value at once.
+ * The library evaluates B ONLY through the compact form (get_compact_mat), for user approximations as for its own;
+ * mult / mult_add serve po_qn_mult / po_qn_mult_add alone (po_qn_check_compact compares the two).  The library asks
+ * for the compact form after every reset / update / update_multipliers it issues, at the head of every KKT set-up and
+ * at the start of optimize(), and redoes its LU of M only when k, d or M changed. */
+typedef struct {
+  void *user;
+  int (*reset)(void *user);                                                          /* .h:42 */
+  /* .h:45-46; *rc = 0 normal, 1 damped, 2 skipped.  x, zw may be NULL (po_qn_update has neither) */
+  int (*update)(void *user, po_vec x, const double *z, po_vec zw, po_vec s, po_vec y, int *rc);
+  int (*update_multipliers)(void *user, po_vec x, const double *z, po_vec zw);       /* .h:51-53; may be NULL */
+  int (*mult)(void *user, po_vec x, po_vec y);                                       /* .h:56 */
+  int (*mult_add)(void *user, double alpha, po_vec x, po_vec y);                     /* .h:59 */
+  /* .h:62-63: B = b0 I - Z diag(d) M^-1 diag(d) Z^T.  d[k], M[k*k] column-major (as po_qn_get_compact), Z[k]:
+   * BORROWED until the next callback into this table.  Z[i] are po_vec of this context and local size. */
+  int (*get_compact_mat)(void *user, int *size, double *b0, const double **d, const double **M, const po_vec **Z);
+  int (*get_max_size)(void *user, int *size);                                        /* .h:66 */
+  int (*set_init_diagonal_type)(void *user, int diag_type);                          /* .h:38-39; may be NULL */
+} po_qn_callbacks;
+/* The result is a po_qn like any other (po_ip_set_quasi_newton, po_trsub_create_quadratic, po_eigqn_create, po_qn_*).
+ * The table is copied; `user` stays the caller's and must outlive the handle.  po_qn_set_update_type is a no-op for it
+ * and po_qn_debug_load answers PO_ERR_ARG: the class has no pair storage to load. */
+int po_qn_create_callbacks(po_ctx ctx, int64_t nlocal, const po_qn_callbacks *cb, po_qn *out);
+/* max|mult(x) - (b0 x - Z d M^-1 d Z^T x)| / max|mult(x)| for a probe x = po_vec_fill_hash(seed): how far the
+ * approximation's mult is from its own compact form.  Works for every po_qn. */
+int po_qn_check_compact(po_qn qn, uint64_t seed, double *rel_err);
+
 /* ---- ParOptProblem: src/ParOptProblem.h:42-296 -------------------------------------------- */
 /* User problems are bound the way the reference's own FFI binds them: a table of C callbacks
  * (src/CyParOptProblem.h:44-69).  Callbacks receive device vectors; use

@@ -5,6 +5,7 @@ InteriorPoint) so tests read like the reference's own; all arithmetic happens in
 libparopt_amd.so on the GPU.
 """
 import contextlib
+import math
 import ctypes as C
 
 import numpy as np
@@ -428,6 +429,12 @@ class _QuasiNewton:
         check(lib.po_qn_debug_load(self._h, msub, float(b0), Bf.ctypes.data_as(L.c_double_p),
                                    Lf.ctypes.data_as(L.c_double_p), Df.ctypes.data_as(L.c_double_p), ld, sh, yh))
 
+    def checkCompactForm(self, seed=0):
+        """max|mult(x) - (b0 x - Z d M^-1 d Z^T x)| / max|mult(x)| for a hashed probe x (po_qn_check_compact)."""
+        err = C.c_double()
+        _qn_check(lib.po_qn_check_compact(self._h, int(seed), C.byref(err)))
+        return err.value
+
     def getCompactMat(self):
         k, b0 = C.c_int(), C.c_double()
         d0, M, Z = L.c_double_p(), L.c_double_p(), L.vec_p()
@@ -448,6 +455,292 @@ class LBFGS(_QuasiNewton):
 class LSR1(_QuasiNewton):
     def __init__(self, ctx, n, subspace=10):
         super().__init__(ctx, 1, n, subspace)
+
+
+# The first exception thrown inside a callback of a user-written quasi-Newton approximation: the callback reports a
+# failed call, the library winds down with PO_ERR_USER, and the optimize() that drove it re-raises the exception.
+_QN_PENDING = [None]
+
+
+def _raise_qn_pending():
+    e, _QN_PENDING[0] = _QN_PENDING[0], None
+    if e is not None:
+        raise e
+
+
+def _qn_check(rc):
+    _raise_qn_pending()
+    check(rc)
+
+
+class CompactQuasiNewton(_QuasiNewton):
+    """ParOptCompactQuasiNewton (reference src/ParOptQuasiNewton.h:32-67) as a base class to SUBCLASS: a compact
+    quasi-Newton approximation B = b0 I - Z diag(d) M^-1 diag(d) Z^T written by the user, bound through
+    po_qn_create_callbacks.  Override
+
+        reset()
+        update(x, z, zw, s, y) -> 0 normal | 1 damped | 2 skipped     (x, z, zw may be None)
+        updateMultipliers(x, z, zw)                                    (optional)
+        mult(x, y)                 y <- B x
+        multAdd(alpha, x, y)       y <- y + alpha B x
+        getCompactMat() -> (b0, d, M, Z)     M a (k, k) array with M[i, j] = row i, column j; Z a list of k PVec
+        getMaxLimitedMemorySize() -> int
+        setInitDiagonalType(t)                                         (optional)
+
+    Vector arguments arrive as PVec wrappers of the library's vectors, valid during the call (`.as_tensor()` is the
+    zero-copy torch view; with stream_scope=True every callback runs under `torch.cuda.stream(ctx.torch_stream())`).
+    host=True: x, zw, s, y arrive as numpy copies, y of mult / multAdd as a live host array written in place, and Z may
+    hold numpy arrays: the binding uploads them into vectors it owns and re-uploads a column only when its content
+    changed.  z is a numpy array when `ncon` is known (InteriorPoint.setQuasiNewton fills it in), else the raw pointer.
+
+    The library evaluates B through getCompactMat() alone; mult / multAdd serve the handle's po_qn_mult / po_qn_mult_add
+    (checkCompactForm() compares the two).  An exception thrown in a callback is re-raised by optimize().  The object
+    must stay alive while it is attached.  `driver()` returns the object as the LIBRARY sees it (update(s, y), mult,
+    getCompactMat, ... through the C ABI and the callback table)."""
+
+    def __init__(self, ctx, n, host=False, stream_scope=False, ncon=None):
+        self.ctx, self.n, self.host, self.ncon = ctx, int(n), bool(host), ncon
+        self._zcache = []  # host mode: (PVec, content) per column
+        self._keep = None
+        scope = contextlib.nullcontext
+        if stream_scope:
+            import torch
+
+            stream = ctx.torch_stream()
+
+            def scope():
+                cur = torch.cuda.current_stream(stream.device)
+                if cur.cuda_stream != stream.cuda_stream:
+                    stream.wait_stream(cur)
+                return torch.cuda.stream(stream)
+
+        def vec(h):
+            return PVec(ctx, handle=L.po_vec(h), owned=False) if h else None
+
+        def arg(h):
+            v = vec(h)
+            return v.to_numpy() if (self.host and v is not None) else v
+
+        def zarr(z):
+            if not z:
+                return None
+            return np.array([z[i] for i in range(self.ncon)]) if self.ncon is not None else z
+
+        def guard(fn):
+            def _g(*args):
+                if _QN_PENDING[0] is not None:
+                    return 1
+                try:
+                    with scope():
+                        return int(fn(*args) or 0)
+                except BaseException as e:  # noqa: BLE001 - re-raised by optimize()
+                    if _QN_PENDING[0] is None:
+                        _QN_PENDING[0] = e
+                    return 1
+            return _g
+
+        def _reset(user):
+            self.reset()
+
+        def _update(user, x, z, zw, s, y, rc):
+            rc[0] = int(self.update(arg(x), zarr(z), arg(zw), arg(s), arg(y)) or 0)
+
+        def _updmult(user, x, z, zw):
+            self.updateMultipliers(arg(x), zarr(z), arg(zw))
+
+        def out_call(fn, y):
+            vy = vec(y)
+            if not self.host:
+                return fn(vy)
+            try:
+                return fn(vy.getArray())
+            finally:
+                vy.releaseArray(True)
+
+        def _mult(user, x, y):
+            ax = arg(x)
+            out_call(lambda yy: self.mult(ax, yy), y)
+
+        def _mult_add(user, alpha, x, y):
+            ax = arg(x)
+            out_call(lambda yy: self.multAdd(alpha, ax, yy), y)
+
+        def _compact(user, size, b0, d, M, Z):
+            b, dd, MM, ZZ = self.getCompactMat()
+            k = len(ZZ)
+            dd = np.ascontiguousarray(dd, dtype=np.float64).ravel()
+            MM = np.asarray(MM, dtype=np.float64).reshape(k, k)
+            if len(dd) != k:
+                raise ValueError("getCompactMat: d has %d entries for %d columns of Z" % (len(dd), k))
+            Mf = np.ascontiguousarray(MM.T).ravel()  # column-major, as the C ABI holds it
+            cols = self._columns(ZZ)
+            zh = (L.po_vec * max(k, 1))(*[v.handle.value for v in cols])
+            self._keep = (dd, Mf, zh, cols)
+            size[0], b0[0] = k, float(b)
+            d[0] = dd.ctypes.data_as(L.c_double_p)
+            M[0] = Mf.ctypes.data_as(L.c_double_p)
+            Z[0] = C.cast(zh, L.vec_p)
+
+        def _max_size(user, size):
+            size[0] = int(self.getMaxLimitedMemorySize())
+
+        def _diag(user, t):
+            self._user_diag_type(t)
+
+        cls = type(self)
+        has_um = cls.updateMultipliers is not CompactQuasiNewton.updateMultipliers
+        has_dt = cls.setInitDiagonalType is not CompactQuasiNewton.setInitDiagonalType
+        self._user_diag_type = self.setInitDiagonalType if has_dt else (lambda t: None)
+        cb = L.QnCallbacks()
+        self._fns = (L.QN_VOID_FN(guard(_reset)), L.QN_UPDATE_FN(guard(_update)),
+                     L.QN_UPDMULT_FN(guard(_updmult)) if has_um else L.QN_UPDMULT_FN(),
+                     L.QN_MULT_FN(guard(_mult)), L.QN_MULTADD_FN(guard(_mult_add)), L.QN_COMPACT_FN(guard(_compact)),
+                     L.QN_SIZE_FN(guard(_max_size)), L.QN_DIAG_FN(guard(_diag)) if has_dt else L.QN_DIAG_FN())
+        cb.user = None
+        (cb.reset, cb.update, cb.update_multipliers, cb.mult, cb.mult_add, cb.get_compact_mat, cb.get_max_size,
+         cb.set_init_diagonal_type) = self._fns
+        self._cb = cb
+        self._h = L.po_qn()
+        self._owned = True
+        check(lib.po_qn_create_callbacks(ctx.handle, self.n, C.byref(cb), C.byref(self._h)))
+
+    def _columns(self, ZZ):
+        """Z as a list of PVec: host-mode numpy columns go through vectors the binding owns (uploaded on change)."""
+        cols = []
+        for i, zc in enumerate(ZZ):
+            if isinstance(zc, PVec):
+                cols.append(zc)
+                continue
+            a = np.asarray(zc, dtype=np.float64)
+            if i >= len(self._zcache):
+                self._zcache.append([PVec(self.ctx, len(a)), None])
+            slot = self._zcache[i]
+            if slot[1] is None or slot[1].shape != a.shape or not np.array_equal(slot[1], a):
+                if len(slot[0]) != len(a):
+                    slot[0] = PVec(self.ctx, len(a))
+                slot[0].from_numpy(a)
+                slot[1] = a.copy()
+            cols.append(slot[0])
+        return cols
+
+    # -- the user's side: override these ---------------------------------------------------------
+    def reset(self):
+        raise NotImplementedError
+
+    def update(self, x, z, zw, s, y):
+        raise NotImplementedError
+
+    def updateMultipliers(self, x, z, zw):
+        return None
+
+    def mult(self, x, y):
+        raise NotImplementedError
+
+    def multAdd(self, alpha, x, y):
+        raise NotImplementedError
+
+    def getCompactMat(self):
+        raise NotImplementedError
+
+    def getMaxLimitedMemorySize(self):
+        raise NotImplementedError
+
+    def setInitDiagonalType(self, t):
+        return None
+
+    def debugLoad(self, *args):
+        raise L.ParOptAMDError(2, "a user-written approximation has no pair storage to load")
+
+    def driver(self):
+        return _QuasiNewtonDriver(self)
+
+
+class _QuasiNewtonDriver(_QuasiNewton):
+    """A user-written approximation as the library sees it: every call goes through the C ABI and the callback table."""
+
+    def __init__(self, user):
+        super().__init__(user.ctx, 0, 0, 0, handle=user._h)
+        self.user = user
+
+    def _call(self, fn, *args):
+        try:
+            return fn(*args)
+        finally:
+            _raise_qn_pending()
+
+    def reset(self):
+        return self._call(super().reset)
+
+    def update(self, s, y):
+        return self._call(super().update, s, y)
+
+    def mult(self, x, y):
+        return self._call(super().mult, x, y)
+
+    def multAdd(self, alpha, x, y):
+        return self._call(super().multAdd, alpha, x, y)
+
+    def getCompactMat(self):
+        return self._call(super().getCompactMat)
+
+    def checkCompactForm(self, seed=0):
+        return self._call(super().checkCompactForm, seed)
+
+
+class ScaledQuasiNewton(CompactQuasiNewton):
+    """ParOptScaledQuasiNewton: B = z0 B0 with B0 the wrapped approximation and z0 = z[0], the multiplier of a
+    problem's single constraint, taken at every update.  Written on the public methods alone:
+    update scales y by 1/z0 into a vector of its own and forwards, mult / multAdd scale by z0, the compact form is
+    (z0 b0, sqrt(z0) d, M, Z).  A multiplier z0 <= 0 (which the reference divides by) leaves the previous scaling in
+    place; it starts at 1."""
+
+    def __init__(self, problem, qn):
+        self.qn = qn
+        self.z0 = 1.0
+        self._y0 = PVec(problem.ctx, int(problem.nvars))
+        super().__init__(problem.ctx, int(problem.nvars), ncon=int(problem.ncon))
+
+    def _take(self, z):
+        if z is not None and self.ncon and z[0] > 0.0:
+            self.z0 = float(z[0])
+
+    def reset(self):
+        self.qn.reset()
+        self.z0 = 1.0
+
+    def update(self, x, z, zw, s, y):
+        self._take(z)
+        self._y0.copyValues(y)
+        self._y0.scale(1.0 / self.z0)
+        if isinstance(self.qn, CompactQuasiNewton):
+            return self.qn.update(x, z, zw, s, self._y0)
+        return self.qn.update(s, self._y0)
+
+    def updateMultipliers(self, x, z, zw):
+        self._take(z)
+        if isinstance(self.qn, CompactQuasiNewton):
+            self.qn.updateMultipliers(x, z, zw)
+
+    def mult(self, x, y):
+        self.qn.mult(x, y)
+        y.scale(self.z0)
+
+    def multAdd(self, alpha, x, y):
+        self.qn.multAdd(self.z0 * alpha, x, y)
+
+    def getCompactMat(self):
+        b0, d, M, Z = self.qn.getCompactMat()
+        return self.z0 * b0, math.sqrt(self.z0) * np.asarray(d), M, Z
+
+    def getMaxLimitedMemorySize(self):
+        if isinstance(self.qn, CompactQuasiNewton):
+            return self.qn.getMaxLimitedMemorySize()
+        v = C.c_int()
+        check(lib.po_qn_max_size(self.qn._h, C.byref(v)))
+        return v.value
+
+    def setInitDiagonalType(self, t):
+        self.qn.setInitDiagonalType(t)
 
 
 class _QuasiDefBinding:
@@ -1148,6 +1441,7 @@ class InteriorPoint:
         rc = lib.po_ip_optimize(self._h, checkpoint.encode() if checkpoint else None)
         if hasattr(self.problem, "_raise_pending"):
             self.problem._raise_pending()  # an exception thrown inside a problem callback
+        _raise_qn_pending()  # ... or inside a user-written quasi-Newton approximation
         if rc not in (0,):
             raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
         return rc
@@ -1198,7 +1492,9 @@ class InteriorPoint:
     def setQuasiNewton(self, qn):
         """Use a caller-owned LBFGS / LSR1 (kept alive by this object); None detaches it."""
         self._qn_ref = qn
-        check(lib.po_ip_set_quasi_newton(self._h, qn._h if qn is not None else None))
+        if isinstance(qn, CompactQuasiNewton) and qn.ncon is None:
+            qn.ncon = int(self.problem.ncon)
+        _qn_check(lib.po_ip_set_quasi_newton(self._h, qn._h if qn is not None else None))
 
     def resetProblemInstance(self, problem):
         self._prob_ref = problem
@@ -1826,6 +2122,7 @@ class TrustRegion:
             rc = lib.po_tr_optimize(self._h)
         if hasattr(self.problem, "_raise_pending"):
             self.problem._raise_pending()
+        _raise_qn_pending()
         if rc != 0:
             raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
         return rc

@@ -480,6 +480,49 @@ int po_qn_create(po_ctx ctx, int type, int64_t nlocal, int subspace, po_qn *out)
   *out = h;
   return PO_OK;
 }
+int po_qn_create_callbacks(po_ctx ctx, int64_t nlocal, const po_qn_callbacks *cb, po_qn *out) {
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(cb);
+  PO_CHECK_PTR(out);
+  if (nlocal < 0 || !cb->reset || !cb->update || !cb->mult || !cb->mult_add || !cb->get_compact_mat ||
+      !cb->get_max_size) {
+    po::set_error("po_qn_create_callbacks: reset, update, mult, mult_add, get_compact_mat and get_max_size are "
+                  "mandatory");
+    return PO_ERR_ARG;
+  }
+  po_qn_s *h = new po_qn_s();
+  h->qn = new CallbackQuasiNewton(ctx, nlocal, *cb);
+  *out = h;
+  return PO_OK;
+}
+int po_qn_check_compact(po_qn qn, uint64_t seed, double *rel_err) {
+  PO_CHECK_PTR(qn);
+  PO_CHECK_PTR(rel_err);
+  CompactQuasiNewton *q = qn->qn;
+  PO_TRY(q->refresh());
+  Vec *x = vec_new(q->ctx, q->n), *y = vec_new(q->ctx, q->n);
+  int rc = (x && y) ? PO_OK : PO_ERR_HIP;
+  double num = 0.0, den = 0.0;
+  if (rc == PO_OK) rc = k_fill_hash(q->ctx, x->d, q->n, seed, 0, 0, 2.0, -1.0);
+  if (rc == PO_OK) rc = q->mult(x, y);
+  if (rc == PO_OK) rc = k_reduce1(q->ctx, RED_AMAX, y->d, nullptr, q->n, &den);
+  if (rc == PO_OK) {
+    std::vector<const double *> zp = q->zPointers();
+    const int k = (int)zp.size();
+    std::vector<double> rz(k > 0 ? k : 1, 0.0);
+    if (k > 0) rc = k_mdot(q->ctx, x->d, zp.data(), k, q->n, rz.data());
+    if (rc == PO_OK) {
+      q->applyCompactInverse(rz.data());
+      // y <- y - b0 x + Z (d M^-1 d Z^T x)
+      rc = k_panel_axpy(q->ctx, y->d, -q->diag(), x->d, 1.0, rz.data(), zp.data(), k, q->n);
+    }
+  }
+  if (rc == PO_OK) rc = k_reduce1(q->ctx, RED_AMAX, y->d, nullptr, q->n, &num);
+  vec_decref(x);
+  vec_decref(y);
+  if (rc == PO_OK) *rel_err = den > 0.0 ? num / den : num;
+  return rc;
+}
 int po_qn_destroy(po_qn qn) {
   if (!qn) return PO_OK;
   delete qn->qn;
@@ -534,6 +577,7 @@ int po_qn_get_compact(po_qn qn, int *size, double *b0, const double **d0, const 
                       const po_vec **Z) {
   PO_CHECK_PTR(qn);
   Vec **z = nullptr;
+  PO_TRY(qn->qn->refresh());
   int k = qn->qn->getCompactMat(b0, d0, M, &z);
   if (size) *size = k;
   if (Z) {
@@ -552,6 +596,10 @@ int po_qn_get_pivots(po_qn qn, const int **mfpiv, int *n) {
 int po_qn_debug_load(po_qn qn, int msub, double b0, const double *B, const double *L, const double *D, int ld,
                      const po_vec *S, const po_vec *Y) {
   PO_CHECK_PTR(qn);
+  if (dynamic_cast<CallbackQuasiNewton *>(qn->qn)) {
+    po::set_error("po_qn_debug_load: a user-written approximation has no pair storage to load");
+    return PO_ERR_ARG;
+  }
   if (msub > 0) {
     PO_CHECK_PTR(B);
     PO_CHECK_PTR(L);

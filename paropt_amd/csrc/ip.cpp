@@ -129,7 +129,13 @@ int InteriorPoint::setQuasiNewton(CompactQuasiNewton *qn_) {  // :1193-1234
   qn_owned = false;
   qn_created = true;
   qn_handle.qn = qn;
-  return PO_OK;
+  return refreshQuasiNewton();  // a user-written approximation is validated at hand-over
+}
+
+int InteriorPoint::refreshQuasiNewton() {
+  // (no width check on c + k: panels wider than one kernel's pointer table go through the launchers' slabs, for a
+  // user-written approximation as for the built-in ones)
+  return qn ? qn->refresh() : PO_OK;
 }
 
 int InteriorPoint::resetProblemInstance(Problem *p) {  // :745-764
@@ -638,6 +644,7 @@ int InteriorPoint::getComplementarity(double *comp) {
 // the KKT system
 // ================================================================================================
 int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs_mu) {  // setUpKKTDiagSystem + setUpKKTSystem
+  if (qn) PO_TRY(refreshQuasiNewton());
   step_flags.ptpx_valid = false;
   scratch_flags.t0_valid = false;
   const double sigma = options.real("qn_sigma");
@@ -1869,12 +1876,12 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
       std::vector<double> zts(kz);
       for (int j = 0; j < kz; j++) zts[j] = alpha * sx * ptpx[c + j];
       qn->take_buffers = true;  // s_qn / y_qn are rewritten from scratch before their next use
-      const int urc = qn->updateWithZTs(s_qn, y_qn, zts.data(), update_type);
+      const int urc = qn->updateAt(x, vars.z.data(), has_w ? wvar[0] : nullptr, s_qn, y_qn, zts.data(), update_type);
       qn->take_buffers = false;
       PO_TRY(urc);
     } else {
       qn->take_buffers = true;
-      const int urc = qn->update(s_qn, y_qn, update_type);
+      const int urc = qn->updateAt(x, vars.z.data(), has_w ? wvar[0] : nullptr, s_qn, y_qn, nullptr, update_type);
       qn->take_buffers = false;
       PO_TRY(urc);
     }
@@ -1935,6 +1942,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
     if (any) PO_HIP(hipStreamSynchronize(ctx->stream));  // the pinned mirrors may be rewritten by the caller at once
   }
   PO_TRY(createQuasiNewton());
+  PO_TRY(refreshQuasiNewton());
   const double abs_res_tol = options.real("abs_res_tol");
   const double rel_func_tol = options.real("rel_func_tol");
   const double fprec = options.real("function_precision");

@@ -328,6 +328,7 @@ class InteriorPoint {
                     double *diag);
 
   int createQuasiNewton();
+  int refreshQuasiNewton();  // validates a user-written approximation and refreshes its cached compact form
   int initAndCheckDesignAndBounds();
   int initLeastSquaresMultipliers();
   int initAffineStepMultipliers();

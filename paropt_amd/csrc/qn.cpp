@@ -418,4 +418,131 @@ int LSR1::ensureZ() const {
   return k_panel_lincomb(ctx, zd.data(), 1.0, yp.data(), -b0, sp.data(), k, n);
 }
 
+// ------------------------------------------------------------------------------------------------
+// A user-written approximation behind a callback table (include/paropt_amd.h, po_qn_callbacks)
+static int upload_live(Vec *v) {  // a live host mirror is the authoritative copy; the callback reads the device
+  if (!v || !v->h_live || !v->h || v->n <= 0) return PO_OK;
+  PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, v->ctx->stream));
+  return PO_OK;
+}
+
+CallbackQuasiNewton::CallbackQuasiNewton(Ctx *ctx_, int64_t n_, const po_qn_callbacks &cb_)
+    : CompactQuasiNewton(ctx_, n_, 0, false), cb(cb_), status(PO_OK) {}
+
+int CallbackQuasiNewton::failed(int rc, const char *what) {
+  if (what) set_error("user quasi-Newton: %s failed", what);
+  CompactQuasiNewton::reset();  // no panel: nothing is ever launched on what was refused
+  return status = rc;
+}
+
+void CallbackQuasiNewton::setInitDiagonalType(int t) {
+  diag_type = t;
+  if (status == PO_OK && cb.set_init_diagonal_type && cb.set_init_diagonal_type(cb.user, t) != 0)
+    failed(PO_ERR_USER, "set_init_diagonal_type");
+}
+
+int CallbackQuasiNewton::getMaxLimitedMemorySize() {
+  int m = 0;
+  if (status != PO_OK) return 0;
+  if (cb.get_max_size(cb.user, &m) != 0) {
+    failed(PO_ERR_USER, "get_max_size");
+    return 0;
+  }
+  return m;
+}
+
+int CallbackQuasiNewton::refresh() {
+  if (status != PO_OK) return status;
+  int k = 0, kmax = 0;
+  double b = 1.0;
+  const double *d = nullptr, *Mu = nullptr;
+  const po_vec *Zu = nullptr;
+  if (cb.get_max_size(cb.user, &kmax) != 0) return failed(PO_ERR_USER, "get_max_size");
+  if (cb.get_compact_mat(cb.user, &k, &b, &d, &Mu, &Zu) != 0) return failed(PO_ERR_USER, "get_compact_mat");
+  if (k < 0 || k > kmax) {
+    set_error("user quasi-Newton: compact size %d outside 0..%d (get_max_size)", k, kmax);
+    return failed(PO_ERR_ARG, nullptr);
+  }
+  if (k > 0 && (!d || !Mu || !Zu)) {
+    set_error("user quasi-Newton: get_compact_mat returned size %d without d, M or Z", k);
+    return failed(PO_ERR_ARG, nullptr);
+  }
+  for (int i = 0; i < k; i++) {
+    if (!Zu[i]) {
+      set_error("user quasi-Newton: column %d of Z is NULL", i);
+      return failed(PO_ERR_ARG, nullptr);
+    }
+    if (Zu[i]->ctx != ctx || Zu[i]->n != n) {
+      set_error("user quasi-Newton: column %d of Z %s (local size %lld, expected %lld)", i,
+                Zu[i]->ctx != ctx ? "belongs to another context" : "has the wrong size", (long long)Zu[i]->n,
+                (long long)n);
+      return failed(PO_ERR_ARG, nullptr);
+    }
+  }
+  const bool same = (int)d0.size() == k && M.size() == (size_t)k * k && (int)piv.size() == k &&
+                    (k == 0 || (memcmp(d0.data(), d, sizeof(double) * k) == 0 &&
+                                memcmp(M.data(), Mu, sizeof(double) * (size_t)k * k) == 0));
+  b0 = b;
+  Z.assign(Zu, Zu + k);
+  for (Vec *v : Z) PO_TRY(upload_live(v));
+  if (!same) {  // the LU is redone only when k, d or M changed
+    d0.assign(d, d + k);
+    M.assign(Mu, Mu + (size_t)k * k);
+    factorM();
+  }
+  return PO_OK;
+}
+
+void CallbackQuasiNewton::reset() {
+  if (status != PO_OK) return;
+  if (cb.reset(cb.user) != 0) {
+    failed(PO_ERR_USER, "reset");
+    return;
+  }
+  (void)refresh();
+}
+
+int CallbackQuasiNewton::updateAt(Vec *x, const double *z, Vec *zw, Vec *s, Vec *y, const double *, int *rc) {
+  if (status != PO_OK) return status;
+  PO_TRY(upload_live(x));
+  PO_TRY(upload_live(zw));
+  PO_TRY(upload_live(s));
+  PO_TRY(upload_live(y));
+  int r = 0;
+  if (cb.update(cb.user, static_cast<po_vec>(x), z, static_cast<po_vec>(zw), static_cast<po_vec>(s),
+                static_cast<po_vec>(y), &r) != 0)
+    return failed(PO_ERR_USER, "update");
+  if (rc) *rc = r;
+  return refresh();
+}
+
+int CallbackQuasiNewton::updateMult(Vec *x, const double *z, Vec *zw) {
+  if (status != PO_OK) return status;
+  if (!cb.update_multipliers) return 0;
+  PO_TRY(upload_live(x));
+  PO_TRY(upload_live(zw));
+  if (cb.update_multipliers(cb.user, static_cast<po_vec>(x), z, static_cast<po_vec>(zw)) != 0)
+    return failed(PO_ERR_USER, "update_multipliers");
+  return refresh();
+}
+
+int CallbackQuasiNewton::mult(Vec *x, Vec *y) {
+  if (status != PO_OK) return status;
+  PO_TRY(upload_live(y));
+  if (cb.mult(cb.user, static_cast<po_vec>(x), static_cast<po_vec>(y)) != 0) {
+    set_error("user quasi-Newton: mult failed");
+    return PO_ERR_USER;
+  }
+  return PO_OK;
+}
+
+int CallbackQuasiNewton::multAdd(double alpha, Vec *x, Vec *y) {
+  if (status != PO_OK) return status;
+  if (cb.mult_add(cb.user, alpha, static_cast<po_vec>(x), static_cast<po_vec>(y)) != 0) {
+    set_error("user quasi-Newton: mult_add failed");
+    return PO_ERR_USER;
+  }
+  return PO_OK;
+}
+
 }  // namespace po

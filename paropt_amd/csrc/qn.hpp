@@ -22,7 +22,7 @@ class CompactQuasiNewton {
   CompactQuasiNewton(Ctx *ctx, int64_t n, int msub_max, bool keep_z);
   virtual ~CompactQuasiNewton();
 
-  void setInitDiagonalType(int t) { diag_type = t; }
+  virtual void setInitDiagonalType(int t) { diag_type = t; }
   virtual void reset();
   // returns PO_* status; *rc = 0 normal, 1 damped, 2 skipped (src/ParOptQuasiNewton.cpp:162-334)
   virtual int update(Vec *s, Vec *y, int *rc) = 0;
@@ -31,6 +31,16 @@ class CompactQuasiNewton {
   // implied -- none for L-BFGS (Z = [S | Y]), the S columns for L-SR1 (Y_j.s = Z_j.s + b0 S_j.s).  zTs has
   // size() entries in the order of the current panel.  Default: ignores the hint.
   virtual int updateWithZTs(Vec *s, Vec *y, const double *zTs, int *rc) { return update(s, y, rc); }
+  // The reference's full signature, update(x, z, zw, s, y) (src/ParOptQuasiNewton.h:45-46): the point and the
+  // multipliers the pair was taken at.  The built-in classes read neither and are reached exactly as before; an
+  // approximation written by the user (CallbackQuasiNewton) receives all five.  x, z, zw may be null.
+  virtual int updateAt(Vec *x, const double *z, Vec *zw, Vec *s, Vec *y, const double *zTs, int *rc) {
+    return zTs ? updateWithZTs(s, y, zTs, rc) : update(s, y, rc);
+  }
+  // Bring the cached compact form (size(), diag(), zPointers(), the LU behind applyCompactInverse()) up to date with
+  // whoever owns it.  The built-in classes own theirs: nothing to do.  Called at the start of optimize() and at the
+  // head of every setUpKKTSystem.
+  virtual int refresh() { return PO_OK; }
   // true: update() issues its reductions through the internal launchers only and tolerates an enclosing BatchScope
   // (core.hpp); false for approximations that call out to user code (ParOptEigenQuasiNewton's update callback)
   virtual bool reductionsBatchable() const { return false; }
@@ -139,6 +149,31 @@ class LSR1 : public CompactQuasiNewton {
 
  private:
   mutable bool z_pending;
+};
+
+// An approximation the USER wrote, reached through a po_qn_callbacks table (po_qn_create_callbacks).  It owns no pairs.
+// It keeps a host copy of (k, b0, d, M) and the column pointers of the user's Z, taken by refresh(); M is factored by
+// the in-repo LU, and only when k, d or M changed.  The library evaluates B through this copy alone; mult / multAdd of
+// the table serve po_qn_mult / po_qn_mult_add.  reductionsBatchable() stays false: the user's code may call any
+// reduction and gets its value at once.  None of the built-in shortcuts (updateWithZTs, pendingZ, take_buffers) is
+// taken: s and y are only read.
+class CallbackQuasiNewton : public CompactQuasiNewton {
+ public:
+  CallbackQuasiNewton(Ctx *ctx, int64_t n, const po_qn_callbacks &cb_);
+  void setInitDiagonalType(int t) override;
+  void reset() override;
+  int update(Vec *s, Vec *y, int *rc) override { return updateAt(nullptr, nullptr, nullptr, s, y, nullptr, rc); }
+  int updateAt(Vec *x, const double *z, Vec *zw, Vec *s, Vec *y, const double *zTs, int *rc) override;
+  int updateMult(Vec *x, const double *z, Vec *zw) override;
+  int mult(Vec *x, Vec *y) override;
+  int multAdd(double alpha, Vec *x, Vec *y) override;
+  int getMaxLimitedMemorySize() override;
+  int refresh() override;
+
+ private:
+  po_qn_callbacks cb;
+  int failed(int rc, const char *what);
+  int status;  // sticky:the first failure of a callback or of the validation (reset() cannot report one)
 };
 
 }  // namespace po

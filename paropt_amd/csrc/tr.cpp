@@ -370,7 +370,7 @@ int QuadraticSubproblem::evalTrialStepAndUpdate(int update_flag, Vec *step, cons
   if (qn && update_flag) {
     PO_TRY(lagrangianGradientDifference(z, zw));
     if (prob->computeQuasiNewtonUpdateCorrection(xtemp, z, step, t) != 0) return PO_ERR_USER;
-    PO_TRY(qn->update(step, t, &qn_update_type));
+    PO_TRY(qn->updateAt(xtemp, z, zw, step, t, nullptr, &qn_update_type));
   }
   return PO_OK;
 }

@@ -40,6 +40,7 @@ class EigenQuasiNewton : public CompactQuasiNewton {
   void reset() override;
   int update(Vec *s, Vec *y, int *rc) override;
   int updateMult(Vec *x, const double *z, Vec *zw) override;
+  int refresh() override { return qn ? qn->refresh() : PO_OK; }
   int mult(Vec *x, Vec *y) override;
   int multAdd(double alpha, Vec *x, Vec *y) override;
   int getCompactMat(double *b0_, const double **d0_, const double **M_, Vec ***Z_) override;

@@ -102,6 +102,25 @@ class QuasiDefCallbacks(C.Structure):
     ]
 
 
+# po_qn_callbacks (include/paropt_amd.h): a user-written ParOptCompactQuasiNewton
+QN_VOID_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
+QN_UPDATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, c_double_p, po_vec, po_vec, po_vec, c_int_p)
+QN_UPDMULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, c_double_p, po_vec)
+QN_MULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, po_vec)
+QN_MULTADD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, po_vec, po_vec)
+QN_COMPACT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_int_p, c_double_p, C.POINTER(c_double_p), C.POINTER(c_double_p),
+                            C.POINTER(vec_p))
+QN_SIZE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_int_p)
+QN_DIAG_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
+
+
+class QnCallbacks(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("reset", QN_VOID_FN), ("update", QN_UPDATE_FN),
+                ("update_multipliers", QN_UPDMULT_FN), ("mult", QN_MULT_FN), ("mult_add", QN_MULTADD_FN),
+                ("get_compact_mat", QN_COMPACT_FN), ("get_max_size", QN_SIZE_FN),
+                ("set_init_diagonal_type", QN_DIAG_FN)]
+
+
 class ProblemSparseCallbacks(C.Structure):
     _fields_ = [
         ("eval_sparse_con", SPARSE_CON_FN),
@@ -203,6 +222,8 @@ SIGNATURES = {
     "po_vec_maxpy": (C.c_int, [po_vec, C.c_double, c_double_p, vec_p, C.c_int]),
     "po_vec_fill_hash": (C.c_int, [po_vec, C.c_uint64, C.c_uint64, C.c_int64, C.c_double, C.c_double]),
     "po_qn_create": (C.c_int, [po_ctx, C.c_int, C.c_int64, C.c_int, C.POINTER(po_qn)]),
+    "po_qn_create_callbacks": (C.c_int, [po_ctx, C.c_int64, C.POINTER(QnCallbacks), C.POINTER(po_qn)]),
+    "po_qn_check_compact": (C.c_int, [po_qn, C.c_uint64, c_double_p]),
     "po_qn_destroy": (C.c_int, [po_qn]),
     "po_qn_set_update_type": (C.c_int, [po_qn, C.c_int]),
     "po_qn_set_diag_type": (C.c_int, [po_qn, C.c_int]),
