@@ -1217,6 +1217,25 @@ class ParOptInteriorPoint : public ParOptBase {
       if (rank == 0) fputs(report, stdout);
     }
   }
+  // Extension (no reference counterpart): Hessian-vector products by differences of the Lagrangian's gradient, so that
+  // use_hvec_product runs with a problem that does not override evalHvecProduct (po_ip_set_hvec_finite_difference).
+  // mode: PO_HVEC_EXACT (default), PO_HVEC_FD_WHEN_MISSING, PO_HVEC_FD_ALWAYS; returns 0 or the library's error code.
+  int setHvecFiniteDifference(int mode, int central = 0, double rel_step = 0.0) {
+    const int rc = po_ip_set_hvec_finite_difference(ip, mode, central, rel_step);
+    if (rc != 0) fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+    return rc;
+  }
+  // differenced products and the evalObjCon + evalObjConGradient pairs they cost (not part of getIterationCounters)
+  void getHvecFiniteDifferenceCount(int *products, int *evaluations) {
+    po_ip_get_hvec_fd_count(ip, products, evaluations);
+  }
+  double getHvecFiniteDifferenceStep() { double h = 0; po_ip_get_hvec_fd_step(ip, &h); return h; }
+  // hvec = H(x, z, zw) px at the solver's current point by the configured mode; zw may be NULL without sparse constraints
+  int evalHvec(const ParOptScalar *z, ParOptVec *zw, ParOptVec *px, ParOptVec *hvec) {
+    const int rc = po_ip_eval_hvec(ip, z, zw ? zw->handle() : NULL, px->handle(), hvec->handle());
+    if (rc != 0) fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+    return rc;
+  }
   // setBFGSUpdateType (.h:172, .cpp:1179-1186): applies to the solver's own L-BFGS object
   void setBFGSUpdateType(ParOptBFGSUpdateType update) {
     po_qn q = NULL;

@@ -492,6 +492,28 @@ int po_ip_set_quasi_newton(po_ip ip, po_qn qn);
 int po_ip_reset_problem_instance(po_ip ip, po_problem prob);
 /* number of Hessian-vector products of the last optimize (getIterationCounters' 4th output) */
 int po_ip_get_hvec_count(po_ip ip, int *nhvec);
+/* extension (no reference counterpart): Hessian-vector products by differences of the Lagrangian's gradient, for
+ * problems without evalHvecProduct under use_hvec_product.  H p = [grad L(x + h p) - grad L(x)] / h (central != 0:
+ * [grad L(x + h p) - grad L(x - h p)] / 2h) with L = f - z^T c - zw^T cw and h = min(rel_step (1 + |x|) / |p|, half the
+ * step to the nearest bound along p); rel_step <= 0 selects sqrt(DBL_EPSILON) (forward) or cbrt(DBL_EPSILON) (central).
+ * Each extra point costs one evalObjCon followed by one evalObjConGradient at that point, written into vectors the
+ * solver owns; they are counted by po_ip_get_hvec_fd_count and NOT by po_ip_get_counters.
+ *   PO_HVEC_EXACT            the problem's evalHvecProduct and nothing else (the default)
+ *   PO_HVEC_FD_WHEN_MISSING  the first evalHvecProduct that returns non-zero switches this solver to differences
+ *   PO_HVEC_FD_ALWAYS        the problem's evalHvecProduct is never called
+ * The solver of a trust-region or MMA subproblem accepts PO_HVEC_EXACT only (PO_ERR_ARG otherwise). */
+enum { PO_HVEC_EXACT = 0, PO_HVEC_FD_WHEN_MISSING = 1, PO_HVEC_FD_ALWAYS = 2 };
+int po_ip_set_hvec_finite_difference(po_ip ip, int mode, int central, double rel_step /* <= 0: default */);
+/* differenced products and the evaluation pairs they cost since the last optimize() began */
+int po_ip_get_hvec_fd_count(po_ip ip, int *products, int *evaluations);
+/* the step h of the last differenced product (the same value on every rank; 0 before the first and for p = 0) */
+int po_ip_get_hvec_fd_step(po_ip ip, double *h);
+/* H(x, z, zw) px at the solver's current point by the configured mode; valid where po_ip_check_gradients is (the
+ * forward form needs the gradient optimize() left at that point).  px and hvec are two different vectors; zw may be
+ * NULL without sparse constraints.  Collective.  With po_ip_set_callback_timing on, the stream time of the problem's
+ * callbacks inside the products taken HERE accumulates in the phase "hvec_user_eval" of po_ip_get_phase_times (inside
+ * optimize() they are part of "user_eval"). */
+int po_ip_eval_hvec(po_ip ip, const double *z, po_vec zw, po_vec px, po_vec hvec);
 int po_ip_reset_design_and_bounds(po_ip ip);                /* .cpp:1249-1251 */
 /* checkGradients(dh) (.h:166, .cpp:6196-6199): the problem's finite-difference check at the solver's current point;
  * *report (borrowed, valid until the next call) holds the text the reference prints */

@@ -16,7 +16,8 @@ Callbacks receive PVec objects with the reference's numpy-style item access on h
 (``x[:]``, ``g[:] = ...``); the values move to the GPU when the callback returns.  The MPI
 communicator argument is accepted and ignored: ranks are those of the paropt_amd Context (one process
 per GPU; ``ParOpt.setContext`` to supply one that is already wired to RCCL or to a host callback).
-Not provided: the CSR sparse problem form (``rowp``/``cols``).
+The CSR sparse problem form (``rowp``/``cols`` keywords of ``Problem``) is provided as well.  Beyond the reference:
+``InteriorPoint.setHvecFiniteDifference`` lets ``use_hvec_product`` run with a problem that has no ``evalHvecProduct``.
 """
 import numpy as np
 

@@ -1537,6 +1537,45 @@ class InteriorPoint:
         check(lib.po_ip_get_hvec_count(self._h, C.byref(v)))
         return v.value
 
+    HVEC_MODES = {"exact": 0, "when_missing": 1, "always": 2}
+
+    def setHvecFiniteDifference(self, mode="when_missing", central=False, rel_step=None):
+        """Hessian-vector products by differences of the Lagrangian's gradient (po_ip_set_hvec_finite_difference; no
+        reference counterpart): lets use_hvec_product run with a problem that has no evalHvecProduct.  mode: "exact"
+        (the problem's product only, the default of a new solver), "when_missing" (differences once the problem's
+        product has failed) or "always"; central: two extra evaluations per product instead of one; rel_step: None
+        for sqrt(eps) / cbrt(eps)."""
+        m = self.HVEC_MODES[mode] if isinstance(mode, str) else int(mode)
+        check(lib.po_ip_set_hvec_finite_difference(self._h, m, 1 if central else 0,
+                                                   0.0 if rel_step is None else float(rel_step)))
+        return self
+
+    def getHvecFiniteDifferenceCount(self):
+        """(products, evaluations) of the differenced products since optimize() began; the evaluations are NOT part
+        of getIterationCounters()."""
+        a, b = C.c_int(), C.c_int()
+        check(lib.po_ip_get_hvec_fd_count(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def getHvecFiniteDifferenceStep(self):
+        """The step h of the last differenced product (identical on every rank)."""
+        v = C.c_double()
+        check(lib.po_ip_get_hvec_fd_step(self._h, C.byref(v)))
+        return v.value
+
+    def evalHvec(self, z, zw, px, hvec):
+        """hvec = H(x, z, zw) px at the solver's current point by the configured mode (po_ip_eval_hvec); z: dense
+        multipliers (array), zw: PVec or None, px / hvec: two different PVec."""
+        arr = np.ascontiguousarray(z if z is not None else [], dtype=np.float64)
+        assert len(arr) == self.problem.ncon
+        raw = [getattr(v, "_v", v) for v in (zw, px, hvec)]  # (ParOpt.PVec wraps the library's vector)
+        rc = lib.po_ip_eval_hvec(self._h, arr.ctypes.data_as(L.c_double_p),
+                                 raw[0].handle if raw[0] is not None else None, raw[1].handle, raw[2].handle)
+        if hasattr(self.problem, "_raise_pending"):
+            self.problem._raise_pending()
+        check(rc)
+        return hvec
+
     def getBarrierParameter(self):
         v = C.c_double()
         check(lib.po_ip_get_barrier_parameter(self._h, C.byref(v)))

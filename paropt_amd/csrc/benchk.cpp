@@ -210,7 +210,7 @@ extern "C" int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, c
 namespace {
 typedef double bk_f64x2 __attribute__((ext_vector_type(2)));
 struct MixPtrs {
-  const double *in[48];
+  const double *in[72];
   double *out[2];
 };
 template <int NIN, int NOUT>
@@ -243,12 +243,14 @@ int run_mix(Ctx *c, int nin, int nout, const MixPtrs &P, int64_t n, double *sink
   PO_MIX(0, 1);
   PO_MIX(1, 1);
   PO_MIX(2, 1);
+  PO_MIX(4, 0);
   PO_MIX(11, 0);
   PO_MIX(11, 1);
   PO_MIX(12, 1);
   PO_MIX(41, 0);
   PO_MIX(41, 1);
   PO_MIX(42, 1);
+  PO_MIX(66, 1);
 #undef PO_MIX
   set_error("po_bench_vec_api: no trivial kernel for the mix %d in / %d out", nin, nout);
   return PO_ERR_ARG;
@@ -437,6 +439,49 @@ extern "C" int po_bench_vec_api(po_ctx ctx, int64_t n, int reps, char *report, i
       PO_TRY(T.time([&] { return q.qn->multAdd(1e-9, x, y); }, &ms));
       snprintf(mix, sizeof(mix), "%d in / 0 out + %d in / 1 out", q.k + 1, q.k + 2);
       T.row(q.name_add, q.ref_add, 8.0 * (2 * q.k + 4) * N, ms, mix, cm0 + cm2, 8.0 * (2 * q.k + 4) * N);
+    }
+    // Hessian-vector products by differences (ip_hvec_fd.cpp; no reference counterpart): the pass that takes the
+    // step size's sums and minima -- x, p and both bound vectors, or x and p alone when the bounds are uniform -- and
+    // the writer that combines the gradient and Jacobian pairs, at config 3's width (c = 32: 2 c + 2 = 66 input
+    // streams, every one a vector of its own) and for a problem with linear constraints (the gradient pair alone)
+    {
+      const int cfd = 32;
+      std::vector<const double *> Ap(V.begin(), V.begin() + cfd), Am;
+      for (int j = 0; j < cfd + 2; j++) {
+        Vec *v = mk(300 + j, 2.0, -1.0);
+        if (!v) return PO_ERR_HIP;
+        Am.push_back(v->d);
+      }
+      const double *gp = Am[cfd], *gm = Am[cfd + 1];
+      std::vector<double> zz(cfd, 0.5);
+      MixPtrs Q = P;
+      for (int j = 0; j < cfd; j++) {
+        Q.in[2 * j] = Ap[j];
+        Q.in[2 * j + 1] = Am[j];
+      }
+      Q.in[2 * cfd] = gp;
+      Q.in[2 * cfd + 1] = gm;
+      double c661 = 0.0, c40 = 0.0, km_p = 0.0;
+      PO_TRY(T.time([&] { return run_mix(cx, 2 * cfd + 2, 1, Q, n, sink); }, &c661));
+      PO_TRY(T.time([&] { return k_hvec_fd_combine(cx, y->d, 1e8, gp, gm, zz.data(), Ap.data(), Am.data(), cfd, n); },
+                    &ms));
+      T.row("hvec_fd_combine(c=32)", "--", 8.0 * (2 * cfd + 3) * N, ms, "66 in / 1 out", c661, 8.0 * (2 * cfd + 3) * N);
+      PO_TRY(T.time([&] { return k_hvec_fd_combine(cx, y->d, 1e8, gp, gm, nullptr, nullptr, nullptr, 0, n); }, &ms));
+      T.row("hvec_fd_combine(c=0)", "--", 24.0 * N, ms, "2 in / 1 out", c21, 24.0 * N);
+      PO_TRY(ceiling(4, 0, &c40));
+      Bounds bb{x->d, V[0], V[1], nullptr, nullptr, 1e20, 1, 1};
+      std::vector<double> pr((size_t)(reps + 1) * 4, 0.0);
+      int ps = 0;
+      auto prep = [&]() -> int { return k_hvec_fd_prepare(cx, bb, V[2], n, &pr[(size_t)(ps++ % (reps + 1)) * 4], false); };
+      PO_TRY(T.time(prep, &ms));
+      PO_TRY(T.time_batched(prep, &km_p));
+      T.row("hvec_fd_prepare", "--", 32.0 * N, ms, "4 in / 0 out", c40, 32.0 * N, km_p);
+      bb.lb_uni = bb.ub_uni = 1;
+      bb.lb_c = -2.0;
+      bb.ub_c = 2.0;
+      PO_TRY(T.time(prep, &ms));
+      PO_TRY(T.time_batched(prep, &km_p));
+      T.row("hvec_fd_prepare(uniform bounds)", "--", 16.0 * N, ms, "2 in / 0 out", c20, 16.0 * N, km_p);
     }
     snprintf(report, (size_t)report_len, "[%s]", T.out.c_str());
     return PO_OK;

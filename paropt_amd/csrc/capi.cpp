@@ -1093,6 +1093,30 @@ int po_ip_get_hvec_count(po_ip ip, int *nhvec) {
   *nhvec = ip->ip->nhvec;
   return PO_OK;
 }
+int po_ip_set_hvec_finite_difference(po_ip ip, int mode, int central, double rel_step) {
+  PO_CHECK_PTR(ip);
+  return ip->ip->setHvecFiniteDifference(mode, central, rel_step);
+}
+int po_ip_get_hvec_fd_count(po_ip ip, int *products, int *evaluations) {
+  PO_CHECK_PTR(ip);
+  ip->ip->getHvecFiniteDifferenceCount(products, evaluations);
+  return PO_OK;
+}
+int po_ip_get_hvec_fd_step(po_ip ip, double *h) {
+  PO_CHECK_PTR(ip);
+  PO_CHECK_PTR(h);
+  *h = ip->ip->hvecFiniteDifferenceStep();
+  return PO_OK;
+}
+int po_ip_eval_hvec(po_ip ip, const double *z, po_vec zw, po_vec px, po_vec hvec) {
+  PO_CHECK_PTR(ip);
+  PO_CHECK_PTR(px);
+  PO_CHECK_PTR(hvec);
+  if (zw) PO_TRY(mirror_up(zw));
+  PO_TRY(mirror_up(px));
+  PO_TRY(ip->ip->evalHvec(z, zw, px, hvec));
+  return mirror_down(hvec);
+}
 int po_ip_reset_design_and_bounds(po_ip ip) {
   PO_CHECK_PTR(ip);
   return ip->ip->resetDesignAndBounds();

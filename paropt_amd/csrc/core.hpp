@@ -533,6 +533,15 @@ int k_clamp_count(Ctx *c, const double *x, const double *lb, const double *ub, c
                   double eps, int64_t n, double out[4]);
 int k_zero_inactive(Ctx *c, const double *lb, const double *ub, double *zl, double *zu,
                     double max_bound, int64_t n);
+// Hessian-vector products by differences of the Lagrangian's gradient (ip_hvec_fd.cpp).
+// out = {sum x^2, sum p^2, largest a with x + a p inside the bounded components, the same for x - a p}: both sums and
+// both minima (+inf: nothing bounds the direction) in ONE reduction payload over all ranks; reads b.x, b.lb, b.ub.
+// now: the values are in `out` on return even inside an open BatchScope (the solver branches on the step size at once)
+int k_hvec_fd_prepare(Ctx *c, const Bounds &b, const double *p, int64_t n, double out[4], bool now = true);
+// hvec <- [hvec +] s ((gp - gm) - sum_j z_j (Ap_j - Am_j)), every pair subtracted before it is scaled and summed;
+// gp == nullptr: no gradient pair; any nc (slabs of kMaxPanel pairs accumulate); hvec aliases no input
+int k_hvec_fd_combine(Ctx *c, double *hvec, double s, const double *gp, const double *gm, const double *z,
+                      const double *const *Ap, const double *const *Am, int nc, int64_t n, int accumulate = 0);
 
 // ---- built-in problems --------------------------------------------------------------------------
 // f-parts: quadratic sum(0.5 q x^2 + b x), convex sum(b^2/(eps+x)), rosenbrock chain

@@ -110,6 +110,10 @@ InteriorPoint::~InteriorPoint() {
   for (Vec *v : Yw) vec_decref(v);
   for (Vec *v : gmresW) vec_decref(v);
   vec_decref(hdiag);
+  Vec *hall[] = {hvec_xp, hvec_csr_data, hvec_csr_cw};
+  for (Vec *v : hall) vec_decref(v);
+  for (int s = 0; s < 2; s++)
+    for (Vec *v : hvec_work[s]) vec_decref(v);
   if (qn_owned) delete qn;
   if (user_events_ready)
     for (int i = 0; i < 2 * kUserRing; i++) (void)hipEventDestroy(user_ev[i]);
@@ -248,7 +252,7 @@ int InteriorPoint::residualCoefs(ResTerm term, const double *z, const double *zt
   } else if (term != RES_SIGMA) {
     *diag = 0.0;
     if (term == RES_HVEC) {
-      if (prob->evalHvecProduct(x, vars.z.data(), nullptr, px, xt) != 0) return PO_ERR_USER;
+      PO_TRY(hvecProduct(vars.z.data(), nullptr, px, xt));
     } else {
       PO_TRY(k_mul(ctx, xt->d, 1.0, hdiag->d, px->d, n));
     }
@@ -1981,6 +1985,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
   const int gradient_verification_frequency = options.integer("gradient_verification_frequency");
   const std::string start = options.str("starting_point_strategy");
   niter = neval = ngeval = nhvec = 0;
+  hvec_fd_products = hvec_fd_evals = 0;
   stateReplaced();
   spec_dt_want = false;
   spec_enabled = false;

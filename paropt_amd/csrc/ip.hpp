@@ -107,6 +107,16 @@ class InteriorPoint {
   // checkMeritFuncGradient(xpt, dh) (:3280-3432): forward difference of the merit function along the current step
   // (xpt == nullptr) or, from xpt, along -g/|g| with the reference's fixed slack steps; out = {fd, actual}
   int checkMeritFuncGradient(Vec *xpt, double dh, double out[2]);
+  // Hessian-vector products by differences of the Lagrangian's gradient (ip_hvec_fd.cpp; no reference counterpart).
+  // mode: PO_HVEC_EXACT (the problem's evalHvecProduct, the default), PO_HVEC_FD_WHEN_MISSING (differences from the
+  // first evalHvecProduct that returns non-zero on), PO_HVEC_FD_ALWAYS; rel_step <= 0: the default of the form
+  int setHvecFiniteDifference(int mode, int central, double rel_step);
+  // differenced products so far and the evalObjCon + evalObjConGradient pairs they cost (NOT part of neval / ngeval,
+  // which keep counting the evaluations the algorithm asked for); both restart with optimize()
+  void getHvecFiniteDifferenceCount(int *products, int *evaluations) const;
+  double hvecFiniteDifferenceStep() const { return hvec_fd_h; }  // h of the last differenced product (0: none yet)
+  // hvec = H(x, z, zw) p at the current point by the configured mode (p, hvec: two different n-sized vectors)
+  int evalHvec(const double *z, Vec *zw, Vec *p, Vec *hvec);
 
   Problem *prob;
   Ctx *ctx;
@@ -262,6 +272,24 @@ class InteriorPoint {
   Vec *wscalev[5];
   double w_merit_last[10];  // k_w_merit sums of the last evalObjBarrierDeriv (sparse part)
   int computeKKTGMRESStep(double rtol, double atol, bool use_qn, double tau, int *gmres_iters);
+
+  // ---- Hessian-vector products, exact or differenced (ip_hvec_fd.cpp) ----
+  int hvec_mode = PO_HVEC_EXACT, hvec_central = 0;
+  double hvec_rel = 0.0;        // 0: sqrt(eps) forward, cbrt(eps) central
+  bool hvec_fd_active = false;  // PO_HVEC_FD_WHEN_MISSING: the problem's product has failed once
+  int hvec_fd_products = 0, hvec_fd_evals = 0;
+  double hvec_fd_h = 0.0;
+  // scratch, allocated by the first differenced product: the perturbed point, (g, A_1 .. A_c) of the plus side and,
+  // central form, of the minus side; CSR form: the iterate's Jacobian entries and constraint values while the
+  // problem's arrays hold those of a perturbed point
+  Vec *hvec_xp = nullptr;
+  std::vector<Vec *> hvec_work[2];
+  Vec *hvec_csr_data = nullptr, *hvec_csr_cw = nullptr;
+  int64_t hvec_csr_nnz = 0;
+  int hvecProduct(const double *z, Vec *zw, Vec *p, Vec *hvec);  // every product of the solver goes through here
+  int hvecFiniteDifference(const double *z, Vec *zw, Vec *p, Vec *hvec);
+  int hvecScratch(int sides, int nc);
+  int hvecEvalAt(double a, Vec *p, int side, bool with_jac);
 
   // ---- sparse-constraint path (ip_w.cpp) ----
   Vec *gsw, *gtw, *Cw, *wd2, *wyw, *wtmp, *wtmp2;

@@ -222,10 +222,7 @@ int InteriorPoint::computeKKTGMRESStep(double rtol, double atol, bool use_qn, do
     // sparse part (:5963-5973): -cwscale rzw.(Aw px) + cwscale rzw.(psw - ptw) with rzw = -(cw - sw + tw)
     if (has_w) aproj[i] += cwscale * w_merit_last[9];
     // W_{i+1} = H px - B px + W_i
-    if (prob->evalHvecProduct(x, vars.z.data(), has_w ? wvar[0] : nullptr, px, Wk[i + 1]) != 0) {
-      set_error("evalHvecProduct failed or is not provided by the problem");
-      return PO_ERR_USER;
-    }
+    PO_TRY(hvecProduct(vars.z.data(), has_w ? wvar[0] : nullptr, px, Wk[i + 1]));
     nhvec++;
     {
       std::vector<double> cf(kq + 1, 0.0);

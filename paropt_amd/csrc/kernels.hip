@@ -2661,6 +2661,125 @@ int k_zero_inactive(Ctx *c, const double *lb, const double *ub, double *zl, doub
 }
 
 // ---------------------------------------------------------------------------------------------
+// Hessian-vector products by differences of the Lagrangian's gradient (ip_hvec_fd.cpp)
+// ---------------------------------------------------------------------------------------------
+// What the step size needs, in one pass over x, p and the bounds: sums {x.x, p.p}, minima {largest a with x + a p
+// inside the bounded components, the same for x - a p} (+inf where nothing bounds the direction).  The iterate is
+// strictly inside its bounds, so every quotient is positive.
+__global__ void __launch_bounds__(kBlock)
+    hvec_fd_prepare_kernel(Bounds b, const double *__restrict__ p, int64_t n, double *__restrict__ partials) {
+  __shared__ double sm[4 * 2];
+  double s[2] = {0.0, 0.0}, m[2] = {INFINITY, INFINITY};
+  PO_PAIR_LOOP(q, n) {
+    const double2 xv = ld2(b.x, q, n), pv = ld2(p, q, n);
+    const double2 lbv = PO_LD2_LB(b, q, n), ubv = PO_LD2_UB(b, q, n);
+    const bool has2 = (2 * q + 1 < n);
+    s[0] += xv.x * xv.x + xv.y * xv.y;  // (the pad element of an odd-length vector is zero)
+    s[1] += pv.x * pv.x + pv.y * pv.y;
+    const double xs[2] = {xv.x, xv.y}, ps[2] = {pv.x, pv.y}, ls[2] = {lbv.x, lbv.y}, us[2] = {ubv.x, ubv.y};
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      if (e == 1 && !has2) continue;
+      const bool L = b.use_lower && (ls[e] > -b.max_bound), U = b.use_upper && (us[e] < b.max_bound);
+      const double ap = fabs(ps[e]);
+      if (ap == 0.0) continue;
+      const double tl = (xs[e] - ls[e]) / ap, tu = (us[e] - xs[e]) / ap;
+      if (ps[e] > 0.0) {  // x + a p moves up, x - a p moves down
+        if (U) m[0] = fmin(m[0], tu);
+        if (L) m[1] = fmin(m[1], tl);
+      } else {
+        if (L) m[0] = fmin(m[0], tl);
+        if (U) m[1] = fmin(m[1], tu);
+      }
+    }
+  }
+  block_reduce_store<2, OP_SUM>(s, partials, 0, sm);
+  block_reduce_store<2, OP_MIN>(m, partials, 2, sm);
+}
+int k_hvec_fd_prepare(Ctx *c, const Bounds &b, const double *p, int64_t n, double out[4], bool now) {
+  count_bytes(c, 4 - uniform_bound_streams(b), n);
+  const int grid = grid_for(c, n);
+  PO_TRY(ensure_partials(c, (size_t)grid * 4));
+  PO_LAUNCH(hvec_fd_prepare_kernel, grid, b, p, n, c->d_partials);
+  return reduce_finish(c, grid, 2, 2, 0, out, now);
+}
+
+// hvec <- [hvec +] s ((g+ - g-) - sum_j z_j (A+_j - A-_j)).  Each pair of nearly equal numbers is subtracted FIRST --
+// that difference is exact or nearly so -- and only the differences are scaled and summed: a linear combination of the
+// 2 nc + 2 columns in any other order would round the large terms before they cancel.  NV pairs (2 NV loads) are in
+// flight per batch, issued back to back before their arithmetic (as panel_batch); a zero z_j contributes an exact zero.
+template <int B>
+__device__ __forceinline__ void pair_diff_batch(const PtrTable &Pp, const PtrTable &Pm, const CoefTable &z, int j,
+                                                int64_t q, f64x2 &acc) {
+  f64x2 vp[B], vm[B];
+#pragma unroll
+  for (int u = 0; u < B; u++) {
+    vp[u] = ld_stream(Pp.p[j + u] + 2 * q);
+    vm[u] = ld_stream(Pm.p[j + u] + 2 * q);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < B; u++) {
+    const f64x2 d = vp[u] - vm[u];
+    acc.x -= z.a[j + u] * d.x;
+    acc.y -= z.a[j + u] * d.y;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int NV>
+__global__ void __launch_bounds__(kBlock)
+    hvec_fd_combine_kernel(double *__restrict__ hvec, double s, const double *__restrict__ gp,
+                           const double *__restrict__ gm, CoefTable z, PtrTable Ap, PtrTable Am, int nc,
+                           int accumulate, int64_t n) {
+  PO_PAIR_LOOP(q, n) {
+    f64x2 acc = (f64x2){0.0, 0.0};
+    if (gp) acc = ld_stream(gp + 2 * q) - ld_stream(gm + 2 * q);
+    int j = 0;
+    for (; j + NV <= nc; j += NV) pair_diff_batch<NV>(Ap, Am, z, j, q, acc);
+    if (NV > 4 && j + 4 <= nc) {
+      pair_diff_batch<4>(Ap, Am, z, j, q, acc);
+      j += 4;
+    }
+    if (NV > 2 && j + 2 <= nc) {
+      pair_diff_batch<2>(Ap, Am, z, j, q, acc);
+      j += 2;
+    }
+    if (NV > 1 && j < nc) pair_diff_batch<1>(Ap, Am, z, j, q, acc);
+    double2 r = make_double2(s * acc.x, s * acc.y);
+    if (accumulate) {
+      const double2 h = ld2(hvec, q, n);
+      r.x += h.x;
+      r.y += h.y;
+    }
+    st2(hvec, q, n, r);
+  }
+}
+int k_hvec_fd_combine(Ctx *c, double *hvec, double s, const double *gp, const double *gm, const double *z,
+                      const double *const *Ap, const double *const *Am, int nc, int64_t n, int accumulate) {
+  if (n <= 0) return PO_OK;
+  // widths beyond one launch's tables go by slabs: the first carries the gradient pair, the others accumulate
+  int j0 = 0;
+  do {
+    const int w = nc - j0 > kMaxPanel ? kMaxPanel : nc - j0;
+    const double *g1 = j0 == 0 ? gp : nullptr, *g0 = j0 == 0 ? gm : nullptr;
+    const int acc = (j0 == 0 ? accumulate : 1);
+    count_bytes(c, 2 * w + (g1 ? 2 : 0) + (acc ? 1 : 0) + 1, n);
+    CoefTable ct, unused;
+    PtrTable pp, pm;
+    fill_tables(z ? z + j0 : nullptr, Ap ? Ap + j0 : nullptr, w, &ct, &pp);
+    fill_tables(nullptr, Am ? Am + j0 : nullptr, w, &unused, &pm);
+    const int grid = grid_for(c, n, kBpcPanel);
+    if (w >= 8) {
+      PO_LAUNCH(hvec_fd_combine_kernel<8>, grid, hvec, s, g1, g0, ct, pp, pm, w, acc, n);
+    } else {
+      PO_LAUNCH(hvec_fd_combine_kernel<4>, grid, hvec, s, g1, g0, ct, pp, pm, w, acc, n);
+    }
+    j0 += w;
+  } while (j0 < nc);
+  return PO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // built-in problems (DESIGN.md "Workloads")
 // ---------------------------------------------------------------------------------------------
 template <int KIND>  // 0 quadratic, 1 convex

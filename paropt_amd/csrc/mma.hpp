@@ -42,6 +42,7 @@ class MMA : public Problem {
   int optimize();
 
   // ParOptProblem side (:795-1052)
+  bool isSubproblem() override { return true; }
   int getVarsAndBounds(Vec *x, Vec *lb, Vec *ub) override;
   int evalObjCon(Vec *x, double *fobj, double *cons) override;
   int evalObjConGradient(Vec *x, Vec *g, Vec **Ac) override;

@@ -48,6 +48,9 @@ class Problem {
   // Hessian of the Lagrangian f - z^T c - zw^T cw (src/ParOptProblem.h:160-189); non-zero = not available
   virtual int evalHvecProduct(Vec *x, const double *z, Vec *zw, Vec *px, Vec *hvec) { return 1; }
   virtual int evalHessianDiag(Vec *x, const double *z, Vec *zw, Vec *hdiag) { return 1; }
+  // true for the model problems the trust-region and MMA drivers build around the user's problem: their solver takes
+  // no differenced Hessian-vector products (po_ip_set_hvec_finite_difference)
+  virtual bool isSubproblem() { return false; }
   // sparse constraints (src/ParOptProblem.h:215-262); out / pzw / A are w-sized device vectors.  The
   // defaults serve a problem with a CSR pattern (`csr`, the ParOptSparseProblem form) and are no-ops
   // otherwise.

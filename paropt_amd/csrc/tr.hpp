@@ -79,6 +79,7 @@ class TrustRegionSubproblem : public Problem {
   int evalLinearModel(Vec *step, double *f, double *cons);
 
   // ParOptProblem side, seen by the interior-point solver
+  bool isSubproblem() override { return true; }
   int getVarsAndBounds(Vec *x, Vec *l, Vec *u) override;
   int evalSparseCon(Vec *step, Vec *out) override;
   int addSparseJacobian(double alpha, Vec *x, Vec *px, Vec *out) override;
@@ -238,6 +239,7 @@ class InfeasSubproblem : public Problem {  // :468-650
   enum { CONSTANT_OBJECTIVE = 0, LINEAR_OBJECTIVE = 1, SUBPROBLEM_OBJECTIVE = 2 };
   enum { LINEAR_CONSTRAINT = 0, SUBPROBLEM_CONSTRAINT = 1 };
   InfeasSubproblem(TrustRegionSubproblem *sub_, int objective_, int constraint_);
+  bool isSubproblem() override { return true; }
   int getVarsAndBounds(Vec *x, Vec *l, Vec *u) override { return sub->getVarsAndBounds(x, l, u); }
   int evalObjCon(Vec *step, double *fobj, double *cons) override;
   int evalObjConGradient(Vec *step, Vec *g, Vec **Ac) override;

@@ -296,6 +296,10 @@ SIGNATURES = {
     "po_ip_set_quasi_newton": (C.c_int, [po_ip, po_qn]),
     "po_ip_reset_problem_instance": (C.c_int, [po_ip, po_problem]),
     "po_ip_get_hvec_count": (C.c_int, [po_ip, c_int_p]),
+    "po_ip_set_hvec_finite_difference": (C.c_int, [po_ip, C.c_int, C.c_int, C.c_double]),
+    "po_ip_get_hvec_fd_count": (C.c_int, [po_ip, c_int_p, c_int_p]),
+    "po_ip_get_hvec_fd_step": (C.c_int, [po_ip, c_double_p]),
+    "po_ip_eval_hvec": (C.c_int, [po_ip, c_double_p, po_vec, po_vec, po_vec]),
     "po_ip_reset_design_and_bounds": (C.c_int, [po_ip]),
     "po_ip_check_gradients": (C.c_int, [po_ip, C.c_double, C.POINTER(C.c_char_p)]),
     "po_ip_check_merit_func_gradient": (C.c_int, [po_ip, po_vec, C.c_double, c_double_p, c_double_p]),
