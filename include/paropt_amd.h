@@ -634,6 +634,12 @@ int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, char *report
  * SURVEY.md 8d's algorithmic bytes, the HIP-event time of `reps` back-to-back calls, and beside it the measured
  * ceiling of its stream mix (a trivial kernel moving the same input / output streams).  JSON array in `report`. */
 int po_bench_vec_api(po_ctx ctx, int64_t n, int reps, char *report, int report_len);
+/* One evaluation of the MMA subproblem's dual (see po_mma_dual_eval) at size n with m constraints, on synthetic data,
+ * beside the trivial kernel of its stream mix (2m + 6 streams in; the panel form, form 2, also m + 1 out): HIP-event
+ * averages over `reps` calls in ms.  pass_ms includes the final reduction stage and the host's wait of every call;
+ * gram_ms is the panel form's weighted Gram (0 for form 1), timed apart and not part of pass_ms. */
+int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms, double *gram_ms,
+                      double *ceiling_ms);
 
 /* ---- ParOptTrustRegion over the quadratic / compact-eigenvalue subproblem ------------------------
  * src/ParOptTrustRegion.h:376-480, set up as ParOptOptimizer does for algorithm = "tr"
@@ -799,6 +805,28 @@ int po_mma_get_last_row(po_mma mma, const double **row5);    /* fobj, l1, linfty
 int po_mma_get_history(po_mma mma, const char **text);       /* the paropt.mma table :584-592 */
 typedef int (*po_mma_iteration_fn)(void *user, int mma_iter);
 int po_mma_set_iteration_callback(po_mma mma, po_mma_iteration_fn fn, void *user);
+/* mma_subproblem_solver = dual (no counterpart in the reference, which always runs its interior point on the
+ * subproblem, src/ParOptMMA.cpp:344-352): the separable subproblem of .cpp:523-1010 is solved through its dual in
+ * the m multipliers (Svanberg 1987, section 5).  Counters of the dual solves so far: solves, accepted steps,
+ * evaluations of the dual function (one streaming pass each; also added to subproblem_iter), status (0 converged,
+ * 1 gave up) and max|projected gradient| of the last solve.  Any pointer may be NULL. */
+int po_mma_get_dual_stats(po_mma mma, int *solves, int *iterations, int *evaluations, int *last_status,
+                          double *last_pg);
+/* The CURRENT subproblem (initializeSubProblem .cpp:523-757): borrowed handles of the move limits, the objective's
+ * coefficients and the ncon pairs (p_i, q_i), and b[ncon]; p and q point at arrays of ncon handles owned by the
+ * object, valid until the next call.  Inside the iteration callback of MMA iteration k >= 1 the data, the asymptotes,
+ * x and z still describe subproblem k - 1 and its solution (the callback runs before the asymptotes are updated).
+ * Any pointer may be NULL. */
+int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **p,
+                          const po_vec **q, const double **b);
+/* The dual function of a subproblem given by caller vectors, stand-alone (as po_xgram / po_group_panel are): W,
+ * grad[m] = dW/dlambda and, when hess != NULL, hess[m * m] = minus the Hessian (column-major, symmetric) at lambda[m];
+ * when x / zl / zu are given also the primal point and its bound multipliers.  form: 0 the library's choice, 1 the
+ * Hessian sums fused into the pass (m <= 8), 2 the panel form (columns stored, weighted Gram; m <= 95).
+ * Form 1 with m > 8 is PO_ERR_ARG. */
+int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                     const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
+                     double *grad, double *hess, po_vec x, po_vec zl, po_vec zu);
 
 #ifdef __cplusplus
 }

@@ -2237,7 +2237,8 @@ class TrustRegion:
 
 class MMA:
     """ParOptMMA (reference src/ParOptMMA.h:22-192) with its interior-point sub-solver, assembled the
-    way ParOptOptimizer does for algorithm='mma'.  `options` may mix interior-point and mma_* names."""
+    way ParOptOptimizer does for algorithm='mma'.  `options` may mix interior-point and mma_* names.
+    mma_subproblem_solver='dual' solves the subproblems through their dual instead (getDualStats)."""
 
     def __init__(self, problem, options=None):
         self.problem = problem
@@ -2315,6 +2316,50 @@ class MMA:
         check(lib.po_mma_get_history(self._h, C.byref(t)))
         return t.value.decode()
 
+    def getDualStats(self):
+        """Counters of the dual sub-solver (mma_subproblem_solver='dual'): solves, accepted steps, evaluations of the
+        dual function, and status / max|projected gradient| of the last solve (po_mma_get_dual_stats)."""
+        a, b, e, st, pg = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(lib.po_mma_get_dual_stats(self._h, C.byref(a), C.byref(b), C.byref(e), C.byref(st), C.byref(pg)))
+        return dict(solves=a.value, iterations=b.value, evaluations=e.value, last_status=st.value, last_pg=pg.value)
+
+    def getSubproblem(self):
+        """Borrowed views of the current subproblem (po_mma_get_subproblem): dict with alpha, beta, p0, q0 (PVec),
+        p, q (lists of ncon PVec) and b (numpy copy)."""
+        al, be, p0, q0 = L.po_vec(), L.po_vec(), L.po_vec(), L.po_vec()
+        pp, qq, b = C.POINTER(L.po_vec)(), C.POINTER(L.po_vec)(), L.c_double_p()
+        check(lib.po_mma_get_subproblem(self._h, C.byref(al), C.byref(be), C.byref(p0), C.byref(q0), C.byref(pp),
+                                        C.byref(qq), C.byref(b)))
+        c = self.problem.ncon
+        wrap = lambda h: PVec(self.ctx, handle=L.po_vec(h), owned=False)  # noqa: E731
+        return dict(alpha=wrap(al.value), beta=wrap(be.value), p0=wrap(p0.value), q0=wrap(q0.value),
+                    p=[wrap(pp[i]) for i in range(c)], q=[wrap(qq[i]) for i in range(c)],
+                    b=np.array([b[i] for i in range(c)]))
+
+
+def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessian=True, point=None):
+    """The dual function of an MMA subproblem given by caller vectors (po_mma_dual_eval): returns (W, grad, H) with
+    H = minus the Hessian (None unless `hessian`).  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu)
+    PVecs: also filled with the primal point and its bound multipliers at lam."""
+    m = len(p)
+    if len(q) != m:
+        raise ValueError("mma_dual_eval: p and q must hold the same number of vectors")
+    ba = np.ascontiguousarray(b, dtype=np.float64)
+    la = np.ascontiguousarray(lam, dtype=np.float64)
+    if ba.size != m or la.size != m:
+        raise ValueError("mma_dual_eval: b and lam must hold one entry per constraint")
+    pa_ = (L.po_vec * max(m, 1))(*[v.handle for v in p])
+    qa_ = (L.po_vec * max(m, 1))(*[v.handle for v in q])
+    W = C.c_double()
+    g = np.zeros(max(m, 1))
+    H = np.zeros((m, m)) if hessian else None
+    xs = [v.handle for v in point] if point is not None else [None, None, None]
+    check(lib.po_mma_dual_eval(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle, q0.handle,
+                               pa_, qa_, ba.ctypes.data_as(L.c_double_p), la.ctypes.data_as(L.c_double_p), int(form),
+                               C.byref(W), g.ctypes.data_as(L.c_double_p),
+                               H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1], xs[2]))
+    return W.value, g[:m], H
+
 
 def wgram(d, vecs, rhs_last=False):
     """W = P^T diag(d) P; rhs_last: the last vector is pre-weighted (its row / column are plain dots)."""
@@ -2385,6 +2430,14 @@ def bench_vec_api(ctx, n, reps=10):
     buf = C.create_string_buffer(32768)
     check(lib.po_bench_vec_api(ctx.handle, int(n), int(reps), buf, len(buf)))
     return json.loads(buf.value.decode())
+
+
+def bench_mma_dual(ctx, n, m, form, reps=5):
+    """(pass ms, Gram ms, ms of the trivial kernel of the pass's stream mix) of one evaluation of the MMA dual at
+    (n, m) on synthetic data (po_bench_mma_dual); form 1 fused (m <= 8), 2 panel."""
+    a, g, b = C.c_double(), C.c_double(), C.c_double()
+    check(lib.po_bench_mma_dual(ctx.handle, int(n), int(m), int(form), int(reps), C.byref(a), C.byref(g), C.byref(b)))
+    return a.value, g.value, b.value
 
 
 def bench_stream(x, y, kind, reps=10):

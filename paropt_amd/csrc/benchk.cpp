@@ -494,3 +494,117 @@ extern "C" int po_bench_vec_api(po_ctx ctx, int64_t n, int reps, char *report, i
   for (Vec *v : all) vec_decref(v);
   return rc;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// po_bench_mma_dual: one evaluation of the MMA subproblem's dual (k_mma_dual, mma.hip) at (n, m) beside the trivial
+// kernel of its stream mix -- 2m + 6 streams in and none out for the fused form, m + 1 out for the panel form (whose
+// weighted Gram is timed with it and reported apart).  The stream counts are run-time values here, so the trivial
+// kernel takes its pointer table with run-time bounds (loads in batches of eight).
+// ------------------------------------------------------------------------------------------------------------------
+#include "mma.hpp"
+namespace {
+struct MixTableRt {
+  const double *in[2 * kMaxPanel + 8];
+  double *out[kMaxPanel];
+};
+__global__ void __launch_bounds__(kBlock) trivial_mix_rt_kernel(MixTableRt P, int nin, int nout, int64_t npairs,
+                                                                double *sink) {
+  bk_f64x2 carry = {0.0, 0.0};
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * kBlock) {
+    bk_f64x2 acc = {1.0, 2.0};
+    int j = 0;
+    for (; j + 8 <= nin; j += 8) {
+      bk_f64x2 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = __builtin_nontemporal_load(reinterpret_cast<const bk_f64x2 *>(P.in[j + u] + 2 * q));
+#pragma unroll
+      for (int u = 0; u < 8; u++) acc += v[u];
+    }
+    for (; j < nin; j++) acc += __builtin_nontemporal_load(reinterpret_cast<const bk_f64x2 *>(P.in[j] + 2 * q));
+    for (int o = 0; o < nout; o++) __builtin_nontemporal_store(acc, reinterpret_cast<bk_f64x2 *>(P.out[o] + 2 * q));
+    carry += acc;
+  }
+  if (nout == 0 && carry.x + carry.y == 1.234567e300) sink[0] = carry.x;
+}
+}  // namespace
+
+extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms, double *gram_ms,
+                                 double *ceiling_ms) {
+  if (!ctx || !pass_ms || !gram_ms || !ceiling_ms || n < 2 || reps < 1 || m < 1 || m > kMmaDualMax ||
+      (form != 1 && form != 2) || (form == 1 && m > kMmaDualFused)) {
+    set_error("po_bench_mma_dual: n >= 2, reps >= 1, 1 <= m <= %d, form 1 (m <= %d) or 2", kMmaDualMax, kMmaDualFused);
+    return PO_ERR_ARG;
+  }
+  Ctx *cx = ctx;
+  std::vector<Vec *> all;
+  auto mk = [&](uint64_t aid, double scale, double shift) -> double * {
+    Vec *v = vec_new(cx, n);
+    if (!v) return nullptr;
+    all.push_back(v);
+    (void)k_fill_hash(cx, v->d, n, 13, aid, 0, scale, shift);
+    return v->d;
+  };
+  double *sink = nullptr;
+  auto body = [&]() -> int {
+    PO_HIP(hipMalloc((void **)&sink, 64));
+    // L in (-3, -2) < alpha in (-1, -0.5) < beta in (0.5, 1) < U in (2, 3); P / Q spread over two decades
+    double *L = mk(1, 1.0, -3.0), *U = mk(2, 1.0, 2.0), *al = mk(3, 0.5, -1.0), *be = mk(4, 0.5, 0.5);
+    double *p0 = mk(5, 1.0, 0.01), *q0 = mk(6, 1.0, 0.01);
+    if (!L || !U || !al || !be || !p0 || !q0) return PO_ERR_HIP;
+    std::vector<const double *> p, q;
+    std::vector<double *> G;
+    for (int i = 0; i < m; i++) {
+      const double *a = mk(100 + i, 0.1, 0.0), *b = mk(300 + i, 0.1, 0.0);
+      if (!a || !b) return PO_ERR_HIP;
+      p.push_back(a);
+      q.push_back(b);
+    }
+    double *dvec = nullptr;
+    if (form == 2) {
+      for (int i = 0; i < m; i++) {
+        double *g = mk(500 + i, 0.0, 0.0);
+        if (!g) return PO_ERR_HIP;
+        G.push_back(g);
+      }
+      if (!(dvec = mk(700, 0.0, 0.0))) return PO_ERR_HIP;
+    }
+    std::vector<double> b(m, -1.0), lam(m, 1.0), grad(m), H((size_t)m * m);
+    MmaDualData s{L, U, al, be, p0, q0, p.data(), q.data(), b.data(), m, n};
+    ApiTimer T{cx, "", reps};
+    double W = 0.0, ms = 0.0, ms0 = 0.0;
+    PO_TRY(T.time([&] { return k_mma_dual(cx, s, lam.data(), form, &W, grad.data(), H.data(), G.data(), dvec); }, &ms));
+    *pass_ms = ms;
+    *gram_ms = 0.0;
+    if (form == 2) {  // the Gram alone; the pass is the difference
+      std::vector<const double *> cols(G.begin(), G.end());
+      PO_TRY(T.time([&] { return k_wgram(cx, dvec, cols.data(), m, n, H.data()); }, &ms0));
+      *gram_ms = ms0;
+      *pass_ms = ms - ms0;
+    }
+    MixTableRt P;
+    int nin = 0, nout = 0;
+    for (const double *v : {(const double *)L, (const double *)U, (const double *)al, (const double *)be,
+                            (const double *)p0, (const double *)q0})
+      P.in[nin++] = v;
+    for (int i = 0; i < m; i++) {
+      P.in[nin++] = p[i];
+      P.in[nin++] = q[i];
+    }
+    if (form == 2) {
+      for (int i = 0; i < m; i++) P.out[nout++] = G[i];
+      P.out[nout++] = dvec;
+    }
+    const int grid = grid_for(cx, n, kBpcPanel);
+    PO_TRY(T.time([&]() -> int {
+      hipLaunchKernelGGL(trivial_mix_rt_kernel, dim3(grid), dim3(kBlock), 0, cx->stream, P, nin, nout, n >> 1, sink);
+      PO_HIP(hipGetLastError());
+      return PO_OK;
+    }, ceiling_ms));
+    return PO_OK;
+  };
+  const int rc = body();
+  (void)hipStreamSynchronize(cx->stream);
+  if (sink) (void)hipFree(sink);
+  for (Vec *v : all) vec_decref(v);
+  return rc;
+}

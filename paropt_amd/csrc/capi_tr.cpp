@@ -635,5 +635,111 @@ int po_mma_set_iteration_callback(po_mma mma, po_mma_iteration_fn fn, void *user
   mma->mma->iter_cb_user = user;
   return PO_OK;
 }
+int po_mma_get_dual_stats(po_mma mma, int *solves, int *iterations, int *evaluations, int *last_status,
+                          double *last_pg) {
+  PO_CHECK_PTR(mma);
+  MMA *m = mma->mma;
+  if (solves) *solves = m->dual_solves;
+  if (iterations) *iterations = m->dual_iterations;
+  if (evaluations) *evaluations = m->dual_evaluations;
+  if (last_status) *last_status = m->dual_last_status;
+  if (last_pg) *last_pg = m->dual_last_pg;
+  return PO_OK;
+}
+int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **p,
+                          const po_vec **q, const double **b) {
+  PO_CHECK_PTR(mma);
+  MMA *m = mma->mma;
+  PO_TRY(m->build());
+  if (alpha) *alpha = static_cast<po_vec>(m->alphavec);
+  if (beta) *beta = static_cast<po_vec>(m->betavec);
+  if (p0) *p0 = static_cast<po_vec>(m->p0vec);
+  if (q0) *q0 = static_cast<po_vec>(m->q0vec);
+  mma->p.clear();
+  mma->q.clear();
+  for (Vec *v : m->pivecs) mma->p.push_back(static_cast<po_vec>(v));
+  for (Vec *v : m->qivecs) mma->q.push_back(static_cast<po_vec>(v));
+  if (p) *p = mma->p.data();
+  if (q) *q = mma->q.data();
+  if (b) *b = m->b.data();
+  return PO_OK;
+}
+int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                     const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
+                     double *grad, double *hess, po_vec x, po_vec zl, po_vec zu) {
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(L);
+  PO_CHECK_PTR(W);
+  PO_CHECK_PTR(grad);
+  if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
+    po::set_error("po_mma_dual_eval: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", m, form, kMmaDualMax,
+                  kMmaDualFused);
+    return PO_ERR_ARG;
+  }
+  if (m > 0) {
+    PO_CHECK_PTR(p);
+    PO_CHECK_PTR(q);
+    PO_CHECK_PTR(b);
+    PO_CHECK_PTR(lambda);
+  }
+  const po_vec six[] = {U, alpha, beta, p0, q0};
+  std::vector<const double *> pp, qq;
+  for (po_vec v : six) {
+    PO_CHECK_PTR(v);
+    if (v->ctx != L->ctx || v->n != L->n || L->ctx != ctx) {
+      po::set_error("po_mma_dual_eval: vectors of different layouts");
+      return PO_ERR_ARG;
+    }
+  }
+  const po_vec outs[] = {x, zl, zu};
+  for (po_vec v : outs) {
+    if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
+      po::set_error("po_mma_dual_eval: x, zl and zu are given together, in the layout of L");
+      return PO_ERR_ARG;
+    }
+  }
+  for (int i = 0; i < m; i++) {
+    PO_CHECK_PTR(p[i]);
+    PO_CHECK_PTR(q[i]);
+    if (p[i]->ctx != ctx || q[i]->ctx != ctx || p[i]->n != L->n || q[i]->n != L->n) {
+      po::set_error("po_mma_dual_eval: vectors of different layouts");
+      return PO_ERR_ARG;
+    }
+    pp.push_back(p[i]->d);
+    qq.push_back(q[i]->d);
+  }
+  MmaDualData s;
+  s.L = L->d;
+  s.U = U->d;
+  s.alpha = alpha->d;
+  s.beta = beta->d;
+  s.p0 = p0->d;
+  s.q0 = q0->d;
+  s.p = pp.data();
+  s.q = qq.data();
+  s.b = b;
+  s.m = m;
+  s.n = L->n;
+  if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
+  if (!hess) form = 0;
+  std::vector<Vec *> work;  // the panel form's columns and weights
+  std::vector<double *> G;
+  int rc = PO_OK;
+  if (form == 2) {
+    for (int i = 0; i < m + 1 && rc == PO_OK; i++) {
+      Vec *v = vec_new(ctx, L->n);
+      if (!v) rc = PO_ERR_HIP;
+      else work.push_back(v);
+    }
+    for (int i = 0; i < m && rc == PO_OK; i++) G.push_back(work[i]->d);
+  }
+  if (rc == PO_OK)
+    rc = k_mma_dual(ctx, s, lambda, form, W, grad, hess, form == 2 ? G.data() : nullptr,
+                    form == 2 ? work[m]->d : nullptr);
+  if (rc == PO_OK && x) rc = k_mma_dual_point(ctx, s, lambda, x->d, zl->d, zu->d);
+  if (rc == PO_OK && !work.empty()) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
+  for (Vec *v : work) vec_decref(v);
+  return rc;
+}
 
 }  // extern "C"

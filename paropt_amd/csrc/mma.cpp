@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "mma_dual.hpp"
 #include "tr.hpp"
 
 namespace po {
@@ -17,7 +18,8 @@ MMA::MMA(Problem *p)
       ubvec(nullptr), gvec(nullptr), Lvec(nullptr), Uvec(nullptr), alphavec(nullptr), betavec(nullptr),
       p0vec(nullptr), q0vec(nullptr), rvec(nullptr), zlvec(nullptr), zuvec(nullptr), uinv(nullptr),
       linv(nullptr), cwvec(nullptr), zwvec(nullptr), fobj(0.0), cons(p->ncon, 0.0), b(p->ncon, 0.0),
-      z(p->ncon, 0.0), iter_cb(nullptr), iter_cb_user(nullptr) {
+      z(p->ncon, 0.0), iter_cb(nullptr), iter_cb_user(nullptr), use_dual(false), dual_solves(0), dual_iterations(0),
+      dual_evaluations(0), dual_last_status(0), dual_last_pg(0.0) {
   offset = p->offset;
   nglobal = p->nglobal;
   nwcon = p->nwcon;
@@ -35,6 +37,7 @@ MMA::~MMA() {
   for (Vec *v : Avecs) vec_decref(v);
   for (Vec *v : pivecs) vec_decref(v);
   for (Vec *v : qivecs) vec_decref(v);
+  for (Vec *v : Gvecs) vec_decref(v);
 }
 
 int MMA::allocate() {  // initialize() :131-232
@@ -66,15 +69,83 @@ int MMA::allocate() {  // initialize() :131-232
 }
 
 int MMA::build() {
-  if (ip) return PO_OK;
+  if (ip || xvec) return PO_OK;
   if (m + 1 > kMaxPanel) {
     set_error("MMA: %d constraints exceed the panel width %d", m, kMaxPanel - 1);
     return PO_ERR_ARG;
   }
+  use_dual = std::string(opts.str("mma_subproblem_solver")) == "dual";
   PO_TRY(allocate());
+  if (use_dual) {  // no interior point and none of its 15 + c vectors; uinv / linv serve as the new point / the weights
+    if (m > kMmaDualFused) {
+      for (int i = 0; i < m; i++) {
+        Vec *g = vec_new(ctx, nlocal);
+        if (!g) return PO_ERR_HIP;
+        Gvecs.push_back(g);
+      }
+    }
+    return PO_OK;
+  }
   ip = new InteriorPoint(this);
   ip->options = opts;
   PO_TRY(ip->allocate());
+  return PO_OK;
+}
+
+// ---- the dual sub-solver --------------------------------------------------------------------------
+int MMA::checkDualCovers() {
+  const char *why = nullptr;
+  if (nwcon > 0) why = "sparse constraints are not part of the closed-form primal point";
+  else if (ninequality < m) why = "a dense equality constraint has a free multiplier, which can make P or Q negative";
+  else if (options().integer("mma_use_constraint_linearization")) why = "linearised constraints have no rational dual";
+  if (!why) return PO_OK;
+  set_error("MMA: mma_subproblem_solver = dual does not cover this problem: %s", why);
+  return PO_ERR_ARG;
+}
+
+MmaDualData MMA::dualData() {
+  MmaDualData s;
+  s.L = Lvec->d;
+  s.U = Uvec->d;
+  s.alpha = alphavec->d;
+  s.beta = betavec->d;
+  s.p0 = p0vec->d;
+  s.q0 = q0vec->d;
+  s.p = s.q = nullptr;
+  s.b = b.data();
+  s.m = m;
+  s.n = nlocal;
+  return s;
+}
+
+int MMA::solveDual() {
+  Options &o = options();
+  std::vector<const double *> P, Q;
+  std::vector<double *> G;
+  for (int i = 0; i < m; i++) {
+    P.push_back(pivecs[i]->d);
+    Q.push_back(qivecs[i]->d);
+  }
+  for (Vec *g : Gvecs) G.push_back(g->d);
+  MmaDualData s = dualData();
+  s.p = P.data();
+  s.q = Q.data();
+  const int form = m <= kMmaDualFused ? 1 : 2;
+  std::vector<double> gamma(m, o.real("penalty_gamma")), lambda(z);
+  MmaDualResult res;
+  auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) {
+    return k_mma_dual(ctx, s, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d);
+  };
+  PO_TRY(mma_dual_solve(m, gamma.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"), eval,
+                        lambda.data(), &res));
+  PO_TRY(k_mma_dual_point(ctx, s, lambda.data(), uinv->d, zlvec->d, zuvec->d));
+  z = lambda;
+  subproblem_iter += res.evaluations;
+  dual_solves++;
+  dual_iterations += res.iterations;
+  dual_evaluations += res.evaluations;
+  dual_last_status = res.status;
+  dual_last_pg = res.pg;
   return PO_OK;
 }
 
@@ -187,12 +258,31 @@ void MMA::setMultipliers() {  // :384-400
 }
 
 int MMA::optimize() {  // :318-379
+  const bool want_dual = std::string(options().str("mma_subproblem_solver")) == "dual";
+  if (want_dual) PO_TRY(checkDualCovers());  // refused before anything is allocated or run
   PO_TRY(build());
-  Options &o = ip->options;
+  if (want_dual != use_dual) {
+    set_error("MMA: mma_subproblem_solver cannot change once the solver's vectors exist");
+    return PO_ERR_ARG;
+  }
+  Options &o = options();
   const int max_it = o.integer("mma_max_iterations");
   const double infeas_tol = o.real("mma_infeas_tol"), l1_tol = o.real("mma_l1_tol"),
                linfty_tol = o.real("mma_linfty_tol");
   use_true_mma = o.integer("mma_use_constraint_linearization") ? 0 : 1;
+  if (use_dual) {
+    history.clear();
+    PO_TRY(initializeSubProblem(xvec));
+    for (int i = 0; i < max_it; i++) {
+      PO_TRY(solveDual());
+      PO_TRY(initializeSubProblem(uinv));
+      double infeas = 0.0, l1 = 0.0, linfty = 0.0;  // permuted names, as below
+      PO_TRY(computeKKTError(&infeas, &l1, &linfty));
+      if (infeas < infeas_tol && (l1 < l1_tol || linfty < linfty_tol)) break;
+    }
+    flushHistory();
+    return 0;
+  }
   PO_TRY(o.set("use_diag_hessian", 1));
   PO_TRY(o.set("use_line_search", 0));
   history.clear();

@@ -1,6 +1,8 @@
 // Element-wise kernels of the method of moving asymptotes (reference src/ParOptMMA.cpp:523-1010).
 #include <math.h>
 
+#include <vector>
+
 #include "core.hpp"
 #include "mma.hpp"
 #include "wcon.hpp"
@@ -178,6 +180,343 @@ int k_mma_hdiag(Ctx *c, const double *x, const double *L, const double *U, const
     ct.a[i] = i < nv ? w[i] : 0.0;
   }
   PO_MLAUNCH(mma_hdiag_kernel, grid_for(c, n), x, L, U, pt, qt, ct, nv, n, h);
+  return PO_OK;
+}
+
+// ---- the dual of the separable subproblem (Svanberg 1987, section 5; the subproblem of :523-1010) -----------------
+// For 0 <= lambda <= gamma put P = p0 + sum_i lambda_i p_i, Q = q0 + sum_i lambda_i q_i (> 0).  The minimiser of the
+// Lagrangian is x = clamp((sqrt(P) L + sqrt(Q) U) / (sqrt(P) + sqrt(Q)), alpha, beta), element by element, and with
+// u = 1 / (U - x), l = 1 / (x - L):
+//   W = sum P u + Q l (+ lambda.b on the host),  dW/dlambda_i = sum p_i u + q_i l (+ b_i),
+//   -hess W = sum over the free elements (unclamped x strictly inside (alpha, beta)) of g_i g_k / h,
+//   g_i = p_i u^2 - q_i l^2,  h = 2 (P u^3 + Q l^3).
+// One pass, the primal point in registers.  Per element two square roots and four reciprocals (1 / (sqrt P + sqrt Q),
+// u, l, 1 / h), each formed once.  The element past an odd length (all operands 0.0 there) takes u = l = 1 / h = 0, so
+// that it adds an exact zero to every sum and its stores are zeros.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f64x2 ld_nt(const double *p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(p));
+}
+__device__ __forceinline__ void st_nt(double *p, f64x2 v) {
+  __builtin_nontemporal_store(v, reinterpret_cast<f64x2 *>(p));
+}
+__device__ __forceinline__ f64x2 fma2(double a, f64x2 v, f64x2 acc) {
+  return (f64x2){fma(a, v.x, acc.x), fma(a, v.y, acc.y)};
+}
+// sum of the four products a.x b.x + c.x d.x + a.y b.y + c.y d.y on top of acc, in this fixed order
+__device__ __forceinline__ double dot4(f64x2 a, f64x2 b, f64x2 c, f64x2 d, double acc) {
+  return fma(a.x, b.x, fma(c.x, d.x, fma(a.y, b.y, fma(c.y, d.y, acc))));
+}
+
+struct DualPoint {
+  f64x2 x, u, l, fr;  // fr: 1.0 where the element is free, else 0.0
+};
+__device__ __forceinline__ void dual_point1(double P, double Q, double L, double U, double a, double b, bool live,
+                                            double &x, double &u, double &l, double &fr) {
+  const double sp = sqrt(P), sq = sqrt(Q);
+  const double r = 1.0 / (sp + sq);
+  const double xs = fma(sp, L, sq * U) * r;
+  fr = (live && xs > a && xs < b) ? 1.0 : 0.0;
+  x = fmin(fmax(xs, a), b);
+  u = live ? 1.0 / (U - x) : 0.0;
+  l = live ? 1.0 / (x - L) : 0.0;
+}
+__device__ __forceinline__ DualPoint dual_point(f64x2 P, f64x2 Q, f64x2 L, f64x2 U, f64x2 a, f64x2 b, bool has2) {
+  double x0, u0, l0, f0, x1, u1, l1, f1;
+  dual_point1(P.x, Q.x, L.x, U.x, a.x, b.x, true, x0, u0, l0, f0);
+  dual_point1(P.y, Q.y, L.y, U.y, a.y, b.y, has2, x1, u1, l1, f1);
+  DualPoint t;
+  t.x = (f64x2){x0, x1};
+  t.u = (f64x2){u0, u1};
+  t.l = (f64x2){l0, l1};
+  t.fr = (f64x2){f0, f1};
+  return t;
+}
+// P, Q += sum_{j <= i < j + B} lambda_i (p_i, q_i): 2 B loads in flight, issued back to back before their arithmetic
+template <int B>
+__device__ __forceinline__ void dual_pq_batch(const PtrTable &Pt, const PtrTable &Qt, const CoefTable &lam, int j,
+                                              int64_t q, f64x2 &P, f64x2 &Q) {
+  f64x2 pv[B], qv[B];
+#pragma unroll
+  for (int u = 0; u < B; u++) {
+    pv[u] = ld_nt(Pt.p[j + u] + 2 * q);
+    qv[u] = ld_nt(Qt.p[j + u] + 2 * q);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < B; u++) {
+    P = fma2(lam.a[j + u], pv[u], P);
+    Q = fma2(lam.a[j + u], qv[u], Q);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void dual_pq_all(const PtrTable &Pt, const PtrTable &Qt, const CoefTable &lam, int m,
+                                            int64_t q, f64x2 &P, f64x2 &Q) {
+  int j = 0;
+  for (; j + 8 <= m; j += 8) dual_pq_batch<8>(Pt, Qt, lam, j, q, P, Q);
+  if (j + 4 <= m) {
+    dual_pq_batch<4>(Pt, Qt, lam, j, q, P, Q);
+    j += 4;
+  }
+  if (j + 2 <= m) {
+    dual_pq_batch<2>(Pt, Qt, lam, j, q, P, Q);
+    j += 2;
+  }
+  if (j < m) dual_pq_batch<1>(Pt, Qt, lam, j, q, P, Q);
+}
+
+#ifndef PO_MMA_DUAL_HOLD
+// widest column capacity whose pairs stay in registers (-DPO_MMA_DUAL_HOLD=8 for an A/B: at m = 16 / 32 the pass
+// takes 0.92 / 7.5 ms with 32 and 1.37 / 11.6 ms with 8, n = 10 M / 50 M, profiles/r09_bench_mma_hold_ab.jsonl)
+#define PO_MMA_DUAL_HOLD 32
+#endif
+template <int N>
+__device__ __forceinline__ void dual_block_reduce(double (&a)[N], double *__restrict__ partials, double *sm) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    double v = a[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) sm[wave * N + j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    const int j = threadIdx.x;
+    partials[(size_t)j * gridDim.x + blockIdx.x] = (sm[j] + sm[N + j]) + (sm[2 * N + j] + sm[3 * N + j]);
+  }
+}
+
+// MC: compile-time column capacity (m <= MC; the sums of the columns past m stay 0).  MC <= PO_MMA_DUAL_HOLD (32): the
+// m column pairs of an element pair stay in registers between the formation of P, Q and the sums -- every stream is
+// read once (MC = 32: 390-416 VGPRs, one workgroup per CU, 64 loads of 16 B in flight per lane).  Wider: the columns
+// come in batches of NVB = 8 pairs and are read a second time for the sums, right behind the first (the per-column
+// accumulators are what fills the registers there).
+// MODE 0: slots {W, g[MC]}; 1: ... and the MC (MC + 1) / 2 sums of -hess W (k-major lower triangle, i <= k);
+// 2: slots as 0, and the columns G_i and the weights d = [free] / h are stored for the weighted Gram.
+template <int MC, int MODE>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                    const double *__restrict__ beta, const double *__restrict__ p0, const double *__restrict__ q0,
+                    PtrTable Pt, PtrTable Qt, CoefTable lam, int m, int64_t n, PtrTableW Gt, double *__restrict__ dout,
+                    double *__restrict__ partials) {
+  constexpr bool HOLD = MC <= PO_MMA_DUAL_HOLD;
+  constexpr int NVB = 8;
+  constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
+  constexpr int NS = 1 + MC + NH;
+  static_assert(MODE != 1 || MC <= kMmaDualFused, "the fused Hessian needs the columns in registers");
+  __shared__ double sm[4 * NS];
+  double acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; s++) acc[s] = 0.0;
+  const int64_t npairs = (n + 1) >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+    const bool has2 = 2 * q + 1 < n;
+    const f64x2 Lv = ld_nt(L + 2 * q), Uv = ld_nt(U + 2 * q), av = ld_nt(alpha + 2 * q), bv = ld_nt(beta + 2 * q);
+    f64x2 P = ld_nt(p0 + 2 * q), Q = ld_nt(q0 + 2 * q);
+    f64x2 pv[HOLD ? MC : 1], qv[HOLD ? MC : 1];
+    if (HOLD) {
+#pragma unroll
+      for (int i = 0; i < MC; i++) {
+        pv[i] = (f64x2){0.0, 0.0};
+        qv[i] = (f64x2){0.0, 0.0};
+        if (i < m) {
+          pv[i] = ld_nt(Pt.p[i] + 2 * q);
+          qv[i] = ld_nt(Qt.p[i] + 2 * q);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MC; i++) {
+        if (i < m) {
+          P = fma2(lam.a[i], pv[i], P);
+          Q = fma2(lam.a[i], qv[i], Q);
+        }
+      }
+    } else {
+      dual_pq_all(Pt, Qt, lam, m, q, P, Q);
+    }
+    const DualPoint t = dual_point(P, Q, Lv, Uv, av, bv, has2);
+    acc[0] = dot4(P, t.u, Q, t.l, acc[0]);
+    const f64x2 u2 = t.u * t.u, l2 = t.l * t.l;
+    f64x2 dw = (f64x2){0.0, 0.0};
+    if (MODE != 0) {
+      const f64x2 h = 2.0 * (P * (u2 * t.u) + Q * (l2 * t.l));
+      dw.x = t.fr.x != 0.0 ? 1.0 / h.x : 0.0;
+      dw.y = t.fr.y != 0.0 ? 1.0 / h.y : 0.0;
+      if (MODE == 2) st_nt(dout + 2 * q, dw);
+    }
+    if (HOLD) {
+      f64x2 gv[MODE == 0 ? 1 : MC];
+#pragma unroll
+      for (int i = 0; i < MC; i++) {
+        acc[1 + i] = dot4(pv[i], t.u, qv[i], t.l, acc[1 + i]);
+        if (MODE != 0) {
+          const f64x2 ql = qv[i] * l2;
+          gv[i] = (f64x2){fma(pv[i].x, u2.x, -ql.x), fma(pv[i].y, u2.y, -ql.y)};
+          if (MODE == 2 && i < m) st_nt(Gt.p[i] + 2 * q, gv[i]);
+        }
+      }
+      if (MODE == 1) {
+#pragma unroll
+        for (int k = 0; k < MC; k++) {
+          const f64x2 gd = gv[k] * dw;
+#pragma unroll
+          for (int i = 0; i <= k; i++) {
+            const int s = 1 + MC + k * (k + 1) / 2 + i;
+            acc[s] = fma(gv[i].x, gd.x, fma(gv[i].y, gd.y, acc[s]));
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < MC; j += NVB) {
+        if (j < m) {
+          f64x2 cp[NVB], cq[NVB];
+#pragma unroll
+          for (int v = 0; v < NVB; v++) {
+            cp[v] = (f64x2){0.0, 0.0};
+            cq[v] = (f64x2){0.0, 0.0};
+            if (j + v < m) {
+              cp[v] = ld_nt(Pt.p[j + v] + 2 * q);
+              cq[v] = ld_nt(Qt.p[j + v] + 2 * q);
+            }
+          }
+#pragma unroll
+          for (int v = 0; v < NVB; v++) {
+            acc[1 + j + v] = dot4(cp[v], t.u, cq[v], t.l, acc[1 + j + v]);
+            if (MODE == 2 && j + v < m) {
+              const f64x2 ql = cq[v] * l2;
+              st_nt(Gt.p[j + v] + 2 * q, (f64x2){fma(cp[v].x, u2.x, -ql.x), fma(cp[v].y, u2.y, -ql.y)});
+            }
+          }
+        }
+      }
+    }
+  }
+  dual_block_reduce<NS>(acc, partials, sm);
+}
+
+// one pass at the final lambda: x, and the bound multipliers zl = max(r, 0) where x = alpha, zu = max(-r, 0) where
+// x = beta, r = P u^2 - Q l^2 (0 elsewhere)
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_point_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                          const double *__restrict__ beta, const double *__restrict__ p0,
+                          const double *__restrict__ q0, PtrTable Pt, PtrTable Qt, CoefTable lam, int m, int64_t n,
+                          double *__restrict__ x, double *__restrict__ zl, double *__restrict__ zu) {
+  const int64_t npairs = (n + 1) >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+    const bool has2 = 2 * q + 1 < n;
+    const f64x2 Lv = ld_nt(L + 2 * q), Uv = ld_nt(U + 2 * q), av = ld_nt(alpha + 2 * q), bv = ld_nt(beta + 2 * q);
+    f64x2 P = ld_nt(p0 + 2 * q), Q = ld_nt(q0 + 2 * q);
+    dual_pq_all(Pt, Qt, lam, m, q, P, Q);
+    const DualPoint t = dual_point(P, Q, Lv, Uv, av, bv, has2);
+    const f64x2 ql = Q * (t.l * t.l), u2 = t.u * t.u;
+    const f64x2 r = (f64x2){fma(P.x, u2.x, -ql.x), fma(P.y, u2.y, -ql.y)};
+    f64x2 xo = t.x, lo, up;
+    lo.x = t.x.x == av.x ? fmax(r.x, 0.0) : 0.0;
+    up.x = t.x.x == bv.x ? fmax(-r.x, 0.0) : 0.0;
+    lo.y = (has2 && t.x.y == av.y) ? fmax(r.y, 0.0) : 0.0;
+    up.y = (has2 && t.x.y == bv.y) ? fmax(-r.y, 0.0) : 0.0;
+    if (!has2) xo.y = 0.0;
+    st_nt(x + 2 * q, xo);
+    st_nt(zl + 2 * q, lo);
+    st_nt(zu + 2 * q, up);
+  }
+}
+
+static int dual_tables(const MmaDualData &s, const double *lambda, PtrTable *pt, PtrTable *qt, CoefTable *ct) {
+  if (s.m < 0 || s.m > kMmaDualMax) {
+    set_error("MMA dual: %d constraints outside 0..%d", s.m, kMmaDualMax);
+    return PO_ERR_ARG;
+  }
+  for (int i = 0; i < kMaxPanel; i++) {
+    pt->p[i] = i < s.m ? s.p[i] : nullptr;
+    qt->p[i] = i < s.m ? s.q[i] : nullptr;
+    ct->a[i] = i < s.m ? lambda[i] : 0.0;
+  }
+  return PO_OK;
+}
+
+#define PO_DUAL_LAUNCH(MC, MODE)                                                                               \
+  PO_MLAUNCH((mma_dual_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n, gt, \
+             dvec, c->d_partials)
+#define PO_DUAL_MODES01(MC)                 \
+  do {                                      \
+    if (form == 1) {                        \
+      PO_DUAL_LAUNCH(MC, 1);                \
+    } else if (form == 2) {                 \
+      PO_DUAL_LAUNCH(MC, 2);                \
+    } else {                                \
+      PO_DUAL_LAUNCH(MC, 0);                \
+    }                                       \
+  } while (0)
+#define PO_DUAL_MODES0(MC)                  \
+  do {                                      \
+    if (form == 2) {                        \
+      PO_DUAL_LAUNCH(MC, 2);                \
+    } else {                                \
+      PO_DUAL_LAUNCH(MC, 0);                \
+    }                                       \
+  } while (0)
+
+int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, double *W, double *grad, double *H,
+               double *const *G, double *dvec) {
+  const int m = s.m;
+  PtrTable pt, qt;
+  CoefTable ct;
+  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  if (form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
+    set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
+    return PO_ERR_ARG;
+  }
+  if (form != 0 && !H) form = 0;
+  if (form == 2 && (!G || !dvec)) {
+    set_error("MMA dual: the panel form needs its %d column vectors and the weight vector", m);
+    return PO_ERR_ARG;
+  }
+  PtrTableW gt;
+  for (int i = 0; i < kMaxPanel; i++) gt.p[i] = (form == 2 && i < m) ? G[i] : nullptr;
+  const int mc = m <= 2 ? 2 : m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : m <= 32 ? 32 : m <= 64 ? 64 : 96;
+  const int nh = form == 1 ? mc * (mc + 1) / 2 : 0, ns = 1 + mc + nh;
+  count_bytes(c, 2 * m + 6 + (form == 2 ? m + 1 : 0), s.n);
+  // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  PO_TRY(ensure_partials(c, (size_t)grid * ns));
+  switch (mc) {
+    case 2: PO_DUAL_MODES01(2); break;
+    case 4: PO_DUAL_MODES01(4); break;
+    case 8: PO_DUAL_MODES01(8); break;
+    case 16: PO_DUAL_MODES0(16); break;
+    case 32: PO_DUAL_MODES0(32); break;
+    case 64: PO_DUAL_MODES0(64); break;
+    default: PO_DUAL_MODES0(96); break;
+  }
+  double sums[1 + 96 + 36];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
+  double w = sums[0];
+  for (int i = 0; i < m; i++) {
+    w += lambda[i] * s.b[i];
+    grad[i] = sums[1 + i] + s.b[i];
+  }
+  *W = w;
+  if (form == 1) {
+    for (int k = 0; k < m; k++)
+      for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
+  } else if (form == 2 && m > 0) {
+    std::vector<const double *> cols(G, G + m);
+    PO_TRY(k_wgram(c, dvec, cols.data(), m, s.n, H));
+  }
+  return PO_OK;
+}
+
+int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu) {
+  PtrTable pt, qt;
+  CoefTable ct;
+  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  if (s.n <= 0) return PO_OK;
+  count_bytes(c, 2 * s.m + 6 + 3, s.n);
+  PO_MLAUNCH(mma_dual_point_kernel, grid_for(c, s.n, kBpcPanel), s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct,
+             s.m, s.n, x, zl, zu);
   return PO_OK;
 }
 

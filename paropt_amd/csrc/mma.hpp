@@ -31,6 +31,26 @@ int k_mma_grad(Ctx *c, const double *x, const double *L, const double *U, const 
 int k_mma_hdiag(Ctx *c, const double *x, const double *L, const double *U, const double *const *P,
                 const double *const *Q, const double *w, int nv, int64_t n, double *h);
 
+
+// ---- the dual of the separable subproblem (mma.hip) ----------------------------------------------------------------
+constexpr int kMmaDualFused = 8;  // M_F: widest m whose m (m + 1) / 2 Hessian sums ride in the pass (no scratch, no spill)
+constexpr int kMmaDualMax = kMaxPanel - 1;
+struct MmaDualData {  // one subproblem: device pointers of n elements, m column pairs, b[m] on the host
+  const double *L, *U, *alpha, *beta, *p0, *q0;
+  const double *const *p, *const *q;
+  const double *b;
+  int m;
+  int64_t n;
+};
+// W(lambda), grad[m] and, when H != nullptr, H[m * m] = -hess W (symmetric, column-major); collective.
+// form 0: value and gradient only; 1: the Hessian sums in the same pass (m <= kMmaDualFused); 2: the pass stores the
+// columns G_i = p_i u^2 - q_i l^2 in G[i] and the weights [free] / h in dvec, H = G^T diag(dvec) G by k_wgram.
+// W and grad have the same bits in every form.
+int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, double *W, double *grad, double *H,
+               double *const *G, double *dvec);
+// the primal point and the bound multipliers at lambda
+int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu);
+
 typedef int (*MmaIterationFn)(void *user, int iter);
 
 class MMA : public Problem {
@@ -86,6 +106,12 @@ class MMA : public Problem {
   MmaIterationFn iter_cb;
   void *iter_cb_user;
   double last_row[5];  // fobj, l1, linfty, l1_lambda, infeas of the last table row
+  // mma_subproblem_solver = dual: the subproblem is solved through its dual (mma_dual.hpp) -- no InteriorPoint object
+  bool use_dual;
+  std::vector<Vec *> Gvecs;  // the m columns of the panel form (m > kMmaDualFused only)
+  int dual_solves, dual_iterations, dual_evaluations, dual_last_status;
+  double dual_last_pg;
+  MmaDualData dualData();
 
  private:
   MmaParams params() ;
@@ -93,6 +119,8 @@ class MMA : public Problem {
   int initializeSubProblem(Vec *xv);
   int computeKKTError(double *l1, double *linfty, double *infeas);
   void setMultipliers();
+  int checkDualCovers();
+  int solveDual();
   void flushHistory();
 };
 
@@ -100,4 +128,5 @@ class MMA : public Problem {
 
 struct po_mma_s {
   po::MMA *mma;
+  std::vector<po_vec> p, q;  // the handle arrays po_mma_get_subproblem hands out
 };

@@ -211,6 +211,19 @@ void Options::addMMADefaults() {
   F("mma_eps_regularization", 1e-5, 0.0, 1e20);
   F("mma_delta_regularization", 1e-3, 0.0, 1e20);
   F("mma_move_limit", 0.2, 0.0, 1e20);
+  // the sub-solver (no counterpart in the reference, which always takes the interior point: src/ParOptMMA.cpp:344-352)
+  Entry sub;
+  sub.type = ENUM;
+  sub.s = "interior_point";
+  sub.choices = {"interior_point", "dual"};
+  e["mma_subproblem_solver"] = sub;
+  F("mma_dual_tol", 1e-8, 0.0, 1e20);
+  Entry dit;
+  dit.type = INT;
+  dit.i = 200;
+  dit.ilo = 1;
+  dit.ihi = 1000000;
+  e["mma_dual_max_iterations"] = dit;
 }
 
 int Options::set(const char *name, const char *value) {

@@ -393,6 +393,13 @@ SIGNATURES = {
     "po_mma_get_last_row": (C.c_int, [po_mma, C.POINTER(c_double_p)]),
     "po_mma_get_history": (C.c_int, [po_mma, C.POINTER(C.c_char_p)]),
     "po_mma_set_iteration_callback": (C.c_int, [po_mma, TR_ITER_FN, C.c_void_p]),
+    "po_mma_get_dual_stats": (C.c_int, [po_mma, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]),
+    "po_mma_get_subproblem": (
+        C.c_int, [po_mma] + [C.POINTER(po_vec)] * 4 + [C.POINTER(C.POINTER(po_vec))] * 2 + [C.POINTER(c_double_p)]),
+    "po_mma_dual_eval": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, c_double_p, C.c_int,
+                                                                              c_double_p, c_double_p, c_double_p]
+        + [po_vec] * 3),
     "po_wgram": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
     "po_xgram": (C.c_int, [vec_p, vec_p, C.c_int, c_double_p]),
     "po_wgram_with_rhs": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
@@ -407,6 +414,7 @@ SIGNATURES = {
     "po_bench_kernels": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "po_bench_stream": (C.c_int, [po_vec, po_vec, C.c_int, C.c_int, c_double_p]),
     "po_bench_vec_api": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
+    "po_bench_mma_dual": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
