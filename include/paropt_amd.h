@@ -640,6 +640,10 @@ int po_bench_vec_api(po_ctx ctx, int64_t n, int reps, char *report, int report_l
  * gram_ms is the panel form's weighted Gram (0 for form 1), timed apart and not part of pass_ms. */
 int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms, double *gram_ms,
                       double *ceiling_ms);
+/* The same pass and its rho form (see po_mma_dual_eval_rho; 2m + 7 streams in) alternating in one call, two readings
+ * of each: pass_ms2[2], rho_ms2[2]; ceiling_ms is the trivial kernel of the rho form's mix. */
+int po_bench_mma_dual_rho(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms2, double *rho_ms2,
+                          double *gram_ms, double *ceiling_ms);
 
 /* ---- ParOptTrustRegion over the quadratic / compact-eigenvalue subproblem ------------------------
  * src/ParOptTrustRegion.h:376-480, set up as ParOptOptimizer does for algorithm = "tr"
@@ -827,6 +831,29 @@ int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, p
 int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
                      const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
                      double *grad, double *hess, po_vec x, po_vec zl, po_vec zu);
+/* mma_globalization = conservative (no counterpart in the reference; Svanberg 2002 / 2007, dual sub-solver only):
+ * every approximation carries rho_i d(x), d(x) = sum (x - xk)^2 / ((U - x)(x - L)), and a subproblem solution is
+ * accepted only where the problem's own values lie under the approximations; otherwise the rho_i of the violated
+ * functions are raised and the subproblem is solved again (no gradient evaluation).  Counters so far: raises in
+ * total, in the last MMA iteration and the most in one iteration, iterations that spent mma_gcmma_max_inner raises
+ * (their point was taken anyway), and rho[ncon + 1] (borrowed: the objective's, then one per constraint) of the last
+ * accepted iteration.  Any pointer may be NULL. */
+int po_mma_get_globalization_stats(po_mma mma, int *inner_total, int *inner_last, int *inner_max, int *cap_hits,
+                                   const double **rho);
+/* po_mma_dual_eval for the conservative approximations around the expansion point xk with rho[m + 1]: W, grad, hess
+ * as there and, when D != NULL, D = d(x) at the primal point.  With every rho_i = 0 the bits of po_mma_dual_eval. */
+int po_mma_dual_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                         const po_vec *p, const po_vec *q, const double *b, const double *lambda, po_vec xk,
+                         const double *rho, int form, double *W, double *grad, double *hess, double *D);
+/* The point pass of an inner iteration, stand-alone: the primal point x and its bound multipliers zl, zu at lambda[m]
+ * for the same approximations, and sums[m + 2] = {Delta_0, Delta_1..m, D}, Delta_i = f~_i(x) - f~_i(xk) without
+ * the rho term (0: the objective's coefficients p0, q0; i: the pair p_i, q_i), D = d(x). */
+int po_mma_gcmma_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                       const po_vec *p, const po_vec *q, const double *lambda, po_vec xk, const double *rho, po_vec x,
+                       po_vec zl, po_vec zu, double *sums);
+/* The sums behind the start values of rho, stand-alone: sums[m + 1] = {sum_j |g_j| (U_j - L_j), sum_j |A_i,j| (U_j -
+ * L_j)}, one read-only pass; rho_i = max(mma_gcmma_rho_init / n * sums[i], mma_gcmma_rho_min) on the host. */
+int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const po_vec *A, double *sums);
 
 #ifdef __cplusplus
 }

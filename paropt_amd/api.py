@@ -2323,6 +2323,16 @@ class MMA:
         check(lib.po_mma_get_dual_stats(self._h, C.byref(a), C.byref(b), C.byref(e), C.byref(st), C.byref(pg)))
         return dict(solves=a.value, iterations=b.value, evaluations=e.value, last_status=st.value, last_pg=pg.value)
 
+    def getGlobalizationStats(self):
+        """Counters of mma_globalization='conservative' (po_mma_get_globalization_stats): raises of rho in total, in
+        the last MMA iteration and the most in one, iterations that hit mma_gcmma_max_inner, and rho (ncon + 1 values,
+        the objective's first) of the last accepted iteration."""
+        a, b, mx, cap, rho = C.c_int(), C.c_int(), C.c_int(), C.c_int(), L.c_double_p()
+        check(lib.po_mma_get_globalization_stats(self._h, C.byref(a), C.byref(b), C.byref(mx), C.byref(cap),
+                                                 C.byref(rho)))
+        return dict(inner_total=a.value, inner_last=b.value, inner_max=mx.value, cap_hits=cap.value,
+                    rho=np.array([rho[i] for i in range(self.problem.ncon + 1)]))
+
     def getSubproblem(self):
         """Borrowed views of the current subproblem (po_mma_get_subproblem): dict with alpha, beta, p0, q0 (PVec),
         p, q (lists of ncon PVec) and b (numpy copy)."""
@@ -2337,10 +2347,18 @@ class MMA:
                     b=np.array([b[i] for i in range(c)]))
 
 
-def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessian=True, point=None):
+def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessian=True, point=None, xk=None, rho=None):
     """The dual function of an MMA subproblem given by caller vectors (po_mma_dual_eval): returns (W, grad, H) with
     H = minus the Hessian (None unless `hessian`).  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu)
-    PVecs: also filled with the primal point and its bound multipliers at lam."""
+    PVecs: also filled with the primal point and its bound multipliers at lam.
+    xk (PVec) and rho (ncon + 1 values) given: the conservative approximations f~_i + rho_i d around xk
+    (po_mma_dual_eval_rho); returns (W, grad, H, D) with D = d at the primal point."""
+    if (xk is None) != (rho is None):
+        raise ValueError("mma_dual_eval: xk and rho are given together")
+    if xk is not None:
+        if point is not None:
+            raise ValueError("mma_dual_eval: the point of the rho form comes from mma_gcmma_point")
+        return _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho)
     m = len(p)
     if len(q) != m:
         raise ValueError("mma_dual_eval: p and q must hold the same number of vectors")
@@ -2359,6 +2377,58 @@ def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessia
                                C.byref(W), g.ctypes.data_as(L.c_double_p),
                                H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1], xs[2]))
     return W.value, g[:m], H
+
+
+def _mma_tables(p, q, lam, rho):
+    m = len(p)
+    if len(q) != m:
+        raise ValueError("p and q must hold the same number of vectors")
+    la = np.ascontiguousarray(lam, dtype=np.float64)
+    ra = np.ascontiguousarray(rho, dtype=np.float64)
+    if la.size != m or ra.size != m + 1:
+        raise ValueError("lam holds one entry per constraint, rho one more")
+    pa_ = (L.po_vec * max(m, 1))(*[v.handle for v in p])
+    qa_ = (L.po_vec * max(m, 1))(*[v.handle for v in q])
+    return m, pa_, qa_, la, ra
+
+
+def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho):
+    m, pa_, qa_, la, ra = _mma_tables(p, q, lam, rho)
+    ba = np.ascontiguousarray(b, dtype=np.float64)
+    if ba.size != m:
+        raise ValueError("mma_dual_eval: b must hold one entry per constraint")
+    W, D = C.c_double(), C.c_double()
+    g = np.zeros(max(m, 1))
+    H = np.zeros((m, m)) if hessian else None
+    check(lib.po_mma_dual_eval_rho(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle,
+                                   q0.handle, pa_, qa_, ba.ctypes.data_as(L.c_double_p),
+                                   la.ctypes.data_as(L.c_double_p), xk.handle, ra.ctypes.data_as(L.c_double_p),
+                                   int(form), C.byref(W), g.ctypes.data_as(L.c_double_p),
+                                   H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, C.byref(D)))
+    return W.value, g[:m], H, D.value
+
+
+def mma_gcmma_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, xk, rho, point):
+    """The point pass of a conservative inner iteration (po_mma_gcmma_point): fills point = (x, zl, zu) PVecs at lam
+    and returns the m + 2 sums [Delta_0, Delta_1..m, D]."""
+    m, pa_, qa_, la, ra = _mma_tables(p, q, lam, rho)
+    sums = np.zeros(m + 2)
+    check(lib.po_mma_gcmma_point(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle, q0.handle,
+                                 pa_, qa_, la.ctypes.data_as(L.c_double_p), xk.handle,
+                                 ra.ctypes.data_as(L.c_double_p), point[0].handle, point[1].handle, point[2].handle,
+                                 sums.ctypes.data_as(L.c_double_p)))
+    return sums
+
+
+def mma_gcmma_rho_sums(ctx, Lo, Up, g, A):
+    """The m + 1 sums behind the start values of rho (po_mma_gcmma_rho_sums): sum |g| (U - L), then sum |A_i| (U - L)
+    per constraint."""
+    m = len(A)
+    arr = (L.po_vec * max(m, 1))(*[v.handle for v in A])
+    sums = np.zeros(m + 1)
+    check(lib.po_mma_gcmma_rho_sums(ctx.handle, m, Lo.handle, Up.handle, g.handle, arr,
+                                    sums.ctypes.data_as(L.c_double_p)))
+    return sums
 
 
 def wgram(d, vecs, rhs_last=False):
@@ -2438,6 +2508,14 @@ def bench_mma_dual(ctx, n, m, form, reps=5):
     a, g, b = C.c_double(), C.c_double(), C.c_double()
     check(lib.po_bench_mma_dual(ctx.handle, int(n), int(m), int(form), int(reps), C.byref(a), C.byref(g), C.byref(b)))
     return a.value, g.value, b.value
+
+
+def bench_mma_dual_rho(ctx, n, m, form, reps=5):
+    """The dual pass and its rho form alternating in one call (po_bench_mma_dual_rho): ([plain ms] * 2, [rho ms] * 2,
+    Gram ms, ms of the trivial kernel of the rho form's stream mix, 2m + 7 in)."""
+    a, r, g, b = (C.c_double * 2)(), (C.c_double * 2)(), C.c_double(), C.c_double()
+    check(lib.po_bench_mma_dual_rho(ctx.handle, int(n), int(m), int(form), int(reps), a, r, C.byref(g), C.byref(b)))
+    return list(a), list(r), g.value, b.value
 
 
 def bench_stream(x, y, kind, reps=10):

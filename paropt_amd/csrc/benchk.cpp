@@ -528,11 +528,13 @@ __global__ void __launch_bounds__(kBlock) trivial_mix_rt_kernel(MixTableRt P, in
 }
 }  // namespace
 
-extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms, double *gram_ms,
-                                 double *ceiling_ms) {
+// rho_ms == nullptr: the plain pass, pass_ms[1].  Else the plain pass and the rho form (one more stream, xk)
+// alternate, two readings each: pass_ms[2], rho_ms[2]; the trivial kernel then moves the rho form's mix.
+static int bench_mma_dual(const char *who, po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms,
+                          double *rho_ms, double *gram_ms, double *ceiling_ms) {
   if (!ctx || !pass_ms || !gram_ms || !ceiling_ms || n < 2 || reps < 1 || m < 1 || m > kMmaDualMax ||
       (form != 1 && form != 2) || (form == 1 && m > kMmaDualFused)) {
-    set_error("po_bench_mma_dual: n >= 2, reps >= 1, 1 <= m <= %d, form 1 (m <= %d) or 2", kMmaDualMax, kMmaDualFused);
+    set_error("%s: n >= 2, reps >= 1, 1 <= m <= %d, form 1 (m <= %d) or 2", who, kMmaDualMax, kMmaDualFused);
     return PO_ERR_ARG;
   }
   Ctx *cx = ctx;
@@ -551,6 +553,8 @@ extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int rep
     double *L = mk(1, 1.0, -3.0), *U = mk(2, 1.0, 2.0), *al = mk(3, 0.5, -1.0), *be = mk(4, 0.5, 0.5);
     double *p0 = mk(5, 1.0, 0.01), *q0 = mk(6, 1.0, 0.01);
     if (!L || !U || !al || !be || !p0 || !q0) return PO_ERR_HIP;
+    double *xk = nullptr;  // the expansion point in (-0.5, 0.5)
+    if (rho_ms && !(xk = mk(7, 1.0, -0.5))) return PO_ERR_HIP;
     std::vector<const double *> p, q;
     std::vector<double *> G;
     for (int i = 0; i < m; i++) {
@@ -568,24 +572,34 @@ extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int rep
       }
       if (!(dvec = mk(700, 0.0, 0.0))) return PO_ERR_HIP;
     }
-    std::vector<double> b(m, -1.0), lam(m, 1.0), grad(m), H((size_t)m * m);
+    std::vector<double> b(m, -1.0), lam(m, 1.0), grad(m), H((size_t)m * m), rho(m + 1, 0.01);
     MmaDualData s{L, U, al, be, p0, q0, p.data(), q.data(), b.data(), m, n};
+    const MmaDualRho r{xk, rho.data()};
     ApiTimer T{cx, "", reps};
-    double W = 0.0, ms = 0.0, ms0 = 0.0;
-    PO_TRY(T.time([&] { return k_mma_dual(cx, s, lam.data(), form, &W, grad.data(), H.data(), G.data(), dvec); }, &ms));
-    *pass_ms = ms;
+    double W = 0.0, ms0 = 0.0;
+    for (int k = 0; k < (rho_ms ? 2 : 1); k++) {
+      PO_TRY(T.time([&] { return k_mma_dual(cx, s, lam.data(), form, &W, grad.data(), H.data(), G.data(), dvec); },
+                    &pass_ms[k]));
+      if (rho_ms)
+        PO_TRY(T.time([&] { return k_mma_dual(cx, s, lam.data(), form, &W, grad.data(), H.data(), G.data(), dvec, &r); },
+                      &rho_ms[k]));
+    }
     *gram_ms = 0.0;
     if (form == 2) {  // the Gram alone; the pass is the difference
       std::vector<const double *> cols(G.begin(), G.end());
       PO_TRY(T.time([&] { return k_wgram(cx, dvec, cols.data(), m, n, H.data()); }, &ms0));
       *gram_ms = ms0;
-      *pass_ms = ms - ms0;
+      for (int k = 0; k < (rho_ms ? 2 : 1); k++) {
+        pass_ms[k] -= ms0;
+        if (rho_ms) rho_ms[k] -= ms0;
+      }
     }
     MixTableRt P;
     int nin = 0, nout = 0;
     for (const double *v : {(const double *)L, (const double *)U, (const double *)al, (const double *)be,
                             (const double *)p0, (const double *)q0})
       P.in[nin++] = v;
+    if (xk) P.in[nin++] = xk;
     for (int i = 0; i < m; i++) {
       P.in[nin++] = p[i];
       P.in[nin++] = q[i];
@@ -607,4 +621,16 @@ extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int rep
   if (sink) (void)hipFree(sink);
   for (Vec *v : all) vec_decref(v);
   return rc;
+}
+extern "C" int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms, double *gram_ms,
+                                 double *ceiling_ms) {
+  return bench_mma_dual("po_bench_mma_dual", ctx, n, m, form, reps, pass_ms, nullptr, gram_ms, ceiling_ms);
+}
+extern "C" int po_bench_mma_dual_rho(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms2,
+                                     double *rho_ms2, double *gram_ms, double *ceiling_ms) {
+  if (!rho_ms2) {
+    set_error("po_bench_mma_dual_rho: rho_ms2 is NULL");
+    return PO_ERR_ARG;
+  }
+  return bench_mma_dual("po_bench_mma_dual_rho", ctx, n, m, form, reps, pass_ms2, rho_ms2, gram_ms, ceiling_ms);
 }

@@ -664,16 +664,20 @@ int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, p
   if (b) *b = m->b.data();
   return PO_OK;
 }
-int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                     const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
-                     double *grad, double *hess, po_vec x, po_vec zl, po_vec zu) {
+// the shared body of po_mma_dual_eval / po_mma_dual_eval_rho / po_mma_gcmma_point: argument checks, the tables and the
+// panel form's work vectors
+static int mma_dual_entry(const char *who, po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0,
+                          po_vec q0, const po_vec *p, const po_vec *q, const double *b, const double *lambda,
+                          po_vec xk, const double *rho, int form, double *W, double *grad, double *hess, double *D,
+                          po_vec x, po_vec zl, po_vec zu, double *point_sums) {
   PO_CHECK_PTR(ctx);
   PO_CHECK_PTR(L);
-  PO_CHECK_PTR(W);
-  PO_CHECK_PTR(grad);
+  if (!point_sums) {
+    PO_CHECK_PTR(W);
+    PO_CHECK_PTR(grad);
+  }
   if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    po::set_error("po_mma_dual_eval: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", m, form, kMmaDualMax,
-                  kMmaDualFused);
+    po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax, kMmaDualFused);
     return PO_ERR_ARG;
   }
   if (m > 0) {
@@ -682,19 +686,19 @@ int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec
     PO_CHECK_PTR(b);
     PO_CHECK_PTR(lambda);
   }
-  const po_vec six[] = {U, alpha, beta, p0, q0};
+  const po_vec six[] = {U, alpha, beta, p0, q0, rho ? xk : U};
   std::vector<const double *> pp, qq;
   for (po_vec v : six) {
     PO_CHECK_PTR(v);
     if (v->ctx != L->ctx || v->n != L->n || L->ctx != ctx) {
-      po::set_error("po_mma_dual_eval: vectors of different layouts");
+      po::set_error("%s: vectors of different layouts", who);
       return PO_ERR_ARG;
     }
   }
   const po_vec outs[] = {x, zl, zu};
   for (po_vec v : outs) {
     if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
-      po::set_error("po_mma_dual_eval: x, zl and zu are given together, in the layout of L");
+      po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
       return PO_ERR_ARG;
     }
   }
@@ -702,7 +706,7 @@ int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec
     PO_CHECK_PTR(p[i]);
     PO_CHECK_PTR(q[i]);
     if (p[i]->ctx != ctx || q[i]->ctx != ctx || p[i]->n != L->n || q[i]->n != L->n) {
-      po::set_error("po_mma_dual_eval: vectors of different layouts");
+      po::set_error("%s: vectors of different layouts", who);
       return PO_ERR_ARG;
     }
     pp.push_back(p[i]->d);
@@ -720,6 +724,8 @@ int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec
   s.b = b;
   s.m = m;
   s.n = L->n;
+  const MmaDualRho r{rho ? xk->d : nullptr, rho};
+  if (point_sums) return k_mma_gcmma_point(ctx, s, r, lambda, x->d, zl->d, zu->d, point_sums);
   if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
   if (!hess) form = 0;
   std::vector<Vec *> work;  // the panel form's columns and weights
@@ -735,11 +741,72 @@ int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec
   }
   if (rc == PO_OK)
     rc = k_mma_dual(ctx, s, lambda, form, W, grad, hess, form == 2 ? G.data() : nullptr,
-                    form == 2 ? work[m]->d : nullptr);
+                    form == 2 ? work[m]->d : nullptr, rho ? &r : nullptr, D);
   if (rc == PO_OK && x) rc = k_mma_dual_point(ctx, s, lambda, x->d, zl->d, zu->d);
   if (rc == PO_OK && !work.empty()) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
   for (Vec *v : work) vec_decref(v);
   return rc;
+}
+int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                     const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
+                     double *grad, double *hess, po_vec x, po_vec zl, po_vec zu) {
+  return mma_dual_entry("po_mma_dual_eval", ctx, m, L, U, alpha, beta, p0, q0, p, q, b, lambda, nullptr, nullptr,
+                        form, W, grad, hess, nullptr, x, zl, zu, nullptr);
+}
+int po_mma_dual_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                         const po_vec *p, const po_vec *q, const double *b, const double *lambda, po_vec xk,
+                         const double *rho, int form, double *W, double *grad, double *hess, double *D) {
+  PO_CHECK_PTR(xk);
+  PO_CHECK_PTR(rho);
+  return mma_dual_entry("po_mma_dual_eval_rho", ctx, m, L, U, alpha, beta, p0, q0, p, q, b, lambda, xk, rho, form, W,
+                        grad, hess, D, nullptr, nullptr, nullptr, nullptr);
+}
+int po_mma_gcmma_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                       const po_vec *p, const po_vec *q, const double *lambda, po_vec xk, const double *rho, po_vec x,
+                       po_vec zl, po_vec zu, double *sums) {
+  PO_CHECK_PTR(xk);
+  PO_CHECK_PTR(rho);
+  PO_CHECK_PTR(x);
+  PO_CHECK_PTR(sums);
+  const double none = 0.0;  // (the point pass does not read b)
+  return mma_dual_entry("po_mma_gcmma_point", ctx, m, L, U, alpha, beta, p0, q0, p, q, &none, lambda, xk, rho, 0,
+                        nullptr, nullptr, nullptr, nullptr, x, zl, zu, sums);
+}
+int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const po_vec *A, double *sums) {
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(L);
+  PO_CHECK_PTR(U);
+  PO_CHECK_PTR(g);
+  PO_CHECK_PTR(sums);
+  if (m < 0 || m > kMmaDualMax) {
+    po::set_error("po_mma_gcmma_rho_sums: m = %d outside 0..%d", m, kMmaDualMax);
+    return PO_ERR_ARG;
+  }
+  if (m > 0) PO_CHECK_PTR(A);
+  std::vector<const double *> cols;
+  for (int i = 0; i < m; i++) {
+    PO_CHECK_PTR(A[i]);
+    cols.push_back(A[i]->d);
+  }
+  for (int i = -2; i < m; i++) {
+    const po_vec v = i == -2 ? U : i == -1 ? g : A[i];
+    if (v->ctx != ctx || L->ctx != ctx || v->n != L->n) {
+      po::set_error("po_mma_gcmma_rho_sums: vectors of different layouts");
+      return PO_ERR_ARG;
+    }
+  }
+  return k_mma_gcmma_rho_sums(ctx, L->d, U->d, g->d, cols.data(), m, L->n, sums);
+}
+int po_mma_get_globalization_stats(po_mma mma, int *inner_total, int *inner_last, int *inner_max, int *cap_hits,
+                                   const double **rho) {
+  PO_CHECK_PTR(mma);
+  MMA *m = mma->mma;
+  if (inner_total) *inner_total = m->gcmma_inner_total;
+  if (inner_last) *inner_last = m->gcmma_inner_last;
+  if (inner_max) *inner_max = m->gcmma_inner_max;
+  if (cap_hits) *cap_hits = m->gcmma_cap_hits;
+  if (rho) *rho = m->gcmma_rho.data();
+  return PO_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "mma_dual.hpp"
+#include "mma_gcmma.hpp"
 #include "tr.hpp"
 
 namespace po {
@@ -19,7 +20,9 @@ MMA::MMA(Problem *p)
       p0vec(nullptr), q0vec(nullptr), rvec(nullptr), zlvec(nullptr), zuvec(nullptr), uinv(nullptr),
       linv(nullptr), cwvec(nullptr), zwvec(nullptr), fobj(0.0), cons(p->ncon, 0.0), b(p->ncon, 0.0),
       z(p->ncon, 0.0), iter_cb(nullptr), iter_cb_user(nullptr), use_dual(false), dual_solves(0), dual_iterations(0),
-      dual_evaluations(0), dual_last_status(0), dual_last_pg(0.0) {
+      dual_evaluations(0), dual_last_status(0), dual_last_pg(0.0), gcmma_inner_total(0), gcmma_inner_last(0),
+      gcmma_inner_max(0), gcmma_cap_hits(0), gcmma_rho(p->ncon + 1, 0.0), have_trial_values(false), fobj_trial(0.0),
+      cons_trial(p->ncon, 0.0) {
   offset = p->offset;
   nglobal = p->nglobal;
   nwcon = p->nwcon;
@@ -118,7 +121,9 @@ MmaDualData MMA::dualData() {
   return s;
 }
 
-int MMA::solveDual() {
+// rho != nullptr: the subproblem in the conservative approximations f~_i + rho_i d around xvec; point_sums[m + 2] then
+// receives {Delta_0..m, D} of the solution (mma_gcmma.hpp)
+int MMA::solveDual(const double *rho, double *point_sums) {
   Options &o = options();
   std::vector<const double *> P, Q;
   std::vector<double *> G;
@@ -133,12 +138,15 @@ int MMA::solveDual() {
   const int form = m <= kMmaDualFused ? 1 : 2;
   std::vector<double> gamma(m, o.real("penalty_gamma")), lambda(z);
   MmaDualResult res;
+  const MmaDualRho r{xvec->d, rho};
   auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) {
-    return k_mma_dual(ctx, s, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d);
+    return k_mma_dual(ctx, s, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d,
+                      rho ? &r : nullptr);
   };
   PO_TRY(mma_dual_solve(m, gamma.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"), eval,
                         lambda.data(), &res));
-  PO_TRY(k_mma_dual_point(ctx, s, lambda.data(), uinv->d, zlvec->d, zuvec->d));
+  if (rho) PO_TRY(k_mma_gcmma_point(ctx, s, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
+  else PO_TRY(k_mma_dual_point(ctx, s, lambda.data(), uinv->d, zlvec->d, zuvec->d));
   z = lambda;
   subproblem_iter += res.evaluations;
   dual_solves++;
@@ -146,6 +154,44 @@ int MMA::solveDual() {
   dual_evaluations += res.evaluations;
   dual_last_status = res.status;
   dual_last_pg = res.pg;
+  return PO_OK;
+}
+
+// One MMA iteration of the conservative variant: rho from the gradients at xvec, then subproblem solves (each
+// warm-started from the last multipliers) until the problem's own values at the new point lie under the
+// approximations.  No gradient is evaluated and no coefficient vector is rewritten in here.
+int MMA::solveConservative() {
+  Options &o = options();
+  GcmmaParams gp;
+  gp.rho_init = o.real("mma_gcmma_rho_init");
+  gp.rho_min = o.real("mma_gcmma_rho_min");
+  gp.tol = o.real("mma_gcmma_tol");
+  gp.max_inner = o.integer("mma_gcmma_max_inner");
+  std::vector<const double *> A;
+  for (Vec *a : Avecs) A.push_back(a->d);
+  std::vector<double> sums(m + 1), fk(m + 1);
+  PO_TRY(k_mma_gcmma_rho_sums(ctx, Lvec->d, Uvec->d, gvec->d, A.data(), m, nlocal, sums.data()));
+  gcmma_rho_start(m, sums.data(), nglobal, gp, gcmma_rho.data());
+  fk[0] = fobj;
+  for (int i = 0; i < m; i++) fk[1 + i] = -cons[i];
+  auto trial = [&](const double *rho, double *psums, double *fnew) -> int {
+    PO_TRY(solveDual(rho, psums));
+    if (prob->evalObjCon(uinv, &fobj_trial, cons_trial.data()) != 0) {
+      fprintf(stderr, "ParOptMMA: Objective evaluation failed\n");
+      return PO_ERR_USER;
+    }
+    fnew[0] = fobj_trial;
+    for (int i = 0; i < m; i++) fnew[1 + i] = -cons_trial[i];
+    return PO_OK;
+  };
+  int raises = 0;
+  bool capped = false;
+  PO_TRY(gcmma_inner(m, fk.data(), gp, trial, gcmma_rho.data(), &raises, &capped));
+  have_trial_values = true;  // (the next initializeSubProblem takes uinv: no second evaluation there)
+  gcmma_inner_total += raises;
+  gcmma_inner_last = raises;
+  gcmma_inner_max = std::max(gcmma_inner_max, raises);
+  if (capped) gcmma_cap_hits++;
   return PO_OK;
 }
 
@@ -201,7 +247,11 @@ int MMA::initializeSubProblem(Vec *xv) {  // :523-757
   PO_TRY(k_copy(ctx, x2vec->d, x1vec->d, n));
   PO_TRY(k_copy(ctx, x1vec->d, xvec->d, n));
   if (xv && xv != xvec) PO_TRY(k_copy(ctx, xvec->d, xv->d, n));
-  if (prob->evalObjCon(xvec, &fobj, cons.data()) != 0) {
+  if (have_trial_values) {  // the inner iteration evaluated the problem at this point last
+    fobj = fobj_trial;
+    cons = cons_trial;
+    have_trial_values = false;
+  } else if (prob->evalObjCon(xvec, &fobj, cons.data()) != 0) {
     fprintf(stderr, "ParOptMMA: Objective evaluation failed\n");
     return PO_ERR_USER;
   }
@@ -259,6 +309,11 @@ void MMA::setMultipliers() {  // :384-400
 
 int MMA::optimize() {  // :318-379
   const bool want_dual = std::string(options().str("mma_subproblem_solver")) == "dual";
+  const bool conservative = std::string(options().str("mma_globalization")) == "conservative";
+  if (conservative && !want_dual) {  // (an inner raise would rewrite the interior point's 2 m + 2 coefficient vectors)
+    set_error("MMA: mma_globalization = conservative requires mma_subproblem_solver = dual");
+    return PO_ERR_ARG;
+  }
   if (want_dual) PO_TRY(checkDualCovers());  // refused before anything is allocated or run
   PO_TRY(build());
   if (want_dual != use_dual) {
@@ -274,7 +329,8 @@ int MMA::optimize() {  // :318-379
     history.clear();
     PO_TRY(initializeSubProblem(xvec));
     for (int i = 0; i < max_it; i++) {
-      PO_TRY(solveDual());
+      if (conservative) PO_TRY(solveConservative());
+      else PO_TRY(solveDual());
       PO_TRY(initializeSubProblem(uinv));
       double infeas = 0.0, l1 = 0.0, linfty = 0.0;  // permuted names, as below
       PO_TRY(computeKKTError(&infeas, &l1, &linfty));

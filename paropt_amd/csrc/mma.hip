@@ -289,31 +289,54 @@ __device__ __forceinline__ void dual_block_reduce(double (&a)[N], double *__rest
 
 // MC: compile-time column capacity (m <= MC; the sums of the columns past m stay 0).  MC <= PO_MMA_DUAL_HOLD (32): the
 // m column pairs of an element pair stay in registers between the formation of P, Q and the sums -- every stream is
-// read once (MC = 32: 390-416 VGPRs, one workgroup per CU, 64 loads of 16 B in flight per lane).  Wider: the columns
-// come in batches of NVB = 8 pairs and are read a second time for the sums, right behind the first (the per-column
-// accumulators are what fills the registers there).
+// read once (MC = 32: 392-406 VGPRs, 408-428 in the rho form, one workgroup per CU, 64 loads of 16 B in flight per
+// lane).  Wider: the columns come in batches of NVB = 8 pairs and are read a second time for the sums, right behind
+// the first (the per-column accumulators are what fills the registers there).
 // MODE 0: slots {W, g[MC]}; 1: ... and the MC (MC + 1) / 2 sums of -hess W (k-major lower triangle, i <= k);
 // 2: slots as 0, and the columns G_i and the weights d = [free] / h are stored for the weighted Gram.
-template <int MC, int MODE>
-__global__ void __launch_bounds__(kBlock)
-    mma_dual_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
-                    const double *__restrict__ beta, const double *__restrict__ p0, const double *__restrict__ q0,
-                    PtrTable Pt, PtrTable Qt, CoefTable lam, int m, int64_t n, PtrTableW Gt, double *__restrict__ dout,
-                    double *__restrict__ partials) {
+//
+// RHO (mma_globalization = conservative): every approximation carries Svanberg's term rho_i d(x),
+//   d(x) = sum (x - xk)^2 u l = sum w_U u + w_L l - 1,  w_U = (U - xk)^2 / (U - L),  w_L = (xk - L)^2 / (U - L),
+// so the Lagrangian keeps its form with P = P0 + sigma w_U, Q = Q0 + sigma w_L (sigma = rho_0 + lambda . rho, added
+// last; P0, Q0 the sums above).  One more stream (xk) and one more slot, D = d(x), the last one; slot 0 is taken on
+// P0, Q0 (the host adds sigma D and rho_i D), the Hessian columns gain rho_i (w_U u^2 - w_L l^2) and h is taken on the
+// full P, Q.  With every rho_i = 0 each added term is an exact zero: same bits as the plain form.
+// MODE 3 (RHO only), the point pass of an inner iteration: x, zl, zu are stored and the slots are
+// {Delta_0, Delta_i[MC], D}, Delta_i = sum p_i (u - u_k) + q_i (l - l_k) = f~_i(x) - f~_i(xk), with
+// u - u_k = (x - xk) u u_k and l - l_k = -(x - xk) l l_k (no cancellation against n).
+template <int MC, int MODE, bool RHO>
+struct DualSlots {
+  static constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
+  static constexpr int NS = 1 + MC + NH + (RHO ? 1 : 0);
+};
+template <int MC, int MODE, bool RHO>
+__device__ __forceinline__ void dual_body(const double *__restrict__ L, const double *__restrict__ U,
+                                          const double *__restrict__ alpha, const double *__restrict__ beta,
+                                          const double *__restrict__ p0, const double *__restrict__ q0,
+                                          const PtrTable &Pt, const PtrTable &Qt, const CoefTable &lam, int m,
+                                          int64_t n,
+                                          const PtrTableW &Gt, double *__restrict__ dout,
+                                          double *__restrict__ partials, double *sm, int64_t qfirst, int64_t qstride,
+                                          const double *__restrict__ xk,
+                                          const CoefTable &rho, double sigma, double *__restrict__ xo,
+                                          double *__restrict__ zlo, double *__restrict__ zuo) {
   constexpr bool HOLD = MC <= PO_MMA_DUAL_HOLD;
+  constexpr bool POINT = MODE == 3;
+  constexpr bool HESS = MODE == 1 || MODE == 2;
   constexpr int NVB = 8;
-  constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
-  constexpr int NS = 1 + MC + NH;
+  constexpr int NS = DualSlots<MC, MODE, RHO>::NS;
   static_assert(MODE != 1 || MC <= kMmaDualFused, "the fused Hessian needs the columns in registers");
-  __shared__ double sm[4 * NS];
+  static_assert(!POINT || RHO, "the point pass with sums belongs to the rho form");
   double acc[NS];
 #pragma unroll
   for (int s = 0; s < NS; s++) acc[s] = 0.0;
   const int64_t npairs = (n + 1) >> 1;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t q = qfirst; q < npairs; q += qstride) {
     const bool has2 = 2 * q + 1 < n;
     const f64x2 Lv = ld_nt(L + 2 * q), Uv = ld_nt(U + 2 * q), av = ld_nt(alpha + 2 * q), bv = ld_nt(beta + 2 * q);
     f64x2 P = ld_nt(p0 + 2 * q), Q = ld_nt(q0 + 2 * q);
+    f64x2 xkv = (f64x2){0.0, 0.0}, p0v = P, q0v = Q;
+    if (RHO) xkv = ld_nt(xk + 2 * q);
     f64x2 pv[HOLD ? MC : 1], qv[HOLD ? MC : 1];
     if (HOLD) {
 #pragma unroll
@@ -335,35 +358,78 @@ __global__ void __launch_bounds__(kBlock)
     } else {
       dual_pq_all(Pt, Qt, lam, m, q, P, Q);
     }
+    const f64x2 P0s = P, Q0s = Q;
+    f64x2 wU = (f64x2){0.0, 0.0}, wL = (f64x2){0.0, 0.0}, rs = (f64x2){0.0, 0.0}, dx = (f64x2){0.0, 0.0};
+    if (RHO) {
+      const f64x2 dU = Uv - xkv, dL = xkv - Lv;
+      rs.x = 1.0 / (Uv.x - Lv.x);
+      rs.y = has2 ? 1.0 / (Uv.y - Lv.y) : 0.0;
+      wU = dU * dU * rs;
+      wL = dL * dL * rs;
+      P = fma2(sigma, wU, P);
+      Q = fma2(sigma, wL, Q);
+    }
     const DualPoint t = dual_point(P, Q, Lv, Uv, av, bv, has2);
-    acc[0] = dot4(P, t.u, Q, t.l, acc[0]);
     const f64x2 u2 = t.u * t.u, l2 = t.l * t.l;
-    f64x2 dw = (f64x2){0.0, 0.0};
-    if (MODE != 0) {
+    f64x2 su = t.u, sl = t.l;  // what the column sums are taken on
+    if (RHO) {
+      dx = t.x - xkv;
+      if (!has2) dx.y = 0.0;
+      const f64x2 ul = t.u * t.l;
+      acc[NS - 1] = fma(dx.x * dx.x, ul.x, fma(dx.y * dx.y, ul.y, acc[NS - 1]));
+      if (POINT) {
+        f64x2 uk, lk;
+        uk.x = 1.0 / (Uv.x - xkv.x);
+        lk.x = 1.0 / (xkv.x - Lv.x);
+        uk.y = has2 ? 1.0 / (Uv.y - xkv.y) : 0.0;
+        lk.y = has2 ? 1.0 / (xkv.y - Lv.y) : 0.0;
+        su = dx * t.u * uk;
+        sl = -(dx * t.l * lk);
+        const f64x2 ql = Q * l2;
+        const f64x2 r = (f64x2){fma(P.x, u2.x, -ql.x), fma(P.y, u2.y, -ql.y)};
+        f64x2 xs = t.x, lo, up;
+        lo.x = t.x.x == av.x ? fmax(r.x, 0.0) : 0.0;
+        up.x = t.x.x == bv.x ? fmax(-r.x, 0.0) : 0.0;
+        lo.y = (has2 && t.x.y == av.y) ? fmax(r.y, 0.0) : 0.0;
+        up.y = (has2 && t.x.y == bv.y) ? fmax(-r.y, 0.0) : 0.0;
+        if (!has2) xs.y = 0.0;
+        st_nt(xo + 2 * q, xs);
+        st_nt(zlo + 2 * q, lo);
+        st_nt(zuo + 2 * q, up);
+      }
+    }
+    if (POINT) acc[0] = dot4(p0v, su, q0v, sl, acc[0]);
+    else acc[0] = dot4(P0s, t.u, Q0s, t.l, acc[0]);
+    f64x2 dw = (f64x2){0.0, 0.0}, gd = (f64x2){0.0, 0.0};
+    if (HESS) {
       const f64x2 h = 2.0 * (P * (u2 * t.u) + Q * (l2 * t.l));
       dw.x = t.fr.x != 0.0 ? 1.0 / h.x : 0.0;
       dw.y = t.fr.y != 0.0 ? 1.0 / h.y : 0.0;
       if (MODE == 2) st_nt(dout + 2 * q, dw);
+      // w_U u^2 - w_L l^2 = (a - b)(a + b) / (U - L) with a = (U - xk) u = 1 + dx u, b = (xk - L) l = 1 - dx l: the
+      // derivative of d, which vanishes at xk -- taken in the form that does not cancel there
+      if (RHO) gd = dx * (t.u + t.l) * (2.0 + dx * (t.u - t.l)) * rs;
     }
     if (HOLD) {
-      f64x2 gv[MODE == 0 ? 1 : MC];
+      f64x2 gv[HESS ? MC : 1];
 #pragma unroll
       for (int i = 0; i < MC; i++) {
-        acc[1 + i] = dot4(pv[i], t.u, qv[i], t.l, acc[1 + i]);
-        if (MODE != 0) {
+        acc[1 + i] = dot4(pv[i], su, qv[i], sl, acc[1 + i]);
+        if (HESS) {
           const f64x2 ql = qv[i] * l2;
           gv[i] = (f64x2){fma(pv[i].x, u2.x, -ql.x), fma(pv[i].y, u2.y, -ql.y)};
+          if (RHO) gv[i] = fma2(rho.a[i], gd, gv[i]);
           if (MODE == 2 && i < m) st_nt(Gt.p[i] + 2 * q, gv[i]);
         }
       }
       if (MODE == 1) {
 #pragma unroll
         for (int k = 0; k < MC; k++) {
-          const f64x2 gd = gv[k] * dw;
+          const f64x2 gk = gv[k] * dw;
 #pragma unroll
           for (int i = 0; i <= k; i++) {
             const int s = 1 + MC + k * (k + 1) / 2 + i;
-            acc[s] = fma(gv[i].x, gd.x, fma(gv[i].y, gd.y, acc[s]));
+            acc[s] = fma(gv[i].x, gk.x, fma(gv[i].y, gk.y, acc[s]));
           }
         }
       }
@@ -383,13 +449,92 @@ __global__ void __launch_bounds__(kBlock)
           }
 #pragma unroll
           for (int v = 0; v < NVB; v++) {
-            acc[1 + j + v] = dot4(cp[v], t.u, cq[v], t.l, acc[1 + j + v]);
+            acc[1 + j + v] = dot4(cp[v], su, cq[v], sl, acc[1 + j + v]);
             if (MODE == 2 && j + v < m) {
               const f64x2 ql = cq[v] * l2;
-              st_nt(Gt.p[j + v] + 2 * q, (f64x2){fma(cp[v].x, u2.x, -ql.x), fma(cp[v].y, u2.y, -ql.y)});
+              f64x2 gc = (f64x2){fma(cp[v].x, u2.x, -ql.x), fma(cp[v].y, u2.y, -ql.y)};
+              if (RHO) gc = fma2(rho.a[j + v], gd, gc);
+              st_nt(Gt.p[j + v] + 2 * q, gc);
             }
           }
         }
+      }
+    }
+  }
+  dual_block_reduce<NS>(acc, partials, sm);
+}
+
+template <int MC, int MODE>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                    const double *__restrict__ beta, const double *__restrict__ p0, const double *__restrict__ q0,
+                    PtrTable Pt, PtrTable Qt, CoefTable lam, int m, int64_t n, PtrTableW Gt, double *__restrict__ dout,
+                    double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, MODE, false>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  dual_body<MC, MODE, false>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, Gt, dout, partials, sm, qfirst, qstride,
+                             nullptr, lam, 0.0, nullptr, nullptr, nullptr);
+}
+// the rho form of the pass (modes 0, 1, 2)
+template <int MC, int MODE>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_rho_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                        const double *__restrict__ beta, const double *__restrict__ p0, const double *__restrict__ q0,
+                        const double *__restrict__ xk, PtrTable Pt, PtrTable Qt, CoefTable lam, CoefTable rho,
+                        double sigma, int m, int64_t n, PtrTableW Gt, double *__restrict__ dout,
+                        double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, MODE, true>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  dual_body<MC, MODE, true>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, Gt, dout, partials, sm, qfirst, qstride,
+                            xk, rho, sigma, nullptr, nullptr, nullptr);
+}
+// the point pass of an inner iteration: x, zl, zu and the m + 2 sums {Delta_0, Delta_i, D}; every stream read once
+// (MC <= 32; wider, the columns a second time as in the pass above)
+template <int MC>
+__global__ void __launch_bounds__(kBlock)
+    mma_gcmma_point_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                           const double *__restrict__ beta, const double *__restrict__ p0,
+                           const double *__restrict__ q0, const double *__restrict__ xk, PtrTable Pt, PtrTable Qt,
+                           CoefTable lam, double sigma, int m, int64_t n, double *__restrict__ x,
+                           double *__restrict__ zl, double *__restrict__ zu, double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, 3, true>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  PtrTableW none = {};
+  dual_body<MC, 3, true>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, none, nullptr, partials, sm, qfirst, qstride,
+                         xk, lam, sigma, x, zl, zu);
+}
+
+// the start values of rho: slots {sum |g| (U - L), sum |A_i| (U - L)}, one read-only pass
+template <int MC>
+__global__ void __launch_bounds__(kBlock)
+    mma_gcmma_rho_start_kernel(const double *__restrict__ L, const double *__restrict__ U,
+                               const double *__restrict__ g, PtrTable At, int m, int64_t n,
+                               double *__restrict__ partials) {
+  constexpr int NVB = 8;
+  constexpr int NS = 1 + MC;
+  __shared__ double sm[4 * NS];
+  double acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; s++) acc[s] = 0.0;
+  const int64_t npairs = (n + 1) >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+    const f64x2 w = ld_nt(U + 2 * q) - ld_nt(L + 2 * q), gv = ld_nt(g + 2 * q);
+    acc[0] = fma(fabs(gv.x), w.x, fma(fabs(gv.y), w.y, acc[0]));
+#pragma unroll
+    for (int j = 0; j < MC; j += NVB) {
+      if (j < m) {
+        f64x2 cv[NVB < MC ? NVB : MC];
+#pragma unroll
+        for (int v = 0; v < NVB && v < MC; v++) {
+          cv[v] = (f64x2){0.0, 0.0};
+          if (j + v < m) cv[v] = ld_nt(At.p[j + v] + 2 * q);
+        }
+#pragma unroll
+        for (int v = 0; v < NVB && v < MC; v++)
+          acc[1 + j + v] = fma(fabs(cv[v].x), w.x, fma(fabs(cv[v].y), w.y, acc[1 + j + v]));
       }
     }
   }
@@ -437,9 +582,16 @@ static int dual_tables(const MmaDualData &s, const double *lambda, PtrTable *pt,
   return PO_OK;
 }
 
-#define PO_DUAL_LAUNCH(MC, MODE)                                                                               \
-  PO_MLAUNCH((mma_dual_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n, gt, \
-             dvec, c->d_partials)
+#define PO_DUAL_LAUNCH(MC, MODE)                                                                                  \
+  do {                                                                                                            \
+    if (r) {                                                                                                      \
+      PO_MLAUNCH((mma_dual_rho_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, pt, qt, ct, \
+                 rt, sigma, m, s.n, gt, dvec, c->d_partials);                                                     \
+    } else {                                                                                                      \
+      PO_MLAUNCH((mma_dual_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n,    \
+                 gt, dvec, c->d_partials);                                                                        \
+    }                                                                                                             \
+  } while (0)
 #define PO_DUAL_MODES01(MC)                 \
   do {                                      \
     if (form == 1) {                        \
@@ -459,11 +611,22 @@ static int dual_tables(const MmaDualData &s, const double *lambda, PtrTable *pt,
     }                                       \
   } while (0)
 
+static int dual_capacity(int m) {
+  return m <= 2 ? 2 : m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : m <= 32 ? 32 : m <= 64 ? 64 : 96;
+}
+// sigma = rho_0 + lambda . rho and the table of rho_1..m
+static double rho_tables(const MmaDualRho &r, int m, const double *lambda, CoefTable *rt) {
+  double sigma = r.rho[0];
+  for (int i = 0; i < kMaxPanel; i++) rt->a[i] = i < m ? r.rho[1 + i] : 0.0;
+  for (int i = 0; i < m; i++) sigma += lambda[i] * r.rho[1 + i];
+  return sigma;
+}
+
 int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, double *W, double *grad, double *H,
-               double *const *G, double *dvec) {
+               double *const *G, double *dvec, const MmaDualRho *r, double *D) {
   const int m = s.m;
   PtrTable pt, qt;
-  CoefTable ct;
+  CoefTable ct, rt;
   PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
   if (form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
     set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
@@ -476,9 +639,10 @@ int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, dou
   }
   PtrTableW gt;
   for (int i = 0; i < kMaxPanel; i++) gt.p[i] = (form == 2 && i < m) ? G[i] : nullptr;
-  const int mc = m <= 2 ? 2 : m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : m <= 32 ? 32 : m <= 64 ? 64 : 96;
-  const int nh = form == 1 ? mc * (mc + 1) / 2 : 0, ns = 1 + mc + nh;
-  count_bytes(c, 2 * m + 6 + (form == 2 ? m + 1 : 0), s.n);
+  const double sigma = r ? rho_tables(*r, m, lambda, &rt) : 0.0;
+  const int mc = dual_capacity(m);
+  const int nh = form == 1 ? mc * (mc + 1) / 2 : 0, ns = 1 + mc + nh + (r ? 1 : 0);
+  count_bytes(c, 2 * m + 6 + (r ? 1 : 0) + (form == 2 ? m + 1 : 0), s.n);
   // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
   const int grid = grid_for(c, s.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * ns));
@@ -491,9 +655,15 @@ int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, dou
     case 64: PO_DUAL_MODES0(64); break;
     default: PO_DUAL_MODES0(96); break;
   }
-  double sums[1 + 96 + 36];
+  double sums[1 + 96 + 36 + 1];
   PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
   double w = sums[0];
+  if (r) {  // (exact zeros where rho = 0)
+    const double d = sums[ns - 1];
+    w += sigma * d;
+    for (int i = 0; i < m; i++) sums[1 + i] += r->rho[1 + i] * d;
+    if (D) *D = d;
+  }
   for (int i = 0; i < m; i++) {
     w += lambda[i] * s.b[i];
     grad[i] = sums[1 + i] + s.b[i];
@@ -506,6 +676,66 @@ int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, dou
     std::vector<const double *> cols(G, G + m);
     PO_TRY(k_wgram(c, dvec, cols.data(), m, s.n, H));
   }
+  return PO_OK;
+}
+
+#define PO_GCMMA_POINT(MC)                                                                                          \
+  PO_MLAUNCH((mma_gcmma_point_kernel<MC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r.xk, pt, qt, ct, sigma, m, \
+             s.n, x, zl, zu, c->d_partials)
+int k_mma_gcmma_point(Ctx *c, const MmaDualData &s, const MmaDualRho &r, const double *lambda, double *x, double *zl,
+                      double *zu, double *sums) {
+  const int m = s.m;
+  PtrTable pt, qt;
+  CoefTable ct;
+  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  double sigma = r.rho[0];
+  for (int i = 0; i < m; i++) sigma += lambda[i] * r.rho[1 + i];
+  const int mc = dual_capacity(m), ns = mc + 2;
+  count_bytes(c, 2 * m + 7 + 3, s.n);
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  PO_TRY(ensure_partials(c, (size_t)grid * ns));
+  switch (mc) {
+    case 2: PO_GCMMA_POINT(2); break;
+    case 4: PO_GCMMA_POINT(4); break;
+    case 8: PO_GCMMA_POINT(8); break;
+    case 16: PO_GCMMA_POINT(16); break;
+    case 32: PO_GCMMA_POINT(32); break;
+    case 64: PO_GCMMA_POINT(64); break;
+    default: PO_GCMMA_POINT(96); break;
+  }
+  double all[96 + 2];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
+  for (int i = 0; i <= m; i++) sums[i] = all[i];
+  sums[m + 1] = all[ns - 1];
+  return PO_OK;
+}
+
+#define PO_GCMMA_RHO_START(MC) \
+  PO_MLAUNCH((mma_gcmma_rho_start_kernel<MC>), grid, L, U, g, at, m, n, c->d_partials)
+int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double *g, const double *const *A, int m,
+                         int64_t n, double *sums) {
+  if (m < 0 || m > kMmaDualMax) {
+    set_error("MMA: %d constraints outside 0..%d", m, kMmaDualMax);
+    return PO_ERR_ARG;
+  }
+  PtrTable at;
+  for (int i = 0; i < kMaxPanel; i++) at.p[i] = i < m ? A[i] : nullptr;
+  const int mc = dual_capacity(m), ns = 1 + mc;
+  count_bytes(c, m + 3, n);
+  const int grid = grid_for(c, n, kBpcPanel);
+  PO_TRY(ensure_partials(c, (size_t)grid * ns));
+  switch (mc) {
+    case 2: PO_GCMMA_RHO_START(2); break;
+    case 4: PO_GCMMA_RHO_START(4); break;
+    case 8: PO_GCMMA_RHO_START(8); break;
+    case 16: PO_GCMMA_RHO_START(16); break;
+    case 32: PO_GCMMA_RHO_START(32); break;
+    case 64: PO_GCMMA_RHO_START(64); break;
+    default: PO_GCMMA_RHO_START(96); break;
+  }
+  double all[96 + 1];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
+  for (int i = 0; i <= m; i++) sums[i] = all[i];
   return PO_OK;
 }
 

@@ -46,8 +46,21 @@ struct MmaDualData {  // one subproblem: device pointers of n elements, m column
 // form 0: value and gradient only; 1: the Hessian sums in the same pass (m <= kMmaDualFused); 2: the pass stores the
 // columns G_i = p_i u^2 - q_i l^2 in G[i] and the weights [free] / h in dvec, H = G^T diag(dvec) G by k_wgram.
 // W and grad have the same bits in every form.
+// r != nullptr: the rho form (mma_globalization = conservative) -- every approximation carries rho_i d(x) around the
+// expansion point xk; *D (optional) receives d at the primal point.  With every rho_i = 0: the bits of the plain form.
+struct MmaDualRho {
+  const double *xk;   // device, n elements
+  const double *rho;  // host, m + 1 values: the objective's, then one per constraint
+};
 int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, double *W, double *grad, double *H,
-               double *const *G, double *dvec);
+               double *const *G, double *dvec, const MmaDualRho *r = nullptr, double *D = nullptr);
+// the point pass of the rho form: x, zl, zu at lambda and sums[m + 2] = {Delta_0, Delta_1..m, D},
+// Delta_i = f~_i(x) - f~_i(xk) without the rho term, D = d(x); collective
+int k_mma_gcmma_point(Ctx *c, const MmaDualData &s, const MmaDualRho &r, const double *lambda, double *x, double *zl,
+                      double *zu, double *sums);
+// sums[m + 1] = {sum |g| (U - L), sum |A_i| (U - L)}: the start values of rho; collective
+int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double *g, const double *const *A, int m,
+                         int64_t n, double *sums);
 // the primal point and the bound multipliers at lambda
 int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu);
 
@@ -112,6 +125,11 @@ class MMA : public Problem {
   int dual_solves, dual_iterations, dual_evaluations, dual_last_status;
   double dual_last_pg;
   MmaDualData dualData();
+  // mma_globalization = conservative (mma_gcmma.hpp; dual sub-solver only): raises of rho so far, in the last MMA
+  // iteration and the most in one, iterations that spent mma_gcmma_max_inner raises, and the m + 1 values of rho the
+  // last iteration was accepted with
+  int gcmma_inner_total, gcmma_inner_last, gcmma_inner_max, gcmma_cap_hits;
+  std::vector<double> gcmma_rho;
 
  private:
   MmaParams params() ;
@@ -120,7 +138,11 @@ class MMA : public Problem {
   int computeKKTError(double *l1, double *linfty, double *infeas);
   void setMultipliers();
   int checkDualCovers();
-  int solveDual();
+  int solveDual(const double *rho = nullptr, double *point_sums = nullptr);
+  int solveConservative();
+  bool have_trial_values;  // fobj_trial / cons_trial hold the problem's values at the point initializeSubProblem takes
+  double fobj_trial;
+  std::vector<double> cons_trial;
   void flushHistory();
 };
 

@@ -224,6 +224,21 @@ void Options::addMMADefaults() {
   dit.ilo = 1;
   dit.ihi = 1000000;
   e["mma_dual_max_iterations"] = dit;
+  // the globally convergent variant (Svanberg 2002; mma_gcmma.hpp), on the dual sub-solver only
+  Entry glob;
+  glob.type = ENUM;
+  glob.s = "none";
+  glob.choices = {"none", "conservative"};
+  e["mma_globalization"] = glob;
+  F("mma_gcmma_rho_init", 0.1, 0.0, 1e20);
+  F("mma_gcmma_rho_min", 1e-6, 1e-300, 1e20);
+  F("mma_gcmma_tol", 1e-7, 0.0, 1e20);
+  Entry inner;
+  inner.type = INT;
+  inner.i = 15;
+  inner.ilo = 0;
+  inner.ihi = 1000;
+  e["mma_gcmma_max_inner"] = inner;
 }
 
 int Options::set(const char *name, const char *value) {

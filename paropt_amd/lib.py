@@ -400,6 +400,14 @@ SIGNATURES = {
         C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, c_double_p, C.c_int,
                                                                               c_double_p, c_double_p, c_double_p]
         + [po_vec] * 3),
+    "po_mma_get_globalization_stats": (C.c_int, [po_mma, c_int_p, c_int_p, c_int_p, c_int_p, C.POINTER(c_double_p)]),
+    "po_mma_dual_eval_rho": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, c_double_p, po_vec,
+                                                                              c_double_p, C.c_int] + [c_double_p] * 4),
+    "po_mma_gcmma_point": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, po_vec, c_double_p]
+        + [po_vec] * 3 + [c_double_p]),
+    "po_mma_gcmma_rho_sums": (C.c_int, [po_ctx, C.c_int] + [po_vec] * 3 + [C.POINTER(po_vec), c_double_p]),
     "po_wgram": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
     "po_xgram": (C.c_int, [vec_p, vec_p, C.c_int, c_double_p]),
     "po_wgram_with_rhs": (C.c_int, [po_vec, vec_p, C.c_int, c_double_p]),
@@ -415,6 +423,7 @@ SIGNATURES = {
     "po_bench_stream": (C.c_int, [po_vec, po_vec, C.c_int, C.c_int, c_double_p]),
     "po_bench_vec_api": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
     "po_bench_mma_dual": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+    "po_bench_mma_dual_rho": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int] + [c_double_p] * 4),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -5,6 +5,13 @@ few MMA iterations each; then one evaluation of the dual is timed beside the tri
 (po_bench_mma_dual).  One JSON line per run, appended to profiles/r09_bench_mma.jsonl (--out), whatever comes out.
 
     python tools/bench_mma.py [--shapes 10000000x8,50000000x32] [--mma-iters 4] [--rounds 3] [--out FILE]
+
+--globalization conservative: the dual sub-solver without and with the conservative inner loop alternate instead (ms
+per MMA iteration and per inner raise, evaluations per solve), and the dual pass is timed beside its rho form and the
+trivial kernel of the rho form's mix, 2m + 7 in (po_bench_mma_dual_rho; profiles/r10_bench_gcmma.jsonl).  --problem
+picks the built-in problem of the whole runs.  --small: instead, whole runs to the stop test on small problems
+(--shapes 300x3,200x2, dual tolerance 1e-9, at most --mma-iters iterations, default there 120) with and without the
+inner loop: iterations, raises, cap hits, rises of fobj (the `convex_small` lines).
 """
 import argparse
 import json
@@ -19,10 +26,10 @@ HBM_PEAK_GBPS = 8000.0
 M_F = 8
 
 
-def run_mma(pa, ctx, n, c, solver, iters):
-    prob = pa.SeparableProblem(ctx, "convex", n, c, 0)
+def run_mma(pa, ctx, n, c, solver, iters, globalization="none", problem="convex"):
+    prob = pa.SeparableProblem(ctx, problem, n, c, 0)
     mma = pa.MMA(prob, {"mma_subproblem_solver": solver, "mma_max_iterations": iters, "mma_l1_tol": 0.0,
-                        "mma_linfty_tol": 0.0, "write_output_frequency": 0})
+                        "mma_linfty_tol": 0.0, "write_output_frequency": 0, "mma_globalization": globalization})
     stamps = []
     # (the callback follows the reductions of the table row, which the host has waited for: nothing is in flight)
     mma.setIterationCallback(lambda k: stamps.append(time.perf_counter()))
@@ -34,30 +41,103 @@ def run_mma(pa, ctx, n, c, solver, iters):
                subproblem_evaluations_per_mma_iteration=st["subproblem_iter"] / max(1, its), fobj=st["fobj"],
                vectors=pa.live_objects()[0], GB=pa.live_objects()[1] * 1e-9)
     if solver == "dual":
-        out["dual_stats"] = mma.getDualStats()
+        out["dual_stats"] = ds = mma.getDualStats()
+        out["evaluations_per_solve"] = ds["evaluations"] / max(1, ds["solves"])
+        gs = mma.getGlobalizationStats()
+        out.update(globalization=globalization, inner_total=gs["inner_total"], inner_max=gs["inner_max"],
+                   cap_hits=gs["cap_hits"], rho=gs["rho"].tolist())
     return out
+
+
+def small_run_lines(pa, ctx, n, c, iters, problem):
+    """Whole runs to the stop test with and without the conservative inner loop."""
+    lines = []
+    for glob in ("none", "conservative"):
+        mma = pa.MMA(pa.SeparableProblem(ctx, problem, n, c, 0),
+                     {"mma_subproblem_solver": "dual", "mma_dual_tol": 1e-9, "mma_max_iterations": iters,
+                      "mma_globalization": glob})
+        rows, inner = [], []
+
+        def cb(k):
+            rows.append(mma.getLastRow())
+            inner.append(mma.getGlobalizationStats()["inner_last"])
+
+        mma.setIterationCallback(cb)
+        mma.optimize()
+        gs = mma.getGlobalizationStats()
+        rises = sum(1 for k in range(1, len(rows)) if rows[k][0] > rows[k - 1][0] + 1e-7 * max(1.0, abs(rows[k][0])))
+        r = dict(kind="%s_small" % problem, n=n, c=c, globalization=glob, mma_iterations=len(rows) - 1,
+                 last_row=rows[-1], inner_total=gs["inner_total"], inner_max=gs["inner_max"], cap_hits=gs["cap_hits"],
+                 inner_per_iteration_first20=inner[1:21], fobj_every_20=[rows[k][0] for k in range(0, len(rows), 20)],
+                 rises=rises)
+        lines.append(r)
+        print(json.dumps(r), flush=True)
+    return lines
+
+
+def rho_pass_lines(pa, ctx, n, c, reps):
+    """The dual pass, its rho form and the trivial kernel of the rho form's mix, alternating in one call."""
+    lines = []
+    for form in ([1, 2] if c <= M_F else [2]):
+        plain, rho, gram_ms, ceil_ms = pa.bench_mma_dual_rho(ctx, n, c, form, reps)
+        r = dict(kind="dual_rho_pass", n=n, c=c, form=form, mix_rho="%d in / %d out" % (2 * c + 7, c + 1 if form == 2 else 0),
+                 plain_ms=plain, rho_ms=rho, gram_ms=gram_ms, trivial_rho_mix_ms=ceil_ms,
+                 rho_over_plain=[rho[0] / plain[0], rho[1] / plain[1]], predicted_by_bytes=(2 * c + 7) / (2 * c + 6),
+                 spread_plain=abs(plain[0] - plain[1]) / min(plain), spread_rho=abs(rho[0] - rho[1]) / min(rho),
+                 rho_frac_of_trivial=ceil_ms / min(rho))
+        lines.append(r)
+        print(json.dumps(r), flush=True)
+    return lines
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="10000000x8,50000000x32")
-    ap.add_argument("--mma-iters", type=int, default=4)
+    ap.add_argument("--shapes", default=None)
+    ap.add_argument("--mma-iters", type=int, default=None)
+    ap.add_argument("--small", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_bench_mma.jsonl"))
+    ap.add_argument("--globalization", choices=("none", "conservative"), default="none")
+    ap.add_argument("--problem", default="convex")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.small:
+        a.globalization = "conservative"
+    if a.shapes is None:
+        a.shapes = "300x3,200x2" if a.small else "10000000x8,50000000x32"
+    if a.mma_iters is None:
+        a.mma_iters = 120 if a.small else 4
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r10_bench_gcmma.jsonl" if a.globalization == "conservative"
+                             else "r09_bench_mma.jsonl")
     import paropt_amd as pa
 
     ctx = pa.Context(0)
     lines = []
     for shape in a.shapes.split(","):
         n, c = (int(v) for v in shape.split("x"))
+        if a.small:
+            lines += small_run_lines(pa, ctx, n, c, a.mma_iters, a.problem)
+            continue
         for rnd in range(a.rounds):
+            if a.globalization == "conservative":
+                for glob in ("none", "conservative"):
+                    r = run_mma(pa, ctx, n, c, "dual", a.mma_iters, glob, a.problem)
+                    r.update(kind="mma_gcmma", problem=a.problem, n=n, c=c, round=rnd)
+                    if glob == "conservative":  # what a raise costs beyond the plain iteration of the same round
+                        r["ms_per_inner_raise"] = ((r["ms_per_mma_iteration"] - lines[-1]["ms_per_mma_iteration"])
+                                                   * r["mma_iterations"] / max(1, r["inner_total"]))
+                    lines.append(r)
+                    print(json.dumps(r), flush=True)
+                continue
             for solver in ("interior_point", "dual"):
                 r = run_mma(pa, ctx, n, c, solver, a.mma_iters)
                 r.update(kind="mma", n=n, c=c, round=rnd)
                 lines.append(r)
                 print(json.dumps(r), flush=True)
+        if a.globalization == "conservative":
+            lines += rho_pass_lines(pa, ctx, n, c, a.reps)
+            continue
         for form in ([1, 2] if c <= M_F else [2]):
             pass_ms, gram_ms, ceil_ms = pa.bench_mma_dual(ctx, n, c, form, a.reps)
             streams_in, streams_out = 2 * c + 6, (c + 1 if form == 2 else 0)
