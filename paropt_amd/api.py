@@ -1391,8 +1391,66 @@ def quasidef_factor_info(problem):
     return s.decode() if s else None
 
 
-class InteriorPoint:
+class _Driver:
+    """What InteriorPoint, TrustRegion and MMA share over their po_<x>_* entries: typed setOption, the handle's release,
+    the iteration callback and the tail of optimize()."""
+
+    _PREFIX = None  # "ip", "tr", "mma"
+    _ITER_FN = L.TR_ITER_FN
+    _QN_CALLBACKS = True  # optimize() can run a user-written quasi-Newton approximation
+
+    def _entry(self, name):
+        return getattr(lib, "po_%s_%s" % (self._PREFIX, name))
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx._h:
+                self._entry("destroy")(self._h)
+        except Exception:
+            pass
+
+    def setOption(self, name, value):
+        nm = name.encode()
+        if isinstance(value, bool):
+            check(self._entry("set_option_int")(self._h, nm, int(value)))
+        elif isinstance(value, int):
+            # int given for a float option is a type error in the reference too; be lenient only
+            # in the obvious direction (python ints for float-valued settings)
+            rc = self._entry("set_option_int")(self._h, nm, value)
+            if rc != 0:
+                check(self._entry("set_option_float")(self._h, nm, float(value)))
+        elif isinstance(value, float):
+            check(self._entry("set_option_float")(self._h, nm, value))
+        else:
+            check(self._entry("set_option_str")(self._h, nm, str(value).encode()))
+
+    def _keep_callback(self, cb):
+        self._cbs.append(cb)
+
+    def setIterationCallback(self, fn):
+        def _cb(user, k):
+            fn(k)
+            return 0
+
+        cb = self._ITER_FN(_cb)
+        self._keep_callback(cb)
+        check(self._entry("set_iteration_callback")(self._h, cb, None))
+
+    def _finish_optimize(self, rc):
+        if hasattr(self.problem, "_raise_pending"):
+            self.problem._raise_pending()  # an exception thrown inside a problem callback
+        if self._QN_CALLBACKS:
+            _raise_qn_pending()  # ... or inside a user-written quasi-Newton approximation
+        if rc != 0:
+            raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
+        return rc
+
+
+class InteriorPoint(_Driver):
     """ParOptInteriorPoint (reference src/ParOptInteriorPoint.h:128-217)."""
+
+    _PREFIX = "ip"
+    _ITER_FN = L.ITER_FN
 
     def __init__(self, problem, options=None):
         self.problem = problem
@@ -1407,44 +1465,11 @@ class InteriorPoint:
         for k, v in opts.items():
             self.setOption(k, v)
 
-    def __del__(self):
-        try:
-            if self._h and self.ctx._h:
-                lib.po_ip_destroy(self._h)
-        except Exception:
-            pass
-
-    def setOption(self, name, value):
-        nm = name.encode()
-        if isinstance(value, bool):
-            check(lib.po_ip_set_option_int(self._h, nm, int(value)))
-        elif isinstance(value, int):
-            # int given for a float option is a type error in the reference too; be lenient only
-            # in the obvious direction (python ints for float-valued settings)
-            rc = lib.po_ip_set_option_int(self._h, nm, value)
-            if rc != 0:
-                check(lib.po_ip_set_option_float(self._h, nm, float(value)))
-        elif isinstance(value, float):
-            check(lib.po_ip_set_option_float(self._h, nm, value))
-        else:
-            check(lib.po_ip_set_option_str(self._h, nm, str(value).encode()))
-
-    def setIterationCallback(self, fn):
-        def _cb(user, k):
-            fn(k)
-            return 0
-
-        self._iter_cb = L.ITER_FN(_cb)
-        check(lib.po_ip_set_iteration_callback(self._h, self._iter_cb, None))
+    def _keep_callback(self, cb):
+        self._iter_cb = cb  # one slot: a new callback releases the last
 
     def optimize(self, checkpoint=None):
-        rc = lib.po_ip_optimize(self._h, checkpoint.encode() if checkpoint else None)
-        if hasattr(self.problem, "_raise_pending"):
-            self.problem._raise_pending()  # an exception thrown inside a problem callback
-        _raise_qn_pending()  # ... or inside a user-written quasi-Newton approximation
-        if rc not in (0,):
-            raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
-        return rc
+        return self._finish_optimize(lib.po_ip_optimize(self._h, checkpoint.encode() if checkpoint else None))
 
     def writeSolutionFile(self, filename):
         check(lib.po_ip_write_solution_file(self._h, filename.encode()))
@@ -2085,13 +2110,14 @@ class InfeasSubproblem:
         return lib.po_problem_eval_obj_con_gradient(self._h, x.handle, g.handle, hs)
 
 
-class TrustRegion:
+class TrustRegion(_Driver):
     """ParOptTrustRegion.  ``TrustRegion(problem, options)`` assembles quasi-Newton object, quadratic (or eigenvalue)
     subproblem and interior-point solver the way ParOptOptimizer does for algorithm='tr' (reference
     src/ParOptOptimizer.cpp:108-183); ``TrustRegion(subproblem, options)`` with a TrustRegionSubproblem is the
     reference's own constructor (src/ParOptTrustRegion.cpp:660-718) and takes the solver at ``optimize(ip)``.
     `options` may mix interior-point and trust-region option names (one shared registry)."""
 
+    _PREFIX = "tr"
     COLS = ("fobj", "infeas", "l1", "linfty", "smax", "tr", "rho", "model_reduc", "zav", "zmax", "gav", "gmax")
 
     def __init__(self, problem, options=None):
@@ -2109,26 +2135,6 @@ class TrustRegion:
         for k, v in opts.items():
             self.setOption(k, v)
 
-    def __del__(self):
-        try:
-            if self._h and self.ctx._h:
-                lib.po_tr_destroy(self._h)
-        except Exception:
-            pass
-
-    def setOption(self, name, value):
-        nm = name.encode()
-        if isinstance(value, bool):
-            check(lib.po_tr_set_option_int(self._h, nm, int(value)))
-        elif isinstance(value, int):
-            rc = lib.po_tr_set_option_int(self._h, nm, value)
-            if rc != 0:
-                check(lib.po_tr_set_option_float(self._h, nm, float(value)))
-        elif isinstance(value, float):
-            check(lib.po_tr_set_option_float(self._h, nm, value))
-        else:
-            check(lib.po_tr_set_option_str(self._h, nm, str(value).encode()))
-
     def setEigenModel(self, N, index, update):
         """update(x: PVec, approx: EigenApprox) fills approx.hvecs / M / Minv (c0, g0 are preset)."""
         def _cb(user, x, approx):
@@ -2142,15 +2148,6 @@ class TrustRegion:
     def setEigenModelSynthetic(self, N, index, seed=0, curv=1.0):
         check(lib.po_tr_set_eigen_model_synthetic(self._h, int(N), int(index), int(seed), float(curv)))
 
-    def setIterationCallback(self, fn):
-        def _cb(user, k):
-            fn(k)
-            return 0
-
-        cb = L.TR_ITER_FN(_cb)
-        self._cbs.append(cb)
-        check(lib.po_tr_set_iteration_callback(self._h, cb, None))
-
     def optimize(self, ip=None):
         """optimize() for the self-assembled form; optimize(ip) with an InteriorPoint built on the subproblem for the
         reference's form (ParOptTrustRegion::optimize(ParOptInteriorPoint*), .cpp:2365-2384)."""
@@ -2159,12 +2156,7 @@ class TrustRegion:
             rc = lib.po_tr_optimize_with(self._h, ip._h)
         else:
             rc = lib.po_tr_optimize(self._h)
-        if hasattr(self.problem, "_raise_pending"):
-            self.problem._raise_pending()
-        _raise_qn_pending()
-        if rc != 0:
-            raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
-        return rc
+        return self._finish_optimize(rc)
 
     def initialize(self):
         check(lib.po_tr_initialize(self._h))
@@ -2235,10 +2227,13 @@ class TrustRegion:
         return d
 
 
-class MMA:
+class MMA(_Driver):
     """ParOptMMA (reference src/ParOptMMA.h:22-192) with its interior-point sub-solver, assembled the
     way ParOptOptimizer does for algorithm='mma'.  `options` may mix interior-point and mma_* names.
     mma_subproblem_solver='dual' solves the subproblems through their dual instead (getDualStats)."""
+
+    _PREFIX = "mma"
+    _QN_CALLBACKS = False  # (MMA takes no quasi-Newton object, user-written or not)
 
     def __init__(self, problem, options=None):
         self.problem = problem
@@ -2251,42 +2246,8 @@ class MMA:
         for k, v in opts.items():
             self.setOption(k, v)
 
-    def __del__(self):
-        try:
-            if self._h and self.ctx._h:
-                lib.po_mma_destroy(self._h)
-        except Exception:
-            pass
-
-    def setOption(self, name, value):
-        nm = name.encode()
-        if isinstance(value, bool):
-            check(lib.po_mma_set_option_int(self._h, nm, int(value)))
-        elif isinstance(value, int):
-            rc = lib.po_mma_set_option_int(self._h, nm, value)
-            if rc != 0:
-                check(lib.po_mma_set_option_float(self._h, nm, float(value)))
-        elif isinstance(value, float):
-            check(lib.po_mma_set_option_float(self._h, nm, value))
-        else:
-            check(lib.po_mma_set_option_str(self._h, nm, str(value).encode()))
-
-    def setIterationCallback(self, fn):
-        def _cb(user, k):
-            fn(k)
-            return 0
-
-        cb = L.TR_ITER_FN(_cb)
-        self._cbs.append(cb)
-        check(lib.po_mma_set_iteration_callback(self._h, cb, None))
-
     def optimize(self):
-        rc = lib.po_mma_optimize(self._h)
-        if hasattr(self.problem, "_raise_pending"):
-            self.problem._raise_pending()
-        if rc != 0:
-            raise L.ParOptAMDError(rc, lib.po_last_error().decode(errors="replace"))
-        return rc
+        return self._finish_optimize(lib.po_mma_optimize(self._h))
 
     def getOptimizedPoint(self):
         x, z, zw, zl, zu = L.po_vec(), L.c_double_p(), L.po_vec(), L.po_vec(), L.po_vec()
@@ -2347,6 +2308,21 @@ class MMA:
                     b=np.array([b[i] for i in range(c)]))
 
 
+def _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, who=""):
+    """m and the (ctx, m, L, U, alpha, beta, p0, q0, p[], q[]) head of the po_mma_dual_eval family's arguments."""
+    m = len(p)
+    if len(q) != m:
+        raise ValueError(who + "p and q must hold the same number of vectors")
+    pa_ = (L.po_vec * max(m, 1))(*[v.handle for v in p])
+    qa_ = (L.po_vec * max(m, 1))(*[v.handle for v in q])
+    return m, (ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle, q0.handle, pa_, qa_)
+
+
+def _f64(values):
+    a = np.ascontiguousarray(values, dtype=np.float64)
+    return a, a.ctypes.data_as(L.c_double_p)
+
+
 def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessian=True, point=None, xk=None, rho=None):
     """The dual function of an MMA subproblem given by caller vectors (po_mma_dual_eval): returns (W, grad, H) with
     H = minus the Hessian (None unless `hessian`).  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu)
@@ -2359,51 +2335,31 @@ def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessia
         if point is not None:
             raise ValueError("mma_dual_eval: the point of the rho form comes from mma_gcmma_point")
         return _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho)
-    m = len(p)
-    if len(q) != m:
-        raise ValueError("mma_dual_eval: p and q must hold the same number of vectors")
-    ba = np.ascontiguousarray(b, dtype=np.float64)
-    la = np.ascontiguousarray(lam, dtype=np.float64)
+    m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_dual_eval: ")
+    (ba, bp), (la, lp) = _f64(b), _f64(lam)
     if ba.size != m or la.size != m:
         raise ValueError("mma_dual_eval: b and lam must hold one entry per constraint")
-    pa_ = (L.po_vec * max(m, 1))(*[v.handle for v in p])
-    qa_ = (L.po_vec * max(m, 1))(*[v.handle for v in q])
     W = C.c_double()
     g = np.zeros(max(m, 1))
     H = np.zeros((m, m)) if hessian else None
     xs = [v.handle for v in point] if point is not None else [None, None, None]
-    check(lib.po_mma_dual_eval(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle, q0.handle,
-                               pa_, qa_, ba.ctypes.data_as(L.c_double_p), la.ctypes.data_as(L.c_double_p), int(form),
-                               C.byref(W), g.ctypes.data_as(L.c_double_p),
+    check(lib.po_mma_dual_eval(*head, bp, lp, int(form), C.byref(W), g.ctypes.data_as(L.c_double_p),
                                H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1], xs[2]))
     return W.value, g[:m], H
 
 
-def _mma_tables(p, q, lam, rho):
-    m = len(p)
-    if len(q) != m:
-        raise ValueError("p and q must hold the same number of vectors")
-    la = np.ascontiguousarray(lam, dtype=np.float64)
-    ra = np.ascontiguousarray(rho, dtype=np.float64)
+def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho):
+    m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q)
+    (la, lp), (ra, rp), (ba, bp) = _f64(lam), _f64(rho), _f64(b)
     if la.size != m or ra.size != m + 1:
         raise ValueError("lam holds one entry per constraint, rho one more")
-    pa_ = (L.po_vec * max(m, 1))(*[v.handle for v in p])
-    qa_ = (L.po_vec * max(m, 1))(*[v.handle for v in q])
-    return m, pa_, qa_, la, ra
-
-
-def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho):
-    m, pa_, qa_, la, ra = _mma_tables(p, q, lam, rho)
-    ba = np.ascontiguousarray(b, dtype=np.float64)
     if ba.size != m:
         raise ValueError("mma_dual_eval: b must hold one entry per constraint")
     W, D = C.c_double(), C.c_double()
     g = np.zeros(max(m, 1))
     H = np.zeros((m, m)) if hessian else None
-    check(lib.po_mma_dual_eval_rho(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle,
-                                   q0.handle, pa_, qa_, ba.ctypes.data_as(L.c_double_p),
-                                   la.ctypes.data_as(L.c_double_p), xk.handle, ra.ctypes.data_as(L.c_double_p),
-                                   int(form), C.byref(W), g.ctypes.data_as(L.c_double_p),
+    check(lib.po_mma_dual_eval_rho(*head, bp, lp, xk.handle, rp, int(form), C.byref(W),
+                                   g.ctypes.data_as(L.c_double_p),
                                    H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, C.byref(D)))
     return W.value, g[:m], H, D.value
 
@@ -2411,11 +2367,12 @@ def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hes
 def mma_gcmma_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, xk, rho, point):
     """The point pass of a conservative inner iteration (po_mma_gcmma_point): fills point = (x, zl, zu) PVecs at lam
     and returns the m + 2 sums [Delta_0, Delta_1..m, D]."""
-    m, pa_, qa_, la, ra = _mma_tables(p, q, lam, rho)
+    m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q)
+    (la, lp), (ra, rp) = _f64(lam), _f64(rho)
+    if la.size != m or ra.size != m + 1:
+        raise ValueError("lam holds one entry per constraint, rho one more")
     sums = np.zeros(m + 2)
-    check(lib.po_mma_gcmma_point(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle, q0.handle,
-                                 pa_, qa_, la.ctypes.data_as(L.c_double_p), xk.handle,
-                                 ra.ctypes.data_as(L.c_double_p), point[0].handle, point[1].handle, point[2].handle,
+    check(lib.po_mma_gcmma_point(*head, lp, xk.handle, rp, point[0].handle, point[1].handle, point[2].handle,
                                  sums.ctypes.data_as(L.c_double_p)))
     return sums
 

@@ -1,7 +1,6 @@
 // C ABI of the trust-region layer (include/paropt_amd.h, "ParOptTrustRegion").
 #include <string.h>
 
-#include "mma.hpp"
 #include "tr.hpp"
 
 using namespace po;
@@ -553,259 +552,6 @@ int po_tr_set_penalty_gamma_array(po_tr tr, const double *gamma) {
   PO_CHECK_PTR(tr);
   PO_CHECK_PTR(gamma);
   tr->tr->setPenaltyGammaArray(gamma);
-  return PO_OK;
-}
-
-// ---- MMA -----------------------------------------------------------------------------------------
-int po_mma_create(po_problem prob, po_mma *out) {
-  PO_CHECK_PTR(prob);
-  PO_CHECK_PTR(out);
-  po_mma_s *h = new po_mma_s();
-  h->mma = new MMA(prob->p);
-  *out = h;
-  return PO_OK;
-}
-int po_mma_destroy(po_mma mma) {
-  if (!mma) return PO_OK;
-  delete mma->mma;
-  delete mma;
-  return PO_OK;
-}
-int po_mma_set_option_str(po_mma mma, const char *name, const char *value) {
-  PO_CHECK_PTR(mma);
-  PO_CHECK_PTR(name);
-  return mma->mma->options().set(name, value);
-}
-int po_mma_set_option_int(po_mma mma, const char *name, int value) {
-  PO_CHECK_PTR(mma);
-  PO_CHECK_PTR(name);
-  return mma->mma->options().set(name, value);
-}
-int po_mma_set_option_float(po_mma mma, const char *name, double value) {
-  PO_CHECK_PTR(mma);
-  PO_CHECK_PTR(name);
-  return mma->mma->options().set(name, value);
-}
-int po_mma_optimize(po_mma mma) {
-  PO_CHECK_PTR(mma);
-  return mma->mma->optimize();
-}
-int po_mma_get_optimized_point(po_mma mma, po_vec *x, const double **z, po_vec *zw, po_vec *zl, po_vec *zu) {
-  PO_CHECK_PTR(mma);
-  MMA *m = mma->mma;
-  PO_TRY(m->build());
-  if (x) *x = static_cast<po_vec>(m->xvec);
-  if (z) *z = m->z.data();
-  if (zw) *zw = static_cast<po_vec>(m->zwvec);
-  if (zl) *zl = static_cast<po_vec>(m->zlvec);
-  if (zu) *zu = static_cast<po_vec>(m->zuvec);
-  return PO_OK;
-}
-int po_mma_get_asymptotes(po_mma mma, po_vec *L, po_vec *U) {
-  PO_CHECK_PTR(mma);
-  PO_TRY(mma->mma->build());
-  if (L) *L = static_cast<po_vec>(mma->mma->Lvec);
-  if (U) *U = static_cast<po_vec>(mma->mma->Uvec);
-  return PO_OK;
-}
-int po_mma_get_state(po_mma mma, int *mma_iter, int *subproblem_iter, double *fobj, const double **cons) {
-  PO_CHECK_PTR(mma);
-  MMA *m = mma->mma;
-  if (mma_iter) *mma_iter = m->mma_iter;
-  if (subproblem_iter) *subproblem_iter = m->subproblem_iter;
-  if (fobj) *fobj = m->fobj;
-  if (cons) *cons = m->cons.data();
-  return PO_OK;
-}
-int po_mma_get_last_row(po_mma mma, const double **row5) {
-  PO_CHECK_PTR(mma);
-  PO_CHECK_PTR(row5);
-  *row5 = mma->mma->last_row;
-  return PO_OK;
-}
-int po_mma_get_history(po_mma mma, const char **text) {
-  PO_CHECK_PTR(mma);
-  PO_CHECK_PTR(text);
-  *text = mma->mma->history.c_str();
-  return PO_OK;
-}
-int po_mma_set_iteration_callback(po_mma mma, po_mma_iteration_fn fn, void *user) {
-  PO_CHECK_PTR(mma);
-  mma->mma->iter_cb = fn;
-  mma->mma->iter_cb_user = user;
-  return PO_OK;
-}
-int po_mma_get_dual_stats(po_mma mma, int *solves, int *iterations, int *evaluations, int *last_status,
-                          double *last_pg) {
-  PO_CHECK_PTR(mma);
-  MMA *m = mma->mma;
-  if (solves) *solves = m->dual_solves;
-  if (iterations) *iterations = m->dual_iterations;
-  if (evaluations) *evaluations = m->dual_evaluations;
-  if (last_status) *last_status = m->dual_last_status;
-  if (last_pg) *last_pg = m->dual_last_pg;
-  return PO_OK;
-}
-int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **p,
-                          const po_vec **q, const double **b) {
-  PO_CHECK_PTR(mma);
-  MMA *m = mma->mma;
-  PO_TRY(m->build());
-  if (alpha) *alpha = static_cast<po_vec>(m->alphavec);
-  if (beta) *beta = static_cast<po_vec>(m->betavec);
-  if (p0) *p0 = static_cast<po_vec>(m->p0vec);
-  if (q0) *q0 = static_cast<po_vec>(m->q0vec);
-  mma->p.clear();
-  mma->q.clear();
-  for (Vec *v : m->pivecs) mma->p.push_back(static_cast<po_vec>(v));
-  for (Vec *v : m->qivecs) mma->q.push_back(static_cast<po_vec>(v));
-  if (p) *p = mma->p.data();
-  if (q) *q = mma->q.data();
-  if (b) *b = m->b.data();
-  return PO_OK;
-}
-// the shared body of po_mma_dual_eval / po_mma_dual_eval_rho / po_mma_gcmma_point: argument checks, the tables and the
-// panel form's work vectors
-static int mma_dual_entry(const char *who, po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0,
-                          po_vec q0, const po_vec *p, const po_vec *q, const double *b, const double *lambda,
-                          po_vec xk, const double *rho, int form, double *W, double *grad, double *hess, double *D,
-                          po_vec x, po_vec zl, po_vec zu, double *point_sums) {
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
-  if (!point_sums) {
-    PO_CHECK_PTR(W);
-    PO_CHECK_PTR(grad);
-  }
-  if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax, kMmaDualFused);
-    return PO_ERR_ARG;
-  }
-  if (m > 0) {
-    PO_CHECK_PTR(p);
-    PO_CHECK_PTR(q);
-    PO_CHECK_PTR(b);
-    PO_CHECK_PTR(lambda);
-  }
-  const po_vec six[] = {U, alpha, beta, p0, q0, rho ? xk : U};
-  std::vector<const double *> pp, qq;
-  for (po_vec v : six) {
-    PO_CHECK_PTR(v);
-    if (v->ctx != L->ctx || v->n != L->n || L->ctx != ctx) {
-      po::set_error("%s: vectors of different layouts", who);
-      return PO_ERR_ARG;
-    }
-  }
-  const po_vec outs[] = {x, zl, zu};
-  for (po_vec v : outs) {
-    if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
-      po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
-      return PO_ERR_ARG;
-    }
-  }
-  for (int i = 0; i < m; i++) {
-    PO_CHECK_PTR(p[i]);
-    PO_CHECK_PTR(q[i]);
-    if (p[i]->ctx != ctx || q[i]->ctx != ctx || p[i]->n != L->n || q[i]->n != L->n) {
-      po::set_error("%s: vectors of different layouts", who);
-      return PO_ERR_ARG;
-    }
-    pp.push_back(p[i]->d);
-    qq.push_back(q[i]->d);
-  }
-  MmaDualData s;
-  s.L = L->d;
-  s.U = U->d;
-  s.alpha = alpha->d;
-  s.beta = beta->d;
-  s.p0 = p0->d;
-  s.q0 = q0->d;
-  s.p = pp.data();
-  s.q = qq.data();
-  s.b = b;
-  s.m = m;
-  s.n = L->n;
-  const MmaDualRho r{rho ? xk->d : nullptr, rho};
-  if (point_sums) return k_mma_gcmma_point(ctx, s, r, lambda, x->d, zl->d, zu->d, point_sums);
-  if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
-  if (!hess) form = 0;
-  std::vector<Vec *> work;  // the panel form's columns and weights
-  std::vector<double *> G;
-  int rc = PO_OK;
-  if (form == 2) {
-    for (int i = 0; i < m + 1 && rc == PO_OK; i++) {
-      Vec *v = vec_new(ctx, L->n);
-      if (!v) rc = PO_ERR_HIP;
-      else work.push_back(v);
-    }
-    for (int i = 0; i < m && rc == PO_OK; i++) G.push_back(work[i]->d);
-  }
-  if (rc == PO_OK)
-    rc = k_mma_dual(ctx, s, lambda, form, W, grad, hess, form == 2 ? G.data() : nullptr,
-                    form == 2 ? work[m]->d : nullptr, rho ? &r : nullptr, D);
-  if (rc == PO_OK && x) rc = k_mma_dual_point(ctx, s, lambda, x->d, zl->d, zu->d);
-  if (rc == PO_OK && !work.empty()) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
-  for (Vec *v : work) vec_decref(v);
-  return rc;
-}
-int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                     const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
-                     double *grad, double *hess, po_vec x, po_vec zl, po_vec zu) {
-  return mma_dual_entry("po_mma_dual_eval", ctx, m, L, U, alpha, beta, p0, q0, p, q, b, lambda, nullptr, nullptr,
-                        form, W, grad, hess, nullptr, x, zl, zu, nullptr);
-}
-int po_mma_dual_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                         const po_vec *p, const po_vec *q, const double *b, const double *lambda, po_vec xk,
-                         const double *rho, int form, double *W, double *grad, double *hess, double *D) {
-  PO_CHECK_PTR(xk);
-  PO_CHECK_PTR(rho);
-  return mma_dual_entry("po_mma_dual_eval_rho", ctx, m, L, U, alpha, beta, p0, q0, p, q, b, lambda, xk, rho, form, W,
-                        grad, hess, D, nullptr, nullptr, nullptr, nullptr);
-}
-int po_mma_gcmma_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                       const po_vec *p, const po_vec *q, const double *lambda, po_vec xk, const double *rho, po_vec x,
-                       po_vec zl, po_vec zu, double *sums) {
-  PO_CHECK_PTR(xk);
-  PO_CHECK_PTR(rho);
-  PO_CHECK_PTR(x);
-  PO_CHECK_PTR(sums);
-  const double none = 0.0;  // (the point pass does not read b)
-  return mma_dual_entry("po_mma_gcmma_point", ctx, m, L, U, alpha, beta, p0, q0, p, q, &none, lambda, xk, rho, 0,
-                        nullptr, nullptr, nullptr, nullptr, x, zl, zu, sums);
-}
-int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const po_vec *A, double *sums) {
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
-  PO_CHECK_PTR(U);
-  PO_CHECK_PTR(g);
-  PO_CHECK_PTR(sums);
-  if (m < 0 || m > kMmaDualMax) {
-    po::set_error("po_mma_gcmma_rho_sums: m = %d outside 0..%d", m, kMmaDualMax);
-    return PO_ERR_ARG;
-  }
-  if (m > 0) PO_CHECK_PTR(A);
-  std::vector<const double *> cols;
-  for (int i = 0; i < m; i++) {
-    PO_CHECK_PTR(A[i]);
-    cols.push_back(A[i]->d);
-  }
-  for (int i = -2; i < m; i++) {
-    const po_vec v = i == -2 ? U : i == -1 ? g : A[i];
-    if (v->ctx != ctx || L->ctx != ctx || v->n != L->n) {
-      po::set_error("po_mma_gcmma_rho_sums: vectors of different layouts");
-      return PO_ERR_ARG;
-    }
-  }
-  return k_mma_gcmma_rho_sums(ctx, L->d, U->d, g->d, cols.data(), m, L->n, sums);
-}
-int po_mma_get_globalization_stats(po_mma mma, int *inner_total, int *inner_last, int *inner_max, int *cap_hits,
-                                   const double **rho) {
-  PO_CHECK_PTR(mma);
-  MMA *m = mma->mma;
-  if (inner_total) *inner_total = m->gcmma_inner_total;
-  if (inner_last) *inner_last = m->gcmma_inner_last;
-  if (inner_max) *inner_max = m->gcmma_inner_max;
-  if (cap_hits) *cap_hits = m->gcmma_cap_hits;
-  if (rho) *rho = m->gcmma_rho.data();
   return PO_OK;
 }
 

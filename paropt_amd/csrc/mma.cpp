@@ -14,22 +14,16 @@
 namespace po {
 
 MMA::MMA(Problem *p)
-    : Problem(p->ctx, p->nlocal, p->ncon, p->ninequality), prob(p), ip(nullptr), m(p->ncon), use_true_mma(1),
-      mma_iter(0), subproblem_iter(0), xvec(nullptr), x1vec(nullptr), x2vec(nullptr), lbvec(nullptr),
-      ubvec(nullptr), gvec(nullptr), Lvec(nullptr), Uvec(nullptr), alphavec(nullptr), betavec(nullptr),
-      p0vec(nullptr), q0vec(nullptr), rvec(nullptr), zlvec(nullptr), zuvec(nullptr), uinv(nullptr),
-      linv(nullptr), cwvec(nullptr), zwvec(nullptr), fobj(0.0), cons(p->ncon, 0.0), b(p->ncon, 0.0),
-      z(p->ncon, 0.0), iter_cb(nullptr), iter_cb_user(nullptr), use_dual(false), dual_solves(0), dual_iterations(0),
-      dual_evaluations(0), dual_last_status(0), dual_last_pg(0.0), gcmma_inner_total(0), gcmma_inner_last(0),
-      gcmma_inner_max(0), gcmma_cap_hits(0), gcmma_rho(p->ncon + 1, 0.0), have_trial_values(false), fobj_trial(0.0),
-      cons_trial(p->ncon, 0.0) {
+    : Problem(p->ctx, p->nlocal, p->ncon, p->ninequality), cons(p->ncon, 0.0), b(p->ncon, 0.0), z(p->ncon, 0.0),
+      prob(p), m(p->ncon) {
   offset = p->offset;
   nglobal = p->nglobal;
   nwcon = p->nwcon;
   nwinequality = p->nwinequality;
   opts.addMMADefaults();
   opts.set("output_file", "");
-  for (double &v : last_row) v = 0.0;
+  gcmma.rho.assign(m + 1, 0.0);
+  trial.cons.assign(m, 0.0);
 }
 
 MMA::~MMA() {
@@ -68,8 +62,22 @@ int MMA::allocate() {  // initialize() :131-232
   if (prob->getVarsAndBounds(xvec, lbvec, ubvec) != 0) return PO_ERR_USER;
   if (!prob->useUpperBounds()) PO_TRY(k_fill(ctx, ubvec->d, n, 10.0));
   if (!prob->useLowerBounds()) PO_TRY(k_fill(ctx, lbvec->d, n, -9.0));
+  // the tables of the subproblem: none of these vectors is replaced before the destructor
+  P0p.push_back(p0vec->d);
+  Q0q.push_back(q0vec->d);
+  for (int i = 0; i < m; i++) {
+    P0p.push_back(pivecs[i]->d);
+    Q0q.push_back(qivecs[i]->d);
+    A.push_back(Avecs[i]->d);
+  }
+  A.push_back(zlvec->d);  // (the two columns computeKKTError adds to the constraint gradients)
+  A.push_back(zuvec->d);
+  sub = mma_dual_data(Lvec->d, Uvec->d, alphavec->d, betavec->d, p0vec->d, q0vec->d, P0p.data() + 1, Q0q.data() + 1,
+                      b.data(), m, n);
   return PO_OK;
 }
+
+bool MMA::wantDual() { return std::string(options().str("mma_subproblem_solver")) == "dual"; }
 
 int MMA::build() {
   if (ip || xvec) return PO_OK;
@@ -77,7 +85,7 @@ int MMA::build() {
     set_error("MMA: %d constraints exceed the panel width %d", m, kMaxPanel - 1);
     return PO_ERR_ARG;
   }
-  use_dual = std::string(opts.str("mma_subproblem_solver")) == "dual";
+  use_dual = wantDual();
   PO_TRY(allocate());
   if (use_dual) {  // no interior point and none of its 15 + c vectors; uinv / linv serve as the new point / the weights
     if (m > kMmaDualFused) {
@@ -85,6 +93,7 @@ int MMA::build() {
         Vec *g = vec_new(ctx, nlocal);
         if (!g) return PO_ERR_HIP;
         Gvecs.push_back(g);
+        G.push_back(g->d);
       }
     }
     return PO_OK;
@@ -106,54 +115,29 @@ int MMA::checkDualCovers() {
   return PO_ERR_ARG;
 }
 
-MmaDualData MMA::dualData() {
-  MmaDualData s;
-  s.L = Lvec->d;
-  s.U = Uvec->d;
-  s.alpha = alphavec->d;
-  s.beta = betavec->d;
-  s.p0 = p0vec->d;
-  s.q0 = q0vec->d;
-  s.p = s.q = nullptr;
-  s.b = b.data();
-  s.m = m;
-  s.n = nlocal;
-  return s;
-}
-
 // rho != nullptr: the subproblem in the conservative approximations f~_i + rho_i d around xvec; point_sums[m + 2] then
 // receives {Delta_0..m, D} of the solution (mma_gcmma.hpp)
 int MMA::solveDual(const double *rho, double *point_sums) {
   Options &o = options();
-  std::vector<const double *> P, Q;
-  std::vector<double *> G;
-  for (int i = 0; i < m; i++) {
-    P.push_back(pivecs[i]->d);
-    Q.push_back(qivecs[i]->d);
-  }
-  for (Vec *g : Gvecs) G.push_back(g->d);
-  MmaDualData s = dualData();
-  s.p = P.data();
-  s.q = Q.data();
   const int form = m <= kMmaDualFused ? 1 : 2;
   std::vector<double> gamma(m, o.real("penalty_gamma")), lambda(z);
   MmaDualResult res;
   const MmaDualRho r{xvec->d, rho};
   auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) {
-    return k_mma_dual(ctx, s, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d,
+    return k_mma_dual(ctx, sub, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d,
                       rho ? &r : nullptr);
   };
   PO_TRY(mma_dual_solve(m, gamma.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"), eval,
                         lambda.data(), &res));
-  if (rho) PO_TRY(k_mma_gcmma_point(ctx, s, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
-  else PO_TRY(k_mma_dual_point(ctx, s, lambda.data(), uinv->d, zlvec->d, zuvec->d));
+  if (rho) PO_TRY(k_mma_gcmma_point(ctx, sub, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
+  else PO_TRY(k_mma_dual_point(ctx, sub, lambda.data(), uinv->d, zlvec->d, zuvec->d));
   z = lambda;
   subproblem_iter += res.evaluations;
-  dual_solves++;
-  dual_iterations += res.iterations;
-  dual_evaluations += res.evaluations;
-  dual_last_status = res.status;
-  dual_last_pg = res.pg;
+  dual.solves++;
+  dual.iterations += res.iterations;
+  dual.evaluations += res.evaluations;
+  dual.last_status = res.status;
+  dual.last_pg = res.pg;
   return PO_OK;
 }
 
@@ -167,31 +151,29 @@ int MMA::solveConservative() {
   gp.rho_min = o.real("mma_gcmma_rho_min");
   gp.tol = o.real("mma_gcmma_tol");
   gp.max_inner = o.integer("mma_gcmma_max_inner");
-  std::vector<const double *> A;
-  for (Vec *a : Avecs) A.push_back(a->d);
   std::vector<double> sums(m + 1), fk(m + 1);
   PO_TRY(k_mma_gcmma_rho_sums(ctx, Lvec->d, Uvec->d, gvec->d, A.data(), m, nlocal, sums.data()));
-  gcmma_rho_start(m, sums.data(), nglobal, gp, gcmma_rho.data());
+  gcmma_rho_start(m, sums.data(), nglobal, gp, gcmma.rho.data());
   fk[0] = fobj;
   for (int i = 0; i < m; i++) fk[1 + i] = -cons[i];
-  auto trial = [&](const double *rho, double *psums, double *fnew) -> int {
+  auto try_rho = [&](const double *rho, double *psums, double *fnew) -> int {
     PO_TRY(solveDual(rho, psums));
-    if (prob->evalObjCon(uinv, &fobj_trial, cons_trial.data()) != 0) {
+    if (prob->evalObjCon(uinv, &trial.fobj, trial.cons.data()) != 0) {
       fprintf(stderr, "ParOptMMA: Objective evaluation failed\n");
       return PO_ERR_USER;
     }
-    fnew[0] = fobj_trial;
-    for (int i = 0; i < m; i++) fnew[1 + i] = -cons_trial[i];
+    fnew[0] = trial.fobj;
+    for (int i = 0; i < m; i++) fnew[1 + i] = -trial.cons[i];
     return PO_OK;
   };
   int raises = 0;
   bool capped = false;
-  PO_TRY(gcmma_inner(m, fk.data(), gp, trial, gcmma_rho.data(), &raises, &capped));
-  have_trial_values = true;  // (the next initializeSubProblem takes uinv: no second evaluation there)
-  gcmma_inner_total += raises;
-  gcmma_inner_last = raises;
-  gcmma_inner_max = std::max(gcmma_inner_max, raises);
-  if (capped) gcmma_cap_hits++;
+  PO_TRY(gcmma_inner(m, fk.data(), gp, try_rho, gcmma.rho.data(), &raises, &capped));
+  trial.have = true;  // (the next initializeSubProblem takes uinv: no second evaluation there)
+  gcmma.inner_total += raises;
+  gcmma.inner_last = raises;
+  gcmma.inner_max = std::max(gcmma.inner_max, raises);
+  if (capped) gcmma.cap_hits++;
   return PO_OK;
 }
 
@@ -212,19 +194,13 @@ MmaParams MMA::params() {
 int MMA::computeKKTError(double *l1, double *linfty, double *infeas) {  // :406-484
   const double relax = options().real("mma_bound_relax");
   const int64_t n = nlocal;
-  std::vector<const double *> P;
-  std::vector<double> cf;
-  for (int i = 0; i < m; i++) {
-    P.push_back(Avecs[i]->d);
-    cf.push_back(-z[i]);
-  }
+  std::vector<double> cf;  // over [A_i | zl | zu]
+  for (int i = 0; i < m; i++) cf.push_back(-z[i]);
   if (relax <= 0.0) {
-    P.push_back(zlvec->d);
     cf.push_back(-1.0);
-    P.push_back(zuvec->d);
     cf.push_back(1.0);
   }
-  PO_TRY(k_panel_axpy(ctx, rvec->d, 1.0, gvec->d, 0.0, cf.data(), P.data(), (int)P.size(), n));
+  PO_TRY(k_panel_axpy(ctx, rvec->d, 1.0, gvec->d, 0.0, cf.data(), A.data(), (int)cf.size(), n));
   if (nwcon > 0) {
     if (prob->addSparseJacobianTranspose(-1.0, xvec, zwvec, rvec) != 0) return PO_ERR_USER;
   }
@@ -247,10 +223,10 @@ int MMA::initializeSubProblem(Vec *xv) {  // :523-757
   PO_TRY(k_copy(ctx, x2vec->d, x1vec->d, n));
   PO_TRY(k_copy(ctx, x1vec->d, xvec->d, n));
   if (xv && xv != xvec) PO_TRY(k_copy(ctx, xvec->d, xv->d, n));
-  if (have_trial_values) {  // the inner iteration evaluated the problem at this point last
-    fobj = fobj_trial;
-    cons = cons_trial;
-    have_trial_values = false;
+  if (trial.have) {  // the inner iteration evaluated the problem at this point last
+    fobj = trial.fobj;
+    cons = trial.cons;
+    trial.have = false;
   } else if (prob->evalObjCon(xvec, &fobj, cons.data()) != 0) {
     fprintf(stderr, "ParOptMMA: Objective evaluation failed\n");
     return PO_ERR_USER;
@@ -292,6 +268,7 @@ int MMA::initializeSubProblem(Vec *xv) {  // :523-757
     }
   }
   mma_iter++;
+  if (ip) PO_TRY(ip->resetDesignAndBounds());  // the interior point restarts from xvec inside the new move limits
   return PO_OK;
 }
 
@@ -307,8 +284,25 @@ void MMA::setMultipliers() {  // :384-400
   if (zu) k_copy(ctx, zuvec->d, zu->d, nlocal);
 }
 
+// The new point stays where the sub-solver left it: *xnew is the interior point's own vector or uinv.
+int MMA::solveSubproblem(Vec **xnew) {
+  switch (mode) {
+    case Mode::INTERIOR_POINT: {
+      const int rc = ip->optimize(nullptr);
+      if (rc != 0 && rc != 1) return rc;
+      setMultipliers();
+      ip->getOptimizedPoint(xnew, nullptr, nullptr, nullptr);
+      return PO_OK;
+    }
+    case Mode::DUAL: PO_TRY(solveDual()); break;
+    case Mode::DUAL_CONSERVATIVE: PO_TRY(solveConservative()); break;
+  }
+  *xnew = uinv;
+  return PO_OK;
+}
+
 int MMA::optimize() {  // :318-379
-  const bool want_dual = std::string(options().str("mma_subproblem_solver")) == "dual";
+  const bool want_dual = wantDual();
   const bool conservative = std::string(options().str("mma_globalization")) == "conservative";
   if (conservative && !want_dual) {  // (an inner raise would rewrite the interior point's 2 m + 2 coefficient vectors)
     set_error("MMA: mma_globalization = conservative requires mma_subproblem_solver = dual");
@@ -320,38 +314,22 @@ int MMA::optimize() {  // :318-379
     set_error("MMA: mma_subproblem_solver cannot change once the solver's vectors exist");
     return PO_ERR_ARG;
   }
+  mode = !use_dual ? Mode::INTERIOR_POINT : conservative ? Mode::DUAL_CONSERVATIVE : Mode::DUAL;
   Options &o = options();
   const int max_it = o.integer("mma_max_iterations");
   const double infeas_tol = o.real("mma_infeas_tol"), l1_tol = o.real("mma_l1_tol"),
                linfty_tol = o.real("mma_linfty_tol");
   use_true_mma = o.integer("mma_use_constraint_linearization") ? 0 : 1;
-  if (use_dual) {
-    history.clear();
-    PO_TRY(initializeSubProblem(xvec));
-    for (int i = 0; i < max_it; i++) {
-      if (conservative) PO_TRY(solveConservative());
-      else PO_TRY(solveDual());
-      PO_TRY(initializeSubProblem(uinv));
-      double infeas = 0.0, l1 = 0.0, linfty = 0.0;  // permuted names, as below
-      PO_TRY(computeKKTError(&infeas, &l1, &linfty));
-      if (infeas < infeas_tol && (l1 < l1_tol || linfty < linfty_tol)) break;
-    }
-    flushHistory();
-    return 0;
+  if (mode == Mode::INTERIOR_POINT) {  // the subproblem hands the interior point its diagonal Hessian (.cpp:344-346)
+    PO_TRY(o.set("use_diag_hessian", 1));
+    PO_TRY(o.set("use_line_search", 0));
   }
-  PO_TRY(o.set("use_diag_hessian", 1));
-  PO_TRY(o.set("use_line_search", 0));
   history.clear();
   PO_TRY(initializeSubProblem(xvec));
-  PO_TRY(ip->resetDesignAndBounds());
   for (int i = 0; i < max_it; i++) {
-    int rc = ip->optimize(nullptr);
-    if (rc != 0 && rc != 1) return rc;
-    setMultipliers();
-    Vec *x = nullptr;
-    ip->getOptimizedPoint(&x, nullptr, nullptr, nullptr);
-    PO_TRY(initializeSubProblem(x));
-    PO_TRY(ip->resetDesignAndBounds());
+    Vec *xnew = nullptr;
+    PO_TRY(solveSubproblem(&xnew));
+    PO_TRY(initializeSubProblem(xnew));
     // the reference calls computeKKTError(&infeas, &l1, &linfty) on a function declared as
     // (l1, linfty, infeas) (:364-366): the names below therefore hold permuted quantities
     double infeas = 0.0, l1 = 0.0, linfty = 0.0;
@@ -390,18 +368,9 @@ int MMA::evalObjCon(Vec *xv, double *fval, double *cvals) {  // :804-866
   const int64_t n = nlocal;
   if (k_mma_inv(ctx, xv->d, Lvec->d, Uvec->d, n, uinv->d, linv->d) != PO_OK) return 1;
   const int nv = use_true_mma ? m + 1 : 1;
-  std::vector<const double *> P, Q;
-  P.push_back(p0vec->d);
-  Q.push_back(q0vec->d);
-  if (use_true_mma) {
-    for (int i = 0; i < m; i++) {
-      P.push_back(pivecs[i]->d);
-      Q.push_back(qivecs[i]->d);
-    }
-  }
   std::vector<double> du(nv, 0.0), dl(nv, 0.0);
-  if (k_mdot(ctx, uinv->d, P.data(), nv, n, du.data()) != PO_OK) return 1;
-  if (k_mdot(ctx, linv->d, Q.data(), nv, n, dl.data()) != PO_OK) return 1;
+  if (k_mdot(ctx, uinv->d, P0p.data(), nv, n, du.data()) != PO_OK) return 1;
+  if (k_mdot(ctx, linv->d, Q0q.data(), nv, n, dl.data()) != PO_OK) return 1;
   *fval = du[0] + dl[0];
   if (use_true_mma) {
     for (int i = 0; i < m; i++) cvals[i] = -((du[1 + i] + dl[1 + i]) + b[i]);
@@ -410,8 +379,6 @@ int MMA::evalObjCon(Vec *xv, double *fval, double *cvals) {  // :804-866
     const double mone[1] = {-1.0};
     const double *vv[1] = {xvec->d};
     if (k_panel_axpy(ctx, rvec->d, 1.0, xv->d, 0.0, mone, vv, 1, n) != PO_OK) return 1;
-    std::vector<const double *> A;
-    for (Vec *a : Avecs) A.push_back(a->d);
     if (k_mdot(ctx, rvec->d, A.data(), m, n, cvals) != PO_OK) return 1;
     for (int i = 0; i < m; i++) cvals[i] += cons[i];
   }
@@ -421,55 +388,28 @@ int MMA::evalObjCon(Vec *xv, double *fval, double *cvals) {  // :804-866
 int MMA::evalObjConGradient(Vec *xv, Vec *gv, Vec **Ac) {  // :871-924
   subproblem_iter++;
   const int64_t n = nlocal;
-  std::vector<const double *> P, Q;
-  std::vector<double *> out;
-  P.push_back(p0vec->d);
-  Q.push_back(q0vec->d);
-  out.push_back(gv->d);
-  if (use_true_mma) {
-    for (int i = 0; i < m; i++) {
-      P.push_back(pivecs[i]->d);
-      Q.push_back(qivecs[i]->d);
-      out.push_back(Ac[i]->d);
-    }
-  }
-  if (k_mma_grad(ctx, xv->d, Lvec->d, Uvec->d, P.data(), Q.data(), (int)P.size(), n, out.data()) != PO_OK) return 1;
+  const int nv = use_true_mma ? m + 1 : 1;
+  std::vector<double *> out(1, gv->d);  // [g | Ac_i]: the caller's vectors
+  for (int i = 0; i < m; i++) out.push_back(Ac[i]->d);
+  if (k_mma_grad(ctx, xv->d, Lvec->d, Uvec->d, P0p.data(), Q0q.data(), nv, n, out.data()) != PO_OK) return 1;
   if (!use_true_mma && m > 0) {
-    std::vector<double *> dst;
-    std::vector<const double *> src;
-    for (int i = 0; i < m; i++) {
-      dst.push_back(Ac[i]->d);
-      src.push_back(Avecs[i]->d);
-    }
-    if (k_panel_lincomb(ctx, dst.data(), 1.0, src.data(), 0.0, nullptr, m, n) != PO_OK) return 1;
+    if (k_panel_lincomb(ctx, out.data() + 1, 1.0, A.data(), 0.0, nullptr, m, n) != PO_OK) return 1;
   }
   return 0;
 }
 
 int MMA::evalHvecProduct(Vec *xv, const double *, Vec *, Vec *px, Vec *hvec) {  // :929-962 (objective only)
   const double one[1] = {1.0};
-  const double *P[1] = {p0vec->d}, *Q[1] = {q0vec->d};
-  if (k_mma_hdiag(ctx, xv->d, Lvec->d, Uvec->d, P, Q, one, 1, nlocal, hvec->d) != PO_OK) return 1;
+  if (k_mma_hdiag(ctx, xv->d, Lvec->d, Uvec->d, P0p.data(), Q0q.data(), one, 1, nlocal, hvec->d) != PO_OK) return 1;
   return k_mul(ctx, hvec->d, 1.0, hvec->d, px->d, nlocal) == PO_OK ? 0 : 1;
 }
 
 int MMA::evalHessianDiag(Vec *xv, const double *zz, Vec *, Vec *hdiag) {  // :967-1010
-  std::vector<const double *> P, Q;
-  std::vector<double> w;
-  P.push_back(p0vec->d);
-  Q.push_back(q0vec->d);
-  w.push_back(1.0);
-  if (use_true_mma) {
-    for (int i = 0; i < m; i++) {
-      P.push_back(pivecs[i]->d);
-      Q.push_back(qivecs[i]->d);
-      w.push_back(zz[i]);
-    }
-  }
-  return k_mma_hdiag(ctx, xv->d, Lvec->d, Uvec->d, P.data(), Q.data(), w.data(), (int)P.size(), nlocal,
-                     hdiag->d) == PO_OK
-             ? 0
-             : 1;
+  const int nv = use_true_mma ? m + 1 : 1;
+  std::vector<double> w(1, 1.0);
+  for (int i = 1; i < nv; i++) w.push_back(zz[i - 1]);
+  return k_mma_hdiag(ctx, xv->d, Lvec->d, Uvec->d, P0p.data(), Q0q.data(), w.data(), nv, nlocal, hdiag->d) == PO_OK ? 0
+                                                                                                                   : 1;
 }
 
 int MMA::evalSparseCon(Vec *x, Vec *out) {  // :1015-1021

@@ -1,6 +1,7 @@
 // Element-wise kernels of the method of moving asymptotes (reference src/ParOptMMA.cpp:523-1010).
 #include <math.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "core.hpp"
@@ -582,37 +583,18 @@ static int dual_tables(const MmaDualData &s, const double *lambda, PtrTable *pt,
   return PO_OK;
 }
 
-#define PO_DUAL_LAUNCH(MC, MODE)                                                                                  \
-  do {                                                                                                            \
-    if (r) {                                                                                                      \
-      PO_MLAUNCH((mma_dual_rho_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, pt, qt, ct, \
-                 rt, sigma, m, s.n, gt, dvec, c->d_partials);                                                     \
-    } else {                                                                                                      \
-      PO_MLAUNCH((mma_dual_kernel<MC, MODE>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n,    \
-                 gt, dvec, c->d_partials);                                                                        \
-    }                                                                                                             \
-  } while (0)
-#define PO_DUAL_MODES01(MC)                 \
-  do {                                      \
-    if (form == 1) {                        \
-      PO_DUAL_LAUNCH(MC, 1);                \
-    } else if (form == 2) {                 \
-      PO_DUAL_LAUNCH(MC, 2);                \
-    } else {                                \
-      PO_DUAL_LAUNCH(MC, 0);                \
-    }                                       \
-  } while (0)
-#define PO_DUAL_MODES0(MC)                  \
-  do {                                      \
-    if (form == 2) {                        \
-      PO_DUAL_LAUNCH(MC, 2);                \
-    } else {                                \
-      PO_DUAL_LAUNCH(MC, 0);                \
-    }                                       \
-  } while (0)
-
-static int dual_capacity(int m) {
-  return m <= 2 ? 2 : m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : m <= 32 ? 32 : m <= 64 ? 64 : 96;
+// m -> the compile-time column capacity MC that covers it; f(std::integral_constant<int, MC>) launches
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <class F>
+static int with_capacity(int m, F &&f) {
+  if (m <= 2) return f(Const<2>{});
+  if (m <= 4) return f(Const<4>{});
+  if (m <= 8) return f(Const<8>{});
+  if (m <= 16) return f(Const<16>{});
+  if (m <= 32) return f(Const<32>{});
+  if (m <= 64) return f(Const<64>{});
+  return f(Const<96>{});
 }
 // sigma = rho_0 + lambda . rho and the table of rho_1..m
 static double rho_tables(const MmaDualRho &r, int m, const double *lambda, CoefTable *rt) {
@@ -640,21 +622,29 @@ int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, dou
   PtrTableW gt;
   for (int i = 0; i < kMaxPanel; i++) gt.p[i] = (form == 2 && i < m) ? G[i] : nullptr;
   const double sigma = r ? rho_tables(*r, m, lambda, &rt) : 0.0;
-  const int mc = dual_capacity(m);
-  const int nh = form == 1 ? mc * (mc + 1) / 2 : 0, ns = 1 + mc + nh + (r ? 1 : 0);
   count_bytes(c, 2 * m + 6 + (r ? 1 : 0) + (form == 2 ? m + 1 : 0), s.n);
   // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
   const int grid = grid_for(c, s.n, kBpcPanel);
-  PO_TRY(ensure_partials(c, (size_t)grid * ns));
-  switch (mc) {
-    case 2: PO_DUAL_MODES01(2); break;
-    case 4: PO_DUAL_MODES01(4); break;
-    case 8: PO_DUAL_MODES01(8); break;
-    case 16: PO_DUAL_MODES0(16); break;
-    case 32: PO_DUAL_MODES0(32); break;
-    case 64: PO_DUAL_MODES0(64); break;
-    default: PO_DUAL_MODES0(96); break;
-  }
+  int mc = 0, ns = 0;
+  auto launch = [&](auto MC, auto MODE) -> int {
+    constexpr int kMC = decltype(MC)::value, kMode = decltype(MODE)::value;
+    if constexpr (kMode != 1 || kMC <= kMmaDualFused) {  // (form 1 past kMmaDualFused was refused above)
+      mc = kMC;
+      ns = r ? DualSlots<kMC, kMode, true>::NS : DualSlots<kMC, kMode, false>::NS;
+      PO_TRY(ensure_partials(c, (size_t)grid * ns));
+      if (r) {
+        PO_MLAUNCH((mma_dual_rho_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, pt, qt, ct,
+                   rt, sigma, m, s.n, gt, dvec, c->d_partials);
+      } else {
+        PO_MLAUNCH((mma_dual_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n, gt,
+                   dvec, c->d_partials);
+      }
+    }
+    return PO_OK;
+  };
+  PO_TRY(with_capacity(m, [&](auto MC) {
+    return form == 1 ? launch(MC, Const<1>{}) : form == 2 ? launch(MC, Const<2>{}) : launch(MC, Const<0>{});
+  }));
   double sums[1 + 96 + 36 + 1];
   PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
   double w = sums[0];
@@ -673,36 +663,29 @@ int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, dou
     for (int k = 0; k < m; k++)
       for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
   } else if (form == 2 && m > 0) {
-    std::vector<const double *> cols(G, G + m);
-    PO_TRY(k_wgram(c, dvec, cols.data(), m, s.n, H));
+    PO_TRY(k_wgram(c, dvec, G, m, s.n, H));
   }
   return PO_OK;
 }
 
-#define PO_GCMMA_POINT(MC)                                                                                          \
-  PO_MLAUNCH((mma_gcmma_point_kernel<MC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r.xk, pt, qt, ct, sigma, m, \
-             s.n, x, zl, zu, c->d_partials)
 int k_mma_gcmma_point(Ctx *c, const MmaDualData &s, const MmaDualRho &r, const double *lambda, double *x, double *zl,
                       double *zu, double *sums) {
   const int m = s.m;
   PtrTable pt, qt;
-  CoefTable ct;
+  CoefTable ct, rt;
   PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
-  double sigma = r.rho[0];
-  for (int i = 0; i < m; i++) sigma += lambda[i] * r.rho[1 + i];
-  const int mc = dual_capacity(m), ns = mc + 2;
+  const double sigma = rho_tables(r, m, lambda, &rt);  // (the point pass takes no table of rho)
   count_bytes(c, 2 * m + 7 + 3, s.n);
   const int grid = grid_for(c, s.n, kBpcPanel);
-  PO_TRY(ensure_partials(c, (size_t)grid * ns));
-  switch (mc) {
-    case 2: PO_GCMMA_POINT(2); break;
-    case 4: PO_GCMMA_POINT(4); break;
-    case 8: PO_GCMMA_POINT(8); break;
-    case 16: PO_GCMMA_POINT(16); break;
-    case 32: PO_GCMMA_POINT(32); break;
-    case 64: PO_GCMMA_POINT(64); break;
-    default: PO_GCMMA_POINT(96); break;
-  }
+  int ns = 0;
+  PO_TRY(with_capacity(m, [&](auto MC) -> int {
+    constexpr int kMC = decltype(MC)::value;
+    ns = DualSlots<kMC, 3, true>::NS;
+    PO_TRY(ensure_partials(c, (size_t)grid * ns));
+    PO_MLAUNCH((mma_gcmma_point_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r.xk, pt, qt, ct, sigma, m,
+               s.n, x, zl, zu, c->d_partials);
+    return PO_OK;
+  }));
   double all[96 + 2];
   PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
   for (int i = 0; i <= m; i++) sums[i] = all[i];
@@ -710,8 +693,6 @@ int k_mma_gcmma_point(Ctx *c, const MmaDualData &s, const MmaDualRho &r, const d
   return PO_OK;
 }
 
-#define PO_GCMMA_RHO_START(MC) \
-  PO_MLAUNCH((mma_gcmma_rho_start_kernel<MC>), grid, L, U, g, at, m, n, c->d_partials)
 int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double *g, const double *const *A, int m,
                          int64_t n, double *sums) {
   if (m < 0 || m > kMmaDualMax) {
@@ -720,19 +701,16 @@ int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double 
   }
   PtrTable at;
   for (int i = 0; i < kMaxPanel; i++) at.p[i] = i < m ? A[i] : nullptr;
-  const int mc = dual_capacity(m), ns = 1 + mc;
   count_bytes(c, m + 3, n);
   const int grid = grid_for(c, n, kBpcPanel);
-  PO_TRY(ensure_partials(c, (size_t)grid * ns));
-  switch (mc) {
-    case 2: PO_GCMMA_RHO_START(2); break;
-    case 4: PO_GCMMA_RHO_START(4); break;
-    case 8: PO_GCMMA_RHO_START(8); break;
-    case 16: PO_GCMMA_RHO_START(16); break;
-    case 32: PO_GCMMA_RHO_START(32); break;
-    case 64: PO_GCMMA_RHO_START(64); break;
-    default: PO_GCMMA_RHO_START(96); break;
-  }
+  int ns = 0;
+  PO_TRY(with_capacity(m, [&](auto MC) -> int {
+    constexpr int kMC = decltype(MC)::value;
+    ns = 1 + kMC;  // (the kernel's own NS)
+    PO_TRY(ensure_partials(c, (size_t)grid * ns));
+    PO_MLAUNCH((mma_gcmma_rho_start_kernel<kMC>), grid, L, U, g, at, m, n, c->d_partials);
+    return PO_OK;
+  }));
   double all[96 + 1];
   PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
   for (int i = 0; i <= m; i++) sums[i] = all[i];

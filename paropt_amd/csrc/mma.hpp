@@ -42,6 +42,11 @@ struct MmaDualData {  // one subproblem: device pointers of n elements, m column
   int m;
   int64_t n;
 };
+inline MmaDualData mma_dual_data(const double *L, const double *U, const double *alpha, const double *beta,
+                                 const double *p0, const double *q0, const double *const *p, const double *const *q,
+                                 const double *b, int m, int64_t n) {
+  return MmaDualData{L, U, alpha, beta, p0, q0, p, q, b, m, n};
+}
 // W(lambda), grad[m] and, when H != nullptr, H[m * m] = -hess W (symmetric, column-major); collective.
 // form 0: value and gradient only; 1: the Hessian sums in the same pass (m <= kMmaDualFused); 2: the pass stores the
 // columns G_i = p_i u^2 - q_i l^2 in G[i] and the weights [free] / h in dvec, H = G^T diag(dvec) G by k_wgram.
@@ -65,6 +70,17 @@ int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double 
 int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu);
 
 typedef int (*MmaIterationFn)(void *user, int iter);
+
+struct MmaDualStats {  // mma_subproblem_solver = dual: counters over every solve; status and max |pg| of the last one
+  int solves = 0, iterations = 0, evaluations = 0, last_status = 0;
+  double last_pg = 0.0;
+};
+// mma_globalization = conservative: raises of rho so far, in the last MMA iteration and the most in one, iterations that
+// spent mma_gcmma_max_inner raises, and the m + 1 values of rho the last iteration was accepted with
+struct MmaGcmmaStats {
+  int inner_total = 0, inner_last = 0, inner_max = 0, cap_hits = 0;
+  std::vector<double> rho;
+};
 
 class MMA : public Problem {
  public:
@@ -105,50 +121,57 @@ class MMA : public Problem {
     return prob->sparseCorrection(U, nv, alpha, cw, out, acc);
   }
 
-  Problem *prob;
-  Options opts;
-  InteriorPoint *ip;
-  int m;
-  int use_true_mma, mma_iter, subproblem_iter;
-  Vec *xvec, *x1vec, *x2vec, *lbvec, *ubvec, *gvec, *Lvec, *Uvec, *alphavec, *betavec, *p0vec, *q0vec, *rvec,
-      *zlvec, *zuvec, *uinv, *linv, *cwvec, *zwvec;
-  std::vector<Vec *> Avecs, pivecs, qivecs;
-  double fobj;
+  // what the C layer hands out
+  int mma_iter = 0, subproblem_iter = 0;
+  Vec *xvec = nullptr, *Lvec = nullptr, *Uvec = nullptr, *alphavec = nullptr, *betavec = nullptr, *p0vec = nullptr,
+      *q0vec = nullptr, *zlvec = nullptr, *zuvec = nullptr, *zwvec = nullptr;
+  std::vector<Vec *> pivecs, qivecs;
+  double fobj = 0.0;
   std::vector<double> cons, b, z;
   std::string history;
-  MmaIterationFn iter_cb;
-  void *iter_cb_user;
-  double last_row[5];  // fobj, l1, linfty, l1_lambda, infeas of the last table row
-  // mma_subproblem_solver = dual: the subproblem is solved through its dual (mma_dual.hpp) -- no InteriorPoint object
-  bool use_dual;
-  std::vector<Vec *> Gvecs;  // the m columns of the panel form (m > kMmaDualFused only)
-  int dual_solves, dual_iterations, dual_evaluations, dual_last_status;
-  double dual_last_pg;
-  MmaDualData dualData();
-  // mma_globalization = conservative (mma_gcmma.hpp; dual sub-solver only): raises of rho so far, in the last MMA
-  // iteration and the most in one, iterations that spent mma_gcmma_max_inner raises, and the m + 1 values of rho the
-  // last iteration was accepted with
-  int gcmma_inner_total, gcmma_inner_last, gcmma_inner_max, gcmma_cap_hits;
-  std::vector<double> gcmma_rho;
+  MmaIterationFn iter_cb = nullptr;
+  void *iter_cb_user = nullptr;
+  double last_row[5] = {};  // fobj, l1, linfty, l1_lambda, infeas of the last table row
+  MmaDualStats dual;
+  MmaGcmmaStats gcmma;
 
  private:
-  MmaParams params() ;
+  // how a subproblem is solved: optimize() decides it from mma_subproblem_solver and mma_globalization.  The dual
+  // modes (mma_dual.hpp, mma_gcmma.hpp) run without an InteriorPoint object
+  enum class Mode { INTERIOR_POINT, DUAL, DUAL_CONSERVATIVE };
+  bool wantDual();
+  MmaParams params();
   int allocate();
   int initializeSubProblem(Vec *xv);
+  int solveSubproblem(Vec **xnew);
   int computeKKTError(double *l1, double *linfty, double *infeas);
   void setMultipliers();
   int checkDualCovers();
   int solveDual(const double *rho = nullptr, double *point_sums = nullptr);
   int solveConservative();
-  bool have_trial_values;  // fobj_trial / cons_trial hold the problem's values at the point initializeSubProblem takes
-  double fobj_trial;
-  std::vector<double> cons_trial;
   void flushHistory();
+
+  Problem *prob;
+  Options opts;
+  InteriorPoint *ip = nullptr;
+  int m;
+  int use_true_mma = 1;
+  Mode mode = Mode::INTERIOR_POINT;
+  bool use_dual = false;  // the sub-solver build() allocated for
+  Vec *x1vec = nullptr, *x2vec = nullptr, *lbvec = nullptr, *ubvec = nullptr, *gvec = nullptr, *rvec = nullptr,
+      *uinv = nullptr, *linv = nullptr, *cwvec = nullptr;
+  std::vector<Vec *> Avecs, Gvecs;  // Gvecs: the m columns of the panel form (dual, m > kMmaDualFused only)
+  // the current subproblem as the kernels take it: device-pointer tables over vectors that live from allocate() (G:
+  // build()) to the destructor.  P0p = [p0 | p_i], Q0q = [q0 | q_i], the columns alone from entry 1 on (sub.p, sub.q);
+  // A = [A_i | zl | zu]; sub.b points at b above
+  std::vector<const double *> P0p, Q0q, A;
+  std::vector<double *> G;
+  MmaDualData sub = {};
+  struct {  // the problem's values at the point the next initializeSubProblem takes (the inner iteration's last trial)
+    bool have = false;
+    double fobj = 0.0;
+    std::vector<double> cons;
+  } trial;
 };
 
 }  // namespace po
-
-struct po_mma_s {
-  po::MMA *mma;
-  std::vector<po_vec> p, q;  // the handle arrays po_mma_get_subproblem hands out
-};
