@@ -842,6 +842,26 @@ int po_mma_get_globalization_stats(po_mma mma, int *inner_total, int *inner_last
                                    const double **rho);
 /* po_mma_dual_eval for the conservative approximations around the expansion point xk with rho[m + 1]: W, grad, hess
  * as there and, when D != NULL, D = d(x) at the primal point.  With every rho_i = 0 the bits of po_mma_dual_eval. */
+/* mma_dual_sparse_constraints = groups (no counterpart in the reference): sparse constraints of the grouped
+ * ("weighting") form stay in the dual.  Local constraint i acts on the variables start + i (nw + skip) + [0, nw) with
+ * one Jacobian value a; linearised, psi_i(x) = a sum x_j + c_i >= 0 (= 0 from constraint nwinequality on), multiplier
+ * zw_i in [0, gamma] (equalities [-gamma, gamma]).  For every lambda each group is solved for zw_i and its x_j by
+ * bracketed Newton iterations on the device; W, grad and hess are those of the resulting concave function.
+ * The stand-alone twin of po_mma_dual_eval: W, grad[m], hess[m * m] (may be NULL) and the vectors x, zl, zu (layout
+ * of L) and zw (layout of c, nwcon values), all four required.  stats (may be NULL) receives 8 values: strict groups,
+ * groups at the lower end, groups at gamma, cap hits, evaluations of psi over all groups, the most of one group,
+ * largest |psi| of a strict group, sum zw_i psi_i.  nwcon = 0: c and zw may be NULL. */
+int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                           const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
+                           int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                           double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
+                           double *stats);
+/* Of the last dual solve with mma_dual_sparse_constraints = groups: the groups with zw strictly inside its interval,
+ * at its lower end and at gamma (at the solution, over all ranks); over the solve's evaluations the most evaluations
+ * of psi one group took, the searches that ran into their step cap, and the largest |psi| of a strict group.  Any
+ * pointer may be NULL. */
+int po_mma_get_dual_group_stats(po_mma mma, long *strict, long *at_lower, long *at_gamma, int *max_inner,
+                                long *cap_hits, double *max_psi);
 int po_mma_dual_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
                          const po_vec *p, const po_vec *q, const double *b, const double *lambda, po_vec xk,
                          const double *rho, int form, double *W, double *grad, double *hess, double *D);

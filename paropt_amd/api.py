@@ -2284,6 +2284,17 @@ class MMA(_Driver):
         check(lib.po_mma_get_dual_stats(self._h, C.byref(a), C.byref(b), C.byref(e), C.byref(st), C.byref(pg)))
         return dict(solves=a.value, iterations=b.value, evaluations=e.value, last_status=st.value, last_pg=pg.value)
 
+    def getDualGroupStats(self):
+        """Of the last dual solve with mma_dual_sparse_constraints='groups' (po_mma_get_dual_group_stats): the groups
+        whose multiplier is strictly inside its interval, at its lower end and at gamma; the most evaluations one
+        group's root search took, the searches that hit their step cap, and the largest |psi| of a strict group."""
+        a, b, g, cap = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        mx, psi = C.c_int(), C.c_double()
+        check(lib.po_mma_get_dual_group_stats(self._h, C.byref(a), C.byref(b), C.byref(g), C.byref(mx), C.byref(cap),
+                                              C.byref(psi)))
+        return dict(strict=a.value, at_lower=b.value, at_gamma=g.value, max_inner=mx.value, cap_hits=cap.value,
+                    max_psi=psi.value)
+
     def getGlobalizationStats(self):
         """Counters of mma_globalization='conservative' (po_mma_get_globalization_stats): raises of rho in total, in
         the last MMA iteration and the most in one, iterations that hit mma_gcmma_max_inner, and rho (ncon + 1 values,
@@ -2362,6 +2373,31 @@ def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hes
                                    g.ctypes.data_as(L.c_double_p),
                                    H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, C.byref(D)))
     return W.value, g[:m], H, D.value
+
+
+def mma_dual_group_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, nwcon, nw, start, skip, a, c, nwinequality,
+                        gamma, point, zw, hessian=True):
+    """The dual function with grouped sparse constraints kept in it (po_mma_dual_group_eval): group i owns the variables
+    start + i (nw + skip) + [0, nw), psi_i = a sum x + c[i] >= 0 (= 0 from group nwinequality on), zw_i in [0, gamma]
+    ([-gamma, gamma]).  point = (x, zl, zu) PVecs and zw (PVec of nwcon, None when nwcon = 0) are filled.  Returns
+    (W, grad, H, stats) with stats a dict of the group solve's counters."""
+    m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_dual_group_eval: ")
+    (ba, bp), (la, lp) = _f64(b), _f64(lam)
+    if ba.size != m or la.size != m:
+        raise ValueError("mma_dual_group_eval: b and lam must hold one entry per constraint")
+    W = C.c_double()
+    g = np.zeros(max(m, 1))
+    H = np.zeros((m, m)) if hessian else None
+    st = np.zeros(8)
+    check(lib.po_mma_dual_group_eval(*head, bp, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
+                                     c.handle if c is not None else None, int(nwinequality), float(gamma),
+                                     C.byref(W), g.ctypes.data_as(L.c_double_p),
+                                     H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, point[0].handle,
+                                     point[1].handle, point[2].handle, zw.handle if zw is not None else None,
+                                     st.ctypes.data_as(L.c_double_p)))
+    stats = dict(strict=int(st[0]), at_lower=int(st[1]), at_gamma=int(st[2]), cap_hits=int(st[3]), steps=int(st[4]),
+                 max_inner=int(st[5]), max_psi=float(st[6]), zw_psi=float(st[7]))
+    return W.value, g[:m], H, stats
 
 
 def mma_gcmma_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, xk, rho, point):

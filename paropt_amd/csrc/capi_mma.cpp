@@ -282,6 +282,105 @@ int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const
   }
   return k_mma_gcmma_rho_sums(ctx, L->d, U->d, g->d, cols.data(), m, L->n, sums);
 }
+int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                           const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
+                           int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                           double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
+                           double *stats) {
+  const char *who = "po_mma_dual_group_eval";
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(L);
+  PO_CHECK_PTR(W);
+  PO_CHECK_PTR(grad);
+  if (m < 0 || m > kMmaDualMax) {
+    po::set_error("%s: m = %d outside 0..%d", who, m, kMmaDualMax);
+    return PO_ERR_ARG;
+  }
+  if (m > 0) {
+    PO_CHECK_PTR(p);
+    PO_CHECK_PTR(q);
+    PO_CHECK_PTR(b);
+    PO_CHECK_PTR(lambda);
+  }
+  std::vector<po_vec> nvecs = {L, U, alpha, beta, p0, q0, x, zl, zu};
+  for (int i = 0; i < m; i++) {
+    nvecs.push_back(p[i]);
+    nvecs.push_back(q[i]);
+  }
+  for (po_vec v : nvecs) {
+    PO_CHECK_PTR(v);
+    if (v->ctx != ctx || v->n != L->n) {
+      po::set_error("%s: vectors of different layouts", who);
+      return PO_ERR_ARG;
+    }
+  }
+  MmaDualGroups g;
+  g.map.nwcon = nwcon;
+  g.map.nw = nw;
+  g.map.start = start;
+  g.map.skip = skip;
+  g.a = a;
+  g.nwinequality = nwinequality;
+  g.gamma = gamma;
+  if (nwcon < 0 || (nwcon > 0 && (nw <= 0 || skip < 0 || !mma_dual_groups_tile(g.map, L->n))) || !(gamma > 0.0) ||
+      nwinequality < 0) {
+    po::set_error("%s: groups (nwcon %lld, nw %d, skip %d, start %lld) must lie inside the %lld variables with "
+                  "nw + skip <= 512, and gamma > 0", who, (long long)nwcon, nw, skip, (long long)start, (long long)L->n);
+    return PO_ERR_ARG;
+  }
+  if (nwcon > 0) {
+    PO_CHECK_PTR(c);
+    PO_CHECK_PTR(zw);
+    if (c->ctx != ctx || zw->ctx != ctx || c->n != nwcon || zw->n != nwcon) {
+      po::set_error("%s: c and zw hold nwcon = %lld values", who, (long long)nwcon);
+      return PO_ERR_ARG;
+    }
+    g.c = c->d;
+  }
+  std::vector<const double *> pp, qq;
+  for (int i = 0; i < m; i++) {
+    pp.push_back(p[i]->d);
+    qq.push_back(q[i]->d);
+  }
+  const MmaDualData s = mma_dual_data(L->d, U->d, alpha->d, beta->d, p0->d, q0->d, pp.data(), qq.data(), b, m, L->n);
+  std::vector<Vec *> work;  // G (m of n), d (n), Uw (m of nwcon), sw (nwcon)
+  std::vector<double *> G, Uw;
+  int rc = PO_OK;
+  const int nw_work = nwcon > 0 ? m + 1 : 0;
+  for (int i = 0; i < m + 1 + nw_work && rc == PO_OK; i++) {
+    Vec *v = vec_new(ctx, i <= m ? L->n : nwcon);
+    if (!v) rc = PO_ERR_HIP;
+    else work.push_back(v);
+  }
+  MmaGroupStats st;
+  if (rc == PO_OK) {
+    for (int i = 0; i < m; i++) G.push_back(work[i]->d);
+    for (int i = 0; i < m && nwcon > 0; i++) Uw.push_back(work[m + 1 + i]->d);
+    rc = k_mma_dual_groups(ctx, s, g, lambda, W, grad, hess, G.data(), work[m]->d, x->d, nwcon > 0 ? zw->d : nullptr,
+                           nwcon > 0 ? Uw.data() : nullptr, nwcon > 0 ? work[2 * m + 1]->d : nullptr, zl->d, zu->d,
+                           &st);
+  }
+  if (rc == PO_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
+  for (Vec *v : work) vec_decref(v);
+  if (rc == PO_OK && stats) {
+    const double out[8] = {(double)st.strict,    (double)st.at_lower, (double)st.at_gamma, (double)st.cap_hits,
+                           (double)st.steps,     (double)st.max_inner, st.max_psi,         st.zw_psi};
+    for (int i = 0; i < 8; i++) stats[i] = out[i];
+  }
+  return rc;
+}
+int po_mma_get_dual_group_stats(po_mma mma, long *strict, long *at_lower, long *at_gamma, int *max_inner,
+                                long *cap_hits, double *max_psi) {
+  PO_CHECK_PTR(mma);
+  const MmaGroupStats &s = mma->mma->groups;
+  if (strict) *strict = s.strict;
+  if (at_lower) *at_lower = s.at_lower;
+  if (at_gamma) *at_gamma = s.at_gamma;
+  if (max_inner) *max_inner = s.max_inner;
+  if (cap_hits) *cap_hits = s.cap_hits;
+  if (max_psi) *max_psi = s.max_psi;
+  return PO_OK;
+}
 int po_mma_get_globalization_stats(po_mma mma, int *inner_total, int *inner_last, int *inner_max, int *cap_hits,
                                    const double **rho) {
   PO_CHECK_PTR(mma);

@@ -35,6 +35,9 @@ MMA::~MMA() {
   for (Vec *v : pivecs) vec_decref(v);
   for (Vec *v : qivecs) vec_decref(v);
   for (Vec *v : Gvecs) vec_decref(v);
+  for (Vec *v : Uwvecs) vec_decref(v);
+  vec_decref(cgvec);
+  vec_decref(swvec);
 }
 
 int MMA::allocate() {  // initialize() :131-232
@@ -78,6 +81,7 @@ int MMA::allocate() {  // initialize() :131-232
 }
 
 bool MMA::wantDual() { return std::string(options().str("mma_subproblem_solver")) == "dual"; }
+bool MMA::wantGroups() { return std::string(options().str("mma_dual_sparse_constraints")) == "groups"; }
 
 int MMA::build() {
   if (ip || xvec) return PO_OK;
@@ -86,9 +90,21 @@ int MMA::build() {
     return PO_ERR_ARG;
   }
   use_dual = wantDual();
+  use_groups = use_dual && wantGroups() && nwcon > 0;
   PO_TRY(allocate());
   if (use_dual) {  // no interior point and none of its 15 + c vectors; uinv / linv serve as the new point / the weights
-    if (m > kMmaDualFused) {
+    if (use_groups) {  // 2 + c vectors of nwcon on top of the panel form's c columns
+      cgvec = vec_new(ctx, nwcon);
+      swvec = vec_new(ctx, nwcon);
+      if (!cgvec || !swvec) return PO_ERR_HIP;
+      for (int i = 0; i < m; i++) {
+        Vec *u = vec_new(ctx, nwcon);
+        if (!u) return PO_ERR_HIP;
+        Uwvecs.push_back(u);
+        Uw.push_back(u->d);
+      }
+    }
+    if (m > kMmaDualFused || use_groups) {
       for (int i = 0; i < m; i++) {
         Vec *g = vec_new(ctx, nlocal);
         if (!g) return PO_ERR_HIP;
@@ -107,9 +123,22 @@ int MMA::build() {
 // ---- the dual sub-solver --------------------------------------------------------------------------
 int MMA::checkDualCovers() {
   const char *why = nullptr;
-  if (nwcon > 0) why = "sparse constraints are not part of the closed-form primal point";
-  else if (ninequality < m) why = "a dense equality constraint has a free multiplier, which can make P or Q negative";
-  else if (options().integer("mma_use_constraint_linearization")) why = "linearised constraints have no rational dual";
+  if (nwcon > 0 && !wantGroups()) {
+    why = "sparse constraints are not part of the closed-form primal point";
+  } else if (nwcon > 0 && std::string(options().str("mma_globalization")) == "conservative") {
+    why = "sparse constraints in groups do not run under mma_globalization = conservative";
+  } else if (nwcon > 0 && (!prob->grouped || prob->nwblock != 1 || prob->sparseUserSolver() ||
+                           prob->gmap.nwcon != nwcon || !mma_dual_groups_tile(prob->gmap, nlocal))) {
+    why = "sparse constraints run through the dual only in the grouped form: one constraint per group of nw "
+          "consecutive variables with one Jacobian value (setWeighting, or a CSR pattern recognised as such), "
+          "nwblock = 1, nw + skip within the 512 variables of a tile, and no quasi-definite solver of the problem's own";
+  }
+  if (why) {
+  } else if (ninequality < m) {
+    why = "a dense equality constraint has a free multiplier, which can make P or Q negative";
+  } else if (options().integer("mma_use_constraint_linearization")) {
+    why = "linearised constraints have no rational dual";
+  }
   if (!why) return PO_OK;
   set_error("MMA: mma_subproblem_solver = dual does not cover this problem: %s", why);
   return PO_ERR_ARG;
@@ -123,13 +152,28 @@ int MMA::solveDual(const double *rho, double *point_sums) {
   std::vector<double> gamma(m, o.real("penalty_gamma")), lambda(z);
   MmaDualResult res;
   const MmaDualRho r{xvec->d, rho};
-  auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) {
+  MmaGroupStats over;  // (max_inner, cap_hits, max_psi over the evaluations of this solve)
+  auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) -> int {
+    if (use_groups) {
+      MmaGroupStats st;
+      PO_TRY(k_mma_dual_groups(ctx, sub, grp, lam, W, g, want_h ? H : nullptr, G.data(), linv->d, uinv->d, zwvec->d,
+                               Uw.data(), swvec->d, nullptr, nullptr, &st));
+      over.max_inner = std::max(over.max_inner, st.max_inner);
+      over.cap_hits += st.cap_hits;
+      over.max_psi = std::max(over.max_psi, st.max_psi);
+      return PO_OK;
+    }
     return k_mma_dual(ctx, sub, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d,
                       rho ? &r : nullptr);
   };
   PO_TRY(mma_dual_solve(m, gamma.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"), eval,
                         lambda.data(), &res));
-  if (rho) PO_TRY(k_mma_gcmma_point(ctx, sub, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
+  if (use_groups) {
+    PO_TRY(k_mma_group_solve(ctx, sub, grp, lambda.data(), uinv->d, zwvec->d, zlvec->d, zuvec->d, &groups));
+    groups.max_inner = std::max(groups.max_inner, over.max_inner);
+    groups.cap_hits += over.cap_hits;
+    groups.max_psi = std::max(groups.max_psi, over.max_psi);
+  } else if (rho) PO_TRY(k_mma_gcmma_point(ctx, sub, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
   else PO_TRY(k_mma_dual_point(ctx, sub, lambda.data(), uinv->d, zlvec->d, zuvec->d));
   z = lambda;
   subproblem_iter += res.evaluations;
@@ -236,6 +280,20 @@ int MMA::initializeSubProblem(Vec *xv) {  // :523-757
     return PO_ERR_USER;
   }
   if (nwcon > 0 && prob->evalSparseCon(xvec, cwvec) != 0) return PO_ERR_USER;
+  if (use_groups) {  // psi_i(x) = a sum_{G_i} x + c_i, c_i = cw_i(x^k) - a sum_{G_i} x^k
+    if (!prob->grouped || prob->gmap.nwcon != nwcon) {
+      set_error("MMA: mma_dual_sparse_constraints = groups: the sparse constraints lost their grouped form (the "
+                "entries of the Jacobian are no longer all equal)");
+      return PO_ERR_ARG;
+    }
+    grp.map = prob->gmap;
+    grp.a = prob->group_alpha;
+    grp.c = cgvec->d;
+    grp.nwinequality = nwinequality;
+    grp.gamma = options().real("penalty_gamma");
+    PO_TRY(k_copy(ctx, cgvec->d, cwvec->d, nwcon));
+    PO_TRY(k_group_sum(ctx, grp.map, cgvec->d, 1, 0.0, -grp.a, xvec->d));
+  }
   {  // the table row :571-596
     double l1 = 0.0, linfty = 0.0, infeas = 0.0, l1_lambda = 0.0;
     PO_TRY(computeKKTError(&l1, &linfty, &infeas));
@@ -310,7 +368,7 @@ int MMA::optimize() {  // :318-379
   }
   if (want_dual) PO_TRY(checkDualCovers());  // refused before anything is allocated or run
   PO_TRY(build());
-  if (want_dual != use_dual) {
+  if (want_dual != use_dual || (use_dual && nwcon > 0 && wantGroups() != use_groups)) {
     set_error("MMA: mma_subproblem_solver cannot change once the solver's vectors exist");
     return PO_ERR_ARG;
   }

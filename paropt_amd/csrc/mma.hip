@@ -233,6 +233,19 @@ __device__ __forceinline__ DualPoint dual_point(f64x2 P, f64x2 Q, f64x2 L, f64x2
   t.fr = (f64x2){f0, f1};
   return t;
 }
+// the same quantities at a stored point x (the grouped dual: x comes from the group solve): free where x lies
+// strictly inside (alpha, beta)
+__device__ __forceinline__ DualPoint dual_point_at(f64x2 x, f64x2 L, f64x2 U, f64x2 a, f64x2 b, bool has2) {
+  DualPoint t;
+  t.x = x;
+  t.u.x = 1.0 / (U.x - x.x);
+  t.l.x = 1.0 / (x.x - L.x);
+  t.u.y = has2 ? 1.0 / (U.y - x.y) : 0.0;
+  t.l.y = has2 ? 1.0 / (x.y - L.y) : 0.0;
+  t.fr.x = (x.x > a.x && x.x < b.x) ? 1.0 : 0.0;
+  t.fr.y = (has2 && x.y > a.y && x.y < b.y) ? 1.0 : 0.0;
+  return t;
+}
 // P, Q += sum_{j <= i < j + B} lambda_i (p_i, q_i): 2 B loads in flight, issued back to back before their arithmetic
 template <int B>
 __device__ __forceinline__ void dual_pq_batch(const PtrTable &Pt, const PtrTable &Qt, const CoefTable &lam, int j,
@@ -305,6 +318,7 @@ __device__ __forceinline__ void dual_block_reduce(double (&a)[N], double *__rest
 // MODE 3 (RHO only), the point pass of an inner iteration: x, zl, zu are stored and the slots are
 // {Delta_0, Delta_i[MC], D}, Delta_i = sum p_i (u - u_k) + q_i (l - l_k) = f~_i(x) - f~_i(xk), with
 // u - u_k = (x - xk) u u_k and l - l_k = -(x - xk) l l_k (no cancellation against n).
+// MODE 4 (plain form only), the sums of the grouped dual: as 2, at the stored point xin instead of the closed form.
 template <int MC, int MODE, bool RHO>
 struct DualSlots {
   static constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
@@ -320,14 +334,18 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
                                           double *__restrict__ partials, double *sm, int64_t qfirst, int64_t qstride,
                                           const double *__restrict__ xk,
                                           const CoefTable &rho, double sigma, double *__restrict__ xo,
-                                          double *__restrict__ zlo, double *__restrict__ zuo) {
+                                          double *__restrict__ zlo, double *__restrict__ zuo,
+                                          const double *__restrict__ xin = nullptr) {
   constexpr bool HOLD = MC <= PO_MMA_DUAL_HOLD;
   constexpr bool POINT = MODE == 3;
-  constexpr bool HESS = MODE == 1 || MODE == 2;
+  constexpr bool STORED = MODE == 4;
+  constexpr bool PANEL = MODE == 2 || STORED;
+  constexpr bool HESS = MODE == 1 || PANEL;
   constexpr int NVB = 8;
   constexpr int NS = DualSlots<MC, MODE, RHO>::NS;
   static_assert(MODE != 1 || MC <= kMmaDualFused, "the fused Hessian needs the columns in registers");
   static_assert(!POINT || RHO, "the point pass with sums belongs to the rho form");
+  static_assert(!STORED || !RHO, "the stored point belongs to the plain form");
   double acc[NS];
 #pragma unroll
   for (int s = 0; s < NS; s++) acc[s] = 0.0;
@@ -370,7 +388,8 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
       P = fma2(sigma, wU, P);
       Q = fma2(sigma, wL, Q);
     }
-    const DualPoint t = dual_point(P, Q, Lv, Uv, av, bv, has2);
+    const DualPoint t = STORED ? dual_point_at(ld_nt(xin + 2 * q), Lv, Uv, av, bv, has2)
+                               : dual_point(P, Q, Lv, Uv, av, bv, has2);
     const f64x2 u2 = t.u * t.u, l2 = t.l * t.l;
     f64x2 su = t.u, sl = t.l;  // what the column sums are taken on
     if (RHO) {
@@ -406,7 +425,7 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
       const f64x2 h = 2.0 * (P * (u2 * t.u) + Q * (l2 * t.l));
       dw.x = t.fr.x != 0.0 ? 1.0 / h.x : 0.0;
       dw.y = t.fr.y != 0.0 ? 1.0 / h.y : 0.0;
-      if (MODE == 2) st_nt(dout + 2 * q, dw);
+      if (PANEL) st_nt(dout + 2 * q, dw);
       // w_U u^2 - w_L l^2 = (a - b)(a + b) / (U - L) with a = (U - xk) u = 1 + dx u, b = (xk - L) l = 1 - dx l: the
       // derivative of d, which vanishes at xk -- taken in the form that does not cancel there
       if (RHO) gd = dx * (t.u + t.l) * (2.0 + dx * (t.u - t.l)) * rs;
@@ -420,7 +439,7 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
           const f64x2 ql = qv[i] * l2;
           gv[i] = (f64x2){fma(pv[i].x, u2.x, -ql.x), fma(pv[i].y, u2.y, -ql.y)};
           if (RHO) gv[i] = fma2(rho.a[i], gd, gv[i]);
-          if (MODE == 2 && i < m) st_nt(Gt.p[i] + 2 * q, gv[i]);
+          if (PANEL && i < m) st_nt(Gt.p[i] + 2 * q, gv[i]);
         }
       }
       if (MODE == 1) {
@@ -451,7 +470,7 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
 #pragma unroll
           for (int v = 0; v < NVB; v++) {
             acc[1 + j + v] = dot4(cp[v], su, cq[v], sl, acc[1 + j + v]);
-            if (MODE == 2 && j + v < m) {
+            if (PANEL && j + v < m) {
               const f64x2 ql = cq[v] * l2;
               f64x2 gc = (f64x2){fma(cp[v].x, u2.x, -ql.x), fma(cp[v].y, u2.y, -ql.y)};
               if (RHO) gc = fma2(rho.a[j + v], gd, gc);
@@ -725,6 +744,407 @@ int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double 
   count_bytes(c, 2 * s.m + 6 + 3, s.n);
   PO_MLAUNCH(mma_dual_point_kernel, grid_for(c, s.n, kBpcPanel), s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct,
              s.m, s.n, x, zl, zu);
+  return PO_OK;
+}
+
+// ---- grouped sparse constraints in the dual (mma.hpp) ----------------------------------------------------------------
+// the sums at the stored point: the panel form of the pass above with x loaded
+template <int MC>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_stored_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                           const double *__restrict__ beta, const double *__restrict__ p0,
+                           const double *__restrict__ q0, const double *__restrict__ x, PtrTable Pt, PtrTable Qt,
+                           CoefTable lam, int m, int64_t n, PtrTableW Gt, double *__restrict__ dout,
+                           double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, 4, false>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  dual_body<MC, 4, false>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, Gt, dout, partials, sm, qfirst, qstride,
+                          nullptr, lam, 0.0, nullptr, nullptr, nullptr, x);
+}
+
+// sum of nw consecutive LDS values in index order (row_sum of wcon.hip)
+__device__ __forceinline__ double row_sum_lds(const double *row, int nw) {
+  double sacc = 0.0;
+  int k = 0;
+  for (; k + 4 <= nw; k += 4) {
+    const double a = row[k], b = row[k + 1], c = row[k + 2], e = row[k + 3];
+    sacc += a;
+    sacc += b;
+    sacc += c;
+    sacc += e;
+  }
+  for (; k < nw; k++) sacc += row[k];
+  return sacc;
+}
+// One element of a group: phi'(x) = P u^2 - Q l^2 is increasing on (L, U); ga, gb are its values at alpha and beta.
+struct GroupEl {
+  double P, Q, L, U, a, b, ga, gb;
+};
+__device__ __forceinline__ double group_phi1(double P, double Q, double L, double U, double x) {
+  const double u = 1.0 / (U - x), l = 1.0 / (x - L);
+  const double ql = Q * (l * l);
+  return fma(P, u * u, -ql);
+}
+// clamp(root of phi'(x) = t, alpha, beta) by a bracketed Newton iteration from x0: a step that leaves the bracket is
+// replaced by its midpoint; it ends when the iterate or the bracket stops moving.  *capped is raised at the step cap.
+__device__ __forceinline__ double group_el_root(const GroupEl &e, double t, double x0, int &capped) {
+  if (!(t > e.ga)) return e.a;
+  if (!(t < e.gb)) return e.b;
+  double lo = e.a, hi = e.b, x = x0;
+  if (!(x > lo && x < hi)) x = 0.5 * (lo + hi);
+  int it = 0;
+  for (; it < kGroupNewtonCap; it++) {
+    const double u = 1.0 / (e.U - x), l = 1.0 / (x - e.L);
+    const double u2 = u * u, l2 = l * l;
+    const double f = fma(e.P, u2, -(e.Q * l2)) - t;
+    const double h = 2.0 * (e.P * (u2 * u) + e.Q * (l2 * l));
+    if (f < 0.0) lo = x;
+    else if (f > 0.0) hi = x;
+    else break;
+    double xn = x - f / h;
+    if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+    if (!(xn > lo && xn < hi) || xn == x) break;
+    x = xn;
+  }
+  if (it == kGroupNewtonCap) capped++;
+  return x;
+}
+// the closed form of the plain dual (dual_point1: same expressions, same bits)
+__device__ __forceinline__ double group_closed_form(double P, double Q, double L, double U, double a, double b) {
+  const double sp = sqrt(P), sq = sqrt(Q);
+  const double r = 1.0 / (sp + sq);
+  const double xs = fma(sp, L, sq * U) * r;
+  return fmin(fmax(xs, a), b);
+}
+// P, Q of the element at index i, in the fma order of dual_pq_all (four column pairs requested together)
+__device__ __forceinline__ void group_pq(const double *__restrict__ p0, const double *__restrict__ q0,
+                                         const PtrTable &Pt, const PtrTable &Qt, const CoefTable &lam, int m,
+                                         int64_t i, double &P, double &Q) {
+  P = __builtin_nontemporal_load(p0 + i);
+  Q = __builtin_nontemporal_load(q0 + i);
+  int j = 0;
+  for (; j + 4 <= m; j += 4) {
+    const double a0 = __builtin_nontemporal_load(Pt.p[j] + i), a1 = __builtin_nontemporal_load(Pt.p[j + 1] + i),
+                 a2 = __builtin_nontemporal_load(Pt.p[j + 2] + i), a3 = __builtin_nontemporal_load(Pt.p[j + 3] + i);
+    const double b0 = __builtin_nontemporal_load(Qt.p[j] + i), b1 = __builtin_nontemporal_load(Qt.p[j + 1] + i),
+                 b2 = __builtin_nontemporal_load(Qt.p[j + 2] + i), b3 = __builtin_nontemporal_load(Qt.p[j + 3] + i);
+    P = fma(lam.a[j], a0, P);
+    Q = fma(lam.a[j], b0, Q);
+    P = fma(lam.a[j + 1], a1, P);
+    Q = fma(lam.a[j + 1], b1, Q);
+    P = fma(lam.a[j + 2], a2, P);
+    Q = fma(lam.a[j + 2], b2, Q);
+    P = fma(lam.a[j + 3], a3, P);
+    Q = fma(lam.a[j + 3], b3, Q);
+  }
+  for (; j < m; j++) {
+    const double a0 = __builtin_nontemporal_load(Pt.p[j] + i), b0 = __builtin_nontemporal_load(Qt.p[j] + i);
+    P = fma(lam.a[j], a0, P);
+    Q = fma(lam.a[j], b0, Q);
+  }
+}
+// x, and with zl != nullptr the bound multipliers, of an element whose multiplier term is t (0 outside the groups)
+__device__ __forceinline__ void group_store(const GroupEl &e, double x, double t, int64_t i, double *__restrict__ xo,
+                                            double *__restrict__ zl, double *__restrict__ zu) {
+  xo[i] = x;
+  if (zl) {
+    const double r = group_phi1(e.P, e.Q, e.L, e.U, x) - t;
+    zl[i] = x == e.a ? fmax(r, 0.0) : 0.0;
+    zu[i] = x == e.b ? fmax(-r, 0.0) : 0.0;
+  }
+}
+// {sum zw psi, strict, at zlo, at gamma, cap hits, steps}, {most steps of a group, |psi| strict}
+constexpr int kGroupSums = 6, kGroupMaxs = 2;
+// The group solve.  A workgroup owns a tile of G whole periods (G period <= kGroupTile): lane <-> variable, two
+// variables per lane, P and Q in registers for the whole tile.  Every round the lanes of the unfinished groups solve
+// their elements at the group's current zw and put x and [free] / h into LDS (rows of the padded stride of wcon.hip);
+// one thread per group takes the two row sums, psi = a sum x + c and psi' = a^2 sum [free] / h, and moves zw: Newton
+// inside the bracket [lo, hi], whose upper end gamma is evaluated only when a step reaches it; the midpoint when the
+// step leaves the bracket.  The rounds end when every group of the tile has ended.  Variables before `start`, in the
+// gaps between the groups and behind the last period take the closed form.
+__global__ void __launch_bounds__(kBlock)
+    mma_group_solve_kernel(GroupMap gm, double ga, const double *__restrict__ cvec, int64_t nwineq, double gamma,
+                           const double *__restrict__ L, const double *__restrict__ U,
+                           const double *__restrict__ alpha, const double *__restrict__ beta,
+                           const double *__restrict__ p0, const double *__restrict__ q0, PtrTable Pt, PtrTable Qt,
+                           CoefTable lam, int m, int64_t n, int G, int64_t ntiles, double *__restrict__ xo,
+                           double *__restrict__ zwo, double *__restrict__ zl, double *__restrict__ zu,
+                           double *__restrict__ partials) {
+  __shared__ double smx[kGroupTile + kBlock], smd[kGroupTile + kBlock];
+  __shared__ double sz[kBlock];
+  __shared__ int sdone[kBlock];
+  __shared__ double red[4 * (kGroupSums + kGroupMaxs)];
+  const int period = gm.nw + gm.skip;
+  const int pad = (period & 1) ? 0 : 1, rstride = period + pad;
+  const int tid = threadIdx.x;
+  const int gi0 = tid / period, k0 = tid - gi0 * period;
+  const int gi1 = (tid + kBlock) / period, k1 = tid + kBlock - gi1 * period;
+  const int s0 = tid + pad * gi0, s1 = tid + kBlock + pad * gi1;
+  const int64_t span = gm.start + gm.nwcon * (int64_t)period;
+  const int64_t cover_end = span < n ? span : n;
+  double acc_zp = 0.0, acc_strict = 0.0, acc_lo = 0.0, acc_gam = 0.0, acc_psi = 0.0, acc_steps = 0.0;
+  int capped = 0, most = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t g0 = tile * G;
+    const int ng = (int)((gm.nwcon - g0) < G ? (gm.nwcon - g0) : G);
+    const int64_t v0 = gm.start + g0 * (int64_t)period;
+    int64_t vend = v0 + (int64_t)ng * period;
+    if (vend > n) vend = n;
+    const int nvv = (int)(vend - v0);
+    const bool in0 = tid < nvv, in1 = tid + kBlock < nvv;
+    const bool grp0 = in0 && k0 < gm.nw, grp1 = in1 && k1 < gm.nw;
+    const int64_t i0 = v0 + (in0 ? tid : 0), i1 = v0 + (in1 ? tid + kBlock : 0);
+    GroupEl e0, e1;
+    e0.L = __builtin_nontemporal_load(L + i0);
+    e1.L = __builtin_nontemporal_load(L + i1);
+    e0.U = __builtin_nontemporal_load(U + i0);
+    e1.U = __builtin_nontemporal_load(U + i1);
+    e0.a = __builtin_nontemporal_load(alpha + i0);
+    e1.a = __builtin_nontemporal_load(alpha + i1);
+    e0.b = __builtin_nontemporal_load(beta + i0);
+    e1.b = __builtin_nontemporal_load(beta + i1);
+    group_pq(p0, q0, Pt, Qt, lam, m, i0, e0.P, e0.Q);
+    group_pq(p0, q0, Pt, Qt, lam, m, i1, e1.P, e1.Q);
+    // the closed form: the point of every element at zw = 0, and the start of the root searches
+    const double xc0 = group_closed_form(e0.P, e0.Q, e0.L, e0.U, e0.a, e0.b);
+    const double xc1 = group_closed_form(e1.P, e1.Q, e1.L, e1.U, e1.a, e1.b);
+    double x0 = xc0, x1 = xc1, t0 = 0.0, t1 = 0.0;
+    e0.ga = e0.gb = e1.ga = e1.gb = 0.0;
+    if (grp0) {
+      e0.ga = group_phi1(e0.P, e0.Q, e0.L, e0.U, e0.a);
+      e0.gb = group_phi1(e0.P, e0.Q, e0.L, e0.U, e0.b);
+    }
+    if (grp1) {
+      e1.ga = group_phi1(e1.P, e1.Q, e1.L, e1.U, e1.a);
+      e1.gb = group_phi1(e1.P, e1.Q, e1.L, e1.U, e1.b);
+    }
+    // the state of group g0 + tid
+    const bool mine = tid < ng;
+    const double zlo = (mine && g0 + tid >= nwineq) ? -gamma : 0.0;
+    const double cg = mine ? cvec[g0 + tid] : 0.0;
+    double zw = zlo, lo = zlo, hi = gamma, psi = 0.0;
+    bool hik = false, active = mine;
+    int steps = 0;
+    if (mine) {
+      sz[tid] = zw;
+      sdone[tid] = 0;
+    }
+    __syncthreads();
+    for (;;) {
+      if (grp0 && !sdone[gi0]) {
+        t0 = ga * sz[gi0];
+        x0 = t0 == 0.0 ? xc0 : group_el_root(e0, t0, x0, capped);
+        const double u = 1.0 / (e0.U - x0), l = 1.0 / (x0 - e0.L);
+        smx[s0] = x0;
+        smd[s0] = (x0 > e0.a && x0 < e0.b) ? 1.0 / (2.0 * (e0.P * (u * u * u) + e0.Q * (l * l * l))) : 0.0;
+      }
+      if (grp1 && !sdone[gi1]) {
+        t1 = ga * sz[gi1];
+        x1 = t1 == 0.0 ? xc1 : group_el_root(e1, t1, x1, capped);
+        const double u = 1.0 / (e1.U - x1), l = 1.0 / (x1 - e1.L);
+        smx[s1] = x1;
+        smd[s1] = (x1 > e1.a && x1 < e1.b) ? 1.0 / (2.0 * (e1.P * (u * u * u) + e1.Q * (l * l * l))) : 0.0;
+      }
+      __syncthreads();
+      if (active) {
+        const double sx = row_sum_lds(smx + tid * rstride, gm.nw), sd = row_sum_lds(smd + tid * rstride, gm.nw);
+        psi = fma(ga, sx, cg);
+        steps++;
+        if ((zw == zlo && psi >= 0.0) || (zw == gamma && psi <= 0.0) || psi == 0.0) {
+          active = false;
+        } else {
+          if (psi < 0.0) {
+            lo = zw;
+          } else {
+            hi = zw;
+            hik = true;
+          }
+          double zn = sd > 0.0 ? zw - psi / (ga * ga * sd) : hi;
+          if (!(zn > lo && zn < hi)) zn = hik ? 0.5 * (lo + hi) : gamma;
+          if ((hik && !(zn > lo && zn < hi)) || zn == zw) {
+            active = false;
+          } else if (steps >= kGroupNewtonCap) {
+            active = false;
+            capped++;
+          } else {
+            zw = zn;
+            sz[tid] = zw;
+          }
+        }
+        if (!active) sdone[tid] = 1;
+      }
+      if (!__syncthreads_or(active ? 1 : 0)) break;
+    }
+    if (mine) {
+      zwo[g0 + tid] = zw;
+      acc_zp = fma(zw, psi, acc_zp);
+      const bool strict = zw > zlo && zw < gamma;
+      if (strict) {
+        acc_strict += 1.0;
+        acc_psi = fmax(acc_psi, fabs(psi));
+      } else if (zw < gamma) {
+        acc_lo += 1.0;
+      } else {
+        acc_gam += 1.0;
+      }
+      most = steps > most ? steps : most;
+      acc_steps += (double)steps;
+    }
+    if (in0) group_store(e0, x0, grp0 ? t0 : 0.0, i0, xo, zl, zu);
+    if (in1) group_store(e1, x1, grp1 ? t1 : 0.0, i1, xo, zl, zu);
+  }
+  // variables outside every period: the closed form
+  const int64_t nout = gm.start + (n - cover_end);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + tid; i < nout; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t g = i < gm.start ? i : cover_end + (i - gm.start);
+    GroupEl e;
+    e.L = L[g];
+    e.U = U[g];
+    e.a = alpha[g];
+    e.b = beta[g];
+    e.ga = e.gb = 0.0;
+    group_pq(p0, q0, Pt, Qt, lam, m, g, e.P, e.Q);
+    group_store(e, group_closed_form(e.P, e.Q, e.L, e.U, e.a, e.b), 0.0, g, xo, zl, zu);
+  }
+  if ((n & 1) && blockIdx.x == 0 && tid == 0) {  // the pad element of an odd length stays zero
+    xo[n] = 0.0;
+    if (zl) zl[n] = zu[n] = 0.0;
+  }
+  // the sums and maxima of the workgroup, in a fixed order
+  double v[kGroupSums + kGroupMaxs] = {acc_zp,        acc_strict, acc_lo, acc_gam, (double)capped, acc_steps,
+                                       (double)most, acc_psi};
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int j = 0; j < kGroupSums + kGroupMaxs; j++) {
+    double r = v[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double other = __shfl_xor(r, o, 64);
+      r = j < kGroupSums ? r + other : fmax(r, other);
+    }
+    if (lane == 0) red[wave * (kGroupSums + kGroupMaxs) + j] = r;
+  }
+  __syncthreads();
+  if (tid < kGroupSums + kGroupMaxs) {
+    constexpr int N = kGroupSums + kGroupMaxs;
+    const double a = red[tid], b = red[N + tid], cc = red[2 * N + tid], d = red[3 * N + tid];
+    partials[(size_t)tid * gridDim.x + blockIdx.x] = tid < kGroupSums ? (a + b) + (cc + d) : fmax(fmax(a, b), fmax(cc, d));
+  }
+}
+
+bool mma_dual_groups_tile(const GroupMap &m, int64_t n) {
+  const int64_t period = (int64_t)m.nw + m.skip;
+  if (m.nwcon <= 0) return true;
+  return m.nw > 0 && period <= kGroupTile && m.start >= 0 && m.start + (m.nwcon - 1) * period + m.nw <= n;
+}
+
+int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *x,
+                      double *zw, double *zl, double *zu, MmaGroupStats *st) {
+  PtrTable pt, qt;
+  CoefTable ct;
+  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  GroupMap gm = g.map;
+  if (gm.nwcon <= 0) {  // no group: every variable takes the closed form
+    gm = GroupMap();
+    gm.nw = 1;
+  }
+  if (!mma_dual_groups_tile(gm, s.n) || (zl == nullptr) != (zu == nullptr)) {
+    set_error("MMA dual: the group map (nwcon %lld, nw %d, skip %d, start %lld) does not tile %lld variables",
+              (long long)gm.nwcon, gm.nw, gm.skip, (long long)gm.start, (long long)s.n);
+    return PO_ERR_ARG;
+  }
+  const int period = gm.nw + gm.skip;
+  int G = kGroupTile / period;
+  if (G > kBlock) G = kBlock;
+  const int64_t ntiles = (gm.nwcon + G - 1) / G;
+  count_bytes(c, 2 * s.m + 6 + 1 + (zl ? 2 : 0), s.n);
+  count_bytes(c, 2.0, gm.nwcon);
+  int64_t want = ntiles > (s.n + kBlock - 1) / kBlock / 8 ? ntiles : (s.n + kBlock - 1) / kBlock / 8;
+  if (want > (int64_t)c->num_cu * 4) want = (int64_t)c->num_cu * 4;
+  const int grid = want < 1 ? 1 : (int)want;
+  PO_TRY(ensure_partials(c, (size_t)grid * (kGroupSums + kGroupMaxs)));
+  PO_MLAUNCH(mma_group_solve_kernel, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta, s.p0,
+             s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials);
+  double out[kGroupSums + kGroupMaxs];
+  PO_TRY(reduce_finish(c, grid, kGroupSums, 0, kGroupMaxs, out, true));
+  if (st) {
+    st->zw_psi = out[0];
+    st->strict = (long)out[1];
+    st->at_lower = (long)out[2];
+    st->at_gamma = (long)out[3];
+    st->cap_hits = (long)out[4];
+    st->steps = (long)out[5];
+    st->max_inner = (int)out[6];
+    st->max_psi = out[7];
+  }
+  return PO_OK;
+}
+
+// sw_i <- [zlo_i < zw_i < gamma and sw_i > 0] / sw_i: the weights of the Gram over the group panel
+__global__ void __launch_bounds__(kBlock)
+    mma_group_weights_kernel(const double *__restrict__ zw, int64_t nwcon, int64_t nwineq, double gamma,
+                             double *__restrict__ sw) {
+  PO_M_LOOP(i, nwcon) {
+    const double z = zw[i], sv = sw[i];
+    const double zlo = i >= nwineq ? -gamma : 0.0;
+    sw[i] = (z > zlo && z < gamma && sv > 0.0) ? 1.0 / sv : 0.0;
+  }
+  // (the pad element of an odd length: its panel entries are zeros)
+  if ((nwcon & 1) && blockIdx.x == 0 && threadIdx.x == 0) sw[nwcon] = 0.0;
+}
+
+int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *W,
+                      double *grad, double *H, double *const *G, double *dvec, double *x, double *zw,
+                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st) {
+  const int m = s.m;
+  MmaGroupStats local;
+  if (!st) st = &local;
+  PO_TRY(k_mma_group_solve(c, s, g, lambda, x, zw, zl, zu, st));
+  PtrTable pt, qt;
+  CoefTable ct;
+  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  if (!dvec || (m > 0 && !G)) {
+    set_error("MMA dual: the grouped evaluation needs its %d column vectors and the weight vector", m);
+    return PO_ERR_ARG;
+  }
+  PtrTableW gt;
+  for (int i = 0; i < kMaxPanel; i++) gt.p[i] = i < m ? G[i] : nullptr;
+  count_bytes(c, 2 * m + 7 + m + 1, s.n);
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  int ns = 0;
+  PO_TRY(with_capacity(m, [&](auto MC) -> int {
+    constexpr int kMC = decltype(MC)::value;
+    ns = DualSlots<kMC, 4, false>::NS;
+    PO_TRY(ensure_partials(c, (size_t)grid * ns));
+    PO_MLAUNCH((mma_dual_stored_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, x, pt, qt, ct, m, s.n, gt,
+               dvec, c->d_partials);
+    return PO_OK;
+  }));
+  double sums[1 + 96];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
+  double w = sums[0] - st->zw_psi;
+  for (int i = 0; i < m; i++) {
+    w += lambda[i] * s.b[i];
+    grad[i] = sums[1 + i] + s.b[i];
+  }
+  *W = w;
+  if (!H || m <= 0) return PO_OK;
+  PO_TRY(k_wgram(c, dvec, G, m, s.n, H));
+  if (g.map.nwcon <= 0 && c->size == 1) return PO_OK;
+  if (!Uw || !sw) {
+    set_error("MMA dual: the grouped Hessian needs its %d group columns and the group weights", m);
+    return PO_ERR_ARG;
+  }
+  std::vector<double> H2((size_t)m * m, 0.0);
+  PO_TRY(k_group_panel(c, g.map, G, m, dvec, 1.0, Uw));
+  PO_TRY(k_group_sum(c, g.map, sw, 0, 0.0, 1.0, dvec));
+  if (g.map.nwcon > 0) {
+    count_bytes(c, 3.0, g.map.nwcon);
+    PO_MLAUNCH(mma_group_weights_kernel, grid_for(c, g.map.nwcon), zw, g.map.nwcon, g.nwinequality, g.gamma, sw);
+  }
+  PO_TRY(k_wgram(c, sw, Uw, m, g.map.nwcon, H2.data()));
+  for (size_t i = 0; i < H2.size(); i++) H[i] -= H2[i];
   return PO_OK;
 }
 

@@ -69,6 +69,42 @@ int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double 
 // the primal point and the bound multipliers at lambda
 int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu);
 
+// ---- the dual with grouped ("weighting") sparse constraints (mma_dual_sparse_constraints = groups) -----------------
+// Group i owns the local variables start + i (nw + skip) + [0, nw); its linearised constraint is
+//   psi_i(x) = a sum_{j in G_i} x_j + c_i >= 0   (= 0 from local constraint nwinequality on),
+// and its multiplier zw_i lies in [zlo_i, gamma], zlo_i = 0 for an inequality, -gamma for an equality.  With
+// phi_j(x) = P_j / (U_j - x) + Q_j / (x - L_j) the dual function is
+//   W(lambda) = sum_groups max_zw min_x [sum_{G_i} phi_j(x_j) - zw_i psi_i(x)] + sum_ungrouped phi_j + lambda . b:
+// every group is a one-dimensional root search in zw on top of one-dimensional root searches in x.
+constexpr int kGroupNewtonCap = 100;  // steps of one root search (zw of a group, x of an element); hits are counted
+struct MmaDualGroups {
+  GroupMap map;
+  double a = -1.0;            // the one value of the Jacobian's entries
+  const double *c = nullptr;  // device, nwcon values
+  int64_t nwinequality = 0;
+  double gamma = 0.0;
+};
+struct MmaGroupStats {  // of one group-solve pass, over all ranks
+  double zw_psi = 0.0;  // sum zw_i psi_i
+  long strict = 0, at_lower = 0, at_gamma = 0, cap_hits = 0;
+  long steps = 0;        // evaluations of psi over all groups
+  int max_inner = 0;     // most evaluations of psi one group took
+  double max_psi = 0.0;  // largest |psi| over the strict groups
+};
+// the group map runs through the tiled solve: one constraint per group (nwblock = 1), period within a tile, every
+// group inside the n local variables
+bool mma_dual_groups_tile(const GroupMap &m, int64_t n);
+// x (n) and zw (nwcon) at lambda; zl, zu (both or neither) receive the bound multipliers with the group term in
+// r = P u^2 - Q l^2 - a zw; collective
+int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *x,
+                      double *zw, double *zl, double *zu, MmaGroupStats *st);
+// The evaluation: the group solve, then the sums at the stored point in the panel form (G: m columns, dvec: n), and
+// with H != nullptr  H = G^T diag(dvec) G - sum over the strict groups of a_g a_g^T / s_g  (Uw: m columns of nwcon,
+// sw: nwcon).  x and zw are left at the point of lambda, zl and zu (both or neither) as in the group solve; collective.
+int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *W,
+                      double *grad, double *H, double *const *G, double *dvec, double *x, double *zw,
+                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st);
+
 typedef int (*MmaIterationFn)(void *user, int iter);
 
 struct MmaDualStats {  // mma_subproblem_solver = dual: counters over every solve; status and max |pg| of the last one
@@ -134,12 +170,16 @@ class MMA : public Problem {
   double last_row[5] = {};  // fobj, l1, linfty, l1_lambda, infeas of the last table row
   MmaDualStats dual;
   MmaGcmmaStats gcmma;
+  // mma_dual_sparse_constraints = groups: the classes of the groups at the last solve's point, and over the
+  // evaluations of that solve the most steps of one group, the cap hits and the largest |psi| of a strict group
+  MmaGroupStats groups;
 
  private:
   // how a subproblem is solved: optimize() decides it from mma_subproblem_solver and mma_globalization.  The dual
   // modes (mma_dual.hpp, mma_gcmma.hpp) run without an InteriorPoint object
   enum class Mode { INTERIOR_POINT, DUAL, DUAL_CONSERVATIVE };
   bool wantDual();
+  bool wantGroups();
   MmaParams params();
   int allocate();
   int initializeSubProblem(Vec *xv);
@@ -158,8 +198,14 @@ class MMA : public Problem {
   int use_true_mma = 1;
   Mode mode = Mode::INTERIOR_POINT;
   bool use_dual = false;  // the sub-solver build() allocated for
+  bool use_groups = false;  // ... with the grouped sparse constraints in the dual (nwcon > 0)
   Vec *x1vec = nullptr, *x2vec = nullptr, *lbvec = nullptr, *ubvec = nullptr, *gvec = nullptr, *rvec = nullptr,
       *uinv = nullptr, *linv = nullptr, *cwvec = nullptr;
+  // the grouped dual: c_i of psi_i = a sum x + c_i, the group sums s_g (then the Gram weights), and m columns of nwcon
+  Vec *cgvec = nullptr, *swvec = nullptr;
+  std::vector<Vec *> Uwvecs;
+  std::vector<double *> Uw;
+  MmaDualGroups grp;
   std::vector<Vec *> Avecs, Gvecs;  // Gvecs: the m columns of the panel form (dual, m > kMmaDualFused only)
   // the current subproblem as the kernels take it: device-pointer tables over vectors that live from allocate() (G:
   // build()) to the destructor.  P0p = [p0 | p_i], Q0q = [q0 | q_i], the columns alone from entry 1 on (sub.p, sub.q);

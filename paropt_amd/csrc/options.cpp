@@ -218,6 +218,12 @@ void Options::addMMADefaults() {
   sub.choices = {"interior_point", "dual"};
   e["mma_subproblem_solver"] = sub;
   F("mma_dual_tol", 1e-8, 0.0, 1e20);
+  // what the dual does with sparse constraints: refuse them, or solve the grouped ("weighting") form group by group
+  Entry dsc;
+  dsc.type = ENUM;
+  dsc.s = "refuse";
+  dsc.choices = {"refuse", "groups"};
+  e["mma_dual_sparse_constraints"] = dsc;
   Entry dit;
   dit.type = INT;
   dit.i = 200;

@@ -61,7 +61,7 @@ __device__ __forceinline__ void w_block_reduce(double (&a)[N], double *partials,
 // variables (TV <= kGroupTile): lanes load the tile coalesced (lane <-> variable), products go to LDS,
 // then one thread per (group, column) adds its nw LDS values and the results leave coalesced over the
 // group index.  JB panel columns share one tile pass (one d load, JB independent loads in flight).
-constexpr int kGroupTile = 512;  // variables per tile = 2 per thread
+// (kGroupTile variables per tile = 2 per thread: wcon.hpp)
 // sum of nw consecutive LDS values in index order (the loads of four entries are issued together, the adds keep
 // the order of the plain loop: same bits)
 __device__ __forceinline__ double row_sum(const double *row, int nw) {

@@ -18,6 +18,7 @@ struct GroupMap {
   int64_t nwcon = 0, start = 0;
   int nw = 0, skip = 0;
 };
+constexpr int kGroupTile = 512;  // variables per tile of the tiled group kernels = 2 per thread
 
 int k_group_sum(Ctx *c, const GroupMap &m, double *out, int init, double cst, double alpha,
                 const double *v, int recip = 0);

@@ -12,6 +12,13 @@ trivial kernel of the rho form's mix, 2m + 7 in (po_bench_mma_dual_rho; profiles
 picks the built-in problem of the whole runs.  --small: instead, whole runs to the stop test on small problems
 (--shapes 300x3,200x2, dual tolerance 1e-9, at most --mma-iters iterations, default there 120) with and without the
 inner loop: iterations, raises, cap hits, rises of fobj (the `convex_small` lines).
+
+--nw NW [--nwcon W]: weighting constraints (W groups of NW consecutive variables, default n / NW) stay in the dual
+(mma_dual_sparse_constraints = groups): whole MMA iterations with the interior-point sub-solver and with the grouped
+dual alternate, then on the subproblem the last run left the grouped evaluation (po_mma_dual_group_eval) and the plain
+evaluation of the same shape without groups (po_mma_dual_eval, panel form) alternate, wall time and algorithmic bytes
+per call (both calls allocate their work vectors: the same m + 1 of n; the grouped one m + 1 of w besides).  Appended
+to profiles/r12_bench_mma_groups.jsonl.
 """
 import argparse
 import json
@@ -47,6 +54,67 @@ def run_mma(pa, ctx, n, c, solver, iters, globalization="none", problem="convex"
         out.update(globalization=globalization, inner_total=gs["inner_total"], inner_max=gs["inner_max"],
                    cap_hits=gs["cap_hits"], rho=gs["rho"].tolist())
     return out
+
+
+def group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps):
+    """Whole runs (interior point / grouped dual, alternating), then the two evaluations on the last subproblem."""
+    lines = []
+    mma = None
+    for rnd in range(rounds):
+        for solver in ("interior_point", "dual"):
+            mma = None  # (one solver's vectors at a time)
+            prob = pa.SeparableProblem(ctx, "convex", n, c, 0).setWeighting(nwcon, nw, 0, 0)
+            mma = pa.MMA(prob, {"mma_subproblem_solver": solver, "mma_dual_sparse_constraints": "groups",
+                                "mma_max_iterations": iters, "mma_l1_tol": 0.0, "mma_linfty_tol": 0.0,
+                                "write_output_frequency": 0})
+            stamps = []
+            mma.setIterationCallback(lambda k: stamps.append(time.perf_counter()))
+            mma.optimize()
+            st = mma.getState()
+            its = len(stamps) - 1
+            r = dict(kind="mma_groups", n=n, c=c, nwcon=nwcon, nw=nw, round=rnd, solver=solver, mma_iterations=its,
+                     ms_per_mma_iteration=(stamps[-1] - stamps[0]) / max(1, its) * 1e3,
+                     subproblem_evaluations_per_mma_iteration=st["subproblem_iter"] / max(1, its), fobj=st["fobj"],
+                     vectors=pa.live_objects()[0], GB=pa.live_objects()[1] * 1e-9)
+            if solver == "dual":
+                r.update(dual_stats=mma.getDualStats(), group_stats=mma.getDualGroupStats())
+            lines.append(r)
+            print(json.dumps(r), flush=True)
+    # the evaluations on the subproblem of the last (dual) run, at its multipliers
+    import numpy as np
+
+    s = mma.getSubproblem()
+    lo, up = mma.getAsymptotes()
+    lam = mma.getOptimizedPoint()[1]
+    pt = [pa.PVec(ctx, n) for _ in range(3)]
+    zw = pa.PVec(ctx, nwcon)
+    cvec = pa.PVec(ctx, nwcon).from_numpy(np.ones(nwcon))  # cw = 1 - sum x is linear: psi is the constraint itself
+    head = (ctx, lo, up, s["alpha"], s["beta"], s["p0"], s["q0"], s["p"], s["q"], s["b"], lam)
+
+    def timed(fn):
+        ctx.synchronize()
+        b0 = ctx.algorithmic_bytes()[0]
+        t0 = time.perf_counter()
+        out = fn()
+        ctx.synchronize()
+        return (time.perf_counter() - t0) * 1e3, ctx.algorithmic_bytes()[0] - b0, out
+
+    plain, grouped, stats = [], [], None
+    for _ in range(reps + 1):  # (the first pair warms up)
+        ms_p, by_p, _ = timed(lambda: pa.mma_dual_eval(*head, form=2))
+        ms_g, by_g, out = timed(lambda: pa.mma_dual_group_eval(*head, nwcon, nw, 0, 0, -1.0, cvec, nwcon, 1000.0, pt, zw))
+        plain.append(ms_p)
+        grouped.append(ms_g)
+        stats = out[3]
+    r = dict(kind="dual_group_eval", n=n, c=c, nwcon=nwcon, nw=nw, plain_ms=plain[1:], grouped_ms=grouped[1:],
+             plain_streams=by_p / (8.0 * n), grouped_streams=by_g / (8.0 * n),
+             plain_frac_hbm_8TBps=by_p * 1e-9 / (min(plain[1:]) * 1e-3) / HBM_PEAK_GBPS,
+             grouped_frac_hbm_8TBps=by_g * 1e-9 / (min(grouped[1:]) * 1e-3) / HBM_PEAK_GBPS,
+             grouped_over_plain=min(grouped[1:]) / min(plain[1:]), predicted_by_bytes=by_g / by_p,
+             inner_mean=stats["steps"] / max(1, nwcon), inner_max=stats["max_inner"], group_stats=stats)
+    lines.append(r)
+    print(json.dumps(r), flush=True)
+    return lines
 
 
 def small_run_lines(pa, ctx, n, c, iters, problem):
@@ -100,6 +168,8 @@ def main():
     ap.add_argument("--globalization", choices=("none", "conservative"), default="none")
     ap.add_argument("--problem", default="convex")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--nw", type=int, default=0)
+    ap.add_argument("--nwcon", type=int, default=0)
     a = ap.parse_args()
     if a.small:
         a.globalization = "conservative"
@@ -107,6 +177,8 @@ def main():
         a.shapes = "300x3,200x2" if a.small else "10000000x8,50000000x32"
     if a.mma_iters is None:
         a.mma_iters = 120 if a.small else 4
+    if a.out is None and a.nw > 0:
+        a.out = os.path.join(ROOT, "profiles", "r12_bench_mma_groups.jsonl")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "r10_bench_gcmma.jsonl" if a.globalization == "conservative"
                              else "r09_bench_mma.jsonl")
@@ -116,6 +188,9 @@ def main():
     lines = []
     for shape in a.shapes.split(","):
         n, c = (int(v) for v in shape.split("x"))
+        if a.nw > 0:
+            lines += group_lines(pa, ctx, n, c, a.nwcon or n // a.nw, a.nw, a.mma_iters, a.rounds, a.reps)
+            continue
         if a.small:
             lines += small_run_lines(pa, ctx, n, c, a.mma_iters, a.problem)
             continue
