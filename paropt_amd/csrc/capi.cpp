@@ -729,12 +729,7 @@ int po_quasidef_factor(po_problem p, po_vec x, po_vec dinv, po_vec c) {
     po::set_error("po_quasidef_factor: the problem has no sparse constraints or the sizes do not match");
     return PO_ERR_ARG;
   }
-  const long before = p->p->sparseFactorBreakdowns();
-  PO_TRY(p->p->sparseFactor(x, dinv, c));
-  if (p->p->sparseFactorBreakdowns() == before) return PO_OK;
-  // (the library's own factorizations have set the text; a user solver's failure is announced once only)
-  if (p->p->qd_set) po::set_error("the problem's quasi-definite solver reported a failed factorization (%d)", p->p->qd_last_fail);
-  return PO_ERR_NUMERIC;
+  return p->p->sparseFactorChecked(x, dinv, c);
 }
 int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, po_vec bw, po_vec yx,
                       po_vec yw) {
@@ -807,18 +802,11 @@ int po_csr_symbolic_destroy(po_csr_symbolic h) {
 int po_problem_set_quasidef_callbacks(po_problem p, const po_quasidef_callbacks *cb) {
   PO_CHECK_PTR(p);
   PO_CHECK_PTR(p->p);
-  if (!cb) {
-    p->p->qd = po_quasidef_callbacks();
-    p->p->qd_set = false;
-    return PO_OK;
-  }
-  if (!cb->factor || !cb->apply) {
+  if (cb && (!cb->factor || !cb->apply)) {
     po::set_error("po_problem_set_quasidef_callbacks: factor and apply are mandatory");
     return PO_ERR_ARG;
   }
-  p->p->qd = *cb;
-  p->p->qd_set = true;
-  return PO_OK;
+  return p->p->setUserSolver(cb);
 }
 const char *po_quasidef_factor_info(po_problem p) { return p && p->p ? p->p->sparseFactorInfo() : nullptr; }
 int po_problem_set_sparse_block_size(po_problem p, int nwblock) {

@@ -192,7 +192,7 @@ class InteriorPoint {
     bool t_is_plain_dinv_d1 = false;    // tvec / Dinv are exactly what dinv_d1_kernel forms (t0_diag)
     bool first_t_recomputable = false;  // ... and the first solve's t can be re-formed in registers
     bool wd2_ready = false;             // wd2 = d2 of the next block solve
-    bool panel_valid = false;           // Uw is the panel image of the current setUpKKTSystem (panel_plain)
+    bool panel_valid = false;           // Uw is the panel image of the current setUpKKTSystem (panel_form)
   } scratch_flags;
   // what was evaluated at the current iterate x; stale when x, the bounds or the problem instance change other than
   // by the step update
@@ -301,12 +301,11 @@ class InteriorPoint {
   int sparseConAtIterate(const double **cw);
   Vec *d1v;                 // n-sized: raw d1, then v = d1 + P alpha
   std::vector<Vec *> Uw;    // U_j = Aw (Dinv o P_j)
-  bool panel_plain = false;  // Uw is the unscaled panel image (scalar block form, user solver)
-  // the problem brings its own quasi-definite solver (Problem::sparseUserSolver): Yw_j = -S^-1 U_j beside Uw, the
-  // panel sparseCorrection combines
+  // the report of the problem's solver at the last Gram correction (quasidef.hpp): whether Uw is still the plain
+  // panel image, and whether a solved panel Yw_j = -S^-1 U_j beside it is the one sparseCorrection combines
+  GramForm panel_form = {false, false};
   std::vector<Vec *> Yw;
-  bool panel_solved = false;
-  std::vector<const double *> correctionPanel(int m) const;  // Yw (panel_solved) or Uw, m columns
+  std::vector<const double *> correctionPanel(int m) const;  // Yw (panel_form.solved) or Uw, m columns
   double w_sums[7], w_maxs[5];  // reductions of the last w residual (k_w_res layout)
   double res_out[13] = {0}, wres_out[12] = {0};  // landing area of the residual reductions (see after_reduce)
   // Monotone barrier strategy with the infinity norm (round 4): the residual pass also takes max|rzl|, max|rzu| for the

@@ -116,7 +116,7 @@ int InteriorPoint::panelImageVectors(int m, std::vector<double *> &U) {
 }
 std::vector<const double *> InteriorPoint::correctionPanel(int m) const {
   std::vector<const double *> C(m);
-  for (int j = 0; j < m; j++) C[j] = (panel_solved ? Yw[j] : Uw[j])->d;
+  for (int j = 0; j < m; j++) C[j] = (panel_form.solved ? Yw[j] : Uw[j])->d;
   return C;
 }
 // panel_done: the Gram pass over P has already written U (Problem::sparseGramGroups)
@@ -127,48 +127,43 @@ int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, in
   PO_TRY(panelImageVectors(m, U));
   std::vector<const double *> Uc(U.begin(), U.end());
   if (!panel_done) PO_TRY(prob->sparseJacobianPanel(x, Dinv, P.data(), m, U.data(), work ? work : tvec));
-  panel_solved = prob->sparseUserSolver();
-  if (panel_solved) {
-    // The user exposes no factor, so there is no half solve: Yw_j = -S^-1 U_j from one three-argument apply per panel
-    // column (the reference makes c for G, :1937, and two inside each of the k diagonal solves, :2398, 2427), and the
-    // correction is the cross product W += U^T Yw of two different w-sized panels, symmetric up to rounding: both
-    // halves are averaged.  Uw keeps U itself (panel_plain), Yw is what sparseCorrection combines.
-    while ((int)Yw.size() < m) {
-      Vec *y = vec_new(ctx, nw);
-      if (!y) return PO_ERR_HIP;
-      Yw.push_back(y);
-    }
-    std::vector<double *> Y(m);
-    for (int j = 0; j < m; j++) Y[j] = Yw[j]->d;
-    PO_TRY(prob->sparseSolvedPanel(P.data(), m, Y.data(), work ? work : tvec));
-    std::vector<const double *> Yc(Y.begin(), Y.end());
-    panel_plain = true;
+  // What the problem's solver makes of the panel (quasidef.hpp): a half solve in place -- scalar forms: nothing, the
+  // weights are Cw; packed blocks and CSR: U <- L^-1 U with S = L L^T, unit weights -- or, where the user exposes no
+  // factor, a second panel Yw_j = -S^-1 U_j from one three-argument apply per column (the reference makes c for G,
+  // :1937, and two inside each of the k diagonal solves, :2398, 2427).
+  const GramForm form = panel_form = prob->sparseGramForm();
+  std::vector<double *> Y;
+  while (form.solved && (int)Yw.size() < m) {
+    Vec *y = vec_new(ctx, nw);
+    if (!y) return PO_ERR_HIP;
+    Yw.push_back(y);
+  }
+  for (int j = 0; form.solved && j < m; j++) Y.push_back(Yw[j]->d);
+  const double *weights = nullptr;
+  PO_TRY(prob->sparseGramSolve(P.data(), m, U.data(), Y.data(), Cw, work ? work : tvec, &weights));
+  W2_buf.assign((size_t)m * m, 0.0);
+  if (!weights) {
+    // the cross product W += U^T Yw of two different w-sized panels, symmetric up to rounding: both halves are averaged
     if (kkt.W.size() != (size_t)m * m) {  // (the caller sized W for this panel: a Schur-complement term is never dropped)
       set_error("internal: the Gram matrix holds %zu entries for a panel of %d columns", kkt.W.size(), m);
       return PO_ERR_ARG;
     }
-    W2_buf.assign((size_t)m * m, 0.0);
+    std::vector<const double *> Yc(Y.begin(), Y.end());
     PO_TRY(k_xgram(ctx, Uc.data(), Yc.data(), m, nw, W2_buf.data(), may_defer));
     after_reduce(ctx, [this, m] {
       for (int j = 0; j < m; j++)
         for (int i = 0; i < m; i++)
           kkt.W[i + (size_t)m * j] += 0.5 * (W2_buf[i + (size_t)m * j] + W2_buf[j + (size_t)m * i]);
     });
-    scratch_flags.panel_valid = true;
-    return PO_OK;
+  } else {
+    // (may_defer: inside setUpKKTSystem's batch the product arrives at the flush: a member holds it, the subtraction
+    // follows it there)
+    PO_TRY(k_wgram(ctx, weights, Uc.data(), m, nw, W2_buf.data(), nullptr, nullptr, 0, 0.0, 0, may_defer));
+    after_reduce(ctx, [this] {
+      for (size_t i = 0; i < W2_buf.size() && i < kkt.W.size(); i++) kkt.W[i] -= W2_buf[i];
+    });
   }
-  // block form: U^T Cw U.  CSR form: U <- L^-1 U with S = L L^T, then U^T U
-  const double *weights = Cw->d;
-  PO_TRY(prob->sparseHalfSolve(U.data(), m, Cw, &weights));
-  panel_plain = (weights == Cw->d);  // scalar block form: Uw still holds U = Aw (Dinv o P) itself
-  // (may_defer: inside setUpKKTSystem's batch the product arrives at the flush: a member holds it, the subtraction
-  // follows it there)
-  W2_buf.assign((size_t)m * m, 0.0);
-  PO_TRY(k_wgram(ctx, weights, Uc.data(), m, nw, W2_buf.data(), nullptr, nullptr, 0, 0.0, 0, may_defer));
-  after_reduce(ctx, [this] {
-    for (size_t i = 0; i < W2_buf.size() && i < kkt.W.size(); i++) kkt.W[i] -= W2_buf[i];
-  });
-  scratch_flags.panel_valid = true;  // Uw holds the (half-solved) panel of the CURRENT Dinv, factor and panel columns
+  scratch_flags.panel_valid = true;  // Uw (and Yw) hold the panel of the CURRENT Dinv, factor and panel columns
   return PO_OK;
 }
 
@@ -195,7 +190,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
     scratch_flags.wd2_ready = false;
     PO_TRY(applyK0(d1v->d, wd2->d, tvec, wyw));
     if (refine_pass && step_flags.tdots_valid && (int)tdots.size() == m && m > 0 && scratch_flags.panel_valid &&
-        panel_plain && (int)Uw.size() >= m) {
+        panel_form.plain && (int)Uw.size() >= m) {
       // tvec = Dinv o (d1' + Aw^T yw): P^T tvec = P^T (Dinv o d1') + U^T yw with U = Aw (Dinv o P) -- the first
       // term came out of the fused first pass, the second is a w-sized product with the panel image
       std::vector<const double *> Uc(m);
@@ -235,7 +230,7 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   // over P writes the step, the RAW right-hand side d1' of the refinement solve (its design rows, :1451-1483, with
   // the extra column Aw^T pzw) and the panel products of Dinv o d1'.
   const bool fuse = fuse_residual && !refine_pass && forms.analytic_panel_dots && kq == k && m > 0 &&
-                    (int)Uw.size() >= m && scratch_flags.panel_valid && panel_plain && !cl &&
+                    (int)Uw.size() >= m && scratch_flags.panel_valid && panel_form.plain && !cl &&
                     !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
   if (fuse) {
     std::vector<const double *> Uc = correctionPanel(m);

@@ -123,12 +123,12 @@ int MMA::build() {
 // ---- the dual sub-solver --------------------------------------------------------------------------
 int MMA::checkDualCovers() {
   const char *why = nullptr;
+  const GroupMap *gm = prob->groupedLibraryForm();
   if (nwcon > 0 && !wantGroups()) {
     why = "sparse constraints are not part of the closed-form primal point";
   } else if (nwcon > 0 && std::string(options().str("mma_globalization")) == "conservative") {
     why = "sparse constraints in groups do not run under mma_globalization = conservative";
-  } else if (nwcon > 0 && (!prob->grouped || prob->nwblock != 1 || prob->sparseUserSolver() ||
-                           prob->gmap.nwcon != nwcon || !mma_dual_groups_tile(prob->gmap, nlocal))) {
+  } else if (nwcon > 0 && (!gm || gm->nwcon != nwcon || !mma_dual_groups_tile(*gm, nlocal))) {
     why = "sparse constraints run through the dual only in the grouped form: one constraint per group of nw "
           "consecutive variables with one Jacobian value (setWeighting, or a CSR pattern recognised as such), "
           "nwblock = 1, nw + skip within the 512 variables of a tile, and no quasi-definite solver of the problem's own";
@@ -281,12 +281,13 @@ int MMA::initializeSubProblem(Vec *xv) {  // :523-757
   }
   if (nwcon > 0 && prob->evalSparseCon(xvec, cwvec) != 0) return PO_ERR_USER;
   if (use_groups) {  // psi_i(x) = a sum_{G_i} x + c_i, c_i = cw_i(x^k) - a sum_{G_i} x^k
-    if (!prob->grouped || prob->gmap.nwcon != nwcon) {
+    const GroupMap *gm = prob->groupedLibraryForm();
+    if (!gm || gm->nwcon != nwcon) {
       set_error("MMA: mma_dual_sparse_constraints = groups: the sparse constraints lost their grouped form (the "
                 "entries of the Jacobian are no longer all equal)");
       return PO_ERR_ARG;
     }
-    grp.map = prob->gmap;
+    grp.map = *gm;
     grp.a = prob->group_alpha;
     grp.c = cgvec->d;
     grp.nwinequality = nwinequality;
@@ -484,9 +485,6 @@ int MMA::addSparseJacobianTranspose(double alpha, Vec *, Vec *pzw, Vec *out) {
 }
 int MMA::addSparseInnerProduct(double alpha, Vec *, Vec *cvec, Vec *A) {
   return nwcon > 0 ? prob->addSparseInnerProduct(alpha, xvec, cvec, A) : 0;
-}
-int MMA::sparseJacobianPanel(Vec *, Vec *d, const double *const *P, int nv, double *const *U, Vec *work) {
-  return prob->sparseJacobianPanel(xvec, d, P, nv, U, work);
 }
 
 }  // namespace po

@@ -137,25 +137,17 @@ class MMA : public Problem {
   int addSparseJacobian(double alpha, Vec *x, Vec *px, Vec *out) override;
   int addSparseJacobianTranspose(double alpha, Vec *x, Vec *pzw, Vec *out) override;
   int addSparseInnerProduct(double alpha, Vec *x, Vec *cvec, Vec *A) override;
-  int sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
-                          Vec *work) override;
-  int sparseApplyK0(Vec *, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
-                    Vec *wwork) override {
-    return prob->sparseApplyK0(xvec, d, cw, bx, bw, yx, yw, wwork);
+  // the quasi-definite solver is the wrapped problem's, with its Jacobian taken at the expansion point
+  Problem *sparseOwner(Vec **x) override {
+    *x = xvec;
+    return prob->sparseOwner(x);
   }
-  int sparseFactor(Vec *, Vec *d, Vec *cw) override { return prob->sparseFactor(xvec, d, cw); }
-  int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
-    return prob->sparseHalfSolve(U, nv, cw, weights);
-  }
-  bool sparseUserSolver() override { return prob->sparseUserSolver(); }
-  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
-    return prob->sparseSolvedPanel(P, nv, Yw, work);
-  }
-  const char *sparseFactorInfo() override { return prob->sparseFactorInfo(); }
-  long sparseFactorBreakdowns() override { return prob->sparseFactorBreakdowns(); }
-  int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) override {
-    return prob->sparseCorrection(U, nv, alpha, cw, out, acc);
-  }
+  // The subproblem view takes the unfused Jacobian forms, whatever the wrapped problem could fuse: Cdiag by a pass of
+  // its own ahead of factor (no factorFromSlacks), the set forms as a zero fill followed by the add forms, no group
+  // Gram and no described transpose column (Problem's defaults for a problem that is not `grouped` itself).  Factor,
+  // apply, panel and correction are the wrapped problem's solver's.  This is what MMA has always run; results are
+  // pinned to it bit for bit (tools/sparse_digest.py).
+  bool sparseFusedForms() override { return false; }
 
   // what the C layer hands out
   int mma_iter = 0, subproblem_iter = 0;

@@ -7,14 +7,14 @@
 #include "core.hpp"
 #include "csr.hpp"
 #include "qn.hpp"
+#include "quasidef.hpp"
 #include "wcon.hpp"
 
 namespace po {
 
 class Problem {
  public:
-  Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_)
-      : ctx(c), nlocal(nlocal_), offset(0), nglobal(nlocal_), ncon(ncon_), ninequality(nineq_) {}
+  Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_);
   virtual ~Problem();
   virtual int getVarsAndBounds(Vec *x, Vec *lb, Vec *ub) = 0;
   virtual int evalObjCon(Vec *x, double *fobj, double *cons) = 0;
@@ -51,9 +51,9 @@ class Problem {
   // true for the model problems the trust-region and MMA drivers build around the user's problem: their solver takes
   // no differenced Hessian-vector products (po_ip_set_hvec_finite_difference)
   virtual bool isSubproblem() { return false; }
-  // sparse constraints (src/ParOptProblem.h:215-262); out / pzw / A are w-sized device vectors.  The
-  // defaults serve a problem with a CSR pattern (`csr`, the ParOptSparseProblem form) and are no-ops
-  // otherwise.
+  // ---- sparse constraints, Jacobian side (src/ParOptProblem.h:215-262) ----
+  // out / pzw / A are w-sized device vectors.  The defaults serve a problem with a CSR pattern (`csr`, the
+  // ParOptSparseProblem form) or the grouped pattern below and are no-ops otherwise.
   virtual int evalSparseCon(Vec *x, Vec *out);
   virtual int addSparseJacobian(double alpha, Vec *x, Vec *px, Vec *out);
   virtual int addSparseJacobianTranspose(double alpha, Vec *x, Vec *pzw, Vec *out);
@@ -64,64 +64,54 @@ class Problem {
   // write every entry in one pass overrides it
   virtual int setSparseJacobianTranspose(double alpha, Vec *x, Vec *pzw, Vec *out);
   // Structured problems describe that n-sized vector instead of writing it (core.hpp: GroupCol): the pass that would
-  // have read it forms its entries from pzw in registers.  false (the default): the caller materialises the vector.
+  // have read it forms its entries from pzw in registers.  false (the default, and whenever the problem brings its own
+  // quasi-definite solver): the caller materialises the vector.
   virtual bool sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *col);
   virtual int addSparseInnerProduct(double alpha, Vec *x, Vec *cvec, Vec *A);
-  // U_j = Aw (d o P_j) for a whole panel; the default goes column by column through
-  // addSparseJacobian with `work` (n-sized) as scratch, structured problems do it in one pass
-  virtual int sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
-                                  Vec *work);
+  // U_j = Aw (d o P_j) for a whole panel in the problem's row order: the grouped pattern in one pass, anything else
+  // column by column through addSparseJacobian with `work` (n-sized) as scratch.  The solver's panel() calls this.
+  virtual int sparsePanelImage(Vec *x, Vec *d, const double *const *P, int nv, double *const *U, Vec *work);
   // Structured problems (one constraint per group of consecutive variables) let that panel image ride in the Gram
   // pass over the same panel (k_wgram's `groups`, one pass over P instead of two): the map and the Jacobian's
-  // entry value, or false (the default: the panel image is sparseJacobianPanel's pass of its own)
+  // entry value, or false (the default, and with a quasi-definite solver of the problem's own: the panel image is
+  // sparseJacobianPanel's pass of its own)
   virtual bool sparseGramGroups(Vec *x, GramGroups *g);
-  // (yx, yw) = K0^-1 (bx, bw) of ParOptQuasiDefBlockMat::apply (src/ParOptSparseMat.cpp:122-190) with
-  // the diagonal blocks d (n) and cw (w): yx = d o bx; yw = cw o (bw - Aw yx); yx = d o (bx + Aw^T yw).
-  // The default is that sequence through the Jacobian callbacks (11 n-sized passes); structured problems
-  // do it in 5.  bx must not alias yx; bw may be null (zero block); `wwork` is w-sized scratch.
-  virtual int sparseApplyK0(Vec *x, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
-                            Vec *wwork);
-  // ParOptQuasiDefMat::factor (src/ParOptSparseMat.h:25): cw holds Cdiag on entry.  Block form
-  // (nwblock = 1): cw <- 1/(Cdiag + diag(Aw d Aw^T)).  CSR form: S = Cdiag + Aw d Aw^T is factored on the
-  // device and cw is left alone.
-  virtual int sparseFactor(Vec *x, Vec *d, Vec *cw);
-  // The same with Cdiag = sw/zsw + tw/ztw (:1912-1927) formed from the sparse slack blocks on the way (one launch
-  // less where the form allows it); the default forms Cdiag into cw and calls sparseFactor
-  virtual int sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw);
-  // Second half of the Gram correction W -= U^T S^-1 U: turns the panel from sparseJacobianPanel into Y
-  // with U^T S^-1 U = Y^T diag(weights) Y.  Block form: Y = U, weights = cw.  CSR form: Y = L^-1 U in
-  // place, unit weights.
-  virtual int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights);
-  // out = -S^-1 (U alpha) for the panel as sparseHalfSolve left it (nv columns, w-sized, `out` w-sized):
-  // K0^-1 (P alpha, 0) = (Dinv (P alpha + Aw^T out), out), which turns the second quasi-definite apply of a
-  // bordered solve into a correction of the first.  Block form: -cw o (U alpha).  CSR form: -L^-T (Y alpha).
-  // acc != nullptr: acc += out as well (the caller's running sparse multiplier part), in the same launch where the
-  // form allows it
-  virtual int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out,
-                               Vec *acc = nullptr);
-  // one line for the output file, null when there is nothing to say (getFactorInfo, :61)
-  virtual const char *sparseFactorInfo();
-  // number of factorizations so far that met a non-positive pivot (CSR form; 0 otherwise), or that the user's
-  // factor reported as failed
-  virtual long sparseFactorBreakdowns() { return qd_set ? qd_breakdowns : (csr ? csr->breakdowns : blk_breakdowns); }
-  // createQuasiDefMat (src/ParOptProblem.h:72): the problem brings its own quasi-definite solver
-  // (po_problem_set_quasidef_callbacks).  sparseFactor then forms nothing and calls the user's factor(x, d, Cdiag)
-  // with cw = Cdiag left alone, sparseApplyK0 is the user's apply and nothing else, the fused group path is off
-  // (sparseGramGroups / sparseTransposeColumn return false), and the Gram correction cannot be a half solve -- the
-  // user exposes no factor -- so it takes the SOLVED panel below.  Subproblems forward both hooks to the problem they
-  // wrap, which is how they carry its table.
-  virtual bool sparseUserSolver() { return qd_set; }
-  // Yw_j = -S^-1 Aw (d o P_j), j < nv: one three-argument apply(P_j -> work, Yw_j) of the user's solver per column
-  // (P_j n-sized, Yw_j w-sized, `work` n-sized scratch that no P_j aliases).  With U from sparseJacobianPanel the Gram
-  // correction is then the CROSS product W += U^T Yw (k_xgram), and sparseCorrection on the panel Yw is the linear
-  // combination Yw alpha = -S^-1 (U alpha): no further user call.
-  virtual int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work);
-  po_quasidef_callbacks qd = {};
-  bool qd_set = false;
-  long qd_breakdowns = 0;  // factor calls that returned non-zero (qd_last_fail: the last such value)
-  int qd_last_fail = 0;
-  long blk_breakdowns = 0;   // block form with nwblock > 1: factorizations that replaced a non-positive pivot
-  int64_t blk_nwcon = 0;     // nwcon the packed-block buffers were sized for
+
+  // ---- sparse constraints, solver side: the quasi-definite solver this problem created (quasidef.hpp) ----
+  // The model problems of the trust-region and MMA drivers have no solver of their own: they name the problem whose
+  // solver answers and the point its Jacobian is taken at (*x <- their linearisation point).  Every entry below
+  // resolves the owner first, so a wrapper overrides this and nothing else.
+  virtual Problem *sparseOwner(Vec **x) { return this; }
+  // false: factorFromSlacks of the owner's solver is not taken -- Cdiag is formed by a pass of its own and handed to
+  // factor.  (Overridden by MMA alone, see there.)
+  virtual bool sparseFusedForms() { return true; }
+  int sparseFactor(Vec *x, Vec *d, Vec *cw) { return sparseSolver(&x)->factor(x, d, cw); }
+  int sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw);
+  int sparseApplyK0(Vec *x, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw, Vec *wwork) {
+    return sparseSolver(&x)->applyK0(x, d, cw, bx, bw, yx, yw, wwork);
+  }
+  int sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U, Vec *work) {
+    return sparseSolver(&x)->panel(x, d, P, nv, U, work);
+  }
+  GramForm sparseGramForm() { return sparseSolver()->gramForm(); }
+  int sparseGramSolve(const double *const *P, int nv, double *const *U, double *const *Yw, Vec *cw, Vec *work,
+                      const double **weights) {
+    return sparseSolver()->gramSolve(P, nv, U, Yw, cw, work, weights);
+  }
+  int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc = nullptr) {
+    return sparseSolver()->correction(U, nv, alpha, cw, out, acc);
+  }
+  const char *sparseFactorInfo() { return sparseSolver()->info(); }
+  long sparseFactorBreakdowns() { return sparseSolver()->breakdowns(); }
+  // po_quasidef_factor: sparseFactor, with a breakdown it met reported as PO_ERR_NUMERIC and the error text set
+  int sparseFactorChecked(Vec *x, Vec *d, Vec *cw);
+  // the problem brings its own solver (po_problem_set_quasidef_callbacks; null detaches and brings the library's form
+  // back): the fused group paths are then off and the Gram correction takes the solved panel (GramForm)
+  bool sparseUserSolver() { return sparseSolver()->userTable() != nullptr; }
+  int setUserSolver(const po_quasidef_callbacks *cb) { return chooseSolver(cb, nwblock); }
+  // the grouped scalar form with the library's solver (what MMA's grouped dual can take over): its map, else null
+  const GroupMap *groupedLibraryForm() { return grouped && !solver->userTable() ? &gmap : nullptr; }
+
   // fixed CSR pattern of the sparse Jacobian (ParOptSparseProblem::setSparseJacobianData, .cpp:632-677);
   // owned.  Sets nwcon / nwinequality.
   int setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *rowp, const int *cols);
@@ -149,11 +139,20 @@ class Problem {
   // triangles of the nwblock x nwblock blocks (nwcon (nwblock+1)/2 entries)
   int setSparseBlockSize(int nwblock_);
   int nwblock = 1;
-  Vec *blk = nullptr;    // packed blocks: C + Aw D^-1 Aw^T, then its Cholesky factor U (A = U^T U)
-  Vec *wones = nullptr;  // unit weights for the Gram of the half-solved panel
-  int *blk_flag = nullptr;
-  std::string factor_info;
 
+ protected:
+  // the one place the form of the solver is chosen (quasidef.cpp); the sites that change one of its inputs call it
+  int chooseSolver(const po_quasidef_callbacks *user, int nwblock_);
+  const po_quasidef_callbacks *userSolverTable() { return solver->userTable(); }
+
+ private:
+  QuasiDefSolver *sparseSolver(Vec **x = nullptr) {
+    Vec *none = nullptr;
+    return sparseOwner(x ? x : &none)->solver;
+  }
+  QuasiDefSolver *solver = nullptr;  // owned, never null
+
+ public:
   Ctx *ctx;
   int64_t nlocal, offset, nglobal;
   int ncon, ninequality;
@@ -188,7 +187,7 @@ class CallbackProblem : public Problem {
   int deferred_reductions = 0;
   // (... and not with a quasi-definite solver of the problem's own attached: its factor / apply are user code that the
   // promise does not cover, and they run where the solver would otherwise have a batch open)
-  bool reductionsBatchable() override { return deferred_reductions != 0 && !qd_set; }
+  bool reductionsBatchable() override { return deferred_reductions != 0 && !sparseUserSolver(); }
   po_problem_callbacks cb;
   SparseCallbacks sparse;
   // CSR form (CyParOptSparseProblem, src/CyParOptProblem.h:177-262): the two evaluation callbacks also fill
@@ -210,7 +209,7 @@ class SeparableProblem : public Problem {
   int evalObjCon(Vec *x, double *fobj, double *cons) override;
   int evalObjConGradient(Vec *x, Vec *g, Vec **Ac) override;
   // (a user-supplied quasi-definite solver is user code: its reductions must return their values at once)
-  bool reductionsBatchable() override { return !qd_set; }
+  bool reductionsBatchable() override { return !sparseUserSolver(); }
   double rosen_out[3] = {0, 0, 0};  // landing area of the Rosenbrock reductions (BatchScope::end_then)
   // weighting constraints cw_i = 1 - sum_{k<nw} x[nwstart + i (nw + nwskip) + k] on GLOBAL indices;
   // groups must not straddle rank boundaries (checked)

@@ -69,7 +69,7 @@ int Problem::setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *r
   grouped = rec;
   gmap = rec ? gm : GroupMap();
   group_alpha = 0.0;  // known after the first gradient evaluation (csrValuesChanged)
-  return PO_OK;
+  return chooseSolver(userSolverTable(), nwblock);
 }
 
 int Problem::csrValuesChanged() {
@@ -94,66 +94,43 @@ int Problem::csrValuesChanged() {
   csr_group_fallbacks++;
   grouped = false;
   gmap = GroupMap();
+  // (mid-run, inside a gradient evaluation: whatever the interior point built with the grouped solver stands until
+  // its next setUpKKTSystem rebuilds it)
+  PO_TRY(chooseSolver(userSolverTable(), nwblock));
   PO_TRY(csr->upgradeFromLight());
   return csr->valuesChanged();
 }
+Problem::Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_)
+    : ctx(c), nlocal(nlocal_), offset(0), nglobal(nlocal_), ncon(ncon_), ninequality(nineq_) {
+  (void)chooseSolver(nullptr, 1);  // (the generic scalar form allocates nothing)
+}
 Problem::~Problem() {
+  delete solver;
   delete csr;
-  vec_decref(blk);
-  vec_decref(wones);
-  if (blk_flag) (void)hipFree(blk_flag);
 }
-// A real po_vec handle that borrows raw device storage for the length of a user callback: host-side callbacks may ask
-// it for a pinned mirror (po_vec_get_array), which is released here -- the handle never reaches vec_decref
-struct BorrowedVec : po_vec_s {
-  BorrowedVec(Ctx *c, int64_t n_, const double *d_) {
-    ctx = c;
-    n = n_;
-    d = const_cast<double *>(d_);
-    ref = 1;
-    h = nullptr;
-  }
-  ~BorrowedVec() {
-    if (h) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipHostFree(h);
-      mirror_freed();
-    }
-  }
-};
 
-const char *Problem::sparseFactorInfo() {
-  if (qd_set) return qd.factor_info ? qd.factor_info(qd.user) : nullptr;
-  if (csr && !grouped) return csr->factorInfo();
-  factor_info = "nblock: " + std::to_string(nwblock);  // ParOptQuasiDefBlockMat::getFactorInfo (:218-221)
-  return factor_info.c_str();
-}
 int Problem::setSparseBlockSize(int nwblock_) {
   if (nwblock_ < 1 || nwblock_ > 16 || (nwcon % nwblock_) != 0 || csr) {
     set_error("sparse block size %d: must be 1..16, divide the %lld local sparse constraints, and the problem must "
               "not be in the CSR form", nwblock_, (long long)nwcon);
     return PO_ERR_ARG;
   }
-  // allocate first, commit on success: a failure leaves the problem in its previous (consistent) state
-  Vec *nblk = nullptr, *nones = nullptr;
-  if (nwblock_ > 1) {
-    nblk = vec_new(ctx, nwcon * (nwblock_ + 1) / 2);
-    nones = vec_new(ctx, nwcon);
-    int rc = (nblk && nones) ? k_fill(ctx, nones->d, nwcon, 1.0) : PO_ERR_HIP;
-    if (rc == PO_OK && !blk_flag && hipMalloc((void **)&blk_flag, 4 * sizeof(int)) != hipSuccess) rc = PO_ERR_HIP;
-    if (rc != PO_OK) {
-      vec_decref(nblk);
-      vec_decref(nones);
-      return rc;
-    }
-  }
-  vec_decref(blk);
-  vec_decref(wones);
-  blk = nblk;
-  wones = nones;
-  nwblock = nwblock_;
-  blk_nwcon = nwcon;
-  return PO_OK;
+  // (the packed-block solver allocates first and is committed on success: a failure leaves the problem in its
+  // previous, consistent, state)
+  return chooseSolver(userSolverTable(), nwblock_);
+}
+int Problem::sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw) {
+  if (sparseFusedForms()) return sparseSolver(&x)->factorFromSlacks(x, d, v, cw);
+  PO_TRY(k_w_cdiag(ctx, v, nwcon, cw->d));
+  return sparseFactor(x, d, cw);
+}
+int Problem::sparseFactorChecked(Vec *x, Vec *d, Vec *cw) {
+  QuasiDefSolver *s = sparseSolver(&x);
+  const long before = s->breakdowns();
+  PO_TRY(s->factor(x, d, cw));
+  if (s->breakdowns() == before) return PO_OK;
+  s->describeBreakdown();
+  return PO_ERR_NUMERIC;
 }
 // ParOptSparseProblem::evalSparseCon copies the values the last evaluation stored (.cpp:750-760)
 int Problem::evalSparseCon(Vec *, Vec *out) {
@@ -181,134 +158,18 @@ int Problem::setSparseJacobian(double alpha, Vec *x, Vec *px, Vec *out) {
   PO_TRY(k_fill(ctx, out->d, nwcon, 0.0));
   return addSparseJacobian(alpha, x, px, out) != 0 ? PO_ERR_USER : PO_OK;
 }
-int Problem::sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw) {
-  // grouped with entries +-1: Cdiag from the slack blocks, the group sums of d and the reciprocal in ONE launch
-  if (!qd_set && grouped && nwblock == 1 && group_alpha * group_alpha == 1.0) return k_group_factor(ctx, gmap, v, d->d, cw->d);
-  PO_TRY(k_w_cdiag(ctx, v, nwcon, cw->d));
-  return sparseFactor(x, d, cw);
-}
 int Problem::addSparseInnerProduct(double alpha, Vec *, Vec *cvec, Vec *A) {
   if (grouped) return k_group_sum(ctx, gmap, A->d, 1, 0.0, alpha * (group_alpha * group_alpha), cvec->d);
   if (!csr) return 0;
   return csr->innerProduct(alpha, cvec->d, A->d) != PO_OK;
 }
-int Problem::sparseFactor(Vec *x, Vec *d, Vec *cw) {
-  if (qd_set) {  // the user's factor(x, Dinv, Cdiag); cw stays Cdiag
-    const int fail = qd.factor(qd.user, static_cast<po_vec>(x), static_cast<po_vec>(d), static_cast<po_vec>(cw));
-    if (fail != 0) {  // the reference ignores the value (src/ParOptInteriorPoint.cpp:1930, 5429): warn once, count
-      if (qd_breakdowns == 0) set_error("the problem's quasi-definite solver reported a failed factorization (%d)", fail);
-      qd_breakdowns++;
-      qd_last_fail = fail;
-    }
-    return PO_OK;
-  }
-  // grouped: Cw = 1 / (Cdiag + alpha^2 (sum of d over the group)): the group sum and the reciprocal in one launch
-  if (grouped && nwblock == 1) return k_group_sum(ctx, gmap, cw->d, 1, 0.0, group_alpha * group_alpha, d->d, 1);
-  if (csr) return csr->factor(d->d, cw->d);
-  if (nwblock > 1) {  // :60-112
-    const int64_t nb = nwcon / nwblock;
-    PO_TRY(k_blk_init(ctx, cw->d, nb, nwblock, blk->d));
-    if (addSparseInnerProduct(1.0, x, d, blk) != 0) return PO_ERR_USER;
-    const int flag0[4] = {0, 0x7fffffff, 0, 0};
-    PO_HIP(hipMemcpyAsync(blk_flag, flag0, sizeof(flag0), hipMemcpyHostToDevice, ctx->stream));
-    PO_TRY(k_blk_factor(ctx, blk->d, nb, nwblock, blk_flag));
-    int flag[4] = {0, 0, 0, 0};
-    PO_HIP(hipMemcpyAsync(flag, blk_flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
-    PO_HIP(hipStreamSynchronize(ctx->stream));
-    if (flag[0] != 0) {  // the reference returns dpptrf's info, which its caller ignores (:1930)
-      if (blk_breakdowns == 0 && ctx->rank == 0) {  // warn once, like the CSR form
-        fprintf(stderr,
-                "ParOpt warning: the sparse constraint matrix is not positive definite (first failing row %d, block "
-                "%d; %d pivots replaced)\n", flag[1], flag[1] / nwblock, flag[0]);
-      }
-      blk_breakdowns++;
-    }
-    return PO_OK;
-  }
-  if (addSparseInnerProduct(1.0, x, d, cw) != 0) return PO_ERR_USER;
-  return k_recip(ctx, cw->d, nwcon);
-}
-int Problem::sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) {
-  if (!qd_set) {
-    set_error("internal: the solved panel belongs to a problem with its own quasi-definite solver");
-    return PO_ERR_ARG;
-  }
-  for (int j = 0; j < nv; j++) {
-    BorrowedVec bx(ctx, nlocal, P[j]), yw(ctx, nwcon, Yw[j]);
-    const int fail = qd.apply(qd.user, &bx, nullptr, static_cast<po_vec>(work), &yw);
-    if (fail != 0) {
-      set_error("the problem's quasi-definite solver failed in apply (%d)", fail);
-      return PO_ERR_USER;
-    }
-  }
-  return PO_OK;
-}
-int Problem::sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) {
-  if (qd_set) {
-    set_error("internal: a problem with its own quasi-definite solver has no half solve");
-    return PO_ERR_ARG;
-  }
-  if (csr && !grouped) {
-    *weights = csr->unitWeights();
-    return csr->halfSolve(U, nv);
-  }
-  if (nwblock > 1) {  // S = U^T U per block: U_panel^T S^-1 U_panel = (U^-T P)^T (U^-T P)
-    *weights = wones->d;
-    return k_blk_solve(ctx, blk->d, nwcon / nwblock, nwblock, U, nv, 1);
-  }
-  *weights = cw->d;
-  return PO_OK;
-}
-
-int Problem::sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) {
-  if (qd_set) {  // U is the solved panel Yw = -S^-1 U: out = Yw alpha
-    PO_TRY(k_panel_axpy(ctx, out->d, 0.0, nullptr, 0.0, alpha, U, nv, nwcon));
-    if (acc) PO_TRY(k_axpy(ctx, acc->d, 1.0, out->d, nwcon));
-    return PO_OK;
-  }
-  if ((!csr || grouped) && nwblock == 1 && nv <= kMaxPanel) {
-    // scalar block form: sum, scale by -cw and the caller's accumulation in ONE w-sized launch (round 4; the same
-    // operations in the same order as the three launches below)
-    return k_w_correction(ctx, U, nv, alpha, cw->d, nwcon, out->d, acc ? acc->d : nullptr);
-  }
-  if (csr && !grouped) {
-    PO_TRY(csr->correction(U, nv, alpha, out->d));
-  } else {
-    PO_TRY(k_panel_axpy(ctx, out->d, 0.0, nullptr, 0.0, alpha, U, nv, nwcon));
-    if (nwblock > 1) {  // -U^-1 (Y alpha)
-      double *Y[1] = {out->d};
-      PO_TRY(k_blk_solve(ctx, blk->d, nwcon / nwblock, nwblock, Y, 1, 2));
-      PO_TRY(k_scale(ctx, out->d, nwcon, -1.0));
-    } else {
-      PO_TRY(k_mul(ctx, out->d, -1.0, cw->d, out->d, nwcon));
-    }
-  }
-  if (acc) PO_TRY(k_axpy(ctx, acc->d, 1.0, out->d, nwcon));
-  return PO_OK;
-}
-
-int Problem::sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
-                                 Vec *work) {
+int Problem::sparsePanelImage(Vec *x, Vec *d, const double *const *P, int nv, double *const *U, Vec *work) {
   if (grouped) return k_group_panel(ctx, gmap, P, nv, d->d, group_alpha, U);
-  if (csr && !qd_set) return csr->panelPermuted(d->d, P, nv, U);
   for (int j = 0; j < nv; j++) {
     PO_TRY(k_mul(ctx, work->d, 1.0, d->d, P[j], nlocal));
     PO_TRY(k_fill(ctx, U[j], nwcon, 0.0));
-    // a real po_vec handle that borrows the panel column: host-side callbacks may ask it for a pinned mirror
-    // (po_vec_get_array), which is released here -- the handle never reaches vec_decref
-    po_vec_s u;
-    u.ctx = ctx;
-    u.n = nwcon;
-    u.d = U[j];
-    u.ref = 1;
-    u.h = nullptr;
-    const int fail = addSparseJacobian(1.0, x, work, &u);
-    if (u.h) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipHostFree(u.h);
-      mirror_freed();
-    }
-    if (fail != 0) return PO_ERR_USER;
+    BorrowedVec u(ctx, nwcon, U[j]);
+    if (addSparseJacobian(1.0, x, work, &u) != 0) return PO_ERR_USER;
   }
   return PO_OK;
 }
@@ -387,7 +248,7 @@ int Problem::checkGradients(double dh, Vec *x, bool check_hvec, Vec *xt, Vec *px
 }
 
 bool Problem::sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *col) {
-  if (qd_set || !grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
+  if (sparseUserSolver() || !grouped || nwcon <= 0 || gmap.start != 0 || nlocal >= 2000000000LL) return false;
   col->w = pzw->d;
   col->scale = alpha * group_alpha;  // the value k_group_scatter_set(..., alpha * group_alpha, ...) stores
   col->period = (unsigned)(gmap.nw + gmap.skip);
@@ -396,57 +257,13 @@ bool Problem::sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *co
   return true;
 }
 bool Problem::sparseGramGroups(Vec *x, GramGroups *g) {
-  if (qd_set || !grouped || nwblock > 1 || nwcon <= 0) return false;
+  if (sparseUserSolver() || !grouped || nwcon <= 0) return false;
   g->nwcon = gmap.nwcon;
   g->start = gmap.start;
   g->nw = gmap.nw;
   g->skip = gmap.skip;
   g->alpha = group_alpha;  // as in sparseJacobianPanel
   return true;
-}
-
-int Problem::sparseApplyK0(Vec *x, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
-                           Vec *wwork) {
-  if (qd_set) {  // the user's apply and nothing else
-    BorrowedVec vbx(ctx, nlocal, bx), vbw(ctx, nwcon, bw);
-    const int fail = qd.apply(qd.user, &vbx, bw ? static_cast<po_vec>(&vbw) : nullptr, static_cast<po_vec>(yx),
-                              static_cast<po_vec>(yw));
-    if (fail != 0) {
-      set_error("the problem's quasi-definite solver failed in apply (%d)", fail);
-      return PO_ERR_USER;
-    }
-    return PO_OK;
-  }
-  if (grouped && nwblock == 1) {
-    // u = Aw (d o bx) in one tiled pass, yw = cw (bw - u), yx = d (bx + alpha yw[group]); one launch where the map tiles
-    bool done = false;
-    PO_TRY(k_group_k0(ctx, gmap, d->d, bx, cw->d, bw, group_alpha, nlocal, yx->d, yw->d, &done));
-    if (done) return PO_OK;
-    const double *P[1] = {bx};
-    double *U[1] = {wwork->d};
-    PO_TRY(k_group_panel(ctx, gmap, P, 1, d->d, group_alpha, U));
-    PO_TRY(k_w_apply_mid(ctx, cw->d, bw, wwork->d, nwcon, yw->d));
-    return k_group_apply(ctx, gmap, d->d, bx, group_alpha, yw->d, nlocal, yx->d);
-  }
-  if (csr) return csr->applyK0(d->d, bx, bw, yx->d, yw->d);
-  const int64_t n = nlocal, w = nwcon;
-  PO_TRY(k_mul(ctx, yx->d, 1.0, d->d, bx, n));
-  if (bw) {
-    PO_TRY(k_copy(ctx, yw->d, bw, w));
-  } else {
-    PO_TRY(k_fill(ctx, yw->d, w, 0.0));
-  }
-  if (addSparseJacobian(-1.0, x, yx, yw) != 0) return PO_ERR_USER;
-  if (nwblock > 1) {  // applyFactor (:192-216)
-    double *Y[1] = {yw->d};
-    PO_TRY(k_blk_solve(ctx, blk->d, w / nwblock, nwblock, Y, 1, 0));
-  } else {
-    PO_TRY(k_mul(ctx, yw->d, 1.0, cw->d, yw->d, w));
-  }
-  PO_TRY(k_copy(ctx, yx->d, bx, n));
-  if (addSparseJacobianTranspose(1.0, x, yw, yx) != 0) return PO_ERR_USER;
-  PO_TRY(k_mul(ctx, yx->d, 1.0, d->d, yx->d, n));
-  return PO_OK;
 }
 
 // ---- callbacks --------------------------------------------------------------------------------
@@ -620,7 +437,7 @@ int SeparableProblem::setWeighting(int64_t nwg, int nw, int64_t nwstart, int nws
   nwinequality = nwineq - first;
   if (nwinequality < 0) nwinequality = 0;
   if (nwinequality > count) nwinequality = count;
-  return PO_OK;
+  return chooseSolver(userSolverTable(), nwblock);
 }
 int SeparableProblem::setChain(int span, int stride, int reverse_cols) {
   if (span < 1 || stride < 1) {

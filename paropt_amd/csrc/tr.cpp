@@ -196,10 +196,6 @@ int TrustRegionSubproblem::addSparseJacobianTranspose(double alpha, Vec *, Vec *
 int TrustRegionSubproblem::addSparseInnerProduct(double alpha, Vec *, Vec *cvec, Vec *A) {
   return prob->addSparseInnerProduct(alpha, xk, cvec, A);
 }
-int TrustRegionSubproblem::sparseJacobianPanel(Vec *, Vec *d, const double *const *P, int nv,
-                                               double *const *U, Vec *work) {
-  return prob->sparseJacobianPanel(xk, d, P, nv, U, work);
-}
 void TrustRegionSubproblem::rejectTrialStep() {  // :226-231
   ft = 0.0;
   for (int i = 0; i < m; i++) ct[i] = 0.0;

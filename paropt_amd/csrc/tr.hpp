@@ -88,34 +88,17 @@ class TrustRegionSubproblem : public Problem {
     return prob->setSparseJacobianTranspose(alpha, xk, pzw, out);
   }
   int addSparseInnerProduct(double alpha, Vec *x, Vec *cvec, Vec *A) override;
-  int sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
-                          Vec *work) override;
-  int sparseApplyK0(Vec *, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
-                    Vec *wwork) override {
-    return prob->sparseApplyK0(xk, d, cw, bx, bw, yx, yw, wwork);
-  }
-  int sparseFactor(Vec *, Vec *d, Vec *cw) override { return prob->sparseFactor(xk, d, cw); }
   bool sparseGramGroups(Vec *, GramGroups *g) override { return prob->sparseGramGroups(xk, g); }
   bool sparseTransposeColumn(double alpha, Vec *, Vec *pzw, GroupCol *col) override {
     return prob->sparseTransposeColumn(alpha, xk, pzw, col);
   }
-  int sparseFactorFromSlacks(Vec *, Vec *d, const WVars &v, Vec *cw) override {
-    return prob->sparseFactorFromSlacks(xk, d, v, cw);
-  }
   int setSparseJacobian(double alpha, Vec *, Vec *px, Vec *out) override {
     return prob->setSparseJacobian(alpha, xk, px, out);
   }
-  int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
-    return prob->sparseHalfSolve(U, nv, cw, weights);
-  }
-  bool sparseUserSolver() override { return prob->sparseUserSolver(); }
-  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
-    return prob->sparseSolvedPanel(P, nv, Yw, work);
-  }
-  const char *sparseFactorInfo() override { return prob->sparseFactorInfo(); }
-  long sparseFactorBreakdowns() override { return prob->sparseFactorBreakdowns(); }
-  int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) override {
-    return prob->sparseCorrection(U, nv, alpha, cw, out, acc);
+  // the quasi-definite solver is the wrapped problem's, with its Jacobian taken at the base point
+  Problem *sparseOwner(Vec **x) override {
+    *x = xk;
+    return prob->sparseOwner(x);
   }
   int writeOutput(int iter, Vec *x) override { return prob->writeOutput(iter, x); }
   // the model evaluations issue their reductions through the internal launchers and finish with
@@ -262,35 +245,12 @@ class InfeasSubproblem : public Problem {  // :468-650
   int addSparseInnerProduct(double a, Vec *x, Vec *cvec, Vec *A) override {
     return sub->addSparseInnerProduct(a, x, cvec, A);
   }
-  int sparseJacobianPanel(Vec *x, Vec *d, const double *const *P, int nv, double *const *U,
-                          Vec *work) override {
-    return sub->sparseJacobianPanel(x, d, P, nv, U, work);
-  }
-  int sparseApplyK0(Vec *x, Vec *d, Vec *cw, const double *bx, const double *bw, Vec *yx, Vec *yw,
-                    Vec *wwork) override {
-    return sub->sparseApplyK0(x, d, cw, bx, bw, yx, yw, wwork);
-  }
-  int sparseFactor(Vec *x, Vec *d, Vec *cw) override { return sub->sparseFactor(x, d, cw); }
   bool sparseGramGroups(Vec *x, GramGroups *g) override { return sub->sparseGramGroups(x, g); }
   bool sparseTransposeColumn(double alpha, Vec *x, Vec *pzw, GroupCol *col) override {
     return sub->sparseTransposeColumn(alpha, x, pzw, col);
   }
-  int sparseFactorFromSlacks(Vec *x, Vec *d, const WVars &v, Vec *cw) override {
-    return sub->sparseFactorFromSlacks(x, d, v, cw);
-  }
   int setSparseJacobian(double a, Vec *x, Vec *px, Vec *out) override { return sub->setSparseJacobian(a, x, px, out); }
-  int sparseHalfSolve(double *const *U, int nv, Vec *cw, const double **weights) override {
-    return sub->sparseHalfSolve(U, nv, cw, weights);
-  }
-  bool sparseUserSolver() override { return sub->sparseUserSolver(); }
-  int sparseSolvedPanel(const double *const *P, int nv, double *const *Yw, Vec *work) override {
-    return sub->sparseSolvedPanel(P, nv, Yw, work);
-  }
-  const char *sparseFactorInfo() override { return sub->sparseFactorInfo(); }
-  long sparseFactorBreakdowns() override { return sub->sparseFactorBreakdowns(); }
-  int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc) override {
-    return sub->sparseCorrection(U, nv, alpha, cw, out, acc);
-  }
+  Problem *sparseOwner(Vec **x) override { return sub->sparseOwner(x); }
   TrustRegionSubproblem *sub;
   int objective, constraint;
   double obj_scale;
