@@ -874,6 +874,26 @@ int po_mma_gcmma_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_v
 /* The sums behind the start values of rho, stand-alone: sums[m + 1] = {sum_j |g_j| (U_j - L_j), sum_j |A_i,j| (U_j -
  * L_j)}, one read-only pass; rho_i = max(mma_gcmma_rho_init / n * sums[i], mma_gcmma_rho_min) on the host. */
 int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const po_vec *A, double *sums);
+/* mma_gcmma_sparse_constraints = groups (default refuse; on top of mma_dual_sparse_constraints = groups and
+ * mma_globalization = conservative): the grouped sparse constraints stay in the dual of the conservative
+ * approximations.  In the grouped form they are affine, so they carry no rho and take no part in the acceptance test.
+ * po_mma_dual_group_eval for those approximations around xk with rho[m + 1]: W, grad, hess, the vectors and stats as
+ * there and, when D != NULL, D = d(x) at the point.  With every rho_i = 0 the bits of po_mma_dual_group_eval, except
+ * where an element's root search of the plain form creeps below the resolution of U - x and x - L: this form ends
+ * such a search (it also stops when a step changes neither difference), the plain form runs it into its step cap. */
+int po_mma_dual_group_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                               const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
+                               int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                               double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
+                               double *stats, po_vec xk, const double *rho, double *D);
+/* The point of a conservative trial with groups, stand-alone: the group solve at lambda[m] for the same approximations
+ * (x, zl, zu, zw all required; zw and c may be NULL when nwcon = 0), then sums[m + 2] = {Delta_0, Delta_1..m, D} as
+ * po_mma_gcmma_point defines them, taken at the stored x by one read-only pass; stats (may be NULL) as above. */
+int po_mma_gcmma_group_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                             const po_vec *p, const po_vec *q, const double *lambda, int64_t nwcon, int nw,
+                             int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                             po_vec xk, const double *rho, po_vec x, po_vec zl, po_vec zu, po_vec zw, double *sums,
+                             double *stats);
 
 #ifdef __cplusplus
 }

@@ -2376,28 +2376,59 @@ def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hes
 
 
 def mma_dual_group_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, nwcon, nw, start, skip, a, c, nwinequality,
-                        gamma, point, zw, hessian=True):
+                        gamma, point, zw, hessian=True, xk=None, rho=None):
     """The dual function with grouped sparse constraints kept in it (po_mma_dual_group_eval): group i owns the variables
     start + i (nw + skip) + [0, nw), psi_i = a sum x + c[i] >= 0 (= 0 from group nwinequality on), zw_i in [0, gamma]
     ([-gamma, gamma]).  point = (x, zl, zu) PVecs and zw (PVec of nwcon, None when nwcon = 0) are filled.  Returns
-    (W, grad, H, stats) with stats a dict of the group solve's counters."""
+    (W, grad, H, stats) with stats a dict of the group solve's counters.
+    xk (PVec) and rho (ncon + 1 values) given: the conservative approximations f~_i + rho_i d around xk
+    (po_mma_dual_group_eval_rho); returns (W, grad, H, stats, D) with D = d at the point."""
+    if (xk is None) != (rho is None):
+        raise ValueError("mma_dual_group_eval: xk and rho are given together")
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_dual_group_eval: ")
     (ba, bp), (la, lp) = _f64(b), _f64(lam)
     if ba.size != m or la.size != m:
         raise ValueError("mma_dual_group_eval: b and lam must hold one entry per constraint")
-    W = C.c_double()
+    W, D = C.c_double(), C.c_double()
     g = np.zeros(max(m, 1))
     H = np.zeros((m, m)) if hessian else None
     st = np.zeros(8)
-    check(lib.po_mma_dual_group_eval(*head, bp, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
-                                     c.handle if c is not None else None, int(nwinequality), float(gamma),
-                                     C.byref(W), g.ctypes.data_as(L.c_double_p),
-                                     H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, point[0].handle,
-                                     point[1].handle, point[2].handle, zw.handle if zw is not None else None,
-                                     st.ctypes.data_as(L.c_double_p)))
-    stats = dict(strict=int(st[0]), at_lower=int(st[1]), at_gamma=int(st[2]), cap_hits=int(st[3]), steps=int(st[4]),
-                 max_inner=int(st[5]), max_psi=float(st[6]), zw_psi=float(st[7]))
-    return W.value, g[:m], H, stats
+    args = (*head, bp, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
+            c.handle if c is not None else None, int(nwinequality), float(gamma), C.byref(W),
+            g.ctypes.data_as(L.c_double_p), H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None,
+            point[0].handle, point[1].handle, point[2].handle, zw.handle if zw is not None else None,
+            st.ctypes.data_as(L.c_double_p))
+    if xk is None:
+        check(lib.po_mma_dual_group_eval(*args))
+        return W.value, g[:m], H, _group_stats(st)
+    ra, rp = _f64(rho)
+    if ra.size != m + 1:
+        raise ValueError("mma_dual_group_eval: rho holds one entry per constraint and one more")
+    check(lib.po_mma_dual_group_eval_rho(*args, xk.handle, rp, C.byref(D)))
+    return W.value, g[:m], H, _group_stats(st), D.value
+
+
+def _group_stats(st):
+    return dict(strict=int(st[0]), at_lower=int(st[1]), at_gamma=int(st[2]), cap_hits=int(st[3]), steps=int(st[4]),
+                max_inner=int(st[5]), max_psi=float(st[6]), zw_psi=float(st[7]))
+
+
+def mma_gcmma_group_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, nwcon, nw, start, skip, a, c, nwinequality,
+                          gamma, xk, rho, point, zw):
+    """The point of a conservative trial with grouped sparse constraints (po_mma_gcmma_group_point): the group solve
+    at lam for the approximations f~_i + rho_i d around xk fills point = (x, zl, zu) and zw; returns (sums, stats)
+    with the m + 2 sums [Delta_0, Delta_1..m, D] of mma_gcmma_point at that x."""
+    m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_gcmma_group_point: ")
+    (la, lp), (ra, rp) = _f64(lam), _f64(rho)
+    if la.size != m or ra.size != m + 1:
+        raise ValueError("lam holds one entry per constraint, rho one more")
+    sums, st = np.zeros(m + 2), np.zeros(8)
+    check(lib.po_mma_gcmma_group_point(*head, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
+                                       c.handle if c is not None else None, int(nwinequality), float(gamma),
+                                       xk.handle, rp, point[0].handle, point[1].handle, point[2].handle,
+                                       zw.handle if zw is not None else None, sums.ctypes.data_as(L.c_double_p),
+                                       st.ctypes.data_as(L.c_double_p)))
+    return sums, _group_stats(st)
 
 
 def mma_gcmma_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, xk, rho, point):

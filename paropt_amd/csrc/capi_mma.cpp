@@ -282,16 +282,48 @@ int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const
   }
   return k_mma_gcmma_rho_sums(ctx, L->d, U->d, g->d, cols.data(), m, L->n, sums);
 }
-int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                           const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
-                           int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
-                           double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
-                           double *stats) {
-  const char *who = "po_mma_dual_group_eval";
+namespace {
+struct GroupCall {  // po_mma_dual_group_eval / _rho (W != NULL) and po_mma_gcmma_group_point (sums != NULL)
+  const char *who;
+  po_ctx ctx;
+  int m;
+  DualVectors v;
+  const double *b, *lambda;
+  int64_t nwcon;
+  int nw;
+  int64_t start;
+  int skip;
+  double a;
+  po_vec c;
+  int64_t nwinequality;
+  double gamma;
+  double *W, *grad, *hess;
+  po_vec x, zl, zu, zw;
+  double *stats;
+  po_vec xk;          // the rho form (with rho) and the point
+  const double *rho;
+  double *D, *sums;
+};
+}  // namespace
+static int mma_group_entry(const GroupCall &k) {
+  const char *who = k.who;
+  const po_ctx ctx = k.ctx;
+  const int m = k.m;
+  const po_vec L = k.v.L, U = k.v.U, alpha = k.v.alpha, beta = k.v.beta, p0 = k.v.p0, q0 = k.v.q0;
+  const po_vec *p = k.v.p, *q = k.v.q;
+  const double *b = k.b, *lambda = k.lambda;
+  const int64_t nwcon = k.nwcon, start = k.start, nwinequality = k.nwinequality;
+  const int nw = k.nw, skip = k.skip;
+  const double a = k.a, gamma = k.gamma;
+  const po_vec c = k.c, x = k.x, zl = k.zl, zu = k.zu, zw = k.zw;
+  double *W = k.W, *grad = k.grad, *hess = k.hess, *stats = k.stats;
+  const bool point = k.sums != nullptr;
   PO_CHECK_PTR(ctx);
   PO_CHECK_PTR(L);
-  PO_CHECK_PTR(W);
-  PO_CHECK_PTR(grad);
+  if (!point) {
+    PO_CHECK_PTR(W);
+    PO_CHECK_PTR(grad);
+  }
   if (m < 0 || m > kMmaDualMax) {
     po::set_error("%s: m = %d outside 0..%d", who, m, kMmaDualMax);
     return PO_ERR_ARG;
@@ -303,6 +335,7 @@ int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, 
     PO_CHECK_PTR(lambda);
   }
   std::vector<po_vec> nvecs = {L, U, alpha, beta, p0, q0, x, zl, zu};
+  if (k.rho) nvecs.push_back(k.xk);
   for (int i = 0; i < m; i++) {
     nvecs.push_back(p[i]);
     nvecs.push_back(q[i]);
@@ -343,6 +376,19 @@ int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, 
     qq.push_back(q[i]->d);
   }
   const MmaDualData s = mma_dual_data(L->d, U->d, alpha->d, beta->d, p0->d, q0->d, pp.data(), qq.data(), b, m, L->n);
+  const MmaDualRho r{k.rho ? k.xk->d : nullptr, k.rho};
+  MmaGroupStats st;
+  auto put_stats = [&]() {
+    const double out[8] = {(double)st.strict,    (double)st.at_lower, (double)st.at_gamma, (double)st.cap_hits,
+                           (double)st.steps,     (double)st.max_inner, st.max_psi,         st.zw_psi};
+    for (int i = 0; i < 8 && stats; i++) stats[i] = out[i];
+  };
+  if (point) {
+    PO_TRY(k_mma_group_solve(ctx, s, g, lambda, x->d, nwcon > 0 ? zw->d : nullptr, zl->d, zu->d, &st, &r));
+    PO_TRY(k_mma_gcmma_group_sums(ctx, s, r.xk, x->d, k.sums));
+    put_stats();
+    return PO_OK;
+  }
   std::vector<Vec *> work;  // G (m of n), d (n), Uw (m of nwcon), sw (nwcon)
   std::vector<double *> G, Uw;
   int rc = PO_OK;
@@ -352,22 +398,55 @@ int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, 
     if (!v) rc = PO_ERR_HIP;
     else work.push_back(v);
   }
-  MmaGroupStats st;
   if (rc == PO_OK) {
     for (int i = 0; i < m; i++) G.push_back(work[i]->d);
     for (int i = 0; i < m && nwcon > 0; i++) Uw.push_back(work[m + 1 + i]->d);
     rc = k_mma_dual_groups(ctx, s, g, lambda, W, grad, hess, G.data(), work[m]->d, x->d, nwcon > 0 ? zw->d : nullptr,
                            nwcon > 0 ? Uw.data() : nullptr, nwcon > 0 ? work[2 * m + 1]->d : nullptr, zl->d, zu->d,
-                           &st);
+                           &st, k.rho ? &r : nullptr, k.D);
   }
   if (rc == PO_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
   for (Vec *v : work) vec_decref(v);
-  if (rc == PO_OK && stats) {
-    const double out[8] = {(double)st.strict,    (double)st.at_lower, (double)st.at_gamma, (double)st.cap_hits,
-                           (double)st.steps,     (double)st.max_inner, st.max_psi,         st.zw_psi};
-    for (int i = 0; i < 8; i++) stats[i] = out[i];
-  }
+  if (rc == PO_OK) put_stats();
   return rc;
+}
+int po_mma_dual_group_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                           const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
+                           int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                           double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
+                           double *stats) {
+  return mma_group_entry({.who = "po_mma_dual_group_eval", .ctx = ctx, .m = m, .v = {L, U, alpha, beta, p0, q0, p, q},
+                          .b = b, .lambda = lambda, .nwcon = nwcon, .nw = nw, .start = start, .skip = skip, .a = a,
+                          .c = c, .nwinequality = nwinequality, .gamma = gamma, .W = W, .grad = grad, .hess = hess,
+                          .x = x, .zl = zl, .zu = zu, .zw = zw, .stats = stats});
+}
+int po_mma_dual_group_eval_rho(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                               const po_vec *p, const po_vec *q, const double *b, const double *lambda, int64_t nwcon,
+                               int nw, int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                               double *W, double *grad, double *hess, po_vec x, po_vec zl, po_vec zu, po_vec zw,
+                               double *stats, po_vec xk, const double *rho, double *D) {
+  PO_CHECK_PTR(xk);
+  PO_CHECK_PTR(rho);
+  return mma_group_entry({.who = "po_mma_dual_group_eval_rho", .ctx = ctx, .m = m,
+                          .v = {L, U, alpha, beta, p0, q0, p, q}, .b = b, .lambda = lambda, .nwcon = nwcon, .nw = nw,
+                          .start = start, .skip = skip, .a = a, .c = c, .nwinequality = nwinequality, .gamma = gamma,
+                          .W = W, .grad = grad, .hess = hess, .x = x, .zl = zl, .zu = zu, .zw = zw, .stats = stats,
+                          .xk = xk, .rho = rho, .D = D});
+}
+int po_mma_gcmma_group_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                             const po_vec *p, const po_vec *q, const double *lambda, int64_t nwcon, int nw,
+                             int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
+                             po_vec xk, const double *rho, po_vec x, po_vec zl, po_vec zu, po_vec zw, double *sums,
+                             double *stats) {
+  PO_CHECK_PTR(xk);
+  PO_CHECK_PTR(rho);
+  PO_CHECK_PTR(sums);
+  const double none = 0.0;  // (the point does not read b)
+  return mma_group_entry({.who = "po_mma_gcmma_group_point", .ctx = ctx, .m = m,
+                          .v = {L, U, alpha, beta, p0, q0, p, q}, .b = &none, .lambda = lambda, .nwcon = nwcon,
+                          .nw = nw, .start = start, .skip = skip, .a = a, .c = c, .nwinequality = nwinequality,
+                          .gamma = gamma, .x = x, .zl = zl, .zu = zu, .zw = zw, .stats = stats, .xk = xk, .rho = rho,
+                          .sums = sums});
 }
 int po_mma_get_dual_group_stats(po_mma mma, long *strict, long *at_lower, long *at_gamma, int *max_inner,
                                 long *cap_hits, double *max_psi) {

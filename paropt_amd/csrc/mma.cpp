@@ -126,8 +126,10 @@ int MMA::checkDualCovers() {
   const GroupMap *gm = prob->groupedLibraryForm();
   if (nwcon > 0 && !wantGroups()) {
     why = "sparse constraints are not part of the closed-form primal point";
-  } else if (nwcon > 0 && std::string(options().str("mma_globalization")) == "conservative") {
-    why = "sparse constraints in groups do not run under mma_globalization = conservative";
+  } else if (nwcon > 0 && std::string(options().str("mma_globalization")) == "conservative" &&
+             std::string(options().str("mma_gcmma_sparse_constraints")) != "groups") {
+    why = "sparse constraints in groups run under mma_globalization = conservative only with "
+          "mma_gcmma_sparse_constraints = groups";
   } else if (nwcon > 0 && (!gm || gm->nwcon != nwcon || !mma_dual_groups_tile(*gm, nlocal))) {
     why = "sparse constraints run through the dual only in the grouped form: one constraint per group of nw "
           "consecutive variables with one Jacobian value (setWeighting, or a CSR pattern recognised as such), "
@@ -145,7 +147,8 @@ int MMA::checkDualCovers() {
 }
 
 // rho != nullptr: the subproblem in the conservative approximations f~_i + rho_i d around xvec; point_sums[m + 2] then
-// receives {Delta_0..m, D} of the solution (mma_gcmma.hpp)
+// receives {Delta_0..m, D} of the solution (mma_gcmma.hpp).  Grouped sparse constraints are affine in the grouped form,
+// so their approximation is exact: they carry no rho and take no part in the acceptance test
 int MMA::solveDual(const double *rho, double *point_sums) {
   Options &o = options();
   const int form = m <= kMmaDualFused ? 1 : 2;
@@ -157,7 +160,7 @@ int MMA::solveDual(const double *rho, double *point_sums) {
     if (use_groups) {
       MmaGroupStats st;
       PO_TRY(k_mma_dual_groups(ctx, sub, grp, lam, W, g, want_h ? H : nullptr, G.data(), linv->d, uinv->d, zwvec->d,
-                               Uw.data(), swvec->d, nullptr, nullptr, &st));
+                               Uw.data(), swvec->d, nullptr, nullptr, &st, rho ? &r : nullptr));
       over.max_inner = std::max(over.max_inner, st.max_inner);
       over.cap_hits += st.cap_hits;
       over.max_psi = std::max(over.max_psi, st.max_psi);
@@ -169,7 +172,9 @@ int MMA::solveDual(const double *rho, double *point_sums) {
   PO_TRY(mma_dual_solve(m, gamma.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"), eval,
                         lambda.data(), &res));
   if (use_groups) {
-    PO_TRY(k_mma_group_solve(ctx, sub, grp, lambda.data(), uinv->d, zwvec->d, zlvec->d, zuvec->d, &groups));
+    PO_TRY(k_mma_group_solve(ctx, sub, grp, lambda.data(), uinv->d, zwvec->d, zlvec->d, zuvec->d, &groups,
+                             rho ? &r : nullptr));
+    if (rho) PO_TRY(k_mma_gcmma_group_sums(ctx, sub, xvec->d, uinv->d, point_sums));
     groups.max_inner = std::max(groups.max_inner, over.max_inner);
     groups.cap_hits += over.cap_hits;
     groups.max_psi = std::max(groups.max_psi, over.max_psi);

@@ -318,7 +318,9 @@ __device__ __forceinline__ void dual_block_reduce(double (&a)[N], double *__rest
 // MODE 3 (RHO only), the point pass of an inner iteration: x, zl, zu are stored and the slots are
 // {Delta_0, Delta_i[MC], D}, Delta_i = sum p_i (u - u_k) + q_i (l - l_k) = f~_i(x) - f~_i(xk), with
 // u - u_k = (x - xk) u u_k and l - l_k = -(x - xk) l l_k (no cancellation against n).
-// MODE 4 (plain form only), the sums of the grouped dual: as 2, at the stored point xin instead of the closed form.
+// MODE 4, the sums of the grouped dual: as 2, at the stored point xin instead of the closed form.
+// MODE 5 (RHO only), the sums of the point pass at the stored point xin: slots as 3, read-only -- nothing is stored and
+// P, Q are not formed.
 template <int MC, int MODE, bool RHO>
 struct DualSlots {
   static constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
@@ -338,14 +340,14 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
                                           const double *__restrict__ xin = nullptr) {
   constexpr bool HOLD = MC <= PO_MMA_DUAL_HOLD;
   constexpr bool POINT = MODE == 3;
-  constexpr bool STORED = MODE == 4;
-  constexpr bool PANEL = MODE == 2 || STORED;
+  constexpr bool PSUMS = POINT || MODE == 5;  // the slots {Delta_0, Delta_i, D}
+  constexpr bool STORED = MODE == 4 || MODE == 5;
+  constexpr bool PANEL = MODE == 2 || MODE == 4;
   constexpr bool HESS = MODE == 1 || PANEL;
   constexpr int NVB = 8;
   constexpr int NS = DualSlots<MC, MODE, RHO>::NS;
   static_assert(MODE != 1 || MC <= kMmaDualFused, "the fused Hessian needs the columns in registers");
-  static_assert(!POINT || RHO, "the point pass with sums belongs to the rho form");
-  static_assert(!STORED || !RHO, "the stored point belongs to the plain form");
+  static_assert(!PSUMS || RHO, "the point pass with sums belongs to the rho form");
   double acc[NS];
 #pragma unroll
   for (int s = 0; s < NS; s++) acc[s] = 0.0;
@@ -367,14 +369,16 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
           qv[i] = ld_nt(Qt.p[i] + 2 * q);
         }
       }
+      if (MODE != 5) {
 #pragma unroll
-      for (int i = 0; i < MC; i++) {
-        if (i < m) {
-          P = fma2(lam.a[i], pv[i], P);
-          Q = fma2(lam.a[i], qv[i], Q);
+        for (int i = 0; i < MC; i++) {
+          if (i < m) {
+            P = fma2(lam.a[i], pv[i], P);
+            Q = fma2(lam.a[i], qv[i], Q);
+          }
         }
       }
-    } else {
+    } else if (MODE != 5) {
       dual_pq_all(Pt, Qt, lam, m, q, P, Q);
     }
     const f64x2 P0s = P, Q0s = Q;
@@ -397,7 +401,7 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
       if (!has2) dx.y = 0.0;
       const f64x2 ul = t.u * t.l;
       acc[NS - 1] = fma(dx.x * dx.x, ul.x, fma(dx.y * dx.y, ul.y, acc[NS - 1]));
-      if (POINT) {
+      if (PSUMS) {
         f64x2 uk, lk;
         uk.x = 1.0 / (Uv.x - xkv.x);
         lk.x = 1.0 / (xkv.x - Lv.x);
@@ -405,6 +409,8 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
         lk.y = has2 ? 1.0 / (xkv.y - Lv.y) : 0.0;
         su = dx * t.u * uk;
         sl = -(dx * t.l * lk);
+      }
+      if (POINT) {
         const f64x2 ql = Q * l2;
         const f64x2 r = (f64x2){fma(P.x, u2.x, -ql.x), fma(P.y, u2.y, -ql.y)};
         f64x2 xs = t.x, lo, up;
@@ -418,7 +424,7 @@ __device__ __forceinline__ void dual_body(const double *__restrict__ L, const do
         st_nt(zuo + 2 * q, up);
       }
     }
-    if (POINT) acc[0] = dot4(p0v, su, q0v, sl, acc[0]);
+    if (PSUMS) acc[0] = dot4(p0v, su, q0v, sl, acc[0]);
     else acc[0] = dot4(P0s, t.u, Q0s, t.l, acc[0]);
     f64x2 dw = (f64x2){0.0, 0.0}, gd = (f64x2){0.0, 0.0};
     if (HESS) {
@@ -762,6 +768,37 @@ __global__ void __launch_bounds__(kBlock)
   dual_body<MC, 4, false>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, Gt, dout, partials, sm, qfirst, qstride,
                           nullptr, lam, 0.0, nullptr, nullptr, nullptr, x);
 }
+// ... in the rho form: slot 0 on P0, Q0, the columns with rho_i times the derivative of d, h on the full P, Q, and D
+template <int MC>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_stored_rho_kernel(const double *__restrict__ L, const double *__restrict__ U,
+                               const double *__restrict__ alpha, const double *__restrict__ beta,
+                               const double *__restrict__ p0, const double *__restrict__ q0,
+                               const double *__restrict__ xk, const double *__restrict__ x, PtrTable Pt, PtrTable Qt,
+                               CoefTable lam, CoefTable rho, double sigma, int m, int64_t n, PtrTableW Gt,
+                               double *__restrict__ dout, double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, 4, true>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  dual_body<MC, 4, true>(L, U, alpha, beta, p0, q0, Pt, Qt, lam, m, n, Gt, dout, partials, sm, qfirst, qstride, xk,
+                         rho, sigma, nullptr, nullptr, nullptr, x);
+}
+// the sums {Delta_0, Delta_i, D} of a conservative trial at the stored point: read-only, once per trial
+template <int MC>
+__global__ void __launch_bounds__(kBlock)
+    mma_gcmma_group_sums_kernel(const double *__restrict__ L, const double *__restrict__ U,
+                                const double *__restrict__ p0, const double *__restrict__ q0,
+                                const double *__restrict__ xk, const double *__restrict__ x, PtrTable Pt, PtrTable Qt,
+                                int m, int64_t n, double *__restrict__ partials) {
+  __shared__ double sm[4 * DualSlots<MC, 5, true>::NS];
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  PtrTableW none = {};
+  CoefTable zero = {};
+  // (the move limits only decide [free], which no slot of this mode takes: L, U stand in for them)
+  dual_body<MC, 5, true>(L, U, L, U, p0, q0, Pt, Qt, zero, m, n, none, nullptr, partials, sm, qfirst, qstride, xk,
+                         zero, 0.0, nullptr, nullptr, nullptr, x);
+}
 
 // sum of nw consecutive LDS values in index order (row_sum of wcon.hip)
 __device__ __forceinline__ double row_sum_lds(const double *row, int nw) {
@@ -788,6 +825,11 @@ __device__ __forceinline__ double group_phi1(double P, double Q, double L, doubl
 }
 // clamp(root of phi'(x) = t, alpha, beta) by a bracketed Newton iteration from x0: a step that leaves the bracket is
 // replaced by its midpoint; it ends when the iterate or the bracket stops moving.  *capped is raised at the step cap.
+// RHO: it also ends when the step changes neither U - x nor x - L.  Where |x| is far below |L|, |U| a step of one ulp
+// of x is below the resolution of both differences: phi' keeps its value (a rounding residue of P u^2 - Q l^2, which
+// sigma makes large), the step keeps its size, and x creeps one ulp at a time into the cap.  The plain form keeps its
+// stop test, and with it its bits.
+template <bool RHO>
 __device__ __forceinline__ double group_el_root(const GroupEl &e, double t, double x0, int &capped) {
   if (!(t > e.ga)) return e.a;
   if (!(t < e.gb)) return e.b;
@@ -805,6 +847,7 @@ __device__ __forceinline__ double group_el_root(const GroupEl &e, double t, doub
     double xn = x - f / h;
     if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
     if (!(xn > lo && xn < hi) || xn == x) break;
+    if (RHO && e.U - xn == e.U - x && xn - e.L == x - e.L) break;
     x = xn;
   }
   if (it == kGroupNewtonCap) capped++;
@@ -844,6 +887,16 @@ __device__ __forceinline__ void group_pq(const double *__restrict__ p0, const do
     Q = fma(lam.a[j], b0, Q);
   }
 }
+// the rho form (dual_body, RHO): P, Q of the element at index i gain sigma (w_U, w_L) -- the same expressions
+__device__ __forceinline__ void group_pq_rho(const double *__restrict__ xk, double sigma, double L, double U,
+                                             int64_t i, double &P, double &Q) {
+  const double xkv = __builtin_nontemporal_load(xk + i);
+  const double dU = U - xkv, dL = xkv - L;
+  const double rs = 1.0 / (U - L);
+  const double wU = dU * dU * rs, wL = dL * dL * rs;
+  P = fma(sigma, wU, P);
+  Q = fma(sigma, wL, Q);
+}
 // x, and with zl != nullptr the bound multipliers, of an element whose multiplier term is t (0 outside the groups)
 __device__ __forceinline__ void group_store(const GroupEl &e, double x, double t, int64_t i, double *__restrict__ xo,
                                             double *__restrict__ zl, double *__restrict__ zu) {
@@ -863,6 +916,9 @@ constexpr int kGroupSums = 6, kGroupMaxs = 2;
 // inside the bracket [lo, hi], whose upper end gamma is evaluated only when a step reaches it; the midpoint when the
 // step leaves the bracket.  The rounds end when every group of the tile has ended.  Variables before `start`, in the
 // gaps between the groups and behind the last period take the closed form.
+// RHO: the conservative approximations around xk -- P, Q gain sigma (w_U, w_L) once, right after they are formed (one
+// more stream); everything downstream takes the full P, Q.  The groups themselves are affine and carry no rho.
+template <bool RHO>
 __global__ void __launch_bounds__(kBlock)
     mma_group_solve_kernel(GroupMap gm, double ga, const double *__restrict__ cvec, int64_t nwineq, double gamma,
                            const double *__restrict__ L, const double *__restrict__ U,
@@ -870,7 +926,7 @@ __global__ void __launch_bounds__(kBlock)
                            const double *__restrict__ p0, const double *__restrict__ q0, PtrTable Pt, PtrTable Qt,
                            CoefTable lam, int m, int64_t n, int G, int64_t ntiles, double *__restrict__ xo,
                            double *__restrict__ zwo, double *__restrict__ zl, double *__restrict__ zu,
-                           double *__restrict__ partials) {
+                           double *__restrict__ partials, const double *__restrict__ xk, double sigma) {
   __shared__ double smx[kGroupTile + kBlock], smd[kGroupTile + kBlock];
   __shared__ double sz[kBlock];
   __shared__ int sdone[kBlock];
@@ -906,6 +962,10 @@ __global__ void __launch_bounds__(kBlock)
     e1.b = __builtin_nontemporal_load(beta + i1);
     group_pq(p0, q0, Pt, Qt, lam, m, i0, e0.P, e0.Q);
     group_pq(p0, q0, Pt, Qt, lam, m, i1, e1.P, e1.Q);
+    if (RHO) {
+      group_pq_rho(xk, sigma, e0.L, e0.U, i0, e0.P, e0.Q);
+      group_pq_rho(xk, sigma, e1.L, e1.U, i1, e1.P, e1.Q);
+    }
     // the closed form: the point of every element at zw = 0, and the start of the root searches
     const double xc0 = group_closed_form(e0.P, e0.Q, e0.L, e0.U, e0.a, e0.b);
     const double xc1 = group_closed_form(e1.P, e1.Q, e1.L, e1.U, e1.a, e1.b);
@@ -934,14 +994,14 @@ __global__ void __launch_bounds__(kBlock)
     for (;;) {
       if (grp0 && !sdone[gi0]) {
         t0 = ga * sz[gi0];
-        x0 = t0 == 0.0 ? xc0 : group_el_root(e0, t0, x0, capped);
+        x0 = t0 == 0.0 ? xc0 : group_el_root<RHO>(e0, t0, x0, capped);
         const double u = 1.0 / (e0.U - x0), l = 1.0 / (x0 - e0.L);
         smx[s0] = x0;
         smd[s0] = (x0 > e0.a && x0 < e0.b) ? 1.0 / (2.0 * (e0.P * (u * u * u) + e0.Q * (l * l * l))) : 0.0;
       }
       if (grp1 && !sdone[gi1]) {
         t1 = ga * sz[gi1];
-        x1 = t1 == 0.0 ? xc1 : group_el_root(e1, t1, x1, capped);
+        x1 = t1 == 0.0 ? xc1 : group_el_root<RHO>(e1, t1, x1, capped);
         const double u = 1.0 / (e1.U - x1), l = 1.0 / (x1 - e1.L);
         smx[s1] = x1;
         smd[s1] = (x1 > e1.a && x1 < e1.b) ? 1.0 / (2.0 * (e1.P * (u * u * u) + e1.Q * (l * l * l))) : 0.0;
@@ -1005,6 +1065,7 @@ __global__ void __launch_bounds__(kBlock)
     e.b = beta[g];
     e.ga = e.gb = 0.0;
     group_pq(p0, q0, Pt, Qt, lam, m, g, e.P, e.Q);
+    if (RHO) group_pq_rho(xk, sigma, e.L, e.U, g, e.P, e.Q);
     group_store(e, group_closed_form(e.P, e.Q, e.L, e.U, e.a, e.b), 0.0, g, xo, zl, zu);
   }
   if ((n & 1) && blockIdx.x == 0 && tid == 0) {  // the pad element of an odd length stays zero
@@ -1040,10 +1101,11 @@ bool mma_dual_groups_tile(const GroupMap &m, int64_t n) {
 }
 
 int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *x,
-                      double *zw, double *zl, double *zu, MmaGroupStats *st) {
+                      double *zw, double *zl, double *zu, MmaGroupStats *st, const MmaDualRho *r) {
   PtrTable pt, qt;
-  CoefTable ct;
+  CoefTable ct, rt;
   PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  const double sigma = r ? rho_tables(*r, s.m, lambda, &rt) : 0.0;  // (the groups take no table of rho)
   GroupMap gm = g.map;
   if (gm.nwcon <= 0) {  // no group: every variable takes the closed form
     gm = GroupMap();
@@ -1058,14 +1120,19 @@ int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
   int G = kGroupTile / period;
   if (G > kBlock) G = kBlock;
   const int64_t ntiles = (gm.nwcon + G - 1) / G;
-  count_bytes(c, 2 * s.m + 6 + 1 + (zl ? 2 : 0), s.n);
+  count_bytes(c, 2 * s.m + 6 + 1 + (r ? 1 : 0) + (zl ? 2 : 0), s.n);
   count_bytes(c, 2.0, gm.nwcon);
   int64_t want = ntiles > (s.n + kBlock - 1) / kBlock / 8 ? ntiles : (s.n + kBlock - 1) / kBlock / 8;
   if (want > (int64_t)c->num_cu * 4) want = (int64_t)c->num_cu * 4;
   const int grid = want < 1 ? 1 : (int)want;
   PO_TRY(ensure_partials(c, (size_t)grid * (kGroupSums + kGroupMaxs)));
-  PO_MLAUNCH(mma_group_solve_kernel, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta, s.p0,
-             s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials);
+  if (r) {
+    PO_MLAUNCH(mma_group_solve_kernel<true>, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta,
+               s.p0, s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, r->xk, sigma);
+  } else {
+    PO_MLAUNCH(mma_group_solve_kernel<false>, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta,
+               s.p0, s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, nullptr, 0.0);
+  }
   double out[kGroupSums + kGroupMaxs];
   PO_TRY(reduce_finish(c, grid, kGroupSums, 0, kGroupMaxs, out, true));
   if (st) {
@@ -1078,6 +1145,29 @@ int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
     st->max_inner = (int)out[6];
     st->max_psi = out[7];
   }
+  return PO_OK;
+}
+
+int k_mma_gcmma_group_sums(Ctx *c, const MmaDualData &s, const double *xk, const double *x, double *sums) {
+  const int m = s.m;
+  PtrTable pt, qt;
+  CoefTable ct;
+  std::vector<double> none(m > 0 ? m : 1, 0.0);  // (the pass takes no multipliers)
+  PO_TRY(dual_tables(s, none.data(), &pt, &qt, &ct));
+  count_bytes(c, 2 * m + 6, s.n);
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  int ns = 0;
+  PO_TRY(with_capacity(m, [&](auto MC) -> int {
+    constexpr int kMC = decltype(MC)::value;
+    ns = DualSlots<kMC, 5, true>::NS;
+    PO_TRY(ensure_partials(c, (size_t)grid * ns));
+    PO_MLAUNCH((mma_gcmma_group_sums_kernel<kMC>), grid, s.L, s.U, s.p0, s.q0, xk, x, pt, qt, m, s.n, c->d_partials);
+    return PO_OK;
+  }));
+  double all[96 + 2];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
+  for (int i = 0; i <= m; i++) sums[i] = all[i];
+  sums[m + 1] = all[ns - 1];
   return PO_OK;
 }
 
@@ -1096,34 +1186,48 @@ __global__ void __launch_bounds__(kBlock)
 
 int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *W,
                       double *grad, double *H, double *const *G, double *dvec, double *x, double *zw,
-                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st) {
+                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st, const MmaDualRho *r,
+                      double *D) {
   const int m = s.m;
   MmaGroupStats local;
   if (!st) st = &local;
-  PO_TRY(k_mma_group_solve(c, s, g, lambda, x, zw, zl, zu, st));
+  PO_TRY(k_mma_group_solve(c, s, g, lambda, x, zw, zl, zu, st, r));
   PtrTable pt, qt;
-  CoefTable ct;
+  CoefTable ct, rt;
   PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  const double sigma = r ? rho_tables(*r, m, lambda, &rt) : 0.0;
   if (!dvec || (m > 0 && !G)) {
     set_error("MMA dual: the grouped evaluation needs its %d column vectors and the weight vector", m);
     return PO_ERR_ARG;
   }
   PtrTableW gt;
   for (int i = 0; i < kMaxPanel; i++) gt.p[i] = i < m ? G[i] : nullptr;
-  count_bytes(c, 2 * m + 7 + m + 1, s.n);
+  count_bytes(c, 2 * m + 7 + (r ? 1 : 0) + m + 1, s.n);
   const int grid = grid_for(c, s.n, kBpcPanel);
   int ns = 0;
   PO_TRY(with_capacity(m, [&](auto MC) -> int {
     constexpr int kMC = decltype(MC)::value;
-    ns = DualSlots<kMC, 4, false>::NS;
+    ns = r ? DualSlots<kMC, 4, true>::NS : DualSlots<kMC, 4, false>::NS;
     PO_TRY(ensure_partials(c, (size_t)grid * ns));
-    PO_MLAUNCH((mma_dual_stored_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, x, pt, qt, ct, m, s.n, gt,
-               dvec, c->d_partials);
+    if (r) {
+      PO_MLAUNCH((mma_dual_stored_rho_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, x, pt, qt, ct,
+                 rt, sigma, m, s.n, gt, dvec, c->d_partials);
+    } else {
+      PO_MLAUNCH((mma_dual_stored_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, x, pt, qt, ct, m, s.n, gt,
+                 dvec, c->d_partials);
+    }
     return PO_OK;
   }));
-  double sums[1 + 96];
+  double sums[1 + 96 + 1];
   PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
-  double w = sums[0] - st->zw_psi;
+  double w = sums[0];
+  if (r) {  // (exact zeros where rho = 0)
+    const double d = sums[ns - 1];
+    w += sigma * d;
+    for (int i = 0; i < m; i++) sums[1 + i] += r->rho[1 + i] * d;
+    if (D) *D = d;
+  }
+  w -= st->zw_psi;
   for (int i = 0; i < m; i++) {
     w += lambda[i] * s.b[i];
     grad[i] = sums[1 + i] + s.b[i];

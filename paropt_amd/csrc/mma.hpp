@@ -96,14 +96,22 @@ struct MmaGroupStats {  // of one group-solve pass, over all ranks
 bool mma_dual_groups_tile(const GroupMap &m, int64_t n);
 // x (n) and zw (nwcon) at lambda; zl, zu (both or neither) receive the bound multipliers with the group term in
 // r = P u^2 - Q l^2 - a zw; collective
+// r != nullptr: the rho form -- P, Q gain sigma (w_U, w_L) around r->xk; the groups are affine and carry no rho
 int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *x,
-                      double *zw, double *zl, double *zu, MmaGroupStats *st);
+                      double *zw, double *zl, double *zu, MmaGroupStats *st, const MmaDualRho *r = nullptr);
 // The evaluation: the group solve, then the sums at the stored point in the panel form (G: m columns, dvec: n), and
 // with H != nullptr  H = G^T diag(dvec) G - sum over the strict groups of a_g a_g^T / s_g  (Uw: m columns of nwcon,
 // sw: nwcon).  x and zw are left at the point of lambda, zl and zu (both or neither) as in the group solve; collective.
+// r != nullptr: the rho form of k_mma_dual on top of the groups; *D (optional) receives d at the point.  With every
+// rho_i = 0: the bits of the plain form wherever the rho form's second stop of the element search (mma.hip,
+// group_el_root) does not act.
 int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *W,
                       double *grad, double *H, double *const *G, double *dvec, double *x, double *zw,
-                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st);
+                      double *const *Uw, double *sw, double *zl, double *zu, MmaGroupStats *st,
+                      const MmaDualRho *r = nullptr, double *D = nullptr);
+// sums[m + 2] = {Delta_0, Delta_1..m, D} of k_mma_gcmma_point at a stored point x (the final group solve's): one
+// read-only pass per conservative trial; collective
+int k_mma_gcmma_group_sums(Ctx *c, const MmaDualData &s, const double *xk, const double *x, double *sums);
 
 typedef int (*MmaIterationFn)(void *user, int iter);
 

@@ -245,6 +245,13 @@ void Options::addMMADefaults() {
   inner.ilo = 0;
   inner.ihi = 1000;
   e["mma_gcmma_max_inner"] = inner;
+  // grouped sparse constraints under the conservative variant: an opt-in of its own on top of
+  // mma_dual_sparse_constraints = groups (the groups are affine: no rho, no acceptance test)
+  Entry gsc;
+  gsc.type = ENUM;
+  gsc.s = "refuse";
+  gsc.choices = {"refuse", "groups"};
+  e["mma_gcmma_sparse_constraints"] = gsc;
 }
 
 int Options::set(const char *name, const char *value) {

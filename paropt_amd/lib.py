@@ -412,6 +412,16 @@ SIGNATURES = {
                                                                               C.c_int, C.c_int64, C.c_int, C.c_double,
                                                                               po_vec, C.c_int64, C.c_double]
         + [c_double_p] * 3 + [po_vec] * 4 + [c_double_p]),
+    "po_mma_dual_group_eval_rho": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, c_double_p, C.c_int64,
+                                                                              C.c_int, C.c_int64, C.c_int, C.c_double,
+                                                                              po_vec, C.c_int64, C.c_double]
+        + [c_double_p] * 3 + [po_vec] * 4 + [c_double_p, po_vec, c_double_p, c_double_p]),
+    "po_mma_gcmma_group_point": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec)] * 2 + [c_double_p, C.c_int64, C.c_int,
+                                                                              C.c_int64, C.c_int, C.c_double, po_vec,
+                                                                              C.c_int64, C.c_double, po_vec, c_double_p]
+        + [po_vec] * 4 + [c_double_p, c_double_p]),
     "po_mma_get_dual_group_stats": (
         C.c_int, [po_mma, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long), c_int_p,
                   C.POINTER(C.c_long), c_double_p]),

@@ -19,6 +19,13 @@ dual alternate, then on the subproblem the last run left the grouped evaluation 
 evaluation of the same shape without groups (po_mma_dual_eval, panel form) alternate, wall time and algorithmic bytes
 per call (both calls allocate their work vectors: the same m + 1 of n; the grouped one m + 1 of w besides).  Appended
 to profiles/r12_bench_mma_groups.jsonl.
+
+--nw NW [--nwcon W] --globalization conservative: the grouped dual without and with the conservative inner loop
+(mma_gcmma_sparse_constraints = groups) alternate instead: ms per MMA iteration, raises, cap hits of the inner loop and
+of the root searches, dual evaluations per solve.  Then on the last subproblem the grouped evaluation without and with
+rho (po_mma_dual_group_eval / _rho; the rho form once with rho = 0, which is the same point and the same searches as
+the plain form, so that it prices the form alone, and once with the run's rho) alternate, and the point of a trial
+(po_mma_gcmma_group_point: the group solve and the read-only sums pass) is timed beside them.  Appended to profiles/r14_bench_mma_gcmma_groups.jsonl.
 """
 import argparse
 import json
@@ -117,6 +124,80 @@ def group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps):
     return lines
 
 
+def gcmma_group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps, problem):
+    """Whole runs of the grouped dual (none / conservative, alternating), then the evaluations on the last subproblem."""
+    import numpy as np
+
+    lines = []
+    mma = None
+    for rnd in range(rounds):
+        for glob in ("none", "conservative"):
+            mma = None  # (one solver's vectors at a time)
+            prob = pa.SeparableProblem(ctx, problem, n, c, 0).setWeighting(nwcon, nw, 0, 0)
+            mma = pa.MMA(prob, {"mma_subproblem_solver": "dual", "mma_dual_sparse_constraints": "groups",
+                                "mma_globalization": glob, "mma_gcmma_sparse_constraints": "groups",
+                                "mma_max_iterations": iters, "mma_l1_tol": 0.0, "mma_linfty_tol": 0.0,
+                                "write_output_frequency": 0})
+            stamps, root_caps = [], []
+            mma.setIterationCallback(lambda k: (stamps.append(time.perf_counter()),
+                                                root_caps.append(mma.getDualGroupStats()["cap_hits"])))
+            mma.optimize()
+            st, ds, gs = mma.getState(), mma.getDualStats(), mma.getGlobalizationStats()
+            its = len(stamps) - 1
+            r = dict(kind="mma_gcmma_groups", problem=problem, n=n, c=c, nwcon=nwcon, nw=nw, round=rnd,
+                     globalization=glob, mma_iterations=its,
+                     ms_per_mma_iteration=(stamps[-1] - stamps[0]) / max(1, its) * 1e3, fobj=st["fobj"],
+                     evaluations_per_solve=ds["evaluations"] / max(1, ds["solves"]), dual_stats=ds,
+                     inner_total=gs["inner_total"], inner_max=gs["inner_max"], cap_hits=gs["cap_hits"],
+                     root_search_cap_hits=sum(root_caps[1:]), rho=gs["rho"].tolist(),
+                     group_stats=mma.getDualGroupStats(), vectors=pa.live_objects()[0], GB=pa.live_objects()[1] * 1e-9)
+            lines.append(r)
+            print(json.dumps(r), flush=True)
+    # the evaluations on the subproblem of the last (conservative) run, at its multipliers and its rho; the expansion
+    # point of that subproblem is gone, the accepted point stands in for it
+    s = mma.getSubproblem()
+    lo, up = mma.getAsymptotes()
+    xk, lam = mma.getOptimizedPoint()[0], mma.getOptimizedPoint()[1]
+    rho = mma.getGlobalizationStats()["rho"]
+    pt = [pa.PVec(ctx, n) for _ in range(3)]
+    zw = pa.PVec(ctx, nwcon)
+    cvec = pa.PVec(ctx, nwcon).from_numpy(np.ones(nwcon))  # cw = 1 - sum x is linear: psi is the constraint itself
+    sub = (ctx, lo, up, s["alpha"], s["beta"], s["p0"], s["q0"], s["p"], s["q"])
+    groups = (nwcon, nw, 0, 0, -1.0, cvec, nwcon, 1000.0)
+
+    def timed(fn):
+        ctx.synchronize()
+        b0 = ctx.algorithmic_bytes()[0]
+        t0 = time.perf_counter()
+        out = fn()
+        ctx.synchronize()
+        return (time.perf_counter() - t0) * 1e3, ctx.algorithmic_bytes()[0] - b0, out
+
+    plain, rho_zero, with_rho, point = [], [], [], []
+    zero = np.zeros(c + 1)
+    for _ in range(reps + 1):  # (the first round warms up)
+        ms_p, by_p, out_p = timed(lambda: pa.mma_dual_group_eval(*sub, s["b"], lam, *groups, pt, zw))
+        ms_z, by_z, out_z = timed(lambda: pa.mma_dual_group_eval(*sub, s["b"], lam, *groups, pt, zw, xk=xk, rho=zero))
+        ms_r, by_r, out_r = timed(lambda: pa.mma_dual_group_eval(*sub, s["b"], lam, *groups, pt, zw, xk=xk, rho=rho))
+        ms_t, by_t, out_t = timed(lambda: pa.mma_gcmma_group_point(*sub, lam, *groups, xk, rho, pt, zw))
+        plain.append(ms_p)
+        rho_zero.append(ms_z)
+        with_rho.append(ms_r)
+        point.append(ms_t)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    r = dict(kind="dual_group_eval_rho", problem=problem, n=n, c=c, nwcon=nwcon, nw=nw, plain_ms=plain[1:],
+             rho_zero_ms=rho_zero[1:], rho_ms=with_rho[1:], point_ms=point[1:], plain_streams=by_p / (8.0 * n),
+             rho_streams=by_r / (8.0 * n), point_streams=by_t / (8.0 * n),
+             rho_zero_over_plain=med(rho_zero[1:]) / med(plain[1:]), predicted_by_bytes=by_z / by_p,
+             spread_plain=(max(plain[1:]) - min(plain[1:])) / min(plain[1:]),
+             spread_rho_zero=(max(rho_zero[1:]) - min(rho_zero[1:])) / min(rho_zero[1:]),
+             same_point=bool(out_z[3] == out_p[3] and out_z[0] == out_p[0]),
+             plain_stats=out_p[3], rho_stats=out_r[3], point_stats=out_t[1])
+    lines.append(r)
+    print(json.dumps(r), flush=True)
+    return lines
+
+
 def small_run_lines(pa, ctx, n, c, iters, problem):
     """Whole runs to the stop test with and without the conservative inner loop."""
     lines = []
@@ -178,7 +259,8 @@ def main():
     if a.mma_iters is None:
         a.mma_iters = 120 if a.small else 4
     if a.out is None and a.nw > 0:
-        a.out = os.path.join(ROOT, "profiles", "r12_bench_mma_groups.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "r14_bench_mma_gcmma_groups.jsonl" if a.globalization == "conservative"
+                             else "r12_bench_mma_groups.jsonl")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "r10_bench_gcmma.jsonl" if a.globalization == "conservative"
                              else "r09_bench_mma.jsonl")
@@ -188,6 +270,10 @@ def main():
     lines = []
     for shape in a.shapes.split(","):
         n, c = (int(v) for v in shape.split("x"))
+        if a.nw > 0 and a.globalization == "conservative":
+            lines += gcmma_group_lines(pa, ctx, n, c, a.nwcon or n // a.nw, a.nw, a.mma_iters, a.rounds, a.reps,
+                                       a.problem)
+            continue
         if a.nw > 0:
             lines += group_lines(pa, ctx, n, c, a.nwcon or n // a.nw, a.nw, a.mma_iters, a.rounds, a.reps)
             continue
