@@ -86,6 +86,19 @@ extern "C" int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, c
     std::vector<double> coef(kMaxPanel, 1e-3), coef2(kMaxPanel, 2e-3), out(kMaxPanel + 16, 0.0);
     std::vector<double> W((size_t)(m + 1) * (m + 1), 0.0);
     Timer T{cx, "", reps};
+    // the operands of the solve passes and the residual pass as the rows below vary them
+    const KktResArgs res{.b = b, .g = g->d, .A = P.data(), .z = coef.data(), .nc = c, .beta_mu = 1e-3, .n = n,
+                         .rx = t2->d, .out = out.data()};
+    const Solve2DotsArgs sd{.b = b, .t = t->d, .dinv = dinv->d, .alpha = coef.data(), .coef2 = coef2.data(),
+                            .P = P.data(), .nv = m, .beta_mu = 1e-3, .tau = 0.95, .rx = rx->d, .diag = 1.0, .n = n,
+                            .px = px->d, .pzl = pzl->d, .pzu = pzu->d, .tout = t2->d, .va = va->d, .nca = c,
+                            .out = out.data()};
+    const Solve2rArgs sr{.b = b, .t1 = t->d, .t2 = t2->d, .dinv = dinv->d, .a1 = coef.data(), .a2 = coef2.data(),
+                         .P = P.data(), .nv = m, .beta_mu = 1e-3, .tau = 0.95, .n = n, .px = px->d, .pzl = pzl->d,
+                         .pzu = pzu->d, .va = va->d, .nca = c, .out = out.data()};
+    const Solve2Args s2{.b = b, .t = t->d, .dinv = dinv->d, .alpha = coef.data(), .P = P.data(), .nv = m,
+                        .beta_mu = 1e-3, .refine = 0, .tau = 0.95, .n = n, .px = px->d, .pzl = pzl->d, .pzu = pzu->d,
+                        .out = out.data(), .rx = rx->d, .diag = 1.0, .tout = t2->d, .va = va->d, .nca = c};
     auto seq = [&]() -> int {
       std::vector<const double *> Pt(P);
       Pt.push_back(t->d);
@@ -120,41 +133,47 @@ extern "C" int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, c
           }));
       }
       PO_TRY(T.run("kkt_res", 8.0 * (c + 8) * N, 0.0,
-                   [&] { return k_kkt_res(cx, b, g->d, P.data(), coef.data(), c, 1e-3, n, t2->d, out.data()); }));
+                   [&] { return k_kkt_res(cx, res); }));
       PO_TRY(T.run("dinv", 8.0 * 6 * N, 0.0, [&] { return k_dinv(cx, b, 1.0, n, t2->d); }));
       PO_TRY(T.run("d1", 8.0 * 8 * N, 0.0, [&] { return k_d1(cx, b, rx->d, dinv->d, 1e-3, n, t2->d); }));
-      PO_TRY(T.run("solve2_dots", 8.0 * (m + 13) * N, 0.0, [&] {
-        return k_solve2_dots(cx, b, t->d, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, rx->d, 1.0, n,
-                             px->d, pzl->d, pzu->d, t2->d, va->d, c, out.data());
-      }));
+      PO_TRY(T.run("solve2_dots", 8.0 * (m + 13) * N, 0.0, [&] { return k_solve2_dots(cx, sd); }));
       PO_TRY(T.run("solve2_dots(step not stored)", 8.0 * (m + 9) * N, 0.0, [&] {
-        return k_solve2_dots(cx, b, t->d, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, rx->d, 1.0, n,
-                             px->d, pzl->d, pzu->d, t2->d, va->d, c, out.data(), nullptr, 0);
+        Solve2DotsArgs a = sd;
+        a.store_step = 0;
+        return k_solve2_dots(cx, a);
       }));
-      PO_TRY(T.run("solve2r(refine, first step recomputed)", 8.0 * (m + 12) * N, 0.0, [&] {
-        return k_solve2r(cx, b, t->d, t2->d, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, n, px->d,
-                         pzl->d, pzu->d, va->d, c, out.data());
-      }));
+      PO_TRY(T.run("solve2r(refine, first step recomputed)", 8.0 * (m + 12) * N, 0.0,
+                   [&] { return k_solve2r(cx, sr); }));
       PO_TRY(T.run("solve2_dots(nothing stored)", 8.0 * (m + 8) * N, 0.0, [&] {
-        return k_solve2_dots(cx, b, t->d, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, rx->d, 1.0, n,
-                             px->d, pzl->d, pzu->d, nullptr, va->d, c, out.data(), nullptr, 0);
+        Solve2DotsArgs a = sd;
+        a.tout = nullptr;
+        a.store_step = 0;
+        return k_solve2_dots(cx, a);
       }));
       PO_TRY(T.run("solve2r(refine, step and rhs recomputed)", 8.0 * (m + 12) * N, 0.0, [&] {
-        return k_solve2r(cx, b, t->d, nullptr, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, n, px->d,
-                         pzl->d, pzu->d, va->d, c, out.data(), coef2.data(), rx->d, 1.0);
+        Solve2rArgs a = sr;
+        a.t2 = nullptr;
+        a.ar = coef2.data();
+        a.rx = rx->d;
+        a.diag = 1.0;
+        return k_solve2r(cx, a);
       }));
       PO_TRY(T.run("solve2r(refine, recomputed, + merit sums)", 8.0 * (m + 13) * N, 0.0, [&] {
-        return k_solve2r(cx, b, t->d, nullptr, dinv->d, coef.data(), coef2.data(), P.data(), m, 1e-3, 0.95, n, px->d,
-                         pzl->d, pzu->d, va->d, c, out.data(), coef2.data(), rx->d, 1.0, 0, g->d, out.data());
+        Solve2rArgs a = sr;
+        a.t2 = nullptr;
+        a.ar = coef2.data();
+        a.rx = rx->d;
+        a.diag = 1.0;
+        a.g = g->d;
+        a.merit_out = out.data();
+        return k_solve2r(cx, a);
       }));
       PO_TRY(T.run("solve2(refine)", 8.0 * (m + 14) * N, 0.0, [&] {
-        return k_solve2(cx, b, t->d, dinv->d, coef.data(), P.data(), m, 1e-3, 1, 0.95, n, px->d, pzl->d, pzu->d,
-                        out.data(), nullptr, rx->d, 1.0, t2->d, va->d, c);
+        Solve2Args a = s2;
+        a.refine = 1;
+        return k_solve2(cx, a);
       }));
-      PO_TRY(T.run("solve2(first)", 8.0 * (m + 11) * N, 0.0, [&] {
-        return k_solve2(cx, b, t->d, dinv->d, coef.data(), P.data(), m, 1e-3, 0, 0.95, n, px->d, pzl->d, pzu->d,
-                        out.data(), nullptr, rx->d, 1.0, t2->d, va->d, c);
-      }));
+      PO_TRY(T.run("solve2(first)", 8.0 * (m + 11) * N, 0.0, [&] { return k_solve2(cx, s2); }));
       // round 6: the predictor-corrector's corrector right-hand side and solve, each as ONE pass (panels of <= 15
       // columns: the first min(m, 15) columns here), beside the kernels they replace (corrector + d1 + mdot: rows
       // above / below; solve2(first) + comp_merit)
@@ -167,8 +186,9 @@ extern "C" int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, c
             return k_corr_d1_dots(cx, b, px->d, pzl->d, pzu->d, rx->d, dinv->d, 1e-3, P.data(), mc, n, t2->d, out.data());
           }));
           PO_TRY(T.run("solve2c(min(c+k,15) columns)", 8.0 * (mc + 15) * N, 0.0, [&] {
-            return k_solve2c(cx, b, t->d, dinv->d, coef.data(), P.data(), mc, 1e-3, 0.95, n, px->d, pzl->d, pzu->d, va->d,
-                             c < mc ? c : mc, g->d, 1, out.data());
+            return k_solve2c(cx, {.b = b, .t = t->d, .dinv = dinv->d, .alpha = coef.data(), .P = P.data(), .nv = mc,
+                                  .beta_mu = 1e-3, .tau = 0.95, .n = n, .px = px->d, .pzl = pzl->d, .pzu = pzu->d,
+                                  .va = va->d, .nca = c < mc ? c : mc, .g = g->d, .want_logs = 1, .out = out.data()});
           }));
           (void)k_fill_hash(cx, px->d, n, 7, 10, 0, 2.0, -1.0);  // (the solve overwrote the step: restore the inputs)
           (void)k_fill_hash(cx, pzl->d, n, 7, 11, 0, 2.0, -1.0);
@@ -176,9 +196,10 @@ extern "C" int po_bench_kernels(po_ctx ctx, int64_t n, int c, int k, int reps, c
         }
       }
       PO_TRY(T.run("kkt_res_update(+ Dinv, t of the next solve)", 8.0 * (c + 13) * N, 0.0, [&] {
-        return k_kkt_res_update(cx, b, g->d, P.data(), coef.data(), c, 1e-3, n, t2->d, out.data(), nullptr, zl->d, pzl->d,
-                                zu->d, pzu->d, 0.0, 1e-14, nullptr, 0.0, nullptr, 0.0, nullptr, nullptr, 0.0, -1.0,
-                                nullptr, 0.0, yq->d, xt->d, 1.0, 1e-3);
+        KktResArgs a = res;
+        a.update = {.zl = zl->d, .pzl = pzl->d, .zu = zu->d, .pzu = pzu->d, .eps = 1e-14, .dinv_out = yq->d,
+                    .t_out = xt->d, .spec_diag = 1.0, .spec_beta_mu = 1e-3};
+        return k_kkt_res_update(cx, a);
       }));
       PO_TRY(T.run("comp_merit", 8.0 * 9 * N, 0.0, [&] {
         return k_comp_merit(cx, b, px->d, pzl->d, pzu->d, 0.5, 0.5, g->d, n, out.data());

@@ -381,31 +381,58 @@ struct Bounds {  // the per-element data every bound-aware kernel needs
 };
 // n-sized streams of lb / ub a bound-aware kernel does not read (count_bytes)
 inline int uniform_bound_streams(const Bounds &b) { return (b.lb_uni ? 1 : 0) + (b.ub_uni ? 1 : 0); }
+// The reduction results of the design-sized passes below come as plain structs, one field per slot of the kernel's
+// output: the launcher takes as_array(), the caller reads the fields.
+struct ResidualSums {  // k_kkt_res / k_kkt_res_update / k_res_norms
+  double comp_prod = 0, comp_count = 0, l1_rx = 0, l1_rzl = 0, l1_rzu = 0, l2_rx = 0, l2_rzl = 0, l2_rzu = 0;
+  double max_rx = 0, max_rzl = 0, max_rzu = 0;
+  double spec_max_rzl = 0, spec_max_rzu = 0;  // max|rzl|, max|rzu| for the second barrier term (beta_mu2 >= 0)
+  double *as_array() { return &comp_prod; }
+};
+static_assert(sizeof(ResidualSums) == 13 * sizeof(double), "k_kkt_res writes 13 slots");
 // rx = [L]zl - [U]zu - g + sum z_j A_j ; out = {comp product, active-bound count, l1 rx, l1 rzl,
 // l1 rzu, l2^2 rx, l2^2 rzl, l2^2 rzu, max|rx|, max|rzl|, max|rzu|} with
 // rzl = -((x-lb) zl - beta*mu), rzu = -((ub-x) zu - beta*mu).
 // (computeKKTRes :1337-1446 + computeComp :2742-2820 + computeResNorm :1588-1723)
-// yqn != nullptr: the same pass also completes the quasi-Newton gradient difference, yqn += [lo]zl - [up]zu - rx
-// beta_mu2 >= 0: out has 13 entries, the last two are max|rzl|, max|rzu| for that second barrier term
-// gcol != nullptr: one more column with coefficient gcoef behind the nc columns of A
-int k_kkt_res(Ctx *c, const Bounds &b, const double *g, const double *const *A, const double *z,
-              int nc, double beta_mu, int64_t n, double *rx, double *out, double *yqn = nullptr,
-              double beta_mu2 = -1.0, const GroupCol *gcol = nullptr, double gcoef = 0.0);
-// k_update_mult_yqn + k_kkt_res(..., yqn) in one pass (see kernels.hip): the bound multipliers take their step
-// zl <- max(zl + a pzl, eps) here, y_qn gets both brackets, rx / out are those of the new point
-int k_kkt_res_update(Ctx *c, const Bounds &b, const double *g, const double *const *A, const double *z, int nc,
-                     double beta_mu, int64_t n, double *rx, double *out, double *yqn, double *zl,
-                     const double *pzl, double *zu, const double *pzu, double a, double eps, const double *va,
-                     double az, double *acz, double az_acz,
-                     // lean step (pxs != nullptr): pzl / pzu are not read but formed from the design step pxs, the
-                     // old point xold and the old multipliers with the barrier term of the step's solve
-                     const double *pxs = nullptr, const double *xold = nullptr, double beta_mu_step = 0.0,
-                     double beta_mu2 = -1.0,  // as k_kkt_res
-                     const GroupCol *gcol = nullptr, double gcoef = 0.0,  // as k_kkt_res
-                     // dinv_out != nullptr: also Dinv (diagonal spec_diag) and t = Dinv o d1 (spec_beta_mu) of the new
-                     // point, as k_dinv_d1 would form them from what this pass has just stored
-                     double *dinv_out = nullptr, double *t_out = nullptr, double spec_diag = 0.0,
-                     double spec_beta_mu = 0.0);
+// k_kkt_res_update is k_update_mult_yqn + k_kkt_res(..., yqn) in one pass (see kernels.hip): the bound multipliers take
+// their step zl <- max(zl + a pzl, eps) there, y_qn gets both brackets, rx / out are those of the new point.
+struct KktResArgs {
+  Bounds b;
+  const double *g = nullptr;
+  const double *const *A = nullptr;  // nc constraint gradients with coefficients z
+  const double *z = nullptr;
+  int nc = 0;
+  double beta_mu = 0.0;
+  int64_t n = 0;
+  double *rx = nullptr;
+  double *out = nullptr;
+  double *yqn = nullptr;       // != nullptr: the same pass completes the quasi-Newton gradient difference,
+                               // yqn += [lo]zl - [up]zu - rx
+  double beta_mu2 = -1.0;      // >= 0: out has 13 entries, the last two are max|rzl|, max|rzu| for that second barrier term
+  const GroupCol *gcol = nullptr;  // != nullptr: one more column with coefficient gcoef behind the nc columns of A
+  double gcoef = 0.0;
+  struct Update {  // the multiplier step: read by k_kkt_res_update only
+    double *zl = nullptr;
+    const double *pzl = nullptr;
+    double *zu = nullptr;
+    const double *pzu = nullptr;
+    double a = 0.0, eps = 0.0;
+    const double *va = nullptr;
+    double az = 0.0;
+    double *acz = nullptr;
+    double az_acz = 0.0;
+    // lean step (pxs != nullptr): pzl / pzu are not read but formed from the design step pxs, the old point xold and
+    // the old multipliers with the barrier term of the step's solve
+    const double *pxs = nullptr, *xold = nullptr;
+    double beta_mu_step = 0.0;
+    // dinv_out != nullptr: also Dinv (diagonal spec_diag) and t = Dinv o d1 (spec_beta_mu) of the new point, as
+    // k_dinv_d1 would form them from what this pass has just stored
+    double *dinv_out = nullptr, *t_out = nullptr;
+    double spec_diag = 0.0, spec_beta_mu = 0.0;
+  } update;
+};
+int k_kkt_res(Ctx *c, const KktResArgs &o);
+int k_kkt_res_update(Ctx *c, const KktResArgs &o);
 // the mu-dependent part only (when the barrier parameter changes): out = {comp product,
 // count, max|rzl|, max|rzu|}
 int k_res_norms(Ctx *c, const Bounds &b, double beta_mu, int64_t n, double out[11]);
@@ -434,55 +461,127 @@ constexpr int kCorrDotsMax = 15;
 int k_corr_d1_dots(Ctx *c, const Bounds &b, const double *px, const double *pzl, const double *pzu, const double *rx,
                    const double *dinv, double beta_mu, const double *const *V, int nv, int64_t n, double *t,
                    double *out);
+struct CorrectorSums {  // k_solve2c: complementarity polynomial, merit pieces, log-barrier sums of the iterate
+  double S10 = 0, S01 = 0, S11 = 0, ppos = 0, pneg = 0, gpx = 0, pxpx = 0, pos_log = 0, neg_log = 0;
+  double max_x = 0, max_z = 0;  // fraction-to-boundary minima
+  double px_amax = 0;           // max|px|
+  double *as_array() { return &S10; }
+};
+static_assert(sizeof(CorrectorSums) == 12 * sizeof(double), "k_solve2c writes 12 slots");
 // ... and the corrector solve that follows: k_solve2 (first solve, corrector terms re-formed from the affine step in
 // (px, pzl, pzu), which it overwrites) + the sums of k_comp_merit in polynomial form.
-// out[12] = {S10, S01, S11, ppos, pneg, g.px, px.px, pos log, neg log | max_x, max_z | max|px|}
-int k_solve2c(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-              const double *const *P, int nv, double beta_mu, double tau, int64_t n, double *px, double *pzl,
-              double *pzu, double *va, int nca, const double *g, int want_logs, double out[12]);
+struct Solve2cArgs {
+  Bounds b;
+  const double *t = nullptr, *dinv = nullptr;
+  const double *alpha = nullptr;  // nv coefficients of the panel P
+  const double *const *P = nullptr;
+  int nv = 0;
+  double beta_mu = 0.0, tau = 0.0;
+  int64_t n = 0;
+  double *px = nullptr, *pzl = nullptr, *pzu = nullptr;  // in: the affine step; out: the corrector step
+  double *va = nullptr;  // != nullptr: A^T pz over the first nca columns of P
+  int nca = 0;
+  const double *g = nullptr;
+  int want_logs = 0;  // != 0: the log-barrier sums of the iterate land in out[7], out[8]
+  // out[12] = {S10, S01, S11, ppos, pneg, g.px, px.px, pos log, neg log | max_x, max_z | max|px|}
+  double *out = nullptr;
+};
+int k_solve2c(Ctx *c, const Solve2cArgs &o);
 // Second half of the bordered solve.  acc = sum_j alpha_j P_j ; dx = t + Dinv*acc.
 //   first solve  (refine == 0): px = dx; pzl = [L](rzl - zl dx)/(x-lb); pzu = [U](rzu + zu dx)/(ub-x)
 //   refinement   (refine == 1): r'zl = rzl - [L]((x-lb) pzl + px zl), r'zu likewise;
 //                               px += dx; pzl += [L](r'zl - zl dx)/(x-lb); pzu += ...
-// out = {max_x, max_z}: the fraction-to-boundary minima of computeMaxStep :2942-3103 for the
-// final (px, pzl, pzu) with fraction tau (NOT masked by the bound predicates for px, as in the
-// reference).
-// When coef2 != nullptr (first pass only) the same panel pass also evaluates the refinement
-// residual with coefficient set coef2 and writes t' = Dinv*d1' (see k_res_step) to tout (which may
-// alias t): one panel pass less per iteration.
-int k_solve2(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-             const double *const *P, int nv, double beta_mu, int refine, double tau, int64_t n,
-             double *px, double *pzl, double *pzu, double out[2], const double *coef2 = nullptr,
-             const double *rx = nullptr, double diag = 0.0, double *tout = nullptr,
-             double *va = nullptr, int nca = 0, const double *cl = nullptr,
-             const double *cu = nullptr);
-// first solve pass + refinement residual + its panel dots in ONE pass: out = {P^T t' [nv], max_x, max_z}.
-// traw != nullptr: the RAW right-hand side d1' is stored there instead of t' = Dinv o d1' in tout (the sparse-constraint
-// path applies its block solve to d1'); the dots are those of t' either way.
-int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-                  const double *coef2, const double *const *P, int nv, double beta_mu, double tau,
-                  const double *rx, double diag, int64_t n, double *px, double *pzl, double *pzu,
-                  double *tout, double *va, int nca, double *out, double *traw = nullptr,
-                  int store_step = 1,  // 0: nothing of the step, 1: px, pzl, pzu (and va), 2: px only
-                  int ca0 = 0,  // the nca constraint columns are P[ca0 .. ca0 + nca)
-                  double dinv_diag = 0.0,  // t == nullptr: Dinv (this diagonal) and t re-formed from the bound data and rx
-                  // grouped columns behind P (panel positions nv, nv + 1): they enter the two row sums with (ca, cb);
-                  // no panel dots are taken for them (out keeps its layout {dots[nv], max_x, max_z})
-                  const GroupCols2 *gcols = nullptr);
+struct Solve2Args {
+  Bounds b;
+  const double *t = nullptr, *dinv = nullptr;
+  const double *alpha = nullptr;  // nv coefficients of the panel P (a panel wider than kMaxPanel is collapsed first)
+  const double *const *P = nullptr;
+  int nv = 0;
+  double beta_mu = 0.0;
+  int refine = 0;  // 0: first solve, 1: refinement on top of the stored step
+  double tau = 0.0;
+  int64_t n = 0;
+  double *px = nullptr, *pzl = nullptr, *pzu = nullptr;
+  // out = {max_x, max_z}: the fraction-to-boundary minima of computeMaxStep :2942-3103 for the final (px, pzl, pzu)
+  // with fraction tau (NOT masked by the bound predicates for px, as in the reference)
+  double *out = nullptr;
+  // coef2 != nullptr (first solve only): the same panel pass also evaluates the refinement residual with coefficient
+  // set coef2 (rx, diag) and writes t' = Dinv*d1' (see k_res_step) to tout, which may alias t: one panel pass less
+  const double *coef2 = nullptr, *rx = nullptr;
+  double diag = 0.0;
+  double *tout = nullptr;
+  double *va = nullptr;  // != nullptr: A^T pz over the first nca columns of P
+  int nca = 0;
+  const double *cl = nullptr, *cu = nullptr;  // != nullptr: stored Mehrotra corrector products (k_corrector)
+};
+int k_solve2(Ctx *c, const Solve2Args &o);
+// first solve pass + refinement residual + its panel dots in ONE pass
+struct Solve2DotsArgs {
+  Bounds b;
+  const double *t = nullptr;  // nullptr: Dinv (diagonal dinv_diag) and t re-formed from the bound data and rx
+  const double *dinv = nullptr;
+  const double *alpha = nullptr, *coef2 = nullptr;  // coefficients of the step and of the refinement residual
+  const double *const *P = nullptr;
+  int nv = 0;
+  double beta_mu = 0.0, tau = 0.0;
+  const double *rx = nullptr;
+  double diag = 0.0;
+  int64_t n = 0;
+  double *px = nullptr, *pzl = nullptr, *pzu = nullptr;
+  double *tout = nullptr;  // t' = Dinv o d1' (nullptr: not stored)
+  double *va = nullptr;
+  int nca = 0;
+  double *out = nullptr;  // {P^T t' [nv], max_x, max_z}
+  // != nullptr: the RAW right-hand side d1' is stored there instead of t' in tout (the sparse-constraint path applies
+  // its block solve to d1'); the dots are those of t' either way
+  double *traw = nullptr;
+  int store_step = 1;      // 0: nothing of the step, 1: px, pzl, pzu (and va), 2: px only
+  int ca0 = 0;             // the nca constraint columns are P[ca0 .. ca0 + nca)
+  double dinv_diag = 0.0;  // the diagonal of the t == nullptr form
+  // grouped columns behind P (panel positions nv, nv + 1): they enter the two row sums with (ca, cb); no panel dots
+  // are taken for them (out keeps its layout)
+  const GroupCols2 *gcols = nullptr;
+};
+int k_solve2_dots(Ctx *c, const Solve2DotsArgs &o);
+struct FusedMeritSums {  // k_solve2r with g: the complementarity polynomial and merit pieces of the final step
+  double S10 = 0, S01 = 0, S11 = 0, ppos = 0, pneg = 0, gpx = 0, pxpx = 0;
+  double max_x = 0, max_z = 0;
+  double px_amax = 0;
+  double *as_array() { return &S10; }
+};
+static_assert(sizeof(FusedMeritSums) == 10 * sizeof(double), "k_solve2r writes 10 slots");
 // store_step == 0 above leaves (px, pzl, pzu, va) unwritten; this refinement pass recomputes that first step from
-// (t1, a1) and applies the refinement (t2, a2) on top in ONE sweep over P: out = {max_x, max_z} of the final step
-int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const double *dinv, const double *a1,
-              const double *a2, const double *const *P, int nv, double beta_mu, double tau, int64_t n, double *px,
-              double *pzl, double *pzu, double *va, int nca, double out[2], const double *ar = nullptr,
-              const double *rx = nullptr, double diag = 0.0,  // t2 == nullptr: t2 recomputed from (ar, rx, diag)
-              int ca0 = 0,  // the nca constraint columns are P[ca0 .. ca0 + nca)
-              // g != nullptr (recomputed right-hand side form only): merit_out[10] = {S10, S01, S11, ppos, pneg, g.px,
-              // px.px | max_x, max_z | max|px|} of the final step (see solve2r_kernel) instead of `out`
-              const double *g = nullptr, double *merit_out = nullptr,
-              // t1 == nullptr: Dinv (diagonal dinv_diag) and t1 re-formed from the bound data and rx in registers
-              double dinv_diag = 0.0,
-              // stored right-hand side form: one more column behind P with coefficients gc1 / gc2 in the two sets
-              const GroupCol *gcol = nullptr, double gc1 = 0.0, double gc2 = 0.0);
+// (t1, a1) and applies the refinement (t2, a2) on top in ONE sweep over P
+struct Solve2rArgs {
+  Bounds b;
+  const double *t1 = nullptr;  // nullptr: Dinv (diagonal dinv_diag) and t1 re-formed from the bound data and rx in
+                               // registers (recomputed right-hand side form only)
+  const double *t2 = nullptr;  // nullptr: the recomputed right-hand side form, t2 from (ar, rx, diag);
+                               // otherwise the stored right-hand side form
+  const double *dinv = nullptr;
+  const double *a1 = nullptr, *a2 = nullptr;
+  const double *const *P = nullptr;
+  int nv = 0;
+  double beta_mu = 0.0, tau = 0.0;
+  int64_t n = 0;
+  double *px = nullptr;
+  double *pzl = nullptr, *pzu = nullptr;  // nullptr: lean step, the bound-multiplier steps stay in registers
+  double *va = nullptr;
+  int nca = 0;
+  double *out = nullptr;  // {max_x, max_z} of the final step
+  const double *ar = nullptr, *rx = nullptr;  // refinement-residual coefficients and rx of the t2 == nullptr form
+  double diag = 0.0;
+  int ca0 = 0;  // the nca constraint columns are P[ca0 .. ca0 + nca)
+  // g != nullptr with merit_out: merit_out[10] = {S10, S01, S11, ppos, pneg, g.px, px.px | max_x, max_z | max|px|} of
+  // the final step (see solve2r_kernel) instead of `out`
+  const double *g = nullptr;
+  double *merit_out = nullptr;
+  double dinv_diag = 0.0;  // the diagonal of the t1 == nullptr form
+  // stored right-hand side form: one more column behind P with coefficients gc1 / gc2 in the two sets
+  const GroupCol *gcol = nullptr;
+  double gc1 = 0.0, gc2 = 0.0;
+};
+int k_solve2r(Ctx *c, const Solve2rArgs &o);
 // (pzl, pzu) of a lean step as vectors: [L] (rzl - zl px) / (x - lb), [U] (rzu + zu px) / (ub - x)
 int k_form_pz(Ctx *c, const Bounds &b, const double *px, double beta_mu, int64_t n, double *pzl, double *pzu);
 // multiplier update fused with y_qn = rx - [lo]zl_old + [up]zu_old + az*va (see kernels.hip)
@@ -507,6 +606,13 @@ int k_comp_step(Ctx *c, const Bounds &b, const double *px, const double *pzl, co
 // ppos, pneg, g.px, px.px, max|px|}
 int k_comp_merit(Ctx *c, const Bounds &b, const double *px, const double *pzl, const double *pzu, double ax,
                  double az, const double *g, int64_t n, double out[9]);
+struct MeritSums {  // the merit pieces of a step: slots 2..8 of k_comp_merit's output
+  double pos_log, neg_log, ppos, pneg, gpx, pxpx, px_amax;
+  static MeritSums fromCompMerit(const double out[9]) {
+    return {out[2], out[3], out[4], out[5], out[6], out[7], out[8]};
+  }
+};
+static_assert(sizeof(MeritSums) == 7 * sizeof(double), "k_comp_merit yields 7 merit slots");
 // evalMeritInitDeriv :3652-3714 barrier part + the three design-space inner products:
 // out = {pos log, neg log, pos presult, neg presult, g.px, px.px}; px is scaled by sx.
 int k_merit0(Ctx *c, const Bounds &b, const double *px, double sx, const double *g, int64_t n,

@@ -35,7 +35,7 @@ InteriorPoint::InteriorPoint(Problem *p)
       iter_cb(nullptr),
       iter_cb_user(nullptr), px(nullptr), pzl(nullptr), pzu(nullptr), Dinv(nullptr), rx(nullptr),
       tvec(nullptr), xt(nullptr), y_qn(nullptr), s_qn(nullptr), vA(nullptr), qn_created(false), qn_owned(true),
-      comp_prod(0), comp_count(0), max_rx(0), max_rzl(0), max_rzu(0), sx(1.0), sz(1.0),
+      comp_prod(0), comp_count(0), max_rx(0), max_rzl(0), max_rzu(0),
       corrector_active(false), norm_type(0), phase_t0(0) {
   qn_handle.qn = nullptr;
   hdiag = nullptr;
@@ -460,7 +460,7 @@ double InteriorPoint::nextMonotoneMu() const {
 
 int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, const MultUpdate *upd) {
   const double beta_mu = options.real("rel_bound_barrier") * mu;
-  double *out = res_out;  // a member: inside a BatchScope the values arrive at the flush (after_reduce below)
+  double *out = res_out.as_array();  // a member: inside a BatchScope the values arrive at the flush (after_reduce below)
   // speculative maxima for the next barrier parameter (see ip.hpp): only beside the norms of the CURRENT one
   const bool spec = vectors && spec_enabled && !has_w && mu == barrier_param;
   const double mu2 = spec ? nextMonotoneMu() : 0.0;
@@ -504,6 +504,10 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
       A.push_back(tvec->d);
       zc.push_back(1.0);
     }
+    const KktResArgs ra{.b = bounds(), .g = g->d, .A = A.data(), .z = zc.data(), .nc = (int)A.size(),
+                        .beta_mu = beta_mu, .n = n, .rx = rx->d, .out = out,
+                        .yqn = yqn_complete ? yqn_complete->d : nullptr, .beta_mu2 = beta_mu2,
+                        .gcol = have_gcol ? &gcol : nullptr, .gcoef = 1.0};
     if (upd) {
       // the bound multipliers take their step in the same pass (see kkt_res_update_kernel); A^T z follows the dense
       // multiplier step by recurrence unless it has just been rebuilt from the new multipliers
@@ -517,46 +521,47 @@ int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, c
       const double sdiag = spec_dt ? options.real("qn_sigma") + ((qn && !options.integer("sequential_linear_method"))
                                                                     ? qn->diag() : 0.0) : 0.0;
       const double sbmu = spec_dt ? options.real("rel_bound_barrier") * spec_dt_mu : 0.0;
-      PO_TRY(k_kkt_res_update(ctx, bounds(), g->d, A.data(), zc.data(), acz_mode ? 0 : (int)A.size(), beta_mu, n,
-                              rx->d, out, yqn_complete ? yqn_complete->d : nullptr, zl->d, pzl->d, zu->d, pzu->d,
-                              upd->a, upd->eps, (yqn_complete || az_acz != 0.0) ? vA->d : nullptr,
-                              upd->az, acz_mode ? acz->d : nullptr, az_acz, step_flags.pz_stored ? nullptr : px->d,
-                              step_flags.pz_stored ? nullptr : xt->d, step_beta_mu, beta_mu2,
-                              have_gcol ? &gcol : nullptr, 1.0,
-                              spec_dt ? Dinv->d : nullptr, spec_dt ? tvec->d : nullptr, sdiag, sbmu));
+      KktResArgs ru = ra;
+      if (acz_mode) ru.nc = 0;  // A^T z is read from acz
+      ru.update = {.zl = zl->d, .pzl = pzl->d, .zu = zu->d, .pzu = pzu->d, .a = upd->a, .eps = upd->eps,
+                   .va = (yqn_complete || az_acz != 0.0) ? vA->d : nullptr, .az = upd->az,
+                   .acz = acz_mode ? acz->d : nullptr, .az_acz = az_acz,
+                   .pxs = step_flags.pz_stored ? nullptr : px->d, .xold = step_flags.pz_stored ? nullptr : xt->d,
+                   .beta_mu_step = step_beta_mu, .dinv_out = spec_dt ? Dinv->d : nullptr,
+                   .t_out = spec_dt ? tvec->d : nullptr, .spec_diag = sdiag, .spec_beta_mu = sbmu};
+      PO_TRY(k_kkt_res_update(ctx, ru));
       if (spec_dt) {
         scratch_flags.spec_dt_valid = true;
         spec_dt_diag = sdiag;
         spec_dt_bmu = sbmu;
       }
     } else {
-      PO_TRY(k_kkt_res(ctx, bounds(), g->d, A.data(), zc.data(), (int)A.size(), beta_mu, n, rx->d, out,
-                       yqn_complete ? yqn_complete->d : nullptr, beta_mu2, have_gcol ? &gcol : nullptr, 1.0));
+      PO_TRY(k_kkt_res(ctx, ra));
     }
   } else {
     PO_TRY(k_res_norms(ctx, bounds(), beta_mu, n, out));
   }
   after_reduce(ctx, [this, vectors, spec, mu2] {
-    const double *o = res_out;
+    const ResidualSums &o = res_out;
     if (vectors) {
-      l1_rx = o[2];
-      l2_rx = o[5];
-      max_rx = o[8];
+      l1_rx = o.l1_rx;
+      l2_rx = o.l2_rx;
+      max_rx = o.max_rx;
     }
     if (spec) {
       spec_mu = mu2;
-      spec_max[0] = o[11];
-      spec_max[1] = o[12];
+      spec_max[0] = o.spec_max_rzl;
+      spec_max[1] = o.spec_max_rzu;
       iterate_flags.spec_valid = true;
     }
-    comp_prod = o[0];
-    comp_count = o[1];
-    l1_rzl = o[3];
-    l1_rzu = o[4];
-    l2_rzl = o[6];
-    l2_rzu = o[7];
-    max_rzl = o[9];
-    max_rzu = o[10];
+    comp_prod = o.comp_prod;
+    comp_count = o.comp_count;
+    l1_rzl = o.l1_rzl;
+    l1_rzu = o.l1_rzu;
+    l2_rzl = o.l2_rzl;
+    l2_rzu = o.l2_rzu;
+    max_rzl = o.max_rzl;
+    max_rzu = o.max_rzu;
   });
   // (inside computeStepAndUpdate's batch the norms arrive with the quasi-Newton products: everything above that reads
   // them runs through after_reduce)
@@ -647,73 +652,90 @@ int InteriorPoint::getComplementarity(double *comp) {
 // ================================================================================================
 // the KKT system
 // ================================================================================================
+// Step 1 of setUpKKTSystem: Dinv for the diagonal `diag` (+ h_i with use_hdiag, :1840-1842) and, where the right-hand
+// side of the solve that follows is known already (rx, the bounds and *rhs_mu), its vector out of the same pass over
+// the bound data.  kz: quasi-Newton columns of the panel.  Sets t_is_plain_dinv_d1 (with t0_diag), consumes spec_dt_valid.
+int InteriorPoint::formDinvAndRhs(double diag, bool use_hdiag, const double *rhs_mu, int kz, RhsFormed *formed) {
+  const double *h = use_hdiag ? hdiag->d : nullptr;
+  const double bmu = rhs_mu ? options.real("rel_bound_barrier") * (*rhs_mu) : 0.0;
+  // dense constraints: t = Dinv o d1 rides through the Gram pass as one more, pre-weighted, column, so that P^T t -- the
+  // mdot pass at the head of solveKKT -- comes out of the pass over P that the Schur complements need anyway
+  const bool want_t = rhs_mu && !has_w && c + kz > 0;
+  // sparse constraints: the block solve applies to the RAW right-hand side d1 (used when the fused first solve is taken)
+  const bool want_raw_d1 = has_w && rhs_mu && !corrector_active;
+  const bool have_spec_dt = scratch_flags.spec_dt_valid;
+  scratch_flags.spec_dt_valid = false;  // consumed here, or overwritten below
+  scratch_flags.t_is_plain_dinv_d1 = false;
+  *formed = RHS_NONE;
+  if (want_t) {
+    // (the residual pass of this iterate may have left exactly this Dinv and t behind: kkt_res_update_kernel)
+    const bool left_behind = have_spec_dt && !use_hdiag && spec_dt_diag == diag && spec_dt_bmu == bmu;
+    if (!left_behind) PO_TRY(k_dinv_d1(ctx, bounds(), diag, h, rx->d, bmu, n, Dinv->d, tvec->d));
+    scratch_flags.t_is_plain_dinv_d1 = !use_hdiag;
+    t0_diag = diag;
+    *formed = RHS_T;
+  } else if (want_raw_d1) {
+    PO_TRY(k_dinv_d1(ctx, bounds(), diag, h, rx->d, bmu, n, Dinv->d, d1v->d, 1));
+    *formed = RHS_RAW_D1;
+  } else {
+    PO_TRY(k_dinv(ctx, bounds(), diag, n, Dinv->d, h));
+  }
+  return PO_OK;
+}
+
+// Step 2 of setUpKKTSystem: W = V^T Dinv V in one launch, unpacked into kkt.W (and t0dots) in the order [Ac | Z] once
+// the reduction has arrived.
+int InteriorPoint::gramPass(const GramPlan &plan, bool *groups_done) {
+  const int m = (int)plan.V.size(), mt = m + (plan.with_t ? 1 : 0), k = plan.kform;
+  const bool with_t = plan.with_t;
+  std::vector<const double *> V(plan.V);
+  if (with_t) V.push_back(tvec->d);
+  Wt_buf.assign((size_t)mt * mt, 0.0);
+  PO_TRY(k_wgram(ctx, Dinv->d, V.data(), mt, n, Wt_buf.data(), k > 0 ? plan.S.data() : nullptr,
+                 k > 0 ? plan.Zout.data() : nullptr, k, plan.b0, with_t ? 1 : 0, plan.may_defer, plan.groups,
+                 groups_done));
+  t0dots.assign(with_t ? m : 0, 0.0);
+  after_reduce(ctx, [this, m, mt, k, with_t] {
+    // index in [Ac | Z] -> index in the launch order: [Z | Ac] when the pass formed Z, the same order otherwise
+    auto at = [&](int i) { return k == 0 ? i : (i < c ? k + i : i - c); };
+    for (int j = 0; j < m; j++)
+      for (int i = 0; i < m; i++) kkt.W[i + (size_t)m * j] = Wt_buf[at(i) + (size_t)mt * at(j)];
+    for (int i = 0; with_t && i < m; i++) t0dots[i] = Wt_buf[at(i) + (size_t)mt * m];
+  });
+  return PO_OK;
+}
+
 int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs_mu) {  // setUpKKTDiagSystem + setUpKKTSystem
   if (qn) PO_TRY(refreshQuasiNewton());
   step_flags.ptpx_valid = false;
   scratch_flags.t0_valid = false;
-  const double sigma = options.real("qn_sigma");
   const bool use_hdiag = options.integer("use_diag_hessian") && hdiag;  // h_i replaces b0 (:1840-1842)
   const double b0 = (!use_hdiag && qn && (use_qn || diag_only)) ? qn->diag() : 0.0;
-  // The right-hand side of the solve that follows is known already (rx, the bounds and mu): t = Dinv o d1 is
-  // built now (in the same pass over the bound data as Dinv) and rides through the Gram pass as one more,
-  // pre-weighted, column, so that P^T t -- the mdot pass at the head of solveKKT -- comes out of the pass over P
-  // that the Schur complements need anyway.
-  const bool fuse_t = rhs_mu && !has_w && c + (qn && use_qn && !diag_only ? qn->size() : 0) > 0;
-  scratch_flags.t_is_plain_dinv_d1 = false;
-  // sparse constraints: the RAW right-hand side d1 of the first solve (the block solve applies to it) comes out of
-  // the same pass over the bound data as Dinv (round 4; it is used below when the fused first solve is taken)
-  const bool raw_d1_w = has_w && rhs_mu && !corrector_active;
-  const bool have_spec_dt = scratch_flags.spec_dt_valid;
-  scratch_flags.spec_dt_valid = false;  // consumed here, or overwritten below
-  if (fuse_t && have_spec_dt && !use_hdiag && spec_dt_diag == b0 + sigma &&
-      spec_dt_bmu == options.real("rel_bound_barrier") * (*rhs_mu)) {
-    // the residual pass of this iterate left exactly this Dinv and t behind (kkt_res_update_kernel)
-    scratch_flags.t_is_plain_dinv_d1 = true;
-    t0_diag = b0 + sigma;
-  } else if (fuse_t) {
-    PO_TRY(k_dinv_d1(ctx, bounds(), b0 + sigma, use_hdiag ? hdiag->d : nullptr, rx->d,
-                     options.real("rel_bound_barrier") * (*rhs_mu), n, Dinv->d, tvec->d));
-    scratch_flags.t_is_plain_dinv_d1 = !use_hdiag;
-    t0_diag = b0 + sigma;
-  } else if (raw_d1_w) {
-    PO_TRY(k_dinv_d1(ctx, bounds(), b0 + sigma, use_hdiag ? hdiag->d : nullptr, rx->d,
-                     options.real("rel_bound_barrier") * (*rhs_mu), n, Dinv->d, d1v->d, 1));
-  } else {
-    PO_TRY(k_dinv(ctx, bounds(), b0 + sigma, n, Dinv->d, use_hdiag ? hdiag->d : nullptr));
-  }
-  int k = 0;
-  // L-SR1 leaves its columns Z_j = Y_j - b0 S_j unformed after an update; when this Gram pass is their
-  // first consumer they are formed on the fly (and written out for the later passes): the panel is
-  // ordered [Z | Ac] for that launch and the result permuted back to [Ac | Z]
+  const bool with_z = use_qn && !diag_only;  // the low-rank part of the quasi-Newton approximation enters the panel
+  // 1. Dinv and, where it is known already, the right-hand side of the first solve
+  RhsFormed rhs = RHS_NONE;
+  PO_TRY(formDinvAndRhs(b0 + options.real("qn_sigma"), use_hdiag, rhs_mu, (qn && with_z) ? qn->size() : 0, &rhs));
+  const bool fuse_t = rhs == RHS_T, raw_d1_w = rhs == RHS_RAW_D1;
+  // The panel.  L-SR1 leaves its columns Z_j = Y_j - b0 S_j unformed after an update; when this Gram pass is their
+  // first consumer they are formed on the fly (and written out for the later passes): the launch takes [Z | Ac].
+  // Otherwise panel() forms what is unformed and the launch takes [Ac | Z].
+  GramPlan plan;
   std::vector<const double *> Yp, Sp;
   std::vector<double *> Zo;
   double b0z = 0.0;
-  const bool fuse_z = qn && use_qn && !diag_only && !has_w && qn->pendingZ(&Yp, &Sp, &Zo, &b0z) &&
-                      !Yp.empty() && Yp.size() <= 12 && c + (int)Yp.size() + (fuse_t ? 1 : 0) <= kWgramMaxVecs;
+  const bool fuse_z = qn && with_z && !has_w && qn->pendingZ(&Yp, &Sp, &Zo, &b0z) && !Yp.empty() && Yp.size() <= 12 &&
+                      c + (int)Yp.size() + (fuse_t ? 1 : 0) <= kWgramMaxVecs;
+  int k = 0;
+  std::vector<const double *> P;  // [Ac | Z] with every column formed (left empty when the Gram pass forms Z)
   if (fuse_z) {
-    k = (int)Yp.size();
-    const int m2 = c + k, mt = m2 + (fuse_t ? 1 : 0);
-    std::vector<const double *> P2(Yp);
-    for (Vec *a : Ac) P2.push_back(a->d);
-    if (fuse_t) P2.push_back(tvec->d);
-    std::vector<double> W2((size_t)mt * mt, 0.0);
-    PO_TRY(k_wgram(ctx, Dinv->d, P2.data(), mt, n, W2.data(), Sp.data(), Zo.data(), k, b0z, fuse_t ? 1 : 0));
-    qn->pendingZDone();
-    kkt.W.assign((size_t)m2 * m2, 0.0);
-    auto perm = [&](int i) { return i < c ? k + i : i - c; };  // index in [Ac | Z] -> index in [Z | Ac]
-    for (int j = 0; j < m2; j++)
-      for (int i = 0; i < m2; i++) kkt.W[i + (size_t)m2 * j] = W2[perm(i) + (size_t)mt * perm(j)];
-    if (fuse_t) {
-      t0dots.assign(m2, 0.0);
-      for (int i = 0; i < m2; i++) t0dots[i] = W2[perm(i) + (size_t)mt * m2];
-    }
-  }
-  std::vector<const double *> P;
-  if (!fuse_z) {
-    P = panel(use_qn && !diag_only, &k);  // (forms unformed columns: the plain Gram launch below reads them)
-  } else if (has_w) {
-    int k2 = 0;
-    P = panel(use_qn && !diag_only, &k2);
+    plan.kform = k = (int)Yp.size();
+    plan.V = Yp;
+    for (Vec *a : Ac) plan.V.push_back(a->d);
+    plan.S = Sp;
+    plan.Zout = Zo;
+    plan.b0 = b0z;
+  } else {
+    plan.V = P = panel(with_z, &k);  // (forms unformed columns: the Gram launch below reads them)
   }
   const int m = c + k;
   kkt.k = k;
@@ -724,7 +746,6 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // sparse constraints: the sparse residual norms of the new barrier parameter, the Gram pass and its sparse correction
   // share ONE collective + host sync (three before); the host algebra on W waits for the flush below
   BatchScope wbatch(ctx, has_w && prob->reductionsBatchable());
-  bool t0_ready = fuse_z && fuse_t;
   if (has_w) {  // Cw = 1/(sw/zsw + tw/ztw + Aw Dinv Aw^T) (:1912-1930)
     PO_TRY(prob->sparseFactorFromSlacks(x, Dinv, wv(), Cw));  // Cdiag (:1912-1927) + mat->factor (:1930)
     fuse_tw = rhs_mu && m > 0 && m + 1 <= kWgramMaxVecs && !corrector_active;
@@ -739,38 +760,21 @@ int InteriorPoint::setUpKKTSystem(bool use_qn, bool diag_only, const double *rhs
   // itself (one pass over the panel instead of two) where the problem and the kernel allow it
   GramGroups gram_groups;
   std::vector<double *> Ugs;
-  const GramGroups *ggp = nullptr;
-  bool panel_done = false;
-  if (has_w && !fuse_z && m > 0 && prob->sparseGramGroups(x, &gram_groups)) {
+  if (has_w && m > 0 && prob->sparseGramGroups(x, &gram_groups)) {
     PO_TRY(panelImageVectors(m, Ugs));
     gram_groups.ncols = m;
     gram_groups.U = Ugs.data();
-    ggp = &gram_groups;
+    plan.groups = &gram_groups;
   }
-  if (!fuse_z) {
-    kkt.W.assign((size_t)m * m, 0.0);
-    if (m > 0 && (fuse_t || fuse_tw) && m + 1 <= kWgramMaxVecs) {
-      std::vector<const double *> Pt(P);
-      Pt.push_back(tvec->d);
-      const int mt = m + 1;
-      Wt_buf.assign((size_t)mt * mt, 0.0);
-      PO_TRY(k_wgram(ctx, Dinv->d, Pt.data(), mt, n, Wt_buf.data(), nullptr, nullptr, 0, 0.0, 1, wbatch.open, ggp,
-                     &panel_done));
-      t0dots.assign(m, 0.0);
-      after_reduce(ctx, [this, m, mt] {
-        for (int j = 0; j < m; j++)
-          for (int i = 0; i < m; i++) kkt.W[i + (size_t)m * j] = Wt_buf[i + (size_t)mt * j];
-        for (int i = 0; i < m; i++) t0dots[i] = Wt_buf[i + (size_t)mt * m];
-      });
-      t0_ready = true;
-    } else {
-      if (m > 0)
-        PO_TRY(k_wgram(ctx, Dinv->d, P.data(), m, n, kkt.W.data(), nullptr, nullptr, 0, 0.0, 0, wbatch.open, ggp,
-                       &panel_done));
-      t0dots.clear();
-    }
-  }
-  if ((fuse_t || fuse_tw) && m > 0 && t0_ready && (int)t0dots.size() == m) {
+  // 2. the Gram pass; with the right-hand side t at hand, P^T t of the first solve comes out of it
+  plan.with_t = (fuse_t || fuse_tw) && m > 0 && m + 1 <= kWgramMaxVecs;
+  plan.may_defer = wbatch.open;
+  bool panel_done = false;
+  kkt.W.assign((size_t)m * m, 0.0);
+  t0dots.clear();
+  if (m > 0) PO_TRY(gramPass(plan, &panel_done));
+  if (fuse_z) qn->pendingZDone();
+  if (plan.with_t) {
     scratch_flags.t0_valid = true;
     t0_mu = *rhs_mu;
   }
@@ -848,12 +852,7 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
   if (!refine_pass) scratch_flags.first_t_recomputable = have_t0 && scratch_flags.t_is_plain_dinv_d1;
   if (!refine_pass) scratch_flags.t0_valid = false;  // tvec is overwritten by the passes below
   const bool deferred = refine_pass && step_flags.step_deferred;  // the first pass stored no step
-  stepWillChange();
-  Bordered::Sol sol;
-  kkt.solve(1.0, b, vars, dots.data(), &sol);
-  const std::vector<double> &alpha = sol.coef;
-  kkt.panelDots(dots.data(), sol, refine_pass, &ptpx);  // P^T (t + Dinv P alpha) = dots + W alpha
-  step_flags.ptpx_valid = true;
+  const Bordered::Sol sol = solveBordered(b, dots.data(), refine_pass);
   // Fused refinement residual: the coefficients of addKKTResStep (:1475-1483) are known before
   // the axpy pass starts (A-part = p.z = alpha_A; Z-part = d0 M^-1 d0 Z^T px with Z^T px = ptpx),
   // so the same pass over P also emits the right-hand side t' of the refinement solve.
@@ -865,86 +864,135 @@ int InteriorPoint::solveKKT(const Dense &b, double mu, bool use_qn, bool refine_
   step_flags.vA_valid = true;
   std::vector<double> coef(m > 0 ? m : 1, 0.0);
   double diag = options.real("qn_sigma");
-  if (fuse) PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, alpha.data(), ptpx.data() + c, k, coef, &diag));
-  const bool first_fused = fuse && m > 0 && !corr;
+  if (fuse) PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, sol.coef.data(), ptpx.data() + c, k, coef, &diag));
   need_panel();
-  if (first_fused) {
-    // one pass: t' = refinement rhs and P^T t' for the refinement solve.  The step itself (px, pzl, pzu, A^T pz) is
-    // NOT stored: the refinement pass recomputes it from (t, alpha) in registers (k_solve2r) -- four output streams
-    // less, and an HBM write costs about four reads here.  t' goes to xt (free during the solves), t stays in tvec.
-    std::vector<double> out(m + 2, 0.0);
-    const bool defer = forms.recompute_first_step;
-    // ... and with recompute_rhs not even t': the pass only takes the products P^T t', the refinement pass forms t'
-    // again from the residual coefficients (an output stream costs about four input streams)
-    double *tp_out = !defer ? tvec->d : (forms.recompute_rhs ? nullptr : xt->d);
-    // Dinv and t re-formed in the element epilogue from the bound data and rx it loads anyway (same bits)
-    const bool redo_dt1 = forms.recompute_dt && defer && forms.recompute_rhs && scratch_flags.first_t_recomputable;
-    const double *t_in = redo_dt1 ? nullptr : tvec->d;
-    PO_TRY(k_solve2_dots(ctx, bounds(), t_in, Dinv->d, alpha.data(), coef.data(), P.data(), m, beta_mu, tau, rx->d,
-                         diag, n, px->d, pzl->d, pzu->d, tp_out, vA->d, c, out.data(), nullptr, defer ? 0 : 1, 0,
-                         t0_diag));
-    tdots.assign(out.begin(), out.begin() + m);
-    step_flags.tdots_valid = true;
-    step_mins[0] = out[m];
-    step_mins[1] = out[m + 1];
-    step_flags.step_deferred = defer;
-    if (defer) {
-      alpha_first = alpha;
-      coef_first = coef;
-      diag_first = diag;
-    }
+  const SolvePass sp{P, sol.coef, m, beta_mu, tau};
+  if (fuse && m > 0 && !corr) {
+    PO_TRY(fusedFirstPass(sp, coef, diag));
   } else if (deferred) {
-    // the same sweep takes the sums the complementarity check of scaleKKTStep and the merit derivative need of the
-    // final step (see solve2r_kernel): no separate pass over the step afterwards
-    const bool take_merit = forms.fuse_merit && forms.recompute_rhs && !corr;
-    const double *gm = take_merit ? g->d : nullptr;
-    double *mo = take_merit ? fused_merit : nullptr;
-    // lean step: (pzl, pzu) stay in registers; their only consumer left, the multiplier update, re-forms them
-    const bool lean = forms.lean_step && lean_step_allowed && take_merit && iterate_flags.iterate_logs_valid;
-    double *pzl_out = lean ? nullptr : pzl->d, *pzu_out = lean ? nullptr : pzu->d;
-    // Dinv and the first right-hand side t re-formed in registers from data the pass loads anyway (same bits)
-    const bool redo_dt = forms.recompute_dt && forms.recompute_rhs && scratch_flags.first_t_recomputable;
-    const double *t1p = redo_dt ? nullptr : tvec->d;
-    if (lean) {
-      step_flags.pz_stored = false;
-      step_beta_mu = beta_mu;
-    }
-    PO_TRY(k_solve2r(ctx, bounds(), t1p, forms.recompute_rhs ? nullptr : xt->d, Dinv->d, alpha_first.data(),
-                     alpha.data(), P.data(), m, beta_mu, tau, n, px->d, pzl_out, pzu_out, vA->d, c, step_mins,
-                     coef_first.data(), rx->d, diag_first, 0, gm, mo, t0_diag));
-    if (take_merit) {
-      after_reduce(ctx, [this] {
-        step_mins[0] = fused_merit[7];
-        step_mins[1] = fused_merit[8];
-        step_flags.fused_merit_valid = true;
-      });
-    }
+    PO_TRY(recomputingRefinementPass(sp, corr));
   } else if (corr_fused) {
-    // corrector solve: the corrector terms re-formed from the affine step this pass overwrites, and the sums of
-    // scaleKKTStep / evalMeritInitDeriv of the step it has in registers (k_comp_merit and its round trip disappear)
-    const bool want_logs = !iterate_flags.iterate_logs_valid;
-    PO_TRY(k_solve2c(ctx, bounds(), tvec->d, Dinv->d, alpha.data(), P.data(), m, beta_mu, tau, n, px->d, pzl->d,
-                     pzu->d, vA->d, c, g->d, want_logs ? 1 : 0, corr_out));
-    after_reduce(ctx, [this, want_logs] {
-      for (int i = 0; i < 7; i++) fused_merit[i] = corr_out[i];
-      fused_merit[7] = step_mins[0] = corr_out[9];
-      fused_merit[8] = step_mins[1] = corr_out[10];
-      fused_merit[9] = corr_out[11];
-      if (want_logs) {  // the barrier sums of the iterate, as k_comp_merit takes them
-        iterate_logs[0] = corr_out[7];
-        iterate_logs[1] = corr_out[8];
-        iterate_flags.iterate_logs_valid = true;
-      }
-      step_flags.fused_merit_valid = true;
-    });
+    PO_TRY(correctorSolve(sp));
   } else {
-    PO_TRY(k_solve2(ctx, bounds(), tvec->d, Dinv->d, alpha.data(), P.data(), m, beta_mu,
-                    refine_pass ? 1 : 0, tau, n, px->d, pzl->d, pzu->d, step_mins,
-                    fuse ? coef.data() : nullptr, rx->d, diag, tvec->d, vA->d, c, cl, cu));
+    PO_TRY(storedStepSolve(sp, refine_pass, fuse ? coef.data() : nullptr, diag, cl, cu));
   }
   step_flags.residual_fused = fuse;
   kkt.backSubstitute(1.0, b, vars, sol, true, out);
   return PO_OK;
+}
+
+// The head of the bordered solve that solveKKT and solveKKTW share: every record of the previous step is dropped, the
+// dense algebra yields the panel coefficients (sol.coef) from dots = P^T t, and ptpx = P^T px of the step about to be
+// written follows analytically, P^T (t + Dinv P coef) = dots + W coef (step_flags.ptpx_valid).
+Bordered::Sol InteriorPoint::solveBordered(const Dense &b, const double *dots, bool refine_pass) {
+  stepWillChange();
+  Bordered::Sol sol;
+  kkt.solve(1.0, b, vars, dots, &sol);
+  kkt.panelDots(dots, sol, refine_pass, &ptpx);
+  step_flags.ptpx_valid = true;
+  return sol;
+}
+
+// Fused first pass -- taken for the first solve of a step whose refinement residual can be written as panel
+// coefficients (`fuse` in solveKKT), m > 0, no corrector.  One pass: t' = refinement rhs and P^T t' for the refinement
+// solve.  Sets tdots_valid and step_deferred (with alpha_first, coef_first, diag_first).
+int InteriorPoint::fusedFirstPass(const SolvePass &sp, const std::vector<double> &coef, double diag) {
+  const int m = sp.m;
+  // The step itself (px, pzl, pzu, A^T pz) is NOT stored: the refinement pass recomputes it from (t, alpha) in registers
+  // (k_solve2r) -- four output streams less, and an HBM write costs about four reads here.  t' goes to xt (free during
+  // the solves), t stays in tvec.
+  std::vector<double> out(m + 2, 0.0);
+  const bool defer = forms.recompute_first_step;
+  // ... and with recompute_rhs not even t': the pass only takes the products P^T t', the refinement pass forms t'
+  // again from the residual coefficients (an output stream costs about four input streams)
+  double *tp_out = !defer ? tvec->d : (forms.recompute_rhs ? nullptr : xt->d);
+  // Dinv and t re-formed in the element epilogue from the bound data and rx it loads anyway (same bits)
+  const bool redo_dt1 = forms.recompute_dt && defer && forms.recompute_rhs && scratch_flags.first_t_recomputable;
+  PO_TRY(k_solve2_dots(ctx, {.b = bounds(), .t = redo_dt1 ? nullptr : tvec->d, .dinv = Dinv->d,
+                             .alpha = sp.alpha.data(), .coef2 = coef.data(), .P = sp.P.data(), .nv = m,
+                             .beta_mu = sp.beta_mu, .tau = sp.tau, .rx = rx->d, .diag = diag, .n = n, .px = px->d,
+                             .pzl = pzl->d, .pzu = pzu->d, .tout = tp_out, .va = vA->d, .nca = c, .out = out.data(),
+                             .store_step = defer ? 0 : 1, .dinv_diag = t0_diag}));
+  tdots.assign(out.begin(), out.begin() + m);
+  step_flags.tdots_valid = true;
+  step_mins[0] = out[m];
+  step_mins[1] = out[m + 1];
+  step_flags.step_deferred = defer;
+  if (defer) {
+    alpha_first = sp.alpha;
+    coef_first = coef;
+    diag_first = diag;
+  }
+  return PO_OK;
+}
+
+// Recomputing refinement pass -- taken for the refinement solve after a fused first pass that stored no step
+// (step_deferred): the first step is re-formed from (t, alpha_first) and the refinement applied on top in one sweep.
+// Sets fused_merit_valid when it takes the merit sums, and clears pz_stored (with step_beta_mu) for a lean step.
+int InteriorPoint::recomputingRefinementPass(const SolvePass &sp, bool corr) {
+  // the same sweep takes the sums the complementarity check of scaleKKTStep and the merit derivative need of the
+  // final step (see solve2r_kernel): no separate pass over the step afterwards
+  const bool take_merit = forms.fuse_merit && forms.recompute_rhs && !corr;
+  // lean step: (pzl, pzu) stay in registers; their only consumer left, the multiplier update, re-forms them
+  const bool lean = forms.lean_step && lean_step_allowed && take_merit && iterate_flags.iterate_logs_valid;
+  // Dinv and the first right-hand side t re-formed in registers from data the pass loads anyway (same bits)
+  const bool redo_dt = forms.recompute_dt && forms.recompute_rhs && scratch_flags.first_t_recomputable;
+  if (lean) {
+    step_flags.pz_stored = false;
+    step_beta_mu = sp.beta_mu;
+  }
+  PO_TRY(k_solve2r(ctx, {.b = bounds(), .t1 = redo_dt ? nullptr : tvec->d,
+                         .t2 = forms.recompute_rhs ? nullptr : xt->d, .dinv = Dinv->d, .a1 = alpha_first.data(),
+                         .a2 = sp.alpha.data(), .P = sp.P.data(), .nv = sp.m, .beta_mu = sp.beta_mu, .tau = sp.tau,
+                         .n = n, .px = px->d, .pzl = lean ? nullptr : pzl->d, .pzu = lean ? nullptr : pzu->d,
+                         .va = vA->d, .nca = c, .out = step_mins, .ar = coef_first.data(), .rx = rx->d,
+                         .diag = diag_first, .g = take_merit ? g->d : nullptr,
+                         .merit_out = take_merit ? fused_merit.as_array() : nullptr, .dinv_diag = t0_diag}));
+  if (take_merit) {
+    after_reduce(ctx, [this] {
+      step_mins[0] = fused_merit.max_x;
+      step_mins[1] = fused_merit.max_z;
+      step_flags.fused_merit_valid = true;
+    });
+  }
+  return PO_OK;
+}
+
+// Corrector solve -- taken for the first solve of a Mehrotra corrector whose products were not stored
+// (corrector_fused, 1 <= m <= kCorrDotsMax): the corrector terms are re-formed from the affine step this pass
+// overwrites, and it takes the sums of scaleKKTStep / evalMeritInitDeriv of the step it has in registers (k_comp_merit
+// and its round trip disappear).  Sets fused_merit_valid and, when it took them, iterate_logs_valid.
+int InteriorPoint::correctorSolve(const SolvePass &sp) {
+  const bool want_logs = !iterate_flags.iterate_logs_valid;
+  PO_TRY(k_solve2c(ctx, {.b = bounds(), .t = tvec->d, .dinv = Dinv->d, .alpha = sp.alpha.data(), .P = sp.P.data(),
+                         .nv = sp.m, .beta_mu = sp.beta_mu, .tau = sp.tau, .n = n, .px = px->d, .pzl = pzl->d,
+                         .pzu = pzu->d, .va = vA->d, .nca = c, .g = g->d, .want_logs = want_logs ? 1 : 0,
+                         .out = corr_out.as_array()}));
+  after_reduce(ctx, [this, want_logs] {
+    const CorrectorSums &o = corr_out;
+    fused_merit = {.S10 = o.S10, .S01 = o.S01, .S11 = o.S11, .ppos = o.ppos, .pneg = o.pneg, .gpx = o.gpx,
+                   .pxpx = o.pxpx, .max_x = o.max_x, .max_z = o.max_z, .px_amax = o.px_amax};
+    step_mins[0] = o.max_x;
+    step_mins[1] = o.max_z;
+    if (want_logs) {  // the barrier sums of the iterate, as k_comp_merit takes them
+      iterate_logs[0] = o.pos_log;
+      iterate_logs[1] = o.neg_log;
+      iterate_flags.iterate_logs_valid = true;
+    }
+    step_flags.fused_merit_valid = true;
+  });
+  return PO_OK;
+}
+
+// Stored-step solve -- every other case: the first solve or a refinement on top of the step in (px, pzl, pzu), with
+// stored corrector products (cl, cu) if any; coef2 != nullptr: the same pass writes the refinement right-hand side t'
+// over tvec.  Sets no flag of its own.
+int InteriorPoint::storedStepSolve(const SolvePass &sp, bool refine_pass, const double *coef2, double diag,
+                                   const double *cl, const double *cu) {
+  return k_solve2(ctx, {.b = bounds(), .t = tvec->d, .dinv = Dinv->d, .alpha = sp.alpha.data(), .P = sp.P.data(),
+                        .nv = sp.m, .beta_mu = sp.beta_mu, .refine = refine_pass ? 1 : 0, .tau = sp.tau, .n = n,
+                        .px = px->d, .pzl = pzl->d, .pzu = pzu->d, .out = step_mins, .coef2 = coef2, .rx = rx->d,
+                        .diag = diag, .tout = tvec->d, .va = vA->d, .nca = c, .cl = cl, .cu = cu});
 }
 
 int InteriorPoint::computeKKTStepWithRefinement(double mu, bool use_qn, double tau) {
@@ -1246,7 +1294,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
     // the refinement pass of the affine solve took the complementarity polynomial of its step (solve2r_kernel):
     // S00 + ax S10 + az S01 + ax az S11 at the probe lengths, S00 / the bound count from the residual pass of this
     // iterate -- no pass over the step and no host round trip (round 6; scaleKKTStep uses the same form)
-    cs[0] = comp_prod + max_x * fused_merit[0] + max_z * fused_merit[1] + max_x * max_z * fused_merit[2];
+    cs[0] = comp_prod + max_x * fused_merit.S10 + max_z * fused_merit.S01 + max_x * max_z * fused_merit.S11;
     cs[1] = comp_count;
   } else {
     PO_TRY(k_comp_step(ctx, bounds(), px->d, pzl->d, pzu->d, max_x, max_z, n, cs));
@@ -1362,20 +1410,16 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     // writer of the iterate clears the flags; an iteration callback or a getArray view must not WRITE the iterate
     // mid-solve (po_ip_set_iteration_callback: an observer) -- resetDesignAndBounds / readSolutionFile between solves
     // refresh mirrors and flags (refreshLiveMirror)
-    out[0] = comp_prod + ax * fused_merit[0] + az * fused_merit[1] + ax * az * fused_merit[2];
+    out[0] = comp_prod + ax * fused_merit.S10 + az * fused_merit.S01 + ax * az * fused_merit.S11;
     out[1] = comp_count;
-    merit_cache[0] = iterate_logs[0];
-    merit_cache[1] = iterate_logs[1];
-    merit_cache[2] = fused_merit[3];
-    merit_cache[3] = fused_merit[4];
-    merit_cache[4] = fused_merit[5];
-    merit_cache[5] = fused_merit[6];
-    merit_cache[6] = fused_merit[9];
+    merit_cache = {.pos_log = iterate_logs[0], .neg_log = iterate_logs[1], .ppos = fused_merit.ppos,
+                   .pneg = fused_merit.pneg, .gpx = fused_merit.gpx, .pxpx = fused_merit.pxpx,
+                   .px_amax = fused_merit.px_amax};
     step_flags.merit_cache_valid = true;
   } else if (!has_w) {
     // one pass also yields the merit pieces and the step norm the line search is about to ask for
     PO_TRY(k_comp_merit(ctx, bounds(), px->d, pzl->d, pzu->d, ax, az, g->d, n, out));
-    for (int i = 0; i < 7; i++) merit_cache[i] = out[2 + i];
+    merit_cache = MeritSums::fromCompMerit(out);
     step_flags.merit_cache_valid = true;
   } else {
     BatchScope batch(ctx);  // design and sparse parts of the complementarity: one collective + sync
@@ -1384,7 +1428,7 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     PO_TRY(k_comp_merit(ctx, bounds(), px->d, pzl->d, pzu->d, ax, az, g->d, n, out));
     PO_TRY(wCompStep(ax, az, &wprod));  // :2866-2889
     PO_TRY(batch.end());
-    for (int i = 0; i < 7; i++) merit_cache[i] = out[2 + i];
+    merit_cache = MeritSums::fromCompMerit(out);
     step_flags.merit_cache_valid = true;
   }
   double prod = out[0] / options.real("rel_bound_barrier"), count = out[1];
@@ -1471,12 +1515,12 @@ int InteriorPoint::evalMeritInitDeriv(double max_x, double *merit_, double *pmer
     // problem's sparse callbacks run in between: built-in problems only)
     BatchScope batch(ctx, has_w && prob->reductionsBatchable());
     if (step_flags.merit_cache_valid) {
-      out[0] = merit_cache[0];
-      out[1] = merit_cache[1];
-      out[2] = sx * merit_cache[2];
-      out[3] = sx * merit_cache[3];
-      out[4] = sx * merit_cache[4];
-      out[5] = sx * sx * merit_cache[5];
+      out[0] = merit_cache.pos_log;
+      out[1] = merit_cache.neg_log;
+      out[2] = sx * merit_cache.ppos;
+      out[3] = sx * merit_cache.pneg;
+      out[4] = sx * merit_cache.gpx;
+      out[5] = sx * sx * merit_cache.pxpx;
     } else {
       PO_TRY(k_merit0(ctx, bounds(), px->d, sx, g->d, n, out));
       if (batch.open) {  // max|px| for the line search's minimum step rides in this batch (its own sync otherwise)
@@ -2072,10 +2116,10 @@ int InteriorPoint::optimize(const char *checkpoint) {
     double comp = 0.0;
     // (the inexact Newton step reads the 2-norms of the bound residuals, computeKKTGMRESStep: no shortcut there)
     spec_enabled = barrier_strategy == B_MONOTONE && norm_type == 0 && !has_w && !use_hvec_product;
+    if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
+    iterate_flags.residual_cached = false;
+    comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
     if (barrier_strategy == B_MONOTONE) {
-      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      iterate_flags.residual_cached = false;
-      comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       denseResidual(barrier_param, res);
       resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
       if (k > 0 && ((res_norm < 10.0 * barrier_param) || rel_function_test || (line_search_test >= 2))) {
@@ -2103,15 +2147,9 @@ int InteriorPoint::optimize(const char *checkpoint) {
         barrier_param = new_mu;
       }
     } else if (barrier_strategy == B_MEHROTRA || barrier_strategy == B_MPC) {  // :4737-4746
-      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      iterate_flags.residual_cached = false;
-      comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       denseResidual(barrier_param, res);
       resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
     } else {  // complementarity fraction (:4747-4762)
-      if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
-      iterate_flags.residual_cached = false;
-      comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
       barrier_param = options.real("monotone_barrier_fraction") * comp;
       if (barrier_param < 0.1 * abs_res_tol) barrier_param = 0.1 * abs_res_tol;
       PO_TRY(computeResidual(barrier_param, false));
@@ -2216,22 +2254,20 @@ int InteriorPoint::optimize(const char *checkpoint) {
       }
     }
 
-    if (inexact_newton_step) {
-      // nothing to do: computeKKTGMRESStep left the step in (px, pzl, pzu, step)
-    } else {
-    const double rhs_mu = mehrotra ? 0.0 : barrier_param;  // of the solve that follows
-    PO_TRY(setUpKKTSystem(use_qn, diagonal_quasi_newton_step != 0, &rhs_mu));
-    phaseEnd("setup_kkt");
-    if (!mehrotra) {
-      // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
-      lean_step_allowed = qn && use_qnu && use_qn && !diagonal_quasi_newton_step && forms.analytic_panel_dots &&
-                          forms.fuse_mult_update && !use_hvec_product && !use_diag_hessian && !seq_lin;
-      const int step_rc = computeKKTStepWithRefinement(barrier_param, use_qn, tau);
-      lean_step_allowed = false;
-      PO_TRY(step_rc);
-    } else {
-      PO_TRY(mehrotraStep(use_qn, comp, barrier_strategy == B_MPC, min_frac, abs_res_tol, &tau));
-    }
+    if (!inexact_newton_step) {  // (otherwise computeKKTGMRESStep left the step in (px, pzl, pzu, step))
+      const double rhs_mu = mehrotra ? 0.0 : barrier_param;  // of the solve that follows
+      PO_TRY(setUpKKTSystem(use_qn, diagonal_quasi_newton_step != 0, &rhs_mu));
+      phaseEnd("setup_kkt");
+      if (!mehrotra) {
+        // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
+        lean_step_allowed = qn && use_qnu && use_qn && !diagonal_quasi_newton_step && forms.analytic_panel_dots &&
+                            forms.fuse_mult_update && !use_hvec_product && !use_diag_hessian && !seq_lin;
+        const int step_rc = computeKKTStepWithRefinement(barrier_param, use_qn, tau);
+        lean_step_allowed = false;
+        PO_TRY(step_rc);
+      } else {
+        PO_TRY(mehrotraStep(use_qn, comp, barrier_strategy == B_MPC, min_frac, abs_res_tol, &tau));
+      }
     }
     phaseEnd("kkt_step");
     // step_verification_frequency (:5056-5073): block maxima of the linearised KKT residual at the step
@@ -2284,7 +2320,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
         } else {
           double px_norm = 0.0;
           if (step_flags.merit_cache_valid) {
-            px_norm = merit_cache[6];
+            px_norm = merit_cache.px_amax;
           } else if (step_flags.px_amax_valid) {
             px_norm = px_amax_w;
           } else {

@@ -140,7 +140,7 @@ class InteriorPoint {
   std::vector<std::string> phase_names;
   std::vector<double> phase_seconds;
   std::string phase_names_joined;
-  // Event timing of the problem's callbacks (the "user_eval" phase).  Off by default (round 6): every event record
+  // Event timing of the problem's callbacks (the "user_eval" phase).  Off by default: every event record
   // is a packet between two kernels and costs the stream dispatch latency -- 850 / 853 against 863 / 866 inner it/s
   // at config 5 in one call (5-6 callbacks per 1.2 ms inner iteration), nothing measurable at n >= 10 M.
   // po_ip_set_callback_timing switches it on (bench.py does, for the figure it reports).
@@ -166,10 +166,20 @@ class InteriorPoint {
 
   // small dense systems: the weighted Gram W of the panel and the factors of the bordered solve
   Bordered kkt;
+  std::vector<double> Wt_buf, W2_buf;  // landing areas of Gram launches deferred to a batch flush (setUpKKTSystem)
+  // the head solveKKT and solveKKTW share, and what every pass form of theirs is handed: the panel, its coefficients
+  // in the step (sol.coef) and the scalars of the solve
+  Bordered::Sol solveBordered(const Dense &b, const double *dots, bool refine_pass);
+  struct SolvePass {
+    const std::vector<const double *> &P;
+    const std::vector<double> &alpha;
+    int m;
+    double beta_mu, tau;
+  };
 
   // What the carried buffers and caches hold, grouped by the event that makes them stale.  Each group is dropped as a
   // whole by its event method (group = {}: a member added later cannot be missed); a flag consumed by the one pass
-  // that reads it is cleared there.  The values recorded with a flag sit beside it below.
+  // that reads it is cleared there.  The values recorded with a flag sit below its group.
   struct StepFlags {  // the current step in px / pzl / pzu and what was taken of it; stale when a solve writes a step
     bool ptpx_valid = false;           // ptpx = P^T px
     bool tdots_valid = false;          // tdots = P^T t' of the fused first pass (consumed by the refinement pass)
@@ -180,10 +190,37 @@ class InteriorPoint {
     bool w_merit_cache_valid = false;  // w_merit_cache
     bool vA_valid = false;             // vA = A^T pz, maintained by the solves
     bool residual_fused = false;       // the first pass already wrote the refinement right-hand side t'
-    bool pz_stored = true;             // pzl / pzu hold the step (false after a lean step: px only)
+    bool pz_stored = true;             // pzl / pzu hold the step (false after a lean step: px only; step_beta_mu)
     bool step_deferred = false;        // the first pass stored no step (alpha_first, coef_first, diag_first)
     bool px_first_only = false;        // sparse path: the first pass stored px only
   } step_flags;
+  // P^T px of the current (unscaled) step, P = [Ac | Z]: maintained analytically from the solves
+  // (px = t + Dinv*(P alpha)  =>  P^T px = P^T t + W alpha), so that neither iterative refinement
+  // nor the merit derivative needs another pass over the panel
+  std::vector<double> ptpx;
+  std::vector<double> tdots;
+  // merit pieces of the current (unscaled) step, produced together with the complementarity check of scaleKKTStep
+  MeritSums merit_cache;
+  // the same pieces taken by the refinement pass itself (k_solve2r with g), or handed over by the corrector solve
+  // (corr_out: what k_solve2c reduced); the log-barrier sums of the iterate are those of the accepted trial point of
+  // the last line search (same kernel arithmetic, same element order as the separate pass took them)
+  FusedMeritSums fused_merit;
+  CorrectorSums corr_out;
+  double px_amax_w = 0.0;  // max|px| taken inside evalMeritInitDeriv's batch (sparse-constraint path)
+  // Sparse constraints: the sparse blocks' share of the complementarity polynomial comes out of the step kernel
+  // (w_step_out -> w_comp_poly) and the sparse merit sums ride in the refinement's batch (w_merit_cache, at sx = 1)
+  double w_step_out[5] = {0, 0, 0, 0, 0}, w_comp_poly[3] = {0, 0, 0}, w_merit_cache[10] = {0};
+  // Lean step: in the plain quasi-Newton iteration the refinement pass stores px only; the bound-multiplier steps are
+  // re-formed from it inside the multiplier update (kkt_res_update_kernel, with the barrier term step_beta_mu of the
+  // step's solve) -- two output streams of the refinement pass less.  lean_step_allowed is set by optimize() around the
+  // step computation of an iteration whose every later consumer of (pzl, pzu) is that update.
+  bool lean_step_allowed = false;
+  double step_beta_mu = 0.0;
+  std::vector<double> alpha_first, coef_first;  // coefficients of a deferred first pass (solve, refinement residual)
+  double diag_first = 0.0;
+  double step_mins[2];         // fraction-to-boundary minima {max_x, max_z} of the current step
+  double sx = 1.0, sz = 1.0;  // lazily applied step scalings (scaleKKTStep :3253-3268)
+
   // what the scratch vectors tvec, Dinv, d1v, wd2 and Uw hold; stale when they are lent out (checkGradients) or the
   // state is written from outside
   struct ScratchFlags {
@@ -194,6 +231,16 @@ class InteriorPoint {
     bool wd2_ready = false;             // wd2 = d2 of the next block solve
     bool panel_valid = false;           // Uw is the panel image of the current setUpKKTSystem (panel_form)
   } scratch_flags;
+  // Dinv / t of the next first solve left behind by the residual pass of the new point when no quasi-Newton update
+  // comes in between (spec_dt_want); valid for the diagonal and the barrier parameter recorded with them
+  bool spec_dt_want = false;
+  double spec_dt_diag = 0.0, spec_dt_bmu = 0.0, spec_dt_mu = 0.0;
+  double t0_mu = 0.0;
+  std::vector<double> t0dots;  // P^T t of the next first solve, out of setUpKKTSystem's Gram pass
+  // tvec / Dinv hold exactly what dinv_d1_kernel formed for (t0_diag, t0_mu) from the bound data and rx: a pass that
+  // loads those anyway may re-form them in registers instead of reading them (k_solve2r with t1 == nullptr)
+  double t0_diag = 0.0;
+
   // what was evaluated at the current iterate x; stale when x, the bounds or the problem instance change other than
   // by the step update
   struct IterateFlags {
@@ -207,6 +254,18 @@ class InteriorPoint {
     bool spec_valid = false;          // spec_max for spec_mu
     bool s_qn_from_trial = false;     // s_qn holds s_qn_a * px, written by the last trial pass of the line search
   } iterate_flags;
+  // A^T z of a problem with linear dense constraints, kept by recurrence (computeResidual / computeStepAndUpdate)
+  static const int kAczRefresh = 16;
+  Vec *acz = nullptr;
+  int acz_age = 0;
+  double trial_logs[2] = {0, 0}, iterate_logs[2] = {0, 0};
+  // Monotone barrier strategy with the infinity norm: the residual pass also takes max|rzl|, max|rzu| for the barrier
+  // parameter the strategy would switch to (a function of the current one alone), so that the switch needs neither
+  // the mu-only pass over the bound data nor its host synchronisation
+  bool spec_enabled = false;
+  double spec_mu = 0.0, spec_max[2] = {0.0, 0.0};
+  double s_qn_a = 0.0;
+
   void stepWillChange() { step_flags = {}; }
   void scratchLent() { scratch_flags = {}; }
   void iterateReplaced() { iterate_flags = {}; }
@@ -215,51 +274,22 @@ class InteriorPoint {
     scratchLent();
     iterateReplaced();
   }
-  // residual bookkeeping of the last computeResidual call
+
+  // residual bookkeeping of the last computeResidual call; res_out / wres_out: landing areas of its reductions (inside
+  // a BatchScope the values arrive at the flush, see after_reduce)
+  ResidualSums res_out;
+  double wres_out[12] = {0};
   double comp_prod, comp_count, max_rx, max_rzl, max_rzu;
   double l1_rx = 0, l1_rzl = 0, l1_rzu = 0, l2_rx = 0, l2_rzl = 0, l2_rzu = 0;
-  // lazily applied step scalings (scaleKKTStep :3253-3268)
-  double sx, sz;
-  double step_mins[2];
-  // P^T px of the current (unscaled) step, P = [Ac | Z]: maintained analytically from the solves
-  // (px = t + Dinv*(P alpha)  =>  P^T px = P^T t + W alpha), so that neither iterative refinement
-  // nor the merit derivative needs another pass over the panel
-  std::vector<double> ptpx;
   bool corrector_active;  // Mehrotra predictor-corrector: s_qn / y_qn hold the corrector products
-  // ... unless the corrector solve forms them itself (round 6: k_corr_d1_dots + k_solve2c, two launches and two host
-  // round trips instead of five and three); corr_out: what k_solve2c reduced
+  // ... unless the corrector solve forms them itself (k_corr_d1_dots + k_solve2c)
   bool corrector_fused = false;
-  // Dinv / t of the next first solve left behind by the residual pass of the new point (no quasi-Newton update in
-  // between: round 6; scratch_flags.spec_dt_valid); valid for the diagonal and the barrier parameter recorded with them
-  bool spec_dt_want = false;
-  double spec_dt_diag = 0.0, spec_dt_bmu = 0.0, spec_dt_mu = 0.0;
-  double corr_out[12] = {0};
-  int norm_type;          // 0 infinity, 1 l1, 2 l2 (ParOptNormType)
-  std::vector<double> tdots;  // P^T t' produced by the fused first solve pass
+  int norm_type;  // 0 infinity, 1 l1, 2 l2 (ParOptNormType)
 
   // ---- second-order information (ip_gmres.cpp) ----
   Vec *hdiag;                  // use_diag_hessian: diagonal of the Lagrangian Hessian (zero until evaluated)
   std::vector<Vec *> gmresW;   // Krylov basis of computeKKTGMRESStep
   bool inexact_newton_step;    // the current step came from computeKKTGMRESStep
-  // merit pieces of the current (unscaled) step, produced together with the complementarity check of
-  // scaleKKTStep: {pos log, neg log, ppos, pneg, g.px, px.px, max|px|}
-  double merit_cache[7];
-  double px_amax_w = 0.0;       // max|px| taken inside evalMeritInitDeriv's batch (sparse-constraint path)
-  std::vector<double> Wt_buf, W2_buf;  // landing areas of Gram launches deferred to a batch flush (setUpKKTSystem)
-  // the same pieces taken by the refinement pass itself (k_solve2r with g): {S10, S01, S11, ppos, pneg, g.px, px.px,
-  // max_x, max_z, max|px|}; the log-barrier sums of the iterate are those of the accepted trial point of the last
-  // line search (same kernel arithmetic, same element order as the separate pass took them)
-  double fused_merit[10] = {0};
-  // "lean step" (round 3): in the plain quasi-Newton iteration the refinement pass stores px only; the bound-
-  // multiplier steps are re-formed from it inside the multiplier update (kkt_res_update_kernel) -- two output streams
-  // of the refinement pass less.  lean_step_allowed is set by optimize() around the step computation of an iteration
-  // whose every later consumer of (pzl, pzu) is that update; pz_stored says whether the vectors hold the current step.
-  // tvec / Dinv hold exactly what dinv_d1_kernel formed for (t0_diag, t0_mu) from the bound data and rx: a pass that
-  // loads those anyway may re-form them in registers instead of reading them (k_solve2r with t1 == nullptr)
-  double t0_diag = 0.0;
-  bool lean_step_allowed = false;
-  double step_beta_mu = 0.0;
-  double trial_logs[2] = {0, 0}, iterate_logs[2] = {0, 0};
   int gatherCounts(int64_t mine, std::vector<int64_t> *all);
   int solutionFileOffsets(int64_t *nvars_total, int64_t *var_off, int64_t *nw_total, int64_t *w_off);
   int ensureHdiag();
@@ -293,7 +323,7 @@ class InteriorPoint {
 
   // ---- sparse-constraint path (ip_w.cpp) ----
   Vec *gsw, *gtw, *Cw, *wd2, *wyw, *wtmp, *wtmp2;
-  // cw(x) of the CURRENT iterate (round 4): the residual (twice per iteration: new barrier parameter), the
+  // cw(x) of the CURRENT iterate: the residual (twice per iteration: new barrier parameter), the
   // refinement's residual and the merit derivative all need the sparse constraint values at the same point; the
   // reference calls evalSparseCon each time (:1358, 3740), here the callback runs once per point and the accepted
   // trial point of the line search hands its values over.  Dropped whenever x or the problem instance changes.
@@ -307,12 +337,6 @@ class InteriorPoint {
   std::vector<Vec *> Yw;
   std::vector<const double *> correctionPanel(int m) const;  // Yw (panel_form.solved) or Uw, m columns
   double w_sums[7], w_maxs[5];  // reductions of the last w residual (k_w_res layout)
-  double res_out[13] = {0}, wres_out[12] = {0};  // landing area of the residual reductions (see after_reduce)
-  // Monotone barrier strategy with the infinity norm (round 4): the residual pass also takes max|rzl|, max|rzu| for the
-  // barrier parameter the strategy would switch to (a function of the current one alone), so that the switch needs
-  // neither the mu-only pass over the bound data nor its host synchronisation
-  bool spec_enabled = false;
-  double spec_mu = 0.0, spec_max[2] = {0.0, 0.0};
   double nextMonotoneMu() const;
   WVars wv() const;
   WVars wr() const;
@@ -326,6 +350,12 @@ class InteriorPoint {
   int panelImageVectors(int m, std::vector<double *> &U);  // Uw[0..m) as raw pointers (allocated on demand)
   int solveKKTW(const Dense &b, double mu, bool use_qn, bool refine_pass, double tau, Dense &out,
                 bool fuse_residual = false);
+  // its pass forms (ip_w.cpp); mins_x / mins_w: the fraction-to-boundary minima of the design and sparse blocks
+  int fusedFirstPassW(const SolvePass &sp, int k, double mins_x[2], double mins_w[2]);
+  int correctionPanelSolve(const SolvePass &sp, bool refine_pass, bool first_px_only, const double *cl,
+                           const double *cu, double mins_x[2], double mins_w[2]);
+  int blockSolveFallback(const SolvePass &sp, bool refine_pass, const double *cl, const double *cu, double mins_x[2],
+                         double mins_w[2]);
   int initLeastSquaresMultipliersW();
   int wCompStep(double ax, double az, double *prod);
 
@@ -371,8 +401,30 @@ class InteriorPoint {
   // diag_only: keep b0 of the quasi-Newton approximation in Dinv but leave its low-rank part out
   // (the "diagonal quasi-Newton step" of :4923-4980)
   int setUpKKTSystem(bool use_qn, bool diag_only = false, const double *rhs_mu = nullptr);
+  // its steps: (1) Dinv and, where the right-hand side of the first solve is known already, that vector from the same
+  // pass -- t = Dinv o d1 in tvec (dense constraints) or the raw d1 in d1v (sparse constraints);
+  enum RhsFormed { RHS_NONE, RHS_T, RHS_RAW_D1 };
+  int formDinvAndRhs(double diag, bool use_hdiag, const double *rhs_mu, int kz, RhsFormed *formed);
+  // (2) the Gram pass of the panel, (3) kkt.factor
+  struct GramPlan {
+    std::vector<const double *> V;  // the panel in launch order: [Ac | Z], or [Z | Ac] with kform > 0
+    int kform = 0;                  // leading columns the pass forms itself: L-SR1's Z_j = Y_j - b0 S_j, V_j = Y_j
+    std::vector<const double *> S;  // ... from these S_j,
+    std::vector<double *> Zout;     // ... written out here for the later passes
+    double b0 = 0.0;
+    bool with_t = false;  // tvec rides as the pre-weighted last column: P^T t lands in t0dots
+    const GramGroups *groups = nullptr;  // structured sparse constraints: the panel image rides too (k_wgram)
+    bool may_defer = false;              // inside an open batch the result arrives at the flush
+  };
+  int gramPass(const GramPlan &plan, bool *groups_done);
   int solveKKT(const Dense &b, double mu, bool use_qn, bool refine_pass, double tau, Dense &out,
                bool fuse_residual = false);
+  // the pass forms of solveKKT (ip.cpp)
+  int fusedFirstPass(const SolvePass &sp, const std::vector<double> &coef, double diag);
+  int recomputingRefinementPass(const SolvePass &sp, bool corr);
+  int correctorSolve(const SolvePass &sp);
+  int storedStepSolve(const SolvePass &sp, bool refine_pass, const double *coef2, double diag, const double *cl,
+                      const double *cu);
   int computeKKTStepWithRefinement(double mu, bool use_qn, double tau);
   int mehrotraStep(bool use_qn, double comp, bool corrector, double min_frac, double abs_res_tol, double *tau_out);
   int scaleKKTStep(double tau, double comp, double *alpha_x, double *alpha_z, int *ceq,
@@ -413,21 +465,6 @@ class InteriorPoint {
   // kernels); every other writer of lb / ub clears them
   int bounds_uni[2] = {0, 0};
   double bounds_val[2] = {0.0, 0.0};
-  // A^T z of a problem with linear dense constraints, kept by recurrence (computeResidual / computeStepAndUpdate)
-  static const int kAczRefresh = 16;
-  Vec *acz = nullptr;
-  int acz_age = 0;
-  // sparse constraints, round 4: y_qn from the residuals, and "lean" solve passes: the fused
-  // first pass stores px only (px_first_only), the refinement pass re-forms the first bound-multiplier steps from it,
-  // takes the complementarity / merit sums of the final step (fused_merit, as on the dense path) and, in the plain
-  // quasi-Newton iteration, stores px only again; the sparse blocks' share of the complementarity polynomial comes
-  // out of the step kernel (w_comp_poly) and the sparse merit sums ride in the same batch (w_merit_cache, sx = 1)
-  double w_step_out[5] = {0, 0, 0, 0, 0}, w_comp_poly[3] = {0, 0, 0}, w_merit_cache[10] = {0};
-  double s_qn_a = 0.0;
-  std::vector<double> alpha_first, coef_first;  // coefficients of that first pass (solve, refinement residual)
-  double diag_first = 0.0;
-  double t0_mu = 0.0;
-  std::vector<double> t0dots;  // Ac holds the Jacobian of a problem with linear_constraints
 };
 
 }  // namespace po

@@ -203,13 +203,9 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   }
   if (!refine_pass) scratch_flags.t0_valid = false;  // tvec is overwritten below
   bool first_px_only = refine_pass && step_flags.px_first_only;  // px holds the first step, pzl / pzu were not stored
-  stepWillChange();
-  Bordered::Sol sol;
-  kkt.solve(1.0, b, vars, dots.data(), &sol);
-  const std::vector<double> &alpha = sol.coef;
-  kkt.panelDots(dots.data(), sol, refine_pass, &ptpx);
-  step_flags.ptpx_valid = true;
-  if (first_px_only && !(m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid)) {
+  const Bordered::Sol sol = solveBordered(b, dots.data(), refine_pass);
+  const bool have_corr_panel = m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid;
+  if (first_px_only && !have_corr_panel) {
     // (not reached with the flags as they are set: the fused first pass implies a valid panel) the stored-step forms
     // below need the first bound-multiplier steps as vectors
     PO_TRY(k_form_pz(ctx, bounds(), px->d, beta_mu, n, pzl->d, pzu->d));
@@ -218,145 +214,177 @@ int InteriorPoint::solveKKTW(const Dense &b, double mu, bool use_qn, bool refine
   // (dx, dzw) = K0^-1 (d1 + P alpha, d2) = K0^-1 (d1, d2) + K0^-1 (P alpha, 0), and the second term comes from
   // the panel the Gram correction already holds: dzw += -S^-1 (U alpha), dx += Dinv (P alpha + Aw^T of that) -
   // no second quasi-definite apply, and P alpha rides in the same pass that forms the bound multipliers
-  double mins_x[2], mins_w[2];
-  bool w_done = false;  // the refinement branch below already took the sparse step with its other sums
-  // the fraction-to-boundary minima of the design and of the sparse blocks: one collective + sync (opened right
-  // before the first of the two launches: no user code runs between them)
-  BatchScope minbatch(ctx, false);
   const bool seq_lin = options.integer("sequential_linear_method");
   const int kq = (qn && !seq_lin) ? qn->size() : 0;
   // Fused refinement residual (as on the dense path, ip.cpp solveKKT): the coefficients of addKKTResStep are known
   // before the axpy pass starts, and so is the sparse multiplier step pzw (it depends on wyw only), so ONE pass
   // over P writes the step, the RAW right-hand side d1' of the refinement solve (its design rows, :1451-1483, with
   // the extra column Aw^T pzw) and the panel products of Dinv o d1'.
-  const bool fuse = fuse_residual && !refine_pass && forms.analytic_panel_dots && kq == k && m > 0 &&
-                    (int)Uw.size() >= m && scratch_flags.panel_valid && panel_form.plain && !cl &&
-                    !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
+  const bool fuse = fuse_residual && !refine_pass && forms.analytic_panel_dots && kq == k && have_corr_panel &&
+                    panel_form.plain && !cl && !(options.integer("use_diag_hessian") && hdiag) && m + 2 <= kMaxPanel;
+  // the fraction-to-boundary minima of the design and of the sparse blocks: one collective + sync in every form
+  double mins_x[2], mins_w[2];
+  const SolvePass sp{P, sol.coef, m, beta_mu, tau};
   if (fuse) {
-    std::vector<const double *> Uc = correctionPanel(m);
-    PO_TRY(prob->sparseCorrection(Uc.data(), m, alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
-    // the two extra columns Aw^T wtmp2 (coefficient 1 in the step's row sum) and Aw^T pzw (1 in the residual's): n-sized
-    // vectors from Problem::setSparseJacobianTranspose, or -- structured problems -- described and formed by the pass
-    GroupCols2 gcs;
-    const bool grouped = prob->sparseTransposeColumn(1.0, x, wtmp2, &gcs.g[0]);
-    if (!grouped && prob->setSparseJacobianTranspose(1.0, x, wtmp2, d1v) != 0) return PO_ERR_USER;
-    // sparse blocks of the step first: pzw = wstepv[0] feeds the residual column Aw^T pzw (its minima wait for
-    // those of the design blocks unless user code runs in between)
-    if (prob->reductionsBatchable()) minbatch.begin();
-    PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, 0, tau, wp(), nw, mins_w));
-    if (grouped) {
-      if (!prob->sparseTransposeColumn(1.0, x, wstepv[0], &gcs.g[1])) {
-        set_error("internal: the problem describes one sparse transpose column but not the other");
-        return PO_ERR_ARG;
-      }
-      gcs.count = 2;
-      gcs.ca[0] = 1.0;
-      gcs.cb[1] = 1.0;
-    } else if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], xt) != 0) {
-      return PO_ERR_USER;
-    }
-    std::vector<const double *> P1(P);
-    std::vector<double> a1(alpha.begin(), alpha.begin() + m), c2(m + 2, 0.0);
-    if (!grouped) {
-      P1.push_back(d1v->d);
-      a1.push_back(1.0);
-      P1.push_back(xt->d);
-      a1.push_back(0.0);
-    }
-    const int np1 = (int)P1.size();
-    double diag = 0.0;  // (alpha[0..c) = step.z)
-    PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, alpha.data(), ptpx.data() + c, k, c2, &diag));
-    c2[m + 1] = 1.0;
-    std::vector<double> so(m + 4, 0.0);
-    // the raw right-hand side lands in y_qn (free while no corrector is active: y_qn is rebuilt from scratch by
-    // computeStepAndUpdate) -- d1v is one of the columns being read -- and the two exchange buffers afterwards.
-    // Of the step only px is stored (store_step 2): the refinement's sparse rows need Aw px as a vector, the bound-
-    // multiplier steps are re-formed from px by the refinement pass (two output streams less)
-    PO_TRY(k_solve2_dots(ctx, bounds(), tvec->d, Dinv->d, a1.data(), c2.data(), P1.data(), np1, beta_mu, tau,
-                         rx->d, diag, n, px->d, pzl->d, pzu->d, nullptr, nullptr, 0, so.data(), y_qn->d, 2, 0,
-                         0.0, grouped ? &gcs : nullptr));
-    step_flags.px_first_only = true;
-    std::swap(d1v->d, y_qn->d);
-    PO_TRY(minbatch.end());
-    tdots.assign(so.begin(), so.begin() + m);
-    step_flags.tdots_valid = true;
-    step_flags.residual_fused = true;
-    mins_x[0] = so[np1];  // out = {dots[np1], max_x, max_z}
-    mins_x[1] = so[np1 + 1];
-  } else if (m > 0 && (int)Uw.size() >= m && scratch_flags.panel_valid) {
-    std::vector<const double *> Uc = correctionPanel(m);
-    PO_TRY(prob->sparseCorrection(Uc.data(), m, alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
-    // the extra column Aw^T wtmp2 (coefficient 1): stored, or (structured problems, refinement of a px-only first
-    // step) described and formed by the pass itself
-    GroupCol gcol;
-    const bool grouped = first_px_only && prob->sparseTransposeColumn(1.0, x, wtmp2, &gcol);
-    if (!grouped && prob->setSparseJacobianTranspose(1.0, x, wtmp2, d1v) != 0) return PO_ERR_USER;
-    std::vector<const double *> P1(P);
-    std::vector<double> a1(alpha.begin(), alpha.begin() + m);
-    if (!grouped) {
-      P1.push_back(d1v->d);
-      a1.push_back(1.0);
-    }
-    minbatch.begin();
-    if (first_px_only) {
-      // Refinement on top of a first step of which only px was stored: solve2r_kernel in its stored right-hand side
-      // form with a ZERO first coefficient set and t1 = px -- it re-forms (pzl, pzu) of the first step from px
-      // (the very expressions the first pass evaluated: same bits), applies the refinement (t2 = tvec, a2) and takes
-      // the complementarity / merit sums of the FINAL step (fused_merit); the final px goes to xt (free during the
-      // solves) and the two buffers are exchanged.  Lean step: (pzl, pzu) are not stored either -- their only
-      // consumer left is the multiplier update of computeStepAndUpdate, which re-forms them (kkt_res_update_kernel)
-      const bool take_merit = forms.fuse_merit && !cl;
-      const bool lean = take_merit && forms.lean_step && lean_step_allowed && iterate_flags.iterate_logs_valid &&
-                        !prob->linear_constraints && options.integer("iterative_refinement_steps") == 1;
-      std::vector<double> azero(m + 1, 0.0);
-      PO_TRY(k_solve2r(ctx, bounds(), px->d, tvec->d, Dinv->d, azero.data(), a1.data(), P1.data(), (int)P1.size(), beta_mu,
-                       tau, n, xt->d, lean ? nullptr : pzl->d, lean ? nullptr : pzu->d, nullptr, 0, mins_x, nullptr,
-                       nullptr, 0.0, 0, take_merit ? g->d : nullptr,
-                       take_merit ? fused_merit : nullptr, 0.0, grouped ? &gcol : nullptr, 0.0, 1.0));
-      std::swap(px->d, xt->d);
-      if (lean) {
-        step_flags.pz_stored = false;
-        step_beta_mu = beta_mu;
-      }
-      if (take_merit) {
-        // the sparse blocks of the final step, their share of the complementarity polynomial and the sparse merit
-        // sums (at sx = 1) in the same batch: scaleKKTStep and evalMeritInitDeriv then launch nothing
-        PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, 1, tau, wp(), nw, w_step_out, 1));
-        const double *cw = nullptr;
-        PO_TRY(sparseConAtIterate(&cw));
-        PO_TRY(prob->setSparseJacobian(1.0, x, px, wtmp2));
-        PO_TRY(k_w_merit(ctx, wv(), wp(), 1.0, gsw->d, gtw->d, cw, wtmp2->d, nw, w_merit_cache));
-        PO_TRY(minbatch.end());
-        mins_x[0] = fused_merit[7];
-        mins_x[1] = fused_merit[8];
-        mins_w[0] = w_step_out[3];
-        mins_w[1] = w_step_out[4];
-        for (int i = 0; i < 3; i++) w_comp_poly[i] = w_step_out[i];
-        step_flags.fused_merit_valid = true;
-        step_flags.w_comp_valid = true;
-        step_flags.w_merit_cache_valid = true;
-        w_done = true;
-      }
-    } else {
-      PO_TRY(k_solve2(ctx, bounds(), tvec->d, Dinv->d, a1.data(), P1.data(), m + 1, beta_mu, refine_pass ? 1 : 0,
-                      tau, n, px->d, pzl->d, pzu->d, mins_x, nullptr, rx->d, 0.0, nullptr, nullptr, 0, cl, cu));
-    }
+    PO_TRY(fusedFirstPassW(sp, k, mins_x, mins_w));
+  } else if (have_corr_panel) {
+    PO_TRY(correctionPanelSolve(sp, refine_pass, first_px_only, cl, cu, mins_x, mins_w));
   } else {
-    if (m > 0) PO_TRY(k_panel_axpy(ctx, d1v->d, 0.0, nullptr, 1.0, alpha.data(), P.data(), m, n));
-    PO_TRY(applyK0(d1v->d, wd2->d, tvec, wyw));
-    minbatch.begin();
-    PO_TRY(k_solve2(ctx, bounds(), tvec->d, Dinv->d, nullptr, nullptr, 0, beta_mu, refine_pass ? 1 : 0,
-                    tau, n, px->d, pzl->d, pzu->d, mins_x, nullptr, rx->d, 0.0, nullptr, nullptr, 0, cl,
-                    cu));
-  }
-  if (!fuse && !w_done) {
-    PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, refine_pass ? 1 : 0, tau, wp(), nw, mins_w));
-    PO_TRY(minbatch.end());
+    PO_TRY(blockSolveFallback(sp, refine_pass, cl, cu, mins_x, mins_w));
   }
   step_mins[0] = std::min(mins_x[0], mins_w[0]);
   step_mins[1] = std::min(mins_x[1], mins_w[1]);
   kkt.backSubstitute(1.0, b, vars, sol, true, out);
   return PO_OK;
+}
+
+// Fused first pass, sparse constraints -- taken for the first solve when the correction panel is the plain image of the
+// current system and the refinement residual can be written as panel coefficients (`fuse` in solveKKTW).  Of the step
+// only px is stored.  Sets px_first_only, tdots_valid and residual_fused.
+int InteriorPoint::fusedFirstPassW(const SolvePass &sp, int k, double mins_x[2], double mins_w[2]) {
+  const int m = sp.m;
+  const bool seq_lin = options.integer("sequential_linear_method");
+  BatchScope minbatch(ctx, false);  // (opened right before the first of the two launches: no user code runs between them)
+  std::vector<const double *> Uc = correctionPanel(m);
+  PO_TRY(prob->sparseCorrection(Uc.data(), m, sp.alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
+  // the two extra columns Aw^T wtmp2 (coefficient 1 in the step's row sum) and Aw^T pzw (1 in the residual's): n-sized
+  // vectors from Problem::setSparseJacobianTranspose, or -- structured problems -- described and formed by the pass
+  GroupCols2 gcs;
+  const bool grouped = prob->sparseTransposeColumn(1.0, x, wtmp2, &gcs.g[0]);
+  if (!grouped && prob->setSparseJacobianTranspose(1.0, x, wtmp2, d1v) != 0) return PO_ERR_USER;
+  // sparse blocks of the step first: pzw = wstepv[0] feeds the residual column Aw^T pzw (its minima wait for
+  // those of the design blocks unless user code runs in between)
+  if (prob->reductionsBatchable()) minbatch.begin();
+  PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, 0, sp.tau, wp(), nw, mins_w));
+  if (grouped) {
+    if (!prob->sparseTransposeColumn(1.0, x, wstepv[0], &gcs.g[1])) {
+      set_error("internal: the problem describes one sparse transpose column but not the other");
+      return PO_ERR_ARG;
+    }
+    gcs.count = 2;
+    gcs.ca[0] = 1.0;
+    gcs.cb[1] = 1.0;
+  } else if (prob->setSparseJacobianTranspose(1.0, x, wstepv[0], xt) != 0) {
+    return PO_ERR_USER;
+  }
+  std::vector<const double *> P1(sp.P);
+  std::vector<double> a1(sp.alpha.begin(), sp.alpha.begin() + m), c2(m + 2, 0.0);
+  if (!grouped) {
+    P1.push_back(d1v->d);
+    a1.push_back(1.0);
+    P1.push_back(xt->d);
+    a1.push_back(0.0);
+  }
+  const int np1 = (int)P1.size();
+  double diag = 0.0;  // (alpha[0..c) = step.z)
+  PO_TRY(residualCoefs(qn && !seq_lin ? RES_QN : RES_SIGMA, sp.alpha.data(), ptpx.data() + c, k, c2, &diag));
+  c2[m + 1] = 1.0;
+  std::vector<double> so(m + 4, 0.0);
+  // the raw right-hand side lands in y_qn (free while no corrector is active: y_qn is rebuilt from scratch by
+  // computeStepAndUpdate) -- d1v is one of the columns being read -- and the two exchange buffers afterwards.
+  // Of the step only px is stored (store_step 2): the refinement's sparse rows need Aw px as a vector, the bound-
+  // multiplier steps are re-formed from px by the refinement pass (two output streams less)
+  PO_TRY(k_solve2_dots(ctx, {.b = bounds(), .t = tvec->d, .dinv = Dinv->d, .alpha = a1.data(), .coef2 = c2.data(),
+                             .P = P1.data(), .nv = np1, .beta_mu = sp.beta_mu, .tau = sp.tau, .rx = rx->d,
+                             .diag = diag, .n = n, .px = px->d, .pzl = pzl->d, .pzu = pzu->d, .out = so.data(),
+                             .traw = y_qn->d, .store_step = 2, .gcols = grouped ? &gcs : nullptr}));
+  step_flags.px_first_only = true;
+  std::swap(d1v->d, y_qn->d);
+  PO_TRY(minbatch.end());
+  tdots.assign(so.begin(), so.begin() + m);
+  step_flags.tdots_valid = true;
+  step_flags.residual_fused = true;
+  mins_x[0] = so[np1];  // out = {dots[np1], max_x, max_z}
+  mins_x[1] = so[np1 + 1];
+  return PO_OK;
+}
+
+// Correction-panel solve -- taken whenever the panel image of the current system is at hand and the fused first pass is
+// not: K0^-1 (P alpha, 0) comes from the panel, one more column Aw^T wtmp2 rides in the design pass.  first_px_only:
+// the refinement on top of a fused first pass, which re-forms the first bound-multiplier steps from px; when it takes
+// the merit sums it sets fused_merit_valid, w_comp_valid and w_merit_cache_valid, and a lean step clears pz_stored
+// (with step_beta_mu).  Otherwise the stored-step kernel, which sets no flag.
+int InteriorPoint::correctionPanelSolve(const SolvePass &sp, bool refine_pass, bool first_px_only, const double *cl,
+                                        const double *cu, double mins_x[2], double mins_w[2]) {
+  const int m = sp.m;
+  BatchScope minbatch(ctx, false);
+  std::vector<const double *> Uc = correctionPanel(m);
+  PO_TRY(prob->sparseCorrection(Uc.data(), m, sp.alpha.data(), Cw, wtmp2, wyw));  // ... and wyw += wtmp2
+  // the extra column Aw^T wtmp2 (coefficient 1): stored, or (structured problems, refinement of a px-only first
+  // step) described and formed by the pass itself
+  GroupCol gcol;
+  const bool grouped = first_px_only && prob->sparseTransposeColumn(1.0, x, wtmp2, &gcol);
+  if (!grouped && prob->setSparseJacobianTranspose(1.0, x, wtmp2, d1v) != 0) return PO_ERR_USER;
+  std::vector<const double *> P1(sp.P);
+  std::vector<double> a1(sp.alpha.begin(), sp.alpha.begin() + m);
+  if (!grouped) {
+    P1.push_back(d1v->d);
+    a1.push_back(1.0);
+  }
+  minbatch.begin();
+  if (!first_px_only) {
+    PO_TRY(k_solve2(ctx, {.b = bounds(), .t = tvec->d, .dinv = Dinv->d, .alpha = a1.data(), .P = P1.data(),
+                          .nv = m + 1, .beta_mu = sp.beta_mu, .refine = refine_pass ? 1 : 0, .tau = sp.tau, .n = n,
+                          .px = px->d, .pzl = pzl->d, .pzu = pzu->d, .out = mins_x, .rx = rx->d, .cl = cl, .cu = cu}));
+  } else {
+    // Refinement on top of a first step of which only px was stored: solve2r_kernel in its stored right-hand side
+    // form with a ZERO first coefficient set and t1 = px -- it re-forms (pzl, pzu) of the first step from px
+    // (the very expressions the first pass evaluated: same bits), applies the refinement (t2 = tvec, a2) and takes
+    // the complementarity / merit sums of the FINAL step (fused_merit); the final px goes to xt (free during the
+    // solves) and the two buffers are exchanged.  Lean step: (pzl, pzu) are not stored either -- their only
+    // consumer left is the multiplier update of computeStepAndUpdate, which re-forms them (kkt_res_update_kernel)
+    const bool take_merit = forms.fuse_merit && !cl;
+    const bool lean = take_merit && forms.lean_step && lean_step_allowed && iterate_flags.iterate_logs_valid &&
+                      !prob->linear_constraints && options.integer("iterative_refinement_steps") == 1;
+    std::vector<double> azero(m + 1, 0.0);
+    PO_TRY(k_solve2r(ctx, {.b = bounds(), .t1 = px->d, .t2 = tvec->d, .dinv = Dinv->d, .a1 = azero.data(),
+                           .a2 = a1.data(), .P = P1.data(), .nv = (int)P1.size(), .beta_mu = sp.beta_mu,
+                           .tau = sp.tau, .n = n, .px = xt->d, .pzl = lean ? nullptr : pzl->d,
+                           .pzu = lean ? nullptr : pzu->d, .out = mins_x, .g = take_merit ? g->d : nullptr,
+                           .merit_out = take_merit ? fused_merit.as_array() : nullptr,
+                           .gcol = grouped ? &gcol : nullptr, .gc2 = 1.0}));
+    std::swap(px->d, xt->d);
+    if (lean) {
+      step_flags.pz_stored = false;
+      step_beta_mu = sp.beta_mu;
+    }
+    if (take_merit) {
+      // the sparse blocks of the final step, their share of the complementarity polynomial and the sparse merit
+      // sums (at sx = 1) in the same batch: scaleKKTStep and evalMeritInitDeriv then launch nothing
+      PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, 1, sp.tau, wp(), nw, w_step_out, 1));
+      const double *cw = nullptr;
+      PO_TRY(sparseConAtIterate(&cw));
+      PO_TRY(prob->setSparseJacobian(1.0, x, px, wtmp2));
+      PO_TRY(k_w_merit(ctx, wv(), wp(), 1.0, gsw->d, gtw->d, cw, wtmp2->d, nw, w_merit_cache));
+      PO_TRY(minbatch.end());
+      mins_x[0] = fused_merit.max_x;
+      mins_x[1] = fused_merit.max_z;
+      mins_w[0] = w_step_out[3];
+      mins_w[1] = w_step_out[4];
+      for (int i = 0; i < 3; i++) w_comp_poly[i] = w_step_out[i];
+      step_flags.fused_merit_valid = true;
+      step_flags.w_comp_valid = true;
+      step_flags.w_merit_cache_valid = true;
+      return PO_OK;  // (the sparse step was taken above, with its other sums)
+    }
+  }
+  PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, refine_pass ? 1 : 0, sp.tau, wp(), nw, mins_w));
+  return minbatch.end();
+}
+
+// Block-solve fallback -- no panel image at hand (no panel columns, or a problem-supplied solver that keeps none):
+// P alpha is formed as a vector and goes through a second quasi-definite apply.  Sets no flag.
+int InteriorPoint::blockSolveFallback(const SolvePass &sp, bool refine_pass, const double *cl, const double *cu,
+                                      double mins_x[2], double mins_w[2]) {
+  BatchScope minbatch(ctx, false);
+  if (sp.m > 0) PO_TRY(k_panel_axpy(ctx, d1v->d, 0.0, nullptr, 1.0, sp.alpha.data(), sp.P.data(), sp.m, n));
+  PO_TRY(applyK0(d1v->d, wd2->d, tvec, wyw));
+  minbatch.begin();
+  PO_TRY(k_solve2(ctx, {.b = bounds(), .t = tvec->d, .dinv = Dinv->d, .beta_mu = sp.beta_mu,
+                        .refine = refine_pass ? 1 : 0, .tau = sp.tau, .n = n, .px = px->d, .pzl = pzl->d,
+                        .pzu = pzu->d, .out = mins_x, .rx = rx->d, .cl = cl, .cu = cu}));
+  PO_TRY(k_w_step(ctx, wv(), wr(), wyw->d, refine_pass ? 1 : 0, sp.tau, wp(), nw, mins_w));
+  return minbatch.end();
 }
 
 // initLeastSquaresMultipliers (:5366-5534) with the sparse blocks

@@ -1022,25 +1022,27 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-int k_kkt_res(Ctx *c, const Bounds &b, const double *g, const double *const *A, const double *z,
-              int nc, double beta_mu, int64_t n, double *rx, double *out, double *yqn, double beta_mu2,
-              const GroupCol *gcol, double gcoef) {
-  PO_TRY(gcol_check(gcol, n, "k_kkt_res"));
-  if (nc > kMaxPanel) {  // wide A^T z: one collapsed column
+int k_kkt_res(Ctx *c, const KktResArgs &o) {
+  PO_TRY(gcol_check(o.gcol, o.n, "k_kkt_res"));
+  if (o.nc > kMaxPanel) {  // wide A^T z: one collapsed column
     const double *w = nullptr, one = 1.0;
-    PO_TRY(collapse_range(c, 0, z, A, 0, nc, n, &w));
-    return k_kkt_res(c, b, g, &w, &one, 1, beta_mu, n, rx, out, yqn, beta_mu2, gcol, gcoef);
+    PO_TRY(collapse_range(c, 0, o.z, o.A, 0, o.nc, o.n, &w));
+    KktResArgs o1 = o;
+    o1.A = &w;
+    o1.z = &one;
+    o1.nc = 1;
+    return k_kkt_res(c, o1);
   }
-  count_bytes(c, 7 + nc + (yqn ? 2 : 0) - uniform_bound_streams(b), n);
-  const int grid = grid_for(c, n, kBpcPanel);
+  count_bytes(c, 7 + o.nc + (o.yqn ? 2 : 0) - uniform_bound_streams(o.b), o.n);
+  const int grid = grid_for(c, o.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 13));
   PtrTable pt;
   CoefTable ct;
-  fill_tables(z, A, nc, &ct, &pt);
-  if (gcol) count_bytes(c, 1.0, gcol->nwcon);
-  PO_LAUNCH(kkt_res_kernel, grid, b, g, pt, ct, nc, beta_mu, n, rx, yqn, beta_mu2, gcol ? *gcol : GroupCol(), gcoef,
-            c->d_partials);
-  return reduce_finish(c, grid, 8, 0, beta_mu2 >= 0.0 ? 5 : 3, out);
+  fill_tables(o.z, o.A, o.nc, &ct, &pt);
+  if (o.gcol) count_bytes(c, 1.0, o.gcol->nwcon);
+  PO_LAUNCH(kkt_res_kernel, grid, o.b, o.g, pt, ct, o.nc, o.beta_mu, o.n, o.rx, o.yqn, o.beta_mu2,
+            o.gcol ? *o.gcol : GroupCol(), o.gcoef, c->d_partials);
+  return reduce_finish(c, grid, 8, 0, o.beta_mu2 >= 0.0 ? 5 : 3, o.out);
 }
 
 // the mu-dependent part only: sums {comp product, count, -, l1 rzl, l1 rzu, -, l2 rzl, l2 rzu}
@@ -1501,100 +1503,96 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-int k_solve2r(Ctx *c, const Bounds &b, const double *t1, const double *t2, const double *dinv, const double *a1,
-              const double *a2, const double *const *P, int nv, double beta_mu, double tau, int64_t n, double *px,
-              double *pzl, double *pzu, double *va, int nca, double out[2], const double *ar, const double *rx,
-              double diag, int ca0, const double *g, double *merit_out, double dinv_diag, const GroupCol *gcol,
-              double gc1, double gc2) {
-  count_bytes(c, nv + 7 + (t1 ? 2 : 0) + (pzl ? 2 : 0) + (va ? 1 : 0) + (g ? 1 : 0) - uniform_bound_streams(b), n);
-  PO_TRY(gcol_check(gcol, n, "k_solve2r"));
-  if (gcol && t2 == nullptr) {
+int k_solve2r(Ctx *c, const Solve2rArgs &o) {
+  count_bytes(c, o.nv + 7 + (o.t1 ? 2 : 0) + (o.pzl ? 2 : 0) + (o.va ? 1 : 0) + (o.g ? 1 : 0) - uniform_bound_streams(o.b),
+              o.n);
+  PO_TRY(gcol_check(o.gcol, o.n, "k_solve2r"));
+  if (o.gcol && o.t2 == nullptr) {
     set_error("k_solve2r: a grouped column is only taken in the stored right-hand side form");
     return PO_ERR_ARG;
   }
-  if (gcol) count_bytes(c, 1.0, gcol->nwcon);
-  const GroupCol gcv = gcol ? *gcol : GroupCol();
-  if (!t1 && (t2 != nullptr || !rx)) {
+  if (o.gcol) count_bytes(c, 1.0, o.gcol->nwcon);
+  const GroupCol gcv = o.gcol ? *o.gcol : GroupCol();
+  if (!o.t1 && (o.t2 != nullptr || !o.rx)) {
     set_error("k_solve2r: Dinv / t can only be re-formed in the recomputed right-hand side form");
     return PO_ERR_ARG;
   }
-  if (nv > kMaxPanel) {
-    set_error("panel of %d vectors exceeds kMaxPanel=%d", nv, kMaxPanel);
+  if (o.nv > kMaxPanel) {
+    set_error("panel of %d vectors exceeds kMaxPanel=%d", o.nv, kMaxPanel);
     return PO_ERR_ARG;
   }
-  const int grid = grid_for(c, n, kBpcPanel);
+  const int grid = grid_for(c, o.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 10));
   PtrTable pt;
   CoefTable ct1, ct2, ctr;
-  fill_tables(a1, P, nv, &ct1, &pt);
-  fill_tables(a2, P, nv, &ct2, &pt);
-  fill_tables(ar, P, nv, &ctr, &pt);
-  if (t2 != nullptr && ca0 != 0) {
+  fill_tables(o.a1, o.P, o.nv, &ct1, &pt);
+  fill_tables(o.a2, o.P, o.nv, &ct2, &pt);
+  fill_tables(o.ar, o.P, o.nv, &ctr, &pt);
+  if (o.t2 != nullptr && o.ca0 != 0) {
     set_error("k_solve2r: the stored right-hand side form expects the constraint columns first");
     return PO_ERR_ARG;
   }
-  if (t2 == nullptr) {
-    if (!ar || !rx) {
+  if (o.t2 == nullptr) {
+    if (!o.ar || !o.rx) {
       set_error("k_solve2r: neither the refinement right-hand side nor the data to recompute it");
       return PO_ERR_ARG;
     }
-    if (g && merit_out) {
-      PO_LAUNCH((solve2r_kernel<1, 1>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px,
-                pzl, pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+    if (o.g && o.merit_out) {
+      PO_LAUNCH((solve2r_kernel<1, 1>), grid, o.b, o.t1, o.t2, o.dinv, ct1, ct2, ctr, pt, o.nv, o.beta_mu, o.tau, o.rx,
+                o.diag, o.n, o.px, o.pzl, o.pzu, o.va, o.nca, o.ca0, o.g, o.dinv_diag, gcv, o.gc1, o.gc2, c->d_partials);
       // {7 sums, 2 minima, 1 maximum} land in merit_out[0..10); the minima are copied to `out` by the caller's hook
-      (void)out;
-      return reduce_finish(c, grid, 7, 2, 1, merit_out);
+      return reduce_finish(c, grid, 7, 2, 1, o.merit_out);
     }
-    PO_LAUNCH((solve2r_kernel<1, 0>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
-  } else if (g && merit_out) {
-    PO_LAUNCH((solve2r_kernel<0, 1>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
-    (void)out;
-    return reduce_finish(c, grid, 7, 2, 1, merit_out);
+    PO_LAUNCH((solve2r_kernel<1, 0>), grid, o.b, o.t1, o.t2, o.dinv, ct1, ct2, ctr, pt, o.nv, o.beta_mu, o.tau, o.rx,
+              o.diag, o.n, o.px, o.pzl, o.pzu, o.va, o.nca, o.ca0, o.g, o.dinv_diag, gcv, o.gc1, o.gc2, c->d_partials);
+  } else if (o.g && o.merit_out) {
+    PO_LAUNCH((solve2r_kernel<0, 1>), grid, o.b, o.t1, o.t2, o.dinv, ct1, ct2, ctr, pt, o.nv, o.beta_mu, o.tau, o.rx,
+              o.diag, o.n, o.px, o.pzl, o.pzu, o.va, o.nca, o.ca0, o.g, o.dinv_diag, gcv, o.gc1, o.gc2, c->d_partials);
+    return reduce_finish(c, grid, 7, 2, 1, o.merit_out);
   } else {
-    PO_LAUNCH((solve2r_kernel<0, 0>), grid, b, t1, t2, dinv, ct1, ct2, ctr, pt, nv, beta_mu, tau, rx, diag, n, px, pzl,
-              pzu, va, nca, ca0, g, dinv_diag, gcv, gc1, gc2, c->d_partials);
+    PO_LAUNCH((solve2r_kernel<0, 0>), grid, o.b, o.t1, o.t2, o.dinv, ct1, ct2, ctr, pt, o.nv, o.beta_mu, o.tau, o.rx,
+              o.diag, o.n, o.px, o.pzl, o.pzu, o.va, o.nca, o.ca0, o.g, o.dinv_diag, gcv, o.gc1, o.gc2, c->d_partials);
   }
-  return reduce_finish(c, grid, 0, 2, 0, out);
+  return reduce_finish(c, grid, 0, 2, 0, o.out);
 }
 
-int k_solve2(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-             const double *const *P, int nv, double beta_mu, int refine, double tau, int64_t n,
-             double *px, double *pzl, double *pzu, double out[2], const double *coef2,
-             const double *rx, double diag, double *tout, double *va, int nca, const double *cl,
-             const double *cu) {
-  count_bytes(c, nv + 10 + (refine ? 3 : 0) + (va ? (refine ? 2 : 1) : 0) + (coef2 ? 2 : 0) + (cl ? 2 : 0) - uniform_bound_streams(b), n);
-  if (nv > kMaxPanel) {
-    if (coef2) {
-      set_error("k_solve2: the fused refinement residual is not available for a panel of %d (> %d) columns", nv,
+int k_solve2(Ctx *c, const Solve2Args &o) {
+  count_bytes(c, o.nv + 10 + (o.refine ? 3 : 0) + (o.va ? (o.refine ? 2 : 1) : 0) + (o.coef2 ? 2 : 0) + (o.cl ? 2 : 0) -
+                     uniform_bound_streams(o.b), o.n);
+  if (o.nv > kMaxPanel) {
+    if (o.coef2) {
+      set_error("k_solve2: the fused refinement residual is not available for a panel of %d (> %d) columns", o.nv,
                 kMaxPanel);
       return PO_ERR_ARG;
     }
     const double *P2[2] = {nullptr, nullptr};
     double a2[2] = {0.0, 0.0};
     int nv2 = 0, nca2 = 0;
-    PO_TRY(collapse_panel(c, alpha, P, nv, va ? nca : 0, n, P2, a2, &nv2, &nca2));
-    return k_solve2(c, b, t, dinv, a2, P2, nv2, beta_mu, refine, tau, n, px, pzl, pzu, out, nullptr, rx, diag, tout, va,
-                    nca2, cl, cu);
+    PO_TRY(collapse_panel(c, o.alpha, o.P, o.nv, o.va ? o.nca : 0, o.n, P2, a2, &nv2, &nca2));
+    Solve2Args o1 = o;
+    o1.alpha = a2;
+    o1.P = P2;
+    o1.nv = nv2;
+    o1.nca = nca2;
+    return k_solve2(c, o1);
   }
-  const int grid = grid_for(c, n, kBpcPanel);
+  const int grid = grid_for(c, o.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 2));
   PtrTable pt;
   CoefTable ct, ct2;
-  fill_tables(alpha, P, nv, &ct, &pt);
-  fill_tables(coef2, P, nv, &ct2, &pt);
-  if (refine) {
-    PO_LAUNCH((solve2_kernel<1, 0>), grid, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, px,
-              pzl, pzu, tout, va, nca, cl, cu, c->d_partials);
-  } else if (coef2) {
-    PO_LAUNCH((solve2_kernel<0, 1>), grid, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, px,
-              pzl, pzu, tout, va, nca, cl, cu, c->d_partials);
+  fill_tables(o.alpha, o.P, o.nv, &ct, &pt);
+  fill_tables(o.coef2, o.P, o.nv, &ct2, &pt);
+  if (o.refine) {
+    PO_LAUNCH((solve2_kernel<1, 0>), grid, o.b, o.t, o.dinv, ct, ct2, pt, o.nv, o.beta_mu, o.tau, o.rx, o.diag, o.n, o.px, o.pzl,
+              o.pzu, o.tout, o.va, o.nca, o.cl, o.cu, c->d_partials);
+  } else if (o.coef2) {
+    PO_LAUNCH((solve2_kernel<0, 1>), grid, o.b, o.t, o.dinv, ct, ct2, pt, o.nv, o.beta_mu, o.tau, o.rx, o.diag, o.n, o.px, o.pzl,
+              o.pzu, o.tout, o.va, o.nca, o.cl, o.cu, c->d_partials);
   } else {
-    PO_LAUNCH((solve2_kernel<0, 0>), grid, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, px,
-              pzl, pzu, tout, va, nca, cl, cu, c->d_partials);
+    PO_LAUNCH((solve2_kernel<0, 0>), grid, o.b, o.t, o.dinv, ct, ct2, pt, o.nv, o.beta_mu, o.tau, o.rx, o.diag, o.n, o.px, o.pzl,
+              o.pzu, o.tout, o.va, o.nca, o.cl, o.cu, c->d_partials);
   }
-  return reduce_finish(c, grid, 0, 2, 0, out);
+  return reduce_finish(c, grid, 0, 2, 0, o.out);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1845,31 +1843,29 @@ static int solve2_dots_launch(Ctx *c, int grid_cap, const Bounds &b, const doubl
 #define PO_S2D_CASE(NP)                                                                                    \
   case NP: {                                                                                               \
     constexpr int OD = NP <= 8 ? 3 : (NP <= 16 ? 2 : 1);                                                   \
-    PO_TRY((solve2_dots_launch<NP, OD>(c, 0, b, t, dinv, ct, ct2, pt, nv, beta_mu, tau, rx, diag, n, ntiles, px, pzl, \
-                                       pzu, tout, va, nca, traw, store_step, ca0, dinv_diag, &grid, gcs)));  \
+    PO_TRY((solve2_dots_launch<NP, OD>(c, 0, o.b, o.t, o.dinv, ct, ct2, pt, o.nv, o.beta_mu, o.tau, o.rx, o.diag, o.n,  \
+                                       ntiles, o.px, o.pzl, o.pzu, o.tout, o.va, o.nca, o.traw, o.store_step, o.ca0, \
+                                       o.dinv_diag, &grid, gcs)));                                         \
   } break;
 
 // out = {dots[nv] = P^T t', max_x, max_z}
-int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-                  const double *coef2, const double *const *P, int nv, double beta_mu, double tau,
-                  const double *rx, double diag, int64_t n, double *px, double *pzl, double *pzu,
-                  double *tout, double *va, int nca, double *out, double *traw, int store_step, int ca0,
-                  double dinv_diag, const GroupCols2 *gcols) {
-  count_bytes(c, nv + 6 + (t ? 2 : 0) + (store_step == 1 ? 3 + (va ? 1 : 0) : (store_step == 2 ? 1 : 0)) + ((traw || tout) ? 1 : 0) - uniform_bound_streams(b), n);
-  const GroupCols2 gcs = gcols ? *gcols : GroupCols2();
-  for (int e = 0; e < gcs.count; e++) PO_TRY(gcol_check(&gcs.g[e], n, "k_solve2_dots"));
+int k_solve2_dots(Ctx *c, const Solve2DotsArgs &o) {
+  count_bytes(c, o.nv + 6 + (o.t ? 2 : 0) + (o.store_step == 1 ? 3 + (o.va ? 1 : 0) : (o.store_step == 2 ? 1 : 0)) +
+                     ((o.traw || o.tout) ? 1 : 0) - uniform_bound_streams(o.b), o.n);
+  const GroupCols2 gcs = o.gcols ? *o.gcols : GroupCols2();
+  for (int e = 0; e < gcs.count; e++) PO_TRY(gcol_check(&gcs.g[e], o.n, "k_solve2_dots"));
   for (int e = 0; e < gcs.count; e++) count_bytes(c, 1.0, gcs.g[e].nwcon);
-  if (nv > kMaxPanel || nv < 1) {
-    set_error("panel of %d vectors outside 1..%d", nv, kMaxPanel);
+  if (o.nv > kMaxPanel || o.nv < 1) {
+    set_error("panel of %d vectors outside 1..%d", o.nv, kMaxPanel);
     return PO_ERR_ARG;
   }
-  const int64_t ntiles = (((n + 1) >> 1) + 63) / 64;
+  const int64_t ntiles = (((o.n + 1) >> 1) + 63) / 64;
   int grid = 0;
   PtrTable pt;
   CoefTable ct, ct2;
-  fill_tables(alpha, P, nv, &ct, &pt);
-  fill_tables(coef2, P, nv, &ct2, &pt);
-  const int need = (nv + 3) / 4;
+  fill_tables(o.alpha, o.P, o.nv, &ct, &pt);
+  fill_tables(o.coef2, o.P, o.nv, &ct2, &pt);
+  const int need = (o.nv + 3) / 4;
   // (column slots per wave: a slot beyond the panel re-reads column 0 with a zero coefficient -- no HBM traffic, but a
   // load per tile all the same: 2 and 6 slots for the narrow panels of configs 5 and 4 instead of 4 and 8; same
   // workgroups per CU, so the same grid and the same bits)
@@ -1879,7 +1875,7 @@ int k_solve2_dots(Ctx *c, const Bounds &b, const double *t, const double *dinv, 
     PO_S2D_CASE(2) PO_S2D_CASE(4) PO_S2D_CASE(6) PO_S2D_CASE(8) PO_S2D_CASE(11) PO_S2D_CASE(12) PO_S2D_CASE(16)
     PO_S2D_CASE(20) PO_S2D_CASE(24)
   }
-  return reduce_finish(c, grid, nv, 2, 0, out);
+  return reduce_finish(c, grid, o.nv, 2, 0, o.out);
 }
 
 // stand-alone refinement residual (second and later refinement steps, or when the fused form of
@@ -2175,22 +2171,20 @@ __global__ void __launch_bounds__(kBlock)
   block_reduce_store<2, OP_MIN>(mins, partials, 9, sm);
   block_reduce_store<1, OP_MAX>(mx, partials, 11, sm);
 }
-int k_solve2c(Ctx *c, const Bounds &b, const double *t, const double *dinv, const double *alpha,
-              const double *const *P, int nv, double beta_mu, double tau, int64_t n, double *px, double *pzl,
-              double *pzu, double *va, int nca, const double *g, int want_logs, double out[12]) {
-  if (nv > kMaxPanel) {
-    set_error("k_solve2c: panel of %d vectors exceeds kMaxPanel=%d", nv, kMaxPanel);
+int k_solve2c(Ctx *c, const Solve2cArgs &o) {
+  if (o.nv > kMaxPanel) {
+    set_error("k_solve2c: panel of %d vectors exceeds kMaxPanel=%d", o.nv, kMaxPanel);
     return PO_ERR_ARG;
   }
-  count_bytes(c, nv + 14 + (va ? 1 : 0) - uniform_bound_streams(b), n);
-  const int grid = grid_for(c, n);  // comp_merit_kernel's grid
+  count_bytes(c, o.nv + 14 + (o.va ? 1 : 0) - uniform_bound_streams(o.b), o.n);
+  const int grid = grid_for(c, o.n);  // comp_merit_kernel's grid
   PO_TRY(ensure_partials(c, (size_t)grid * 12));
   PtrTable pt;
   CoefTable ct;
-  fill_tables(alpha, P, nv, &ct, &pt);
-  PO_LAUNCH(solve2c_kernel, grid, b, t, dinv, ct, pt, nv, beta_mu, tau, n, px, pzl, pzu, va, nca, g, want_logs,
-            c->d_partials);
-  return reduce_finish(c, grid, 9, 2, 1, out);
+  fill_tables(o.alpha, o.P, o.nv, &ct, &pt);
+  PO_LAUNCH(solve2c_kernel, grid, o.b, o.t, o.dinv, ct, pt, o.nv, o.beta_mu, o.tau, o.n, o.px, o.pzl, o.pzu, o.va, o.nca, o.g,
+            o.want_logs, c->d_partials);
+  return reduce_finish(c, grid, 9, 2, 1, o.out);
 }
 
 __device__ __forceinline__ double clamp_elem(double v, bool has_l, double lb, bool has_u, double ub,
@@ -2464,34 +2458,34 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-int k_kkt_res_update(Ctx *c, const Bounds &b, const double *g, const double *const *A, const double *z, int nc,
-                     double beta_mu, int64_t n, double *rx, double *out, double *yqn, double *zl,
-                     const double *pzl, double *zu, const double *pzu, double a, double eps, const double *va,
-                     double az, double *acz, double az_acz, const double *pxs, const double *xold,
-                     double beta_mu_step, double beta_mu2, const GroupCol *gcol, double gcoef, double *dinv_out,
-                     double *t_out, double spec_diag, double spec_beta_mu) {
-  PO_TRY(gcol_check(gcol, n, "k_kkt_res_update"));
-  if (acz && gcol) {
+int k_kkt_res_update(Ctx *c, const KktResArgs &o) {
+  const KktResArgs::Update &u = o.update;
+  PO_TRY(gcol_check(o.gcol, o.n, "k_kkt_res_update"));
+  if (u.acz && o.gcol) {
     set_error("kkt_res_update: a grouped column cannot follow the A^T z vector of the linear-constraint mode");
     return PO_ERR_ARG;
   }
-  if (nc > kMaxPanel) {
+  if (o.nc > kMaxPanel) {
     const double *w = nullptr, one = 1.0;
-    PO_TRY(collapse_range(c, 0, z, A, 0, nc, n, &w));
-    return k_kkt_res_update(c, b, g, &w, &one, 1, beta_mu, n, rx, out, yqn, zl, pzl, zu, pzu, a, eps, va, az, acz, az_acz,
-                            pxs, xold, beta_mu_step, beta_mu2, gcol, gcoef, dinv_out, t_out, spec_diag, spec_beta_mu);
+    PO_TRY(collapse_range(c, 0, o.z, o.A, 0, o.nc, o.n, &w));
+    KktResArgs o1 = o;
+    o1.A = &w;
+    o1.z = &one;
+    o1.nc = 1;
+    return k_kkt_res_update(c, o1);
   }
-  count_bytes(c, (yqn ? 14 : 11) + (acz ? (az_acz != 0.0 ? 2 : 1) : nc) + (dinv_out ? 2 : 0) - uniform_bound_streams(b), n);
-  const int grid = grid_for(c, n, kBpcPanel);
+  count_bytes(c, (o.yqn ? 14 : 11) + (u.acz ? (u.az_acz != 0.0 ? 2 : 1) : o.nc) + (u.dinv_out ? 2 : 0) -
+                     uniform_bound_streams(o.b), o.n);
+  const int grid = grid_for(c, o.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 13));
   PtrTable pt;
   CoefTable ct;
-  fill_tables(z, A, nc, &ct, &pt);
-  if (gcol) count_bytes(c, 1.0, gcol->nwcon);
-  PO_LAUNCH(kkt_res_update_kernel, grid, b, g, pt, ct, nc, beta_mu, n, rx, yqn, zl, pzl, zu, pzu, a, eps, va, az, acz,
-            az_acz, pxs, xold, beta_mu_step, beta_mu2, gcol ? *gcol : GroupCol(), gcoef, dinv_out, t_out, spec_diag,
-            spec_beta_mu, c->d_partials);
-  return reduce_finish(c, grid, 8, 0, beta_mu2 >= 0.0 ? 5 : 3, out);
+  fill_tables(o.z, o.A, o.nc, &ct, &pt);
+  if (o.gcol) count_bytes(c, 1.0, o.gcol->nwcon);
+  PO_LAUNCH(kkt_res_update_kernel, grid, o.b, o.g, pt, ct, o.nc, o.beta_mu, o.n, o.rx, o.yqn, u.zl, u.pzl, u.zu, u.pzu, u.a,
+            u.eps, u.va, u.az, u.acz, u.az_acz, u.pxs, u.xold, u.beta_mu_step, o.beta_mu2, o.gcol ? *o.gcol : GroupCol(),
+            o.gcoef, u.dinv_out, u.t_out, u.spec_diag, u.spec_beta_mu, c->d_partials);
+  return reduce_finish(c, grid, 8, 0, o.beta_mu2 >= 0.0 ? 5 : 3, o.out);
 }
 
 __global__ void __launch_bounds__(kBlock)

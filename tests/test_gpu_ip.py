@@ -1271,3 +1271,41 @@ def test_dinv_and_rhs_left_by_the_residual_pass_keep_every_bit(ctx, case):
         np.testing.assert_array_equal(va, vb)
     table = lambda h: [ln for ln in h.splitlines() if ln[:5].strip().isdigit()]  # noqa: E731
     assert len(table(a[5])) >= 8 and table(a[5]) == table(b[5])
+
+
+# The four bench shapes at n = 2001, each a fixed-length solve (abs_res_tol out of reach).  launches / syncs: what
+# optimize() adds to Context.counters() -- taken with tools/ip_digest.py from the library of the commit BEFORE the host
+# code of the solve passes was restructured (profiles/r15_ip_digest_parent.jsonl), not from the build under
+# test: a restructuring of the host code may not add, drop or reorder a launch or a host round trip.
+_FIXED = {"abs_res_tol": 1e-30, "start_affine_multiplier_min": 0.01, "max_major_iters": 12}
+ON_RECORD = {
+    "config2": dict(ip=dict(problem="quadratic", n=2001, c=8, wt=None,
+                            opts=dict(_FIXED, qn_type="bfgs", qn_subspace_size=20)), launches=245, syncs=72),
+    "config3": dict(ip=dict(problem="convex", n=2001, c=32, wt=None,
+                            opts=dict(_FIXED, qn_type="sr1", qn_subspace_size=10)), launches=241, syncs=71),
+    "config4": dict(ip=dict(problem="convex", n=2001, c=4, wt=(100, 20, 0, 0, 100),
+                            opts=dict(_FIXED, qn_type="bfgs", qn_subspace_size=10)), launches=548, syncs=90),
+    "config5": dict(tr=dict(problem="quadratic", n=2001, c=4, eig=(10, 0, 0, 2.0),
+                            opts={"qn_subspace_size": 10, "tr_max_iterations": 4, "max_major_iters": 200}),
+                    launches=3709, syncs=1368),
+}
+
+
+@pytest.mark.parametrize("name", sorted(ON_RECORD))
+def test_launches_and_syncs_of_the_configurations_on_record(ctx, name):
+    import paropt_amd as pa
+
+    rec = ON_RECORD[name]
+    a = rec.get("ip") or rec["tr"]
+    prob = pa.SeparableProblem(ctx, a["problem"], a["n"], a["c"])
+    if "tr" in rec:
+        solver = pa.TrustRegion(prob, a["opts"])
+        solver.setEigenModelSynthetic(*a["eig"])
+    else:
+        if a["wt"]:
+            prob.setWeighting(*a["wt"])
+        solver = pa.InteriorPoint(prob, dict(a["opts"], write_output_frequency=0))
+    syncs0, launches0 = ctx.counters()
+    solver.optimize()
+    syncs1, launches1 = ctx.counters()
+    assert (launches1 - launches0, syncs1 - syncs0) == (rec["launches"], rec["syncs"])
