@@ -644,6 +644,13 @@ int po_bench_mma_dual(po_ctx ctx, int64_t n, int m, int form, int reps, double *
  * of each: pass_ms2[2], rho_ms2[2]; ceiling_ms is the trivial kernel of the rho form's mix. */
 int po_bench_mma_dual_rho(po_ctx ctx, int64_t n, int m, int form, int reps, double *pass_ms2, double *rho_ms2,
                           double *gram_ms, double *ceiling_ms);
+/* One evaluation of the dual with linearised constraints (see po_mma_dual_linear_eval) at size n with m constraints,
+ * on synthetic data, beside the trivial kernel of its stream mix (m + 8 streams in, 1 out; form 2 one more out).
+ * warm_ms: every root search starts from the point the call before left (an evaluation inside a solve); cold_ms: from
+ * the expansion point (the first evaluation of a solve).  gram_ms as in po_bench_mma_dual, not part of either.
+ * steps[2] (may be NULL): the most evaluations one root search took, warm and cold. */
+int po_bench_mma_dual_linear(po_ctx ctx, int64_t n, int m, int form, int reps, double *warm_ms, double *cold_ms,
+                             double *gram_ms, double *ceiling_ms, double *steps);
 
 /* ---- ParOptTrustRegion over the quadratic / compact-eigenvalue subproblem ------------------------
  * src/ParOptTrustRegion.h:376-480, set up as ParOptOptimizer does for algorithm = "tr"
@@ -894,6 +901,35 @@ int po_mma_gcmma_group_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha
                              int64_t start, int skip, double a, po_vec c, int64_t nwinequality, double gamma,
                              po_vec xk, const double *rho, po_vec x, po_vec zl, po_vec zu, po_vec zw, double *sums,
                              double *stats);
+/* mma_dual_linearized_constraints = newton (default refuse; no counterpart in the reference): with
+ * mma_use_constraint_linearization = 1 the subproblem of src/ParOptMMA.cpp:804-924 -- the objective's rational
+ * approximation and the constraints c_i(x) = cons_i + A_i . (x - xk) >= 0, = 0 for the dense equalities behind the
+ * ninequality inequalities -- is solved through its dual.  With t = sum_i lambda_i A_i the element-wise minimiser is
+ * the root of p0 u^2 - q0 l^2 = t clamped into [alpha, beta] (a bracketed Newton iteration per element, at most 100
+ * steps), lambda_i in [0, penalty_gamma] and [-penalty_gamma, penalty_gamma].  mma_globalization = conservative and any
+ * sparse constraints stay PO_ERR_ARG in this mode, and so does po_mma_get_subproblem: the solver holds no p_i, q_i.
+ *
+ * The dual function stand-alone on caller vectors: W, grad[m] = -c(x(lambda)) and, when hess != NULL, hess[m * m] =
+ * minus the Hessian at lambda[m].  form as in po_mma_dual_eval (2: the weighted Gram runs over the A_i themselves).
+ * xstart_inout holds the starts of the root searches on entry (an entry outside (alpha, beta) restarts from the
+ * midpoint) and x(lambda) on return.  x, zl, zu (all three or none): also the point pass at lambda, started from
+ * xstart_inout, with zl = max(r, 0) where x = alpha, zu = max(-r, 0) where x = beta, r = p0 u^2 - q0 l^2 - t.
+ * stats (may be NULL) receives {searches that ran into the step cap, most evaluations one search took}. */
+int po_mma_dual_linear_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                            const po_vec *A, const double *cons, po_vec xk, const double *lambda, int form,
+                            po_vec xstart_inout, double *W, double *grad, double *hess, po_vec x, po_vec zl,
+                            po_vec zu, double *stats);
+/* Over every pass of this solver in that mode: element root searches that ran into their step cap (never taken as
+ * converged silently: a non-zero count says so) and the most evaluations one search took.  Any pointer may be NULL. */
+int po_mma_get_dual_linear_stats(po_mma mma, long *cap_hits, int *max_steps);
+/* The CURRENT linearised subproblem (initializeSubProblem .cpp:523-757): borrowed handles of the move limits, the
+ * objective's coefficients, the ncon constraint gradients A_i and the expansion point xk, and cons[ncon]; A points at
+ * an array of ncon handles owned by the object.  Inside the iteration callback of MMA iteration k >= 1 the move
+ * limits, p0, q0 and the asymptotes still describe subproblem k - 1 (as in po_mma_get_subproblem), while A, cons and
+ * xk are already those of subproblem k: the pieces of subproblem k - 1 that the new point replaces are the ones
+ * callback k - 1 saw.  Works in every mode.  Any pointer may be NULL. */
+int po_mma_get_linear_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **A,
+                                 const double **cons, po_vec *xk);
 
 #ifdef __cplusplus
 }

@@ -2319,6 +2319,27 @@ class MMA(_Driver):
                     b=np.array([b[i] for i in range(c)]))
 
 
+    def getDualLinearStats(self):
+        """Of mma_dual_linearized_constraints='newton' (po_mma_get_dual_linear_stats), over every pass of this solver:
+        element root searches that ran into their step cap, and the most evaluations one search took."""
+        cap, mx = C.c_long(), C.c_int()
+        check(lib.po_mma_get_dual_linear_stats(self._h, C.byref(cap), C.byref(mx)))
+        return dict(cap_hits=cap.value, max_steps=mx.value)
+
+    def getLinearSubproblem(self):
+        """Borrowed views of the current linearised subproblem (po_mma_get_linear_subproblem): dict with alpha, beta,
+        p0, q0, xk (PVec), A (list of ncon PVec) and cons (numpy copy).  Inside the iteration callback of iteration k
+        the move limits and p0, q0 still describe subproblem k - 1; A, cons and xk are already those of subproblem k."""
+        al, be, p0, q0, xk = L.po_vec(), L.po_vec(), L.po_vec(), L.po_vec(), L.po_vec()
+        aa, cons = C.POINTER(L.po_vec)(), L.c_double_p()
+        check(lib.po_mma_get_linear_subproblem(self._h, C.byref(al), C.byref(be), C.byref(p0), C.byref(q0),
+                                               C.byref(aa), C.byref(cons), C.byref(xk)))
+        c = self.problem.ncon
+        wrap = lambda h: PVec(self.ctx, handle=L.po_vec(h), owned=False)  # noqa: E731
+        return dict(alpha=wrap(al.value), beta=wrap(be.value), p0=wrap(p0.value), q0=wrap(q0.value),
+                    xk=wrap(xk.value), A=[wrap(aa[i]) for i in range(c)], cons=np.array([cons[i] for i in range(c)]))
+
+
 def _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, who=""):
     """m and the (ctx, m, L, U, alpha, beta, p0, q0, p[], q[]) head of the po_mma_dual_eval family's arguments."""
     m = len(p)
@@ -2373,6 +2394,30 @@ def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hes
                                    g.ctypes.data_as(L.c_double_p),
                                    H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, C.byref(D)))
     return W.value, g[:m], H, D.value
+
+
+def mma_dual_linear_eval(ctx, Lo, Up, alpha, beta, p0, q0, A, cons, xk, lam, xstart, form=0, hessian=True, point=None):
+    """The dual function of an MMA subproblem with linearised constraints c_i = cons_i + A_i . (x - xk), given by caller
+    vectors (po_mma_dual_linear_eval): returns (W, grad, H, stats) with H = minus the Hessian (None unless `hessian`)
+    and stats = dict(cap_hits, max_steps) of the element root searches.  xstart (PVec) holds their starts on entry and
+    x(lam) on return.  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu) PVecs: also filled with the
+    primal point and its bound multipliers at lam."""
+    m = len(A)
+    (ca, cp), (la, lp) = _f64(cons), _f64(lam)
+    if ca.size != m or la.size != m:
+        raise ValueError("mma_dual_linear_eval: cons and lam must hold one entry per constraint")
+    cols = (L.po_vec * max(m, 1))(*[v.handle for v in A])
+    W = C.c_double()
+    g = np.zeros(max(m, 1))
+    H = np.zeros((m, m)) if hessian else None
+    st = np.zeros(2)
+    xs = [v.handle for v in point] if point is not None else [None, None, None]
+    check(lib.po_mma_dual_linear_eval(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle,
+                                      q0.handle, cols, cp, xk.handle, lp, int(form), xstart.handle, C.byref(W),
+                                      g.ctypes.data_as(L.c_double_p),
+                                      H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1],
+                                      xs[2], st.ctypes.data_as(L.c_double_p)))
+    return W.value, g[:m], H, dict(cap_hits=int(st[0]), max_steps=int(st[1]))
 
 
 def mma_dual_group_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, nwcon, nw, start, skip, a, c, nwinequality,
@@ -2532,6 +2577,17 @@ def bench_mma_dual(ctx, n, m, form, reps=5):
     a, g, b = C.c_double(), C.c_double(), C.c_double()
     check(lib.po_bench_mma_dual(ctx.handle, int(n), int(m), int(form), int(reps), C.byref(a), C.byref(g), C.byref(b)))
     return a.value, g.value, b.value
+
+
+def bench_mma_dual_linear(ctx, n, m, form, reps=5):
+    """The dual pass with linearised constraints on synthetic data (po_bench_mma_dual_linear): (warm ms, cold ms,
+    gram ms, ceiling ms, [most root-search evaluations warm, cold]); warm starts every root search from the point of
+    the call before, cold from the expansion point."""
+    w, c, g, b = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    st = (C.c_double * 2)()
+    check(lib.po_bench_mma_dual_linear(ctx.handle, int(n), int(m), int(form), int(reps), C.byref(w), C.byref(c),
+                                       C.byref(g), C.byref(b), st))
+    return w.value, c.value, g.value, b.value, [int(st[0]), int(st[1])]
 
 
 def bench_mma_dual_rho(ctx, n, m, form, reps=5):

@@ -655,3 +655,87 @@ extern "C" int po_bench_mma_dual_rho(po_ctx ctx, int64_t n, int m, int form, int
   }
   return bench_mma_dual("po_bench_mma_dual_rho", ctx, n, m, form, reps, pass_ms2, rho_ms2, gram_ms, ceiling_ms);
 }
+
+// po_bench_mma_dual_linear: one evaluation of the dual with linearised constraints (k_mma_dual_linear, mma.hip) at
+// (n, m) beside the trivial kernel of its stream mix -- m + 8 streams in and one out, the panel form one more out.
+// warm: the root searches start from the point of the call before (they confirm it); cold: from the expansion point.
+extern "C" int po_bench_mma_dual_linear(po_ctx ctx, int64_t n, int m, int form, int reps, double *warm_ms,
+                                        double *cold_ms, double *gram_ms, double *ceiling_ms, double *steps) {
+  if (!ctx || !warm_ms || !cold_ms || !gram_ms || !ceiling_ms || n < 2 || reps < 1 || m < 1 || m > kMmaDualMax ||
+      (form != 1 && form != 2) || (form == 1 && m > kMmaDualFused)) {
+    set_error("po_bench_mma_dual_linear: n >= 2, reps >= 1, 1 <= m <= %d, form 1 (m <= %d) or 2", kMmaDualMax,
+              kMmaDualFused);
+    return PO_ERR_ARG;
+  }
+  Ctx *cx = ctx;
+  std::vector<Vec *> all;
+  auto mk = [&](uint64_t aid, double scale, double shift) -> double * {
+    Vec *v = vec_new(cx, n);
+    if (!v) return nullptr;
+    all.push_back(v);
+    (void)k_fill_hash(cx, v->d, n, 13, aid, 0, scale, shift);
+    return v->d;
+  };
+  double *sink = nullptr;
+  auto body = [&]() -> int {
+    PO_HIP(hipMalloc((void **)&sink, 64));
+    // the move limits and coefficients of po_bench_mma_dual; xk in (-0.5, 0.5); A_i in (-0.1, 0.1), lambda = 1: free
+    // and clamped elements both occur
+    double *L = mk(1, 1.0, -3.0), *U = mk(2, 1.0, 2.0), *al = mk(3, 0.5, -1.0), *be = mk(4, 0.5, 0.5);
+    double *p0 = mk(5, 1.0, 0.01), *q0 = mk(6, 1.0, 0.01), *xk = mk(7, 1.0, -0.5), *x = mk(8, 0.0, 0.0);
+    if (!L || !U || !al || !be || !p0 || !q0 || !xk || !x) return PO_ERR_HIP;
+    std::vector<const double *> A;
+    for (int i = 0; i < m; i++) {
+      const double *a = mk(100 + i, 0.2, -0.1);
+      if (!a) return PO_ERR_HIP;
+      A.push_back(a);
+    }
+    double *dvec = nullptr;
+    if (form == 2 && !(dvec = mk(700, 0.0, 0.0))) return PO_ERR_HIP;
+    std::vector<double> cons(m, -1.0), lam(m, 1.0), grad(m), H((size_t)m * m);
+    const MmaDualLinear s{L, U, al, be, p0, q0, xk, A.data(), cons.data(), m, n};
+    ApiTimer T{cx, "", reps};
+    double W = 0.0, ms0 = 0.0;
+    MmaLinearStats warm, cold;
+    PO_TRY(T.time([&] { return k_mma_dual_linear(cx, s, lam.data(), form, xk, x, &W, grad.data(), H.data(), dvec, &cold); },
+                  cold_ms));
+    PO_TRY(T.time([&] {
+      warm = MmaLinearStats();
+      return k_mma_dual_linear(cx, s, lam.data(), form, x, x, &W, grad.data(), H.data(), dvec, &warm);
+    }, warm_ms));
+    if (steps) {
+      steps[0] = warm.max_steps;
+      steps[1] = cold.max_steps;
+    }
+    *gram_ms = 0.0;
+    if (form == 2) {  // the Gram alone; the pass is the difference
+      PO_TRY(T.time([&] { return k_wgram(cx, dvec, A.data(), m, n, H.data()); }, &ms0));
+      *gram_ms = ms0;
+      *warm_ms -= ms0;
+      *cold_ms -= ms0;
+    }
+    MixTableRt P;
+    int nin = 0, nout = 0;
+    for (const double *v : {(const double *)L, (const double *)U, (const double *)al, (const double *)be,
+                            (const double *)p0, (const double *)q0, (const double *)xk, (const double *)x})
+      P.in[nin++] = v;
+    for (int i = 0; i < m; i++) P.in[nin++] = A[i];
+    // (the trivial kernel writes what it sums: its one output stream is a vector of its own, not x)
+    double *xout = mk(9, 0.0, 0.0);
+    if (!xout) return PO_ERR_HIP;
+    P.out[nout++] = xout;
+    if (form == 2) P.out[nout++] = dvec;
+    const int grid = grid_for(cx, n, kBpcPanel);
+    PO_TRY(T.time([&]() -> int {
+      hipLaunchKernelGGL(trivial_mix_rt_kernel, dim3(grid), dim3(kBlock), 0, cx->stream, P, nin, nout, n >> 1, sink);
+      PO_HIP(hipGetLastError());
+      return PO_OK;
+    }, ceiling_ms));
+    return PO_OK;
+  };
+  const int rc = body();
+  (void)hipStreamSynchronize(cx->stream);
+  if (sink) (void)hipFree(sink);
+  for (Vec *v : all) vec_decref(v);
+  return rc;
+}

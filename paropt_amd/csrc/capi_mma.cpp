@@ -17,6 +17,7 @@ using namespace po;
 struct po_mma_s {
   po::MMA *mma;
   std::vector<po_vec> p, q;  // the handle arrays po_mma_get_subproblem hands out
+  std::vector<po_vec> a;     // ... and po_mma_get_linear_subproblem
 };
 
 extern "C" {
@@ -115,6 +116,11 @@ int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, p
   PO_CHECK_PTR(mma);
   MMA *m = mma->mma;
   PO_TRY(m->build());
+  if (m->linearDual()) {
+    po::set_error("po_mma_get_subproblem: with mma_dual_linearized_constraints = newton the solver holds no p_i, q_i; "
+                  "po_mma_get_linear_subproblem hands out the linearised subproblem");
+    return PO_ERR_ARG;
+  }
   if (alpha) *alpha = static_cast<po_vec>(m->alphavec);
   if (beta) *beta = static_cast<po_vec>(m->betavec);
   if (p0) *p0 = static_cast<po_vec>(m->p0vec);
@@ -127,6 +133,86 @@ int po_mma_get_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, p
   if (q) *q = mma->q.data();
   if (b) *b = m->b.data();
   return PO_OK;
+}
+// the linearised subproblem of src/ParOptMMA.cpp:804-866 (use_true_mma = 0): cons + A (x - xk)
+int po_mma_get_linear_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **A,
+                                 const double **cons, po_vec *xk) {
+  PO_CHECK_PTR(mma);
+  MMA *m = mma->mma;
+  PO_TRY(m->build());
+  if (alpha) *alpha = static_cast<po_vec>(m->alphavec);
+  if (beta) *beta = static_cast<po_vec>(m->betavec);
+  if (p0) *p0 = static_cast<po_vec>(m->p0vec);
+  if (q0) *q0 = static_cast<po_vec>(m->q0vec);
+  if (mma->a.empty())  // the vectors stay from build() to the destructor
+    for (Vec *v : m->constraintGradients()) mma->a.push_back(static_cast<po_vec>(v));
+  if (A) *A = mma->a.data();
+  if (cons) *cons = m->cons.data();
+  if (xk) *xk = static_cast<po_vec>(m->xvec);
+  return PO_OK;
+}
+int po_mma_get_dual_linear_stats(po_mma mma, long *cap_hits, int *max_steps) {
+  PO_CHECK_PTR(mma);
+  const MmaLinearStats &s = mma->mma->linear;
+  if (cap_hits) *cap_hits = s.cap_hits;
+  if (max_steps) *max_steps = s.max_steps;
+  return PO_OK;
+}
+// the dual of that subproblem on caller vectors (gradients of :871-924 with use_true_mma = 0: the A_i themselves)
+int po_mma_dual_linear_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                            const po_vec *A, const double *cons, po_vec xk, const double *lambda, int form,
+                            po_vec xstart_inout, double *W, double *grad, double *hess, po_vec x, po_vec zl,
+                            po_vec zu, double *stats) {
+  const char *who = "po_mma_dual_linear_eval";
+  PO_CHECK_PTR(ctx);
+  PO_CHECK_PTR(L);
+  PO_CHECK_PTR(W);
+  PO_CHECK_PTR(grad);
+  if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
+    po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax, kMmaDualFused);
+    return PO_ERR_ARG;
+  }
+  if (m > 0) {
+    PO_CHECK_PTR(A);
+    PO_CHECK_PTR(cons);
+    PO_CHECK_PTR(lambda);
+  }
+  std::vector<po_vec> nvecs = {L, U, alpha, beta, p0, q0, xk, xstart_inout};
+  for (int i = 0; i < m; i++) nvecs.push_back(A[i]);
+  for (po_vec v : nvecs) {
+    PO_CHECK_PTR(v);
+    if (v->ctx != ctx || v->n != L->n) {
+      po::set_error("%s: vectors of different layouts", who);
+      return PO_ERR_ARG;
+    }
+  }
+  const po_vec outs[] = {x, zl, zu};
+  for (po_vec v : outs) {
+    if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
+      po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
+      return PO_ERR_ARG;
+    }
+  }
+  std::vector<const double *> cols;
+  for (int i = 0; i < m; i++) cols.push_back(A[i]->d);
+  const MmaDualLinear s{L->d, U->d, alpha->d, beta->d, p0->d, q0->d, xk->d, cols.data(), cons, m, L->n};
+  if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
+  if (!hess) form = 0;
+  Vec *dvec = nullptr;  // the panel form's weights
+  if (form == 2 && !(dvec = vec_new(ctx, L->n))) return PO_ERR_HIP;
+  MmaLinearStats st;
+  int rc = k_mma_dual_linear(ctx, s, lambda, form, xstart_inout->d, xstart_inout->d, W, grad, hess,
+                             dvec ? dvec->d : nullptr, &st);
+  if (rc == PO_OK && x) rc = k_mma_dual_linear_point(ctx, s, lambda, xstart_inout->d, x->d, zl->d, zu->d, &st);
+  if (dvec) {
+    if (rc == PO_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
+    vec_decref(dvec);
+  }
+  if (rc == PO_OK && stats) {
+    stats[0] = (double)st.cap_hits;
+    stats[1] = (double)st.max_steps;
+  }
+  return rc;
 }
 // ---- the dual of a subproblem given by caller vectors ---------------------------------------------------------------
 namespace {

@@ -49,9 +49,12 @@ int MMA::allocate() {  // initialize() :131-232
     if (!*v) return PO_ERR_HIP;
   }
   for (int i = 0; i < m; i++) {
-    Vec *a = vec_new(ctx, n), *pv = vec_new(ctx, n), *qv = vec_new(ctx, n);
-    if (!a || !pv || !qv) return PO_ERR_HIP;
+    Vec *a = vec_new(ctx, n);
+    if (!a) return PO_ERR_HIP;
     Avecs.push_back(a);
+    if (use_linear) continue;  // (the linear form never reads p_i, q_i)
+    Vec *pv = vec_new(ctx, n), *qv = vec_new(ctx, n);
+    if (!pv || !qv) return PO_ERR_HIP;
     pivecs.push_back(pv);
     qivecs.push_back(qv);
   }
@@ -69,8 +72,10 @@ int MMA::allocate() {  // initialize() :131-232
   P0p.push_back(p0vec->d);
   Q0q.push_back(q0vec->d);
   for (int i = 0; i < m; i++) {
-    P0p.push_back(pivecs[i]->d);
-    Q0q.push_back(qivecs[i]->d);
+    if (!use_linear) {
+      P0p.push_back(pivecs[i]->d);
+      Q0q.push_back(qivecs[i]->d);
+    }
     A.push_back(Avecs[i]->d);
   }
   A.push_back(zlvec->d);  // (the two columns computeKKTError adds to the constraint gradients)
@@ -82,6 +87,10 @@ int MMA::allocate() {  // initialize() :131-232
 
 bool MMA::wantDual() { return std::string(options().str("mma_subproblem_solver")) == "dual"; }
 bool MMA::wantGroups() { return std::string(options().str("mma_dual_sparse_constraints")) == "groups"; }
+bool MMA::wantLinear() {
+  return options().integer("mma_use_constraint_linearization") != 0 &&
+         std::string(options().str("mma_dual_linearized_constraints")) == "newton";
+}
 
 int MMA::build() {
   if (ip || xvec) return PO_OK;
@@ -91,7 +100,9 @@ int MMA::build() {
   }
   use_dual = wantDual();
   use_groups = use_dual && wantGroups() && nwcon > 0;
+  use_linear = use_dual && wantLinear();
   PO_TRY(allocate());
+  if (use_linear) return PO_OK;  // 17 + c vectors: the panel form's columns are the A_i themselves
   if (use_dual) {  // no interior point and none of its 15 + c vectors; uinv / linv serve as the new point / the weights
     if (use_groups) {  // 2 + c vectors of nwcon on top of the panel form's c columns
       cgvec = vec_new(ctx, nwcon);
@@ -135,7 +146,15 @@ int MMA::checkDualCovers() {
           "consecutive variables with one Jacobian value (setWeighting, or a CSR pattern recognised as such), "
           "nwblock = 1, nw + skip within the 512 variables of a tile, and no quasi-definite solver of the problem's own";
   }
-  if (why) {
+  const bool conservative = std::string(options().str("mma_globalization")) == "conservative";
+  if (wantLinear() && nwcon > 0 && wantGroups()) {
+    why = "the dual of the linearised subproblem (mma_dual_linearized_constraints = newton) takes no sparse "
+          "constraints, grouped ones included";
+  } else if (why) {
+  } else if (wantLinear()) {  // P = p0, Q = q0 whatever the multipliers: equalities included
+    if (conservative)
+      why = "mma_globalization = conservative does not run on linearised constraints: a linearisation is not "
+            "conservative and would need a rho of its own";
   } else if (ninequality < m) {
     why = "a dense equality constraint has a free multiplier, which can make P or Q negative";
   } else if (options().integer("mma_use_constraint_linearization")) {
@@ -180,6 +199,37 @@ int MMA::solveDual(const double *rho, double *point_sums) {
     groups.max_psi = std::max(groups.max_psi, over.max_psi);
   } else if (rho) PO_TRY(k_mma_gcmma_point(ctx, sub, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
   else PO_TRY(k_mma_dual_point(ctx, sub, lambda.data(), uinv->d, zlvec->d, zuvec->d));
+  z = lambda;
+  subproblem_iter += res.evaluations;
+  dual.solves++;
+  dual.iterations += res.iterations;
+  dual.evaluations += res.evaluations;
+  dual.last_status = res.status;
+  dual.last_pg = res.pg;
+  return PO_OK;
+}
+
+// The subproblem with linearised constraints (mma.hpp): inequalities in [0, gamma], equalities in [-gamma, gamma].  The
+// root searches of the first evaluation start from xvec, those of every later pass from the point the pass before it
+// left in uinv.
+int MMA::solveDualLinear() {
+  Options &o = options();
+  const int form = m <= kMmaDualFused ? 1 : 2;
+  const double gamma = o.real("penalty_gamma");
+  std::vector<double> lower(m, 0.0), upper(m, gamma), lambda(z);
+  for (int i = ninequality; i < m; i++) lower[i] = -gamma;
+  const MmaDualLinear lin{Lvec->d, Uvec->d, alphavec->d, betavec->d, p0vec->d, q0vec->d, xvec->d, A.data(),
+                          cons.data(), m, nlocal};
+  MmaDualResult res;
+  const double *start = xvec->d;
+  auto eval = [&](const double *lam, bool want_h, double *W, double *g, double *H) -> int {
+    PO_TRY(k_mma_dual_linear(ctx, lin, lam, want_h ? form : 0, start, uinv->d, W, g, H, linv->d, &linear));
+    start = uinv->d;
+    return PO_OK;
+  };
+  PO_TRY(mma_dual_solve(m, lower.data(), upper.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"),
+                        eval, lambda.data(), &res));
+  PO_TRY(k_mma_dual_linear_point(ctx, lin, lambda.data(), start, uinv->d, zlvec->d, zuvec->d, &linear));
   z = lambda;
   subproblem_iter += res.evaluations;
   dual.solves++;
@@ -358,7 +408,7 @@ int MMA::solveSubproblem(Vec **xnew) {
       ip->getOptimizedPoint(xnew, nullptr, nullptr, nullptr);
       return PO_OK;
     }
-    case Mode::DUAL: PO_TRY(solveDual()); break;
+    case Mode::DUAL: PO_TRY(use_linear ? solveDualLinear() : solveDual()); break;
     case Mode::DUAL_CONSERVATIVE: PO_TRY(solveConservative()); break;
   }
   *xnew = uinv;
@@ -374,7 +424,8 @@ int MMA::optimize() {  // :318-379
   }
   if (want_dual) PO_TRY(checkDualCovers());  // refused before anything is allocated or run
   PO_TRY(build());
-  if (want_dual != use_dual || (use_dual && nwcon > 0 && wantGroups() != use_groups)) {
+  if (want_dual != use_dual || (use_dual && nwcon > 0 && wantGroups() != use_groups) ||
+      (use_dual && wantLinear() != use_linear)) {
     set_error("MMA: mma_subproblem_solver cannot change once the solver's vectors exist");
     return PO_ERR_ARG;
   }

@@ -829,8 +829,14 @@ __device__ __forceinline__ double group_phi1(double P, double Q, double L, doubl
 // of x is below the resolution of both differences: phi' keeps its value (a rounding residue of P u^2 - Q l^2, which
 // sigma makes large), the step keeps its size, and x creeps one ulp at a time into the cap.  The plain form keeps its
 // stop test, and with it its bits.
-template <bool RHO>
-__device__ __forceinline__ double group_el_root(const GroupEl &e, double t, double x0, int &capped) {
+// `steps` receives the evaluations of phi' the search took (0 on a move limit).
+// EARLY: a Newton step below the resolution of x ends the search at once.  Without it such a step is first tested
+// against the bracket, whose end x itself has just become: it counts as having left the bracket, and where the
+// iterates came from one side only the far end is still a move limit, so the search goes on by bisection from there
+// (some 50 more steps, seen on a fifth of the free elements).  The grouped kernels keep that order, and their bits.
+template <bool RHO, bool EARLY = false>
+__device__ __forceinline__ double group_el_root_steps(const GroupEl &e, double t, double x0, int &capped, int &steps) {
+  steps = 0;
   if (!(t > e.ga)) return e.a;
   if (!(t < e.gb)) return e.b;
   double lo = e.a, hi = e.b, x = x0;
@@ -845,13 +851,20 @@ __device__ __forceinline__ double group_el_root(const GroupEl &e, double t, doub
     else if (f > 0.0) hi = x;
     else break;
     double xn = x - f / h;
+    if (EARLY && xn == x) break;
     if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
     if (!(xn > lo && xn < hi) || xn == x) break;
     if (RHO && e.U - xn == e.U - x && xn - e.L == x - e.L) break;
     x = xn;
   }
   if (it == kGroupNewtonCap) capped++;
+  steps = it == kGroupNewtonCap ? it : it + 1;
   return x;
+}
+template <bool RHO>
+__device__ __forceinline__ double group_el_root(const GroupEl &e, double t, double x0, int &capped) {
+  int steps;
+  return group_el_root_steps<RHO>(e, t, x0, capped, steps);
 }
 // the closed form of the plain dual (dual_point1: same expressions, same bits)
 __device__ __forceinline__ double group_closed_form(double P, double Q, double L, double U, double a, double b) {
@@ -1249,6 +1262,301 @@ int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
   }
   PO_TRY(k_wgram(c, sw, Uw, m, g.map.nwcon, H2.data()));
   for (size_t i = 0; i < H2.size(); i++) H[i] -= H2[i];
+  return PO_OK;
+}
+
+// ---- the dual of the subproblem with linearised constraints (mma.hpp; the subproblem of :804-924 with
+// mma_use_constraint_linearization) ------------------------------------------------------------------------------------
+// With t = sum_i lambda_i A_i the minimiser of the Lagrangian is, element by element, the root of the increasing
+// function p0 u^2 - q0 l^2 = t clamped into [alpha, beta]: the bracketed Newton iteration of the grouped constraints
+// (group_el_root_steps with both of its extra stops), started from the stored x.  P = p0 and Q = q0 never depend on lambda, so a multiplier of
+// either sign is harmless.
+struct LinearPoint {
+  f64x2 x, u, l, fr;  // fr: 1.0 where the root lies strictly inside (alpha, beta), else 0.0
+};
+__device__ __forceinline__ void linear_point1(double p0, double q0, double L, double U, double a, double b, double t,
+                                              double xs, bool live, double &x, double &u, double &l, double &fr,
+                                              int &capped, int &most) {
+  x = u = l = fr = 0.0;
+  if (!live) return;
+  GroupEl e;
+  e.P = p0;
+  e.Q = q0;
+  e.L = L;
+  e.U = U;
+  e.a = a;
+  e.b = b;
+  e.ga = group_phi1(p0, q0, L, U, a);
+  e.gb = group_phi1(p0, q0, L, U, b);
+  int steps;
+  // (both extra stops: where |x| is far below |L|, |U| the search would otherwise creep into the cap, see above)
+  x = group_el_root_steps<true, true>(e, t, xs, capped, steps);
+  most = steps > most ? steps : most;
+  u = 1.0 / (U - x);
+  l = 1.0 / (x - L);
+  fr = (x > a && x < b) ? 1.0 : 0.0;
+}
+__device__ __forceinline__ LinearPoint linear_point(f64x2 p0, f64x2 q0, f64x2 L, f64x2 U, f64x2 a, f64x2 b, f64x2 t,
+                                                    f64x2 xs, bool has2, int &capped, int &most) {
+  double x0, u0, l0, f0, x1, u1, l1, f1;
+  linear_point1(p0.x, q0.x, L.x, U.x, a.x, b.x, t.x, xs.x, true, x0, u0, l0, f0, capped, most);
+  linear_point1(p0.y, q0.y, L.y, U.y, a.y, b.y, t.y, xs.y, has2, x1, u1, l1, f1, capped, most);
+  LinearPoint r;
+  r.x = (f64x2){x0, x1};
+  r.u = (f64x2){u0, u1};
+  r.l = (f64x2){l0, l1};
+  r.fr = (f64x2){f0, f1};
+  return r;
+}
+// t += sum_{j <= i < j + B} lambda_i A_i: B loads in flight, issued back to back before their arithmetic (the one-table
+// form of dual_pq_batch: same fma order)
+template <int B>
+__device__ __forceinline__ void linear_t_batch(const PtrTable &At, const CoefTable &lam, int j, int64_t q, f64x2 &t) {
+  f64x2 av[B];
+#pragma unroll
+  for (int u = 0; u < B; u++) av[u] = ld_nt(At.p[j + u] + 2 * q);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < B; u++) t = fma2(lam.a[j + u], av[u], t);
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void linear_t_all(const PtrTable &At, const CoefTable &lam, int m, int64_t q, f64x2 &t) {
+  int j = 0;
+  for (; j + 8 <= m; j += 8) linear_t_batch<8>(At, lam, j, q, t);
+  if (j + 4 <= m) {
+    linear_t_batch<4>(At, lam, j, q, t);
+    j += 4;
+  }
+  if (j + 2 <= m) {
+    linear_t_batch<2>(At, lam, j, q, t);
+    j += 2;
+  }
+  if (j < m) linear_t_batch<1>(At, lam, j, q, t);
+}
+// Sums: {sum p0 u + q0 l, s_i[MC] = sum A_i (x - xk), in MODE 1 the MC (MC + 1) / 2 sums of [free] A_i A_k / h (k-major
+// lower triangle), cap hits of the root searches}; one maximum behind them: the most evaluations one root search took.
+template <int MC, int MODE>
+struct LinearSlots {
+  static constexpr int NH = MODE == 1 ? MC * (MC + 1) / 2 : 0;
+  static constexpr int NS = 1 + MC + NH + 1;
+};
+// MC, MODE 0 / 1 / 2 as in mma_dual_kernel; the columns are the A_i themselves (MODE 2 stores only the weights
+// [free] / h).  xs: the start of the root searches, xo: the point of this evaluation (may be the same vector: a lane
+// reads its pair before it writes it).  Streams: 8 + m in, 1 out (2 in MODE 2).
+template <int MC, int MODE>
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_linear_kernel(const double *__restrict__ L, const double *__restrict__ U, const double *__restrict__ alpha,
+                           const double *__restrict__ beta, const double *__restrict__ p0,
+                           const double *__restrict__ q0, const double *__restrict__ xk, const double *xs, PtrTable At,
+                           CoefTable lam, int m, int64_t n, double *xo, double *__restrict__ dout,
+                           double *__restrict__ partials) {
+  constexpr bool HOLD = MC <= PO_MMA_DUAL_HOLD;
+  constexpr int NVB = 8;
+  constexpr int NS = LinearSlots<MC, MODE>::NS;
+  static_assert(MODE != 1 || MC <= kMmaDualFused, "the fused Hessian needs the columns in registers");
+  __shared__ double sm[4 * NS];
+  __shared__ double smax[4];
+  double acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; s++) acc[s] = 0.0;
+  int capped = 0, most = 0;
+  const int64_t npairs = (n + 1) >> 1;
+  // first pair and stride of a lane: taken here, where the workgroup size is a launch constant
+  const int64_t qfirst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, qstride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = qfirst; q < npairs; q += qstride) {
+    const bool has2 = 2 * q + 1 < n;
+    const f64x2 Lv = ld_nt(L + 2 * q), Uv = ld_nt(U + 2 * q), av = ld_nt(alpha + 2 * q), bv = ld_nt(beta + 2 * q);
+    const f64x2 P = ld_nt(p0 + 2 * q), Q = ld_nt(q0 + 2 * q), xkv = ld_nt(xk + 2 * q), xsv = ld_nt(xs + 2 * q);
+    f64x2 t = (f64x2){0.0, 0.0};
+    f64x2 cv[HOLD ? MC : 1];
+    if (HOLD) {
+#pragma unroll
+      for (int i = 0; i < MC; i++) {
+        cv[i] = (f64x2){0.0, 0.0};
+        if (i < m) cv[i] = ld_nt(At.p[i] + 2 * q);
+      }
+#pragma unroll
+      for (int i = 0; i < MC; i++)
+        if (i < m) t = fma2(lam.a[i], cv[i], t);
+    } else {
+      linear_t_all(At, lam, m, q, t);
+    }
+    const LinearPoint pt = linear_point(P, Q, Lv, Uv, av, bv, t, xsv, has2, capped, most);
+    st_nt(xo + 2 * q, pt.x);
+    acc[0] = dot4(P, pt.u, Q, pt.l, acc[0]);
+    f64x2 dx = pt.x - xkv;
+    if (!has2) dx.y = 0.0;
+    f64x2 dw = (f64x2){0.0, 0.0};
+    if (MODE != 0) {
+      const f64x2 h = 2.0 * (P * (pt.u * pt.u * pt.u) + Q * (pt.l * pt.l * pt.l));
+      dw.x = pt.fr.x != 0.0 ? 1.0 / h.x : 0.0;
+      dw.y = pt.fr.y != 0.0 ? 1.0 / h.y : 0.0;
+      if (MODE == 2) st_nt(dout + 2 * q, dw);
+    }
+    if (HOLD) {
+#pragma unroll
+      for (int i = 0; i < MC; i++) acc[1 + i] = fma(cv[i].x, dx.x, fma(cv[i].y, dx.y, acc[1 + i]));
+      if (MODE == 1) {
+#pragma unroll
+        for (int k = 0; k < MC; k++) {
+          const f64x2 gk = cv[k] * dw;
+#pragma unroll
+          for (int i = 0; i <= k; i++) {
+            const int s = 1 + MC + k * (k + 1) / 2 + i;
+            acc[s] = fma(cv[i].x, gk.x, fma(cv[i].y, gk.y, acc[s]));
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < MC; j += NVB) {
+        if (j < m) {
+          f64x2 cb[NVB];
+#pragma unroll
+          for (int v = 0; v < NVB; v++) {
+            cb[v] = (f64x2){0.0, 0.0};
+            if (j + v < m) cb[v] = ld_nt(At.p[j + v] + 2 * q);
+          }
+#pragma unroll
+          for (int v = 0; v < NVB; v++) acc[1 + j + v] = fma(cb[v].x, dx.x, fma(cb[v].y, dx.y, acc[1 + j + v]));
+        }
+      }
+    }
+  }
+  acc[NS - 1] = (double)capped;
+  dual_block_reduce<NS>(acc, partials, sm);
+  double mx = (double)most;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[(size_t)NS * gridDim.x + blockIdx.x] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+}
+
+// one pass at the final lambda: x (root searches started from xs), zl = max(r, 0) where x = alpha, zu = max(-r, 0)
+// where x = beta, r = p0 u^2 - q0 l^2 - t (0 elsewhere); slots {cap hits} and the maximum {most evaluations}
+__global__ void __launch_bounds__(kBlock)
+    mma_dual_linear_point_kernel(const double *__restrict__ L, const double *__restrict__ U,
+                                 const double *__restrict__ alpha, const double *__restrict__ beta,
+                                 const double *__restrict__ p0, const double *__restrict__ q0, const double *xs,
+                                 PtrTable At, CoefTable lam, int m, int64_t n, double *x, double *__restrict__ zl,
+                                 double *__restrict__ zu, double *__restrict__ partials) {
+  __shared__ double sm[4];
+  __shared__ double smax[4];
+  int capped = 0, most = 0;
+  const int64_t npairs = (n + 1) >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < npairs; q += (int64_t)gridDim.x * blockDim.x) {
+    const bool has2 = 2 * q + 1 < n;
+    const f64x2 Lv = ld_nt(L + 2 * q), Uv = ld_nt(U + 2 * q), av = ld_nt(alpha + 2 * q), bv = ld_nt(beta + 2 * q);
+    const f64x2 P = ld_nt(p0 + 2 * q), Q = ld_nt(q0 + 2 * q), xsv = ld_nt(xs + 2 * q);
+    f64x2 t = (f64x2){0.0, 0.0};
+    linear_t_all(At, lam, m, q, t);
+    const LinearPoint pt = linear_point(P, Q, Lv, Uv, av, bv, t, xsv, has2, capped, most);
+    const f64x2 ql = Q * (pt.l * pt.l), u2 = pt.u * pt.u;
+    const f64x2 r = (f64x2){fma(P.x, u2.x, -ql.x) - t.x, fma(P.y, u2.y, -ql.y) - t.y};
+    f64x2 lo, up;
+    lo.x = pt.x.x == av.x ? fmax(r.x, 0.0) : 0.0;
+    up.x = pt.x.x == bv.x ? fmax(-r.x, 0.0) : 0.0;
+    lo.y = (has2 && pt.x.y == av.y) ? fmax(r.y, 0.0) : 0.0;
+    up.y = (has2 && pt.x.y == bv.y) ? fmax(-r.y, 0.0) : 0.0;
+    st_nt(x + 2 * q, pt.x);
+    st_nt(zl + 2 * q, lo);
+    st_nt(zu + 2 * q, up);
+  }
+  double acc[1] = {(double)capped};
+  dual_block_reduce<1>(acc, partials, sm);
+  double mx = (double)most;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[(size_t)gridDim.x + blockIdx.x] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+}
+
+static int linear_tables(const MmaDualLinear &s, const double *lambda, PtrTable *at, CoefTable *ct) {
+  if (s.m < 0 || s.m > kMmaDualMax) {
+    set_error("MMA dual: %d constraints outside 0..%d", s.m, kMmaDualMax);
+    return PO_ERR_ARG;
+  }
+  for (int i = 0; i < kMaxPanel; i++) {
+    at->p[i] = i < s.m ? s.A[i] : nullptr;
+    ct->a[i] = i < s.m ? lambda[i] : 0.0;
+  }
+  return PO_OK;
+}
+static void linear_stats(const double *capmax, MmaLinearStats *st) {
+  if (!st) return;
+  st->cap_hits += (long)capmax[0];
+  st->max_steps = st->max_steps > (int)capmax[1] ? st->max_steps : (int)capmax[1];
+}
+
+int k_mma_dual_linear(Ctx *c, const MmaDualLinear &s, const double *lambda, int form, const double *xstart, double *x,
+                      double *W, double *grad, double *H, double *dvec, MmaLinearStats *st) {
+  const int m = s.m;
+  PtrTable at;
+  CoefTable ct;
+  PO_TRY(linear_tables(s, lambda, &at, &ct));
+  if (form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
+    set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
+    return PO_ERR_ARG;
+  }
+  if (form != 0 && !H) form = 0;
+  if (form == 2 && !dvec) {
+    set_error("MMA dual: the panel form needs the weight vector");
+    return PO_ERR_ARG;
+  }
+  count_bytes(c, m + 9 + (form == 2 ? 1 : 0), s.n);
+  // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  int mc = 0, ns = 0;
+  auto launch = [&](auto MC, auto MODE) -> int {
+    constexpr int kMC = decltype(MC)::value, kMode = decltype(MODE)::value;
+    if constexpr (kMode != 1 || kMC <= kMmaDualFused) {  // (form 1 past kMmaDualFused was refused above)
+      mc = kMC;
+      ns = LinearSlots<kMC, kMode>::NS;
+      PO_TRY(ensure_partials(c, (size_t)grid * (ns + 1)));
+      PO_MLAUNCH((mma_dual_linear_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, s.xk, xstart, at, ct,
+                 m, s.n, x, dvec, c->d_partials);
+    }
+    return PO_OK;
+  };
+  PO_TRY(with_capacity(m, [&](auto MC) {
+    return form == 1 ? launch(MC, Const<1>{}) : form == 2 ? launch(MC, Const<2>{}) : launch(MC, Const<0>{});
+  }));
+  double sums[1 + 96 + 36 + 2];
+  PO_TRY(reduce_finish(c, grid, ns, 0, 1, sums, true));
+  linear_stats(sums + ns - 1, st);
+  double w = sums[0];
+  for (int i = 0; i < m; i++) {
+    const double ci = s.cons[i] + sums[1 + i];
+    w -= lambda[i] * ci;
+    grad[i] = -ci;
+  }
+  *W = w;
+  if (form == 1) {
+    for (int k = 0; k < m; k++)
+      for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
+  } else if (form == 2 && m > 0) {
+    PO_TRY(k_wgram(c, dvec, s.A, m, s.n, H));
+  }
+  return PO_OK;
+}
+
+int k_mma_dual_linear_point(Ctx *c, const MmaDualLinear &s, const double *lambda, const double *xstart, double *x,
+                            double *zl, double *zu, MmaLinearStats *st) {
+  PtrTable at;
+  CoefTable ct;
+  PO_TRY(linear_tables(s, lambda, &at, &ct));
+  count_bytes(c, s.m + 7 + 3, s.n);
+  const int grid = grid_for(c, s.n, kBpcPanel);
+  PO_TRY(ensure_partials(c, (size_t)grid * 2));
+  PO_MLAUNCH(mma_dual_linear_point_kernel, grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, xstart, at, ct, s.m, s.n, x, zl,
+             zu, c->d_partials);
+  double capmax[2];
+  PO_TRY(reduce_finish(c, grid, 1, 0, 1, capmax, true));
+  linear_stats(capmax, st);
   return PO_OK;
 }
 

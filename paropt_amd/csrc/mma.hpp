@@ -113,6 +113,35 @@ int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
 // read-only pass per conservative trial; collective
 int k_mma_gcmma_group_sums(Ctx *c, const MmaDualData &s, const double *xk, const double *x, double *sums);
 
+// ---- the dual with linearised constraints (mma_dual_linearized_constraints = newton) --------------------------------
+// minimise sum p0 / (U - x) + q0 / (x - L) over alpha <= x <= beta subject to c_i(x) = cons_i + A_i . (x - xk) >= 0
+// (= 0 for an equality).  The Lagrangian stays separable; with t = sum_i lambda_i A_i its element-wise minimiser is
+// x = clamp(root of p0 u^2 - q0 l^2 = t, alpha, beta), found by the bracketed Newton iteration of the grouped
+// constraints, and
+//   W = sum p0 u + q0 l - sum_i lambda_i c_i(x),  dW/dlambda_i = -c_i(x),
+//   -hess W = sum over the free elements of A_i A_k / h,  h = 2 (p0 u^3 + q0 l^3).
+// P = p0 and Q = q0 do not depend on lambda: an equality's multiplier may take either sign.
+struct MmaDualLinear {  // device pointers of n elements, m columns A_i, cons[m] on the host
+  const double *L, *U, *alpha, *beta, *p0, *q0, *xk;
+  const double *const *A;
+  const double *cons;
+  int m;
+  int64_t n;
+};
+struct MmaLinearStats {  // the element root searches, over all ranks: accumulated by the passes below
+  long cap_hits = 0;     // searches that ran into kGroupNewtonCap
+  int max_steps = 0;     // most evaluations one search took
+};
+// W(lambda), grad[m] and, when H != nullptr, H[m * m] = -hess W (symmetric, column-major); collective.  The root
+// searches start from xstart and the point is stored into x (the same vector is allowed).  form 0: value and gradient
+// only; 1: the Hessian sums in the same pass (m <= kMmaDualFused); 2: the pass stores the weights [free] / h in dvec and
+// H = A^T diag(dvec) A by k_wgram over the A_i themselves.  W and grad have the same bits in every form.
+int k_mma_dual_linear(Ctx *c, const MmaDualLinear &s, const double *lambda, int form, const double *xstart, double *x,
+                      double *W, double *grad, double *H, double *dvec, MmaLinearStats *st = nullptr);
+// the primal point and the bound multipliers at lambda (r = p0 u^2 - q0 l^2 - t); collective
+int k_mma_dual_linear_point(Ctx *c, const MmaDualLinear &s, const double *lambda, const double *xstart, double *x,
+                            double *zl, double *zu, MmaLinearStats *st = nullptr);
+
 typedef int (*MmaIterationFn)(void *user, int iter);
 
 struct MmaDualStats {  // mma_subproblem_solver = dual: counters over every solve; status and max |pg| of the last one
@@ -173,6 +202,11 @@ class MMA : public Problem {
   // mma_dual_sparse_constraints = groups: the classes of the groups at the last solve's point, and over the
   // evaluations of that solve the most steps of one group, the cap hits and the largest |psi| of a strict group
   MmaGroupStats groups;
+  // mma_dual_linearized_constraints = newton: the element root searches over every pass of this solver
+  MmaLinearStats linear;
+  // the dual of the linearised subproblem is what build() allocated for (no p_i, q_i: po_mma_get_linear_subproblem)
+  bool linearDual() const { return use_linear; }
+  const std::vector<Vec *> &constraintGradients() const { return Avecs; }
 
  private:
   // how a subproblem is solved: optimize() decides it from mma_subproblem_solver and mma_globalization.  The dual
@@ -180,6 +214,7 @@ class MMA : public Problem {
   enum class Mode { INTERIOR_POINT, DUAL, DUAL_CONSERVATIVE };
   bool wantDual();
   bool wantGroups();
+  bool wantLinear();
   MmaParams params();
   int allocate();
   int initializeSubProblem(Vec *xv);
@@ -188,6 +223,7 @@ class MMA : public Problem {
   void setMultipliers();
   int checkDualCovers();
   int solveDual(const double *rho = nullptr, double *point_sums = nullptr);
+  int solveDualLinear();
   int solveConservative();
   void flushHistory();
 
@@ -199,6 +235,7 @@ class MMA : public Problem {
   Mode mode = Mode::INTERIOR_POINT;
   bool use_dual = false;  // the sub-solver build() allocated for
   bool use_groups = false;  // ... with the grouped sparse constraints in the dual (nwcon > 0)
+  bool use_linear = false;  // ... with linearised constraints in the dual: pivecs, qivecs and Gvecs stay empty
   Vec *x1vec = nullptr, *x2vec = nullptr, *lbvec = nullptr, *ubvec = nullptr, *gvec = nullptr, *rvec = nullptr,
       *uinv = nullptr, *linv = nullptr, *cwvec = nullptr;
   // the grouped dual: c_i of psi_i = a sum x + c_i, the group sums s_g (then the Gram weights), and m columns of nwcon

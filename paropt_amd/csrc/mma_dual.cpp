@@ -13,10 +13,11 @@ namespace {
 constexpr double kNoise = 1e-13;  // relative evaluation error allowed for W (the reductions' own bound per term)
 
 // pg_i = 0 where the bound blocks the ascent direction, g_i elsewhere; returns max|pg|
-double projected_gradient(int m, const double *lam, const double *gamma, const double *g, double *pg) {
+double projected_gradient(int m, const double *lam, const double *lower, const double *upper, const double *g,
+                          double *pg) {
   double mx = 0.0;
   for (int i = 0; i < m; i++) {
-    const bool blocked = (lam[i] <= 0.0 && g[i] < 0.0) || (lam[i] >= gamma[i] && g[i] > 0.0);
+    const bool blocked = (lam[i] <= lower[i] && g[i] < 0.0) || (lam[i] >= upper[i] && g[i] > 0.0);
     pg[i] = blocked ? 0.0 : g[i];
     mx = std::max(mx, fabs(pg[i]));
   }
@@ -55,11 +56,17 @@ bool chol_solve(int k, double *A, double *b) {
 
 int mma_dual_solve(int m, const double *gamma, double tol, int max_evaluations, const MmaDualEvalFn &eval,
                    double *lambda, MmaDualResult *res) {
+  const std::vector<double> lower(m, 0.0);
+  return mma_dual_solve(m, lower.data(), gamma, tol, max_evaluations, eval, lambda, res);
+}
+
+int mma_dual_solve(int m, const double *lower, const double *upper, double tol, int max_evaluations,
+                   const MmaDualEvalFn &eval, double *lambda, MmaDualResult *res) {
   MmaDualResult r;
   const size_t mm = (size_t)m * m;
   std::vector<double> g(m), H(mm), gc(m), Hc(mm), cand(m), pg(m), A(mm), d(m);
   std::vector<int> freeset;
-  for (int i = 0; i < m; i++) lambda[i] = std::min(std::max(lambda[i], 0.0), gamma[i]);
+  for (int i = 0; i < m; i++) lambda[i] = std::min(std::max(lambda[i], lower[i]), upper[i]);
   double W = 0.0, Wc = 0.0;
   int rc = eval(lambda, true, &W, g.data(), H.data());
   r.evaluations = 1;
@@ -72,7 +79,7 @@ int mma_dual_solve(int m, const double *gamma, double tol, int max_evaluations, 
   double tau = 1e-8 * std::max(1.0, trace);
   r.status = 1;
   for (;;) {
-    r.pg = projected_gradient(m, lambda, gamma, g.data(), pg.data());
+    r.pg = projected_gradient(m, lambda, lower, upper, g.data(), pg.data());
     if (r.pg <= tol) {
       r.status = 0;
       break;
@@ -94,7 +101,7 @@ int mma_dual_solve(int m, const double *gamma, double tol, int max_evaluations, 
     for (int i = 0; i < m; i++) cand[i] = lambda[i];
     for (int b = 0; b < k; b++) {
       const int i = freeset[b];
-      cand[i] = std::min(std::max(lambda[i] + d[b], 0.0), gamma[i]);
+      cand[i] = std::min(std::max(lambda[i] + d[b], lower[i]), upper[i]);
     }
     rc = eval(cand.data(), true, &Wc, gc.data(), Hc.data());
     r.evaluations++;
@@ -108,7 +115,7 @@ int mma_dual_solve(int m, const double *gamma, double tol, int max_evaluations, 
     // it lowers max|pg| -- that quantity then decreases strictly, so the slack cannot cycle.  (A NaN fails both.)
     bool accept = Wc >= W + 1e-4 * slope;
     if (!accept && Wc >= W + 1e-4 * slope - kNoise * std::max(1.0, fabs(W)))
-      accept = projected_gradient(m, cand.data(), gamma, gc.data(), pg.data()) < r.pg;
+      accept = projected_gradient(m, cand.data(), lower, upper, gc.data(), pg.data()) < r.pg;
     if (accept) {
       for (int i = 0; i < m; i++) lambda[i] = cand[i];
       W = Wc;

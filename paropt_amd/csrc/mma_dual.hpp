@@ -27,5 +27,10 @@ struct MmaDualResult {
 // solution on return.  Returns the first non-zero code of eval, else 0.
 int mma_dual_solve(int m, const double *gamma, double tol, int max_evaluations, const MmaDualEvalFn &eval,
                    double *lambda, MmaDualResult *res);
+// The same iteration over the box lower <= lambda <= upper (per component; the clip, the projected gradient and the
+// free set take both ends): the dual with linearised constraints, whose equality multipliers lie in [-gamma, gamma].
+// The form above is this one with lower = 0.
+int mma_dual_solve(int m, const double *lower, const double *upper, double tol, int max_evaluations,
+                   const MmaDualEvalFn &eval, double *lambda, MmaDualResult *res);
 
 }  // namespace po

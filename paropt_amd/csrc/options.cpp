@@ -224,6 +224,13 @@ void Options::addMMADefaults() {
   dsc.s = "refuse";
   dsc.choices = {"refuse", "groups"};
   e["mma_dual_sparse_constraints"] = dsc;
+  // ... and with mma_use_constraint_linearization = 1: refuse, or solve the linearised subproblem's dual, whose
+  // element-wise minimiser is a bracketed Newton root search (this also admits dense equality constraints)
+  Entry dlc;
+  dlc.type = ENUM;
+  dlc.s = "refuse";
+  dlc.choices = {"refuse", "newton"};
+  e["mma_dual_linearized_constraints"] = dlc;
   Entry dit;
   dit.type = INT;
   dit.i = 200;

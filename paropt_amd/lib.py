@@ -442,6 +442,14 @@ SIGNATURES = {
     "po_bench_vec_api": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_char_p, C.c_int]),
     "po_bench_mma_dual": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "po_bench_mma_dual_rho": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int] + [c_double_p] * 4),
+    "po_bench_mma_dual_linear": (C.c_int, [po_ctx, C.c_int64, C.c_int, C.c_int, C.c_int] + [c_double_p] * 5),
+    "po_mma_dual_linear_eval": (
+        C.c_int, [po_ctx, C.c_int] + [po_vec] * 6 + [C.POINTER(po_vec), c_double_p, po_vec, c_double_p, C.c_int, po_vec]
+        + [c_double_p] * 3 + [po_vec] * 3 + [c_double_p]),
+    "po_mma_get_dual_linear_stats": (C.c_int, [po_mma, C.POINTER(C.c_long), c_int_p]),
+    "po_mma_get_linear_subproblem": (
+        C.c_int, [po_mma] + [C.POINTER(po_vec)] * 4 + [C.POINTER(C.POINTER(po_vec)), C.POINTER(c_double_p),
+                                                      C.POINTER(po_vec)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

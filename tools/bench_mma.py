@@ -26,6 +26,12 @@ of the root searches, dual evaluations per solve.  Then on the last subproblem t
 rho (po_mma_dual_group_eval / _rho; the rho form once with rho = 0, which is the same point and the same searches as
 the plain form, so that it prices the form alone, and once with the run's rho) alternate, and the point of a trial
 (po_mma_gcmma_group_point: the group solve and the read-only sums pass) is timed beside them.  Appended to profiles/r14_bench_mma_gcmma_groups.jsonl.
+
+--linearized: mma_use_constraint_linearization = 1.  Whole MMA iterations with the interior-point sub-solver and with
+the dual of the linearised subproblem (mma_dual_linearized_constraints = newton) alternate; then the linear pass
+(po_bench_mma_dual_linear: root searches started warm, from the point of the call before, and cold, from the expansion
+point) and the rational pass (po_bench_mma_dual) alternate at the same (n, m): ms, GB/s over the algorithmic m + 9
+(m + 10 in the panel form) streams and the fraction of 8 TB/s.  Appended to profiles/r16_bench_mma_linear.jsonl.
 """
 import argparse
 import json
@@ -40,10 +46,13 @@ HBM_PEAK_GBPS = 8000.0
 M_F = 8
 
 
-def run_mma(pa, ctx, n, c, solver, iters, globalization="none", problem="convex"):
+def run_mma(pa, ctx, n, c, solver, iters, globalization="none", problem="convex", linearized=False):
     prob = pa.SeparableProblem(ctx, problem, n, c, 0)
-    mma = pa.MMA(prob, {"mma_subproblem_solver": solver, "mma_max_iterations": iters, "mma_l1_tol": 0.0,
-                        "mma_linfty_tol": 0.0, "write_output_frequency": 0, "mma_globalization": globalization})
+    opts = {"mma_subproblem_solver": solver, "mma_max_iterations": iters, "mma_l1_tol": 0.0,
+            "mma_linfty_tol": 0.0, "write_output_frequency": 0, "mma_globalization": globalization}
+    if linearized:
+        opts.update(mma_use_constraint_linearization=1, mma_dual_linearized_constraints="newton")
+    mma = pa.MMA(prob, opts)
     stamps = []
     # (the callback follows the reductions of the table row, which the host has waited for: nothing is in flight)
     mma.setIterationCallback(lambda k: stamps.append(time.perf_counter()))
@@ -60,7 +69,34 @@ def run_mma(pa, ctx, n, c, solver, iters, globalization="none", problem="convex"
         gs = mma.getGlobalizationStats()
         out.update(globalization=globalization, inner_total=gs["inner_total"], inner_max=gs["inner_max"],
                    cap_hits=gs["cap_hits"], rho=gs["rho"].tolist())
+        if linearized:
+            out["linear_stats"] = mma.getDualLinearStats()
     return out
+
+
+def linear_pass_lines(pa, ctx, n, c, reps, rounds):
+    """The linear pass (warm and cold starts of the root searches) and the rational pass, alternating in one process."""
+    lines = []
+    for form in ([1, 2] if c <= M_F else [2]):
+        for rnd in range(rounds):
+            warm, cold, gram_l, ceil_l, steps = pa.bench_mma_dual_linear(ctx, n, c, form, reps)
+            rat_ms, gram_r, ceil_r = pa.bench_mma_dual(ctx, n, c, form, reps)
+            streams = c + 9 + (1 if form == 2 else 0)
+            gb = 8.0 * streams * n * 1e-9
+            gb_r = 8.0 * (2 * c + 6 + (c + 1 if form == 2 else 0)) * n * 1e-9
+            r = dict(kind="dual_linear_pass", n=n, c=c, form=form, round=rnd,
+                     mix="%d in / %d out" % (c + 8, 2 if form == 2 else 1), alg_GB=gb, warm_ms=warm, cold_ms=cold,
+                     gram_ms=gram_l, trivial_ms=ceil_l, max_root_steps_warm_cold=steps,
+                     warm_GBps=gb / (warm * 1e-3), cold_GBps=gb / (cold * 1e-3),
+                     warm_frac_hbm_8TBps=gb / (warm * 1e-3) / HBM_PEAK_GBPS,
+                     cold_frac_hbm_8TBps=gb / (cold * 1e-3) / HBM_PEAK_GBPS, warm_frac_of_trivial=ceil_l / warm,
+                     rational_alg_GB=gb_r, rational_ms=rat_ms, rational_gram_ms=gram_r, rational_trivial_ms=ceil_r,
+                     rational_frac_hbm_8TBps=gb_r / (rat_ms * 1e-3) / HBM_PEAK_GBPS,
+                     warm_over_rational=(warm + gram_l) / (rat_ms + gram_r),
+                     cold_over_rational=(cold + gram_l) / (rat_ms + gram_r))
+            lines.append(r)
+            print(json.dumps(r), flush=True)
+    return lines
 
 
 def group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps):
@@ -251,6 +287,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--nw", type=int, default=0)
     ap.add_argument("--nwcon", type=int, default=0)
+    ap.add_argument("--linearized", action="store_true")
     a = ap.parse_args()
     if a.small:
         a.globalization = "conservative"
@@ -258,6 +295,8 @@ def main():
         a.shapes = "300x3,200x2" if a.small else "10000000x8,50000000x32"
     if a.mma_iters is None:
         a.mma_iters = 120 if a.small else 4
+    if a.out is None and a.linearized:
+        a.out = os.path.join(ROOT, "profiles", "r16_bench_mma_linear.jsonl")
     if a.out is None and a.nw > 0:
         a.out = os.path.join(ROOT, "profiles", "r14_bench_mma_gcmma_groups.jsonl" if a.globalization == "conservative"
                              else "r12_bench_mma_groups.jsonl")
@@ -279,6 +318,15 @@ def main():
             continue
         if a.small:
             lines += small_run_lines(pa, ctx, n, c, a.mma_iters, a.problem)
+            continue
+        if a.linearized:
+            for rnd in range(a.rounds):
+                for solver in ("interior_point", "dual"):
+                    r = run_mma(pa, ctx, n, c, solver, a.mma_iters, problem=a.problem, linearized=True)
+                    r.update(kind="mma_linearized", problem=a.problem, n=n, c=c, round=rnd)
+                    lines.append(r)
+                    print(json.dumps(r), flush=True)
+            lines += linear_pass_lines(pa, ctx, n, c, a.reps, 2)
             continue
         for rnd in range(a.rounds):
             if a.globalization == "conservative":
