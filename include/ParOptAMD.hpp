@@ -766,6 +766,16 @@ class ParOptSparseProblem : public ParOptProblem {
     cols.assign(_cols, _cols + rowp[nwcon]);
     data.assign(cols.size() > 0 ? cols.size() : 1, 0.0);
   }
+  // Facade extension: the dense-column rule (po_problem_set_sparse_dense_columns: > 0 a row count, 0 automatic, -1
+  // never), before setSparseJacobianData -- a column that enters nearly every sparse constraint, such as the epigraph
+  // variable of a min-max formulation, is solved by a low-rank update instead of filling S
+  void setDenseColumnThreshold(int min_rows) { dense_min_rows = min_rows; }
+  // the columns the rule took out, ascending (borrowed); returns their number
+  int getDenseColumns(const int **_cols) {
+    int count = 0;
+    if (!hprob || po_problem_sparse_dense_columns(hprob, _cols, &count) != 0) return 0;
+    return count;
+  }
   // (src/ParOptProblem.cpp:689-703) the HOST copy of the entries: what the last evalSparseObjConGradient wrote
   int getSparseJacobianData(const int **_rowp, const int **_cols, const ParOptScalar **_data) {
     if (_rowp) *_rowp = rowp.data();
@@ -805,6 +815,9 @@ class ParOptSparseProblem : public ParOptProblem {
 
  protected:
   void attachSparse() {
+    if (dense_min_rows != 0 && po_problem_set_sparse_dense_columns(hprob, dense_min_rows) != 0) {
+      fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+    }
     if (po_problem_set_sparse_jacobian_data(hprob, nwcon, nwinequality, rowp.data(), cols.data(),
                                             &ParOptSparseProblem::tramp_sobjcon,
                                             &ParOptSparseProblem::tramp_sgrad) != 0) {
@@ -815,6 +828,7 @@ class ParOptSparseProblem : public ParOptProblem {
  private:
   std::vector<int> rowp, cols;
   std::vector<ParOptScalar> data;
+  int dense_min_rows = 0;
   static int tramp_sobjcon(void *self, po_vec x, double *fobj, double *cons, po_vec sparse) {
     Arg vx(x, 0), vs(sparse, 1);
     return static_cast<ParOptSparseProblem *>(self)->evalSparseObjCon(vx.p(), fobj, cons, vs.p());

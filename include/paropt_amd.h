@@ -333,6 +333,19 @@ typedef int (*po_eval_sparse_obj_con_gradient_fn)(void *user, po_vec x, po_vec g
 int po_problem_set_sparse_jacobian_data(po_problem p, int64_t nwcon, int64_t nwinequality, const int *rowp,
                                         const int *cols, po_eval_sparse_obj_con_fn eval_sparse_obj_con,
                                         po_eval_sparse_obj_con_gradient_fn eval_sparse_obj_con_gradient);
+/* The dense-column rule of the CSR form, to be called BEFORE po_problem_set_sparse_jacobian_data.  A column of Aw
+ * that enters (nearly) every sparse constraint -- the epigraph variable t of a min-max formulation t - f_i(x) >= 0 --
+ * would make S = C + Aw D^-1 Aw^T dense.  Such columns J are taken out of the factored matrix and put back by a
+ * low-rank (Sherman-Morrison-Woodbury) correction: S = S0 + V E V^T, S0 = C + As D^-1 As^T sparse, V = Aw[:, J],
+ * E = diag(D^-1[J]), at most 64 columns.
+ *   min_rows > 0   every column with at least min_rows entries is dense
+ *   min_rows = 0   (default) automatic: nothing changes unless the pattern would be refused (more than 1.5e9 entries
+ *                  in Aw Aw^T); then the columns with at least max(1024, nwcon / 8) entries are dense
+ *   min_rows = -1  never: such a pattern is refused
+ * More than 64 qualifying columns, or more than 1.5e9 entries left, are refused in every mode. */
+int po_problem_set_sparse_dense_columns(po_problem p, int64_t min_rows);
+/* the dense columns of the problem's pattern, ascending (borrowed, valid like the pattern); *count = 0 without any */
+int po_problem_sparse_dense_columns(po_problem p, const int **cols, int *count);
 /* getSparseJacobianData (src/ParOptProblem.cpp:689-703): host pattern, device values; returns nnz in *nnz.
  * Borrowed pointers, valid until the next po_problem_set_sparse_jacobian_data or the problem's destruction -- also
  * across the library's own change of path when a recognised grouped pattern turns out to have non-uniform entries. */
@@ -378,9 +391,14 @@ int po_problem_set_quasidef_callbacks(po_problem p, const po_quasidef_callbacks 
  * elimination tree, pattern of L (CSR, diagonal last in each row) and the dependency level sets the device
  * factorization and solves are scheduled by.  No context needed.
  * info = {nnz(Aw), nnz(lower S), nnz(L), dependency levels, 1 if `cols` was already sorted, number of fronts,
- * rows of the largest front}. */
+ * rows of the largest front}.  With dense columns taken out (po_problem_set_sparse_dense_columns) everything but
+ * nnz(Aw) describes S0, the matrix that is factored.  po_csr_symbolic_create is min_rows = 0. */
 typedef struct po_csr_symbolic_s *po_csr_symbolic;
 int po_csr_symbolic_create(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, po_csr_symbolic *out);
+int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
+                                 po_csr_symbolic *out);
+/* the dense columns, ascending (borrowed); *count = 0 and *cols = NULL without any */
+int po_csr_symbolic_dense_columns(po_csr_symbolic h, const int **cols, int *count);
 int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]);
 /* borrowed host arrays: perm[new] = old (nwcon), parent (nwcon), Lrowp (nwcon+1), Lcols (nnz(L)), level_ptr
  * (levels+1), front_of (nwcon).  Rows are numbered level by level; level l is the rows level_ptr[l] ..
@@ -419,6 +437,10 @@ int po_problem_sparse_sizes(po_problem p, int64_t *nwcon_local, int64_t *nwinequ
  * cw_i = 1 - sum_{k<span} x[i*stride + k]^2 >= 0, i < (nlocal - span)/stride + 1.  reverse_cols stores each
  * row's columns in descending order (exercises the unsorted-pattern path).  Before po_ip_create. */
 int po_problem_set_chain(po_problem p, int span, int stride, int reverse_cols);
+/* The same chain over the first nlocal - dense_vars variables, with the last dense_vars local variables entering
+ * EVERY row: cw_i -= sum_j x[nlocal - dense_vars + j]^2 (the shape of a min-max formulation's epigraph variable).
+ * Their columns are dense columns of the Jacobian: see po_problem_set_sparse_dense_columns. */
+int po_problem_set_chain_dense(po_problem p, int span, int stride, int reverse_cols, int dense_vars);
 /* useLowerBounds / useUpperBounds (src/ParOptProblem.h:140-150; CyParOptProblem::setVarBoundOptions):
  * a problem that declares a side unused never has that side's bound multipliers formed.  Before
  * po_ip_create. */

@@ -843,6 +843,13 @@ class _QuasiDefMixin:
         self._quasidef = _QuasiDefBinding(self, obj, self._quasidef_device if device is None else device)
         return self
 
+    @property
+    def dense_columns(self):
+        """The columns of the CSR sparse Jacobian that are solved by low-rank update, ascending ([] without any)."""
+        dc, cnt = L.c_int_p(), C.c_int()
+        check(lib.po_problem_sparse_dense_columns(self.handle, C.byref(dc), C.byref(cnt)))
+        return [int(dc[i]) for i in range(cnt.value)]
+
     def getSparseJacobianData(self, device=False):
         """(rowp, cols, data) of the CSR sparse Jacobian (ParOptSparseProblem::getSparseJacobianData): the host
         pattern and the current entries in the order of cols -- a numpy copy, or with device=True a zero-copy
@@ -877,11 +884,12 @@ class Problem(_QuasiDefMixin):
 
     With rowp / cols (the reference's CSR form, paropt/ParOpt.pyx:849-881) override instead
     evalSparseObjCon(x, sparse_cons) -> (fail, fobj, con) and evalSparseObjConGradient(x, g, A, data) -> fail;
-    sparse_cons (nwcon) and data (nnz, in the order of cols) are filled in place.
+    sparse_cons (nwcon) and data (nnz, in the order of cols) are filled in place.  dense_column_rows is the
+    dense-column rule of that form (CsrSymbolic; 0 = automatic), `dense_columns` the columns it took out.
     """
 
     def __init__(self, ctx, nvars, ncon, ninequality=-1, nwcon=0, nwinequality=0, use_lower=True,
-                 use_upper=True, rowp=None, cols=None, nwblock=1):
+                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0):
         self.ctx = ctx
         self.nvars, self.ncon = int(nvars), int(ncon)
         self.nwcon = int(nwcon)
@@ -1001,6 +1009,8 @@ class Problem(_QuasiDefMixin):
                 return int(fail or 0)
 
             self._csr_cbs = (L.SPARSE_OBJCON_FN(_sobjcon), L.SPARSE_GRAD_FN(_sgrad))
+            if dense_column_rows != 0:
+                check(lib.po_problem_set_sparse_dense_columns(self._h, int(dense_column_rows)))
             check(lib.po_problem_set_sparse_jacobian_data(
                 self._h, self.nwcon, int(nwinequality), self._rowp.ctypes.data_as(L.c_int_p),
                 self._cols.ctypes.data_as(L.c_int_p), self._csr_cbs[0], self._csr_cbs[1]))
@@ -1124,7 +1134,7 @@ class TorchProblem(Problem):
     """
 
     def __init__(self, ctx, nvars, ncon, ninequality=-1, nwcon=0, nwinequality=0, use_lower=True,
-                 use_upper=True, rowp=None, cols=None, nwblock=1):
+                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0):
         import collections
 
         import torch
@@ -1136,7 +1146,8 @@ class TorchProblem(Problem):
         self._drop_cb = L.AFTER_REDUCE_FN(self._drop_held)
         self._data_view = None
         super().__init__(ctx, nvars, ncon, ninequality, nwcon=nwcon, nwinequality=nwinequality, use_lower=use_lower,
-                         use_upper=use_upper, rowp=rowp, cols=cols, nwblock=nwblock)
+                         use_upper=use_upper, rowp=rowp, cols=cols, nwblock=nwblock,
+                         dense_column_rows=dense_column_rows)
 
     _quasidef_device = True  # createQuasiDefMat's solver works on device tensors too
 
@@ -1230,10 +1241,18 @@ class SeparableProblem(_QuasiDefMixin):
         self.nwcon = a.value
         return self
 
-    def setChain(self, span=2, stride=1, reverse_cols=False):
+    def setChain(self, span=2, stride=1, reverse_cols=False, dense_vars=0, dense_column_rows=0):
         """Rank-local overlapping sparse constraints in CSR form: cw_i = 1 - sum_{k<span} x[i*stride+k]^2 >= 0
-        (examples/rosenbrock/sparse_rosenbrock.cpp is span 2, stride 1)."""
-        check(lib.po_problem_set_chain(self._h, int(span), int(stride), int(bool(reverse_cols))))
+        (examples/rosenbrock/sparse_rosenbrock.cpp is span 2, stride 1).  dense_vars > 0: the chain runs over the
+        first variables and the last dense_vars local ones enter every row, cw_i -= sum_j x[n - dense_vars + j]^2;
+        dense_column_rows is the dense-column rule their columns fall under (Problem)."""
+        if dense_column_rows != 0:
+            check(lib.po_problem_set_sparse_dense_columns(self._h, int(dense_column_rows)))
+        if dense_vars:
+            check(lib.po_problem_set_chain_dense(self._h, int(span), int(stride), int(bool(reverse_cols)),
+                                                 int(dense_vars)))
+        else:
+            check(lib.po_problem_set_chain(self._h, int(span), int(stride), int(bool(reverse_cols))))
         a, b = C.c_int64(), C.c_int64()
         check(lib.po_problem_sparse_sizes(self._h, C.byref(a), C.byref(b)))
         self.nwcon = a.value
@@ -1348,14 +1367,20 @@ class CsrSymbolic:
     """The one-time host analysis of a CSR sparse Jacobian pattern (no device needed): ordering,
     elimination tree, pattern of the Cholesky factor of S = C + Aw D^-1 Aw^T, dependency level sets."""
 
-    def __init__(self, nvars, rowp, cols):
+    def __init__(self, nvars, rowp, cols, dense_column_rows=0):
+        """dense_column_rows: the dense-column rule (> 0: columns with at least that many entries leave S and come
+        back as a low-rank correction; 0: automatic, only where the pattern would otherwise be refused; -1: never).
+        With dense columns (`dense_cols`, ascending) every other field describes S0 = C + As D^-1 As^T."""
         rowp = np.ascontiguousarray(rowp, dtype=np.intc)
         cols = np.ascontiguousarray(cols, dtype=np.intc)
         w = len(rowp) - 1
         h = L.po_csr_symbolic()
-        check(lib.po_csr_symbolic_create(int(nvars), w, rowp.ctypes.data_as(L.c_int_p),
-                                         cols.ctypes.data_as(L.c_int_p), C.byref(h)))
+        check(lib.po_csr_symbolic_create_split(int(nvars), w, rowp.ctypes.data_as(L.c_int_p),
+                                               cols.ctypes.data_as(L.c_int_p), int(dense_column_rows), C.byref(h)))
         try:
+            dc, cnt = L.c_int_p(), C.c_int()
+            check(lib.po_csr_symbolic_dense_columns(h, C.byref(dc), C.byref(cnt)))
+            self.dense_cols = [int(dc[i]) for i in range(cnt.value)]
             info = (C.c_int64 * 7)()
             check(lib.po_csr_symbolic_info(h, info))
             self.nnz, self.nnzS, self.nnzL, self.nlevels = (int(v) for v in info[:4])

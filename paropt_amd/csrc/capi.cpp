@@ -706,6 +706,23 @@ int po_problem_set_sparse_jacobian_data(po_problem p, int64_t nwcon, int64_t nwi
   q->csr_gradient = eval_sparse_obj_con_gradient;
   return PO_OK;
 }
+int po_problem_set_sparse_dense_columns(po_problem p, int64_t min_rows) {
+  PO_CHECK_PTR(p);
+  if (min_rows < -1) {
+    po::set_error("po_problem_set_sparse_dense_columns: min_rows must be -1 (never), 0 (automatic) or a row count");
+    return PO_ERR_ARG;
+  }
+  p->p->dense_min_rows = min_rows;
+  return PO_OK;
+}
+int po_problem_sparse_dense_columns(po_problem p, const int **cols, int *count) {
+  PO_CHECK_PTR(p);
+  PO_CHECK_PTR(count);
+  po::CsrSparse *m = p->p->csr;
+  *count = m ? m->ndense() : 0;
+  if (cols) *cols = m && m->ndense() > 0 ? m->sym.dense_cols.data() : nullptr;
+  return PO_OK;
+}
 int po_problem_get_sparse_jacobian_data(po_problem p, const int **rowp, const int **cols, double **data,
                                         int64_t *nnz) {
   PO_CHECK_PTR(p);
@@ -757,14 +774,25 @@ struct po_csr_symbolic_s {
   po::CsrSymbolic s;
 };
 int po_csr_symbolic_create(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, po_csr_symbolic *out) {
+  return po_csr_symbolic_create_split(nvars, nwcon, rowp, cols, 0, out);
+}
+int po_csr_symbolic_dense_columns(po_csr_symbolic h, const int **cols, int *count) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(count);
+  *count = (int)h->s.dense_cols.size();
+  if (cols) *cols = h->s.dense_cols.empty() ? nullptr : h->s.dense_cols.data();
+  return PO_OK;
+}
+int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
+                                 po_csr_symbolic *out) {
   PO_CHECK_PTR(rowp);
   PO_CHECK_PTR(out);
-  if (nwcon < 0 || nvars < 0 || (rowp[nwcon] > 0 && !cols)) {
+  if (nwcon < 0 || nvars < 0 || min_rows < -1 || (rowp[nwcon] > 0 && !cols)) {
     po::set_error("po_csr_symbolic_create: bad arguments");
     return PO_ERR_ARG;
   }
   po_csr_symbolic h = new po_csr_symbolic_s;
-  int rc = po::csr_analyse(nvars, nwcon, rowp, cols, &h->s);
+  int rc = po::csr_analyse(nvars, nwcon, rowp, cols, &h->s, min_rows);
   if (rc != PO_OK) {
     delete h;
     return rc;
@@ -847,6 +875,15 @@ int po_problem_set_chain(po_problem p, int span, int stride, int reverse_cols) {
     return PO_ERR_ARG;
   }
   return q->setChain(span, stride, reverse_cols);
+}
+int po_problem_set_chain_dense(po_problem p, int span, int stride, int reverse_cols, int dense_vars) {
+  PO_CHECK_PTR(p);
+  SeparableProblem *q = dynamic_cast<SeparableProblem *>(p->p);
+  if (!q) {
+    po::set_error("po_problem_set_chain_dense needs a built-in separable problem");
+    return PO_ERR_ARG;
+  }
+  return q->setChain(span, stride, reverse_cols, dense_vars);
 }
 int po_problem_sparse_sizes(po_problem p, int64_t *nwcon_local, int64_t *nwinequality_local) {
   PO_CHECK_PTR(p);

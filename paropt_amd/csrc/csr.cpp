@@ -146,19 +146,19 @@ struct Dissector {
 }  // namespace
 
 static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int *cols, CsrSymbolic *out,
-                            bool allow_fronts);
+                            bool allow_fronts, int64_t min_rows);
 
-int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out) {
-  int rc = csr_analyse_impl(n, w, rowp, cols, out, dbg_switch(SW_NO_FRONTS) <= 0);
+int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows) {
+  int rc = csr_analyse_impl(n, w, rowp, cols, out, dbg_switch(SW_NO_FRONTS) <= 0, min_rows);
   if (rc == PO_ERR_NUMERIC) {  // a chain that is not a dense front after all: schedule row by row
     *out = CsrSymbolic();
-    rc = csr_analyse_impl(n, w, rowp, cols, out, false);
+    rc = csr_analyse_impl(n, w, rowp, cols, out, false, min_rows);
   }
   return rc;
 }
 
 static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int *cols, CsrSymbolic *out,
-                            bool allow_fronts) {
+                            bool allow_fronts, int64_t min_rows) {
   CsrSymbolic &s = *out;
   if (w64 < 0 || n64 < 0 || w64 > 2000000000LL || n64 > 2000000000LL) {
     set_error("sparse Jacobian: sizes out of range (nwcon %lld, nvars %lld)", (long long)w64, (long long)n64);
@@ -215,18 +215,64 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
   for (int j = 0; j < n; j++) {
     const double cnt = s.colp[j + 1];
     pairs += cnt * cnt;
-    s.colp[j + 1] += s.colp[j];
+  }
+  // The dense-column rule (csr.hpp).  A qualifying column leaves the transposed index, and with it the pattern of
+  // S, the ordering and the factor; its entries are recorded on their own.
+  int64_t dense_from = 0;  // 0: no column is taken out
+  if (min_rows > 0) {
+    dense_from = min_rows;
+  } else if (min_rows == 0 && pairs > 1.5e9) {
+    dense_from = std::max<int64_t>(1024, w / 8);
+  }
+  s.dense_cols.clear();
+  s.dense_ptr.assign(1, 0);
+  long long qualified = 0;
+  if (dense_from > 0) {
+    for (int j = 0; j < n; j++) qualified += s.colp[j + 1] >= dense_from ? 1 : 0;
+    if (qualified > kMaxDenseCols) {
+      set_error("sparse Jacobian: %lld columns qualify as dense (at least %lld entries each), more than the %d a "
+                "low-rank correction takes", qualified, (long long)dense_from, kMaxDenseCols);
+      return PO_ERR_ARG;
+    }
+    for (int j = 0; j < n; j++) {
+      const int cnt = s.colp[j + 1];
+      if (cnt < dense_from) continue;
+      pairs -= (double)cnt * cnt;
+      s.dense_cols.push_back(j);
+      s.dense_ptr.push_back(s.dense_ptr.back() + cnt);
+      s.colp[j + 1] = 0;
+    }
   }
   if (pairs > 1.5e9) {
-    set_error("sparse Jacobian: Aw Aw^T would have more than 1.5e9 entries (a dense column?)");
+    if (dense_from > 0) {
+      set_error("sparse Jacobian: Aw Aw^T would have more than 1.5e9 entries (a dense column?) after %lld columns "
+                "with at least %lld entries qualified as dense and were taken out", qualified, (long long)dense_from);
+    } else {
+      set_error("sparse Jacobian: Aw Aw^T would have more than 1.5e9 entries (a dense column?)");
+    }
     return PO_ERR_ARG;
   }
-  s.rowsT.resize(nnz);
-  s.srcT.resize(nnz);
+  for (int j = 0; j < n; j++) s.colp[j + 1] += s.colp[j];
+  s.rowsT.resize(s.colp[n]);
+  s.srcT.resize(s.colp[n]);
+  s.dense_rows.resize(s.dense_ptr.back());
+  s.dense_slot.resize(s.dense_ptr.back());
   {
     std::vector<int> fill(s.colp.begin(), s.colp.end() - 1);
+    std::vector<int> dense_of, dfill(s.dense_ptr.begin(), s.dense_ptr.end() - 1);
+    if (!s.dense_cols.empty()) {
+      dense_of.assign(n, -1);
+      for (size_t j = 0; j < s.dense_cols.size(); j++) dense_of[s.dense_cols[j]] = (int)j;
+    }
     for (int i = 0; i < w; i++) {
       for (int p = s.rowp[i]; p < s.rowp[i + 1]; p++) {
+        const int jd = dense_of.empty() ? -1 : dense_of[s.cols[p]];
+        if (jd >= 0) {
+          const int q = dfill[jd]++;
+          s.dense_rows[q] = i;
+          s.dense_slot[q] = p;
+          continue;
+        }
         const int q = fill[s.cols[p]]++;
         s.rowsT[q] = i;
         s.srcT[q] = p;
@@ -515,6 +561,8 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
       s.front_ptr[l + 1] = (int)s.front_start.size();
     }
   }
+  s.dense_pos.resize(s.dense_rows.size());
+  for (size_t q = 0; q < s.dense_rows.size(); q++) s.dense_pos[q] = s.iperm[s.dense_rows[q]];
   return PO_OK;
 }
 
@@ -567,7 +615,38 @@ CsrSparse::~CsrSparse() {
   dfree(ones);
   dfree(wwork);
   dfree(d_flag);
+  (void)freeDense();
   if (cw) vec_decref(cw);
+}
+
+int CsrSparse::freeDense() {
+  dfree(Vd);
+  dfree(Yv);
+  dfree(Vind);
+  dfree(Kfac);
+  dfree(Zd);
+  dfree(part);
+  dfree(spanel);
+  dfree(d_dmask);
+  dfree(d_dcols);
+  dfree(d_dptr);
+  dfree(d_dpos);
+  dfree(d_dslot);
+  part_cap = spanel_cap = 0;
+  return PO_OK;
+}
+
+int CsrSparse::densePartials(int nv) {
+  const int r = ndense();
+  if (nv <= part_cap) return PO_OK;
+  PO_HIP(hipStreamSynchronize(ctx->stream));  // (grows a few times in the life of a pattern)
+  dfree(part);
+  dfree(Zd);
+  part_cap = 0;
+  PO_HIP(hipMalloc((void **)&part, ((size_t)dense_nb * r * nv + 4) * sizeof(double)));
+  PO_HIP(hipMalloc((void **)&Zd, ((size_t)r * nv + 4) * sizeof(double)));
+  part_cap = nv;
+  return PO_OK;
 }
 
 static int group_for(double avg) {
@@ -578,7 +657,7 @@ static int group_for(double avg) {
 }
 
 int CsrSparse::setPattern(const int *rowp, const int *cols) {
-  PO_TRY(csr_analyse(n, w, rowp, cols, &sym));
+  PO_TRY(csr_analyse(n, w, rowp, cols, &sym, dense_min_rows));
   nnz = sym.nnz;
   user_rowp.assign(rowp, rowp + w + 1);
   user_cols.assign(cols, cols + nnz);
@@ -649,7 +728,32 @@ int CsrSparse::setPattern(const int *rowp, const int *cols) {
   }
   nlevels_f = (int)sym.fwd_ptr.size() - 1;
   spmv_group = group_for(w > 0 ? (double)nnz / (double)w : 0.0);
-  spmvT_group = group_for(n > 0 ? (double)nnz / (double)n : 0.0);
+  // (the transposed index holds the sparse columns alone)
+  spmvT_group = group_for(n > 0 ? (double)sym.rowsT.size() / (double)n : 0.0);
+  PO_TRY(freeDense());
+  if (const int r = ndense()) {
+    dense_nb = dense_dot_blocks(w);
+    dense_ld = (w + 3) / 4 * 4 + 4;
+    dense_maxlen = 0;
+    for (int j = 0; j < r; j++) dense_maxlen = std::max(dense_maxlen, sym.dense_ptr[j + 1] - sym.dense_ptr[j]);
+    std::vector<unsigned char> mask((size_t)n, 0);
+    for (int j : sym.dense_cols) mask[j] = 1;
+    PO_TRY(upload(d_dmask, mask));
+    PO_TRY(upload(d_dcols, sym.dense_cols));
+    PO_TRY(upload(d_dptr, sym.dense_ptr));
+    PO_TRY(upload(d_dpos, sym.dense_pos));
+    PO_TRY(upload(d_dslot, sym.dense_slot));
+    const size_t pbytes = (size_t)r * dense_ld * sizeof(double);
+    PO_HIP(hipMalloc((void **)&Vd, pbytes));
+    PO_HIP(hipMalloc((void **)&Yv, pbytes));
+    PO_HIP(hipMalloc((void **)&Kfac, ((size_t)r * r + 4) * sizeof(double)));
+    PO_HIP(hipMemset(Vd, 0, pbytes));  // the positions outside the pattern stay zero for good
+    PO_HIP(hipMemset(Yv, 0, pbytes));
+    PO_HIP(hipMemset(Kfac, 0, ((size_t)r * r + 4) * sizeof(double)));
+    PO_TRY(densePartials(std::max(r, 32)));  // (wider panels grow it once)
+    PO_HIP(hipDeviceSynchronize());
+    PO_TRY(k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, vals, r, dense_maxlen, dense_ld, Vd));
+  }
   return PO_OK;
 }
 
@@ -700,8 +804,9 @@ int CsrSparse::upgradeFromLight() {
 }
 
 int CsrSparse::valuesChanged() {
-  if (light || vals == data || nnz == 0) return PO_OK;
-  return k_csr_gather(ctx, vals, data, d_src, nnz);
+  if (light || nnz == 0) return PO_OK;
+  if (vals != data) PO_TRY(k_csr_gather(ctx, vals, data, d_src, nnz));
+  return k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, vals, ndense(), dense_maxlen, dense_ld, Vd);
 }
 
 int CsrSparse::spmv(double alpha, const double *px, double *out) {
@@ -709,7 +814,32 @@ int CsrSparse::spmv(double alpha, const double *px, double *out) {
 }
 
 int CsrSparse::spmvT(double alpha, const double *pzw, double *out) {
-  return k_csr_spmvT(ctx, spmvT_group, d_colp, d_rowsT, d_srcT, vals, n, alpha, pzw, out, nullptr, out);
+  PO_TRY(k_csr_spmvT(ctx, spmvT_group, d_colp, d_rowsT, d_srcT, vals, n, alpha, pzw, out, nullptr, out));
+  return denseColumnsOut(false, pzw, d_perm, alpha, out, nullptr, out);
+}
+
+int CsrSparse::denseColumnsOut(bool pattern_only, const double *y, const int *idx, double alpha, const double *bx,
+                               const double *dscale, double *out) {
+  const int r = ndense();
+  if (r == 0 || w <= 0) return PO_OK;
+  if (pattern_only && !Vind) {  // the indicator of V, made when the first column sum asks for it
+    const size_t pbytes = (size_t)r * dense_ld * sizeof(double);
+    PO_HIP(hipMalloc((void **)&Vind, pbytes));
+    PO_HIP(hipMemsetAsync(Vind, 0, pbytes, ctx->stream));
+    PO_TRY(k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, nullptr, r, dense_maxlen, dense_ld, Vind));
+  }
+  const double *B[1] = {y};
+  PO_TRY(k_dense_dot(ctx, pattern_only ? Vind : Vd, dense_ld, r, B, 1, idx, w, part));
+  return k_dense_out(ctx, part, dense_nb, r, d_dcols, alpha, bx, dscale, out);
+}
+
+int CsrSparse::lowRankStep(double *const *Y, int nv) {
+  const int r = ndense();
+  if (r == 0 || nv <= 0 || w <= 0) return PO_OK;
+  PO_TRY(densePartials(nv));
+  PO_TRY(k_dense_dot(ctx, Yv, dense_ld, r, Y, nv, nullptr, w, part));
+  PO_TRY(k_dense_ksolve(ctx, part, dense_nb, r, nv, Kfac, Zd));
+  return k_dense_update(ctx, Yv, dense_ld, r, Y, nv, Zd, w);
 }
 
 int CsrSparse::innerProduct(double alpha, const double *cvec, double *out) {
@@ -721,11 +851,16 @@ int CsrSparse::colSum(double scale, const double *y, double *out) {
     set_error("CsrSparse::colSum on a light (grouped) pattern");
     return PO_ERR_ARG;
   }
-  return k_csr_colsum(ctx, d_colp, d_rowsT, n, scale, y, out);
+  PO_TRY(k_csr_colsum(ctx, d_colp, d_rowsT, n, scale, y, out));
+  return denseColumnsOut(true, y, d_perm, scale, nullptr, nullptr, out);
 }
 
 int CsrSparse::panelPermuted(const double *d, const double *const *P, int nv, double *const *U) {
   return k_csr_panel(ctx, d_rowp, d_cols, vals, w, d, P, nv, U, d_iperm);
+}
+
+int CsrSparse::panelNatural(const double *d, const double *const *P, int nv, double *const *U) {
+  return k_csr_panel(ctx, d_rowp, d_cols, vals, w, d, P, nv, U, nullptr);
 }
 
 // one thread per row when the rows of a level are short, or when there are so many that even long rows keep
@@ -737,7 +872,7 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
   PO_HIP(hipMemsetAsync(Lvals, 0, ((size_t)sym.nnzL + 4) * sizeof(double), ctx->stream));
   PO_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), ctx->stream));
   PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_slot,
-                        (int64_t)sym.ent_slot.size(), Lvals));
+                        (int64_t)sym.ent_slot.size(), Lvals, d_dmask));
   for (int l = 0; l < nlevels_f; l++) {
     const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
     const int oe = sym.ord_end[l], f0 = sym.front_ptr[l], nf = sym.front_ptr[l + 1] - f0;
@@ -745,6 +880,15 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
                         thinLevel(sym.fwd_maxlen[l], oe - b), sym.fwd_maxlen[l]));
     PO_TRY(k_chol_fronts(ctx, d_Lrowp, d_Lcols, Lvals, oe, e - oe, d_front_of, d_fstart + f0, d_fsize + f0, nf,
                          sym.front_maxdesc[l], d_flag));
+  }
+  if (const int r = ndense()) {
+    // Yv = L^-1 P V, T = Yv^T Yv, K = E^-1 + T = Lk Lk^T: all queued ahead of the one flag read below
+    PO_HIP(hipMemcpyAsync(Yv, Vd, (size_t)r * dense_ld * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    std::vector<double *> cols((size_t)r);
+    for (int j = 0; j < r; j++) cols[j] = Yv + (int64_t)j * dense_ld;
+    PO_TRY(solveInPlace(cols.data(), r, true, false));
+    PO_TRY(k_dense_dot(ctx, Yv, dense_ld, r, cols.data(), r, nullptr, w, part));
+    PO_TRY(k_dense_kfactor(ctx, part, dense_nb, r, dinv, d_dcols, Kfac, d_flag, w));
   }
   int flag[4] = {0, 0, 0, 0};
   PO_HIP(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
@@ -771,8 +915,13 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
         if (v < cmin) cmin = v;
       }
     }
-    set_error("sparse Cholesky: non-positive pivot in row %d of the permuted Schur complement "
-              "(min D^-1 %.3e, min C %.3e, %ld non-finite inputs)", flag[1], dmin, cmin, bad);
+    if (flag[1] >= w) {
+      set_error("sparse Cholesky: non-positive pivot in dense column %d of the low-rank correction "
+                "(min D^-1 %.3e, min C %.3e, %ld non-finite inputs)", sym.dense_cols[flag[1] - w], dmin, cmin, bad);
+    } else {
+      set_error("sparse Cholesky: non-positive pivot in row %d of the permuted Schur complement "
+                "(min D^-1 %.3e, min C %.3e, %ld non-finite inputs)", flag[1], dmin, cmin, bad);
+    }
     if (breakdowns++ == 0 && ctx->rank == 0) {
       fprintf(stderr, "ParOpt warning: sparse Cholesky breakdown, the quasi-definite matrix is not positive "
                       "definite (min D^-1 %.3e, min C %.3e); continuing as the reference does\n", dmin, cmin);
@@ -826,10 +975,41 @@ int CsrSparse::applyK0(const double *dinv, const double *bx, const double *bw, d
   PO_TRY(k_csr_spmv(ctx, spmv_group, d_rowp, d_cols, vals, w, -1.0, bx, dinv, bw ? 1.0 : 0.0, bw, wwork,
                     d_iperm));
   double *Y[1] = {wwork};
-  PO_TRY(solveInPlace(Y, 1, true, true));
+  if (ndense() == 0) {
+    PO_TRY(solveInPlace(Y, 1, true, true));
+  } else {
+    PO_TRY(solveInPlace(Y, 1, true, false));
+    PO_TRY(lowRankStep(Y, 1));
+    PO_TRY(solveInPlace(Y, 1, false, true));
+  }
   PO_TRY(k_csr_gather(ctx, yw, wwork, d_iperm, w));
-  // yx = dinv o (bx + Aw^T yw)
-  return k_csr_spmvT(ctx, spmvT_group, d_colp, d_rowsT, d_srcT, vals, n, 1.0, yw, bx, dinv, yx);
+  // yx = dinv o (bx + Aw^T yw); the dense columns take yw where it still lies in the elimination order
+  PO_TRY(k_csr_spmvT(ctx, spmvT_group, d_colp, d_rowsT, d_srcT, vals, n, 1.0, yw, bx, dinv, yx));
+  return denseColumnsOut(false, wwork, nullptr, 1.0, bx, dinv, yx);
+}
+
+int CsrSparse::solvePanel(const double *const *U, int nv, double *const *Yw) {
+  if (w <= 0 || nv <= 0) return PO_OK;
+  if (nv > kMaxPanel) {  // independent columns: slabs of one kernel's pointer table
+    for (int j0 = 0; j0 < nv; j0 += kMaxPanel)
+      PO_TRY(solvePanel(U + j0, nv - j0 > kMaxPanel ? kMaxPanel : nv - j0, Yw + j0));
+    return PO_OK;
+  }
+  const int64_t ld = (w + 3) / 4 * 4 + 4;
+  if (nv > spanel_cap) {
+    PO_HIP(hipStreamSynchronize(ctx->stream));  // (grows a few times in the life of a pattern)
+    dfree(spanel);
+    spanel_cap = 0;
+    PO_HIP(hipMalloc((void **)&spanel, (size_t)nv * ld * sizeof(double)));
+    spanel_cap = nv;
+  }
+  std::vector<double *> Y((size_t)nv);
+  for (int j = 0; j < nv; j++) Y[j] = spanel + (int64_t)j * ld;
+  PO_TRY(k_csr_panel_gather(ctx, Y.data(), U, nv, d_perm, 1.0, w));
+  PO_TRY(solveInPlace(Y.data(), nv, true, false));
+  PO_TRY(lowRankStep(Y.data(), nv));
+  PO_TRY(solveInPlace(Y.data(), nv, false, true));
+  return k_csr_panel_gather(ctx, Yw, Y.data(), nv, d_iperm, -1.0, w);
 }
 
 const char *CsrSparse::factorInfo() {
@@ -842,6 +1022,7 @@ const char *CsrSparse::factorInfo() {
            (long long)w, nlevels_f, (int)sym.front_start.size(), (long long)sym.nnzS, (long long)sym.nnzL,
            sym.nnzS > 0 ? (double)sym.nnzL / (double)sym.nnzS : 0.0, tri > 0 ? (double)sym.nnzL / tri : 0.0);
   info = buf;
+  if (ndense() > 0) info += " ndense " + std::to_string(ndense());
   return info.c_str();
 }
 

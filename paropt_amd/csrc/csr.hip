@@ -210,17 +210,22 @@ int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, in
 
 // One thread per structural entry (a, b) of lower(P S P^T): the two column-sorted rows of Aw are merged,
 // Lvals[slot] = [a == b] cdiag[a] + sum_k Aw[a,k] dinv[k] Aw[b,k].  Fill entries were zeroed by the caller.
+// SKIP: the columns marked in `skip` (the dense columns, csr.hpp) stay out of the sums -- S0 is assembled.
+template <bool SKIP>
 __global__ void __launch_bounds__(kBlock)
     csr_assemble_kernel(const int *__restrict__ rowp, const int *__restrict__ cols,
                         const double *__restrict__ vals, const double *__restrict__ dinv,
                         const double *__restrict__ cdiag, const int *__restrict__ ent_a,
                         const int *__restrict__ ent_b, const int *__restrict__ ent_slot, int64_t nent,
-                        double *__restrict__ Lvals) {
+                        double *__restrict__ Lvals, const unsigned char *__restrict__ skip) {
   PO_C_LOOP(e, nent) {
     const int a = ent_a[e], b = ent_b[e];
     double acc = 0.0;
     if (a == b) {
-      for (int q = rowp[a]; q < rowp[a + 1]; q++) acc += vals[q] * vals[q] * dinv[cols[q]];
+      for (int q = rowp[a]; q < rowp[a + 1]; q++) {
+        if (SKIP && skip[cols[q]]) continue;
+        acc += vals[q] * vals[q] * dinv[cols[q]];
+      }
       acc += cdiag[a];
     } else {
       int qa = rowp[a], qb = rowp[b];
@@ -228,7 +233,7 @@ __global__ void __launch_bounds__(kBlock)
       while (qa < ea && qb < eb) {
         const int ka = cols[qa], kb = cols[qb];
         if (ka == kb) {
-          acc += vals[qa] * dinv[ka] * vals[qb];
+          if (!SKIP || !skip[ka]) acc += vals[qa] * dinv[ka] * vals[qb];
           qa++;
           qb++;
         } else if (ka < kb) {
@@ -243,10 +248,15 @@ __global__ void __launch_bounds__(kBlock)
 }
 int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
                    const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
-                   double *Lvals) {
+                   double *Lvals, const unsigned char *skip) {
   if (nent <= 0) return PO_OK;
-  PO_CLAUNCH(csr_assemble_kernel, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b, ent_slot,
-             nent, Lvals);
+  if (skip) {
+    PO_CLAUNCH(csr_assemble_kernel<true>, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
+               ent_slot, nent, Lvals, skip);
+  } else {
+    PO_CLAUNCH(csr_assemble_kernel<false>, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
+               ent_slot, nent, Lvals, skip);
+  }
   return PO_OK;
 }
 
@@ -280,6 +290,46 @@ __global__ void __launch_bounds__(kBlock)
 int k_chain_jac(Ctx *c, const double *x, int64_t w, int span, int stride, int reverse, double *data) {
   if (w <= 0) return PO_OK;
   PO_CLAUNCH(chain_jac_kernel, cgrid(c, w * span), kBlock, x, w, span, stride, reverse, data);
+  return PO_OK;
+}
+// The same with `nd` further variables xd[0..nd) that enter every row (a min-max formulation's epigraph variables):
+// cw_i = 1 - sum_{k<span} x[i*stride + k]^2 - sum_{j<nd} xd[j]^2, rows of span + nd entries
+__global__ void __launch_bounds__(kBlock)
+    chain_dense_con_kernel(const double *__restrict__ x, int64_t w, int span, int stride,
+                           const double *__restrict__ xd, int nd, double *__restrict__ cw) {
+  PO_C_LOOP(i, w) {
+    double v = 1.0;
+    for (int k = 0; k < span; k++) {
+      const double xi = x[i * stride + k];
+      v -= xi * xi;
+    }
+    for (int j = 0; j < nd; j++) v -= xd[j] * xd[j];
+    cw[i] = v;
+  }
+}
+__global__ void __launch_bounds__(kBlock)
+    chain_dense_jac_kernel(const double *__restrict__ x, int64_t w, int span, int stride, int reverse,
+                           const double *__restrict__ xd, int nd, double *__restrict__ data) {
+  const int len = span + nd;
+  PO_C_LOOP(e, w * len) {
+    const int64_t i = e / len;
+    const int s = (int)(e - i * len);
+    if (s >= span) {
+      data[e] = -2.0 * xd[s - span];
+    } else {
+      data[e] = -2.0 * x[i * stride + (reverse ? span - 1 - s : s)];
+    }
+  }
+}
+int k_chain_dense_con(Ctx *c, const double *x, int64_t w, int span, int stride, const double *xd, int nd, double *cw) {
+  if (w <= 0) return PO_OK;
+  PO_CLAUNCH(chain_dense_con_kernel, cgrid(c, w), kBlock, x, w, span, stride, xd, nd, cw);
+  return PO_OK;
+}
+int k_chain_dense_jac(Ctx *c, const double *x, int64_t w, int span, int stride, int reverse, const double *xd, int nd,
+                      double *data) {
+  if (w <= 0) return PO_OK;
+  PO_CLAUNCH(chain_dense_jac_kernel, cgrid(c, w * (span + nd)), kBlock, x, w, span, stride, reverse, xd, nd, data);
   return PO_OK;
 }
 
@@ -972,6 +1022,221 @@ int k_trsv_bwd_level(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows
                      Ltrows, Ltsrc, Lvals, rows, nrows, t, nv);
   c->n_launches++;
   PO_HIP(hipGetLastError());
+  return PO_OK;
+}
+
+// ---- dense columns: the low-rank correction S^-1 = S0^-1 - S0^-1 V K^-1 V^T S0^-1 (csr.hpp) --------------------------
+// The r <= kMaxDenseCols dense columns live as r w-vectors with a common stride (V, and Yv = L^-1 P V).  Every sum
+// below has one writer and a fixed order: a two-stage block reduction whose grid depends on w alone, no atomics, and
+// nothing leaves the device -- these products belong to one rank's constraints and never meet a collective.
+
+// V_j[pos[e]] = vals[slot[e]] (vals == nullptr: 1) over the entries e of dense column j = blockIdx.y
+__global__ void __launch_bounds__(kBlock)
+    dense_scatter_kernel(const int *__restrict__ ptr, const int *__restrict__ pos, const int *__restrict__ slot,
+                         const double *__restrict__ vals, int64_t ld, double *__restrict__ V) {
+  const int j = blockIdx.y;
+  const int b = ptr[j], e = ptr[j + 1];
+  double *v = V + (int64_t)j * ld;
+  for (int64_t q = (int64_t)b + blockIdx.x * kBlock + threadIdx.x; q < e; q += (int64_t)gridDim.x * kBlock)
+    v[pos[q]] = vals ? vals[slot[q]] : 1.0;
+}
+int k_dense_scatter(Ctx *c, const int *ptr, const int *pos, const int *slot, const double *vals, int r, int maxlen,
+                    int64_t ld, double *V) {
+  if (r <= 0 || maxlen <= 0) return PO_OK;
+  hipLaunchKernelGGL(dense_scatter_kernel, dim3(cgrid(c, maxlen), r), dim3(kBlock), 0, c->stream, ptr, pos, slot, vals,
+                     ld, V);
+  c->n_launches++;
+  PO_HIP(hipGetLastError());
+  return PO_OK;
+}
+
+// Stage 1 of G = A^T B (r x nv): workgroup (b, j, i0 / kDenseIB) sums its share of the rows k for column j of B and
+// kDenseIB columns of A, part[(b r + i) nv + j] = sum_k A_i[k] B_j[idx ? idx[k] : k]
+constexpr int kDenseIB = 8;
+__global__ void __launch_bounds__(kBlock)
+    dense_dot_kernel(const double *__restrict__ A, int64_t lda, int r, PtrTable B, int nv,
+                     const int *__restrict__ idx, int64_t w, double *__restrict__ part) {
+  const int j = blockIdx.y, i0 = blockIdx.z * kDenseIB;
+  const double *__restrict__ bj = B.p[j];
+  double acc[kDenseIB];
+#pragma unroll
+  for (int ii = 0; ii < kDenseIB; ii++) acc[ii] = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < w; k += (int64_t)gridDim.x * kBlock) {
+    const double bv = bj[idx ? idx[k] : k];
+#pragma unroll
+    for (int ii = 0; ii < kDenseIB; ii++) {
+      if (i0 + ii < r) acc[ii] += A[(int64_t)(i0 + ii) * lda + k] * bv;
+    }
+  }
+  __shared__ double red[kDenseIB][kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int ii = 0; ii < kDenseIB; ii++) {
+    const double v = wave_sum(acc[ii]);
+    if (lane == 0) red[ii][wave] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kDenseIB && i0 + (int)threadIdx.x < r) {
+    const int ii = threadIdx.x;
+    part[((int64_t)blockIdx.x * r + i0 + ii) * nv + j] = ((red[ii][0] + red[ii][1]) + red[ii][2]) + red[ii][3];
+  }
+}
+int dense_dot_blocks(int64_t w) {
+  int64_t b = (w + 4 * kBlock - 1) / (4 * kBlock);
+  return b < 1 ? 1 : (b > 256 ? 256 : (int)b);
+}
+int k_dense_dot(Ctx *c, const double *A, int64_t lda, int r, const double *const *B, int nv, const int *idx,
+                int64_t w, double *part) {
+  if (r <= 0 || nv <= 0) return PO_OK;
+  if (nv > kMaxPanel || r > kMaxDenseCols) {
+    set_error("dense-column panel product: %d x %d exceeds %d x %d", r, nv, kMaxDenseCols, kMaxPanel);
+    return PO_ERR_ARG;
+  }
+  PtrTable bt;
+  for (int j = 0; j < kMaxPanel; j++) bt.p[j] = j < nv ? B[j] : B[0];
+  hipLaunchKernelGGL(dense_dot_kernel, dim3(dense_dot_blocks(w), nv, (r + kDenseIB - 1) / kDenseIB), dim3(kBlock), 0,
+                     c->stream, A, lda, r, bt, nv, idx, w, part);
+  c->n_launches++;
+  PO_HIP(hipGetLastError());
+  return PO_OK;
+}
+
+// Stage 2, one workgroup: K = diag(1 / dinv[J]) + sum_b part[b] (r x r) and its Cholesky factor in LDS, written to
+// Kfac (row-major, lower).  A non-positive pivot raises the factorization's breakdown flag (row w + i) and becomes 1.
+__global__ void __launch_bounds__(kBlock)
+    dense_kfactor_kernel(const double *__restrict__ part, int nb, int r, const double *__restrict__ dinv,
+                         const int *__restrict__ J, double *__restrict__ Kfac, int *flag, int w) {
+  __shared__ double K[kMaxDenseCols * kMaxDenseCols];
+  const int tid = threadIdx.x;
+  for (int t = tid; t < r * r; t += kBlock) {
+    const int i = t / r, j = t - i * r;
+    double s = 0.0;
+    for (int b = 0; b < nb; b++) s += part[((int64_t)b * r + i) * r + j];
+    if (i == j) s += 1.0 / dinv[J[i]];
+    K[t] = s;
+  }
+  __syncthreads();
+  for (int k = 0; k < r; k++) {
+    if (tid == 0) {
+      double a = K[k * r + k];
+      if (!(a > 0.0)) {
+        flag[0] = 1;
+        flag[1] = w + k;
+        a = 1.0;
+      }
+      K[k * r + k] = sqrt(a);
+    }
+    __syncthreads();
+    const double piv = K[k * r + k];
+    for (int i = k + 1 + tid; i < r; i += kBlock) K[i * r + k] /= piv;
+    __syncthreads();
+    const int m = r - k - 1;
+    for (int t = tid; t < m * m; t += kBlock) {
+      const int i = k + 1 + t / m, j = k + 1 + t % m;
+      if (j <= i) K[i * r + j] -= K[i * r + k] * K[j * r + k];
+    }
+    __syncthreads();
+  }
+  for (int t = tid; t < r * r; t += kBlock) Kfac[t] = K[t];
+}
+int k_dense_kfactor(Ctx *c, const double *part, int nb, int r, const double *dinv, const int *J, double *Kfac,
+                    int *flag, int64_t w) {
+  if (r <= 0) return PO_OK;
+  PO_CLAUNCH(dense_kfactor_kernel, 1, kBlock, part, nb, r, dinv, J, Kfac, flag, (int)w);
+  return PO_OK;
+}
+
+// Its twin: G = sum_b part[b] (r x nv), Z = K^-1 G with one thread per column, Z[i nv + j]
+__global__ void __launch_bounds__(kBlock)
+    dense_ksolve_kernel(const double *__restrict__ part, int nb, int r, int nv, const double *__restrict__ Kfac,
+                        double *Z) {
+  __shared__ double K[kMaxDenseCols * kMaxDenseCols];
+  for (int t = threadIdx.x; t < r * r; t += kBlock) K[t] = Kfac[t];
+  __syncthreads();
+  for (int j = threadIdx.x; j < nv; j += kBlock) {
+    for (int i = 0; i < r; i++) {
+      double s = 0.0;
+      for (int b = 0; b < nb; b++) s += part[((int64_t)b * r + i) * nv + j];
+      for (int k = 0; k < i; k++) s -= K[i * r + k] * Z[k * nv + j];
+      Z[i * nv + j] = s / K[i * r + i];
+    }
+    for (int i = r - 1; i >= 0; i--) {
+      double s = Z[i * nv + j];
+      for (int k = i + 1; k < r; k++) s -= K[k * r + i] * Z[k * nv + j];
+      Z[i * nv + j] = s / K[i * r + i];
+    }
+  }
+}
+int k_dense_ksolve(Ctx *c, const double *part, int nb, int r, int nv, const double *Kfac, double *Z) {
+  if (r <= 0 || nv <= 0) return PO_OK;
+  PO_CLAUNCH(dense_ksolve_kernel, 1, kBlock, part, nb, r, nv, Kfac, Z);
+  return PO_OK;
+}
+
+// Y_j[k] -= sum_i Yv_i[k] Z[i nv + j], the coefficients read from device memory
+__global__ void __launch_bounds__(kBlock)
+    dense_update_kernel(const double *__restrict__ Yv, int64_t ld, int r, PtrTableW Y, int nv,
+                        const double *__restrict__ Z, int64_t w) {
+  PO_C_LOOP(k, w) {
+    for (int i0 = 0; i0 < r; i0 += kDenseIB) {
+      double yv[kDenseIB];
+#pragma unroll
+      for (int ii = 0; ii < kDenseIB; ii++) yv[ii] = i0 + ii < r ? Yv[(int64_t)(i0 + ii) * ld + k] : 0.0;
+      for (int j = 0; j < nv; j++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int ii = 0; ii < kDenseIB; ii++) {
+          if (i0 + ii < r) acc += yv[ii] * Z[(i0 + ii) * nv + j];
+        }
+        Y.p[j][k] -= acc;
+      }
+    }
+  }
+}
+int k_dense_update(Ctx *c, const double *Yv, int64_t ld, int r, double *const *Y, int nv, const double *Z, int64_t w) {
+  if (r <= 0 || nv <= 0 || w <= 0) return PO_OK;
+  PtrTableW t;
+  PO_TRY(fill_table(t, Y, nv));
+  PO_CLAUNCH(dense_update_kernel, cgrid(c, w), kBlock, Yv, ld, r, t, nv, Z, w);
+  return PO_OK;
+}
+
+// The dense columns' share of k_csr_spmvT, r values: out[J[i]] = dscale[J[i]] (bx[J[i]] + alpha sum_b part[b r + i]);
+// bx may alias out
+__global__ void __launch_bounds__(64)
+    dense_out_kernel(const double *__restrict__ part, int nb, int r, const int *__restrict__ J, double alpha,
+                     const double *bx, const double *__restrict__ dscale, double *out) {
+  const int i = threadIdx.x;
+  if (i >= r) return;
+  double s = 0.0;
+  for (int b = 0; b < nb; b++) s += part[(int64_t)b * r + i];
+  const int j = J[i];
+  const double v = (bx ? bx[j] : 0.0) + alpha * s;
+  out[j] = dscale ? dscale[j] * v : v;
+}
+int k_dense_out(Ctx *c, const double *part, int nb, int r, const int *J, double alpha, const double *bx,
+                const double *dscale, double *out) {
+  if (r <= 0) return PO_OK;
+  PO_CLAUNCH(dense_out_kernel, 1, 64, part, nb, r, J, alpha, bx, dscale, out);
+  return PO_OK;
+}
+
+// dst_j[k] = sign * src_j[idx[k]] for a whole panel (into and out of the elimination order)
+__global__ void __launch_bounds__(kBlock)
+    panel_gather_kernel(PtrTableW dst, PtrTable src, int nv, const int *__restrict__ idx, double sign, int64_t w) {
+  PO_C_LOOP(k, w) {
+    const int s = idx[k];
+    for (int j = 0; j < nv; j++) dst.p[j][k] = sign * src.p[j][s];
+  }
+}
+int k_csr_panel_gather(Ctx *c, double *const *dst, const double *const *src, int nv, const int *idx, double sign,
+                       int64_t w) {
+  if (w <= 0 || nv <= 0) return PO_OK;
+  PtrTableW dt;
+  PO_TRY(fill_table(dt, dst, nv));
+  PtrTable st;
+  for (int j = 0; j < kMaxPanel; j++) st.p[j] = j < nv ? src[j] : src[0];
+  PO_CLAUNCH(panel_gather_kernel, cgrid(c, w), kBlock, dt, st, nv, idx, sign, w);
   return PO_OK;
 }
 

@@ -13,6 +13,8 @@
 //                            triangular solves for a whole panel of right-hand sides, CSR/CSC products
 // Everything is rank-local (the reference's sparse constraints never couple ranks), deterministic
 // (no atomics), and there is no host numeric path.
+// Columns of Aw that enter (nearly) every row would make S dense: the analysis takes them out and the
+// device puts them back by a low-rank correction of every solve (CsrSymbolic: DENSE COLUMNS).
 //
 // PARITY UNPINNED for the factorization itself: the reference's ParOptSparseCholesky.cpp needs METIS,
 // which this image lacks, so no reference-run golden exists for it.  What IS pinned: trajectories of
@@ -52,16 +54,29 @@ struct CsrSymbolic {
   int max_front = 0;
   int64_t nnzS = 0, nnzL = 0;
   bool identity_src = true;
+  // DENSE COLUMNS (at most kMaxDenseCols): columns of Aw taken out of S and put back by a low-rank correction,
+  //     S = S0 + V E V^T,  S0 = C + As D^-1 As^T,  V = Aw[:, J],  E = diag(Dinv[J]).
+  // Everything above except rowp/cols/src then describes S0 and As: the transposed index colp/rowsT/srcT leaves the
+  // columns of J empty, the row storage keeps them.  Column dense_cols[j] (ascending) holds the entries
+  // dense_ptr[j] .. dense_ptr[j+1]-1: row dense_rows (ascending), position dense_pos = iperm[row] in the elimination
+  // order, value slot dense_slot in the SORTED value array.  Empty when no column qualifies: every array above is
+  // then what the analysis without the rule produces.
+  std::vector<int> dense_cols, dense_ptr, dense_rows, dense_pos, dense_slot;
 };
 
-// returns PO_OK or PO_ERR_ARG (message set); pure host code, testable without a GPU
-int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out);
+constexpr int kMaxDenseCols = 64;
+
+// returns PO_OK or PO_ERR_ARG (message set); pure host code, testable without a GPU.  min_rows is the dense-column
+// rule: > 0, every column with at least that many entries is dense; 0 (automatic), nothing is taken out unless the
+// pattern would be refused (more than 1.5e9 pairs), then the columns with at least max(1024, w/8) entries; -1, never.
+int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows = 0);
 
 class CsrSparse {
  public:
   CsrSparse(Ctx *c, int64_t n_, int64_t w_);
   ~CsrSparse();
   int setPattern(const int *rowp, const int *cols);
+  int64_t dense_min_rows = 0;  // the dense-column rule of csr_analyse; set before setPattern
   // The pattern was recognised as the grouped one (problem.hpp): only what the user's callbacks and
   // getSparseJacobianData need -- host copies of the pattern, the value array, the constraint vector -- and NO
   // symbolic analysis (at w = 1 M rows it would cost seconds and hundreds of MB that the block form never uses).
@@ -82,12 +97,17 @@ class CsrSparse {
   int colSum(double scale, const double *y, double *out);    // out_j = scale * sum of y over the rows touching j
   // U_j = Aw (d o P_j), rows in the factor's elimination order (only the Gram correction reads them)
   int panelPermuted(const double *d, const double *const *P, int nv, double *const *U);
+  int panelNatural(const double *d, const double *const *P, int nv, double *const *U);  // the same, Aw's row order
   int factor(const double *dinv, const double *cdiag);       // S = diag(cdiag) + Aw diag(dinv) Aw^T = L L^T
   int halfSolve(double *const *U, int nv);                   // U_j <- L^-1 U_j (elimination order, in place)
   // out (natural order) = -S^-1 (U alpha) from the half-solved panel Y = L^-1 U: -L^-T (Y alpha)
   int correction(const double *const *Y, int nv, const double *alpha, double *out);
   // (yx, yw) = K0^-1 (bx, bw); bw may be null; bx must not alias yx
   int applyK0(const double *dinv, const double *bx, const double *bw, double *yx, double *yw);
+  // Yw_j (natural order) = -S^-1 U_j for a whole panel U in natural order, one sweep: permute, forward solve, the
+  // low-rank step, backward solve, un-permute and negate.  U is left alone.
+  int solvePanel(const double *const *U, int nv, double *const *Yw);
+  int ndense() const { return (int)sym.dense_cols.size(); }
   const double *unitWeights() const { return ones; }
   const char *factorInfo();
   // host copies for getSparseJacobianData (src/ParOptProblem.cpp:689-703)
@@ -100,6 +120,20 @@ class CsrSparse {
 
  private:
   int solveInPlace(double *const *Y, int nv, bool forward, bool backward);
+  // dense columns (csr.hpp: CsrSymbolic): Y_j -= Yv K^-1 (Yv^T Y_j) on half-solved columns in the elimination order
+  int lowRankStep(double *const *Y, int nv);
+  // out[J] = dscale[J] (bx[J] + alpha A^T y[J]) with A = V (pattern_only: its indicator) and y in the order `idx` names
+  int denseColumnsOut(bool pattern_only, const double *y, const int *idx, double alpha, const double *bx,
+                      const double *dscale, double *out);
+  int densePartials(int nv);  // room for the block partials of an r x nv product
+  int freeDense();
+  int dense_nb = 1;           // workgroups of the first reduction stage: a function of w alone
+  int64_t dense_ld = 0;       // stride of the r w-vectors below
+  int dense_maxlen = 0, part_cap = 0, spanel_cap = 0;
+  double *Vd = nullptr, *Yv = nullptr, *Vind = nullptr;  // V and L^-1 P V (elimination order); indicator of V, on demand
+  double *Kfac = nullptr, *Zd = nullptr, *part = nullptr, *spanel = nullptr;
+  unsigned char *d_dmask = nullptr;
+  int *d_dcols = nullptr, *d_dptr = nullptr, *d_dpos = nullptr, *d_dslot = nullptr;
   double *vals = nullptr;  // column-sorted values (== data when the user's order is already sorted)
   int *d_rowp = nullptr, *d_cols = nullptr, *d_src = nullptr;
   int *d_colp = nullptr, *d_rowsT = nullptr, *d_srcT = nullptr;
@@ -128,7 +162,7 @@ int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, in
                 const double *const *P, int nv, double *const *U, const int *outperm);
 int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
                    const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
-                   double *Lvals);
+                   double *Lvals, const unsigned char *skip = nullptr);
 int k_chol_level(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, const int *rows, int nrows, int *flag,
                  int thin, int maxlen);
 int k_chol_fronts(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, int row0, int nrows,
@@ -143,8 +177,26 @@ int k_trsv_fwd_level(Ctx *c, const int *Lrowp, const int *Lcols, const double *L
                      double *const *Y, int nv, int thin);
 int k_trsv_bwd_level(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows, const int *Ltsrc,
                      const double *Lvals, const int *rows, int nrows, double *const *Y, int nv, int thin);
+// dense columns (csr.hip): scatter of V, the two-stage panel product and its consumers, the low-rank update
+int k_dense_scatter(Ctx *c, const int *ptr, const int *pos, const int *slot, const double *vals, int r, int maxlen,
+                    int64_t ld, double *V);
+int dense_dot_blocks(int64_t w);
+int k_dense_dot(Ctx *c, const double *A, int64_t lda, int r, const double *const *B, int nv, const int *idx,
+                int64_t w, double *part);
+int k_dense_kfactor(Ctx *c, const double *part, int nb, int r, const double *dinv, const int *J, double *Kfac,
+                    int *flag, int64_t w);
+int k_dense_ksolve(Ctx *c, const double *part, int nb, int r, int nv, const double *Kfac, double *Z);
+int k_dense_update(Ctx *c, const double *Yv, int64_t ld, int r, double *const *Y, int nv, const double *Z, int64_t w);
+int k_dense_out(Ctx *c, const double *part, int nb, int r, const int *J, double alpha, const double *bx,
+                const double *dscale, double *out);
+int k_csr_panel_gather(Ctx *c, double *const *dst, const double *const *src, int nv, const int *idx, double sign,
+                       int64_t w);
 // built-in chain constraints cw_i = 1 - sum_{k<span} x[i*stride + k]^2 and their Jacobian entries
 int k_chain_con(Ctx *c, const double *x, int64_t w, int span, int stride, double *cw);
 int k_chain_jac(Ctx *c, const double *x, int64_t w, int span, int stride, int reverse, double *data);
+// ... plus nd variables xd that enter every row: cw_i -= sum_j xd[j]^2, rows of span + nd entries
+int k_chain_dense_con(Ctx *c, const double *x, int64_t w, int span, int stride, const double *xd, int nd, double *cw);
+int k_chain_dense_jac(Ctx *c, const double *x, int64_t w, int span, int stride, int reverse, const double *xd, int nd,
+                      double *data);
 
 }  // namespace po

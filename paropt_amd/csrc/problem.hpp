@@ -116,6 +116,12 @@ class Problem {
   // owned.  Sets nwcon / nwinequality.
   int setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *rowp, const int *cols);
   CsrSparse *csr = nullptr;
+  // The dense-column rule of the CSR analysis (csr.hpp: csr_analyse), read by setSparseJacobianData.  csr_dense_form:
+  // some rank's pattern has dense columns, so every rank solves through the low-rank form (quasidef.cpp) -- agreed once,
+  // where the pattern is set.
+  int64_t dense_min_rows = 0;
+  bool csr_dense_form = false;
+  int agreeDenseForm();
   // Structured ("grouped") sparse Jacobian: constraint i acts on the nw consecutive local variables
   // start + i (nw + skip) + [0, nw) and every entry of the Jacobian has the same value group_alpha -- the weighting
   // constraints of multi-material topology optimisation (examples/dmo_truss/dmo_truss_analysis.py:650-679,
@@ -217,8 +223,10 @@ class SeparableProblem : public Problem {
   // overlapping nonlinear sparse constraints in CSR form, rank-local like the reference's example
   // (examples/rosenbrock/sparse_rosenbrock.cpp:38-118 is span = 2, stride = 1):
   //   cw_i = 1 - sum_{k<span} x[i*stride + k]^2,  i < (nlocal - span)/stride + 1, all inequalities
-  int setChain(int span, int stride, int reverse_cols);
-  int chain_span = 0, chain_stride = 0, chain_reverse = 0;
+  // chain_dense > 0: the chain runs over the first nlocal - chain_dense variables and the last chain_dense ones enter
+  // every row, cw_i -= sum_j x[nlocal - chain_dense + j]^2 (dense columns of the Jacobian, csr.hpp)
+  int setChain(int span, int stride, int reverse_cols, int dense_vars = 0);
+  int chain_span = 0, chain_stride = 0, chain_reverse = 0, chain_dense = 0;
   Vec *chain_tmp = nullptr;
   int chainHessian(Vec *zw, Vec *px, Vec *h);
   // (the Jacobian hooks of the weighting constraints are the base class's grouped forms)

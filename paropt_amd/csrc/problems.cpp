@@ -57,6 +57,7 @@ int Problem::setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *r
     rec = flag != 0.0;
   }
   CsrSparse *m = new CsrSparse(ctx, nlocal, nwcon_);
+  m->dense_min_rows = dense_min_rows;
   int rc = rec ? m->setPatternLight(rowp, cols) : m->setPattern(rowp, cols);
   if (rc != PO_OK) {
     delete m;
@@ -64,6 +65,7 @@ int Problem::setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *r
   }
   delete csr;
   csr = m;
+  PO_TRY(agreeDenseForm());
   nwcon = nwcon_;
   nwinequality = nwineq_;
   grouped = rec;
@@ -96,9 +98,17 @@ int Problem::csrValuesChanged() {
   gmap = GroupMap();
   // (mid-run, inside a gradient evaluation: whatever the interior point built with the grouped solver stands until
   // its next setUpKKTSystem rebuilds it)
-  PO_TRY(chooseSolver(userSolverTable(), nwblock));
   PO_TRY(csr->upgradeFromLight());
+  PO_TRY(agreeDenseForm());
+  PO_TRY(chooseSolver(userSolverTable(), nwblock));
   return csr->valuesChanged();
+}
+
+int Problem::agreeDenseForm() {
+  double flag = csr && csr->ndense() > 0 ? 1.0 : 0.0;
+  if (ctx->size > 1) PO_TRY(comm_allreduce_host(ctx, &flag, 1, 2));  // any rank
+  csr_dense_form = flag != 0.0;
+  return PO_OK;
 }
 Problem::Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_)
     : ctx(c), nlocal(nlocal_), offset(0), nglobal(nlocal_), ncon(ncon_), ninequality(nineq_) {
@@ -439,28 +449,31 @@ int SeparableProblem::setWeighting(int64_t nwg, int nw, int64_t nwstart, int nws
   if (nwinequality > count) nwinequality = count;
   return chooseSolver(userSolverTable(), nwblock);
 }
-int SeparableProblem::setChain(int span, int stride, int reverse_cols) {
-  if (span < 1 || stride < 1) {
-    set_error("setChain: span and stride must be positive");
+int SeparableProblem::setChain(int span, int stride, int reverse_cols, int dense_vars) {
+  if (span < 1 || stride < 1 || dense_vars < 0 || dense_vars > nlocal) {
+    set_error("setChain: span and stride must be positive, the dense variables between 0 and the local size");
     return PO_ERR_ARG;
   }
-  const int64_t rows = nlocal >= span ? (nlocal - span) / stride + 1 : 0;
-  if (rows * span > 2000000000LL) {
+  const int64_t nchain = nlocal - dense_vars, len = span + dense_vars;
+  const int64_t rows = nchain >= span ? (nchain - span) / stride + 1 : 0;
+  if (rows * len > 2000000000LL) {
     set_error("setChain: more than 2e9 Jacobian entries on one rank");
     return PO_ERR_ARG;
   }
-  std::vector<int> rowp(rows + 1), cols((size_t)rows * span);
+  std::vector<int> rowp(rows + 1), cols((size_t)rows * len);
   for (int64_t i = 0; i < rows; i++) {
-    rowp[i] = (int)(i * span);
+    rowp[i] = (int)(i * len);
     for (int k = 0; k < span; k++) {
-      cols[i * span + (reverse_cols ? span - 1 - k : k)] = (int)(i * stride + k);
+      cols[i * len + (reverse_cols ? span - 1 - k : k)] = (int)(i * stride + k);
     }
+    for (int j = 0; j < dense_vars; j++) cols[i * len + span + j] = (int)(nchain + j);
   }
-  rowp[rows] = (int)(rows * span);
+  rowp[rows] = (int)(rows * len);
   PO_TRY(setSparseJacobianData(rows, rows, rowp.data(), cols.data()));
   chain_span = span;
   chain_stride = stride;
   chain_reverse = reverse_cols;
+  chain_dense = dense_vars;
   // (gmap is setSparseJacobianData's: a chain with stride >= span has row-disjoint groups, is recognised as the grouped
   // pattern and runs the group kernels for as long as its Jacobian entries -2 x are uniform -- a start at x = -1, say.
   // Until round 5's random campaign this function reset gmap behind the recognition: `grouped` with an empty map.)
@@ -524,7 +537,12 @@ int SeparableProblem::getVarsAndBounds(Vec *x, Vec *lb, Vec *ub) {
 
 int SeparableProblem::evalObjCon(Vec *x, double *fobj, double *cons) {
   const int64_t n = nlocal;
-  if (csr) PO_TRY(k_chain_con(ctx, x->d, nwcon, chain_span, chain_stride, csr->cw->d));
+  if (csr && chain_dense > 0) {
+    PO_TRY(k_chain_dense_con(ctx, x->d, nwcon, chain_span, chain_stride, x->d + (nlocal - chain_dense), chain_dense,
+                             csr->cw->d));
+  } else if (csr) {
+    PO_TRY(k_chain_con(ctx, x->d, nwcon, chain_span, chain_stride, csr->cw->d));
+  }
   if (kind == PO_PROBLEM_ROSENBROCK) {
     BatchScope batch(ctx);
     PO_TRY(k_rosen_f(ctx, x->d, n, rosen_out));
@@ -555,7 +573,12 @@ int SeparableProblem::evalObjCon(Vec *x, double *fobj, double *cons) {
 int SeparableProblem::evalObjConGradient(Vec *x, Vec *g, Vec **Ac) {
   const int64_t n = nlocal;
   if (csr) {
-    PO_TRY(k_chain_jac(ctx, x->d, nwcon, chain_span, chain_stride, chain_reverse, csr->data));
+    if (chain_dense > 0) {
+      PO_TRY(k_chain_dense_jac(ctx, x->d, nwcon, chain_span, chain_stride, chain_reverse,
+                               x->d + (nlocal - chain_dense), chain_dense, csr->data));
+    } else {
+      PO_TRY(k_chain_jac(ctx, x->d, nwcon, chain_span, chain_stride, chain_reverse, csr->data));
+    }
     PO_TRY(csrValuesChanged());
   }
   if (kind == PO_PROBLEM_ROSENBROCK) {

@@ -204,6 +204,29 @@ class CsrSolver : public QuasiDefSolver {
   long breakdowns() const override { return prob->csr->breakdowns; }
 };
 
+// General CSR pattern with dense columns taken out of S (csr.hpp): S^-1 is the factor of S0 plus a low-rank
+// correction, so no half-solved panel Y with U^T S^-1 U = Y^T Y exists.  The Gram correction takes the SOLVED panel, as
+// for a user's solver, filled for all columns in one sweep; factor, applyK0 and the factor line are the CSR form's.
+// (Also chosen on a rank without a dense column when another rank has one: the form decides which collective the
+// interior point issues, so it is the same on every rank.)
+class CsrDenseColumnSolver : public CsrSolver {
+ public:
+  using CsrSolver::CsrSolver;
+  int panel(Vec *, Vec *d, const double *const *P, int nv, double *const *U, Vec *) override {
+    return prob->csr->panelNatural(d->d, P, nv, U);
+  }
+  GramForm gramForm() const override { return {true, true}; }
+  int gramSolve(const double *const *, int nv, double *const *U, double *const *Yw, Vec *, Vec *,
+                const double **weights) override {
+    *weights = nullptr;
+    return prob->csr->solvePanel(U, nv, Yw);  // Yw = -S^-1 U
+  }
+  int correction(const double *const *Yw, int nv, const double *alpha, Vec *, Vec *out, Vec *acc) override {
+    PO_TRY(combine(Yw, nv, alpha, out));  // Yw alpha = -S^-1 (U alpha): no further solve
+    return accumulate(out, acc);
+  }
+};
+
 // createQuasiDefMat (src/ParOptProblem.h:72): the problem brings its own quasi-definite solver.  factor forms nothing
 // and calls the user's factor(x, d, Cdiag) with cw = Cdiag left alone, applyK0 is the user's apply and nothing else.
 // The user exposes no factor, so the Gram correction takes the SOLVED panel: one three-argument apply per column.
@@ -258,7 +281,8 @@ class UserSolver : public QuasiDefSolver {
 
 }  // namespace
 
-// The precedence of the forms, written once: user > grouped > CSR > packed block > generic scalar.  Called wherever
+// The precedence of the forms, written once: user > grouped > CSR with dense columns > CSR > packed block > generic
+// scalar.  Called wherever
 // one of its inputs changes; `user` is the table to carry (userSolverTable() keeps what is attached, null detaches).
 // A failure leaves the previous solver and block size in place.
 int Problem::chooseSolver(const po_quasidef_callbacks *user, int nwblock_) {
@@ -267,6 +291,8 @@ int Problem::chooseSolver(const po_quasidef_callbacks *user, int nwblock_) {
     s = new UserSolver(this, *user);
   } else if (grouped) {
     s = new GroupedSolver(this);
+  } else if (csr && csr_dense_form) {
+    s = new CsrDenseColumnSolver(this);
   } else if (csr) {
     s = new CsrSolver(this);
   } else if (nwblock_ > 1) {

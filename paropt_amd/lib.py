@@ -254,12 +254,18 @@ SIGNATURES = {
     "po_problem_get_sparse_jacobian_data": (
         C.c_int, [po_problem, c_int_pp, c_int_pp, C.POINTER(C.c_void_p), c_i64_p]),
     "po_problem_set_chain": (C.c_int, [po_problem, C.c_int, C.c_int, C.c_int]),
+    "po_problem_set_chain_dense": (C.c_int, [po_problem, C.c_int, C.c_int, C.c_int, C.c_int]),
     "po_problem_set_sparse_block_size": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_quasidef_callbacks": (C.c_int, [po_problem, C.POINTER(QuasiDefCallbacks)]),
     "po_quasidef_factor": (C.c_int, [po_problem, po_vec, po_vec, po_vec]),
     "po_quasidef_apply": (C.c_int, [po_problem, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec]),
     "po_quasidef_factor_info": (C.c_char_p, [po_problem]),
     "po_csr_symbolic_create": (C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, C.POINTER(po_csr_symbolic)]),
+    "po_csr_symbolic_create_split": (
+        C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, C.c_int64, C.POINTER(po_csr_symbolic)]),
+    "po_csr_symbolic_dense_columns": (C.c_int, [po_csr_symbolic, c_int_pp, C.POINTER(C.c_int)]),
+    "po_problem_set_sparse_dense_columns": (C.c_int, [po_problem, C.c_int64]),
+    "po_problem_sparse_dense_columns": (C.c_int, [po_problem, c_int_pp, C.POINTER(C.c_int)]),
     "po_csr_symbolic_info": (C.c_int, [po_csr_symbolic, c_i64_p]),
     "po_csr_symbolic_arrays": (
         C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),

@@ -6,6 +6,11 @@ rows that is assembled, factored and solved on the GPU every interior-point iter
 the reference's sparse Cholesky needs METIS, which this image lacks.  Prints one JSON line.
 
     python tools/bench_csr.py [--nglobal 4000000] [--ncon 4] [--span 2] [--stride 1] [--steps 20] [--warmup 5]
+                              [--dense-columns R]
+
+--dense-columns R: R further variables that enter EVERY sparse constraint (cw_i -= sum_j xd_j^2, the shape of an
+epigraph variable): their columns of the Jacobian are dense, leave the factored matrix and come back by a low-rank
+update.  The chain itself keeps its n variables, so R = 0 is the run of record.
 
 --quasidef user: the same run with a USER quasi-definite solver attached (createQuasiDefMat) that only forwards factor
 and apply to the library's own solver of a twin problem with the same pattern and entries.  The solve itself then
@@ -66,12 +71,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--quasidef", choices=("library", "user"), default="library")
+    ap.add_argument("--dense-columns", dest="dense", type=int, default=0)
     a = ap.parse_args()
+    if a.dense and a.quasidef == "user":
+        ap.error("--dense-columns measures the library's solver")
     import paropt_amd as pa
 
     ctx = pa.Context(0)
     t0 = time.perf_counter()
-    prob = pa.SeparableProblem(ctx, a.problem, a.n, a.ncon, 0).setChain(a.span, a.stride)
+    prob = pa.SeparableProblem(ctx, a.problem, a.n + a.dense, a.ncon, 0).setChain(a.span, a.stride,
+                                                                                 dense_vars=a.dense)
     t_sym = time.perf_counter() - t0
     fwd = None
     if a.quasidef == "user":
@@ -88,6 +97,7 @@ def main():
         if k in (a.warmup, a.warmup + a.steps):
             ctx.synchronize()
             marks[k] = time.perf_counter()
+            marks["counters", k] = ctx.counters()
             if fwd is not None:
                 marks["apply", k] = (fwd.t_apply, fwd.napply, fwd.t_factor)
 
@@ -99,6 +109,9 @@ def main():
     steps = min(niter, a.warmup + a.steps) - a.warmup
     dt = t1 - marks[a.warmup]
     extra = {}
+    if a.dense:
+        extra = {"dense_columns": prob.dense_columns}
+    (s0, l0), (s1, l1) = marks["counters", a.warmup], marks.get(("counters", a.warmup + a.steps), ctx.counters())
     if fwd is not None:
         (ta0, na0, tf0), (ta1, na1, tf1) = marks["apply", a.warmup], marks.get(("apply", a.warmup + a.steps),
                                                                            (fwd.t_apply, fwd.napply, fwd.t_factor))
@@ -109,9 +122,11 @@ def main():
         **extra,
         "metric": "interior-point iterations/s (CSR sparse constraints)", "value": steps / dt,
         "unit": "IP iterations/s", "n_gpus": 1, "steps": steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / steps,
-        "dtype": "f64", "data": "synthetic",
+        "dtype": "f64", "data": "synthetic", "launches_per_step": (l1 - l0) / steps,
+        "host_syncs_per_step": (s1 - s0) / steps,
         "config": {"workload": "%s n=%d c=%d chain span=%d stride=%d (w=%d) L-BFGS(%d)" % (
-            a.problem, a.n, a.ncon, a.span, a.stride, prob.nwcon, a.qn_size)},
+            a.problem, a.n + a.dense, a.ncon, a.span, a.stride, prob.nwcon, a.qn_size) + (
+                " + %d dense columns" % a.dense if a.dense else "")},
         "fobj": ip.getObjective()[0], "symbolic_seconds": t_sym, "factor_info": pa.quasidef_factor_info(prob),
     }))
 
