@@ -2057,4 +2057,73 @@ inline double ParOptProblem::checkGradients(double dh, ParOptVec *xvec, int chec
   return worst;
 }
 
+// ---- ParOptSparseCholesky (src/ParOptSparseCholesky.h:7-47) ------------------------------------------------------------
+// L L^T = P A P^T on the device (po_sparse_chol_* in paropt_amd.h).  PAROPT_AMD_ORDER is accepted and gets the same
+// nested dissection as PAROPT_ND_ORDER.  The reference's constructor has no communicator: with PAROPT_AMD_USE_MPI the
+// reference's exact signature works on MPI_COMM_SELF, and either way a leading ParOptComm names the device context.
+// setValues with an entry outside the factor's pattern fails (the reference drops it): the message is printed.
+enum ParOptOrderingType { PAROPT_NATURAL_ORDER, PAROPT_AMD_ORDER, PAROPT_ND_ORDER };
+
+class ParOptSparseCholesky {
+ public:
+  ParOptSparseCholesky(ParOptComm comm, int _size, const int *Acolp, const int *Arows,
+                       ParOptOrderingType order = PAROPT_ND_ORDER, const int *_perm = NULL)
+      : h(NULL) {
+    create(paropt_amd_context(comm), _size, Acolp, Arows, order, _perm);
+  }
+#ifdef PAROPT_AMD_USE_MPI
+  ParOptSparseCholesky(int _size, const int *Acolp, const int *Arows, ParOptOrderingType order = PAROPT_ND_ORDER,
+                       const int *_perm = NULL)
+      : h(NULL) {
+    int up = 0;
+    MPI_Initialized(&up);
+    if (!up) MPI_Init(NULL, NULL);  // (the reference's class needs no MPI; its example never calls MPI_Init)
+    create(paropt_amd_context(MPI_COMM_SELF), _size, Acolp, Arows, order, _perm);
+  }
+#endif
+  ~ParOptSparseCholesky() { po_sparse_chol_destroy(h); }
+  void setValues(int n, const int Acolp[], const int Arows[], const ParOptScalar Avals[]) {
+    report(po_sparse_chol_set_values(h, n, Acolp, Arows, Avals));
+  }
+  // 0, or like LAPACK's info 1 + the (permuted) index of the first non-positive pivot
+  int factor() {
+    int info = 0;
+    if (report(po_sparse_chol_factor(h, &info)) != 0) return -1;
+    return info;
+  }
+  void solve(ParOptScalar *x) { report(po_sparse_chol_solve(h, x, 1, size)); }
+  // nrhs right-hand sides, column j at x + j * size
+  void solve(ParOptScalar *x, int nrhs) { report(po_sparse_chol_solve(h, x, nrhs, size)); }
+  // the same on a DEVICE array (queued on the context's stream)
+  void solveDevice(ParOptScalar *dx, int nrhs = 1) { report(po_sparse_chol_solve_device(h, dx, nrhs, size)); }
+  void getInfo(int *_size, int *_num_snodes, int *_nnzL) {
+    int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    po_sparse_chol_info(h, info);
+    if (_size) *_size = (int)info[0];
+    if (_num_snodes) *_num_snodes = (int)info[1];
+    if (_nnzL) *_nnzL = (int)info[2];
+  }
+  po_sparse_chol handle() { return h; }
+
+ private:
+  ParOptSparseCholesky(const ParOptSparseCholesky &);
+  ParOptSparseCholesky &operator=(const ParOptSparseCholesky &);
+  void create(po_ctx ctx, int _size, const int *Acolp, const int *Arows, ParOptOrderingType order, const int *_perm) {
+    size = _size;
+    const int kind = order == PAROPT_NATURAL_ORDER ? PO_ORDER_NATURAL
+                                                   : (order == PAROPT_AMD_ORDER ? PO_ORDER_AMD : PO_ORDER_ND);
+    if (!ctx) {
+      fprintf(stderr, "ParOptSparseCholesky: no device context (%s)\n", po_last_error());
+      return;
+    }
+    report(po_sparse_chol_create(ctx, _size, Acolp, Arows, kind, _perm, &h));
+  }
+  static int report(int rc) {
+    if (rc != 0) fprintf(stderr, "ParOptSparseCholesky: %s\n", po_last_error());
+    return rc;
+  }
+  po_sparse_chol h;
+  int size;
+};
+
 #endif  // PAROPT_AMD_HPP

@@ -953,6 +953,46 @@ int po_mma_get_dual_linear_stats(po_mma mma, long *cap_hits, int *max_steps);
 int po_mma_get_linear_subproblem(po_mma mma, po_vec *alpha, po_vec *beta, po_vec *p0, po_vec *q0, const po_vec **A,
                                  const double **cons, po_vec *xk);
 
+/* ---- ParOptSparseCholesky (src/ParOptSparseCholesky.h:29-47): L L^T = P A P^T of a caller's own SPD matrix ----------
+ * A supernodal multifrontal factorization with dense fronts on the device (paropt_amd/csrc/sparse_chol.hpp).  The
+ * pattern is the FULL symmetric one in compressed columns, both triangles, as the reference's callers pass it; rows
+ * may be unsorted and repeated, the pattern is symmetrised and the diagonal added for the analysis.  PO_ORDER_ND is
+ * this library's nested dissection; PO_ORDER_NATURAL is the identity or, with perm (perm[new] = old, read under this
+ * ordering type only), the caller's order; PO_ORDER_AMD is accepted and gets the same nested dissection -- there is
+ * no minimum-degree ordering here.  Every order is then relabelled into a postorder of its elimination tree (the
+ * same factor), and that is the perm the handle reports.  ctx == NULL gives an analysis-only handle (no device):
+ * the info and array entries work, the numeric ones answer PO_ERR_ARG. */
+typedef struct po_sparse_chol_s *po_sparse_chol;
+enum { PO_ORDER_NATURAL = 0, PO_ORDER_AMD = 1, PO_ORDER_ND = 2 };
+/* the constructor, ParOptSparseCholesky.h:31-33.  PO_ERR_ARG with a message for an index out of range, a negative
+ * size, a perm that is no permutation, or work space that cannot be allocated (the message names the bytes). */
+int po_sparse_chol_create(po_ctx ctx, int64_t size, const int *colp, const int *rows, int order, const int *perm,
+                          po_sparse_chol *out);
+/* setValues, ParOptSparseCholesky.h:37-38 (.cpp:205-252): host arrays; entries at the permuted-lower position are
+ * summed into the factor's storage in entry order (repeated entries add up), the permuted-upper copies are not read.
+ * A pattern other than the creation pattern gets its map built on the host in this call.  DIFFERENCE: an entry outside
+ * the factor's pattern is PO_ERR_ARG here; the reference drops it silently. */
+int po_sparse_chol_set_values(po_sparse_chol h, int64_t n, const int *colp, const int *rows, const double *vals);
+/* the same from a DEVICE array holding the values in the entry order of the creation pattern (queued on the
+ * context's stream, no host synchronisation) */
+int po_sparse_chol_set_values_device(po_sparse_chol h, const double *dvals);
+/* factor, ParOptSparseCholesky.h:41: *info = 0, or 1 + the permuted index of the first non-positive pivot (LAPACK's
+ * info in the reference, .cpp:631).  Such a pivot is replaced by 1 and the factorization finishes; the return value
+ * is PO_OK either way.  Needs values set since the last factorization (the factor overwrites them). */
+int po_sparse_chol_factor(po_sparse_chol h, int *info);
+/* solve, ParOptSparseCholesky.h:44, for nrhs right-hand sides in place, column j at x + j * ldx */
+int po_sparse_chol_solve(po_sparse_chol h, double *x, int nrhs, int64_t ldx);
+int po_sparse_chol_solve_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx);
+/* getInfo, ParOptSparseCholesky.h:47, and more: {size, num_snodes, nnzL = sum s (s + 1) / 2 + b s, levels of the
+ * supernode tree, largest s, largest front s + b, work_bytes (update-matrix arena and solve work space), block
+ * width NB of the blocked fronts} */
+int po_sparse_chol_info(po_sparse_chol h, int64_t info[8]);
+/* borrowed host arrays, any pointer may be NULL: perm (size, perm[new] = old), snode_first (num_snodes + 1),
+ * snode_parent (num_snodes, -1 at a root), snode_level (num_snodes, above every child's) */
+int po_sparse_chol_arrays(po_sparse_chol h, const int **perm, const int **snode_first, const int **snode_parent,
+                          const int **snode_level);
+int po_sparse_chol_destroy(po_sparse_chol h); /* NULL is fine */
+
 #ifdef __cplusplus
 }
 #endif

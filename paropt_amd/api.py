@@ -1400,6 +1400,128 @@ class CsrSymbolic:
             lib.po_csr_symbolic_destroy(h)
 
 
+class SparseCholesky:
+    """ParOptSparseCholesky (src/ParOptSparseCholesky.h:29-47): L L^T = P A P^T of an SPD matrix given by its full
+    symmetric pattern in compressed columns, as a multifrontal factorization with dense fronts on the device.
+
+    ctx=None gives an analysis-only object (no device).  order: "nd" (nested dissection), "amd" (accepted, gets the
+    same nested dissection), "natural" (the identity, or `perm` with perm[new] = old)."""
+
+    ORDERS = {"natural": 0, "amd": 1, "nd": 2}
+
+    def __init__(self, ctx, size, colp, rows, order="nd", perm=None):
+        self.ctx = ctx
+        self._colp = np.ascontiguousarray(colp, dtype=np.intc)
+        self._rows = np.ascontiguousarray(rows, dtype=np.intc)
+        self._h = L.po_sparse_chol()
+        p = None
+        if perm is not None:
+            p = np.ascontiguousarray(perm, dtype=np.intc)
+            if p.shape != (int(size),):
+                raise ValueError("perm must have `size` entries")
+        if self._colp.shape != (int(size) + 1,) and int(size) >= 0:
+            raise ValueError("colp must have size + 1 entries")
+        if int(size) >= 0 and len(self._rows) < int(self._colp[-1]):
+            raise ValueError("rows is shorter than colp[size]")
+        check(lib.po_sparse_chol_create(ctx.handle if ctx is not None else None, int(size),
+                                        self._colp.ctypes.data_as(L.c_int_p), self._rows.ctypes.data_as(L.c_int_p),
+                                        self.ORDERS[order] if isinstance(order, str) else int(order),
+                                        p.ctypes.data_as(L.c_int_p) if p is not None else None, C.byref(self._h)))
+        info = (C.c_int64 * 8)()
+        check(lib.po_sparse_chol_info(self._h, info))
+        (self.size, self.num_snodes, self.nnzL, self.nlevels, self.max_snode, self.max_front, self.work_bytes,
+         self.block_width) = (int(v) for v in info)
+        ptrs = [L.c_int_p() for _ in range(4)]
+        check(lib.po_sparse_chol_arrays(self._h, *[C.byref(q) for q in ptrs]))
+
+        def arr(q, n):
+            return np.ctypeslib.as_array(q, shape=(n,)).copy() if n > 0 else np.zeros(0, dtype=np.intc)
+
+        self.perm = arr(ptrs[0], self.size)
+        self.snode_first = arr(ptrs[1], self.num_snodes + 1)
+        self.snode_parent = arr(ptrs[2], self.num_snodes)
+        self.snode_level = arr(ptrs[3], self.num_snodes)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def getInfo(self):
+        """(size, num_snodes, nnzL) as ParOptSparseCholesky::getInfo."""
+        return self.size, self.num_snodes, self.nnzL
+
+    def set_values(self, *args):
+        """set_values(vals): values in the entry order of the creation pattern; set_values(colp, rows, vals): any
+        pattern inside the factor's (the reference's setValues).  Repeated entries add up."""
+        if len(args) == 1:
+            colp, rows = self._colp, self._rows
+        elif len(args) == 3:
+            colp = np.ascontiguousarray(args[0], dtype=np.intc)
+            rows = np.ascontiguousarray(args[1], dtype=np.intc)
+            if colp.shape != (self.size + 1,) or len(rows) < int(colp[-1]):
+                raise ValueError("set_values: colp / rows do not describe a matrix of this size")
+        else:
+            raise TypeError("set_values(vals) or set_values(colp, rows, vals)")
+        vals = np.ascontiguousarray(args[-1], dtype=np.float64)
+        if len(vals) < int(colp[-1]):
+            raise ValueError("set_values: fewer values than entries")
+        check(lib.po_sparse_chol_set_values(self._h, self.size, colp.ctypes.data_as(L.c_int_p),
+                                            rows.ctypes.data_as(L.c_int_p), vals.ctypes.data_as(L.c_double_p)))
+
+    def _tensor_ptr(self, t, count, who):
+        import torch
+
+        if self.ctx is None:
+            raise L.ParOptAMDError(3, who + ": an analysis-only object has no device")
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous()
+                or t.device != torch.device("cuda", self.ctx.device()) or t.numel() < count):
+            raise ValueError(who + ": a contiguous float64 tensor on the context's device is required")
+        torch.cuda.current_stream(t.device).synchronize()  # (what produced t is done before the context's stream reads it)
+        return t.data_ptr()
+
+    def set_values_device(self, t):
+        """Values from a torch tensor on the context's device, in the entry order of the creation pattern (no copy)."""
+        ptr = self._tensor_ptr(t, int(self._colp[-1]), "set_values_device")
+        check(lib.po_sparse_chol_set_values_device(self._h, ptr))
+
+    def factor(self):
+        """0, or 1 + the permuted index of the first non-positive pivot (it is replaced by 1 and the factorization
+        finishes)."""
+        info = C.c_int()
+        check(lib.po_sparse_chol_factor(self._h, C.byref(info)))
+        return info.value
+
+    def solve(self, b):
+        """x = A^-1 b for b of shape (n,) or (nrhs, n); returns a new array."""
+        x = np.array(b, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (1, 2) or x.shape[-1] != self.size:
+            raise ValueError("solve: b must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        check(lib.po_sparse_chol_solve(self._h, x.ctypes.data_as(L.c_double_p), nrhs, self.size))
+        return x
+
+    def solve_tensor(self, t):
+        """In place on a contiguous float64 torch tensor of shape (n,) or (nrhs, n) on the context's device."""
+        if t.dim() not in (1, 2) or t.shape[-1] != self.size:
+            raise ValueError("solve_tensor: t must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if t.dim() == 1 else t.shape[0]
+        ptr = self._tensor_ptr(t, nrhs * self.size, "solve_tensor")
+        check(lib.po_sparse_chol_solve_device(self._h, ptr, nrhs, self.size))
+        self.ctx.synchronize()
+        return t
+
+    def close(self):
+        if self._h:
+            lib.po_sparse_chol_destroy(self._h)
+            self._h = L.po_sparse_chol()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
 def quasidef_factor(problem, x, dinv, c):
     """ParOptQuasiDefMat::factor (src/ParOptSparseMat.h:25) of the problem's sparse constraints."""
     check(lib.po_quasidef_factor(problem.handle, x.handle, dinv.handle, c.handle))

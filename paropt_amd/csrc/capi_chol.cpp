@@ -1,0 +1,110 @@
+// C ABI of the multifrontal sparse Cholesky (include/paropt_amd.h, "ParOptSparseCholesky"); each entry names the line
+// of the reference's src/ParOptSparseCholesky.h it stands for.
+#include "sparse_chol.hpp"
+
+using namespace po;
+
+#define PO_CHECK_PTR(p)                         \
+  do {                                          \
+    if (!(p)) {                                 \
+      po::set_error("null argument: %s", #p);   \
+      return PO_ERR_ARG;                        \
+    }                                           \
+  } while (0)
+
+struct po_sparse_chol_s {
+  po::SparseChol *c;
+};
+
+#define PO_CHECK_NUMERIC(h)                                                                         \
+  do {                                                                                              \
+    PO_CHECK_PTR(h);                                                                                \
+    if (!(h)->c->ctx) {                                                                             \
+      po::set_error("sparse Cholesky: an analysis-only handle (created with ctx == NULL) has no numeric part"); \
+      return PO_ERR_ARG;                                                                            \
+    }                                                                                               \
+  } while (0)
+
+extern "C" {
+
+// ParOptSparseCholesky::ParOptSparseCholesky, ParOptSparseCholesky.h:31-33
+int po_sparse_chol_create(po_ctx ctx, int64_t size, const int *colp, const int *rows, int order, const int *perm,
+                          po_sparse_chol *out) {
+  PO_CHECK_PTR(out);
+  *out = nullptr;
+  PO_CHECK_PTR(colp);
+  po::SparseChol *c = new po::SparseChol(ctx);
+  int rc = po::chol_analyse(size, colp, rows, order, perm, &c->sym);
+  if (rc == PO_OK && ctx) rc = c->upload();
+  if (rc != PO_OK) {
+    delete c;
+    return rc;
+  }
+  *out = new po_sparse_chol_s{c};
+  return PO_OK;
+}
+// setValues, ParOptSparseCholesky.h:37-38
+int po_sparse_chol_set_values(po_sparse_chol h, int64_t n, const int *colp, const int *rows, const double *vals) {
+  PO_CHECK_NUMERIC(h);
+  PO_CHECK_PTR(colp);
+  if (n == h->c->sym.n && n >= 0 && colp[n] > 0) {
+    PO_CHECK_PTR(rows);
+    PO_CHECK_PTR(vals);
+  }
+  return h->c->setValuesHost(n, colp, rows, vals);
+}
+int po_sparse_chol_set_values_device(po_sparse_chol h, const double *dvals) {
+  PO_CHECK_NUMERIC(h);
+  if (!h->c->sym.rows.empty()) PO_CHECK_PTR(dvals);
+  return h->c->setValuesDevice(dvals);
+}
+// factor, ParOptSparseCholesky.h:41
+int po_sparse_chol_factor(po_sparse_chol h, int *info) {
+  PO_CHECK_NUMERIC(h);
+  return h->c->factor(info);
+}
+// solve, ParOptSparseCholesky.h:44
+int po_sparse_chol_solve(po_sparse_chol h, double *x, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(x);
+  return h->c->solveHost(x, nrhs, ldx);
+}
+int po_sparse_chol_solve_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(dx);
+  return h->c->solveDevice(dx, nrhs, ldx);
+}
+// getInfo, ParOptSparseCholesky.h:47
+int po_sparse_chol_info(po_sparse_chol h, int64_t info[8]) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  const po::CholSymbolic &s = h->c->sym;
+  info[0] = s.n;
+  info[1] = s.nsn;
+  info[2] = s.nnzL;
+  info[3] = s.nlev;
+  info[4] = s.max_s;
+  info[5] = s.max_front;
+  info[6] = s.work_bytes;
+  info[7] = po::kCholNB;
+  return PO_OK;
+}
+int po_sparse_chol_arrays(po_sparse_chol h, const int **perm, const int **snode_first, const int **snode_parent,
+                          const int **snode_level) {
+  PO_CHECK_PTR(h);
+  const po::CholSymbolic &s = h->c->sym;
+  if (perm) *perm = s.perm.data();
+  if (snode_first) *snode_first = s.sn_first.data();
+  if (snode_parent) *snode_parent = s.sn_parent.data();
+  if (snode_level) *snode_level = s.sn_level.data();
+  return PO_OK;
+}
+// ~ParOptSparseCholesky, ParOptSparseCholesky.h:34
+int po_sparse_chol_destroy(po_sparse_chol h) {
+  if (!h) return PO_OK;
+  delete h->c;
+  delete h;
+  return PO_OK;
+}
+
+}  // extern "C"

@@ -145,6 +145,63 @@ struct Dissector {
 
 }  // namespace
 
+// The three steps of the analysis that do not depend on where the graph came from (csr.hpp); the multifrontal
+// analysis of sparse_chol.cpp calls the same ones.
+void sym_nd_order(const std::vector<int> &adjp, const std::vector<int> &adj, int w, std::vector<int> *perm) {
+  Dissector nd(adjp, adj, w);
+  std::vector<int> all(w);
+  std::iota(all.begin(), all.end(), 0);
+  nd.order(all, 0, 0, 0);
+  perm->swap(nd.perm);
+}
+
+// elimination tree (Liu, with path compression)
+void sym_etree(const std::vector<int> &adjp, const std::vector<int> &adj, const std::vector<int> &perm,
+               const std::vector<int> &iperm, std::vector<int> *parent_out) {
+  const int w = (int)perm.size();
+  std::vector<int> &parent = *parent_out;
+  parent.assign(w, -1);
+  std::vector<int> anc(w, -1);
+  for (int i = 0; i < w; i++) {
+    const int old = perm[i];
+    for (int p = adjp[old]; p < adjp[old + 1]; p++) {
+      int r = iperm[adj[p]];
+      if (r >= i) continue;
+      while (anc[r] != -1 && anc[r] != i) {
+        const int nx = anc[r];
+        anc[r] = i;
+        r = nx;
+      }
+      if (anc[r] == -1) {
+        anc[r] = i;
+        parent[r] = i;
+      }
+    }
+  }
+}
+
+// entries of every column of L, the diagonal included
+void sym_colcount(const std::vector<int> &adjp, const std::vector<int> &adj, const std::vector<int> &perm,
+                  const std::vector<int> &iperm, const std::vector<int> &parent, std::vector<int> *colcount_out) {
+  const int w = (int)perm.size();
+  std::vector<int> &colcount = *colcount_out;
+  colcount.assign(w, 1);
+  std::vector<int> mark(w, -1);
+  for (int i = 0; i < w; i++) {
+    const int old = perm[i];
+    mark[i] = i;
+    for (int p = adjp[old]; p < adjp[old + 1]; p++) {
+      int j = iperm[adj[p]];
+      if (j >= i) continue;
+      while (mark[j] != i) {
+        colcount[j]++;
+        mark[j] = i;
+        j = parent[j];
+      }
+    }
+  }
+}
+
 static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int *cols, CsrSymbolic *out,
                             bool allow_fronts, int64_t min_rows);
 
@@ -300,13 +357,7 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
   }
   s.nnzS = (int64_t)(adj.size() / 2) + w;
   // ordering
-  {
-    Dissector nd(adjp, adj, w);
-    std::vector<int> all(w);
-    std::iota(all.begin(), all.end(), 0);
-    nd.order(all, 0, 0, 0);
-    s.perm.swap(nd.perm);
-  }
+  sym_nd_order(adjp, adj, w, &s.perm);
   // The dissection ordering fixes the elimination TREE; any topological order of that tree gives the same
   // factor up to a relabelling.  Rows are renumbered level by level (a row's level = the height of its
   // subtree), so the rows a launch works on - and their storage in L - are contiguous in memory.
@@ -318,26 +369,8 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
     }
     return true;
   };
-  // elimination tree (Liu, with path compression)
   auto etree = [&](const std::vector<int> &perm, const std::vector<int> &iperm, std::vector<int> &parent) {
-    parent.assign(w, -1);
-    std::vector<int> anc(w, -1);
-    for (int i = 0; i < w; i++) {
-      const int old = perm[i];
-      for (int p = adjp[old]; p < adjp[old + 1]; p++) {
-        int r = iperm[adj[p]];
-        if (r >= i) continue;
-        while (anc[r] != -1 && anc[r] != i) {
-          const int nx = anc[r];
-          anc[r] = i;
-          r = nx;
-        }
-        if (anc[r] == -1) {
-          anc[r] = i;
-          parent[r] = i;
-        }
-      }
-    }
+    sym_etree(adjp, adj, perm, iperm, &parent);
   };
   auto levels_of = [&](const std::vector<int> &parent, std::vector<int> &lev) -> int {
     lev.assign(w, 0);
@@ -363,23 +396,8 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
   {
     etree(s.perm, s.iperm, s.parent);
     const std::vector<int> &parent = s.parent;
-    std::vector<int> colcount(w, 1), nchild(w, 0), head(w);
-    {
-      std::vector<int> mark(w, -1);
-      for (int i = 0; i < w; i++) {
-        const int old = s.perm[i];
-        mark[i] = i;
-        for (int p = adjp[old]; p < adjp[old + 1]; p++) {
-          int j = s.iperm[adj[p]];
-          if (j >= i) continue;
-          while (mark[j] != i) {
-            colcount[j]++;
-            mark[j] = i;
-            j = parent[j];
-          }
-        }
-      }
-    }
+    std::vector<int> colcount, nchild(w, 0), head(w);
+    sym_colcount(adjp, adj, s.perm, s.iperm, parent, &colcount);
     for (int i = 0; i < w; i++) {
       if (parent[i] >= 0) nchild[parent[i]]++;
     }

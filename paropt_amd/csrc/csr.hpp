@@ -71,6 +71,14 @@ constexpr int kMaxDenseCols = 64;
 // pattern would be refused (more than 1.5e9 pairs), then the columns with at least max(1024, w/8) entries; -1, never.
 int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows = 0);
 
+// Steps of the analysis shared with the multifrontal factor (sparse_chol.cpp).  adjp / adj is the graph of the
+// matrix without its diagonal, both triangles; perm[new] = old and iperm is its inverse.
+void sym_nd_order(const std::vector<int> &adjp, const std::vector<int> &adj, int w, std::vector<int> *perm);
+void sym_etree(const std::vector<int> &adjp, const std::vector<int> &adj, const std::vector<int> &perm,
+               const std::vector<int> &iperm, std::vector<int> *parent);
+void sym_colcount(const std::vector<int> &adjp, const std::vector<int> &adj, const std::vector<int> &perm,
+                  const std::vector<int> &iperm, const std::vector<int> &parent, std::vector<int> *colcount);
+
 class CsrSparse {
  public:
   CsrSparse(Ctx *c, int64_t n_, int64_t w_);

@@ -1,0 +1,445 @@
+// Host analysis of the multifrontal sparse Cholesky (sparse_chol.hpp).  Pure host code: nothing here touches the
+// device, so analysis-only handles work on a machine without one.
+#include "sparse_chol.hpp"
+
+#include <algorithm>
+#include <map>
+#include <numeric>
+
+#include "csr.hpp"
+
+namespace po {
+
+namespace {
+
+int chol_internal(const char *what) {
+  set_error("internal: multifrontal analysis: %s", what);
+  return PO_ERR_ARG;
+}
+
+// First-fit layout of slots whose lifetimes are known level by level: a front's slot is taken at its own level and
+// given back once its parent's level has consumed it.
+struct ArenaLayout {
+  std::map<int64_t, int64_t> free_;  // offset -> size
+  int64_t end = 0;
+  int64_t take(int64_t size) {
+    if (size == 0) return 0;
+    int looked = 0;
+    for (auto it = free_.begin(); it != free_.end() && looked < 64; ++it, ++looked) {
+      if (it->second >= size) {
+        const int64_t off = it->first, rest = it->second - size;
+        free_.erase(it);
+        if (rest > 0) free_[off + size] = rest;
+        return off;
+      }
+    }
+    const int64_t off = end;
+    end += size;
+    return off;
+  }
+  void give(int64_t off, int64_t size) {
+    if (size == 0) return;
+    auto it = free_.emplace(off, size).first;
+    auto nx = std::next(it);
+    if (nx != free_.end() && it->first + it->second == nx->first) {
+      it->second += nx->second;
+      free_.erase(nx);
+    }
+    if (it != free_.begin()) {
+      auto pv = std::prev(it);
+      if (pv->first + pv->second == it->first) {
+        pv->second += it->second;
+        free_.erase(it);
+      }
+    }
+  }
+};
+
+// position of the permuted entry (pr, pc), pr >= pc, in L's storage; -1 when outside the pattern
+int64_t locate(const CholSymbolic &s, int pr, int pc) {
+  const int J = s.sn_of[pc], first = s.sn_first[J], sz = s.sn_first[J + 1] - first;
+  int64_t row;
+  if (pr < first + sz) {
+    row = pr - first;
+  } else {
+    const int *b = s.below_rows.data() + s.rows_ptr[J], *e = s.below_rows.data() + s.rows_ptr[J + 1];
+    const int *f = std::lower_bound(b, e, pr);
+    if (f == e || *f != pr) return -1;
+    row = sz + (f - b);
+  }
+  return s.panel_off[J] + (int64_t)(pc - first) * s.sn_ld[J] + row;
+}
+
+}  // namespace
+
+int chol_scatter_table(const CholSymbolic &s, int64_t n, const int *colp, const int *rows, std::vector<int> *ptr,
+                       std::vector<int64_t> *dst, std::vector<int> *src) {
+  if (n != s.n || !colp || colp[0] != 0) {
+    set_error("sparse Cholesky values: the pattern has size %lld, the factor %d (or colp[0] is not 0)", (long long)n,
+              s.n);
+    return PO_ERR_ARG;
+  }
+  std::vector<std::pair<int64_t, int>> ent;
+  for (int j = 0; j < s.n; j++) {
+    if (colp[j + 1] < colp[j]) {
+      set_error("sparse Cholesky values: colp is not non-decreasing at column %d", j);
+      return PO_ERR_ARG;
+    }
+    const int pc = s.iperm[j];
+    for (int p = colp[j]; p < colp[j + 1]; p++) {
+      const int i = rows[p];
+      if (i < 0 || i >= s.n) {
+        set_error("sparse Cholesky values: row %d out of range in column %d", i, j);
+        return PO_ERR_ARG;
+      }
+      const int pr = s.iperm[i];
+      if (pr < pc) continue;  // the permuted-upper copy is not read (src/ParOptSparseCholesky.cpp:228)
+      const int64_t d = locate(s, pr, pc);
+      if (d < 0) {
+        set_error("sparse Cholesky values: entry (%d, %d) lies outside the pattern the factor was created with", i, j);
+        return PO_ERR_ARG;
+      }
+      ent.push_back(std::make_pair(d, p));
+    }
+  }
+  std::sort(ent.begin(), ent.end());
+  ptr->assign(1, 0);
+  dst->clear();
+  src->resize(ent.size());
+  for (size_t k = 0; k < ent.size(); k++) {
+    if (k > 0 && ent[k].first != ent[k - 1].first) ptr->push_back((int)k);
+    if (k == 0 || ent[k].first != ent[k - 1].first) dst->push_back(ent[k].first);
+    (*src)[k] = ent[k].second;
+  }
+  if (ent.empty()) {
+    ptr->assign(1, 0);
+  } else {
+    ptr->push_back((int)ent.size());
+  }
+  return PO_OK;
+}
+
+int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *user_perm, CholSymbolic *out) {
+  CholSymbolic &s = *out;
+  if (size < 0 || size > 2000000000LL) {
+    set_error("sparse Cholesky: size %lld out of range", (long long)size);
+    return PO_ERR_ARG;
+  }
+  if (order != PO_ORDER_NATURAL && order != PO_ORDER_AMD && order != PO_ORDER_ND) {
+    set_error("sparse Cholesky: unknown ordering type %d", order);
+    return PO_ERR_ARG;
+  }
+  if (!colp || colp[0] != 0) {
+    set_error("sparse Cholesky: colp is missing or colp[0] is not 0");
+    return PO_ERR_ARG;
+  }
+  const int n = (int)size;
+  for (int j = 0; j < n; j++) {
+    if (colp[j + 1] < colp[j]) {
+      set_error("sparse Cholesky: colp is not non-decreasing at column %d", j);
+      return PO_ERR_ARG;
+    }
+  }
+  const int nnz = colp[n];
+  if (nnz > 0 && !rows) {
+    set_error("sparse Cholesky: rows is missing");
+    return PO_ERR_ARG;
+  }
+  s.n = n;
+  s.order = order;
+  s.colp.assign(colp, colp + n + 1);
+  s.rows.assign(rows, rows + nnz);
+  // graph of A + A^T without the diagonal: sorted, no duplicates
+  std::vector<int> adjp((size_t)n + 1, 0), adj;
+  {
+    std::vector<int64_t> cnt((size_t)n + 1, 0);
+    for (int j = 0; j < n; j++) {
+      for (int p = colp[j]; p < colp[j + 1]; p++) {
+        const int i = rows[p];
+        if (i < 0 || i >= n) {
+          set_error("sparse Cholesky: row %d out of range in column %d", i, j);
+          return PO_ERR_ARG;
+        }
+        if (i == j) continue;
+        cnt[i + 1]++;
+        cnt[j + 1]++;
+      }
+    }
+    for (int j = 0; j < n; j++) cnt[j + 1] += cnt[j];
+    if (cnt[n] > 2000000000LL) {
+      set_error("sparse Cholesky: the symmetrised pattern has more than 2e9 entries");
+      return PO_ERR_ARG;
+    }
+    std::vector<int> raw((size_t)cnt[n]);
+    std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
+    for (int j = 0; j < n; j++) {
+      for (int p = colp[j]; p < colp[j + 1]; p++) {
+        const int i = rows[p];
+        if (i == j) continue;
+        raw[fill[i]++] = j;
+        raw[fill[j]++] = i;
+      }
+    }
+    adj.reserve(raw.size() / 2 + 1);
+    for (int j = 0; j < n; j++) {
+      std::sort(raw.begin() + cnt[j], raw.begin() + cnt[j + 1]);
+      for (int64_t p = cnt[j]; p < cnt[j + 1]; p++) {
+        if (p == cnt[j] || raw[p] != raw[p - 1]) adj.push_back(raw[p]);
+      }
+      adjp[j + 1] = (int)adj.size();
+    }
+  }
+  // ordering
+  if (order == PO_ORDER_NATURAL) {
+    s.perm.resize(n);
+    if (user_perm) {
+      s.perm.assign(user_perm, user_perm + n);
+    } else {
+      std::iota(s.perm.begin(), s.perm.end(), 0);
+    }
+  } else {
+    sym_nd_order(adjp, adj, n, &s.perm);
+  }
+  auto invert = [&](const std::vector<int> &perm, std::vector<int> &iperm) -> bool {
+    iperm.assign(n, -1);
+    for (int i = 0; i < n; i++) {
+      if (perm[i] < 0 || perm[i] >= n || iperm[perm[i]] != -1) return false;
+      iperm[perm[i]] = i;
+    }
+    return true;
+  };
+  if (!invert(s.perm, s.iperm)) {
+    set_error("sparse Cholesky: perm is not a permutation of 0 .. %d", n - 1);
+    return PO_ERR_ARG;
+  }
+  // The elimination tree in POSTORDER: the same factor up to a relabelling, and every chain of the tree -- so every
+  // supernode -- becomes a run of consecutive columns with its subtree right in front of it.
+  std::vector<int> parent, colcount;
+  sym_etree(adjp, adj, s.perm, s.iperm, &parent);
+  {
+    std::vector<int> head(n, -1), next(n, -1);
+    for (int j = n - 1; j >= 0; j--) {  // children ascending
+      const int p = parent[j];
+      if (p >= 0) {
+        next[j] = head[p];
+        head[p] = j;
+      }
+    }
+    std::vector<int> post, stack;
+    post.reserve(n);
+    for (int r = 0; r < n; r++) {
+      if (parent[r] >= 0) continue;
+      stack.push_back(r);
+      while (!stack.empty()) {
+        const int v = stack.back();
+        const int c = head[v];
+        if (c >= 0) {
+          head[v] = next[c];
+          stack.push_back(c);
+        } else {
+          post.push_back(v);
+          stack.pop_back();
+        }
+      }
+    }
+    if ((int)post.size() != n) return chol_internal("the elimination tree is not a forest");
+    std::vector<int> np(n);
+    for (int k = 0; k < n; k++) np[k] = s.perm[post[k]];
+    s.perm.swap(np);
+    invert(s.perm, s.iperm);
+  }
+  sym_etree(adjp, adj, s.perm, s.iperm, &parent);
+  sym_colcount(adjp, adj, s.perm, s.iperm, parent, &colcount);
+  // fundamental supernodes
+  s.sn_of.assign(n, 0);
+  s.sn_first.clear();
+  {
+    std::vector<int> nchild(n, 0);
+    for (int j = 0; j < n; j++) {
+      if (parent[j] >= 0) nchild[parent[j]]++;
+    }
+    for (int j = 0; j < n; j++) {
+      const bool joins = j > 0 && parent[j - 1] == j && nchild[j] == 1 && colcount[j - 1] == colcount[j] + 1;
+      if (!joins) s.sn_first.push_back(j);
+      s.sn_of[j] = (int)s.sn_first.size() - 1;
+    }
+    s.nsn = (int)s.sn_first.size();
+    s.sn_first.push_back(n);
+  }
+  const int nsn = s.nsn;
+  // row structures, children first
+  s.sn_b.assign(nsn, 0);
+  s.sn_parent.assign(nsn, -1);
+  s.rows_ptr.assign((size_t)nsn + 1, 0);
+  s.below_rows.clear();
+  {
+    std::vector<int> mark(n, -1), chead(nsn, -1), cnext(nsn, -1), ctail(nsn, -1);
+    for (int J = 0; J < nsn; J++) {
+      const int first = s.sn_first[J], last = s.sn_first[J + 1] - 1;
+      const size_t begin = s.below_rows.size();
+      for (int j = first; j <= last; j++) {
+        const int old = s.perm[j];
+        for (int p = adjp[old]; p < adjp[old + 1]; p++) {
+          const int r = s.iperm[adj[p]];
+          if (r > last && mark[r] != J) {
+            mark[r] = J;
+            s.below_rows.push_back(r);
+          }
+        }
+      }
+      for (int c = chead[J]; c >= 0; c = cnext[c]) {
+        for (int64_t q = s.rows_ptr[c]; q < s.rows_ptr[c + 1]; q++) {
+          const int r = s.below_rows[q];
+          if (r > last && mark[r] != J) {
+            mark[r] = J;
+            s.below_rows.push_back(r);
+          }
+        }
+      }
+      std::sort(s.below_rows.begin() + begin, s.below_rows.end());
+      const int b = (int)(s.below_rows.size() - begin);
+      if (b != colcount[first] - (last - first + 1)) return chol_internal("a supernode's rows disagree with its column count");
+      s.sn_b[J] = b;
+      s.rows_ptr[J + 1] = (int64_t)s.below_rows.size();
+      if (b > 0) {
+        const int P = s.sn_of[s.below_rows[begin]];
+        if (P <= J) return chol_internal("a supernode's parent does not come after it");
+        s.sn_parent[J] = P;
+        if (chead[P] < 0) {
+          chead[P] = J;
+        } else {
+          cnext[ctail[P]] = J;
+        }
+        ctail[P] = J;
+      }
+    }
+    s.child_ptr.assign((size_t)nsn + 1, 0);
+    s.child.clear();
+    for (int J = 0; J < nsn; J++) {
+      for (int c = chead[J]; c >= 0; c = cnext[c]) s.child.push_back(c);
+      s.child_ptr[J + 1] = (int)s.child.size();
+    }
+  }
+  // relative indices, levels, storage
+  s.rel.assign(s.below_rows.size(), 0);
+  s.sn_level.assign(nsn, 0);
+  s.sn_ld.assign(nsn, 0);
+  s.upd_ld.assign(nsn, 0);
+  s.panel_off.assign(nsn, 0);
+  s.nnzL = 0;
+  s.Lsize = 0;
+  s.max_s = s.max_front = 0;
+  for (int J = 0; J < nsn; J++) {
+    const int sz = s.sn_first[J + 1] - s.sn_first[J], b = s.sn_b[J], P = s.sn_parent[J];
+    if (P >= 0) {
+      const int pf = s.sn_first[P], ps = s.sn_first[P + 1] - pf;
+      const int *pb = s.below_rows.data() + s.rows_ptr[P], *pe = s.below_rows.data() + s.rows_ptr[P + 1];
+      for (int64_t q = s.rows_ptr[J]; q < s.rows_ptr[J + 1]; q++) {
+        const int r = s.below_rows[q];
+        if (r < pf + ps) {
+          s.rel[q] = r - pf;
+        } else {
+          const int *f = std::lower_bound(pb, pe, r);
+          if (f == pe || *f != r) return chol_internal("a child's row is missing from its parent's front");
+          s.rel[q] = ps + (int)(f - pb);
+        }
+      }
+      s.sn_level[P] = std::max(s.sn_level[P], s.sn_level[J] + 1);
+    }
+    s.sn_ld[J] = (sz + b + 1) / 2 * 2;
+    s.upd_ld[J] = (b + 1) / 2 * 2;
+    s.panel_off[J] = s.Lsize;
+    s.Lsize += (int64_t)s.sn_ld[J] * sz;
+    s.nnzL += (int64_t)sz * (sz + 1) / 2 + (int64_t)b * sz;
+    s.max_s = std::max(s.max_s, sz);
+    s.max_front = std::max(s.max_front, sz + b);
+  }
+  s.nlev = 0;
+  for (int J = 0; J < nsn; J++) s.nlev = std::max(s.nlev, s.sn_level[J] + 1);
+  auto order_of = [&](int J) { return s.sn_first[J + 1] - s.sn_first[J] + s.sn_b[J]; };
+  auto nblk_of = [&](int J) { return (s.sn_first[J + 1] - s.sn_first[J] + kCholNB - 1) / kCholNB; };
+  // level lists
+  s.lev_ptr.assign((size_t)s.nlev + 1, 0);
+  for (int J = 0; J < nsn; J++) s.lev_ptr[s.sn_level[J] + 1]++;
+  for (int l = 0; l < s.nlev; l++) s.lev_ptr[l + 1] += s.lev_ptr[l];
+  s.lev_sn.resize(nsn);
+  s.lev_nsmall.assign(s.nlev, 0);
+  {
+    std::vector<int> fill(s.lev_ptr.begin(), s.lev_ptr.end() - 1);
+    for (int J = 0; J < nsn; J++) s.lev_sn[fill[s.sn_level[J]]++] = J;
+    for (int l = 0; l < s.nlev; l++) {
+      auto b = s.lev_sn.begin() + s.lev_ptr[l], e = s.lev_sn.begin() + s.lev_ptr[l + 1];
+      auto mid = std::stable_partition(b, e, [&](int J) { return order_of(J) <= kCholSmall; });
+      s.lev_nsmall[l] = (int)(mid - b);
+      std::stable_sort(mid, e, [&](int x, int y) { return nblk_of(x) > nblk_of(y); });
+    }
+  }
+  // arena layouts: update matrices (factorization) and update vectors (forward solve), the same lifetimes
+  s.upd_off.assign(nsn, 0);
+  s.sol_off.assign(nsn, 0);
+  {
+    ArenaLayout fa, so;
+    for (int l = 0; l < s.nlev; l++) {
+      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) {
+        const int J = s.lev_sn[q];
+        s.upd_off[J] = fa.take((int64_t)s.upd_ld[J] * s.sn_b[J]);
+        s.sol_off[J] = so.take((int64_t)s.upd_ld[J] * kCholMaxRhs);
+      }
+      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) {
+        const int J = s.lev_sn[q];
+        for (int c = s.child_ptr[J]; c < s.child_ptr[J + 1]; c++) {
+          const int C = s.child[c];
+          fa.give(s.upd_off[C], (int64_t)s.upd_ld[C] * s.sn_b[C]);
+          so.give(s.sol_off[C], (int64_t)s.upd_ld[C] * kCholMaxRhs);
+        }
+      }
+    }
+    s.arena = fa.end;
+    s.sol_arena = so.end;
+  }
+  s.work_bytes = 8 * (std::max(s.arena, s.sol_arena) + s.ldy() * kCholMaxRhs);  // one buffer serves both arenas
+  // launch tables
+  s.chunk_ptr.assign((size_t)s.nlev + 1, 0);
+  s.chunk_sn.clear();
+  s.chunk_c0.clear();
+  s.step_ptr.assign((size_t)s.nlev + 1, 0);
+  s.step_nact.clear();
+  s.step_tab.clear();
+  s.tab.clear();
+  for (int l = 0; l < s.nlev; l++) {
+    for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) {
+      const int J = s.lev_sn[q], sz = s.sn_first[J + 1] - s.sn_first[J], m = sz + s.sn_b[J];
+      const bool kids = s.child_ptr[J + 1] > s.child_ptr[J];
+      for (int c0 = 0; c0 < m; c0 += kCholChunk) {
+        if (!kids && c0 + kCholChunk <= sz) continue;  // nothing to zero, nothing to gather
+        s.chunk_sn.push_back(J);
+        s.chunk_c0.push_back(c0);
+      }
+    }
+    s.chunk_ptr[l + 1] = (int)s.chunk_sn.size();
+    const int b0 = s.lev_ptr[l] + s.lev_nsmall[l], nbig = s.lev_ptr[l + 1] - b0;
+    const int steps = nbig > 0 ? nblk_of(s.lev_sn[b0]) : 0;
+    for (int kb = 0; kb < steps; kb++) {
+      int nact = 0;
+      while (nact < nbig && nblk_of(s.lev_sn[b0 + nact]) > kb) nact++;
+      s.step_nact.push_back(nact);
+      s.step_tab.push_back((int)s.tab.size());
+      int64_t run = 0;
+      s.tab.push_back(0);
+      for (int a = 0; a < nact; a++) {
+        const int J = s.lev_sn[b0 + a], sz = s.sn_first[J + 1] - s.sn_first[J], m = sz + s.sn_b[J];
+        const int r0 = std::min(sz, (kb + 1) * kCholNB);
+        run += (m - r0 + kCholTile - 1) / kCholTile;
+        if (run > 2000000000LL) {
+          set_error("sparse Cholesky: a level has more than 2e9 row tiles");
+          return PO_ERR_ARG;
+        }
+        s.tab.push_back((int)run);
+      }
+    }
+    s.step_ptr[l + 1] = (int)s.step_nact.size();
+  }
+  return chol_scatter_table(s, n, colp, rows, &s.asm_ptr, &s.asm_dst, &s.asm_src);
+}
+
+}  // namespace po

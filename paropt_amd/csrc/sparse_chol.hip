@@ -1,0 +1,625 @@
+// Device side of the multifrontal sparse Cholesky (sparse_chol.hpp): numeric factorization and solves, level by level,
+// every front of a level in the same launches.  gfx950 only.
+//
+// Kernels per level of the factorization:
+//   chol_assemble_kernel   a workgroup owns kCholChunk target columns of one front: zeroes the update-matrix part and
+//                          gathers the children's update matrices through their relative indices, child after child
+//                          (fixed order, no atomics: two entries of one child never share a target)
+//   chol_small_kernel      front of order <= kCholSmall: one wavefront, the whole front in LDS, scalar fp64
+//   per block column of kCholNB columns of the larger fronts (right-looking):
+//   chol_diag_kernel       the diagonal block in LDS, one wavefront per front
+//   chol_trsm_kernel       rows below it, kCholTile rows per workgroup, one row per lane, the block's triangle in LDS
+//   chol_update_kernel     C -= A B^T on the rest of the front (panel columns and the b x b update matrix alike), one
+//                          workgroup per 64 x 64 tile of the lower triangle, grid over (row tile of any front, column
+//                          tile) through the level's running tile counts -- a large front spreads over the whole GPU
+//
+// Matrix instruction: v_mfma_f64_4x4x4_4b_f64 with the operand layout measured in wgram.hip (A lane = i + 4 b + 16 k,
+// B lane = j + 4 b + 16 k, D lane = j + 4 b + 16 i).  It sustains 75.8 TFLOP/s against 47 for 16x16x4 (wgram.hip), the
+// fp64 vector peak is the same as the matrix peak, so what it buys is operand reuse: per k-step of 4 a wavefront reads
+// 2 + 8 operands from LDS for 16 instructions (a 32 x 32 block of the tile), where a vector kernel would read one
+// operand pair per 1-4 fma.  The four blocks b are four row groups of the tile and the A operand (the column block) is
+// the same in all four, so the 16 lanes of a result register hold 16 consecutive rows of one column: stores into the
+// column-major front are 128-byte runs.
+#include "sparse_chol.hpp"
+
+#include <string.h>
+
+namespace po {
+
+namespace {
+
+struct CholDev {
+  const int *first, *nb, *ld, *uld;
+  const int64_t *panel, *upd, *sol, *rows_ptr;
+  const int *below, *rel, *child_ptr, *child;
+  double *L, *arena;
+};
+
+constexpr int kLdsLd = kCholNB + 1;
+constexpr int kOpLd = kCholTile + 16;  // operand tiles: == 16 mod 32 doubles, two k rows hit disjoint bank pairs
+
+__device__ inline double *front_entry(double *P, int ld, double *U, int uld, int s, int row, int col) {
+  return col < s ? P + (int64_t)col * ld + row : U + (int64_t)(col - s) * uld + (row - s);
+}
+
+__global__ void chol_scatter_kernel(const int *__restrict__ ptr, const int64_t *__restrict__ dst,
+                                    const int *__restrict__ src, int64_t ndst, const double *__restrict__ vals,
+                                    double *L) {
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= ndst) return;
+  double sum = 0.0;
+  for (int p = ptr[d]; p < ptr[d + 1]; p++) sum += vals[src[p]];
+  L[dst[d]] = sum;
+}
+
+__global__ __launch_bounds__(128) void chol_assemble_kernel(CholDev d, const int *__restrict__ chunk_sn,
+                                                            const int *__restrict__ chunk_c0) {
+  const int J = chunk_sn[blockIdx.x], c0 = chunk_c0[blockIdx.x];
+  const int s = d.first[J + 1] - d.first[J], b = d.nb[J], m = s + b;
+  const int c1 = min(c0 + kCholChunk, m);
+  const int ld = d.ld[J], uld = d.uld[J];
+  double *P = d.L + d.panel[J], *U = d.arena + d.upd[J];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int z0 = max(c0, s);
+  if (c1 > z0) {
+    const int total = (c1 - z0) * b;
+    for (int idx = tid; idx < total; idx += nt) {
+      const int col = z0 + idx / b, row = s + idx % b;
+      if (row >= col) U[(int64_t)(col - s) * uld + (row - s)] = 0.0;
+    }
+  }
+  __syncthreads();
+  for (int c = d.child_ptr[J]; c < d.child_ptr[J + 1]; c++) {
+    const int C = d.child[c], bc = d.nb[C], ulc = d.uld[C];
+    const int *__restrict__ rel = d.rel + d.rows_ptr[C];
+    const double *__restrict__ Uc = d.arena + d.upd[C];
+    int ja = 0, jb = 0;
+    {  // rel ascends: the child's columns that land in [c0, c1)
+      int lo = 0, hi = bc;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rel[mid] < c0) lo = mid + 1; else hi = mid;
+      }
+      ja = lo;
+      hi = bc;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rel[mid] < c1) lo = mid + 1; else hi = mid;
+      }
+      jb = lo;
+    }
+    const int total = (jb - ja) * bc;
+    for (int idx = tid; idx < total; idx += nt) {
+      const int j = ja + idx / bc, i = idx % bc;
+      if (i < j) continue;
+      *front_entry(P, ld, U, uld, s, rel[i], rel[j]) += Uc[(int64_t)j * ulc + i];
+    }
+    __syncthreads();
+  }
+}
+
+__device__ inline void flag_pivot(int *flag, int index) {
+  flag[0] = 1;
+  atomicMin(&flag[1], index);  // (the smallest index wins whatever the order: deterministic)
+}
+
+// Partial Cholesky of the first s columns of the m x m lower triangle F (column-major, kLdsLd) in LDS by ONE
+// wavefront.  A non-positive (or NaN) pivot is flagged and replaced by 1, as chol_front_dense_kernel does.
+__device__ inline void lds_partial_chol(double *F, int m, int s, int index0, int *flag) {
+  const int tid = threadIdx.x, i = tid & 31, half = tid >> 5;
+  for (int k = 0; k < s; k++) {
+    double piv = F[k * kLdsLd + k];
+    if (!(piv > 0.0)) {
+      if (tid == 0) flag_pivot(flag, index0 + k);
+      piv = 1.0;
+    }
+    const double r = sqrt(piv);
+    __syncthreads();
+    if (tid == 0) F[k * kLdsLd + k] = r;
+    if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= r;
+    __syncthreads();
+    if (i > k && i < m) {
+      const double lik = F[k * kLdsLd + i];
+      for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * F[k * kLdsLd + j];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(64) void chol_small_kernel(CholDev d, const int *__restrict__ list, int *flag) {
+  __shared__ double F[kCholSmall * kLdsLd];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
+  const int ld = d.ld[J], uld = d.uld[J];
+  double *P = d.L + d.panel[J], *U = d.arena + d.upd[J];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < m * m; idx += 64) {
+    const int col = idx / m, row = idx % m;
+    if (row >= col) F[col * kLdsLd + row] = *front_entry(P, ld, U, uld, s, row, col);
+  }
+  __syncthreads();
+  lds_partial_chol(F, m, s, first, flag);
+  for (int idx = tid; idx < m * m; idx += 64) {
+    const int col = idx / m, row = idx % m;
+    if (row >= col) *front_entry(P, ld, U, uld, s, row, col) = F[col * kLdsLd + row];
+  }
+}
+
+__global__ __launch_bounds__(64) void chol_diag_kernel(CholDev d, const int *__restrict__ list, int kb, int *flag) {
+  __shared__ double F[kCholNB * kLdsLd];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, ld = d.ld[J];
+  const int k0 = kb * kCholNB, w = min(kCholNB, s - k0);
+  double *P = d.L + d.panel[J] + (int64_t)k0 * ld + k0;
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < w * w; idx += 64) {
+    const int col = idx / w, row = idx % w;
+    if (row >= col) F[col * kLdsLd + row] = P[(int64_t)col * ld + row];
+  }
+  __syncthreads();
+  lds_partial_chol(F, w, w, first + k0, flag);
+  for (int idx = tid; idx < w * w; idx += 64) {
+    const int col = idx / w, row = idx % w;
+    if (row >= col) P[(int64_t)col * ld + row] = F[col * kLdsLd + row];
+  }
+}
+
+// which active front does row tile t belong to: tab[a] <= t < tab[a + 1]
+__device__ inline int tile_front(const int *__restrict__ tab, int nact, int t) {
+  int lo = 0, hi = nact;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tab[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kCholTile) void chol_trsm_kernel(CholDev d, const int *__restrict__ list,
+                                                              const int *__restrict__ tab, int nact, int kb) {
+  __shared__ double D[kCholNB * kLdsLd], X[kCholTile * kLdsLd];
+  const int t = blockIdx.x, a = tile_front(tab, nact, t), J = list[a];
+  const int s = d.first[J + 1] - d.first[J], m = s + d.nb[J], ld = d.ld[J];
+  const int k0 = kb * kCholNB, w = min(kCholNB, s - k0);
+  double *P = d.L + d.panel[J] + (int64_t)k0 * ld;
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < kCholNB * kCholNB; idx += kCholTile) {
+    const int col = idx / kCholNB, row = idx % kCholNB;
+    double v = row == col ? 1.0 : 0.0;  // (identity outside a partial block)
+    if (col < w && row < w && row >= col) v = P[(int64_t)col * ld + k0 + row];
+    D[col * kLdsLd + row] = v;
+  }
+  __syncthreads();
+  const int row = k0 + w + (t - tab[a]) * kCholTile + tid;
+  if (row >= m) return;
+  // the lane's row lives in LDS (stride 33: no bank conflicts), so the loops need no unrolling and no registers
+  double *x = X + tid * kLdsLd;
+  for (int k = 0; k < w; k++) x[k] = P[(int64_t)k * ld + row];
+  for (int k = 0; k < w; k++) {
+    const double xk = x[k] / D[k * kLdsLd + k];
+    P[(int64_t)k * ld + row] = xk;
+    for (int j = k + 1; j < w; j++) x[j] -= xk * D[k * kLdsLd + j];
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_update_kernel(CholDev d, const int *__restrict__ list,
+                                                          const int *__restrict__ tab, int nact, int kb) {
+  __shared__ double Rs[kCholNB * kOpLd], Cs[kCholNB * kOpLd];
+  const int t = blockIdx.x, a = tile_front(tab, nact, t);
+  const int ti = t - tab[a], tj = blockIdx.y;
+  if (tj > ti) return;
+  const int J = list[a];
+  const int s = d.first[J + 1] - d.first[J], m = s + d.nb[J], ld = d.ld[J], uld = d.uld[J];
+  const int k0 = kb * kCholNB, w = min(kCholNB, s - k0), r0 = k0 + w;
+  double *P = d.L + d.panel[J], *U = d.arena + d.upd[J];
+  const double *__restrict__ Pk = P + (int64_t)k0 * ld;
+  const int R0 = r0 + ti * kCholTile, C0 = r0 + tj * kCholTile;
+  const int tid = threadIdx.x;
+  {
+    const int row = tid & 63, kq = tid >> 6;
+#pragma unroll
+    for (int it = 0; it < kCholNB / 4; it++) {
+      const int kk = kq + 4 * it;
+      const bool live = kk < w;
+      Rs[kk * kOpLd + row] = (live && R0 + row < m) ? Pk[(int64_t)kk * ld + R0 + row] : 0.0;
+      Cs[kk * kOpLd + row] = (live && C0 + row < m) ? Pk[(int64_t)kk * ld + C0 + row] : 0.0;
+    }
+  }
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63, wr = wave & 1, wc = wave >> 1;
+  if (ti == tj && wr < wc) return;  // this quarter lies above the diagonal
+  double acc[2][8];
+#pragma unroll
+  for (int rb = 0; rb < 2; rb++) {
+#pragma unroll
+    for (int cb = 0; cb < 8; cb++) acc[rb][cb] = 0.0;
+  }
+  const int ksteps = (w + 3) / 4;
+  for (int kk = 0; kk < ksteps; kk++) {
+    const int k = kk * 4 + (lane >> 4);
+    double bop[2], aop[8];
+#pragma unroll
+    for (int rb = 0; rb < 2; rb++) bop[rb] = Rs[k * kOpLd + wr * 32 + rb * 16 + (lane & 15)];
+#pragma unroll
+    for (int cb = 0; cb < 8; cb++) aop[cb] = Cs[k * kOpLd + wc * 32 + cb * 4 + (lane & 3)];
+#pragma unroll
+    for (int rb = 0; rb < 2; rb++) {
+#pragma unroll
+      for (int cb = 0; cb < 8; cb++)
+        acc[rb][cb] = __builtin_amdgcn_mfma_f64_4x4x4f64(aop[cb], bop[rb], acc[rb][cb], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int rb = 0; rb < 2; rb++) {
+    const int row = R0 + wr * 32 + rb * 16 + (lane & 15);
+#pragma unroll
+    for (int cb = 0; cb < 8; cb++) {
+      const int col = C0 + wc * 32 + cb * 4 + (lane >> 4);
+      if (row < m && col < m && row >= col) *front_entry(P, ld, U, uld, s, row, col) -= acc[rb][cb];
+    }
+  }
+}
+
+// ---- solves ------------------------------------------------------------------------------------------------------
+__global__ void chol_permute_kernel(double *Y, int64_t ldy, double *x, int64_t ldx, const int *__restrict__ perm,
+                                    int n, int nrhs, int out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)n * nrhs) return;
+  const int p = (int)(idx % n), r = (int)(idx / n);
+  if (out) {
+    x[perm[p] + r * ldx] = Y[p + r * ldy];
+  } else {
+    Y[p + r * ldy] = x[perm[p] + r * ldx];
+  }
+}
+
+__device__ inline void load_triangle(double *D, const double *P, int ld, int w) {
+  for (int idx = threadIdx.x; idx < w * w; idx += blockDim.x) {
+    const int col = idx / w, row = idx % w;
+    if (row >= col) D[col * kLdsLd + row] = P[(int64_t)col * ld + row];
+  }
+}
+
+// Forward: the front's block = its rows of the right-hand side plus the children's update vectors (fixed order),
+// y_J = L11^-1 (.), and the update vector u = (children's part below) - L21 y_J for the parent.
+__global__ __launch_bounds__(256) void chol_fwd_kernel(CholDev d, const int *__restrict__ list, double *Y, int64_t ldy,
+                                                       int nrhs) {
+  __shared__ double D[kCholNB * kLdsLd], yb[kCholNB * kCholMaxRhs];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
+  const int ld = d.ld[J], ul = d.uld[J];
+  const double *__restrict__ P = d.L + d.panel[J];
+  double *u = d.arena + d.sol[J];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < b * nrhs; idx += 256) u[idx % b + (int64_t)(idx / b) * ul] = 0.0;
+  __syncthreads();
+  for (int c = d.child_ptr[J]; c < d.child_ptr[J + 1]; c++) {
+    const int C = d.child[c], bc = d.nb[C], ulc = d.uld[C];
+    const int *__restrict__ rel = d.rel + d.rows_ptr[C];
+    const double *__restrict__ uc = d.arena + d.sol[C];
+    for (int idx = tid; idx < bc * nrhs; idx += 256) {
+      const int i = idx % bc, r = idx / bc, t = rel[i];
+      const double v = uc[i + (int64_t)r * ulc];
+      if (t < s) {
+        Y[first + t + r * ldy] += v;
+      } else {
+        u[t - s + (int64_t)r * ul] += v;
+      }
+    }
+    __syncthreads();
+  }
+  for (int k0 = 0; k0 < s; k0 += kCholNB) {
+    const int w = min(kCholNB, s - k0);
+    load_triangle(D, P + (int64_t)k0 * ld + k0, ld, w);
+    for (int idx = tid; idx < w * nrhs; idx += 256) {
+      const int k = idx % w, r = idx / w;
+      yb[k * kCholMaxRhs + r] = Y[first + k0 + k + r * ldy];
+    }
+    __syncthreads();
+    if (tid < nrhs) {
+      const int r = tid;
+      for (int j = 0; j < w; j++) {
+        double acc = yb[j * kCholMaxRhs + r];
+        for (int k = 0; k < j; k++) acc -= D[k * kLdsLd + j] * yb[k * kCholMaxRhs + r];
+        acc /= D[j * kLdsLd + j];
+        yb[j * kCholMaxRhs + r] = acc;
+        Y[first + k0 + j + r * ldy] = acc;
+      }
+    }
+    __syncthreads();
+    const int i0 = k0 + w, nrow = m - i0;
+    for (int idx = tid; idx < nrow * nrhs; idx += 256) {
+      const int i = i0 + idx % nrow, r = idx / nrow;
+      double acc = 0.0;
+      for (int k = 0; k < w; k++) acc += P[(int64_t)(k0 + k) * ld + i] * yb[k * kCholMaxRhs + r];
+      if (i < s) {
+        Y[first + i + r * ldy] -= acc;
+      } else {
+        u[i - s + (int64_t)r * ul] -= acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Backward: x_J = L11^-T (y_J - L21^T x_below); the rows below belong to ancestors, finished in earlier launches.
+__global__ __launch_bounds__(256) void chol_bwd_kernel(CholDev d, const int *__restrict__ list, double *Y, int64_t ldy,
+                                                       int nrhs) {
+  __shared__ double D[kCholNB * kLdsLd], z[kCholNB * kCholMaxRhs];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
+  const int ld = d.ld[J];
+  const double *__restrict__ P = d.L + d.panel[J];
+  const int *__restrict__ rows = d.below + d.rows_ptr[J];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int nblk = (s + kCholNB - 1) / kCholNB;
+  for (int kb = nblk - 1; kb >= 0; kb--) {
+    const int k0 = kb * kCholNB, w = min(kCholNB, s - k0);
+    load_triangle(D, P + (int64_t)k0 * ld + k0, ld, w);
+    for (int p = wave; p < w * nrhs; p += 4) {
+      const int k = p % w, r = p / w;
+      const double *__restrict__ col = P + (int64_t)(k0 + k) * ld;
+      double sum = 0.0;
+      for (int i = k0 + w + lane; i < m; i += 64) {
+        const double xv = i < s ? Y[first + i + r * ldy] : Y[rows[i - s] + r * ldy];
+        sum += col[i] * xv;
+      }
+      for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+      if (lane == 0) z[k * kCholMaxRhs + r] = Y[first + k0 + k + r * ldy] - sum;
+    }
+    __syncthreads();
+    if (tid < nrhs) {
+      const int r = tid;
+      for (int k = w - 1; k >= 0; k--) {
+        double acc = z[k * kCholMaxRhs + r];
+        for (int j = k + 1; j < w; j++) acc -= D[k * kLdsLd + j] * z[j * kCholMaxRhs + r];
+        acc /= D[k * kLdsLd + k];
+        z[k * kCholMaxRhs + r] = acc;
+        Y[first + k0 + k + r * ldy] = acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <class T>
+void dfree(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+template <class T>
+int upload(T *&dst, const std::vector<T> &src) {
+  dfree(dst);
+  const size_t bytes = (src.size() + 4) * sizeof(T);
+  PO_HIP(hipMalloc((void **)&dst, bytes));
+  PO_HIP(hipMemset(dst, 0, bytes));
+  if (!src.empty()) PO_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return PO_OK;
+}
+
+}  // namespace
+
+SparseChol::~SparseChol() {
+  dfree(L);
+  dfree(arena);
+  dfree(Y);
+  dfree(avals);
+  dfree(xbuf);
+  dfree(d_flag);
+  dfree(d_perm);
+  dfree(d_first);
+  dfree(d_b);
+  dfree(d_ld);
+  dfree(d_uld);
+  dfree(d_below);
+  dfree(d_rel);
+  dfree(d_child_ptr);
+  dfree(d_child);
+  dfree(d_rows_ptr);
+  dfree(d_panel);
+  dfree(d_upd);
+  dfree(d_sol);
+  dfree(d_lev_sn);
+  dfree(d_chunk_sn);
+  dfree(d_chunk_c0);
+  dfree(d_tab);
+  dfree(d_asm_ptr);
+  dfree(d_asm_src);
+  dfree(d_asm_dst);
+}
+
+int SparseChol::upload() {
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t arena_doubles = std::max(sym.arena, sym.sol_arena) + 4;
+  const int64_t y_doubles = sym.ldy() * kCholMaxRhs;
+  if (hipMalloc((void **)&arena, (size_t)arena_doubles * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&Y, (size_t)y_doubles * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&L, ((size_t)sym.Lsize + 4) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("sparse Cholesky: cannot allocate the factor (%lld bytes) and its work space (%lld bytes)",
+              (long long)(8 * sym.Lsize), (long long)sym.work_bytes);
+    return PO_ERR_ARG;
+  }
+  PO_HIP(hipMemset(arena, 0, (size_t)arena_doubles * sizeof(double)));
+  PO_HIP(hipMemset(Y, 0, (size_t)y_doubles * sizeof(double)));
+  PO_HIP(hipMemset(L, 0, ((size_t)sym.Lsize + 4) * sizeof(double)));
+  PO_HIP(hipMalloc((void **)&avals, (sym.rows.size() + 4) * sizeof(double)));
+  PO_HIP(hipMalloc((void **)&d_flag, 4 * sizeof(int)));
+  PO_TRY(po::upload(d_perm, sym.perm));
+  PO_TRY(po::upload(d_first, sym.sn_first));
+  PO_TRY(po::upload(d_b, sym.sn_b));
+  PO_TRY(po::upload(d_ld, sym.sn_ld));
+  PO_TRY(po::upload(d_uld, sym.upd_ld));
+  PO_TRY(po::upload(d_below, sym.below_rows));
+  PO_TRY(po::upload(d_rel, sym.rel));
+  PO_TRY(po::upload(d_child_ptr, sym.child_ptr));
+  PO_TRY(po::upload(d_child, sym.child));
+  PO_TRY(po::upload(d_rows_ptr, sym.rows_ptr));
+  PO_TRY(po::upload(d_panel, sym.panel_off));
+  PO_TRY(po::upload(d_upd, sym.upd_off));
+  PO_TRY(po::upload(d_sol, sym.sol_off));
+  PO_TRY(po::upload(d_lev_sn, sym.lev_sn));
+  PO_TRY(po::upload(d_chunk_sn, sym.chunk_sn));
+  PO_TRY(po::upload(d_chunk_c0, sym.chunk_c0));
+  PO_TRY(po::upload(d_tab, sym.tab));
+  PO_TRY(po::upload(d_asm_ptr, sym.asm_ptr));
+  PO_TRY(po::upload(d_asm_src, sym.asm_src));
+  PO_TRY(po::upload(d_asm_dst, sym.asm_dst));
+  PO_HIP(hipDeviceSynchronize());
+  return PO_OK;
+}
+
+int SparseChol::scatter(const int *ptr, const int64_t *dst, const int *src, int64_t ndst, const double *dvals) {
+  PO_HIP(hipMemsetAsync(L, 0, ((size_t)sym.Lsize + 4) * sizeof(double), ctx->stream));
+  if (ndst > 0) {
+    hipLaunchKernelGGL(chol_scatter_kernel, dim3((unsigned)((ndst + 255) / 256)), dim3(256), 0, ctx->stream, ptr, dst,
+                       src, ndst, dvals, L);
+    PO_HIP(hipGetLastError());
+  }
+  have_values = true;
+  factored = false;
+  return PO_OK;
+}
+
+int SparseChol::setValuesDevice(const double *dvals) {
+  PO_HIP(hipSetDevice(ctx->device));
+  return scatter(d_asm_ptr, d_asm_dst, d_asm_src, (int64_t)sym.asm_dst.size(), dvals);
+}
+
+int SparseChol::setValuesHost(int64_t n, const int *colp, const int *rows, const double *vals) {
+  PO_HIP(hipSetDevice(ctx->device));
+  const bool same = n == sym.n && memcmp(colp, sym.colp.data(), ((size_t)n + 1) * sizeof(int)) == 0 &&
+                    (sym.rows.empty() || memcmp(rows, sym.rows.data(), sym.rows.size() * sizeof(int)) == 0);
+  if (same) {
+    if (!sym.rows.empty())
+      PO_HIP(hipMemcpyAsync(avals, vals, sym.rows.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PO_TRY(setValuesDevice(avals));
+    PO_HIP(hipStreamSynchronize(ctx->stream));  // (the caller's array may go away)
+    return PO_OK;
+  }
+  // another pattern: its own table, built on the host and used once
+  std::vector<int> ptr, src;
+  std::vector<int64_t> dst;
+  PO_TRY(chol_scatter_table(sym, n, colp, rows, &ptr, &dst, &src));
+  int *tp = nullptr, *ts = nullptr;
+  int64_t *td = nullptr;
+  double *tv = nullptr;
+  const std::vector<double> hv(vals, vals + colp[n]);
+  int rc = po::upload(tp, ptr);
+  if (rc == PO_OK) rc = po::upload(ts, src);
+  if (rc == PO_OK) rc = po::upload(td, dst);
+  if (rc == PO_OK) rc = po::upload(tv, hv);
+  if (rc == PO_OK) rc = scatter(tp, td, ts, (int64_t)dst.size(), tv);
+  (void)hipStreamSynchronize(ctx->stream);
+  dfree(tp);
+  dfree(ts);
+  dfree(td);
+  dfree(tv);
+  return rc;
+}
+
+int SparseChol::factor(int *info) {
+  if (info) *info = 0;
+  if (!have_values) {
+    set_error("sparse Cholesky: factor() needs values set since the last factorization");
+    return PO_ERR_ARG;
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // flag[0] = 0, flag[1] = 0x7f7f7f7f (above every index)
+  PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), st));
+  PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
+                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  for (int l = 0; l < sym.nlev; l++) {
+    const int nch = sym.chunk_ptr[l + 1] - sym.chunk_ptr[l];
+    if (nch > 0) {
+      hipLaunchKernelGGL(chol_assemble_kernel, dim3(nch), dim3(128), 0, st, d, d_chunk_sn + sym.chunk_ptr[l],
+                         d_chunk_c0 + sym.chunk_ptr[l]);
+    }
+    const int nsmall = sym.lev_nsmall[l];
+    if (nsmall > 0) {
+      hipLaunchKernelGGL(chol_small_kernel, dim3(nsmall), dim3(64), 0, st, d, d_lev_sn + sym.lev_ptr[l], d_flag);
+    }
+    const int *big = d_lev_sn + sym.lev_ptr[l] + nsmall;
+    for (int step = sym.step_ptr[l]; step < sym.step_ptr[l + 1]; step++) {
+      const int kb = step - sym.step_ptr[l], nact = sym.step_nact[step];
+      const int *htab = &sym.tab[sym.step_tab[step]];
+      const int *dtab = d_tab + sym.step_tab[step];
+      hipLaunchKernelGGL(chol_diag_kernel, dim3(nact), dim3(64), 0, st, d, big, kb, d_flag);
+      const int total = htab[nact];
+      if (total > 0) {
+        int most = 0;
+        for (int a = 0; a < nact; a++) most = std::max(most, htab[a + 1] - htab[a]);
+        hipLaunchKernelGGL(chol_trsm_kernel, dim3(total), dim3(kCholTile), 0, st, d, big, dtab, nact, kb);
+        hipLaunchKernelGGL(chol_update_kernel, dim3(total, most), dim3(256), 0, st, d, big, dtab, nact, kb);
+      }
+    }
+    PO_HIP(hipGetLastError());
+  }
+  int flag[4] = {0, 0, 0, 0};
+  PO_HIP(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  PO_HIP(hipStreamSynchronize(st));
+  have_values = false;
+  factored = true;
+  if (flag[0] != 0) {
+    // like LAPACK's info behind the reference's factor() (src/ParOptSparseCholesky.cpp:631): the pivot was
+    // replaced by 1 and the factorization finished, the caller decides
+    set_error("sparse Cholesky: non-positive pivot at permuted index %d", flag[1]);
+    if (info) *info = 1 + flag[1];
+  }
+  return PO_OK;
+}
+
+int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
+  if (!factored) {
+    set_error("sparse Cholesky: solve() before factor()");
+    return PO_ERR_ARG;
+  }
+  if (nrhs < 0 || (nrhs > 1 && ldx < sym.n)) {
+    set_error("sparse Cholesky: solve with nrhs %d, ldx %lld (size %d)", nrhs, (long long)ldx, sym.n);
+    return PO_ERR_ARG;
+  }
+  if (sym.n == 0 || nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
+                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  const int64_t ldy = sym.ldy();
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    double *x = dx + (int64_t)r0 * ldx;
+    const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 0);
+    for (int l = 0; l < sym.nlev; l++) {
+      const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
+      hipLaunchKernelGGL(chol_fwd_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy, nr);
+    }
+    for (int l = sym.nlev - 1; l >= 0; l--) {
+      const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
+      hipLaunchKernelGGL(chol_bwd_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy, nr);
+    }
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::solveHost(double *x, int nrhs, int64_t ldx) {
+  if (sym.n == 0 || nrhs <= 0) return solveDevice(nullptr, nrhs, ldx);
+  if (nrhs > 1 && ldx < sym.n) return solveDevice(nullptr, nrhs, ldx);
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t count = (int64_t)(nrhs - 1) * ldx + sym.n;
+  if (count > xbuf_cap) {
+    dfree(xbuf);
+    xbuf_cap = 0;
+    PO_HIP(hipMalloc((void **)&xbuf, (size_t)count * sizeof(double)));
+    xbuf_cap = count;
+  }
+  PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PO_TRY(solveDevice(xbuf, nrhs, ldx));
+  PO_HIP(hipMemcpyAsync(x, xbuf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
+
+}  // namespace po

@@ -1,0 +1,101 @@
+// ParOptSparseCholesky (reference src/ParOptSparseCholesky.h:29-162): a sparse Cholesky factorization
+//     L L^T = P A P^T
+// of a user's own SPD matrix, as a supernodal MULTIFRONTAL method with dense fronts on the device.  It stands beside
+// CsrSparse (csr.hpp), which stays the interior point's factor.
+//
+// Split of the work:
+//   host, once per pattern (sparse_chol.cpp, no device needed): symmetrised pattern, ordering, elimination tree in
+//     postorder, fundamental supernodes, the row structure of every supernode, level sets over the supernode tree,
+//     relative indices child -> parent front, the scatter table A -> L, the layout of the work arena and the launch
+//     tables of every level;
+//   device, every factorization (sparse_chol.hip): level by level, every front of a level in the same launches --
+//     assemble (zero + extend-add, the parent gathers its children in a fixed order, no atomics), partial Cholesky of
+//     the first s columns (one wavefront for a small front; diagonal block / trsm / MFMA tile update per block column
+//     for the others), and level-scheduled forward and backward solves for up to kCholMaxRhs right-hand sides a sweep.
+//
+// Ordering.  PO_ORDER_ND is the nested dissection of csr.cpp (sym_nd_order).  PO_ORDER_NATURAL is the identity, or the
+// caller's perm (perm[new] = old).  PO_ORDER_AMD is ACCEPTED AND GIVEN THE SAME NESTED DISSECTION: this project has no
+// minimum-degree code, and the reference's is not taken over.
+//
+// Supernode J: s columns first .. first + s - 1 and b rows below them (below_rows, ascending); its front is dense of
+// order m = s + b.  The (s + b) x s panel of L is stored column-major with an even leading dimension (16-byte aligned
+// columns); the b x b update matrix lives in the arena until the parent has gathered it.  Only lower triangles are
+// read or written anywhere.
+#pragma once
+#include <vector>
+
+#include "core.hpp"
+
+namespace po {
+
+constexpr int kCholNB = 32;      // block width of a blocked front
+constexpr int kCholSmall = 32;   // a front of order <= this is factored by one wavefront in LDS
+constexpr int kCholTile = 64;    // trsm row chunk and edge of an update tile (one workgroup)
+constexpr int kCholChunk = 32;   // target columns of a front that one assembling workgroup owns
+constexpr int kCholMaxRhs = 32;  // right-hand sides per solve sweep
+
+struct CholSymbolic {
+  int n = 0, order = 0;
+  std::vector<int> colp, rows;   // the creation pattern as given
+  std::vector<int> perm, iperm;  // perm[new] = old
+  int nsn = 0;
+  std::vector<int> sn_first;     // nsn + 1
+  std::vector<int> sn_parent, sn_level, sn_of;
+  std::vector<int> sn_b, sn_ld, upd_ld;
+  std::vector<int64_t> rows_ptr;     // nsn + 1, into below_rows and rel
+  std::vector<int> below_rows, rel;  // rel: position of each below-row in the PARENT's front
+  std::vector<int64_t> panel_off, upd_off, sol_off;
+  int64_t Lsize = 0, arena = 0, sol_arena = 0;
+  std::vector<int> child_ptr, child;
+  int nlev = 0;
+  // level l = supernodes lev_sn[lev_ptr[l] .. lev_ptr[l+1]): the small fronts first (lev_nsmall[l] of them), then the
+  // blocked ones with the most block columns first, so the fronts that still have block column kb form a prefix
+  std::vector<int> lev_ptr, lev_sn, lev_nsmall;
+  std::vector<int> chunk_ptr, chunk_sn, chunk_c0;  // assembling workgroups of each level
+  // block column kb of level l: step = step_ptr[l] + kb; step_nact fronts take part; tab[step_tab[step] .. + nact]
+  // is the running count of their row tiles (a trsm chunk, or a row of update tiles, each)
+  std::vector<int> step_ptr, step_nact, step_tab, tab;
+  // value scatter of the creation pattern: destination d (asm_dst, an offset into L) sums asm_src[asm_ptr[d] ..]
+  std::vector<int> asm_ptr, asm_src;
+  std::vector<int64_t> asm_dst;
+  int64_t nnzL = 0, work_bytes = 0;
+  int max_s = 0, max_front = 0;
+  int64_t ldy() const { return ((int64_t)n + 3) / 4 * 4 + 4; }
+};
+
+// PO_OK or PO_ERR_ARG with a message; pure host code
+int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *perm, CholSymbolic *out);
+// the scatter table of any pattern onto the factor: entries at the permuted-lower position, in entry order per
+// destination (the reference's setValues, src/ParOptSparseCholesky.cpp:205-252); an entry outside the pattern of L is
+// PO_ERR_ARG (the reference drops it silently)
+int chol_scatter_table(const CholSymbolic &s, int64_t n, const int *colp, const int *rows, std::vector<int> *ptr,
+                       std::vector<int64_t> *dst, std::vector<int> *src);
+
+class SparseChol {
+ public:
+  SparseChol(Ctx *c) : ctx(c) {}
+  ~SparseChol();
+  CholSymbolic sym;
+  Ctx *ctx;  // null: analysis only
+  int upload();  // after chol_analyse: device tables, L, arena
+  int setValuesDevice(const double *dvals);
+  int setValuesHost(int64_t n, const int *colp, const int *rows, const double *vals);
+  int factor(int *info);
+  int solveDevice(double *dx, int nrhs, int64_t ldx);
+  int solveHost(double *x, int nrhs, int64_t ldx);
+
+ private:
+  int scatter(const int *d_ptr, const int64_t *d_dst, const int *d_src, int64_t ndst, const double *dvals);
+  bool have_values = false, factored = false;
+  double *L = nullptr, *arena = nullptr, *Y = nullptr, *avals = nullptr, *xbuf = nullptr;
+  int64_t xbuf_cap = 0;
+  int *d_flag = nullptr;
+  int *d_perm = nullptr, *d_first = nullptr, *d_b = nullptr, *d_ld = nullptr, *d_uld = nullptr;
+  int *d_below = nullptr, *d_rel = nullptr, *d_child_ptr = nullptr, *d_child = nullptr;
+  int64_t *d_rows_ptr = nullptr, *d_panel = nullptr, *d_upd = nullptr, *d_sol = nullptr;
+  int *d_lev_sn = nullptr, *d_chunk_sn = nullptr, *d_chunk_c0 = nullptr, *d_tab = nullptr;
+  int *d_asm_ptr = nullptr, *d_asm_src = nullptr;
+  int64_t *d_asm_dst = nullptr;
+};
+
+}  // namespace po

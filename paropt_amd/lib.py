@@ -49,6 +49,7 @@ SPARSE_JAC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, po_vec, po_vec, po_
 SPARSE_OBJCON_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, c_double_p, c_double_p, po_vec)
 SPARSE_GRAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, po_vec, po_vec, vec_p, C.c_void_p, C.c_int64)
 po_csr_symbolic = C.c_void_p
+po_sparse_chol = C.c_void_p
 c_int_pp = C.POINTER(c_int_p)
 
 
@@ -270,6 +271,16 @@ SIGNATURES = {
     "po_csr_symbolic_arrays": (
         C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
     "po_csr_symbolic_destroy": (C.c_int, [po_csr_symbolic]),
+    "po_sparse_chol_create": (
+        C.c_int, [po_ctx, C.c_int64, c_int_p, c_int_p, C.c_int, c_int_p, C.POINTER(po_sparse_chol)]),
+    "po_sparse_chol_set_values": (C.c_int, [po_sparse_chol, C.c_int64, c_int_p, c_int_p, c_double_p]),
+    "po_sparse_chol_set_values_device": (C.c_int, [po_sparse_chol, C.c_void_p]),
+    "po_sparse_chol_factor": (C.c_int, [po_sparse_chol, c_int_p]),
+    "po_sparse_chol_solve": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_solve_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_info": (C.c_int, [po_sparse_chol, c_i64_p]),
+    "po_sparse_chol_arrays": (C.c_int, [po_sparse_chol, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
+    "po_sparse_chol_destroy": (C.c_int, [po_sparse_chol]),
     "po_problem_set_bounds_mode": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_linear_constraints": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_var_bound_options": (C.c_int, [po_problem, C.c_int, C.c_int]),

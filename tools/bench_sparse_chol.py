@@ -1,0 +1,138 @@
+"""
+The multifrontal SparseCholesky against the interior point's row factor on the same matrix: for the grid pattern of
+tools/bench_csr_factor.py, S = C + Aw D^-1 Aw^T is built on the host (scipy) and, in one process, alternating, three
+repeats each, timed are
+    pa.quasidef_factor / pa.quasidef_apply             (CsrSparse, the engine of the interior point)
+    SparseCholesky.set_values_device + factor / solve_tensor   on the same S
+One JSON line per size.
+
+    python tools/bench_sparse_chol.py [--sizes 150 300] [--repeats 3] [--inner 3] [--out file.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def run(ctx, nx, repeats, inner):
+    import scipy.sparse as sp
+    import torch
+
+    import paropt_amd as pa
+    from csr_helpers import grid_pattern
+
+    n = nx * nx
+    rowp, cols = grid_pattern(nx, nx)
+    w = len(rowp) - 1
+    rng = np.random.default_rng(0)
+    data = rng.uniform(0.5, 1.5, size=int(rowp[-1]))
+
+    class P(pa.Problem):
+        def __init__(self):
+            super().__init__(ctx, n, 1, 1, nwcon=w, nwinequality=w, rowp=rowp, cols=cols)
+
+        def getVarsAndBounds(self, x, lb, ub):
+            x[:], lb[:], ub[:] = 0.5, 0.0, 1.0
+
+        def evalSparseObjCon(self, x, sparse):
+            sparse[:] = 1.0
+            return 0, float(np.sum(x * x)), np.array([1.0 - np.sum(x) / n])
+
+        def evalSparseObjConGradient(self, x, g, A, d):
+            g[:] = 2.0 * x
+            A[0][:] = -1.0 / n
+            d[:] = data
+            return 0
+
+    prob = P()
+    pa.InteriorPoint(prob, {"max_major_iters": 0}).optimize()  # uploads the Jacobian entries
+
+    def vec(arr):
+        v = pa.PVec(ctx, len(arr))
+        v.from_numpy(arr)
+        return v
+
+    dinv, cdiag = rng.uniform(0.5, 2.0, n), rng.uniform(0.1, 1.0, w)
+    x, d, c = vec(np.full(n, 0.5)), vec(dinv), vec(cdiag)
+    bx, bw = vec(np.zeros(n)), vec(rng.standard_normal(w))
+    yx, yw = pa.PVec(ctx, n), pa.PVec(ctx, w)
+    Aw = sp.csr_matrix((data, cols, rowp), shape=(w, n))
+    S = (sp.diags(cdiag) + Aw @ sp.diags(dinv) @ Aw.T).tocsc()
+    S.sort_indices()
+    t0 = time.perf_counter()
+    chol = pa.SparseCholesky(ctx, w, S.indptr, S.indices)
+    t_setup = time.perf_counter() - t0
+    dev = torch.device("cuda", ctx.device())
+    svals = torch.from_numpy(np.ascontiguousarray(S.data)).to(dev)
+    rhs = torch.from_numpy(bw.to_numpy().copy()).to(dev)
+    work = rhs.clone()
+    # warm both engines, and check that they solve the same system
+    pa.quasidef_factor(prob, x, d, c)
+    pa.quasidef_apply(prob, x, d, c, bx, bw, yx, yw)
+    chol.set_values_device(svals)
+    assert chol.factor() == 0
+    chol.solve_tensor(work)
+    ctx.synchronize()
+    # [D Aw^T; Aw -C] [yx; -yw] = [0; bw]  =>  yx = D^-1 Aw^T yw and S yw = bw
+    diff = float(np.abs(work.cpu().numpy() - yw.to_numpy()).max())
+    scale = float(np.abs(yw.to_numpy()).max())
+
+    def timed(fn):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        ctx.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / inner
+
+    def chol_factor():
+        chol.set_values_device(svals)
+        chol.factor()
+
+    def chol_solve():
+        work.copy_(rhs)
+        chol.solve_tensor(work)
+
+    rec = {"pattern": "grid %dx%d" % (nx, nx), "n": w, "nnzS": int(S.nnz), "nnzL_multifrontal": chol.nnzL,
+           "nnzL_row": pa.CsrSymbolic(n, rowp, cols).nnzL, "snodes": chol.num_snodes, "levels": chol.nlevels,
+           "max_snode": chol.max_snode, "max_front": chol.max_front, "work_bytes": chol.work_bytes,
+           "setup_s": t_setup, "solutions_max_abs_diff": diff, "solution_max_abs": scale,
+           "quasidef_factor_ms": [], "chol_factor_ms": [], "quasidef_apply_ms": [], "chol_solve_ms": []}
+    for _ in range(repeats):
+        rec["quasidef_factor_ms"].append(timed(lambda: pa.quasidef_factor(prob, x, d, c)))
+        rec["chol_factor_ms"].append(timed(chol_factor))
+        rec["quasidef_apply_ms"].append(timed(lambda: pa.quasidef_apply(prob, x, d, c, bx, bw, yx, yw)))
+        rec["chol_solve_ms"].append(timed(chol_solve))
+    rec["factor_ratio_row_over_multifrontal"] = [a / b for a, b in zip(rec["quasidef_factor_ms"], rec["chol_factor_ms"])]
+    rec["solve_ratio_row_over_multifrontal"] = [a / b for a, b in zip(rec["quasidef_apply_ms"], rec["chol_solve_ms"])]
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[150, 300])
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--inner", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import paropt_amd as pa
+
+    ctx = pa.Context(0)
+    lines = []
+    for nx in a.sizes:
+        lines.append(json.dumps(run(ctx, nx, a.repeats, a.inner)))
+        print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
