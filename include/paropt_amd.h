@@ -360,6 +360,15 @@ int po_problem_get_sparse_jacobian_data(po_problem p, const int **rowp, const in
  * NULL (the three-argument apply :39).  bx must not alias yx. */
 int po_quasidef_factor(po_problem p, po_vec x, po_vec dinv, po_vec c);
 int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, po_vec bw, po_vec yx, po_vec yw);
+/* The panel steps of the sparse solver, stand-alone, with the factor of the last po_quasidef_factor (c as that call
+ * left it): for nv vectors P_j (n) and U_j = Aw (dinv o P_j)
+ *   W2 (host, nv x nv, column-major) = U^T S^-1 U,   and with alpha (host, nv) != NULL   out (w) = -S^-1 (U alpha).
+ * It runs what the interior point's Gram correction runs, in its order and through the problem's solver, whatever
+ * its form: panel image, the solver's half (or full) solve of the panel, the weighted Gram of the half-solved panel
+ * or the symmetrised cross product with the solved one, then the correction from the same panel.  nv is not
+ * limited: panels wider than one kernel's pointer table go in slabs.  out may be NULL when alpha is. */
+int po_quasidef_gram(po_problem p, po_vec x, po_vec dinv, po_vec c, const po_vec *P, int nv, double *W2,
+                     const double *alpha, po_vec out);
 /* getFactorInfo (src/ParOptSparseMat.cpp:433-450): one line about the sparse factor, NULL for the block form */
 const char *po_quasidef_factor_info(po_problem p);
 /* createQuasiDefMat (src/ParOptProblem.h:72): a problem brings its own solver for the quasi-definite block
@@ -409,6 +418,18 @@ int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]);
  * only; the triangle inside is factored / solved by one workgroup).  Any output pointer may be NULL. */
 int po_csr_symbolic_arrays(po_csr_symbolic h, const int **perm, const int **parent, const int **Lrowp,
                            const int **Lcols, const int **level_ptr, const int **front_of);
+/* The kernel forms the device factorization and the two triangular sweeps launch on this pattern, for a panel of nv
+ * right-hand sides (the factorization does not depend on nv; nv above one kernel's pointer table is cut into slabs
+ * and a level counts a form that any slab uses).  *count forms; names[f] (static) and levels[f] = number of
+ * elimination levels that launch form f (borrowed until the next call on h).  The names: "level:thin|table|search"
+ * (ordinary rows: a thread per row, a wavefront per row with an LDS hash table, ... with binary search where the row
+ * exceeds the table), "front_rows:table|wide|search" and "front_syrk:table|search" (the part of the front rows left
+ * of their fronts), "front_dense:lds|global" (the dense triangle of a front, by its size), and for the sweeps
+ * "trsv_fwd:" / "trsv_bwd:" "thin|wave|wave_split" (a thread or a wavefront per row and right-hand side; split: the
+ * right-hand sides of a row spread over several workgroups).  This function is what the solver itself launches by.
+ * No context needed. */
+int po_csr_symbolic_kernel_forms(po_csr_symbolic h, int nv, int *count, const char *const **names,
+                                 const int **levels);
 int po_csr_symbolic_destroy(po_csr_symbolic h);
 /* nwblock of ParOptQuasiDefBlockMat (src/ParOptSparseMat.cpp:11-229) for the callback form: consecutive blocks of
  * nwblock (1..16) sparse constraints may share variables inside a block.  add_sparse_inner_product then receives,

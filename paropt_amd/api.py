@@ -1377,6 +1377,7 @@ class CsrSymbolic:
         h = L.po_csr_symbolic()
         check(lib.po_csr_symbolic_create_split(int(nvars), w, rowp.ctypes.data_as(L.c_int_p),
                                                cols.ctypes.data_as(L.c_int_p), int(dense_column_rows), C.byref(h)))
+        self._h = h
         try:
             dc, cnt = L.c_int_p(), C.c_int()
             check(lib.po_csr_symbolic_dense_columns(h, C.byref(dc), C.byref(cnt)))
@@ -1396,8 +1397,28 @@ class CsrSymbolic:
             self.Lrowp, self.Lcols = arr(ptrs[2], w + 1), arr(ptrs[3], self.nnzL)
             self.level_ptr = arr(ptrs[4], self.nlevels + 1)
             self.front_of = arr(ptrs[5], w)
-        finally:
-            lib.po_csr_symbolic_destroy(h)
+        except Exception:
+            self.close()
+            raise
+
+    def kernel_forms(self, nv=1):
+        """The kernel forms the device factorization and the two triangular sweeps launch on this pattern for a panel
+        of nv right-hand sides: {form name: number of elimination levels that launch it}, every name the solver knows
+        (a form no level uses maps to 0).  It is the function the solver itself launches by; no device needed."""
+        cnt, names, levels = C.c_int(), C.POINTER(C.c_char_p)(), L.c_int_p()
+        check(lib.po_csr_symbolic_kernel_forms(self._h, int(nv), C.byref(cnt), C.byref(names), C.byref(levels)))
+        return {names[f].decode(): int(levels[f]) for f in range(cnt.value)}
+
+    def close(self):
+        if self._h:
+            lib.po_csr_symbolic_destroy(self._h)
+            self._h = L.po_csr_symbolic()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
 
 
 class SparseCholesky:
@@ -1531,6 +1552,26 @@ def quasidef_apply(problem, x, dinv, c, bx, bw, yx, yw):
     """ParOptQuasiDefMat::apply (:39-56); bw may be None."""
     check(lib.po_quasidef_apply(problem.handle, x.handle, dinv.handle, c.handle, bx.handle,
                                 bw.handle if bw is not None else None, yx.handle, yw.handle))
+
+
+def quasidef_gram(problem, x, dinv, c, P, alpha=None):
+    """The panel steps of the sparse solver, stand-alone, after quasidef_factor (c as that call left it): for the list
+    P of nv PVecs (n) and U_j = Aw (dinv o P_j) returns (W2, out) with W2 = U^T S^-1 U (nv x nv numpy) and, when alpha
+    (nv coefficients) is given, out = -S^-1 (U alpha) as a new PVec (else None).  The sequence is the interior point's
+    Gram correction and correction, through the problem's own solver; nv is not limited."""
+    nv = len(P)
+    handles = (L.po_vec * max(nv, 1))(*[v.handle for v in P])
+    W2 = np.zeros((nv, nv), dtype=np.float64, order="F")
+    out, a = None, None
+    if alpha is not None:
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        if a.shape != (nv,):
+            raise ValueError("quasidef_gram: alpha must have one coefficient per panel vector")
+        out = PVec(c.ctx, len(c))
+    check(lib.po_quasidef_gram(problem.handle, x.handle, dinv.handle, c.handle, handles, nv,
+                               W2.ctypes.data_as(L.c_double_p), a.ctypes.data_as(L.c_double_p) if a is not None else None,
+                               out.handle if out is not None else None))
+    return W2, out
 
 
 def quasidef_factor_info(problem):

@@ -770,8 +770,66 @@ int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, 
   po::vec_decref(work);
   return rc;
 }
+int po_quasidef_gram(po_problem p, po_vec x, po_vec dinv, po_vec c, const po_vec *P, int nv, double *W2,
+                     const double *alpha, po_vec out) {
+  PO_CHECK_PTR(p);
+  PO_CHECK_PTR(x);
+  PO_CHECK_PTR(dinv);
+  PO_CHECK_PTR(c);
+  PO_CHECK_PTR(P);
+  PO_CHECK_PTR(W2);
+  po::Problem *q = p->p;
+  bool ok = nv >= 1 && q->nwcon > 0 && c->n == q->nwcon && dinv->n == q->nlocal && (!alpha || out) &&
+            (!out || out->n == q->nwcon);
+  for (int j = 0; ok && j < nv; j++) ok = P[j] && P[j]->n == q->nlocal;
+  if (!ok) {
+    po::set_error("po_quasidef_gram: the problem has no sparse constraints, nv < 1, or the sizes do not match");
+    return PO_ERR_ARG;
+  }
+  // the vectors InteriorPoint::sparseGramCorrection keeps as members: the panel image, the solved panel where the form
+  // asks for one, n-sized scratch
+  const po::GramForm form = q->sparseGramForm();
+  std::vector<po::Vec *> owned;
+  auto fresh = [&](int64_t len) -> po::Vec * {
+    po::Vec *v = po::vec_new(q->ctx, len);
+    if (v) owned.push_back(v);
+    return v;
+  };
+  std::vector<const double *> Pc((size_t)nv);
+  std::vector<double *> U((size_t)nv), Y;
+  int rc = PO_OK;
+  for (int j = 0; j < nv && rc == PO_OK; j++) {
+    Pc[j] = P[j]->d;
+    po::Vec *u = fresh(q->nwcon), *y = form.solved ? fresh(q->nwcon) : nullptr;
+    if (!u || (form.solved && !y)) rc = PO_ERR_HIP;
+    U[j] = u ? u->d : nullptr;
+    if (form.solved) Y.push_back(y ? y->d : nullptr);
+  }
+  po::Vec *work = rc == PO_OK ? fresh(q->nlocal) : nullptr;
+  if (rc == PO_OK && !work) rc = PO_ERR_HIP;
+  std::vector<double> raw((size_t)nv * nv, 0.0);
+  bool cross = false;
+  if (rc == PO_OK) {
+    rc = q->sparseGramProduct(x, dinv, Pc.data(), nv, U.data(), Y.data(), c, work, false, false, raw.data(), &cross);
+  }
+  if (rc == PO_OK && alpha) {
+    std::vector<const double *> Cp((size_t)nv);
+    for (int j = 0; j < nv; j++) Cp[j] = form.solved ? Y[j] : U[j];
+    rc = q->sparseCorrection(Cp.data(), nv, alpha, c, out);
+  }
+  if (rc == PO_OK && hipStreamSynchronize(q->ctx->stream) != hipSuccess) rc = PO_ERR_HIP;
+  for (int j = 0; rc == PO_OK && j < nv; j++) {
+    for (int i = 0; i < nv; i++) {
+      const double a = raw[i + (size_t)nv * j], b = raw[j + (size_t)nv * i];
+      W2[i + (size_t)nv * j] = cross ? -0.5 * (a + b) : a;  // (U^T Yw = -U^T S^-1 U: the interior point ADDS its average)
+    }
+  }
+  for (po::Vec *v : owned) po::vec_decref(v);
+  return rc;
+}
 struct po_csr_symbolic_s {
   po::CsrSymbolic s;
+  int form_counts[po::CF_COUNT];
 };
 int po_csr_symbolic_create(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, po_csr_symbolic *out) {
   return po_csr_symbolic_create_split(nvars, nwcon, rowp, cols, 0, out);
@@ -821,6 +879,22 @@ int po_csr_symbolic_arrays(po_csr_symbolic h, const int **perm, const int **pare
   if (Lcols) *Lcols = h->s.Lcols.data();
   if (level_ptr) *level_ptr = h->s.fwd_ptr.data();
   if (front_of) *front_of = h->s.front_of.data();
+  return PO_OK;
+}
+int po_csr_symbolic_kernel_forms(po_csr_symbolic h, int nv, int *count, const char *const **names,
+                                 const int **levels) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(count);
+  if (nv < 1) {
+    po::set_error("po_csr_symbolic_kernel_forms: nv must be at least 1");
+    return PO_ERR_ARG;
+  }
+  static const char *form_names[po::CF_COUNT];
+  for (int f = 0; f < po::CF_COUNT; f++) form_names[f] = po::csr_form_name(f);
+  po::csr_kernel_forms(h->s, nv, h->form_counts);
+  *count = po::CF_COUNT;
+  if (names) *names = form_names;
+  if (levels) *levels = h->form_counts;
   return PO_OK;
 }
 int po_csr_symbolic_destroy(po_csr_symbolic h) {

@@ -881,9 +881,89 @@ int CsrSparse::panelNatural(const double *d, const double *const *P, int nv, dou
   return k_csr_panel(ctx, d_rowp, d_cols, vals, w, d, P, nv, U, nullptr);
 }
 
+// ---- kernel forms (csr.hpp): every threshold that picks a kernel lives in the functions below ----------------------
+static const char *const kFormNames[CF_COUNT] = {
+    "level:thin",        "level:table",       "level:search",      "front_rows:table", "front_rows:wide",
+    "front_rows:search", "front_syrk:table",  "front_syrk:search", "front_dense:lds",  "front_dense:global",
+    "trsv_fwd:thin",     "trsv_fwd:wave",     "trsv_fwd:wave_split", "trsv_bwd:thin",  "trsv_bwd:wave",
+    "trsv_bwd:wave_split"};
+const char *csr_form_name(int form) { return form >= 0 && form < CF_COUNT ? kFormNames[form] : nullptr; }
+
 // one thread per row when the rows of a level are short, or when there are so many that even long rows keep
 // every lane busy; a wavefront per row otherwise
-static int thinLevel(int maxlen, int64_t work_items) { return maxlen <= 24 || (work_items >= 65536 && maxlen <= 96); }
+static bool thinLevel(int maxlen, int64_t work_items) { return maxlen <= 24 || (work_items >= 65536 && maxlen <= 96); }
+
+// Capacity of the LDS hash table (csr.hip: RowTable) for rows of at most maxlen entries: a power of two of at least
+// twice the row, at most 4096 slots (16 KB of keys + 32 KB of values).  0: the rows are too long, use the search kernels.
+static int table_cap(int maxlen) {
+  constexpr int kMaxTable = 4096;
+  int cap = 64;
+  while (cap < 2 * maxlen) cap <<= 1;
+  return cap <= kMaxTable ? cap : 0;
+}
+
+// a wavefront per (row, right-hand side): with few rows in the level the right-hand sides of a row are spread over
+// gridDim.y workgroups of four wavefronts, with many rows one workgroup walks through all of them
+static int waveGridY(int nrows, int nv) { return nv > 4 ? (nrows < 1024 ? (nv + 3) / 4 : 1) : 1; }
+
+CsrLevelPlan csr_level_plan(const CsrSymbolic &s, int l, int nv) {
+  CsrLevelPlan p;
+  const int nord = s.ord_end[l] - s.fwd_ptr[l];
+  p.trsv_waves = nv > 1 ? 4 : 1;
+  if (nord > 0) {
+    if (thinLevel(s.fwd_maxlen[l], nord)) {
+      p.level = CF_LEVEL_THIN;
+    } else {
+      p.level_tcap = table_cap(s.fwd_maxlen[l]);
+      p.level = p.level_tcap > 0 ? CF_LEVEL_TABLE : CF_LEVEL_SEARCH;
+    }
+    if (thinLevel(s.fwd_maxlen[l], (int64_t)nord * nv)) {
+      p.trsv_fwd = CF_TRSV_FWD_THIN;
+    } else {
+      p.fwd_gy = waveGridY(nord, nv);
+      p.trsv_fwd = p.fwd_gy > 1 ? CF_TRSV_FWD_WAVE_SPLIT : CF_TRSV_FWD_WAVE;
+    }
+    if (thinLevel(s.bwd_maxlen[l], (int64_t)nord * nv)) {
+      p.trsv_bwd = CF_TRSV_BWD_THIN;
+    } else {
+      p.bwd_gy = waveGridY(nord, nv);
+      p.trsv_bwd = p.bwd_gy > 1 ? CF_TRSV_BWD_WAVE_SPLIT : CF_TRSV_BWD_WAVE;
+    }
+  }
+  if (s.front_ptr[l + 1] > s.front_ptr[l]) {
+    const int maxdesc = s.front_maxdesc[l];
+    p.front_tcap = table_cap(maxdesc);
+    if (p.front_tcap > 0) {
+      // long front rows (the top separators): eight wavefronts share each row
+      p.front_rows = maxdesc >= 256 ? CF_FRONT_ROWS_WIDE : CF_FRONT_ROWS_TABLE;
+      p.front_syrk = CF_FRONT_SYRK_TABLE;
+    } else {
+      p.front_rows = CF_FRONT_ROWS_SEARCH;
+      p.front_syrk = CF_FRONT_SYRK_SEARCH;
+    }
+    for (int f = s.front_ptr[l]; f < s.front_ptr[l + 1]; f++) {
+      (front_in_lds(s.front_size[f]) ? p.front_dense_lds : p.front_dense_global) = true;
+    }
+  }
+  return p;
+}
+
+void csr_kernel_forms(const CsrSymbolic &s, int nv, int counts[CF_COUNT]) {
+  for (int f = 0; f < CF_COUNT; f++) counts[f] = 0;
+  const int nlev = (int)s.fwd_ptr.size() - 1;
+  for (int l = 0; l < nlev; l++) {
+    bool used[CF_COUNT] = {false};
+    for (int j0 = 0; j0 < nv; j0 += csr_slab(nv - j0)) {
+      const CsrLevelPlan p = csr_level_plan(s, l, csr_slab(nv - j0));
+      for (int f : {p.level, p.front_rows, p.front_syrk, p.trsv_fwd, p.trsv_bwd}) {
+        if (f >= 0) used[f] = true;
+      }
+      if (p.front_dense_lds) used[CF_FRONT_DENSE_LDS] = true;
+      if (p.front_dense_global) used[CF_FRONT_DENSE_GLOBAL] = true;
+    }
+    for (int f = 0; f < CF_COUNT; f++) counts[f] += used[f] ? 1 : 0;
+  }
+}
 
 int CsrSparse::factor(const double *dinv, const double *cdiag) {
   if (w <= 0) return PO_OK;
@@ -894,10 +974,10 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
   for (int l = 0; l < nlevels_f; l++) {
     const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
     const int oe = sym.ord_end[l], f0 = sym.front_ptr[l], nf = sym.front_ptr[l + 1] - f0;
-    PO_TRY(k_chol_level(ctx, d_Lrowp, d_Lcols, Lvals, d_fwd + b, oe - b, d_flag,
-                        thinLevel(sym.fwd_maxlen[l], oe - b), sym.fwd_maxlen[l]));
+    const CsrLevelPlan plan = csr_level_plan(sym, l, 1);
+    PO_TRY(k_chol_level(ctx, d_Lrowp, d_Lcols, Lvals, d_fwd + b, oe - b, d_flag, plan));
     PO_TRY(k_chol_fronts(ctx, d_Lrowp, d_Lcols, Lvals, oe, e - oe, d_front_of, d_fstart + f0, d_fsize + f0, nf,
-                         sym.front_maxdesc[l], d_flag));
+                         plan, d_flag));
   }
   if (const int r = ndense()) {
     // Yv = L^-1 P V, T = Yv^T Yv, K = E^-1 + T = Lk Lk^T: all queued ahead of the one flag read below
@@ -949,9 +1029,8 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
 }
 
 int CsrSparse::solveInPlace(double *const *Y, int nv, bool forward, bool backward) {
-  if (nv > kMaxPanel) {  // independent right-hand sides: slabs of one kernel's pointer table
-    for (int j0 = 0; j0 < nv; j0 += kMaxPanel)
-      PO_TRY(solveInPlace(Y + j0, nv - j0 > kMaxPanel ? kMaxPanel : nv - j0, forward, backward));
+  if (csr_slab(nv) < nv) {  // independent right-hand sides: slabs of one kernel's pointer table
+    for (int j0 = 0; j0 < nv; j0 += csr_slab(nv - j0)) PO_TRY(solveInPlace(Y + j0, csr_slab(nv - j0), forward, backward));
     return PO_OK;
   }
   if (w <= 0 || nv <= 0) return PO_OK;
@@ -959,20 +1038,20 @@ int CsrSparse::solveInPlace(double *const *Y, int nv, bool forward, bool backwar
     for (int l = 0; l < nlevels_f; l++) {
       const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
       const int oe = sym.ord_end[l], f0 = sym.front_ptr[l], nf = sym.front_ptr[l + 1] - f0;
-      PO_TRY(k_trsv_fwd_level(ctx, d_Lrowp, d_Lcols, Lvals, d_fwd + b, oe - b, Y, nv,
-                              thinLevel(sym.fwd_maxlen[l], (int64_t)(oe - b) * nv)));
+      const CsrLevelPlan plan = csr_level_plan(sym, l, nv);
+      PO_TRY(k_trsv_fwd_level(ctx, d_Lrowp, d_Lcols, Lvals, d_fwd + b, oe - b, Y, nv, plan));
       PO_TRY(k_trsv_fronts_fwd(ctx, d_Lrowp, d_Lcols, Lvals, oe, e - oe, d_front_of, d_fstart + f0, d_fsize + f0,
-                               nf, Y, nv));
+                               nf, Y, nv, plan));
     }
   }
   if (backward) {
     for (int l = nlevels_f - 1; l >= 0; l--) {
       const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
       const int oe = sym.ord_end[l], f0 = sym.front_ptr[l], nf = sym.front_ptr[l + 1] - f0;
+      const CsrLevelPlan plan = csr_level_plan(sym, l, nv);
       PO_TRY(k_trsv_fronts_bwd(ctx, d_Lrowp, d_Ltp, d_Ltrows, d_Ltsrc, Lvals, oe, e - oe, d_front_of, d_front_end,
-                               d_fstart + f0, d_fsize + f0, nf, Y, nv));
-      PO_TRY(k_trsv_bwd_level(ctx, d_Lrowp, d_Ltp, d_Ltrows, d_Ltsrc, Lvals, d_fwd + b, oe - b, Y, nv,
-                              thinLevel(sym.bwd_maxlen[l], (int64_t)(oe - b) * nv)));
+                               d_fstart + f0, d_fsize + f0, nf, Y, nv, plan));
+      PO_TRY(k_trsv_bwd_level(ctx, d_Lrowp, d_Ltp, d_Ltrows, d_Ltsrc, Lvals, d_fwd + b, oe - b, Y, nv, plan));
     }
   }
   return PO_OK;
@@ -1008,9 +1087,8 @@ int CsrSparse::applyK0(const double *dinv, const double *bx, const double *bw, d
 
 int CsrSparse::solvePanel(const double *const *U, int nv, double *const *Yw) {
   if (w <= 0 || nv <= 0) return PO_OK;
-  if (nv > kMaxPanel) {  // independent columns: slabs of one kernel's pointer table
-    for (int j0 = 0; j0 < nv; j0 += kMaxPanel)
-      PO_TRY(solvePanel(U + j0, nv - j0 > kMaxPanel ? kMaxPanel : nv - j0, Yw + j0));
+  if (csr_slab(nv) < nv) {  // independent columns: slabs of one kernel's pointer table
+    for (int j0 = 0; j0 < nv; j0 += csr_slab(nv - j0)) PO_TRY(solvePanel(U + j0, csr_slab(nv - j0), Yw + j0));
     return PO_OK;
   }
   const int64_t ld = (w + 3) / 4 * 4 + 4;

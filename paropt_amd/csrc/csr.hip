@@ -193,9 +193,9 @@ __global__ void __launch_bounds__(kBlock)
 int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, int64_t w, const double *d,
                 const double *const *P, int nv, double *const *U, const int *outperm) {
   if (w <= 0 || nv <= 0) return PO_OK;
-  if (nv > kMaxPanel) {  // independent columns: slabs of one kernel's pointer table
-    for (int j0 = 0; j0 < nv; j0 += kMaxPanel)
-      PO_TRY(k_csr_panel(c, rowp, cols, vals, w, d, P + j0, nv - j0 > kMaxPanel ? kMaxPanel : nv - j0, U + j0, outperm));
+  if (csr_slab(nv) < nv) {  // independent columns: slabs of one kernel's pointer table
+    for (int j0 = 0; j0 < nv; j0 += csr_slab(nv - j0))
+      PO_TRY(k_csr_panel(c, rowp, cols, vals, w, d, P + j0, csr_slab(nv - j0), U + j0, outperm));
     return PO_OK;
   }
   PtrTable pt;
@@ -375,13 +375,6 @@ __device__ __forceinline__ RowTable row_table(int *lds, int tcap) {
   t.mask = tcap - 1;
   return t;
 }
-constexpr int kMaxTable = 4096;  // 16 KB of keys + 32 KB of values
-static int table_cap(int maxlen) {  // 0: the rows are too long, use the search kernels
-  int cap = 64;
-  while (cap < 2 * maxlen) cap <<= 1;
-  return cap <= kMaxTable ? cap : 0;
-}
-
 // Row Cholesky of one dependency level: one wavefront per row i, entries left to right,
 //   L_ij = (S_ij - sum_{k<j} L_ik L_jk) / L_jj,   L_ii = sqrt(S_ii - sum_k L_ik^2).
 // Row j (j < i) was finished by an earlier launch; the lanes stride over row j and look each column up in the
@@ -520,13 +513,13 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 int k_chol_level(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, const int *rows, int nrows,
-                 int *flag, int thin, int maxlen) {
+                 int *flag, const CsrLevelPlan &plan) {
   if (nrows <= 0) return PO_OK;
-  if (thin) {
+  if (plan.level == CF_LEVEL_THIN) {
     PO_CLAUNCH(chol_level_thin_kernel, cgrid(c, nrows), kBlock, Lrowp, Lcols, Lvals, rows, nrows, flag);
   } else {
-    const int tcap = table_cap(maxlen);
-    if (tcap > 0) {
+    const int tcap = plan.level_tcap;
+    if (plan.level == CF_LEVEL_TABLE) {
       hipLaunchKernelGGL(chol_level_kernel<1>, dim3(nrows), dim3(64), (size_t)tcap * 12, c->stream, Lrowp, Lcols,
                          Lvals, rows, nrows, flag, tcap);
     } else {
@@ -726,7 +719,6 @@ __global__ void __launch_bounds__(kBlock)
 // Step 3: dense right-looking Cholesky of the triangle, one workgroup of 1024 per front.  Per column: the
 // scaled column goes to LDS (and back to L), then the trailing triangle is updated from LDS - two barriers.
 constexpr int kFrontThreads = 1024;
-constexpr int kFrontLds = 2048;  // fronts up to this many rows keep their row offsets and the column in LDS
 #define PO_T(r, q) Lvals[Lrowp[f0 + (r) + 1] - 1 - (r) + (q)]
 __global__ void __launch_bounds__(kFrontThreads)
     chol_front_dense_kernel(const int *__restrict__ Lrowp, double *Lvals, const int *__restrict__ fstart,
@@ -735,7 +727,7 @@ __global__ void __launch_bounds__(kFrontThreads)
   __shared__ double colk[kFrontLds];
   const int f0 = fstart[blockIdx.x], s = fsize[blockIdx.x];
   const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-  if (s <= kFrontLds) {
+  if (front_in_lds(s)) {
     for (int r = tid; r < s; r += kFrontThreads) tb[r] = Lrowp[f0 + r + 1] - 1 - r;
     __syncthreads();
     for (int k = 0; k < s; k++) {
@@ -790,13 +782,14 @@ __global__ void __launch_bounds__(kFrontThreads)
   }
 }
 int k_chol_fronts(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, int row0, int nrows,
-                  const int *front_of, const int *fstart, const int *fsize, int nfronts, int maxdesc, int *flag) {
+                  const int *front_of, const int *fstart, const int *fsize, int nfronts, const CsrLevelPlan &plan,
+                  int *flag) {
   if (nrows <= 0 || nfronts <= 0) return PO_OK;
-  const int tcap = table_cap(maxdesc);
-  if (tcap > 0 && maxdesc >= 256) {
+  const int tcap = plan.front_tcap;
+  if (plan.front_rows == CF_FRONT_ROWS_WIDE) {
     hipLaunchKernelGGL(chol_front_rows_wide_kernel<8>, dim3(nrows), dim3(512), (size_t)tcap * 12, c->stream, Lrowp,
                        Lcols, Lvals, row0, front_of, tcap);
-  } else if (tcap > 0) {
+  } else if (plan.front_rows == CF_FRONT_ROWS_TABLE) {
     hipLaunchKernelGGL(chol_front_rows_kernel<1>, dim3(nrows), dim3(64), (size_t)tcap * 12, c->stream, Lrowp, Lcols,
                        Lvals, row0, front_of, tcap);
   } else {
@@ -805,7 +798,7 @@ int k_chol_fronts(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, int
   }
   c->n_launches++;
   PO_HIP(hipGetLastError());
-  if (tcap > 0) {
+  if (plan.front_syrk == CF_FRONT_SYRK_TABLE) {
     hipLaunchKernelGGL(chol_front_syrk_kernel<1>, dim3(nrows), dim3(kBlock), (size_t)tcap * 12, c->stream, Lrowp,
                        Lcols, Lvals, row0, front_of, tcap);
   } else {
@@ -899,21 +892,22 @@ __global__ void __launch_bounds__(kFrontThreads)
 static int fill_table(PtrTableW &t, double *const *Y, int nv);
 int k_trsv_fronts_fwd(Ctx *c, const int *Lrowp, const int *Lcols, const double *Lvals, int row0, int nrows,
                       const int *front_of, const int *fstart, const int *fsize, int nfronts, double *const *Y,
-                      int nv) {
+                      int nv, const CsrLevelPlan &plan) {
   if (nrows <= 0 || nfronts <= 0 || nv <= 0) return PO_OK;
   PtrTableW t;
   PO_TRY(fill_table(t, Y, nv));
-  PO_CLAUNCH(trsv_front_fwd_rows_kernel, nrows, nv > 1 ? kBlock : 64, Lrowp, Lcols, Lvals, row0, front_of, t, nv);
+  PO_CLAUNCH(trsv_front_fwd_rows_kernel, nrows, 64 * plan.trsv_waves, Lrowp, Lcols, Lvals, row0, front_of, t, nv);
   PO_CLAUNCH(trsv_front_fwd_dense_kernel, nfronts, kFrontThreads, Lrowp, Lvals, fstart, fsize, t, nv);
   return PO_OK;
 }
 int k_trsv_fronts_bwd(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows, const int *Ltsrc,
                       const double *Lvals, int row0, int nrows, const int *front_of, const int *front_end,
-                      const int *fstart, const int *fsize, int nfronts, double *const *Y, int nv) {
+                      const int *fstart, const int *fsize, int nfronts, double *const *Y, int nv,
+                      const CsrLevelPlan &plan) {
   if (nrows <= 0 || nfronts <= 0 || nv <= 0) return PO_OK;
   PtrTableW t;
   PO_TRY(fill_table(t, Y, nv));
-  PO_CLAUNCH(trsv_front_bwd_cols_kernel, nrows, nv > 1 ? kBlock : 64, Ltp, Ltrows, Ltsrc, Lvals, row0, front_of,
+  PO_CLAUNCH(trsv_front_bwd_cols_kernel, nrows, 64 * plan.trsv_waves, Ltp, Ltrows, Ltsrc, Lvals, row0, front_of,
              front_end, t, nv);
   PO_CLAUNCH(trsv_front_bwd_dense_kernel, nfronts, kFrontThreads, Lrowp, Lvals, fstart, fsize, t, nv);
   return PO_OK;
@@ -992,33 +986,32 @@ static int fill_table(PtrTableW &t, double *const *Y, int nv) {
   return PO_OK;
 }
 int k_trsv_fwd_level(Ctx *c, const int *Lrowp, const int *Lcols, const double *Lvals, const int *rows, int nrows,
-                     double *const *Y, int nv, int thin) {
+                     double *const *Y, int nv, const CsrLevelPlan &plan) {
   if (nrows <= 0 || nv <= 0) return PO_OK;
   PtrTableW t;
   PO_TRY(fill_table(t, Y, nv));
-  if (thin) {
+  if (plan.trsv_fwd == CF_TRSV_FWD_THIN) {
     PO_CLAUNCH(trsv_fwd_thin_kernel, cgrid(c, (int64_t)nrows * nv), kBlock, Lrowp, Lcols, Lvals, rows, nrows, t, nv);
     return PO_OK;
   }
-  const int gy = nv > 4 ? (nrows < 1024 ? (nv + 3) / 4 : 1) : 1;
-  hipLaunchKernelGGL(trsv_fwd_kernel, dim3(nrows, gy), dim3(nv > 1 ? kBlock : 64), 0, c->stream, Lrowp, Lcols,
+  hipLaunchKernelGGL(trsv_fwd_kernel, dim3(nrows, plan.fwd_gy), dim3(64 * plan.trsv_waves), 0, c->stream, Lrowp, Lcols,
                      Lvals, rows, nrows, t, nv);
   c->n_launches++;
   PO_HIP(hipGetLastError());
   return PO_OK;
 }
 int k_trsv_bwd_level(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows, const int *Ltsrc,
-                     const double *Lvals, const int *rows, int nrows, double *const *Y, int nv, int thin) {
+                     const double *Lvals, const int *rows, int nrows, double *const *Y, int nv,
+                     const CsrLevelPlan &plan) {
   if (nrows <= 0 || nv <= 0) return PO_OK;
   PtrTableW t;
   PO_TRY(fill_table(t, Y, nv));
-  if (thin) {
+  if (plan.trsv_bwd == CF_TRSV_BWD_THIN) {
     PO_CLAUNCH(trsv_bwd_thin_kernel, cgrid(c, (int64_t)nrows * nv), kBlock, Lrowp, Ltp, Ltrows, Ltsrc, Lvals, rows,
                nrows, t, nv);
     return PO_OK;
   }
-  const int gy = nv > 4 ? (nrows < 1024 ? (nv + 3) / 4 : 1) : 1;
-  hipLaunchKernelGGL(trsv_bwd_kernel, dim3(nrows, gy), dim3(nv > 1 ? kBlock : 64), 0, c->stream, Lrowp, Ltp,
+  hipLaunchKernelGGL(trsv_bwd_kernel, dim3(nrows, plan.bwd_gy), dim3(64 * plan.trsv_waves), 0, c->stream, Lrowp, Ltp,
                      Ltrows, Ltsrc, Lvals, rows, nrows, t, nv);
   c->n_launches++;
   PO_HIP(hipGetLastError());

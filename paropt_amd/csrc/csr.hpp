@@ -79,6 +79,54 @@ void sym_etree(const std::vector<int> &adjp, const std::vector<int> &adj, const 
 void sym_colcount(const std::vector<int> &adjp, const std::vector<int> &adj, const std::vector<int> &perm,
                   const std::vector<int> &iperm, const std::vector<int> &parent, std::vector<int> *colcount);
 
+// KERNEL FORMS.  Every elimination level of the factorization and of the two triangular sweeps is launched in one of
+// several forms; csr_level_plan() is the one place that chooses among them, from the analysis alone.  CsrSparse::factor
+// and solveInPlace launch what it returns, and po_csr_symbolic_kernel_forms reports it without a device.
+enum CsrForm {
+  CF_LEVEL_THIN = 0,      // chol_level_thin_kernel: one thread per ordinary row
+  CF_LEVEL_TABLE,         // chol_level_kernel<1>: one wavefront per row, lookups in the LDS hash table
+  CF_LEVEL_SEARCH,        // chol_level_kernel<0>: the row is too long for the table, binary search
+  CF_FRONT_ROWS_TABLE,    // chol_front_rows_kernel<1>
+  CF_FRONT_ROWS_WIDE,     // chol_front_rows_wide_kernel<8>: eight wavefronts share a long front row
+  CF_FRONT_ROWS_SEARCH,   // chol_front_rows_kernel<0>
+  CF_FRONT_SYRK_TABLE,    // chol_front_syrk_kernel<1>
+  CF_FRONT_SYRK_SEARCH,   // chol_front_syrk_kernel<0>
+  CF_FRONT_DENSE_LDS,     // chol_front_dense_kernel on a front whose column fits LDS
+  CF_FRONT_DENSE_GLOBAL,  // ... on a larger front, through global memory
+  CF_TRSV_FWD_THIN,       // trsv_fwd_thin_kernel: one thread per (row, right-hand side)
+  CF_TRSV_FWD_WAVE,       // trsv_fwd_kernel: one wavefront per (row, right-hand side), one workgroup per row
+  CF_TRSV_FWD_WAVE_SPLIT, // ... the right-hand sides of a row split over gridDim.y workgroups
+  CF_TRSV_BWD_THIN,
+  CF_TRSV_BWD_WAVE,
+  CF_TRSV_BWD_WAVE_SPLIT,
+  CF_COUNT
+};
+const char *csr_form_name(int form);  // "level:thin", ... (null past CF_COUNT)
+
+// fronts up to this many rows keep their row offsets and the current column in LDS (chol_front_dense_kernel)
+constexpr int kFrontLds = 2048;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool front_in_lds(int rows) { return rows <= kFrontLds; }
+
+// right-hand sides of the next launch when nv_left remain: one kernel's pointer table holds kMaxPanel
+inline int csr_slab(int nv_left) { return nv_left > kMaxPanel ? kMaxPanel : nv_left; }
+
+// What one level launches for a panel of nv <= kMaxPanel right-hand sides (the factorization ignores nv).  A form of
+// -1: nothing of that kind in the level.
+struct CsrLevelPlan {
+  int level = -1, level_tcap = 0;                         // ordinary rows; capacity of the LDS table (0: none)
+  int front_rows = -1, front_syrk = -1, front_tcap = 0;   // the part of the front rows left of their fronts
+  bool front_dense_lds = false, front_dense_global = false;  // the kernel chooses per front: which sizes occur
+  int trsv_fwd = -1, trsv_bwd = -1;                       // ordinary rows of the two sweeps
+  int fwd_gy = 1, bwd_gy = 1;                             // gridDim.y of the wave forms
+  int trsv_waves = 1;                                     // wavefronts per workgroup of the wave and front-row solves
+};
+CsrLevelPlan csr_level_plan(const CsrSymbolic &s, int level, int nv);
+// counts[f] = number of levels that launch form f for a panel of nv right-hand sides (nv > kMaxPanel: in any slab)
+void csr_kernel_forms(const CsrSymbolic &s, int nv, int counts[CF_COUNT]);
+
 class CsrSparse {
  public:
   CsrSparse(Ctx *c, int64_t n_, int64_t w_);
@@ -171,20 +219,24 @@ int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, in
 int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
                    const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
                    double *Lvals, const unsigned char *skip = nullptr);
+// (the forms, table capacities and grid shapes below are what csr_level_plan chose: the launchers decide nothing)
 int k_chol_level(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, const int *rows, int nrows, int *flag,
-                 int thin, int maxlen);
+                 const CsrLevelPlan &plan);
 int k_chol_fronts(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, int row0, int nrows,
-                  const int *front_of, const int *fstart, const int *fsize, int nfronts, int maxdesc, int *flag);
+                  const int *front_of, const int *fstart, const int *fsize, int nfronts, const CsrLevelPlan &plan,
+                  int *flag);
 int k_trsv_fronts_fwd(Ctx *c, const int *Lrowp, const int *Lcols, const double *Lvals, int row0, int nrows,
                       const int *front_of, const int *fstart, const int *fsize, int nfronts, double *const *Y,
-                      int nv);
+                      int nv, const CsrLevelPlan &plan);
 int k_trsv_fronts_bwd(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows, const int *Ltsrc,
                       const double *Lvals, int row0, int nrows, const int *front_of, const int *front_end,
-                      const int *fstart, const int *fsize, int nfronts, double *const *Y, int nv);
+                      const int *fstart, const int *fsize, int nfronts, double *const *Y, int nv,
+                      const CsrLevelPlan &plan);
 int k_trsv_fwd_level(Ctx *c, const int *Lrowp, const int *Lcols, const double *Lvals, const int *rows, int nrows,
-                     double *const *Y, int nv, int thin);
+                     double *const *Y, int nv, const CsrLevelPlan &plan);
 int k_trsv_bwd_level(Ctx *c, const int *Lrowp, const int *Ltp, const int *Ltrows, const int *Ltsrc,
-                     const double *Lvals, const int *rows, int nrows, double *const *Y, int nv, int thin);
+                     const double *Lvals, const int *rows, int nrows, double *const *Y, int nv,
+                     const CsrLevelPlan &plan);
 // dense columns (csr.hip): scatter of V, the two-stage panel product and its consumers, the low-rank update
 int k_dense_scatter(Ctx *c, const int *ptr, const int *pos, const int *slot, const double *vals, int r, int maxlen,
                     int64_t ld, double *V);

@@ -125,8 +125,6 @@ int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, in
   if (m <= 0) return PO_OK;
   std::vector<double *> U;
   PO_TRY(panelImageVectors(m, U));
-  std::vector<const double *> Uc(U.begin(), U.end());
-  if (!panel_done) PO_TRY(prob->sparseJacobianPanel(x, Dinv, P.data(), m, U.data(), work ? work : tvec));
   // What the problem's solver makes of the panel (quasidef.hpp): a half solve in place -- scalar forms: nothing, the
   // weights are Cw; packed blocks and CSR: U <- L^-1 U with S = L L^T, unit weights -- or, where the user exposes no
   // factor, a second panel Yw_j = -S^-1 U_j from one three-argument apply per column (the reference makes c for G,
@@ -139,26 +137,25 @@ int InteriorPoint::sparseGramCorrection(const std::vector<const double *> &P, in
     Yw.push_back(y);
   }
   for (int j = 0; form.solved && j < m; j++) Y.push_back(Yw[j]->d);
-  const double *weights = nullptr;
-  PO_TRY(prob->sparseGramSolve(P.data(), m, U.data(), Y.data(), Cw, work ? work : tvec, &weights));
+  if (form.solved && kkt.W.size() != (size_t)m * m) {
+    // (the caller sized W for this panel: a Schur-complement term is never dropped)
+    set_error("internal: the Gram matrix holds %zu entries for a panel of %d columns", kkt.W.size(), m);
+    return PO_ERR_ARG;
+  }
   W2_buf.assign((size_t)m * m, 0.0);
-  if (!weights) {
+  // panel, gramSolve and the w-sized product (Problem::sparseGramProduct, shared with po_quasidef_gram).  may_defer:
+  // inside setUpKKTSystem's batch the product arrives at the flush: a member holds it, the update of W follows it there
+  bool cross = false;
+  PO_TRY(prob->sparseGramProduct(x, Dinv, P.data(), m, U.data(), Y.data(), Cw, work ? work : tvec, panel_done, may_defer,
+                                 W2_buf.data(), &cross));
+  if (cross) {
     // the cross product W += U^T Yw of two different w-sized panels, symmetric up to rounding: both halves are averaged
-    if (kkt.W.size() != (size_t)m * m) {  // (the caller sized W for this panel: a Schur-complement term is never dropped)
-      set_error("internal: the Gram matrix holds %zu entries for a panel of %d columns", kkt.W.size(), m);
-      return PO_ERR_ARG;
-    }
-    std::vector<const double *> Yc(Y.begin(), Y.end());
-    PO_TRY(k_xgram(ctx, Uc.data(), Yc.data(), m, nw, W2_buf.data(), may_defer));
     after_reduce(ctx, [this, m] {
       for (int j = 0; j < m; j++)
         for (int i = 0; i < m; i++)
           kkt.W[i + (size_t)m * j] += 0.5 * (W2_buf[i + (size_t)m * j] + W2_buf[j + (size_t)m * i]);
     });
   } else {
-    // (may_defer: inside setUpKKTSystem's batch the product arrives at the flush: a member holds it, the subtraction
-    // follows it there)
-    PO_TRY(k_wgram(ctx, weights, Uc.data(), m, nw, W2_buf.data(), nullptr, nullptr, 0, 0.0, 0, may_defer));
     after_reduce(ctx, [this] {
       for (size_t i = 0; i < W2_buf.size() && i < kkt.W.size(); i++) kkt.W[i] -= W2_buf[i];
     });

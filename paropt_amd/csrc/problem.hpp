@@ -101,6 +101,13 @@ class Problem {
   int sparseCorrection(const double *const *U, int nv, const double *alpha, Vec *cw, Vec *out, Vec *acc = nullptr) {
     return sparseSolver()->correction(U, nv, alpha, cw, out, acc);
   }
+  // The panel steps of the Gram correction W -= U^T S^-1 U in the order the interior point runs them: the panel image
+  // U = Aw (d o P) (panel_done: U already holds it), gramSolve, then the w-sized product the form calls for -- the
+  // weighted Gram U^T diag(weights) U of the half-solved panel (*cross = false: W2 = U^T S^-1 U) or, for a solved panel,
+  // the cross product U^T Yw (*cross = true: W2 = -U^T S^-1 U up to rounding, to be symmetrised by the caller).  W2
+  // (m x m, host) is complete once the context's pending reductions are flushed (may_defer as k_wgram takes it).
+  int sparseGramProduct(Vec *x, Vec *d, const double *const *P, int m, double *const *U, double *const *Yw, Vec *cw,
+                        Vec *work, bool panel_done, bool may_defer, double *W2, bool *cross);
   const char *sparseFactorInfo() { return sparseSolver()->info(); }
   long sparseFactorBreakdowns() { return sparseSolver()->breakdowns(); }
   // po_quasidef_factor: sparseFactor, with a breakdown it met reported as PO_ERR_NUMERIC and the error text set

@@ -173,6 +173,20 @@ int Problem::addSparseInnerProduct(double alpha, Vec *, Vec *cvec, Vec *A) {
   if (!csr) return 0;
   return csr->innerProduct(alpha, cvec->d, A->d) != PO_OK;
 }
+int Problem::sparseGramProduct(Vec *x, Vec *d, const double *const *P, int m, double *const *U, double *const *Yw,
+                               Vec *cw, Vec *work, bool panel_done, bool may_defer, double *W2, bool *cross) {
+  if (!panel_done) PO_TRY(sparseJacobianPanel(x, d, P, m, U, work));
+  const double *weights = nullptr;
+  PO_TRY(sparseGramSolve(P, m, U, Yw, cw, work, &weights));
+  *cross = weights == nullptr;
+  std::vector<const double *> Uc(U, U + m);
+  if (*cross) {
+    std::vector<const double *> Yc(Yw, Yw + m);
+    return k_xgram(ctx, Uc.data(), Yc.data(), m, nwcon, W2, may_defer);
+  }
+  return k_wgram(ctx, weights, Uc.data(), m, nwcon, W2, nullptr, nullptr, 0, 0.0, 0, may_defer);
+}
+
 int Problem::sparsePanelImage(Vec *x, Vec *d, const double *const *P, int nv, double *const *U, Vec *work) {
   if (grouped) return k_group_panel(ctx, gmap, P, nv, d->d, group_alpha, U);
   for (int j = 0; j < nv; j++) {

@@ -260,6 +260,8 @@ SIGNATURES = {
     "po_problem_set_quasidef_callbacks": (C.c_int, [po_problem, C.POINTER(QuasiDefCallbacks)]),
     "po_quasidef_factor": (C.c_int, [po_problem, po_vec, po_vec, po_vec]),
     "po_quasidef_apply": (C.c_int, [po_problem, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec, po_vec]),
+    "po_quasidef_gram": (C.c_int, [po_problem, po_vec, po_vec, po_vec, C.POINTER(po_vec), C.c_int, c_double_p,
+                                   c_double_p, po_vec]),
     "po_quasidef_factor_info": (C.c_char_p, [po_problem]),
     "po_csr_symbolic_create": (C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, C.POINTER(po_csr_symbolic)]),
     "po_csr_symbolic_create_split": (
@@ -270,6 +272,8 @@ SIGNATURES = {
     "po_csr_symbolic_info": (C.c_int, [po_csr_symbolic, c_i64_p]),
     "po_csr_symbolic_arrays": (
         C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
+    "po_csr_symbolic_kernel_forms": (
+        C.c_int, [po_csr_symbolic, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), c_int_pp]),
     "po_csr_symbolic_destroy": (C.c_int, [po_csr_symbolic]),
     "po_sparse_chol_create": (
         C.c_int, [po_ctx, C.c_int64, c_int_p, c_int_p, C.c_int, c_int_p, C.POINTER(po_sparse_chol)]),

@@ -45,6 +45,32 @@ def grid_pattern(nx, ny):
     return np.array(rowp, dtype=np.intc), np.array(cols, dtype=np.intc)
 
 
+def arrow_pattern(k, r):
+    """k rows {i}, then r rows over all k variables (n = k): the last r rows of L are k + 1 .. k + r long, and for
+    r >= 16 they form one front whose rows have k entries left of it."""
+    rowp = np.concatenate([np.arange(k + 1), k + k * np.arange(1, r + 1)]).astype(np.intc)
+    cols = np.concatenate([np.arange(k)] + [np.arange(k)] * r).astype(np.intc)
+    return rowp, cols
+
+
+def shared_pattern(w):
+    """Row i is {0, i + 1} (n = w + 1): every pair of rows shares variable 0, S is dense and L one front of w rows."""
+    rowp = (2 * np.arange(w + 1)).astype(np.intc)
+    cols = np.zeros(2 * w, dtype=np.intc)
+    cols[1::2] = np.arange(1, w + 1)
+    return rowp, cols
+
+
+def arrow_blocks_pattern(nb, k):
+    """nb independent copies of arrow_pattern(k, 1) (n = nb k): block b is the rows b (k + 1) .. b (k + 1) + k over
+    the variables b k .. b k + k - 1."""
+    rp, cl = arrow_pattern(k, 1)
+    rowp = (np.arange(nb)[:, None] * int(rp[-1]) + rp[None, :-1]).ravel()
+    rowp = np.append(rowp, nb * int(rp[-1])).astype(np.intc)
+    cols = (np.arange(nb)[:, None] * k + cl[None, :]).ravel().astype(np.intc)
+    return rowp, cols
+
+
 def dense_jacobian(n, rowp, cols, data):
     w = len(rowp) - 1
     A = np.zeros((w, n))

@@ -440,8 +440,10 @@ def test_interior_point_on_grid_pattern_with_fronts(ctx):
 
 def test_quasidef_solve_random_soak(ctx):
     """Thirty random patterns (row lengths, locality, grids with random extra rows) against dense solves: guards
-    the corner cases of the scheduler (levels without ordinary rows, fronts next to thin rows, table capacity at
-    its limits, empty rows)."""
+    the corner cases of the scheduler (levels without ordinary rows, fronts next to thin rows, empty rows).  It does
+    NOT reach the limits of the LDS row table: w stays below 300 here, so the largest table is a fraction of the 2048
+    entries a row may have and no search kernel runs.  Those limits, the wide front-row kernel and the large-front
+    path are the subject of tests/test_gpu_csr_forms.py."""
     import paropt_amd as pa
 
     rng = np.random.default_rng(2024)
