@@ -4,10 +4,12 @@
 // example: f = sum (1-x_i)^2 + 100 (x_{i+1}-x_i^2)^2, c0 = 0.25 - sum x^2 >= 0, c1 = 10 + sum_{i even} x_i
 // >= 0, and nvars-1 overlapping sparse constraints cw_i = 1 - x_i^2 - x_{i+1}^2 >= 0; -2 <= x <= 1, x0 = -1.
 // The Schur complement of the sparse block is tridiagonal here; it is assembled, factored (nested-dissection
-// ordered, level-scheduled sparse Cholesky) and solved on the GPU.
+// ordered, level-scheduled sparse Cholesky) and solved on the GPU.  factor=multifrontal chooses the multifrontal engine
+// of ParOptSparseCholesky for that factor instead (ParOptSparseProblem::setSparseFactor); the factor line it prints
+// then names supernodes.
 //
 // build: g++ -std=c++17 -Iinclude examples/sparse_rosenbrock_amd.cpp -Lparopt_amd -lparopt_amd
-//        -Wl,-rpath,$PWD/paropt_amd -o examples/sparse_rosenbrock_amd ; run: ./examples/sparse_rosenbrock_amd nvars=100
+//        -Wl,-rpath,$PWD/paropt_amd -o examples/sparse_rosenbrock_amd ; run: ./examples/sparse_rosenbrock_amd nvars=100 [factor=multifrontal]
 #include <stdlib.h>
 #include <string.h>
 
@@ -17,7 +19,8 @@
 
 class SparseRosenbrock : public ParOptSparseProblem {
  public:
-  SparseRosenbrock(po_ctx ctx, int n) : ParOptSparseProblem(ctx) {
+  SparseRosenbrock(po_ctx ctx, int n, int factor) : ParOptSparseProblem(ctx) {
+    setSparseFactor(factor);  // before the pattern is handed over
     setProblemSizes(n, 2, n - 1);
     setNumInequalities(2, n - 1);
     std::vector<int> rowp(n), cols(2 * (n - 1));
@@ -81,13 +84,17 @@ class SparseRosenbrock : public ParOptSparseProblem {
 
 int main(int argc, char *argv[]) {
   int nvars = 100;
-  for (int k = 1; k < argc; k++) sscanf(argv[k], "nvars=%d", &nvars);
+  int factor = PO_SPARSE_FACTOR_ROWS;
+  for (int k = 1; k < argc; k++) {
+    sscanf(argv[k], "nvars=%d", &nvars);
+    if (strcmp(argv[k], "factor=multifrontal") == 0) factor = PO_SPARSE_FACTOR_MULTIFRONTAL;
+  }
   po_ctx ctx = NULL;
   if (po_ctx_create(0, &ctx) != 0) {
     fprintf(stderr, "no MI355X available: %s\n", po_last_error());
     return 2;
   }
-  SparseRosenbrock *rosen = new SparseRosenbrock(ctx, nvars);
+  SparseRosenbrock *rosen = new SparseRosenbrock(ctx, nvars, factor);
   rosen->incref();
   ParOptOptions *options = new ParOptOptions();
   options->incref();

@@ -770,6 +770,10 @@ class ParOptSparseProblem : public ParOptProblem {
   // never), before setSparseJacobianData -- a column that enters nearly every sparse constraint, such as the epigraph
   // variable of a min-max formulation, is solved by a low-rank update instead of filling S
   void setDenseColumnThreshold(int min_rows) { dense_min_rows = min_rows; }
+  // Facade extension: the engine that factors S (po_problem_set_sparse_factor: PO_SPARSE_FACTOR_ROWS, the default, or
+  // PO_SPARSE_FACTOR_MULTIFRONTAL), before setSparseJacobianData is attached like the rule above -- the multifrontal
+  // engine of ParOptSparseCholesky pays on mesh-like patterns with large separators
+  void setSparseFactor(int kind) { sparse_factor = kind; }
   // the columns the rule took out, ascending (borrowed); returns their number
   int getDenseColumns(const int **_cols) {
     int count = 0;
@@ -818,6 +822,9 @@ class ParOptSparseProblem : public ParOptProblem {
     if (dense_min_rows != 0 && po_problem_set_sparse_dense_columns(hprob, dense_min_rows) != 0) {
       fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
     }
+    if (sparse_factor != PO_SPARSE_FACTOR_ROWS && po_problem_set_sparse_factor(hprob, sparse_factor) != 0) {
+      fprintf(stderr, "ParOptAMD: %s\n", po_last_error());
+    }
     if (po_problem_set_sparse_jacobian_data(hprob, nwcon, nwinequality, rowp.data(), cols.data(),
                                             &ParOptSparseProblem::tramp_sobjcon,
                                             &ParOptSparseProblem::tramp_sgrad) != 0) {
@@ -829,6 +836,7 @@ class ParOptSparseProblem : public ParOptProblem {
   std::vector<int> rowp, cols;
   std::vector<ParOptScalar> data;
   int dense_min_rows = 0;
+  int sparse_factor = PO_SPARSE_FACTOR_ROWS;
   static int tramp_sobjcon(void *self, po_vec x, double *fobj, double *cons, po_vec sparse) {
     Arg vx(x, 0), vs(sparse, 1);
     return static_cast<ParOptSparseProblem *>(self)->evalSparseObjCon(vx.p(), fobj, cons, vs.p());

@@ -344,6 +344,22 @@ int po_problem_set_sparse_jacobian_data(po_problem p, int64_t nwcon, int64_t nwi
  *   min_rows = -1  never: such a pattern is refused
  * More than 64 qualifying columns, or more than 1.5e9 entries left, are refused in every mode. */
 int po_problem_set_sparse_dense_columns(po_problem p, int64_t min_rows);
+/* Which engine factors the CSR form's S0, to be called BEFORE po_problem_set_sparse_jacobian_data (or
+ * po_problem_set_chain / _chain_dense), like the dense-column rule.
+ *   PO_SPARSE_FACTOR_ROWS          (default) the level-scheduled row Cholesky of the CSR form
+ *   PO_SPARSE_FACTOR_MULTIFRONTAL  the supernodal multifrontal engine of ParOptSparseCholesky below, analysed with
+ *                                  PO_ORDER_ND: S0 is assembled straight into its front panels, the triangular sweeps
+ *                                  of every solve run over its fronts, and "elimination order" everywhere means ITS
+ *                                  order.  Dense columns work on it unchanged.  po_quasidef_factor_info then reports
+ *                                  "nsnodes" as the reference does.  Worth it on mesh-like patterns with large
+ *                                  separators; on chain-like patterns (fronts of order 3) the row factor is the
+ *                                  faster one (README, "Sparse factor engines").
+ * An unknown kind, or a call after the pattern was set, is PO_ERR_ARG.  A pattern recognised as the grouped (block)
+ * form has no factor and ignores the setting; if it falls back to the CSR form later the setting is honoured.  Sparse
+ * constraints are rank-local; the setting must agree on all ranks. */
+enum { PO_SPARSE_FACTOR_ROWS = 0, PO_SPARSE_FACTOR_MULTIFRONTAL = 1 };
+int po_problem_set_sparse_factor(po_problem p, int kind);
+int po_problem_sparse_factor(po_problem p, int *kind);
 /* the dense columns of the problem's pattern, ascending (borrowed, valid like the pattern); *count = 0 without any */
 int po_problem_sparse_dense_columns(po_problem p, const int **cols, int *count);
 /* getSparseJacobianData (src/ParOptProblem.cpp:689-703): host pattern, device values; returns nnz in *nnz.
@@ -369,7 +385,9 @@ int po_quasidef_apply(po_problem p, po_vec x, po_vec dinv, po_vec c, po_vec bx, 
  * limited: panels wider than one kernel's pointer table go in slabs.  out may be NULL when alpha is. */
 int po_quasidef_gram(po_problem p, po_vec x, po_vec dinv, po_vec c, const po_vec *P, int nv, double *W2,
                      const double *alpha, po_vec out);
-/* getFactorInfo (src/ParOptSparseMat.cpp:433-450): one line about the sparse factor, NULL for the block form */
+/* getFactorInfo (src/ParOptSparseMat.cpp:433-450): one line about the sparse factor, NULL for the block form.  The
+ * row factor puts its level and front counts in the supernode column; the multifrontal factor reports "nsnodes" as
+ * the reference does.  Both report nnz(K), nnz(L), their ratio and the sparsity, then " ndense r" with dense columns. */
 const char *po_quasidef_factor_info(po_problem p);
 /* createQuasiDefMat (src/ParOptProblem.h:72): a problem brings its own solver for the quasi-definite block
  * [D Aw^T; Aw -C] (ParOptQuasiDefMat, src/ParOptSparseMat.h:18-62).  Attach the table to ANY problem (callback, CSR,
@@ -406,6 +424,27 @@ typedef struct po_csr_symbolic_s *po_csr_symbolic;
 int po_csr_symbolic_create(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, po_csr_symbolic *out);
 int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
                                  po_csr_symbolic *out);
+/* the same analysis for the factor engine `kind` (PO_SPARSE_FACTOR_*; _create_split is PO_SPARSE_FACTOR_ROWS).  On a
+ * PO_SPARSE_FACTOR_MULTIFRONTAL handle po_csr_symbolic_info, _arrays and _kernel_forms answer PO_ERR_ARG -- they
+ * describe the row factor -- and the three entries below describe the factor instead (PO_ERR_ARG on a row handle):
+ *   _frontal_info     the fields of po_sparse_chol_info;
+ *   _frontal_arrays   the arrays of po_sparse_chol_arrays (perm is the elimination order of everything, dense
+ *                     columns' positions included) and the borrowed ASSEMBLY TABLE: entry e < *ent_count is the
+ *                     structural entry {ent_a[e], ent_b[e]} of the symmetric S0, two rows of Aw, one e per unordered
+ *                     pair, and ent_dst[e] its offset in the engine's L array (inside a front panel, all distinct);
+ *   _frontal_scatter  the engine's own value scatter of the pattern it analysed, S0 with both triangles in
+ *                     compressed columns (colp, rows; the copy in the lower triangle after the permutation is read): destination d < *asm_count at offset asm_dst[d] sums the entries
+ *                     asm_src[asm_ptr[d] .. asm_ptr[d+1]); *l_size doubles of L.  The assembly table is this scatter
+ *                     composed with the entry list. */
+int po_csr_symbolic_create_factor(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
+                                  int kind, po_csr_symbolic *out);
+int po_csr_symbolic_frontal_info(po_csr_symbolic h, int64_t info[8]);
+int po_csr_symbolic_frontal_arrays(po_csr_symbolic h, const int **perm, const int **snode_first,
+                                   const int **snode_parent, const int **snode_level, const int **ent_a,
+                                   const int **ent_b, const int64_t **ent_dst, int64_t *ent_count);
+int po_csr_symbolic_frontal_scatter(po_csr_symbolic h, const int **colp, const int **rows, const int **asm_ptr,
+                                    const int **asm_src, const int64_t **asm_dst, int64_t *asm_count,
+                                    int64_t *l_size);
 /* the dense columns, ascending (borrowed); *count = 0 and *cols = NULL without any */
 int po_csr_symbolic_dense_columns(po_csr_symbolic h, const int **cols, int *count);
 int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]);

@@ -844,6 +844,13 @@ class _QuasiDefMixin:
         return self
 
     @property
+    def sparse_factor(self):
+        """The engine that factors the CSR form's S: "rows" or "multifrontal" (po_problem_sparse_factor)."""
+        kind = C.c_int()
+        check(lib.po_problem_sparse_factor(self.handle, C.byref(kind)))
+        return _SPARSE_FACTORS[kind.value]
+
+    @property
     def dense_columns(self):
         """The columns of the CSR sparse Jacobian that are solved by low-rank update, ascending ([] without any)."""
         dc, cnt = L.c_int_p(), C.c_int()
@@ -886,10 +893,12 @@ class Problem(_QuasiDefMixin):
     evalSparseObjCon(x, sparse_cons) -> (fail, fobj, con) and evalSparseObjConGradient(x, g, A, data) -> fail;
     sparse_cons (nwcon) and data (nnz, in the order of cols) are filled in place.  dense_column_rows is the
     dense-column rule of that form (CsrSymbolic; 0 = automatic), `dense_columns` the columns it took out.
+    sparse_factor is the engine that factors that form's S: "rows" (default) or "multifrontal"
+    (po_problem_set_sparse_factor); `sparse_factor` reads it back.
     """
 
     def __init__(self, ctx, nvars, ncon, ninequality=-1, nwcon=0, nwinequality=0, use_lower=True,
-                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0):
+                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0, sparse_factor="rows"):
         self.ctx = ctx
         self.nvars, self.ncon = int(nvars), int(ncon)
         self.nwcon = int(nwcon)
@@ -1011,6 +1020,8 @@ class Problem(_QuasiDefMixin):
             self._csr_cbs = (L.SPARSE_OBJCON_FN(_sobjcon), L.SPARSE_GRAD_FN(_sgrad))
             if dense_column_rows != 0:
                 check(lib.po_problem_set_sparse_dense_columns(self._h, int(dense_column_rows)))
+            if sparse_factor != "rows":
+                check(lib.po_problem_set_sparse_factor(self._h, _sparse_factor_kind(sparse_factor)))
             check(lib.po_problem_set_sparse_jacobian_data(
                 self._h, self.nwcon, int(nwinequality), self._rowp.ctypes.data_as(L.c_int_p),
                 self._cols.ctypes.data_as(L.c_int_p), self._csr_cbs[0], self._csr_cbs[1]))
@@ -1134,7 +1145,7 @@ class TorchProblem(Problem):
     """
 
     def __init__(self, ctx, nvars, ncon, ninequality=-1, nwcon=0, nwinequality=0, use_lower=True,
-                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0):
+                 use_upper=True, rowp=None, cols=None, nwblock=1, dense_column_rows=0, sparse_factor="rows"):
         import collections
 
         import torch
@@ -1147,7 +1158,7 @@ class TorchProblem(Problem):
         self._data_view = None
         super().__init__(ctx, nvars, ncon, ninequality, nwcon=nwcon, nwinequality=nwinequality, use_lower=use_lower,
                          use_upper=use_upper, rowp=rowp, cols=cols, nwblock=nwblock,
-                         dense_column_rows=dense_column_rows)
+                         dense_column_rows=dense_column_rows, sparse_factor=sparse_factor)
 
     _quasidef_device = True  # createQuasiDefMat's solver works on device tensors too
 
@@ -1241,13 +1252,16 @@ class SeparableProblem(_QuasiDefMixin):
         self.nwcon = a.value
         return self
 
-    def setChain(self, span=2, stride=1, reverse_cols=False, dense_vars=0, dense_column_rows=0):
+    def setChain(self, span=2, stride=1, reverse_cols=False, dense_vars=0, dense_column_rows=0, sparse_factor="rows"):
         """Rank-local overlapping sparse constraints in CSR form: cw_i = 1 - sum_{k<span} x[i*stride+k]^2 >= 0
         (examples/rosenbrock/sparse_rosenbrock.cpp is span 2, stride 1).  dense_vars > 0: the chain runs over the
         first variables and the last dense_vars local ones enter every row, cw_i -= sum_j x[n - dense_vars + j]^2;
-        dense_column_rows is the dense-column rule their columns fall under (Problem)."""
+        dense_column_rows is the dense-column rule their columns fall under, sparse_factor the engine that factors
+        S, "rows" or "multifrontal" (Problem)."""
         if dense_column_rows != 0:
             check(lib.po_problem_set_sparse_dense_columns(self._h, int(dense_column_rows)))
+        if sparse_factor != "rows":
+            check(lib.po_problem_set_sparse_factor(self._h, _sparse_factor_kind(sparse_factor)))
         if dense_vars:
             check(lib.po_problem_set_chain_dense(self._h, int(span), int(stride), int(bool(reverse_cols)),
                                                  int(dense_vars)))
@@ -1363,25 +1377,44 @@ class UserLibraryProblem:
             pass
 
 
+_SPARSE_FACTORS = ("rows", "multifrontal")  # PO_SPARSE_FACTOR_ROWS, PO_SPARSE_FACTOR_MULTIFRONTAL
+
+
+def _sparse_factor_kind(name):
+    if name not in _SPARSE_FACTORS:
+        raise ValueError("sparse_factor must be one of %s, not %r" % (", ".join(_SPARSE_FACTORS), name))
+    return _SPARSE_FACTORS.index(name)
+
+
 class CsrSymbolic:
     """The one-time host analysis of a CSR sparse Jacobian pattern (no device needed): ordering,
     elimination tree, pattern of the Cholesky factor of S = C + Aw D^-1 Aw^T, dependency level sets."""
 
-    def __init__(self, nvars, rowp, cols, dense_column_rows=0):
+    def __init__(self, nvars, rowp, cols, dense_column_rows=0, sparse_factor="rows"):
         """dense_column_rows: the dense-column rule (> 0: columns with at least that many entries leave S and come
         back as a low-rank correction; 0: automatic, only where the pattern would otherwise be refused; -1: never).
-        With dense columns (`dense_cols`, ascending) every other field describes S0 = C + As D^-1 As^T."""
+        With dense columns (`dense_cols`, ascending) every other field describes S0 = C + As D^-1 As^T.
+
+        sparse_factor="multifrontal": the analysis for the multifrontal engine.  The fields are then those of
+        SparseCholesky (num_snodes, nnzL, nlevels, max_snode, max_front, work_bytes, block, perm, snode_first,
+        snode_parent, snode_level) plus nnz / nnzS, the assembly table ent_a, ent_b, ent_dst (one entry of lower(S0)
+        each, its offset in the engine's L) and frontal_scatter(); the row factor's fields do not exist."""
         rowp = np.ascontiguousarray(rowp, dtype=np.intc)
         cols = np.ascontiguousarray(cols, dtype=np.intc)
         w = len(rowp) - 1
         h = L.po_csr_symbolic()
-        check(lib.po_csr_symbolic_create_split(int(nvars), w, rowp.ctypes.data_as(L.c_int_p),
-                                               cols.ctypes.data_as(L.c_int_p), int(dense_column_rows), C.byref(h)))
+        self.sparse_factor = sparse_factor
+        check(lib.po_csr_symbolic_create_factor(int(nvars), w, rowp.ctypes.data_as(L.c_int_p),
+                                                cols.ctypes.data_as(L.c_int_p), int(dense_column_rows),
+                                                _sparse_factor_kind(sparse_factor), C.byref(h)))
         self._h = h
         try:
             dc, cnt = L.c_int_p(), C.c_int()
             check(lib.po_csr_symbolic_dense_columns(h, C.byref(dc), C.byref(cnt)))
             self.dense_cols = [int(dc[i]) for i in range(cnt.value)]
+            if sparse_factor == "multifrontal":
+                self._frontal(w, len(cols))
+                return
             info = (C.c_int64 * 7)()
             check(lib.po_csr_symbolic_info(h, info))
             self.nnz, self.nnzS, self.nnzL, self.nlevels = (int(v) for v in info[:4])
@@ -1400,6 +1433,43 @@ class CsrSymbolic:
         except Exception:
             self.close()
             raise
+
+    def _frontal(self, w, nnz):
+        h = self._h
+        info = (C.c_int64 * 8)()
+        check(lib.po_csr_symbolic_frontal_info(h, info))
+        (self.size, self.num_snodes, self.nnzL, self.nlevels, self.max_snode, self.max_front, self.work_bytes,
+         self.block) = (int(v) for v in info)
+        ptrs = [L.c_int_p() for _ in range(6)]
+        dst, cnt = L.c_i64_p(), C.c_int64()
+        check(lib.po_csr_symbolic_frontal_arrays(h, *[C.byref(p) for p in ptrs], C.byref(dst), C.byref(cnt)))
+
+        def arr(p, n, dtype=np.intc):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n > 0 else np.zeros(0, dtype=dtype)
+
+        ns, ne = self.num_snodes, cnt.value
+        self.perm, self.snode_first = arr(ptrs[0], w), arr(ptrs[1], ns + 1)
+        self.snode_parent, self.snode_level = arr(ptrs[2], ns), arr(ptrs[3], ns)
+        self.ent_a, self.ent_b, self.ent_dst = arr(ptrs[4], ne), arr(ptrs[5], ne), arr(dst, ne, np.int64)
+        self.nnz, self.nnzS = nnz, ne
+
+    def frontal_scatter(self):
+        """The engine's own value scatter of lower(S0) (multifrontal analysis only): (colp, rows, asm_ptr, asm_src,
+        asm_dst, l_size) -- destination d at offset asm_dst[d] of the l_size doubles of L sums the entries
+        asm_src[asm_ptr[d]:asm_ptr[d+1]] of the pattern (colp, rows)."""
+        ptrs = [L.c_int_p() for _ in range(4)]
+        dst, cnt, lsize = L.c_i64_p(), C.c_int64(), C.c_int64()
+        check(lib.po_csr_symbolic_frontal_scatter(self._h, *[C.byref(p) for p in ptrs], C.byref(dst), C.byref(cnt),
+                                                  C.byref(lsize)))
+
+        def arr(p, n, dtype=np.intc):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n > 0 else np.zeros(0, dtype=dtype)
+
+        w, nd = len(self.perm), cnt.value
+        colp = arr(ptrs[0], w + 1)
+        ne = int(colp[-1])
+        return (colp, arr(ptrs[1], ne), arr(ptrs[2], nd + 1), arr(ptrs[3], ne), arr(dst, nd, np.int64),
+                int(lsize.value))
 
     def kernel_forms(self, nv=1):
         """The kernel forms the device factorization and the two triangular sweeps launch on this pattern for a panel

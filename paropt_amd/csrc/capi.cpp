@@ -715,6 +715,27 @@ int po_problem_set_sparse_dense_columns(po_problem p, int64_t min_rows) {
   p->p->dense_min_rows = min_rows;
   return PO_OK;
 }
+int po_problem_set_sparse_factor(po_problem p, int kind) {
+  PO_CHECK_PTR(p);
+  if (kind != PO_SPARSE_FACTOR_ROWS && kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_problem_set_sparse_factor: unknown kind %d (PO_SPARSE_FACTOR_ROWS = 0, "
+                  "PO_SPARSE_FACTOR_MULTIFRONTAL = 1)", kind);
+    return PO_ERR_ARG;
+  }
+  if (p->p->csr) {
+    po::set_error("po_problem_set_sparse_factor: the sparse Jacobian pattern is already set; choose the factor before "
+                  "po_problem_set_sparse_jacobian_data (or po_problem_set_chain)");
+    return PO_ERR_ARG;
+  }
+  p->p->sparse_factor_kind = kind;
+  return PO_OK;
+}
+int po_problem_sparse_factor(po_problem p, int *kind) {
+  PO_CHECK_PTR(p);
+  PO_CHECK_PTR(kind);
+  *kind = p->p->sparse_factor_kind;
+  return PO_OK;
+}
 int po_problem_sparse_dense_columns(po_problem p, const int **cols, int *count) {
   PO_CHECK_PTR(p);
   PO_CHECK_PTR(count);
@@ -843,6 +864,10 @@ int po_csr_symbolic_dense_columns(po_csr_symbolic h, const int **cols, int *coun
 }
 int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
                                  po_csr_symbolic *out) {
+  return po_csr_symbolic_create_factor(nvars, nwcon, rowp, cols, min_rows, PO_SPARSE_FACTOR_ROWS, out);
+}
+int po_csr_symbolic_create_factor(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, int64_t min_rows,
+                                  int kind, po_csr_symbolic *out) {
   PO_CHECK_PTR(rowp);
   PO_CHECK_PTR(out);
   if (nwcon < 0 || nvars < 0 || min_rows < -1 || (rowp[nwcon] > 0 && !cols)) {
@@ -850,7 +875,7 @@ int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, 
     return PO_ERR_ARG;
   }
   po_csr_symbolic h = new po_csr_symbolic_s;
-  int rc = po::csr_analyse(nvars, nwcon, rowp, cols, &h->s, min_rows);
+  int rc = po::csr_analyse(nvars, nwcon, rowp, cols, &h->s, min_rows, kind);
   if (rc != PO_OK) {
     delete h;
     return rc;
@@ -858,9 +883,73 @@ int po_csr_symbolic_create_split(int64_t nvars, int64_t nwcon, const int *rowp, 
   *out = h;
   return PO_OK;
 }
+// the row factor's accessors describe levels, fronts and kernel forms that a multifrontal handle does not have
+static int rows_only(po_csr_symbolic h, const char *what) {
+  if (h->s.factor_kind == PO_SPARSE_FACTOR_ROWS) return PO_OK;
+  po::set_error("%s describes the row factor; this handle was analysed for the multifrontal factor "
+                "(po_csr_symbolic_frontal_info / po_csr_symbolic_frontal_arrays)", what);
+  return PO_ERR_ARG;
+}
+int po_csr_symbolic_frontal_info(po_csr_symbolic h, int64_t info[8]) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  if (h->s.factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_csr_symbolic_frontal_info: the handle was analysed for the row factor (po_csr_symbolic_info)");
+    return PO_ERR_ARG;
+  }
+  const po::CholSymbolic &c = h->s.chol;
+  info[0] = c.n;
+  info[1] = c.nsn;
+  info[2] = c.nnzL;
+  info[3] = c.nlev;
+  info[4] = c.max_s;
+  info[5] = c.max_front;
+  info[6] = c.work_bytes;
+  info[7] = po::kCholNB;
+  return PO_OK;
+}
+int po_csr_symbolic_frontal_arrays(po_csr_symbolic h, const int **perm, const int **snode_first,
+                                   const int **snode_parent, const int **snode_level, const int **ent_a,
+                                   const int **ent_b, const int64_t **ent_dst, int64_t *ent_count) {
+  PO_CHECK_PTR(h);
+  if (h->s.factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_csr_symbolic_frontal_arrays: the handle was analysed for the row factor "
+                  "(po_csr_symbolic_arrays)");
+    return PO_ERR_ARG;
+  }
+  const po::CholSymbolic &c = h->s.chol;
+  if (perm) *perm = c.perm.data();
+  if (snode_first) *snode_first = c.sn_first.data();
+  if (snode_parent) *snode_parent = c.sn_parent.data();
+  if (snode_level) *snode_level = c.sn_level.data();
+  if (ent_a) *ent_a = h->s.ent_a.data();
+  if (ent_b) *ent_b = h->s.ent_b.data();
+  if (ent_dst) *ent_dst = h->s.ent_off.data();
+  if (ent_count) *ent_count = (int64_t)h->s.ent_off.size();
+  return PO_OK;
+}
+int po_csr_symbolic_frontal_scatter(po_csr_symbolic h, const int **colp, const int **rows, const int **asm_ptr,
+                                    const int **asm_src, const int64_t **asm_dst, int64_t *asm_count,
+                                    int64_t *l_size) {
+  PO_CHECK_PTR(h);
+  if (h->s.factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_csr_symbolic_frontal_scatter: the handle was analysed for the row factor");
+    return PO_ERR_ARG;
+  }
+  const po::CholSymbolic &c = h->s.chol;
+  if (colp) *colp = c.colp.data();
+  if (rows) *rows = c.rows.data();
+  if (asm_ptr) *asm_ptr = c.asm_ptr.data();
+  if (asm_src) *asm_src = c.asm_src.data();
+  if (asm_dst) *asm_dst = c.asm_dst.data();
+  if (asm_count) *asm_count = (int64_t)c.asm_dst.size();
+  if (l_size) *l_size = c.Lsize;
+  return PO_OK;
+}
 int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]) {
   PO_CHECK_PTR(h);
   PO_CHECK_PTR(info);
+  PO_TRY(rows_only(h, "po_csr_symbolic_info"));
   info[0] = h->s.nnz;
   info[1] = h->s.nnzS;
   info[2] = h->s.nnzL;
@@ -873,6 +962,7 @@ int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]) {
 int po_csr_symbolic_arrays(po_csr_symbolic h, const int **perm, const int **parent, const int **Lrowp,
                            const int **Lcols, const int **level_ptr, const int **front_of) {
   PO_CHECK_PTR(h);
+  PO_TRY(rows_only(h, "po_csr_symbolic_arrays"));
   if (perm) *perm = h->s.perm.data();
   if (parent) *parent = h->s.parent.data();
   if (Lrowp) *Lrowp = h->s.Lrowp.data();
@@ -885,6 +975,7 @@ int po_csr_symbolic_kernel_forms(po_csr_symbolic h, int nv, int *count, const ch
                                  const int **levels) {
   PO_CHECK_PTR(h);
   PO_CHECK_PTR(count);
+  PO_TRY(rows_only(h, "po_csr_symbolic_kernel_forms"));
   if (nv < 1) {
     po::set_error("po_csr_symbolic_kernel_forms: nv must be at least 1");
     return PO_ERR_ARG;

@@ -203,19 +203,79 @@ void sym_colcount(const std::vector<int> &adjp, const std::vector<int> &adj, con
 }
 
 static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int *cols, CsrSymbolic *out,
-                            bool allow_fronts, int64_t min_rows);
+                            bool allow_fronts, int64_t min_rows, int factor_kind);
 
-int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows) {
-  int rc = csr_analyse_impl(n, w, rowp, cols, out, dbg_switch(SW_NO_FRONTS) <= 0, min_rows);
+int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows,
+                int factor_kind) {
+  if (factor_kind != PO_SPARSE_FACTOR_ROWS && factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    set_error("sparse Jacobian: unknown sparse factor kind %d", factor_kind);
+    return PO_ERR_ARG;
+  }
+  int rc = csr_analyse_impl(n, w, rowp, cols, out, dbg_switch(SW_NO_FRONTS) <= 0, min_rows, factor_kind);
   if (rc == PO_ERR_NUMERIC) {  // a chain that is not a dense front after all: schedule row by row
     *out = CsrSymbolic();
-    rc = csr_analyse_impl(n, w, rowp, cols, out, false, min_rows);
+    rc = csr_analyse_impl(n, w, rowp, cols, out, false, min_rows, factor_kind);
   }
   return rc;
 }
 
+// The multifrontal factor (csr.hpp: CsrSymbolic) of the matrix whose graph is adjp / adj: the engine's own analysis of
+// S0 with its nested dissection, its order taken over, and the entry list of lower(P S0 P^T) composed with the
+// engine's value scatter into offsets in its L.
+static int analyse_multifrontal(CsrSymbolic &s, const std::vector<int> &adjp, const std::vector<int> &adj) {
+  const int w = s.w;
+  // S0 in compressed columns, rows ascending, BOTH triangles as the engine's callers pass a matrix: its scatter reads
+  // the copy of an entry that lies in the lower triangle AFTER the permutation, which may be either one (the order is
+  // the one lower(S0) alone gives: the analysis symmetrises the pattern)
+  if (adj.size() + (size_t)w > 2000000000ULL) {
+    set_error("sparse Jacobian: Aw Aw^T has more than 2e9 entries, more than the multifrontal factor takes");
+    return PO_ERR_ARG;
+  }
+  std::vector<int> colp((size_t)w + 1, 0), rows;
+  rows.reserve(adj.size() + (size_t)w);
+  for (int j = 0; j < w; j++) {
+    const size_t begin = rows.size();
+    rows.push_back(j);
+    rows.insert(rows.end(), adj.begin() + adjp[j], adj.begin() + adjp[j + 1]);
+    std::sort(rows.begin() + begin, rows.end());
+    colp[j + 1] = (int)rows.size();
+  }
+  PO_TRY(chol_analyse(w, colp.data(), rows.data(), PO_ORDER_ND, nullptr, &s.chol));
+  s.factor_kind = PO_SPARSE_FACTOR_MULTIFRONTAL;
+  s.perm = s.chol.perm;
+  s.iperm = s.chol.iperm;
+  s.nnzL = s.chol.nnzL;
+  // every destination of the engine's scatter has one source: the copy of the entry that it reads
+  std::vector<int64_t> off(rows.size(), -1);
+  for (size_t d = 0; d < s.chol.asm_dst.size(); d++) {
+    if (s.chol.asm_ptr[d + 1] - s.chol.asm_ptr[d] != 1) return internal_error("an entry of S shares its place in L");
+    off[s.chol.asm_src[s.chol.asm_ptr[d]]] = s.chol.asm_dst[d];
+  }
+  // (column by column, rows ascending: already the order of Aw's rows that the assembly wants, see below)
+  const size_t ne = s.chol.asm_dst.size();
+  if ((int64_t)ne != s.nnzS) return internal_error("the scatter does not cover lower(S)");
+  s.ent_a.clear();
+  s.ent_b.clear();
+  s.ent_off.clear();
+  s.ent_a.reserve(ne);
+  s.ent_b.reserve(ne);
+  s.ent_off.reserve(ne);
+  for (int j = 0; j < w; j++) {
+    for (int p = colp[j]; p < colp[j + 1]; p++) {
+      if (off[p] < 0) continue;  // the mirror image is the one that is read
+      if (off[p] >= s.chol.Lsize) return internal_error("an entry of S has no place in L");
+      s.ent_a.push_back(j);
+      s.ent_b.push_back(rows[p]);
+      s.ent_off.push_back(off[p]);
+    }
+  }
+  s.dense_pos.resize(s.dense_rows.size());
+  for (size_t q = 0; q < s.dense_rows.size(); q++) s.dense_pos[q] = s.iperm[s.dense_rows[q]];
+  return PO_OK;
+}
+
 static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int *cols, CsrSymbolic *out,
-                            bool allow_fronts, int64_t min_rows) {
+                            bool allow_fronts, int64_t min_rows, int factor_kind) {
   CsrSymbolic &s = *out;
   if (w64 < 0 || n64 < 0 || w64 > 2000000000LL || n64 > 2000000000LL) {
     set_error("sparse Jacobian: sizes out of range (nwcon %lld, nvars %lld)", (long long)w64, (long long)n64);
@@ -356,6 +416,7 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
     }
   }
   s.nnzS = (int64_t)(adj.size() / 2) + w;
+  if (factor_kind == PO_SPARSE_FACTOR_MULTIFRONTAL) return analyse_multifrontal(s, adjp, adj);
   // ordering
   sym_nd_order(adjp, adj, w, &s.perm);
   // The dissection ordering fixes the elimination TREE; any topological order of that tree gives the same
@@ -624,6 +685,8 @@ CsrSparse::~CsrSparse() {
   dfree(d_ent_a);
   dfree(d_ent_b);
   dfree(d_ent_slot);
+  dfree(d_ent_off);
+  delete mf;
   dfree(d_fwd);
   dfree(d_front_of);
   dfree(d_front_end);
@@ -675,7 +738,8 @@ static int group_for(double avg) {
 }
 
 int CsrSparse::setPattern(const int *rowp, const int *cols) {
-  PO_TRY(csr_analyse(n, w, rowp, cols, &sym, dense_min_rows));
+  sym = CsrSymbolic();
+  PO_TRY(csr_analyse(n, w, rowp, cols, &sym, dense_min_rows, factor_kind));
   nnz = sym.nnz;
   user_rowp.assign(rowp, rowp + w + 1);
   user_cols.assign(cols, cols + nnz);
@@ -705,16 +769,37 @@ int CsrSparse::setPattern(const int *rowp, const int *cols) {
   PO_TRY(upload(d_srcT, sym.srcT));
   PO_TRY(upload(d_perm, sym.perm));
   PO_TRY(upload(d_iperm, sym.iperm));
-  PO_TRY(upload(d_Lrowp, sym.Lrowp));
-  PO_TRY(upload(d_Lcols, sym.Lcols));
-  PO_TRY(upload(d_Ltp, sym.Ltp));
-  PO_TRY(upload(d_Ltrows, sym.Ltrows));
-  PO_TRY(upload(d_Ltsrc, sym.Ltsrc));
   PO_TRY(upload(d_ent_a, sym.ent_a));
   PO_TRY(upload(d_ent_b, sym.ent_b));
-  PO_TRY(upload(d_ent_slot, sym.ent_slot));
-  PO_TRY(upload(d_fwd, sym.fwd_order));
-  {
+  delete mf;
+  mf = nullptr;
+  dfree(Lvals);
+  if (sym.factor_kind == PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    // the engine owns the factor and every table of its sweeps; of the row factor nothing is allocated
+    mf = new SparseChol(ctx);
+    mf->sym = std::move(sym.chol);
+    sym.chol = CholSymbolic();
+    PO_TRY(mf->upload(true));
+    PO_TRY(upload(d_ent_off, sym.ent_off));
+    dfree(d_Lrowp);
+    dfree(d_Lcols);
+    dfree(d_Ltp);
+    dfree(d_Ltrows);
+    dfree(d_Ltsrc);
+    dfree(d_ent_slot);
+    dfree(d_fwd);
+    dfree(d_front_of);
+    dfree(d_front_end);
+    dfree(d_fstart);
+    dfree(d_fsize);
+  } else {
+    PO_TRY(upload(d_Lrowp, sym.Lrowp));
+    PO_TRY(upload(d_Lcols, sym.Lcols));
+    PO_TRY(upload(d_Ltp, sym.Ltp));
+    PO_TRY(upload(d_Ltrows, sym.Ltrows));
+    PO_TRY(upload(d_Ltsrc, sym.Ltsrc));
+    PO_TRY(upload(d_ent_slot, sym.ent_slot));
+    PO_TRY(upload(d_fwd, sym.fwd_order));
     std::vector<int> front_end(sym.front_of.size(), -1);
     for (size_t f = 0; f < sym.front_start.size(); f++) {
       for (int r = 0; r < sym.front_size[f]; r++) front_end[sym.front_start[f] + r] = sym.front_start[f] + sym.front_size[f];
@@ -723,12 +808,11 @@ int CsrSparse::setPattern(const int *rowp, const int *cols) {
     PO_TRY(upload(d_front_end, front_end));
     PO_TRY(upload(d_fstart, sym.front_start));
     PO_TRY(upload(d_fsize, sym.front_size));
+    PO_HIP(hipMalloc((void **)&Lvals, ((size_t)sym.nnzL + 4) * sizeof(double)));
   }
-  dfree(Lvals);
   dfree(ones);
   dfree(wwork);
   dfree(d_flag);
-  PO_HIP(hipMalloc((void **)&Lvals, ((size_t)sym.nnzL + 4) * sizeof(double)));
   PO_HIP(hipMalloc((void **)&ones, ((size_t)w + 4) * sizeof(double)));
   PO_HIP(hipMalloc((void **)&wwork, ((size_t)w + 4) * sizeof(double)));
   PO_HIP(hipMalloc((void **)&d_flag, 4 * sizeof(int)));
@@ -744,7 +828,7 @@ int CsrSparse::setPattern(const int *rowp, const int *cols) {
     cw = vec_new(ctx, w);
     if (!cw) return PO_ERR_HIP;
   }
-  nlevels_f = (int)sym.fwd_ptr.size() - 1;
+  nlevels_f = mf ? 0 : (int)sym.fwd_ptr.size() - 1;
   spmv_group = group_for(w > 0 ? (double)nnz / (double)w : 0.0);
   // (the transposed index holds the sparse columns alone)
   spmvT_group = group_for(n > 0 ? (double)sym.rowsT.size() / (double)n : 0.0);
@@ -967,10 +1051,22 @@ void csr_kernel_forms(const CsrSymbolic &s, int nv, int counts[CF_COUNT]) {
 
 int CsrSparse::factor(const double *dinv, const double *cdiag) {
   if (w <= 0) return PO_OK;
-  PO_HIP(hipMemsetAsync(Lvals, 0, ((size_t)sym.nnzL + 4) * sizeof(double), ctx->stream));
-  PO_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), ctx->stream));
-  PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_slot,
-                        (int64_t)sym.ent_slot.size(), Lvals, d_dmask));
+  if (mf) {
+    // S0 goes straight into the engine's front panels, one thread per structural entry as below; flag[1] starts above
+    // every index (the engine keeps the smallest)
+    double *L = nullptr;
+    PO_TRY(mf->beginAssembly(&L));
+    PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), ctx->stream));
+    PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
+    PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_off,
+                          (int64_t)sym.ent_off.size(), L, d_dmask));
+    PO_TRY(mf->factorAssembled(d_flag));
+  } else {
+    PO_HIP(hipMemsetAsync(Lvals, 0, ((size_t)sym.nnzL + 4) * sizeof(double), ctx->stream));
+    PO_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), ctx->stream));
+    PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_slot,
+                          (int64_t)sym.ent_slot.size(), Lvals, d_dmask));
+  }
   for (int l = 0; l < nlevels_f; l++) {
     const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
     const int oe = sym.ord_end[l], f0 = sym.front_ptr[l], nf = sym.front_ptr[l + 1] - f0;
@@ -1029,6 +1125,7 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
 }
 
 int CsrSparse::solveInPlace(double *const *Y, int nv, bool forward, bool backward) {
+  if (mf) return w <= 0 || nv <= 0 ? PO_OK : mf->sweep(Y, nv, forward, backward);  // (any nv: its own slabs)
   if (csr_slab(nv) < nv) {  // independent right-hand sides: slabs of one kernel's pointer table
     for (int j0 = 0; j0 < nv; j0 += csr_slab(nv - j0)) PO_TRY(solveInPlace(Y + j0, csr_slab(nv - j0), forward, backward));
     return PO_OK;
@@ -1109,14 +1206,20 @@ int CsrSparse::solvePanel(const double *const *U, int nv, double *const *Yw) {
 }
 
 const char *CsrSparse::factorInfo() {
-  // the fields of ParOptQuasiDefSparseMat::getFactorInfo (src/ParOptSparseMat.cpp:433-450); this factor has
-  // the level and front counts take the supernode column
+  // the fields of ParOptQuasiDefSparseMat::getFactorInfo (src/ParOptSparseMat.cpp:433-450); the row factor has no
+  // supernodes, its level and front counts take the supernode column
   char buf[192];
   const double tri = 0.5 * (double)w * ((double)w + 1.0);
-  snprintf(buf, sizeof(buf),
-           "n %5lld nlevels %5d nfronts %5d nnz(K) %7lld nnz(L) %7lld nnz(L) / nnz(K) %8.4f sparsity(L) %8.2e",
-           (long long)w, nlevels_f, (int)sym.front_start.size(), (long long)sym.nnzS, (long long)sym.nnzL,
-           sym.nnzS > 0 ? (double)sym.nnzL / (double)sym.nnzS : 0.0, tri > 0 ? (double)sym.nnzL / tri : 0.0);
+  if (mf) {  // the reference's own terms: its factor is supernodal too (src/ParOptSparseMat.cpp:433-450)
+    snprintf(buf, sizeof(buf), "n %5lld nsnodes %5d nnz(K) %7lld nnz(L) %7lld nnz(L) / nnz(K) %8.4f sparsity(L) %8.2e",
+             (long long)w, mf->sym.nsn, (long long)sym.nnzS, (long long)sym.nnzL,
+             sym.nnzS > 0 ? (double)sym.nnzL / (double)sym.nnzS : 0.0, tri > 0 ? (double)sym.nnzL / tri : 0.0);
+  } else {
+    snprintf(buf, sizeof(buf),
+             "n %5lld nlevels %5d nfronts %5d nnz(K) %7lld nnz(L) %7lld nnz(L) / nnz(K) %8.4f sparsity(L) %8.2e",
+             (long long)w, nlevels_f, (int)sym.front_start.size(), (long long)sym.nnzS, (long long)sym.nnzL,
+             sym.nnzS > 0 ? (double)sym.nnzL / (double)sym.nnzS : 0.0, tri > 0 ? (double)sym.nnzL / tri : 0.0);
+  }
   info = buf;
   if (ndense() > 0) info += " ndense " + std::to_string(ndense());
   return info.c_str();

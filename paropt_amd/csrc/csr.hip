@@ -211,12 +211,12 @@ int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, in
 // One thread per structural entry (a, b) of lower(P S P^T): the two column-sorted rows of Aw are merged,
 // Lvals[slot] = [a == b] cdiag[a] + sum_k Aw[a,k] dinv[k] Aw[b,k].  Fill entries were zeroed by the caller.
 // SKIP: the columns marked in `skip` (the dense columns, csr.hpp) stay out of the sums -- S0 is assembled.
-template <bool SKIP>
+template <bool SKIP, class Slot>
 __global__ void __launch_bounds__(kBlock)
     csr_assemble_kernel(const int *__restrict__ rowp, const int *__restrict__ cols,
                         const double *__restrict__ vals, const double *__restrict__ dinv,
                         const double *__restrict__ cdiag, const int *__restrict__ ent_a,
-                        const int *__restrict__ ent_b, const int *__restrict__ ent_slot, int64_t nent,
+                        const int *__restrict__ ent_b, const Slot *__restrict__ ent_slot, int64_t nent,
                         double *__restrict__ Lvals, const unsigned char *__restrict__ skip) {
   PO_C_LOOP(e, nent) {
     const int a = ent_a[e], b = ent_b[e];
@@ -246,18 +246,31 @@ __global__ void __launch_bounds__(kBlock)
     Lvals[ent_slot[e]] = acc;
   }
 }
-int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
-                   const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
-                   double *Lvals, const unsigned char *skip) {
+template <class Slot>
+static int csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
+                        const double *cdiag, const int *ent_a, const int *ent_b, const Slot *ent_slot, int64_t nent,
+                        double *Lvals, const unsigned char *skip) {
   if (nent <= 0) return PO_OK;
+  const auto masked = csr_assemble_kernel<true, Slot>, plain = csr_assemble_kernel<false, Slot>;
   if (skip) {
-    PO_CLAUNCH(csr_assemble_kernel<true>, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
+    PO_CLAUNCH(masked, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
                ent_slot, nent, Lvals, skip);
   } else {
-    PO_CLAUNCH(csr_assemble_kernel<false>, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
+    PO_CLAUNCH(plain, cgrid(c, nent), kBlock, rowp, cols, vals, dinv, cdiag, ent_a, ent_b,
                ent_slot, nent, Lvals, skip);
   }
   return PO_OK;
+}
+int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
+                   const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
+                   double *Lvals, const unsigned char *skip) {
+  return csr_assemble(c, rowp, cols, vals, dinv, cdiag, ent_a, ent_b, ent_slot, nent, Lvals, skip);
+}
+// (the multifrontal engine's panels: an entry's destination is a 64-bit offset into its L)
+int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
+                   const double *cdiag, const int *ent_a, const int *ent_b, const int64_t *ent_off, int64_t nent,
+                   double *L, const unsigned char *skip) {
+  return csr_assemble(c, rowp, cols, vals, dinv, cdiag, ent_a, ent_b, ent_off, nent, L, skip);
 }
 
 // built-in chain constraints (examples/rosenbrock/sparse_rosenbrock.cpp:75-118 is span 2, stride 1)

@@ -27,6 +27,7 @@
 
 #include "core.hpp"
 #include "qn.hpp"
+#include "sparse_chol.hpp"
 
 namespace po {
 
@@ -62,6 +63,16 @@ struct CsrSymbolic {
   // order, value slot dense_slot in the SORTED value array.  Empty when no column qualifies: every array above is
   // then what the analysis without the rule produces.
   std::vector<int> dense_cols, dense_ptr, dense_rows, dense_pos, dense_slot;
+  // THE MULTIFRONTAL FACTOR (factor_kind == PO_SPARSE_FACTOR_MULTIFRONTAL): S0 is factored by the engine of
+  // sparse_chol.hpp instead of the row factor.  `chol` is its analysis of S0 with PO_ORDER_ND, perm / iperm are
+  // ITS elimination order (so dense_pos, the permuted panels and every gather follow it), nnzL its fill.  ent_a / ent_b
+  // are the structural entries of lower(P S0 P^T) as above and ent_off[e] is where entry e lies in the engine's L: the
+  // engine's own value scatter (asm_src -> asm_dst) composed with the entry list, so S0 is assembled straight into
+  // the front panels.  Nothing of the row factor exists then: parent, L*, Lt*, ent_slot, the level and front tables
+  // stay empty.
+  int factor_kind = 0;
+  CholSymbolic chol;
+  std::vector<int64_t> ent_off;
 };
 
 constexpr int kMaxDenseCols = 64;
@@ -69,7 +80,9 @@ constexpr int kMaxDenseCols = 64;
 // returns PO_OK or PO_ERR_ARG (message set); pure host code, testable without a GPU.  min_rows is the dense-column
 // rule: > 0, every column with at least that many entries is dense; 0 (automatic), nothing is taken out unless the
 // pattern would be refused (more than 1.5e9 pairs), then the columns with at least max(1024, w/8) entries; -1, never.
-int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows = 0);
+// factor_kind: PO_SPARSE_FACTOR_ROWS or PO_SPARSE_FACTOR_MULTIFRONTAL (CsrSymbolic).
+int csr_analyse(int64_t n, int64_t w, const int *rowp, const int *cols, CsrSymbolic *out, int64_t min_rows = 0,
+                int factor_kind = 0);
 
 // Steps of the analysis shared with the multifrontal factor (sparse_chol.cpp).  adjp / adj is the graph of the
 // matrix without its diagonal, both triangles; perm[new] = old and iperm is its inverse.
@@ -133,6 +146,10 @@ class CsrSparse {
   ~CsrSparse();
   int setPattern(const int *rowp, const int *cols);
   int64_t dense_min_rows = 0;  // the dense-column rule of csr_analyse; set before setPattern
+  int factor_kind = 0;         // PO_SPARSE_FACTOR_*: which engine factors S0; set before setPattern
+  // the multifrontal engine (owned; null with the row factor).  Its CholSymbolic is the analysis: sym.chol is moved
+  // into it by setPattern.
+  SparseChol *mf = nullptr;
   // The pattern was recognised as the grouped one (problem.hpp): only what the user's callbacks and
   // getSparseJacobianData need -- host copies of the pattern, the value array, the constraint vector -- and NO
   // symbolic analysis (at w = 1 M rows it would cost seconds and hundreds of MB that the block form never uses).
@@ -197,6 +214,7 @@ class CsrSparse {
   int *d_Lrowp = nullptr, *d_Lcols = nullptr;
   int *d_Ltp = nullptr, *d_Ltrows = nullptr, *d_Ltsrc = nullptr;
   int *d_ent_a = nullptr, *d_ent_b = nullptr, *d_ent_slot = nullptr;
+  int64_t *d_ent_off = nullptr;
   int *d_fwd = nullptr;
   int *d_front_of = nullptr, *d_front_end = nullptr, *d_fstart = nullptr, *d_fsize = nullptr;
   double *Lvals = nullptr, *ones = nullptr, *wwork = nullptr;
@@ -219,6 +237,10 @@ int k_csr_panel(Ctx *c, const int *rowp, const int *cols, const double *vals, in
 int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
                    const double *cdiag, const int *ent_a, const int *ent_b, const int *ent_slot, int64_t nent,
                    double *Lvals, const unsigned char *skip = nullptr);
+// the same with 64-bit destinations (the multifrontal engine's panels)
+int k_csr_assemble(Ctx *c, const int *rowp, const int *cols, const double *vals, const double *dinv,
+                   const double *cdiag, const int *ent_a, const int *ent_b, const int64_t *ent_off, int64_t nent,
+                   double *L, const unsigned char *skip = nullptr);
 // (the forms, table capacities and grid shapes below are what csr_level_plan chose: the launchers decide nothing)
 int k_chol_level(Ctx *c, const int *Lrowp, const int *Lcols, double *Lvals, const int *rows, int nrows, int *flag,
                  const CsrLevelPlan &plan);

@@ -127,6 +127,9 @@ class Problem {
   // some rank's pattern has dense columns, so every rank solves through the low-rank form (quasidef.cpp) -- agreed once,
   // where the pattern is set.
   int64_t dense_min_rows = 0;
+  // Which engine factors the CSR form's S0 (PO_SPARSE_FACTOR_*; csr.hpp: CsrSymbolic), read by setSparseJacobianData
+  // like the rule above.  The grouped form has no factor and ignores it until a fall-back to the CSR form.
+  int sparse_factor_kind = 0;
   bool csr_dense_form = false;
   int agreeDenseForm();
   // Structured ("grouped") sparse Jacobian: constraint i acts on the nw consecutive local variables

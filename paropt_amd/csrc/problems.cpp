@@ -58,6 +58,7 @@ int Problem::setSparseJacobianData(int64_t nwcon_, int64_t nwineq_, const int *r
   }
   CsrSparse *m = new CsrSparse(ctx, nlocal, nwcon_);
   m->dense_min_rows = dense_min_rows;
+  m->factor_kind = sparse_factor_kind;
   int rc = rec ? m->setPatternLight(rowp, cols) : m->setPattern(rowp, cols);
   if (rc != PO_OK) {
     delete m;

@@ -12,6 +12,8 @@
 //   chol_update_kernel     C -= A B^T on the rest of the front (panel columns and the b x b update matrix alike), one
 //                          workgroup per 64 x 64 tile of the lower triangle, grid over (row tile of any front, column
 //                          tile) through the level's running tile counts -- a large front spreads over the whole GPU
+// Solves, level by level, a workgroup per front: chol_fwd / chol_bwd (solveDevice: its own permuted buffer, both
+// sweeps) and chol_fwd_panel / chol_bwd_panel (sweep: the interior point's pointer-table panels, see there).
 //
 // Matrix instruction: v_mfma_f64_4x4x4_4b_f64 with the operand layout measured in wgram.hip (A lane = i + 4 b + 16 k,
 // B lane = j + 4 b + 16 k, D lane = j + 4 b + 16 i).  It sustains 75.8 TFLOP/s against 47 for 16x16x4 (wgram.hip), the
@@ -381,6 +383,136 @@ __global__ __launch_bounds__(256) void chol_bwd_kernel(CholDev d, const int *__r
   }
 }
 
+// ---- sweeps over a pointer table (SparseChol::sweep) ---------------------------------------------------------------
+// The interior point's panels: up to kCholMaxRhs vectors a launch, each already in the elimination order, solved in
+// place, forward and backward apart.  What differs from the two kernels above is the solve with the diagonal block.
+// There one lane per right-hand side walks the block, so a single right-hand side -- what the interior point asks
+// for several times an iteration -- leaves 255 lanes of 256 idle through every block of every front.  Here HALF A
+// WAVEFRONT owns a right-hand side and lane i holds entry i of it in a register: column-oriented substitution, after
+// y_j the lanes below (forward) or above (backward) it update their own entry with one LDS read each.
+// LDS: D is the block's lower triangle, column-major with leading dimension 33 doubles.  Forward, the 32 lanes of a
+// half read D[j * 33 + lane], consecutive doubles: one bank row, no conflict.  Backward they read D[lane * 33 + j],
+// a stride of 33 doubles = 66 banks: lane l sits 2 l banks on, 32 distinct bank pairs.  rd holds the reciprocals of
+// the diagonal (32 divisions in parallel once a block, none in the dependent chain); yb is [right-hand side][entry]
+// with the same leading dimension, written by consecutive lanes and read as a broadcast by the L21 products.
+// Every column sees the same operations in the same order whatever nv is: a column of a panel equals the column
+// solved alone, bit for bit.
+struct CholPtrs {
+  double *p[kCholMaxRhs];
+};
+
+__device__ inline void load_triangle_rd(double *D, double *rd, const double *P, int ld, int w) {
+  for (int idx = threadIdx.x; idx < w * w; idx += blockDim.x) {
+    const int col = idx / w, row = idx % w;
+    if (row >= col) {
+      const double v = P[(int64_t)col * ld + row];
+      D[col * kLdsLd + row] = v;
+      if (row == col) rd[col] = 1.0 / v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_fwd_panel_kernel(CholDev d, const int *__restrict__ list, CholPtrs Y,
+                                                             int nv) {
+  __shared__ double D[kCholNB * kLdsLd], yb[kCholMaxRhs * kLdsLd], rd[kCholNB];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
+  const int ld = d.ld[J], ul = d.uld[J];
+  const double *__restrict__ P = d.L + d.panel[J];
+  double *u = d.arena + d.sol[J];
+  const int tid = threadIdx.x, half = tid >> 5, hl = tid & 31;
+  for (int idx = tid; idx < b * nv; idx += 256) u[idx % b + (int64_t)(idx / b) * ul] = 0.0;
+  __syncthreads();
+  for (int c = d.child_ptr[J]; c < d.child_ptr[J + 1]; c++) {
+    const int C = d.child[c], bc = d.nb[C], ulc = d.uld[C];
+    const int *__restrict__ rel = d.rel + d.rows_ptr[C];
+    const double *__restrict__ uc = d.arena + d.sol[C];
+    for (int idx = tid; idx < bc * nv; idx += 256) {
+      const int i = idx % bc, r = idx / bc, t = rel[i];
+      const double v = uc[i + (int64_t)r * ulc];
+      if (t < s) {
+        Y.p[r][first + t] += v;
+      } else {
+        u[t - s + (int64_t)r * ul] += v;
+      }
+    }
+    __syncthreads();
+  }
+  for (int k0 = 0; k0 < s; k0 += kCholNB) {
+    const int w = min(kCholNB, s - k0);
+    load_triangle_rd(D, rd, P + (int64_t)k0 * ld + k0, ld, w);
+    __syncthreads();
+    for (int r0 = 0; r0 < nv; r0 += 8) {  // (uniform trip count: the shuffles below see whole half-wavefronts)
+      const int r = r0 + half;
+      const bool live = r < nv && hl < w;
+      double *yr = Y.p[r < nv ? r : 0] + first + k0;
+      double y = live ? yr[hl] : 0.0;
+      for (int j = 0; j < w; j++) {
+        const double yj = __shfl(y, j, 32) * rd[j];
+        if (hl == j) y = yj;
+        if (hl > j && hl < w) y -= D[j * kLdsLd + hl] * yj;
+      }
+      if (live) {
+        yr[hl] = y;
+        yb[r * kLdsLd + hl] = y;
+      }
+    }
+    __syncthreads();
+    const int i0 = k0 + w, nrow = m - i0;
+    for (int idx = tid; idx < nrow * nv; idx += 256) {
+      const int i = i0 + idx % nrow, r = idx / nrow;
+      const double *__restrict__ yk = yb + r * kLdsLd;
+      double acc = 0.0;
+      for (int k = 0; k < w; k++) acc += P[(int64_t)(k0 + k) * ld + i] * yk[k];
+      if (i < s) {
+        Y.p[r][first + i] -= acc;
+      } else {
+        u[i - s + (int64_t)r * ul] -= acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_bwd_panel_kernel(CholDev d, const int *__restrict__ list, CholPtrs Y,
+                                                             int nv) {
+  __shared__ double D[kCholNB * kLdsLd], z[kCholMaxRhs * kLdsLd], rd[kCholNB];
+  const int J = list[blockIdx.x];
+  const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
+  const int ld = d.ld[J];
+  const double *__restrict__ P = d.L + d.panel[J];
+  const int *__restrict__ rows = d.below + d.rows_ptr[J];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = tid >> 5, hl = tid & 31;
+  const int nblk = (s + kCholNB - 1) / kCholNB;
+  for (int kb = nblk - 1; kb >= 0; kb--) {
+    const int k0 = kb * kCholNB, w = min(kCholNB, s - k0);
+    load_triangle_rd(D, rd, P + (int64_t)k0 * ld + k0, ld, w);
+    // z = y_block - L21^T x_below: a wavefront per (column, right-hand side), coalesced down the column
+    for (int p = wave; p < w * nv; p += 4) {
+      const int k = p % w, r = p / w;
+      const double *__restrict__ col = P + (int64_t)(k0 + k) * ld;
+      const double *yr = Y.p[r];
+      double sum = 0.0;
+      for (int i = k0 + w + lane; i < m; i += 64) sum += col[i] * (i < s ? yr[first + i] : yr[rows[i - s]]);
+      for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+      if (lane == 0) z[r * kLdsLd + k] = yr[first + k0 + k] - sum;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < nv; r0 += 8) {
+      const int r = r0 + half;
+      const bool live = r < nv && hl < w;
+      double x = live ? z[r * kLdsLd + hl] : 0.0;
+      for (int j = w - 1; j >= 0; j--) {
+        const double xj = __shfl(x, j, 32) * rd[j];
+        if (hl == j) x = xj;
+        if (hl < j) x -= D[hl * kLdsLd + j] * xj;
+      }
+      if (live) Y.p[r][first + k0 + hl] = x;
+    }
+    __syncthreads();
+  }
+}
+
 template <class T>
 void dfree(T *&p) {
   if (p) (void)hipFree(p);
@@ -427,10 +559,10 @@ SparseChol::~SparseChol() {
   dfree(d_asm_dst);
 }
 
-int SparseChol::upload() {
+int SparseChol::upload(bool embedded) {
   PO_HIP(hipSetDevice(ctx->device));
   const int64_t arena_doubles = std::max(sym.arena, sym.sol_arena) + 4;
-  const int64_t y_doubles = sym.ldy() * kCholMaxRhs;
+  const int64_t y_doubles = embedded ? 4 : sym.ldy() * kCholMaxRhs;
   if (hipMalloc((void **)&arena, (size_t)arena_doubles * sizeof(double)) != hipSuccess ||
       hipMalloc((void **)&Y, (size_t)y_doubles * sizeof(double)) != hipSuccess ||
       hipMalloc((void **)&L, ((size_t)sym.Lsize + 4) * sizeof(double)) != hipSuccess) {
@@ -442,7 +574,7 @@ int SparseChol::upload() {
   PO_HIP(hipMemset(arena, 0, (size_t)arena_doubles * sizeof(double)));
   PO_HIP(hipMemset(Y, 0, (size_t)y_doubles * sizeof(double)));
   PO_HIP(hipMemset(L, 0, ((size_t)sym.Lsize + 4) * sizeof(double)));
-  PO_HIP(hipMalloc((void **)&avals, (sym.rows.size() + 4) * sizeof(double)));
+  if (!embedded) PO_HIP(hipMalloc((void **)&avals, (sym.rows.size() + 4) * sizeof(double)));
   PO_HIP(hipMalloc((void **)&d_flag, 4 * sizeof(int)));
   PO_TRY(po::upload(d_perm, sym.perm));
   PO_TRY(po::upload(d_first, sym.sn_first));
@@ -461,9 +593,11 @@ int SparseChol::upload() {
   PO_TRY(po::upload(d_chunk_sn, sym.chunk_sn));
   PO_TRY(po::upload(d_chunk_c0, sym.chunk_c0));
   PO_TRY(po::upload(d_tab, sym.tab));
-  PO_TRY(po::upload(d_asm_ptr, sym.asm_ptr));
-  PO_TRY(po::upload(d_asm_src, sym.asm_src));
-  PO_TRY(po::upload(d_asm_dst, sym.asm_dst));
+  if (!embedded) {
+    PO_TRY(po::upload(d_asm_ptr, sym.asm_ptr));
+    PO_TRY(po::upload(d_asm_src, sym.asm_src));
+    PO_TRY(po::upload(d_asm_dst, sym.asm_dst));
+  }
   PO_HIP(hipDeviceSynchronize());
   return PO_OK;
 }
@@ -517,17 +651,31 @@ int SparseChol::setValuesHost(int64_t n, const int *colp, const int *rows, const
   return rc;
 }
 
-int SparseChol::factor(int *info) {
-  if (info) *info = 0;
+int SparseChol::beginAssembly(double **Lout) {
+  PO_HIP(hipSetDevice(ctx->device));
+  PO_HIP(hipMemsetAsync(L, 0, ((size_t)sym.Lsize + 4) * sizeof(double), ctx->stream));
+  have_values = true;
+  factored = false;
+  *Lout = L;
+  return PO_OK;
+}
+
+int SparseChol::factorAssembled(int *flag) {
   if (!have_values) {
-    set_error("sparse Cholesky: factor() needs values set since the last factorization");
+    set_error("sparse Cholesky: factorAssembled() needs beginAssembly() since the last factorization");
     return PO_ERR_ARG;
   }
   PO_HIP(hipSetDevice(ctx->device));
+  PO_TRY(launchFactor(flag));
+  have_values = false;
+  factored = true;
+  return PO_OK;
+}
+
+// every level of the numeric factorization, queued on the stream; pivots are flagged in `flag` (device)
+int SparseChol::launchFactor(int *flag) {
   hipStream_t st = ctx->stream;
-  // flag[0] = 0, flag[1] = 0x7f7f7f7f (above every index)
-  PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), st));
-  PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  int *const d_flag = flag;
   const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
                      d_below, d_rel, d_child_ptr, d_child, L, arena};
   for (int l = 0; l < sym.nlev; l++) {
@@ -556,6 +704,21 @@ int SparseChol::factor(int *info) {
     }
     PO_HIP(hipGetLastError());
   }
+  return PO_OK;
+}
+
+int SparseChol::factor(int *info) {
+  if (info) *info = 0;
+  if (!have_values) {
+    set_error("sparse Cholesky: factor() needs values set since the last factorization");
+    return PO_ERR_ARG;
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // flag[0] = 0, flag[1] = 0x7f7f7f7f (above every index)
+  PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), st));
+  PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+  PO_TRY(launchFactor(d_flag));
   int flag[4] = {0, 0, 0, 0};
   PO_HIP(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
   PO_HIP(hipStreamSynchronize(st));
@@ -599,6 +762,37 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
       hipLaunchKernelGGL(chol_bwd_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy, nr);
     }
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::sweep(double *const *Yh, int nv, bool forward, bool backward) {
+  if (!factored) {
+    set_error("sparse Cholesky: sweep() before the factorization");
+    return PO_ERR_ARG;
+  }
+  if (sym.n == 0 || nv <= 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
+                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  for (int r0 = 0; r0 < nv; r0 += kCholMaxRhs) {  // (sol_off lays the update vectors out for kCholMaxRhs columns)
+    const int nr = std::min(kCholMaxRhs, nv - r0);
+    CholPtrs t;
+    for (int j = 0; j < kCholMaxRhs; j++) t.p[j] = Yh[r0 + (j < nr ? j : 0)];
+    if (forward) {
+      for (int l = 0; l < sym.nlev; l++) {
+        const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
+        hipLaunchKernelGGL(chol_fwd_panel_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], t, nr);
+      }
+    }
+    if (backward) {
+      for (int l = sym.nlev - 1; l >= 0; l--) {
+        const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
+        hipLaunchKernelGGL(chol_bwd_panel_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], t, nr);
+      }
+    }
     PO_HIP(hipGetLastError());
   }
   return PO_OK;

@@ -1,7 +1,8 @@
 // ParOptSparseCholesky (reference src/ParOptSparseCholesky.h:29-162): a sparse Cholesky factorization
 //     L L^T = P A P^T
 // of a user's own SPD matrix, as a supernodal MULTIFRONTAL method with dense fronts on the device.  It stands beside
-// CsrSparse (csr.hpp), which stays the interior point's factor.
+// CsrSparse (csr.hpp), whose row factor stays the interior point's default; a problem that asks for
+// PO_SPARSE_FACTOR_MULTIFRONTAL has CsrSparse own one of these and factor S through it.
 //
 // Split of the work:
 //   host, once per pattern (sparse_chol.cpp, no device needed): symmetrised pattern, ordering, elimination tree in
@@ -77,15 +78,29 @@ class SparseChol {
   ~SparseChol();
   CholSymbolic sym;
   Ctx *ctx;  // null: analysis only
-  int upload();  // after chol_analyse: device tables, L, arena
+  // after chol_analyse: device tables, L, arena.  embedded: the owner assembles L itself (beginAssembly) and solves
+  // through sweep(), so the value scatter, its staging array and the right-hand-side buffer are not allocated
+  int upload(bool embedded = false);
   int setValuesDevice(const double *dvals);
   int setValuesHost(int64_t n, const int *colp, const int *rows, const double *vals);
   int factor(int *info);
   int solveDevice(double *dx, int nrhs, int64_t ldx);
   int solveHost(double *x, int nrhs, int64_t ldx);
+  // The interior point's side (csr.cpp: CsrSparse).  beginAssembly queues the zeroing of L and hands it out: the
+  // caller writes lower(P A P^T) at the offsets of asm_dst with kernels of its own on the same stream.
+  // factorAssembled queues the numeric factorization of what was written and returns without a host read: a
+  // non-positive pivot is replaced by 1, flag[0] is set and flag[1] takes the smallest permuted index (the caller
+  // sets flag[0] = 0 and flag[1] above every index beforehand, and reads them when it likes).
+  int beginAssembly(double **Lout);
+  int factorAssembled(int *flag);
+  // Triangular sweeps over a panel given as a HOST table of nv device vectors that are already in the elimination
+  // order, in place: forward Y <- L^-1 Y, backward Y <- L^-T Y, or both.  No permutation, no copy; any nv (slabs of
+  // kCholMaxRhs columns).  Every column is solved by the same operations whatever nv is.
+  int sweep(double *const *Y, int nv, bool forward, bool backward);
 
  private:
   int scatter(const int *d_ptr, const int64_t *d_dst, const int *d_src, int64_t ndst, const double *dvals);
+  int launchFactor(int *flag);
   bool have_values = false, factored = false;
   double *L = nullptr, *arena = nullptr, *Y = nullptr, *avals = nullptr, *xbuf = nullptr;
   int64_t xbuf_cap = 0;

@@ -267,6 +267,16 @@ SIGNATURES = {
     "po_csr_symbolic_create_split": (
         C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, C.c_int64, C.POINTER(po_csr_symbolic)]),
     "po_csr_symbolic_dense_columns": (C.c_int, [po_csr_symbolic, c_int_pp, C.POINTER(C.c_int)]),
+    "po_csr_symbolic_create_factor": (
+        C.c_int, [C.c_int64, C.c_int64, c_int_p, c_int_p, C.c_int64, C.c_int, C.POINTER(po_csr_symbolic)]),
+    "po_csr_symbolic_frontal_info": (C.c_int, [po_csr_symbolic, c_i64_p]),
+    "po_csr_symbolic_frontal_arrays": (
+        C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp,
+                  C.POINTER(c_i64_p), c_i64_p]),
+    "po_csr_symbolic_frontal_scatter": (
+        C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, C.POINTER(c_i64_p), c_i64_p, c_i64_p]),
+    "po_problem_set_sparse_factor": (C.c_int, [po_problem, C.c_int]),
+    "po_problem_sparse_factor": (C.c_int, [po_problem, C.POINTER(C.c_int)]),
     "po_problem_set_sparse_dense_columns": (C.c_int, [po_problem, C.c_int64]),
     "po_problem_sparse_dense_columns": (C.c_int, [po_problem, c_int_pp, C.POINTER(C.c_int)]),
     "po_csr_symbolic_info": (C.c_int, [po_csr_symbolic, c_i64_p]),
