@@ -445,6 +445,13 @@ int po_csr_symbolic_frontal_arrays(po_csr_symbolic h, const int **perm, const in
 int po_csr_symbolic_frontal_scatter(po_csr_symbolic h, const int **colp, const int **rows, const int **asm_ptr,
                                     const int **asm_src, const int64_t **asm_dst, int64_t *asm_count,
                                     int64_t *l_size);
+/* po_sparse_chol_packing and po_sparse_chol_kernel_forms (below) for the factor of a PO_SPARSE_FACTOR_MULTIFRONTAL
+ * handle; PO_ERR_ARG on a row handle */
+int po_csr_symbolic_frontal_packing(po_csr_symbolic h, int64_t info[4], const int **group_first,
+                                    const int **group_root, const int **group_level, const int **front_order,
+                                    const int64_t **upd_off);
+int po_csr_symbolic_frontal_kernel_forms(po_csr_symbolic h, int nv, int *count, const char *const **names,
+                                         const int **levels);
 /* the dense columns, ascending (borrowed); *count = 0 and *cols = NULL without any */
 int po_csr_symbolic_dense_columns(po_csr_symbolic h, const int **cols, int *count);
 int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]);
@@ -1051,6 +1058,26 @@ int po_sparse_chol_info(po_sparse_chol h, int64_t info[8]);
  * snode_parent (num_snodes, -1 at a root), snode_level (num_snodes, above every child's) */
 int po_sparse_chol_arrays(po_sparse_chol h, const int **perm, const int **snode_first, const int **snode_parent,
                           const int **snode_level);
+/* PACKED GROUPS.  A front of order s + b <= info[0] (8) is tiny.  A subtree of the supernode tree made of tiny fronts
+ * only, of at most `cap` fronts, whose parent's subtree is not such a one, is a group; every tiny front left over is a
+ * group of one.  One lane runs a whole group, children before parents, in the launches of the level of its root,
+ * with the same floating-point operations in the same order as the kernels of the unpacked fronts: results do not
+ * depend on the cap.  The cap is read when the handle is created, from debug switch 38 (po_debug_set_switch; default
+ * 0 = no packing: every front is launched on its own, by a workgroup).
+ * info = {tiny order, cap in force (0 = off), number of groups, levels that launch anything in the factorization}.
+ * Borrowed host arrays, any pointer may be NULL: group g is the supernodes group_first[g] .. group_root[g] (ascending
+ * by group_first) and runs at level group_level[g]; front_order (num_snodes) is s + b; upd_off (num_snodes) is the
+ * offset in doubles of the front's b x b update matrix (leading dimension b rounded up to even) in the work arena.
+ * Works on analysis-only handles. */
+int po_sparse_chol_packing(po_sparse_chol h, int64_t info[4], const int **group_first, const int **group_root,
+                           const int **group_level, const int **front_order, const int64_t **upd_off);
+/* What the factorization and one forward and one backward sweep over nv right-hand sides launch, in the style of
+ * po_csr_symbolic_kernel_forms: *count forms, names[f] (static) and levels[f] = number of levels that launch form f
+ * (borrowed until the next call on h; a sweep counts its levels once per slab of 32 right-hand sides).  Names:
+ * "assemble", "small", "blocked" (unpacked fronts: extend-add, one-wavefront fronts, block columns of larger ones),
+ * "pack_factor", "fwd", "bwd" (a workgroup per unpacked front), "pack_fwd", "pack_bwd".  It is computed by the code
+ * the launchers loop over.  No context needed. */
+int po_sparse_chol_kernel_forms(po_sparse_chol h, int nv, int *count, const char *const **names, const int **levels);
 int po_sparse_chol_destroy(po_sparse_chol h); /* NULL is fine */
 
 #ifdef __cplusplus

@@ -1479,6 +1479,14 @@ class CsrSymbolic:
         check(lib.po_csr_symbolic_kernel_forms(self._h, int(nv), C.byref(cnt), C.byref(names), C.byref(levels)))
         return {names[f].decode(): int(levels[f]) for f in range(cnt.value)}
 
+    def frontal_packing(self):
+        """SparseCholesky.packing() for the factor of a multifrontal analysis."""
+        return _chol_packing(lib.po_csr_symbolic_frontal_packing, self._h, lambda: self.num_snodes)
+
+    def frontal_kernel_forms(self, nv=1):
+        """SparseCholesky.kernel_forms() for the factor of a multifrontal analysis."""
+        return _chol_kernel_forms(lib.po_csr_symbolic_frontal_kernel_forms, self._h, nv)
+
     def close(self):
         if self._h:
             lib.po_csr_symbolic_destroy(self._h)
@@ -1489,6 +1497,27 @@ class CsrSymbolic:
             self.close()
         except Exception:  # pragma: no cover
             pass
+
+
+def _chol_packing(fn, h, num_snodes):
+    info = (C.c_int64 * 4)()
+    ptrs = [L.c_int_p() for _ in range(4)]
+    upd = L.c_i64_p()
+    check(fn(h, info, *[C.byref(p) for p in ptrs], C.byref(upd)))
+
+    def arr(p, n, dtype=np.intc):
+        return np.ctypeslib.as_array(p, shape=(n,)).copy() if n > 0 else np.zeros(0, dtype=dtype)
+
+    ng, num_snodes = int(info[2]), num_snodes()  # (asked for after the call: a handle without fronts was refused)
+    return {"tiny": int(info[0]), "cap": int(info[1]), "num_groups": ng, "factor_levels": int(info[3]),
+            "group_first": arr(ptrs[0], ng), "group_root": arr(ptrs[1], ng), "group_level": arr(ptrs[2], ng),
+            "front_order": arr(ptrs[3], num_snodes), "upd_off": arr(upd, num_snodes, np.int64)}
+
+
+def _chol_kernel_forms(fn, h, nv):
+    cnt, names, levels = C.c_int(), C.POINTER(C.c_char_p)(), L.c_int_p()
+    check(fn(h, int(nv), C.byref(cnt), C.byref(names), C.byref(levels)))
+    return {names[f].decode(): int(levels[f]) for f in range(cnt.value)}
 
 
 class SparseCholesky:
@@ -1536,6 +1565,19 @@ class SparseCholesky:
     @property
     def handle(self):
         return self._h
+
+    def packing(self):
+        """The packed groups of tiny fronts (po_sparse_chol_packing): a dict with tiny (the order up to which a front
+        is tiny), cap (fronts per group at most, read from debug switch 38 at creation; 0: no packing), num_groups,
+        factor_levels (levels that launch anything in the factorization), group_first / group_root / group_level
+        (group g is the supernodes group_first[g] .. group_root[g], run by one lane at level group_level[g]),
+        front_order (s + b of every supernode) and upd_off (its update matrix's offset in the arena)."""
+        return _chol_packing(lib.po_sparse_chol_packing, self._h, lambda: self.num_snodes)
+
+    def kernel_forms(self, nv=1):
+        """{kernel form: number of levels that launch it} for the factorization and one forward and one backward
+        sweep over nv right-hand sides, computed by the code the launchers loop over; no device needed."""
+        return _chol_kernel_forms(lib.po_sparse_chol_kernel_forms, self._h, nv)
 
     def getInfo(self):
         """(size, num_snodes, nnzL) as ParOptSparseCholesky::getInfo."""

@@ -851,6 +851,7 @@ int po_quasidef_gram(po_problem p, po_vec x, po_vec dinv, po_vec c, const po_vec
 struct po_csr_symbolic_s {
   po::CsrSymbolic s;
   int form_counts[po::CF_COUNT];
+  int frontal_form_counts[po::CHF_COUNT];
 };
 int po_csr_symbolic_create(int64_t nvars, int64_t nwcon, const int *rowp, const int *cols, po_csr_symbolic *out) {
   return po_csr_symbolic_create_split(nvars, nwcon, rowp, cols, 0, out);
@@ -944,6 +945,39 @@ int po_csr_symbolic_frontal_scatter(po_csr_symbolic h, const int **colp, const i
   if (asm_dst) *asm_dst = c.asm_dst.data();
   if (asm_count) *asm_count = (int64_t)c.asm_dst.size();
   if (l_size) *l_size = c.Lsize;
+  return PO_OK;
+}
+int po_csr_symbolic_frontal_packing(po_csr_symbolic h, int64_t info[4], const int **group_first,
+                                    const int **group_root, const int **group_level, const int **front_order,
+                                    const int64_t **upd_off) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  if (h->s.factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_csr_symbolic_frontal_packing: the handle was analysed for the row factor");
+    return PO_ERR_ARG;
+  }
+  po::chol_packing(h->s.chol, info, group_first, group_root, group_level, front_order, upd_off);
+  return PO_OK;
+}
+int po_csr_symbolic_frontal_kernel_forms(po_csr_symbolic h, int nv, int *count, const char *const **names,
+                                         const int **levels) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(count);
+  if (h->s.factor_kind != PO_SPARSE_FACTOR_MULTIFRONTAL) {
+    po::set_error("po_csr_symbolic_frontal_kernel_forms: the handle was analysed for the row factor "
+                  "(po_csr_symbolic_kernel_forms)");
+    return PO_ERR_ARG;
+  }
+  if (nv < 1) {
+    po::set_error("po_csr_symbolic_frontal_kernel_forms: nv must be at least 1");
+    return PO_ERR_ARG;
+  }
+  static const char *form_names[po::CHF_COUNT];
+  for (int f = 0; f < po::CHF_COUNT; f++) form_names[f] = po::chol_form_name(f);
+  po::chol_kernel_forms(h->s.chol, nv, h->frontal_form_counts);
+  *count = po::CHF_COUNT;
+  if (names) *names = form_names;
+  if (levels) *levels = h->frontal_form_counts;
   return PO_OK;
 }
 int po_csr_symbolic_info(po_csr_symbolic h, int64_t info[7]) {

@@ -14,6 +14,7 @@ using namespace po;
 
 struct po_sparse_chol_s {
   po::SparseChol *c;
+  int form_counts[po::CHF_COUNT];
 };
 
 #define PO_CHECK_NUMERIC(h)                                                                         \
@@ -40,7 +41,7 @@ int po_sparse_chol_create(po_ctx ctx, int64_t size, const int *colp, const int *
     delete c;
     return rc;
   }
-  *out = new po_sparse_chol_s{c};
+  *out = new po_sparse_chol_s{c, {}};
   return PO_OK;
 }
 // setValues, ParOptSparseCholesky.h:37-38
@@ -97,6 +98,28 @@ int po_sparse_chol_arrays(po_sparse_chol h, const int **perm, const int **snode_
   if (snode_first) *snode_first = s.sn_first.data();
   if (snode_parent) *snode_parent = s.sn_parent.data();
   if (snode_level) *snode_level = s.sn_level.data();
+  return PO_OK;
+}
+int po_sparse_chol_packing(po_sparse_chol h, int64_t info[4], const int **group_first, const int **group_root,
+                           const int **group_level, const int **front_order, const int64_t **upd_off) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  po::chol_packing(h->c->sym, info, group_first, group_root, group_level, front_order, upd_off);
+  return PO_OK;
+}
+int po_sparse_chol_kernel_forms(po_sparse_chol h, int nv, int *count, const char *const **names, const int **levels) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(count);
+  if (nv < 1) {
+    po::set_error("po_sparse_chol_kernel_forms: nv must be at least 1");
+    return PO_ERR_ARG;
+  }
+  static const char *form_names[po::CHF_COUNT];
+  for (int f = 0; f < po::CHF_COUNT; f++) form_names[f] = po::chol_form_name(f);
+  po::chol_kernel_forms(h->c->sym, nv, h->form_counts);
+  *count = po::CHF_COUNT;
+  if (names) *names = form_names;
+  if (levels) *levels = h->form_counts;
   return PO_OK;
 }
 // ~ParOptSparseCholesky, ParOptSparseCholesky.h:34

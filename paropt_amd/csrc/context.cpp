@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "core.hpp"
+#include "sparse_chol.hpp"
 
 namespace po {
 
@@ -69,6 +70,7 @@ static const SwitchDef kSwitches[] = {
     {SW_SYNC_TRACE, "PAROPT_AMD_SYNC_TRACE", 0, true},
     {SW_USER_TIMING, "PAROPT_AMD_USER_TIMING", 0, true},
     {SW_DUMP_LONG_SOLVES, "PAROPT_AMD_DUMP_LONG_SOLVES", -1, false},
+    {SW_CHOL_PACK, nullptr, kCholPackMax, false},
 };
 static struct {
   int value = -1;  // >= 0: set through po_debug_set_switch

@@ -358,15 +358,75 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
   for (int J = 0; J < nsn; J++) s.nlev = std::max(s.nlev, s.sn_level[J] + 1);
   auto order_of = [&](int J) { return s.sn_first[J + 1] - s.sn_first[J] + s.sn_b[J]; };
   auto nblk_of = [&](int J) { return (s.sn_first[J + 1] - s.sn_first[J] + kCholNB - 1) / kCholNB; };
-  // level lists
+  // packed groups: supernodes are in postorder, so the subtree of J is the range [J - cnt[J] + 1, J]
+  s.pack_cap = std::max(0, dbg_switch(SW_CHOL_PACK));
+  s.front_order.resize(nsn);
+  for (int J = 0; J < nsn; J++) s.front_order[J] = order_of(J);
+  std::vector<int> grp_of(nsn, -1);
+  s.grp_first.clear();
+  s.grp_root.clear();
+  s.grp_level.clear();
+  if (s.pack_cap > 0) {
+    std::vector<int> cnt(nsn, 1);
+    std::vector<char> packable(nsn, 0), cand(nsn, 0);
+    for (int J = 0; J < nsn; J++) {
+      bool ok = order_of(J) <= kCholTiny;
+      for (int c = s.child_ptr[J]; c < s.child_ptr[J + 1]; c++) {
+        cnt[J] += cnt[s.child[c]];
+        ok = ok && packable[s.child[c]];
+      }
+      packable[J] = ok;
+      cand[J] = ok && cnt[J] <= s.pack_cap;
+    }
+    for (int J = 0; J < nsn; J++) {
+      const int P = s.sn_parent[J];
+      if (cand[J] && !(P >= 0 && cand[P])) {
+        for (int K = J - cnt[J] + 1; K <= J; K++) {
+          if (grp_of[K] != -1 || (K < J && (s.sn_parent[K] < 0 || s.sn_parent[K] > J)))
+            return chol_internal("a supernode's subtree is not the run of supernodes in front of it");
+          grp_of[K] = J;  // (the root for now)
+        }
+      }
+    }
+    for (int J = 0; J < nsn; J++) {
+      if (grp_of[J] == -1 && order_of(J) <= kCholTiny) grp_of[J] = J;
+    }
+    for (int J = 0; J < nsn; J++) {
+      if (grp_of[J] != J) continue;
+      int f = J;
+      while (f > 0 && grp_of[f - 1] == J) f--;
+      s.grp_first.push_back(f);
+      s.grp_root.push_back(J);
+      s.grp_level.push_back(s.sn_level[J]);
+    }
+  }
+  const int ngrp = (int)s.grp_root.size();
+  s.glev_ptr.assign((size_t)s.nlev + 1, 0);
+  for (int g = 0; g < ngrp; g++) s.glev_ptr[s.grp_level[g] + 1]++;
+  for (int l = 0; l < s.nlev; l++) s.glev_ptr[l + 1] += s.glev_ptr[l];
+  s.glev_first.resize(ngrp);
+  s.glev_root.resize(ngrp);
+  {
+    std::vector<int> fill(s.glev_ptr.begin(), s.glev_ptr.end() - 1);
+    for (int g = 0; g < ngrp; g++) {
+      const int q = fill[s.grp_level[g]]++;
+      s.glev_first[q] = s.grp_first[g];
+      s.glev_root[q] = s.grp_root[g];
+    }
+  }
+  // level lists of the unpacked fronts
   s.lev_ptr.assign((size_t)s.nlev + 1, 0);
-  for (int J = 0; J < nsn; J++) s.lev_ptr[s.sn_level[J] + 1]++;
+  for (int J = 0; J < nsn; J++) {
+    if (grp_of[J] == -1) s.lev_ptr[s.sn_level[J] + 1]++;
+  }
   for (int l = 0; l < s.nlev; l++) s.lev_ptr[l + 1] += s.lev_ptr[l];
-  s.lev_sn.resize(nsn);
+  s.lev_sn.resize(s.lev_ptr[s.nlev]);
   s.lev_nsmall.assign(s.nlev, 0);
   {
     std::vector<int> fill(s.lev_ptr.begin(), s.lev_ptr.end() - 1);
-    for (int J = 0; J < nsn; J++) s.lev_sn[fill[s.sn_level[J]]++] = J;
+    for (int J = 0; J < nsn; J++) {
+      if (grp_of[J] == -1) s.lev_sn[fill[s.sn_level[J]]++] = J;
+    }
     for (int l = 0; l < s.nlev; l++) {
       auto b = s.lev_sn.begin() + s.lev_ptr[l], e = s.lev_sn.begin() + s.lev_ptr[l + 1];
       auto mid = std::stable_partition(b, e, [&](int J) { return order_of(J) <= kCholSmall; });
@@ -374,24 +434,32 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
       std::stable_sort(mid, e, [&](int x, int y) { return nblk_of(x) > nblk_of(y); });
     }
   }
-  // arena layouts: update matrices (factorization) and update vectors (forward solve), the same lifetimes
+  // Arena layouts: update matrices (factorization) and update vectors (forward solve), the same lifetimes.  A slot is
+  // taken at the level that launches its front -- a packed front's is the level of its group's root, whose lane both
+  // writes and reads the slots inside the group -- and given back once the level of the front's parent is through.
   s.upd_off.assign(nsn, 0);
   s.sol_off.assign(nsn, 0);
   {
     ArenaLayout fa, so;
-    for (int l = 0; l < s.nlev; l++) {
-      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) {
-        const int J = s.lev_sn[q];
-        s.upd_off[J] = fa.take((int64_t)s.upd_ld[J] * s.sn_b[J]);
-        s.sol_off[J] = so.take((int64_t)s.upd_ld[J] * kCholMaxRhs);
+    auto take = [&](int J) {
+      s.upd_off[J] = fa.take((int64_t)s.upd_ld[J] * s.sn_b[J]);
+      s.sol_off[J] = so.take((int64_t)s.upd_ld[J] * kCholMaxRhs);
+    };
+    auto give_children = [&](int J) {
+      for (int c = s.child_ptr[J]; c < s.child_ptr[J + 1]; c++) {
+        const int C = s.child[c];
+        fa.give(s.upd_off[C], (int64_t)s.upd_ld[C] * s.sn_b[C]);
+        so.give(s.sol_off[C], (int64_t)s.upd_ld[C] * kCholMaxRhs);
       }
-      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) {
-        const int J = s.lev_sn[q];
-        for (int c = s.child_ptr[J]; c < s.child_ptr[J + 1]; c++) {
-          const int C = s.child[c];
-          fa.give(s.upd_off[C], (int64_t)s.upd_ld[C] * s.sn_b[C]);
-          so.give(s.sol_off[C], (int64_t)s.upd_ld[C] * kCholMaxRhs);
-        }
+    };
+    for (int l = 0; l < s.nlev; l++) {
+      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) take(s.lev_sn[q]);
+      for (int q = s.glev_ptr[l]; q < s.glev_ptr[l + 1]; q++) {
+        for (int J = s.glev_first[q]; J <= s.glev_root[q]; J++) take(J);
+      }
+      for (int q = s.lev_ptr[l]; q < s.lev_ptr[l + 1]; q++) give_children(s.lev_sn[q]);
+      for (int q = s.glev_ptr[l]; q < s.glev_ptr[l + 1]; q++) {
+        for (int J = s.glev_first[q]; J <= s.glev_root[q]; J++) give_children(J);
       }
     }
     s.arena = fa.end;
@@ -440,6 +508,50 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
     s.step_ptr[l + 1] = (int)s.step_nact.size();
   }
   return chol_scatter_table(s, n, colp, rows, &s.asm_ptr, &s.asm_dst, &s.asm_src);
+}
+
+const char *chol_form_name(int form) {
+  static const char *const names[CHF_COUNT] = {"assemble", "small",    "blocked", "pack_factor",
+                                               "fwd",      "bwd",      "pack_fwd", "pack_bwd"};
+  return form >= 0 && form < CHF_COUNT ? names[form] : "";
+}
+
+void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]) {
+  for (int f = 0; f < CHF_COUNT; f++) counts[f] = 0;
+  const int slabs = (nv + kCholMaxRhs - 1) / kCholMaxRhs;
+  for (int l = 0; l < s.nlev; l++) {
+    const CholLevelPlan p = chol_level_plan(s, l);
+    counts[CHF_ASSEMBLE] += p.nchunk > 0;
+    counts[CHF_SMALL] += p.nsmall > 0;
+    counts[CHF_BLOCKED] += p.nsteps > 0;
+    counts[CHF_PACK_FACTOR] += p.ngroup > 0;
+    counts[CHF_FWD] += slabs * (p.nfront > 0);
+    counts[CHF_BWD] += slabs * (p.nfront > 0);
+    counts[CHF_PACK_FWD] += slabs * (p.ngroup > 0);
+    counts[CHF_PACK_BWD] += slabs * (p.ngroup > 0);
+  }
+}
+
+void chol_packing(const CholSymbolic &s, int64_t info[4], const int **group_first, const int **group_root,
+                  const int **group_level, const int **front_order, const int64_t **upd_off) {
+  info[0] = kCholTiny;
+  info[1] = s.pack_cap;
+  info[2] = (int64_t)s.grp_root.size();
+  info[3] = chol_factor_levels(s);
+  if (group_first) *group_first = s.grp_first.data();
+  if (group_root) *group_root = s.grp_root.data();
+  if (group_level) *group_level = s.grp_level.data();
+  if (front_order) *front_order = s.front_order.data();
+  if (upd_off) *upd_off = s.upd_off.data();
+}
+
+int chol_factor_levels(const CholSymbolic &s) {
+  int count = 0;
+  for (int l = 0; l < s.nlev; l++) {
+    const CholLevelPlan p = chol_level_plan(s, l);
+    count += p.nchunk + p.nsmall + p.nsteps + p.ngroup > 0;
+  }
+  return count;
 }
 
 }  // namespace po

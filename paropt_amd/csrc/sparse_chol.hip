@@ -12,8 +12,11 @@
 //   chol_update_kernel     C -= A B^T on the rest of the front (panel columns and the b x b update matrix alike), one
 //                          workgroup per 64 x 64 tile of the lower triangle, grid over (row tile of any front, column
 //                          tile) through the level's running tile counts -- a large front spreads over the whole GPU
+//   chol_pack_factor_kernel  the packed groups of the level (tiny fronts and their subtrees, SW_CHOL_PACK): a lane per
+//                          group does what chol_assemble + chol_small do for each of its fronts, see "packed groups"
 // Solves, level by level, a workgroup per front: chol_fwd / chol_bwd (solveDevice: its own permuted buffer, both
-// sweeps) and chol_fwd_panel / chol_bwd_panel (sweep: the interior point's pointer-table panels, see there).
+// sweeps) and chol_fwd_panel / chol_bwd_panel (sweep: the interior point's pointer-table panels, see there).  The packed
+// groups of a level: chol_pack_fwd / chol_pack_bwd, a lane per group and right-hand side, both forms.
 //
 // Matrix instruction: v_mfma_f64_4x4x4_4b_f64 with the operand layout measured in wgram.hip (A lane = i + 4 b + 16 k,
 // B lane = j + 4 b + 16 k, D lane = j + 4 b + 16 i).  It sustains 75.8 TFLOP/s against 47 for 16x16x4 (wgram.hip), the
@@ -261,6 +264,268 @@ __global__ __launch_bounds__(256) void chol_update_kernel(CholDev d, const int *
   }
 }
 
+// ---- packed groups (sparse_chol.hpp: CholSymbolic::grp_*) ----------------------------------------------------------
+// A front of order <= kCholTiny holds a few lanes' worth of arithmetic, and the bottom levels of every elimination tree
+// are made of them.  ONE LANE runs a whole group of such fronts -- a subtree in postorder -- so a level costs one
+// launch of one thread per group (factorization) or per (group, right-hand side) (sweeps) instead of a workgroup per
+// front, and a chain of one-column fronts inside a group costs no launch at all.  No barriers and nothing shared
+// between lanes: a lane past the end of the list simply leaves.
+// For every front these kernels do the floating-point operations of chol_assemble_kernel + chol_small_kernel, of
+// chol_fwd / chol_bwd and of chol_fwd_panel / chol_bwd_panel in the same order, so L and every solve are bit for bit
+// what the unpacked kernels give.  Contraction is therefore OFF in them and every fused multiply-add of the unpacked
+// kernels is written out (__fma_rn); where those reduce over lanes (the backward sum) the same tree is spelled out.
+// A lane's working set is addressed through rel / below, so it lives in a slot of LDS (odd stride in doubles), never
+// in a private array.
+constexpr int kPackLanes = 64;
+constexpr int kPackB = kCholTiny - 1;                      // rows below the columns of a tiny front at most
+// A CHILD of a tiny front may carry more: its rows below are rows of the parent's front, up to all kCholTiny of them
+// (such a child has order > kCholTiny and is never packed itself, its tiny parent is then a group of one).
+constexpr int kPackChildB = kCholTiny;
+constexpr int kPackTri = kCholTiny * (kCholTiny + 1) / 2;  // entries of the lane's triangle
+constexpr int kPackFactorSlot = kPackTri + 1;              // 37 doubles
+constexpr int kPackSweepSlot = kPackTri + 2 * kCholTiny + 1;  // triangle, block of the vector, update vector: 53
+
+// What a lane needs of a front, loaded one front ahead: the loads of the next front are in flight while the current
+// one is worked on (a lane's fronts are a chain of dependent global loads otherwise).
+struct PackFront {
+  int first, s, b, ld, uld, c0, c1;
+  int64_t panel, rows_ptr, off;  // off: the update matrix (factorization) or the update vector (sweeps)
+};
+__device__ inline PackFront pack_front(const CholDev &d, int J, bool sweep) {
+  PackFront f;
+  f.first = d.first[J];
+  f.s = d.first[J + 1] - f.first;
+  f.b = d.nb[J];
+  f.ld = d.ld[J];
+  f.uld = d.uld[J];
+  f.c0 = d.child_ptr[J];
+  f.c1 = d.child_ptr[J + 1];
+  f.panel = d.panel[J];
+  f.rows_ptr = d.rows_ptr[J];
+  f.off = sweep ? d.sol[J] : d.upd[J];
+  return f;
+}
+
+// entry (row, col), row >= col, of the packed lower triangle of order <= kCholTiny (column after column)
+__device__ inline int tri(int row, int col) { return col * kCholTiny - col * (col - 1) / 2 + row - col; }
+
+// The s panel columns of a front into the lane's triangle.  Global loads are issued a whole column (a whole vector,
+// a whole child, ...) at a time into registers with constant indices and only then used: a load per loop iteration
+// would make a lane wait out the memory latency entry by entry.
+__device__ inline void pack_load_panel(double *F, const double *P, int ld, int s, int m) {
+  for (int col = 0; col < s; col++) {
+    const double *pc = P + (int64_t)col * ld + col;
+    const int len = m - col, base = tri(col, col);
+    double v[kCholTiny];
+#pragma unroll
+    for (int i = 0; i < kCholTiny; i++) v[i] = i < len ? pc[i] : 0.0;
+#pragma unroll
+    for (int i = 0; i < kCholTiny; i++) {
+      if (i < len) F[base + i] = v[i];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kPackLanes) void chol_pack_factor_kernel(CholDev d, const int *__restrict__ gfirst,
+                                                                      const int *__restrict__ groot, int ngroup,
+                                                                      int *flag) {
+#pragma clang fp contract(off)
+  __shared__ double Fs[kPackLanes * kPackFactorSlot];
+  const int g = blockIdx.x * kPackLanes + threadIdx.x;
+  if (g >= ngroup) return;
+  double *F = Fs + threadIdx.x * kPackFactorSlot;
+  const int root = groot[g];
+  PackFront next = pack_front(d, gfirst[g], false);
+  for (int J = gfirst[g]; J <= root; J++) {
+    const PackFront f = next;
+    if (J < root) next = pack_front(d, J + 1, false);
+    const int first = f.first, s = f.s, b = f.b, m = s + b;
+    const int ld = f.ld, uld = f.uld;
+    double *P = d.L + f.panel, *U = d.arena + f.off;
+    pack_load_panel(F, P, ld, s, m);
+    for (int col = s; col < m; col++) {
+      for (int row = col; row < m; row++) F[tri(row, col)] = 0.0;
+    }
+    for (int c = f.c0; c < f.c1; c++) {
+      const int C = d.child[c], bc = d.nb[C], ulc = d.uld[C];
+      const int *__restrict__ rel = d.rel + d.rows_ptr[C];
+      const double *Uc = d.arena + d.upd[C];
+      int rl[kPackChildB];
+#pragma unroll
+      for (int i = 0; i < kPackChildB; i++) rl[i] = i < bc ? rel[i] : 0;
+#pragma unroll
+      for (int j = 0; j < kPackChildB; j++) {
+        if (j < bc) {
+          double v[kPackChildB];
+#pragma unroll
+          for (int i = j; i < kPackChildB; i++) v[i] = i < bc ? Uc[(int64_t)j * ulc + i] : 0.0;
+#pragma unroll
+          for (int i = j; i < kPackChildB; i++) {
+            if (i < bc) F[tri(rl[i], rl[j])] += v[i];
+          }
+        }
+      }
+    }
+    for (int k = 0; k < s; k++) {
+      double piv = F[tri(k, k)];
+      if (!(piv > 0.0)) {
+        flag_pivot(flag, first + k);
+        piv = 1.0;
+      }
+      const double r = sqrt(piv);
+      F[tri(k, k)] = r;
+      for (int i = k + 1; i < m; i++) F[tri(i, k)] /= r;
+      for (int i = k + 1; i < m; i++) {
+        const double lik = F[tri(i, k)];
+        for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, F[tri(j, k)], F[tri(i, j)]);
+      }
+    }
+    for (int col = 0; col < m; col++) {
+      for (int row = col; row < m; row++) *front_entry(P, ld, U, uld, s, row, col) = F[tri(row, col)];
+    }
+  }
+}
+
+struct CholPtrs {
+  double *p[kCholMaxRhs];
+};
+
+// kPanel: the right-hand sides of sweep() (a pointer table, reciprocal pivots, column-oriented substitution as in
+// chol_fwd_panel / chol_bwd_panel); otherwise those of solveDevice (Yb, ldy; row-oriented with a division as in
+// chol_fwd / chol_bwd).  Thread = (group, right-hand side), the right-hand side fastest: the lanes of a group load the
+// same front data and the same entries of L -- one request a wavefront -- and each walks its own vector, whose
+// neighbouring entries the group's next fronts use.  (The group index fastest was measured first: with 21 right-hand
+// sides every lane then fetches the front data and L for itself, and the chain's Gram panel was slower than unpacked.)
+template <bool kPanel>
+__global__ __launch_bounds__(kPackLanes) void chol_pack_fwd_kernel(CholDev d, const int *__restrict__ gfirst,
+                                                                   const int *__restrict__ groot, int ngroup,
+                                                                   CholPtrs Yp, double *Yb, int64_t ldy, int nrhs) {
+#pragma clang fp contract(off)
+  __shared__ double slots[kPackLanes * kPackSweepSlot];
+  const int64_t t = (int64_t)blockIdx.x * kPackLanes + threadIdx.x;
+  if (t >= (int64_t)ngroup * nrhs) return;
+  const int g = (int)(t / nrhs), r = (int)(t % nrhs);
+  double *F = slots + threadIdx.x * kPackSweepSlot, *yl = F + kPackTri, *ul = yl + kCholTiny;
+  double *Y = kPanel ? Yp.p[r] : Yb + r * ldy;
+  const int root = groot[g];
+  PackFront next = pack_front(d, gfirst[g], true);
+  for (int J = gfirst[g]; J <= root; J++) {
+    const PackFront f = next;
+    if (J < root) next = pack_front(d, J + 1, true);
+    const int first = f.first, s = f.s, b = f.b, m = s + b;
+    double *u = d.arena + f.off + (int64_t)r * f.uld;
+    pack_load_panel(F, d.L + f.panel, f.ld, s, m);
+    {
+      double v[kCholTiny];
+#pragma unroll
+      for (int k = 0; k < kCholTiny; k++) v[k] = k < s ? Y[first + k] : 0.0;
+#pragma unroll
+      for (int k = 0; k < kCholTiny; k++) yl[k] = v[k];
+    }
+    for (int i = 0; i < b; i++) ul[i] = 0.0;
+    for (int c = f.c0; c < f.c1; c++) {
+      const int C = d.child[c], bc = d.nb[C];
+      const int *__restrict__ rel = d.rel + d.rows_ptr[C];
+      const double *uc = d.arena + d.sol[C] + (int64_t)r * d.uld[C];
+      int rl[kPackChildB];
+      double v[kPackChildB];
+#pragma unroll
+      for (int i = 0; i < kPackChildB; i++) {
+        rl[i] = i < bc ? rel[i] : 0;
+        v[i] = i < bc ? uc[i] : 0.0;
+      }
+#pragma unroll
+      for (int i = 0; i < kPackChildB; i++) {
+        if (i < bc) {
+          if (rl[i] < s) {
+            yl[rl[i]] += v[i];
+          } else {
+            ul[rl[i] - s] += v[i];
+          }
+        }
+      }
+    }
+    if (kPanel) {
+      for (int j = 0; j < s; j++) {
+        const double yj = yl[j] * (1.0 / F[tri(j, j)]);
+        yl[j] = yj;
+        for (int i = j + 1; i < s; i++) yl[i] = __fma_rn(-F[tri(i, j)], yj, yl[i]);
+      }
+    } else {
+      for (int j = 0; j < s; j++) {
+        double acc = yl[j];
+        for (int k = 0; k < j; k++) acc = __fma_rn(-F[tri(j, k)], yl[k], acc);
+        yl[j] = acc / F[tri(j, j)];
+      }
+    }
+    for (int k = 0; k < s; k++) Y[first + k] = yl[k];
+    for (int i = s; i < m; i++) {
+      double acc = 0.0;
+      for (int k = 0; k < s; k++) acc = __fma_rn(F[tri(i, k)], yl[k], acc);
+      u[i - s] = ul[i - s] - acc;
+    }
+  }
+}
+
+template <bool kPanel>
+__global__ __launch_bounds__(kPackLanes) void chol_pack_bwd_kernel(CholDev d, const int *__restrict__ gfirst,
+                                                                   const int *__restrict__ groot, int ngroup,
+                                                                   CholPtrs Yp, double *Yb, int64_t ldy, int nrhs) {
+#pragma clang fp contract(off)
+  __shared__ double slots[kPackLanes * kPackSweepSlot];
+  const int64_t t = (int64_t)blockIdx.x * kPackLanes + threadIdx.x;
+  if (t >= (int64_t)ngroup * nrhs) return;
+  const int g = (int)(t / nrhs), r = (int)(t % nrhs);
+  double *F = slots + threadIdx.x * kPackSweepSlot, *z = F + kPackTri;
+  double *Y = kPanel ? Yp.p[r] : Yb + r * ldy;
+  const int gf = gfirst[g];
+  PackFront next = pack_front(d, groot[g], true);
+  for (int J = groot[g]; J >= gf; J--) {
+    const PackFront f = next;
+    if (J > gf) next = pack_front(d, J - 1, true);
+    const int first = f.first, s = f.s, b = f.b, m = s + b;
+    const int *__restrict__ rows = d.below + f.rows_ptr;
+    pack_load_panel(F, d.L + f.panel, f.ld, s, m);
+    double x[kPackB];  // the solution at the rows below: ancestors, finished by this lane or by an earlier launch
+    {
+      int rw[kPackB];
+      double v[kCholTiny];
+#pragma unroll
+      for (int i = 0; i < kPackB; i++) rw[i] = i < b ? rows[i] : 0;
+#pragma unroll
+      for (int i = 0; i < kPackB; i++) x[i] = i < b ? Y[rw[i]] : 0.0;
+#pragma unroll
+      for (int k = 0; k < kCholTiny; k++) v[k] = k < s ? Y[first + k] : 0.0;
+#pragma unroll
+      for (int k = 0; k < kCholTiny; k++) z[k] = v[k];
+    }
+    for (int k = 0; k < s; k++) {
+      // The unpacked kernels give lane i the product of below-row i (added to 0.0) and reduce by a __shfl_xor
+      // butterfly, offsets 32 .. 1, in which the lanes past the rows hold 0.0: lane 0 ends with this tree.
+      double q[kCholTiny];
+#pragma unroll
+      for (int i = 0; i < kPackB; i++) q[i] = i < b ? __fma_rn(F[tri(s + i, k)], x[i], 0.0) + 0.0 : 0.0;
+      q[kPackB] = 0.0;
+      const double sum = ((q[0] + q[4]) + (q[2] + q[6])) + ((q[1] + q[5]) + (q[3] + q[7]));
+      z[k] = z[k] - sum;
+    }
+    if (kPanel) {
+      for (int j = s - 1; j >= 0; j--) {
+        const double xj = z[j] * (1.0 / F[tri(j, j)]);
+        z[j] = xj;
+        for (int i = 0; i < j; i++) z[i] = __fma_rn(-F[tri(j, i)], xj, z[i]);
+      }
+    } else {
+      for (int k = s - 1; k >= 0; k--) {
+        double acc = z[k];
+        for (int j = k + 1; j < s; j++) acc = __fma_rn(-F[tri(j, k)], z[j], acc);
+        z[k] = acc / F[tri(k, k)];
+      }
+    }
+    for (int k = 0; k < s; k++) Y[first + k] = z[k];
+  }
+}
+
 // ---- solves ------------------------------------------------------------------------------------------------------
 __global__ void chol_permute_kernel(double *Y, int64_t ldy, double *x, int64_t ldx, const int *__restrict__ perm,
                                     int n, int nrhs, int out) {
@@ -397,9 +662,6 @@ __global__ __launch_bounds__(256) void chol_bwd_kernel(CholDev d, const int *__r
 // with the same leading dimension, written by consecutive lanes and read as a broadcast by the L21 products.
 // Every column sees the same operations in the same order whatever nv is: a column of a panel equals the column
 // solved alone, bit for bit.
-struct CholPtrs {
-  double *p[kCholMaxRhs];
-};
 
 __device__ inline void load_triangle_rd(double *D, double *rd, const double *P, int ld, int w) {
   for (int idx = threadIdx.x; idx < w * w; idx += blockDim.x) {
@@ -513,6 +775,9 @@ __global__ __launch_bounds__(256) void chol_bwd_panel_kernel(CholDev d, const in
   }
 }
 
+// workgroups of a packed sweep: one lane per (group, right-hand side)
+unsigned pack_grid(int ngroup, int nrhs) { return (unsigned)(((int64_t)ngroup * nrhs + kPackLanes - 1) / kPackLanes); }
+
 template <class T>
 void dfree(T *&p) {
   if (p) (void)hipFree(p);
@@ -550,6 +815,8 @@ SparseChol::~SparseChol() {
   dfree(d_panel);
   dfree(d_upd);
   dfree(d_sol);
+  dfree(d_glev_first);
+  dfree(d_glev_root);
   dfree(d_lev_sn);
   dfree(d_chunk_sn);
   dfree(d_chunk_c0);
@@ -589,6 +856,8 @@ int SparseChol::upload(bool embedded) {
   PO_TRY(po::upload(d_panel, sym.panel_off));
   PO_TRY(po::upload(d_upd, sym.upd_off));
   PO_TRY(po::upload(d_sol, sym.sol_off));
+  PO_TRY(po::upload(d_glev_first, sym.glev_first));
+  PO_TRY(po::upload(d_glev_root, sym.glev_root));
   PO_TRY(po::upload(d_lev_sn, sym.lev_sn));
   PO_TRY(po::upload(d_chunk_sn, sym.chunk_sn));
   PO_TRY(po::upload(d_chunk_c0, sym.chunk_c0));
@@ -679,12 +948,16 @@ int SparseChol::launchFactor(int *flag) {
   const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
                      d_below, d_rel, d_child_ptr, d_child, L, arena};
   for (int l = 0; l < sym.nlev; l++) {
-    const int nch = sym.chunk_ptr[l + 1] - sym.chunk_ptr[l];
-    if (nch > 0) {
-      hipLaunchKernelGGL(chol_assemble_kernel, dim3(nch), dim3(128), 0, st, d, d_chunk_sn + sym.chunk_ptr[l],
+    const CholLevelPlan plan = chol_level_plan(sym, l);
+    if (plan.ngroup > 0) {  // (independent of the level's unpacked fronts)
+      hipLaunchKernelGGL(chol_pack_factor_kernel, dim3((plan.ngroup + kPackLanes - 1) / kPackLanes), dim3(kPackLanes),
+                         0, st, d, d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, d_flag);
+    }
+    if (plan.nchunk > 0) {
+      hipLaunchKernelGGL(chol_assemble_kernel, dim3(plan.nchunk), dim3(128), 0, st, d, d_chunk_sn + sym.chunk_ptr[l],
                          d_chunk_c0 + sym.chunk_ptr[l]);
     }
-    const int nsmall = sym.lev_nsmall[l];
+    const int nsmall = plan.nsmall;
     if (nsmall > 0) {
       hipLaunchKernelGGL(chol_small_kernel, dim3(nsmall), dim3(64), 0, st, d, d_lev_sn + sym.lev_ptr[l], d_flag);
     }
@@ -753,13 +1026,30 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
     double *x = dx + (int64_t)r0 * ldx;
     const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 0);
+    const CholPtrs none = {};
     for (int l = 0; l < sym.nlev; l++) {
-      const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
-      hipLaunchKernelGGL(chol_fwd_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy, nr);
+      const CholLevelPlan plan = chol_level_plan(sym, l);
+      if (plan.ngroup > 0) {
+        hipLaunchKernelGGL(chol_pack_fwd_kernel<false>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
+                           d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, none, Y, ldy,
+                           nr);
+      }
+      if (plan.nfront > 0) {
+        hipLaunchKernelGGL(chol_fwd_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy,
+                           nr);
+      }
     }
     for (int l = sym.nlev - 1; l >= 0; l--) {
-      const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
-      hipLaunchKernelGGL(chol_bwd_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy, nr);
+      const CholLevelPlan plan = chol_level_plan(sym, l);
+      if (plan.ngroup > 0) {
+        hipLaunchKernelGGL(chol_pack_bwd_kernel<false>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
+                           d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, none, Y, ldy,
+                           nr);
+      }
+      if (plan.nfront > 0) {
+        hipLaunchKernelGGL(chol_bwd_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy,
+                           nr);
+      }
     }
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 1);
     PO_HIP(hipGetLastError());
@@ -783,14 +1073,30 @@ int SparseChol::sweep(double *const *Yh, int nv, bool forward, bool backward) {
     for (int j = 0; j < kCholMaxRhs; j++) t.p[j] = Yh[r0 + (j < nr ? j : 0)];
     if (forward) {
       for (int l = 0; l < sym.nlev; l++) {
-        const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
-        hipLaunchKernelGGL(chol_fwd_panel_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], t, nr);
+        const CholLevelPlan plan = chol_level_plan(sym, l);
+        if (plan.ngroup > 0) {
+          hipLaunchKernelGGL(chol_pack_fwd_kernel<true>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
+                             d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, t, nullptr,
+                             (int64_t)0, nr);
+        }
+        if (plan.nfront > 0) {
+          hipLaunchKernelGGL(chol_fwd_panel_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l],
+                             t, nr);
+        }
       }
     }
     if (backward) {
       for (int l = sym.nlev - 1; l >= 0; l--) {
-        const int cnt = sym.lev_ptr[l + 1] - sym.lev_ptr[l];
-        hipLaunchKernelGGL(chol_bwd_panel_kernel, dim3(cnt), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], t, nr);
+        const CholLevelPlan plan = chol_level_plan(sym, l);
+        if (plan.ngroup > 0) {
+          hipLaunchKernelGGL(chol_pack_bwd_kernel<true>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
+                             d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, t, nullptr,
+                             (int64_t)0, nr);
+        }
+        if (plan.nfront > 0) {
+          hipLaunchKernelGGL(chol_bwd_panel_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l],
+                             t, nr);
+        }
       }
     }
     PO_HIP(hipGetLastError());

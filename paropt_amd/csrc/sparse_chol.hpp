@@ -13,6 +13,7 @@
 //     assemble (zero + extend-add, the parent gathers its children in a fixed order, no atomics), partial Cholesky of
 //     the first s columns (one wavefront for a small front; diagonal block / trsm / MFMA tile update per block column
 //     for the others), and level-scheduled forward and backward solves for up to kCholMaxRhs right-hand sides a sweep.
+//     With a cap on packed groups (below; off by default) a subtree of tiny fronts is run by one lane instead.
 //
 // Ordering.  PO_ORDER_ND is the nested dissection of csr.cpp (sym_nd_order).  PO_ORDER_NATURAL is the identity, or the
 // caller's perm (perm[new] = old).  PO_ORDER_AMD is ACCEPTED AND GIVEN THE SAME NESTED DISSECTION: this project has no
@@ -34,6 +35,12 @@ constexpr int kCholSmall = 32;   // a front of order <= this is factored by one 
 constexpr int kCholTile = 64;    // trsm row chunk and edge of an update tile (one workgroup)
 constexpr int kCholChunk = 32;   // target columns of a front that one assembling workgroup owns
 constexpr int kCholMaxRhs = 32;  // right-hand sides per solve sweep
+constexpr int kCholTiny = 8;     // a front of order <= this may be packed: a whole group of them is run by one lane
+// Fronts per packed group at most: the default of SW_CHOL_PACK, 0 = no packing.  It IS 0: on the chain pattern every
+// cap from 8 to 64 is several times faster than no packing, but on the grid patterns every one of them is 1 - 7 %
+// slower (a lane walks its group's fronts one after the other in levels that launch their other fronts anyway), and
+// the cap was to be the best one that costs the grids nothing (HISTORY.md, profiles/r19_bench_chol_packing.jsonl).
+constexpr int kCholPackMax = 0;
 
 struct CholSymbolic {
   int n = 0, order = 0;
@@ -49,8 +56,18 @@ struct CholSymbolic {
   int64_t Lsize = 0, arena = 0, sol_arena = 0;
   std::vector<int> child_ptr, child;
   int nlev = 0;
-  // level l = supernodes lev_sn[lev_ptr[l] .. lev_ptr[l+1]): the small fronts first (lev_nsmall[l] of them), then the
-  // blocked ones with the most block columns first, so the fronts that still have block column kb form a prefix
+  // Packed groups (SW_CHOL_PACK, read by chol_analyse).  A front is tiny when its order is <= kCholTiny and packable
+  // when it and its whole subtree are tiny; a packable subtree of at most pack_cap fronts whose parent's subtree is not
+  // one is a group, and every tiny front left over is a group of one.  Group g = fronts grp_first[g] .. grp_root[g]
+  // (postorder: the subtree of its root), run by ONE lane in the launches of level grp_level[g] = sn_level[root];
+  // ascending by first front.  glev_first / glev_root list them level by level for the device.
+  int pack_cap = 0;
+  std::vector<int> front_order;  // nsn: s + b
+  std::vector<int> grp_first, grp_root, grp_level;
+  std::vector<int> glev_ptr, glev_first, glev_root;
+  // level l = the UNPACKED supernodes lev_sn[lev_ptr[l] .. lev_ptr[l+1]): the small fronts first (lev_nsmall[l] of
+  // them), then the blocked ones with the most block columns first, so the fronts that still have block column kb
+  // form a prefix
   std::vector<int> lev_ptr, lev_sn, lev_nsmall;
   std::vector<int> chunk_ptr, chunk_sn, chunk_c0;  // assembling workgroups of each level
   // block column kb of level l: step = step_ptr[l] + kb; step_nact fronts take part; tab[step_tab[step] .. + nact]
@@ -63,6 +80,29 @@ struct CholSymbolic {
   int max_s = 0, max_front = 0;
   int64_t ldy() const { return ((int64_t)n + 3) / 4 * 4 + 4; }
 };
+
+// What one level launches: the launchers of sparse_chol.hip loop over this and chol_kernel_forms counts it.
+struct CholLevelPlan {
+  int nchunk, nsmall, nsteps;  // factorization: assembling workgroups, one-wavefront fronts, block columns
+  int nfront;                  // sweeps: unpacked fronts, a workgroup each
+  int ngroup;                  // packed groups: a lane each (factorization), a lane per right-hand side (sweeps)
+};
+inline CholLevelPlan chol_level_plan(const CholSymbolic &s, int l) {
+  return {s.chunk_ptr[l + 1] - s.chunk_ptr[l], s.lev_nsmall[l], s.step_ptr[l + 1] - s.step_ptr[l],
+          s.lev_ptr[l + 1] - s.lev_ptr[l], s.glev_ptr[l + 1] - s.glev_ptr[l]};
+}
+enum CholForm {
+  CHF_ASSEMBLE, CHF_SMALL, CHF_BLOCKED, CHF_PACK_FACTOR, CHF_FWD, CHF_BWD, CHF_PACK_FWD, CHF_PACK_BWD, CHF_COUNT
+};
+const char *chol_form_name(int form);
+// counts[form] = the levels that launch the form: in one factorization, and in one forward and one backward sweep over
+// nv right-hand sides (every slab of kCholMaxRhs columns counts its levels again)
+void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]);
+// the levels of the factorization that launch anything
+int chol_factor_levels(const CholSymbolic &s);
+// po_sparse_chol_packing / po_csr_symbolic_frontal_packing (paropt_amd.h)
+void chol_packing(const CholSymbolic &s, int64_t info[4], const int **group_first, const int **group_root,
+                  const int **group_level, const int **front_order, const int64_t **upd_off);
 
 // PO_OK or PO_ERR_ARG with a message; pure host code
 int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *perm, CholSymbolic *out);
@@ -108,6 +148,7 @@ class SparseChol {
   int *d_perm = nullptr, *d_first = nullptr, *d_b = nullptr, *d_ld = nullptr, *d_uld = nullptr;
   int *d_below = nullptr, *d_rel = nullptr, *d_child_ptr = nullptr, *d_child = nullptr;
   int64_t *d_rows_ptr = nullptr, *d_panel = nullptr, *d_upd = nullptr, *d_sol = nullptr;
+  int *d_glev_first = nullptr, *d_glev_root = nullptr;
   int *d_lev_sn = nullptr, *d_chunk_sn = nullptr, *d_chunk_c0 = nullptr, *d_tab = nullptr;
   int *d_asm_ptr = nullptr, *d_asm_src = nullptr;
   int64_t *d_asm_dst = nullptr;

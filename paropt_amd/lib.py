@@ -284,6 +284,10 @@ SIGNATURES = {
         C.c_int, [po_csr_symbolic, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
     "po_csr_symbolic_kernel_forms": (
         C.c_int, [po_csr_symbolic, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), c_int_pp]),
+    "po_csr_symbolic_frontal_packing": (
+        C.c_int, [po_csr_symbolic, c_i64_p, c_int_pp, c_int_pp, c_int_pp, c_int_pp, C.POINTER(c_i64_p)]),
+    "po_csr_symbolic_frontal_kernel_forms": (
+        C.c_int, [po_csr_symbolic, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), c_int_pp]),
     "po_csr_symbolic_destroy": (C.c_int, [po_csr_symbolic]),
     "po_sparse_chol_create": (
         C.c_int, [po_ctx, C.c_int64, c_int_p, c_int_p, C.c_int, c_int_p, C.POINTER(po_sparse_chol)]),
@@ -294,6 +298,10 @@ SIGNATURES = {
     "po_sparse_chol_solve_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
     "po_sparse_chol_info": (C.c_int, [po_sparse_chol, c_i64_p]),
     "po_sparse_chol_arrays": (C.c_int, [po_sparse_chol, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
+    "po_sparse_chol_packing": (
+        C.c_int, [po_sparse_chol, c_i64_p, c_int_pp, c_int_pp, c_int_pp, c_int_pp, C.POINTER(c_i64_p)]),
+    "po_sparse_chol_kernel_forms": (
+        C.c_int, [po_sparse_chol, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), c_int_pp]),
     "po_sparse_chol_destroy": (C.c_int, [po_sparse_chol]),
     "po_problem_set_bounds_mode": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_linear_constraints": (C.c_int, [po_problem, C.c_int]),

@@ -13,8 +13,14 @@ On the grid pattern of tools/bench_sparse_chol.py (one constraint per edge of an
 and on the chain pattern of tools/bench_csr.py at its default size (fronts of order 3) factor, apply and the
 interior-point iterations per second of that tool's run.  One JSON line per pattern.
 
+--pack 0 8 16 ... runs the multifrontal engine once per cap on its packed groups of tiny fronts (debug switch 38, set
+before each problem is created and reset after): the engines are then "rows", "multifrontal:cap0", "multifrontal:cap8",
+...  Cap 0 is the engine without packing -- a workgroup per front -- and is the baseline of the other caps, in the same
+process, alternating.
+
     python tools/bench_csr_multifrontal.py [--sizes 150 300] [--chain-nglobal 4000000] [--repeats 3] [--inner 3]
-                                           [--steps 15] [--warmup 5] [--out profiles/r18_bench_csr_multifrontal.jsonl]
+                                           [--steps 15] [--warmup 5] [--pack 0 8 16 32 64]
+                                           [--out profiles/r19_bench_chol_packing.jsonl]
 """
 import argparse
 import json
@@ -28,10 +34,49 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-ENGINES = ("rows", "multifrontal")
+ENGINES = ("rows", "multifrontal")  # (--pack: one "multifrontal:cap<k>" per value instead of the second, engines_of)
+SW_CHOL_PACK = 38  # core.hpp DbgSwitch
+
+
+def create(label, build):
+    """the problem of engine `label`, analysed under its cap"""
+    import paropt_amd as pa
+    from paropt_amd.lib import lib
+
+    kind, _, cap = label.partition(":cap")
+    if cap:
+        lib.po_debug_set_switch(SW_CHOL_PACK, int(cap))
+    try:
+        prob = build(kind)
+        pa.InteriorPoint(prob, {"max_major_iters": 0}).optimize()  # uploads the Jacobian entries
+    finally:
+        lib.po_debug_set_switch(SW_CHOL_PACK, -1)
+    return prob
+
 IP_OPTS = {"qn_type": "bfgs", "qn_subspace_size": 10, "abs_res_tol": 1e-30, "abs_step_tol": 0.0,
            "starting_point_strategy": "affine_step", "start_affine_multiplier_min": 0.01, "penalty_gamma": 1000.0,
            "write_output_frequency": 0}
+
+
+def engines_of(a):
+    return ("rows",) + tuple("multifrontal:cap%d" % cap for cap in a.pack) if a.pack else ENGINES
+
+
+def time_ratios(rec, key, engines):
+    """rows / engine of every repeat: a list under the name this tool always wrote, or with --pack one list per cap"""
+    name = key.replace("_ms", "_ratio_rows_over")
+    if engines == ENGINES:
+        rec[name + "_multifrontal"] = [a / b for a, b in zip(rec[key]["rows"], rec[key]["multifrontal"])]
+    else:
+        rec[name] = {e: [a / b for a, b in zip(rec[key]["rows"], rec[key][e])] for e in engines[1:]}
+
+
+def rate_ratios(rec, engines):
+    rates = rec["ip_iterations_per_s"]
+    if engines == ENGINES:
+        rec["ip_ratio_multifrontal_over_rows"] = [m / r for r, m in zip(rates["rows"], rates["multifrontal"])]
+    else:
+        rec["ip_ratio_over_rows"] = {e: [m / r for r, m in zip(rates["rows"], rates[e])] for e in engines[1:]}
 
 
 def timed(ctx, fn, inner):
@@ -66,30 +111,34 @@ def vec(pa, ctx, arr):
 
 
 def solver_times(pa, ctx, probs, n, w, rng, repeats, inner, widths, rec):
-    """factor / apply / gram of both problems, alternating; checks that the two engines solve the same system"""
+    """factor / apply / gram of every problem, alternating; checks that the engines solve the same system"""
+    engines = tuple(probs)
     dinv, cdiag = rng.uniform(0.5, 2.0, n), rng.uniform(0.1, 1.0, w)
     x, d, c = vec(pa, ctx, np.full(n, 0.5)), vec(pa, ctx, dinv), vec(pa, ctx, cdiag)
     bx, bw = vec(pa, ctx, rng.standard_normal(n)), vec(pa, ctx, rng.standard_normal(w))
     out = {}
-    for e in ENGINES:
+    for e in engines:
         yx, yw = pa.PVec(ctx, n), pa.PVec(ctx, w)
         pa.quasidef_factor(probs[e], x, d, c)
         pa.quasidef_apply(probs[e], x, d, c, bx, bw, yx, yw)
         out[e] = (yx, yw)
         rec["factor_info_" + e] = pa.quasidef_factor_info(probs[e])
     ref = out["rows"][1].to_numpy()
-    rec["solutions_max_abs_diff"] = float(np.abs(out["multifrontal"][1].to_numpy() - ref).max())
+    rec["solutions_max_abs_diff"] = max(float(np.abs(out[e][1].to_numpy() - ref).max()) for e in engines[1:])
+    mf = [out[e][1].to_numpy() for e in engines[1:]]
+    if len(mf) > 1:
+        rec["multifrontal_solutions_bit_equal"] = all(np.array_equal(mf[0], y) for y in mf)
     rec["solution_max_abs"] = float(np.abs(ref).max())
     panels = {nv: [pa.PVec(ctx, n).fill_hash(0, 20 + j, 0, 2.0, -1.0 + 0.01 * j) for j in range(nv)] for nv in widths}
     alphas = {nv: rng.standard_normal(nv) for nv in widths}
-    for e in ENGINES:
+    for e in engines:
         for nv in widths:
             pa.quasidef_gram(probs[e], x, d, c, panels[nv], alpha=alphas[nv])  # (warm: the work vectors grow once)
     keys = ["quasidef_factor_ms", "quasidef_apply_ms"] + ["quasidef_gram_nv%d_ms" % nv for nv in widths]
     for k in keys:
-        rec[k] = {e: [] for e in ENGINES}
+        rec[k] = {e: [] for e in engines}
     for _ in range(repeats):
-        for e in ENGINES:
+        for e in engines:
             p = probs[e]
             yx, yw = out[e]
             rec["quasidef_factor_ms"][e].append(timed(ctx, lambda: pa.quasidef_factor(p, x, d, c), inner))
@@ -97,10 +146,9 @@ def solver_times(pa, ctx, probs, n, w, rng, repeats, inner, widths, rec):
             for nv in widths:
                 rec["quasidef_gram_nv%d_ms" % nv][e].append(
                     timed(ctx, lambda: pa.quasidef_gram(p, x, d, c, panels[nv], alpha=alphas[nv]), inner))
-        print("# repeat done", {k: {e: round(rec[k][e][-1], 3) for e in ENGINES} for k in keys}, flush=True)
+        print("# repeat done", {k: {e: round(rec[k][e][-1], 3) for e in engines} for k in keys}, flush=True)
     for k in keys:
-        rec[k.replace("_ms", "_ratio_rows_over_multifrontal")] = [
-            a / b for a, b in zip(rec[k]["rows"], rec[k]["multifrontal"])]
+        time_ratios(rec, k, engines)
 
 
 def run_grid(ctx, nx, a):
@@ -139,26 +187,24 @@ def run_grid(ctx, nx, a):
 
         return P()
 
+    engines = engines_of(a)
     rec = {"pattern": "grid %dx%d" % (nx, nx), "n": n, "w": w, "repeats": a.repeats, "inner": a.inner}
-    t0 = time.perf_counter()
     probs = {}
-    for e in ENGINES:
+    for e in engines:
         t0 = time.perf_counter()
-        probs[e] = problem(e)
+        probs[e] = create(e, problem)
         rec["setup_s_" + e] = time.perf_counter() - t0
-        pa.InteriorPoint(probs[e], {"max_major_iters": 0}).optimize()  # uploads the Jacobian entries
     solver_times(pa, ctx, probs, n, w, rng, a.repeats, a.inner, (21, 73), rec)
-    rec["ip_iterations_per_s"] = {e: [] for e in ENGINES}
+    rec["ip_iterations_per_s"] = {e: [] for e in engines}
     rec["ip_workload"] = "sum (x - xt)^2, 1 dense linear constraint, cw = b - A x >= 0, L-BFGS(10), host callbacks"
     for _ in range(a.repeats):
-        for e in ENGINES:
+        for e in engines:
             rate, done, fobj = iterations_per_second(pa, ctx, probs[e], a.warmup, a.steps)
             rec["ip_iterations_per_s"][e].append(rate)
             rec.setdefault("ip_steps", {})[e] = done
             rec.setdefault("ip_fobj", {})[e] = fobj
-        print("# ip repeat done", {e: round(rec["ip_iterations_per_s"][e][-1], 3) for e in ENGINES}, flush=True)
-    rec["ip_ratio_multifrontal_over_rows"] = [
-        m / r for r, m in zip(rec["ip_iterations_per_s"]["rows"], rec["ip_iterations_per_s"]["multifrontal"])]
+        print("# ip repeat done", {e: round(rec["ip_iterations_per_s"][e][-1], 3) for e in engines}, flush=True)
+    rate_ratios(rec, engines)
     return rec
 
 
@@ -166,26 +212,30 @@ def run_chain(ctx, a):
     import paropt_amd as pa
 
     n = a.chain_nglobal
+    engines = engines_of(a)
     rec = {"pattern": "chain span 2 stride 1 (tools/bench_csr.py)", "n": n, "repeats": a.repeats, "inner": a.inner}
     probs = {}
-    for e in ENGINES:
+
+    def problem(kind):
+        return pa.SeparableProblem(ctx, "convex", n, 4, 0).setChain(2, 1, sparse_factor=kind)
+
+    for e in engines:
         t0 = time.perf_counter()
-        probs[e] = pa.SeparableProblem(ctx, "convex", n, 4, 0).setChain(2, 1, sparse_factor=e)
+        probs[e] = create(e, problem)
         rec["setup_s_" + e] = time.perf_counter() - t0
         print("# chain set up", e, round(rec["setup_s_" + e], 2), "s", flush=True)
     w = probs["rows"].nwcon
     rec["w"] = w
-    rec["ip_iterations_per_s"] = {e: [] for e in ENGINES}
+    rec["ip_iterations_per_s"] = {e: [] for e in engines}
     rec["ip_workload"] = "convex n=%d c=4 chain span=2 stride=1 (w=%d) L-BFGS(10), built in" % (n, w)
     for _ in range(a.repeats):
-        for e in ENGINES:
+        for e in engines:
             rate, done, fobj = iterations_per_second(pa, ctx, probs[e], a.warmup, a.steps)
             rec["ip_iterations_per_s"][e].append(rate)
             rec.setdefault("ip_steps", {})[e] = done
             rec.setdefault("ip_fobj", {})[e] = fobj
-        print("# ip repeat done", {e: round(rec["ip_iterations_per_s"][e][-1], 3) for e in ENGINES}, flush=True)
-    rec["ip_ratio_multifrontal_over_rows"] = [
-        m / r for r, m in zip(rec["ip_iterations_per_s"]["rows"], rec["ip_iterations_per_s"]["multifrontal"])]
+        print("# ip repeat done", {e: round(rec["ip_iterations_per_s"][e][-1], 3) for e in engines}, flush=True)
+    rate_ratios(rec, engines)
     # (the Jacobian entries are those of the last evaluation of each run: the same point on both engines)
     solver_times(pa, ctx, probs, n, w, np.random.default_rng(0), a.repeats, a.inner, (21,), rec)
     return rec
@@ -199,6 +249,8 @@ def main():
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--steps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--pack", type=int, nargs="*", default=None,
+                    help="caps of the packed groups to run the multifrontal engine with (0: no packing)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="add the lines to --out instead of replacing the file")
     a = ap.parse_args()

@@ -115,9 +115,78 @@ def run(ctx, nx, repeats, inner):
     return rec
 
 
+def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16):
+    """the public class with its packed groups of tiny fronts switched off (cap 0: a workgroup per front) and with
+    groups of at most `cap` fronts, alternating: factor and a solve of one right-hand side"""
+    import torch
+
+    import paropt_amd as pa
+    from paropt_amd.lib import lib
+
+    dev = torch.device("cuda", ctx.device())
+    svals = torch.from_numpy(np.ascontiguousarray(vals)).to(dev)
+    rhs = torch.from_numpy(np.random.default_rng(0).standard_normal(n)).to(dev)
+    work = rhs.clone()
+    chol = {}
+    packed = "cap%d" % cap
+    for key, value in (("cap0", 0), (packed, cap)):
+        lib.po_debug_set_switch(38, value)  # core.hpp SW_CHOL_PACK, read by the analysis
+        try:
+            chol[key] = pa.SparseCholesky(ctx, n, colp, rows)
+        finally:
+            lib.po_debug_set_switch(38, -1)
+
+    def timed(fn):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        ctx.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / inner
+
+    def factor(c):
+        c.set_values_device(svals)
+        assert c.factor() == 0
+
+    def solve(c):
+        work.copy_(rhs)
+        c.solve_tensor(work)
+
+    sols = {}
+    for key, c in chol.items():
+        factor(c)
+        solve(c)
+        sols[key] = work.cpu().numpy().copy()
+    p = chol[packed].packing()
+    rec = {"pattern": name, "n": n, "snodes": chol[packed].num_snodes, "levels": chol[packed].nlevels,
+           "cap": p["cap"], "groups": p["num_groups"], "factor_levels": p["factor_levels"],
+           "kernel_forms": chol[packed].kernel_forms(),
+           "bit_equal": bool(np.array_equal(sols["cap0"], sols[packed])),
+           "chol_factor_ms": {k: [] for k in chol}, "chol_solve_ms": {k: [] for k in chol}}
+    for _ in range(repeats):
+        for key, c in chol.items():
+            rec["chol_factor_ms"][key].append(timed(lambda: factor(c)))
+            rec["chol_solve_ms"][key].append(timed(lambda: solve(c)))
+    return rec
+
+
+def packing_patterns(tridiag_n, nx):
+    import scipy.sparse as sp
+
+    T = sp.diags([-np.ones(tridiag_n - 1), np.full(tridiag_n, 2.5), -np.ones(tridiag_n - 1)], [-1, 0, 1]).tocsc()
+    G = sp.kron(sp.eye(nx), sp.diags([-np.ones(nx - 1), np.full(nx, 2.25), -np.ones(nx - 1)], [-1, 0, 1]))
+    G = (G + sp.kron(sp.diags([-np.ones(nx - 1), np.full(nx, 2.25), -np.ones(nx - 1)], [-1, 0, 1]), sp.eye(nx))).tocsc()
+    for name, M in (("tridiagonal n=%d" % tridiag_n, T), ("5-point grid %dx%d" % (nx, nx), G)):
+        M.sort_indices()
+        yield name, M.shape[0], M.indptr, M.indices, M.data
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", type=int, nargs="+", default=[150, 300])
+    ap.add_argument("--packing", type=int, nargs=2, default=None, metavar=("TRIDIAG_N", "GRID_NX"),
+                    help="also one line each for a tridiagonal and a 5-point grid matrix on the public class, "
+                         "packed groups off against groups of at most 16 fronts")
+    ap.add_argument("--sizes", type=int, nargs="*", default=[150, 300])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--out", default=None)
@@ -129,6 +198,10 @@ def main():
     for nx in a.sizes:
         lines.append(json.dumps(run(ctx, nx, a.repeats, a.inner)))
         print(lines[-1], flush=True)
+    if a.packing:
+        for name, n, colp, rows, vals in packing_patterns(*a.packing):
+            lines.append(json.dumps(run_packing(ctx, name, n, colp, rows, vals, a.repeats, a.inner)))
+            print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
