@@ -2070,7 +2070,11 @@ inline double ParOptProblem::checkGradients(double dh, ParOptVec *xvec, int chec
 // nested dissection as PAROPT_ND_ORDER.  The reference's constructor has no communicator: with PAROPT_AMD_USE_MPI the
 // reference's exact signature works on MPI_COMM_SELF, and either way a leading ParOptComm names the device context.
 // setValues with an entry outside the factor's pattern fails (the reference drops it): the message is printed.
+// setFactorization(PAROPT_CHOLESKY_LDLT) -- no counterpart in the reference -- makes the next factor() compute
+// L S L^T = P A P^T with S = diag(+-1) and no pivoting: for symmetric quasi-definite matrices ([[E, B^T], [B, -F]] with
+// E, F SPD), which have it under every permutation; for a general indefinite matrix it is only as good as its pivots.
 enum ParOptOrderingType { PAROPT_NATURAL_ORDER, PAROPT_AMD_ORDER, PAROPT_ND_ORDER };
+enum ParOptFactorizationType { PAROPT_CHOLESKY_LLT, PAROPT_CHOLESKY_LDLT };
 
 class ParOptSparseCholesky {
  public:
@@ -2098,6 +2102,22 @@ class ParOptSparseCholesky {
     int info = 0;
     if (report(po_sparse_chol_factor(h, &info)) != 0) return -1;
     return info;
+  }
+  // read by the next factor(); values are set before every factor() in either kind.  In LDLT a negative pivot is no
+  // error and factor() reports a pivot that is exactly zero or NaN (replaced by +1).  0, or non-zero with a message.
+  int setFactorization(ParOptFactorizationType kind) {
+    return report(po_sparse_chol_set_factorization(h, kind == PAROPT_CHOLESKY_LDLT ? PO_CHOL_LDLT : PO_CHOL_LLT));
+  }
+  // the pivots of the last factor(): positive, negative, replaced (they sum to size); any pointer may be NULL.
+  // 0, or non-zero with a message before the first factor() and after an LLT factor() that replaced pivots (those
+  // are not counted).
+  int getInertia(int *pos, int *neg, int *replaced) {
+    int64_t in[3] = {0, 0, 0};
+    const int rc = report(po_sparse_chol_inertia(h, in));
+    if (pos) *pos = (int)in[0];
+    if (neg) *neg = (int)in[1];
+    if (replaced) *replaced = (int)in[2];
+    return rc;
   }
   void solve(ParOptScalar *x) { report(po_sparse_chol_solve(h, x, 1, size)); }
   // nrhs right-hand sides, column j at x + j * size

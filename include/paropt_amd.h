@@ -1047,6 +1047,31 @@ int po_sparse_chol_set_values_device(po_sparse_chol h, const double *dvals);
  * info in the reference, .cpp:631).  Such a pivot is replaced by 1 and the factorization finishes; the return value
  * is PO_OK either way.  Needs values set since the last factorization (the factor overwrites them). */
 int po_sparse_chol_factor(po_sparse_chol h, int *info);
+/* FACTORIZATION KIND.  PO_CHOL_LLT (the default) is the Cholesky factorization above.  PO_CHOL_LDLT computes
+ *     P A P^T = L S L^T,   L lower triangular with a positive diagonal (the pattern and storage of the Cholesky
+ *     factor),   S = diag(+-1) the signs of the pivots,
+ * with NO pivoting and no threshold: column k has s_k = sign(piv), l_kk = sqrt|piv|, l_ik = a_ik / (s_k l_kk).  It is
+ * meant for symmetric QUASI-DEFINITE matrices, [[E, B^T], [B, -F]] with E and F SPD (a KKT system with a regularised
+ * corner, the interior point's [[D, Aw^T], [Aw, -C]]): those have this factorization under every symmetric
+ * permutation (Vanderbei), so the analysis, the ordering and the launch plan are the ones of the Cholesky
+ * factorization.  For a general symmetric indefinite matrix the result is only as good as its pivots -- nothing
+ * guards against a small one.  In this mode a negative pivot is no error; a pivot that is exactly zero or NaN is
+ * replaced by +1, the factorization finishes, *info of po_sparse_chol_factor is 1 + the smallest permuted index of
+ * such a pivot and the return value is PO_OK.  A solve is a forward sweep with L, y_k <- s_k y_k, and a backward
+ * sweep with L^T, all queued on the context's stream.
+ * _set_factorization may be called at any time, also between factorizations (the next po_sparse_chol_factor reads
+ * it; a solve follows the factorization it solves with), and on an analysis-only handle, where the kind is recorded.
+ * PO_ERR_ARG with a message for an unknown kind or a NULL handle.  The kind changes neither po_sparse_chol_info nor
+ * po_sparse_chol_kernel_forms: both kinds launch the same plan. */
+enum { PO_CHOL_LLT = 0, PO_CHOL_LDLT = 1 };
+int po_sparse_chol_set_factorization(po_sparse_chol h, int kind);
+int po_sparse_chol_get_factorization(po_sparse_chol h, int *kind);
+/* inertia = {positive, negative, replaced} pivots of the last factorization, counted on the device; the three sum to
+ * size.  PO_ERR_ARG before a factorization and on an analysis-only handle.  DIFFERENCE between the kinds: a
+ * PO_CHOL_LLT factorization that replaced no pivot (*info == 0) reports {size, 0, 0}; one that did is PO_ERR_ARG with
+ * a message, because the Cholesky kernels report the first such pivot and do not count the others (they are the
+ * kernels of the handles that never heard of a kind, unchanged). */
+int po_sparse_chol_inertia(po_sparse_chol h, int64_t inertia[3]);
 /* solve, ParOptSparseCholesky.h:44, for nrhs right-hand sides in place, column j at x + j * ldx */
 int po_sparse_chol_solve(po_sparse_chol h, double *x, int nrhs, int64_t ldx);
 int po_sparse_chol_solve_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx);

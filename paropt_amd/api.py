@@ -1525,11 +1525,16 @@ class SparseCholesky:
     symmetric pattern in compressed columns, as a multifrontal factorization with dense fronts on the device.
 
     ctx=None gives an analysis-only object (no device).  order: "nd" (nested dissection), "amd" (accepted, gets the
-    same nested dissection), "natural" (the identity, or `perm` with perm[new] = old)."""
+    same nested dissection), "natural" (the identity, or `perm` with perm[new] = old).
+
+    factorization: "llt" (Cholesky, the default) or "ldlt": L S L^T = P A P^T with S = diag(+-1) and NO pivoting, for
+    symmetric quasi-definite matrices ([[E, B^T], [B, -F]] with E, F SPD), which have it under every permutation.  For
+    a general indefinite matrix it is only as good as its pivots."""
 
     ORDERS = {"natural": 0, "amd": 1, "nd": 2}
+    FACTORIZATIONS = {"llt": 0, "ldlt": 1}
 
-    def __init__(self, ctx, size, colp, rows, order="nd", perm=None):
+    def __init__(self, ctx, size, colp, rows, order="nd", perm=None, factorization="llt"):
         self.ctx = ctx
         self._colp = np.ascontiguousarray(colp, dtype=np.intc)
         self._rows = np.ascontiguousarray(rows, dtype=np.intc)
@@ -1561,10 +1566,34 @@ class SparseCholesky:
         self.snode_first = arr(ptrs[1], self.num_snodes + 1)
         self.snode_parent = arr(ptrs[2], self.num_snodes)
         self.snode_level = arr(ptrs[3], self.num_snodes)
+        if factorization != "llt":
+            self.set_factorization(factorization)
 
     @property
     def handle(self):
         return self._h
+
+    def set_factorization(self, kind):
+        """ "llt" or "ldlt" (or PO_CHOL_LLT = 0 / PO_CHOL_LDLT = 1), read by the next factor(); allowed at any time,
+        also on an analysis-only object."""
+        if isinstance(kind, str):
+            if kind not in self.FACTORIZATIONS:
+                raise ValueError("factorization must be one of %s" % sorted(self.FACTORIZATIONS))
+            kind = self.FACTORIZATIONS[kind]
+        check(lib.po_sparse_chol_set_factorization(self._h, int(kind)))
+
+    @property
+    def factorization(self):
+        kind = C.c_int()
+        check(lib.po_sparse_chol_get_factorization(self._h, C.byref(kind)))
+        return {v: k for k, v in self.FACTORIZATIONS.items()}[kind.value]
+
+    def inertia(self):
+        """(positive, negative, replaced) pivots of the last factor(); they sum to size.  An "llt" factorization that
+        replaced no pivot gives (size, 0, 0); one that did raises (its kernels do not count them)."""
+        out = (C.c_int64 * 3)()
+        check(lib.po_sparse_chol_inertia(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def packing(self):
         """The packed groups of tiny fronts (po_sparse_chol_packing): a dict with tiny (the order up to which a front
@@ -1619,7 +1648,7 @@ class SparseCholesky:
 
     def factor(self):
         """0, or 1 + the permuted index of the first non-positive pivot (it is replaced by 1 and the factorization
-        finishes)."""
+        finishes).  With "ldlt": of the first pivot that is exactly zero or NaN."""
         info = C.c_int()
         check(lib.po_sparse_chol_factor(self._h, C.byref(info)))
         return info.value

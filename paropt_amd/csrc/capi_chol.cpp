@@ -64,7 +64,22 @@ int po_sparse_chol_factor(po_sparse_chol h, int *info) {
   PO_CHECK_NUMERIC(h);
   return h->c->factor(info);
 }
-// solve, ParOptSparseCholesky.h:44
+// no counterpart in the reference: L S L^T for quasi-definite matrices (paropt_amd.h, "FACTORIZATION KIND")
+int po_sparse_chol_set_factorization(po_sparse_chol h, int kind) {
+  PO_CHECK_PTR(h);
+  return h->c->setFactorization(kind);
+}
+int po_sparse_chol_get_factorization(po_sparse_chol h, int *kind) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(kind);
+  *kind = h->c->factorization();
+  return PO_OK;
+}
+int po_sparse_chol_inertia(po_sparse_chol h, int64_t inertia[3]) {
+  PO_CHECK_NUMERIC(h);
+  PO_CHECK_PTR(inertia);
+  return h->c->inertia(inertia);
+}
 int po_sparse_chol_solve(po_sparse_chol h, double *x, int nrhs, int64_t ldx) {
   PO_CHECK_NUMERIC(h);
   if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(x);

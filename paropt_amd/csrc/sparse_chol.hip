@@ -103,35 +103,76 @@ __global__ __launch_bounds__(128) void chol_assemble_kernel(CholDev d, const int
   }
 }
 
+// The flag block, four ints: [0] a pivot was replaced, [1] the smallest permuted index of one, and from the signed
+// forms only [2] negative pivots (chol_count_negative_kernel), [3] replaced pivots.  Integer atomics: whatever the
+// order, the same block.
 __device__ inline void flag_pivot(int *flag, int index) {
   flag[0] = 1;
   atomicMin(&flag[1], index);  // (the smallest index wins whatever the order: deterministic)
 }
 
+// SIGNED FORMS (kSigned, PO_CHOL_LDLT): P A P^T = L S L^T with S = diag(+-1) and a positive diagonal of L.  Column k:
+// s_k = sign(piv), l_kk = sqrt|piv|, l_ik = a_ik / (s_k l_kk), a_ij -= l_ik (s_k l_jk).  In every kernel s_k sits on
+// the COLUMN operand l_jk (here F[k][j], the triangle D of chol_trsm_kernel, Cs of chol_update_kernel, F[tri(j, k)]
+// of the packed kernel), so with all signs + every form does the unsigned form's operations on the same values.
+// A pivot that is zero or NaN is flagged and replaced by +1.  sgn[index0 + k] = s_k is written by the one thread that
+// forms the pivot.  The unsigned instantiations are the code as it was, instruction for instruction: they do not
+// count the pivots they replace (one more atomic on that never-taken path was measured at + 1.3 % on the
+// factorization of the 300 x 300 grid, HISTORY.md R22).
+__device__ inline double signed_pivot(double &piv, int *flag, int index, double *sgn, bool writer) {
+  double sk = 1.0;
+  if (!(piv > 0.0 || piv < 0.0)) {
+    if (writer) {
+      flag_pivot(flag, index);
+      atomicAdd(&flag[3], 1);
+    }
+    piv = 1.0;
+  } else if (piv < 0.0) {
+    sk = -1.0;
+    piv = -piv;
+  }
+  if (writer) sgn[index] = sk;
+  return sk;
+}
+
 // Partial Cholesky of the first s columns of the m x m lower triangle F (column-major, kLdsLd) in LDS by ONE
 // wavefront.  A non-positive (or NaN) pivot is flagged and replaced by 1, as chol_front_dense_kernel does.
-__device__ inline void lds_partial_chol(double *F, int m, int s, int index0, int *flag) {
+template <bool kSigned>
+__device__ inline void lds_partial_chol(double *F, int m, int s, int index0, int *flag, double *sgn) {
   const int tid = threadIdx.x, i = tid & 31, half = tid >> 5;
   for (int k = 0; k < s; k++) {
     double piv = F[k * kLdsLd + k];
-    if (!(piv > 0.0)) {
+    double sk = 1.0;
+    if (kSigned) {
+      sk = signed_pivot(piv, flag, index0 + k, sgn, tid == 0);
+    } else if (!(piv > 0.0)) {
       if (tid == 0) flag_pivot(flag, index0 + k);
       piv = 1.0;
     }
     const double r = sqrt(piv);
     __syncthreads();
     if (tid == 0) F[k * kLdsLd + k] = r;
-    if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= r;
+    if (kSigned) {
+      if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= sk * r;
+    } else {
+      if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= r;
+    }
     __syncthreads();
     if (i > k && i < m) {
       const double lik = F[k * kLdsLd + i];
-      for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * F[k * kLdsLd + j];
+      if (kSigned) {
+        for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * (sk * F[k * kLdsLd + j]);
+      } else {
+        for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * F[k * kLdsLd + j];
+      }
     }
     __syncthreads();
   }
 }
 
-__global__ __launch_bounds__(64) void chol_small_kernel(CholDev d, const int *__restrict__ list, int *flag) {
+template <bool kSigned>
+__global__ __launch_bounds__(64) void chol_small_kernel(CholDev d, const int *__restrict__ list, int *flag,
+                                                        double *sgn) {
   __shared__ double F[kCholSmall * kLdsLd];
   const int J = list[blockIdx.x];
   const int first = d.first[J], s = d.first[J + 1] - first, b = d.nb[J], m = s + b;
@@ -143,14 +184,16 @@ __global__ __launch_bounds__(64) void chol_small_kernel(CholDev d, const int *__
     if (row >= col) F[col * kLdsLd + row] = *front_entry(P, ld, U, uld, s, row, col);
   }
   __syncthreads();
-  lds_partial_chol(F, m, s, first, flag);
+  lds_partial_chol<kSigned>(F, m, s, first, flag, sgn);
   for (int idx = tid; idx < m * m; idx += 64) {
     const int col = idx / m, row = idx % m;
     if (row >= col) *front_entry(P, ld, U, uld, s, row, col) = F[col * kLdsLd + row];
   }
 }
 
-__global__ __launch_bounds__(64) void chol_diag_kernel(CholDev d, const int *__restrict__ list, int kb, int *flag) {
+template <bool kSigned>
+__global__ __launch_bounds__(64) void chol_diag_kernel(CholDev d, const int *__restrict__ list, int kb, int *flag,
+                                                       double *sgn) {
   __shared__ double F[kCholNB * kLdsLd];
   const int J = list[blockIdx.x];
   const int first = d.first[J], s = d.first[J + 1] - first, ld = d.ld[J];
@@ -162,7 +205,7 @@ __global__ __launch_bounds__(64) void chol_diag_kernel(CholDev d, const int *__r
     if (row >= col) F[col * kLdsLd + row] = P[(int64_t)col * ld + row];
   }
   __syncthreads();
-  lds_partial_chol(F, w, w, first + k0, flag);
+  lds_partial_chol<kSigned>(F, w, w, first + k0, flag, sgn);
   for (int idx = tid; idx < w * w; idx += 64) {
     const int col = idx / w, row = idx % w;
     if (row >= col) P[(int64_t)col * ld + row] = F[col * kLdsLd + row];
@@ -179,8 +222,12 @@ __device__ inline int tile_front(const int *__restrict__ tab, int nact, int t) {
   return lo;
 }
 
+// kSigned: the rows solve against S L11^T -- column k of the triangle in LDS is s_k times that of L11, the diagonal
+// included, and the substitution below is the unsigned one.
+template <bool kSigned>
 __global__ __launch_bounds__(kCholTile) void chol_trsm_kernel(CholDev d, const int *__restrict__ list,
-                                                              const int *__restrict__ tab, int nact, int kb) {
+                                                              const int *__restrict__ tab, int nact, int kb,
+                                                              const double *__restrict__ sgn) {
   __shared__ double D[kCholNB * kLdsLd], X[kCholTile * kLdsLd];
   const int t = blockIdx.x, a = tile_front(tab, nact, t), J = list[a];
   const int s = d.first[J + 1] - d.first[J], m = s + d.nb[J], ld = d.ld[J];
@@ -190,7 +237,10 @@ __global__ __launch_bounds__(kCholTile) void chol_trsm_kernel(CholDev d, const i
   for (int idx = tid; idx < kCholNB * kCholNB; idx += kCholTile) {
     const int col = idx / kCholNB, row = idx % kCholNB;
     double v = row == col ? 1.0 : 0.0;  // (identity outside a partial block)
-    if (col < w && row < w && row >= col) v = P[(int64_t)col * ld + k0 + row];
+    if (col < w && row < w && row >= col) {
+      v = P[(int64_t)col * ld + k0 + row];
+      if (kSigned) v *= sgn[d.first[J] + k0 + col];
+    }
     D[col * kLdsLd + row] = v;
   }
   __syncthreads();
@@ -206,8 +256,11 @@ __global__ __launch_bounds__(kCholTile) void chol_trsm_kernel(CholDev d, const i
   }
 }
 
+// kSigned: C -= A S B^T, the signs multiply the column operand Cs as it is loaded.
+template <bool kSigned>
 __global__ __launch_bounds__(256) void chol_update_kernel(CholDev d, const int *__restrict__ list,
-                                                          const int *__restrict__ tab, int nact, int kb) {
+                                                          const int *__restrict__ tab, int nact, int kb,
+                                                          const double *__restrict__ sgn) {
   __shared__ double Rs[kCholNB * kOpLd], Cs[kCholNB * kOpLd];
   const int t = blockIdx.x, a = tile_front(tab, nact, t);
   const int ti = t - tab[a], tj = blockIdx.y;
@@ -226,7 +279,9 @@ __global__ __launch_bounds__(256) void chol_update_kernel(CholDev d, const int *
       const int kk = kq + 4 * it;
       const bool live = kk < w;
       Rs[kk * kOpLd + row] = (live && R0 + row < m) ? Pk[(int64_t)kk * ld + R0 + row] : 0.0;
-      Cs[kk * kOpLd + row] = (live && C0 + row < m) ? Pk[(int64_t)kk * ld + C0 + row] : 0.0;
+      double cv = (live && C0 + row < m) ? Pk[(int64_t)kk * ld + C0 + row] : 0.0;
+      if (kSigned && live) cv *= sgn[d.first[J] + k0 + kk];
+      Cs[kk * kOpLd + row] = cv;
     }
   }
   __syncthreads();
@@ -326,9 +381,10 @@ __device__ inline void pack_load_panel(double *F, const double *P, int ld, int s
   }
 }
 
+template <bool kSigned>
 __global__ __launch_bounds__(kPackLanes) void chol_pack_factor_kernel(CholDev d, const int *__restrict__ gfirst,
                                                                       const int *__restrict__ groot, int ngroup,
-                                                                      int *flag) {
+                                                                      int *flag, double *sgn) {
 #pragma clang fp contract(off)
   __shared__ double Fs[kPackLanes * kPackFactorSlot];
   const int g = blockIdx.x * kPackLanes + threadIdx.x;
@@ -368,16 +424,27 @@ __global__ __launch_bounds__(kPackLanes) void chol_pack_factor_kernel(CholDev d,
     }
     for (int k = 0; k < s; k++) {
       double piv = F[tri(k, k)];
-      if (!(piv > 0.0)) {
+      double sk = 1.0;
+      if (kSigned) {
+        sk = signed_pivot(piv, flag, first + k, sgn, true);
+      } else if (!(piv > 0.0)) {
         flag_pivot(flag, first + k);
         piv = 1.0;
       }
       const double r = sqrt(piv);
       F[tri(k, k)] = r;
-      for (int i = k + 1; i < m; i++) F[tri(i, k)] /= r;
+      if (kSigned) {
+        for (int i = k + 1; i < m; i++) F[tri(i, k)] /= sk * r;
+      } else {
+        for (int i = k + 1; i < m; i++) F[tri(i, k)] /= r;
+      }
       for (int i = k + 1; i < m; i++) {
         const double lik = F[tri(i, k)];
-        for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, F[tri(j, k)], F[tri(i, j)]);
+        if (kSigned) {
+          for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, sk * F[tri(j, k)], F[tri(i, j)]);
+        } else {
+          for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, F[tri(j, k)], F[tri(i, j)]);
+        }
       }
     }
     for (int col = 0; col < m; col++) {
@@ -537,6 +604,32 @@ __global__ void chol_permute_kernel(double *Y, int64_t ldy, double *x, int64_t l
   } else {
     Y[p + r * ldy] = x[perm[p] + r * ldx];
   }
+}
+
+// The negative pivots of a signed factorization, from its signs: one atomic a workgroup.  (An atomic a pivot, from
+// the thread that forms it, was measured first: half a million of them on one address cost the tridiagonal matrix
+// of a million unknowns 5 ms, three times its factorization.)
+__global__ __launch_bounds__(256) void chol_count_negative_kernel(const double *__restrict__ sgn, int n, int *flag) {
+  __shared__ int part[4];
+  int count = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    count += sgn[i] < 0.0 ? 1 : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = count;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int total = part[0] + part[1] + part[2] + part[3];
+    if (total > 0) atomicAdd(&flag[2], total);
+  }
+}
+
+// y_k <- s_k y_k between the forward and the backward sweep of a signed factorization (L S L^T x = b)
+__global__ void chol_sign_kernel(double *Y, int64_t ldy, const double *__restrict__ sgn, int n, int nrhs) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)n * nrhs) return;
+  const int p = (int)(idx % n), r = (int)(idx / n);
+  Y[p + r * ldy] *= sgn[p];
 }
 
 __device__ inline void load_triangle(double *D, const double *P, int ld, int w) {
@@ -802,6 +895,7 @@ SparseChol::~SparseChol() {
   dfree(avals);
   dfree(xbuf);
   dfree(d_flag);
+  dfree(d_sign);
   dfree(d_perm);
   dfree(d_first);
   dfree(d_b);
@@ -935,23 +1029,52 @@ int SparseChol::factorAssembled(int *flag) {
     return PO_ERR_ARG;
   }
   PO_HIP(hipSetDevice(ctx->device));
-  PO_TRY(launchFactor(flag));
+  PO_TRY(launchFactor<false>(flag));
   have_values = false;
   factored = true;
+  factored_kind = PO_CHOL_LLT;
+  have_inertia = uncounted = false;
+  return PO_OK;
+}
+
+int SparseChol::setFactorization(int k) {
+  if (k != PO_CHOL_LLT && k != PO_CHOL_LDLT) {
+    set_error("sparse Cholesky: unknown factorization kind %d (PO_CHOL_LLT = 0, PO_CHOL_LDLT = 1)", k);
+    return PO_ERR_ARG;
+  }
+  if (k == PO_CHOL_LDLT && ctx && !d_sign) {
+    PO_HIP(hipSetDevice(ctx->device));
+    PO_HIP(hipMalloc((void **)&d_sign, ((size_t)sym.n + 4) * sizeof(double)));
+  }
+  kind = k;
+  return PO_OK;
+}
+
+int SparseChol::inertia(int64_t out[3]) const {
+  if (!have_inertia) {
+    set_error(uncounted ? "sparse Cholesky: the last L L^T factorization replaced non-positive pivots and does not "
+                          "count them (factor() reported the first); PO_CHOL_LDLT gives the inertia of such a matrix"
+                        : "sparse Cholesky: inertia() before factor()");
+    return PO_ERR_ARG;
+  }
+  for (int i = 0; i < 3; i++) out[i] = inertia_[i];
   return PO_OK;
 }
 
 // every level of the numeric factorization, queued on the stream; pivots are flagged in `flag` (device)
+template <bool kSigned>
 int SparseChol::launchFactor(int *flag) {
   hipStream_t st = ctx->stream;
   int *const d_flag = flag;
+  double *const sgn = kSigned ? d_sign : nullptr;
   const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
                      d_below, d_rel, d_child_ptr, d_child, L, arena};
   for (int l = 0; l < sym.nlev; l++) {
     const CholLevelPlan plan = chol_level_plan(sym, l);
     if (plan.ngroup > 0) {  // (independent of the level's unpacked fronts)
-      hipLaunchKernelGGL(chol_pack_factor_kernel, dim3((plan.ngroup + kPackLanes - 1) / kPackLanes), dim3(kPackLanes),
-                         0, st, d, d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, d_flag);
+      hipLaunchKernelGGL(chol_pack_factor_kernel<kSigned>, dim3((plan.ngroup + kPackLanes - 1) / kPackLanes),
+                         dim3(kPackLanes), 0, st, d, d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l],
+                         plan.ngroup, d_flag, sgn);
     }
     if (plan.nchunk > 0) {
       hipLaunchKernelGGL(chol_assemble_kernel, dim3(plan.nchunk), dim3(128), 0, st, d, d_chunk_sn + sym.chunk_ptr[l],
@@ -959,20 +1082,23 @@ int SparseChol::launchFactor(int *flag) {
     }
     const int nsmall = plan.nsmall;
     if (nsmall > 0) {
-      hipLaunchKernelGGL(chol_small_kernel, dim3(nsmall), dim3(64), 0, st, d, d_lev_sn + sym.lev_ptr[l], d_flag);
+      hipLaunchKernelGGL(chol_small_kernel<kSigned>, dim3(nsmall), dim3(64), 0, st, d, d_lev_sn + sym.lev_ptr[l],
+                         d_flag, sgn);
     }
     const int *big = d_lev_sn + sym.lev_ptr[l] + nsmall;
     for (int step = sym.step_ptr[l]; step < sym.step_ptr[l + 1]; step++) {
       const int kb = step - sym.step_ptr[l], nact = sym.step_nact[step];
       const int *htab = &sym.tab[sym.step_tab[step]];
       const int *dtab = d_tab + sym.step_tab[step];
-      hipLaunchKernelGGL(chol_diag_kernel, dim3(nact), dim3(64), 0, st, d, big, kb, d_flag);
+      hipLaunchKernelGGL(chol_diag_kernel<kSigned>, dim3(nact), dim3(64), 0, st, d, big, kb, d_flag, sgn);
       const int total = htab[nact];
       if (total > 0) {
         int most = 0;
         for (int a = 0; a < nact; a++) most = std::max(most, htab[a + 1] - htab[a]);
-        hipLaunchKernelGGL(chol_trsm_kernel, dim3(total), dim3(kCholTile), 0, st, d, big, dtab, nact, kb);
-        hipLaunchKernelGGL(chol_update_kernel, dim3(total, most), dim3(256), 0, st, d, big, dtab, nact, kb);
+        hipLaunchKernelGGL(chol_trsm_kernel<kSigned>, dim3(total), dim3(kCholTile), 0, st, d, big, dtab, nact, kb,
+                           (const double *)sgn);
+        hipLaunchKernelGGL(chol_update_kernel<kSigned>, dim3(total, most), dim3(256), 0, st, d, big, dtab, nact, kb,
+                           (const double *)sgn);
       }
     }
     PO_HIP(hipGetLastError());
@@ -988,19 +1114,36 @@ int SparseChol::factor(int *info) {
   }
   PO_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  // flag[0] = 0, flag[1] = 0x7f7f7f7f (above every index)
-  PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), st));
-  PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-  PO_TRY(launchFactor(d_flag));
+  // flag[0] = 0, flag[1] = 0x7f7f7f7f (above every index), the counts flag[2] = flag[3] = 0
+  PO_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), st));
+  PO_HIP(hipMemsetAsync(d_flag + 1, 0x7f, sizeof(int), st));
+  const bool ldlt = kind == PO_CHOL_LDLT;
+  PO_TRY(ldlt ? launchFactor<true>(d_flag) : launchFactor<false>(d_flag));
+  if (ldlt && sym.n > 0) {
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)sym.n + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(chol_count_negative_kernel, dim3(blocks), dim3(256), 0, st, (const double *)d_sign, sym.n,
+                       d_flag);
+    PO_HIP(hipGetLastError());
+  }
   int flag[4] = {0, 0, 0, 0};
   PO_HIP(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
   PO_HIP(hipStreamSynchronize(st));
   have_values = false;
   factored = true;
+  factored_kind = kind;
+  // (the counts came with the flag read: nothing of size n goes to the host).  The unsigned kernels count nothing:
+  // a Cholesky factorization that replaced no pivot has n positive ones, one that did has no inertia to report.
+  inertia_[1] = ldlt ? flag[2] : 0;
+  inertia_[2] = ldlt ? flag[3] : 0;
+  inertia_[0] = (int64_t)sym.n - inertia_[1] - inertia_[2];
+  have_inertia = ldlt || flag[0] == 0;
+  uncounted = !have_inertia;
   if (flag[0] != 0) {
     // like LAPACK's info behind the reference's factor() (src/ParOptSparseCholesky.cpp:631): the pivot was
     // replaced by 1 and the factorization finished, the caller decides
-    set_error("sparse Cholesky: non-positive pivot at permuted index %d", flag[1]);
+    set_error(ldlt ? "sparse Cholesky (LDLT): zero or NaN pivot at permuted index %d"
+                   : "sparse Cholesky: non-positive pivot at permuted index %d",
+              flag[1]);
     if (info) *info = 1 + flag[1];
   }
   return PO_OK;
@@ -1038,6 +1181,9 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
         hipLaunchKernelGGL(chol_fwd_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy,
                            nr);
       }
+    }
+    if (factored_kind == PO_CHOL_LDLT) {
+      hipLaunchKernelGGL(chol_sign_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, (const double *)d_sign, sym.n, nr);
     }
     for (int l = sym.nlev - 1; l >= 0; l--) {
       const CholLevelPlan plan = chol_level_plan(sym, l);

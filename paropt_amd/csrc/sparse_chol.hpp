@@ -124,13 +124,22 @@ class SparseChol {
   int setValuesDevice(const double *dvals);
   int setValuesHost(int64_t n, const int *colp, const int *rows, const double *vals);
   int factor(int *info);
+  // PO_CHOL_LLT (default) or PO_CHOL_LDLT: P A P^T = L S L^T, S = diag(+-1), for symmetric quasi-definite matrices
+  // (no pivoting; sparse_chol.hip, "signed forms").  Read by the next factor(); a solve follows the kind of the
+  // factorization it solves with.  The first LDLT allocates the sign array (n doubles, elimination order).
+  int setFactorization(int kind);
+  int factorization() const { return kind; }
+  // {positive, negative, replaced} pivots of the last factor(), counted on the device and read with its flag.  LLT:
+  // {n, 0, 0}, or PO_ERR_ARG after a factorization that replaced pivots (its kernels do not count them)
+  int inertia(int64_t out[3]) const;
   int solveDevice(double *dx, int nrhs, int64_t ldx);
   int solveHost(double *x, int nrhs, int64_t ldx);
   // The interior point's side (csr.cpp: CsrSparse).  beginAssembly queues the zeroing of L and hands it out: the
   // caller writes lower(P A P^T) at the offsets of asm_dst with kernels of its own on the same stream.
   // factorAssembled queues the numeric factorization of what was written and returns without a host read: a
   // non-positive pivot is replaced by 1, flag[0] is set and flag[1] takes the smallest permuted index (the caller
-  // sets flag[0] = 0 and flag[1] above every index beforehand, and reads them when it likes).
+  // sets flag[0] = 0 and flag[1] above every index beforehand, and reads them when it likes).  Always the unsigned
+  // (L L^T) kernels.
   int beginAssembly(double **Lout);
   int factorAssembled(int *flag);
   // Triangular sweeps over a panel given as a HOST table of nv device vectors that are already in the elimination
@@ -140,8 +149,12 @@ class SparseChol {
 
  private:
   int scatter(const int *d_ptr, const int64_t *d_dst, const int *d_src, int64_t ndst, const double *dvals);
+  template <bool kSigned>
   int launchFactor(int *flag);
-  bool have_values = false, factored = false;
+  bool have_values = false, factored = false, have_inertia = false, uncounted = false;
+  int kind = 0, factored_kind = 0;
+  int64_t inertia_[3] = {0, 0, 0};
+  double *d_sign = nullptr;  // s_k = +-1.0 in elimination order (LDLT)
   double *L = nullptr, *arena = nullptr, *Y = nullptr, *avals = nullptr, *xbuf = nullptr;
   int64_t xbuf_cap = 0;
   int *d_flag = nullptr;

@@ -294,6 +294,9 @@ SIGNATURES = {
     "po_sparse_chol_set_values": (C.c_int, [po_sparse_chol, C.c_int64, c_int_p, c_int_p, c_double_p]),
     "po_sparse_chol_set_values_device": (C.c_int, [po_sparse_chol, C.c_void_p]),
     "po_sparse_chol_factor": (C.c_int, [po_sparse_chol, c_int_p]),
+    "po_sparse_chol_set_factorization": (C.c_int, [po_sparse_chol, C.c_int]),
+    "po_sparse_chol_get_factorization": (C.c_int, [po_sparse_chol, C.POINTER(C.c_int)]),
+    "po_sparse_chol_inertia": (C.c_int, [po_sparse_chol, c_i64_p]),
     "po_sparse_chol_solve": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
     "po_sparse_chol_solve_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
     "po_sparse_chol_info": (C.c_int, [po_sparse_chol, c_i64_p]),

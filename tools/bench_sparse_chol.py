@@ -7,6 +7,11 @@ repeats each, timed are
 One JSON line per size.
 
     python tools/bench_sparse_chol.py [--sizes 150 300] [--repeats 3] [--inner 3] [--out file.jsonl]
+
+--factorization ldlt runs SparseCholesky in its L S L^T mode (the signed kernels and the sign pass of the solve): on the
+same SPD S above, and on the --packing matrices with the diagonal negated at every odd-coloured unknown (red/black:
+symmetric quasi-definite, half the pivots negative).  Its lines carry "factorization": "ldlt"; without the flag the
+output is what it was.
 """
 import argparse
 import json
@@ -21,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def run(ctx, nx, repeats, inner):
+def run(ctx, nx, repeats, inner, factorization="llt"):
     import scipy.sparse as sp
     import torch
 
@@ -68,6 +73,8 @@ def run(ctx, nx, repeats, inner):
     S.sort_indices()
     t0 = time.perf_counter()
     chol = pa.SparseCholesky(ctx, w, S.indptr, S.indices)
+    if factorization != "llt":
+        chol.set_factorization(factorization)
     t_setup = time.perf_counter() - t0
     dev = torch.device("cuda", ctx.device())
     svals = torch.from_numpy(np.ascontiguousarray(S.data)).to(dev)
@@ -110,12 +117,15 @@ def run(ctx, nx, repeats, inner):
         rec["chol_factor_ms"].append(timed(chol_factor))
         rec["quasidef_apply_ms"].append(timed(lambda: pa.quasidef_apply(prob, x, d, c, bx, bw, yx, yw)))
         rec["chol_solve_ms"].append(timed(chol_solve))
+    if factorization != "llt":
+        rec["factorization"] = factorization
+        rec["inertia"] = chol.inertia()
     rec["factor_ratio_row_over_multifrontal"] = [a / b for a, b in zip(rec["quasidef_factor_ms"], rec["chol_factor_ms"])]
     rec["solve_ratio_row_over_multifrontal"] = [a / b for a, b in zip(rec["quasidef_apply_ms"], rec["chol_solve_ms"])]
     return rec
 
 
-def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16):
+def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16, factorization="llt"):
     """the public class with its packed groups of tiny fronts switched off (cap 0: a workgroup per front) and with
     groups of at most `cap` fronts, alternating: factor and a solve of one right-hand side"""
     import torch
@@ -133,6 +143,8 @@ def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16):
         lib.po_debug_set_switch(38, value)  # core.hpp SW_CHOL_PACK, read by the analysis
         try:
             chol[key] = pa.SparseCholesky(ctx, n, colp, rows)
+            if factorization != "llt":
+                chol[key].set_factorization(factorization)
         finally:
             lib.po_debug_set_switch(38, -1)
 
@@ -163,6 +175,9 @@ def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16):
            "kernel_forms": chol[packed].kernel_forms(),
            "bit_equal": bool(np.array_equal(sols["cap0"], sols[packed])),
            "chol_factor_ms": {k: [] for k in chol}, "chol_solve_ms": {k: [] for k in chol}}
+    if factorization != "llt":
+        rec["factorization"] = factorization
+        rec["inertia"] = {k: c.inertia() for k, c in chol.items()}
     for _ in range(repeats):
         for key, c in chol.items():
             rec["chol_factor_ms"][key].append(timed(lambda: factor(c)))
@@ -170,13 +185,17 @@ def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16):
     return rec
 
 
-def packing_patterns(tridiag_n, nx):
+def packing_patterns(tridiag_n, nx, quasi_definite=False):
     import scipy.sparse as sp
 
     T = sp.diags([-np.ones(tridiag_n - 1), np.full(tridiag_n, 2.5), -np.ones(tridiag_n - 1)], [-1, 0, 1]).tocsc()
     G = sp.kron(sp.eye(nx), sp.diags([-np.ones(nx - 1), np.full(nx, 2.25), -np.ones(nx - 1)], [-1, 0, 1]))
     G = (G + sp.kron(sp.diags([-np.ones(nx - 1), np.full(nx, 2.25), -np.ones(nx - 1)], [-1, 0, 1]), sp.eye(nx))).tocsc()
     for name, M in (("tridiagonal n=%d" % tridiag_n, T), ("5-point grid %dx%d" % (nx, nx), G)):
+        if quasi_definite:  # negate the diagonal at the odd colour of the red/black colouring
+            k = np.arange(M.shape[0])
+            odd = (k % 2 == 1) if M is T else ((k // nx + k % nx) % 2 == 1)
+            M = (M - 2.0 * sp.diags(np.where(odd, M.diagonal(), 0.0))).tocsc()
         M.sort_indices()
         yield name, M.shape[0], M.indptr, M.indices, M.data
 
@@ -189,6 +208,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="*", default=[150, 300])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--inner", type=int, default=3)
+    ap.add_argument("--factorization", choices=("llt", "ldlt"), default="llt")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import paropt_amd as pa
@@ -196,11 +216,12 @@ def main():
     ctx = pa.Context(0)
     lines = []
     for nx in a.sizes:
-        lines.append(json.dumps(run(ctx, nx, a.repeats, a.inner)))
+        lines.append(json.dumps(run(ctx, nx, a.repeats, a.inner, factorization=a.factorization)))
         print(lines[-1], flush=True)
     if a.packing:
-        for name, n, colp, rows, vals in packing_patterns(*a.packing):
-            lines.append(json.dumps(run_packing(ctx, name, n, colp, rows, vals, a.repeats, a.inner)))
+        for name, n, colp, rows, vals in packing_patterns(*a.packing, quasi_definite=a.factorization == "ldlt"):
+            lines.append(json.dumps(run_packing(ctx, name, n, colp, rows, vals, a.repeats, a.inner,
+                                                factorization=a.factorization)))
             print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:
