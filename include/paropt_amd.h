@@ -73,9 +73,11 @@ int po_ctx_sync_counters(po_ctx ctx, int64_t *flag_waits, int64_t *flag_timeouts
  * iteration-level roofline is (bytes of the timed iterations) / time / HBM peak. */
 int po_ctx_algorithmic_bytes(po_ctx ctx, double *total, double *user);
 /* Leak check: device vectors currently alive in this process (every ParOptVec, the panels of the quasi-Newton
- * objects, the work vectors of the solvers) and the HBM bytes behind them.  The reference's intrusive
- * reference counts (src/ParOptVec.h:28-47) are kept, so after the last decref / destroy both return to their
- * values before the objects were made. */
+ * objects, the work vectors of the solvers) and the HBM bytes behind them.  `bytes` also counts every device array of
+ * the sparse factors (the CSR sparse constraints' tables, factor and dense-column panels; po_sparse_chol's L, arena,
+ * tables, sign array and solve buffer); `vectors` counts vectors only.  The reference's intrusive reference counts
+ * (src/ParOptVec.h:28-47) are kept, so after the last decref / destroy both return to their values before the
+ * objects were made. */
 int po_live_objects(int64_t *vectors, int64_t *bytes);
 /* pinned host mirrors (po_vec_get_array) currently alive in this process */
 int po_live_host_mirrors(int64_t *mirrors);

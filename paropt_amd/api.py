@@ -15,7 +15,8 @@ from .lib import check, lib
 
 
 def live_objects():
-    """(device vectors alive in this process, HBM bytes behind them): the leak check of the C ABI."""
+    """(device vectors alive in this process, HBM bytes behind them and behind the sparse factors' arrays): the leak
+    check of the C ABI."""
     a, b = C.c_int64(), C.c_int64()
     check(lib.po_live_objects(C.byref(a), C.byref(b)))
     return a.value, b.value

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <functional>
 #include <string>
 #include <vector>
@@ -137,6 +138,61 @@ struct Vec {
   double *h;       // pinned host mirror (lazy)
   int h_live = 0;  // the mirror has been handed out (po_vec_get_array) and is the authoritative copy: every
                    // C-ABI operation on the vector uploads it first / downloads the result (po_vec_release_array)
+};
+
+// HBM bytes behind everything alive that po_live_objects counts: device vectors (qn.cpp) and DevArrays.  Inline, so
+// that code using a DevArray links without qn.cpp.
+inline std::atomic<long long> &live_bytes() {
+  static std::atomic<long long> bytes(0);
+  return bytes;
+}
+
+// An owning device array: move-only, freed by its destructor, its bytes counted in live_bytes().  alloc() gives
+// exactly `count` elements (callers add their own padding) and zeroes them only when asked; upload() gives
+// size() + 4 elements, zero-filled, then the copy -- kernels may read a few elements past a table's end.  Both
+// replace whatever the array held.  Synchronous calls only (hipMalloc, hipMemset, hipMemcpy, hipFree).
+template <class T>
+class DevArray {
+ public:
+  DevArray() = default;
+  DevArray(const DevArray &) = delete;
+  DevArray &operator=(const DevArray &) = delete;
+  DevArray(DevArray &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  DevArray &operator=(DevArray &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, n_ = o.n_;
+      o.p_ = nullptr, o.n_ = 0;
+    }
+    return *this;
+  }
+  ~DevArray() { reset(); }
+  void reset() {
+    if (!p_) return;
+    (void)hipFree(p_);
+    live_bytes() -= (long long)(n_ * sizeof(T));
+    p_ = nullptr, n_ = 0;
+  }
+  int alloc(size_t count, bool zero) {
+    reset();
+    PO_HIP(hipMalloc((void **)&p_, count * sizeof(T)));
+    n_ = count;
+    live_bytes() += (long long)(n_ * sizeof(T));
+    if (zero) PO_HIP(hipMemset(p_, 0, count * sizeof(T)));
+    return PO_OK;
+  }
+  int upload(const std::vector<T> &src) {
+    PO_TRY(alloc(src.size() + 4, true));
+    if (!src.empty()) PO_HIP(hipMemcpy(p_, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PO_OK;
+  }
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+  size_t size() const { return n_; }  // elements allocated
+
+ private:
+  T *p_ = nullptr;
+  size_t n_ = 0;
 };
 
 // A small table of raw device pointers passed by value as a kernel argument.

@@ -648,85 +648,19 @@ static int csr_analyse_impl(int64_t n64, int64_t w64, const int *rowp, const int
 // ---------------------------------------------------------------------------------------------------
 CsrSparse::CsrSparse(Ctx *c, int64_t n_, int64_t w_) : ctx(c), n(n_), w(w_), nnz(0) {}
 
-namespace {
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-template <class T>
-int upload(T *&dst, const std::vector<T> &src) {
-  dfree(dst);
-  const size_t bytes = (src.size() + 4) * sizeof(T);
-  PO_HIP(hipMalloc((void **)&dst, bytes));
-  PO_HIP(hipMemset(dst, 0, bytes));
-  if (!src.empty()) PO_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return PO_OK;
-}
-}  // namespace
-
 CsrSparse::~CsrSparse() {
-  if (vals != data) dfree(vals);
-  vals = nullptr;
-  dfree(data);
-  dfree(d_rowp);
-  dfree(d_cols);
-  dfree(d_src);
-  dfree(d_colp);
-  dfree(d_rowsT);
-  dfree(d_srcT);
-  dfree(d_perm);
-  dfree(d_iperm);
-  dfree(d_Lrowp);
-  dfree(d_Lcols);
-  dfree(d_Ltp);
-  dfree(d_Ltrows);
-  dfree(d_Ltsrc);
-  dfree(d_ent_a);
-  dfree(d_ent_b);
-  dfree(d_ent_slot);
-  dfree(d_ent_off);
   delete mf;
-  dfree(d_fwd);
-  dfree(d_front_of);
-  dfree(d_front_end);
-  dfree(d_fstart);
-  dfree(d_fsize);
-  dfree(Lvals);
-  dfree(ones);
-  dfree(wwork);
-  dfree(d_flag);
-  (void)freeDense();
   if (cw) vec_decref(cw);
-}
-
-int CsrSparse::freeDense() {
-  dfree(Vd);
-  dfree(Yv);
-  dfree(Vind);
-  dfree(Kfac);
-  dfree(Zd);
-  dfree(part);
-  dfree(spanel);
-  dfree(d_dmask);
-  dfree(d_dcols);
-  dfree(d_dptr);
-  dfree(d_dpos);
-  dfree(d_dslot);
-  part_cap = spanel_cap = 0;
-  return PO_OK;
 }
 
 int CsrSparse::densePartials(int nv) {
   const int r = ndense();
-  if (nv <= part_cap) return PO_OK;
+  if (nv <= dense.part_cap) return PO_OK;
   PO_HIP(hipStreamSynchronize(ctx->stream));  // (grows a few times in the life of a pattern)
-  dfree(part);
-  dfree(Zd);
-  part_cap = 0;
-  PO_HIP(hipMalloc((void **)&part, ((size_t)dense_nb * r * nv + 4) * sizeof(double)));
-  PO_HIP(hipMalloc((void **)&Zd, ((size_t)r * nv + 4) * sizeof(double)));
-  part_cap = nv;
+  dense.part_cap = 0;
+  PO_TRY(dense.part.alloc((size_t)dense.nb * r * nv + 4, false));
+  PO_TRY(dense.Zd.alloc((size_t)r * nv + 4, false));
+  dense.part_cap = nv;
   return PO_OK;
 }
 
@@ -737,143 +671,105 @@ static int group_for(double avg) {
   return 64;
 }
 
-int CsrSparse::setPattern(const int *rowp, const int *cols) {
-  sym = CsrSymbolic();
-  PO_TRY(csr_analyse(n, w, rowp, cols, &sym, dense_min_rows, factor_kind));
-  nnz = sym.nnz;
+int CsrSparse::allocUser(const int *rowp, const int *cols) {
+  nnz = rowp[w];
   user_rowp.assign(rowp, rowp + w + 1);
   user_cols.assign(cols, cols + nnz);
   PO_HIP(hipSetDevice(ctx->device));
-  if (vals != data) dfree(vals);
-  vals = nullptr;
-  const size_t vbytes = ((size_t)nnz + 4) * sizeof(double);
-  if (adopt_data) {  // upgradeFromLight: the user-visible value array (and what the user wrote into it) stays
-    data = adopt_data;
-    adopt_data = nullptr;
-  } else {
-    dfree(data);
-    PO_HIP(hipMalloc((void **)&data, vbytes));
-    PO_HIP(hipMemset(data, 0, vbytes));
+  PO_TRY(data.alloc((size_t)nnz + 4, true));
+  vals = data;
+  cw = vec_new(ctx, w);
+  return cw ? PO_OK : PO_ERR_HIP;
+}
+
+int CsrSparse::analyse(const int *rowp, const int *cols) {
+  const int rc = csr_analyse(n, w, rowp, cols, &sym, dense_min_rows, factor_kind);
+  if (rc != PO_OK) {
+    sym = CsrSymbolic();
+    return rc;
   }
-  if (sym.identity_src) {
-    vals = data;
-  } else {
-    PO_HIP(hipMalloc((void **)&vals, vbytes));
-    PO_HIP(hipMemset(vals, 0, vbytes));
-  }
-  PO_TRY(upload(d_rowp, sym.rowp));
-  PO_TRY(upload(d_cols, sym.cols));
-  PO_TRY(upload(d_src, sym.src));
-  PO_TRY(upload(d_colp, sym.colp));
-  PO_TRY(upload(d_rowsT, sym.rowsT));
-  PO_TRY(upload(d_srcT, sym.srcT));
-  PO_TRY(upload(d_perm, sym.perm));
-  PO_TRY(upload(d_iperm, sym.iperm));
-  PO_TRY(upload(d_ent_a, sym.ent_a));
-  PO_TRY(upload(d_ent_b, sym.ent_b));
-  delete mf;
-  mf = nullptr;
-  dfree(Lvals);
+  PO_HIP(hipSetDevice(ctx->device));
+  PO_TRY(d_rowp.upload(sym.rowp));
+  PO_TRY(d_cols.upload(sym.cols));
+  PO_TRY(d_src.upload(sym.src));
+  PO_TRY(d_colp.upload(sym.colp));
+  PO_TRY(d_rowsT.upload(sym.rowsT));
+  PO_TRY(d_srcT.upload(sym.srcT));
+  PO_TRY(d_perm.upload(sym.perm));
+  PO_TRY(d_iperm.upload(sym.iperm));
+  PO_TRY(d_ent_a.upload(sym.ent_a));
+  PO_TRY(d_ent_b.upload(sym.ent_b));
   if (sym.factor_kind == PO_SPARSE_FACTOR_MULTIFRONTAL) {
     // the engine owns the factor and every table of its sweeps; of the row factor nothing is allocated
     mf = new SparseChol(ctx);
     mf->sym = std::move(sym.chol);
     sym.chol = CholSymbolic();
     PO_TRY(mf->upload(true));
-    PO_TRY(upload(d_ent_off, sym.ent_off));
-    dfree(d_Lrowp);
-    dfree(d_Lcols);
-    dfree(d_Ltp);
-    dfree(d_Ltrows);
-    dfree(d_Ltsrc);
-    dfree(d_ent_slot);
-    dfree(d_fwd);
-    dfree(d_front_of);
-    dfree(d_front_end);
-    dfree(d_fstart);
-    dfree(d_fsize);
+    PO_TRY(d_ent_off.upload(sym.ent_off));
   } else {
-    PO_TRY(upload(d_Lrowp, sym.Lrowp));
-    PO_TRY(upload(d_Lcols, sym.Lcols));
-    PO_TRY(upload(d_Ltp, sym.Ltp));
-    PO_TRY(upload(d_Ltrows, sym.Ltrows));
-    PO_TRY(upload(d_Ltsrc, sym.Ltsrc));
-    PO_TRY(upload(d_ent_slot, sym.ent_slot));
-    PO_TRY(upload(d_fwd, sym.fwd_order));
+    PO_TRY(d_Lrowp.upload(sym.Lrowp));
+    PO_TRY(d_Lcols.upload(sym.Lcols));
+    PO_TRY(d_Ltp.upload(sym.Ltp));
+    PO_TRY(d_Ltrows.upload(sym.Ltrows));
+    PO_TRY(d_Ltsrc.upload(sym.Ltsrc));
+    PO_TRY(d_ent_slot.upload(sym.ent_slot));
+    PO_TRY(d_fwd.upload(sym.fwd_order));
     std::vector<int> front_end(sym.front_of.size(), -1);
     for (size_t f = 0; f < sym.front_start.size(); f++) {
       for (int r = 0; r < sym.front_size[f]; r++) front_end[sym.front_start[f] + r] = sym.front_start[f] + sym.front_size[f];
     }
-    PO_TRY(upload(d_front_of, sym.front_of));
-    PO_TRY(upload(d_front_end, front_end));
-    PO_TRY(upload(d_fstart, sym.front_start));
-    PO_TRY(upload(d_fsize, sym.front_size));
-    PO_HIP(hipMalloc((void **)&Lvals, ((size_t)sym.nnzL + 4) * sizeof(double)));
+    PO_TRY(d_front_of.upload(sym.front_of));
+    PO_TRY(d_front_end.upload(front_end));
+    PO_TRY(d_fstart.upload(sym.front_start));
+    PO_TRY(d_fsize.upload(sym.front_size));
+    PO_TRY(Lvals.alloc((size_t)sym.nnzL + 4, false));
   }
-  dfree(ones);
-  dfree(wwork);
-  dfree(d_flag);
-  PO_HIP(hipMalloc((void **)&ones, ((size_t)w + 4) * sizeof(double)));
-  PO_HIP(hipMalloc((void **)&wwork, ((size_t)w + 4) * sizeof(double)));
-  PO_HIP(hipMalloc((void **)&d_flag, 4 * sizeof(int)));
-  PO_HIP(hipMemset(wwork, 0, ((size_t)w + 4) * sizeof(double)));
-  PO_HIP(hipMemset(ones, 0, ((size_t)w + 4) * sizeof(double)));
+  PO_TRY(ones.alloc((size_t)w + 4, true));
+  PO_TRY(wwork.alloc((size_t)w + 4, true));
+  PO_TRY(d_flag.alloc(4, false));
   PO_HIP(hipDeviceSynchronize());
   PO_TRY(k_fill(ctx, ones, w, 1.0));
-  if (adopt_cw) {  // (the same Vec object: handles the user holds stay valid)
-    cw = adopt_cw;
-    adopt_cw = nullptr;
-  } else {
-    if (cw) vec_decref(cw);
-    cw = vec_new(ctx, w);
-    if (!cw) return PO_ERR_HIP;
-  }
   nlevels_f = mf ? 0 : (int)sym.fwd_ptr.size() - 1;
-  spmv_group = group_for(w > 0 ? (double)nnz / (double)w : 0.0);
+  spmv_group = group_for(w > 0 ? (double)sym.nnz / (double)w : 0.0);
   // (the transposed index holds the sparse columns alone)
   spmvT_group = group_for(n > 0 ? (double)sym.rowsT.size() / (double)n : 0.0);
-  PO_TRY(freeDense());
   if (const int r = ndense()) {
-    dense_nb = dense_dot_blocks(w);
-    dense_ld = (w + 3) / 4 * 4 + 4;
-    dense_maxlen = 0;
-    for (int j = 0; j < r; j++) dense_maxlen = std::max(dense_maxlen, sym.dense_ptr[j + 1] - sym.dense_ptr[j]);
+    dense.nb = dense_dot_blocks(w);
+    dense.ld = (w + 3) / 4 * 4 + 4;
+    for (int j = 0; j < r; j++) dense.maxlen = std::max(dense.maxlen, sym.dense_ptr[j + 1] - sym.dense_ptr[j]);
     std::vector<unsigned char> mask((size_t)n, 0);
     for (int j : sym.dense_cols) mask[j] = 1;
-    PO_TRY(upload(d_dmask, mask));
-    PO_TRY(upload(d_dcols, sym.dense_cols));
-    PO_TRY(upload(d_dptr, sym.dense_ptr));
-    PO_TRY(upload(d_dpos, sym.dense_pos));
-    PO_TRY(upload(d_dslot, sym.dense_slot));
-    const size_t pbytes = (size_t)r * dense_ld * sizeof(double);
-    PO_HIP(hipMalloc((void **)&Vd, pbytes));
-    PO_HIP(hipMalloc((void **)&Yv, pbytes));
-    PO_HIP(hipMalloc((void **)&Kfac, ((size_t)r * r + 4) * sizeof(double)));
-    PO_HIP(hipMemset(Vd, 0, pbytes));  // the positions outside the pattern stay zero for good
-    PO_HIP(hipMemset(Yv, 0, pbytes));
-    PO_HIP(hipMemset(Kfac, 0, ((size_t)r * r + 4) * sizeof(double)));
+    PO_TRY(dense.mask.upload(mask));
+    PO_TRY(dense.cols.upload(sym.dense_cols));
+    PO_TRY(dense.ptr.upload(sym.dense_ptr));
+    PO_TRY(dense.pos.upload(sym.dense_pos));
+    PO_TRY(dense.slot.upload(sym.dense_slot));
+    // Vd: the positions outside the pattern stay zero for good, the others are written by valuesChanged()
+    PO_TRY(dense.Vd.alloc((size_t)r * dense.ld, true));
+    PO_TRY(dense.Yv.alloc((size_t)r * dense.ld, true));
+    PO_TRY(dense.Kfac.alloc((size_t)r * r + 4, true));
     PO_TRY(densePartials(std::max(r, 32)));  // (wider panels grow it once)
     PO_HIP(hipDeviceSynchronize());
-    PO_TRY(k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, vals, r, dense_maxlen, dense_ld, Vd));
   }
   return PO_OK;
 }
 
+// vals after the analysis: a separate column-sorted copy when the user's entry order is not the sorted one
+int CsrSparse::sortedValues() {
+  if (sym.identity_src) return PO_OK;
+  PO_TRY(sorted_vals.alloc((size_t)nnz + 4, true));
+  vals = sorted_vals;
+  return PO_OK;
+}
+
+int CsrSparse::setPattern(const int *rowp, const int *cols) {
+  PO_TRY(analyse(rowp, cols));  // (first: it is what validates the pattern)
+  PO_TRY(allocUser(rowp, cols));
+  return sortedValues();
+}
+
 int CsrSparse::setPatternLight(const int *rowp, const int *cols) {
-  nnz = rowp[w];
-  user_rowp.assign(rowp, rowp + w + 1);
-  user_cols.assign(cols, cols + nnz);
-  PO_HIP(hipSetDevice(ctx->device));
-  if (vals != data) dfree(vals);
-  vals = nullptr;
-  dfree(data);
-  const size_t vbytes = ((size_t)nnz + 4) * sizeof(double);
-  PO_HIP(hipMalloc((void **)&data, vbytes));
-  PO_HIP(hipMemset(data, 0, vbytes));
-  vals = data;
-  if (cw) vec_decref(cw);
-  cw = vec_new(ctx, w);
-  if (!cw) return PO_ERR_HIP;
+  PO_TRY(allocUser(rowp, cols));
   light = true;
   return PO_OK;
 }
@@ -882,33 +778,17 @@ int CsrSparse::upgradeFromLight() {
   if (!light) return PO_OK;
   // The analysis runs after all.  The user-visible value array `data` (po_problem_get_sparse_jacobian_data hands it
   // out as a borrowed pointer, like the reference's getSparseJacobianData) and the constraint-value vector `cw` are
-  // ADOPTED by setPattern, not reallocated: a caller that cached either keeps a valid pointer, and what the gradient
-  // callback just wrote stays in place.
-  adopt_data = data;
-  adopt_cw = cw;
-  data = nullptr;
-  vals = nullptr;
-  cw = nullptr;
+  // not touched: a caller that cached either keeps a valid pointer, and what the gradient callback just wrote stays
+  // in place.  If the analysis fails the object stays light, with both.
+  PO_TRY(analyse(user_rowp.data(), user_cols.data()));
   light = false;
-  const std::vector<int> rp(user_rowp), cl(user_cols);
-  int rc = setPattern(rp.data(), cl.data());
-  if (adopt_data) {  // setPattern failed before it took them over
-    data = adopt_data;
-    adopt_data = nullptr;
-    if (!vals) vals = data;
-  }
-  if (adopt_cw) {
-    if (cw && cw != adopt_cw) vec_decref(cw);
-    cw = adopt_cw;
-    adopt_cw = nullptr;
-  }
-  return rc;
+  return sortedValues();
 }
 
 int CsrSparse::valuesChanged() {
   if (light || nnz == 0) return PO_OK;
   if (vals != data) PO_TRY(k_csr_gather(ctx, vals, data, d_src, nnz));
-  return k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, vals, ndense(), dense_maxlen, dense_ld, Vd);
+  return k_dense_scatter(ctx, dense.ptr, dense.pos, dense.slot, vals, ndense(), dense.maxlen, dense.ld, dense.Vd);
 }
 
 int CsrSparse::spmv(double alpha, const double *px, double *out) {
@@ -924,24 +804,23 @@ int CsrSparse::denseColumnsOut(bool pattern_only, const double *y, const int *id
                                const double *dscale, double *out) {
   const int r = ndense();
   if (r == 0 || w <= 0) return PO_OK;
-  if (pattern_only && !Vind) {  // the indicator of V, made when the first column sum asks for it
-    const size_t pbytes = (size_t)r * dense_ld * sizeof(double);
-    PO_HIP(hipMalloc((void **)&Vind, pbytes));
-    PO_HIP(hipMemsetAsync(Vind, 0, pbytes, ctx->stream));
-    PO_TRY(k_dense_scatter(ctx, d_dptr, d_dpos, d_dslot, nullptr, r, dense_maxlen, dense_ld, Vind));
+  if (pattern_only && !dense.Vind) {  // the indicator of V, made when the first column sum asks for it
+    PO_TRY(dense.Vind.alloc((size_t)r * dense.ld, false));
+    PO_HIP(hipMemsetAsync(dense.Vind, 0, (size_t)r * dense.ld * sizeof(double), ctx->stream));
+    PO_TRY(k_dense_scatter(ctx, dense.ptr, dense.pos, dense.slot, nullptr, r, dense.maxlen, dense.ld, dense.Vind));
   }
   const double *B[1] = {y};
-  PO_TRY(k_dense_dot(ctx, pattern_only ? Vind : Vd, dense_ld, r, B, 1, idx, w, part));
-  return k_dense_out(ctx, part, dense_nb, r, d_dcols, alpha, bx, dscale, out);
+  PO_TRY(k_dense_dot(ctx, pattern_only ? dense.Vind : dense.Vd, dense.ld, r, B, 1, idx, w, dense.part));
+  return k_dense_out(ctx, dense.part, dense.nb, r, dense.cols, alpha, bx, dscale, out);
 }
 
 int CsrSparse::lowRankStep(double *const *Y, int nv) {
   const int r = ndense();
   if (r == 0 || nv <= 0 || w <= 0) return PO_OK;
   PO_TRY(densePartials(nv));
-  PO_TRY(k_dense_dot(ctx, Yv, dense_ld, r, Y, nv, nullptr, w, part));
-  PO_TRY(k_dense_ksolve(ctx, part, dense_nb, r, nv, Kfac, Zd));
-  return k_dense_update(ctx, Yv, dense_ld, r, Y, nv, Zd, w);
+  PO_TRY(k_dense_dot(ctx, dense.Yv, dense.ld, r, Y, nv, nullptr, w, dense.part));
+  PO_TRY(k_dense_ksolve(ctx, dense.part, dense.nb, r, nv, dense.Kfac, dense.Zd));
+  return k_dense_update(ctx, dense.Yv, dense.ld, r, Y, nv, dense.Zd, w);
 }
 
 int CsrSparse::innerProduct(double alpha, const double *cvec, double *out) {
@@ -1059,13 +938,13 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
     PO_HIP(hipMemsetAsync(d_flag, 0x7f, 4 * sizeof(int), ctx->stream));
     PO_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
     PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_off,
-                          (int64_t)sym.ent_off.size(), L, d_dmask));
+                          (int64_t)sym.ent_off.size(), L, dense.mask));
     PO_TRY(mf->factorAssembled(d_flag));
   } else {
     PO_HIP(hipMemsetAsync(Lvals, 0, ((size_t)sym.nnzL + 4) * sizeof(double), ctx->stream));
     PO_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), ctx->stream));
     PO_TRY(k_csr_assemble(ctx, d_rowp, d_cols, vals, dinv, cdiag, d_ent_a, d_ent_b, d_ent_slot,
-                          (int64_t)sym.ent_slot.size(), Lvals, d_dmask));
+                          (int64_t)sym.ent_slot.size(), Lvals, dense.mask));
   }
   for (int l = 0; l < nlevels_f; l++) {
     const int b = sym.fwd_ptr[l], e = sym.fwd_ptr[l + 1];
@@ -1077,12 +956,12 @@ int CsrSparse::factor(const double *dinv, const double *cdiag) {
   }
   if (const int r = ndense()) {
     // Yv = L^-1 P V, T = Yv^T Yv, K = E^-1 + T = Lk Lk^T: all queued ahead of the one flag read below
-    PO_HIP(hipMemcpyAsync(Yv, Vd, (size_t)r * dense_ld * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    PO_HIP(hipMemcpyAsync(dense.Yv, dense.Vd, (size_t)r * dense.ld * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     std::vector<double *> cols((size_t)r);
-    for (int j = 0; j < r; j++) cols[j] = Yv + (int64_t)j * dense_ld;
+    for (int j = 0; j < r; j++) cols[j] = dense.Yv + (int64_t)j * dense.ld;
     PO_TRY(solveInPlace(cols.data(), r, true, false));
-    PO_TRY(k_dense_dot(ctx, Yv, dense_ld, r, cols.data(), r, nullptr, w, part));
-    PO_TRY(k_dense_kfactor(ctx, part, dense_nb, r, dinv, d_dcols, Kfac, d_flag, w));
+    PO_TRY(k_dense_dot(ctx, dense.Yv, dense.ld, r, cols.data(), r, nullptr, w, dense.part));
+    PO_TRY(k_dense_kfactor(ctx, dense.part, dense.nb, r, dinv, dense.cols, dense.Kfac, d_flag, w));
   }
   int flag[4] = {0, 0, 0, 0};
   PO_HIP(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
@@ -1189,15 +1068,14 @@ int CsrSparse::solvePanel(const double *const *U, int nv, double *const *Yw) {
     return PO_OK;
   }
   const int64_t ld = (w + 3) / 4 * 4 + 4;
-  if (nv > spanel_cap) {
+  if (nv > dense.spanel_cap) {
     PO_HIP(hipStreamSynchronize(ctx->stream));  // (grows a few times in the life of a pattern)
-    dfree(spanel);
-    spanel_cap = 0;
-    PO_HIP(hipMalloc((void **)&spanel, (size_t)nv * ld * sizeof(double)));
-    spanel_cap = nv;
+    dense.spanel_cap = 0;
+    PO_TRY(dense.spanel.alloc((size_t)nv * ld, false));
+    dense.spanel_cap = nv;
   }
   std::vector<double *> Y((size_t)nv);
-  for (int j = 0; j < nv; j++) Y[j] = spanel + (int64_t)j * ld;
+  for (int j = 0; j < nv; j++) Y[j] = dense.spanel + (int64_t)j * ld;
   PO_TRY(k_csr_panel_gather(ctx, Y.data(), U, nv, d_perm, 1.0, w));
   PO_TRY(solveInPlace(Y.data(), nv, true, false));
   PO_TRY(lowRankStep(Y.data(), nv));

@@ -144,23 +144,22 @@ class CsrSparse {
  public:
   CsrSparse(Ctx *c, int64_t n_, int64_t w_);
   ~CsrSparse();
+  // A CsrSparse is BUILT ONCE: one of setPattern / setPatternLight on a fresh object, and at most one
+  // upgradeFromLight() afterwards.  Every device array is a DevArray (core.hpp): freed with the object, counted by
+  // po_live_objects.
   int setPattern(const int *rowp, const int *cols);
   int64_t dense_min_rows = 0;  // the dense-column rule of csr_analyse; set before setPattern
   int factor_kind = 0;         // PO_SPARSE_FACTOR_*: which engine factors S0; set before setPattern
-  // the multifrontal engine (owned; null with the row factor).  Its CholSymbolic is the analysis: sym.chol is moved
-  // into it by setPattern.
-  SparseChol *mf = nullptr;
   // The pattern was recognised as the grouped one (problem.hpp): only what the user's callbacks and
   // getSparseJacobianData need -- host copies of the pattern, the value array, the constraint vector -- and NO
   // symbolic analysis (at w = 1 M rows it would cost seconds and hundreds of MB that the block form never uses).
-  // upgradeFromLight() runs the analysis after all, keeping the values (the entries turned out not to be uniform).
+  // upgradeFromLight() runs the analysis after all (the entries turned out not to be uniform): `data`, what the user
+  // wrote into it and the Vec `cw` stay the objects they were, also when the analysis fails.
   int setPatternLight(const int *rowp, const int *cols);
   int upgradeFromLight();
   bool light = false;
-  double *adopt_data = nullptr;  // upgradeFromLight -> setPattern: keep these allocations instead of new ones
-  Vec *adopt_cw = nullptr;
   // the user's value array in the user's entry order (device, nnz doubles) and the constraint values
-  double *data = nullptr;
+  DevArray<double> data;
   Vec *cw = nullptr;
   // call after `data` changed (evalObjConGradient): refreshes the column-sorted copy
   int valuesChanged();
@@ -192,6 +191,9 @@ class CsrSparse {
   long breakdowns = 0;  // factorizations that met a non-positive pivot (see factor())
 
  private:
+  int allocUser(const int *rowp, const int *cols);  // what the user sees: data, the vals alias, cw
+  int analyse(const int *rowp, const int *cols);    // the analysis and its device tables; touches none of the above
+  int sortedValues();                               // after both: vals, where it is not `data` itself
   int solveInPlace(double *const *Y, int nv, bool forward, bool backward);
   // dense columns (csr.hpp: CsrSymbolic): Y_j -= Yv K^-1 (Yv^T Y_j) on half-solved columns in the elimination order
   int lowRankStep(double *const *Y, int nv);
@@ -199,28 +201,39 @@ class CsrSparse {
   int denseColumnsOut(bool pattern_only, const double *y, const int *idx, double alpha, const double *bx,
                       const double *dscale, double *out);
   int densePartials(int nv);  // room for the block partials of an r x nv product
-  int freeDense();
-  int dense_nb = 1;           // workgroups of the first reduction stage: a function of w alone
-  int64_t dense_ld = 0;       // stride of the r w-vectors below
-  int dense_maxlen = 0, part_cap = 0, spanel_cap = 0;
-  double *Vd = nullptr, *Yv = nullptr, *Vind = nullptr;  // V and L^-1 P V (elimination order); indicator of V, on demand
-  double *Kfac = nullptr, *Zd = nullptr, *part = nullptr, *spanel = nullptr;
-  unsigned char *d_dmask = nullptr;
-  int *d_dcols = nullptr, *d_dptr = nullptr, *d_dpos = nullptr, *d_dslot = nullptr;
-  double *vals = nullptr;  // column-sorted values (== data when the user's order is already sorted)
-  int *d_rowp = nullptr, *d_cols = nullptr, *d_src = nullptr;
-  int *d_colp = nullptr, *d_rowsT = nullptr, *d_srcT = nullptr;
-  int *d_perm = nullptr, *d_iperm = nullptr;
-  int *d_Lrowp = nullptr, *d_Lcols = nullptr;
-  int *d_Ltp = nullptr, *d_Ltrows = nullptr, *d_Ltsrc = nullptr;
-  int *d_ent_a = nullptr, *d_ent_b = nullptr, *d_ent_slot = nullptr;
-  int64_t *d_ent_off = nullptr;
-  int *d_fwd = nullptr;
-  int *d_front_of = nullptr, *d_front_end = nullptr, *d_fstart = nullptr, *d_fsize = nullptr;
-  double *Lvals = nullptr, *ones = nullptr, *wwork = nullptr;
-  int *d_flag = nullptr;
-  std::string info;
+  // THE PATTERN AND ITS TRANSPOSE.  vals: the column-sorted values, `data` itself when the user's order is already
+  // sorted, sorted_vals otherwise
+  double *vals = nullptr;
+  DevArray<double> sorted_vals;
+  DevArray<int> d_rowp, d_cols, d_src;
+  DevArray<int> d_colp, d_rowsT, d_srcT;
+  DevArray<int> d_perm, d_iperm;
+  DevArray<int> d_ent_a, d_ent_b;
+  DevArray<double> ones, wwork;
+  DevArray<int> d_flag;
   int spmv_group = 1, spmvT_group = 1;
+  // THE ROW FACTOR (empty under the multifrontal kind)
+  DevArray<double> Lvals;
+  DevArray<int> d_Lrowp, d_Lcols;
+  DevArray<int> d_Ltp, d_Ltrows, d_Ltsrc;
+  DevArray<int> d_fwd;
+  DevArray<int> d_front_of, d_front_end, d_fstart, d_fsize;
+  DevArray<int> d_ent_slot;
+  // THE MULTIFRONTAL SIDE: the engine (owned; null with the row factor; its CholSymbolic is the analysis, sym.chol is
+  // moved into it) and where each structural entry of S0 lies in its L
+  SparseChol *mf = nullptr;
+  DevArray<int64_t> d_ent_off;
+  // THE DENSE COLUMNS (and the panel of solvePanel); a fresh one is the state without any
+  struct DenseCols {
+    int nb = 1;        // workgroups of the first reduction stage: a function of w alone
+    int64_t ld = 0;    // stride of the r w-vectors below
+    int maxlen = 0, part_cap = 0, spanel_cap = 0;
+    DevArray<double> Vd, Yv, Vind;  // V and L^-1 P V (elimination order); indicator of V, on demand
+    DevArray<double> Kfac, Zd, part, spanel;
+    DevArray<unsigned char> mask;
+    DevArray<int> cols, ptr, pos, slot;
+  } dense;
+  std::string info;
 };
 
 // kernels (csr.hip)

@@ -17,16 +17,16 @@ namespace po {
 // kernels can always use full 16-byte accesses on the last pair (kernels.hip::ld2/st2).
 static size_t padded_elems(int64_t n) { return (size_t)(((n + 1) >> 1) << 1) + 2; }
 
-// live-object accounting (po_live_objects): every device vector alive and the bytes behind them
+// live-object accounting (po_live_objects): every device vector alive; the bytes behind them are added to
+// live_bytes() (core.hpp), which the DevArrays of the sparse factors share
 static std::atomic<long> g_live_vecs(0);
-static std::atomic<long long> g_live_bytes(0);
 static std::atomic<long> g_live_mirrors(0);  // pinned host mirrors behind po_vec_get_array
 void mirror_created() { g_live_mirrors++; }
 void mirror_freed() { g_live_mirrors--; }
 long live_mirrors() { return g_live_mirrors.load(); }
 void live_objects(long *vecs, long long *bytes) {
   if (vecs) *vecs = g_live_vecs.load();
-  if (bytes) *bytes = g_live_bytes.load();
+  if (bytes) *bytes = live_bytes().load();
 }
 
 Vec *vec_new(Ctx *c, int64_t n) {
@@ -46,7 +46,7 @@ Vec *vec_new(Ctx *c, int64_t n) {
     set_error("hipMemsetAsync failed");
   }
   g_live_vecs++;
-  g_live_bytes += (long long)bytes;
+  live_bytes() += (long long)bytes;
   return v;
 }
 
@@ -60,7 +60,7 @@ void vec_decref(Vec *v) {
       mirror_freed();
     }
     g_live_vecs--;
-    g_live_bytes -= (long long)(sizeof(double) * padded_elems(v->n));
+    live_bytes() -= (long long)(sizeof(double) * padded_elems(v->n));
     delete static_cast<po_vec_s *>(v);
   }
 }

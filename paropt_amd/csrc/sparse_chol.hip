@@ -135,6 +135,23 @@ __device__ inline double signed_pivot(double &piv, int *flag, int index, double 
   return sk;
 }
 
+// The sign switch, once: the pivot of column `index` (tested, flagged and replaced by 1 where it cannot be used, its
+// sign s_k returned -- 1 in the unsigned form), the divisor of the column below it and the column operand that
+// carries s_k.  The unsigned forms multiply by nothing.
+template <bool kSigned>
+__device__ inline double form_pivot(double &piv, int *flag, int index, double *sgn, bool writer) {
+  if (kSigned) return signed_pivot(piv, flag, index, sgn, writer);
+  if (!(piv > 0.0)) {
+    if (writer) flag_pivot(flag, index);
+    piv = 1.0;
+  }
+  return 1.0;
+}
+template <bool kSigned>
+__device__ inline double pivot_divisor(double sk, double r) { return kSigned ? sk * r : r; }
+template <bool kSigned>
+__device__ inline double column_operand(double sk, double v) { return kSigned ? sk * v : v; }
+
 // Partial Cholesky of the first s columns of the m x m lower triangle F (column-major, kLdsLd) in LDS by ONE
 // wavefront.  A non-positive (or NaN) pivot is flagged and replaced by 1, as chol_front_dense_kernel does.
 template <bool kSigned>
@@ -142,29 +159,16 @@ __device__ inline void lds_partial_chol(double *F, int m, int s, int index0, int
   const int tid = threadIdx.x, i = tid & 31, half = tid >> 5;
   for (int k = 0; k < s; k++) {
     double piv = F[k * kLdsLd + k];
-    double sk = 1.0;
-    if (kSigned) {
-      sk = signed_pivot(piv, flag, index0 + k, sgn, tid == 0);
-    } else if (!(piv > 0.0)) {
-      if (tid == 0) flag_pivot(flag, index0 + k);
-      piv = 1.0;
-    }
+    const double sk = form_pivot<kSigned>(piv, flag, index0 + k, sgn, tid == 0);
     const double r = sqrt(piv);
     __syncthreads();
     if (tid == 0) F[k * kLdsLd + k] = r;
-    if (kSigned) {
-      if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= sk * r;
-    } else {
-      if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= r;
-    }
+    if (half == 0 && i > k && i < m) F[k * kLdsLd + i] /= pivot_divisor<kSigned>(sk, r);
     __syncthreads();
     if (i > k && i < m) {
       const double lik = F[k * kLdsLd + i];
-      if (kSigned) {
-        for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * (sk * F[k * kLdsLd + j]);
-      } else {
-        for (int j = k + 1 + half; j <= i; j += 2) F[j * kLdsLd + i] -= lik * F[k * kLdsLd + j];
-      }
+      for (int j = k + 1 + half; j <= i; j += 2)
+        F[j * kLdsLd + i] -= lik * column_operand<kSigned>(sk, F[k * kLdsLd + j]);
     }
     __syncthreads();
   }
@@ -424,27 +428,14 @@ __global__ __launch_bounds__(kPackLanes) void chol_pack_factor_kernel(CholDev d,
     }
     for (int k = 0; k < s; k++) {
       double piv = F[tri(k, k)];
-      double sk = 1.0;
-      if (kSigned) {
-        sk = signed_pivot(piv, flag, first + k, sgn, true);
-      } else if (!(piv > 0.0)) {
-        flag_pivot(flag, first + k);
-        piv = 1.0;
-      }
+      const double sk = form_pivot<kSigned>(piv, flag, first + k, sgn, true);
       const double r = sqrt(piv);
       F[tri(k, k)] = r;
-      if (kSigned) {
-        for (int i = k + 1; i < m; i++) F[tri(i, k)] /= sk * r;
-      } else {
-        for (int i = k + 1; i < m; i++) F[tri(i, k)] /= r;
-      }
+      for (int i = k + 1; i < m; i++) F[tri(i, k)] /= pivot_divisor<kSigned>(sk, r);
       for (int i = k + 1; i < m; i++) {
         const double lik = F[tri(i, k)];
-        if (kSigned) {
-          for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, sk * F[tri(j, k)], F[tri(i, j)]);
-        } else {
-          for (int j = k + 1; j <= i; j++) F[tri(i, j)] = __fma_rn(-lik, F[tri(j, k)], F[tri(i, j)]);
-        }
+        for (int j = k + 1; j <= i; j++)
+          F[tri(i, j)] = __fma_rn(-lik, column_operand<kSigned>(sk, F[tri(j, k)]), F[tri(i, j)]);
       }
     }
     for (int col = 0; col < m; col++) {
@@ -871,95 +862,71 @@ __global__ __launch_bounds__(256) void chol_bwd_panel_kernel(CholDev d, const in
 // workgroups of a packed sweep: one lane per (group, right-hand side)
 unsigned pack_grid(int ngroup, int nrhs) { return (unsigned)(((int64_t)ngroup * nrhs + kPackLanes - 1) / kPackLanes); }
 
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-template <class T>
-int upload(T *&dst, const std::vector<T> &src) {
-  dfree(dst);
-  const size_t bytes = (src.size() + 4) * sizeof(T);
-  PO_HIP(hipMalloc((void **)&dst, bytes));
-  PO_HIP(hipMemset(dst, 0, bytes));
-  if (!src.empty()) PO_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return PO_OK;
+// One direction of a triangular sweep: level after level (ascending: forward), the packed groups of the level, then
+// its unpacked fronts, a workgroup each.  `pack` and `front` are the kernel pair; the front kernel takes d, its
+// level's list and front_args.
+template <class PackKernel, class FrontKernel, class... FrontArgs>
+void launch_levels(const CholSymbolic &sym, hipStream_t st, const CholDev &d, const int *glev_first,
+                   const int *glev_root, const int *lev_sn, bool ascending, int nr, PackKernel pack, CholPtrs Yp,
+                   double *Yb, int64_t ldy, FrontKernel front, FrontArgs... front_args) {
+  for (int i = 0; i < sym.nlev; i++) {
+    const int l = ascending ? i : sym.nlev - 1 - i;
+    const CholLevelPlan plan = chol_level_plan(sym, l);
+    if (plan.ngroup > 0) {
+      hipLaunchKernelGGL(pack, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
+                         glev_first + sym.glev_ptr[l], glev_root + sym.glev_ptr[l], plan.ngroup, Yp, Yb, ldy, nr);
+    }
+    if (plan.nfront > 0) {
+      hipLaunchKernelGGL(front, dim3(plan.nfront), dim3(256), 0, st, d, lev_sn + sym.lev_ptr[l], front_args...);
+    }
+  }
 }
 
 }  // namespace
 
-SparseChol::~SparseChol() {
-  dfree(L);
-  dfree(arena);
-  dfree(Y);
-  dfree(avals);
-  dfree(xbuf);
-  dfree(d_flag);
-  dfree(d_sign);
-  dfree(d_perm);
-  dfree(d_first);
-  dfree(d_b);
-  dfree(d_ld);
-  dfree(d_uld);
-  dfree(d_below);
-  dfree(d_rel);
-  dfree(d_child_ptr);
-  dfree(d_child);
-  dfree(d_rows_ptr);
-  dfree(d_panel);
-  dfree(d_upd);
-  dfree(d_sol);
-  dfree(d_glev_first);
-  dfree(d_glev_root);
-  dfree(d_lev_sn);
-  dfree(d_chunk_sn);
-  dfree(d_chunk_c0);
-  dfree(d_tab);
-  dfree(d_asm_ptr);
-  dfree(d_asm_src);
-  dfree(d_asm_dst);
+// the anonymous namespace's CholDev under a name the header can declare
+struct SparseChol::DevTables : CholDev {};
+SparseChol::DevTables SparseChol::dev() const {
+  return {{d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr, d_below, d_rel, d_child_ptr, d_child, L,
+           arena}};
 }
 
 int SparseChol::upload(bool embedded) {
   PO_HIP(hipSetDevice(ctx->device));
   const int64_t arena_doubles = std::max(sym.arena, sym.sol_arena) + 4;
   const int64_t y_doubles = embedded ? 4 : sym.ldy() * kCholMaxRhs;
-  if (hipMalloc((void **)&arena, (size_t)arena_doubles * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&Y, (size_t)y_doubles * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&L, ((size_t)sym.Lsize + 4) * sizeof(double)) != hipSuccess) {
+  if (arena.alloc((size_t)arena_doubles, true) != PO_OK || Y.alloc((size_t)y_doubles, true) != PO_OK ||
+      L.alloc((size_t)sym.Lsize + 4, true) != PO_OK) {
     (void)hipGetLastError();
     set_error("sparse Cholesky: cannot allocate the factor (%lld bytes) and its work space (%lld bytes)",
               (long long)(8 * sym.Lsize), (long long)sym.work_bytes);
     return PO_ERR_ARG;
   }
-  PO_HIP(hipMemset(arena, 0, (size_t)arena_doubles * sizeof(double)));
-  PO_HIP(hipMemset(Y, 0, (size_t)y_doubles * sizeof(double)));
-  PO_HIP(hipMemset(L, 0, ((size_t)sym.Lsize + 4) * sizeof(double)));
-  if (!embedded) PO_HIP(hipMalloc((void **)&avals, (sym.rows.size() + 4) * sizeof(double)));
-  PO_HIP(hipMalloc((void **)&d_flag, 4 * sizeof(int)));
-  PO_TRY(po::upload(d_perm, sym.perm));
-  PO_TRY(po::upload(d_first, sym.sn_first));
-  PO_TRY(po::upload(d_b, sym.sn_b));
-  PO_TRY(po::upload(d_ld, sym.sn_ld));
-  PO_TRY(po::upload(d_uld, sym.upd_ld));
-  PO_TRY(po::upload(d_below, sym.below_rows));
-  PO_TRY(po::upload(d_rel, sym.rel));
-  PO_TRY(po::upload(d_child_ptr, sym.child_ptr));
-  PO_TRY(po::upload(d_child, sym.child));
-  PO_TRY(po::upload(d_rows_ptr, sym.rows_ptr));
-  PO_TRY(po::upload(d_panel, sym.panel_off));
-  PO_TRY(po::upload(d_upd, sym.upd_off));
-  PO_TRY(po::upload(d_sol, sym.sol_off));
-  PO_TRY(po::upload(d_glev_first, sym.glev_first));
-  PO_TRY(po::upload(d_glev_root, sym.glev_root));
-  PO_TRY(po::upload(d_lev_sn, sym.lev_sn));
-  PO_TRY(po::upload(d_chunk_sn, sym.chunk_sn));
-  PO_TRY(po::upload(d_chunk_c0, sym.chunk_c0));
-  PO_TRY(po::upload(d_tab, sym.tab));
+  if (!embedded) PO_TRY(avals.alloc(sym.rows.size() + 4, false));
+  PO_TRY(d_flag.alloc(4, false));
+  PO_TRY(d_perm.upload(sym.perm));
+  PO_TRY(d_first.upload(sym.sn_first));
+  PO_TRY(d_b.upload(sym.sn_b));
+  PO_TRY(d_ld.upload(sym.sn_ld));
+  PO_TRY(d_uld.upload(sym.upd_ld));
+  PO_TRY(d_below.upload(sym.below_rows));
+  PO_TRY(d_rel.upload(sym.rel));
+  PO_TRY(d_child_ptr.upload(sym.child_ptr));
+  PO_TRY(d_child.upload(sym.child));
+  PO_TRY(d_rows_ptr.upload(sym.rows_ptr));
+  PO_TRY(d_panel.upload(sym.panel_off));
+  PO_TRY(d_upd.upload(sym.upd_off));
+  PO_TRY(d_sol.upload(sym.sol_off));
+  PO_TRY(d_glev_first.upload(sym.glev_first));
+  PO_TRY(d_glev_root.upload(sym.glev_root));
+  PO_TRY(d_lev_sn.upload(sym.lev_sn));
+  PO_TRY(d_chunk_sn.upload(sym.chunk_sn));
+  PO_TRY(d_chunk_c0.upload(sym.chunk_c0));
+  PO_TRY(d_tab.upload(sym.tab));
   if (!embedded) {
-    PO_TRY(po::upload(d_asm_ptr, sym.asm_ptr));
-    PO_TRY(po::upload(d_asm_src, sym.asm_src));
-    PO_TRY(po::upload(d_asm_dst, sym.asm_dst));
+    PO_TRY(d_asm_ptr.upload(sym.asm_ptr));
+    PO_TRY(d_asm_src.upload(sym.asm_src));
+    PO_TRY(d_asm_dst.upload(sym.asm_dst));
   }
   PO_HIP(hipDeviceSynchronize());
   return PO_OK;
@@ -997,20 +964,15 @@ int SparseChol::setValuesHost(int64_t n, const int *colp, const int *rows, const
   std::vector<int> ptr, src;
   std::vector<int64_t> dst;
   PO_TRY(chol_scatter_table(sym, n, colp, rows, &ptr, &dst, &src));
-  int *tp = nullptr, *ts = nullptr;
-  int64_t *td = nullptr;
-  double *tv = nullptr;
-  const std::vector<double> hv(vals, vals + colp[n]);
-  int rc = po::upload(tp, ptr);
-  if (rc == PO_OK) rc = po::upload(ts, src);
-  if (rc == PO_OK) rc = po::upload(td, dst);
-  if (rc == PO_OK) rc = po::upload(tv, hv);
-  if (rc == PO_OK) rc = scatter(tp, td, ts, (int64_t)dst.size(), tv);
-  (void)hipStreamSynchronize(ctx->stream);
-  dfree(tp);
-  dfree(ts);
-  dfree(td);
-  dfree(tv);
+  DevArray<int> tp, ts;
+  DevArray<int64_t> td;
+  DevArray<double> tv;
+  PO_TRY(tp.upload(ptr));
+  PO_TRY(ts.upload(src));
+  PO_TRY(td.upload(dst));
+  PO_TRY(tv.upload(std::vector<double>(vals, vals + colp[n])));
+  const int rc = scatter(tp, td, ts, (int64_t)dst.size(), tv);
+  (void)hipStreamSynchronize(ctx->stream);  // (the tables go away with this scope)
   return rc;
 }
 
@@ -1044,7 +1006,7 @@ int SparseChol::setFactorization(int k) {
   }
   if (k == PO_CHOL_LDLT && ctx && !d_sign) {
     PO_HIP(hipSetDevice(ctx->device));
-    PO_HIP(hipMalloc((void **)&d_sign, ((size_t)sym.n + 4) * sizeof(double)));
+    PO_TRY(d_sign.alloc((size_t)sym.n + 4, false));
   }
   kind = k;
   return PO_OK;
@@ -1067,8 +1029,7 @@ int SparseChol::launchFactor(int *flag) {
   hipStream_t st = ctx->stream;
   int *const d_flag = flag;
   double *const sgn = kSigned ? d_sign : nullptr;
-  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
-                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  const CholDev d = dev();
   for (int l = 0; l < sym.nlev; l++) {
     const CholLevelPlan plan = chol_level_plan(sym, l);
     if (plan.ngroup > 0) {  // (independent of the level's unpacked fronts)
@@ -1161,8 +1122,7 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
   if (sym.n == 0 || nrhs == 0) return PO_OK;
   PO_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
-                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  const CholDev d = dev();
   const int64_t ldy = sym.ldy();
   for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
     const int nr = std::min(kCholMaxRhs, nrhs - r0);
@@ -1170,33 +1130,13 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
     const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 0);
     const CholPtrs none = {};
-    for (int l = 0; l < sym.nlev; l++) {
-      const CholLevelPlan plan = chol_level_plan(sym, l);
-      if (plan.ngroup > 0) {
-        hipLaunchKernelGGL(chol_pack_fwd_kernel<false>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
-                           d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, none, Y, ldy,
-                           nr);
-      }
-      if (plan.nfront > 0) {
-        hipLaunchKernelGGL(chol_fwd_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy,
-                           nr);
-      }
-    }
+    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, Y, ldy,
+                  chol_fwd_kernel, Y.get(), ldy, nr);
     if (factored_kind == PO_CHOL_LDLT) {
       hipLaunchKernelGGL(chol_sign_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, (const double *)d_sign, sym.n, nr);
     }
-    for (int l = sym.nlev - 1; l >= 0; l--) {
-      const CholLevelPlan plan = chol_level_plan(sym, l);
-      if (plan.ngroup > 0) {
-        hipLaunchKernelGGL(chol_pack_bwd_kernel<false>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
-                           d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, none, Y, ldy,
-                           nr);
-      }
-      if (plan.nfront > 0) {
-        hipLaunchKernelGGL(chol_bwd_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l], Y, ldy,
-                           nr);
-      }
-    }
+    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<false>, none, Y,
+                  ldy, chol_bwd_kernel, Y.get(), ldy, nr);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 1);
     PO_HIP(hipGetLastError());
   }
@@ -1211,39 +1151,18 @@ int SparseChol::sweep(double *const *Yh, int nv, bool forward, bool backward) {
   if (sym.n == 0 || nv <= 0) return PO_OK;
   PO_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const CholDev d = {d_first, d_b, d_ld, d_uld, d_panel, d_upd, d_sol, d_rows_ptr,
-                     d_below, d_rel, d_child_ptr, d_child, L, arena};
+  const CholDev d = dev();
   for (int r0 = 0; r0 < nv; r0 += kCholMaxRhs) {  // (sol_off lays the update vectors out for kCholMaxRhs columns)
     const int nr = std::min(kCholMaxRhs, nv - r0);
     CholPtrs t;
     for (int j = 0; j < kCholMaxRhs; j++) t.p[j] = Yh[r0 + (j < nr ? j : 0)];
     if (forward) {
-      for (int l = 0; l < sym.nlev; l++) {
-        const CholLevelPlan plan = chol_level_plan(sym, l);
-        if (plan.ngroup > 0) {
-          hipLaunchKernelGGL(chol_pack_fwd_kernel<true>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
-                             d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, t, nullptr,
-                             (int64_t)0, nr);
-        }
-        if (plan.nfront > 0) {
-          hipLaunchKernelGGL(chol_fwd_panel_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l],
-                             t, nr);
-        }
-      }
+      launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<true>, t, nullptr,
+                    (int64_t)0, chol_fwd_panel_kernel, t, nr);
     }
     if (backward) {
-      for (int l = sym.nlev - 1; l >= 0; l--) {
-        const CholLevelPlan plan = chol_level_plan(sym, l);
-        if (plan.ngroup > 0) {
-          hipLaunchKernelGGL(chol_pack_bwd_kernel<true>, dim3(pack_grid(plan.ngroup, nr)), dim3(kPackLanes), 0, st, d,
-                             d_glev_first + sym.glev_ptr[l], d_glev_root + sym.glev_ptr[l], plan.ngroup, t, nullptr,
-                             (int64_t)0, nr);
-        }
-        if (plan.nfront > 0) {
-          hipLaunchKernelGGL(chol_bwd_panel_kernel, dim3(plan.nfront), dim3(256), 0, st, d, d_lev_sn + sym.lev_ptr[l],
-                             t, nr);
-        }
-      }
+      launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<true>, t, nullptr,
+                    (int64_t)0, chol_bwd_panel_kernel, t, nr);
     }
     PO_HIP(hipGetLastError());
   }
@@ -1256,9 +1175,8 @@ int SparseChol::solveHost(double *x, int nrhs, int64_t ldx) {
   PO_HIP(hipSetDevice(ctx->device));
   const int64_t count = (int64_t)(nrhs - 1) * ldx + sym.n;
   if (count > xbuf_cap) {
-    dfree(xbuf);
     xbuf_cap = 0;
-    PO_HIP(hipMalloc((void **)&xbuf, (size_t)count * sizeof(double)));
+    PO_TRY(xbuf.alloc((size_t)count, false));
     xbuf_cap = count;
   }
   PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

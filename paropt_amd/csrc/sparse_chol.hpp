@@ -115,7 +115,6 @@ int chol_scatter_table(const CholSymbolic &s, int64_t n, const int *colp, const 
 class SparseChol {
  public:
   SparseChol(Ctx *c) : ctx(c) {}
-  ~SparseChol();
   CholSymbolic sym;
   Ctx *ctx;  // null: analysis only
   // after chol_analyse: device tables, L, arena.  embedded: the owner assembles L itself (beginAssembly) and solves
@@ -148,23 +147,26 @@ class SparseChol {
   int sweep(double *const *Y, int nv, bool forward, bool backward);
 
  private:
+  struct DevTables;       // the table of device pointers every kernel takes (sparse_chol.hip: CholDev)
+  DevTables dev() const;
   int scatter(const int *d_ptr, const int64_t *d_dst, const int *d_src, int64_t ndst, const double *dvals);
   template <bool kSigned>
   int launchFactor(int *flag);
   bool have_values = false, factored = false, have_inertia = false, uncounted = false;
   int kind = 0, factored_kind = 0;
   int64_t inertia_[3] = {0, 0, 0};
-  double *d_sign = nullptr;  // s_k = +-1.0 in elimination order (LDLT)
-  double *L = nullptr, *arena = nullptr, *Y = nullptr, *avals = nullptr, *xbuf = nullptr;
+  // every device array is freed with the object and counted by po_live_objects (core.hpp: DevArray)
+  DevArray<double> d_sign;  // s_k = +-1.0 in elimination order (LDLT)
+  DevArray<double> L, arena, Y, avals, xbuf;
   int64_t xbuf_cap = 0;
-  int *d_flag = nullptr;
-  int *d_perm = nullptr, *d_first = nullptr, *d_b = nullptr, *d_ld = nullptr, *d_uld = nullptr;
-  int *d_below = nullptr, *d_rel = nullptr, *d_child_ptr = nullptr, *d_child = nullptr;
-  int64_t *d_rows_ptr = nullptr, *d_panel = nullptr, *d_upd = nullptr, *d_sol = nullptr;
-  int *d_glev_first = nullptr, *d_glev_root = nullptr;
-  int *d_lev_sn = nullptr, *d_chunk_sn = nullptr, *d_chunk_c0 = nullptr, *d_tab = nullptr;
-  int *d_asm_ptr = nullptr, *d_asm_src = nullptr;
-  int64_t *d_asm_dst = nullptr;
+  DevArray<int> d_flag;
+  DevArray<int> d_perm, d_first, d_b, d_ld, d_uld;
+  DevArray<int> d_below, d_rel, d_child_ptr, d_child;
+  DevArray<int64_t> d_rows_ptr, d_panel, d_upd, d_sol;
+  DevArray<int> d_glev_first, d_glev_root;
+  DevArray<int> d_lev_sn, d_chunk_sn, d_chunk_c0, d_tab;
+  DevArray<int> d_asm_ptr, d_asm_src;
+  DevArray<int64_t> d_asm_dst;
 };
 
 }  // namespace po

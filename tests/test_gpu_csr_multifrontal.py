@@ -39,9 +39,9 @@ def _vec(ctx, arr):
     return pa.PVec(ctx, len(arr)).from_numpy(np.asarray(arr, dtype=float))
 
 
-def pattern_problem(ctx, n, rowp, cols, data, dense_column_rows=0, sparse_factor="multifrontal"):
+def pattern_problem(ctx, n, rowp, cols, data, dense_column_rows=0, sparse_factor="multifrontal", before=None):
     """tests/test_gpu_csr.py: PatternProblem (fixed Jacobian entries, linear sparse constraints) on the chosen engine,
-    with the entries uploaded by one gradient evaluation"""
+    with the entries uploaded by one gradient evaluation; before(prob) is called ahead of that evaluation"""
     import paropt_amd as pa
 
     A = dense_jacobian(n, rowp, cols, data)
@@ -66,6 +66,8 @@ def pattern_problem(ctx, n, rowp, cols, data, dense_column_rows=0, sparse_factor
 
     prob = _P()
     assert prob.sparse_factor == sparse_factor
+    if before is not None:
+        before(prob)
     pa.InteriorPoint(prob, {"max_major_iters": 0}).optimize()
     return prob, A
 
@@ -77,9 +79,10 @@ def symbolic_shape(name, n, rowp, cols, dense_column_rows=0):
                                       sparse_factor="multifrontal"))
 
 
-def check_solves(ctx, prob, A, n, w, rng, r=0):
+def check_solves(ctx, prob, A, n, w, rng, r=0, sparse_factor="multifrontal"):
     """factor + apply with and without bw against np.linalg.solve on the dense S (tests/test_gpu_csr.py:
-    test_quasidef_solve_matches_dense), C left alone, a repeated factor + apply bit-identical"""
+    test_quasidef_solve_matches_dense), C left alone, a repeated factor + apply bit-identical; the factor line names
+    supernodes on the multifrontal engine and levels on the row factor"""
     import paropt_amd as pa
 
     x = _vec(ctx, np.full(n, 0.5))
@@ -90,7 +93,8 @@ def check_solves(ctx, prob, A, n, w, rng, r=0):
     pa.quasidef_factor(prob, x, dv, cv)
     np.testing.assert_array_equal(cv.to_numpy(), c)
     info = pa.quasidef_factor_info(prob)
-    assert info and "nnz(L)" in info and "nsnodes" in info and "nnz(K)" in info and "sparsity(L)" in info, info
+    assert info and "nnz(L)" in info and "nnz(K)" in info and "sparsity(L)" in info, info
+    assert ("nsnodes" if sparse_factor == "multifrontal" else "nlevels") in info, info
     assert info.endswith(" ndense %d" % r) if r else "ndense" not in info, info
     for with_bw in (True, False):
         bx = rng.standard_normal(n)

@@ -1,7 +1,9 @@
 // Host-side C++ of the product under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only, no GPU, no HIP
 // runtime): the in-repo LU (lu.cpp, the reference's dgetrf/dgetrs sites), the dense algebra of the bordered KKT solve
 // and of the linearised KKT residual (bordered.cpp), the one-time symbolic analysis of the sparse Cholesky
-// (csr.cpp::csr_analyse) and the option registry (options.cpp).  Built by
+// (csr.cpp::csr_analyse, both factor kinds; sparse_chol.cpp::chol_analyse with and without packed groups), the option
+// registry (options.cpp) and the owning device array DevArray (core.hpp) over malloc-backed stand-ins for the four
+// runtime calls it makes.  Built by
 // `make -C paropt_amd/csrc sanitize`, run by tests/test_host_sanitize.py.  Exit code 0 = every check passed and no
 // sanitizer report.
 #include <math.h>
@@ -234,7 +236,63 @@ static void test_dense_res_step() {
   }
 }
 
+// the multifrontal analysis of the same pattern: a permutation, supernodes that cover it, every entry of S0 inside L
+static void analyse_multifrontal(int64_t n, const std::vector<int> &rowp, const std::vector<int> &cols, bool expect_ok) {
+  CsrSymbolic sym;
+  const int64_t w = (int64_t)rowp.size() - 1;
+  const int rc = csr_analyse(n, w, rowp.data(), cols.data(), &sym, 0, PO_SPARSE_FACTOR_MULTIFRONTAL);
+  CHECK((rc == PO_OK) == expect_ok);
+  if (rc != PO_OK) return;
+  const CholSymbolic &c = sym.chol;
+  CHECK(sym.factor_kind == PO_SPARSE_FACTOR_MULTIFRONTAL && c.n == (int)w && sym.Lrowp.empty());
+  CHECK((int64_t)sym.perm.size() == w && (int64_t)sym.iperm.size() == w);
+  for (int64_t i = 0; i < w; i++) CHECK(sym.perm[i] >= 0 && sym.perm[i] < w && sym.iperm[sym.perm[i]] == (int)i);
+  CHECK((int)c.sn_first.size() == c.nsn + 1 && c.sn_first[0] == 0 && c.sn_first[c.nsn] == (int)w);
+  CHECK((int64_t)sym.ent_off.size() == sym.nnzS && sym.ent_a.size() == sym.ent_off.size());
+  for (int64_t off : sym.ent_off) CHECK(off >= 0 && off < c.Lsize);
+}
+
+// chol_analyse on a tridiagonal of 40 (both triangles by columns, as a caller passes a matrix): without packing, and with a positive cap on the
+// packed groups (switch 38, which chol_analyse reads)
+static void test_chol_analyse() {
+  const int n = 40;
+  std::vector<int> colp(1, 0), rows;
+  for (int j = 0; j < n; j++) {
+    if (j > 0) rows.push_back(j - 1);
+    rows.push_back(j);
+    if (j + 1 < n) rows.push_back(j + 1);
+    colp.push_back((int)rows.size());
+  }
+  for (int cap : {0, 16}) {
+    dbg_switch_set(SW_CHOL_PACK, cap);
+    CholSymbolic c;
+    CHECK(chol_analyse(n, colp.data(), rows.data(), PO_ORDER_ND, nullptr, &c) == PO_OK);
+    CHECK(c.n == n && c.pack_cap == cap && (int)c.perm.size() == n);
+    std::vector<char> seen(n, 0);
+    for (int i = 0; i < n; i++) {
+      CHECK(c.perm[i] >= 0 && c.perm[i] < n && c.iperm[c.perm[i]] == i);
+      if (c.perm[i] >= 0 && c.perm[i] < n) seen[c.perm[i]] = 1;
+    }
+    for (int i = 0; i < n; i++) CHECK(seen[i]);
+    CHECK((int)c.sn_first.size() == c.nsn + 1 && c.sn_first[c.nsn] == n && c.nnzL >= 2 * n - 1);
+    // of each entry the copy that is lower after the permutation is read: 2 n - 1 places in L, one source each
+    CHECK((int)c.asm_dst.size() == 2 * n - 1 && c.asm_src.size() == c.asm_dst.size() &&
+          c.asm_ptr.size() == c.asm_dst.size() + 1);
+    for (int64_t off : c.asm_dst) CHECK(off >= 0 && off < c.Lsize);
+    // every front is either in a packed group or in its level's list, once
+    size_t packed = 0;
+    for (size_t g = 0; g < c.grp_first.size(); g++) packed += (size_t)(c.grp_root[g] - c.grp_first[g] + 1);
+    CHECK(cap > 0 ? !c.grp_first.empty() : c.grp_first.empty());
+    CHECK(packed + c.lev_sn.size() == (size_t)c.nsn);
+    int counts[CHF_COUNT];
+    chol_kernel_forms(c, 40, counts);
+    CHECK((counts[CHF_PACK_FACTOR] > 0) == (cap > 0));
+  }
+  dbg_switch_set(SW_CHOL_PACK, -1);
+}
+
 static void analyse(int64_t n, const std::vector<int> &rowp, const std::vector<int> &cols, bool expect_ok) {
+  analyse_multifrontal(n, rowp, cols, expect_ok);
   CsrSymbolic sym;
   const int64_t w = (int64_t)rowp.size() - 1;
   const int rc = csr_analyse(n, w, rowp.data(), cols.data(), &sym);
@@ -314,6 +372,70 @@ static void test_csr() {
   }
 }
 
+// Stand-ins for the runtime calls of DevArray: "device" memory is the heap, so the sanitizers see every byte of it.
+static long g_dev_allocs = 0;
+extern "C" {
+hipError_t hipMalloc(void **ptr, size_t size) {
+  *ptr = malloc(size ? size : 1);
+  g_dev_allocs++;
+  return *ptr ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void *ptr) {
+  if (ptr) g_dev_allocs--;
+  free(ptr);
+  return hipSuccess;
+}
+hipError_t hipMemset(void *dst, int value, size_t sizeBytes) {
+  memset(dst, value, sizeBytes);
+  return hipSuccess;
+}
+hipError_t hipMemcpy(void *dst, const void *src, size_t sizeBytes, hipMemcpyKind) {
+  memcpy(dst, src, sizeBytes);
+  return hipSuccess;
+}
+}
+
+static void test_dev_array() {
+  const long long base = live_bytes().load();
+  {
+    DevArray<double> empty;  // destroyed empty
+    CHECK(empty.get() == nullptr && empty.size() == 0 && !empty);
+    empty.reset();
+    DevArray<double> a;
+    CHECK(a.alloc(10, true) == PO_OK && a.size() == 10);
+    CHECK(live_bytes().load() == base + 80);
+    for (int i = 0; i < 10; i++) CHECK(a[i] == 0.0);
+    double *raw = a;
+    CHECK(raw == a.get());
+    DevArray<int> t;
+    const std::vector<int> v3 = {1, 2, 3};
+    CHECK(t.upload(v3) == PO_OK && t.size() == 7);  // size() + 4, zero-filled, then the copy
+    for (int i = 0; i < 7; i++) CHECK(t[i] == (i < 3 ? i + 1 : 0));
+    CHECK(live_bytes().load() == base + 80 + 28);
+    const std::vector<int> v9 = {9, 8, 7, 6, 5, 4, 3, 2, 1};
+    CHECK(t.upload(v9) == PO_OK && t.size() == 13 && t[8] == 1 && t[12] == 0);  // over a live array
+    CHECK(t.upload(std::vector<int>()) == PO_OK && t.size() == 4 && t[3] == 0);  // an empty table: the padding alone
+    CHECK(live_bytes().load() == base + 80 + 16 && g_dev_allocs == 2);
+    DevArray<double> b(std::move(a));  // move construction
+    CHECK(a.get() == nullptr && a.size() == 0 && b.get() == raw && b.size() == 10);
+    DevArray<double> c;
+    CHECK(c.alloc(3, false) == PO_OK);
+    c = std::move(b);  // move assignment over a live array: its own memory is freed
+    CHECK(b.get() == nullptr && c.get() == raw && c.size() == 10 && g_dev_allocs == 2);
+    CHECK(live_bytes().load() == base + 80 + 16);
+    t.reset();
+    CHECK(t.get() == nullptr && t.size() == 0 && live_bytes().load() == base + 80);
+    t.reset();  // twice is once
+    struct Group {  // what CsrSparse does with its dense columns: an empty group assigned over a full one
+      DevArray<double> x, y;
+    } g;
+    CHECK(g.x.alloc(5, true) == PO_OK && g.y.alloc(6, false) == PO_OK && g_dev_allocs == 3);
+    g = Group();
+    CHECK(g.x.get() == nullptr && g_dev_allocs == 1);
+  }  // c is destroyed full
+  CHECK(live_bytes().load() == base && g_dev_allocs == 0);
+}
+
 static void test_options() {
   Options o;
   o.addTrustRegionDefaults();
@@ -341,6 +463,8 @@ int main() {
   test_bordered();
   test_dense_res_step();
   test_csr();
+  test_chol_analyse();
+  test_dev_array();
   test_options();
   if (fails) {
     fprintf(stderr, "%d check(s) failed\n", fails);
