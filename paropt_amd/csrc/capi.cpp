@@ -213,17 +213,7 @@ int po_ctx_comm_init_callback(po_ctx ctx, int rank, int size, po_allgather_fn fn
 // ---- vectors ------------------------------------------------------------------------------------
 // getArray contract (src/ParOptVec.cpp:212-217: the pointer IS the data).  While a mirror is live, reads through
 // the ABI see what the host wrote and results of ABI operations are visible through the pointer at once.
-static int mirror_up(Vec *v) {
-  if (!v || !v->h_live || !v->h || v->n <= 0) return PO_OK;
-  PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, v->ctx->stream));
-  return PO_OK;  // stream-ordered before the kernels that follow
-}
-static int mirror_down(Vec *v) {
-  if (!v || !v->h_live || !v->h || v->n <= 0) return PO_OK;
-  PO_HIP(hipMemcpyAsync(v->h, v->d, sizeof(double) * (size_t)v->n, hipMemcpyDeviceToHost, v->ctx->stream));
-  PO_HIP(hipStreamSynchronize(v->ctx->stream));
-  return PO_OK;
-}
+// (vec_mirror_upload is stream-ordered before the kernels that follow; vec_mirror_refresh ends in a stream sync)
 int po_vec_create(po_ctx ctx, int64_t nlocal, po_vec *out) {
   PO_CHECK_PTR(ctx);
   PO_CHECK_PTR(out);
@@ -253,43 +243,43 @@ int po_vec_size(po_vec v, int64_t *nlocal) {
 int po_vec_set(po_vec v, double alpha) {
   PO_CHECK_PTR(v);
   PO_TRY(k_fill(v->ctx, v->d, v->n, alpha));
-  return mirror_down(v);
+  return vec_mirror_refresh(v);
 }
 int po_vec_zero(po_vec v) {
   PO_CHECK_PTR(v);
   PO_TRY(k_fill(v->ctx, v->d, v->n, 0.0));
-  return mirror_down(v);
+  return vec_mirror_refresh(v);
 }
 int po_vec_copy(po_vec dst, po_vec src) {
   PO_CHECK_PTR(dst);
   PO_CHECK_PTR(src);
   PO_TRY(same_layout(dst, src));
-  PO_TRY(mirror_up(src));
+  PO_TRY(vec_mirror_upload(src));
   PO_TRY(k_copy(dst->ctx, dst->d, src->d, dst->n));
-  return mirror_down(dst);
+  return vec_mirror_refresh(dst);
 }
 int po_vec_scale(po_vec v, double alpha) {
   PO_CHECK_PTR(v);
-  PO_TRY(mirror_up(v));
+  PO_TRY(vec_mirror_upload(v));
   PO_TRY(k_scale(v->ctx, v->d, v->n, alpha));
-  return mirror_down(v);
+  return vec_mirror_refresh(v);
 }
 int po_vec_axpy(po_vec y, double alpha, po_vec x) {
   PO_CHECK_PTR(y);
   PO_CHECK_PTR(x);
   PO_TRY(same_layout(y, x));
-  PO_TRY(mirror_up(x));
-  PO_TRY(mirror_up(y));
+  PO_TRY(vec_mirror_upload(x));
+  PO_TRY(vec_mirror_upload(y));
   PO_TRY(k_axpy(y->ctx, y->d, alpha, x->d, y->n));
-  return mirror_down(y);
+  return vec_mirror_refresh(y);
 }
 int po_vec_dot(po_vec x, po_vec y, double *out) {
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(y);
   PO_CHECK_PTR(out);
   PO_TRY(same_layout(x, y));
-  PO_TRY(mirror_up(x));
-  PO_TRY(mirror_up(y));
+  PO_TRY(vec_mirror_upload(x));
+  PO_TRY(vec_mirror_upload(y));
   return k_reduce1(x->ctx, RED_DOT, x->d, y->d, x->n, out);
 }
 int po_vec_mdot(po_vec x, const po_vec *vecs, int nvecs, double *out) {
@@ -301,10 +291,10 @@ int po_vec_mdot(po_vec x, const po_vec *vecs, int nvecs, double *out) {
   for (int j = 0; j < nvecs; j++) {
     PO_CHECK_PTR(vecs[j]);
     PO_TRY(same_layout(x, vecs[j]));
-    PO_TRY(mirror_up(vecs[j]));
+    PO_TRY(vec_mirror_upload(vecs[j]));
     p[j] = vecs[j]->d;
   }
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   // wider panels than one kernel accepts are processed in slabs
   int j0 = 0;
   while (j0 < nvecs) {
@@ -318,7 +308,7 @@ int po_vec_norm(po_vec x, double *out) {
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(out);
   double ss = 0.0;
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   PO_TRY(k_reduce1(x->ctx, RED_SUMSQ, x->d, nullptr, x->n, &ss));
   *out = sqrt(ss);
   return PO_OK;
@@ -326,13 +316,13 @@ int po_vec_norm(po_vec x, double *out) {
 int po_vec_maxabs(po_vec x, double *out) {
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(out);
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   return k_reduce1(x->ctx, RED_AMAX, x->d, nullptr, x->n, out);
 }
 int po_vec_l1norm(po_vec x, double *out) {
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(out);
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   return k_reduce1(x->ctx, RED_ASUM, x->d, nullptr, x->n, out);
 }
 static int ensure_mirror(po_vec v) {
@@ -449,18 +439,18 @@ int po_vec_maxpy(po_vec y, double beta, const double *alpha, const po_vec *vecs,
   for (int j = 0; j < nvecs; j++) {
     PO_CHECK_PTR(vecs[j]);
     PO_TRY(same_layout(y, vecs[j]));
-    PO_TRY(mirror_up(vecs[j]));
+    PO_TRY(vec_mirror_upload(vecs[j]));
     p[j] = vecs[j]->d;
   }
-  PO_TRY(mirror_up(y));
+  PO_TRY(vec_mirror_upload(y));
   PO_TRY(k_panel_axpy(y->ctx, y->d, 0.0, nullptr, beta, alpha, p.data(), nvecs, y->n));
-  return mirror_down(y);
+  return vec_mirror_refresh(y);
 }
 int po_vec_fill_hash(po_vec v, uint64_t seed, uint64_t array_id, int64_t offset, double scale,
                      double shift) {
   PO_CHECK_PTR(v);
   PO_TRY(k_fill_hash(v->ctx, v->d, v->n, seed, array_id, offset, scale, shift));
-  return mirror_down(v);
+  return vec_mirror_refresh(v);
 }
 
 // ---- quasi-Newton -------------------------------------------------------------------------------
@@ -550,8 +540,8 @@ int po_qn_update(po_qn qn, po_vec s, po_vec y, int *rc) {
   PO_CHECK_PTR(s);
   PO_CHECK_PTR(y);
   int r = 0;
-  PO_TRY(mirror_up(s));
-  PO_TRY(mirror_up(y));
+  PO_TRY(vec_mirror_upload(s));
+  PO_TRY(vec_mirror_upload(y));
   PO_TRY(qn->qn->update(s, y, &r));
   if (rc) *rc = r;
   return PO_OK;
@@ -560,18 +550,18 @@ int po_qn_mult(po_qn qn, po_vec x, po_vec y) {
   PO_CHECK_PTR(qn);
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(y);
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   PO_TRY(qn->qn->mult(x, y));
-  return mirror_down(y);
+  return vec_mirror_refresh(y);
 }
 int po_qn_mult_add(po_qn qn, double alpha, po_vec x, po_vec y) {
   PO_CHECK_PTR(qn);
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(y);
-  PO_TRY(mirror_up(x));
-  PO_TRY(mirror_up(y));
+  PO_TRY(vec_mirror_upload(x));
+  PO_TRY(vec_mirror_upload(y));
   PO_TRY(qn->qn->multAdd(alpha, x, y));
-  return mirror_down(y);
+  return vec_mirror_refresh(y);
 }
 int po_qn_get_compact(po_qn qn, int *size, double *b0, const double **d0, const double **M,
                       const po_vec **Z) {
@@ -1163,7 +1153,7 @@ int po_problem_sizes(po_problem p, int64_t *nlocal, int64_t *offset, int *ncon) 
 int po_problem_eval_obj_con(po_problem p, po_vec x, double *fobj, double *cons) {
   PO_CHECK_PTR(p);
   PO_CHECK_PTR(x);
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   return p->p->evalObjCon(x, fobj, cons);
 }
 int po_problem_eval_obj_con_gradient(po_problem p, po_vec x, po_vec g, const po_vec *Ac) {
@@ -1172,18 +1162,18 @@ int po_problem_eval_obj_con_gradient(po_problem p, po_vec x, po_vec g, const po_
   PO_CHECK_PTR(g);
   std::vector<Vec *> a(p->p->ncon > 0 ? p->p->ncon : 1);
   for (int j = 0; j < p->p->ncon; j++) a[j] = Ac[j];
-  PO_TRY(mirror_up(x));
+  PO_TRY(vec_mirror_upload(x));
   int rc = p->p->evalObjConGradient(x, g, a.data());
-  PO_TRY(mirror_down(g));
-  for (int j = 0; j < p->p->ncon; j++) PO_TRY(mirror_down(a[j]));
+  PO_TRY(vec_mirror_refresh(g));
+  for (int j = 0; j < p->p->ncon; j++) PO_TRY(vec_mirror_refresh(a[j]));
   return rc;
 }
 int po_problem_get_vars_and_bounds(po_problem p, po_vec x, po_vec lb, po_vec ub) {
   PO_CHECK_PTR(p);
   int rc = p->p->getVarsAndBounds(x, lb, ub);
-  PO_TRY(mirror_down(x));
-  PO_TRY(mirror_down(lb));
-  PO_TRY(mirror_down(ub));
+  PO_TRY(vec_mirror_refresh(x));
+  PO_TRY(vec_mirror_refresh(lb));
+  PO_TRY(vec_mirror_refresh(ub));
   return rc;
 }
 
@@ -1218,7 +1208,7 @@ int po_ip_check_gradients(po_ip ip, double dh, const char **report) {
 }
 int po_ip_check_merit_func_gradient(po_ip ip, po_vec xpt, double dh, double *fd, double *actual) {
   PO_CHECK_PTR(ip);
-  if (xpt) PO_TRY(mirror_up(xpt));
+  if (xpt) PO_TRY(vec_mirror_upload(xpt));
   double out[2] = {0.0, 0.0};
   PO_TRY(ip->ip->checkMeritFuncGradient(xpt, dh, out));
   if (fd) *fd = out[0];
@@ -1336,10 +1326,10 @@ int po_ip_eval_hvec(po_ip ip, const double *z, po_vec zw, po_vec px, po_vec hvec
   PO_CHECK_PTR(ip);
   PO_CHECK_PTR(px);
   PO_CHECK_PTR(hvec);
-  if (zw) PO_TRY(mirror_up(zw));
-  PO_TRY(mirror_up(px));
+  if (zw) PO_TRY(vec_mirror_upload(zw));
+  PO_TRY(vec_mirror_upload(px));
   PO_TRY(ip->ip->evalHvec(z, zw, px, hvec));
-  return mirror_down(hvec);
+  return vec_mirror_refresh(hvec);
 }
 int po_ip_reset_design_and_bounds(po_ip ip) {
   PO_CHECK_PTR(ip);

@@ -29,8 +29,8 @@ struct EigSynthetic {
 // kernels of the model evaluations read the device copies
 int release_mirror(Vec *v, bool upload) {
   if (!v) return PO_OK;
-  if (v->h_live && upload && v->h && v->n > 0) {
-    PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, v->ctx->stream));
+  if (upload && vec_mirror_live(v)) {
+    PO_TRY(vec_mirror_upload(v));
     PO_HIP(hipStreamSynchronize(v->ctx->stream));
   }
   v->h_live = 0;
@@ -241,58 +241,23 @@ int po_eig_destroy(po_eig approx) {
   delete approx;
   return PO_OK;
 }
-// tmp = M (H^T x): the N x N product of multAdd / evalApproximationGradient (.cpp:52-64, 108-120)
-static int eig_scaled_dots(CompactEigenApprox *e, Vec *x, std::vector<double> *dots, std::vector<double> *scaled) {
-  const int N = e->N;
-  std::vector<const double *> hp = e->hPointers();
-  dots->assign(N, 0.0);
-  PO_TRY(k_mdot(e->ctx, x->d, hp.data(), N, e->n, dots->data()));
-  scaled->assign(N, 0.0);
-  for (int i = 0; i < N; i++) {
-    double v = 0.0;
-    for (int j = 0; j < N; j++) v += e->M[(size_t)i * N + j] * (*dots)[j];
-    (*scaled)[i] = v;
-  }
-  return PO_OK;
-}
 int po_eig_mult_add(po_eig approx, double alpha, po_vec x, po_vec y) {
   PO_CHECK_PTR(approx);
   PO_CHECK_PTR(x);
   PO_CHECK_PTR(y);
-  CompactEigenApprox *e = approx->e;
-  std::vector<double> dots, sc;
-  PO_TRY(eig_scaled_dots(e, x, &dots, &sc));
-  for (double &v : sc) v *= alpha;
-  std::vector<const double *> hp = e->hPointers();
-  return k_panel_axpy(e->ctx, y->d, 0.0, nullptr, 1.0, sc.data(), hp.data(), e->N, e->n);
+  return approx->e->multAdd(alpha, x, y);
 }
 int po_eig_eval_approximation(po_eig approx, po_vec s, po_vec t, double *value) {
   PO_CHECK_PTR(approx);
   PO_CHECK_PTR(value);
-  CompactEigenApprox *e = approx->e;
-  double c = e->c0;
-  if (s && t) {  // the reference only looks at s (t is a scratch argument there too)
-    const int N = e->N;
-    std::vector<const double *> P = e->hPointers();
-    P.push_back(e->g0->d);
-    std::vector<double> dots(N + 1, 0.0);
-    PO_TRY(k_mdot(e->ctx, s->d, P.data(), N + 1, e->n, dots.data()));
-    c += dots[N];
-    for (int i = 0; i < N; i++)
-      for (int j = 0; j < N; j++) c += 0.5 * e->M[(size_t)i * N + j] * dots[i] * dots[j];
-  }
-  *value = c;
-  return PO_OK;
+  // (the reference only looks at s: t is a scratch argument there too)
+  return approx->e->evalApproximation(s && t ? static_cast<Vec *>(s) : nullptr, value);
 }
 int po_eig_eval_approximation_gradient(po_eig approx, po_vec s, po_vec grad) {
   PO_CHECK_PTR(approx);
   PO_CHECK_PTR(s);
   PO_CHECK_PTR(grad);
-  CompactEigenApprox *e = approx->e;
-  std::vector<double> dots, sc;
-  PO_TRY(eig_scaled_dots(e, s, &dots, &sc));
-  std::vector<const double *> hp = e->hPointers();
-  return k_panel_axpy(e->ctx, grad->d, 1.0, e->g0->d, 0.0, sc.data(), hp.data(), e->N, e->n);
+  return approx->e->evalApproximationGradient(s, grad);
 }
 int po_eigqn_create(po_qn qn, po_eig approx, int index, po_qn *out) {
   PO_CHECK_PTR(approx);

@@ -165,21 +165,7 @@ void InteriorPoint::setPenaltyGammaArray(const double *gamma) {  // :1160-1172 (
 int InteriorPoint::createQuasiNewton() {  // ctor :262-292
   if (qn_created) return PO_OK;
   qn_created = true;
-  const std::string qt = options.str("qn_type");
-  const int msub = options.integer("qn_subspace_size");
-  if (qt == "bfgs") {
-    LBFGS *b = new LBFGS(ctx, n, msub);
-    b->setBFGSUpdateType(std::string(options.str("qn_update_type")) == "damped_update"
-                             ? PO_BFGS_DAMPED_UPDATE
-                             : PO_BFGS_SKIP_NEGATIVE_CURVATURE);
-    qn = b;
-  } else if (qt == "sr1") {
-    qn = new LSR1(ctx, n, msub);
-  }
-  if (qn) {
-    const std::string dt = options.str("qn_diag_type");
-    qn->setInitDiagonalType(dt == "yts_over_sts" ? PO_QN_YTS_OVER_STS : PO_QN_YTY_OVER_YTS);
-  }
+  qn = make_quasi_newton(ctx, n, options);
   qn_handle.qn = qn;
   return PO_OK;
 }
@@ -348,22 +334,15 @@ int InteriorPoint::clampCounts(double out[8]) {
 // A host mirror the caller still holds for one of the solver's vectors (getOptimizedPoint + getArray) is the vector's
 // data while it is live: after an internal writer has changed the device copy the mirror is refreshed, so that the
 // caller's pointer shows the new values (the reference has one buffer) and optimize()'s upload of live mirrors cannot
-// put the old ones back.
-static int refreshLiveMirror(Vec *v) {
-  if (!v || !v->h_live || !v->h || v->n <= 0) return PO_OK;
-  PO_HIP(hipMemcpyAsync(v->h, v->d, sizeof(double) * (size_t)v->n, hipMemcpyDeviceToHost, v->ctx->stream));
-  PO_HIP(hipStreamSynchronize(v->ctx->stream));
-  return PO_OK;
-}
-
+// put the old ones back (vec_mirror_refresh).
 int InteriorPoint::resetDesignAndBounds() {  // :1249-1251
   stateReplaced();
   bounds_uni[0] = bounds_uni[1] = 0;  // (found again by the next optimize())
   int rc = prob->getVarsAndBounds(x, lb, ub);
   if (rc != 0) return PO_ERR_USER;
-  PO_TRY(refreshLiveMirror(x));
-  PO_TRY(refreshLiveMirror(lb));
-  return refreshLiveMirror(ub);
+  PO_TRY(vec_mirror_refresh(x));
+  PO_TRY(vec_mirror_refresh(lb));
+  return vec_mirror_refresh(ub);
 }
 
 void InteriorPoint::resetQuasiNewtonHessian() {
@@ -1409,7 +1388,7 @@ int InteriorPoint::scaleKKTStep(double tau, double comp, double *alpha_x, double
     // Validity: comp_prod / iterate_logs belong to (x, zl, zu) as the last residual pass saw them.  Every internal
     // writer of the iterate clears the flags; an iteration callback or a getArray view must not WRITE the iterate
     // mid-solve (po_ip_set_iteration_callback: an observer) -- resetDesignAndBounds / readSolutionFile between solves
-    // refresh mirrors and flags (refreshLiveMirror)
+    // refresh mirrors and flags (vec_mirror_refresh)
     out[0] = comp_prod + ax * fused_merit.S10 + az * fused_merit.S01 + ax * az * fused_merit.S11;
     out[1] = comp_count;
     merit_cache = {.pos_log = iterate_logs[0], .neg_log = iterate_logs[1], .ppos = fused_merit.ppos,
@@ -1981,10 +1960,8 @@ int InteriorPoint::optimize(const char *checkpoint) {
     Vec *mine[] = {x, zl, zu, wvar[0], wvar[1], wvar[2], wvar[3], wvar[4]};
     bool any = false;
     for (Vec *v : mine) {
-      if (v && v->h_live && v->h && v->n > 0) {
-        PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, ctx->stream));
-        any = true;
-      }
+      any = any || vec_mirror_live(v);
+      PO_TRY(vec_mirror_upload(v));
       if (v) v->h_live = 0;
     }
     if (any) PO_HIP(hipStreamSynchronize(ctx->stream));  // the pinned mirrors may be rewritten by the caller at once
@@ -2416,10 +2393,13 @@ void InteriorPoint::flushHistory() {
               history.substr(len > 4000 ? len - 4000 : 0).c_str());
     }
   }
+  write_history_file(ctx, fname, "ParOptInteriorPoint", history);
+}
+void write_history_file(Ctx *ctx, const std::string &fname, const char *solver, const std::string &history) {
   if (ctx->rank != 0 || fname.empty()) return;
   FILE *fp = fopen(fname.c_str(), "w");
   if (!fp) return;
-  fputs("ParOptInteriorPoint (paropt_amd, MI355X)\n", fp);
+  fprintf(fp, "%s (paropt_amd, MI355X)\n", solver);
   fputs(history.c_str(), fp);
   fclose(fp);
 }
@@ -2582,7 +2562,7 @@ int InteriorPoint::readSolutionFile(const char *filename) {
     }
   }
   Vec *written[5] = {x, zl, zu, has_w ? wvar[0] : nullptr, has_w ? wvar[1] : nullptr};
-  for (Vec *v : written) PO_TRY(refreshLiveMirror(v));
+  for (Vec *v : written) PO_TRY(vec_mirror_refresh(v));
   return PO_OK;
 }
 

@@ -48,6 +48,9 @@ class Options {
   std::map<std::string, Entry> e;
 };
 
+// the iteration table of a solver, written to `fname` on the root rank when optimize() returns (empty name: no file)
+void write_history_file(Ctx *ctx, const std::string &fname, const char *solver, const std::string &history);
+
 class InteriorPoint {
  public:
   InteriorPoint(Problem *prob);

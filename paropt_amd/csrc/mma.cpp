@@ -14,12 +14,7 @@
 namespace po {
 
 MMA::MMA(Problem *p)
-    : Problem(p->ctx, p->nlocal, p->ncon, p->ninequality), cons(p->ncon, 0.0), b(p->ncon, 0.0), z(p->ncon, 0.0),
-      prob(p), m(p->ncon) {
-  offset = p->offset;
-  nglobal = p->nglobal;
-  nwcon = p->nwcon;
-  nwinequality = p->nwinequality;
+    : Problem(p), cons(p->ncon, 0.0), b(p->ncon, 0.0), z(p->ncon, 0.0), prob(p), m(p->ncon) {
   opts.addMMADefaults();
   opts.set("output_file", "");
   gcmma.rho.assign(m + 1, 0.0);
@@ -456,13 +451,7 @@ int MMA::optimize() {  // :318-379
 }
 
 void MMA::flushHistory() {
-  const std::string fname = options().str("mma_output_file");
-  if (ctx->rank != 0 || fname.empty()) return;
-  FILE *fp = fopen(fname.c_str(), "w");
-  if (!fp) return;
-  fputs("ParOptMMA (paropt_amd, MI355X)\n", fp);
-  fputs(history.c_str(), fp);
-  fclose(fp);
+  write_history_file(ctx, options().str("mma_output_file"), "ParOptMMA", history);
 }
 
 // ---- the subproblem ---------------------------------------------------------------------------------

@@ -15,6 +15,8 @@ namespace po {
 class Problem {
  public:
   Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_);
+  // the layout of another problem (sizes, offset, sparse-constraint counts): the model problems that wrap one
+  explicit Problem(const Problem *like);
   virtual ~Problem();
   virtual int getVarsAndBounds(Vec *x, Vec *lb, Vec *ub) = 0;
   virtual int evalObjCon(Vec *x, double *fobj, double *cons) = 0;

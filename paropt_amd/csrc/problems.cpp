@@ -115,6 +115,12 @@ Problem::Problem(Ctx *c, int64_t nlocal_, int ncon_, int nineq_)
     : ctx(c), nlocal(nlocal_), offset(0), nglobal(nlocal_), ncon(ncon_), ninequality(nineq_) {
   (void)chooseSolver(nullptr, 1);  // (the generic scalar form allocates nothing)
 }
+Problem::Problem(const Problem *like) : Problem(like->ctx, like->nlocal, like->ncon, like->ninequality) {
+  offset = like->offset;
+  nglobal = like->nglobal;
+  nwcon = like->nwcon;
+  nwinequality = like->nwinequality;
+}
 Problem::~Problem() {
   delete solver;
   delete csr;

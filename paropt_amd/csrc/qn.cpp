@@ -6,6 +6,8 @@
 // Z^T s it already formed inside mult(s) (:183), so they are reused.
 #include "qn.hpp"
 
+#include "ip.hpp"  // Options (make_quasi_newton)
+
 #include <math.h>
 #include <string.h>
 
@@ -48,6 +50,18 @@ Vec *vec_new(Ctx *c, int64_t n) {
   g_live_vecs++;
   live_bytes() += (long long)bytes;
   return v;
+}
+
+int vec_mirror_upload(Vec *v) {
+  if (!vec_mirror_live(v)) return PO_OK;
+  PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, v->ctx->stream));
+  return PO_OK;
+}
+int vec_mirror_refresh(Vec *v) {
+  if (!vec_mirror_live(v)) return PO_OK;
+  PO_HIP(hipMemcpyAsync(v->h, v->d, sizeof(double) * (size_t)v->n, hipMemcpyDeviceToHost, v->ctx->stream));
+  PO_HIP(hipStreamSynchronize(v->ctx->stream));
+  return PO_OK;
 }
 
 void vec_decref(Vec *v) {
@@ -418,13 +432,29 @@ int LSR1::ensureZ() const {
   return k_panel_lincomb(ctx, zd.data(), 1.0, yp.data(), -b0, sp.data(), k, n);
 }
 
+CompactQuasiNewton *make_quasi_newton(Ctx *ctx, int64_t n, const Options &options) {  // ctor :262-292
+  CompactQuasiNewton *qn = nullptr;
+  const std::string qt = options.str("qn_type");
+  const int msub = options.integer("qn_subspace_size");
+  if (qt == "bfgs") {
+    LBFGS *b = new LBFGS(ctx, n, msub);
+    b->setBFGSUpdateType(std::string(options.str("qn_update_type")) == "damped_update"
+                             ? PO_BFGS_DAMPED_UPDATE
+                             : PO_BFGS_SKIP_NEGATIVE_CURVATURE);
+    qn = b;
+  } else if (qt == "sr1") {
+    qn = new LSR1(ctx, n, msub);
+  }
+  if (qn) {
+    const std::string dt = options.str("qn_diag_type");
+    qn->setInitDiagonalType(dt == "yts_over_sts" ? PO_QN_YTS_OVER_STS : PO_QN_YTY_OVER_YTS);
+  }
+  return qn;
+}
+
 // ------------------------------------------------------------------------------------------------
 // A user-written approximation behind a callback table (include/paropt_amd.h, po_qn_callbacks)
-static int upload_live(Vec *v) {  // a live host mirror is the authoritative copy; the callback reads the device
-  if (!v || !v->h_live || !v->h || v->n <= 0) return PO_OK;
-  PO_HIP(hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, v->ctx->stream));
-  return PO_OK;
-}
+// (a live host mirror is the authoritative copy; the callbacks read the device: vec_mirror_upload ahead of each)
 
 CallbackQuasiNewton::CallbackQuasiNewton(Ctx *ctx_, int64_t n_, const po_qn_callbacks &cb_)
     : CompactQuasiNewton(ctx_, n_, 0, false), cb(cb_), status(PO_OK) {}
@@ -484,7 +514,7 @@ int CallbackQuasiNewton::refresh() {
                                 memcmp(M.data(), Mu, sizeof(double) * (size_t)k * k) == 0));
   b0 = b;
   Z.assign(Zu, Zu + k);
-  for (Vec *v : Z) PO_TRY(upload_live(v));
+  for (Vec *v : Z) PO_TRY(vec_mirror_upload(v));
   if (!same) {  // the LU is redone only when k, d or M changed
     d0.assign(d, d + k);
     M.assign(Mu, Mu + (size_t)k * k);
@@ -504,10 +534,10 @@ void CallbackQuasiNewton::reset() {
 
 int CallbackQuasiNewton::updateAt(Vec *x, const double *z, Vec *zw, Vec *s, Vec *y, const double *, int *rc) {
   if (status != PO_OK) return status;
-  PO_TRY(upload_live(x));
-  PO_TRY(upload_live(zw));
-  PO_TRY(upload_live(s));
-  PO_TRY(upload_live(y));
+  PO_TRY(vec_mirror_upload(x));
+  PO_TRY(vec_mirror_upload(zw));
+  PO_TRY(vec_mirror_upload(s));
+  PO_TRY(vec_mirror_upload(y));
   int r = 0;
   if (cb.update(cb.user, static_cast<po_vec>(x), z, static_cast<po_vec>(zw), static_cast<po_vec>(s),
                 static_cast<po_vec>(y), &r) != 0)
@@ -519,8 +549,8 @@ int CallbackQuasiNewton::updateAt(Vec *x, const double *z, Vec *zw, Vec *s, Vec 
 int CallbackQuasiNewton::updateMult(Vec *x, const double *z, Vec *zw) {
   if (status != PO_OK) return status;
   if (!cb.update_multipliers) return 0;
-  PO_TRY(upload_live(x));
-  PO_TRY(upload_live(zw));
+  PO_TRY(vec_mirror_upload(x));
+  PO_TRY(vec_mirror_upload(zw));
   if (cb.update_multipliers(cb.user, static_cast<po_vec>(x), z, static_cast<po_vec>(zw)) != 0)
     return failed(PO_ERR_USER, "update_multipliers");
   return refresh();
@@ -528,7 +558,7 @@ int CallbackQuasiNewton::updateMult(Vec *x, const double *z, Vec *zw) {
 
 int CallbackQuasiNewton::mult(Vec *x, Vec *y) {
   if (status != PO_OK) return status;
-  PO_TRY(upload_live(y));
+  PO_TRY(vec_mirror_upload(y));
   if (cb.mult(cb.user, static_cast<po_vec>(x), static_cast<po_vec>(y)) != 0) {
     set_error("user quasi-Newton: mult failed");
     return PO_ERR_USER;

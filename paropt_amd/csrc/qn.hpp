@@ -12,6 +12,13 @@ namespace po {
 
 Vec *vec_new(Ctx *c, int64_t n);
 void vec_decref(Vec *v);
+// The two directions of the getArray contract (src/ParOptVec.cpp:212-217: the pointer IS the data) for a host mirror
+// that is live, i.e. handed out and authoritative.  upload: asynchronous host-to-device copy on the vector's stream;
+// refresh: device-to-host copy followed by a stream sync.  A null vector, a mirror that is not live and an empty vector
+// are no-ops.  Neither changes h_live.
+inline bool vec_mirror_live(const Vec *v) { return v && v->h_live && v->h && v->n > 0; }
+int vec_mirror_upload(Vec *v);
+int vec_mirror_refresh(Vec *v);
 void live_objects(long *vecs, long long *bytes);
 void mirror_created();
 void mirror_freed();
@@ -127,6 +134,11 @@ class LBFGS : public CompactQuasiNewton {
   void computeMatUpdate();
   int update_type;
 };
+
+class Options;
+// the approximation that qn_type, qn_subspace_size, qn_update_type and qn_diag_type of a registry ask for (null for
+// "none"); owned by the caller
+CompactQuasiNewton *make_quasi_newton(Ctx *ctx, int64_t n, const Options &options);
 
 class LSR1 : public CompactQuasiNewton {
  public:

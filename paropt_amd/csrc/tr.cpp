@@ -44,6 +44,43 @@ std::vector<const double *> CompactEigenApprox::hPointers() const {
   for (Vec *v : hvecs) p.push_back(v->d);
   return p;
 }
+void CompactEigenApprox::applyM(const double *h, double *out) const {
+  for (int i = 0; i < N; i++) {
+    double s = 0.0;
+    for (int j = 0; j < N; j++) s += M[(size_t)i * N + j] * h[j];
+    out[i] = s;
+  }
+}
+double CompactEigenApprox::quadraticForm(const double *h, double c) const {
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < N; j++) c += 0.5 * M[(size_t)i * N + j] * h[i] * h[j];
+  return c;
+}
+int CompactEigenApprox::multAdd(double alpha, Vec *x, Vec *y) const {
+  std::vector<const double *> hp = hPointers();
+  std::vector<double> dots(N, 0.0), sc(N, 0.0);
+  PO_TRY(k_mdot(ctx, x->d, hp.data(), N, n, dots.data()));
+  applyM(dots.data(), sc.data());
+  for (double &v : sc) v *= alpha;
+  return k_panel_axpy(ctx, y->d, 0.0, nullptr, 1.0, sc.data(), hp.data(), N, n);
+}
+int CompactEigenApprox::evalApproximation(Vec *s, double *value) const {
+  *value = c0;
+  if (!s) return PO_OK;
+  std::vector<const double *> P = hPointers();
+  P.push_back(g0->d);
+  std::vector<double> dots(N + 1, 0.0);
+  PO_TRY(k_mdot(ctx, s->d, P.data(), N + 1, n, dots.data()));
+  *value = quadraticForm(dots.data(), c0 + dots[N]);
+  return PO_OK;
+}
+int CompactEigenApprox::evalApproximationGradient(Vec *s, Vec *grad) const {
+  std::vector<const double *> hp = hPointers();
+  std::vector<double> dots(N, 0.0), sc(N, 0.0);
+  PO_TRY(k_mdot(ctx, s->d, hp.data(), N, n, dots.data()));
+  applyM(dots.data(), sc.data());
+  return k_panel_axpy(ctx, grad->d, 1.0, g0->d, 0.0, sc.data(), hp.data(), N, n);
+}
 
 EigenQuasiNewton::EigenQuasiNewton(CompactQuasiNewton *qn_, CompactEigenApprox *eigh_, int index_)
     : CompactQuasiNewton(eigh_->ctx, eigh_->n, 0, false), qn(qn_), eigh(eigh_), index(index_), z0(1.0),
@@ -76,12 +113,8 @@ void EigenQuasiNewton::applyCompactInverse(double *rz) const {
   const int kq = qnSize(), N = eigh->N;
   if (kq > 0) qn->applyCompactInverse(rz);
   std::vector<double> out(N, 0.0);
-  for (int i = 0; i < N; i++) {
-    double s = 0.0;
-    for (int j = 0; j < N; j++) s += eigh->M[(size_t)i * N + j] * rz[kq + j];
-    out[i] = z0 * s;
-  }
-  for (int i = 0; i < N; i++) rz[kq + i] = out[i];
+  eigh->applyM(rz + kq, out.data());
+  for (int i = 0; i < N; i++) rz[kq + i] = z0 * out[i];
 }
 int EigenQuasiNewton::getCompactMat(double *b0_, const double **d0_, const double **M_, Vec ***Z_) {
   const int kq = qnSize(), N = eigh->N, k = kq + N;
@@ -130,14 +163,9 @@ int EigenQuasiNewton::mult(Vec *x, Vec *y) {  // :189-196
 // subproblems
 // ================================================================================================
 TrustRegionSubproblem::TrustRegionSubproblem(Problem *p)
-    : Problem(p->ctx, p->nlocal, p->ncon, p->ninequality), prob(p), m(p->ncon), xk(nullptr), lk(nullptr),
-      uk(nullptr), lb(nullptr), ub(nullptr), gk(nullptr), gt(nullptr), t(nullptr), xtemp(nullptr), fk(0.0),
-      ft(0.0), ck(p->ncon, 0.0), ct(p->ncon, 0.0), qn_update_type(0) {
-  offset = p->offset;
-  nglobal = p->nglobal;
-  nwcon = p->nwcon;
-  nwinequality = p->nwinequality;
-}
+    : Problem(p), prob(p), m(p->ncon), xk(nullptr), lk(nullptr), uk(nullptr), lb(nullptr), ub(nullptr), gk(nullptr),
+      gt(nullptr), t(nullptr), xtemp(nullptr), fk(0.0), ft(0.0), ck(p->ncon, 0.0), ct(p->ncon, 0.0),
+      qn_update_type(0) {}
 TrustRegionSubproblem::~TrustRegionSubproblem() {
   Vec *all[] = {xk, lk, uk, lb, ub, gk, gt, t, xtemp};
   for (Vec *v : all) vec_decref(v);
@@ -201,9 +229,7 @@ void TrustRegionSubproblem::rejectTrialStep() {  // :226-231
   for (int i = 0; i < m; i++) ct[i] = 0.0;
 }
 int TrustRegionSubproblem::evalLinearModel(Vec *step, double *f, double *cons) {
-  std::vector<const double *> P;
-  P.push_back(gk->d);
-  for (Vec *a : Ak) P.push_back(a->d);
+  std::vector<const double *> P = modelPanel(nullptr, nullptr, nullptr);
   lin_dots.assign(m + 1, 0.0);
   BatchScope batch(ctx);
   PO_TRY(k_mdot(ctx, step->d, P.data(), m + 1, nlocal, lin_dots.data()));
@@ -253,6 +279,82 @@ void TrustRegionSubproblem::acceptModel() {
   }
 }
 
+// ---- the compact model, shared by the quadratic and the eigenvalue subproblem ------------------------------------
+std::vector<const double *> TrustRegionSubproblem::modelPanel(const std::vector<const double *> *zp,
+                                                              const double *extra, Vec *step) const {
+  std::vector<const double *> P;
+  P.push_back(gk->d);
+  for (Vec *a : Ak) P.push_back(a->d);
+  if (zp) {
+    P.insert(P.end(), zp->begin(), zp->end());
+    if (extra) P.push_back(extra);
+    P.push_back(step->d);
+  }
+  return P;
+}
+double TrustRegionSubproblem::curvatureTerm(const CompactQuasiNewton *B, const double *rz, int k, double sts) {
+  std::vector<double> cf(rz, rz + k);
+  if (k > 0) B->applyCompactInverse(cf.data());
+  double sBs = B->diag() * sts;
+  for (int i = 0; i < k; i++) sBs -= rz[i] * cf[i];
+  return sBs;
+}
+std::vector<double> TrustRegionSubproblem::gradientCoefficients(const CompactQuasiNewton *B, const double *rz, int k) {
+  std::vector<double> cf(k + 1, 0.0);
+  for (int i = 0; i < k; i++) cf[1 + i] = rz[i];
+  if (k > 0) B->applyCompactInverse(cf.data() + 1);
+  for (int i = 0; i < k; i++) cf[1 + i] = -cf[1 + i];
+  cf[0] = B->diag();
+  return cf;
+}
+int TrustRegionSubproblem::stepProducts(Vec *step, const std::vector<const double *> &zp, double *rz) {
+  const int k = (int)zp.size();
+  if (k == 0) return PO_OK;
+  if (zts_valid && zts_ptr == step->d && (int)zts_cache.size() == k) {
+    for (int i = 0; i < k; i++) rz[i] = zts_cache[i];  // the products evalCompactModel(step) just took
+    return PO_OK;
+  }
+  return k_mdot(ctx, step->d, zp.data(), k, nlocal, rz);
+}
+int TrustRegionSubproblem::evalCompactModel(const CompactQuasiNewton *B, const double *extra, Vec *step, double *fobj,
+                                            double *cons, std::function<void(const double *, int, double)> modelled) {
+  std::vector<const double *> zp;
+  if (B) zp = B->zPointers();
+  const int k = (int)zp.size();
+  std::vector<const double *> P = modelPanel(B ? &zp : nullptr, extra, step);
+  eo_dots.assign(P.size(), 0.0);
+  zts_valid = false;
+  BatchScope batch(ctx);
+  if (k_mdot(ctx, step->d, P.data(), (int)P.size(), nlocal, eo_dots.data()) != PO_OK) return 1;
+  const double *sd = step->d;
+  const int rc = batch.end_then([this, B, extra, fobj, cons, k, sd, modelled] {
+    const std::vector<double> &dots = eo_dots;
+    const double *rz = dots.data() + 1 + m;
+    double f = fk + dots[0];
+    if (B) {
+      f += 0.5 * curvatureTerm(B, rz, k, dots[1 + m + k + (extra ? 1 : 0)]);
+      zts_cache.assign(rz, rz + k);  // Z^T step for the gradient evaluation at this very step
+      zts_ptr = sd;
+      zts_valid = true;
+    }
+    *fobj = f;
+    for (int i = 0; i < m; i++) cons[i] = ck[i] + dots[1 + i];
+    if (modelled) modelled(rz, k, extra ? dots[1 + m + k] : 0.0);
+  });
+  return rc == PO_OK ? 0 : 1;
+}
+int TrustRegionSubproblem::copyJacobianColumns(Vec **Ac, int skip_index) {
+  std::vector<double *> dst;
+  std::vector<const double *> src;
+  for (int i = 0; Ac && i < m; i++) {
+    if (i == skip_index || !Ac[i]) continue;
+    dst.push_back(Ac[i]->d);
+    src.push_back(Ak[i]->d);
+  }
+  if (dst.empty()) return PO_OK;
+  return k_panel_lincomb(ctx, dst.data(), 1.0, src.data(), 0.0, nullptr, (int)dst.size(), nlocal);
+}
+
 // ---- user-written subproblem behind a callback table ----------------------------------------------------------
 static inline po_vec PV(Vec *v) { return static_cast<po_vec>(v); }
 void CallbackSubproblem::dropModel() {
@@ -292,9 +394,7 @@ int CallbackSubproblem::syncLinearModel() {
   auto take = [&](po_vec h) -> Vec * {
     Vec *v = h;
     v->ref++;
-    if (v->h_live && v->h && v->n > 0 &&
-        hipMemcpyAsync(v->d, v->h, sizeof(double) * (size_t)v->n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      up_rc = PO_ERR_HIP;
+    if (vec_mirror_upload(v) != PO_OK) up_rc = PO_ERR_HIP;
     return v;
   };
   xk = take(hx);
@@ -381,66 +481,17 @@ int QuadraticSubproblem::evalObjCon(Vec *step, double *fobj, double *cons) {  //
     for (int i = 0; i < m; i++) cons[i] = ck[i];
     return 0;
   }
-  std::vector<const double *> P;
-  P.push_back(gk->d);
-  for (Vec *a : Ak) P.push_back(a->d);
-  int k = 0;
-  if (qn) {
-    std::vector<const double *> zp = qn->zPointers();
-    k = (int)zp.size();
-    P.insert(P.end(), zp.begin(), zp.end());
-    P.push_back(step->d);
-  }
-  eo_dots.assign(P.size(), 0.0);
-  zts_valid = false;
-  BatchScope batch(ctx);
-  if (k_mdot(ctx, step->d, P.data(), (int)P.size(), nlocal, eo_dots.data()) != PO_OK) return 1;
-  const double *sd = step->d;
-  const int rc = batch.end_then([this, fobj, cons, k, sd] {
-    const std::vector<double> &dots = eo_dots;
-    double f = fk + dots[0];
-    if (qn) {
-      std::vector<double> rz(dots.begin() + 1 + m, dots.begin() + 1 + m + k), cf = rz;
-      if (k > 0) qn->applyCompactInverse(cf.data());
-      double sBs = qn->diag() * dots[1 + m + k];
-      for (int i = 0; i < k; i++) sBs -= rz[i] * cf[i];
-      f += 0.5 * sBs;
-      zts_cache = rz;  // Z^T step for the gradient evaluation at this very step
-      zts_ptr = sd;
-      zts_valid = true;
-    }
-    *fobj = f;
-    for (int i = 0; i < m; i++) cons[i] = ck[i] + dots[1 + i];
-  });
-  return rc == PO_OK ? 0 : 1;
+  return evalCompactModel(qn, nullptr, step, fobj, cons);  // [gk | Ak | Z | step], or [gk | Ak] without qn
 }
 int QuadraticSubproblem::evalObjConGradient(Vec *step, Vec *g, Vec **Ac) {  // :328-343
-  // Ac == nullptr: the constraint model is linear (linear_constraints is set), the solver kept the Jacobian of the
-  // first evaluation of this solve
-  std::vector<double *> dst;
-  std::vector<const double *> src;
-  for (int i = 0; Ac && i < m; i++) {
-    dst.push_back(Ac[i]->d);
-    src.push_back(Ak[i]->d);
-  }
-  if (Ac && m > 0 && k_panel_lincomb(ctx, dst.data(), 1.0, src.data(), 0.0, nullptr, m, nlocal) != PO_OK) return 1;
+  if (copyJacobianColumns(Ac, -1) != PO_OK) return 1;
   if (!qn) return k_copy(ctx, g->d, gk->d, nlocal) == PO_OK ? 0 : 1;
-  std::vector<const double *> zp = qn->zPointers();
-  const int k = (int)zp.size();
-  std::vector<double> cf(k + 1, 0.0);
-  if (k > 0) {
-    if (zts_valid && zts_ptr == step->d && (int)zts_cache.size() == k) {
-      for (int i = 0; i < k; i++) cf[1 + i] = zts_cache[i];  // the products evalObjCon(step) just took
-    } else if (k_mdot(ctx, step->d, zp.data(), k, nlocal, cf.data() + 1) != PO_OK) {
-      return 1;
-    }
-    qn->applyCompactInverse(cf.data() + 1);
-    for (int i = 0; i < k; i++) cf[1 + i] = -cf[1 + i];
-  }
-  cf[0] = qn->diag();
-  std::vector<const double *> P;
-  P.push_back(step->d);
-  P.insert(P.end(), zp.begin(), zp.end());
+  std::vector<const double *> P = qn->zPointers();
+  const int k = (int)P.size();
+  std::vector<double> rz(k > 0 ? k : 1, 0.0);
+  if (stepProducts(step, P, rz.data()) != PO_OK) return 1;
+  const std::vector<double> cf = gradientCoefficients(qn, rz.data(), k);
+  P.insert(P.begin(), step->d);  // [step | Z]
   return k_panel_axpy(ctx, g->d, 1.0, gk->d, 0.0, cf.data(), P.data(), k + 1, nlocal) == PO_OK ? 0 : 1;
 }
 
@@ -482,97 +533,44 @@ int EigenSubproblem::acceptTrialStep(Vec *step, const double *z, Vec *zw) {  // 
   acceptModel();
   return PO_OK;
 }
-// dots of `step` with [gk | Ak | Z_qn (if used) | H | g0 | step]
-int EigenSubproblem::modelDots(Vec *step, std::vector<double> &dots, int *kq) {
-  std::vector<const double *> P;
-  P.push_back(gk->d);
-  for (Vec *a : Ak) P.push_back(a->d);
-  std::vector<const double *> zp = approx->zPointers();  // [Z_qn | H]
-  *kq = (int)zp.size() - approx->eigh->N;
-  P.insert(P.end(), zp.begin(), zp.end());
-  P.push_back(approx->eigh->g0->d);
-  P.push_back(step->d);
-  dots.assign(P.size(), 0.0);
-  return k_mdot(ctx, step->d, P.data(), (int)P.size(), nlocal, dots.data());
-}
 int EigenSubproblem::evalObjCon(Vec *step, double *fobj, double *cons) {  // :585-621
   CompactEigenApprox *e = approx->eigh;
-  const int idx = approx->index, N = e->N;
+  const int idx = approx->index;
   if (!step) {
     *fobj = fk;
     for (int i = 0; i < m; i++) cons[i] = ck[i];
     cons[idx] = e->c0;
     return 0;
   }
-  int kq = 0;
-  zts_valid = false;
-  BatchScope batch(ctx);
-  if (modelDots(step, eo_dots, &kq) != PO_OK) return 1;
-  const double *sd = step->d;
-  const int rc = batch.end_then([this, fobj, cons, kq, sd, e, idx, N] {
-    const std::vector<double> &dots = eo_dots;
-    const int k = kq + N;
-    const double *rz = dots.data() + 1 + m;
-    std::vector<double> cf(rz, rz + k);
-    approx->applyCompactInverse(cf.data());
-    double sBs = approx->diag() * dots[1 + m + k + 1];
-    for (int i = 0; i < k; i++) sBs -= rz[i] * cf[i];
-    *fobj = fk + dots[0] + 0.5 * sBs;
-    for (int i = 0; i < m; i++) cons[i] = ck[i] + dots[1 + i];
-    const double *h = rz + kq;  // H^T s
-    double c = e->c0 + dots[1 + m + k];
-    for (int i = 0; i < N; i++)
-      for (int j = 0; j < N; j++) c += 0.5 * e->M[(size_t)i * N + j] * h[i] * h[j];
-    cons[idx] = c;
-    zts_cache.assign(rz, rz + k);  // [Z_qn | H]^T step for the gradient evaluation at this very step
-    zts_ptr = sd;
-    zts_valid = true;
+  // [gk | Ak | Z_qn (if used) | H | g0 | step]; the modelled constraint is c0 + g0.s + 1/2 (H^T s)^T M (H^T s)
+  return evalCompactModel(approx, e->g0->d, step, fobj, cons, [e, idx, cons](const double *zts, int k, double g0s) {
+    const int kq = k - e->N;
+    cons[idx] = e->quadraticForm(zts + kq, e->c0 + g0s);
   });
-  return rc == PO_OK ? 0 : 1;
 }
 int EigenSubproblem::evalObjConGradient(Vec *step, Vec *g, Vec **Ac) {  // :626-643
   CompactEigenApprox *e = approx->eigh;
   const int idx = approx->index, N = e->N;
-  std::vector<const double *> zp = approx->zPointers();
-  const int k = (int)zp.size(), kq = k - N;
+  std::vector<const double *> P = approx->zPointers();
+  const int k = (int)P.size(), kq = k - N;
   std::vector<double> rz(k > 0 ? k : 1, 0.0);
-  if (k > 0 && zts_valid && zts_ptr == step->d && (int)zts_cache.size() == k) {
-    for (int i = 0; i < k; i++) rz[i] = zts_cache[i];  // the products evalObjCon(step) just took
-  } else if (k > 0 && k_mdot(ctx, step->d, zp.data(), k, nlocal, rz.data()) != PO_OK) {
-    return 1;
-  }
+  if (stepProducts(step, P, rz.data()) != PO_OK) return 1;
   // constraint gradients: copies, except the modelled one: g0 + H (M H^T s)
-  std::vector<double *> dst;
-  std::vector<const double *> src;
-  for (int i = 0; Ac && i < m; i++) {  // (Ac == nullptr: objective gradient only, asked for by a linearised wrapper)
-    if (i == idx || !Ac[i]) continue;  // (Ac[i] == nullptr: the solver kept this constant column, constantJacobianMask)
-    dst.push_back(Ac[i]->d);
-    src.push_back(Ak[i]->d);
-  }
-  if (!dst.empty() &&
-      k_panel_lincomb(ctx, dst.data(), 1.0, src.data(), 0.0, nullptr, (int)dst.size(), nlocal) != PO_OK)
-    return 1;
+  // (Ac == nullptr: objective gradient only, asked for by a linearised wrapper)
+  if (copyJacobianColumns(Ac, idx) != PO_OK) return 1;
   // g = gk + B s
-  std::vector<double> cf(k + 1, 0.0);
-  for (int i = 0; i < k; i++) cf[1 + i] = rz[i];
-  approx->applyCompactInverse(cf.data() + 1);
-  for (int i = 0; i < k; i++) cf[1 + i] = -cf[1 + i];
-  cf[0] = approx->diag();
-  std::vector<const double *> P;
-  P.push_back(step->d);
-  P.insert(P.end(), zp.begin(), zp.end());
+  const std::vector<double> cf = gradientCoefficients(approx, rz.data(), k);
+  P.insert(P.begin(), step->d);  // [step | Z_qn | H]
   if (Ac && Ac[idx] && k + 1 <= kMaxPanel) {
     // ... and the modelled constraint's gradient g0 + H (M H^T s) in the same pass over [step | Z_qn | H]
     std::vector<double> ch(k + 1, 0.0);
-    for (int i = 0; i < N; i++)
-      for (int j = 0; j < N; j++) ch[1 + kq + i] += e->M[(size_t)i * N + j] * rz[kq + j];
+    e->applyM(rz.data() + kq, ch.data() + 1 + kq);
     return k_panel_axpy2(ctx, g->d, 1.0, gk->d, cf.data(), Ac[idx]->d, 1.0, e->g0->d, ch.data(), P.data(), k + 1,
                          nlocal) == PO_OK ? 0 : 1;
   }
   if (Ac && Ac[idx]) {
     std::vector<double> mh(N, 0.0);
-    for (int i = 0; i < N; i++)
-      for (int j = 0; j < N; j++) mh[i] += e->M[(size_t)i * N + j] * rz[kq + j];
+    e->applyM(rz.data() + kq, mh.data());
     std::vector<const double *> hp = e->hPointers();
     if (k_panel_axpy(ctx, Ac[idx]->d, 1.0, e->g0->d, 0.0, mh.data(), hp.data(), N, nlocal) != PO_OK) return 1;
   }
@@ -581,12 +579,7 @@ int EigenSubproblem::evalObjConGradient(Vec *step, Vec *g, Vec **Ac) {  // :626-
 
 // ---- infeasibility (steering) problem -----------------------------------------------------------
 InfeasSubproblem::InfeasSubproblem(TrustRegionSubproblem *sub_, int objective_, int constraint_)
-    : Problem(sub_->ctx, sub_->nlocal, sub_->ncon, sub_->ninequality), sub(sub_), objective(objective_),
-      constraint(constraint_), obj_scale(1.0) {
-  offset = sub_->offset;
-  nglobal = sub_->nglobal;
-  nwcon = sub_->nwcon;
-  nwinequality = sub_->nwinequality;
+    : Problem(sub_), sub(sub_), objective(objective_), constraint(constraint_), obj_scale(1.0) {
   // a linear constraint model has a constant Jacobian within a solve: the interior point keeps it (Ac == nullptr
   // in later gradient calls) and carries A^T z by recurrence (po_problem_set_linear_constraints)
   linear_constraints = (constraint_ == LINEAR_CONSTRAINT || sub_->linear_constraints) ? 1 : 0;
@@ -617,7 +610,6 @@ int InfeasSubproblem::evalObjCon(Vec *step, double *fobj, double *cons) {  // :5
   return rc == PO_OK ? 0 : 1;
 }
 int InfeasSubproblem::evalObjConGradient(Vec *step, Vec *g, Vec **Ac) {  // :585-612
-  const int m = sub->m;
   if (objective == SUBPROBLEM_OBJECTIVE || constraint == SUBPROBLEM_CONSTRAINT) {
     if (sub->evalObjConGradient(step, g, Ac) != 0) return 1;
   }
@@ -629,41 +621,21 @@ int InfeasSubproblem::evalObjConGradient(Vec *step, Vec *g, Vec **Ac) {  // :585
   } else {
     if (k_scale(ctx, g->d, nlocal, obj_scale) != PO_OK) return 1;
   }
-  if (constraint == LINEAR_CONSTRAINT && m > 0 && Ac) {
-    std::vector<double *> dst;
-    std::vector<const double *> src;
-    for (int i = 0; i < m; i++) {
-      dst.push_back(Ac[i]->d);
-      src.push_back(sub->Ak[i]->d);
-    }
-    if (k_panel_lincomb(ctx, dst.data(), 1.0, src.data(), 0.0, nullptr, m, nlocal) != PO_OK) return 1;
-  }
+  if (constraint == LINEAR_CONSTRAINT && sub->copyJacobianColumns(Ac, -1) != PO_OK) return 1;
   return 0;
 }
 
 // ================================================================================================
 // the driver
 // ================================================================================================
-TrustRegion::TrustRegion(Problem *p)
-    : prob(p), ctx(p->ctx), qn(nullptr), eigh(nullptr), eqn(nullptr), sub(nullptr), infeas(nullptr), ip(nullptr),
-      m(p->ncon), nineq(p->ninequality), tr_size(0.1), iter_count(0), subproblem_iters(0),
-      adaptive_subproblem_iters(0), iter_cb(nullptr), iter_cb_user(nullptr), eig_N(0), eig_index(0),
-      eig_update(nullptr), eig_user(nullptr), tvec(nullptr) {
+TrustRegion::TrustRegion(Problem *p) : TrustRegion(p, nullptr) {}
+TrustRegion::TrustRegion(TrustRegionSubproblem *s) : TrustRegion(s->prob, s) {}
+TrustRegion::TrustRegion(Problem *p, TrustRegionSubproblem *s)
+    : prob(p), ctx(p->ctx), sub(s), m(p->ncon), nineq(p->ninequality), own_sub(s == nullptr) {
   qn_handle.qn = nullptr;
   opts.addTrustRegionDefaults();
   // the inner interior-point solves do not write an iteration table unless asked to
   opts.set("output_file", "");
-  for (double &v : row) v = 0.0;
-}
-TrustRegion::TrustRegion(TrustRegionSubproblem *s)
-    : prob(s->prob), ctx(s->ctx), qn(nullptr), eigh(nullptr), eqn(nullptr), sub(s), infeas(nullptr), ip(nullptr),
-      m(s->ncon), nineq(s->ninequality), tr_size(0.1), iter_count(0), subproblem_iters(0),
-      adaptive_subproblem_iters(0), iter_cb(nullptr), iter_cb_user(nullptr), own_sub(false), eig_N(0), eig_index(0),
-      eig_update(nullptr), eig_user(nullptr), tvec(nullptr) {
-  qn_handle.qn = nullptr;
-  opts.addTrustRegionDefaults();
-  opts.set("output_file", "");
-  for (double &v : row) v = 0.0;
 }
 TrustRegion::~TrustRegion() {
   if (own_ip) delete ip;
@@ -716,51 +688,43 @@ int TrustRegion::initialize() {
 
 int TrustRegion::build() {
   if (ip) return initState();
-  const int64_t n = prob->nlocal;
-  if (!own_sub) {
-    // the caller's subproblem (allocated by its creator); an interior-point solver of our own only if optimize() is
-    // called without one
-    if (!tvec) tvec = vec_new(ctx, n);
-    if (!tvec) return PO_ERR_HIP;
+  if (own_sub) {
+    const int64_t n = prob->nlocal;
+    qn = make_quasi_newton(ctx, n, opts);
+    if (eig_N > 0) {
+      eigh = new CompactEigenApprox(ctx, n, eig_N);
+      PO_TRY(eigh->allocate());
+      eqn = new EigenQuasiNewton(qn, eigh, eig_index);
+      EigenSubproblem *es = new EigenSubproblem(prob, eqn);
+      es->update_model = eig_update;
+      es->update_user = eig_user;
+      sub = es;
+    } else {
+      sub = new QuadraticSubproblem(prob, qn);
+    }
+    PO_TRY(sub->allocate());
+  }
+  // (the caller's subproblem was allocated by its creator; it gets an interior-point solver of our own only if
+  // optimize() is called without one)
+  return attachSolver(nullptr);
+}
+int TrustRegion::attachSolver(InteriorPoint *ext) {
+  if (!tvec) tvec = vec_new(ctx, prob->nlocal);
+  if (!tvec) return PO_ERR_HIP;
+  if (!ext) {
     ip = new InteriorPoint(sub);
     ip->options = opts;
-    PO_TRY(ip->allocate());
     own_ip = true;
-    qn_handle.qn = sub->getQuasiNewton();
-    return initState();
+    PO_TRY(ip->allocate());
+  } else if (ip != ext) {
+    // one registry, as in the reference (the same ParOptOptions object serves both): the trust-region entries set on
+    // this object move into the solver's registry; the interior-point entries are the solver's own
+    Options base;
+    ext->options.adoptExtras(ip ? ip->options : opts, base);
+    if (ip && own_ip) delete ip;
+    ip = ext;
+    own_ip = false;
   }
-  const std::string qt = opts.str("qn_type");
-  const int msub = opts.integer("qn_subspace_size");
-  if (qt == "bfgs") {
-    LBFGS *b = new LBFGS(ctx, n, msub);
-    b->setBFGSUpdateType(std::string(opts.str("qn_update_type")) == "damped_update"
-                             ? PO_BFGS_DAMPED_UPDATE
-                             : PO_BFGS_SKIP_NEGATIVE_CURVATURE);
-    qn = b;
-  } else if (qt == "sr1") {
-    qn = new LSR1(ctx, n, msub);
-  }
-  if (qn) {
-    const std::string dt = opts.str("qn_diag_type");
-    qn->setInitDiagonalType(dt == "yts_over_sts" ? PO_QN_YTS_OVER_STS : PO_QN_YTY_OVER_YTS);
-  }
-  if (eig_N > 0) {
-    eigh = new CompactEigenApprox(ctx, n, eig_N);
-    PO_TRY(eigh->allocate());
-    eqn = new EigenQuasiNewton(qn, eigh, eig_index);
-    EigenSubproblem *es = new EigenSubproblem(prob, eqn);
-    es->update_model = eig_update;
-    es->update_user = eig_user;
-    sub = es;
-  } else {
-    sub = new QuadraticSubproblem(prob, qn);
-  }
-  PO_TRY(sub->allocate());
-  tvec = vec_new(ctx, n);
-  if (!tvec) return PO_ERR_HIP;
-  ip = new InteriorPoint(sub);
-  ip->options = opts;
-  PO_TRY(ip->allocate());
   qn_handle.qn = sub->getQuasiNewton();
   return initState();
 }
@@ -768,8 +732,7 @@ int TrustRegion::build() {
 double TrustRegion::infeasOf(const double *c, const double *weights) const {
   double tot = 0.0;
   for (int i = 0; i < m; i++) {
-    const double v = i < nineq ? std::max(0.0, -c[i]) : fabs(c[i]);
-    tot += weights ? weights[i] * v : v;
+    tot += weights ? weights[i] * violation(c, i) : violation(c, i);
   }
   return tot;
 }
@@ -863,11 +826,9 @@ int TrustRegion::minimizeInfeas(std::vector<double> *best_out) {  // :1105-1228
   infeas->obj_scale = 1.0 / gamma;
   ip->setPenaltyGamma(1.0);
   PO_TRY(ip->resetDesignAndBounds());
-  int rc = ip->optimize(nullptr);
-  if (rc != 0 && rc != 1) return rc;
-  captureSolveLine(0);
-  Vec *step = nullptr;
-  ip->getOptimizedPoint(&step, nullptr, nullptr, nullptr);
+  const Solution sol = solveSubproblem(0);
+  if (sol.rc != PO_OK) return sol.rc;
+  Vec *step = sol.step;
   if (std::string(o.str("tr_accept_step_strategy")) == "penalty_method" && o.integer("tr_adaptive_gamma_update")) {
     ip->getIterationCounters(&adaptive_subproblem_iters, nullptr, nullptr);
   }
@@ -876,7 +837,7 @@ int TrustRegion::minimizeInfeas(std::vector<double> *best_out) {  // :1105-1228
     double dummy = 0.0;
     best.assign(m > 0 ? m : 1, 0.0);
     if (sub->evalObjCon(step, &dummy, best.data()) != 0) return PO_ERR_USER;
-    for (int j = 0; j < m; j++) best[j] = j < nineq ? std::max(0.0, -best[j]) : fabs(best[j]);
+    for (int j = 0; j < m; j++) best[j] = violation(best.data(), j);
   }
   ip->setPenaltyGammaArray(penalty_gamma.data());
   PO_TRY(ip->resetProblemInstance(sub));
@@ -885,6 +846,40 @@ int TrustRegion::minimizeInfeas(std::vector<double> *best_out) {  // :1105-1228
   PO_TRY(o.set("barrier_strategy", barrier_option.c_str()));
   PO_TRY(o.set("sequential_linear_method", is_seq));
   return PO_OK;
+}
+
+TrustRegion::Solution TrustRegion::solveSubproblem(int which) {
+  Solution sol = {ip->optimize(nullptr), nullptr, nullptr, nullptr};
+  if (sol.rc != 0 && sol.rc != 1) return sol;
+  sol.rc = PO_OK;
+  captureSolveLine(which);
+  // step / z / zw alias the solver's storage: the next solve replaces them (:1797-1799)
+  ip->getOptimizedPoint(&sol.step, &sol.z, nullptr, nullptr);
+  Vec *wv[5];
+  ip->getOptimizedSparse(wv);
+  sol.zw = wv[0];
+  return sol;
+}
+
+void TrustRegion::finishRow(const double head[8], const double *z, const std::string &info_tail, double t0) {
+  double zmax = 0.0, zav = 0.0, gmax = 0.0, gav = 0.0;
+  for (int i = 0; i < m; i++) {
+    zav += fabs(z[i]);
+    gav += penalty_gamma[i];
+    zmax = std::max(zmax, fabs(z[i]));
+    gmax = std::max(gmax, penalty_gamma[i]);
+  }
+  zav = zav / m;  // (m = 0: 0 / 0, as the reference prints it)
+  gav = gav / m;
+  std::string info;
+  const int ut = sub->getQuasiNewtonUpdateType();
+  if (ut == 1) info += "dampH ";
+  else if (ut == 2) info += "skipH ";
+  info += info_tail;
+  const double vals[12] = {head[0], head[1], head[2], head[3], head[4], head[5],
+                           head[6], head[7], zav,     zmax,    gav,     gmax};
+  appendRow(vals, info, now_seconds() - t0);
+  iter_count++;
 }
 
 int TrustRegion::sl1qpUpdate(Vec *step, const double *z, Vec *zw, double *infeas_, double *l1,
@@ -924,19 +919,7 @@ int TrustRegion::sl1qpUpdate(Vec *step, const double *z, Vec *zw, double *infeas
   }
   PO_TRY(sub->setTrustRegionBounds(tr_size));
   PO_TRY(computeKKTError(z, zw, l1, linfty));
-  double zmax = 0.0, zav = 0.0, gmax = 0.0, gav = 0.0;
-  for (int i = 0; i < m; i++) {
-    zav += fabs(z[i]);
-    gav += penalty_gamma[i];
-    zmax = std::max(zmax, fabs(z[i]));
-    gmax = std::max(gmax, penalty_gamma[i]);
-  }
-  zav = zav / m;
-  gav = gav / m;
   std::string info;
-  const int ut = sub->getQuasiNewtonUpdateType();
-  if (ut == 1) info += "dampH ";
-  else if (ut == 2) info += "skipH ";
   char buf[64];
   if (adaptive) {
     snprintf(buf, sizeof(buf), "%d/%d ", subproblem_iters, adaptive_subproblem_iters);
@@ -945,9 +928,8 @@ int TrustRegion::sl1qpUpdate(Vec *step, const double *z, Vec *zw, double *infeas
   }
   info += buf;
   if (!accepted) info += "rej ";
-  const double vals[12] = {fk, *infeas_, *l1, *linfty, smax, tr_size, rho, model_reduc, zav, zmax, gav, gmax};
-  appendRow(vals, info, now_seconds() - t0);
-  iter_count++;
+  const double head[8] = {fk, *infeas_, *l1, *linfty, smax, tr_size, rho, model_reduc};
+  finishRow(head, z, info, t0);
   return PO_OK;
 }
 
@@ -972,20 +954,7 @@ int TrustRegion::optimize(InteriorPoint *ext) {  // optimize :2365-2384
       set_error("ParOptTrustRegion::optimize: the interior-point solver was not built on this subproblem");
       return PO_ERR_ARG;
     }
-    // one registry, as in the reference (the same ParOptOptions object serves both): the trust-region entries set on
-    // this object move into the solver's registry; the interior-point entries are the solver's own
-    Options base;
-    if (ip != ext) {
-      const Options &mine = ip ? ip->options : opts;
-      ext->options.adoptExtras(mine, base);
-      if (ip && own_ip) delete ip;
-      ip = ext;
-      own_ip = false;
-    }
-    if (!tvec) tvec = vec_new(ctx, prob->nlocal);
-    if (!tvec) return PO_ERR_HIP;
-    qn_handle.qn = sub->getQuasiNewton();
-    PO_TRY(initState());
+    PO_TRY(attachSolver(ext));
   }
   PO_TRY(build());
   // tr_use_soc has no effect in the reference either: the only call of isAcceptedBySoc is commented
@@ -1028,16 +997,11 @@ int TrustRegion::filterOptimize() {
     PO_TRY(ip->resetProblemInstance(sub));
     PO_TRY(o.set("sequential_linear_method", 0));
     PO_TRY(ip->resetDesignAndBounds());
-    int rc = ip->optimize(nullptr);
-    if (rc != 0 && rc != 1) return rc;
-    captureSolveLine(1);
-    // step / z / zw alias the solver's storage, so a restoration solve below replaces them (:1797-1799)
-    Vec *step = nullptr;
-    const double *z = nullptr;
-    ip->getOptimizedPoint(&step, &z, nullptr, nullptr);
-    Vec *wv[5];
-    ip->getOptimizedSparse(wv);
-    Vec *zw = wv[0];
+    // (step / z / zw alias the solver's storage, so a restoration solve below replaces them, :1797-1799)
+    const Solution sol = solveSubproblem(1);
+    if (sol.rc != PO_OK) return sol.rc;
+    Vec *step = sol.step, *zw = sol.zw;
+    const double *z = sol.z;
     if (o.integer("filter_has_feas_restore_phase")) {
       double dummy = 0.0, infeas_v = 0.0;
       if (sub->evalObjCon(step, &dummy, cm.data()) != 0) return PO_ERR_USER;
@@ -1100,29 +1064,16 @@ int TrustRegion::filterOptimize() {
     if (iter_cb) iter_cb(iter_cb_user, iteration);
     double l1 = 0.0, linfty = 0.0;
     PO_TRY(computeKKTError(z, zw, &l1, &linfty));
-    double zmax = 0.0, zav = 0.0, gmax = 0.0, gav = 0.0;
-    for (int i = 0; i < m; i++) {
-      zav += fabs(z[i]);
-      gav += penalty_gamma[i];
-      zmax = std::max(zmax, fabs(z[i]));
-      gmax = std::max(gmax, penalty_gamma[i]);
-    }
-    zav = zav / m;
-    gav = gav / m;
     int qp_iters = 0;
     ip->getIterationCounters(&qp_iters, nullptr, nullptr);
     subproblem_iters = qp_iters;
-    std::string info;
-    const int ut = sub->getQuasiNewtonUpdateType();
-    if (ut == 1) info += "dampH ";
-    else if (ut == 2) info += "skipH ";
     char buf[64];
     snprintf(buf, sizeof(buf), "%d f%ld ", qp_iters, (long)filter.size());
-    info += buf;
+    std::string info = buf;
     if (this_resto) info += "R ";
     if (!accepted) info += (rej.empty() ? std::string("rej") : rej) + " ";
-    const double vals[12] = {fobj_trial, infeas_trial, l1, linfty, smax, tr_size, rho, model_red, zav, zmax, gav, gmax};
-    appendRow(vals, info, now_seconds() - t0);
+    const double head[8] = {fobj_trial, infeas_trial, l1, linfty, smax, tr_size, rho, model_red};
+    finishRow(head, z, info, t0);
     if (inc_tr) {
       tr_size = std::min(2.0 * tr_size, tr_max);
     } else if (dec_tr) {
@@ -1130,11 +1081,10 @@ int TrustRegion::filterOptimize() {
     }
     if (init_tr) tr_size = tr_max;
     PO_TRY(sub->setTrustRegionBounds(tr_size));
-    iter_count++;
     last_resto = this_resto;
     if (infeas_trial < infeas_tol && (l1 < l1_tol || linfty < linf_tol)) break;
   }
-  flushHistory();
+  write_history_file(ctx, options().str("tr_output_file"), "ParOptTrustRegion", history);
   return 0;
 }
 
@@ -1167,23 +1117,18 @@ int TrustRegion::sl1qpOptimize() {  // :1453-1687
     if (wfreq > 0 && i % wfreq == 0) sub->writeOutput(i, sub->xk);
     if (iter_cb) iter_cb(iter_cb_user, i);
     PO_TRY(ip->resetDesignAndBounds());
-    int rc = ip->optimize(nullptr);
-    if (rc != 0 && rc != 1) return rc;
-    captureSolveLine(1);
-    Vec *step = nullptr, *zw = nullptr;
-    const double *z = nullptr;
-    ip->getOptimizedPoint(&step, &z, nullptr, nullptr);
-    Vec *wv[5];
-    ip->getOptimizedSparse(wv);
-    zw = wv[0];
+    const Solution sol = solveSubproblem(1);
+    if (sol.rc != PO_OK) return sol.rc;
+    Vec *step = sol.step, *zw = sol.zw;
+    const double *z = sol.z;
     ip->getIterationCounters(&subproblem_iters, nullptr, nullptr);
     if (adaptive) {
       double f0 = 0.0, fm = 0.0;
       if (sub->evalObjCon(nullptr, &f0, con_infeas.data()) != 0) return PO_ERR_USER;
       if (sub->evalObjCon(step, &fm, model_con_infeas.data()) != 0) return PO_ERR_USER;
       for (int j = 0; j < m; j++) {
-        con_infeas[j] = j < nineq ? std::max(0.0, -con_infeas[j]) : fabs(con_infeas[j]);
-        model_con_infeas[j] = j < nineq ? std::max(0.0, -model_con_infeas[j]) : fabs(model_con_infeas[j]);
+        con_infeas[j] = violation(con_infeas.data(), j);
+        model_con_infeas[j] = violation(model_con_infeas.data(), j);
       }
     }
     double infeas_v = 0.0, l1 = 0.0, linfty = 0.0;
@@ -1201,18 +1146,8 @@ int TrustRegion::sl1qpOptimize() {  // :1453-1687
       }
     }
   }
-  flushHistory();
+  write_history_file(ctx, options().str("tr_output_file"), "ParOptTrustRegion", history);
   return 0;
-}
-
-void TrustRegion::flushHistory() {
-  const std::string fname = options().str("tr_output_file");
-  if (ctx->rank != 0 || fname.empty()) return;
-  FILE *fp = fopen(fname.c_str(), "w");
-  if (!fp) return;
-  fputs("ParOptTrustRegion (paropt_amd, MI355X)\n", fp);
-  fputs(history.c_str(), fp);
-  fclose(fp);
 }
 
 }  // namespace po

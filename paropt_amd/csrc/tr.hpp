@@ -4,6 +4,9 @@
 // adaptive penalty update.  Same method names and argument meaning; every n-sized operation is a
 // launch of the kernels the interior-point path already uses (mdot / panel_axpy / panel_lincomb).
 #pragma once
+#include <math.h>
+
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -23,6 +26,13 @@ class CompactEigenApprox {
   ~CompactEigenApprox();
   int allocate();
   std::vector<const double *> hPointers() const;
+  // the N x N products on the host (.cpp:52-64, 108-120): out = M h, and c + 1/2 h^T M h accumulated term by term
+  // onto c (row by row)
+  void applyM(const double *h, double *out) const;
+  double quadraticForm(const double *h, double c = 0.0) const;
+  int multAdd(double alpha, Vec *x, Vec *y) const;                 // y += alpha H M H^T x (.cpp:52-64)
+  int evalApproximation(Vec *s, double *value) const;              // c0 + g0.s + 1/2 s^T H M H^T s; s == nullptr: c0
+  int evalApproximationGradient(Vec *s, Vec *grad) const;          // g0 + H M H^T s (.cpp:108-120)
   Ctx *ctx;
   int64_t n;
   int N;
@@ -77,6 +87,10 @@ class TrustRegionSubproblem : public Problem {
   virtual int getQuasiNewtonUpdateType() const { return qn_update_type; }
   // linear model values at a step: f = fk + gk.s, cons = ck + Ak s (one panel-dot pass)
   int evalLinearModel(Vec *step, double *f, double *cons);
+  // Ac[i] <- Ak[i] in one launch for every column the solver asks for (Ac == nullptr: the solver kept the constant
+  // Jacobian of the first evaluation of this solve; Ac[i] == nullptr: it kept that column, constantJacobianMask) but
+  // `skip_index`, the constraint a subclass models itself (-1: none)
+  int copyJacobianColumns(Vec **Ac, int skip_index);
 
   // ParOptProblem side, seen by the interior-point solver
   bool isSubproblem() override { return true; }
@@ -116,6 +130,21 @@ class TrustRegionSubproblem : public Problem {
   int evalTrialPoint(Vec *step, double *fobj, double *cons);
   int lagrangianGradientDifference(const double *z, Vec *zw);  // into t (:187-205)
   void acceptModel();
+  // ---- the compact model over B = b0 I - Z C Z^T (a CompactQuasiNewton), shared by the quadratic and the eigenvalue
+  // subproblem:  f(s) = fk + gk.s + 1/2 (b0 s.s - (Z^T s)^T C (Z^T s)),  g(s) = gk + b0 s - Z C Z^T s
+  // Columns of the model pass, rebuilt per call (acceptModel swaps buffers, a user-written subproblem re-borrows
+  // its vectors): [gk | Ak], then with `zp` also [Z | extra (if any) | step]
+  std::vector<const double *> modelPanel(const std::vector<const double *> *zp, const double *extra, Vec *step) const;
+  // f(s) and the linear c(s) in ONE pass over modelPanel (B == nullptr: the linear model, no cache); leaves Z^T s in
+  // the cache.  `modelled(Z^T s, k, extra.s)`, if given, runs where the values land, after fobj and cons are written.
+  int evalCompactModel(const CompactQuasiNewton *B, const double *extra, Vec *step, double *fobj, double *cons,
+                       std::function<void(const double *, int, double)> modelled = nullptr);
+  // b0 s.s - sum_i rz[i] (C rz)[i], subtracted term by term in index order
+  static double curvatureTerm(const CompactQuasiNewton *B, const double *rz, int k, double sts);
+  // [b0 | -C rz]: the coefficients of [step | Z] in the gradient
+  static std::vector<double> gradientCoefficients(const CompactQuasiNewton *B, const double *rz, int k);
+  // rz = Z^T step: what evalCompactModel(step) just took, else one panel-dot pass
+  int stepProducts(Vec *step, const std::vector<const double *> &zp, double *rz);
   int qn_update_type;
   // landing areas of the model reductions (the values may arrive at the flush of an enclosing batch)
   std::vector<double> eo_dots, lin_dots;
@@ -163,9 +192,6 @@ class EigenSubproblem : public TrustRegionSubproblem {  // ParOptCompactEigenval
   EigenQuasiNewton *approx;
   EigenModelUpdate update_model;
   void *update_user;
-
- private:
-  int modelDots(Vec *step, std::vector<double> &dots, int *kq);
 };
 
 
@@ -280,24 +306,24 @@ class TrustRegion {
   Problem *prob;
   Ctx *ctx;
   Options opts;  // registry until the interior-point object exists, then ip->options is the one
-  CompactQuasiNewton *qn;
-  CompactEigenApprox *eigh;
-  EigenQuasiNewton *eqn;
+  CompactQuasiNewton *qn = nullptr;
+  CompactEigenApprox *eigh = nullptr;
+  EigenQuasiNewton *eqn = nullptr;
   TrustRegionSubproblem *sub;
-  InfeasSubproblem *infeas;
-  InteriorPoint *ip;
+  InfeasSubproblem *infeas = nullptr;
+  InteriorPoint *ip = nullptr;
   po_qn_s qn_handle;
 
   int m, nineq;
   std::vector<double> penalty_gamma;
-  double tr_size;
-  int iter_count, subproblem_iters, adaptive_subproblem_iters;
+  double tr_size = 0.1;
+  int iter_count = 0, subproblem_iters = 0, adaptive_subproblem_iters = 0;
   std::string history;
-  TrIterationFn iter_cb;
-  void *iter_cb_user;
+  TrIterationFn iter_cb = nullptr;
+  void *iter_cb_user = nullptr;
   // last iteration's table row (for observers): fobj, infeas, l1, linfty, smax, tr, rho, model_reduc,
   // zav, zmax, gav, gmax
-  double row[12];
+  double row[12] = {};
   std::string row_info;
   // last line of the interior point's iteration table in the two subproblem solves of the latest iteration
   // ([0] steering / restoration solve, [1] the QP): how each solve ended (po_tr_get_last_solve_lines)
@@ -305,13 +331,32 @@ class TrustRegion {
   void captureSolveLine(int which);
 
  private:
-  bool own_sub = true, own_ip = true, state_ready = false;
+  TrustRegion(Problem *prob, TrustRegionSubproblem *subproblem);  // (subproblem == nullptr: built from the options)
+  bool own_sub, own_ip = true, state_ready = false;
   int initState();  // penalty parameters and radius from the options (the reference's constructor)
-  int eig_N, eig_index;
-  EigenModelUpdate eig_update;
-  void *eig_user;
-  Vec *tvec;
+  // the tail of build() and of optimize(ext): scratch, the interior-point solver (a new one on the subproblem, or
+  // the caller's `ext`), the quasi-Newton handle, the state
+  int attachSolver(InteriorPoint *ext);
+  int eig_N = 0, eig_index = 0;
+  EigenModelUpdate eig_update = nullptr;
+  void *eig_user = nullptr;
+  Vec *tvec = nullptr;
+  // violation of dense constraint i at the values c: max(0, -c_i) for an inequality, |c_i| for an equality
+  double violation(const double *c, int i) const { return i < nineq ? std::max(0.0, -c[i]) : fabs(c[i]); }
   double infeasOf(const double *c, const double *weights) const;
+  // One interior-point solve of the problem instance and options its caller has set: optimize, the last table line
+  // into last_solve_line[which], and where the solver left the step and the multipliers (its own storage).
+  // rc != PO_OK: the solve failed (not: stopped at its iteration limit) and nothing else is set.
+  struct Solution {
+    int rc;
+    Vec *step;
+    const double *z;
+    Vec *zw;
+  };
+  Solution solveSubproblem(int which);
+  // the tail of an iteration: multiplier and penalty statistics behind the caller's first eight columns, the
+  // quasi-Newton update token in front of the caller's info, the table row, the iteration count
+  void finishRow(const double head[8], const double *z, const std::string &info_tail, double t0);
   int computeKKTError(const double *z, Vec *zw, double *l1, double *linfty);
   int minimizeInfeas(std::vector<double> *best_con_infeas);
   int sl1qpOptimize();
@@ -326,7 +371,6 @@ class TrustRegion {
   void addToFilter(double f, double h);
   void appendRow(const double vals[12], const std::string &info, double seconds);
   int sl1qpUpdate(Vec *step, const double *z, Vec *zw, double *infeas, double *l1, double *linfty);
-  void flushHistory();
 };
 
 }  // namespace po

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden
-from tr_helpers import TR_REFERENCE_IRREPRODUCIBLE, compare_tr, eig_model, tr_options_from_case
+from tr_helpers import TR_REFERENCE_IRREPRODUCIBLE, compare_tr, eig_model, parse_tr_table, tr_options_from_case
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,8 @@ def ctx():
     c.close()
 
 
-def run_gpu_tr(ctx, case, python_eig_callback=False, capture_lines=None):
+def make_gpu_tr(ctx, case, python_eig_callback=False):
+    """problem and self-assembled driver of a golden's case (also what tools/tr_digest.py runs)"""
     import paropt_amd as pa
 
     a = case["args"]
@@ -53,6 +54,11 @@ def run_gpu_tr(ctx, case, python_eig_callback=False, capture_lines=None):
             tr.setEigenModel(N, a.get("eig_index", 0), upd)
         else:
             tr.setEigenModelSynthetic(N, a.get("eig_index", 0), a.get("seed", 0), a.get("eig_curv", 1.0))
+    return prob, tr
+
+
+def run_gpu_tr(ctx, case, python_eig_callback=False, capture_lines=None):
+    prob, tr = make_gpu_tr(ctx, case, python_eig_callback)
     snaps, rows = [], []
 
     def cb(i):
@@ -163,7 +169,7 @@ def test_tr_eigen_model_python_callback(ctx):
     compare_tr(g, rows, snaps, final, 12)
 
 
-def run_gpu_tr_objects(ctx, case):
+def make_gpu_tr_objects(ctx, case):
     """The reference's own assembly (src/ParOptOptimizer.cpp:108-183, examples/eigenvalue/eigenvalue_opt.py:298-308)
     through the object-level API: quasi-Newton object, (eigenvalue approximation + combined quasi-Newton object,)
     subproblem, an InteriorPoint built ON the subproblem, TrustRegion(subproblem).optimize(ip)."""
@@ -201,6 +207,11 @@ def run_gpu_tr_objects(ctx, case):
         sub = pa.QuadraticSubproblem(prob, qn)
     ip = pa.InteriorPoint(sub, opts)
     tr = pa.TrustRegion(sub, dict(tropts, **({"penalty_gamma": opts["penalty_gamma"]} if "penalty_gamma" in opts else {})))
+    return tr, ip, sub
+
+
+def run_gpu_tr_objects(ctx, case):
+    tr, ip, sub = make_gpu_tr_objects(ctx, case)
     rows = []
     tr.setIterationCallback(lambda i: rows.append(tr.getLastRow()) if i > 0 else None)
     tr.optimize(ip)
@@ -639,3 +650,53 @@ def test_infeas_subproblem_as_a_public_class(ctx):
     t = np.maximum(0.0, -(ck + A_np @ x))
     mine = scale * g_np @ x + gamma * t.sum()
     assert abs(mine - res.fun) <= 1e-6 * max(1.0, abs(res.fun)), (mine, res.fun)
+
+
+# Three paths of the driver that the configurations on record of tests/test_gpu_ip.py do not reach, each a fixed-length
+# optimize() at n = 201 (the stop test's l1 / linfty tolerances out of reach).  launches / syncs: what optimize() adds
+# to Context.counters() -- printed by tools/tr_digest.py with the library of the commit BEFORE the trust-region host
+# code was restructured (profiles/r24_tr_digest_parent.jsonl), not taken from the build under test: a restructuring
+# of the host code may not add, drop or reorder a launch or a host round trip.
+_TR_FIXED = {"tr_max_iterations": 6, "tr_l1_tol": 0.0, "tr_linfty_tol": 0.0, "qn_subspace_size": 5}
+TR_ON_RECORD = {
+    "filter_with_restoration": dict(problem="quadratic", n=201, c=3, user_subproblem=False, info_token="R",
+                                    opts=dict(_TR_FIXED, tr_accept_step_strategy="filter_method"),
+                                    launches=4248, syncs=1604),
+    "adaptive_gamma_subproblem_model": dict(problem="quadratic", n=201, c=3, user_subproblem=False, info_token=None,
+                                            opts=dict(_TR_FIXED, tr_adaptive_objective="subproblem_objective",
+                                                      tr_adaptive_constraint="subproblem_constraint",
+                                                      max_major_iters=100),  # (a steering solve may crawl)
+                                            launches=11818, syncs=4574),
+    "user_written_subproblem": dict(problem="quadratic", n=201, c=3, user_subproblem=True, info_token=None,
+                                    opts=_TR_FIXED, launches=6140, syncs=2356),
+}
+
+
+def optimize_tr_on_record(ctx, rec):
+    """runs rec's optimize(); returns the driver and (launches, syncs) added by it"""
+    import paropt_amd as pa
+
+    prob = pa.SeparableProblem(ctx, rec["problem"], rec["n"], rec["c"])
+    ip = None
+    if rec["user_subproblem"]:
+        sub = _user_quadratic_subproblem(pa, prob, pa.LBFGS(ctx, prob.nvars, rec["opts"]["qn_subspace_size"]))
+        ip = pa.InteriorPoint(sub, {"qn_subspace_size": rec["opts"]["qn_subspace_size"]})
+        tr = pa.TrustRegion(sub, {k: v for k, v in rec["opts"].items() if k.startswith("tr_")})
+    else:
+        tr = pa.TrustRegion(prob, rec["opts"])
+    syncs0, launches0 = ctx.counters()
+    tr.optimize(ip)
+    syncs1, launches1 = ctx.counters()
+    return tr, (launches1 - launches0, syncs1 - syncs0)
+
+
+@pytest.mark.parametrize("name", sorted(TR_ON_RECORD))
+def test_launches_and_syncs_of_the_trust_region_paths_on_record(ctx, name):
+    rec = TR_ON_RECORD[name]
+    tr, counts = optimize_tr_on_record(ctx, rec)
+    print(name, "launches, syncs:", counts)
+    infos = [toks for _, toks in parse_tr_table(tr.getHistory()).values()]
+    assert len(infos) == rec["opts"]["tr_max_iterations"]  # (fixed length: the stop test never fires)
+    if rec["info_token"]:  # the path the record is about was taken
+        assert any(rec["info_token"] in toks for toks in infos), infos
+    assert counts == (rec["launches"], rec["syncs"])

@@ -69,22 +69,13 @@ SWITCHES = [("SW_EXPLICIT_DOTS", 20, 1, {}), ("SW_NO_RECOMPUTE", 21, 1, {}), ("S
             ("SW_NO_FUSED_UPDATE", 26, 1, {}), ("SW_MPC_FUSE", 14, 0, MPC), ("SW_SPEC_DT", 16, 0, SEQ_LIN)]
 
 
-def main():
-    import numpy as np
-
-    import paropt_amd as pa
-    import sparse_forms_helpers as H
-    from paropt_amd import lib as L
-    from test_gpu_ip import ON_RECORD, SWEEP
-
-    ctx = pa.Context(0)
-
-    brief = "--brief" in sys.argv[1:]
+def helpers(ctx, brief, brief_keys=("config", "switch", "iteration_counters", "deltas")):
+    """(counters, delta, emit) of a digest over `ctx` (shared with tools/tr_digest.py)"""
 
     def emit(**rec):
         line = json.dumps(rec, sort_keys=True)
         if brief:
-            keep = {k: rec[k] for k in ("config", "switch", "iteration_counters", "deltas") if k in rec}
+            keep = {k: rec[k] for k in brief_keys if k in rec}
             line = json.dumps(dict(keep, sha256_of_line=hashlib.sha256(line.encode()).hexdigest()), sort_keys=True)
         print(line, flush=True)
 
@@ -96,6 +87,21 @@ def main():
     def delta(before):
         after = counters()
         return {k: after[k] - before[k] for k in sorted(after)}
+
+    return counters, delta, emit
+
+
+def main():
+    import numpy as np
+
+    import paropt_amd as pa
+    import sparse_forms_helpers as H
+    from paropt_amd import lib as L
+    from test_gpu_ip import ON_RECORD, SWEEP
+
+    ctx = pa.Context(0)
+
+    counters, delta, emit = helpers(ctx, "--brief" in sys.argv[1:])
 
     def run_ip(s, **tags):
         prob = pa.SeparableProblem(ctx, s["problem"], s["n"], s["c"])
