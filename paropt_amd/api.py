@@ -2685,6 +2685,36 @@ def _f64(values):
     return a, a.ctypes.data_as(L.c_double_p)
 
 
+def _f64_sized(sizes, message, *values):
+    """_f64 of each array; ValueError(message) unless array i holds sizes[i] entries.  Returns the pointers."""
+    pairs = [_f64(v) for v in values]
+    if any(a.size != n for (a, _), n in zip(pairs, sizes)):
+        raise ValueError(message)
+    return [ptr for _, ptr in pairs]
+
+
+def _mma_eval_outputs(m, hessian):
+    """W, grad and H (None unless `hessian`) of an evaluation, and the three pointers the entries take for them."""
+    W, g = C.c_double(), np.zeros(max(m, 1))
+    H = np.zeros((m, m)) if hessian else None
+    return W, g, H, (C.byref(W), g.ctypes.data_as(L.c_double_p),
+                     H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None)
+
+
+def _handles(vecs, count=3):
+    """The handles of optional PVecs: of each of `vecs`, or `count` times None when there are none."""
+    if vecs is None:
+        return [None] * count
+    return [v.handle if v is not None else None for v in vecs]
+
+
+def _group_args(nwcon, nw, start, skip, a, c, nwinequality, gamma):
+    return (int(nwcon), int(nw), int(start), int(skip), float(a), _handles([c])[0], int(nwinequality), float(gamma))
+
+
+_LAM_RHO = "lam holds one entry per constraint, rho one more"
+
+
 def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessian=True, point=None, xk=None, rho=None):
     """The dual function of an MMA subproblem given by caller vectors (po_mma_dual_eval): returns (W, grad, H) with
     H = minus the Hessian (None unless `hessian`).  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu)
@@ -2698,31 +2728,19 @@ def mma_dual_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form=0, hessia
             raise ValueError("mma_dual_eval: the point of the rho form comes from mma_gcmma_point")
         return _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho)
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_dual_eval: ")
-    (ba, bp), (la, lp) = _f64(b), _f64(lam)
-    if ba.size != m or la.size != m:
-        raise ValueError("mma_dual_eval: b and lam must hold one entry per constraint")
-    W = C.c_double()
-    g = np.zeros(max(m, 1))
-    H = np.zeros((m, m)) if hessian else None
-    xs = [v.handle for v in point] if point is not None else [None, None, None]
-    check(lib.po_mma_dual_eval(*head, bp, lp, int(form), C.byref(W), g.ctypes.data_as(L.c_double_p),
-                               H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1], xs[2]))
+    bp, lp = _f64_sized((m, m), "mma_dual_eval: b and lam must hold one entry per constraint", b, lam)
+    W, g, H, out = _mma_eval_outputs(m, hessian)
+    check(lib.po_mma_dual_eval(*head, bp, lp, int(form), *out, *_handles(point)))
     return W.value, g[:m], H
 
 
 def _mma_dual_eval_rho(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, form, hessian, xk, rho):
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q)
-    (la, lp), (ra, rp), (ba, bp) = _f64(lam), _f64(rho), _f64(b)
-    if la.size != m or ra.size != m + 1:
-        raise ValueError("lam holds one entry per constraint, rho one more")
-    if ba.size != m:
-        raise ValueError("mma_dual_eval: b must hold one entry per constraint")
-    W, D = C.c_double(), C.c_double()
-    g = np.zeros(max(m, 1))
-    H = np.zeros((m, m)) if hessian else None
-    check(lib.po_mma_dual_eval_rho(*head, bp, lp, xk.handle, rp, int(form), C.byref(W),
-                                   g.ctypes.data_as(L.c_double_p),
-                                   H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, C.byref(D)))
+    lp, rp = _f64_sized((m, m + 1), _LAM_RHO, lam, rho)
+    bp, = _f64_sized((m,), "mma_dual_eval: b must hold one entry per constraint", b)
+    W, g, H, out = _mma_eval_outputs(m, hessian)
+    D = C.c_double()
+    check(lib.po_mma_dual_eval_rho(*head, bp, lp, xk.handle, rp, int(form), *out, C.byref(D)))
     return W.value, g[:m], H, D.value
 
 
@@ -2733,20 +2751,13 @@ def mma_dual_linear_eval(ctx, Lo, Up, alpha, beta, p0, q0, A, cons, xk, lam, xst
     x(lam) on return.  form: 0 the library's choice, 1 fused, 2 panel.  point = (x, zl, zu) PVecs: also filled with the
     primal point and its bound multipliers at lam."""
     m = len(A)
-    (ca, cp), (la, lp) = _f64(cons), _f64(lam)
-    if ca.size != m or la.size != m:
-        raise ValueError("mma_dual_linear_eval: cons and lam must hold one entry per constraint")
+    cp, lp = _f64_sized((m, m), "mma_dual_linear_eval: cons and lam must hold one entry per constraint", cons, lam)
     cols = (L.po_vec * max(m, 1))(*[v.handle for v in A])
-    W = C.c_double()
-    g = np.zeros(max(m, 1))
-    H = np.zeros((m, m)) if hessian else None
+    W, g, H, out = _mma_eval_outputs(m, hessian)
     st = np.zeros(2)
-    xs = [v.handle for v in point] if point is not None else [None, None, None]
     check(lib.po_mma_dual_linear_eval(ctx.handle, m, Lo.handle, Up.handle, alpha.handle, beta.handle, p0.handle,
-                                      q0.handle, cols, cp, xk.handle, lp, int(form), xstart.handle, C.byref(W),
-                                      g.ctypes.data_as(L.c_double_p),
-                                      H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None, xs[0], xs[1],
-                                      xs[2], st.ctypes.data_as(L.c_double_p)))
+                                      q0.handle, cols, cp, xk.handle, lp, int(form), xstart.handle, *out,
+                                      *_handles(point), st.ctypes.data_as(L.c_double_p)))
     return W.value, g[:m], H, dict(cap_hits=int(st[0]), max_steps=int(st[1]))
 
 
@@ -2761,24 +2772,16 @@ def mma_dual_group_eval(ctx, Lo, Up, alpha, beta, p0, q0, p, q, b, lam, nwcon, n
     if (xk is None) != (rho is None):
         raise ValueError("mma_dual_group_eval: xk and rho are given together")
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_dual_group_eval: ")
-    (ba, bp), (la, lp) = _f64(b), _f64(lam)
-    if ba.size != m or la.size != m:
-        raise ValueError("mma_dual_group_eval: b and lam must hold one entry per constraint")
-    W, D = C.c_double(), C.c_double()
-    g = np.zeros(max(m, 1))
-    H = np.zeros((m, m)) if hessian else None
+    bp, lp = _f64_sized((m, m), "mma_dual_group_eval: b and lam must hold one entry per constraint", b, lam)
+    W, g, H, out = _mma_eval_outputs(m, hessian)
     st = np.zeros(8)
-    args = (*head, bp, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
-            c.handle if c is not None else None, int(nwinequality), float(gamma), C.byref(W),
-            g.ctypes.data_as(L.c_double_p), H.ctypes.data_as(L.c_double_p) if hessian and m > 0 else None,
-            point[0].handle, point[1].handle, point[2].handle, zw.handle if zw is not None else None,
-            st.ctypes.data_as(L.c_double_p))
+    args = (*head, bp, lp, *_group_args(nwcon, nw, start, skip, a, c, nwinequality, gamma), *out,
+            *_handles([*point, zw]), st.ctypes.data_as(L.c_double_p))
     if xk is None:
         check(lib.po_mma_dual_group_eval(*args))
         return W.value, g[:m], H, _group_stats(st)
-    ra, rp = _f64(rho)
-    if ra.size != m + 1:
-        raise ValueError("mma_dual_group_eval: rho holds one entry per constraint and one more")
+    rp, = _f64_sized((m + 1,), "mma_dual_group_eval: rho holds one entry per constraint and one more", rho)
+    D = C.c_double()
     check(lib.po_mma_dual_group_eval_rho(*args, xk.handle, rp, C.byref(D)))
     return W.value, g[:m], H, _group_stats(st), D.value
 
@@ -2794,14 +2797,10 @@ def mma_gcmma_group_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, nwcon, nw
     at lam for the approximations f~_i + rho_i d around xk fills point = (x, zl, zu) and zw; returns (sums, stats)
     with the m + 2 sums [Delta_0, Delta_1..m, D] of mma_gcmma_point at that x."""
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q, "mma_gcmma_group_point: ")
-    (la, lp), (ra, rp) = _f64(lam), _f64(rho)
-    if la.size != m or ra.size != m + 1:
-        raise ValueError("lam holds one entry per constraint, rho one more")
+    lp, rp = _f64_sized((m, m + 1), _LAM_RHO, lam, rho)
     sums, st = np.zeros(m + 2), np.zeros(8)
-    check(lib.po_mma_gcmma_group_point(*head, lp, int(nwcon), int(nw), int(start), int(skip), float(a),
-                                       c.handle if c is not None else None, int(nwinequality), float(gamma),
-                                       xk.handle, rp, point[0].handle, point[1].handle, point[2].handle,
-                                       zw.handle if zw is not None else None, sums.ctypes.data_as(L.c_double_p),
+    check(lib.po_mma_gcmma_group_point(*head, lp, *_group_args(nwcon, nw, start, skip, a, c, nwinequality, gamma),
+                                       xk.handle, rp, *_handles([*point, zw]), sums.ctypes.data_as(L.c_double_p),
                                        st.ctypes.data_as(L.c_double_p)))
     return sums, _group_stats(st)
 
@@ -2810,12 +2809,9 @@ def mma_gcmma_point(ctx, Lo, Up, alpha, beta, p0, q0, p, q, lam, xk, rho, point)
     """The point pass of a conservative inner iteration (po_mma_gcmma_point): fills point = (x, zl, zu) PVecs at lam
     and returns the m + 2 sums [Delta_0, Delta_1..m, D]."""
     m, head = _mma_subproblem_args(ctx, Lo, Up, alpha, beta, p0, q0, p, q)
-    (la, lp), (ra, rp) = _f64(lam), _f64(rho)
-    if la.size != m or ra.size != m + 1:
-        raise ValueError("lam holds one entry per constraint, rho one more")
+    lp, rp = _f64_sized((m, m + 1), _LAM_RHO, lam, rho)
     sums = np.zeros(m + 2)
-    check(lib.po_mma_gcmma_point(*head, lp, xk.handle, rp, point[0].handle, point[1].handle, point[2].handle,
-                                 sums.ctypes.data_as(L.c_double_p)))
+    check(lib.po_mma_gcmma_point(*head, lp, xk.handle, rp, *_handles(point), sums.ctypes.data_as(L.c_double_p)))
     return sums
 
 

@@ -1,5 +1,7 @@
 // C ABI of the method of moving asymptotes (include/paropt_amd.h, "ParOptMMA"): the driver object, the views of its
 // current subproblem, and the dual passes on caller vectors.
+#include <initializer_list>
+#include <utility>
 #include <vector>
 
 #include "mma.hpp"
@@ -158,56 +160,114 @@ int po_mma_get_dual_linear_stats(po_mma mma, long *cap_hits, int *max_steps) {
   if (max_steps) *max_steps = s.max_steps;
   return PO_OK;
 }
-// the dual of that subproblem on caller vectors (gradients of :871-924 with use_true_mma = 0: the A_i themselves)
-int po_mma_dual_linear_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
-                            const po_vec *A, const double *cons, po_vec xk, const double *lambda, int form,
-                            po_vec xstart_inout, double *W, double *grad, double *hess, po_vec x, po_vec zl,
-                            po_vec zu, double *stats) {
-  const char *who = "po_mma_dual_linear_eval";
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
-  PO_CHECK_PTR(W);
-  PO_CHECK_PTR(grad);
-  if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax, kMmaDualFused);
+// ---- the dual passes on caller vectors --------------------------------------------------------------------------------
+namespace {
+struct Columns {  // m caller vectors, the name a null entry is reported under, and the table of their device pointers
+  const po_vec *v;
+  const char *name;
+  std::vector<const double *> *table;
+};
+// The argument checks of the entries below.  Each entry calls them in the order it has always checked in, so a call
+// with several faults is refused for the same one as before.
+struct ArgCheck {
+  const char *who;
+  po_ctx ctx;
+  int m;
+  po_vec L;  // every other vector has its layout
+
+  static int null(const char *name) {
+    po::set_error("null argument: %s", name);
     return PO_ERR_ARG;
   }
-  if (m > 0) {
-    PO_CHECK_PTR(A);
-    PO_CHECK_PTR(cons);
-    PO_CHECK_PTR(lambda);
+  int head(bool outputs, const double *W, const double *grad) const {  // ctx, L and the outputs of an evaluation
+    if (!ctx) return null("ctx");
+    if (!L) return null("L");
+    if (outputs && !W) return null("W");
+    if (outputs && !grad) return null("grad");
+    return PO_OK;
   }
-  std::vector<po_vec> nvecs = {L, U, alpha, beta, p0, q0, xk, xstart_inout};
-  for (int i = 0; i < m; i++) nvecs.push_back(A[i]);
-  for (po_vec v : nvecs) {
-    PO_CHECK_PTR(v);
+  int range(int form) const {
+    if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
+      po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax,
+                    kMmaDualFused);
+      return PO_ERR_ARG;
+    }
+    return PO_OK;
+  }
+  int range() const {
+    if (m < 0 || m > kMmaDualMax) {
+      po::set_error("%s: m = %d outside 0..%d", who, m, kMmaDualMax);
+      return PO_ERR_ARG;
+    }
+    return PO_OK;
+  }
+  int arrays(std::initializer_list<std::pair<const void *, const char *>> given) const {  // of m entries: read if m > 0
+    for (const auto &a : given)
+      if (m > 0 && !a.first) return null(a.second);
+    return PO_OK;
+  }
+  int vec(po_vec v, const char *name = "v") const {  // given, on ctx, of the length of L
+    if (!v) return null(name);
     if (v->ctx != ctx || v->n != L->n) {
       po::set_error("%s: vectors of different layouts", who);
       return PO_ERR_ARG;
     }
+    return PO_OK;
   }
-  const po_vec outs[] = {x, zl, zu};
-  for (po_vec v : outs) {
-    if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
-      po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
-      return PO_ERR_ARG;
+  int vectors(std::initializer_list<po_vec> vs) const {
+    for (po_vec v : vs) PO_TRY(vec(v));
+    return PO_OK;
+  }
+  int point(po_vec x, po_vec zl, po_vec zu) const {  // the optional outputs: all or none
+    for (po_vec v : {x, zl, zu}) {
+      if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
+        po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
+        return PO_ERR_ARG;
+      }
     }
+    return PO_OK;
   }
-  std::vector<const double *> cols;
-  for (int i = 0; i < m; i++) cols.push_back(A[i]->d);
-  const MmaDualLinear s{L->d, U->d, alpha->d, beta->d, p0->d, q0->d, xk->d, cols.data(), cons, m, L->n};
+  // column by column; nulls_first: the entries of one index are all checked for null before any layout of that index
+  int columns(std::initializer_list<Columns> arrays, bool nulls_first) const {
+    for (int i = 0; i < m; i++) {
+      for (const Columns &a : arrays)
+        if (nulls_first && !a.v[i]) return null(a.name);
+      for (const Columns &a : arrays) PO_TRY(vec(a.v[i], a.name));
+    }
+    for (const Columns &a : arrays)
+      for (int i = 0; i < m; i++) a.table->push_back(a.v[i]->d);
+    return PO_OK;
+  }
+};
+// form 0 is the library's choice; without a Hessian every form is the value and the gradient alone
+int entry_form(int form, int m, const double *hess) {
   if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
-  if (!hess) form = 0;
-  Vec *dvec = nullptr;  // the panel form's weights
-  if (form == 2 && !(dvec = vec_new(ctx, L->n))) return PO_ERR_HIP;
+  return hess ? form : 0;
+}
+}  // namespace
+
+// the dual of the linearised subproblem (gradients of :871-924 with use_true_mma = 0: the A_i themselves)
+int po_mma_dual_linear_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
+                            const po_vec *A, const double *cons, po_vec xk, const double *lambda, int form,
+                            po_vec xstart_inout, double *W, double *grad, double *hess, po_vec x, po_vec zl,
+                            po_vec zu, double *stats) {
+  const ArgCheck ck{"po_mma_dual_linear_eval", ctx, m, L};
+  std::vector<const double *> cols;
+  PO_TRY(ck.head(true, W, grad));
+  PO_TRY(ck.range(form));
+  PO_TRY(ck.arrays({{A, "A"}, {cons, "cons"}, {lambda, "lambda"}}));
+  PO_TRY(ck.vectors({L, U, alpha, beta, p0, q0, xk, xstart_inout}));
+  PO_TRY(ck.columns({{A, "v", &cols}}, false));
+  PO_TRY(ck.point(x, zl, zu));
+  const MmaDualLinear s{L->d, U->d, alpha->d, beta->d, p0->d, q0->d, xk->d, cols.data(), cons, m, L->n};
+  form = entry_form(form, m, hess);
+  WorkVecs work(ctx);  // the panel form's weights
+  if (form == 2) PO_TRY(work.add(1, L->n));
   MmaLinearStats st;
   int rc = k_mma_dual_linear(ctx, s, lambda, form, xstart_inout->d, xstart_inout->d, W, grad, hess,
-                             dvec ? dvec->d : nullptr, &st);
+                             form == 2 ? work.d(0) : nullptr, &st);
   if (rc == PO_OK && x) rc = k_mma_dual_linear_point(ctx, s, lambda, xstart_inout->d, x->d, zl->d, zu->d, &st);
-  if (dvec) {
-    if (rc == PO_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
-    vec_decref(dvec);
-  }
+  rc = work.release(rc);
   if (rc == PO_OK && stats) {
     stats[0] = (double)st.cap_hits;
     stats[1] = (double)st.max_steps;
@@ -239,81 +299,32 @@ struct DualCall {
 // the shared body of po_mma_dual_eval / po_mma_dual_eval_rho / po_mma_gcmma_point: argument checks, the tables and the
 // panel form's work vectors
 static int mma_dual_entry(const DualCall &a) {
-  const char *who = a.who;
-  const po_ctx ctx = a.ctx;
+  const DualVectors &v = a.v;
   const int m = a.m;
-  const po_vec L = a.v.L, x = a.x, zl = a.zl, zu = a.zu;
-  const po_vec *p = a.v.p, *q = a.v.q;
-  const double *b = a.b, *lambda = a.lambda;
-  double *W = a.W, *grad = a.grad, *hess = a.hess;
   const bool with_rho = a.pass != EVAL;
-  int form = a.form;
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
-  if (a.pass != POINT) {
-    PO_CHECK_PTR(W);
-    PO_CHECK_PTR(grad);
-  }
-  if (m < 0 || m > kMmaDualMax || form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    po::set_error("%s: m = %d, form = %d: m is 0..%d, form 1 covers m <= %d", who, m, form, kMmaDualMax, kMmaDualFused);
-    return PO_ERR_ARG;
-  }
-  if (m > 0) {
-    PO_CHECK_PTR(p);
-    PO_CHECK_PTR(q);
-    PO_CHECK_PTR(b);
-    PO_CHECK_PTR(lambda);
-  }
-  const po_vec six[] = {a.v.U, a.v.alpha, a.v.beta, a.v.p0, a.v.q0, with_rho ? a.xk : a.v.U};
+  const ArgCheck ck{a.who, a.ctx, m, v.L};
   std::vector<const double *> pp, qq;
-  for (po_vec v : six) {
-    PO_CHECK_PTR(v);
-    if (v->ctx != L->ctx || v->n != L->n || L->ctx != ctx) {
-      po::set_error("%s: vectors of different layouts", who);
-      return PO_ERR_ARG;
-    }
-  }
-  const po_vec outs[] = {x, zl, zu};
-  for (po_vec v : outs) {
-    if ((v != nullptr) != (x != nullptr) || (v && (v->ctx != ctx || v->n != L->n))) {
-      po::set_error("%s: x, zl and zu are given together, in the layout of L", who);
-      return PO_ERR_ARG;
-    }
-  }
-  for (int i = 0; i < m; i++) {
-    PO_CHECK_PTR(p[i]);
-    PO_CHECK_PTR(q[i]);
-    if (p[i]->ctx != ctx || q[i]->ctx != ctx || p[i]->n != L->n || q[i]->n != L->n) {
-      po::set_error("%s: vectors of different layouts", who);
-      return PO_ERR_ARG;
-    }
-    pp.push_back(p[i]->d);
-    qq.push_back(q[i]->d);
-  }
-  const MmaDualData s = mma_dual_data(L->d, a.v.U->d, a.v.alpha->d, a.v.beta->d, a.v.p0->d, a.v.q0->d, pp.data(),
-                                      qq.data(), b, m, L->n);
+  PO_TRY(ck.head(a.pass != POINT, a.W, a.grad));
+  PO_TRY(ck.range(a.form));
+  PO_TRY(ck.arrays({{v.p, "p"}, {v.q, "q"}, {a.b, "b"}, {a.lambda, "lambda"}}));
+  PO_TRY(ck.vectors({v.L, v.U, v.alpha, v.beta, v.p0, v.q0, with_rho ? a.xk : v.U}));
+  PO_TRY(ck.point(a.x, a.zl, a.zu));
+  PO_TRY(ck.columns({{v.p, "p[i]", &pp}, {v.q, "q[i]", &qq}}, true));
+  const int64_t n = v.L->n;
+  const MmaDualData s = mma_dual_data(v.L->d, v.U->d, v.alpha->d, v.beta->d, v.p0->d, v.q0->d, pp.data(), qq.data(),
+                                      a.b, m, n);
   const MmaDualRho r{with_rho ? a.xk->d : nullptr, a.rho};
-  if (a.pass == POINT) return k_mma_gcmma_point(ctx, s, r, lambda, x->d, zl->d, zu->d, a.sums);
-  if (form == 0) form = m <= kMmaDualFused ? 1 : 2;
-  if (!hess) form = 0;
-  std::vector<Vec *> work;  // the panel form's columns and weights
-  std::vector<double *> G;
-  int rc = PO_OK;
-  if (form == 2) {
-    for (int i = 0; i < m + 1 && rc == PO_OK; i++) {
-      Vec *v = vec_new(ctx, L->n);
-      if (!v) rc = PO_ERR_HIP;
-      else work.push_back(v);
-    }
-    for (int i = 0; i < m && rc == PO_OK; i++) G.push_back(work[i]->d);
+  if (a.pass == POINT) return k_mma_gcmma_point(a.ctx, s, r, a.lambda, a.x->d, a.zl->d, a.zu->d, a.sums);
+  const int form = entry_form(a.form, m, a.hess);
+  WorkVecs work(a.ctx);  // the panel form's columns and weights
+  int rc = form == 2 ? work.add(m + 1, n) : PO_OK;
+  if (rc == PO_OK) {
+    const std::vector<double *> G = work.pointers(0, form == 2 ? m : 0);
+    rc = k_mma_dual(a.ctx, s, a.lambda, form, a.W, a.grad, a.hess, form == 2 ? G.data() : nullptr,
+                    form == 2 ? work.d(m) : nullptr, with_rho ? &r : nullptr, a.D);
   }
-  if (rc == PO_OK)
-    rc = k_mma_dual(ctx, s, lambda, form, W, grad, hess, form == 2 ? G.data() : nullptr,
-                    form == 2 ? work[m]->d : nullptr, with_rho ? &r : nullptr, a.D);
-  if (rc == PO_OK && x) rc = k_mma_dual_point(ctx, s, lambda, x->d, zl->d, zu->d);
-  if (rc == PO_OK && !work.empty()) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
-  for (Vec *v : work) vec_decref(v);
-  return rc;
+  if (rc == PO_OK && a.x) rc = k_mma_dual_point(a.ctx, s, a.lambda, a.x->d, a.zl->d, a.zu->d);
+  return work.release(rc);
 }
 int po_mma_dual_eval(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_vec beta, po_vec p0, po_vec q0,
                      const po_vec *p, const po_vec *q, const double *b, const double *lambda, int form, double *W,
@@ -344,28 +355,17 @@ int po_mma_gcmma_point(po_ctx ctx, int m, po_vec L, po_vec U, po_vec alpha, po_v
                          .x = x, .zl = zl, .zu = zu, .sums = sums});
 }
 int po_mma_gcmma_rho_sums(po_ctx ctx, int m, po_vec L, po_vec U, po_vec g, const po_vec *A, double *sums) {
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
+  const ArgCheck ck{"po_mma_gcmma_rho_sums", ctx, m, L};
+  std::vector<const double *> cols;
+  PO_TRY(ck.head(false, nullptr, nullptr));
   PO_CHECK_PTR(U);
   PO_CHECK_PTR(g);
   PO_CHECK_PTR(sums);
-  if (m < 0 || m > kMmaDualMax) {
-    po::set_error("po_mma_gcmma_rho_sums: m = %d outside 0..%d", m, kMmaDualMax);
-    return PO_ERR_ARG;
-  }
-  if (m > 0) PO_CHECK_PTR(A);
-  std::vector<const double *> cols;
-  for (int i = 0; i < m; i++) {
-    PO_CHECK_PTR(A[i]);
-    cols.push_back(A[i]->d);
-  }
-  for (int i = -2; i < m; i++) {
-    const po_vec v = i == -2 ? U : i == -1 ? g : A[i];
-    if (v->ctx != ctx || L->ctx != ctx || v->n != L->n) {
-      po::set_error("po_mma_gcmma_rho_sums: vectors of different layouts");
-      return PO_ERR_ARG;
-    }
-  }
+  PO_TRY(ck.range());
+  PO_TRY(ck.arrays({{A, "A"}}));
+  for (int i = 0; i < m; i++) PO_CHECK_PTR(A[i]);  // (every null column is reported before any layout)
+  PO_TRY(ck.vectors({L, U, g}));
+  PO_TRY(ck.columns({{A, "A[i]", &cols}}, true));
   return k_mma_gcmma_rho_sums(ctx, L->d, U->d, g->d, cols.data(), m, L->n, sums);
 }
 namespace {
@@ -392,107 +392,70 @@ struct GroupCall {  // po_mma_dual_group_eval / _rho (W != NULL) and po_mma_gcmm
 };
 }  // namespace
 static int mma_group_entry(const GroupCall &k) {
-  const char *who = k.who;
-  const po_ctx ctx = k.ctx;
+  const DualVectors &v = k.v;
   const int m = k.m;
-  const po_vec L = k.v.L, U = k.v.U, alpha = k.v.alpha, beta = k.v.beta, p0 = k.v.p0, q0 = k.v.q0;
-  const po_vec *p = k.v.p, *q = k.v.q;
-  const double *b = k.b, *lambda = k.lambda;
-  const int64_t nwcon = k.nwcon, start = k.start, nwinequality = k.nwinequality;
-  const int nw = k.nw, skip = k.skip;
-  const double a = k.a, gamma = k.gamma;
-  const po_vec c = k.c, x = k.x, zl = k.zl, zu = k.zu, zw = k.zw;
-  double *W = k.W, *grad = k.grad, *hess = k.hess, *stats = k.stats;
+  const int64_t nwcon = k.nwcon;
   const bool point = k.sums != nullptr;
-  PO_CHECK_PTR(ctx);
-  PO_CHECK_PTR(L);
-  if (!point) {
-    PO_CHECK_PTR(W);
-    PO_CHECK_PTR(grad);
-  }
-  if (m < 0 || m > kMmaDualMax) {
-    po::set_error("%s: m = %d outside 0..%d", who, m, kMmaDualMax);
-    return PO_ERR_ARG;
-  }
-  if (m > 0) {
-    PO_CHECK_PTR(p);
-    PO_CHECK_PTR(q);
-    PO_CHECK_PTR(b);
-    PO_CHECK_PTR(lambda);
-  }
-  std::vector<po_vec> nvecs = {L, U, alpha, beta, p0, q0, x, zl, zu};
-  if (k.rho) nvecs.push_back(k.xk);
-  for (int i = 0; i < m; i++) {
-    nvecs.push_back(p[i]);
-    nvecs.push_back(q[i]);
-  }
-  for (po_vec v : nvecs) {
-    PO_CHECK_PTR(v);
-    if (v->ctx != ctx || v->n != L->n) {
-      po::set_error("%s: vectors of different layouts", who);
-      return PO_ERR_ARG;
-    }
-  }
+  const ArgCheck ck{k.who, k.ctx, m, v.L};
+  const char *who = k.who;
+  std::vector<const double *> pp, qq;
+  PO_TRY(ck.head(!point, k.W, k.grad));
+  PO_TRY(ck.range());
+  PO_TRY(ck.arrays({{v.p, "p"}, {v.q, "q"}, {k.b, "b"}, {k.lambda, "lambda"}}));
+  PO_TRY(ck.vectors({v.L, v.U, v.alpha, v.beta, v.p0, v.q0, k.x, k.zl, k.zu}));
+  if (k.rho) PO_TRY(ck.vec(k.xk));
+  PO_TRY(ck.columns({{v.p, "v", &pp}, {v.q, "v", &qq}}, false));
+  const int64_t n = v.L->n;
   MmaDualGroups g;
   g.map.nwcon = nwcon;
-  g.map.nw = nw;
-  g.map.start = start;
-  g.map.skip = skip;
-  g.a = a;
-  g.nwinequality = nwinequality;
-  g.gamma = gamma;
-  if (nwcon < 0 || (nwcon > 0 && (nw <= 0 || skip < 0 || !mma_dual_groups_tile(g.map, L->n))) || !(gamma > 0.0) ||
-      nwinequality < 0) {
+  g.map.nw = k.nw;
+  g.map.start = k.start;
+  g.map.skip = k.skip;
+  g.a = k.a;
+  g.nwinequality = k.nwinequality;
+  g.gamma = k.gamma;
+  if (nwcon < 0 || (nwcon > 0 && (k.nw <= 0 || k.skip < 0 || !mma_dual_groups_tile(g.map, n))) || !(k.gamma > 0.0) ||
+      k.nwinequality < 0) {
     po::set_error("%s: groups (nwcon %lld, nw %d, skip %d, start %lld) must lie inside the %lld variables with "
-                  "nw + skip <= 512, and gamma > 0", who, (long long)nwcon, nw, skip, (long long)start, (long long)L->n);
+                  "nw + skip <= 512, and gamma > 0", who, (long long)nwcon, k.nw, k.skip, (long long)k.start,
+                  (long long)n);
     return PO_ERR_ARG;
   }
   if (nwcon > 0) {
-    PO_CHECK_PTR(c);
-    PO_CHECK_PTR(zw);
-    if (c->ctx != ctx || zw->ctx != ctx || c->n != nwcon || zw->n != nwcon) {
+    if (!k.c) return ArgCheck::null("c");
+    if (!k.zw) return ArgCheck::null("zw");
+    if (k.c->ctx != k.ctx || k.zw->ctx != k.ctx || k.c->n != nwcon || k.zw->n != nwcon) {
       po::set_error("%s: c and zw hold nwcon = %lld values", who, (long long)nwcon);
       return PO_ERR_ARG;
     }
-    g.c = c->d;
+    g.c = k.c->d;
   }
-  std::vector<const double *> pp, qq;
-  for (int i = 0; i < m; i++) {
-    pp.push_back(p[i]->d);
-    qq.push_back(q[i]->d);
-  }
-  const MmaDualData s = mma_dual_data(L->d, U->d, alpha->d, beta->d, p0->d, q0->d, pp.data(), qq.data(), b, m, L->n);
+  double *const zw = nwcon > 0 ? k.zw->d : nullptr;
+  const MmaDualData s = mma_dual_data(v.L->d, v.U->d, v.alpha->d, v.beta->d, v.p0->d, v.q0->d, pp.data(), qq.data(),
+                                      k.b, m, n);
   const MmaDualRho r{k.rho ? k.xk->d : nullptr, k.rho};
   MmaGroupStats st;
   auto put_stats = [&]() {
     const double out[8] = {(double)st.strict,    (double)st.at_lower, (double)st.at_gamma, (double)st.cap_hits,
                            (double)st.steps,     (double)st.max_inner, st.max_psi,         st.zw_psi};
-    for (int i = 0; i < 8 && stats; i++) stats[i] = out[i];
+    for (int i = 0; i < 8 && k.stats; i++) k.stats[i] = out[i];
   };
   if (point) {
-    PO_TRY(k_mma_group_solve(ctx, s, g, lambda, x->d, nwcon > 0 ? zw->d : nullptr, zl->d, zu->d, &st, &r));
-    PO_TRY(k_mma_gcmma_group_sums(ctx, s, r.xk, x->d, k.sums));
+    PO_TRY(k_mma_group_solve(k.ctx, s, g, k.lambda, k.x->d, zw, k.zl->d, k.zu->d, &st, &r));
+    PO_TRY(k_mma_gcmma_group_sums(k.ctx, s, r.xk, k.x->d, k.sums));
     put_stats();
     return PO_OK;
   }
-  std::vector<Vec *> work;  // G (m of n), d (n), Uw (m of nwcon), sw (nwcon)
-  std::vector<double *> G, Uw;
-  int rc = PO_OK;
-  const int nw_work = nwcon > 0 ? m + 1 : 0;
-  for (int i = 0; i < m + 1 + nw_work && rc == PO_OK; i++) {
-    Vec *v = vec_new(ctx, i <= m ? L->n : nwcon);
-    if (!v) rc = PO_ERR_HIP;
-    else work.push_back(v);
-  }
+  WorkVecs work(k.ctx);  // G (m of n), d (n), and with groups Uw (m of nwcon), sw (nwcon)
+  int rc = work.add(m + 1, n);
+  if (rc == PO_OK && nwcon > 0) rc = work.add(m + 1, nwcon);
   if (rc == PO_OK) {
-    for (int i = 0; i < m; i++) G.push_back(work[i]->d);
-    for (int i = 0; i < m && nwcon > 0; i++) Uw.push_back(work[m + 1 + i]->d);
-    rc = k_mma_dual_groups(ctx, s, g, lambda, W, grad, hess, G.data(), work[m]->d, x->d, nwcon > 0 ? zw->d : nullptr,
-                           nwcon > 0 ? Uw.data() : nullptr, nwcon > 0 ? work[2 * m + 1]->d : nullptr, zl->d, zu->d,
+    const std::vector<double *> G = work.pointers(0, m), Uw = work.pointers(m + 1, nwcon > 0 ? m : 0);
+    rc = k_mma_dual_groups(k.ctx, s, g, k.lambda, k.W, k.grad, k.hess, G.data(), work.d(m), k.x->d, zw,
+                           nwcon > 0 ? Uw.data() : nullptr, nwcon > 0 ? work.d(2 * m + 1) : nullptr, k.zl->d, k.zu->d,
                            &st, k.rho ? &r : nullptr, k.D);
   }
-  if (rc == PO_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? PO_OK : PO_ERR_HIP;
-  for (Vec *v : work) vec_decref(v);
+  rc = work.release(rc);
   if (rc == PO_OK) put_stats();
   return rc;
 }

@@ -80,12 +80,14 @@ int MMA::allocate() {  // initialize() :131-232
   return PO_OK;
 }
 
-bool MMA::wantDual() { return std::string(options().str("mma_subproblem_solver")) == "dual"; }
-bool MMA::wantGroups() { return std::string(options().str("mma_dual_sparse_constraints")) == "groups"; }
-bool MMA::wantLinear() {
-  return options().integer("mma_use_constraint_linearization") != 0 &&
-         std::string(options().str("mma_dual_linearized_constraints")) == "newton";
-}
+// what the options ask for: every option string is compared here
+bool MMA::optionIs(const char *name, const char *value) { return std::string(options().str(name)) == value; }
+bool MMA::wantDual() { return optionIs("mma_subproblem_solver", "dual"); }
+bool MMA::wantGroups() { return optionIs("mma_dual_sparse_constraints", "groups"); }
+bool MMA::wantGcmmaGroups() { return optionIs("mma_gcmma_sparse_constraints", "groups"); }
+bool MMA::conservative() { return optionIs("mma_globalization", "conservative"); }
+bool MMA::linearised() { return options().integer("mma_use_constraint_linearization") != 0; }
+bool MMA::wantLinear() { return linearised() && optionIs("mma_dual_linearized_constraints", "newton"); }
 
 int MMA::build() {
   if (ip || xvec) return PO_OK;
@@ -132,8 +134,7 @@ int MMA::checkDualCovers() {
   const GroupMap *gm = prob->groupedLibraryForm();
   if (nwcon > 0 && !wantGroups()) {
     why = "sparse constraints are not part of the closed-form primal point";
-  } else if (nwcon > 0 && std::string(options().str("mma_globalization")) == "conservative" &&
-             std::string(options().str("mma_gcmma_sparse_constraints")) != "groups") {
+  } else if (nwcon > 0 && conservative() && !wantGcmmaGroups()) {
     why = "sparse constraints in groups run under mma_globalization = conservative only with "
           "mma_gcmma_sparse_constraints = groups";
   } else if (nwcon > 0 && (!gm || gm->nwcon != nwcon || !mma_dual_groups_tile(*gm, nlocal))) {
@@ -141,18 +142,17 @@ int MMA::checkDualCovers() {
           "consecutive variables with one Jacobian value (setWeighting, or a CSR pattern recognised as such), "
           "nwblock = 1, nw + skip within the 512 variables of a tile, and no quasi-definite solver of the problem's own";
   }
-  const bool conservative = std::string(options().str("mma_globalization")) == "conservative";
   if (wantLinear() && nwcon > 0 && wantGroups()) {
     why = "the dual of the linearised subproblem (mma_dual_linearized_constraints = newton) takes no sparse "
           "constraints, grouped ones included";
   } else if (why) {
   } else if (wantLinear()) {  // P = p0, Q = q0 whatever the multipliers: equalities included
-    if (conservative)
+    if (conservative())
       why = "mma_globalization = conservative does not run on linearised constraints: a linearisation is not "
             "conservative and would need a rho of its own";
   } else if (ninequality < m) {
     why = "a dense equality constraint has a free multiplier, which can make P or Q negative";
-  } else if (options().integer("mma_use_constraint_linearization")) {
+  } else if (linearised()) {
     why = "linearised constraints have no rational dual";
   }
   if (!why) return PO_OK;
@@ -160,12 +160,23 @@ int MMA::checkDualCovers() {
   return PO_ERR_ARG;
 }
 
+// the multipliers and the counters a finished dual solve leaves behind
+void MMA::finishDualSolve(const MmaDualResult &res, const std::vector<double> &lambda) {
+  z = lambda;
+  subproblem_iter += res.evaluations;
+  dual.solves++;
+  dual.iterations += res.iterations;
+  dual.evaluations += res.evaluations;
+  dual.last_status = res.status;
+  dual.last_pg = res.pg;
+}
+
 // rho != nullptr: the subproblem in the conservative approximations f~_i + rho_i d around xvec; point_sums[m + 2] then
 // receives {Delta_0..m, D} of the solution (mma_gcmma.hpp).  Grouped sparse constraints are affine in the grouped form,
 // so their approximation is exact: they carry no rho and take no part in the acceptance test
 int MMA::solveDual(const double *rho, double *point_sums) {
   Options &o = options();
-  const int form = m <= kMmaDualFused ? 1 : 2;
+  const int form = dualForm();
   std::vector<double> gamma(m, o.real("penalty_gamma")), lambda(z);
   MmaDualResult res;
   const MmaDualRho r{xvec->d, rho};
@@ -175,9 +186,7 @@ int MMA::solveDual(const double *rho, double *point_sums) {
       MmaGroupStats st;
       PO_TRY(k_mma_dual_groups(ctx, sub, grp, lam, W, g, want_h ? H : nullptr, G.data(), linv->d, uinv->d, zwvec->d,
                                Uw.data(), swvec->d, nullptr, nullptr, &st, rho ? &r : nullptr));
-      over.max_inner = std::max(over.max_inner, st.max_inner);
-      over.cap_hits += st.cap_hits;
-      over.max_psi = std::max(over.max_psi, st.max_psi);
+      over.absorb(st);
       return PO_OK;
     }
     return k_mma_dual(ctx, sub, lam, want_h ? form : 0, W, g, H, G.empty() ? nullptr : G.data(), linv->d,
@@ -189,18 +198,10 @@ int MMA::solveDual(const double *rho, double *point_sums) {
     PO_TRY(k_mma_group_solve(ctx, sub, grp, lambda.data(), uinv->d, zwvec->d, zlvec->d, zuvec->d, &groups,
                              rho ? &r : nullptr));
     if (rho) PO_TRY(k_mma_gcmma_group_sums(ctx, sub, xvec->d, uinv->d, point_sums));
-    groups.max_inner = std::max(groups.max_inner, over.max_inner);
-    groups.cap_hits += over.cap_hits;
-    groups.max_psi = std::max(groups.max_psi, over.max_psi);
+    groups.absorb(over);
   } else if (rho) PO_TRY(k_mma_gcmma_point(ctx, sub, r, lambda.data(), uinv->d, zlvec->d, zuvec->d, point_sums));
   else PO_TRY(k_mma_dual_point(ctx, sub, lambda.data(), uinv->d, zlvec->d, zuvec->d));
-  z = lambda;
-  subproblem_iter += res.evaluations;
-  dual.solves++;
-  dual.iterations += res.iterations;
-  dual.evaluations += res.evaluations;
-  dual.last_status = res.status;
-  dual.last_pg = res.pg;
+  finishDualSolve(res, lambda);
   return PO_OK;
 }
 
@@ -209,7 +210,7 @@ int MMA::solveDual(const double *rho, double *point_sums) {
 // left in uinv.
 int MMA::solveDualLinear() {
   Options &o = options();
-  const int form = m <= kMmaDualFused ? 1 : 2;
+  const int form = dualForm();
   const double gamma = o.real("penalty_gamma");
   std::vector<double> lower(m, 0.0), upper(m, gamma), lambda(z);
   for (int i = ninequality; i < m; i++) lower[i] = -gamma;
@@ -225,13 +226,7 @@ int MMA::solveDualLinear() {
   PO_TRY(mma_dual_solve(m, lower.data(), upper.data(), o.real("mma_dual_tol"), o.integer("mma_dual_max_iterations"),
                         eval, lambda.data(), &res));
   PO_TRY(k_mma_dual_linear_point(ctx, lin, lambda.data(), start, uinv->d, zlvec->d, zuvec->d, &linear));
-  z = lambda;
-  subproblem_iter += res.evaluations;
-  dual.solves++;
-  dual.iterations += res.iterations;
-  dual.evaluations += res.evaluations;
-  dual.last_status = res.status;
-  dual.last_pg = res.pg;
+  finishDualSolve(res, lambda);
   return PO_OK;
 }
 
@@ -412,8 +407,7 @@ int MMA::solveSubproblem(Vec **xnew) {
 
 int MMA::optimize() {  // :318-379
   const bool want_dual = wantDual();
-  const bool conservative = std::string(options().str("mma_globalization")) == "conservative";
-  if (conservative && !want_dual) {  // (an inner raise would rewrite the interior point's 2 m + 2 coefficient vectors)
+  if (conservative() && !want_dual) {  // (an inner raise would rewrite the interior point's 2 m + 2 coefficient vectors)
     set_error("MMA: mma_globalization = conservative requires mma_subproblem_solver = dual");
     return PO_ERR_ARG;
   }
@@ -424,12 +418,12 @@ int MMA::optimize() {  // :318-379
     set_error("MMA: mma_subproblem_solver cannot change once the solver's vectors exist");
     return PO_ERR_ARG;
   }
-  mode = !use_dual ? Mode::INTERIOR_POINT : conservative ? Mode::DUAL_CONSERVATIVE : Mode::DUAL;
+  mode = !use_dual ? Mode::INTERIOR_POINT : conservative() ? Mode::DUAL_CONSERVATIVE : Mode::DUAL;
   Options &o = options();
   const int max_it = o.integer("mma_max_iterations");
   const double infeas_tol = o.real("mma_infeas_tol"), l1_tol = o.real("mma_l1_tol"),
                linfty_tol = o.real("mma_linfty_tol");
-  use_true_mma = o.integer("mma_use_constraint_linearization") ? 0 : 1;
+  use_true_mma = linearised() ? 0 : 1;
   if (mode == Mode::INTERIOR_POINT) {  // the subproblem hands the interior point its diagonal Hessian (.cpp:344-346)
     PO_TRY(o.set("use_diag_hessian", 1));
     PO_TRY(o.set("use_line_search", 0));

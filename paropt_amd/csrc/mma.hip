@@ -595,17 +595,40 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-static int dual_tables(const MmaDualData &s, const double *lambda, PtrTable *pt, PtrTable *qt, CoefTable *ct) {
-  if (s.m < 0 || s.m > kMmaDualMax) {
-    set_error("MMA dual: %d constraints outside 0..%d", s.m, kMmaDualMax);
+// ---- host scaffolding of the dual passes --------------------------------------------------------------------------
+static int check_m(int m, const char *who = "MMA dual") {
+  if (m < 0 || m > kMmaDualMax) {
+    set_error("%s: %d constraints outside 0..%d", who, m, kMmaDualMax);
     return PO_ERR_ARG;
   }
-  for (int i = 0; i < kMaxPanel; i++) {
-    pt->p[i] = i < s.m ? s.p[i] : nullptr;
-    qt->p[i] = i < s.m ? s.q[i] : nullptr;
-    ct->a[i] = i < s.m ? lambda[i] : 0.0;
-  }
   return PO_OK;
+}
+// the first m entries from cols / values, null or 0.0 past them (Table: PtrTable or PtrTableW)
+template <class Table, class P>
+static Table ptr_table(P *const *cols, int m) {
+  Table t;
+  for (int i = 0; i < kMaxPanel; i++) t.p[i] = i < m ? cols[i] : nullptr;
+  return t;
+}
+static CoefTable coef_table(const double *values, int m) {
+  CoefTable t;
+  for (int i = 0; i < kMaxPanel; i++) t.a[i] = i < m ? values[i] : 0.0;
+  return t;
+}
+struct DualTables {  // of a rational subproblem at lambda
+  PtrTable pt, qt;
+  CoefTable ct;
+};
+static int dual_tables(const MmaDualData &s, const double *lambda, DualTables *t) {
+  PO_TRY(check_m(s.m));
+  *t = DualTables{ptr_table<PtrTable>(s.p, s.m), ptr_table<PtrTable>(s.q, s.m), coef_table(lambda, s.m)};
+  return PO_OK;
+}
+// sigma = rho_0 + lambda . rho (the table of rho_1..m is coef_table(r.rho + 1, m))
+static double rho_sigma(const MmaDualRho &r, int m, const double *lambda) {
+  double sigma = r.rho[0];
+  for (int i = 0; i < m; i++) sigma += lambda[i] * r.rho[1 + i];
+  return sigma;
 }
 
 // m -> the compile-time column capacity MC that covers it; f(std::integral_constant<int, MC>) launches
@@ -619,137 +642,170 @@ static int with_capacity(int m, F &&f) {
   if (m <= 16) return f(Const<16>{});
   if (m <= 32) return f(Const<32>{});
   if (m <= 64) return f(Const<64>{});
-  return f(Const<96>{});
+  return f(Const<kMaxPanel>{});
 }
-// sigma = rho_0 + lambda . rho and the table of rho_1..m
-static double rho_tables(const MmaDualRho &r, int m, const double *lambda, CoefTable *rt) {
-  double sigma = r.rho[0];
-  for (int i = 0; i < kMaxPanel; i++) rt->a[i] = i < m ? r.rho[1 + i] : 0.0;
-  for (int i = 0; i < m; i++) sigma += lambda[i] * r.rho[1 + i];
-  return sigma;
+// the widest result of a reducing pass: the value, kMaxPanel columns or kMmaDualFused with their Hessian sums, and two
+// slots behind them (D or the cap hits, the most steps)
+constexpr int kFusedSums = kMmaDualFused * (kMmaDualFused + 1) / 2;
+constexpr int kPassSlots = 1 + kMaxPanel + kFusedSums + 2;
+struct PassShape {
+  int mc = 0, ns = 0;  // the capacity that ran and its sum slots
+};
+// One reducing pass over n at the panel grid: slots(MC) sum slots and nmax maxima per workgroup, launch(MC, grid)
+// writes them to c->d_partials, out[slots + nmax] receives them reduced; collective.
+template <class Slots, class Launch>
+static int reducing_pass(Ctx *c, int m, int64_t n, int nmax, Slots &&slots, Launch &&launch, double *out,
+                         PassShape *shape) {
+  const int grid = grid_for(c, n, kBpcPanel);
+  PO_TRY(with_capacity(m, [&](auto MC) -> int {
+    shape->mc = decltype(MC)::value;
+    shape->ns = slots(MC);
+    PO_TRY(ensure_partials(c, (size_t)grid * (shape->ns + nmax)));
+    return launch(MC, grid);
+  }));
+  return reduce_finish(c, grid, shape->ns, 0, nmax, out, true);
+}
+
+// The forms of an evaluation (mma.hpp): 0 value and gradient, 1 the Hessian sums in the pass, 2 the panel form.
+static int check_form(int *form, int m, const double *H) {
+  if (*form < 0 || *form > 2 || (*form == 1 && m > kMmaDualFused)) {
+    set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
+    return PO_ERR_ARG;
+  }
+  if (*form != 0 && !H) *form = 0;
+  return PO_OK;
+}
+// f(MC, MODE) with MODE = form at compile time, for the pairs that exist (check_form refused form 1 past kMmaDualFused)
+template <class MC, class F>
+static int with_form(int form, MC mc, F &&f) {
+  auto guarded = [&](auto MODE) -> int {
+    if constexpr (decltype(MODE)::value != 1 || MC::value <= kMmaDualFused) return f(mc, MODE);
+    return PO_OK;
+  };
+  return form == 1 ? guarded(Const<1>{}) : form == 2 ? guarded(Const<2>{}) : guarded(Const<0>{});
+}
+// H from the pass: the fused sums behind the mc columns, or the weighted Gram of the panel form's columns
+static int form_hessian(Ctx *c, int form, const double *sums, int mc, const double *dvec, const double *const *cols,
+                        int m, int64_t n, double *H) {
+  if (form == 1) {
+    for (int k = 0; k < m; k++)
+      for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
+  } else if (form == 2 && m > 0) {
+    PO_TRY(k_wgram(c, dvec, cols, m, n, H));
+  }
+  return PO_OK;
+}
+
+// the rho form's last slot d: the value gains sigma d, column i gains rho_i d (exact zeros where rho = 0)
+static void apply_rho(double *sums, int ns, double sigma, const double *rho, int m, double *D) {
+  const double d = sums[ns - 1];
+  sums[0] += sigma * d;
+  for (int i = 0; i < m; i++) sums[1 + i] += rho[1 + i] * d;
+  if (D) *D = d;
+}
+// W = w + lambda . b and grad = sums_1..m + b of the rational dual
+static void dual_value_grad(double w, const double *sums, const double *lambda, const double *b, int m, double *W,
+                            double *grad) {
+  for (int i = 0; i < m; i++) {
+    w += lambda[i] * b[i];
+    grad[i] = sums[1 + i] + b[i];
+  }
+  *W = w;
+}
+// {Delta_0..m, D}: the first m + 1 slots and the last one
+static void copy_point_sums(const double *all, int ns, int m, double *sums) {
+  for (int i = 0; i <= m; i++) sums[i] = all[i];
+  sums[m + 1] = all[ns - 1];
 }
 
 int k_mma_dual(Ctx *c, const MmaDualData &s, const double *lambda, int form, double *W, double *grad, double *H,
                double *const *G, double *dvec, const MmaDualRho *r, double *D) {
   const int m = s.m;
-  PtrTable pt, qt;
-  CoefTable ct, rt;
-  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
-  if (form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
-    return PO_ERR_ARG;
-  }
-  if (form != 0 && !H) form = 0;
+  DualTables t;
+  PO_TRY(dual_tables(s, lambda, &t));
+  PO_TRY(check_form(&form, m, H));
   if (form == 2 && (!G || !dvec)) {
     set_error("MMA dual: the panel form needs its %d column vectors and the weight vector", m);
     return PO_ERR_ARG;
   }
-  PtrTableW gt;
-  for (int i = 0; i < kMaxPanel; i++) gt.p[i] = (form == 2 && i < m) ? G[i] : nullptr;
-  const double sigma = r ? rho_tables(*r, m, lambda, &rt) : 0.0;
+  const PtrTableW gt = ptr_table<PtrTableW>(G, form == 2 ? m : 0);
+  const CoefTable rt = r ? coef_table(r->rho + 1, m) : CoefTable();
+  const double sigma = r ? rho_sigma(*r, m, lambda) : 0.0;
   count_bytes(c, 2 * m + 6 + (r ? 1 : 0) + (form == 2 ? m + 1 : 0), s.n);
   // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
-  const int grid = grid_for(c, s.n, kBpcPanel);
-  int mc = 0, ns = 0;
-  auto launch = [&](auto MC, auto MODE) -> int {
-    constexpr int kMC = decltype(MC)::value, kMode = decltype(MODE)::value;
-    if constexpr (kMode != 1 || kMC <= kMmaDualFused) {  // (form 1 past kMmaDualFused was refused above)
-      mc = kMC;
-      ns = r ? DualSlots<kMC, kMode, true>::NS : DualSlots<kMC, kMode, false>::NS;
-      PO_TRY(ensure_partials(c, (size_t)grid * ns));
-      if (r) {
-        PO_MLAUNCH((mma_dual_rho_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, pt, qt, ct,
-                   rt, sigma, m, s.n, gt, dvec, c->d_partials);
-      } else {
-        PO_MLAUNCH((mma_dual_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct, m, s.n, gt,
-                   dvec, c->d_partials);
-      }
-    }
-    return PO_OK;
+  const auto slots = [&](auto MC) {
+    return with_form(form, MC, [&](auto MC_, auto MODE) -> int {
+      constexpr int kMC = decltype(MC_)::value, kMode = decltype(MODE)::value;
+      return r ? DualSlots<kMC, kMode, true>::NS : DualSlots<kMC, kMode, false>::NS;
+    });
   };
-  PO_TRY(with_capacity(m, [&](auto MC) {
-    return form == 1 ? launch(MC, Const<1>{}) : form == 2 ? launch(MC, Const<2>{}) : launch(MC, Const<0>{});
-  }));
-  double sums[1 + 96 + 36 + 1];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
-  double w = sums[0];
-  if (r) {  // (exact zeros where rho = 0)
-    const double d = sums[ns - 1];
-    w += sigma * d;
-    for (int i = 0; i < m; i++) sums[1 + i] += r->rho[1 + i] * d;
-    if (D) *D = d;
-  }
-  for (int i = 0; i < m; i++) {
-    w += lambda[i] * s.b[i];
-    grad[i] = sums[1 + i] + s.b[i];
-  }
-  *W = w;
-  if (form == 1) {
-    for (int k = 0; k < m; k++)
-      for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
-  } else if (form == 2 && m > 0) {
-    PO_TRY(k_wgram(c, dvec, G, m, s.n, H));
-  }
-  return PO_OK;
+  const auto launch = [&](auto MC, int grid) {
+    return with_form(form, MC, [&](auto MC_, auto MODE) -> int {
+      constexpr int kMC = decltype(MC_)::value, kMode = decltype(MODE)::value;
+      if (r) {
+        PO_MLAUNCH((mma_dual_rho_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, t.pt, t.qt,
+                   t.ct, rt, sigma, m, s.n, gt, dvec, c->d_partials);
+      } else {
+        PO_MLAUNCH((mma_dual_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, t.pt, t.qt, t.ct, m, s.n,
+                   gt, dvec, c->d_partials);
+      }
+      return PO_OK;
+    });
+  };
+  double sums[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(c, m, s.n, 0, slots, launch, sums, &sh));
+  if (r) apply_rho(sums, sh.ns, sigma, r->rho, m, D);
+  dual_value_grad(sums[0], sums, lambda, s.b, m, W, grad);
+  return form_hessian(c, form, sums, sh.mc, dvec, G, m, s.n, H);
 }
 
 int k_mma_gcmma_point(Ctx *c, const MmaDualData &s, const MmaDualRho &r, const double *lambda, double *x, double *zl,
                       double *zu, double *sums) {
   const int m = s.m;
-  PtrTable pt, qt;
-  CoefTable ct, rt;
-  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
-  const double sigma = rho_tables(r, m, lambda, &rt);  // (the point pass takes no table of rho)
+  DualTables t;
+  PO_TRY(dual_tables(s, lambda, &t));
+  const double sigma = rho_sigma(r, m, lambda);  // (the point pass takes no table of rho)
   count_bytes(c, 2 * m + 7 + 3, s.n);
-  const int grid = grid_for(c, s.n, kBpcPanel);
-  int ns = 0;
-  PO_TRY(with_capacity(m, [&](auto MC) -> int {
-    constexpr int kMC = decltype(MC)::value;
-    ns = DualSlots<kMC, 3, true>::NS;
-    PO_TRY(ensure_partials(c, (size_t)grid * ns));
-    PO_MLAUNCH((mma_gcmma_point_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r.xk, pt, qt, ct, sigma, m,
-               s.n, x, zl, zu, c->d_partials);
-    return PO_OK;
-  }));
-  double all[96 + 2];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
-  for (int i = 0; i <= m; i++) sums[i] = all[i];
-  sums[m + 1] = all[ns - 1];
+  double all[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(
+      c, m, s.n, 0, [](auto MC) { return DualSlots<decltype(MC)::value, 3, true>::NS; },
+      [&](auto MC, int grid) -> int {
+        PO_MLAUNCH((mma_gcmma_point_kernel<decltype(MC)::value>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r.xk,
+                   t.pt, t.qt, t.ct, sigma, m, s.n, x, zl, zu, c->d_partials);
+        return PO_OK;
+      },
+      all, &sh));
+  copy_point_sums(all, sh.ns, m, sums);
   return PO_OK;
 }
 
 int k_mma_gcmma_rho_sums(Ctx *c, const double *L, const double *U, const double *g, const double *const *A, int m,
                          int64_t n, double *sums) {
-  if (m < 0 || m > kMmaDualMax) {
-    set_error("MMA: %d constraints outside 0..%d", m, kMmaDualMax);
-    return PO_ERR_ARG;
-  }
-  PtrTable at;
-  for (int i = 0; i < kMaxPanel; i++) at.p[i] = i < m ? A[i] : nullptr;
+  PO_TRY(check_m(m, "MMA"));
+  const PtrTable at = ptr_table<PtrTable>(A, m);
   count_bytes(c, m + 3, n);
-  const int grid = grid_for(c, n, kBpcPanel);
-  int ns = 0;
-  PO_TRY(with_capacity(m, [&](auto MC) -> int {
-    constexpr int kMC = decltype(MC)::value;
-    ns = 1 + kMC;  // (the kernel's own NS)
-    PO_TRY(ensure_partials(c, (size_t)grid * ns));
-    PO_MLAUNCH((mma_gcmma_rho_start_kernel<kMC>), grid, L, U, g, at, m, n, c->d_partials);
-    return PO_OK;
-  }));
-  double all[96 + 1];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
+  double all[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(
+      c, m, n, 0, [](auto MC) { return 1 + decltype(MC)::value; },  // (the kernel's own NS)
+      [&](auto MC, int grid) -> int {
+        PO_MLAUNCH((mma_gcmma_rho_start_kernel<decltype(MC)::value>), grid, L, U, g, at, m, n, c->d_partials);
+        return PO_OK;
+      },
+      all, &sh));
   for (int i = 0; i <= m; i++) sums[i] = all[i];
   return PO_OK;
 }
 
 int k_mma_dual_point(Ctx *c, const MmaDualData &s, const double *lambda, double *x, double *zl, double *zu) {
-  PtrTable pt, qt;
-  CoefTable ct;
-  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
+  DualTables t;
+  PO_TRY(dual_tables(s, lambda, &t));
   if (s.n <= 0) return PO_OK;
   count_bytes(c, 2 * s.m + 6 + 3, s.n);
-  PO_MLAUNCH(mma_dual_point_kernel, grid_for(c, s.n, kBpcPanel), s.L, s.U, s.alpha, s.beta, s.p0, s.q0, pt, qt, ct,
-             s.m, s.n, x, zl, zu);
+  PO_MLAUNCH(mma_dual_point_kernel, grid_for(c, s.n, kBpcPanel), s.L, s.U, s.alpha, s.beta, s.p0, s.q0, t.pt, t.qt,
+             t.ct, s.m, s.n, x, zl, zu);
   return PO_OK;
 }
 
@@ -1115,10 +1171,9 @@ bool mma_dual_groups_tile(const GroupMap &m, int64_t n) {
 
 int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, const double *lambda, double *x,
                       double *zw, double *zl, double *zu, MmaGroupStats *st, const MmaDualRho *r) {
-  PtrTable pt, qt;
-  CoefTable ct, rt;
-  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
-  const double sigma = r ? rho_tables(*r, s.m, lambda, &rt) : 0.0;  // (the groups take no table of rho)
+  DualTables t;
+  PO_TRY(dual_tables(s, lambda, &t));
+  const double sigma = r ? rho_sigma(*r, s.m, lambda) : 0.0;  // (the groups take no table of rho)
   GroupMap gm = g.map;
   if (gm.nwcon <= 0) {  // no group: every variable takes the closed form
     gm = GroupMap();
@@ -1141,10 +1196,10 @@ int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
   PO_TRY(ensure_partials(c, (size_t)grid * (kGroupSums + kGroupMaxs)));
   if (r) {
     PO_MLAUNCH(mma_group_solve_kernel<true>, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta,
-               s.p0, s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, r->xk, sigma);
+               s.p0, s.q0, t.pt, t.qt, t.ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, r->xk, sigma);
   } else {
     PO_MLAUNCH(mma_group_solve_kernel<false>, grid, gm, g.a, g.c, g.nwinequality, g.gamma, s.L, s.U, s.alpha, s.beta,
-               s.p0, s.q0, pt, qt, ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, nullptr, 0.0);
+               s.p0, s.q0, t.pt, t.qt, t.ct, s.m, s.n, G, ntiles, x, zw, zl, zu, c->d_partials, nullptr, 0.0);
   }
   double out[kGroupSums + kGroupMaxs];
   PO_TRY(reduce_finish(c, grid, kGroupSums, 0, kGroupMaxs, out, true));
@@ -1163,24 +1218,20 @@ int k_mma_group_solve(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
 
 int k_mma_gcmma_group_sums(Ctx *c, const MmaDualData &s, const double *xk, const double *x, double *sums) {
   const int m = s.m;
-  PtrTable pt, qt;
-  CoefTable ct;
-  std::vector<double> none(m > 0 ? m : 1, 0.0);  // (the pass takes no multipliers)
-  PO_TRY(dual_tables(s, none.data(), &pt, &qt, &ct));
+  PO_TRY(check_m(m));
+  const PtrTable pt = ptr_table<PtrTable>(s.p, m), qt = ptr_table<PtrTable>(s.q, m);  // (the pass takes no multipliers)
   count_bytes(c, 2 * m + 6, s.n);
-  const int grid = grid_for(c, s.n, kBpcPanel);
-  int ns = 0;
-  PO_TRY(with_capacity(m, [&](auto MC) -> int {
-    constexpr int kMC = decltype(MC)::value;
-    ns = DualSlots<kMC, 5, true>::NS;
-    PO_TRY(ensure_partials(c, (size_t)grid * ns));
-    PO_MLAUNCH((mma_gcmma_group_sums_kernel<kMC>), grid, s.L, s.U, s.p0, s.q0, xk, x, pt, qt, m, s.n, c->d_partials);
-    return PO_OK;
-  }));
-  double all[96 + 2];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 0, all, true));
-  for (int i = 0; i <= m; i++) sums[i] = all[i];
-  sums[m + 1] = all[ns - 1];
+  double all[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(
+      c, m, s.n, 0, [](auto MC) { return DualSlots<decltype(MC)::value, 5, true>::NS; },
+      [&](auto MC, int grid) -> int {
+        PO_MLAUNCH((mma_gcmma_group_sums_kernel<decltype(MC)::value>), grid, s.L, s.U, s.p0, s.q0, xk, x, pt, qt, m, s.n,
+                   c->d_partials);
+        return PO_OK;
+      },
+      all, &sh));
+  copy_point_sums(all, sh.ns, m, sums);
   return PO_OK;
 }
 
@@ -1205,47 +1256,38 @@ int k_mma_dual_groups(Ctx *c, const MmaDualData &s, const MmaDualGroups &g, cons
   MmaGroupStats local;
   if (!st) st = &local;
   PO_TRY(k_mma_group_solve(c, s, g, lambda, x, zw, zl, zu, st, r));
-  PtrTable pt, qt;
-  CoefTable ct, rt;
-  PO_TRY(dual_tables(s, lambda, &pt, &qt, &ct));
-  const double sigma = r ? rho_tables(*r, m, lambda, &rt) : 0.0;
+  DualTables t;
+  PO_TRY(dual_tables(s, lambda, &t));
   if (!dvec || (m > 0 && !G)) {
     set_error("MMA dual: the grouped evaluation needs its %d column vectors and the weight vector", m);
     return PO_ERR_ARG;
   }
-  PtrTableW gt;
-  for (int i = 0; i < kMaxPanel; i++) gt.p[i] = i < m ? G[i] : nullptr;
+  const PtrTableW gt = ptr_table<PtrTableW>(G, m);
+  const CoefTable rt = r ? coef_table(r->rho + 1, m) : CoefTable();
+  const double sigma = r ? rho_sigma(*r, m, lambda) : 0.0;
   count_bytes(c, 2 * m + 7 + (r ? 1 : 0) + m + 1, s.n);
-  const int grid = grid_for(c, s.n, kBpcPanel);
-  int ns = 0;
-  PO_TRY(with_capacity(m, [&](auto MC) -> int {
-    constexpr int kMC = decltype(MC)::value;
-    ns = r ? DualSlots<kMC, 4, true>::NS : DualSlots<kMC, 4, false>::NS;
-    PO_TRY(ensure_partials(c, (size_t)grid * ns));
-    if (r) {
-      PO_MLAUNCH((mma_dual_stored_rho_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, x, pt, qt, ct,
-                 rt, sigma, m, s.n, gt, dvec, c->d_partials);
-    } else {
-      PO_MLAUNCH((mma_dual_stored_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, x, pt, qt, ct, m, s.n, gt,
-                 dvec, c->d_partials);
-    }
-    return PO_OK;
-  }));
-  double sums[1 + 96 + 1];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 0, sums, true));
-  double w = sums[0];
-  if (r) {  // (exact zeros where rho = 0)
-    const double d = sums[ns - 1];
-    w += sigma * d;
-    for (int i = 0; i < m; i++) sums[1 + i] += r->rho[1 + i] * d;
-    if (D) *D = d;
-  }
-  w -= st->zw_psi;
-  for (int i = 0; i < m; i++) {
-    w += lambda[i] * s.b[i];
-    grad[i] = sums[1 + i] + s.b[i];
-  }
-  *W = w;
+  double sums[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(
+      c, m, s.n, 0,
+      [&](auto MC) {
+        constexpr int kMC = decltype(MC)::value;
+        return r ? DualSlots<kMC, 4, true>::NS : DualSlots<kMC, 4, false>::NS;
+      },
+      [&](auto MC, int grid) -> int {
+        constexpr int kMC = decltype(MC)::value;
+        if (r) {
+          PO_MLAUNCH((mma_dual_stored_rho_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, r->xk, x, t.pt,
+                     t.qt, t.ct, rt, sigma, m, s.n, gt, dvec, c->d_partials);
+        } else {
+          PO_MLAUNCH((mma_dual_stored_kernel<kMC>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, x, t.pt, t.qt, t.ct, m,
+                     s.n, gt, dvec, c->d_partials);
+        }
+        return PO_OK;
+      },
+      sums, &sh));
+  if (r) apply_rho(sums, sh.ns, sigma, r->rho, m, D);
+  dual_value_grad(sums[0] - st->zw_psi, sums, lambda, s.b, m, W, grad);
   if (!H || m <= 0) return PO_OK;
   PO_TRY(k_wgram(c, dvec, G, m, s.n, H));
   if (g.map.nwcon <= 0 && c->size == 1) return PO_OK;
@@ -1475,17 +1517,6 @@ __global__ void __launch_bounds__(kBlock)
     partials[(size_t)gridDim.x + blockIdx.x] = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
 }
 
-static int linear_tables(const MmaDualLinear &s, const double *lambda, PtrTable *at, CoefTable *ct) {
-  if (s.m < 0 || s.m > kMmaDualMax) {
-    set_error("MMA dual: %d constraints outside 0..%d", s.m, kMmaDualMax);
-    return PO_ERR_ARG;
-  }
-  for (int i = 0; i < kMaxPanel; i++) {
-    at->p[i] = i < s.m ? s.A[i] : nullptr;
-    ct->a[i] = i < s.m ? lambda[i] : 0.0;
-  }
-  return PO_OK;
-}
 static void linear_stats(const double *capmax, MmaLinearStats *st) {
   if (!st) return;
   st->cap_hits += (long)capmax[0];
@@ -1495,39 +1526,32 @@ static void linear_stats(const double *capmax, MmaLinearStats *st) {
 int k_mma_dual_linear(Ctx *c, const MmaDualLinear &s, const double *lambda, int form, const double *xstart, double *x,
                       double *W, double *grad, double *H, double *dvec, MmaLinearStats *st) {
   const int m = s.m;
-  PtrTable at;
-  CoefTable ct;
-  PO_TRY(linear_tables(s, lambda, &at, &ct));
-  if (form < 0 || form > 2 || (form == 1 && m > kMmaDualFused)) {
-    set_error("MMA dual: the fused form covers at most %d constraints (%d given)", kMmaDualFused, m);
-    return PO_ERR_ARG;
-  }
-  if (form != 0 && !H) form = 0;
+  PO_TRY(check_m(s.m));
+  const PtrTable at = ptr_table<PtrTable>(s.A, s.m);
+  const CoefTable ct = coef_table(lambda, s.m);
+  PO_TRY(check_form(&form, m, H));
   if (form == 2 && !dvec) {
     set_error("MMA dual: the panel form needs the weight vector");
     return PO_ERR_ARG;
   }
   count_bytes(c, m + 9 + (form == 2 ? 1 : 0), s.n);
   // (one grid for every form: the value and the gradient have the same bits whichever form computed them)
-  const int grid = grid_for(c, s.n, kBpcPanel);
-  int mc = 0, ns = 0;
-  auto launch = [&](auto MC, auto MODE) -> int {
-    constexpr int kMC = decltype(MC)::value, kMode = decltype(MODE)::value;
-    if constexpr (kMode != 1 || kMC <= kMmaDualFused) {  // (form 1 past kMmaDualFused was refused above)
-      mc = kMC;
-      ns = LinearSlots<kMC, kMode>::NS;
-      PO_TRY(ensure_partials(c, (size_t)grid * (ns + 1)));
-      PO_MLAUNCH((mma_dual_linear_kernel<kMC, kMode>), grid, s.L, s.U, s.alpha, s.beta, s.p0, s.q0, s.xk, xstart, at, ct,
-                 m, s.n, x, dvec, c->d_partials);
-    }
-    return PO_OK;
+  const auto slots = [&](auto MC) {
+    return with_form(form, MC, [](auto MC_, auto MODE) -> int {
+      return LinearSlots<decltype(MC_)::value, decltype(MODE)::value>::NS;
+    });
   };
-  PO_TRY(with_capacity(m, [&](auto MC) {
-    return form == 1 ? launch(MC, Const<1>{}) : form == 2 ? launch(MC, Const<2>{}) : launch(MC, Const<0>{});
-  }));
-  double sums[1 + 96 + 36 + 2];
-  PO_TRY(reduce_finish(c, grid, ns, 0, 1, sums, true));
-  linear_stats(sums + ns - 1, st);
+  const auto launch = [&](auto MC, int grid) {
+    return with_form(form, MC, [&](auto MC_, auto MODE) -> int {
+      PO_MLAUNCH((mma_dual_linear_kernel<decltype(MC_)::value, decltype(MODE)::value>), grid, s.L, s.U, s.alpha, s.beta,
+                 s.p0, s.q0, s.xk, xstart, at, ct, m, s.n, x, dvec, c->d_partials);
+      return PO_OK;
+    });
+  };
+  double sums[kPassSlots];
+  PassShape sh;
+  PO_TRY(reducing_pass(c, m, s.n, 1, slots, launch, sums, &sh));  // (the most steps ride as a maximum)
+  linear_stats(sums + sh.ns - 1, st);
   double w = sums[0];
   for (int i = 0; i < m; i++) {
     const double ci = s.cons[i] + sums[1 + i];
@@ -1535,20 +1559,14 @@ int k_mma_dual_linear(Ctx *c, const MmaDualLinear &s, const double *lambda, int 
     grad[i] = -ci;
   }
   *W = w;
-  if (form == 1) {
-    for (int k = 0; k < m; k++)
-      for (int i = 0; i <= k; i++) H[i + (size_t)m * k] = H[k + (size_t)m * i] = sums[1 + mc + k * (k + 1) / 2 + i];
-  } else if (form == 2 && m > 0) {
-    PO_TRY(k_wgram(c, dvec, s.A, m, s.n, H));
-  }
-  return PO_OK;
+  return form_hessian(c, form, sums, sh.mc, dvec, s.A, m, s.n, H);
 }
 
 int k_mma_dual_linear_point(Ctx *c, const MmaDualLinear &s, const double *lambda, const double *xstart, double *x,
                             double *zl, double *zu, MmaLinearStats *st) {
-  PtrTable at;
-  CoefTable ct;
-  PO_TRY(linear_tables(s, lambda, &at, &ct));
+  PO_TRY(check_m(s.m));
+  const PtrTable at = ptr_table<PtrTable>(s.A, s.m);
+  const CoefTable ct = coef_table(lambda, s.m);
   count_bytes(c, s.m + 7 + 3, s.n);
   const int grid = grid_for(c, s.n, kBpcPanel);
   PO_TRY(ensure_partials(c, (size_t)grid * 2));

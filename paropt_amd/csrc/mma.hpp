@@ -5,6 +5,7 @@
 // or one of the reductions of the interior-point path; the subproblem's objective / constraint values
 // are two mdot passes over the coefficient panels [p0 | p_i] and [q0 | q_i].
 #pragma once
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -90,6 +91,11 @@ struct MmaGroupStats {  // of one group-solve pass, over all ranks
   long steps = 0;        // evaluations of psi over all groups
   int max_inner = 0;     // most evaluations of psi one group took
   double max_psi = 0.0;  // largest |psi| over the strict groups
+  void absorb(const MmaGroupStats &o) {  // the most steps, the cap hits and the largest |psi| over both
+    max_inner = std::max(max_inner, o.max_inner);
+    cap_hits += o.cap_hits;
+    max_psi = std::max(max_psi, o.max_psi);
+  }
 };
 // the group map runs through the tiled solve: one constraint per group (nwblock = 1), period within a tile, every
 // group inside the n local variables
@@ -143,6 +149,7 @@ int k_mma_dual_linear_point(Ctx *c, const MmaDualLinear &s, const double *lambda
                             double *zl, double *zu, MmaLinearStats *st = nullptr);
 
 typedef int (*MmaIterationFn)(void *user, int iter);
+struct MmaDualResult;  // (mma_dual.hpp)
 
 struct MmaDualStats {  // mma_subproblem_solver = dual: counters over every solve; status and max |pg| of the last one
   int solves = 0, iterations = 0, evaluations = 0, last_status = 0;
@@ -212,9 +219,14 @@ class MMA : public Problem {
   // how a subproblem is solved: optimize() decides it from mma_subproblem_solver and mma_globalization.  The dual
   // modes (mma_dual.hpp, mma_gcmma.hpp) run without an InteriorPoint object
   enum class Mode { INTERIOR_POINT, DUAL, DUAL_CONSERVATIVE };
+  bool optionIs(const char *name, const char *value);
   bool wantDual();
   bool wantGroups();
+  bool wantGcmmaGroups();
+  bool conservative();
+  bool linearised();
   bool wantLinear();
+  int dualForm() const { return m <= kMmaDualFused ? 1 : 2; }
   MmaParams params();
   int allocate();
   int initializeSubProblem(Vec *xv);
@@ -224,6 +236,7 @@ class MMA : public Problem {
   int checkDualCovers();
   int solveDual(const double *rho = nullptr, double *point_sums = nullptr);
   int solveDualLinear();
+  void finishDualSolve(const MmaDualResult &res, const std::vector<double> &lambda);
   int solveConservative();
   void flushHistory();
 

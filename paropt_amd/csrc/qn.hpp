@@ -20,6 +20,36 @@ inline bool vec_mirror_live(const Vec *v) { return v && v->h_live && v->h && v->
 int vec_mirror_upload(Vec *v);
 int vec_mirror_refresh(Vec *v);
 void live_objects(long *vecs, long long *bytes);
+// The work vectors of one call: allocated in order, released together.  release() hands the call's return code on; it
+// waits for the stream first if it holds any vector, since a pass of the call may still be using them.
+struct WorkVecs {
+  Ctx *ctx;
+  std::vector<Vec *> v;
+  explicit WorkVecs(Ctx *c) : ctx(c) {}
+  WorkVecs(const WorkVecs &) = delete;
+  WorkVecs &operator=(const WorkVecs &) = delete;
+  ~WorkVecs() { release(PO_OK); }
+  int add(int k, int64_t n) {  // k more vectors of n elements
+    for (int i = 0; i < k; i++) {
+      Vec *w = vec_new(ctx, n);
+      if (!w) return PO_ERR_HIP;
+      v.push_back(w);
+    }
+    return PO_OK;
+  }
+  double *d(int i) const { return v[i]->d; }
+  std::vector<double *> pointers(int first, int k) const {  // the device pointers of vectors first .. first + k - 1
+    std::vector<double *> out;
+    for (int i = 0; i < k; i++) out.push_back(v[first + i]->d);
+    return out;
+  }
+  int release(int rc) {
+    if (!v.empty() && hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PO_OK) rc = PO_ERR_HIP;
+    for (Vec *w : v) vec_decref(w);
+    v.clear();
+    return rc;
+  }
+};
 void mirror_created();
 void mirror_freed();
 long live_mirrors();

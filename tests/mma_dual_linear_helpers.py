@@ -9,22 +9,10 @@ With t = sum_i lambda_i A_i the element-wise minimiser of the Lagrangian is the 
 p0 u^2 - q0 l^2 = t (u = 1 / (U - x), l = 1 / (x - L)) clamped into [alpha, beta]; it is found here by bisection down
 to a bracket that no longer moves.  W = sum (p0 u + q0 l) - lambda . c(x), dW/dlambda = -c(x), -hess W = sum over the
 free elements (root strictly inside (alpha, beta)) of A_i A_k / h, h = 2 (p0 u^3 + q0 l^3)."""
-import math
-
 import numpy as np
 
 LINEAR_GOLDENS = ("mma_convex_n200_c2_linearized", "mma_quadratic_n200_c2", "mma_convex_n300_c3")
 PENALTY_GAMMA = 1000.0  # the registry's default of penalty_gamma
-
-
-def accurate_sum(terms):
-    """Sums with an error far below the double-precision bound of the checks: x87 extended precision (64-bit
-    mantissa, pairwise) where numpy has it, math.fsum otherwise."""
-    if np.finfo(np.longdouble).eps < 1e-18:
-        return np.sum(terms, axis=-1, dtype=np.longdouble).astype(np.float64)
-    t = np.atleast_2d(terms)
-    out = np.array([math.fsum(row) for row in t])
-    return out if np.ndim(terms) > 1 else out[0]
 
 
 class LinearSubproblem:

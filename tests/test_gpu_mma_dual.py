@@ -4,11 +4,11 @@ GPU: the dual sub-solver of the method of moving asymptotes (mma_subproblem_solv
   1. the kernels (po_mma_dual_eval) against numpy sums in extended precision, both forms, every size class;
   2. optimality of the solved subproblems, checked in numpy on the downloaded data;
   3. whole runs against the unchanged interior-point path, measured by that path's own sensitivity to its tolerance;
-  4. the interfaces: the ParOpt.Optimizer facade, the refused configurations, the registry, leaks, two ranks.
+  4. the interfaces: the ParOpt.Optimizer facade, the refused configurations, the registry, leaks, two ranks;
+  5. launches and host syncs of six iterations on the four paths of the sub-solver, against the integers on record.
 """
 import json
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -17,6 +17,7 @@ from conftest import load_golden
 from mma_dual_helpers import (DUAL_GOLDENS, PENALTY_GAMMA, Subproblem, dual_eval, dual_point, primal_point,
                               projected_gradient)
 from mma_helpers import mma_options_from_case
+from mma_test_util import accurate_sum, run_two_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -56,18 +57,6 @@ def draw_subproblem(n, m, seed):
     if m == 1:
         lam[0] = 0.7
     return Subproblem(L, U, alpha, beta, p0, q0, p, q, b), lam
-
-
-def accurate_sum(terms):
-    """Sums with an error far below the double-precision bound of the checks: x87 extended precision (64-bit
-    mantissa, pairwise) where numpy has it, math.fsum otherwise."""
-    if np.finfo(np.longdouble).eps < 1e-18:
-        return np.sum(terms, axis=-1, dtype=np.longdouble).astype(np.float64)
-    import math
-
-    t = np.atleast_2d(terms)
-    out = np.array([math.fsum(row) for row in t])
-    return out if np.ndim(terms) > 1 else out[0]
 
 
 _UPLOADS = {}
@@ -348,14 +337,6 @@ def test_no_vectors_leak_and_no_interior_point_is_allocated(ctx):
     assert pa.live_objects()[0] == start
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _dual_rows(ctx, case, lams):
     import paropt_amd as pa
 
@@ -394,21 +375,10 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_one_gpu_match_single_rank(ctx):
-    import torch.multiprocessing as mp
-
     _, case = load_golden("mma_quadratic_n200_c2")
     lams1 = []
     rows1, stats1 = _dual_rows(ctx, case, lams1)
-    mpctx = mp.get_context("spawn")
-    q = mpctx.Queue()
-    port = _free_port()
-    procs = [mpctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    rows2, stats2, both = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    rows2, stats2, both = run_two_ranks(_worker)
     assert both[0] == both[1], "the multipliers differ between the ranks"
     assert len(rows2) == len(rows1)
     for (s2, r2), (s1, r1) in zip(rows2, rows1):
@@ -417,3 +387,38 @@ def test_two_ranks_one_gpu_match_single_rank(ctx):
             assert abs(a - b) <= 1e-9 * max(1.0, abs(b)), (r2, r1)
     assert {k: stats2[k] for k in ("solves", "iterations", "evaluations", "last_status")} == \
         {k: stats1[k] for k in ("solves", "iterations", "evaluations", "last_status")}
+
+
+# ---- 5. launches and host syncs on record ---------------------------------------------------------------------------
+# Six MMA iterations at n = 513 on the paths of the dual sub-solver: the plain dual at a fused and at a panel width,
+# grouped sparse constraints (128 groups of nw = 4) and linearised constraints.  The integers are what the library
+# printed before the host code of the dual passes was folded into one pass driver (profiles/README.md, round 25): a
+# refactor of that code leaves them as they are.
+_DUAL = {"mma_subproblem_solver": "dual"}
+MMA_ON_RECORD = {
+    "plain_c3": dict(c=3, opts=_DUAL, weighting=None, launches=297, syncs=109),
+    "plain_c9": dict(c=9, opts=_DUAL, weighting=None, launches=507, syncs=214),
+    "grouped_nw4": dict(c=3, opts=dict(_DUAL, mma_dual_sparse_constraints="groups"), weighting=(128, 4, 0, 0),
+                        launches=623, syncs=204),
+    "linearised_c9": dict(c=9, opts=dict(_DUAL, mma_use_constraint_linearization=1,
+                                         mma_dual_linearized_constraints="newton"), weighting=None,
+                          launches=403, syncs=165),
+}
+
+
+@pytest.mark.parametrize("name", sorted(MMA_ON_RECORD))
+def test_launches_and_syncs_of_the_mma_dual_paths_on_record(ctx, name):
+    import paropt_amd as pa
+
+    rec = MMA_ON_RECORD[name]
+    prob = pa.SeparableProblem(ctx, "convex", 513, rec["c"])
+    if rec["weighting"]:
+        prob.setWeighting(*rec["weighting"])
+    mma = pa.MMA(prob, dict(rec["opts"], mma_max_iterations=6))
+    syncs0, launches0 = ctx.counters()
+    mma.optimize()
+    syncs1, launches1 = ctx.counters()
+    counts = (launches1 - launches0, syncs1 - syncs0)
+    print(name, "launches, syncs:", counts)
+    assert mma.getState()["mma_iter"] == 7 and mma.getDualStats()["solves"] == 6  # (the stop test never fires)
+    assert counts == (rec["launches"], rec["syncs"])

@@ -11,7 +11,6 @@ GPU: grouped ("weighting") sparse constraints kept in the dual sub-solver of the
 import gc
 import json
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ from mma_dual_group_helpers import (WEIGHTING_GOLDEN, Groups, bound_multipliers,
                                     group_solve)
 from mma_dual_helpers import PENALTY_GAMMA, Subproblem, projected_gradient
 from mma_helpers import mma_options_from_case, parse_mma_table
+from mma_test_util import run_two_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -537,14 +537,6 @@ def test_no_vectors_leak_and_no_interior_point_is_allocated(ctx):
     assert pa.live_objects()[0] == start
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _group_rows(ctx, case, lams):
     import paropt_amd as pa
 
@@ -583,21 +575,10 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_one_gpu_match_single_rank(ctx):
-    import torch.multiprocessing as mp
-
     _, case = load_golden(WEIGHTING_GOLDEN)
     lams1 = []
     rows1, stats1, gstats1 = _group_rows(ctx, case, lams1)
-    mpctx = mp.get_context("spawn")
-    q = mpctx.Queue()
-    port = _free_port()
-    procs = [mpctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    rows2, stats2, gstats2, both = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    rows2, stats2, gstats2, both = run_two_ranks(_worker)
     assert both[0] == both[1], "the multipliers differ between the ranks"
     assert len(rows2) == len(rows1)
     for (s2, r2), (s1, r1) in zip(rows2, rows1):

@@ -16,10 +16,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from mma_dual_linear_helpers import (PENALTY_GAMMA, LinearSubproblem, accurate_sum, bound_multipliers,
-                                     projected_gradient, residual_bound, residual_longdouble)
+from mma_dual_linear_helpers import (PENALTY_GAMMA, LinearSubproblem, bound_multipliers, projected_gradient,
+                                     residual_bound, residual_longdouble)
 from mma_helpers import mma_options_from_case, parse_mma_table
-from test_gpu_mma_dual import _free_port, draw_subproblem, make_problem
+from mma_test_util import accurate_sum, run_two_ranks
+from test_gpu_mma_dual import draw_subproblem, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -486,22 +487,11 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_one_gpu_match_single_rank(ctx):
-    import torch.multiprocessing as mp
-
     _, case = load_golden(GOLDEN)
     lams1 = []
     rows1, stats1, lstats1 = _linear_rows(ctx, case, lams1)
     assert len(rows1) == 11 and stats1["last_status"] == 0
-    mpctx = mp.get_context("spawn")
-    q = mpctx.Queue()
-    port = _free_port()
-    procs = [mpctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    rows2, stats2, lstats2, both = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    rows2, stats2, lstats2, both = run_two_ranks(_worker)
     assert both[0] == both[1], "the multipliers differ between the ranks"
     assert len(rows2) == len(rows1)
     for r2, r1 in zip(rows2, rows1):  # the table rows (another summation order over the shards: not the same bits)

@@ -19,7 +19,8 @@ from conftest import load_golden
 from mma_dual_helpers import Subproblem
 from mma_gcmma_helpers import (GCMMA_DEFAULTS, dfun, dprime, fvals, oracle_gcmma, point_rho, primal_point_rho)
 from mma_helpers import mma_options_from_case
-from test_gpu_mma_dual import _free_port, accurate_sum, draw_subproblem, make_problem
+from mma_test_util import accurate_sum, run_two_ranks
+from test_gpu_mma_dual import draw_subproblem, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -427,19 +428,8 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_one_gpu_match_single_rank(ctx):
-    import torch.multiprocessing as mp
-
     one = _counts(ctx)
-    mpctx = mp.get_context("spawn")
-    q = mpctx.Queue()
-    port = _free_port()
-    procs = [mpctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    both = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    both = run_two_ranks(_worker)
     assert both[0] == both[1], "the ranks took different decisions"
     two = both[0]
     print("one rank :", one)

@@ -23,8 +23,9 @@ from mma_dual_helpers import Subproblem
 from mma_gcmma_group_helpers import form_pq_rho, group_solve_rho, oracle_gcmma_groups, quadratic_case
 from mma_gcmma_helpers import GCMMA_DEFAULTS, dfun, dprime, fvals
 from mma_helpers import mma_options_from_case
-from test_gpu_mma_dual_groups import (ALL_KINDS, EQ_KINDS, GAMMA, GROUPS_ON, INEQ_KINDS, SHAPES, _free_port,
-                                      accurate_sum, draw, found_kinds, golden_groups, make_problem)
+from mma_test_util import run_two_ranks
+from test_gpu_mma_dual_groups import (ALL_KINDS, EQ_KINDS, GAMMA, GROUPS_ON, INEQ_KINDS, SHAPES, accurate_sum, draw,
+                                      found_kinds, golden_groups, make_problem)
 
 pytestmark = pytest.mark.gpu
 
@@ -551,19 +552,8 @@ def _worker(rank, world, port, q):
 
 
 def test_two_ranks_one_gpu_match_single_rank(ctx):
-    import torch.multiprocessing as mp
-
     one = _counts(ctx)
-    mpctx = mp.get_context("spawn")
-    q = mpctx.Queue()
-    port = _free_port()
-    procs = [mpctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    both = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    both = run_two_ranks(_worker)
     assert both[0] == both[1], "the ranks took different decisions"
     two = both[0]
     assert one["inner"][1:] == LOCKSTEP_RAISES

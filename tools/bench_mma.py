@@ -32,6 +32,9 @@ the dual of the linearised subproblem (mma_dual_linearized_constraints = newton)
 (po_bench_mma_dual_linear: root searches started warm, from the point of the call before, and cold, from the expansion
 point) and the rational pass (po_bench_mma_dual) alternate at the same (n, m): ms, GB/s over the algorithmic m + 9
 (m + 10 in the panel form) streams and the fraction of 8 TB/s.  Appended to profiles/r16_bench_mma_linear.jsonl.
+
+--dual-only: the whole runs that alternate with the interior-point sub-solver (the default, --nw, --linearized) leave it
+out: what a comparison of two builds of the dual's host code needs, at a hundredth of the time.
 """
 import argparse
 import json
@@ -99,12 +102,12 @@ def linear_pass_lines(pa, ctx, n, c, reps, rounds):
     return lines
 
 
-def group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps):
+def group_lines(pa, ctx, n, c, nwcon, nw, iters, rounds, reps, solvers):
     """Whole runs (interior point / grouped dual, alternating), then the two evaluations on the last subproblem."""
     lines = []
     mma = None
     for rnd in range(rounds):
-        for solver in ("interior_point", "dual"):
+        for solver in solvers:
             mma = None  # (one solver's vectors at a time)
             prob = pa.SeparableProblem(ctx, "convex", n, c, 0).setWeighting(nwcon, nw, 0, 0)
             mma = pa.MMA(prob, {"mma_subproblem_solver": solver, "mma_dual_sparse_constraints": "groups",
@@ -288,7 +291,9 @@ def main():
     ap.add_argument("--nw", type=int, default=0)
     ap.add_argument("--nwcon", type=int, default=0)
     ap.add_argument("--linearized", action="store_true")
+    ap.add_argument("--dual-only", action="store_true")
     a = ap.parse_args()
+    solvers = ("dual",) if a.dual_only else ("interior_point", "dual")
     if a.small:
         a.globalization = "conservative"
     if a.shapes is None:
@@ -314,14 +319,14 @@ def main():
                                        a.problem)
             continue
         if a.nw > 0:
-            lines += group_lines(pa, ctx, n, c, a.nwcon or n // a.nw, a.nw, a.mma_iters, a.rounds, a.reps)
+            lines += group_lines(pa, ctx, n, c, a.nwcon or n // a.nw, a.nw, a.mma_iters, a.rounds, a.reps, solvers)
             continue
         if a.small:
             lines += small_run_lines(pa, ctx, n, c, a.mma_iters, a.problem)
             continue
         if a.linearized:
             for rnd in range(a.rounds):
-                for solver in ("interior_point", "dual"):
+                for solver in solvers:
                     r = run_mma(pa, ctx, n, c, solver, a.mma_iters, problem=a.problem, linearized=True)
                     r.update(kind="mma_linearized", problem=a.problem, n=n, c=c, round=rnd)
                     lines.append(r)
@@ -339,7 +344,7 @@ def main():
                     lines.append(r)
                     print(json.dumps(r), flush=True)
                 continue
-            for solver in ("interior_point", "dual"):
+            for solver in solvers:
                 r = run_mma(pa, ctx, n, c, solver, a.mma_iters)
                 r.update(kind="mma", n=n, c=c, round=rnd)
                 lines.append(r)

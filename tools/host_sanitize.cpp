@@ -2,8 +2,9 @@
 // runtime): the in-repo LU (lu.cpp, the reference's dgetrf/dgetrs sites), the dense algebra of the bordered KKT solve
 // and of the linearised KKT residual (bordered.cpp), the one-time symbolic analysis of the sparse Cholesky
 // (csr.cpp::csr_analyse, both factor kinds; sparse_chol.cpp::chol_analyse with and without packed groups), the option
-// registry (options.cpp) and the owning device array DevArray (core.hpp) over malloc-backed stand-ins for the four
-// runtime calls it makes.  Built by
+// registry (options.cpp), the owning device array DevArray (core.hpp) and the work-vector owner of the MMA entries
+// (WorkVecs, qn.hpp, over vec_new / vec_decref of qn.cpp) over malloc-backed stand-ins for the runtime calls they
+// make.  Built by
 // `make -C paropt_amd/csrc sanitize`, run by tests/test_host_sanitize.py.  Exit code 0 = every check passed and no
 // sanitizer report.
 #include <math.h>
@@ -16,6 +17,7 @@
 #include "core.hpp"
 #include "csr.hpp"
 #include "ip.hpp"
+#include "qn.hpp"
 
 using namespace po;
 
@@ -374,8 +376,11 @@ static void test_csr() {
 
 // Stand-ins for the runtime calls of DevArray: "device" memory is the heap, so the sanitizers see every byte of it.
 static long g_dev_allocs = 0;
+static long g_fail_alloc_in = 0;  // > 0: the allocation that many calls from now fails
+static long g_stream_syncs = 0;
 extern "C" {
 hipError_t hipMalloc(void **ptr, size_t size) {
+  if (g_fail_alloc_in > 0 && --g_fail_alloc_in == 0) return hipErrorOutOfMemory;
   *ptr = malloc(size ? size : 1);
   g_dev_allocs++;
   return *ptr ? hipSuccess : hipErrorOutOfMemory;
@@ -391,6 +396,15 @@ hipError_t hipMemset(void *dst, int value, size_t sizeBytes) {
 }
 hipError_t hipMemcpy(void *dst, const void *src, size_t sizeBytes, hipMemcpyKind) {
   memcpy(dst, src, sizeBytes);
+  return hipSuccess;
+}
+hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipMemsetAsync(void *dst, int value, size_t sizeBytes, hipStream_t) {
+  memset(dst, value, sizeBytes);
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t) {
+  g_stream_syncs++;
   return hipSuccess;
 }
 }
@@ -436,6 +450,37 @@ static void test_dev_array() {
   CHECK(live_bytes().load() == base && g_dev_allocs == 0);
 }
 
+// the work vectors of an MMA entry: m + 1 of them, a failure in the middle, release with and without vectors held
+static void test_work_vecs() {
+  Ctx *ctx = new Ctx();
+  long vecs0 = 0, vecs = 0;
+  live_objects(&vecs0, nullptr);
+  const int m = 5;
+  {
+    WorkVecs work(ctx);
+    g_stream_syncs = 0;
+    CHECK(work.release(PO_OK) == PO_OK && work.release(PO_ERR_ARG) == PO_ERR_ARG && g_stream_syncs == 0);  // empty
+    CHECK(work.add(m + 1, 37) == PO_OK && work.v.size() == (size_t)m + 1);
+    live_objects(&vecs, nullptr);
+    CHECK(vecs == vecs0 + m + 1);
+    for (int i = 0; i <= m; i++)
+      for (int j = 0; j < 37; j++) CHECK(work.d(i)[j] == 0.0);
+    const std::vector<double *> G = work.pointers(1, m);
+    CHECK((int)G.size() == m && G[0] == work.d(1) && G[m - 1] == work.d(m));
+    g_stream_syncs = 0;
+    CHECK(work.release(PO_ERR_USER) == PO_ERR_USER && g_stream_syncs >= 1 && work.v.empty());  // the code is handed on
+    live_objects(&vecs, nullptr);
+    CHECK(vecs == vecs0);
+    g_fail_alloc_in = 3;  // the third of m + 1 allocations fails: two vectors are held, and released
+    CHECK(work.add(m + 1, 37) == PO_ERR_HIP && work.v.size() == 2);
+    g_fail_alloc_in = 0;
+    CHECK(work.add(2, 0) == PO_OK && work.v.size() == 4);  // (empty vectors, and a second group behind the first)
+  }  // destroyed holding vectors
+  live_objects(&vecs, nullptr);
+  CHECK(vecs == vecs0 && g_dev_allocs == 0);
+  delete ctx;
+}
+
 static void test_options() {
   Options o;
   o.addTrustRegionDefaults();
@@ -465,6 +510,7 @@ int main() {
   test_csr();
   test_chol_analyse();
   test_dev_array();
+  test_work_vecs();
   test_options();
   if (fails) {
     fprintf(stderr, "%d check(s) failed\n", fails);
