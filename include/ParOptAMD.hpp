@@ -2124,6 +2124,32 @@ class ParOptSparseCholesky {
   void solve(ParOptScalar *x, int nrhs) { report(po_sparse_chol_solve(h, x, nrhs, size)); }
   // the same on a DEVICE array (queued on the context's stream)
   void solveDevice(ParOptScalar *dx, int nrhs = 1) { report(po_sparse_chol_solve_device(h, dx, nrhs, size)); }
+  // No counterpart in the reference (po_sparse_chol_set_keep_matrix and what follows it in paropt_amd.h).  A is the
+  // symmetric matrix whose permuted lower triangle setValues sums into the factor.  setKeepMatrix(true) retains it
+  // from the next setValues on (creation pattern only from then on); setDiagonalShift(shift) -- size values in the
+  // caller's numbering, NULL clears -- makes the next setValues put A + diag(shift) into the factor while the retained
+  // A stays unshifted.  Each returns 0, or non-zero with a message.
+  int setKeepMatrix(bool on = true) { return report(po_sparse_chol_set_keep_matrix(h, on ? 1 : 0)); }
+  int setDiagonalShift(const ParOptScalar *shift) { return report(po_sparse_chol_set_diagonal_shift(h, shift)); }
+  // y = A x, nrhs columns at x + j * size and y + j * size; multDevice: DEVICE arrays, queued on the context's stream
+  int mult(const ParOptScalar *x, ParOptScalar *y, int nrhs = 1) {
+    return report(po_sparse_chol_matvec(h, x, size, y, size, nrhs));
+  }
+  int multDevice(const ParOptScalar *dx, ParOptScalar *dy, int nrhs = 1) {
+    return report(po_sparse_chol_matvec_device(h, dx, size, dy, size, nrhs));
+  }
+  // solve with the factorization of A + diag(shift), then refine against the retained A until the backward error
+  // eta = max|b - A x| / (||A||_inf max|x| + max|b|) is at most tol, stops halving, or max_steps corrections are done
+  // (defaults: 5 and eps).  Per right-hand side, each pointer nullable: corrections applied, eta before the first,
+  // eta of the x returned.
+  int solveRefined(ParOptScalar *x, int nrhs = 1, int max_steps = -1, double tol = -1.0, int *steps = NULL,
+                   double *eta0 = NULL, double *eta = NULL) {
+    return report(po_sparse_chol_solve_refined(h, x, nrhs, size, max_steps, tol, steps, eta0, eta));
+  }
+  int solveRefinedDevice(ParOptScalar *dx, int nrhs = 1, int max_steps = -1, double tol = -1.0, int *steps = NULL,
+                         double *eta0 = NULL, double *eta = NULL) {
+    return report(po_sparse_chol_solve_refined_device(h, dx, nrhs, size, max_steps, tol, steps, eta0, eta));
+  }
   void getInfo(int *_size, int *_num_snodes, int *_nnzL) {
     int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     po_sparse_chol_info(h, info);

@@ -1077,6 +1077,53 @@ int po_sparse_chol_inertia(po_sparse_chol h, int64_t inertia[3]);
 /* solve, ParOptSparseCholesky.h:44, for nrhs right-hand sides in place, column j at x + j * ldx */
 int po_sparse_chol_solve(po_sparse_chol h, double *x, int nrhs, int64_t ldx);
 int po_sparse_chol_solve_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx);
+/* RETAINED MATRIX AND REFINED SOLVE (no counterpart in the reference; all of it opt-in: a handle that never calls
+ * these entries allocates, launches and computes what it did before).
+ * A is the symmetric matrix whose permuted lower triangle po_sparse_chol_set_values sums into the factor: the entries
+ * with iperm[row] >= iperm[col], repeated entries added in entry order, the permuted-upper copies not read.  A caller
+ * who passes one triangle only under an ordering that moves entries across the diagonal gets the matrix the factor
+ * gets, not another one.
+ * _set_keep_matrix(h, on != 0): from now on every _set_values / _set_values_device also sums one double per distinct
+ * permuted-lower entry into a compact array beside the factor (the same sums, bit for bit); po_sparse_chol_factor
+ * does not touch it.  Values set BEFORE keeping was switched on are not retained.  While keeping is on, _set_values
+ * with a pattern other than the creation pattern is PO_ERR_ARG with a message.  Works on an analysis-only handle,
+ * where only the table below is built.  on == 0 frees what keeping allocated. */
+int po_sparse_chol_set_keep_matrix(po_sparse_chol h, int on);
+int po_sparse_chol_get_keep_matrix(po_sparse_chol h, int *on);
+/* the table of the retained matrix, borrowed host arrays, any pointer may be NULL: the FULL symmetric matrix in
+ * ELIMINATION order (row i is unknown perm[i]) as compressed rows sorted by column: rowp (size + 1), col, vidx, where
+ * vidx indexes the compact values, *nd of them; the two copies of an off-diagonal entry share a vidx.  PO_ERR_ARG
+ * while keeping is off.  Works on analysis-only handles. */
+int po_sparse_chol_matrix_arrays(po_sparse_chol h, const int **rowp, const int **col, const int **vidx, int64_t *nd);
+/* shift: a HOST array of `size` doubles in the caller's numbering, copied; NULL clears it.  The next _set_values /
+ * _set_values_device adds shift[i] to the diagonal entry of unknown i in the factor's storage after the scatter, so
+ * po_sparse_chol_factor factors A + diag(shift) and po_sparse_chol_inertia is that matrix's; the retained values do
+ * NOT get the shift: the product and the refinement see A.  Independent of keeping (without it the handle simply
+ * solves the shifted system) and of the factorization kind. */
+int po_sparse_chol_set_diagonal_shift(po_sparse_chol h, const double *shift);
+/* y = A x in the caller's numbering for nrhs columns, x at x + j * ldx and y at y + j * ldy (they must not overlap).
+ * Needs keeping and values set since it was switched on (PO_ERR_ARG with a message otherwise); works before and after
+ * po_sparse_chol_factor.  Every element of y is a sum in a fixed order: column j has the same bits whatever nrhs is.
+ * _matvec takes host arrays; _matvec_device device arrays, queued on the context's stream without a host
+ * synchronisation. */
+int po_sparse_chol_matvec(po_sparse_chol h, const double *x, int64_t ldx, double *y, int64_t ldy, int nrhs);
+int po_sparse_chol_matvec_device(po_sparse_chol h, const double *dx, int64_t ldx, double *dy, int64_t ldy, int nrhs);
+/* Solve with the factorization (of A + diag(shift)) and refine against the retained A, in place like
+ * po_sparse_chol_solve.  With eta_j = max|b - A x|_j / (||A||_inf max|x|_j + max|b|_j):
+ *     x = solve(b); k = 0
+ *     loop: column j stops when !(eta_j > tol) (so a NaN stops), or k == max_steps, or k > 0 and
+ *           !(eta_j <= previous eta_j / 2) (LAPACK's xGERFS rule; no roll-back);
+ *           every column stopped: return;   x_j += solve(b - A x)_j for the columns still running; k += 1
+ * max_steps < 0 means 5 (ITMAX of xGERFS) and 0 is the plain solve plus one residual; tol < 0 or NaN means eps =
+ * 2^-52.  Per column, each pointer nullable with room for nrhs entries: steps taken, eta before the first
+ * correction (eta0) and eta of the x returned.  A column's x and statistics have the bits it would have alone.  Where
+ * the iteration does not contract (a shift too large, pivots too bad) it stops on the halving rule and eta says so.
+ * One small device-to-host copy and one synchronisation a step.  PO_ERR_ARG with a message without keeping, without
+ * retained values, before po_sparse_chol_factor, and for the nrhs / ldx po_sparse_chol_solve refuses. */
+int po_sparse_chol_solve_refined(po_sparse_chol h, double *x, int nrhs, int64_t ldx, int max_steps, double tol,
+                                 int *steps, double *eta0, double *eta);
+int po_sparse_chol_solve_refined_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx, int max_steps, double tol,
+                                        int *steps, double *eta0, double *eta);
 /* getInfo, ParOptSparseCholesky.h:47, and more: {size, num_snodes, nnzL = sum s (s + 1) / 2 + b s, levels of the
  * supernode tree, largest s, largest front s + b, work_bytes (update-matrix arena and solve work space), block
  * width NB of the blocked fronts} */

@@ -1530,12 +1530,14 @@ class SparseCholesky:
 
     factorization: "llt" (Cholesky, the default) or "ldlt": L S L^T = P A P^T with S = diag(+-1) and NO pivoting, for
     symmetric quasi-definite matrices ([[E, B^T], [B, -F]] with E, F SPD), which have it under every permutation.  For
-    a general indefinite matrix it is only as good as its pivots."""
+    a general indefinite matrix it is only as good as its pivots.
+
+    keep_matrix=True retains A beside the factor (see set_keep_matrix): matvec() and solve_refined() need it."""
 
     ORDERS = {"natural": 0, "amd": 1, "nd": 2}
     FACTORIZATIONS = {"llt": 0, "ldlt": 1}
 
-    def __init__(self, ctx, size, colp, rows, order="nd", perm=None, factorization="llt"):
+    def __init__(self, ctx, size, colp, rows, order="nd", perm=None, factorization="llt", keep_matrix=False):
         self.ctx = ctx
         self._colp = np.ascontiguousarray(colp, dtype=np.intc)
         self._rows = np.ascontiguousarray(rows, dtype=np.intc)
@@ -1569,6 +1571,8 @@ class SparseCholesky:
         self.snode_level = arr(ptrs[3], self.num_snodes)
         if factorization != "llt":
             self.set_factorization(factorization)
+        if keep_matrix:
+            self.set_keep_matrix(True)
 
     @property
     def handle(self):
@@ -1672,6 +1676,97 @@ class SparseCholesky:
         check(lib.po_sparse_chol_solve_device(self._h, ptr, nrhs, self.size))
         self.ctx.synchronize()
         return t
+
+    # ---- retained matrix, diagonal shift, refined solve (po_sparse_chol_set_keep_matrix and what follows it) ----
+    def set_keep_matrix(self, on=True):
+        """Retain A -- the symmetric matrix whose permuted lower triangle set_values sums into the factor -- from the
+        next set_values on; allowed on an analysis-only object (matrix_arrays() then works)."""
+        check(lib.po_sparse_chol_set_keep_matrix(self._h, 1 if on else 0))
+
+    @property
+    def keep_matrix(self):
+        on = C.c_int()
+        check(lib.po_sparse_chol_get_keep_matrix(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def matrix_arrays(self):
+        """(rowp, col, vidx, nd): the full symmetric matrix in elimination order (row i is unknown perm[i]) as
+        compressed rows sorted by column; vidx indexes the nd compact values.  Copies."""
+        ptrs = [L.c_int_p() for _ in range(3)]
+        nd = C.c_int64()
+        check(lib.po_sparse_chol_matrix_arrays(self._h, *[C.byref(q) for q in ptrs], C.byref(nd)))
+        rowp = np.ctypeslib.as_array(ptrs[0], shape=(self.size + 1,)).copy()
+        nnz = int(rowp[-1])
+
+        def arr(q):
+            return np.ctypeslib.as_array(q, shape=(nnz,)).copy() if nnz > 0 else np.zeros(0, dtype=np.intc)
+
+        return rowp, arr(ptrs[1]), arr(ptrs[2]), int(nd.value)
+
+    def set_diagonal_shift(self, shift):
+        """shift (size values, the caller's numbering) is added to the diagonal of what the next set_values puts into
+        the factor: factor() factors A + diag(shift), the retained A does not get it.  None clears it."""
+        if shift is None:
+            check(lib.po_sparse_chol_set_diagonal_shift(self._h, None))
+            return
+        sh = np.ascontiguousarray(shift, dtype=np.float64)
+        if sh.shape != (self.size,):
+            raise ValueError("set_diagonal_shift: shift must have `size` entries")
+        check(lib.po_sparse_chol_set_diagonal_shift(self._h, sh.ctypes.data_as(L.c_double_p)))
+
+    def matvec(self, x):
+        """y = A x for x of shape (n,) or (nrhs, n); returns a new array."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim not in (1, 2) or x.shape[-1] != self.size:
+            raise ValueError("matvec: x must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        y = np.zeros_like(x)
+        check(lib.po_sparse_chol_matvec(self._h, x.ctypes.data_as(L.c_double_p), self.size,
+                                        y.ctypes.data_as(L.c_double_p), self.size, nrhs))
+        return y
+
+    def matvec_tensor(self, x, y):
+        """y = A x on contiguous float64 torch tensors of shape (n,) or (nrhs, n) on the context's device."""
+        if x.dim() not in (1, 2) or x.shape[-1] != self.size or y.shape != x.shape:
+            raise ValueError("matvec_tensor: x and y must both have shape (n,) or (nrhs, n)")
+        nrhs = 1 if x.dim() == 1 else x.shape[0]
+        px = self._tensor_ptr(x, nrhs * self.size, "matvec_tensor")
+        py = self._tensor_ptr(y, nrhs * self.size, "matvec_tensor")
+        check(lib.po_sparse_chol_matvec_device(self._h, px, self.size, py, self.size, nrhs))
+        self.ctx.synchronize()
+        return y
+
+    @staticmethod
+    def _refine_args(nrhs, max_steps, tol):
+        steps = np.zeros(nrhs, dtype=np.intc)
+        eta0, eta = np.zeros(nrhs), np.zeros(nrhs)
+        ptrs = (steps.ctypes.data_as(L.c_int_p), eta0.ctypes.data_as(L.c_double_p), eta.ctypes.data_as(L.c_double_p))
+        return {"steps": steps, "eta0": eta0, "eta": eta}, (int(max_steps), -1.0 if tol is None else float(tol)) + ptrs
+
+    def solve_refined(self, b, max_steps=5, tol=None):
+        """(x, info): x = A^-1 b by the factorization (of A + diag(shift)) and iterative refinement against the
+        retained A; b of shape (n,) or (nrhs, n).  info = {"steps", "eta0", "eta"}, arrays with one entry per
+        right-hand side: corrections applied, the backward error max|b - A x| / (||A||_inf max|x| + max|b|) before
+        the first of them and that of the x returned.  tol=None: eps."""
+        x = np.array(b, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (1, 2) or x.shape[-1] != self.size:
+            raise ValueError("solve_refined: b must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        info, args = self._refine_args(nrhs, max_steps, tol)
+        check(lib.po_sparse_chol_solve_refined(self._h, x.ctypes.data_as(L.c_double_p), nrhs, self.size, *args))
+        return x, info
+
+    def solve_refined_tensor(self, t, max_steps=5, tol=None):
+        """solve_refined in place on a contiguous float64 torch tensor of shape (n,) or (nrhs, n) on the context's
+        device; returns (t, info)."""
+        if t.dim() not in (1, 2) or t.shape[-1] != self.size:
+            raise ValueError("solve_refined_tensor: t must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if t.dim() == 1 else t.shape[0]
+        ptr = self._tensor_ptr(t, nrhs * self.size, "solve_refined_tensor")
+        info, args = self._refine_args(nrhs, max_steps, tol)
+        check(lib.po_sparse_chol_solve_refined_device(self._h, ptr, nrhs, self.size, *args))
+        self.ctx.synchronize()
+        return t, info
 
     def close(self):
         if self._h:

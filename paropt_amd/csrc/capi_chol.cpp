@@ -90,6 +90,63 @@ int po_sparse_chol_solve_device(po_sparse_chol h, double *dx, int nrhs, int64_t 
   if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(dx);
   return h->c->solveDevice(dx, nrhs, ldx);
 }
+// no counterpart in the reference: the retained matrix, the diagonal shift and the refined solve (paropt_amd.h,
+// "RETAINED MATRIX AND REFINED SOLVE")
+int po_sparse_chol_set_keep_matrix(po_sparse_chol h, int on) {
+  PO_CHECK_PTR(h);
+  return h->c->setKeepMatrix(on != 0);
+}
+int po_sparse_chol_get_keep_matrix(po_sparse_chol h, int *on) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(on);
+  *on = h->c->keepMatrix() ? 1 : 0;
+  return PO_OK;
+}
+int po_sparse_chol_matrix_arrays(po_sparse_chol h, const int **rowp, const int **col, const int **vidx, int64_t *nd) {
+  PO_CHECK_PTR(h);
+  if (!h->c->keepMatrix()) {
+    po::set_error("po_sparse_chol_matrix_arrays: keep_matrix is off, there is no table");
+    return PO_ERR_ARG;
+  }
+  const po::CholSymbolic &s = h->c->sym;
+  if (rowp) *rowp = s.mat_rowp.data();
+  if (col) *col = s.mat_col.data();
+  if (vidx) *vidx = s.mat_vidx.data();
+  if (nd) *nd = (int64_t)s.asm_dst.size();
+  return PO_OK;
+}
+int po_sparse_chol_set_diagonal_shift(po_sparse_chol h, const double *shift) {
+  PO_CHECK_NUMERIC(h);
+  return h->c->setDiagonalShift(shift);
+}
+int po_sparse_chol_matvec(po_sparse_chol h, const double *x, int64_t ldx, double *y, int64_t ldy, int nrhs) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) {
+    PO_CHECK_PTR(x);
+    PO_CHECK_PTR(y);
+  }
+  return h->c->matvecHost(x, ldx, y, ldy, nrhs);
+}
+int po_sparse_chol_matvec_device(po_sparse_chol h, const double *dx, int64_t ldx, double *dy, int64_t ldy, int nrhs) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) {
+    PO_CHECK_PTR(dx);
+    PO_CHECK_PTR(dy);
+  }
+  return h->c->matvecDevice(dx, ldx, dy, ldy, nrhs);
+}
+int po_sparse_chol_solve_refined(po_sparse_chol h, double *x, int nrhs, int64_t ldx, int max_steps, double tol,
+                                 int *steps, double *eta0, double *eta) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(x);
+  return h->c->solveRefinedHost(x, nrhs, ldx, max_steps, tol, steps, eta0, eta);
+}
+int po_sparse_chol_solve_refined_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx, int max_steps, double tol,
+                                        int *steps, double *eta0, double *eta) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(dx);
+  return h->c->solveRefinedDevice(dx, nrhs, ldx, max_steps, tol, steps, eta0, eta);
+}
 // getInfo, ParOptSparseCholesky.h:47
 int po_sparse_chol_info(po_sparse_chol h, int64_t info[8]) {
   PO_CHECK_PTR(h);

@@ -119,6 +119,44 @@ int chol_scatter_table(const CholSymbolic &s, int64_t n, const int *colp, const 
   return PO_OK;
 }
 
+void chol_matrix_table(CholSymbolic *out) {
+  CholSymbolic &s = *out;
+  if (!s.mat_rowp.empty()) return;
+  const size_t nd = s.asm_dst.size();
+  // the permuted position of destination d, from its first source (every source of d has the same one)
+  std::vector<int> pr(nd), pc(nd);
+  s.mat_rowp.assign((size_t)s.n + 1, 0);
+  for (size_t d = 0; d < nd; d++) {
+    const int p = s.asm_src[s.asm_ptr[d]];
+    const int j = (int)(std::upper_bound(s.colp.begin(), s.colp.end(), p) - s.colp.begin()) - 1;
+    pr[d] = s.iperm[s.rows[p]];
+    pc[d] = s.iperm[j];
+    s.mat_rowp[pr[d] + 1]++;
+    if (pr[d] != pc[d]) s.mat_rowp[pc[d] + 1]++;
+  }
+  for (int i = 0; i < s.n; i++) s.mat_rowp[i + 1] += s.mat_rowp[i];
+  std::vector<std::pair<int, int>> ent((size_t)s.mat_rowp[s.n]);  // (column, value index), row by row
+  std::vector<int> next(s.mat_rowp.begin(), s.mat_rowp.end() - 1);
+  for (size_t d = 0; d < nd; d++) {
+    ent[next[pr[d]]++] = std::make_pair(pc[d], (int)d);
+    if (pr[d] != pc[d]) ent[next[pc[d]]++] = std::make_pair(pr[d], (int)d);
+  }
+  s.mat_col.resize(ent.size());
+  s.mat_vidx.resize(ent.size());
+  s.mat_long.clear();
+  s.mat_maxrow = 0;
+  for (int i = 0; i < s.n; i++) {
+    std::sort(ent.begin() + s.mat_rowp[i], ent.begin() + s.mat_rowp[i + 1]);
+    const int len = s.mat_rowp[i + 1] - s.mat_rowp[i];
+    s.mat_maxrow = std::max(s.mat_maxrow, len);
+    if (len > kCholLongRow) s.mat_long.push_back(i);
+  }
+  for (size_t k = 0; k < ent.size(); k++) {
+    s.mat_col[k] = ent[k].first;
+    s.mat_vidx[k] = ent[k].second;
+  }
+}
+
 int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *user_perm, CholSymbolic *out) {
   CholSymbolic &s = *out;
   if (size < 0 || size > 2000000000LL) {

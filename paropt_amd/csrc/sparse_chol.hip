@@ -17,6 +17,9 @@
 // Solves, level by level, a workgroup per front: chol_fwd / chol_bwd (solveDevice: its own permuted buffer, both
 // sweeps) and chol_fwd_panel / chol_bwd_panel (sweep: the interior point's pointer-table panels, see there).  The packed
 // groups of a level: chol_pack_fwd / chol_pack_bwd, a lane per group and right-hand side, both forms.
+// Retained matrix (opt-in, see "retained matrix" below): chol_compact_kernel (the compact values at every set_values),
+// chol_shift_kernel (the diagonal shift, into L only), chol_mat_rows / chol_mat_long (product, residual with column
+// maxima, ||A||_inf), chol_colmax, chol_update_masked; the driver is SparseChol::solveRefinedDevice.
 //
 // Matrix instruction: v_mfma_f64_4x4x4_4b_f64 with the operand layout measured in wgram.hip (A lane = i + 4 b + 16 k,
 // B lane = j + 4 b + 16 k, D lane = j + 4 b + 16 i).  It sustains 75.8 TFLOP/s against 47 for 16x16x4 (wgram.hip), the
@@ -882,6 +885,185 @@ void launch_levels(const CholSymbolic &sym, hipStream_t st, const CholDev &d, co
   }
 }
 
+// ---- retained matrix: value compaction, diagonal shift, product, residual, norms -------------------------------------
+// (sparse_chol.hpp, "RETAINED MATRIX").  All panels are in elimination order, column-major, leading dimension ld.
+//
+// Product and residual.  A row of at most kCholLongRow entries belongs to one lane (chol_mat_rows_kernel: consecutive
+// lanes take consecutive rows, so the stores and the loads of B are full runs and the gathers of X stay near the
+// diagonal for the orderings used here); a longer row belongs to one wavefront (chol_mat_long_kernel: lane l sums
+// entries l, l + 64, ..., then a fixed xor tree).  Which of the two a row gets depends on its length alone, and either
+// way an output element is one chain of fma in entry order (plus the tree), whatever nr, the slab or the grid: column
+// j has the same bits whatever other columns are in the panel.  A thread carries kMatCols columns so that the indices
+// and values of its row are read once for them; the columns of a partial group are clamped to the last one, computed
+// again and not stored.  No floating-point atomics: the column maxima go through an integer atomicMax on the bit
+// pattern of |v| (order-independent; a NaN's pattern is above every finite one's, so it shows).
+struct CholMat {
+  const int *rowp, *col, *vidx;
+  const double *aval;
+};
+constexpr int kMatCols = 4;
+enum { MAT_PRODUCT, MAT_RESIDUAL, MAT_NORM };
+// slots of the statistics array (bit patterns of non-negative doubles)
+constexpr int kStatR = 0, kStatX = kCholMaxRhs, kStatB = 2 * kCholMaxRhs, kStatA = 3 * kCholMaxRhs;
+constexpr int kStatCount = 3 * kCholMaxRhs + 4;
+
+__device__ inline unsigned long long abs_bits(double v) { return (unsigned long long)__double_as_longlong(fabs(v)); }
+__device__ inline unsigned long long wave_max_bits(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+__global__ void chol_compact_kernel(const int *__restrict__ ptr, const int *__restrict__ src, int64_t ndst,
+                                    const double *__restrict__ vals, double *__restrict__ aval) {
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= ndst) return;
+  double sum = 0.0;  // (the sum chol_scatter_kernel writes into L, bit for bit)
+  for (int p = ptr[d]; p < ptr[d + 1]; p++) sum += vals[src[p]];
+  aval[d] = sum;
+}
+
+// L_kk += shift_k (elimination order) after the scatter
+__global__ void chol_shift_kernel(CholDev d, const int *__restrict__ sn_of, const double *__restrict__ shift, int n) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int J = sn_of[k], c = k - d.first[J];
+  d.L[d.panel[J] + (int64_t)c * (d.ld[J] + 1)] += shift[k];
+}
+
+template <int kMode>
+__device__ inline void mat_finish(int i, int j0, int nr, const double acc[kMatCols], const double *__restrict__ X,
+                                  const double *__restrict__ B, double *__restrict__ R, int64_t ld,
+                                  unsigned long long rb[kMatCols], unsigned long long xb[kMatCols]) {
+#pragma unroll
+  for (int k = 0; k < kMatCols; k++) {
+    if (j0 + k >= nr) continue;
+    const int64_t at = i + (int64_t)(j0 + k) * ld;
+    if (kMode == MAT_PRODUCT) {
+      R[at] = acc[k];
+    } else {
+      const double r = B[at] - acc[k];
+      R[at] = r;
+      rb[k] = abs_bits(r);
+      xb[k] = abs_bits(X[at]);
+    }
+  }
+}
+
+template <int kMode>
+__global__ __launch_bounds__(256) void chol_mat_rows_kernel(CholMat m, int n, const double *__restrict__ X,
+                                                            const double *__restrict__ B, double *__restrict__ R,
+                                                            int64_t ld, int nr, unsigned long long *stats) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int j0 = blockIdx.y * kMatCols;
+  int beg = 0, end = 0;
+  if (i < n) beg = m.rowp[i], end = m.rowp[i + 1];
+  const bool mine = i < n && end - beg <= kCholLongRow;
+  if (!mine) end = beg;
+  double acc[kMatCols] = {0.0, 0.0, 0.0, 0.0};
+  int64_t colat[kMatCols];
+#pragma unroll
+  for (int k = 0; k < kMatCols; k++) colat[k] = (int64_t)(j0 + k < nr ? j0 + k : nr - 1) * ld;
+  for (int p = beg; p < end; p++) {
+    const double a = m.aval[m.vidx[p]];
+    if (kMode == MAT_NORM) {
+      acc[0] += fabs(a);
+    } else {
+      const int c = m.col[p];
+#pragma unroll
+      for (int k = 0; k < kMatCols; k++) acc[k] = fma(a, X[c + colat[k]], acc[k]);
+    }
+  }
+  if (kMode == MAT_NORM) {
+    const unsigned long long top = wave_max_bits(abs_bits(acc[0]));
+    if ((threadIdx.x & 63) == 0 && top != 0) atomicMax(&stats[kStatA], top);
+    return;
+  }
+  unsigned long long rb[kMatCols] = {0, 0, 0, 0}, xb[kMatCols] = {0, 0, 0, 0};
+  if (mine) mat_finish<kMode>(i, j0, nr, acc, X, B, R, ld, rb, xb);
+  if (kMode == MAT_RESIDUAL) {
+#pragma unroll
+    for (int k = 0; k < kMatCols; k++) {
+      if (j0 + k >= nr) continue;  // (uniform)
+      const unsigned long long rtop = wave_max_bits(rb[k]), xtop = wave_max_bits(xb[k]);
+      if ((threadIdx.x & 63) == 0) {
+        if (rtop != 0) atomicMax(&stats[kStatR + j0 + k], rtop);
+        if (xtop != 0) atomicMax(&stats[kStatX + j0 + k], xtop);
+      }
+    }
+  }
+}
+
+template <int kMode>
+__global__ __launch_bounds__(256) void chol_mat_long_kernel(CholMat m, const int *__restrict__ long_rows, int nlong,
+                                                            const double *__restrict__ X, const double *__restrict__ B,
+                                                            double *__restrict__ R, int64_t ld, int nr,
+                                                            unsigned long long *stats) {
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int j0 = blockIdx.y * kMatCols;
+  if (w >= nlong) return;  // (the whole wavefront)
+  const int i = long_rows[w];
+  const int beg = m.rowp[i], end = m.rowp[i + 1];
+  double acc[kMatCols] = {0.0, 0.0, 0.0, 0.0};
+  int64_t colat[kMatCols];
+#pragma unroll
+  for (int k = 0; k < kMatCols; k++) colat[k] = (int64_t)(j0 + k < nr ? j0 + k : nr - 1) * ld;
+  for (int p = beg + lane; p < end; p += 64) {
+    const double a = m.aval[m.vidx[p]];
+    if (kMode == MAT_NORM) {
+      acc[0] += fabs(a);
+    } else {
+      const int c = m.col[p];
+#pragma unroll
+      for (int k = 0; k < kMatCols; k++) acc[k] = fma(a, X[c + colat[k]], acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < (kMode == MAT_NORM ? 1 : kMatCols); k++) {
+    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off);
+  }
+  if (lane != 0) return;
+  if (kMode == MAT_NORM) {
+    atomicMax(&stats[kStatA], abs_bits(acc[0]));
+    return;
+  }
+  unsigned long long rb[kMatCols] = {0, 0, 0, 0}, xb[kMatCols] = {0, 0, 0, 0};
+  mat_finish<kMode>(i, j0, nr, acc, X, B, R, ld, rb, xb);
+  if (kMode == MAT_RESIDUAL) {
+#pragma unroll
+    for (int k = 0; k < kMatCols; k++) {
+      if (j0 + k >= nr) continue;
+      atomicMax(&stats[kStatR + j0 + k], rb[k]);
+      atomicMax(&stats[kStatX + j0 + k], xb[k]);
+    }
+  }
+}
+
+// max |b| of every column of a panel: grid (row blocks, columns)
+__global__ __launch_bounds__(256) void chol_colmax_kernel(const double *__restrict__ P, int64_t ld, int n,
+                                                          unsigned long long *out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long top = wave_max_bits(i < n ? abs_bits(P[i + (int64_t)blockIdx.y * ld]) : 0ull);
+  if ((threadIdx.x & 63) == 0 && top != 0) atomicMax(&out[blockIdx.y], top);
+}
+
+// X_j += D_j for the columns whose bit is set in mask (a slab has at most 32 columns)
+__global__ void chol_update_masked_kernel(double *__restrict__ X, const double *__restrict__ D, int64_t ld, int n,
+                                          int nr, uint32_t mask) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)n * nr) return;
+  const int p = (int)(idx % n), r = (int)(idx / n);
+  if ((mask >> r) & 1u) X[p + r * ld] += D[p + r * ld];
+}
+
+inline double bits_double(unsigned long long b) {
+  double v;
+  memcpy(&v, &b, sizeof(v));
+  return v;
+}
+
 }  // namespace
 
 // the anonymous namespace's CholDev under a name the header can declare
@@ -939,6 +1121,11 @@ int SparseChol::scatter(const int *ptr, const int64_t *dst, const int *src, int6
                        src, ndst, dvals, L);
     PO_HIP(hipGetLastError());
   }
+  if (d_shift && sym.n > 0) {
+    hipLaunchKernelGGL(chol_shift_kernel, dim3((unsigned)((sym.n + 255) / 256)), dim3(256), 0, ctx->stream, dev(),
+                       (const int *)d_sn_of, (const double *)d_shift, sym.n);
+    PO_HIP(hipGetLastError());
+  }
   have_values = true;
   factored = false;
   return PO_OK;
@@ -946,7 +1133,17 @@ int SparseChol::scatter(const int *ptr, const int64_t *dst, const int *src, int6
 
 int SparseChol::setValuesDevice(const double *dvals) {
   PO_HIP(hipSetDevice(ctx->device));
-  return scatter(d_asm_ptr, d_asm_dst, d_asm_src, (int64_t)sym.asm_dst.size(), dvals);
+  const int64_t ndst = (int64_t)sym.asm_dst.size();
+  if (keep) {
+    if (ndst > 0) {
+      hipLaunchKernelGGL(chol_compact_kernel, dim3((unsigned)((ndst + 255) / 256)), dim3(256), 0, ctx->stream,
+                         (const int *)d_asm_ptr, (const int *)d_asm_src, ndst, dvals, aval.get());
+      PO_HIP(hipGetLastError());
+    }
+    have_aval = true;
+    have_anorm = false;
+  }
+  return scatter(d_asm_ptr, d_asm_dst, d_asm_src, ndst, dvals);
 }
 
 int SparseChol::setValuesHost(int64_t n, const int *colp, const int *rows, const double *vals) {
@@ -959,6 +1156,11 @@ int SparseChol::setValuesHost(int64_t n, const int *colp, const int *rows, const
     PO_TRY(setValuesDevice(avals));
     PO_HIP(hipStreamSynchronize(ctx->stream));  // (the caller's array may go away)
     return PO_OK;
+  }
+  if (keep) {
+    set_error("sparse Cholesky: while the matrix is kept, set_values takes the creation pattern only (the one-off "
+              "table of another pattern has no place in the retained values)");
+    return PO_ERR_ARG;
   }
   // another pattern: its own table, built on the host and used once
   std::vector<int> ptr, src;
@@ -1110,6 +1312,21 @@ int SparseChol::factor(int *info) {
   return PO_OK;
 }
 
+void SparseChol::solvePanel(double *P, int nr) {
+  hipStream_t st = ctx->stream;
+  const CholDev d = dev();
+  const int64_t ldy = sym.ldy();
+  const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+  const CholPtrs none = {};
+  launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, P, ldy,
+                chol_fwd_kernel, P, ldy, nr);
+  if (factored_kind == PO_CHOL_LDLT) {
+    hipLaunchKernelGGL(chol_sign_kernel, dim3(pg), dim3(256), 0, st, P, ldy, (const double *)d_sign, sym.n, nr);
+  }
+  launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<false>, none, P, ldy,
+                chol_bwd_kernel, P, ldy, nr);
+}
+
 int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
   if (!factored) {
     set_error("sparse Cholesky: solve() before factor()");
@@ -1122,21 +1339,13 @@ int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
   if (sym.n == 0 || nrhs == 0) return PO_OK;
   PO_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const CholDev d = dev();
   const int64_t ldy = sym.ldy();
   for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
     const int nr = std::min(kCholMaxRhs, nrhs - r0);
     double *x = dx + (int64_t)r0 * ldx;
     const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 0);
-    const CholPtrs none = {};
-    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, Y, ldy,
-                  chol_fwd_kernel, Y.get(), ldy, nr);
-    if (factored_kind == PO_CHOL_LDLT) {
-      hipLaunchKernelGGL(chol_sign_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, (const double *)d_sign, sym.n, nr);
-    }
-    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<false>, none, Y,
-                  ldy, chol_bwd_kernel, Y.get(), ldy, nr);
+    solvePanel(Y, nr);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y, ldy, x, ldx, d_perm, sym.n, nr, 1);
     PO_HIP(hipGetLastError());
   }
@@ -1174,13 +1383,264 @@ int SparseChol::solveHost(double *x, int nrhs, int64_t ldx) {
   if (nrhs > 1 && ldx < sym.n) return solveDevice(nullptr, nrhs, ldx);
   PO_HIP(hipSetDevice(ctx->device));
   const int64_t count = (int64_t)(nrhs - 1) * ldx + sym.n;
+  PO_TRY(hostBuffer(count));
+  PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PO_TRY(solveDevice(xbuf, nrhs, ldx));
+  PO_HIP(hipMemcpyAsync(x, xbuf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
+
+// ---- retained matrix, diagonal shift, refined solve ----------------------------------------------------------------
+int SparseChol::setKeepMatrix(bool on) {
+  if (!on) {
+    keep = have_aval = have_anorm = false;
+    for (DevArray<int> *a : {&d_mrowp, &d_mcol, &d_mvidx, &d_mlong}) a->reset();
+    for (DevArray<double> *a : {&aval, &Bp, &Xp}) a->reset();
+    d_stats.reset();
+    return PO_OK;
+  }
+  if (keep) return PO_OK;
+  if (2 * (int64_t)sym.asm_dst.size() > 2000000000LL) {
+    set_error("sparse Cholesky: the retained matrix would have more than 2e9 entries");
+    return PO_ERR_ARG;
+  }
+  chol_matrix_table(&sym);
+  if (ctx) {
+    if (!d_asm_ptr) {
+      set_error("sparse Cholesky: an embedded factorization keeps no matrix");
+      return PO_ERR_ARG;
+    }
+    PO_HIP(hipSetDevice(ctx->device));
+    PO_TRY(d_mrowp.upload(sym.mat_rowp));
+    PO_TRY(d_mcol.upload(sym.mat_col));
+    PO_TRY(d_mvidx.upload(sym.mat_vidx));
+    PO_TRY(d_mlong.upload(sym.mat_long));
+    PO_TRY(aval.alloc(sym.asm_dst.size() + 4, true));
+    PO_TRY(d_stats.alloc(kStatCount, true));
+  }
+  keep = true;
+  have_aval = have_anorm = false;  // (values set before this call went into L only)
+  return PO_OK;
+}
+
+int SparseChol::setDiagonalShift(const double *shift) {
+  if (!shift) {
+    d_shift.reset();
+    d_sn_of.reset();
+    return PO_OK;
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  std::vector<double> permuted((size_t)sym.n);
+  for (int k = 0; k < sym.n; k++) permuted[k] = shift[sym.perm[k]];
+  PO_HIP(hipStreamSynchronize(ctx->stream));  // (a scatter that reads the previous shift may still be queued)
+  PO_TRY(d_shift.upload(permuted));
+  if (!d_sn_of) PO_TRY(d_sn_of.upload(sym.sn_of));
+  return PO_OK;
+}
+
+int SparseChol::needMatrix(const char *who) {
+  if (!keep) {
+    set_error("sparse Cholesky: %s needs the retained matrix (keep_matrix is off)", who);
+    return PO_ERR_ARG;
+  }
+  if (!have_aval) {
+    set_error("sparse Cholesky: %s needs values set since keep_matrix was switched on", who);
+    return PO_ERR_ARG;
+  }
+  return PO_OK;
+}
+
+void SparseChol::productPanel(const double *X, const double *B, double *R, int nr, unsigned long long *stats) {
+  const CholMat m = {d_mrowp, d_mcol, d_mvidx, aval};
+  const int64_t ld = sym.ldy();
+  const int nlong = (int)sym.mat_long.size();
+  const dim3 rows_grid((unsigned)((sym.n + 255) / 256), (unsigned)((nr + kMatCols - 1) / kMatCols));
+  const dim3 long_grid((unsigned)((nlong + 3) / 4), rows_grid.y);
+  hipStream_t st = ctx->stream;
+  if (B) {
+    hipLaunchKernelGGL(chol_mat_rows_kernel<MAT_RESIDUAL>, rows_grid, dim3(256), 0, st, m, sym.n, X, B, R, ld, nr,
+                       stats);
+    if (nlong > 0) {
+      hipLaunchKernelGGL(chol_mat_long_kernel<MAT_RESIDUAL>, long_grid, dim3(256), 0, st, m, (const int *)d_mlong,
+                         nlong, X, B, R, ld, nr, stats);
+    }
+  } else {
+    hipLaunchKernelGGL(chol_mat_rows_kernel<MAT_PRODUCT>, rows_grid, dim3(256), 0, st, m, sym.n, X, B, R, ld, nr,
+                       stats);
+    if (nlong > 0) {
+      hipLaunchKernelGGL(chol_mat_long_kernel<MAT_PRODUCT>, long_grid, dim3(256), 0, st, m, (const int *)d_mlong,
+                         nlong, X, B, R, ld, nr, stats);
+    }
+  }
+}
+
+// ||A||_inf, once per set of values
+int SparseChol::matrixNorm() {
+  if (have_anorm) return PO_OK;
+  hipStream_t st = ctx->stream;
+  const CholMat m = {d_mrowp, d_mcol, d_mvidx, aval};
+  const int nlong = (int)sym.mat_long.size();
+  PO_HIP(hipMemsetAsync(d_stats + kStatA, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(chol_mat_rows_kernel<MAT_NORM>, dim3((unsigned)((sym.n + 255) / 256)), dim3(256), 0, st, m, sym.n,
+                     (const double *)nullptr, (const double *)nullptr, (double *)nullptr, (int64_t)0, 1, d_stats.get());
+  if (nlong > 0) {
+    hipLaunchKernelGGL(chol_mat_long_kernel<MAT_NORM>, dim3((unsigned)((nlong + 3) / 4)), dim3(256), 0, st, m,
+                       (const int *)d_mlong, nlong, (const double *)nullptr, (const double *)nullptr,
+                       (double *)nullptr, (int64_t)0, 1, d_stats.get());
+  }
+  PO_HIP(hipGetLastError());
+  unsigned long long bits = 0;
+  PO_HIP(hipMemcpyAsync(&bits, d_stats + kStatA, sizeof(bits), hipMemcpyDeviceToHost, st));
+  PO_HIP(hipStreamSynchronize(st));
+  anorm = bits_double(bits);
+  have_anorm = true;
+  return PO_OK;
+}
+
+int SparseChol::matvecDevice(const double *dx, int64_t ldx, double *dy, int64_t ldy_user, int nrhs) {
+  PO_TRY(needMatrix("matvec()"));
+  if (nrhs < 0 || (nrhs > 1 && (ldx < sym.n || ldy_user < sym.n))) {
+    set_error("sparse Cholesky: matvec with nrhs %d, ldx %lld, ldy %lld (size %d)", nrhs, (long long)ldx,
+              (long long)ldy_user, sym.n);
+    return PO_ERR_ARG;
+  }
+  if (sym.n == 0 || nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t ldy = sym.ldy();
+  if (!Xp) PO_TRY(Xp.alloc((size_t)(ldy * kCholMaxRhs), true));
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Xp.get(), ldy,
+                       const_cast<double *>(dx) + (int64_t)r0 * ldx, ldx, d_perm.get(), sym.n, nr, 0);
+    productPanel(Xp, nullptr, Y, nr, nullptr);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Y.get(), ldy, dy + (int64_t)r0 * ldy_user,
+                       ldy_user, d_perm.get(), sym.n, nr, 1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::hostBuffer(int64_t count) {
   if (count > xbuf_cap) {
     xbuf_cap = 0;
     PO_TRY(xbuf.alloc((size_t)count, false));
     xbuf_cap = count;
   }
+  return PO_OK;
+}
+
+int SparseChol::matvecHost(const double *x, int64_t ldx, double *y, int64_t ldy_user, int nrhs) {
+  if (sym.n == 0 || nrhs <= 0 || (nrhs > 1 && (ldx < sym.n || ldy_user < sym.n))) {
+    return matvecDevice(nullptr, ldx, nullptr, ldy_user, nrhs);
+  }
+  PO_TRY(needMatrix("matvec()"));
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t xcount = (int64_t)(nrhs - 1) * ldx + sym.n, ycount = (int64_t)(nrhs - 1) * ldy_user + sym.n;
+  PO_TRY(hostBuffer(xcount));
+  if (ycount > ybuf_cap) {
+    ybuf_cap = 0;
+    PO_TRY(ybuf.alloc((size_t)ycount, true));
+    ybuf_cap = ycount;
+  }
+  PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)xcount * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PO_TRY(matvecDevice(xbuf, ldx, ybuf, ldy_user, nrhs));
+  // (column by column: what lies between the columns of y is the caller's)
+  const size_t pitch = (size_t)(nrhs > 1 ? ldy_user : sym.n) * sizeof(double);
+  PO_HIP(hipMemcpy2DAsync(y, pitch, ybuf, pitch, (size_t)sym.n * sizeof(double), (size_t)nrhs, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
+
+// Refined solve, slab by slab.  B, X and Y are panels in elimination order:
+//   X = solve(B); k = 0
+//   loop: R = B - A X into Y with max|r|_j and max|x|_j (one small copy to the host and one synchronisation a step);
+//         eta_j = max|r|_j / (||A||_inf max|x|_j + max|b|_j);
+//         column j stops when !(eta_j > tol) -- so a NaN stops --, or k == max_steps, or k > 0 and
+//         !(eta_j <= eta_j_prev / 2) (LAPACK's xGERFS rule; no roll-back, the eta reported is the iterate's);
+//         all stopped: done.  D = solve(R) in Y; X_j += D_j for the columns still running; k += 1
+// A column that has stopped is swept along with the others and never updated: its result and its statistics are the
+// ones it would have alone.
+int SparseChol::solveRefinedDevice(double *dx, int nrhs, int64_t ldx, int max_steps, double tol, int *steps,
+                                   double *eta0, double *eta) {
+  PO_TRY(needMatrix("solve_refined()"));
+  if (!factored) {
+    set_error("sparse Cholesky: solve_refined() before factor()");
+    return PO_ERR_ARG;
+  }
+  if (nrhs < 0 || (nrhs > 1 && ldx < sym.n)) {
+    set_error("sparse Cholesky: solve_refined with nrhs %d, ldx %lld (size %d)", nrhs, (long long)ldx, sym.n);
+    return PO_ERR_ARG;
+  }
+  if (max_steps < 0) max_steps = 5;                 // ITMAX of xGERFS
+  if (!(tol >= 0.0)) tol = 2.220446049250313e-16;   // eps: a residual formed in fp64 is not known better
+  if (sym.n == 0 || nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t ldy = sym.ldy();
+  const size_t panel = (size_t)(ldy * kCholMaxRhs);
+  if (!Xp) PO_TRY(Xp.alloc(panel, true));
+  if (!Bp) PO_TRY(Bp.alloc(panel, true));
+  PO_TRY(matrixNorm());
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    double *x = dx + (int64_t)r0 * ldx;
+    const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+    const size_t bytes = (size_t)(ldy * nr) * sizeof(double);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Bp.get(), ldy, x, ldx, d_perm.get(), sym.n, nr,
+                       0);
+    PO_HIP(hipMemsetAsync(d_stats, 0, kStatA * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(chol_colmax_kernel, dim3((unsigned)((sym.n + 255) / 256), (unsigned)nr), dim3(256), 0, st,
+                       (const double *)Bp, ldy, sym.n, d_stats + kStatB);
+    PO_HIP(hipMemcpyAsync(Y, Bp, bytes, hipMemcpyDeviceToDevice, st));
+    solvePanel(Y, nr);
+    PO_HIP(hipMemcpyAsync(Xp, Y, bytes, hipMemcpyDeviceToDevice, st));
+    uint32_t running = nr == 32 ? 0xffffffffu : ((1u << nr) - 1u);
+    double prev[kCholMaxRhs];
+    for (int k = 0;; k++) {
+      if (k > 0) PO_HIP(hipMemsetAsync(d_stats, 0, kStatB * sizeof(unsigned long long), st));
+      productPanel(Xp, Bp, Y, nr, d_stats);
+      PO_HIP(hipGetLastError());
+      unsigned long long h[kStatA];
+      PO_HIP(hipMemcpyAsync(h, d_stats, sizeof(h), hipMemcpyDeviceToHost, st));
+      PO_HIP(hipStreamSynchronize(st));
+      for (int j = 0; j < nr; j++) {
+        if (!((running >> j) & 1u)) continue;
+        const double e = bits_double(h[kStatR + j]) / (anorm * bits_double(h[kStatX + j]) + bits_double(h[kStatB + j]));
+        if (k == 0 && eta0) eta0[r0 + j] = e;
+        if (eta) eta[r0 + j] = e;
+        if (!(e > tol) || k == max_steps || (k > 0 && !(e <= 0.5 * prev[j]))) {
+          running &= ~(1u << j);
+          if (steps) steps[r0 + j] = k;
+        }
+        prev[j] = e;
+      }
+      if (running == 0) break;
+      solvePanel(Y, nr);
+      hipLaunchKernelGGL(chol_update_masked_kernel, dim3(pg), dim3(256), 0, st, Xp.get(), (const double *)Y, ldy,
+                         sym.n, nr, running);
+    }
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, Xp.get(), ldy, x, ldx, d_perm.get(), sym.n, nr,
+                       1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::solveRefinedHost(double *x, int nrhs, int64_t ldx, int max_steps, double tol, int *steps, double *eta0,
+                                 double *eta) {
+  if (sym.n == 0 || nrhs <= 0 || (nrhs > 1 && ldx < sym.n)) {
+    return solveRefinedDevice(nullptr, nrhs, ldx, max_steps, tol, steps, eta0, eta);
+  }
+  PO_TRY(needMatrix("solve_refined()"));
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t count = (int64_t)(nrhs - 1) * ldx + sym.n;
+  PO_TRY(hostBuffer(count));
   PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  PO_TRY(solveDevice(xbuf, nrhs, ldx));
+  PO_TRY(solveRefinedDevice(xbuf, nrhs, ldx, max_steps, tol, steps, eta0, eta));
   PO_HIP(hipMemcpyAsync(x, xbuf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PO_HIP(hipStreamSynchronize(ctx->stream));
   return PO_OK;

@@ -36,6 +36,7 @@ constexpr int kCholTile = 64;    // trsm row chunk and edge of an update tile (o
 constexpr int kCholChunk = 32;   // target columns of a front that one assembling workgroup owns
 constexpr int kCholMaxRhs = 32;  // right-hand sides per solve sweep
 constexpr int kCholTiny = 8;     // a front of order <= this may be packed: a whole group of them is run by one lane
+constexpr int kCholLongRow = 32; // a row of the retained matrix with more entries is multiplied by a whole wavefront
 // Fronts per packed group at most: the default of SW_CHOL_PACK, 0 = no packing.  It IS 0: on the chain pattern every
 // cap from 8 to 64 is several times faster than no packing, but on the grid patterns every one of them is 1 - 7 %
 // slower (a lane walks its group's fronts one after the other in levels that launch their other fronts anyway), and
@@ -78,6 +79,12 @@ struct CholSymbolic {
   std::vector<int64_t> asm_dst;
   int64_t nnzL = 0, work_bytes = 0;
   int max_s = 0, max_front = 0;
+  // The retained matrix (chol_matrix_table, built when keeping is switched on): the FULL symmetric matrix in
+  // elimination order as compressed rows sorted by column.  mat_vidx indexes the compact value array, one double per
+  // destination of the value scatter (asm_dst.size() of them), so the two copies of an off-diagonal entry share one.
+  // mat_long lists the rows of more than kCholLongRow entries: a wavefront multiplies each, a lane every other row.
+  std::vector<int> mat_rowp, mat_col, mat_vidx, mat_long;
+  int mat_maxrow = 0;  // entries of the longest row
   int64_t ldy() const { return ((int64_t)n + 3) / 4 * 4 + 4; }
 };
 
@@ -111,6 +118,8 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
 // PO_ERR_ARG (the reference drops it silently)
 int chol_scatter_table(const CholSymbolic &s, int64_t n, const int *colp, const int *rows, std::vector<int> *ptr,
                        std::vector<int64_t> *dst, std::vector<int> *src);
+// the retained matrix's compressed rows (mat_*) from the scatter table of the creation pattern; pure host code
+void chol_matrix_table(CholSymbolic *s);
 
 class SparseChol {
  public:
@@ -133,6 +142,24 @@ class SparseChol {
   int inertia(int64_t out[3]) const;
   int solveDevice(double *dx, int nrhs, int64_t ldx);
   int solveHost(double *x, int nrhs, int64_t ldx);
+  // RETAINED MATRIX (opt-in).  A is the symmetric matrix whose permuted lower triangle the value scatter sums into the
+  // factor (the rule of chol_scatter_table).  While keeping is on, every setValues* also sums the compact values
+  // `aval` (the same sums, bit for bit); factor() leaves them alone.  On an analysis-only object only the tables.
+  int setKeepMatrix(bool on);
+  bool keepMatrix() const { return keep; }
+  // shift (host, size doubles, the user's numbering; null clears): the next setValues* adds shift[perm[k]] to the
+  // diagonal entry k of L after the scatter, so factor() factors A + diag(shift); aval does not get it
+  int setDiagonalShift(const double *shift);
+  // y = A x in the user's numbering, nrhs columns (x at dx + j ldx, y at dy + j ldy), queued on the context's stream
+  int matvecDevice(const double *dx, int64_t ldx, double *dy, int64_t ldy, int nrhs);
+  int matvecHost(const double *x, int64_t ldx, double *y, int64_t ldy, int nrhs);
+  // Solve and refine against the retained A (sparse_chol.hip, "refined solve"): per column j the steps taken,
+  // eta before the first correction and eta of the x returned (each pointer nullable, nrhs entries).
+  // max_steps < 0: 5; tol < 0 or NaN: eps.
+  int solveRefinedDevice(double *dx, int nrhs, int64_t ldx, int max_steps, double tol, int *steps, double *eta0,
+                         double *eta);
+  int solveRefinedHost(double *x, int nrhs, int64_t ldx, int max_steps, double tol, int *steps, double *eta0,
+                       double *eta);
   // The interior point's side (csr.cpp: CsrSparse).  beginAssembly queues the zeroing of L and hands it out: the
   // caller writes lower(P A P^T) at the offsets of asm_dst with kernels of its own on the same stream.
   // factorAssembled queues the numeric factorization of what was written and returns without a host read: a
@@ -152,6 +179,20 @@ class SparseChol {
   int scatter(const int *d_ptr, const int64_t *d_dst, const int *d_src, int64_t ndst, const double *dvals);
   template <bool kSigned>
   int launchFactor(int *flag);
+  // forward sweep, sign pass (LDLT), backward sweep on a panel of nr columns in elimination order, in place
+  void solvePanel(double *P, int nr);
+  int needMatrix(const char *who);
+  int matrixNorm();
+  // R = B - A X (B null: R = A X) on panels in elimination order; stats (device, null: none) takes the bit patterns of
+  // max|r| and max|x| per column
+  void productPanel(const double *X, const double *B, double *R, int nr, unsigned long long *stats);
+  int hostBuffer(int64_t count);
+  bool keep = false, have_aval = false, have_anorm = false;
+  double anorm = 0.0;
+  DevArray<int> d_mrowp, d_mcol, d_mvidx, d_mlong, d_sn_of;
+  DevArray<double> aval, d_shift, Bp, Xp, ybuf;
+  DevArray<unsigned long long> d_stats;  // 3 x kCholMaxRhs column maxima (r, x, b) and ||A||_inf, as bit patterns
+  int64_t ybuf_cap = 0;
   bool have_values = false, factored = false, have_inertia = false, uncounted = false;
   int kind = 0, factored_kind = 0;
   int64_t inertia_[3] = {0, 0, 0};

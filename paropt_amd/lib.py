@@ -299,6 +299,19 @@ SIGNATURES = {
     "po_sparse_chol_inertia": (C.c_int, [po_sparse_chol, c_i64_p]),
     "po_sparse_chol_solve": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
     "po_sparse_chol_solve_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_set_keep_matrix": (C.c_int, [po_sparse_chol, C.c_int]),
+    "po_sparse_chol_get_keep_matrix": (C.c_int, [po_sparse_chol, C.POINTER(C.c_int)]),
+    "po_sparse_chol_matrix_arrays": (C.c_int, [po_sparse_chol, c_int_pp, c_int_pp, c_int_pp, c_i64_p]),
+    "po_sparse_chol_set_diagonal_shift": (C.c_int, [po_sparse_chol, c_double_p]),
+    "po_sparse_chol_matvec": (C.c_int, [po_sparse_chol, c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int]),
+    "po_sparse_chol_matvec_device": (
+        C.c_int, [po_sparse_chol, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
+    "po_sparse_chol_solve_refined": (
+        C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64, C.c_int, C.c_double, c_int_p, c_double_p,
+                  c_double_p]),
+    "po_sparse_chol_solve_refined_device": (
+        C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_double, c_int_p, c_double_p,
+                  c_double_p]),
     "po_sparse_chol_info": (C.c_int, [po_sparse_chol, c_i64_p]),
     "po_sparse_chol_arrays": (C.c_int, [po_sparse_chol, c_int_pp, c_int_pp, c_int_pp, c_int_pp]),
     "po_sparse_chol_packing": (

@@ -12,6 +12,12 @@ One JSON line per size.
 same SPD S above, and on the --packing matrices with the diagonal negated at every odd-coloured unknown (red/black:
 symmetric quasi-definite, half the pivots negative).  Its lines carry "factorization": "ldlt"; without the flag the
 output is what it was.
+
+--refine GRID_NX: on the 5-point grid with the red/black diagonal negated, in L S L^T mode with the matrix kept, timed in
+one process, alternating, for 1 and 32 right-hand sides: the plain solve, the product y = A x alone (with the GB/s of
+the bytes it must move: rowp, col, vidx, the compact values, the two panels), the refined solve stopped after its
+first residual pass (max_steps = 0) and after exactly one correction (max_steps = 1, tol = 0); one refinement step
+costs the difference of the last two.  One JSON line per number of right-hand sides.
 """
 import argparse
 import json
@@ -185,6 +191,61 @@ def run_packing(ctx, name, n, colp, rows, vals, repeats, inner, cap=16, factoriz
     return rec
 
 
+def run_refine(ctx, nx, repeats, inner):
+    import torch
+
+    import paropt_amd as pa
+
+    name, n, colp, rows, vals = list(packing_patterns(8, nx, quasi_definite=True))[1]
+    dev = torch.device("cuda", ctx.device())
+    chol = pa.SparseCholesky(ctx, n, colp, rows, factorization="ldlt", keep_matrix=True)
+    chol.set_values_device(torch.from_numpy(np.ascontiguousarray(vals)).to(dev))
+    assert chol.factor() == 0
+    rowp, col, vidx, nd = chol.matrix_arrays()
+    matrix_bytes = 4 * (len(rowp) + len(col) + len(vidx)) + 8 * nd
+
+    def timed(fn):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        ctx.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / inner
+
+    for nrhs in (1, 32):
+        rhs = torch.from_numpy(np.random.default_rng(nrhs).standard_normal((nrhs, n))).to(dev)
+        work, out = rhs.clone(), torch.zeros_like(rhs)
+        stats = {}
+
+        def solve():
+            work.copy_(rhs)
+            chol.solve_tensor(work)
+
+        def product():
+            chol.matvec_tensor(rhs, out)
+
+        def refined(max_steps):
+            work.copy_(rhs)
+            stats[max_steps] = chol.solve_refined_tensor(work, max_steps=max_steps, tol=0.0)[1]
+
+        fns = (("solve_ms", solve), ("product_ms", product), ("refined_0_steps_ms", lambda: refined(0)),
+               ("refined_1_step_ms", lambda: refined(1)))
+        for _, fn in fns:
+            fn()  # warm
+        product_bytes = matrix_bytes + 2 * 8 * n * nrhs
+        rec = {"pattern": name, "n": n, "nnzA": int(rowp[-1]), "longest_row": int(np.diff(rowp).max()), "nrhs": nrhs,
+               "factorization": "ldlt", "levels": chol.nlevels, "product_bytes": product_bytes,
+               "eta0": float(stats[1]["eta0"].max()), "eta_after_one_step": float(stats[1]["eta"].max())}
+        rec.update({k: [] for k, _ in fns})
+        for _ in range(repeats):
+            for k, fn in fns:
+                rec[k].append(timed(fn))
+        rec["product_GBps"] = [1e-6 * product_bytes / t for t in rec["product_ms"]]
+        rec["one_step_ms"] = [b - a for a, b in zip(rec["refined_0_steps_ms"], rec["refined_1_step_ms"])]
+        rec["one_step_over_solve"] = [a / b for a, b in zip(rec["one_step_ms"], rec["solve_ms"])]
+        yield rec
+
+
 def packing_patterns(tridiag_n, nx, quasi_definite=False):
     import scipy.sparse as sp
 
@@ -209,12 +270,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--factorization", choices=("llt", "ldlt"), default="llt")
+    ap.add_argument("--refine", type=int, default=None, metavar="GRID_NX",
+                    help="only the refined solve beside the plain one and the product (see above)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import paropt_amd as pa
 
     ctx = pa.Context(0)
     lines = []
+    if a.refine:
+        a.sizes = []
+        for rec in run_refine(ctx, a.refine, a.repeats, a.inner):
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
     for nx in a.sizes:
         lines.append(json.dumps(run(ctx, nx, a.repeats, a.inner, factorization=a.factorization)))
         print(lines[-1], flush=True)

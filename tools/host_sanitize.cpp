@@ -289,6 +289,16 @@ static void test_chol_analyse() {
     int counts[CHF_COUNT];
     chol_kernel_forms(c, 40, counts);
     CHECK((counts[CHF_PACK_FACTOR] > 0) == (cap > 0));
+    // the retained matrix's table: 40 diagonal and 39 off-diagonal values, each of the latter in two rows
+    chol_matrix_table(&c);
+    CHECK((int)c.mat_rowp.size() == n + 1 && c.mat_rowp[n] == 3 * n - 2 && c.mat_maxrow == 3 && c.mat_long.empty());
+    CHECK(c.mat_col.size() == c.mat_vidx.size() && (int)c.mat_col.size() == c.mat_rowp[n]);
+    for (int i = 0; i < n; i++) {
+      for (int p = c.mat_rowp[i]; p < c.mat_rowp[i + 1]; p++) {
+        CHECK(c.mat_col[p] >= 0 && c.mat_col[p] < n && c.mat_vidx[p] >= 0 && c.mat_vidx[p] < 2 * n - 1);
+        if (p > c.mat_rowp[i]) CHECK(c.mat_col[p] > c.mat_col[p - 1]);
+      }
+    }
   }
   dbg_switch_set(SW_CHOL_PACK, -1);
 }
