@@ -27,6 +27,7 @@ namespace po {
 // ================================================================================================
 static const int LS_SUCCESS = 1, LS_FAILURE = 2, LS_MIN_STEP = 4, LS_MAX_ITERS = 8,
                  LS_NO_IMPROVEMENT = 16, LS_SHORT_STEP = 32;  // src/ParOptInteriorPoint.h:220-225
+static_assert(LS_FAILURE == 2, "IterRecord::line_fail starts as LS_FAILURE (ip.hpp)");
 
 InteriorPoint::InteriorPoint(Problem *p)
     : prob(p), ctx(p->ctx), n(p->nlocal), c(p->ncon), qn(nullptr), x(nullptr), zl(nullptr),
@@ -435,6 +436,13 @@ double InteriorPoint::nextMonotoneMu() const {
   if (mu_pow < mu_frac) new_mu = mu_pow;
   if (new_mu < 0.1 * abs_res_tol) new_mu = 0.09999 * abs_res_tol;
   return new_mu;
+}
+
+// the fraction-to-boundary rule tau = max(min_frac, 1 - mu) (:4822-4826)
+static double fractionToBoundary(double mu, double min_frac) {
+  double tau = min_frac;
+  if (1.0 - mu >= tau) tau = 1.0 - mu;
+  return tau;
 }
 
 int InteriorPoint::computeResidual(double mu, bool vectors, Vec *yqn_complete, const MultUpdate *upd) {
@@ -1296,8 +1304,7 @@ int InteriorPoint::mehrotraStep(bool use_qn, double comp, bool corrector, double
   if (sigma < 0.01) sigma = 0.01;
   barrier_param = sigma * comp;
   if (barrier_param < 0.09999 * abs_res_tol) barrier_param = 0.09999 * abs_res_tol;
-  double tau = min_frac;
-  if (1.0 - barrier_param >= tau) tau = 1.0 - barrier_param;
+  const double tau = fractionToBoundary(barrier_param, min_frac);
   *tau_out = tau;
   if (corrector) {
     // corrector: res.zl -= px*pzl, res.zu += px*pzu, res.zs -= ps*pzs, res.zt -= pt*pzt of the
@@ -1618,6 +1625,49 @@ static void clampStepDense(std::vector<double> &out, const std::vector<double> &
   }
 }
 
+// One trial point of the line search: xt = clamp(x + alpha sx px) with its barrier sums and, when the quasi-Newton
+// update wants it (sq), s = alpha sx px from the same pass; f and c at xt; with_sparse: cw(xt) in wtmp and the sparse
+// slack sums.  t.fail_obj is what evalObjCon returned; a failed evaluation takes no sparse part.
+int InteriorPoint::evalTrial(double alpha, bool with_sparse, double eps, double *sq, TrialSums &t) {
+  const bool batchable = prob->reductionsBatchable();
+  const auto sparse_part = [&]() -> int {
+    if (prob->evalSparseCon(xt, wtmp) != 0) return PO_ERR_USER;
+    iterate_flags.trial_cw_valid = true;  // wtmp = cw(xt): handed to the iterate when this trial is accepted
+    return k_w_trial(ctx, wv(), wp(), alpha * sx, eps, gsw->d, gtw->d, wtmp->d, nw, t.wsums);
+  };
+  {
+    // the barrier sums at the trial point share the collective + host sync of the problem's own reductions
+    // (f, c) when those go through the internal launchers (built-in problems)
+    BatchScope batch(ctx, batchable);
+    iterate_flags.trial_cw_valid = false;  // (xt is rewritten: wtmp is no longer cw(xt))
+    PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, t.sums, sq));
+    s_qn_a = alpha * sx;
+    iterate_flags.s_qn_from_trial = sq != nullptr;
+    userBegin();
+    t.fail_obj = prob->evalObjCon(xt, &fobj, cvals.data());
+    userEnd();
+    if (with_sparse && batchable && !t.fail_obj) PO_TRY(sparse_part());  // ... rides in the same collective
+    PO_TRY(batch.end());
+  }
+  trial_logs[0] = t.sums[0];  // barrier sums at the point xt holds now
+  trial_logs[1] = t.sums[1];
+  iterate_flags.trial_logs_valid = true;
+  neval++;
+  if (with_sparse && !batchable && !t.fail_obj) PO_TRY(sparse_part());
+  return PO_OK;
+}
+
+// The next trial step length (:4101-4130): half of alpha, or the minimiser of the quadratic through m0, dm0 and the
+// merit at alpha (not below alpha / 100); neither below alpha_min, which sets *min_hit
+static double nextTrialAlpha(double alpha, double alpha_min, double merit, double m0, double dm0, bool backtrack,
+                             bool *min_hit) {
+  const double alpha_new = backtrack ? 0.5 * alpha : -0.5 * dm0 * (alpha * alpha) / (merit - m0 - dm0 * alpha);
+  *min_hit = alpha_new <= alpha_min;
+  if (*min_hit) return alpha_min;
+  if (!backtrack && alpha_new < 0.01 * alpha) return 0.01 * alpha;
+  return alpha_new;
+}
+
 int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, double dm0,
                               int *fail_) {  // :3939-4156
   const int max_it = options.integer("max_line_iters");
@@ -1627,49 +1677,24 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
   const double eps = options.real("design_precision");
   double alpha = *alpha_;
   int fail = LS_FAILURE;
-  const bool batchable = prob->reductionsBatchable();
   // the quasi-Newton step s = alpha sx px of the trial point is written by the trial pass itself (the accepted
   // trial is the last one): no separate pass in computeStepAndUpdate
   double *sq = (qn && options.integer("use_quasi_newton_update")) ? s_qn->d : nullptr;
   double merit = 0.0, best_merit = 0.0, best_alpha = -1.0;
   std::vector<double> rs(c), rt(c);
+  TrialSums t;
   int j = 0;
   for (; j < max_it; j++) {
-    double sums[2], wsums[5];
-    // the barrier sums at the trial point share the collective + host sync of the problem's own reductions
-    // (f, c) when those go through the internal launchers (built-in problems)
-    BatchScope batch(ctx, batchable);
-    PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums, sq));
-    s_qn_a = alpha * sx;
-    iterate_flags.s_qn_from_trial = sq != nullptr;
-    clampStepDense(rs, vars.s, alpha, step.s, eps, true);
-    clampStepDense(rt, vars.t, alpha, step.t, eps, true);
-    userBegin();
-    int fail_obj = prob->evalObjCon(xt, &fobj, cvals.data());
-    userEnd();
-    iterate_flags.trial_cw_valid = false;
-    if (has_w && batchable && !fail_obj) {  // the sparse slack sums ride in the same collective
-      if (prob->evalSparseCon(xt, wtmp) != 0) return PO_ERR_USER;
-      iterate_flags.trial_cw_valid = true;  // wtmp = cw(xt): handed to the iterate when this trial is accepted
-      PO_TRY(k_w_trial(ctx, wv(), wp(), alpha * sx, eps, gsw->d, gtw->d, wtmp->d, nw, wsums));
-    }
-    PO_TRY(batch.end());
-    trial_logs[0] = sums[0];  // barrier sums at the point xt holds now
-    trial_logs[1] = sums[1];
-    iterate_flags.trial_logs_valid = true;
-    neval++;
-    if (fail_obj) {
+    PO_TRY(evalTrial(alpha, has_w, eps, sq, t));
+    if (t.fail_obj) {
       fprintf(stderr, "ParOpt: Evaluation failed during line search, trying new point\n");
       alpha *= 0.1;
       continue;
     }
-    if (has_w && !batchable) {
-      if (prob->evalSparseCon(xt, wtmp) != 0) return PO_ERR_USER;
-      iterate_flags.trial_cw_valid = true;
-      PO_TRY(k_w_trial(ctx, wv(), wp(), alpha * sx, eps, gsw->d, gtw->d, wtmp->d, nw, wsums));
-    }
-    merit = evalMeritFromSums(fobj, cvals.data(), rs.data(), rt.data(), sums[0], sums[1],
-                              has_w ? wsums : nullptr);
+    clampStepDense(rs, vars.s, alpha, step.s, eps, true);
+    clampStepDense(rt, vars.t, alpha, step.t, eps, true);
+    merit = evalMeritFromSums(fobj, cvals.data(), rs.data(), rt.data(), t.sums[0], t.sums[1],
+                              has_w ? t.wsums : nullptr);
     if (best_alpha < 0.0 || merit < best_merit) {
       best_alpha = alpha;
       best_merit = merit;
@@ -1682,23 +1707,9 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
       break;
     }
     if (j < max_it - 1) {
-      if (backtrack) {
-        alpha = 0.5 * alpha;
-        if (alpha <= alpha_min) {
-          alpha = alpha_min;
-          fail |= LS_MIN_STEP;
-        }
-      } else {
-        const double alpha_new = -0.5 * dm0 * (alpha * alpha) / (merit - m0 - dm0 * alpha);
-        if (alpha_new <= alpha_min) {
-          alpha = alpha_min;
-          fail |= LS_MIN_STEP;
-        } else if (alpha_new < 0.01 * alpha) {
-          alpha = 0.01 * alpha;
-        } else {
-          alpha = alpha_new;
-        }
-      }
+      bool min_hit = false;
+      alpha = nextTrialAlpha(alpha, alpha_min, merit, m0, dm0, backtrack, &min_hit);
+      if (min_hit) fail |= LS_MIN_STEP;
     }
   }
   if (j == max_it) fail |= LS_MAX_ITERS;
@@ -1709,41 +1720,58 @@ int InteriorPoint::lineSearch(double alpha_min, double *alpha_, double m0, doubl
     } else if ((merit <= m0 + fp) && (merit + fp >= m0)) {
       fail |= LS_NO_IMPROVEMENT;
     }
-    if (alpha != best_alpha) {
-      alpha = best_alpha;
-      iterate_flags.trial_cw_valid = false;  // xt is rebuilt below without its sparse constraint values
-      double sums[2];
-      BatchScope batch(ctx, batchable);
-      PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums, sq));
-      s_qn_a = alpha * sx;
-      iterate_flags.s_qn_from_trial = sq != nullptr;
-      userBegin();
-      int fail_obj = prob->evalObjCon(xt, &fobj, cvals.data());
-      userEnd();
-      PO_TRY(batch.end());
-      trial_logs[0] = sums[0];
-      trial_logs[1] = sums[1];
-      iterate_flags.trial_logs_valid = true;
-      neval++;
-      if (fail_obj) {
+    if (alpha != best_alpha) {  // xt is rebuilt at the best trial, without its sparse constraint values
+      PO_TRY(evalTrial(best_alpha, false, eps, sq, t));
+      if (t.fail_obj) {
         fprintf(stderr, "ParOpt: Evaluation failed during line search\n");
         fail = LS_FAILURE;
       }
-    } else {
-      alpha = best_alpha;
     }
+    alpha = best_alpha;
   }
   *alpha_ = alpha;
   *fail_ = fail;
   return PO_OK;
 }
 
-int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perform_qn_update,
-                                        int *update_type) {  // :4169-4267
-  const bool use_qnu = options.integer("use_quasi_newton_update");
+// The step of length alpha (:4169-4267) in five parts: the multipliers, the dense variables, the hand-over of the trial
+// point, the gradient at the new point and the quasi-Newton update.  form_point: the line search did not form this
+// point, so xt, f and c are taken here.
+int InteriorPoint::computeStepAndUpdate(double alpha, bool form_point, int *update_type) {
   const double eps = options.real("design_precision");
   *update_type = 0;
-  const bool do_qn = qn && perform_qn_update && use_qnu;
+  UpdatePlan plan;
+  plan.do_qn = qn && options.integer("use_quasi_newton_update");
+  PO_TRY(updateMultipliers(alpha, eps, plan));
+  updateDenseVariables(alpha, eps);
+  if (plan.do_qn && !plan.fast_yqn) {  // y_qn = -g + A^T z  at the old point with the new multipliers
+    std::vector<const double *> A;
+    for (Vec *a : Ac) A.push_back(a->d);
+    PO_TRY(k_panel_axpy(ctx, y_qn->d, -1.0, g->d, 0.0, vars.z.data(), A.data(), c, n));
+    if (has_w && prob->addSparseJacobianTranspose(1.0, x, wvar[0], y_qn) != 0) return PO_ERR_USER;
+  }
+  PO_TRY(acceptTrialPoint(alpha, form_point, eps));
+  PO_TRY(evalGradientAtIterate());
+  if (plan.do_qn) {
+    PO_TRY(quasiNewtonUpdate(alpha, plan, update_type));
+  } else if (qn) {  // :4261-4263
+    if (qn->updateMult(x, vars.z.data(), has_w ? wvar[0] : nullptr) != 0) return PO_ERR_USER;
+  }
+  if (plan.fuse_upd_noqn) {
+    spec_dt_want = true;  // (the barrier parameter of the next first solve: spec_dt_mu, set by optimize())
+    const int rc = computeResidual(barrier_param, true, nullptr, &plan.upd);
+    spec_dt_want = false;
+    PO_TRY(rc);
+    iterate_flags.residual_cached = true;
+  }
+  return PO_OK;
+}
+
+// The sparse and the bound multipliers step by alpha sz.  Decides, in `plan`, which pass carries the bound-multiplier
+// step and the first bracket of y_qn, and launches what is not deferred to the residual pass of the new point; sets
+// iterate_flags.acz_valid.
+int InteriorPoint::updateMultipliers(double alpha, double eps, UpdatePlan &plan) {
+  const bool do_qn = plan.do_qn;
   // The gradient difference y_qn = [-g + A^T z+]_old + [g - A^T z+]_new (:4197-4206, 4243-4251)
   // is assembled without streaming the constraint gradients: the first bracket from this
   // iteration's KKT residual rx = [lo]zl - [up]zu - g + A^T z and va = A^T pz (kept by the solves),
@@ -1783,7 +1811,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     set_error("internal: lean step without the fused multiplier update");
     return PO_ERR_ARG;
   }
-  MultUpdate upd;
+  MultUpdate &upd = plan.upd;
   upd.a = upd.az = alpha * sz;
   if (fast_w) upd.az = alpha;  // vA was built from the scaled step
   upd.eps = eps;
@@ -1798,6 +1826,14 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     if (acz_follow) PO_TRY(k_axpy(ctx, acz->d, alpha * sz, vA->d, n));
   }
   if (!acz_follow) iterate_flags.acz_valid = false;
+  plan.fast_yqn = fast_yqn;
+  plan.fuse_upd = fuse_upd;
+  plan.fuse_upd_noqn = fuse_upd_noqn;
+  return PO_OK;
+}
+
+// the dense slacks and multipliers step by alpha (step.* carry sx / sz already: scaleKKTStep), clamped at eps
+void InteriorPoint::updateDenseVariables(double alpha, double eps) {
   for (int i = 0; i < c; i++) {
     double v = vars.s[i] + alpha * step.s[i];
     vars.s[i] = (v <= eps) ? eps : v;
@@ -1809,14 +1845,13 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
     v = vars.zt[i] + alpha * step.zt[i];
     vars.zt[i] = (v <= eps) ? eps : v;
   }
-  std::vector<const double *> A;
-  for (Vec *a : Ac) A.push_back(a->d);
-  if (do_qn && !fast_yqn) {  // y_qn = -g + A^T z  at the old point with the new multipliers
-    PO_TRY(k_panel_axpy(ctx, y_qn->d, -1.0, g->d, 0.0, vars.z.data(), A.data(), c, n));
-    if (has_w && prob->addSparseJacobianTranspose(1.0, x, wvar[0], y_qn) != 0) return PO_ERR_USER;
-  }
-  if (eval_obj_con) {
-    // the line search was skipped: form the new point now
+}
+
+// The trial point becomes the iterate: x <-> xt, with the sparse constraint values and the barrier sums the last trial
+// left (iterate_flags.cwx_valid, iterate_logs_valid; the trial_* flags are consumed).  form_point: xt is formed here
+// first and f, c are evaluated at the new x (neval).
+int InteriorPoint::acceptTrialPoint(double alpha, bool form_point, double eps) {
+  if (form_point) {
     double sums[2];
     PO_TRY(k_trial(ctx, bounds(), px->d, alpha * sx, eps, n, xt->d, sums));  // (not in a batch: sums is local)
     iterate_flags.s_qn_from_trial = false;
@@ -1828,7 +1863,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   std::swap(x->d, xt->d);
   // ... and so are its sparse constraint values when the line search's last trial left them in wtmp
   iterate_flags.cwx_valid = false;
-  if (has_w && iterate_flags.trial_cw_valid && !eval_obj_con) {
+  if (has_w && iterate_flags.trial_cw_valid && !form_point) {
     std::swap(cwx->d, wtmp->d);
     iterate_flags.cwx_valid = true;
   }
@@ -1838,7 +1873,7 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   iterate_logs[1] = trial_logs[1];
   iterate_flags.iterate_logs_valid = iterate_flags.trial_logs_valid;
   iterate_flags.trial_logs_valid = false;
-  if (eval_obj_con) {
+  if (form_point) {
     userBegin();
     int fail = prob->evalObjCon(x, &fobj, cvals.data());
     userEnd();
@@ -1848,6 +1883,11 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
       return PO_ERR_USER;
     }
   }
+  return PO_OK;
+}
+
+// g and the Jacobian at the new iterate (ngeval); a failure is reported and the run goes on, as in the reference
+int InteriorPoint::evalGradientAtIterate() {
   // a problem with linear dense constraints keeps the Jacobian of the first evaluation (Ac == nullptr)
   userBegin();
   // (constantJacobianMask: the library's own model problems may declare single columns constant; those are kept)
@@ -1860,71 +1900,64 @@ int InteriorPoint::computeStepAndUpdate(double alpha, int eval_obj_con, int perf
   userEnd();
   ngeval++;
   if (fail_g) fprintf(stderr, "ParOpt: Gradient evaluation failed at final line search\n");
-  if (do_qn) {
-    if (!(iterate_flags.s_qn_from_trial && s_qn_a == alpha * sx)) {
-      PO_TRY(k_panel_axpy(ctx, s_qn->d, alpha * sx, px->d, 0.0, nullptr, nullptr, 0, n));
-    }
-    iterate_flags.s_qn_from_trial = false;
-    // the next residual's norms and the quasi-Newton products of the update are reduced together: nothing on the
-    // host needs the norms before the update has its dots.  Only when no user code runs in between.
-    // (user code between the two: only computeQuasiNewtonUpdateCorrection, and only when the problem has one)
-    // (sparse constraints: y_qn is assembled by its own passes, the residual of the next iteration is still taken
-    // here, early, so that its norms ride with the products of the update -- built-in problems only: their sparse
-    // callbacks queue nothing that is read before the flush)
-    const bool early_w = has_w && !fast_yqn && prob->reductionsBatchable();
-    BatchScope batch(ctx, (fast_yqn || early_w) && qn->reductionsBatchable() &&
-                              (prob->reductionsBatchable() || !prob->quasiNewtonCorrectionMayChangeStep()));
-    if (fast_yqn) {
-      // residual of the next iteration at (x+, z+, zl+, zu+): rx+ = [lo]zl+ - [up]zu+ - g+ + A+^T z+
-      // ... and y_qn += [lo]zl+ - [up]zu+ - rx+ in the same pass (the residual kernel has all three in registers)
-      // (sequential linear method: the quasi-Newton update that follows does not enter the next KKT diagonal, so this
-      // pass can leave Dinv and t of the next first solve behind as the pass without an update does -- spec_dt_*)
-      spec_dt_want = fuse_upd && options.integer("sequential_linear_method") != 0;
-      const int rcr = computeResidual(barrier_param, true, y_qn, fuse_upd ? &upd : nullptr);
-      spec_dt_want = false;
-      PO_TRY(rcr);
-      iterate_flags.residual_cached = true;
-    } else {
-      std::vector<double> mz(c > 0 ? c : 1);
-      for (int i = 0; i < c; i++) mz[i] = -vars.z[i];
-      PO_TRY(k_panel_axpy(ctx, y_qn->d, 1.0, g->d, 1.0, mz.data(), A.data(), c, n));
-      if (has_w && prob->addSparseJacobianTranspose(-1.0, x, wvar[0], y_qn) != 0) return PO_ERR_USER;
-      if (early_w) {
-        PO_TRY(computeResidual(barrier_param, true));
-        iterate_flags.residual_cached = true;
-      }
-    }
-    int rcc = prob->computeQuasiNewtonUpdateCorrection(x, vars.z.data(), s_qn, y_qn);
-    if (rcc != 0) return PO_ERR_USER;
-    // Z^T s = alpha sx Z^T px is known from the solves (ptpx) when the step came from this very panel
-    const int kz = qn->size();
-    if (forms.analytic_panel_dots && step_flags.ptpx_valid && kz == kkt.k && kz > 0 && (int)ptpx.size() == c + kz &&
-        !inexact_newton_step && !prob->quasiNewtonCorrectionMayChangeStep()) {
-      std::vector<double> zts(kz);
-      for (int j = 0; j < kz; j++) zts[j] = alpha * sx * ptpx[c + j];
-      qn->take_buffers = true;  // s_qn / y_qn are rewritten from scratch before their next use
-      const int urc = qn->updateAt(x, vars.z.data(), has_w ? wvar[0] : nullptr, s_qn, y_qn, zts.data(), update_type);
-      qn->take_buffers = false;
-      PO_TRY(urc);
-    } else {
-      qn->take_buffers = true;
-      const int urc = qn->updateAt(x, vars.z.data(), has_w ? wvar[0] : nullptr, s_qn, y_qn, nullptr, update_type);
-      qn->take_buffers = false;
-      PO_TRY(urc);
-    }
-    PO_TRY(batch.end());
-  } else if (qn && perform_qn_update) {  // :4261-4263
-    if (qn->updateMult(x, vars.z.data(), has_w ? wvar[0] : nullptr) != 0) return PO_ERR_USER;
-    *update_type = 0;
-  }
-  if (fuse_upd_noqn) {
-    spec_dt_want = true;  // (the barrier parameter of the next first solve: spec_dt_mu, set by optimize())
-    const int rc = computeResidual(barrier_param, true, nullptr, &upd);
-    spec_dt_want = false;
-    PO_TRY(rc);
-    iterate_flags.residual_cached = true;
-  }
   return PO_OK;
+}
+
+// s_qn (unless the last trial pass wrote it), the second bracket of y_qn, the problem's correction and the update of the
+// approximation.  Where the plan allows, the residual of the NEXT iteration is taken here, in the batch of the update's
+// products (iterate_flags.residual_cached).
+int InteriorPoint::quasiNewtonUpdate(double alpha, const UpdatePlan &plan, int *update_type) {
+  if (!(iterate_flags.s_qn_from_trial && s_qn_a == alpha * sx)) {
+    PO_TRY(k_panel_axpy(ctx, s_qn->d, alpha * sx, px->d, 0.0, nullptr, nullptr, 0, n));
+  }
+  iterate_flags.s_qn_from_trial = false;
+  // the next residual's norms and the quasi-Newton products of the update are reduced together: nothing on the
+  // host needs the norms before the update has its dots.  Only when no user code runs in between.
+  // (user code between the two: only computeQuasiNewtonUpdateCorrection, and only when the problem has one)
+  // (sparse constraints: y_qn is assembled by its own passes, the residual of the next iteration is still taken
+  // here, early, so that its norms ride with the products of the update -- built-in problems only: their sparse
+  // callbacks queue nothing that is read before the flush)
+  const bool early_w = has_w && !plan.fast_yqn && prob->reductionsBatchable();
+  BatchScope batch(ctx, (plan.fast_yqn || early_w) && qn->reductionsBatchable() &&
+                            (prob->reductionsBatchable() || !prob->quasiNewtonCorrectionMayChangeStep()));
+  if (plan.fast_yqn) {
+    // residual of the next iteration at (x+, z+, zl+, zu+): rx+ = [lo]zl+ - [up]zu+ - g+ + A+^T z+
+    // ... and y_qn += [lo]zl+ - [up]zu+ - rx+ in the same pass (the residual kernel has all three in registers)
+    // (sequential linear method: the quasi-Newton update that follows does not enter the next KKT diagonal, so this
+    // pass can leave Dinv and t of the next first solve behind as the pass without an update does -- spec_dt_*)
+    spec_dt_want = plan.fuse_upd && options.integer("sequential_linear_method") != 0;
+    const int rcr = computeResidual(barrier_param, true, y_qn, plan.fuse_upd ? &plan.upd : nullptr);
+    spec_dt_want = false;
+    PO_TRY(rcr);
+    iterate_flags.residual_cached = true;
+  } else {
+    std::vector<const double *> A;
+    for (Vec *a : Ac) A.push_back(a->d);
+    std::vector<double> mz(c > 0 ? c : 1);
+    for (int i = 0; i < c; i++) mz[i] = -vars.z[i];
+    PO_TRY(k_panel_axpy(ctx, y_qn->d, 1.0, g->d, 1.0, mz.data(), A.data(), c, n));
+    if (has_w && prob->addSparseJacobianTranspose(-1.0, x, wvar[0], y_qn) != 0) return PO_ERR_USER;
+    if (early_w) {
+      PO_TRY(computeResidual(barrier_param, true));
+      iterate_flags.residual_cached = true;
+    }
+  }
+  int rcc = prob->computeQuasiNewtonUpdateCorrection(x, vars.z.data(), s_qn, y_qn);
+  if (rcc != 0) return PO_ERR_USER;
+  // Z^T s = alpha sx Z^T px is known from the solves (ptpx) when the step came from this very panel
+  const int kz = qn->size();
+  std::vector<double> zts;
+  if (forms.analytic_panel_dots && step_flags.ptpx_valid && kz == kkt.k && kz > 0 && (int)ptpx.size() == c + kz &&
+      !inexact_newton_step && !prob->quasiNewtonCorrectionMayChangeStep()) {
+    zts.resize(kz);
+    for (int j = 0; j < kz; j++) zts[j] = alpha * sx * ptpx[c + j];
+  }
+  qn->take_buffers = true;  // s_qn / y_qn are rewritten from scratch before their next use
+  const int urc = qn->updateAt(x, vars.z.data(), has_w ? wvar[0] : nullptr, s_qn, y_qn,
+                               zts.empty() ? nullptr : zts.data(), update_type);
+  qn->take_buffers = false;
+  PO_TRY(urc);
+  return batch.end();
 }
 
 // ================================================================================================
@@ -1949,62 +1982,71 @@ void InteriorPoint::getIterationCounters(int *a, int *b, int *d) {
   if (d) *d = ngeval;
 }
 
-int InteriorPoint::optimize(const char *checkpoint) {
-  // Host mirrors a caller obtained for the solver's vectors (getOptimizedPoint + getArray) are the vectors' data
-  // while they are live (the reference's pointers ARE the data, src/ParOptVec.cpp:212-217): what the caller wrote
-  // through them -- e.g. warm-start multipliers zl / zu for starting_point_strategy = no_start_strategy -- is
-  // uploaded before the first kernel reads it, as po_vec_release_array(v, 1) would.  The mirrors stop being live
-  // here (the kernels below do not look at mirrors): views handed out earlier go stale during the solve and are
-  // refreshed by the next getArray.
-  {
-    Vec *mine[] = {x, zl, zu, wvar[0], wvar[1], wvar[2], wvar[3], wvar[4]};
-    bool any = false;
-    for (Vec *v : mine) {
-      any = any || vec_mirror_live(v);
-      PO_TRY(vec_mirror_upload(v));
-      if (v) v->h_live = 0;
-    }
-    if (any) PO_HIP(hipStreamSynchronize(ctx->stream));  // the pinned mirrors may be rewritten by the caller at once
+// ---- the stages of optimize(), in the order it calls them ----
+
+// Host mirrors a caller obtained for the solver's vectors (getOptimizedPoint + getArray) are the vectors' data
+// while they are live (the reference's pointers ARE the data, src/ParOptVec.cpp:212-217): what the caller wrote
+// through them -- e.g. warm-start multipliers zl / zu for starting_point_strategy = no_start_strategy -- is
+// uploaded before the first kernel reads it, as po_vec_release_array(v, 1) would.  The mirrors stop being live
+// here (the kernels below do not look at mirrors): views handed out earlier go stale during the solve and are
+// refreshed by the next getArray.
+int InteriorPoint::uploadLiveMirrors() {
+  Vec *mine[] = {x, zl, zu, wvar[0], wvar[1], wvar[2], wvar[3], wvar[4]};
+  bool any = false;
+  for (Vec *v : mine) {
+    any = any || vec_mirror_live(v);
+    PO_TRY(vec_mirror_upload(v));
+    if (v) v->h_live = 0;
   }
-  PO_TRY(createQuasiNewton());
-  PO_TRY(refreshQuasiNewton());
-  const double abs_res_tol = options.real("abs_res_tol");
-  const double rel_func_tol = options.real("rel_func_tol");
-  const double fprec = options.real("function_precision");
-  const double design_precision = options.real("design_precision");
+  if (any) PO_HIP(hipStreamSynchronize(ctx->stream));  // the pinned mirrors may be rewritten by the caller at once
+  return PO_OK;
+}
+
+InteriorPoint::RunOptions InteriorPoint::readRunOptions() const {
+  RunOptions o;
+  o.abs_res_tol = options.real("abs_res_tol");
+  o.rel_func_tol = options.real("rel_func_tol");
+  o.function_precision = options.real("function_precision");
+  o.design_precision = options.real("design_precision");
+  const std::string bname = options.str("barrier_strategy");
+  o.barrier_strategy = bname == "monotone" ? Barrier::MONOTONE
+                       : bname == "mehrotra" ? Barrier::MEHROTRA
+                       : bname == "mehrotra_predictor_corrector" ? Barrier::MPC : Barrier::COMP_FRACTION;
+  o.use_hvec_product = options.integer("use_hvec_product");
+  o.use_diag_hessian = options.integer("use_diag_hessian");
+  o.max_major_iters = options.integer("max_major_iters");
+  o.use_quasi_newton_update = options.integer("use_quasi_newton_update");
+  o.hessian_reset_freq = options.integer("hessian_reset_freq");
+  o.sequential_linear_method = options.integer("sequential_linear_method");
+  o.min_fraction_to_boundary = options.real("min_fraction_to_boundary");
+  o.use_line_search = options.integer("use_line_search");
+  o.write_output_frequency = options.integer("write_output_frequency");
+  o.step_verification_frequency = options.integer("step_verification_frequency");
+  o.gradient_verification_frequency = options.integer("gradient_verification_frequency");
+  o.starting_point_strategy = options.str("starting_point_strategy");
+  return o;
+}
+
+// Start of a run: the norm, the initial barrier and penalty parameters, the second-order work vectors, every counter
+// and carried flag back to its start, then the "init" phase -- bounds, f, c, g, A at the starting point (neval,
+// ngeval, iterate_flags.ac_valid) and the starting multipliers.  Returns what the reference returns: 1 without any
+// Hessian approximation, the callback's code for a failed first evaluation.
+int InteriorPoint::startRun(const RunOptions &opt) {
   {
     const std::string nt = options.str("norm_type");
     norm_type = nt == "infinity" ? 0 : (nt == "l1" ? 1 : 2);
   }
-  const std::string bname = options.str("barrier_strategy");
-  enum { B_MONOTONE = 0, B_MEHROTRA = 1, B_MPC = 2, B_COMPFRAC = 3 };
-  const int input_strategy = bname == "monotone" ? B_MONOTONE
-                             : bname == "mehrotra" ? B_MEHROTRA
-                             : bname == "mehrotra_predictor_corrector" ? B_MPC : B_COMPFRAC;
-  int barrier_strategy = B_MONOTONE;  // always start monotone (:4427-4441)
   corrector_active = false;
-  const bool use_hvec_product = options.integer("use_hvec_product");
-  const bool use_diag_hessian = options.integer("use_diag_hessian");
-  if (has_w && use_hvec_product) {
+  if (has_w && opt.use_hvec_product) {
     for (int i = 0; i < 5; i++) {
       if (!wscalev[i]) wscalev[i] = vec_new(ctx, nw);
       if (!wscalev[i]) return PO_ERR_HIP;
     }
   }
-  if (use_diag_hessian) PO_TRY(ensureHdiag());
+  if (opt.use_diag_hessian) PO_TRY(ensureHdiag());
   inexact_newton_step = false;
   barrier_param = options.real("init_barrier_param");
   rho_penalty_search = options.real("init_rho_penalty_search");
-  const int max_major_iters = options.integer("max_major_iters");
-  const bool use_qnu = options.integer("use_quasi_newton_update");
-  const int hessian_reset_freq = options.integer("hessian_reset_freq");
-  const bool seq_lin = options.integer("sequential_linear_method");
-  const double min_frac = options.real("min_fraction_to_boundary");
-  const bool use_line_search = options.integer("use_line_search");
-  const int write_freq = options.integer("write_output_frequency");
-  const int step_verification_frequency = options.integer("step_verification_frequency");
-  const int gradient_verification_frequency = options.integer("gradient_verification_frequency");
-  const std::string start = options.str("starting_point_strategy");
   niter = neval = ngeval = nhvec = 0;
   hvec_fd_products = hvec_fd_evals = 0;
   stateReplaced();
@@ -2015,7 +2057,7 @@ int InteriorPoint::optimize(const char *checkpoint) {
   phase_seconds.clear();
   user_seconds = 0.0;
   user_pending = 0;
-  if (!seq_lin && !qn && !use_diag_hessian) {
+  if (!opt.sequential_linear_method && !qn && !opt.use_diag_hessian) {
     if (ctx->rank == 0)
       fprintf(stderr,
               "ParOpt Error: Must use a sequential linear method if no quasi-Newton approximation "
@@ -2041,335 +2083,379 @@ int InteriorPoint::optimize(const char *checkpoint) {
     return fail_g;
   }
   iterate_flags.ac_valid = true;
-  if (start == "affine_step") {
+  if (opt.starting_point_strategy == "affine_step") {
     PO_TRY(initAffineStepMultipliers());
-  } else if (start == "least_squares_multipliers") {
+  } else if (opt.starting_point_strategy == "least_squares_multipliers") {
     PO_TRY(initLeastSquaresMultipliers());
   }
-  if (qn && !use_qnu) {  // :4569-4573
+  if (qn && !opt.use_quasi_newton_update) {  // :4569-4573
     if (qn->updateMult(x, vars.z.data(), has_w ? wvar[0] : nullptr) != 0) return PO_ERR_USER;
   }
   phaseEnd("init");
+  return PO_OK;
+}
 
-  double fobj_prev = 0.0, alpha_prev = 0.0, alpha_xprev = 0.0, alpha_zprev = 0.0, dm0_prev = 0.0;
-  double res_norm_prev = 0.0;
-  int no_merit_function_improvement = 0, line_search_test = 0, line_search_failed = 0;
-  char info[64];
-  memset(info, 0, sizeof(info));
+// The periodic work at the head of iteration k, in this order: the Hessian reset (qn_hessian_reset), the checkpoint and
+// the problem's writeOutput, the iteration callback, the gradient check.  A checkpoint that cannot be written is not
+// tried again (*checkpoint).
+int InteriorPoint::iterationHead(const RunOptions &opt, int k, const char **checkpoint, IterRecord &it) {
+  if (qn && !opt.sequential_linear_method && k > 0 && k % opt.hessian_reset_freq == 0 &&
+      opt.use_quasi_newton_update) {
+    resetQuasiNewton(it);
+  }
+  if (opt.write_output_frequency > 0 && k % opt.write_output_frequency == 0) {
+    if (*checkpoint) {
+      if (writeSolutionFile(*checkpoint) != PO_OK) *checkpoint = nullptr;
+    }
+    prob->writeOutput(k, x);
+  }
+  if (iter_cb) iter_cb(iter_cb_user, k);
+  // gradient_verification_frequency (:4522-4525, 4635-4639): finite-difference check of the user's gradients
+  if (opt.gradient_verification_frequency > 0 && (k % opt.gradient_verification_frequency) == 0) {
+    std::string rep;
+    PO_TRY(checkGradients(options.real("gradient_check_step_length"), &rep));
+    if (ctx->rank == 0) history += rep;
+  }
+  return PO_OK;
+}
+
+void InteriorPoint::resetQuasiNewton(IterRecord &it) {
+  qn->reset();
+  it.qn_hessian_reset = true;
+}
+
+// the dense part of the residual for `mu` (in res) and the four norms of the whole residual, as the last
+// computeResidual left its vector part
+void InteriorPoint::residualNorms(double mu, IterRecord &it) {
+  denseResidual(mu, res);
+  resNorms(res, &it.max_prime, &it.max_dual, &it.max_infeas, &it.res_norm);
+}
+
+// Complementarity + KKT residual + norms in ONE pass (:4656-4671), unless the last step update took it already, and
+// the barrier parameter of this iteration by the strategy in force (:4673-4762).  Owns barrier_param, the restart of
+// rho_penalty_search at a monotone reduction, spec_enabled, st.line_search_test, and sets it.rel_function_test,
+// it.comp, the four norms and it.monotone_barrier_converged.
+int InteriorPoint::updateBarrierAndNorms(const RunOptions &opt, int k, MajorState &st, IterRecord &it) {
+  it.rel_function_test = (st.alpha_xprev == 1.0 && st.alpha_zprev == 1.0 &&
+                          (fabs(fobj - st.fobj_prev) < opt.rel_func_tol * fabs(st.fobj_prev)));
+  if (st.no_merit_function_improvement) {
+    st.line_search_test += 1;
+  } else {
+    st.line_search_test = 0;
+  }
+  // (the inexact Newton step reads the 2-norms of the bound residuals, computeKKTGMRESStep: no shortcut there)
+  spec_enabled = st.barrier_strategy == Barrier::MONOTONE && norm_type == 0 && !has_w && !opt.use_hvec_product;
+  if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
+  iterate_flags.residual_cached = false;
+  it.comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
+  if (st.barrier_strategy == Barrier::COMP_FRACTION) {  // :4747-4762
+    barrier_param = options.real("monotone_barrier_fraction") * it.comp;
+    if (barrier_param < 0.1 * opt.abs_res_tol) barrier_param = 0.1 * opt.abs_res_tol;
+    PO_TRY(computeResidual(barrier_param, false));
+  }
+  residualNorms(barrier_param, it);
+  if (st.barrier_strategy == Barrier::MONOTONE && k > 0 &&
+      ((it.res_norm < 10.0 * barrier_param) || it.rel_function_test || (st.line_search_test >= 2))) {
+    it.monotone_barrier_converged = true;
+    if (barrier_param > 0.1 * opt.abs_res_tol) st.line_search_test = 0;
+    const double new_mu = nextMonotoneMu();
+    if (iterate_flags.spec_valid && spec_mu == new_mu && norm_type == 0) {
+      // the residual pass of this iterate took the two maxima for new_mu as well (the complementarity product
+      // and the bound count do not depend on mu): what computeResidual(new_mu, false) would produce
+      max_rzl = spec_max[0];
+      max_rzu = spec_max[1];
+      iterate_flags.spec_valid = false;
+    } else {
+      PO_TRY(computeResidual(new_mu, false));  // rx does not depend on mu
+    }
+    residualNorms(new_mu, it);
+    rho_penalty_search = options.real("min_rho_penalty_search");
+    barrier_param = new_mu;
+  }
+  phaseEnd("residual");
+  return PO_OK;
+}
+
+// the row of iteration k in the table (:4777-4801), with the header every ten rows and the problem's factor report
+void InteriorPoint::appendTableRow(int k, const MajorState &st, const IterRecord &it) {
+  if (ctx->rank != 0) return;
   char line[512];
+  if (k == 0 || options.integer("output_level") > 0) {  // :4767-4774
+    const char *inform = prob->sparseFactorInfo();
+    if (inform) history += std::string("MatInfo: ") + inform + "\n";
+  }
+  if (k % 10 == 0) {
+    snprintf(line, sizeof(line),
+             "\n%4s %4s %4s %4s %7s %7s %7s %12s %7s %7s %7s %7s %7s %8s %7s info\n", "iter",
+             "nobj", "ngrd", "nhvc", "alpha", "alphx", "alphz", "fobj", "|opt|", "|infes|",
+             "|dual|", "mu", "comp", "dmerit", "rho");
+    history += line;
+  }
+  if (k == 0) {
+    snprintf(line, sizeof(line),
+             "%4d %4d %4d %4d %7s %7s %7s %12.5e %7.1e %7.1e %7.1e %7.1e %7.1e %8s %7s %s\n", k,
+             neval, ngeval, nhvec, "--", "--", "--", fobj, it.max_prime, it.max_infeas, it.max_dual,
+             barrier_param, it.comp, "--", "--", st.info.c_str());
+  } else {
+    snprintf(line, sizeof(line),
+             "%4d %4d %4d %4d %7.1e %7.1e %7.1e %12.5e %7.1e %7.1e %7.1e %7.1e %7.1e %8.1e %7.1e %s\n",
+             k, neval, ngeval, nhvec, st.alpha_prev, st.alpha_xprev, st.alpha_zprev, fobj, it.max_prime,
+             it.max_infeas, it.max_dual, barrier_param, it.comp, st.dm0_prev, rho_penalty_search, st.info.c_str());
+  }
+  history += line;
+}
 
-  for (int k = 0; k < max_major_iters; k++, niter++) {
-    int qn_hessian_reset = 0;
-    if (qn && !seq_lin) {
-      if (k > 0 && k % hessian_reset_freq == 0 && use_qnu) {
-        qn->reset();
-        qn_hessian_reset = 1;
-      }
-    }
-    if (write_freq > 0 && k % write_freq == 0) {
-      if (checkpoint) {
-        if (writeSolutionFile(checkpoint) != PO_OK) checkpoint = nullptr;
-      }
-      prob->writeOutput(k, x);
-    }
-    if (iter_cb) iter_cb(iter_cb_user, k);
-    // gradient_verification_frequency (:4522-4525, 4635-4639): finite-difference check of the user's gradients
-    if (gradient_verification_frequency > 0 && (k % gradient_verification_frequency) == 0) {
-      std::string rep;
-      PO_TRY(checkGradients(options.real("gradient_check_step_length"), &rep));
-      if (ctx->rank == 0) history += rep;
-    }
-
-    const bool rel_function_test =
-        (alpha_xprev == 1.0 && alpha_zprev == 1.0 && (fabs(fobj - fobj_prev) < rel_func_tol * fabs(fobj_prev)));
-    if (no_merit_function_improvement) {
-      line_search_test += 1;
+// true when the run ends at iteration k (:4803-4818); the reason goes into the history
+bool InteriorPoint::stopTest(const RunOptions &opt, int k, const MajorState &st, const IterRecord &it) {
+  if (!(k > 0 && (barrier_param <= 0.1 * opt.abs_res_tol) &&
+        (it.res_norm < opt.abs_res_tol || it.rel_function_test || (st.line_search_test >= 2)))) {
+    return false;
+  }
+  if (ctx->rank == 0) {
+    if (it.rel_function_test) {
+      history += "\nParOpt: Successfully converged on relative function test\n";
+    } else if (st.line_search_test >= 2) {
+      history +=
+          "\nParOpt Warning: Current design point could not be improved. No barrier function "
+          "decrease in previous two iterations\n";
     } else {
-      line_search_test = 0;
+      history += "\nParOpt: Successfully converged to requested tolerance\n";
     }
-    // complementarity + KKT residual + norms in ONE pass (:4656-4671)
-    double max_prime = 0.0, max_dual = 0.0, max_infeas = 0.0, res_norm = 0.0;
-    int monotone_barrier_converged = 0;
-    double comp = 0.0;
-    // (the inexact Newton step reads the 2-norms of the bound residuals, computeKKTGMRESStep: no shortcut there)
-    spec_enabled = barrier_strategy == B_MONOTONE && norm_type == 0 && !has_w && !use_hvec_product;
-    if (!iterate_flags.residual_cached) PO_TRY(computeResidual(barrier_param, true));
-    iterate_flags.residual_cached = false;
-    comp = compFromSums(comp_prod, comp_count, vars, w_sums[0]);
-    if (barrier_strategy == B_MONOTONE) {
-      denseResidual(barrier_param, res);
-      resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
-      if (k > 0 && ((res_norm < 10.0 * barrier_param) || rel_function_test || (line_search_test >= 2))) {
-        monotone_barrier_converged = 1;
-      }
-      if (monotone_barrier_converged) {
-        if (barrier_param > 0.1 * abs_res_tol) line_search_test = 0;
-        const double mu_frac = options.real("monotone_barrier_fraction") * barrier_param;
-        const double mu_pow = pow(barrier_param, options.real("monotone_barrier_power"));
-        double new_mu = mu_frac;
-        if (mu_pow < mu_frac) new_mu = mu_pow;
-        if (new_mu < 0.1 * abs_res_tol) new_mu = 0.09999 * abs_res_tol;
-        if (iterate_flags.spec_valid && spec_mu == new_mu && norm_type == 0) {
-          // the residual pass of this iterate took the two maxima for new_mu as well (the complementarity product
-          // and the bound count do not depend on mu): what computeResidual(new_mu, false) would produce
-          max_rzl = spec_max[0];
-          max_rzu = spec_max[1];
-          iterate_flags.spec_valid = false;
-        } else {
-          PO_TRY(computeResidual(new_mu, false));  // rx does not depend on mu
-        }
-        denseResidual(new_mu, res);
-        resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
-        rho_penalty_search = options.real("min_rho_penalty_search");
-        barrier_param = new_mu;
-      }
-    } else if (barrier_strategy == B_MEHROTRA || barrier_strategy == B_MPC) {  // :4737-4746
-      denseResidual(barrier_param, res);
-      resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
-    } else {  // complementarity fraction (:4747-4762)
-      barrier_param = options.real("monotone_barrier_fraction") * comp;
-      if (barrier_param < 0.1 * abs_res_tol) barrier_param = 0.1 * abs_res_tol;
-      PO_TRY(computeResidual(barrier_param, false));
-      denseResidual(barrier_param, res);
-      resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
-    }
-    phaseEnd("residual");
+  }
+  return true;
+}
 
-    if (ctx->rank == 0) {  // iteration table :4777-4801
-      if (k == 0 || options.integer("output_level") > 0) {  // :4767-4774
-        const char *inform = prob->sparseFactorInfo();
-        if (inform) history += std::string("MatInfo: ") + inform + "\n";
-      }
-      if (k % 10 == 0) {
-        snprintf(line, sizeof(line),
-                 "\n%4s %4s %4s %4s %7s %7s %7s %12s %7s %7s %7s %7s %7s %8s %7s info\n", "iter",
-                 "nobj", "ngrd", "nhvc", "alpha", "alphx", "alphz", "fobj", "|opt|", "|infes|",
-                 "|dual|", "mu", "comp", "dmerit", "rho");
-        history += line;
-      }
-      if (k == 0) {
-        snprintf(line, sizeof(line),
-                 "%4d %4d %4d %4d %7s %7s %7s %12.5e %7.1e %7.1e %7.1e %7.1e %7.1e %8s %7s %s\n", k,
-                 neval, ngeval, nhvec, "--", "--", "--", fobj, max_prime, max_infeas, max_dual,
-                 barrier_param, comp, "--", "--", info);
-      } else {
-        snprintf(line, sizeof(line),
-                 "%4d %4d %4d %4d %7.1e %7.1e %7.1e %12.5e %7.1e %7.1e %7.1e %7.1e %7.1e %8.1e %7.1e %s\n",
-                 k, neval, ngeval, nhvec, alpha_prev, alpha_xprev, alpha_zprev, fobj, max_prime,
-                 max_infeas, max_dual, barrier_param, comp, dm0_prev, rho_penalty_search, info);
-      }
-      history += line;
-    }
+// Inexact Newton-Krylov step with exact Hessian-vector products (:4853-4900), tried once the three norms are below
+// nk_switch_tol and the Eisenstat-Walker tolerance below max_gmres_rtol.  Owns inexact_newton_step (true: the step is
+// in px, pzl, pzu, step) and it.gmres_iters (negative: no descent direction, the quasi-Newton step follows).
+int InteriorPoint::newtonKrylovAttempt(const RunOptions &opt, const MajorState &st, IterRecord &it) {
+  inexact_newton_step = false;
+  if (!opt.use_hvec_product) return PO_OK;
+  const double gmres_rtol =
+      st.res_norm_prev == 0.0 ? 1e300
+                              : options.real("eisenstat_walker_gamma") *
+                                    pow(it.res_norm / st.res_norm_prev, options.real("eisenstat_walker_alpha"));
+  const double nk = options.real("nk_switch_tol");
+  if (it.max_prime < nk && it.max_dual < nk && it.max_infeas < nk && gmres_rtol < options.real("max_gmres_rtol")) {
+    const bool precon_qn = !(opt.sequential_linear_method || !options.integer("use_qn_gmres_precon"));
+    PO_TRY(setUpKKTSystem(precon_qn));
+    PO_TRY(computeKKTGMRESStep(gmres_rtol, options.real("gmres_atol"), precon_qn, it.tau, &it.gmres_iters));
+    phaseEnd("gmres_step");
+    // negative: GMRES did not produce a descent direction (:4883-4894), fall back to the quasi-Newton step
+    if (it.gmres_iters > 0) inexact_newton_step = true;
+  }
+  return PO_OK;
+}
 
-    int converged = 0;
-    if (k > 0 && (barrier_param <= 0.1 * abs_res_tol) &&
-        (res_norm < abs_res_tol || rel_function_test || (line_search_test >= 2))) {
-      if (ctx->rank == 0) {
-        if (rel_function_test) {
-          history += "\nParOpt: Successfully converged on relative function test\n";
-        } else if (line_search_test >= 2) {
-          history +=
-              "\nParOpt Warning: Current design point could not be improved. No barrier function "
-              "decrease in previous two iterations\n";
-        } else {
-          history += "\nParOpt: Successfully converged to requested tolerance\n";
-        }
-      }
-      converged = 1;
+// The kind of step this iteration takes (:4920-4949); the diagonal Hessian is evaluated here when that is the kind.
+int InteriorPoint::chooseStepKind(const RunOptions &opt, const MajorState &st, IterRecord &it) {
+  const bool seq_lin = opt.sequential_linear_method;
+  if (inexact_newton_step) {
+    it.kind = StepKind::INEXACT_NEWTON;  // the step is already in place
+  } else if (!seq_lin && st.line_search_failed && !opt.use_quasi_newton_update) {
+    // a fixed quasi-Newton approximation whose line search failed (:4923-4939): sequential linear
+    // step, or only the diagonal b0 of the approximation when that is positive
+    it.kind = (qn && qn->diag() > 0.0) ? StepKind::DIAG_QUASI_NEWTON : StepKind::SEQ_LINEAR;
+  } else if (opt.use_diag_hessian && !seq_lin) {  // :4940-4948
+    // (an else-if chain in the reference, :4920-4949: under the sequential linear method the diagonal is never
+    // evaluated -- hdiag keeps its initial zeros, which setUpKKTDiagSystem and addKKTResStep then use)
+    it.kind = StepKind::DIAG_HESSIAN;
+    if (prob->evalHessianDiag(x, vars.z.data(), has_w ? wvar[0] : nullptr, hdiag) != 0) {
+      fprintf(stderr, "ParOpt: Hessian diagonal evaluation failed\n");
+      return PO_ERR_USER;
     }
-    if (converged) {
-      flushHistory();
-      return 0;
-    }
+  } else {
+    it.kind = seq_lin ? StepKind::SEQ_LINEAR : StepKind::QUASI_NEWTON;
+  }
+  return PO_OK;
+}
 
-    const bool mehrotra = (barrier_strategy == B_MEHROTRA || barrier_strategy == B_MPC);
+// The step of the chosen kind (an inexact Newton step is in place already), the step check, and the step lengths:
+// it.tau (Mehrotra's rule replaces it), it.alpha_x, it.alpha_z, it.ceq_step; lean_step_allowed around the solve.
+int InteriorPoint::computeStep(const RunOptions &opt, int k, const MajorState &st, IterRecord &it) {
+  if (it.kind != StepKind::INEXACT_NEWTON) {
+    const bool use_qn = it.kind == StepKind::QUASI_NEWTON;
+    const double rhs_mu = mehrotra(st) ? 0.0 : barrier_param;  // of the solve that follows
+    PO_TRY(setUpKKTSystem(use_qn, it.kind == StepKind::DIAG_QUASI_NEWTON, &rhs_mu));
+    phaseEnd("setup_kkt");
+    if (!mehrotra(st)) {
+      // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
+      lean_step_allowed = qn && opt.use_quasi_newton_update && use_qn && forms.analytic_panel_dots &&
+                          forms.fuse_mult_update && !opt.use_hvec_product && !opt.use_diag_hessian;
+      const int step_rc = computeKKTStepWithRefinement(barrier_param, use_qn, it.tau);
+      lean_step_allowed = false;
+      PO_TRY(step_rc);
+    } else {
+      PO_TRY(mehrotraStep(use_qn, it.comp, st.barrier_strategy == Barrier::MPC, opt.min_fraction_to_boundary,
+                          opt.abs_res_tol, &it.tau));
+    }
+  }
+  phaseEnd("kkt_step");
+  // step_verification_frequency (:5056-5073): block maxima of the linearised KKT residual at the step
+  if (opt.step_verification_frequency > 0 && (k % opt.step_verification_frequency) == 0 && !inexact_newton_step) {
+    if (st.barrier_strategy == Barrier::MPC && ctx->rank == 0)
+      history += "Note: the step check is inconsistent with the predictor-corrector step (corrector terms)\n";
+    PO_TRY(checkKKTStep(k, barrier_param));
+  }
+  PO_TRY(scaleKKTStep(it.tau, it.comp, &it.alpha_x, &it.alpha_z, &it.ceq_step, inexact_newton_step));
+  phaseEnd("scale_step");
+  return PO_OK;
+}
+
+// merit function and its derivative along the scaled step; the derivative is what the next table row prints
+int InteriorPoint::meritDerivative(MajorState &st, const IterRecord &it, double *m0, double *dm0) {
+  PO_TRY(evalMeritInitDeriv(it.alpha_x, m0, dm0));
+  st.dm0_prev = *dm0;
+  return PO_OK;
+}
+
+// Globalisation, first form: the merit derivative is inside the function precision, the full step is taken without a
+// line search (line_search_skipped; line_fail says whether the objective moved).
+int InteriorPoint::stepWithLineSearchSkipped(const RunOptions &opt, const MajorState &st, IterRecord &it) {
+  const double fprec = opt.function_precision;
+  it.line_search_skipped = true;
+  PO_TRY(computeStepAndUpdate(it.alpha, true, &it.update_type));
+  phaseEnd("step_update");
+  if ((st.fobj_prev + fprec <= fobj) && (fobj + fprec <= st.fobj_prev)) it.line_fail = LS_NO_IMPROVEMENT;
+  return PO_OK;
+}
+
+// The step is no descent direction of the merit function (:5130-5173): the quasi-Newton approximation is reset and the
+// step, its lengths and the merit derivative are taken again (qn_hessian_reset, retried_after_reset, the norms).
+int InteriorPoint::retryAfterReset(MajorState &st, IterRecord &it, double *m0, double *dm0) {
+  if (qn) resetQuasiNewton(it);
+  it.retried_after_reset = true;
+  PO_TRY(computeResidual(barrier_param, true));
+  residualNorms(barrier_param, it);
+  PO_TRY(setUpKKTSystem(true, false, &barrier_param));
+  PO_TRY(computeKKTStepWithRefinement(barrier_param, true, it.tau));
+  PO_TRY(scaleKKTStep(it.tau, it.comp, &it.alpha_x, &it.alpha_z, &it.ceq_step));
+  PO_TRY(meritDerivative(st, it, m0, dm0));
+  phaseEnd("qn_reset_step");
+  return PO_OK;
+}
+
+// Globalisation, second form: the line search, after retryAfterReset where the step is no descent direction, and the
+// step update unless the search failed (it.alpha, it.line_fail, it.update_type).
+int InteriorPoint::stepByLineSearch(const RunOptions &opt, MajorState &st, IterRecord &it, double m0, double dm0) {
+  if (dm0 >= 0.0) PO_TRY(retryAfterReset(st, it, &m0, &dm0));
+  if (dm0 >= 0.0) {
+    it.line_fail = LS_FAILURE;
+    return PO_OK;
+  }
+  double px_norm = 0.0;
+  if (step_flags.merit_cache_valid) {
+    px_norm = merit_cache.px_amax;
+  } else if (step_flags.px_amax_valid) {
+    px_norm = px_amax_w;
+  } else {
+    PO_TRY(k_reduce1(ctx, RED_AMAX, px->d, nullptr, n, &px_norm));
+  }
+  px_norm *= fabs(sx);
+  double alpha_min = 1.0;
+  if (px_norm != 0.0) alpha_min = opt.function_precision / px_norm;
+  if (alpha_min > 0.5) alpha_min = 0.5;
+  PO_TRY(lineSearch(alpha_min, &it.alpha, m0, dm0, &it.line_fail));
+  phaseEnd("line_search");
+  if (px_norm < opt.design_precision) it.line_fail |= LS_SHORT_STEP;
+  if (!(it.line_fail & LS_FAILURE)) {
+    PO_TRY(computeStepAndUpdate(it.alpha, false, &it.update_type));
+    phaseEnd("step_update");
+  }
+  return PO_OK;
+}
+
+// Globalisation, third form (use_line_search = 0): the full step, then the merit function at the new point to say
+// whether it improved (it.line_fail).
+int InteriorPoint::stepWithoutLineSearch(const RunOptions &opt, IterRecord &it, double m0, double dm0) {
+  const double fprec = opt.function_precision;
+  it.line_fail = LS_SUCCESS;
+  PO_TRY(computeStepAndUpdate(it.alpha, true, &it.update_type));
+  // merit at the new point (:5236-5237): barrier sums of x itself (a zero step from x)
+  double bs[2];
+  PO_TRY(k_trial(ctx, bounds(), px->d, 0.0, opt.design_precision, n, xt->d, bs));
+  double wsums[5];
+  if (has_w) {
+    const double *cw = nullptr;
+    PO_TRY(sparseConAtIterate(&cw));
+    PO_TRY(k_w_trial(ctx, wv(), wp(), 0.0, opt.design_precision, gsw->d, gtw->d, cw, nw, wsums));
+  }
+  const double m1 = evalMeritFromSums(fobj, cvals.data(), vars.s.data(), vars.t.data(), bs[0], bs[1],
+                                      has_w ? wsums : nullptr);
+  if ((m1 <= m0 + fprec) && (m1 + fprec >= m0)) {
+    it.line_fail |= LS_NO_IMPROVEMENT;
+  } else if (fabs(dm0) <= fprec) {
+    it.line_fail = LS_NO_IMPROVEMENT;
+  }
+  phaseEnd("step_update");
+  return PO_OK;
+}
+
+// What the next iteration inherits: the merit-improvement and line-search flags, the step lengths, the reset of the
+// approximation after a failed line search (qn_hessian_reset), the info column (:5272-5322) and, at the first monotone
+// reduction of the barrier parameter, the strategy of the input.
+void InteriorPoint::closeIteration(const RunOptions &opt, MajorState &st, IterRecord &it) {
+  st.no_merit_function_improvement =
+      ((it.line_fail & LS_NO_IMPROVEMENT) || (it.line_fail & LS_MIN_STEP) ||
+       (it.line_fail & LS_SHORT_STEP) || (it.line_fail & LS_FAILURE));
+  st.line_search_failed = (it.line_fail & LS_FAILURE) ? 1 : 0;
+  st.alpha_prev = it.alpha;
+  st.alpha_xprev = it.alpha_x;
+  st.alpha_zprev = it.alpha_z;
+  if (qn && opt.use_quasi_newton_update && (it.line_fail & LS_FAILURE)) resetQuasiNewton(it);
+  std::string &s = st.info;
+  s.clear();
+  if (it.gmres_iters != 0) s += "iNK" + std::to_string(it.gmres_iters) + " ";
+  if (it.update_type == 1) s += "dampH ";
+  else if (it.update_type == 2) s += "skipH ";
+  if (it.qn_hessian_reset) s += "resetH ";
+  if (it.line_fail & LS_FAILURE) s += "LFail ";
+  if (it.line_fail & LS_MIN_STEP) s += "LMnStp ";
+  if (it.line_fail & LS_MAX_ITERS) s += "LMxItr ";
+  if (it.line_fail & LS_NO_IMPROVEMENT) s += "LNoImprv ";
+  // (SLP marks the fall-back of a fixed approximation, not the method the options chose)
+  if (it.kind == StepKind::SEQ_LINEAR && !opt.sequential_linear_method) s += "SLP ";
+  if (it.kind == StepKind::DIAG_QUASI_NEWTON || it.retried_after_reset) s += "DQN ";
+  if (it.line_search_skipped) s += "LSkip ";
+  if (it.ceq_step) s += "cmpEq ";
+  if (s.size() > 63) s.resize(63);  // the column is 63 characters wide
+  if (it.monotone_barrier_converged) st.barrier_strategy = opt.barrier_strategy;
+}
+
+int InteriorPoint::optimize(const char *checkpoint) {
+  PO_TRY(uploadLiveMirrors());
+  PO_TRY(createQuasiNewton());
+  PO_TRY(refreshQuasiNewton());
+  const RunOptions opt = readRunOptions();
+  PO_TRY(startRun(opt));
+  MajorState st;
+  for (int k = 0; k < opt.max_major_iters; k++, niter++) {
+    IterRecord it;
+    PO_TRY(iterationHead(opt, k, &checkpoint, it));
+    PO_TRY(updateBarrierAndNorms(opt, k, st, it));
+    appendTableRow(k, st, it);
+    if (stopTest(opt, k, st, it)) break;
     // (what the first solve of the NEXT iteration will most likely take as its barrier parameter: see spec_dt_valid)
-    spec_dt_mu = mehrotra ? 0.0 : barrier_param;
-    double tau = min_frac;
-    if (1.0 - barrier_param >= tau) tau = 1.0 - barrier_param;
-
-    // inexact Newton-Krylov step with exact Hessian-vector products (:4853-4900)
-    int gmres_iters = 0;
-    inexact_newton_step = false;
-    if (use_hvec_product) {
-      const double gmres_rtol =
-          res_norm_prev == 0.0 ? 1e300
-                               : options.real("eisenstat_walker_gamma") *
-                                     pow(res_norm / res_norm_prev, options.real("eisenstat_walker_alpha"));
-      const double nk = options.real("nk_switch_tol");
-      if (max_prime < nk && max_dual < nk && max_infeas < nk && gmres_rtol < options.real("max_gmres_rtol")) {
-        const bool precon_qn = !(seq_lin || !options.integer("use_qn_gmres_precon"));
-        PO_TRY(setUpKKTSystem(precon_qn));
-        PO_TRY(computeKKTGMRESStep(gmres_rtol, options.real("gmres_atol"), precon_qn, tau, &gmres_iters));
-        phaseEnd("gmres_step");
-        // negative: GMRES did not produce a descent direction (:4883-4894), fall back to the quasi-Newton step
-        if (gmres_iters > 0) inexact_newton_step = true;
-      }
-    }
-    fobj_prev = fobj;
-    res_norm_prev = res_norm;
-    int seq_linear_step = 0, diagonal_quasi_newton_step = 0;
-    bool use_qn = !seq_lin;
-    if (inexact_newton_step) {
-      // the step is already in place
-    } else if (!seq_lin && line_search_failed && !use_qnu) {
-      // a fixed quasi-Newton approximation whose line search failed (:4923-4939): sequential linear
-      // step, or only the diagonal b0 of the approximation when that is positive
-      use_qn = false;
-      seq_linear_step = 1;
-      if (qn && qn->diag() > 0.0) {
-        seq_linear_step = 0;
-        diagonal_quasi_newton_step = 1;
-      }
-    } else if (use_diag_hessian && !seq_lin) {  // :4940-4948
-      // (an else-if chain in the reference, :4920-4949: under the sequential linear method the diagonal is never
-      // evaluated -- hdiag keeps its initial zeros, which setUpKKTDiagSystem and addKKTResStep then use)
-      use_qn = false;
-      if (prob->evalHessianDiag(x, vars.z.data(), has_w ? wvar[0] : nullptr, hdiag) != 0) {
-        fprintf(stderr, "ParOpt: Hessian diagonal evaluation failed\n");
-        return PO_ERR_USER;
-      }
-    }
-
-    if (!inexact_newton_step) {  // (otherwise computeKKTGMRESStep left the step in (px, pzl, pzu, step))
-      const double rhs_mu = mehrotra ? 0.0 : barrier_param;  // of the solve that follows
-      PO_TRY(setUpKKTSystem(use_qn, diagonal_quasi_newton_step != 0, &rhs_mu));
-      phaseEnd("setup_kkt");
-      if (!mehrotra) {
-        // every consumer of (pzl, pzu) after this solve is the fused multiplier update of computeStepAndUpdate
-        lean_step_allowed = qn && use_qnu && use_qn && !diagonal_quasi_newton_step && forms.analytic_panel_dots &&
-                            forms.fuse_mult_update && !use_hvec_product && !use_diag_hessian && !seq_lin;
-        const int step_rc = computeKKTStepWithRefinement(barrier_param, use_qn, tau);
-        lean_step_allowed = false;
-        PO_TRY(step_rc);
-      } else {
-        PO_TRY(mehrotraStep(use_qn, comp, barrier_strategy == B_MPC, min_frac, abs_res_tol, &tau));
-      }
-    }
-    phaseEnd("kkt_step");
-    // step_verification_frequency (:5056-5073): block maxima of the linearised KKT residual at the step
-    if (step_verification_frequency > 0 && (k % step_verification_frequency) == 0 && !inexact_newton_step) {
-      if (barrier_strategy == B_MPC && ctx->rank == 0)
-        history += "Note: the step check is inconsistent with the predictor-corrector step (corrector terms)\n";
-      PO_TRY(checkKKTStep(k, barrier_param));
-    }
-
-    double alpha_x = 1.0, alpha_z = 1.0;
-    int ceq_step = 0;
-    PO_TRY(scaleKKTStep(tau, comp, &alpha_x, &alpha_z, &ceq_step, inexact_newton_step));
-    phaseEnd("scale_step");
-
-    double alpha = 1.0;
-    int line_fail = LS_FAILURE;
-    int update_type = 0;
-    int line_search_skipped = 0;
-    no_merit_function_improvement = 0;
-
-    if (use_line_search) {
-      double m0 = 0.0, dm0 = 0.0;
-      PO_TRY(evalMeritInitDeriv(alpha_x, &m0, &dm0));
-      phaseEnd("merit_deriv");
-      dm0_prev = dm0;
-      if (dm0 >= 0.0 && dm0 <= fprec) {
-        line_search_skipped = 1;
-        PO_TRY(computeStepAndUpdate(alpha, 1, 1, &update_type));
-        phaseEnd("step_update");
-        if ((fobj_prev + fprec <= fobj) && (fobj + fprec <= fobj_prev)) line_fail = LS_NO_IMPROVEMENT;
-      } else {
-        if (dm0 >= 0.0) {  // :5130-5173
-          if (qn) {
-            qn_hessian_reset = 1;
-            qn->reset();
-          }
-          diagonal_quasi_newton_step = 1;
-          PO_TRY(computeResidual(barrier_param, true));
-          denseResidual(barrier_param, res);
-          resNorms(res, &max_prime, &max_dual, &max_infeas, &res_norm);
-          PO_TRY(setUpKKTSystem(true, false, &barrier_param));
-          PO_TRY(computeKKTStepWithRefinement(barrier_param, true, tau));
-          PO_TRY(scaleKKTStep(tau, comp, &alpha_x, &alpha_z, &ceq_step));
-          PO_TRY(evalMeritInitDeriv(alpha_x, &m0, &dm0));
-          dm0_prev = dm0;
-          phaseEnd("qn_reset_step");
-        }
-        if (dm0 >= 0.0) {
-          line_fail = LS_FAILURE;
-        } else {
-          double px_norm = 0.0;
-          if (step_flags.merit_cache_valid) {
-            px_norm = merit_cache.px_amax;
-          } else if (step_flags.px_amax_valid) {
-            px_norm = px_amax_w;
-          } else {
-            PO_TRY(k_reduce1(ctx, RED_AMAX, px->d, nullptr, n, &px_norm));
-          }
-          px_norm *= fabs(sx);
-          double alpha_min = 1.0;
-          if (px_norm != 0.0) alpha_min = fprec / px_norm;
-          if (alpha_min > 0.5) alpha_min = 0.5;
-          PO_TRY(lineSearch(alpha_min, &alpha, m0, dm0, &line_fail));
-          phaseEnd("line_search");
-          if (px_norm < design_precision) line_fail |= LS_SHORT_STEP;
-          if (!(line_fail & LS_FAILURE)) {
-            PO_TRY(computeStepAndUpdate(alpha, 0, 1, &update_type));
-            phaseEnd("step_update");
-          }
-        }
-      }
+    spec_dt_mu = mehrotra(st) ? 0.0 : barrier_param;
+    it.tau = fractionToBoundary(barrier_param, opt.min_fraction_to_boundary);
+    PO_TRY(newtonKrylovAttempt(opt, st, it));
+    st.fobj_prev = fobj;
+    st.res_norm_prev = it.res_norm;
+    PO_TRY(chooseStepKind(opt, st, it));
+    PO_TRY(computeStep(opt, k, st, it));
+    double m0 = 0.0, dm0 = 0.0;
+    PO_TRY(meritDerivative(st, it, &m0, &dm0));
+    if (!opt.use_line_search) {
+      PO_TRY(stepWithoutLineSearch(opt, it, m0, dm0));
     } else {
-      double m0 = 0.0, dm0 = 0.0;
-      PO_TRY(evalMeritInitDeriv(alpha_x, &m0, &dm0));
-      dm0_prev = dm0;
-      line_fail = LS_SUCCESS;
-      PO_TRY(computeStepAndUpdate(alpha, 1, 1, &update_type));
-      // merit at the new point (:5236-5237): barrier sums of x itself (a zero step from x)
-      double bs[2];
-      PO_TRY(k_trial(ctx, bounds(), px->d, 0.0, design_precision, n, xt->d, bs));
-      double wsums[5];
-      if (has_w) {
-        const double *cw = nullptr;
-        PO_TRY(sparseConAtIterate(&cw));
-        PO_TRY(k_w_trial(ctx, wv(), wp(), 0.0, design_precision, gsw->d, gtw->d, cw, nw, wsums));
+      phaseEnd("merit_deriv");
+      if (dm0 >= 0.0 && dm0 <= opt.function_precision) {
+        PO_TRY(stepWithLineSearchSkipped(opt, st, it));
+      } else {
+        PO_TRY(stepByLineSearch(opt, st, it, m0, dm0));
       }
-      const double m1 = evalMeritFromSums(fobj, cvals.data(), vars.s.data(), vars.t.data(), bs[0], bs[1],
-                                          has_w ? wsums : nullptr);
-      if ((m1 <= m0 + fprec) && (m1 + fprec >= m0)) {
-        line_fail |= LS_NO_IMPROVEMENT;
-      } else if (fabs(dm0) <= fprec) {
-        line_fail = LS_NO_IMPROVEMENT;
-      }
-      phaseEnd("step_update");
     }
-
-    no_merit_function_improvement =
-        ((line_fail & LS_NO_IMPROVEMENT) || (line_fail & LS_MIN_STEP) ||
-         (line_fail & LS_SHORT_STEP) || (line_fail & LS_FAILURE));
-    line_search_failed = (line_fail & LS_FAILURE) ? 1 : 0;
-    alpha_prev = alpha;
-    alpha_xprev = alpha_x;
-    alpha_zprev = alpha_z;
-    if (qn && use_qnu && (line_fail & LS_FAILURE)) {
-      qn_hessian_reset = 1;
-      qn->reset();
-    }
-    {  // info tokens :5272-5322
-      std::string s;
-      if (gmres_iters != 0) s += "iNK" + std::to_string(gmres_iters) + " ";
-      if (update_type == 1) s += "dampH ";
-      else if (update_type == 2) s += "skipH ";
-      if (qn_hessian_reset) s += "resetH ";
-      if (line_fail & LS_FAILURE) s += "LFail ";
-      if (line_fail & LS_MIN_STEP) s += "LMnStp ";
-      if (line_fail & LS_MAX_ITERS) s += "LMxItr ";
-      if (line_fail & LS_NO_IMPROVEMENT) s += "LNoImprv ";
-      if (seq_linear_step) s += "SLP ";
-      if (diagonal_quasi_newton_step) s += "DQN ";
-      if (line_search_skipped) s += "LSkip ";
-      if (ceq_step) s += "cmpEq ";
-      memset(info, 0, sizeof(info));
-      strncpy(info, s.c_str(), sizeof(info) - 1);
-    }
-    if (monotone_barrier_converged) barrier_strategy = input_strategy;
+    closeIteration(opt, st, it);
   }
   flushHistory();
   return 0;

@@ -435,8 +435,78 @@ class InteriorPoint {
   int evalMeritInitDeriv(double max_x, double *merit, double *pmerit);
   double evalMeritFromSums(double fk, const double *ck, const double *sk, const double *tk,
                            double pos, double neg, const double *wsums = nullptr) const;
+  struct TrialSums {  // of one trial point of the line search (evalTrial)
+    double sums[2], wsums[5];  // barrier sums of the design block, slack sums of the sparse blocks
+    int fail_obj;              // what evalObjCon returned
+  };
+  int evalTrial(double alpha, bool with_sparse, double eps, double *sq, TrialSums &t);
   int lineSearch(double alpha_min, double *alpha, double m0, double dm0, int *fail);
-  int computeStepAndUpdate(double alpha, int eval_obj_con, int perform_qn_update, int *update_type);
+  // computeStepAndUpdate and its parts (form_point: the line search did not form this point)
+  struct UpdatePlan {  // which pass carries the multiplier step and the brackets of y_qn: set by updateMultipliers
+    bool do_qn = false, fast_yqn = false, fuse_upd = false, fuse_upd_noqn = false;
+    MultUpdate upd;
+  };
+  int computeStepAndUpdate(double alpha, bool form_point, int *update_type);
+  int updateMultipliers(double alpha, double eps, UpdatePlan &plan);
+  void updateDenseVariables(double alpha, double eps);
+  int acceptTrialPoint(double alpha, bool form_point, double eps);
+  int evalGradientAtIterate();
+  int quasiNewtonUpdate(double alpha, const UpdatePlan &plan, int *update_type);
+
+  // ---- optimize() as a sequence of stages (ip.cpp, "optimize") ----
+  enum class Barrier { MONOTONE, MEHROTRA, MPC, COMP_FRACTION };
+  enum class StepKind { INEXACT_NEWTON, QUASI_NEWTON, SEQ_LINEAR, DIAG_QUASI_NEWTON, DIAG_HESSIAN };
+  // The options optimize() reads ONCE, when it starts.  Every other option is read where it is used, each time it is
+  // used, and stays so: an iteration callback may call setOption during a run (monotone_barrier_fraction / _power,
+  // the Eisenstat-Walker pair, nk_switch_tol, max_gmres_rtol, gmres_atol, use_qn_gmres_precon, output_level,
+  // gradient_check_step_length, min_rho_penalty_search, rel_bound_barrier and what lineSearch / computeStepAndUpdate
+  // read).
+  struct RunOptions {
+    double abs_res_tol, rel_func_tol, function_precision, design_precision, min_fraction_to_boundary;
+    Barrier barrier_strategy;  // of the input; a run starts monotone and switches at the first barrier reduction
+    bool use_hvec_product, use_diag_hessian, use_quasi_newton_update, sequential_linear_method, use_line_search;
+    int max_major_iters, hessian_reset_freq, write_output_frequency, step_verification_frequency,
+        gradient_verification_frequency;
+    std::string starting_point_strategy;
+  };
+  RunOptions readRunOptions() const;
+  struct MajorState {  // what one major iteration hands to the next
+    double fobj_prev = 0.0, alpha_prev = 0.0, alpha_xprev = 0.0, alpha_zprev = 0.0, dm0_prev = 0.0;
+    double res_norm_prev = 0.0;
+    int no_merit_function_improvement = 0, line_search_test = 0, line_search_failed = 0;
+    std::string info;  // the tokens of the last iteration, as the next table row prints them
+    Barrier barrier_strategy = Barrier::MONOTONE;  // always start monotone (:4427-4441)
+  };
+  struct IterRecord {  // what one major iteration decides and its table row / info column report
+    bool rel_function_test = false;
+    double max_prime = 0.0, max_dual = 0.0, max_infeas = 0.0, res_norm = 0.0, comp = 0.0, tau = 0.0;
+    StepKind kind = StepKind::QUASI_NEWTON;
+    int gmres_iters = 0;
+    double alpha = 1.0, alpha_x = 1.0, alpha_z = 1.0;
+    int ceq_step = 0, line_fail = 2 /* LS_FAILURE */, update_type = 0;
+    bool monotone_barrier_converged = false, qn_hessian_reset = false, line_search_skipped = false;
+    bool retried_after_reset = false;  // retryAfterReset ran: reported as a diagonal quasi-Newton step (:5130-5173)
+  };
+  bool mehrotra(const MajorState &st) const {
+    return st.barrier_strategy == Barrier::MEHROTRA || st.barrier_strategy == Barrier::MPC;
+  }
+  int uploadLiveMirrors();
+  int startRun(const RunOptions &opt);
+  int iterationHead(const RunOptions &opt, int k, const char **checkpoint, IterRecord &it);
+  void residualNorms(double mu, IterRecord &it);
+  int updateBarrierAndNorms(const RunOptions &opt, int k, MajorState &st, IterRecord &it);
+  void appendTableRow(int k, const MajorState &st, const IterRecord &it);
+  bool stopTest(const RunOptions &opt, int k, const MajorState &st, const IterRecord &it);
+  int newtonKrylovAttempt(const RunOptions &opt, const MajorState &st, IterRecord &it);
+  int chooseStepKind(const RunOptions &opt, const MajorState &st, IterRecord &it);
+  int computeStep(const RunOptions &opt, int k, const MajorState &st, IterRecord &it);
+  void resetQuasiNewton(IterRecord &it);
+  int meritDerivative(MajorState &st, const IterRecord &it, double *m0, double *dm0);
+  int stepWithLineSearchSkipped(const RunOptions &opt, const MajorState &st, IterRecord &it);
+  int retryAfterReset(MajorState &st, IterRecord &it, double *m0, double *dm0);
+  int stepByLineSearch(const RunOptions &opt, MajorState &st, IterRecord &it, double m0, double dm0);
+  int stepWithoutLineSearch(const RunOptions &opt, IterRecord &it, double m0, double dm0);
+  void closeIteration(const RunOptions &opt, MajorState &st, IterRecord &it);
   void phaseBegin();
   void phaseEnd(const char *name);
   double phase_t0;

@@ -37,7 +37,8 @@ def info_tokens(text):
     return toks
 
 
-def run_gpu(ctx, case, want_vectors=False):
+def build_gpu(ctx, case):
+    """(problem, solver) of a golden's case record, not yet run (tools/ip_digest.py imports this half)"""
     import paropt_amd as pa
 
     a = case["args"]
@@ -54,7 +55,11 @@ def run_gpu(ctx, case, want_vectors=False):
         prob.setBoundsMode(a["bounds_mode"])
     opts = ip_options_from_case(case)
     opts["write_output_frequency"] = 0
-    ip = pa.InteriorPoint(prob, opts)
+    return prob, pa.InteriorPoint(prob, opts)
+
+
+def run_gpu(ctx, case, want_vectors=False):
+    prob, ip = build_gpu(ctx, case)
     snaps = []
 
     def cb(k):
@@ -1288,7 +1293,35 @@ ON_RECORD = {
     "config5": dict(tr=dict(problem="quadratic", n=2001, c=4, eig=(10, 0, 0, 2.0),
                             opts={"qn_subspace_size": 10, "tr_max_iterations": 4, "max_major_iters": 200}),
                     launches=3709, syncs=1368),
+    # One case per branch of the driver (optimize(), lineSearch(), computeStepAndUpdate()): a golden's own case record,
+    # with `extra` options where no golden takes the branch; `tokens`: what the info column has to show for the case to
+    # be still on its branch.  launches / syncs: printed by tools/ip_digest.py with the library of the commit BEFORE
+    # optimize() was cut into stages (profiles/r27_ip_digest_parent.jsonl).
+    "line_search_failure_reset_rebuilt_trial": dict(golden="ip_quadratic_clamp_n200_c2",
+                                                    tokens=("LFail", "resetH", "LMxItr"), launches=1225, syncs=340),
+    "newton_krylov_min_step": dict(golden="ip_convex_hvec_noprecon_n200_c2", tokens=("iNK", "LMnStp", "skipH"),
+                                   launches=19409, syncs=6157),
+    "no_line_search": dict(golden="ip_quadratic_nolinesearch_n200_c2", launches=877, syncs=291),
+    "complementarity_fraction": dict(golden="ip_quadratic_compfrac_n200_c2", tokens=("LNoImprv",),
+                                     launches=1061, syncs=333),
+    "mehrotra_comp_equal_step": dict(golden="ip_rosenbrock_mehrotra_n100", tokens=("cmpEq",), launches=717, syncs=248),
+    "damped_update": dict(golden="ip_convex_nolower_n200_c2", extra={"qn_update_type": "damped_update"},
+                          tokens=("dampH",), launches=509, syncs=148),
+    "fixed_lbfgs_diagonal_step": dict(golden="ip_quadratic_clamp_n200_c2",
+                                      extra={"use_quasi_newton_update": 0, "max_line_iters": 1},
+                                      tokens=("DQN", "LFail"), launches=578, syncs=210),
+    "no_approximation_sequential_linear_step": dict(golden="ip_quadratic_clamp_n200_c2",
+                                                    extra={"use_quasi_newton_update": 0, "max_line_iters": 1,
+                                                           "qn_type": "none", "use_diag_hessian": 1},
+                                                    tokens=("SLP", "LFail"), launches=1005, syncs=330),
 }
+
+
+def golden_case(name, **extra):
+    """the case record of a golden, with interior-point options added or replaced"""
+    case = load_golden(name)[1]
+    case["args"].update({"opt." + k: v for k, v in extra.items()})
+    return case
 
 
 @pytest.mark.parametrize("name", sorted(ON_RECORD))
@@ -1296,16 +1329,23 @@ def test_launches_and_syncs_of_the_configurations_on_record(ctx, name):
     import paropt_amd as pa
 
     rec = ON_RECORD[name]
-    a = rec.get("ip") or rec["tr"]
-    prob = pa.SeparableProblem(ctx, a["problem"], a["n"], a["c"])
-    if "tr" in rec:
-        solver = pa.TrustRegion(prob, a["opts"])
-        solver.setEigenModelSynthetic(*a["eig"])
+    if "golden" in rec:
+        prob, solver = build_gpu(ctx, golden_case(rec["golden"], **rec.get("extra", {})))
     else:
-        if a["wt"]:
-            prob.setWeighting(*a["wt"])
-        solver = pa.InteriorPoint(prob, dict(a["opts"], write_output_frequency=0))
+        a = rec.get("ip") or rec["tr"]
+        prob = pa.SeparableProblem(ctx, a["problem"], a["n"], a["c"])
+        if "tr" in rec:
+            solver = pa.TrustRegion(prob, a["opts"])
+            solver.setEigenModelSynthetic(*a["eig"])
+        else:
+            if a["wt"]:
+                prob.setWeighting(*a["wt"])
+            solver = pa.InteriorPoint(prob, dict(a["opts"], write_output_frequency=0))
     syncs0, launches0 = ctx.counters()
     solver.optimize()
     syncs1, launches1 = ctx.counters()
     assert (launches1 - launches0, syncs1 - syncs0) == (rec["launches"], rec["syncs"])
+    # a case that is here for a branch of the driver has to keep reaching it ("iNK": the token carries a count)
+    seen = {t for row in info_tokens(solver.getHistory()).values() for t in row}
+    for token in rec.get("tokens", ()):
+        assert any(t == token or (token == "iNK" and t.startswith("iNK")) for t in seen), (token, sorted(seen))

@@ -16,7 +16,12 @@ tests/test_gpu_ip.py (imported, not copied); the sizes at which setUpKKTSystem /
 columns formed in the Gram pass: at most 12; Gram panel with t: kWgramMaxVecs = 80; fused corrector: kCorrDotsMax = 15;
 one kernel's argument tables: kMaxPanel = 96; no dense constraint; sequential linear method; a fixed quasi-Newton
 approximation; linear constraints); four TrustRegion iterations on a quadratic and on an eigenvalue subproblem (the table
-without its wall-clock column); and a dense and a weighting problem under each test switch that selects a kernel form.
+without its wall-clock column); a dense and a weighting problem under each test switch that selects a kernel form; every
+golden of tests/test_gpu_ip.py's IP_CASES with n <= 2049 at its own options and length (between them they reach the info
+tokens skipH, resetH, LFail, LMxItr, LNoImprv, iNK, LMnStp, cmpEq); and driver_branches(), small configurations that
+reach three of the four tokens no golden reaches (dampH, DQN, SLP; no small configuration tried reached LSkip, HISTORY
+R27.2) and the periodic work at the head of an iteration.  Every interior-point record also lists its phase names in
+order of first appearance.
 """
 import hashlib
 import json
@@ -63,6 +68,31 @@ def boundaries():
     ]
 
 
+def driver_branches():
+    """(name, golden whose case it starts from, options added) -- branches of optimize() that no golden takes"""
+    fixed = {"use_quasi_newton_update": 0}
+    return [
+        # a fixed L-BFGS whose line search fails (one or two trial points, the clamp goldens' design_precision): the
+        # next step keeps only the diagonal of the approximation (DQN)
+        ("fixed_lbfgs_clamp_quadratic_line1", "ip_quadratic_clamp_n200_c2", dict(fixed, max_line_iters=1)),
+        ("fixed_lbfgs_clamp_convex_line2", "ip_convex_clamp_n300_c3", dict(fixed, max_line_iters=2)),
+        # ... and with no approximation at all (diagonal Hessian) it is a sequential linear step (SLP)
+        ("no_qn_diag_hessian_clamp_quadratic_line1", "ip_quadratic_clamp_n200_c2",
+         dict(fixed, max_line_iters=1, qn_type="none", use_diag_hessian=1)),
+        # damped BFGS update (dampH)
+        ("damped_convex_badbounds7", "ip_convex_badbounds7_n300_c3", {"qn_update_type": "damped_update"}),
+        ("damped_convex_nolower", "ip_convex_nolower_n200_c2", {"qn_update_type": "damped_update"}),
+        # the periodic work at the head of an iteration
+        ("hessian_reset_freq_4", "ip_convex_n300_c5_bfgs", {"hessian_reset_freq": 4, "max_major_iters": 14}),
+        ("gradient_verification_3", "ip_quadratic_n257_c3_bfgs", {"gradient_verification_frequency": 3,
+                                                                  "max_major_iters": 8}),
+        ("step_verification_3", "ip_quadratic_n257_c3_bfgs", {"step_verification_frequency": 3,
+                                                              "max_major_iters": 8}),
+        ("step_verification_3_mpc", "ip_quadratic_mpc_n300_c3", {"step_verification_frequency": 3,
+                                                                 "max_major_iters": 8}),
+    ]
+
+
 # (switch of core.hpp, its number, the value that leaves the default form, options under which it is reached)
 SWITCHES = [("SW_EXPLICIT_DOTS", 20, 1, {}), ("SW_NO_RECOMPUTE", 21, 1, {}), ("SW_NO_RECOMPUTE_RHS", 22, 1, {}),
             ("SW_NO_FUSED_MERIT", 23, 1, {}), ("SW_NO_LEAN_STEP", 24, 1, {}), ("SW_NO_RECOMPUTE_DT", 25, 1, {}),
@@ -97,11 +127,24 @@ def main():
     import paropt_amd as pa
     import sparse_forms_helpers as H
     from paropt_amd import lib as L
-    from test_gpu_ip import ON_RECORD, SWEEP
+    from test_gpu_ip import IP_CASES, ON_RECORD, SWEEP, build_gpu, golden_case
 
     ctx = pa.Context(0)
 
     counters, delta, emit = helpers(ctx, "--brief" in sys.argv[1:])
+
+    def solve_and_emit(ip, name, **tags):
+        before = counters()
+        ip.optimize()
+        d = delta(before)
+        x, z, zl, zu = ip.getOptimizedPoint()
+        vecs = [("x", x), ("zl", zl), ("zu", zu)]
+        sparse = ip.getOptimizedSparse()
+        if sparse is not None:
+            vecs += list(zip(("zw", "sw", "tw", "zsw", "ztw"), sparse))
+        emit(config=name, history=ip.getHistory(), z=np.asarray(z).tolist(), deltas=d,
+             iteration_counters=list(ip.getIterationCounters()), phases=list(ip.getPhaseTimes()),
+             sha256={k: H.sha(v.to_numpy()) for k, v in vecs if v is not None}, **tags)
 
     def run_ip(s, **tags):
         prob = pa.SeparableProblem(ctx, s["problem"], s["n"], s["c"])
@@ -109,18 +152,18 @@ def main():
             prob.setWeighting(*s["wt"])
         if s["linear"]:
             prob.setLinearConstraints(True)
-        ip = pa.InteriorPoint(prob, dict(s["opts"], write_output_frequency=0))
-        before = counters()
-        ip.optimize()
-        d = delta(before)
-        x, z, zl, zu = ip.getOptimizedPoint()
-        vecs = [("x", x), ("zl", zl), ("zu", zu)]
-        if s["wt"]:
-            vecs += list(zip(("zw", "sw", "tw", "zsw", "ztw"), ip.getOptimizedSparse()))
-        emit(config=s["name"], history=ip.getHistory(), z=np.asarray(z).tolist(), deltas=d,
-             iteration_counters=list(ip.getIterationCounters()),
-             sha256={k: H.sha(v.to_numpy()) for k, v in vecs if v is not None}, **tags)
+        solve_and_emit(pa.InteriorPoint(prob, dict(s["opts"], write_output_frequency=0)), s["name"], **tags)
 
+    def run_golden(name, case):
+        prob, ip = build_gpu(ctx, case)
+        solve_and_emit(ip, name)
+
+    for name in IP_CASES:
+        case = golden_case(name)
+        if case["args"]["n"] <= 2049:
+            run_golden("golden_" + name, case)
+    for name, golden, extra in driver_branches():
+        run_golden(name, golden_case(golden, **extra))
     for i, (problem, n, c, qn, m, extra, wt) in enumerate(SWEEP):
         run_ip(spec("sweep_%02d" % i, problem, n, c, qn, m, 8 if qn == "sr1" else 14, extra, wt))
     for s in boundaries():
