@@ -2073,6 +2073,10 @@ inline double ParOptProblem::checkGradients(double dh, ParOptVec *xvec, int chec
 // setFactorization(PAROPT_CHOLESKY_LDLT) -- no counterpart in the reference -- makes the next factor() compute
 // L S L^T = P A P^T with S = diag(+-1) and no pivoting: for symmetric quasi-definite matrices ([[E, B^T], [B, -F]] with
 // E, F SPD), which have it under every permutation; for a general indefinite matrix it is only as good as its pivots.
+// The constructors with (nschur, schur_vars) after perm -- no counterpart in the reference -- make the factorization
+// PARTIAL (po_sparse_chol_create_schur): the nschur unknowns are ordered last, in the order given, and left
+// uneliminated; after factor() getSchur gives S = A22 - A21 A11^-1 A12 and the solve is condense(), the caller's own
+// solve with S, expand().  solve* and solveRefined* fail on such an object, getInertia counts the interior pivots.
 enum ParOptOrderingType { PAROPT_NATURAL_ORDER, PAROPT_AMD_ORDER, PAROPT_ND_ORDER };
 enum ParOptFactorizationType { PAROPT_CHOLESKY_LLT, PAROPT_CHOLESKY_LDLT };
 
@@ -2081,7 +2085,12 @@ class ParOptSparseCholesky {
   ParOptSparseCholesky(ParOptComm comm, int _size, const int *Acolp, const int *Arows,
                        ParOptOrderingType order = PAROPT_ND_ORDER, const int *_perm = NULL)
       : h(NULL) {
-    create(paropt_amd_context(comm), _size, Acolp, Arows, order, _perm);
+    create(paropt_amd_context(comm), _size, Acolp, Arows, order, _perm, 0, NULL);
+  }
+  ParOptSparseCholesky(ParOptComm comm, int _size, const int *Acolp, const int *Arows, ParOptOrderingType order,
+                       const int *_perm, int nschur, const int *schur_vars)
+      : h(NULL) {
+    create(paropt_amd_context(comm), _size, Acolp, Arows, order, _perm, nschur, schur_vars);
   }
 #ifdef PAROPT_AMD_USE_MPI
   ParOptSparseCholesky(int _size, const int *Acolp, const int *Arows, ParOptOrderingType order = PAROPT_ND_ORDER,
@@ -2090,7 +2099,15 @@ class ParOptSparseCholesky {
     int up = 0;
     MPI_Initialized(&up);
     if (!up) MPI_Init(NULL, NULL);  // (the reference's class needs no MPI; its example never calls MPI_Init)
-    create(paropt_amd_context(MPI_COMM_SELF), _size, Acolp, Arows, order, _perm);
+    create(paropt_amd_context(MPI_COMM_SELF), _size, Acolp, Arows, order, _perm, 0, NULL);
+  }
+  ParOptSparseCholesky(int _size, const int *Acolp, const int *Arows, ParOptOrderingType order, const int *_perm,
+                       int nschur, const int *schur_vars)
+      : h(NULL) {
+    int up = 0;
+    MPI_Initialized(&up);
+    if (!up) MPI_Init(NULL, NULL);
+    create(paropt_amd_context(MPI_COMM_SELF), _size, Acolp, Arows, order, _perm, nschur, schur_vars);
   }
 #endif
   ~ParOptSparseCholesky() { po_sparse_chol_destroy(h); }
@@ -2150,6 +2167,31 @@ class ParOptSparseCholesky {
                          double *eta0 = NULL, double *eta = NULL) {
     return report(po_sparse_chol_solve_refined_device(h, dx, nrhs, size, max_steps, tol, steps, eta0, eta));
   }
+  // Schur complement (objects constructed with a Schur set).  getSchur: the full symmetric nschur x nschur S,
+  // column-major with leading dimension lds (< 0: nschur), in the order of schur_vars; valid after factor() until the
+  // next setValues.  condense: x's Schur entries become g = b2 - A21 A11^-1 b1 and its interior entries an opaque
+  // intermediate; expand: with x2 written over the Schur entries, x becomes the solution.  nrhs columns at
+  // x + j * size.  The *Device forms take DEVICE arrays and are queued on the context's stream.  0, or non-zero with a
+  // message.
+  int getNumSchur() {
+    int64_t info[4] = {0, 0, 0, 0};
+    po_sparse_chol_schur_info(h, info);
+    return (int)info[0];
+  }
+  int getSchur(ParOptScalar *S, int lds = -1) {
+    return report(po_sparse_chol_get_schur(h, S, lds < 0 ? getNumSchur() : lds));
+  }
+  int getSchurDevice(ParOptScalar *dS, int lds = -1) {
+    return report(po_sparse_chol_get_schur_device(h, dS, lds < 0 ? getNumSchur() : lds));
+  }
+  int condense(ParOptScalar *x, int nrhs = 1) { return report(po_sparse_chol_solve_condense(h, x, nrhs, size)); }
+  int condenseDevice(ParOptScalar *dx, int nrhs = 1) {
+    return report(po_sparse_chol_solve_condense_device(h, dx, nrhs, size));
+  }
+  int expand(ParOptScalar *x, int nrhs = 1) { return report(po_sparse_chol_solve_expand(h, x, nrhs, size)); }
+  int expandDevice(ParOptScalar *dx, int nrhs = 1) {
+    return report(po_sparse_chol_solve_expand_device(h, dx, nrhs, size));
+  }
   void getInfo(int *_size, int *_num_snodes, int *_nnzL) {
     int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     po_sparse_chol_info(h, info);
@@ -2162,7 +2204,8 @@ class ParOptSparseCholesky {
  private:
   ParOptSparseCholesky(const ParOptSparseCholesky &);
   ParOptSparseCholesky &operator=(const ParOptSparseCholesky &);
-  void create(po_ctx ctx, int _size, const int *Acolp, const int *Arows, ParOptOrderingType order, const int *_perm) {
+  void create(po_ctx ctx, int _size, const int *Acolp, const int *Arows, ParOptOrderingType order, const int *_perm,
+              int nschur, const int *schur_vars) {
     size = _size;
     const int kind = order == PAROPT_NATURAL_ORDER ? PO_ORDER_NATURAL
                                                    : (order == PAROPT_AMD_ORDER ? PO_ORDER_AMD : PO_ORDER_ND);
@@ -2170,7 +2213,11 @@ class ParOptSparseCholesky {
       fprintf(stderr, "ParOptSparseCholesky: no device context (%s)\n", po_last_error());
       return;
     }
-    report(po_sparse_chol_create(ctx, _size, Acolp, Arows, kind, _perm, &h));
+    if (nschur > 0) {
+      report(po_sparse_chol_create_schur(ctx, _size, Acolp, Arows, kind, _perm, nschur, schur_vars, &h));
+    } else {
+      report(po_sparse_chol_create(ctx, _size, Acolp, Arows, kind, _perm, &h));
+    }
   }
   static int report(int rc) {
     if (rc != 0) fprintf(stderr, "ParOptSparseCholesky: %s\n", po_last_error());

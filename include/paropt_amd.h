@@ -1152,6 +1152,57 @@ int po_sparse_chol_packing(po_sparse_chol h, int64_t info[4], const int **group_
  * "pack_factor", "fwd", "bwd" (a workgroup per unpacked front), "pack_fwd", "pack_bwd".  It is computed by the code
  * the launchers loop over.  No context needed. */
 int po_sparse_chol_kernel_forms(po_sparse_chol h, int nv, int *count, const char *const **names, const int **levels);
+/* SCHUR COMPLEMENT (no counterpart in the reference; all of it opt-in: a handle created by po_sparse_chol_create, or
+ * with nschur == 0, allocates, launches and computes what it did before).
+ * _create_schur is po_sparse_chol_create with a Schur set: nschur distinct unknowns, schur[k] in the caller's
+ * numbering.  With A partitioned as [[A11, A12], [A21, A22]], 2 = the set, po_sparse_chol_factor then eliminates the
+ * interior unknowns only and leaves
+ *     S = A22 - A21 A11^-1 A12
+ * on the device.  The ordering type is applied to the graph induced on the interior unknowns (ND and AMD: the nested
+ * dissection; NATURAL: the identity); the set follows as the last nschur columns IN THE CALLER'S ORDER, as one final
+ * supernode that is assembled and not eliminated.  PO_ORDER_NATURAL with perm is valid only if perm lists the set
+ * last, in the order given.  For the analysis the set is a clique: any A22 entry lies inside the factor's pattern,
+ * and nnzL counts its whole lower triangle.  PO_ERR_ARG with a message for an index out of range, a repeated index and
+ * such a perm.  nschur == size is allowed (no interior, S = A).  ctx == NULL gives an analysis-only handle.
+ * Both factorization kinds: in PO_CHOL_LDLT the interior's updates carry their signs, so what is left is S itself
+ * (for [[E, B^T], [B, -F]] reduced onto the second block, S = -(F + B E^-1 B^T), negative definite).
+ * *info of po_sparse_chol_factor and po_sparse_chol_inertia speak of the INTERIOR pivots only: the three counts sum
+ * to size - nschur.  The diagonal shift reaches A22 like any diagonal; keeping the matrix and po_sparse_chol_matvec
+ * see the whole A.  po_sparse_chol_solve* and po_sparse_chol_solve_refined* answer PO_ERR_ARG on such a handle: the
+ * solve is the two halves below around the caller's own solve with S.
+ * The Schur supernode's children -- every interior subtree that touches the set -- are gathered by one table-driven
+ * launch, a lane per entry of S summing its sources in child order: deterministic and independent of the packing
+ * cap.
+ * _schur_info: {nschur, index of the Schur supernode or -1, its number of children, entries of the gather table of
+ * the factorization}.  _schur_indices: the set, a borrowed host array of nschur entries (the last nschur entries of
+ * perm).  Both work on analysis-only handles. */
+int po_sparse_chol_create_schur(po_ctx ctx, int64_t size, const int *colp, const int *rows, int order, const int *perm,
+                                int64_t nschur, const int *schur, po_sparse_chol *out);
+int po_sparse_chol_schur_info(po_sparse_chol h, int64_t info[4]);
+int po_sparse_chol_schur_indices(po_sparse_chol h, const int **schur);
+/* S as the full symmetric nschur x nschur matrix, column-major with leading dimension lds >= nschur, rows and columns
+ * in the order of the set as given; exactly symmetric (the lower triangle mirrored).  Valid after
+ * po_sparse_chol_factor until the next _set_values (PO_ERR_ARG with a message otherwise).  _get_schur takes a host
+ * array; _get_schur_device a device array, queued on the context's stream. */
+int po_sparse_chol_get_schur(po_sparse_chol h, double *S, int64_t lds);
+int po_sparse_chol_get_schur_device(po_sparse_chol h, double *dS, int64_t lds);
+/* The two halves of the solve, in place on x in the caller's numbering, nrhs columns at x + j * ldx; a column has the
+ * same bits whatever nrhs is.
+ * _solve_condense: afterwards the Schur entries hold g = b2 - A21 A11^-1 b1, the right-hand side of S x2 = g.  The
+ * interior entries hold an intermediate of the forward sweep that is OPAQUE: pass it unchanged to _solve_expand.
+ * _solve_expand: the caller has written x2 over the Schur entries; afterwards the interior entries hold
+ * x1 = A11^-1 (b1 - A12 x2) and x is the solution of A x = b.  With x2 = 0 this is the interior solve A11^-1 b1. */
+int po_sparse_chol_solve_condense(po_sparse_chol h, double *x, int nrhs, int64_t ldx);
+int po_sparse_chol_solve_condense_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx);
+int po_sparse_chol_solve_expand(po_sparse_chol h, double *x, int nrhs, int64_t ldx);
+int po_sparse_chol_solve_expand_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx);
+/* For measurements (tools/bench_sparse_schur.py): queue `reps` assemblies of the Schur supernode alone, through the
+ * table-driven gather (chunked == 0) or through the extend-add kernel of the other fronts over a chunk list of this
+ * front (the same sums, child after child).  The front accumulates: set values again before the next factor. */
+int po_sparse_chol_schur_assembly_probe(po_sparse_chol h, int chunked, int reps);
+/* On a handle with a Schur set po_sparse_chol_kernel_forms reports two more forms after the eight above:
+ * "schur_gather" (the factorization's gather launch) and "schur_fwd" (the gather of the update vectors in
+ * _solve_condense, once per slab). */
 int po_sparse_chol_destroy(po_sparse_chol h); /* NULL is fine */
 
 #ifdef __cplusplus

@@ -1532,12 +1532,19 @@ class SparseCholesky:
     symmetric quasi-definite matrices ([[E, B^T], [B, -F]] with E, F SPD), which have it under every permutation.  For
     a general indefinite matrix it is only as good as its pivots.
 
-    keep_matrix=True retains A beside the factor (see set_keep_matrix): matvec() and solve_refined() need it."""
+    keep_matrix=True retains A beside the factor (see set_keep_matrix): matvec() and solve_refined() need it.
+
+    schur=<indices> (distinct unknowns, any order) makes the factorization PARTIAL: the set is ordered last, in the
+    order given, and left uneliminated, so after factor() the device holds S = A22 - A21 A11^-1 A12 (schur(),
+    schur_device()).  The ordering type then applies to the interior unknowns; "natural" with perm needs a perm that
+    ends with the set.  solve() and solve_refined() raise on such an object: the solve is condense(), the caller's own
+    solve with S, expand().  inertia() counts the interior pivots only."""
 
     ORDERS = {"natural": 0, "amd": 1, "nd": 2}
     FACTORIZATIONS = {"llt": 0, "ldlt": 1}
 
-    def __init__(self, ctx, size, colp, rows, order="nd", perm=None, factorization="llt", keep_matrix=False):
+    def __init__(self, ctx, size, colp, rows, order="nd", perm=None, factorization="llt", keep_matrix=False,
+                 schur=None):
         self.ctx = ctx
         self._colp = np.ascontiguousarray(colp, dtype=np.intc)
         self._rows = np.ascontiguousarray(rows, dtype=np.intc)
@@ -1551,10 +1558,16 @@ class SparseCholesky:
             raise ValueError("colp must have size + 1 entries")
         if int(size) >= 0 and len(self._rows) < int(self._colp[-1]):
             raise ValueError("rows is shorter than colp[size]")
-        check(lib.po_sparse_chol_create(ctx.handle if ctx is not None else None, int(size),
-                                        self._colp.ctypes.data_as(L.c_int_p), self._rows.ctypes.data_as(L.c_int_p),
-                                        self.ORDERS[order] if isinstance(order, str) else int(order),
-                                        p.ctypes.data_as(L.c_int_p) if p is not None else None, C.byref(self._h)))
+        args = (ctx.handle if ctx is not None else None, int(size), self._colp.ctypes.data_as(L.c_int_p),
+                self._rows.ctypes.data_as(L.c_int_p), self.ORDERS[order] if isinstance(order, str) else int(order),
+                p.ctypes.data_as(L.c_int_p) if p is not None else None)
+        if schur is None:
+            check(lib.po_sparse_chol_create(*args, C.byref(self._h)))
+        else:
+            sc = np.ascontiguousarray(schur, dtype=np.intc)
+            if sc.ndim != 1:
+                raise ValueError("schur must be a list of indices")
+            check(lib.po_sparse_chol_create_schur(*args, len(sc), sc.ctypes.data_as(L.c_int_p), C.byref(self._h)))
         info = (C.c_int64 * 8)()
         check(lib.po_sparse_chol_info(self._h, info))
         (self.size, self.num_snodes, self.nnzL, self.nlevels, self.max_snode, self.max_front, self.work_bytes,
@@ -1569,6 +1582,11 @@ class SparseCholesky:
         self.snode_first = arr(ptrs[1], self.num_snodes + 1)
         self.snode_parent = arr(ptrs[2], self.num_snodes)
         self.snode_level = arr(ptrs[3], self.num_snodes)
+        sinfo = self.schur_info()
+        self.num_schur = sinfo["num_schur"]
+        q = L.c_int_p()
+        check(lib.po_sparse_chol_schur_indices(self._h, C.byref(q)))
+        self.schur_indices = arr(q, self.num_schur)
         if factorization != "llt":
             self.set_factorization(factorization)
         if keep_matrix:
@@ -1577,6 +1595,67 @@ class SparseCholesky:
     @property
     def handle(self):
         return self._h
+
+    # ---- Schur complement (po_sparse_chol_create_schur and what follows it) ----
+    def schur_info(self):
+        """{"num_schur", "snode" (index of the Schur supernode, -1 without a set), "children" (its fan-in),
+        "gather_entries" (entries of the factorization's gather table)}; no device needed."""
+        info = (C.c_int64 * 4)()
+        check(lib.po_sparse_chol_schur_info(self._h, info))
+        return {"num_schur": int(info[0]), "snode": int(info[1]), "children": int(info[2]),
+                "gather_entries": int(info[3])}
+
+    def schur(self):
+        """S = A22 - A21 A11^-1 A12 as a (num_schur, num_schur) array in the order of the set as given, exactly
+        symmetric; valid after factor() until the next set_values."""
+        ns = self.num_schur
+        S = np.zeros((ns, ns), dtype=np.float64, order="F")
+        check(lib.po_sparse_chol_get_schur(self._h, S.ctypes.data_as(L.c_double_p), max(ns, 1)))
+        return S
+
+    def schur_device(self, ptr, lds):
+        """S written to device memory at `ptr` (an address, or a contiguous float64 torch tensor on the context's
+        device), column-major with leading dimension lds >= num_schur; queued on the context's stream."""
+        if not isinstance(ptr, int):
+            ptr = self._tensor_ptr(ptr, (self.num_schur - 1) * int(lds) + self.num_schur, "schur_device")
+        check(lib.po_sparse_chol_get_schur_device(self._h, ptr, int(lds)))
+        self.ctx.synchronize()
+
+    def _half(self, fn, who, x):
+        x = np.array(x, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (1, 2) or x.shape[-1] != self.size:
+            raise ValueError(who + ": x must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        check(fn(self._h, x.ctypes.data_as(L.c_double_p), nrhs, self.size))
+        return x
+
+    def _half_tensor(self, fn, who, t):
+        if t.dim() not in (1, 2) or t.shape[-1] != self.size:
+            raise ValueError(who + ": t must have shape (n,) or (nrhs, n)")
+        nrhs = 1 if t.dim() == 1 else t.shape[0]
+        ptr = self._tensor_ptr(t, nrhs * self.size, who)
+        check(fn(self._h, ptr, nrhs, self.size))
+        self.ctx.synchronize()
+        return t
+
+    def condense(self, b):
+        """First half of the solve for b of shape (n,) or (nrhs, n); returns a new array whose Schur entries hold
+        g = b2 - A21 A11^-1 b1 (the right-hand side of S x2 = g).  Its interior entries are an opaque intermediate:
+        pass them unchanged to expand()."""
+        return self._half(lib.po_sparse_chol_solve_condense, "condense", b)
+
+    def expand(self, x):
+        """Second half: x is what condense() returned with x2 written over the Schur entries; returns the solution of
+        A x = b (a new array).  With x2 = 0 its interior entries are A11^-1 b1."""
+        return self._half(lib.po_sparse_chol_solve_expand, "expand", x)
+
+    def condense_tensor(self, t):
+        """condense() in place on a contiguous float64 torch tensor of shape (n,) or (nrhs, n) on the device."""
+        return self._half_tensor(lib.po_sparse_chol_solve_condense_device, "condense_tensor", t)
+
+    def expand_tensor(self, t):
+        """expand() in place on a contiguous float64 torch tensor of shape (n,) or (nrhs, n) on the device."""
+        return self._half_tensor(lib.po_sparse_chol_solve_expand_device, "expand_tensor", t)
 
     def set_factorization(self, kind):
         """ "llt" or "ldlt" (or PO_CHOL_LLT = 0 / PO_CHOL_LDLT = 1), read by the next factor(); allowed at any time,

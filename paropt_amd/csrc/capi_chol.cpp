@@ -14,7 +14,7 @@ using namespace po;
 
 struct po_sparse_chol_s {
   po::SparseChol *c;
-  int form_counts[po::CHF_COUNT];
+  int form_counts[po::CHF_COUNT + po::CHF_SCHUR_COUNT];
 };
 
 #define PO_CHECK_NUMERIC(h)                                                                         \
@@ -43,6 +43,73 @@ int po_sparse_chol_create(po_ctx ctx, int64_t size, const int *colp, const int *
   }
   *out = new po_sparse_chol_s{c, {}};
   return PO_OK;
+}
+// no counterpart in the reference: partial factorization with a Schur complement (paropt_amd.h, "SCHUR COMPLEMENT")
+int po_sparse_chol_create_schur(po_ctx ctx, int64_t size, const int *colp, const int *rows, int order, const int *perm,
+                                int64_t nschur, const int *schur, po_sparse_chol *out) {
+  PO_CHECK_PTR(out);
+  *out = nullptr;
+  PO_CHECK_PTR(colp);
+  if (nschur > 0) PO_CHECK_PTR(schur);
+  po::SparseChol *c = new po::SparseChol(ctx);
+  int rc = po::chol_analyse(size, colp, rows, order, perm, nschur, schur, &c->sym);
+  if (rc == PO_OK && ctx) rc = c->upload();
+  if (rc != PO_OK) {
+    delete c;
+    return rc;
+  }
+  *out = new po_sparse_chol_s{c, {}};
+  return PO_OK;
+}
+int po_sparse_chol_schur_info(po_sparse_chol h, int64_t info[4]) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  const po::CholSymbolic &s = h->c->sym;
+  info[0] = s.ns;
+  info[1] = s.schur_sn;
+  info[2] = s.schur_sn >= 0 ? s.child_ptr[s.schur_sn + 1] - s.child_ptr[s.schur_sn] : 0;
+  info[3] = (int64_t)s.schur_src.size();
+  return PO_OK;
+}
+int po_sparse_chol_schur_indices(po_sparse_chol h, const int **schur) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(schur);
+  *schur = h->c->sym.schur.data();
+  return PO_OK;
+}
+int po_sparse_chol_get_schur(po_sparse_chol h, double *S, int64_t lds) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.ns > 0) PO_CHECK_PTR(S);
+  return h->c->getSchurHost(S, lds);
+}
+int po_sparse_chol_get_schur_device(po_sparse_chol h, double *dS, int64_t lds) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.ns > 0) PO_CHECK_PTR(dS);
+  return h->c->getSchurDevice(dS, lds);
+}
+int po_sparse_chol_solve_condense(po_sparse_chol h, double *x, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(x);
+  return h->c->condenseHost(x, nrhs, ldx);
+}
+int po_sparse_chol_solve_condense_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(dx);
+  return h->c->condenseDevice(dx, nrhs, ldx);
+}
+int po_sparse_chol_solve_expand(po_sparse_chol h, double *x, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(x);
+  return h->c->expandHost(x, nrhs, ldx);
+}
+int po_sparse_chol_solve_expand_device(po_sparse_chol h, double *dx, int nrhs, int64_t ldx) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->sym.n > 0 && nrhs > 0) PO_CHECK_PTR(dx);
+  return h->c->expandDevice(dx, nrhs, ldx);
+}
+int po_sparse_chol_schur_assembly_probe(po_sparse_chol h, int chunked, int reps) {
+  PO_CHECK_NUMERIC(h);
+  return h->c->schurAssemblyProbe(chunked != 0, reps);
 }
 // setValues, ParOptSparseCholesky.h:37-38
 int po_sparse_chol_set_values(po_sparse_chol h, int64_t n, const int *colp, const int *rows, const double *vals) {
@@ -186,10 +253,14 @@ int po_sparse_chol_kernel_forms(po_sparse_chol h, int nv, int *count, const char
     po::set_error("po_sparse_chol_kernel_forms: nv must be at least 1");
     return PO_ERR_ARG;
   }
-  static const char *form_names[po::CHF_COUNT];
-  for (int f = 0; f < po::CHF_COUNT; f++) form_names[f] = po::chol_form_name(f);
+  static const char *form_names[po::CHF_COUNT + po::CHF_SCHUR_COUNT];
+  for (int f = 0; f < po::CHF_COUNT + po::CHF_SCHUR_COUNT; f++) form_names[f] = po::chol_form_name(f);
   po::chol_kernel_forms(h->c->sym, nv, h->form_counts);
   *count = po::CHF_COUNT;
+  if (h->c->sym.ns > 0) {  // a handle with a Schur set: its two gather launches on top
+    po::chol_schur_forms(h->c->sym, nv, h->form_counts + po::CHF_COUNT);
+    *count += po::CHF_SCHUR_COUNT;
+  }
   if (names) *names = form_names;
   if (levels) *levels = h->form_counts;
   return PO_OK;

@@ -158,6 +158,138 @@ void chol_matrix_table(CholSymbolic *out) {
 }
 
 int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *user_perm, CholSymbolic *out) {
+  return chol_analyse(size, colp, rows, order, user_perm, 0, nullptr, out);
+}
+
+namespace {
+
+// The Schur set's part of the ordering (sparse_chol.hpp, "Schur complement"): the ordering type on the graph induced
+// on the interior unknowns, the set after it in the caller's order; then adjp / adj get the set as a clique, so the
+// elimination tree chains its columns and every A22 entry lies in the pattern.
+int schur_order(int n, int order, const int *user_perm, const std::vector<int> &schur, std::vector<int> *adjp_io,
+                std::vector<int> *adj_io, std::vector<int> *perm) {
+  const std::vector<int> &adjp = *adjp_io, &adj = *adj_io;
+  const int ns = (int)schur.size(), ni = n - ns;
+  std::vector<int> interior_of(n, 0);  // -1 on the set, else the index among the interior unknowns
+  for (int v : schur) interior_of[v] = -1;
+  std::vector<int> interior;
+  interior.reserve(ni);
+  for (int v = 0; v < n; v++) {
+    if (interior_of[v] == 0) {
+      interior_of[v] = (int)interior.size();
+      interior.push_back(v);
+    }
+  }
+  perm->resize(n);
+  if (order == PO_ORDER_NATURAL) {
+    if (user_perm) {
+      for (int k = 0; k < ns; k++) {
+        if (user_perm[ni + k] != schur[k]) {
+          set_error("sparse Cholesky: with a Schur set, perm must list the set last and in the order given (perm[%d] "
+                    "is %d, the set has %d there)", ni + k, user_perm[ni + k], schur[k]);
+          return PO_ERR_ARG;
+        }
+      }
+      perm->assign(user_perm, user_perm + n);
+    } else {
+      std::copy(interior.begin(), interior.end(), perm->begin());
+    }
+  } else if (ni > 0) {
+    std::vector<int> ip((size_t)ni + 1, 0), ia, iperm;
+    for (int k = 0; k < ni; k++) {
+      const int v = interior[k];
+      for (int p = adjp[v]; p < adjp[v + 1]; p++) {
+        if (interior_of[adj[p]] >= 0) ia.push_back(interior_of[adj[p]]);  // (ascending: interior_of is monotone)
+      }
+      ip[k + 1] = (int)ia.size();
+    }
+    sym_nd_order(ip, ia, ni, &iperm);
+    for (int k = 0; k < ni; k++) (*perm)[k] = interior[iperm[k]];
+  }
+  std::copy(schur.begin(), schur.end(), perm->begin() + ni);
+  // the clique
+  int64_t total = 0;
+  for (int v = 0; v < n; v++) total += interior_of[v] >= 0 ? adjp[v + 1] - adjp[v] : (adjp[v + 1] - adjp[v]) + ns;
+  if (total > 2000000000LL) {
+    set_error("sparse Cholesky: the pattern with the Schur set as a clique has more than 2e9 entries");
+    return PO_ERR_ARG;
+  }
+  std::vector<int> sorted(schur);
+  std::sort(sorted.begin(), sorted.end());
+  std::vector<int> np((size_t)n + 1, 0), na;
+  na.reserve((size_t)total);
+  for (int v = 0; v < n; v++) {
+    if (interior_of[v] >= 0) {
+      na.insert(na.end(), adj.begin() + adjp[v], adj.begin() + adjp[v + 1]);
+    } else {
+      const size_t begin = na.size();
+      for (int p = adjp[v]; p < adjp[v + 1]; p++) {
+        if (interior_of[adj[p]] >= 0) na.push_back(adj[p]);
+      }
+      const size_t mid = na.size();
+      for (int u : sorted) {
+        if (u != v) na.push_back(u);
+      }
+      std::inplace_merge(na.begin() + begin, na.begin() + mid, na.end());
+    }
+    np[v + 1] = (int)na.size();
+  }
+  adjp_io->swap(np);
+  adj_io->swap(na);
+  return PO_OK;
+}
+
+// The gather tables of the Schur supernode S (sparse_chol.hpp: schur_*), the children in child order.
+void schur_tables(CholSymbolic *out) {
+  CholSymbolic &s = *out;
+  const int S = s.schur_sn, ns = s.ns, ld = s.sn_ld[S];
+  // factorization: count per destination (col, row) of the lower triangle, prefix sum, fill child after child
+  std::vector<int64_t> cnt((size_t)ns * ns + 1, 0);
+  std::vector<int64_t> vcnt((size_t)ns + 1, 0);
+  for (int c = s.child_ptr[S]; c < s.child_ptr[S + 1]; c++) {
+    const int C = s.child[c], bc = s.sn_b[C];
+    const int *rel = s.rel.data() + s.rows_ptr[C];
+    for (int j = 0; j < bc; j++) {
+      vcnt[rel[j] + 1]++;
+      for (int i = j; i < bc; i++) cnt[(size_t)rel[j] * ns + rel[i] + 1]++;
+    }
+  }
+  for (size_t k = 0; k < (size_t)ns * ns; k++) cnt[k + 1] += cnt[k];
+  for (int k = 0; k < ns; k++) vcnt[k + 1] += vcnt[k];
+  s.schur_src.assign((size_t)cnt[(size_t)ns * ns], 0);
+  s.schur_vsrc.assign((size_t)vcnt[ns], 0);
+  s.schur_vld.assign((size_t)vcnt[ns], 0);
+  {
+    std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1), vfill(vcnt.begin(), vcnt.end() - 1);
+    for (int c = s.child_ptr[S]; c < s.child_ptr[S + 1]; c++) {
+      const int C = s.child[c], bc = s.sn_b[C], ulc = s.upd_ld[C];
+      const int *rel = s.rel.data() + s.rows_ptr[C];
+      for (int j = 0; j < bc; j++) {
+        const int64_t q = vfill[rel[j]]++;
+        s.schur_vsrc[q] = s.sol_off[C] + j;
+        s.schur_vld[q] = ulc;
+        for (int i = j; i < bc; i++) s.schur_src[fill[(size_t)rel[j] * ns + rel[i]]++] = s.upd_off[C] + (int64_t)j * ulc + i;
+      }
+    }
+  }
+  s.schur_vptr.swap(vcnt);
+  // keep the destinations that have sources
+  s.schur_ptr.assign(1, 0);
+  s.schur_dst.clear();
+  for (int col = 0; col < ns; col++) {
+    for (int row = col; row < ns; row++) {
+      const size_t k = (size_t)col * ns + row;
+      if (cnt[k + 1] == cnt[k]) continue;
+      s.schur_dst.push_back(s.panel_off[S] + (int64_t)col * ld + row);
+      s.schur_ptr.push_back(cnt[k + 1]);
+    }
+  }
+}
+
+}  // namespace
+
+int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *user_perm, int64_t nschur,
+                 const int *schur, CholSymbolic *out) {
   CholSymbolic &s = *out;
   if (size < 0 || size > 2000000000LL) {
     set_error("sparse Cholesky: size %lld out of range", (long long)size);
@@ -176,6 +308,25 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
     if (colp[j + 1] < colp[j]) {
       set_error("sparse Cholesky: colp is not non-decreasing at column %d", j);
       return PO_ERR_ARG;
+    }
+  }
+  if (nschur < 0 || nschur > n || (nschur > 0 && !schur)) {
+    set_error("sparse Cholesky: a Schur set of %lld unknowns (size %d), or its indices are missing", (long long)nschur,
+              n);
+    return PO_ERR_ARG;
+  }
+  const int ns = (int)nschur;
+  s.ns = ns;
+  s.schur_sn = -1;
+  s.schur.assign(schur, schur + ns);
+  if (ns > 0) {
+    std::vector<char> seen(n, 0);
+    for (int k = 0; k < ns; k++) {
+      if (schur[k] < 0 || schur[k] >= n || seen[schur[k]]) {
+        set_error("sparse Cholesky: Schur index %d (entry %d of the set) is out of range or repeated", schur[k], k);
+        return PO_ERR_ARG;
+      }
+      seen[schur[k]] = 1;
     }
   }
   const int nnz = colp[n];
@@ -228,7 +379,19 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
     }
   }
   // ordering
-  if (order == PO_ORDER_NATURAL) {
+  if (ns > 0) {
+    if (order == PO_ORDER_NATURAL && user_perm) {  // (checked here: schur_order reads it as a permutation)
+      std::vector<char> seen(n, 0);
+      for (int i = 0; i < n; i++) {
+        if (user_perm[i] < 0 || user_perm[i] >= n || seen[user_perm[i]]) {
+          set_error("sparse Cholesky: perm is not a permutation of 0 .. %d", n - 1);
+          return PO_ERR_ARG;
+        }
+        seen[user_perm[i]] = 1;
+      }
+    }
+    PO_TRY(schur_order(n, order, user_perm, s.schur, &adjp, &adj, &s.perm));
+  } else if (order == PO_ORDER_NATURAL) {
     s.perm.resize(n);
     if (user_perm) {
       s.perm.assign(user_perm, user_perm + n);
@@ -297,12 +460,20 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
       if (parent[j] >= 0) nchild[parent[j]]++;
     }
     for (int j = 0; j < n; j++) {
-      const bool joins = j > 0 && parent[j - 1] == j && nchild[j] == 1 && colcount[j - 1] == colcount[j] + 1;
+      bool joins = j > 0 && parent[j - 1] == j && nchild[j] == 1 && colcount[j - 1] == colcount[j] + 1;
+      // the Schur set: a break in front of it, none inside it (whatever attaches at its later columns)
+      if (ns > 0 && j >= n - ns) joins = j > n - ns;
       if (!joins) s.sn_first.push_back(j);
       s.sn_of[j] = (int)s.sn_first.size() - 1;
     }
     s.nsn = (int)s.sn_first.size();
     s.sn_first.push_back(n);
+    if (ns > 0) {
+      s.schur_sn = s.nsn - 1;
+      for (int k = 0; k < ns; k++) {
+        if (s.perm[n - ns + k] != s.schur[k]) return chol_internal("the postorder moved the Schur set");
+      }
+    }
   }
   const int nsn = s.nsn;
   // row structures, children first
@@ -408,7 +579,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
     std::vector<int> cnt(nsn, 1);
     std::vector<char> packable(nsn, 0), cand(nsn, 0);
     for (int J = 0; J < nsn; J++) {
-      bool ok = order_of(J) <= kCholTiny;
+      bool ok = order_of(J) <= kCholTiny && J != s.schur_sn;
       for (int c = s.child_ptr[J]; c < s.child_ptr[J + 1]; c++) {
         cnt[J] += cnt[s.child[c]];
         ok = ok && packable[s.child[c]];
@@ -427,7 +598,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
       }
     }
     for (int J = 0; J < nsn; J++) {
-      if (grp_of[J] == -1 && order_of(J) <= kCholTiny) grp_of[J] = J;
+      if (grp_of[J] == -1 && order_of(J) <= kCholTiny && J != s.schur_sn) grp_of[J] = J;
     }
     for (int J = 0; J < nsn; J++) {
       if (grp_of[J] != J) continue;
@@ -455,7 +626,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
   // level lists of the unpacked fronts
   s.lev_ptr.assign((size_t)s.nlev + 1, 0);
   for (int J = 0; J < nsn; J++) {
-    if (grp_of[J] == -1) s.lev_ptr[s.sn_level[J] + 1]++;
+    if (grp_of[J] == -1 && J != s.schur_sn) s.lev_ptr[s.sn_level[J] + 1]++;
   }
   for (int l = 0; l < s.nlev; l++) s.lev_ptr[l + 1] += s.lev_ptr[l];
   s.lev_sn.resize(s.lev_ptr[s.nlev]);
@@ -463,7 +634,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
   {
     std::vector<int> fill(s.lev_ptr.begin(), s.lev_ptr.end() - 1);
     for (int J = 0; J < nsn; J++) {
-      if (grp_of[J] == -1) s.lev_sn[fill[s.sn_level[J]]++] = J;
+      if (grp_of[J] == -1 && J != s.schur_sn) s.lev_sn[fill[s.sn_level[J]]++] = J;
     }
     for (int l = 0; l < s.nlev; l++) {
       auto b = s.lev_sn.begin() + s.lev_ptr[l], e = s.lev_sn.begin() + s.lev_ptr[l + 1];
@@ -499,11 +670,18 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
       for (int q = s.glev_ptr[l]; q < s.glev_ptr[l + 1]; q++) {
         for (int J = s.glev_first[q]; J <= s.glev_root[q]; J++) give_children(J);
       }
+      // (the slots of the Schur supernode's children are never given back: its two gathers may then run at any
+      // point after its level, and it is the last front of its tree anyway)
     }
     s.arena = fa.end;
     s.sol_arena = so.end;
   }
   s.work_bytes = 8 * (std::max(s.arena, s.sol_arena) + s.ldy() * kCholMaxRhs);  // one buffer serves both arenas
+  if (s.schur_sn >= 0) {
+    schur_tables(&s);
+    s.work_bytes += 8 * (int64_t)(s.schur_ptr.size() + s.schur_src.size() + s.schur_dst.size() + s.schur_vptr.size() +
+                                  s.schur_vsrc.size()) + 4 * (int64_t)s.schur_vld.size();
+  }
   // launch tables
   s.chunk_ptr.assign((size_t)s.nlev + 1, 0);
   s.chunk_sn.clear();
@@ -549,9 +727,9 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
 }
 
 const char *chol_form_name(int form) {
-  static const char *const names[CHF_COUNT] = {"assemble", "small",    "blocked", "pack_factor",
-                                               "fwd",      "bwd",      "pack_fwd", "pack_bwd"};
-  return form >= 0 && form < CHF_COUNT ? names[form] : "";
+  static const char *const names[CHF_COUNT + CHF_SCHUR_COUNT] = {
+      "assemble", "small", "blocked", "pack_factor", "fwd", "bwd", "pack_fwd", "pack_bwd", "schur_gather", "schur_fwd"};
+  return form >= 0 && form < CHF_COUNT + CHF_SCHUR_COUNT ? names[form] : "";
 }
 
 void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]) {
@@ -567,6 +745,16 @@ void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]) {
     counts[CHF_BWD] += slabs * (p.nfront > 0);
     counts[CHF_PACK_FWD] += slabs * (p.ngroup > 0);
     counts[CHF_PACK_BWD] += slabs * (p.ngroup > 0);
+  }
+}
+
+void chol_schur_forms(const CholSymbolic &s, int nv, int counts[CHF_SCHUR_COUNT]) {
+  for (int f = 0; f < CHF_SCHUR_COUNT; f++) counts[f] = 0;
+  const int slabs = (nv + kCholMaxRhs - 1) / kCholMaxRhs;
+  for (int l = 0; l < s.nlev; l++) {
+    const CholLevelPlan p = chol_level_plan(s, l);
+    counts[CHF_SCHUR_GATHER] += p.nschur;
+    counts[CHF_SCHUR_FWD] += slabs * p.nschur;
   }
 }
 
@@ -587,7 +775,7 @@ int chol_factor_levels(const CholSymbolic &s) {
   int count = 0;
   for (int l = 0; l < s.nlev; l++) {
     const CholLevelPlan p = chol_level_plan(s, l);
-    count += p.nchunk + p.nsmall + p.nsteps + p.ngroup > 0;
+    count += p.nchunk + p.nsmall + p.nsteps + p.ngroup + p.nschur > 0;
   }
   return count;
 }

@@ -885,6 +885,74 @@ void launch_levels(const CholSymbolic &sym, hipStream_t st, const CholDev &d, co
   }
 }
 
+// ---- Schur complement (sparse_chol.hpp, "Schur complement") ---------------------------------------------------------
+// The Schur supernode's fan-in is every interior subtree that touches the set -- thousands of children for a KKT
+// system whose E is block-diagonal -- and chol_assemble_kernel / chol_fwd_kernel walk the children one after the other
+// with a barrier each.  Here the analysis has turned the walk into a table: a lane per destination adds its sources
+// in child order, which is the order and so the bits of that walk; no atomics, no barrier, nothing that depends on the
+// packing cap.  Four sources are loaded ahead of their adds: the chain of a lane is the adds, not the memory latency.
+__global__ __launch_bounds__(256) void chol_schur_gather_kernel(const int64_t *__restrict__ ptr,
+                                                                const int64_t *__restrict__ dst,
+                                                                const int64_t *__restrict__ src, int64_t ndst,
+                                                                const double *__restrict__ arena, double *L) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndst) return;
+  const int64_t at = dst[d], p1 = ptr[d + 1];
+  int64_t p = ptr[d];
+  double acc = L[at];
+  for (; p + 4 <= p1; p += 4) {
+    const double v0 = arena[src[p]], v1 = arena[src[p + 1]], v2 = arena[src[p + 2]], v3 = arena[src[p + 3]];
+    acc += v0;
+    acc += v1;
+    acc += v2;
+    acc += v3;
+  }
+  for (; p < p1; p++) acc += arena[src[p]];
+  L[at] = acc;
+}
+
+// the children's update vectors into the Schur rows of the right-hand sides: thread = (row, right-hand side)
+__global__ __launch_bounds__(256) void chol_schur_fwd_kernel(const int64_t *__restrict__ vptr,
+                                                             const int64_t *__restrict__ vsrc,
+                                                             const int *__restrict__ vld, int ns, int first,
+                                                             const double *__restrict__ arena, double *Y, int64_t ldy,
+                                                             int nrhs) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)ns * nrhs) return;
+  const int i = (int)(idx % ns), r = (int)(idx / ns);
+  double *y = Y + first + i + r * ldy;
+  double acc = *y;
+  for (int64_t q = vptr[i]; q < vptr[i + 1]; q++) acc += arena[vsrc[q] + (int64_t)r * vld[q]];
+  *y = acc;
+}
+
+// S out of the Schur panel (lower triangle, column-major, leading dimension ld) as the full symmetric matrix
+// (column-major, lds): a workgroup per 64 x 64 tile of the lower triangle, through LDS.  The panel is read down its
+// columns and the lower triangle written the same way; the mirror image is written with the lanes running along the
+// tile's COLUMNS, which are consecutive addresses of the upper triangle: every global access is a 512-byte run.  The
+// tile's leading dimension of 65 doubles keeps both LDS access directions free of bank conflicts.
+constexpr int kSchurLd = kCholTile + 1;
+__global__ __launch_bounds__(256) void chol_schur_copy_kernel(const double *__restrict__ P, int ld, int ns,
+                                                              double *__restrict__ S, int64_t lds) {
+  __shared__ double T[kCholTile * kSchurLd];
+  const int ti = blockIdx.x, tj = blockIdx.y;
+  if (tj > ti) return;
+  const int R0 = ti * kCholTile, C0 = tj * kCholTile;
+  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+  for (int c = q; c < kCholTile; c += 4) {
+    const int row = R0 + lane, col = C0 + c;
+    const bool in = row < ns && col < ns && row >= col;
+    const double v = in ? P[(int64_t)col * ld + row] : 0.0;
+    T[c * kSchurLd + lane] = v;
+    if (in) S[(int64_t)col * lds + row] = v;
+  }
+  __syncthreads();
+  for (int r = q; r < kCholTile; r += 4) {
+    const int row = R0 + r, col = C0 + lane;
+    if (row < ns && col < ns && row > col) S[(int64_t)row * lds + col] = T[lane * kSchurLd + r];
+  }
+}
+
 // ---- retained matrix: value compaction, diagonal shift, product, residual, norms -------------------------------------
 // (sparse_chol.hpp, "RETAINED MATRIX").  All panels are in elimination order, column-major, leading dimension ld.
 //
@@ -1110,6 +1178,14 @@ int SparseChol::upload(bool embedded) {
     PO_TRY(d_asm_src.upload(sym.asm_src));
     PO_TRY(d_asm_dst.upload(sym.asm_dst));
   }
+  if (sym.ns > 0) {
+    PO_TRY(d_schur_ptr.upload(sym.schur_ptr));
+    PO_TRY(d_schur_src.upload(sym.schur_src));
+    PO_TRY(d_schur_dst.upload(sym.schur_dst));
+    PO_TRY(d_schur_vptr.upload(sym.schur_vptr));
+    PO_TRY(d_schur_vsrc.upload(sym.schur_vsrc));
+    PO_TRY(d_schur_vld.upload(sym.schur_vld));
+  }
   PO_HIP(hipDeviceSynchronize());
   return PO_OK;
 }
@@ -1128,6 +1204,7 @@ int SparseChol::scatter(const int *ptr, const int64_t *dst, const int *src, int6
   }
   have_values = true;
   factored = false;
+  schur_ready = false;
   return PO_OK;
 }
 
@@ -1243,6 +1320,7 @@ int SparseChol::launchFactor(int *flag) {
       hipLaunchKernelGGL(chol_assemble_kernel, dim3(plan.nchunk), dim3(128), 0, st, d, d_chunk_sn + sym.chunk_ptr[l],
                          d_chunk_c0 + sym.chunk_ptr[l]);
     }
+    if (plan.nschur > 0) launchSchurGather(1);  // (its children are below this level; the front is then left alone)
     const int nsmall = plan.nsmall;
     if (nsmall > 0) {
       hipLaunchKernelGGL(chol_small_kernel<kSigned>, dim3(nsmall), dim3(64), 0, st, d, d_lev_sn + sym.lev_ptr[l],
@@ -1282,9 +1360,10 @@ int SparseChol::factor(int *info) {
   PO_HIP(hipMemsetAsync(d_flag + 1, 0x7f, sizeof(int), st));
   const bool ldlt = kind == PO_CHOL_LDLT;
   PO_TRY(ldlt ? launchFactor<true>(d_flag) : launchFactor<false>(d_flag));
-  if (ldlt && sym.n > 0) {
-    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)sym.n + 1023) / 1024, 1024);
-    hipLaunchKernelGGL(chol_count_negative_kernel, dim3(blocks), dim3(256), 0, st, (const double *)d_sign, sym.n,
+  const int npiv = sym.n - sym.ns;  // the Schur supernode is not eliminated: the pivots are the interior's
+  if (ldlt && npiv > 0) {
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)npiv + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(chol_count_negative_kernel, dim3(blocks), dim3(256), 0, st, (const double *)d_sign, npiv,
                        d_flag);
     PO_HIP(hipGetLastError());
   }
@@ -1294,11 +1373,12 @@ int SparseChol::factor(int *info) {
   have_values = false;
   factored = true;
   factored_kind = kind;
+  schur_ready = sym.ns > 0;
   // (the counts came with the flag read: nothing of size n goes to the host).  The unsigned kernels count nothing:
   // a Cholesky factorization that replaced no pivot has n positive ones, one that did has no inertia to report.
   inertia_[1] = ldlt ? flag[2] : 0;
   inertia_[2] = ldlt ? flag[3] : 0;
-  inertia_[0] = (int64_t)sym.n - inertia_[1] - inertia_[2];
+  inertia_[0] = (int64_t)npiv - inertia_[1] - inertia_[2];
   have_inertia = ldlt || flag[0] == 0;
   uncounted = !have_inertia;
   if (flag[0] != 0) {
@@ -1327,7 +1407,15 @@ void SparseChol::solvePanel(double *P, int nr) {
                 chol_bwd_kernel, P, ldy, nr);
 }
 
+int SparseChol::refuseWholeSolve(const char *who) const {
+  if (sym.ns == 0) return PO_OK;
+  set_error("sparse Cholesky: %s on a handle with a Schur set: the Schur supernode is not eliminated, the solve is its "
+            "two halves solve_condense() and solve_expand() around the caller's own solve with S (get_schur())", who);
+  return PO_ERR_ARG;
+}
+
 int SparseChol::solveDevice(double *dx, int nrhs, int64_t ldx) {
+  PO_TRY(refuseWholeSolve("solve()"));
   if (!factored) {
     set_error("sparse Cholesky: solve() before factor()");
     return PO_ERR_ARG;
@@ -1379,6 +1467,7 @@ int SparseChol::sweep(double *const *Yh, int nv, bool forward, bool backward) {
 }
 
 int SparseChol::solveHost(double *x, int nrhs, int64_t ldx) {
+  PO_TRY(refuseWholeSolve("solve()"));
   if (sym.n == 0 || nrhs <= 0) return solveDevice(nullptr, nrhs, ldx);
   if (nrhs > 1 && ldx < sym.n) return solveDevice(nullptr, nrhs, ldx);
   PO_HIP(hipSetDevice(ctx->device));
@@ -1390,6 +1479,166 @@ int SparseChol::solveHost(double *x, int nrhs, int64_t ldx) {
   PO_HIP(hipStreamSynchronize(ctx->stream));
   return PO_OK;
 }
+
+// ---- Schur complement: reading S, the two halves of the solve ------------------------------------------------------
+void SparseChol::launchSchurGather(int reps) {
+  const int64_t ndst = (int64_t)sym.schur_dst.size();
+  for (int k = 0; k < reps && ndst > 0; k++) {
+    hipLaunchKernelGGL(chol_schur_gather_kernel, dim3((unsigned)((ndst + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const int64_t *)d_schur_ptr, (const int64_t *)d_schur_dst, (const int64_t *)d_schur_src, ndst,
+                       (const double *)arena, L.get());
+  }
+}
+
+int SparseChol::schurAssemblyProbe(bool chunked, int reps) {
+  if (sym.ns == 0 || reps < 0) {
+    set_error("sparse Cholesky: the assembly probe needs a handle with a Schur set and reps >= 0");
+    return PO_ERR_ARG;
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  if (!chunked) {
+    launchSchurGather(reps);
+  } else {
+    const int nchunk = (sym.ns + kCholChunk - 1) / kCholChunk;
+    if (!d_probe_sn) {
+      std::vector<int> sn((size_t)nchunk, sym.schur_sn), c0((size_t)nchunk);
+      for (int k = 0; k < nchunk; k++) c0[k] = k * kCholChunk;
+      PO_TRY(d_probe_sn.upload(sn));
+      PO_TRY(d_probe_c0.upload(c0));
+    }
+    const CholDev d = dev();
+    for (int k = 0; k < reps; k++) {
+      hipLaunchKernelGGL(chol_assemble_kernel, dim3(nchunk), dim3(128), 0, ctx->stream, d, (const int *)d_probe_sn,
+                         (const int *)d_probe_c0);
+    }
+  }
+  PO_HIP(hipGetLastError());
+  return PO_OK;
+}
+
+int SparseChol::getSchurDevice(double *dS, int64_t lds) {
+  if (sym.ns == 0) {
+    set_error("sparse Cholesky: get_schur() needs a handle created with a Schur set");
+    return PO_ERR_ARG;
+  }
+  if (!schur_ready) {
+    set_error("sparse Cholesky: get_schur() is valid after factor() until the next set_values");
+    return PO_ERR_ARG;
+  }
+  if (lds < sym.ns) {
+    set_error("sparse Cholesky: get_schur() with lds %lld for a Schur set of %d", (long long)lds, sym.ns);
+    return PO_ERR_ARG;
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  const int S = sym.schur_sn;
+  const unsigned nt = (unsigned)((sym.ns + kCholTile - 1) / kCholTile);
+  hipLaunchKernelGGL(chol_schur_copy_kernel, dim3(nt, nt), dim3(256), 0, ctx->stream,
+                     (const double *)(L.get() + sym.panel_off[S]), sym.sn_ld[S], sym.ns, dS, lds);
+  PO_HIP(hipGetLastError());
+  return PO_OK;
+}
+
+int SparseChol::getSchurHost(double *S, int64_t lds) {
+  const int64_t count = (int64_t)sym.ns * sym.ns;
+  if (sym.ns > 0 && schur_ready && lds >= sym.ns && count > sbuf_cap) {
+    PO_HIP(hipSetDevice(ctx->device));
+    sbuf_cap = 0;
+    PO_TRY(sbuf.alloc((size_t)count, false));
+    sbuf_cap = count;
+  }
+  PO_TRY(getSchurDevice(sbuf, lds < sym.ns ? lds : sym.ns));  // (it refuses what this entry refuses)
+  const size_t width = (size_t)sym.ns * sizeof(double);
+  PO_HIP(hipMemcpy2DAsync(S, (size_t)lds * sizeof(double), sbuf, width, width, (size_t)sym.ns, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
+
+int SparseChol::halfSolveCheck(const char *who, int nrhs, int64_t ldx) {
+  if (sym.ns == 0) {
+    set_error("sparse Cholesky: %s needs a handle created with a Schur set", who);
+    return PO_ERR_ARG;
+  }
+  if (!factored) {
+    set_error("sparse Cholesky: %s before factor()", who);
+    return PO_ERR_ARG;
+  }
+  if (nrhs < 0 || (nrhs > 1 && ldx < sym.n)) {
+    set_error("sparse Cholesky: %s with nrhs %d, ldx %lld (size %d)", who, nrhs, (long long)ldx, sym.n);
+    return PO_ERR_ARG;
+  }
+  return PO_OK;
+}
+
+// Schur entries: g = b2 - A21 A11^-1 b1; interior entries: the forward-swept intermediate, which expand reads
+int SparseChol::condenseDevice(double *dx, int nrhs, int64_t ldx) {
+  PO_TRY(halfSolveCheck("solve_condense()", nrhs, ldx));
+  if (nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CholDev d = dev();
+  const int64_t ldy = sym.ldy();
+  const CholPtrs none = {};
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    double *x = dx + (int64_t)r0 * ldx, *P = Y;
+    const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 0);
+    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, P, ldy,
+                  chol_fwd_kernel, P, ldy, nr);
+    for (int l = 0; l < sym.nlev; l++) {
+      if (chol_level_plan(sym, l).nschur == 0) continue;
+      hipLaunchKernelGGL(chol_schur_fwd_kernel, dim3((unsigned)(((int64_t)sym.ns * nr + 255) / 256)), dim3(256), 0, st,
+                         (const int64_t *)d_schur_vptr, (const int64_t *)d_schur_vsrc, (const int *)d_schur_vld, sym.ns,
+                         sym.n - sym.ns, (const double *)arena, P, ldy, nr);
+    }
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+// x2 in the Schur entries, the intermediate of condense in the interior ones: x1 = A11^-1 (b1 - A12 x2)
+int SparseChol::expandDevice(double *dx, int nrhs, int64_t ldx) {
+  PO_TRY(halfSolveCheck("solve_expand()", nrhs, ldx));
+  if (nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const CholDev d = dev();
+  const int64_t ldy = sym.ldy();
+  const int ni = sym.n - sym.ns;
+  const CholPtrs none = {};
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    double *x = dx + (int64_t)r0 * ldx, *P = Y;
+    const unsigned pg = (unsigned)(((int64_t)sym.n * nr + 255) / 256);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 0);
+    if (factored_kind == PO_CHOL_LDLT && ni > 0) {  // (the interior's signs; the Schur columns have none)
+      hipLaunchKernelGGL(chol_sign_kernel, dim3((unsigned)(((int64_t)ni * nr + 255) / 256)), dim3(256), 0, st, P, ldy,
+                         (const double *)d_sign, ni, nr);
+    }
+    launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<false>, none, P, ldy,
+                  chol_bwd_kernel, P, ldy, nr);
+    hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 1);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::halfSolveHost(bool condense, double *x, int nrhs, int64_t ldx) {
+  PO_TRY(halfSolveCheck(condense ? "solve_condense()" : "solve_expand()", nrhs, ldx));
+  if (nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t count = (int64_t)(nrhs - 1) * ldx + sym.n;
+  PO_TRY(hostBuffer(count));
+  PO_HIP(hipMemcpyAsync(xbuf, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PO_TRY(condense ? condenseDevice(xbuf, nrhs, ldx) : expandDevice(xbuf, nrhs, ldx));
+  PO_HIP(hipMemcpyAsync(x, xbuf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
+int SparseChol::condenseHost(double *x, int nrhs, int64_t ldx) { return halfSolveHost(true, x, nrhs, ldx); }
+int SparseChol::expandHost(double *x, int nrhs, int64_t ldx) { return halfSolveHost(false, x, nrhs, ldx); }
 
 // ---- retained matrix, diagonal shift, refined solve ----------------------------------------------------------------
 int SparseChol::setKeepMatrix(bool on) {
@@ -1566,6 +1815,7 @@ int SparseChol::matvecHost(const double *x, int64_t ldx, double *y, int64_t ldy_
 // ones it would have alone.
 int SparseChol::solveRefinedDevice(double *dx, int nrhs, int64_t ldx, int max_steps, double tol, int *steps,
                                    double *eta0, double *eta) {
+  PO_TRY(refuseWholeSolve("solve_refined()"));
   PO_TRY(needMatrix("solve_refined()"));
   if (!factored) {
     set_error("sparse Cholesky: solve_refined() before factor()");
@@ -1632,6 +1882,7 @@ int SparseChol::solveRefinedDevice(double *dx, int nrhs, int64_t ldx, int max_st
 
 int SparseChol::solveRefinedHost(double *x, int nrhs, int64_t ldx, int max_steps, double tol, int *steps, double *eta0,
                                  double *eta) {
+  PO_TRY(refuseWholeSolve("solve_refined()"));
   if (sym.n == 0 || nrhs <= 0 || (nrhs > 1 && ldx < sym.n)) {
     return solveRefinedDevice(nullptr, nrhs, ldx, max_steps, tol, steps, eta0, eta);
   }

@@ -23,6 +23,17 @@
 // order m = s + b.  The (s + b) x s panel of L is stored column-major with an even leading dimension (16-byte aligned
 // columns); the b x b update matrix lives in the arena until the parent has gathered it.  Only lower triangles are
 // read or written anywhere.
+//
+// Schur complement (opt-in: chol_analyse with a Schur set of ns > 0 unknowns).  The set is ordered LAST, in the caller's
+// order, as ONE final supernode with s = ns, b = 0 that is assembled and never eliminated: after factor() its panel
+// holds the lower triangle of S = A22 - A21 A11^-1 A12 (both factorization kinds).  The ordering type is applied to
+// the graph induced on the interior unknowns; for the analysis the set is a clique, so any A22 entry lies inside the
+// pattern.  That supernode is in no factor list, no sweep list, no chunk list and no packed group; the interior
+// subtrees that touch the set are its children, and their update matrices (factorization) and update vectors (forward
+// sweep) reach it through two gather tables built by the analysis (schur_*), one launch each, a lane per destination,
+// sources summed in child order: the sums of chol_assemble_kernel / chol_fwd_kernel without the walk over the
+// children.  The solve splits into condense (forward sweep over the interior, g = b2 - A21 A11^-1 b1 in the Schur
+// entries) and expand (backward sweep over the interior with x2 in the Schur entries).  ns = 0 is the plain analysis.
 #pragma once
 #include <vector>
 
@@ -85,6 +96,15 @@ struct CholSymbolic {
   // mat_long lists the rows of more than kCholLongRow entries: a wavefront multiplies each, a lane every other row.
   std::vector<int> mat_rowp, mat_col, mat_vidx, mat_long;
   int mat_maxrow = 0;  // entries of the longest row
+  // Schur set (header comment): schur = the set in the caller's order = perm[n - ns ..]; schur_sn = its supernode
+  // (-1: none).  Factorization: destination d (schur_dst, an offset into L, lower triangle of the Schur panel) adds
+  // arena[schur_src[schur_ptr[d] ..]] in child order.  Forward sweep: Schur row i adds, for right-hand side r,
+  // arena[schur_vsrc[q] + r * schur_vld[q]], q in schur_vptr[i] .. schur_vptr[i + 1], in child order.
+  int ns = 0, schur_sn = -1;
+  std::vector<int> schur;
+  std::vector<int64_t> schur_ptr, schur_src, schur_dst;
+  std::vector<int64_t> schur_vptr, schur_vsrc;
+  std::vector<int> schur_vld;
   int64_t ldy() const { return ((int64_t)n + 3) / 4 * 4 + 4; }
 };
 
@@ -93,10 +113,12 @@ struct CholLevelPlan {
   int nchunk, nsmall, nsteps;  // factorization: assembling workgroups, one-wavefront fronts, block columns
   int nfront;                  // sweeps: unpacked fronts, a workgroup each
   int ngroup;                  // packed groups: a lane each (factorization), a lane per right-hand side (sweeps)
+  int nschur;                  // 1 at the level of the Schur supernode: its gather launch (factorization, forward sweep)
 };
 inline CholLevelPlan chol_level_plan(const CholSymbolic &s, int l) {
   return {s.chunk_ptr[l + 1] - s.chunk_ptr[l], s.lev_nsmall[l], s.step_ptr[l + 1] - s.step_ptr[l],
-          s.lev_ptr[l + 1] - s.lev_ptr[l], s.glev_ptr[l + 1] - s.glev_ptr[l]};
+          s.lev_ptr[l + 1] - s.lev_ptr[l], s.glev_ptr[l + 1] - s.glev_ptr[l],
+          s.schur_sn >= 0 && s.sn_level[s.schur_sn] == l && !s.schur_dst.empty() ? 1 : 0};
 }
 enum CholForm {
   CHF_ASSEMBLE, CHF_SMALL, CHF_BLOCKED, CHF_PACK_FACTOR, CHF_FWD, CHF_BWD, CHF_PACK_FWD, CHF_PACK_BWD, CHF_COUNT
@@ -105,6 +127,9 @@ const char *chol_form_name(int form);
 // counts[form] = the levels that launch the form: in one factorization, and in one forward and one backward sweep over
 // nv right-hand sides (every slab of kCholMaxRhs columns counts its levels again)
 void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]);
+// the forms a handle with a Schur set launches on top of those: names after chol_form_name(CHF_COUNT + f)
+enum CholSchurForm { CHF_SCHUR_GATHER, CHF_SCHUR_FWD, CHF_SCHUR_COUNT };
+void chol_schur_forms(const CholSymbolic &s, int nv, int counts[CHF_SCHUR_COUNT]);
 // the levels of the factorization that launch anything
 int chol_factor_levels(const CholSymbolic &s);
 // po_sparse_chol_packing / po_csr_symbolic_frontal_packing (paropt_amd.h)
@@ -113,6 +138,9 @@ void chol_packing(const CholSymbolic &s, int64_t info[4], const int **group_firs
 
 // PO_OK or PO_ERR_ARG with a message; pure host code
 int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *perm, CholSymbolic *out);
+// the same with a Schur set of nschur distinct unknowns (header comment); NATURAL with perm: perm must end with the set
+int chol_analyse(int64_t size, const int *colp, const int *rows, int order, const int *perm, int64_t nschur,
+                 const int *schur, CholSymbolic *out);
 // the scatter table of any pattern onto the factor: entries at the permuted-lower position, in entry order per
 // destination (the reference's setValues, src/ParOptSparseCholesky.cpp:205-252); an entry outside the pattern of L is
 // PO_ERR_ARG (the reference drops it silently)
@@ -142,6 +170,19 @@ class SparseChol {
   int inertia(int64_t out[3]) const;
   int solveDevice(double *dx, int nrhs, int64_t ldx);
   int solveHost(double *x, int nrhs, int64_t ldx);
+  // SCHUR COMPLEMENT (sym.ns > 0).  getSchur*: the full symmetric ns x ns S, column-major, in the caller's Schur
+  // order, after factor() until the next setValues*.  condense / expand: the two halves of the solve, in place in the
+  // caller's numbering; between them the interior entries hold an opaque intermediate.
+  int getSchurDevice(double *dS, int64_t lds);
+  int getSchurHost(double *S, int64_t lds);
+  int condenseDevice(double *dx, int nrhs, int64_t ldx);
+  int condenseHost(double *x, int nrhs, int64_t ldx);
+  int expandDevice(double *dx, int nrhs, int64_t ldx);
+  int expandHost(double *x, int nrhs, int64_t ldx);
+  // the Schur front's assembly alone, for measurements (tools/bench_sparse_schur.py): the table-driven gather, or the
+  // same sums by chol_assemble_kernel over a chunk list of that front; `reps` launches on the stream, no host read.
+  // The front accumulates, so the values in it are meaningless afterwards: set values again before factor().
+  int schurAssemblyProbe(bool chunked, int reps);
   // RETAINED MATRIX (opt-in).  A is the symmetric matrix whose permuted lower triangle the value scatter sums into the
   // factor (the rule of chol_scatter_table).  While keeping is on, every setValues* also sums the compact values
   // `aval` (the same sums, bit for bit); factor() leaves them alone.  On an analysis-only object only the tables.
@@ -187,6 +228,10 @@ class SparseChol {
   // max|r| and max|x| per column
   void productPanel(const double *X, const double *B, double *R, int nr, unsigned long long *stats);
   int hostBuffer(int64_t count);
+  int refuseWholeSolve(const char *who) const;
+  int halfSolveCheck(const char *who, int nrhs, int64_t ldx);
+  int halfSolveHost(bool condense, double *x, int nrhs, int64_t ldx);
+  void launchSchurGather(int reps);
   bool keep = false, have_aval = false, have_anorm = false;
   double anorm = 0.0;
   DevArray<int> d_mrowp, d_mcol, d_mvidx, d_mlong, d_sn_of;
@@ -208,6 +253,12 @@ class SparseChol {
   DevArray<int> d_lev_sn, d_chunk_sn, d_chunk_c0, d_tab;
   DevArray<int> d_asm_ptr, d_asm_src;
   DevArray<int64_t> d_asm_dst;
+  // Schur set only (never allocated without one)
+  bool schur_ready = false;
+  DevArray<int64_t> d_schur_ptr, d_schur_src, d_schur_dst, d_schur_vptr, d_schur_vsrc;
+  DevArray<int> d_schur_vld, d_probe_sn, d_probe_c0;
+  DevArray<double> sbuf;
+  int64_t sbuf_cap = 0;
 };
 
 }  // namespace po

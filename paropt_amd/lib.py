@@ -318,6 +318,18 @@ SIGNATURES = {
         C.c_int, [po_sparse_chol, c_i64_p, c_int_pp, c_int_pp, c_int_pp, c_int_pp, C.POINTER(c_i64_p)]),
     "po_sparse_chol_kernel_forms": (
         C.c_int, [po_sparse_chol, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), c_int_pp]),
+    "po_sparse_chol_create_schur": (
+        C.c_int, [po_ctx, C.c_int64, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int64, c_int_p,
+                  C.POINTER(po_sparse_chol)]),
+    "po_sparse_chol_schur_info": (C.c_int, [po_sparse_chol, c_i64_p]),
+    "po_sparse_chol_schur_indices": (C.c_int, [po_sparse_chol, c_int_pp]),
+    "po_sparse_chol_get_schur": (C.c_int, [po_sparse_chol, c_double_p, C.c_int64]),
+    "po_sparse_chol_get_schur_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int64]),
+    "po_sparse_chol_solve_condense": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_solve_condense_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_solve_expand": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_solve_expand_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_schur_assembly_probe": (C.c_int, [po_sparse_chol, C.c_int, C.c_int]),
     "po_sparse_chol_destroy": (C.c_int, [po_sparse_chol]),
     "po_problem_set_bounds_mode": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_linear_constraints": (C.c_int, [po_problem, C.c_int]),

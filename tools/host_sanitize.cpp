@@ -299,6 +299,37 @@ static void test_chol_analyse() {
         if (p > c.mat_rowp[i]) CHECK(c.mat_col[p] > c.mat_col[p - 1]);
       }
     }
+    // with a Schur set (one index, 8 scattered unsorted ones, 33): the set ends perm in the order given, its supernode is
+    // the last and in no list, and every entry of the two gather tables lies inside its arena
+    const std::vector<std::vector<int>> sets = {{13}, {31, 2, 17, 39, 0, 8, 25, 20}, {}};
+    for (std::vector<int> sc : sets) {
+      if (sc.empty()) {
+        for (int k = 0; k < 33; k++) sc.push_back((7 * k + 3) % n);
+      }
+      for (int order : {PO_ORDER_ND, PO_ORDER_NATURAL}) {
+        CholSymbolic s;
+        CHECK(chol_analyse(n, colp.data(), rows.data(), order, nullptr, (int64_t)sc.size(), sc.data(), &s) == PO_OK);
+        const int ns = (int)sc.size(), S = s.schur_sn;
+        CHECK(s.ns == ns && S == s.nsn - 1 && s.sn_first[S] == n - ns && s.sn_b[S] == 0);
+        for (int k = 0; k < ns; k++) CHECK(s.perm[n - ns + k] == sc[k]);
+        for (int J : s.lev_sn) CHECK(J != S);
+        for (size_t g = 0; g < s.grp_root.size(); g++) CHECK(s.grp_root[g] < S);
+        CHECK(s.schur_ptr.size() == s.schur_dst.size() + 1 && s.schur_vptr.size() == (size_t)ns + 1);
+        CHECK(s.schur_ptr.back() == (int64_t)s.schur_src.size() && s.schur_vptr.back() == (int64_t)s.schur_vsrc.size());
+        for (int64_t off : s.schur_src) CHECK(off >= 0 && off < s.arena);
+        for (int64_t off : s.schur_dst) CHECK(off >= s.panel_off[S] && off < s.Lsize);
+        for (size_t q = 0; q < s.schur_vsrc.size(); q++) {
+          CHECK(s.schur_vsrc[q] >= 0 && s.schur_vsrc[q] + (int64_t)(kCholMaxRhs - 1) * s.schur_vld[q] < s.sol_arena);
+        }
+        int extra[CHF_SCHUR_COUNT];
+        chol_schur_forms(s, 40, extra);
+        CHECK(extra[CHF_SCHUR_GATHER] == (s.schur_dst.empty() ? 0 : 1) && extra[CHF_SCHUR_FWD] == 2 * extra[CHF_SCHUR_GATHER]);
+      }
+    }
+    std::vector<int> twice = {4, 9, 4}, outside = {4, n};
+    CholSymbolic refused;
+    CHECK(chol_analyse(n, colp.data(), rows.data(), PO_ORDER_ND, nullptr, 3, twice.data(), &refused) == PO_ERR_ARG);
+    CHECK(chol_analyse(n, colp.data(), rows.data(), PO_ORDER_ND, nullptr, 2, outside.data(), &refused) == PO_ERR_ARG);
   }
   dbg_switch_set(SW_CHOL_PACK, -1);
 }
