@@ -2076,7 +2076,10 @@ inline double ParOptProblem::checkGradients(double dh, ParOptVec *xvec, int chec
 // The constructors with (nschur, schur_vars) after perm -- no counterpart in the reference -- make the factorization
 // PARTIAL (po_sparse_chol_create_schur): the nschur unknowns are ordered last, in the order given, and left
 // uneliminated; after factor() getSchur gives S = A22 - A21 A11^-1 A12 and the solve is condense(), the caller's own
-// solve with S, expand().  solve* and solveRefined* fail on such an object, getInertia counts the interior pivots.
+// solve with S, expand().  solve* and solveRefined* fail on such an object until factorSchur() has factored S (plus an
+// optional add) on the device: then solveSchur solves with it, solve* run the whole solve (bit for bit condense,
+// solveSchur, expand) and solveRefined* work when factorSchur was called without an add.  getInertia counts the
+// interior pivots, getSchurInertia those of S.
 enum ParOptOrderingType { PAROPT_NATURAL_ORDER, PAROPT_AMD_ORDER, PAROPT_ND_ORDER };
 enum ParOptFactorizationType { PAROPT_CHOLESKY_LLT, PAROPT_CHOLESKY_LDLT };
 
@@ -2191,6 +2194,38 @@ class ParOptSparseCholesky {
   int expand(ParOptScalar *x, int nrhs = 1) { return report(po_sparse_chol_solve_expand(h, x, nrhs, size)); }
   int expandDevice(ParOptScalar *dx, int nrhs = 1) {
     return report(po_sparse_chol_solve_expand_device(h, dx, nrhs, size));
+  }
+  // Factored Schur complement (po_sparse_chol_schur_factor and what follows it in paropt_amd.h), valid after factor()
+  // until the next setValues.  factorSchur: S~ = S + add factored on the device in a buffer of its own, in the kind of
+  // the factor() that produced S; add is NULL or a symmetric nschur x nschur matrix in the order of schur_vars,
+  // column-major with leading dimension ldadd (< 0: nschur), of which the lower triangle is read.  Returns info like
+  // factor(): 0, or 1 + the permuted index size - nschur + k of the first pivot replaced; -1 with a message on misuse.
+  // getSchur is untouched by it, and it may be called again with another add.  solveSchur: S~ x2 = g in place on
+  // nschur-vectors, nrhs columns at x2 + j * nschur.  getSchurInertia: the pivots of S~ (they sum to nschur; the LLT
+  // rule of getInertia).  The *Device forms take DEVICE arrays.
+  int factorSchur(const ParOptScalar *add = NULL, int ldadd = -1) {
+    int info = 0;
+    if (report(po_sparse_chol_schur_factor(h, add, ldadd < 0 ? getNumSchur() : ldadd, &info)) != 0) return -1;
+    return info;
+  }
+  int factorSchurDevice(const ParOptScalar *dadd = NULL, int ldadd = -1) {
+    int info = 0;
+    if (report(po_sparse_chol_schur_factor_device(h, dadd, ldadd < 0 ? getNumSchur() : ldadd, &info)) != 0) return -1;
+    return info;
+  }
+  int solveSchur(ParOptScalar *x2, int nrhs = 1) {
+    return report(po_sparse_chol_schur_solve(h, x2, nrhs, getNumSchur()));
+  }
+  int solveSchurDevice(ParOptScalar *dx2, int nrhs = 1) {
+    return report(po_sparse_chol_schur_solve_device(h, dx2, nrhs, getNumSchur()));
+  }
+  int getSchurInertia(int *pos, int *neg, int *replaced) {
+    int64_t in[3] = {0, 0, 0};
+    const int rc = report(po_sparse_chol_schur_inertia(h, in));
+    if (pos) *pos = (int)in[0];
+    if (neg) *neg = (int)in[1];
+    if (replaced) *replaced = (int)in[2];
+    return rc;
   }
   void getInfo(int *_size, int *_num_snodes, int *_nnzL) {
     int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -1169,7 +1169,8 @@ int po_sparse_chol_kernel_forms(po_sparse_chol h, int nv, int *count, const char
  * *info of po_sparse_chol_factor and po_sparse_chol_inertia speak of the INTERIOR pivots only: the three counts sum
  * to size - nschur.  The diagonal shift reaches A22 like any diagonal; keeping the matrix and po_sparse_chol_matvec
  * see the whole A.  po_sparse_chol_solve* and po_sparse_chol_solve_refined* answer PO_ERR_ARG on such a handle: the
- * solve is the two halves below around the caller's own solve with S.
+ * solve is the two halves below around the caller's own solve with S -- or po_sparse_chol_schur_factor first
+ * ("FACTORED SCHUR COMPLEMENT" below), after which the handle solves with S itself.
  * The Schur supernode's children -- every interior subtree that touches the set -- are gathered by one table-driven
  * launch, a lane per entry of S summing its sources in child order: deterministic and independent of the packing
  * cap.
@@ -1203,6 +1204,45 @@ int po_sparse_chol_schur_assembly_probe(po_sparse_chol h, int chunked, int reps)
 /* On a handle with a Schur set po_sparse_chol_kernel_forms reports two more forms after the eight above:
  * "schur_gather" (the factorization's gather launch) and "schur_fwd" (the gather of the update vectors in
  * _solve_condense, once per slab). */
+/* FACTORED SCHUR COMPLEMENT (no counterpart in the reference; opt-in: a handle that never calls these entries
+ * allocates, launches and computes what it did before).
+ * _schur_factor is valid after po_sparse_chol_factor until the next _set_values (PO_ERR_ARG with a message otherwise,
+ * and on a handle without a Schur set).  It copies the lower triangle of S into a buffer of its own (nschur x nschur
+ * doubles, allocated at the first call, freed by _destroy; PO_ERR_ARG naming the bytes if it cannot be had), adds the
+ * lower triangle of `add` -- a symmetric nschur x nschur matrix in the order of the set, column-major with leading
+ * dimension ldadd >= nschur (PO_ERR_ARG below that); NULL: nothing, ldadd is then ignored -- entry by entry, and
+ * factors S~ = S + add in place, by the block-column kernels of the fronts and in the kind of the
+ * po_sparse_chol_factor that produced S.  PO_CHOL_LLT: S~ = L2 L2^T, a non-positive pivot k is replaced by 1 and
+ * *info = 1 + (size - nschur + k), its permuted index (0: none; the first).  PO_CHOL_LDLT: S~ = L2 Sigma2 L2^T, no
+ * pivoting, a zero or NaN pivot is replaced by +1 and reported the same way.  _schur_factor takes a host array,
+ * _schur_factor_device a device array; both return after the factorization has finished.
+ * The Schur front itself is left alone: po_sparse_chol_get_schur* returns S, the same bits, before and after, and
+ * _schur_factor may be called again after the same po_sparse_chol_factor with another add (a new constraint block or
+ * regularisation costs nschur^3 / 3 flops, not a factorization of the interior).  po_sparse_chol_set_values* and
+ * po_sparse_chol_factor end the validity of the factored S~.
+ * _schur_solve: S~ x2 = g in place on nschur-vectors in the order of the set, nrhs columns at x2 + j * ldx2
+ * (PO_ERR_ARG for nrhs < 0, for nrhs > 1 with ldx2 < nschur, and before _schur_factor); a column has the same bits
+ * whatever nrhs is.  With nschur == size the handle is a dense solver on the device.
+ * THE WHOLE SOLVE.  After _schur_factor, po_sparse_chol_solve* work on the handle: per slab of 32 columns the
+ * interior's forward levels, the gather of their update vectors, the dense forward sweep, the signs, the dense
+ * backward sweep and the interior's backward levels -- bit for bit what _solve_condense, _schur_solve and
+ * _solve_expand give.  po_sparse_chol_solve_refined* work too when _schur_factor was called WITHOUT add (the retained
+ * A is then the matrix that is solved; the diagonal shift is the perturbation being refined away, as on a plain
+ * handle); after a _schur_factor with add they answer PO_ERR_ARG.  Before _schur_factor both keep refusing as above.
+ * _schur_inertia: {positive, negative, replaced} pivots of S~, summing to nschur; PO_CHOL_LLT as
+ * po_sparse_chol_inertia: {nschur, 0, 0}, or PO_ERR_ARG after a factorization that replaced pivots.
+ * po_sparse_chol_inertia keeps counting the interior's pivots only.
+ * _schur_solve_info: {W, the panel width of the dense sweeps; the kernel launches of one forward and one backward
+ * dense sweep over one slab, 2 (2 ceil(nschur / W) - 1), computed by the loop that launches them (the sign pass of
+ * PO_CHOL_LDLT not counted; 0 without a set); the bytes of the buffer (0 before the first _schur_factor); 1 while S~
+ * is factored}.  It works on analysis-only handles (the first two entries); the other five entries answer PO_ERR_ARG
+ * there.  po_sparse_chol_kernel_forms and work_bytes do not change. */
+int po_sparse_chol_schur_factor(po_sparse_chol h, const double *add, int64_t ldadd, int *info);
+int po_sparse_chol_schur_factor_device(po_sparse_chol h, const double *dadd, int64_t ldadd, int *info);
+int po_sparse_chol_schur_solve(po_sparse_chol h, double *x2, int nrhs, int64_t ldx2);
+int po_sparse_chol_schur_solve_device(po_sparse_chol h, double *dx2, int nrhs, int64_t ldx2);
+int po_sparse_chol_schur_inertia(po_sparse_chol h, int64_t inertia[3]);
+int po_sparse_chol_schur_solve_info(po_sparse_chol h, int64_t info[4]);
 int po_sparse_chol_destroy(po_sparse_chol h); /* NULL is fine */
 
 #ifdef __cplusplus

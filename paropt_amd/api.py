@@ -1538,7 +1538,9 @@ class SparseCholesky:
     order given, and left uneliminated, so after factor() the device holds S = A22 - A21 A11^-1 A12 (schur(),
     schur_device()).  The ordering type then applies to the interior unknowns; "natural" with perm needs a perm that
     ends with the set.  solve() and solve_refined() raise on such an object: the solve is condense(), the caller's own
-    solve with S, expand().  inertia() counts the interior pivots only."""
+    solve with S, expand() -- until factor_schur() has factored S (plus an optional add) on the device: then
+    schur_solve() solves with it and solve() / solve_refined() run the whole solve.  inertia() counts the interior
+    pivots only, schur_inertia() those of S."""
 
     ORDERS = {"natural": 0, "amd": 1, "nd": 2}
     FACTORIZATIONS = {"llt": 0, "ldlt": 1}
@@ -1656,6 +1658,73 @@ class SparseCholesky:
     def expand_tensor(self, t):
         """expand() in place on a contiguous float64 torch tensor of shape (n,) or (nrhs, n) on the device."""
         return self._half_tensor(lib.po_sparse_chol_solve_expand_device, "expand_tensor", t)
+
+    # ---- factored Schur complement (po_sparse_chol_schur_factor and what follows it) ----
+    def factor_schur(self, add=None):
+        """Factor S~ = S + add on the device, in a buffer of its own and in the kind of the factor() that produced S;
+        valid after factor() until the next set_values.  add: None, or a symmetric (num_schur, num_schur) array in the
+        order of the set (its lower triangle is read).  Returns 0, or 1 + the permuted index size - num_schur + k of
+        the first pivot replaced.  schur() is untouched, and factor_schur may be called again with another add.
+        Afterwards solve() / solve_tensor() work on this object, solve_refined() too when add is None."""
+        info = C.c_int()
+        if add is None:
+            check(lib.po_sparse_chol_schur_factor(self._h, None, 0, C.byref(info)))
+            return info.value
+        ns = self.num_schur
+        a = np.asfortranarray(add, dtype=np.float64)
+        if a.shape != (ns, ns):
+            raise ValueError("factor_schur: add must have shape (num_schur, num_schur)")
+        check(lib.po_sparse_chol_schur_factor(self._h, a.ctypes.data_as(L.c_double_p), max(ns, 1), C.byref(info)))
+        return info.value
+
+    def factor_schur_tensor(self, add=None):
+        """factor_schur with add a contiguous float64 torch tensor of shape (num_schur, num_schur) on the context's
+        device (symmetric: rows and columns are interchangeable), or None."""
+        info = C.c_int()
+        ns = self.num_schur
+        ptr = None
+        if add is not None:
+            if add.dim() != 2 or tuple(add.shape) != (ns, ns):
+                raise ValueError("factor_schur_tensor: add must have shape (num_schur, num_schur)")
+            ptr = self._tensor_ptr(add, ns * ns, "factor_schur_tensor")
+        check(lib.po_sparse_chol_schur_factor_device(self._h, ptr, max(ns, 1), C.byref(info)))
+        return info.value
+
+    def schur_solve(self, g):
+        """x2 = S~^-1 g for g of shape (num_schur,) or (nrhs, num_schur), the order of the set; returns a new array."""
+        x = np.array(g, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (1, 2) or x.shape[-1] != self.num_schur:
+            raise ValueError("schur_solve: g must have shape (num_schur,) or (nrhs, num_schur)")
+        nrhs = 1 if x.ndim == 1 else x.shape[0]
+        check(lib.po_sparse_chol_schur_solve(self._h, x.ctypes.data_as(L.c_double_p), nrhs, self.num_schur))
+        return x
+
+    def schur_solve_tensor(self, t):
+        """schur_solve in place on a contiguous float64 torch tensor of shape (num_schur,) or (nrhs, num_schur) on the
+        context's device."""
+        if t.dim() not in (1, 2) or t.shape[-1] != self.num_schur:
+            raise ValueError("schur_solve_tensor: t must have shape (num_schur,) or (nrhs, num_schur)")
+        nrhs = 1 if t.dim() == 1 else t.shape[0]
+        ptr = self._tensor_ptr(t, nrhs * self.num_schur, "schur_solve_tensor")
+        check(lib.po_sparse_chol_schur_solve_device(self._h, ptr, nrhs, self.num_schur))
+        self.ctx.synchronize()
+        return t
+
+    def schur_inertia(self):
+        """(positive, negative, replaced) pivots of the last factor_schur(); they sum to num_schur.  The "llt" rule of
+        inertia(): (num_schur, 0, 0), or an error after a factorization that replaced pivots."""
+        out = (C.c_int64 * 3)()
+        check(lib.po_sparse_chol_schur_inertia(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def schur_solve_info(self):
+        """{"panel_width" (W of the dense sweeps), "launches" (of one forward and one backward dense sweep over one
+        slab), "factor_bytes" (of the buffer of the factored S~, 0 before the first factor_schur), "factored"}; the
+        first two need no device."""
+        info = (C.c_int64 * 4)()
+        check(lib.po_sparse_chol_schur_solve_info(self._h, info))
+        return {"panel_width": int(info[0]), "launches": int(info[1]), "factor_bytes": int(info[2]),
+                "factored": bool(info[3])}
 
     def set_factorization(self, kind):
         """ "llt" or "ldlt" (or PO_CHOL_LLT = 0 / PO_CHOL_LDLT = 1), read by the next factor(); allowed at any time,

@@ -111,6 +111,39 @@ int po_sparse_chol_schur_assembly_probe(po_sparse_chol h, int chunked, int reps)
   PO_CHECK_NUMERIC(h);
   return h->c->schurAssemblyProbe(chunked != 0, reps);
 }
+// no counterpart in the reference: factoring and solving with S on the device (paropt_amd.h, "FACTORED SCHUR COMPLEMENT")
+int po_sparse_chol_schur_factor(po_sparse_chol h, const double *add, int64_t ldadd, int *info) {
+  PO_CHECK_NUMERIC(h);
+  return h->c->schurFactorHost(add, ldadd, info);
+}
+int po_sparse_chol_schur_factor_device(po_sparse_chol h, const double *dadd, int64_t ldadd, int *info) {
+  PO_CHECK_NUMERIC(h);
+  return h->c->schurFactorDevice(dadd, ldadd, info);
+}
+int po_sparse_chol_schur_solve(po_sparse_chol h, double *x2, int nrhs, int64_t ldx2) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->schurFactored() && nrhs > 0) PO_CHECK_PTR(x2);
+  return h->c->schurSolveHost(x2, nrhs, ldx2);
+}
+int po_sparse_chol_schur_solve_device(po_sparse_chol h, double *dx2, int nrhs, int64_t ldx2) {
+  PO_CHECK_NUMERIC(h);
+  if (h->c->schurFactored() && nrhs > 0) PO_CHECK_PTR(dx2);
+  return h->c->schurSolveDevice(dx2, nrhs, ldx2);
+}
+int po_sparse_chol_schur_inertia(po_sparse_chol h, int64_t inertia[3]) {
+  PO_CHECK_NUMERIC(h);
+  PO_CHECK_PTR(inertia);
+  return h->c->schurInertia(inertia);
+}
+int po_sparse_chol_schur_solve_info(po_sparse_chol h, int64_t info[4]) {
+  PO_CHECK_PTR(h);
+  PO_CHECK_PTR(info);
+  info[0] = h->c->sym.schur_w;
+  info[1] = po::chol_schur_solve_launches(h->c->sym);
+  info[2] = h->c->schurFactorBytes();
+  info[3] = h->c->schurFactored() ? 1 : 0;
+  return PO_OK;
+}
 // setValues, ParOptSparseCholesky.h:37-38
 int po_sparse_chol_set_values(po_sparse_chol h, int64_t n, const int *colp, const int *rows, const double *vals) {
   PO_CHECK_NUMERIC(h);

@@ -71,6 +71,7 @@ static const SwitchDef kSwitches[] = {
     {SW_USER_TIMING, "PAROPT_AMD_USER_TIMING", 0, true},
     {SW_DUMP_LONG_SOLVES, "PAROPT_AMD_DUMP_LONG_SOLVES", -1, false},
     {SW_CHOL_PACK, nullptr, kCholPackMax, false},
+    {SW_CHOL_SCHUR_W, nullptr, kCholSchurW, false},
 };
 static struct {
   int value = -1;  // >= 0: set through po_debug_set_switch

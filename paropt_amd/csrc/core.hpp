@@ -289,7 +289,7 @@ enum DbgSwitch {
   SW_NO_FUSED_MERIT = 23, SW_NO_LEAN_STEP = 24, SW_NO_RECOMPUTE_DT = 25, SW_NO_FUSED_UPDATE = 26,
   SW_NO_CSR_GROUPS = 27, SW_NO_FRONTS = 28, SW_FORCE_RCCL = 29, SW_RCCL_ALLGATHER = 30, SW_NO_DIRECT_RED = 31,
   SW_NO_FLAG_POLL = 32, SW_NO_BATCH = 33, SW_HOST_TRACE = 34, SW_SYNC_TRACE = 35, SW_USER_TIMING = 36,
-  SW_DUMP_LONG_SOLVES = 37, SW_CHOL_PACK = 38, SW_COUNT = 39
+  SW_DUMP_LONG_SOLVES = 37, SW_CHOL_PACK = 38, SW_CHOL_SCHUR_W = 39, SW_COUNT = 40
 };
 // the value set through po_debug_set_switch, else the environment variable, else the default
 int dbg_switch(DbgSwitch id);

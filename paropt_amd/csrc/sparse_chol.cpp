@@ -569,6 +569,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
   auto nblk_of = [&](int J) { return (s.sn_first[J + 1] - s.sn_first[J] + kCholNB - 1) / kCholNB; };
   // packed groups: supernodes are in postorder, so the subtree of J is the range [J - cnt[J] + 1, J]
   s.pack_cap = std::max(0, dbg_switch(SW_CHOL_PACK));
+  s.schur_w = std::max(1, dbg_switch(SW_CHOL_SCHUR_W) / kCholNB) * kCholNB;  // (a multiple of the block width)
   s.front_order.resize(nsn);
   for (int J = 0; J < nsn; J++) s.front_order[J] = order_of(J);
   std::vector<int> grp_of(nsn, -1);
@@ -712,8 +713,7 @@ int chol_analyse(int64_t size, const int *colp, const int *rows, int order, cons
       s.tab.push_back(0);
       for (int a = 0; a < nact; a++) {
         const int J = s.lev_sn[b0 + a], sz = s.sn_first[J + 1] - s.sn_first[J], m = sz + s.sn_b[J];
-        const int r0 = std::min(sz, (kb + 1) * kCholNB);
-        run += (m - r0 + kCholTile - 1) / kCholTile;
+        run += chol_row_tiles(sz, m, kb);
         if (run > 2000000000LL) {
           set_error("sparse Cholesky: a level has more than 2e9 row tiles");
           return PO_ERR_ARG;
@@ -769,6 +769,11 @@ void chol_packing(const CholSymbolic &s, int64_t info[4], const int **group_firs
   if (group_level) *group_level = s.grp_level.data();
   if (front_order) *front_order = s.front_order.data();
   if (upd_off) *upd_off = s.upd_off.data();
+}
+
+int chol_schur_solve_launches(const CholSymbolic &s) {
+  const auto none = [](int, int) {};
+  return chol_schur_panels(s.ns, s.schur_w, true, none, none) + chol_schur_panels(s.ns, s.schur_w, false, none, none);
 }
 
 int chol_factor_levels(const CholSymbolic &s) {

@@ -953,6 +953,184 @@ __global__ __launch_bounds__(256) void chol_schur_copy_kernel(const double *__re
   }
 }
 
+// ---- factored Schur complement: the dense sweeps (sparse_chol.hpp, "FACTORED SCHUR COMPLEMENT") ----------------------
+// F = L2 (lower triangle, column-major, leading dimension ldF) of S~ = L2 L2^T or L2 Sigma2 L2^T, factored by the
+// block-column kernels above through a one-front table.  A front of the elimination tree is swept by ONE workgroup
+// (chol_fwd / chol_bwd); here the triangle is cut into panels of W columns (chol_schur_panels) and everything outside a
+// panel's W x W diagonal block is spread over the device, a launch at a time.  Workgroups are ordered by launch
+// boundaries only: no flags, no spin waits, no atomics.  Y is the ns Schur rows of a slab, nr <= kCholMaxRhs columns of
+// leading dimension ldy, solved in place.  Every (row, right-hand side) is one chain of fused multiply-adds in a fixed
+// order (plus a fixed tree in the backward gather), whatever nr or the grid: a column's bits do not depend on nr.
+//   chol_schur_fwd_diag     one workgroup: the diagonal block, its 32-blocks walked in LDS as chol_fwd_panel_kernel
+//                           does (stride-33 triangle, half a wavefront per right-hand side, reciprocal diagonal), the
+//                           rows of the block below each 32-block updated by all 256 threads.  Latency-bound: W
+//                           dependent substitution steps.
+//   chol_schur_fwd_update   all rows below the panel, right-looking: a wavefront per (64 rows, 8 right-hand sides),
+//                           lane = row, y -= sum over the panel's columns in ascending order; the panel's y through LDS
+//                           as broadcast reads, the rows of L2 as 512-byte runs.  Reads the panel's part of L2 once per
+//                           group of 8 columns (the groups of a tile share it in L2): 2 flop per 8 bytes and right-hand
+//                           side, memory-bound at every nr <= 32.
+//   chol_schur_bwd_gather   left-looking: a workgroup per (column of the panel, 8 right-hand sides) forms
+//                           y_k - sum_{i below the panel} l_ik x_i down the contiguous column, thread t rows t, t + 256,
+//                           ..., then the xor tree of a wavefront and ((w0 + w1) + (w2 + w3)).  Memory-bound like the
+//                           update.
+//   chol_schur_bwd_diag     one workgroup: the diagonal block from its last 32-block, chol_bwd_panel_kernel's walk.
+// LDS: D and rd as in the panel kernels (no conflicts in either direction, see there); yb / z are [right-hand side][33].
+
+// F <- lower(S) (+ lower(add)): thread = row, blockIdx.y strides the columns
+__global__ __launch_bounds__(256) void chol_schur_load_kernel(const double *__restrict__ P, int ld, int ns,
+                                                              const double *__restrict__ add, int64_t ldadd,
+                                                              double *__restrict__ F, int ldF) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= ns) return;
+  for (int col = blockIdx.y; col <= row; col += gridDim.y) {
+    double v = P[(int64_t)col * ld + row];
+    if (add) v += add[(int64_t)col * ldadd + row];
+    F[(int64_t)col * ldF + row] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_schur_fwd_diag_kernel(const double *__restrict__ F, int ldF, int p0, int wp,
+                                                                  double *Y, int64_t ldy, int nr) {
+  __shared__ double D[kCholNB * kLdsLd], yb[kCholMaxRhs * kLdsLd], rd[kCholNB];
+  const double *__restrict__ P = F + (int64_t)p0 * ldF + p0;
+  double *Yp = Y + p0;
+  const int tid = threadIdx.x, half = tid >> 5, hl = tid & 31;
+  for (int k0 = 0; k0 < wp; k0 += kCholNB) {
+    const int w = min(kCholNB, wp - k0);
+    load_triangle_rd(D, rd, P + (int64_t)k0 * ldF + k0, ldF, w);
+    __syncthreads();
+    for (int r0 = 0; r0 < nr; r0 += 8) {  // (uniform trip count: the shuffles below see whole half-wavefronts)
+      const int r = r0 + half;
+      const bool live = r < nr && hl < w;
+      double *yr = Yp + k0 + (int64_t)(r < nr ? r : 0) * ldy;
+      double y = live ? yr[hl] : 0.0;
+      for (int j = 0; j < w; j++) {
+        const double yj = __shfl(y, j, 32) * rd[j];
+        if (hl == j) y = yj;
+        if (hl > j && hl < w) y -= D[j * kLdsLd + hl] * yj;
+      }
+      if (live) {
+        yr[hl] = y;
+        yb[r * kLdsLd + hl] = y;
+      }
+    }
+    __syncthreads();
+    const int i0 = k0 + w, nrow = wp - i0;
+    for (int idx = tid; idx < nrow * nr; idx += 256) {
+      const int i = i0 + idx % nrow, r = idx / nrow;
+      const double *__restrict__ yk = yb + r * kLdsLd;
+      double acc = 0.0;
+      for (int k = 0; k < w; k++) acc = fma(P[(int64_t)(k0 + k) * ldF + i], yk[k], acc);
+      Yp[i + (int64_t)r * ldy] -= acc;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(64) void chol_schur_fwd_update_kernel(const double *__restrict__ F, int ldF, int ns, int p0,
+                                                                   int wp, double *Y, int64_t ldy, int nr) {
+  __shared__ double yb[kCholSchurCols * kLdsLd];
+  const int lane = threadIdx.x;
+  const int row = p0 + wp + blockIdx.x * kCholSchurRows + lane;
+  const int c0 = blockIdx.y * kCholSchurCols, ncol = min(kCholSchurCols, nr - c0);
+  const bool live = row < ns;
+  const double *__restrict__ Frow = F + (int64_t)p0 * ldF + (live ? row : p0);
+  double acc[kCholSchurCols];
+#pragma unroll
+  for (int c = 0; c < kCholSchurCols; c++) acc[c] = 0.0;
+  for (int k0 = 0; k0 < wp; k0 += kCholNB) {
+    const int w = min(kCholNB, wp - k0);
+    __syncthreads();  // (the chunk before has been read)
+    for (int idx = lane; idx < ncol * w; idx += 64) {
+      const int c = idx / w, k = idx % w;
+      yb[c * kLdsLd + k] = Y[p0 + k0 + k + (int64_t)(c0 + c) * ldy];
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int k = 0; k < w; k++) {
+      const double f = Frow[(int64_t)(k0 + k) * ldF];
+#pragma unroll
+      for (int c = 0; c < kCholSchurCols; c++) {
+        if (c < ncol) acc[c] = fma(f, yb[c * kLdsLd + k], acc[c]);
+      }
+    }
+  }
+  if (!live) return;
+#pragma unroll
+  for (int c = 0; c < kCholSchurCols; c++) {
+    if (c < ncol) Y[row + (int64_t)(c0 + c) * ldy] -= acc[c];
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_schur_bwd_gather_kernel(const double *__restrict__ F, int ldF, int ns,
+                                                                    int p0, int wp, double *Y, int64_t ldy, int nr) {
+  __shared__ double part[4 * kCholSchurCols];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int col = p0 + blockIdx.x;
+  const int c0 = blockIdx.y * kCholSchurCols, ncol = min(kCholSchurCols, nr - c0);
+  const double *__restrict__ Fc = F + (int64_t)col * ldF;
+  const double *Yc = Y + (int64_t)c0 * ldy;
+  double acc[kCholSchurCols];
+#pragma unroll
+  for (int c = 0; c < kCholSchurCols; c++) acc[c] = 0.0;
+  for (int i = p0 + wp + tid; i < ns; i += 256) {
+    const double f = Fc[i];
+#pragma unroll
+    for (int c = 0; c < kCholSchurCols; c++) {
+      if (c < ncol) acc[c] = fma(f, Yc[i + (int64_t)c * ldy], acc[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kCholSchurCols; c++) {
+    double sum = acc[c];
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    if (lane == 0) part[wave * kCholSchurCols + c] = sum;
+  }
+  __syncthreads();
+  if (tid < ncol) {
+    const double sum = (part[tid] + part[kCholSchurCols + tid]) +
+                       (part[2 * kCholSchurCols + tid] + part[3 * kCholSchurCols + tid]);
+    Y[col + (int64_t)(c0 + tid) * ldy] -= sum;
+  }
+}
+
+__global__ __launch_bounds__(256) void chol_schur_bwd_diag_kernel(const double *__restrict__ F, int ldF, int p0, int wp,
+                                                                  double *Y, int64_t ldy, int nr) {
+  __shared__ double D[kCholNB * kLdsLd], z[kCholMaxRhs * kLdsLd], rd[kCholNB];
+  const double *__restrict__ P = F + (int64_t)p0 * ldF + p0;
+  double *Yp = Y + p0;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = tid >> 5, hl = tid & 31;
+  const int nblk = (wp + kCholNB - 1) / kCholNB;
+  for (int kb = nblk - 1; kb >= 0; kb--) {
+    const int k0 = kb * kCholNB, w = min(kCholNB, wp - k0);
+    load_triangle_rd(D, rd, P + (int64_t)k0 * ldF + k0, ldF, w);
+    // z = y_block - L21^T x over the later 32-blocks of the panel: a wavefront per (column, right-hand side)
+    for (int p = wave; p < w * nr; p += 4) {
+      const int k = p % w, r = p / w;
+      const double *__restrict__ col = P + (int64_t)(k0 + k) * ldF;
+      const double *yr = Yp + (int64_t)r * ldy;
+      double sum = 0.0;
+      for (int i = k0 + w + lane; i < wp; i += 64) sum = fma(col[i], yr[i], sum);
+      for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+      if (lane == 0) z[r * kLdsLd + k] = yr[k0 + k] - sum;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < nr; r0 += 8) {
+      const int r = r0 + half;
+      const bool live = r < nr && hl < w;
+      double x = live ? z[r * kLdsLd + hl] : 0.0;
+      for (int j = w - 1; j >= 0; j--) {
+        const double xj = __shfl(x, j, 32) * rd[j];
+        if (hl == j) x = xj;
+        if (hl < j) x -= D[hl * kLdsLd + j] * xj;
+      }
+      if (live) Yp[k0 + hl + (int64_t)r * ldy] = x;
+    }
+    __syncthreads();
+  }
+}
+
 // ---- retained matrix: value compaction, diagonal shift, product, residual, norms -------------------------------------
 // (sparse_chol.hpp, "RETAINED MATRIX").  All panels are in elimination order, column-major, leading dimension ld.
 //
@@ -1204,7 +1382,7 @@ int SparseChol::scatter(const int *ptr, const int64_t *dst, const int *src, int6
   }
   have_values = true;
   factored = false;
-  schur_ready = false;
+  schur_ready = schur_factored = false;
   return PO_OK;
 }
 
@@ -1374,6 +1552,7 @@ int SparseChol::factor(int *info) {
   factored = true;
   factored_kind = kind;
   schur_ready = sym.ns > 0;
+  schur_factored = false;
   // (the counts came with the flag read: nothing of size n goes to the host).  The unsigned kernels count nothing:
   // a Cholesky factorization that replaced no pivot has n positive ones, one that did has no inertia to report.
   inertia_[1] = ldlt ? flag[2] : 0;
@@ -1400,17 +1579,24 @@ void SparseChol::solvePanel(double *P, int nr) {
   const CholPtrs none = {};
   launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, P, ldy,
                 chol_fwd_kernel, P, ldy, nr);
-  if (factored_kind == PO_CHOL_LDLT) {
+  double *P2 = P + (sym.n - sym.ns);  // the Schur rows (a handle with a factored S~ only: refuseWholeSolve)
+  if (sym.ns > 0) {
+    launchSchurFwd(P, nr);
+    schurSweep(P2, ldy, nr, true);
+  }
+  if (factored_kind == PO_CHOL_LDLT) {  // (the interior's signs and, behind them, those of S~)
     hipLaunchKernelGGL(chol_sign_kernel, dim3(pg), dim3(256), 0, st, P, ldy, (const double *)d_sign, sym.n, nr);
   }
+  if (sym.ns > 0) schurSweep(P2, ldy, nr, false);
   launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, false, nr, chol_pack_bwd_kernel<false>, none, P, ldy,
                 chol_bwd_kernel, P, ldy, nr);
 }
 
 int SparseChol::refuseWholeSolve(const char *who) const {
-  if (sym.ns == 0) return PO_OK;
+  if (sym.ns == 0 || schur_factored) return PO_OK;
   set_error("sparse Cholesky: %s on a handle with a Schur set: the Schur supernode is not eliminated, the solve is its "
-            "two halves solve_condense() and solve_expand() around the caller's own solve with S (get_schur())", who);
+            "two halves solve_condense() and solve_expand() around the caller's own solve with S (get_schur()), or "
+            "schur_factor() first: the handle then factors and solves with S itself", who);
   return PO_ERR_ARG;
 }
 
@@ -1570,6 +1756,16 @@ int SparseChol::halfSolveCheck(const char *who, int nrhs, int64_t ldx) {
   return PO_OK;
 }
 
+// the children's update vectors into the Schur rows of the panel P (after the interior's forward levels)
+void SparseChol::launchSchurFwd(double *P, int nr) {
+  for (int l = 0; l < sym.nlev; l++) {
+    if (chol_level_plan(sym, l).nschur == 0) continue;
+    hipLaunchKernelGGL(chol_schur_fwd_kernel, dim3((unsigned)(((int64_t)sym.ns * nr + 255) / 256)), dim3(256), 0,
+                       ctx->stream, (const int64_t *)d_schur_vptr, (const int64_t *)d_schur_vsrc,
+                       (const int *)d_schur_vld, sym.ns, sym.n - sym.ns, (const double *)arena, P, sym.ldy(), nr);
+  }
+}
+
 // Schur entries: g = b2 - A21 A11^-1 b1; interior entries: the forward-swept intermediate, which expand reads
 int SparseChol::condenseDevice(double *dx, int nrhs, int64_t ldx) {
   PO_TRY(halfSolveCheck("solve_condense()", nrhs, ldx));
@@ -1586,12 +1782,7 @@ int SparseChol::condenseDevice(double *dx, int nrhs, int64_t ldx) {
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 0);
     launch_levels(sym, st, d, d_glev_first, d_glev_root, d_lev_sn, true, nr, chol_pack_fwd_kernel<false>, none, P, ldy,
                   chol_fwd_kernel, P, ldy, nr);
-    for (int l = 0; l < sym.nlev; l++) {
-      if (chol_level_plan(sym, l).nschur == 0) continue;
-      hipLaunchKernelGGL(chol_schur_fwd_kernel, dim3((unsigned)(((int64_t)sym.ns * nr + 255) / 256)), dim3(256), 0, st,
-                         (const int64_t *)d_schur_vptr, (const int64_t *)d_schur_vsrc, (const int *)d_schur_vld, sym.ns,
-                         sym.n - sym.ns, (const double *)arena, P, ldy, nr);
-    }
+    launchSchurFwd(P, nr);
     hipLaunchKernelGGL(chol_permute_kernel, dim3(pg), dim3(256), 0, st, P, ldy, x, ldx, d_perm, sym.n, nr, 1);
     PO_HIP(hipGetLastError());
   }
@@ -1639,6 +1830,208 @@ int SparseChol::halfSolveHost(bool condense, double *x, int nrhs, int64_t ldx) {
 }
 int SparseChol::condenseHost(double *x, int nrhs, int64_t ldx) { return halfSolveHost(true, x, nrhs, ldx); }
 int SparseChol::expandHost(double *x, int nrhs, int64_t ldx) { return halfSolveHost(false, x, nrhs, ldx); }
+
+// ---- factored Schur complement: S~ = S + add in a buffer of its own, the dense sweeps --------------------------------
+int SparseChol::schurFactorCheck(const char *who, int64_t ldadd) {
+  if (sym.ns == 0) {
+    set_error("sparse Cholesky: %s needs a handle created with a Schur set", who);
+    return PO_ERR_ARG;
+  }
+  if (!schur_ready) {
+    set_error("sparse Cholesky: %s is valid after factor() until the next set_values", who);
+    return PO_ERR_ARG;
+  }
+  if (ldadd < sym.ns) {
+    set_error("sparse Cholesky: %s with ldadd %lld for a Schur set of %d", who, (long long)ldadd, sym.ns);
+    return PO_ERR_ARG;
+  }
+  return PO_OK;
+}
+
+// the block-column kernels of launchFactor on the one front F (first = {n - ns, n}, nb = 0)
+template <bool kSigned>
+void SparseChol::launchSchurFactor(int *flag) {
+  hipStream_t st = ctx->stream;
+  double *const sgn = kSigned ? d_sign : nullptr;
+  const int ns = sym.ns;
+  const int *ti = ftab_i;
+  const int64_t *tl = ftab_l;
+  const CholDev d = {ti, ti + 2, ti + 3, ti + 4, tl, tl + 1, tl, tl, nullptr, nullptr, nullptr, nullptr, F, F};
+  const int *list = ti + 5;
+  if (ns <= kCholSmall) {
+    hipLaunchKernelGGL(chol_small_kernel<kSigned>, dim3(1), dim3(64), 0, st, d, list, flag, sgn);
+    return;
+  }
+  const int steps = (ns + kCholNB - 1) / kCholNB;
+  for (int kb = 0; kb < steps; kb++) {
+    hipLaunchKernelGGL(chol_diag_kernel<kSigned>, dim3(1), dim3(64), 0, st, d, list, kb, flag, sgn);
+    const int total = chol_row_tiles(ns, ns, kb);
+    if (total > 0) {
+      const int *dtab = ti + 6 + 2 * kb;  // {0, total}
+      hipLaunchKernelGGL(chol_trsm_kernel<kSigned>, dim3(total), dim3(kCholTile), 0, st, d, list, dtab, 1, kb,
+                         (const double *)sgn);
+      hipLaunchKernelGGL(chol_update_kernel<kSigned>, dim3(total, total), dim3(256), 0, st, d, list, dtab, 1, kb,
+                         (const double *)sgn);
+    }
+  }
+}
+
+int SparseChol::schurFactorDevice(const double *dadd, int64_t ldadd, int *info) {
+  if (info) *info = 0;
+  PO_TRY(schurFactorCheck("schur_factor()", dadd ? ldadd : (int64_t)sym.ns));
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int ns = sym.ns, S = sym.schur_sn;
+  if (!F) {
+    ldF = (ns + 1) / 2 * 2;
+    const size_t count = (size_t)ldF * ns + 4;
+    if (F.alloc(count, true) != PO_OK) {
+      (void)hipGetLastError();
+      set_error("sparse Cholesky: cannot allocate the factor of the Schur complement (%lld bytes)",
+                (long long)(count * sizeof(double)));
+      return PO_ERR_ARG;
+    }
+    fbytes = (int64_t)(count * sizeof(double));
+    std::vector<int> ti = {sym.n - ns, sym.n, 0, ldF, 0, 0};
+    for (int kb = 0; kb < (ns + kCholNB - 1) / kCholNB; kb++) {
+      ti.push_back(0);
+      ti.push_back(chol_row_tiles(ns, ns, kb));
+    }
+    PO_TRY(ftab_i.upload(ti));
+    PO_TRY(ftab_l.upload(std::vector<int64_t>{0, 0}));
+    PO_TRY(d_sflag.alloc(4, false));
+  }
+  schur_factored = false;
+  hipLaunchKernelGGL(chol_schur_load_kernel, dim3((unsigned)((ns + 255) / 256), (unsigned)std::min(ns, 65535)),
+                     dim3(256), 0, st, (const double *)(L.get() + sym.panel_off[S]), sym.sn_ld[S], ns, dadd, ldadd,
+                     F.get(), ldF);
+  PO_HIP(hipMemsetAsync(d_sflag, 0, 4 * sizeof(int), st));
+  PO_HIP(hipMemsetAsync(d_sflag + 1, 0x7f, sizeof(int), st));
+  const bool ldlt = factored_kind == PO_CHOL_LDLT;
+  if (ldlt) {
+    launchSchurFactor<true>(d_sflag);
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)ns + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(chol_count_negative_kernel, dim3(blocks), dim3(256), 0, st,
+                       (const double *)(d_sign.get() + (sym.n - ns)), ns, d_sflag.get());
+  } else {
+    launchSchurFactor<false>(d_sflag);
+  }
+  PO_HIP(hipGetLastError());
+  int flag[4] = {0, 0, 0, 0};
+  PO_HIP(hipMemcpyAsync(flag, d_sflag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  PO_HIP(hipStreamSynchronize(st));
+  schur_factored = true;
+  schur_added = dadd != nullptr;
+  schur_inertia_[1] = ldlt ? flag[2] : 0;
+  schur_inertia_[2] = ldlt ? flag[3] : 0;
+  schur_inertia_[0] = (int64_t)ns - schur_inertia_[1] - schur_inertia_[2];
+  schur_have_inertia = ldlt || flag[0] == 0;
+  if (flag[0] != 0) {
+    set_error(ldlt ? "sparse Cholesky (LDLT): zero or NaN pivot of the Schur complement at permuted index %d"
+                   : "sparse Cholesky: non-positive pivot of the Schur complement at permuted index %d",
+              flag[1]);
+    if (info) *info = 1 + flag[1];
+  }
+  return PO_OK;
+}
+
+int SparseChol::schurFactorHost(const double *add, int64_t ldadd, int *info) {
+  if (!add) return schurFactorDevice(nullptr, ldadd, info);
+  if (info) *info = 0;
+  PO_TRY(schurFactorCheck("schur_factor()", ldadd));
+  PO_HIP(hipSetDevice(ctx->device));
+  const size_t count = (size_t)sym.ns * sym.ns, width = (size_t)sym.ns * sizeof(double);
+  if (addbuf.size() < count) PO_TRY(addbuf.alloc(count, false));
+  PO_HIP(hipMemcpy2DAsync(addbuf, width, add, (size_t)ldadd * sizeof(double), width, (size_t)sym.ns,
+                          hipMemcpyHostToDevice, ctx->stream));
+  return schurFactorDevice(addbuf, sym.ns, info);  // (it synchronises: the caller's array may go away)
+}
+
+int SparseChol::schurInertia(int64_t out[3]) const {
+  if (!schur_factored || !schur_have_inertia) {
+    set_error(schur_factored ? "sparse Cholesky: the last L L^T factorization of the Schur complement replaced "
+                               "non-positive pivots and does not count them (schur_factor() reported the first)"
+                             : "sparse Cholesky: schur_inertia() before schur_factor()");
+    return PO_ERR_ARG;
+  }
+  for (int i = 0; i < 3; i++) out[i] = schur_inertia_[i];
+  return PO_OK;
+}
+
+void SparseChol::schurSweep(double *Yb, int64_t ld, int nr, bool forward) {
+  hipStream_t st = ctx->stream;
+  const int ns = sym.ns;
+  const double *Fp = F;
+  const int ldf = ldF;
+  const unsigned groups = (unsigned)((nr + kCholSchurCols - 1) / kCholSchurCols);
+  if (forward) {
+    chol_schur_panels(
+        ns, sym.schur_w, true,
+        [&](int p0, int w) {
+          hipLaunchKernelGGL(chol_schur_fwd_diag_kernel, dim3(1), dim3(256), 0, st, Fp, ldf, p0, w, Yb, ld, nr);
+        },
+        [&](int p0, int w) {
+          const unsigned tiles = (unsigned)((ns - p0 - w + kCholSchurRows - 1) / kCholSchurRows);
+          hipLaunchKernelGGL(chol_schur_fwd_update_kernel, dim3(tiles, groups), dim3(64), 0, st, Fp, ldf, ns, p0, w, Yb,
+                             ld, nr);
+        });
+  } else {
+    chol_schur_panels(
+        ns, sym.schur_w, false,
+        [&](int p0, int w) {
+          hipLaunchKernelGGL(chol_schur_bwd_diag_kernel, dim3(1), dim3(256), 0, st, Fp, ldf, p0, w, Yb, ld, nr);
+        },
+        [&](int p0, int w) {
+          hipLaunchKernelGGL(chol_schur_bwd_gather_kernel, dim3((unsigned)w, groups), dim3(256), 0, st, Fp, ldf, ns, p0,
+                             w, Yb, ld, nr);
+        });
+  }
+}
+
+int SparseChol::schurSolveDevice(double *dx2, int nrhs, int64_t ldx2) {
+  if (sym.ns == 0) {
+    set_error("sparse Cholesky: schur_solve() needs a handle created with a Schur set");
+    return PO_ERR_ARG;
+  }
+  if (!schur_factored) {
+    set_error("sparse Cholesky: schur_solve() is valid after schur_factor() until the next set_values or factor()");
+    return PO_ERR_ARG;
+  }
+  if (nrhs < 0 || (nrhs > 1 && ldx2 < sym.ns)) {
+    set_error("sparse Cholesky: schur_solve with nrhs %d, ldx2 %lld (Schur set of %d)", nrhs, (long long)ldx2, sym.ns);
+    return PO_ERR_ARG;
+  }
+  if (nrhs == 0) return PO_OK;
+  PO_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int ns = sym.ns;
+  for (int r0 = 0; r0 < nrhs; r0 += kCholMaxRhs) {
+    const int nr = std::min(kCholMaxRhs, nrhs - r0);
+    double *x = dx2 + (int64_t)r0 * ldx2;
+    schurSweep(x, ldx2, nr, true);
+    if (factored_kind == PO_CHOL_LDLT) {
+      hipLaunchKernelGGL(chol_sign_kernel, dim3((unsigned)(((int64_t)ns * nr + 255) / 256)), dim3(256), 0, st, x, ldx2,
+                         (const double *)(d_sign.get() + (sym.n - ns)), ns, nr);
+    }
+    schurSweep(x, ldx2, nr, false);
+    PO_HIP(hipGetLastError());
+  }
+  return PO_OK;
+}
+
+int SparseChol::schurSolveHost(double *x2, int nrhs, int64_t ldx2) {
+  if (sym.ns == 0 || !schur_factored || nrhs <= 0 || (nrhs > 1 && ldx2 < sym.ns)) {
+    return schurSolveDevice(nullptr, nrhs, ldx2);  // (it refuses what this entry refuses)
+  }
+  PO_HIP(hipSetDevice(ctx->device));
+  const int64_t count = (int64_t)(nrhs - 1) * ldx2 + sym.ns;
+  PO_TRY(hostBuffer(count));
+  PO_HIP(hipMemcpyAsync(xbuf, x2, (size_t)count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PO_TRY(schurSolveDevice(xbuf, nrhs, ldx2));
+  PO_HIP(hipMemcpyAsync(x2, xbuf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PO_HIP(hipStreamSynchronize(ctx->stream));
+  return PO_OK;
+}
 
 // ---- retained matrix, diagonal shift, refined solve ----------------------------------------------------------------
 int SparseChol::setKeepMatrix(bool on) {
@@ -1816,6 +2209,11 @@ int SparseChol::matvecHost(const double *x, int64_t ldx, double *y, int64_t ldy_
 int SparseChol::solveRefinedDevice(double *dx, int nrhs, int64_t ldx, int max_steps, double tol, int *steps,
                                    double *eta0, double *eta) {
   PO_TRY(refuseWholeSolve("solve_refined()"));
+  if (sym.ns > 0 && schur_added) {
+    set_error("sparse Cholesky: solve_refined() after schur_factor() with an add: the retained A is not the matrix "
+              "being solved (A22 + add is); call schur_factor() without one, or solve()");
+    return PO_ERR_ARG;
+  }
   PO_TRY(needMatrix("solve_refined()"));
   if (!factored) {
     set_error("sparse Cholesky: solve_refined() before factor()");

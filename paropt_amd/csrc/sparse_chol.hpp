@@ -53,6 +53,11 @@ constexpr int kCholLongRow = 32; // a row of the retained matrix with more entri
 // slower (a lane walks its group's fronts one after the other in levels that launch their other fronts anyway), and
 // the cap was to be the best one that costs the grids nothing (HISTORY.md, profiles/r19_bench_chol_packing.jsonl).
 constexpr int kCholPackMax = 0;
+// Panel width of the dense sweeps with the factored Schur complement (a multiple of kCholNB): the default of
+// SW_CHOL_SCHUR_W, read by chol_analyse.  Chosen from {64, 128, 256} by tools/bench_sparse_schur_solve.py.
+constexpr int kCholSchurW = 128;
+constexpr int kCholSchurRows = 64;  // rows of the Schur front that one workgroup of the forward update owns
+constexpr int kCholSchurCols = 8;   // right-hand sides a workgroup of the forward update / backward gather carries
 
 struct CholSymbolic {
   int n = 0, order = 0;
@@ -101,6 +106,7 @@ struct CholSymbolic {
   // arena[schur_src[schur_ptr[d] ..]] in child order.  Forward sweep: Schur row i adds, for right-hand side r,
   // arena[schur_vsrc[q] + r * schur_vld[q]], q in schur_vptr[i] .. schur_vptr[i + 1], in child order.
   int ns = 0, schur_sn = -1;
+  int schur_w = kCholSchurW;  // panel width of the dense sweeps with the factored S (SW_CHOL_SCHUR_W)
   std::vector<int> schur;
   std::vector<int64_t> schur_ptr, schur_src, schur_dst;
   std::vector<int64_t> schur_vptr, schur_vsrc;
@@ -130,6 +136,31 @@ void chol_kernel_forms(const CholSymbolic &s, int nv, int counts[CHF_COUNT]);
 // the forms a handle with a Schur set launches on top of those: names after chol_form_name(CHF_COUNT + f)
 enum CholSchurForm { CHF_SCHUR_GATHER, CHF_SCHUR_FWD, CHF_SCHUR_COUNT };
 void chol_schur_forms(const CholSymbolic &s, int nv, int counts[CHF_SCHUR_COUNT]);
+// row tiles of a front of order m with sz columns once block column kb is through: a trsm chunk, or a row of update
+// tiles, each.  The launch tables of every blocked front are made of it, the Schur front's own (schurFactor) too.
+inline int chol_row_tiles(int sz, int m, int kb) {
+  const int r0 = sz < (kb + 1) * kCholNB ? sz : (kb + 1) * kCholNB;
+  return (m - r0 + kCholTile - 1) / kCholTile;
+}
+// The panel loop of the dense sweeps with the factored Schur complement (sparse_chol.hip, "dense sweeps"): panels of W
+// columns of the ns x ns triangle.  Forward, right-looking, ascending: diag(p0, w), then below(p0, w) where rows lie
+// under the panel.  Backward, left-looking, descending: below(p0, w) where rows lie under the panel, then diag(p0, w).
+// Every call is one launch; the count is returned, so the launcher and po_sparse_chol_schur_solve_info share the loop.
+template <class Diag, class Below>
+int chol_schur_panels(int ns, int W, bool forward, Diag diag, Below below) {
+  const int np = (ns + W - 1) / W;
+  int launches = 0;
+  for (int i = 0; i < np; i++) {
+    const int p0 = (forward ? i : np - 1 - i) * W, w = ns - p0 < W ? ns - p0 : W;
+    const bool under = p0 + w < ns;
+    if (!forward && under) below(p0, w), launches++;
+    diag(p0, w), launches++;
+    if (forward && under) below(p0, w), launches++;
+  }
+  return launches;
+}
+// launches of one forward and one backward dense sweep over one slab (the sign pass of an LDLT solve not counted)
+int chol_schur_solve_launches(const CholSymbolic &s);
 // the levels of the factorization that launch anything
 int chol_factor_levels(const CholSymbolic &s);
 // po_sparse_chol_packing / po_csr_symbolic_frontal_packing (paropt_amd.h)
@@ -183,6 +214,24 @@ class SparseChol {
   // same sums by chol_assemble_kernel over a chunk list of that front; `reps` launches on the stream, no host read.
   // The front accumulates, so the values in it are meaningless afterwards: set values again before factor().
   int schurAssemblyProbe(bool chunked, int reps);
+  // FACTORED SCHUR COMPLEMENT (opt-in; nothing below is allocated or launched before the first schurFactor*).
+  // schurFactor*: valid after factor() until the next setValues*; copies the lower triangle of S into a buffer F of
+  // its own (ns x ns, column-major, leading dimension rounded as a front's), adds the lower triangle of `add`
+  // (optional; symmetric ns x ns in the order of the set, column-major, ldadd >= ns) entry by entry and factors
+  // S~ = S + add in place with the block-column kernels of the fronts, in the kind of the factor() that produced S
+  // (LDLT: the signs go to d_sign[n - ns ..]).  *info = 0, or 1 + the permuted index n - ns + k of the first pivot
+  // replaced.  The Schur front itself is not touched: getSchur* keeps returning S, and schurFactor* may be called
+  // again with another add.  Afterwards solveDevice / solveHost work on the handle (the whole solve), and
+  // solveRefined* too when there was no add (the retained A is then the matrix solved).
+  int schurFactorDevice(const double *dadd, int64_t ldadd, int *info);
+  int schurFactorHost(const double *add, int64_t ldadd, int *info);
+  // S~ x2 = g in place on ns-vectors in the order of the set, nrhs columns at x2 + j ldx2
+  int schurSolveDevice(double *dx2, int nrhs, int64_t ldx2);
+  int schurSolveHost(double *x2, int nrhs, int64_t ldx2);
+  // {positive, negative, replaced} pivots of S~ (sum ns); the LLT rule of inertia()
+  int schurInertia(int64_t out[3]) const;
+  bool schurFactored() const { return schur_factored; }
+  int64_t schurFactorBytes() const { return fbytes; }
   // RETAINED MATRIX (opt-in).  A is the symmetric matrix whose permuted lower triangle the value scatter sums into the
   // factor (the rule of chol_scatter_table).  While keeping is on, every setValues* also sums the compact values
   // `aval` (the same sums, bit for bit); factor() leaves them alone.  On an analysis-only object only the tables.
@@ -232,6 +281,12 @@ class SparseChol {
   int halfSolveCheck(const char *who, int nrhs, int64_t ldx);
   int halfSolveHost(bool condense, double *x, int nrhs, int64_t ldx);
   void launchSchurGather(int reps);
+  void launchSchurFwd(double *P, int nr);
+  int schurFactorCheck(const char *who, int64_t ldadd);
+  template <bool kSigned>
+  void launchSchurFactor(int *flag);
+  // forward or backward dense sweep with F in place on ns rows at Yb (leading dimension ld), nr columns
+  void schurSweep(double *Yb, int64_t ld, int nr, bool forward);
   bool keep = false, have_aval = false, have_anorm = false;
   double anorm = 0.0;
   DevArray<int> d_mrowp, d_mcol, d_mvidx, d_mlong, d_sn_of;
@@ -259,6 +314,16 @@ class SparseChol {
   DevArray<int> d_schur_vld, d_probe_sn, d_probe_c0;
   DevArray<double> sbuf;
   int64_t sbuf_cap = 0;
+  // factored Schur complement (never allocated before schurFactor*): F, its one-front table for the factorization
+  // kernels (ftab_i: first[2], nb, ld, uld, list, then the row-tile counts {0, tiles} of every block column;
+  // ftab_l: panel, upd), a flag block of its own
+  bool schur_factored = false, schur_added = false, schur_have_inertia = false;
+  int64_t schur_inertia_[3] = {0, 0, 0};
+  int64_t fbytes = 0;
+  int ldF = 0;
+  DevArray<double> F, addbuf;
+  DevArray<int> ftab_i, d_sflag;
+  DevArray<int64_t> ftab_l;
 };
 
 }  // namespace po

@@ -330,6 +330,12 @@ SIGNATURES = {
     "po_sparse_chol_solve_expand": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
     "po_sparse_chol_solve_expand_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
     "po_sparse_chol_schur_assembly_probe": (C.c_int, [po_sparse_chol, C.c_int, C.c_int]),
+    "po_sparse_chol_schur_factor": (C.c_int, [po_sparse_chol, c_double_p, C.c_int64, C.POINTER(C.c_int)]),
+    "po_sparse_chol_schur_factor_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int64, C.POINTER(C.c_int)]),
+    "po_sparse_chol_schur_solve": (C.c_int, [po_sparse_chol, c_double_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_schur_solve_device": (C.c_int, [po_sparse_chol, C.c_void_p, C.c_int, C.c_int64]),
+    "po_sparse_chol_schur_inertia": (C.c_int, [po_sparse_chol, c_i64_p]),
+    "po_sparse_chol_schur_solve_info": (C.c_int, [po_sparse_chol, c_i64_p]),
     "po_sparse_chol_destroy": (C.c_int, [po_sparse_chol]),
     "po_problem_set_bounds_mode": (C.c_int, [po_problem, C.c_int]),
     "po_problem_set_linear_constraints": (C.c_int, [po_problem, C.c_int]),

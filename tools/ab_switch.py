@@ -17,7 +17,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SW_COUNT = 39  # core.hpp DbgSwitch: ids 0 .. SW_COUNT - 1 (tests/test_docs.py keeps the two equal)
+SW_COUNT = 40  # core.hpp DbgSwitch: ids 0 .. SW_COUNT - 1 (tests/test_docs.py keeps the two equal)
 
 
 def main():
